@@ -7,8 +7,13 @@ Lagrange ODE -> gradient w.r.t. (A_t, b_t)) over one BATCH of `--batch` independ
 BASELINE configuration 3 (Lorenz-96, D=40, RK4, Np=1001, seed 31415926535) and differ in their variational
 parameters x.  Inputs (x) and outputs (gradient) stay resident in HBM; F comes back to the host once per step.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, write the outputs of the last timed step if
+--dump-outputs is given (dump_outputs), print the line.  Everything else -- the per-kernel phase events and rooflines, the anchor
+check of problem 0, the single-problem latency, the CPU baseline and the secondary blocks below -- runs only with --full (the
+--no-* options then switch parts of it off).
 
 N > 1: one process per GPU, independent problems per rank (the path shards over problems; no data-path
 collective), barrier + device sync on both sides of the timed region, MAX over ranks, weak scaling.  Started WITHOUT a
@@ -16,9 +21,9 @@ launcher (`python bench.py --gpus N`, WORLD_SIZE unset) the script starts its N 
 process, before this process has made any GPU call -- and exits with the child's code; a WORLD_SIZE that disagrees with --gpus is
 an error, never a silent one-GPU run.
 
-Secondary block `config4` (rank 0; --no-config4 skips it): BASELINE configs[3]'s matrix size -- ONE Lorenz-96 problem, D = 1024, RK4, the
+Secondary block `config4` (rank 0, --full; --no-config4 skips it): BASELINE configs[3]'s matrix size -- ONE Lorenz-96 problem, D = 1024, RK4, the
 resident fused sweep on a 33-point grid, checked against the committed oracle anchors of that size.
-Secondary block `config5` (every N; --no-config5 skips it): BASELINE configs[4]'s matrix size -- ONE Lorenz-96 problem, D = 4096,
+Secondary block `config5` (every N, --full; --no-config5 skips it): BASELINE configs[4]'s matrix size -- ONE Lorenz-96 problem, D = 4096,
 RK4, short grid -- through vgpa_shard_sweep_sharded: S_t / Psi_t row-sharded over the N ranks with RCCL collectives per RK stage,
 energy / gradient phases time-parallel, x and the gradient memory-sharded.  The problem is fixed, so the per-N values of
 `config5.s_per_sweep` give STRONG scaling; the headline `value` stays the D = 40 metric.  At N > 1 the block runs in CHILD processes
@@ -40,14 +45,22 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 FP64_PEAK_TFLOPS = 78.6   # 256 CU x 4 SIMD x 16 FMA/clk x 2 x 2.4 GHz; measured 64 clk per v_mfma_f64_16x16x4 (profiles/)
-HBM_PEAK_GBS = 8000.0     # /opt/skills/guides/MI355X_MICROARCH.md: 8.0 TB/s spec (6.3 TB/s achievable)
+HBM_PEAK_GBS = 8000.0     # MI355X: 8.0 TB/s spec (6.3 TB/s achievable)
+DUMP_ENTRIES = 1 << 18    # --dump-outputs: gradient entries sampled per sampled problem
+DUMP_PROBLEMS = 16        # --dump-outputs: problems whose gradient is sampled
+DUMP_SEED = 20240917      # --dump-outputs: fixed seed of the sample
 
 
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline: per-kernel phase "
+                    "events and rooflines, the anchor check, the single-problem latency, the CPU baseline, the config2 / config4 / "
+                    "config5 blocks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write what the last one computed "
+                    "(rank 0: F of every problem, the gradient of problem 0, a seeded sample of the other gradients) as DIR/<name>.npy")
     ap.add_argument("--batch", type=int, default=512, help="independent problems per GPU per step")
     ap.add_argument("--np", dest="n_pts", type=int, default=1001)
     ap.add_argument("--dim", type=int, default=40)
@@ -87,6 +100,47 @@ def launch_ranks(args):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     print(f"[bench] no launcher (WORLD_SIZE unset): starting {args.gpus} ranks: {' '.join(cmd)}", file=sys.stderr, flush=True)
     return subprocess.run(cmd, env=env).returncode
+
+
+def batch_inputs(x0, lo, B, world):
+    """x of this rank's B problems: global problem 0 is exactly x0 + 0.05 N(0,1) drawn from rng(0), problem gi from rng(1000 + gi).
+    Every row has a generator of its own, so the rows are filled by a few threads (numpy releases the GIL) with the same bits as one
+    thread would write: the 6.7 GB of the default batch are host time before the first step."""
+    from concurrent.futures import ThreadPoolExecutor
+    xb = np.empty((B, x0.size))
+
+    def row(i):
+        gi = lo + i
+        r = np.random.default_rng(0) if gi == 0 else np.random.default_rng(1000 + gi)
+        r.standard_normal(out=xb[i])
+        xb[i] *= 0.05
+        xb[i] += x0
+
+    threads = max(1, min(16, len(os.sched_getaffinity(0))) // world)
+    with ThreadPoolExecutor(threads) as pool:
+        list(pool.map(row, range(B)))
+    return xb
+
+
+def dump_outputs(out_dir, f_last, g_dev, B, len_x):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as float64 .npy files (about 30 MB at the
+    default size, never more than 64 MB): F.npy, the free energy of each of this rank's B problems; grad0.npy, the whole gradient of
+    problem 0 (or its entries at grad_index when it holds more than 2^21); grad_index.npy, a fixed, seeded, sorted sample of
+    gradient entries; grad_problems.npy, a fixed, seeded sample of problems; grad_sample.npy, their gradients at grad_index."""
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    idx = np.sort(rng.choice(len_x, size=min(len_x, DUMP_ENTRIES), replace=False))
+    probs = np.sort(rng.choice(B, size=min(B, DUMP_PROBLEMS), replace=False))
+    g0 = g_dev.download_at(0, len_x)
+    arrays = {"F": np.atleast_1d(np.asarray(f_last, dtype=np.float64)),
+              "grad0": g0 if len_x <= (1 << 21) else g0[idx],
+              "grad_index": idx.astype(np.float64), "grad_problems": probs.astype(np.float64),
+              "grad_sample": np.stack([g_dev.download_at(int(p) * len_x, len_x)[idx] for p in probs])}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, total
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    print(f"[bench] wrote {len(arrays)} arrays ({total / 2**20:.1f} MiB) to {out_dir}", file=sys.stderr, flush=True)
 
 
 def _cpu_sweep(job):
@@ -480,12 +534,14 @@ def main():
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: the two must agree (n_gpus in the JSON line is the number of "
                          f"ranks that ran)")
+    if args.dump_outputs and args.steps < 1:
+        raise SystemExit("--dump-outputs writes what the last timed step computed: it needs --steps >= 1")
     if args.config5_child:
         return config5_child_main(args)
     if os.environ.get("VGPA_BENCH_LAUNCH_ONLY") == "1":       # CPU test of the launcher: rendezvous, report, leave (no GPU work)
         import torch.distributed as dist
         from vgpa_amd import parallel as par
-        c5 = config5_children(args, rank) if (world > 1 and not args.no_config5) else None
+        c5 = config5_children(args, rank) if (args.full and world > 1 and not args.no_config5) else None
         par.init_from_env("gloo")
         par.barrier()
         seen = par.max_over_ranks(float(rank)) + 1.0
@@ -497,7 +553,7 @@ def main():
 
     # N > 1: the secondary D = 4096 block first, in child processes (nothing here has touched the GPU yet)
     c5_early = None
-    c5_in_children = world > 1 and not args.no_config5 and not args.generic
+    c5_in_children = args.full and world > 1 and not args.no_config5 and not args.generic
     if c5_in_children:
         c5_early = config5_children(args, rank)
 
@@ -508,9 +564,9 @@ def main():
     tf = (n_pts - 1) * dt
     p = build_problem("L96", args.method, tf, dt, d)          # seed 31415926535: the reference's config-3 inputs
     x0 = p["vgp"].initialization()
-    x_first = x0 + 0.05 * np.random.default_rng(0).standard_normal(x0.size)     # global problem 0
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
+        x_first = x0 + 0.05 * np.random.default_rng(0).standard_normal(x0.size)     # global problem 0
         cpu = cpu_baseline(p, x_first, args.method, d, n_pts, dt)
         print(f"[bench] cpu baseline: many cores {cpu['many_cores']}", file=sys.stderr, flush=True)
 
@@ -548,11 +604,7 @@ def main():
                      device=local_rank, flags=flags)
     lo, hi = par.shard_range(B * world, rank, world)        # this rank's slice of the global problem list
     assert hi - lo == B
-    xb = np.empty((B, len_x))
-    for i in range(B):                                       # global problem 0 is exactly x0 + 0.05 N(0,1), rng(0)
-        gi = lo + i
-        r = np.random.default_rng(0) if gi == 0 else np.random.default_rng(1000 + gi)
-        xb[i] = x0 + 0.05 * r.standard_normal(len_x)
+    xb = batch_inputs(x0, lo, B, world)                      # global problem 0 is exactly x0 + 0.05 N(0,1), rng(0)
     x_dev, g_dev = ctx.alloc(B * len_x), ctx.alloc(B * len_x)
     x_dev.upload(xb)
 
@@ -560,7 +612,8 @@ def main():
         ctx.sweep_enqueue(x_dev, g_dev)
         ctx.fetch_f()
     barrier()
-    ctx.profile_begin()
+    if args.full:                                            # per-kernel times: HIP events around the phases of every step
+        ctx.profile_begin()
     t0 = time.perf_counter()
     f_last = None
     for _ in range(args.steps):
@@ -568,14 +621,16 @@ def main():
         f_last = ctx.fetch_f()                               # F of every problem returns to the host each step
     barrier()
     elapsed = time.perf_counter() - t0
-    prof = ctx.profile_end()
+    prof = ctx.profile_end() if args.full else None
 
     elapsed = par.max_over_ranks(elapsed, device="cpu" if rehearse else "cuda")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, f_last, g_dev, B, len_x)
 
     # ---- correctness guard inside the bench: problem 0 of rank 0 must reproduce the reference's anchors -- the free energy AND
     # the norm of the gradient the timed launches left in g_dev (per-problem dot products on the device)
     check = check_g = None
-    if rank == 0 and n_pts == 1001 and d == 40 and args.method.upper() == "RK4":
+    if args.full and rank == 0 and n_pts == 1001 and d == 40 and args.method.upper() == "RK4":
         anchors = json.load(open(os.path.join(ROOT, "tests", "golden", "anchors.json")))
         f_ref, g_ref = anchors["l96d40_rk4_full_p"]["F"], anchors["l96d40_rk4_full_p"]["grad_norm"]
         check = abs(np.atleast_1d(f_last)[0] - f_ref) / abs(f_ref)
@@ -586,7 +641,7 @@ def main():
 
     # ---- single-problem latency (what one SCG evaluation costs), rank 0, outside the timed region
     single = None
-    if rank == 0 and not args.no_single_problem:
+    if args.full and rank == 0 and not args.no_single_problem:
         c1 = va.Context("L96", args.method, d, n_pts, dt, sigma=p["model"].sigma, theta=[8.0], m0=p["m0"], s0=p["s0"],
                         obs_t=p["obs_t"], obs_y=p["obs_y"], obs_noise=p["obs_noise"], e0=e0, batch=1,
                         device=local_rank, flags=flags)
@@ -608,13 +663,13 @@ def main():
 
     # ---- secondary block: BASELINE configs[1] (Lorenz-63), the HBM-bound small-D path; rank 0 only, outside the timed region
     c2 = None
-    if rank == 0 and not args.no_config2 and not args.generic:
+    if args.full and rank == 0 and not args.no_config2 and not args.generic:
         ctx.close()
         del x_dev, g_dev
         ctx = None
         c2 = config2_block(args, local_rank)
     c4 = None
-    if rank == 0 and not args.no_config4 and not args.generic:
+    if args.full and rank == 0 and not args.no_config4 and not args.generic:
         if ctx is not None:
             ctx.close()
             del x_dev, g_dev
@@ -624,7 +679,7 @@ def main():
     # ---- secondary block: BASELINE configs[4]'s matrix size through the row-sharded driver (every rank takes part)
     # (one rank: in this process, behind the headline measurement; N > 1: already measured, in child processes -- see above)
     c5 = c5_early
-    if not args.no_config5 and not args.generic and not c5_in_children:
+    if args.full and not args.no_config5 and not args.generic and not c5_in_children:
         if ctx is not None:
             ctx.close()
             del x_dev, g_dev
@@ -639,6 +694,21 @@ def main():
     total_sweeps = B * args.steps * world
     value = total_sweeps / elapsed
     steps = max(args.steps, 1)
+    head = {
+        "metric": "fwd+bwd sweeps/sec (free-energy+grad eval), Lorenz96 D=40 N=1000",
+        "value": value, "unit": "sweeps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic (seeded Lorenz-96 path + observations, reference generator order)",
+        "config": {"workload": f"Lorenz96 D={d}, {args.method.upper()}, Np={n_pts} (BASELINE configs[2])",
+                   "batch_per_gpu": B, "sharding": "independent problems per GPU, no collective",
+                   "kernels": "generic" if args.generic else "mfma"},
+    }
+    if not args.full:                                # a plain run: the headline and nothing else
+        print(json.dumps(head))
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     # per-kernel rooflines; the one reported as `roofline` is the kernel with the longest launch (the dominant one)
     fwd_s, bwd_s = prof["fwd_ms"] / steps * 1e-3, prof["bwd_ms"] / steps * 1e-3
     en_s, gr_s = prof["energy_ms"] / steps * 1e-3, prof["grad_ms"] / steps * 1e-3
@@ -728,13 +798,7 @@ def main():
     gbs = alg_bytes / kernels[step_dom]["seconds"] / 1e9
     sweep_bytes = 8.0 * n_pts * (5 * d * d + 6 * d)         # SURVEY.md s.8d algorithmic bytes of one fused sweep
     out = {
-        "metric": "fwd+bwd sweeps/sec (free-energy+grad eval), Lorenz96 D=40 N=1000",
-        "value": value, "unit": "sweeps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f64", "data": "synthetic (seeded Lorenz-96 path + observations, reference generator order)",
-        "config": {"workload": f"Lorenz96 D={d}, {args.method.upper()}, Np={n_pts} (BASELINE configs[2])",
-                   "batch_per_gpu": B, "sharding": "independent problems per GPU, no collective",
-                   "kernels": "generic" if args.generic else "mfma"},
+        **head,
         # `value` is BATCH throughput (B independent sweeps per launch); ONE sweep -- what an SCG iteration of the reference's
         # use case waits for -- is latency-bound on one CU:
         "single_problem_sweeps_per_s": None if single is None else single["sweeps_per_s"],

@@ -121,7 +121,7 @@ def test_bench_starts_its_own_ranks_when_no_launcher_is_around():
     (torch.distributed.run as a CHILD of a process that has made no GPU call), they rendezvous, and `n_gpus` is N -- never a silent
     one-GPU run.  VGPA_BENCH_LAUNCH_ONLY=1 stops each rank after the rendezvous: no GPU in this container."""
     import json
-    r = _bench(["--gpus", "2", "--steps", "1", "--warmup", "0"], {"VGPA_BENCH_LAUNCH_ONLY": "1"})
+    r = _bench(["--gpus", "2", "--steps", "1", "--warmup", "0", "--full"], {"VGPA_BENCH_LAUNCH_ONLY": "1"})
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
     out = json.loads(line)
@@ -137,12 +137,12 @@ def test_a_failing_config5_child_cannot_take_the_headline_line_with_it():
     at N > 1 it runs in child processes that the ranks start before they touch the GPU.  Children that hang are killed at
     --config5-timeout and the block reports it; the ranks go on and print their line, exit code 0."""
     import json
-    r = _bench(["--gpus", "2", "--steps", "1", "--warmup", "0", "--config5-timeout", "5"],
+    r = _bench(["--gpus", "2", "--steps", "1", "--warmup", "0", "--full", "--config5-timeout", "5"],
                {"VGPA_BENCH_LAUNCH_ONLY": "1", "VGPA_BENCH_C5_TEST_HANG": "1"})
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert out["ranks_seen"] == 2 and "did not finish" in out["config5"]["error"]
-    r = _bench(["--gpus", "2", "--steps", "1", "--warmup", "0", "--no-config5"], {"VGPA_BENCH_LAUNCH_ONLY": "1"})
+    r = _bench(["--gpus", "2", "--steps", "1", "--warmup", "0", "--full", "--no-config5"], {"VGPA_BENCH_LAUNCH_ONLY": "1"})
     assert r.returncode == 0 and json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])["config5"] is None
 
 
