@@ -428,8 +428,7 @@ def test_diagnostic_phase_repeat_leaves_the_results_alone():
 def test_stepper_variants_of_the_fragment_cover_agree():
     """33 <= D <= 40 on the fragment-cover steppers: with four or eight helper waves beside the four product waves of a workgroup (the
     default up to one problem per CU: the chores of a stage off the product waves' issue slots) and without them the same operations run in the same
-    order -- F and the gradient must not differ in any bit.  (The outer-product cover and the eight-product-wave split, measured and
-    rejected, are no longer part of the product build: -DVGPA_EXPERIMENTS.)  The switch is read once per process: child processes;
+    order -- F and the gradient must not differ in any bit.  The switch is read once per process: child processes;
     RK4 and Heun, an unpadded and a padded dimension, one problem and a small batch."""
     import json
     import os
@@ -451,8 +450,7 @@ def test_stepper_variants_of_the_fragment_cover_agree():
     outs = {}
     for name, env_set in (("helpers", {"VGPA_SYM_HELPERS": "1"}), ("two", {"VGPA_SYM_HELPERS": "2"}), ("plain", {"VGPA_SYM_HELPERS": "0"})):
         env = dict(os.environ)
-        for k in ("VGPA_SYM_HELPERS", "VGPA_SYM_COVER", "VGPA_SYM_WAVES"):
-            env.pop(k, None)
+        env.pop("VGPA_SYM_HELPERS", None)
         env.update(env_set)
         r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, r.stderr[-2000:]

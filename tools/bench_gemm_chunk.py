@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time of one rank's stage product of BASELINE configs[4] (row block 512 x 4096, K = 4096) as the pipelined schedule launches it:
 `chunks` K-chunk launches (vgpa_ld_gemm_chunk, segmented k-tiles), against ONE plain launch (vgpa_ld_gemm).  Prints one JSON line.
-    python tools/bench_gemm_chunk.py [M] [D] [world] [chunks]        (VGPA_GEMM_PF=0: the two-register-set loop)"""
+    python tools/bench_gemm_chunk.py [M] [D] [world] [chunks]"""
 import json
 import os
 import sys
@@ -20,7 +20,7 @@ def main():
     be = HipStageBackend()
     lib, st = be._lib, be._stream()
     dev = torch.device("cuda", 0)
-    out = {"M": m, "D": d, "world": world, "chunks": chunks, "gemm_pf": os.environ.get("VGPA_GEMM_PF", "default")}
+    out = {"M": m, "D": d, "world": world, "chunks": chunks}
     for transa in (0, 1):
         a_d = torch.randn((d, m) if transa else (m, d), dtype=torch.float64, device=dev)
         x_d = torch.randn((d, d), dtype=torch.float64, device=dev)

@@ -28,7 +28,7 @@ CFLAGS = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno
 # do not (large_d_stage.hip)
 FILE_CFLAGS = {"large_d_stage.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "large_d_energy.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 
-# experiments: extra compiler flags (e.g. -DVGPA_SYM_SPLIT_C_FWD=1) without editing the sources; never set by the package itself
+# experiments: extra compiler flags (e.g. -Rpass-analysis=kernel-resource-usage) without editing the sources; never set by the package itself
 CFLAGS += os.environ.get("VGPA_EXTRA_CFLAGS", "").split()
 
 

@@ -385,10 +385,7 @@ __global__ void __launch_bounds__(NT) k_grad_mfma(GradArgs a) {
 }
 
 
-#ifndef VGPA_GRAD_TPW
-#define VGPA_GRAD_TPW 4
-#endif
-constexpr int kGradTPW = VGPA_GRAD_TPW;      // consecutive grid points per workgroup of k_grad_mfma: the loads of point t+1 are in flight under the product of t
+constexpr int kGradTPW = 4;      // consecutive grid points per workgroup of k_grad_mfma: the loads of point t+1 are in flight under the product of t
 // The same assembly for GradArgs::psi_is_q (the batched fused sweeps of 33 <= D <= 40: `psi` holds Q''_t, A_t and a dense <df/dx> are not
 // streamed), software-pipelined over kGradTPW consecutive grid points of one problem.
 template <int NB>
@@ -558,12 +555,8 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(3, 3)))
     // Straight from the accumulators a 320-byte row is written as 128 + 128 + 64 bytes by up to three store instructions of two
     // waves; odd rows start in the middle of a line.  The partial lines do not always meet in L2 before they are evicted: the
     // kernel's WRITE_SIZE was 17 % above the bytes of its two outputs (profiles/r04r_pmc_fetch_write_B512.csv).
-#ifndef VGPA_GRAD_STAGE_OUT
-#define VGPA_GRAD_STAGE_OUT 1
-#endif
-    double* const outb = VGPA_GRAD_STAGE_OUT ? QT : gA;
-    const int ldo = VGPA_GRAD_STAGE_OUT ? LD : D;      // (in LDS with the operand's leading dimension: its zero padding, D < P, stays untouched)
-    if (VGPA_GRAD_STAGE_OUT) __syncthreads();      // every wave has read its fragments of Q^T
+    // (In LDS with the operand's leading dimension: its zero padding, D < P, stays untouched.)
+    __syncthreads();                     // every wave has read its fragments of Q^T
 #pragma unroll
     for (int ii = 0; ii < RW; ii++) {
       const int I = wave + 4 * ii;
@@ -571,7 +564,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(3, 3)))
 #pragma unroll
       for (int q = 0; q < NQ; q++) {
         const int col = 16 * q + 4 * b + c4;
-        if (I < NB && row < D && col < D) outb[row * ldo + col] = a.dt * (acc[q * RW + ii] - uv[row] * mv[col]);
+        if (I < NB && row < D && col < D) QT[row * LD + col] = a.dt * (acc[q * RW + ii] - uv[row] * mv[col]);
       }
     }
 #pragma unroll
@@ -579,17 +572,15 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(3, 3)))
       const int v = wave + 4 * vv;
       const int Ib = v * G + b / rem;
       const int row = 4 * Ib + r4, col = 4 * (4 * NQ + b % rem) + c4;
-      if (v < NLEFT && b < G * REM && Ib < NB && row < D && col < D) outb[row * ldo + col] = a.dt * (accl[vv] - uv[row] * mv[col]);
+      if (v < NLEFT && b < G * REM && Ib < NB && row < D && col < D) QT[row * LD + col] = a.dt * (accl[vv] - uv[row] * mv[col]);
     }
-    if (VGPA_GRAD_STAGE_OUT) {
-      __syncthreads();
+    __syncthreads();
 #pragma unroll
-      for (int q = 0; q < EPT; q++) {
-        const int e = tid + q * NT;
-        if (e < DD) {
-          const int i = (int)(((unsigned)e * magic) >> 20);
-          gA[e] = QT[i * LD + (e - i * D)];
-        }
+    for (int q = 0; q < EPT; q++) {
+      const int e = tid + q * NT;
+      if (e < DD) {
+        const int i = (int)(((unsigned)e * magic) >> 20);
+        gA[e] = QT[i * LD + (e - i * D)];
       }
     }
     if (!QMODE && t + 1 < t_end) request(t + 1);

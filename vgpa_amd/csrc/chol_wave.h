@@ -1,5 +1,5 @@
 // One-wave Cholesky building blocks shared by the Lorenz-96 energy kernels of D <= 64 (energy.hip) and the 64 x 64 diagonal-block
-// kernel of the blocked factorisation above D = 64 (large_d_energy.hip::k_diag64): the reciprocal square root without the library's
+// kernel of the blocked factorisation above D = 64 (large_d_energy.hip::k_diag64m): the reciprocal square root without the library's
 // class test, and the four pivots of a four-column panel with lane = row (src/numerics/utilities.py:239-310 chol_inv /
 // numpy.linalg.cholesky on the lower triangle).
 #pragma once

@@ -13,9 +13,6 @@
 #include "energy_small.h"
 #include "chol_wave.h"
 
-#define VGPA_L96_NOK 0
-#define VGPA_L96_NOPANEL 0
-
 namespace vgpa {
 namespace {
 
@@ -543,40 +540,19 @@ constexpr TriRowTab make_tri_row_tab() {
 }
 __device__ __constant__ TriRowTab kTriRow = make_tri_row_tab();
 
-#ifdef VGPA_ENERGY_TRACE
-// diagnostic build only: cycles per phase of k_energy_l96_r summed over all waves (tools/trace_energy.py)
-__device__ unsigned long long g_energy_trace[16];
-#define VGPA_TRACE_STAMP(k) do { const unsigned long long tn_ = __builtin_amdgcn_s_memtime(); if (l == 0) atomicAdd(&g_energy_trace[k], tn_ - tprev_); tprev_ = tn_; } while (0)
-#else
-#define VGPA_TRACE_STAMP(k) do { } while (0)
-#endif
-
-// TPW > 1 (packed S_t only): the wave takes TPW consecutive grid points of one problem and requests the next point's S_t (13
-// registers of packed triangle at D = 40) and vector entries before the triangular inverse of the current one -- the phases behind
-// that point need few registers, and the wave's entry and the memory round trip of its operands, 23 % of a one-point wave's time
-// (profiles/r03_energy_kernel_phase_trace.json), run under them.
-// (EXPERIMENT, off: -DVGPA_ENERGY_TPW=4 builds the persistent variant.  Measured 11.2 ms against 5.5 ms per 512-problem launch: with a
-//  loop around the body the register allocator spills ~90 values (352 bytes of scratch per lane at the 168-register budget of three
-//  waves per SIMD) wherever the request for the next point is placed -- EXPERIMENTS.md s.10.)
-#ifndef VGPA_ENERGY_TPW
-#define VGPA_ENERGY_TPW 1
-#endif
-constexpr int kEnergyTPW = VGPA_ENERGY_TPW;
-template <int NB, int TPW = 1>
+// (One grid point per wave.  Persistent waves over several grid points, with the next point's operands requested under the current
+//  one's phases, measured 11.2 ms against 5.5 ms per 512-problem launch: with a loop around the body the register allocator spills
+//  ~90 values at the 168-register budget of three waves per SIMD -- EXPERIMENTS.md s.10.)
+template <int NB>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NB <= 10 ? 3 : 2, NB <= 10 ? 3 : 2))) k_energy_l96_r(EnergyArgs a) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int D = a.D, M = 2 * D + 1;
   constexpr int Dp = 4 * NB, LD = Dp + 1, NUU = (NB + 3) / 4;
-  int l = threadIdx.x;
-#ifdef VGPA_ENERGY_TRACE
-  unsigned long long tprev_ = __builtin_amdgcn_s_memtime();
-#endif
+  const int l = threadIdx.x;
   const long long wid = blockIdx.x;
-  const int per = (a.Np + TPW - 1) / TPW;            // waves per problem
-  const int prob = (int)(wid / per);
-  int t = (int)(wid - (long long)prob * per) * TPW;
-  const int t_last = t + TPW < a.Np ? t + TPW : a.Np;
-  size_t o = (size_t)prob * a.Np + t;
+  const int prob = (int)(wid / a.Np);
+  const int t = (int)(wid - (long long)prob * a.Np);
+  const size_t o = (size_t)prob * a.Np + t;
   L96Lds S;
   // (Sigma^-1's diagonal is kept in registers, not in LDS; rows 0 and 1 of the parked G share the space of dl and qq,
   //  which are written after the boundary pass: 17.9 KB per grid point at D = 40, nine waves per CU)
@@ -591,26 +567,21 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NB <= 1
   auto cg2 = [&](int j) -> double* { return S.Lm + j * LD + Dp; };
   auto cps = [&](int minus, int j) -> double* { return S.Lm + (4 + 2 * minus + (j >= 20 ? 1 : 0)) * LD + (j >= 20 ? j : 20 + j); };
   auto cxd = [&](int I, int r, int c) -> double* { return S.Lm + ((I < 6 ? 0 : 4) + r) * LD + 4 * (I < 6 ? I + 4 : I - 1) + c; };
-  const double* At = a.A + (size_t)prob * a.strideA + (size_t)t * D * D;       // (advanced per grid point)
+  const double* At = a.A + (size_t)prob * a.strideA + (size_t)t * D * D;
   const bool spk = a.s_packed != 0;                // S_t as its packed lower triangle (OdeArgs::s_packed): all the factorisation reads
   const int PK = tri_off(D);
   const double* St = a.S + o * (spk ? PK : D * D);
-  static_assert(TPW >= 1, "grid points per wave");
   const double theta = a.theta[0];
   const double kappa = 1.05 * D, c = D + kappa;
-  bool act = l < D;
-  bool pad = l < Dp;
-  int li = pad ? l : Dp - 1;
-  int r4 = l >> 4, c4 = l & 3, b = (l >> 2) & 3;
+  const bool act = l < D;
+  const bool pad = l < Dp;
+  const int li = pad ? l : Dp - 1;
+  const int r4 = l >> 4, c4 = l & 3, b = (l >> 2) & 3;
 
   // ---- A-operand fragments of A, straight from HBM: unit u = block-rows 4u + b, fragment [i = c4][k = r4]
-  // (the last unit's fragments are requested after the Cholesky instead: with them in flight the factorisation would not fit the
-  //  168 registers of three waves per SIMD, and a spilled fragment is a load that is WAITED for at entry; they arrive during the
-  //  first pass of phase 2)
-#ifndef VGPA_ENERGY_EARLY_UNITS
-#define VGPA_ENERGY_EARLY_UNITS 0
-#endif
-  constexpr int NUE = VGPA_ENERGY_EARLY_UNITS < NUU ? VGPA_ENERGY_EARLY_UNITS : NUU;
+  // (requested after the Cholesky: with them in flight the factorisation would not fit the 168 registers of three waves per SIMD,
+  //  and a spilled fragment is a load that is WAITED for at entry; they arrive during the second pass of phase 2)
+  constexpr int NUE = 0;                                    // units whose fragments are requested before the Cholesky
   double af[NUU][NB];
   const int klim = (D - r4 + 3) >> 2;                       // 4K + r4 < D  <=>  K < klim: nothing per K stays alive until the late loads
   auto load_af = [&](int u) {
@@ -620,8 +591,6 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NB <= 1
 #pragma unroll
     for (int K = 0; K < NB; K++) af[u][K] = (K < kl) ? ap[4 * K] : 0.0;
   };
-#pragma unroll
-  for (int u = 0; u < NUE; u++) load_af(u);
 
   // the two entries of S_t that <f>_i needs at the very end (E96_drift): requested now -- at the end they would cost a
   // full memory round trip per wave
@@ -641,7 +610,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NB <= 1
   // loads); `request` asks for everything of grid point tn the wave reads from HBM except A
   constexpr int EPK = (Dp * (Dp + 1) / 2 + 63) / 64;
   double sv[EPK];
-  int rr[TPW == 1 ? EPK : 1];              // rows of this lane's flat indices: looked up (kTriRow) beside the loads they belong to
+  int rr[EPK];                             // rows of this lane's flat indices: looked up (kTriRow) beside the loads they belong to
   auto request = [&](int tn) {
     const size_t on = (size_t)prob * a.Np + tn;
     const double* Sn = a.S + on * PK;
@@ -649,7 +618,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NB <= 1
     for (int q = 0; q < EPK; q++) {
       const int e = l + 64 * q;
       sv[q] = e < PK ? Sn[e] : 0.0;
-      if (TPW == 1) rr[q] = kTriRow.r[e < PK ? e : 0];
+      rr[q] = kTriRow.r[e < PK ? e : 0];
     }
     if (act) {
       nsxa = Sn[tri_idx(f_ip1, f_im1)];
@@ -660,15 +629,6 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NB <= 1
   };
   if (spk) request(t);
 
-  for (;;) {      // the grid points of this wave (one, unless TPW > 1)
-  if (TPW > 1) {
-    // The lane index is made opaque per grid point: everything a lane addresses derives from it, and with a loop around the body
-    // the compiler otherwise hoists every per-lane LDS / HBM offset of every phase out of the loop -- ~300 registers of "invariants"
-    // that a one-grid-point wave computes where it needs them (1.2 KB of scratch per lane before this line).
-    asm volatile("" : "+v"(l));
-    act = l < D; pad = l < Dp; li = pad ? l : Dp - 1;
-    r4 = l >> 4; c4 = l & 3; b = (l >> 2) & 3;
-  }
   // ---- stage c*S into LDS (coalesced); padding: identity.  Every HBM load of the wave (the vectors too) is requested
   //      before the first one is consumed: a lone wave pays each dependent round trip in full.  S_t's requests go first.
   if (spk) {
@@ -683,7 +643,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NB <= 1
     for (int q = 0; q < EPK; q++) {
       const int e = l + 64 * q;
       if (e < PK) {
-        const int r = (TPW > 1) ? tri_row(e) : rr[TPW == 1 ? q : 0];      // (persistent waves: arithmetic instead of 13 more registers)
+        const int r = rr[q];
         S.Lm[r * LD + (e - tri_off(r))] = c * sv[q];
       }
     }
@@ -736,7 +696,6 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NB <= 1
   if (pad) { S.mv[l] = v_m; S.bv[l] = v_b; S.am[l] = 0.0; }
   wave_sync();
 
-  VGPA_TRACE_STAMP(0);
   // ---- 1. Cholesky (identical to k_energy_l96)
   bool bad = false;
   double myrd = 1.0;                       // 1 / L[l][l] (padding rows: 1), stored once after the loop
@@ -773,7 +732,6 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NB <= 1
 #pragma unroll
   for (int u = NUE; u < NUU; u++) load_af(u);
 
-  VGPA_TRACE_STAMP(1);
   // ---- 2. A.m and G = A.L on the matrix cores, results stay in the accumulators (row 16u + 4b + r4, column 4J + c4)
   double amr[NUU], gacc[NUU][NB];
 #pragma unroll
@@ -783,7 +741,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NB <= 1
     for (int J = 0; J < NB; J++) gacc[u][J] = 0.0;
   }
 #pragma unroll
-  for (int pass = 0; pass < (NUE < NUU ? 2 : 1); pass++) {    // units 0 .. NUE-1, then the late unit (its own reads of L)
+  for (int pass = 0; pass < (NUE < NUU ? 2 : 1); pass++) {    // units 0 .. NUE-1, then the late units (their own reads of L)
     const int u0 = pass == 0 ? 0 : NUE, u1 = pass == 0 ? NUE : NUU;
 #pragma unroll
     for (int K = 0; K < NB; K++) {
@@ -805,7 +763,6 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NB <= 1
     if (c4 == 0 && i < D) { S.am[i] = amr[u]; if (a.Am) a.Am[o * D + i] = amr[u]; }
   }
 
-  VGPA_TRACE_STAMP(2);
   // ---- 3. residuals of the sigma points m +- L[:, j] in accumulator layout, rows 2 .. D-2
   // park rows 0, 1, D-1 of G for the boundary pass first (only the units that can hold them: compile-time test), so
   // that the residual loop below is ONE basic block (with branches in between, the compiler sinks all the arithmetic
@@ -900,7 +857,6 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NB <= 1
     }
   }
   wave_sync();
-  VGPA_TRACE_STAMP(3);
 
   double vplus = 0.0, vminus = 0.0, v0 = 0.0;
   {
@@ -1001,11 +957,6 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NB <= 1
   }
   wave_sync();
 
-  VGPA_TRACE_STAMP(4);
-#ifndef VGPA_ENERGY_PF
-#define VGPA_ENERGY_PF 4
-#endif
-  if (VGPA_ENERGY_PF == 4 && TPW > 1 && spk && t + 1 < t_last) request(t + 1);      // the next grid point's operands travel under phases 4 and 5
   // ---- 4. X = L^-1 IN PLACE by blocked forward substitution on the matrix cores (see k_energy_l96): block-row I of X
   //         overwrites block-row I of L, which only step I reads; LDS operations of one wave execute in order.
   const double* l4_a = S.Lm + c4 * LD + r4;
@@ -1042,8 +993,6 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NB <= 1
     wave_sync();
   }
 
-  VGPA_TRACE_STAMP(5);
-  if (VGPA_ENERGY_PF == 5 && TPW > 1 && spk && t + 1 < t_last) request(t + 1);
   // ---- 5. dE/dm = (c/2) X^T delta ; dE/dS = (c/2) X^T diag(q) X
   {
     double s = 0.0;
@@ -1091,7 +1040,6 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NB <= 1
     }
   }
 
-  VGPA_TRACE_STAMP(6);
   // ---- <f> and optionally dense <df/dx>
   if (act) {
     const int i = l, ip1 = wrap(i + 1, D), im1 = wrap(i - 1, D), im2 = wrap(i - 2, D);
@@ -1110,16 +1058,6 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NB <= 1
       if (j == km1) v = S.mv[kp1] - S.mv[km2];
       ed[e] = v;
     }
-  }
-  VGPA_TRACE_STAMP(7);
-  if (TPW == 1) break;
-  if (VGPA_ENERGY_PF == 7 && spk && t + 1 < t_last) request(t + 1);
-  t++;
-  if (t >= t_last) break;
-  o++;
-  At += (size_t)D * D;
-  St += spk ? PK : D * D;
-  wave_sync();                                   // every lane is done with this grid point's LDS before the next one is staged
   }
 }
 
@@ -1170,26 +1108,11 @@ hipError_t launch_energy(const EnergyArgs& a, hipStream_t st) {
     size_t lds = (one_matrix ? l96r_lds_doubles(a.D) : l96_lds_doubles(a.D)) * sizeof(double);
     const long long nwaves = (long long)a.Np * a.batch;
     if (nwaves > 0x7fffffffLL) return hipErrorInvalidValue;
-#if defined(VGPA_EXPERIMENTS) && VGPA_ENERGY_TPW > 1     /* EXPERIMENT: packed S_t, persistent waves, see k_energy_l96_r */
-#define VGPA_L96_TPW(NBV)                                                                                           \
-    if constexpr (NBV == 9 || NBV == 10) {                                                                          \
-      if (one_matrix && a.s_packed) {                                                                               \
-        constexpr int TPW = kEnergyTPW;                                                                             \
-        (void)hipFuncSetAttribute((const void*)k_energy_l96_r<NBV, TPW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        const long long nw = (long long)((a.Np + TPW - 1) / TPW) * a.batch;                                          \
-        hipLaunchKernelGGL((k_energy_l96_r<NBV, TPW>), dim3((unsigned)nw), dim3(64), lds, st, a);                    \
-        break;                                                                                                      \
-      }                                                                                                             \
-    }
-#else
-#define VGPA_L96_TPW(NBV)
-#endif
 #define VGPA_L96_CASE(NBV)                                                                                          \
   case NBV:                                                                                                         \
     if (lds > 48 * 1024)                                                                                            \
       (void)hipFuncSetAttribute(one_matrix ? (const void*)k_energy_l96_r<NBV> : (const void*)k_energy_l96<NBV>,       \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                \
-    VGPA_L96_TPW(NBV)                                                                                               \
     if (one_matrix) hipLaunchKernelGGL(k_energy_l96_r<NBV>, dim3((unsigned)nwaves), dim3(64), lds, st, a);          \
     else hipLaunchKernelGGL(k_energy_l96<NBV>, dim3((unsigned)nwaves), dim3(64), lds, st, a);                        \
     break;
@@ -1200,7 +1123,6 @@ hipError_t launch_energy(const EnergyArgs& a, hipStream_t st) {
       default: return hipErrorInvalidValue;
     }
 #undef VGPA_L96_CASE
-#undef VGPA_L96_TPW
   } else {
     return hipErrorInvalidValue;
   }
@@ -1215,13 +1137,3 @@ hipError_t launch_edf(const EnergyArgs& a, hipStream_t st) {
 
 }  // namespace vgpa
 
-#ifdef VGPA_ENERGY_TRACE
-extern "C" int vgpa_debug_energy_trace(unsigned long long* out, int reset) {
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(vgpa::g_energy_trace), sizeof(unsigned long long) * 16) != hipSuccess) return -1;
-  if (reset) {
-    unsigned long long z[16] = {};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(vgpa::g_energy_trace), z, sizeof(z)) != hipSuccess) return -1;
-  }
-  return 0;
-}
-#endif

@@ -31,9 +31,6 @@
 namespace vgpa {
 namespace ld {
 
-// (diagnostic switch: VGPA_GEMM_SCALAR_LOADS=1 keeps the 8-byte-load kernel for full tiles)
-static const bool gemm_scalar_loads = [] { const char* e = getenv("VGPA_GEMM_SCALAR_LOADS"); return e && e[0] == '1'; }();
-
 struct GemmArgs {
   int M, N, K;              // C[M x N] = op(A)[M x K] . B[K x N]
   const double* A0;         // TRANSA ? [K x M] : [M x K], leading dimension lda
@@ -456,10 +453,8 @@ static void launch_gemm_bm_v(bool transa, const GemmArgs& g, hipStream_t st) {
   dim3 grid(g.N / BN, g.M / BM, g.nb);
   const bool mid = g.A1 != nullptr;
   // four register sets of loads in flight and no load under a branch (k_gemm_v, PFU) when the k-tile count allows it: D = 1024
-  // 44.6 -> 39.6 us per product (47 -> 54 TFLOP/s; 2 sets 44.1, 8 sets 40.1), D = 2048 forward recursion 44.0 -> 47.7 TFLOP/s;
-  // VGPA_GEMM_PF=0: the two-set loop of rounds 2-4
-  static const bool pfu = [] { const char* e = getenv("VGPA_GEMM_PF"); return !(e && e[0] == '0'); }();
-  if (!mid && pfu && (g.K / BK) % 4 == 0) {
+  // 44.6 -> 39.6 us per product (47 -> 54 TFLOP/s; 2 sets 44.1, 8 sets 40.1), D = 2048 forward recursion 44.0 -> 47.7 TFLOP/s
+  if (!mid && (g.K / BK) % 4 == 0) {
     if (transa) hipLaunchKernelGGL((k_gemm_v<true, false, BM, false, 4>), grid, dim3(NT), 0, st, g);
     else hipLaunchKernelGGL((k_gemm_v<false, false, BM, false, 4>), grid, dim3(NT), 0, st, g);
     return;
@@ -477,14 +472,13 @@ template <int BM>
 static void launch_gemm_bm(bool transa, const GemmArgs& g, hipStream_t st) {
   const bool full = g.M % BM == 0 && g.N % BN == 0 && g.K % BK == 0;
   auto al16 = [](const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
-  const bool vec = full && g.lda % 2 == 0 && g.ldb % 2 == 0 && al16(g.A0) && al16(g.A1) && al16(g.B) && !gemm_scalar_loads;
+  const bool vec = full && g.lda % 2 == 0 && g.ldb % 2 == 0 && al16(g.A0) && al16(g.A1) && al16(g.B);
   const bool seg = g.seg_tiles > 0 || g.accumulate;
   if (vec && seg && !g.A1) {        // K-chunk launch (no mid-point operand: the sharded driver forms it once per step)
     GemmArgs h = g;
     if (!h.seg_tiles) { h.seg_tiles = h.K / BK; h.seg_stride = h.K; }
     dim3 grid(g.N / BN, g.M / BM, g.nb);
-    static const bool pfu = [] { const char* e = getenv("VGPA_GEMM_PF"); return !(e && e[0] == '0'); }();
-    if (pfu && (h.K / BK) % 4 == 0) {        // four register sets of loads in flight (launch_gemm_bm_v)
+    if ((h.K / BK) % 4 == 0) {        // four register sets of loads in flight (launch_gemm_bm_v)
       if (transa) hipLaunchKernelGGL((k_gemm_v<true, false, BM, true, 4>), grid, dim3(NT), 0, st, h);
       else hipLaunchKernelGGL((k_gemm_v<false, false, BM, true, 4>), grid, dim3(NT), 0, st, h);
       return;
@@ -508,17 +502,14 @@ hipError_t launch_gemm(bool transa, const GemmArgs& g, hipStream_t st) {
   // resident workgroups of 128-row tiles, and what a CU loses below two workgroups (halving them costs 16 %: D = 1024 at 64 rows
   // 44.0 against 39.6 us, D = 768 / 896 at 64 rows 11.8 / 11.6 against 10.7 / 10.5 ms).  The rounds-2-to-4 rule (the tallest tile
   // with at least 512 workgroups) lost 10-19 % at D = 1536 ... 3072.
-  static const int force_bm = [] { const char* e = getenv("VGPA_GEMM_BM"); return e ? atoi(e) : 0; }();     // (diagnostic: 32 / 64 / 128)
-  int best = force_bm;
-  if (!best) {
-    double best_score = -1.0;
-    const int heights[3] = {32, 64, 128};
-    const double worth[3] = {0.95, 1.0, 0.966};
-    for (int h = 0; h < 3; h++) {
-      const long long w = (long long)((g.N + BN - 1) / BN) * ((g.M + heights[h] - 1) / heights[h]) * g.nb;
-      const double score = (double)w / (double)((w + 255) / 256 * 256) * worth[h] * (w < 512 ? std::pow((double)w / 512.0, 0.22) : 1.0);
-      if (score >= best_score) { best_score = score; best = heights[h]; }      // (ties: the taller tile)
-    }
+  int best = 0;
+  double best_score = -1.0;
+  const int heights[3] = {32, 64, 128};
+  const double worth[3] = {0.95, 1.0, 0.966};
+  for (int h = 0; h < 3; h++) {
+    const long long w = (long long)((g.N + BN - 1) / BN) * ((g.M + heights[h] - 1) / heights[h]) * g.nb;
+    const double score = (double)w / (double)((w + 255) / 256 * 256) * worth[h] * (w < 512 ? std::pow((double)w / 512.0, 0.22) : 1.0);
+    if (score >= best_score) { best_score = score; best = heights[h]; }      // (ties: the taller tile)
   }
   if (best == 128) launch_gemm_bm<128>(transa, g, st);
   else if (best == 64) launch_gemm_bm<64>(transa, g, st);
@@ -606,11 +597,9 @@ static int stage_wide_max_d() {
   return e ? atoi(e) : kStageWideMaxD;
 }
 
-static const bool stage_sym_off = [] { const char* e = getenv("VGPA_STAGE_FULL"); return e && e[0] == '1'; }();
-
 hipError_t launch_stage(const StageArgs& a, hipStream_t st) {
   const int nvec = (a.Mp + (NT / 64) - 1) / (NT / 64);
-  if (a.sym_ok && a.Mp == a.D && a.row0 == 0 && a.cw == a.D && a.W == a.Wcol && !stage_sym_off) {
+  if (a.sym_ok && a.Mp == a.D && a.row0 == 0 && a.cw == a.D && a.W == a.Wcol) {
     const int nt = (a.D + TS - 1) / TS;
     hipLaunchKernelGGL(k_stage_sym, dim3(nt * (nt + 1) / 2 + nvec, 1, a.nb), dim3(NT), 0, st, a);
     return hipGetLastError();

@@ -5,12 +5,10 @@
 //     v_p = sum_i isg_i (l96_flat(chi)[p,i] + (A m)_i +/- G[i][r_p] - b_i)^2
 //     E_t = 1/2 (w0 v_0 + w sum_r (v_+r + v_-r)),  dE/dm = c/2 X^T delta,  dE/dS = c/2 X^T diag(q) X
 // Blocked algorithms with block size 64 (T = ceil(D/64) block columns), all steps batched over `nb` grid points:
-//   Cholesky (right-looking):  diag block: L_JJ = chol(C_JJ), X_JJ = L_JJ^-1      (k_diag64, one wave per block)
+//   Cholesky (right-looking):  diag block: L_JJ = chol(C_JJ), X_JJ = L_JJ^-1      (k_diag64m, one wave per block)
 //                              panel     : L[R,J] = C[R,J] X_JJ^T                 (GEMM, in place)
 //                              trailing  : C[R,R] -= L[R,J] L[R,J]^T              (GEMM, lower tiles only)
-//   inverse  (by block rows):  T1 = L[I,0:I] X[0:I,0:I];  X[I,0:I] = -X_II T1     (2 GEMMs)
-#include <cstdlib>
-
+//   inverse  (by halves)    :  X_21 = -X_22 (L_21 X_11), log2(T) levels          (2 GEMMs per level)
 #include "vgpa_internal.h"
 #include "chol_wave.h"
 
@@ -37,7 +35,6 @@ struct GemmB {
   const double* epi_u;                    // != nullptr: C = alpha (op(A) op(B) - u v^T), u = epi_u + z1 epi_s, v = epi_v + z1 epi_s (the gradient's
   const double* epi_v;                    // rank-one term in the product's epilogue instead of a pass over the result; beta = 0)
   long long epi_s;
-  int k_down;                             // k_tri = 1 in the 16-byte-load kernel: the k loop runs down from the common end (set by gemm_b)
   int mirror;                             // symmetric result (beta = 0, lower_only): the tiles below the diagonal are stored a second
                                           // time, transposed, above it (the skipped tile's own product associates q_k with the other
                                           // factor: equal to it up to rounding, and now symmetric in every bit between tiles)
@@ -228,7 +225,7 @@ __global__ void __launch_bounds__(NT) k_gemm_bv(GemmB g) {
   // k_tri = 1 (op(B) lower triangular: the k range of a tile starts at its first column): the k loop runs DOWN from the common end.  The
   // workgroups of a tile row share the row's A tiles; going up, each starts at its own k and they never read the same A tile at the same
   // time (D = 4096: up to 113 GB of A reads for 3.5 GB of A); going down they start together like the workgroups of a full product.
-  const bool desc = g.k_tri == 1 && g.k_down;
+  const bool desc = g.k_tri == 1;
   const long long astep0 = TA ? (long long)BK * g.lda : (long long)BK, bstep0 = (long long)BK * g.ldb;
   const long long astep = desc ? -astep0 : astep0, bstep = desc ? -bstep0 : bstep0;
   // PF register sets of loads in flight, none under a branch (ld::k_gemm_v: a branch makes the wait counts of its two paths merge
@@ -334,20 +331,16 @@ hipError_t gemm_b(bool ta, bool tb, GemmB g, int nb, hipStream_t st, int nsub = 
   if (g.M <= 0 || g.N <= 0 || nb <= 0 || nsub <= 0) return hipSuccess;
   g.nb1 = nsub > 1 ? nb : 0;
   dim3 grid((g.N + BN - 1) / BN, (g.M + 63) / 64, nb * nsub);
-  static const bool plain_map = [] { const char* e = getenv("VGPA_LDE_TILE_MAP"); return e && e[0] == '0'; }();
-  static const bool k_up = [] { const char* e = getenv("VGPA_LDE_K_DOWN"); return e && e[0] == '0'; }();
-  g.k_down = k_up ? 0 : 1;
   g.tile_map = 0;
-  if (!plain_map && g.lower_only && g.M == g.N) {
+  if (g.lower_only && g.M == g.N) {
     g.tile_map = 2;
     grid.x = grid.y * (grid.y + 1) / 2;
     grid.y = 1;
-  } else if (!plain_map && g.k_tri != 0 && grid.x > 1) {
+  } else if (g.k_tri != 0 && grid.x > 1) {
     g.tile_map = 1;
   }
   auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
-  static const bool scalar_loads = [] { const char* e = getenv("VGPA_GEMM_SCALAR_LOADS"); return e && e[0] == '1'; }();
-  const bool vec = !tb && !scalar_loads && g.M % 64 == 0 && g.N % BN == 0 && g.K % BK == 0 && g.lda % 2 == 0 &&
+  const bool vec = !tb && g.M % 64 == 0 && g.N % BN == 0 && g.K % BK == 0 && g.lda % 2 == 0 &&
                    g.ldb % 2 == 0 && g.sA % 2 == 0 && g.sB % 2 == 0 && al16(g.A) && al16(g.B) &&
                    (nsub == 1 || (g.sA2 % 2 == 0 && g.sB2 % 2 == 0));
   if (vec) {
@@ -375,97 +368,10 @@ __device__ __forceinline__ double lane_value(double v, int j) {
   return __hiloint2double(hi, lo);
 }
 
-__global__ void __launch_bounds__(64) k_diag64(int D, int J, double* Cb, double* Xb, long long strideC, long long strideX,
-                                               int32_t* status, int status_stride_log) {
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  constexpr int LD = NBLK + 1;
-  double* Lm = smem;             // [64][65]
-  double* Xm = Lm + NBLK * LD;   // [64][65]
-  double* rd = Xm + NBLK * LD;   // [64]
-  const int l = threadIdx.x, b = blockIdx.x;
-  double* C = Cb + (long long)b * strideC;
-  double* X = Xb + (long long)b * strideX;
-  const int r0 = J * NBLK;
-  const int nv = (D - r0 < NBLK) ? (D - r0) : NBLK;      // valid rows / columns of this block
-  for (int e = l; e < NBLK * NBLK; e += 64) {
-    const int r = e >> 6, c = e & 63;
-    double v = (r == c) ? 1.0 : 0.0;
-    if (r < nv && c < nv) v = C[(long long)(r0 + r) * D + r0 + c];
-    Lm[r * LD + c] = v;
-  }
-  wave_sync();
-  bool bad = false;
-  for (int j0 = 0; j0 < NBLK && !bad; j0 += 4) {
-    const double* rowi = Lm + l * LD;
-    double s0 = rowi[j0], s1 = rowi[j0 + 1], s2 = rowi[j0 + 2], s3 = rowi[j0 + 3];
-    const double* p0 = Lm + j0 * LD;
-    const double* p1 = p0 + LD; const double* p2 = p1 + LD; const double* p3 = p2 + LD;
-#pragma unroll 4
-    for (int k = 0; k < j0; k++) {
-      const double av = rowi[k];
-      s0 = __builtin_fma(-av, p0[k], s0); s1 = __builtin_fma(-av, p1[k], s1);
-      s2 = __builtin_fma(-av, p2[k], s2); s3 = __builtin_fma(-av, p3[k], s3);
-    }
-    double lq[4], sq[4] = {s0, s1, s2, s3};
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      const int j = j0 + q;
-      double s = sq[q];
-#pragma unroll
-      for (int q2 = 0; q2 < q; q2++) s = __builtin_fma(-lq[q2], lane_value(lq[q2], j), s);
-      const double piv = lane_value(s, j);
-      if (!(piv > 0.0)) bad = true;
-      const double rdv = rsqrt(piv), d = piv * rdv;
-      lq[q] = (l > j) ? s * rdv : 0.0;
-      Lm[l * LD + j] = (l > j) ? lq[q] : ((l == j) ? d : 0.0);
-      if (l == j) rd[j] = rdv;
-    }
-    wave_sync();
-  }
-  if (bad) {
-    if (l == 0) atomicOr(status + (b >> status_stride_log), 1);
-    return;
-  }
-  // X = L^-1, lane = column
-  for (int e = l; e < NBLK * LD; e += 64) Xm[e] = 0.0;
-  wave_sync();
-  for (int i0 = 0; i0 < NBLK; i0 += 4) {
-    const double* r0p = Lm + i0 * LD;
-    const double* r1p = r0p + LD; const double* r2p = r1p + LD; const double* r3p = r2p + LD;
-    double s0 = (i0 == l) ? 1.0 : 0.0, s1 = (i0 + 1 == l) ? 1.0 : 0.0, s2 = (i0 + 2 == l) ? 1.0 : 0.0,
-           s3 = (i0 + 3 == l) ? 1.0 : 0.0;
-    const double* xc = Xm + l;
-#pragma unroll 4
-    for (int k = 0; k < i0; k++) {
-      const double xv = xc[k * LD];
-      s0 = __builtin_fma(-r0p[k], xv, s0); s1 = __builtin_fma(-r1p[k], xv, s1);
-      s2 = __builtin_fma(-r2p[k], xv, s2); s3 = __builtin_fma(-r3p[k], xv, s3);
-    }
-    const double x0 = s0 * rd[i0];
-    s1 = __builtin_fma(-r1p[i0], x0, s1);
-    const double x1 = s1 * rd[i0 + 1];
-    s2 = __builtin_fma(-r2p[i0], x0, s2); s2 = __builtin_fma(-r2p[i0 + 1], x1, s2);
-    const double x2 = s2 * rd[i0 + 2];
-    s3 = __builtin_fma(-r3p[i0], x0, s3); s3 = __builtin_fma(-r3p[i0 + 1], x1, s3); s3 = __builtin_fma(-r3p[i0 + 2], x2, s3);
-    const double x3 = s3 * rd[i0 + 3];
-    double* xw = Xm + i0 * LD + l;
-    xw[0] = x0; xw[LD] = x1; xw[2 * LD] = x2; xw[3 * LD] = x3;
-  }
-  wave_sync();
-  for (int e = l; e < NBLK * NBLK; e += 64) {
-    const int r = e >> 6, c = e & 63;
-    if (r < nv && c < nv) {
-      C[(long long)(r0 + r) * D + r0 + c] = Lm[r * LD + c];
-      X[(long long)(r0 + r) * D + r0 + c] = Xm[r * LD + c];
-    }
-  }
-}
-
-// The same block on the matrix cores: the one-wave Cholesky and blocked forward substitution of the D <= 64 energy kernel
-// (energy.hip::k_energy_l96 phases 1 and 4, NB = 16; chol_wave.h) -- panel updates and the rows of L^-1 as chains of
-// v_mfma_f64_4x4x4_4b, every lane factoring the 4 x 4 diagonal block of its panel itself.  The vector-ALU form above walks
-// ~2 x 1 900 dependent fused multiply-adds per lane behind LDS reads: 63 us per launch, and D / 64 launches in sequence whatever the
-// batch; this one takes a quarter of that.
+// On the matrix cores: the one-wave Cholesky and blocked forward substitution of the D <= 64 energy kernel (energy.hip::k_energy_l96
+// phases 1 and 4, NB = 16; chol_wave.h) -- panel updates and the rows of L^-1 as chains of v_mfma_f64_4x4x4_4b, every lane factoring
+// the 4 x 4 diagonal block of its panel itself.  (A vector-ALU form walked ~2 x 1 900 dependent fused multiply-adds per lane behind LDS
+// reads: 63 us per launch, and D / 64 launches in sequence whatever the batch; this one takes a quarter of that.)
 __global__ void __launch_bounds__(64) k_diag64m(int D, int J, double* Cb, double* Xb, long long strideC, long long strideX,
                                                 int32_t* status, int status_stride_log) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -828,20 +734,6 @@ __global__ void __launch_bounds__(NT) k_grad_fin_dense(int D, double dt, const d
   }
 }
 
-// gA = dt (QS - u m^T) in place on QS ; gB = dt u ; u_i = isg_i (-Ef_i - (A m)_i + b_i) + lam_i
-__global__ void __launch_bounds__(NT) k_grad_fin(int D, double dt, const double* isg, const double* am, const double* b,
-                                                 const double* m, const double* lam, const double* Ef, double* gA, double* gB) {
-  const long long DD = (long long)D * D;
-  const long long vo = (long long)blockIdx.y * D;
-  double* g = gA + (long long)blockIdx.y * DD;
-  for (long long e = (long long)blockIdx.x * NT + threadIdx.x; e < DD; e += (long long)gridDim.x * NT) {
-    const int i = (int)(e / D), j = (int)(e - (long long)i * D);
-    const double u = isg[i] * (-Ef[vo + i] - am[vo + i] + b[vo + i]) + lam[vo + i];
-    g[e] = dt * (g[e] - u * m[vo + j]);
-    if (j == 0) gB[vo + i] = dt * u;
-  }
-}
-
 // u_i = isg_i (-Ef_i - (A m)_i + b_i) + lam_i ; gB = dt u  (the rank-one term itself rides in the epilogue of the product Q S: GemmB::epi_u)
 __global__ void __launch_bounds__(NT) k_grad_u(int D, double dt, const double* isg, const double* am, const double* b, const double* lam,
                                                const double* Ef, double* u, double* gB) {
@@ -883,6 +775,8 @@ int lde_batch(int D, double budget_bytes) {
 }
 
 #define LDE_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return e_; } while (0)
+// between the fork and the join of lde_energy's two streams: a failure returns only once the side stream is done with ws / C / X
+#define LDE_TRY_FORKED(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { if (nh == 2) (void)hipStreamSynchronize(side); return e_; } } while (0)
 
 // Energy terms of Np grid points of ONE problem.  Edf may be nullptr.
 hipError_t lde_energy(int D, int Np, double theta, const double* isg, const double* A, const double* b, const double* m,
@@ -892,16 +786,14 @@ hipError_t lde_energy(int D, int Np, double theta, const double* isg, const doub
   const long long DD = (long long)D * D;
   const int T = (D + NBLK - 1) / NBLK, M = 2 * D + 1;
   const double kappa = 1.05 * D, c = D + kappa;
-  const size_t lds_diag = sizeof(double) * (2 * NBLK * (NBLK + 1) + NBLK);
-  const size_t lds_diagm = sizeof(double) * (2 * NBLK * (NBLK + 1) + 16 * (NBLK / 4) + NBLK);
-  (void)hipFuncSetAttribute((const void*)k_diag64, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_diag);
-  (void)hipFuncSetAttribute((const void*)k_diag64m, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_diagm);
-  static const bool diag_valu = [] { const char* e = getenv("VGPA_LDE_DIAG"); return e && e[0] == 'v'; }();
-  static const bool no_halves = [] { const char* e = getenv("VGPA_LDE_TWO_STREAMS"); return e && e[0] == '0'; }();
-  static const bool no_mirror = [] { const char* e = getenv("VGPA_LDE_SYRK_MIRROR"); return e && e[0] == '0'; }();
-  static const int wpan = [] { const char* e = getenv("VGPA_LDE_PANEL"); const int v = e ? atoi(e) : 4; return v < 1 ? 1 : v; }();
-  static const bool by_rows = [] { const char* e = getenv("VGPA_LDE_INVERSE"); return e && e[0] == 'r'; }();
-  const bool two_halves = side != nullptr && side != st && !no_halves;
+  constexpr size_t lds_diagm = sizeof(double) * (2 * NBLK * (NBLK + 1) + 16 * (NBLK / 4) + NBLK);
+  static const bool diag_lds = [] {
+    (void)hipFuncSetAttribute((const void*)k_diag64m, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_diagm);
+    return true;
+  }();
+  (void)diag_lds;
+  constexpr int wpan = 4;                             // diagonal blocks per outer panel of the Cholesky (see the trailing update)
+  const bool two_halves = side != nullptr && side != st;
   EventPair evs;                                      // (destroyed on every return path)
   if (two_halves && !evs.create()) return hipErrorOutOfMemory;
   hipEvent_t evP = evs.a, evB = evs.b;
@@ -922,8 +814,8 @@ hipError_t lde_energy(int D, int Np, double theta, const double* isg, const doub
     const double* bt = b + (size_t)t0 * D;
     const int eg = (int)((DD + NT * 8 - 1) / (NT * 8));
     hipLaunchKernelGGL(k_prep, dim3(eg, nb), dim3(NT), 0, st, D, c, St, C, X, DD);
-    // ---- blocked Cholesky and X = L^-1, both chains of short launches: k_diag64 is ONE wave per grid point and 50-70 us whatever the
-    // batch (D / 64 of them in sequence), the panels and the first levels of the inverse are a few workgroups each.  With a side stream
+    // ---- blocked Cholesky and X = L^-1, both chains of short launches: k_diag64m is ONE wave per grid point whatever the batch
+    // (D / 64 of them in sequence), the panels and the first levels of the inverse are a few workgroups each.  With a side stream
     // the batch goes through them as two halves on two streams, so that one half's chain runs beside the other half's products (a
     // one-step look-ahead inside one batch was built first: a record / wait pair per step costs the main stream ~20 us, as much as it
     // hid at D = 1024).  Per grid point the same launches in the same order: the same bits.
@@ -932,7 +824,7 @@ hipError_t lde_energy(int D, int Np, double theta, const double* isg, const doub
     const int hb_[3] = {0, nh == 2 ? nb - nb / 2 : nb, nb};
     if (nh == 2) {
       LDE_TRY(hipEventRecord(evP, st));                      // fork behind k_prep
-      LDE_TRY(hipStreamWaitEvent(side, evP, 0));
+      LDE_TRY_FORKED(hipStreamWaitEvent(side, evP, 0));
     }
     for (int J = 0; J < T; J++) {
       const int r1 = (J + 1) * NBLK;
@@ -943,15 +835,14 @@ hipError_t lde_energy(int D, int Np, double theta, const double* isg, const doub
         const int n = hb_[hh + 1] - hb_[hh];
         double* Ch = C + (size_t)hb_[hh] * DD;
         double* Xh = X + (size_t)hb_[hh] * DD;
-        if (diag_valu) hipLaunchKernelGGL(k_diag64, dim3(n), dim3(64), lds_diag, sh, D, J, Ch, Xh, DD, DD, status, 30);
-        else hipLaunchKernelGGL(k_diag64m, dim3(n), dim3(64), lds_diagm, sh, D, J, Ch, Xh, DD, DD, status, 30);
+        hipLaunchKernelGGL(k_diag64m, dim3(n), dim3(64), lds_diagm, sh, D, J, Ch, Xh, DD, DD, status, 30);
         if (r1 >= D) continue;
         GemmB p{};   // L[R,J] = C[R,J] X_JJ^T   (in place)
         p.M = Mr; p.N = kw; p.K = kw; p.A = Ch + (size_t)r1 * D + J * NBLK; p.lda = D; p.sA = DD;
         p.B = Xh + (size_t)(J * NBLK) * D + J * NBLK; p.ldb = D; p.sB = DD;
         p.C = Ch + (size_t)r1 * D + J * NBLK; p.ldc = D; p.sC = DD; p.alpha = 1.0; p.beta = 0.0;
         // in place: every workgroup owns a 64-row block of the panel, reads all of it before its epilogue writes it
-        LDE_TRY(gemm_b(false, true, p, n, sh));
+        LDE_TRY_FORKED(gemm_b(false, true, p, n, sh));
         // Trailing update in two levels: panel J updates the block columns of its own OUTER panel (`wpan` blocks) only; behind the outer
         // panel's last block everything right of it gets ONE update with all its columns (K = 64 wpan instead of wpan updates with
         // K = 64: the update is bound by reading and writing C -- 8 flop per byte at K = 64 -- and this is a quarter of the traffic).
@@ -960,14 +851,14 @@ hipError_t lde_energy(int D, int Np, double theta, const double* isg, const doub
         u.M = Mr; u.N = pend - r1; u.K = kw; u.A = Ch + (size_t)r1 * D + J * NBLK; u.lda = D; u.sA = DD;
         u.B = u.A; u.ldb = D; u.sB = DD; u.C = Ch + (size_t)r1 * D + r1; u.ldc = D; u.sC = DD; u.alpha = -1.0; u.beta = 1.0;
         u.lower_only = 1;
-        LDE_TRY(gemm_b(false, true, u, n, sh));
+        LDE_TRY_FORKED(gemm_b(false, true, u, n, sh));
         if (r1 == pend && pend < D) {   // J was the outer panel's last block: C[R2,R2] -= L[R2,P] L[R2,P]^T
           const int p0 = (J / wpan) * wpan * NBLK;
           GemmB w{};
           w.M = D - pend; w.N = D - pend; w.K = pend - p0; w.A = Ch + (size_t)pend * D + p0; w.lda = D; w.sA = DD;
           w.B = w.A; w.ldb = D; w.sB = DD; w.C = Ch + (size_t)pend * D + pend; w.ldc = D; w.sC = DD; w.alpha = -1.0; w.beta = 1.0;
           w.lower_only = 1;
-          LDE_TRY(gemm_b(false, true, w, n, sh));
+          LDE_TRY_FORKED(gemm_b(false, true, w, n, sh));
         }
       }
       if (r1 >= D) break;
@@ -978,28 +869,7 @@ hipError_t lde_energy(int D, int Np, double theta, const double* isg, const doub
     // neighbouring groups of h blocks; the groups of a level are independent and go into ONE launch per product (second batch level of
     // GemmB), so D / 64 = 16 | 64 takes 8 | 12 launches of growing products instead of 30 | 126 of one 64-row block each.  The
     // intermediate L_21 X_11 sits in G (free until G = A L) at the place of X_21.
-    if (by_rows) {      // the block-row form of rounds 1-4, kept for the A/B measurement (VGPA_LDE_INVERSE=rows)
-      for (int I = 1; I < T; I++) {
-        const int r0 = I * NBLK;
-        const int Mi = (D - r0 < NBLK) ? (D - r0) : NBLK;
-        for (int hh = nh - 1; hh >= 0; hh--) {
-          const int n = hb_[hh + 1] - hb_[hh];
-          double* Ch = C + (size_t)hb_[hh] * DD;
-          double* Xh = X + (size_t)hb_[hh] * DD;
-          double* Th = T1 + (size_t)hb_[hh] * NBLK * D;
-          GemmB a1{};  // T1 = L[I, 0:r0] X[0:r0, 0:r0]
-          a1.M = Mi; a1.N = r0; a1.K = r0; a1.A = Ch + (size_t)r0 * D; a1.lda = D; a1.sA = DD; a1.B = Xh; a1.ldb = D; a1.sB = DD;
-          a1.C = Th; a1.ldc = D; a1.sC = (long long)NBLK * D; a1.alpha = 1.0; a1.beta = 0.0;
-          a1.k_tri = 1;                                  // X[0:r0, 0:r0] is lower triangular
-          LDE_TRY(gemm_b(false, false, a1, n, hs_[hh]));
-          GemmB a2{};  // X[I, 0:r0] = -X_II T1
-          a2.M = Mi; a2.N = r0; a2.K = Mi; a2.A = Xh + (size_t)r0 * D + r0; a2.lda = D; a2.sA = DD; a2.B = Th; a2.ldb = D;
-          a2.sB = (long long)NBLK * D; a2.C = Xh + (size_t)r0 * D; a2.ldc = D; a2.sC = DD; a2.alpha = -1.0; a2.beta = 0.0;
-          LDE_TRY(gemm_b(false, false, a2, n, hs_[hh]));
-        }
-      }
-    }
-    for (int h = 1; h < T && !by_rows; h *= 2) {
+    for (int h = 1; h < T; h *= 2) {
       const int hs = h * NBLK;
       const int ngr = (T - h + 2 * h - 1) / (2 * h);           // groups whose second half exists
       const long long step2 = (long long)2 * hs * (D + 1);     // from one group's blocks to the next group's
@@ -1017,19 +887,19 @@ hipError_t lde_energy(int D, int Np, double theta, const double* isg, const doub
           a1.B = X + org; a1.ldb = D; a1.sB = DD; a1.sB2 = step2;
           a1.C = G + org + (size_t)hs * D; a1.ldc = D; a1.sC = DD; a1.sC2 = step2; a1.alpha = 1.0; a1.beta = 0.0;
           a1.k_tri = 1;                                          // X_11 is lower triangular
-          LDE_TRY(gemm_b(false, false, a1, n, hs_[hh], ng));
+          LDE_TRY_FORKED(gemm_b(false, false, a1, n, hs_[hh], ng));
           GemmB a2{};  // X_21 = -X_22 T
           a2.M = Mi; a2.N = hs; a2.K = Mi; a2.A = X + org + (size_t)hs * (D + 1); a2.lda = D; a2.sA = DD; a2.sA2 = step2;
           a2.B = G + org + (size_t)hs * D; a2.ldb = D; a2.sB = DD; a2.sB2 = step2;
           a2.C = X + org + (size_t)hs * D; a2.ldc = D; a2.sC = DD; a2.sC2 = step2; a2.alpha = -1.0; a2.beta = 0.0;
           a2.k_tri = 3;                                          // X_22 is lower triangular
-          LDE_TRY(gemm_b(false, false, a2, n, hs_[hh], ng));
+          LDE_TRY_FORKED(gemm_b(false, false, a2, n, hs_[hh], ng));
         }
       }
     }
     if (nh == 2) {
-      LDE_TRY(hipEventRecord(evB, side));                      // join
-      LDE_TRY(hipStreamWaitEvent(st, evB, 0));
+      LDE_TRY_FORKED(hipEventRecord(evB, side));               // join
+      LDE_TRY_FORKED(hipStreamWaitEvent(st, evB, 0));
     }
     // ---- G = A L ; A m
     GemmB gg{};
@@ -1061,8 +931,8 @@ hipError_t lde_energy(int D, int Np, double theta, const double* isg, const doub
     sy.M = D; sy.N = D; sy.K = D; sy.A = X; sy.lda = D; sy.sA = DD; sy.B = C; sy.ldb = D; sy.sB = DD;
     sy.C = dEs + (size_t)t0 * DD; sy.ldc = D; sy.sC = DD; sy.alpha = 0.5 * c; sy.beta = 0.0;
     sy.k_tri = 2;                                    // X^T[i][k] = X[k][i] = 0 for k < i and (q X)[k][j] = 0 for k < j
-    sy.lower_only = no_mirror ? 0 : 1;               // the result is symmetric: the tiles on and below the diagonal, mirrored on the way out
-    sy.mirror = sy.lower_only;
+    sy.lower_only = 1;                               // the result is symmetric: the tiles on and below the diagonal, mirrored on the way out
+    sy.mirror = 1;
     LDE_TRY(gemm_b(true, false, sy, nb, st));
     if (Edf) hipLaunchKernelGGL(k_edf, dim3(eg, nb), dim3(NT), 0, st, D, mt, Edf + (size_t)t0 * DD);
     LDE_TRY(hipGetLastError());
@@ -1111,22 +981,17 @@ hipError_t lde_grad(int D, int Np, double dt, const double* isg, const double* A
     GemmB g{};
     g.M = D; g.N = D; g.K = D; g.A = Q; g.lda = D; g.sA = DD; g.B = S + (size_t)t0 * DD; g.ldb = D; g.sB = DD;
     g.C = gA + (size_t)t0 * DD; g.ldc = D; g.sC = DD; g.alpha = 1.0; g.beta = 0.0;
-    static const bool fin_pass = [] { const char* e = getenv("VGPA_LDE_GRAD_EPILOGUE"); return e && e[0] == '0'; }();
-    if (fin_pass) {      // rounds 1-4: the rank-one term and dt in a pass over the product (kept for the A/B measurement)
-      LDE_TRY(gemm_b(false, false, g, nb, st));
-      hipLaunchKernelGGL(k_grad_fin, dim3(eg, nb), dim3(NT), 0, st, D, dt, isg, am, b + (size_t)t0 * D, m + (size_t)t0 * D,
-                         lam + (size_t)t0 * D, Ef + (size_t)t0 * D, gA + (size_t)t0 * DD, gB + (size_t)t0 * D);
-    } else {             // gA = dt (Q S - u m^T) out of the product's epilogue
-      hipLaunchKernelGGL(k_grad_u, dim3((D + NT - 1) / NT, nb), dim3(NT), 0, st, D, dt, isg, am, b + (size_t)t0 * D, lam + (size_t)t0 * D,
-                         Ef + (size_t)t0 * D, u0, gB + (size_t)t0 * D);
-      g.alpha = dt; g.epi_u = u0; g.epi_v = m + (size_t)t0 * D; g.epi_s = D;
-      LDE_TRY(gemm_b(false, false, g, nb, st));
-    }
+    // gA = dt (Q S - u m^T) out of the product's epilogue
+    hipLaunchKernelGGL(k_grad_u, dim3((D + NT - 1) / NT, nb), dim3(NT), 0, st, D, dt, isg, am, b + (size_t)t0 * D, lam + (size_t)t0 * D,
+                       Ef + (size_t)t0 * D, u0, gB + (size_t)t0 * D);
+    g.alpha = dt; g.epi_u = u0; g.epi_v = m + (size_t)t0 * D; g.epi_s = D;
+    LDE_TRY(gemm_b(false, false, g, nb, st));
     LDE_TRY(hipGetLastError());
   }
   return hipSuccess;
 }
 #undef LDE_TRY
+#undef LDE_TRY_FORKED
 
 }  // namespace ld
 }  // namespace vgpa

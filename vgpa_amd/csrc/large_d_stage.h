@@ -14,14 +14,7 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 // the LDS serves as two accesses of 4 x 16 lanes over 32 banks (MI355X_MICROARCH.md, LDS table): 8 cycles at best, and 16 on the
 // row-major tiles ([row][16 k + 2]: rows r and r + 8 then share banks) -- with 8 waves per CU that is as many LDS cycles per k-tile as
 // the MFMA pipe has.
-#ifndef VGPA_LDS_FRAG_VOLATILE
-#define VGPA_LDS_FRAG_VOLATILE 1
-#endif
-#if VGPA_LDS_FRAG_VOLATILE
 typedef const volatile double __attribute__((address_space(3)))* frag_ptr;      // (stated address space: a volatile generic pointer becomes flat loads)
-#else
-typedef const double __attribute__((address_space(3)))* frag_ptr;
-#endif
 __device__ __forceinline__ frag_ptr frag(const double* p) { return (frag_ptr)p; }
 
 constexpr int BN = 64, BK = 16, NT = 256;   // block tile BM x 64 (BM = 128, or 64 when 128 would not fill the chip)

@@ -29,9 +29,7 @@ namespace ld {
 // register sets of operand loads in flight in k_stage_prod (fused sweep, same box, 2 / 4 / 6 sets: D = 72 26.5 / 31.5 / 29.4 ms,
 // 128 31.2 / 32.3 / 40.9, 200 45.9 / 50.4 / 55.4, 256 50.7 / 51.2 / 56.1: the tiles a deeper pipeline multiplies beyond the last one
 // cost more than its depth hides)
-#ifndef VGPA_PROD_PF
-#define VGPA_PROD_PF 2
-#endif
+constexpr int kProdPF = 2;
 // Operand tiles come through buffer descriptors (raw_buffer_load: a per-thread 32-bit offset, advanced by one k-tile after every
 // load): no 64-bit address arithmetic per tile -- with addresses recomputed per tile the register allocator recycles the destination
 // registers of the loads in flight for them and every prefetch waits for the previous one (seen in the ISA of the first version of
@@ -90,7 +88,7 @@ __global__ void __launch_bounds__(NT) k_stage_prod(StageArgs a) {
   // two register sets (prefetch distance two) of RAW loads: the mid-point average and the k-edge select happen when a set moves to
   // LDS, one k-tile later -- next to the loads they would wait for them on the spot
   struct Regs { double a[2][2], b[2][2], x[2][2]; };          // [I | J][q]
-  constexpr int PF = VGPA_PROD_PF;
+  constexpr int PF = kProdPF;
   Regs rs[PF];
   auto load_tiles = [&](Regs& r) {            // the NEXT k-tile (tiles are requested in order)
 #pragma unroll
@@ -210,12 +208,6 @@ __global__ void __launch_bounds__(NT) k_stage_prod(StageArgs a) {
 // 16 instead of 12 fragment reads per 8 MFMAs, four instead of three 16-byte loads and LDS stores per k-tile.  At THIS size (512
 // workgroups, two per CU, one round) neither prefetch depth (2 / 4 / 6 register sets), nor the order of LDS stores and products,
 // nor the XCD-aware tile order moved it by more than 1 %; away from it the latter two pay (below).
-#ifndef VGPA_WIDE_PF
-#define VGPA_WIDE_PF 4
-#endif
-#ifndef VGPA_WIDE_XCD
-#define VGPA_WIDE_XCD 1
-#endif
 typedef double d2v __attribute__((ext_vector_type(2)));
 typedef unsigned int u4v __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ d2v buf_load2(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
@@ -228,7 +220,6 @@ __global__ void __launch_bounds__(NT) k_stage_wide(StageArgs a) {
   const int D = a.D;
   const int nt = (D + TS - 1) / TS;
   const int noff = nt * (nt - 1) / 2, ndg = (nt + 1) / 2;
-#if VGPA_WIDE_XCD
   const int chunk = (noff + ndg + 7) / 8;                      // matrix workgroups per XCD
   if ((int)blockIdx.x >= 8 * chunk) { stage_vector_rows(a, (int)blockIdx.x - 8 * chunk); return; }
   // workgroup -> tiles.  Workgroup b runs on XCD b % 8, each with its own L2: XCD x takes the x-th CONTIGUOUS eighth of a list in
@@ -267,20 +258,6 @@ __global__ void __launch_bounds__(NT) k_stage_wide(StageArgs a) {
     }
     Ra = by * TS; Rb = bx * TS;
   }
-#else
-  if ((int)blockIdx.x >= noff + ndg) { stage_vector_rows(a, (int)blockIdx.x - noff - ndg); return; }
-  const bool pair = (int)blockIdx.x < noff;
-  int Ra, Rb;                                                  // pair: I0, J0 (I < J); diagonal: Ia0, Ib0
-  bool two = true;
-  if (pair) {
-    int by = 0, rem = (int)blockIdx.x;
-    while (rem >= nt - 1 - by) { rem -= nt - 1 - by; by++; }
-    Ra = by * TS; Rb = (by + 1 + rem) * TS;
-  } else {
-    const int dg = (int)blockIdx.x - noff;
-    Ra = 2 * dg * TS; two = 2 * dg + 1 < nt; Rb = two ? Ra + TS : Ra;
-  }
-#endif
   constexpr int LDR = 18, LDT = 48;
   constexpr int SZR = TS * LDR, SZK = BK * LDT;
   constexpr int SZ0 = TRANSA ? SZK : SZR;                    // slots 0 and 3 (tiles of A); slots 1 and 2 (tiles of X) are row-major
@@ -308,8 +285,8 @@ __global__ void __launch_bounds__(NT) k_stage_wide(StageArgs a) {
   }
   const unsigned step_rm = BK * 8u, step_km = TRANSA ? (unsigned)D * BK * 8u : step_rm;
   // PF register sets of loads in flight (fused sweep, same box, PF = 2 -> 4: D = 384 37.4 -> 35.4 ms, 640 30.6 -> 28.9, 1000
-  // 55.1 -> 54.5, 1536 80.1 -> 74.8; at D = 1024, exactly two workgroups per CU, within 1 %: tools/ab_wide_variants.sh)
-  constexpr int PF = VGPA_WIDE_PF;
+  // 55.1 -> 54.5, 1536 80.1 -> 74.8; at D = 1024, exactly two workgroups per CU, within 1 %)
+  constexpr int PF = 4;
   struct Regs { d2v v[4]; };
   Regs rs[PF];
   auto load_tiles = [&](Regs& r) {                             // the NEXT k-tile
@@ -459,7 +436,7 @@ hipError_t launch_stage_fused(int kind, const StageArgs& a, hipStream_t st) {
     }
   } else {
     const int nmat = nt * (nt - 1) / 2 + (nt + 1) / 2;
-    const dim3 grid((VGPA_WIDE_XCD ? 8 * ((nmat + 7) / 8) : nmat) + nvec, 1, a.nb);
+    const dim3 grid(8 * ((nmat + 7) / 8) + nvec, 1, a.nb);      // (matrix workgroups padded to whole XCD rounds: see k_stage_wide)
     if (a.fwd) hipLaunchKernelGGL((k_stage_wide<false>), grid, dim3(NT), 0, st, a);
     else hipLaunchKernelGGL((k_stage_wide<true>), grid, dim3(NT), 0, st, a);
   }

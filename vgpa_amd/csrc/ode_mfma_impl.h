@@ -34,26 +34,16 @@
 
 namespace vgpa {
 namespace sym {
-// VGPA_SYM_RUNS=1 keeps the run layout of the symmetric-unit kernels where the fragment cover exists (comparison runs)
-inline bool runs_only_env() {
-  static const bool r = [] { const char* e = getenv("VGPA_SYM_RUNS"); return e && e[0] == '1'; }();
-  return r;
-}
 // the backward kernels that can store Q''_t = Sigma^-1 A_t - 2 Psi_t instead of Psi_t (OdeArgs::q_on): the fragment-cover
 // kernels (ode_sym_impl.h, 33 <= D <= 40) of the mid-point methods with sparse jumps
 inline bool stores_q(int method, int D) {
-  return (method == VGPA_ODE_RK2 || method == VGPA_ODE_RK4) && D >= 33 && D <= 40 && !runs_only_env();
+  return (method == VGPA_ODE_RK2 || method == VGPA_ODE_RK4) && D >= 33 && D <= 40;
 }
 // the backward kernel that assembles the gradient on its helper waves (OdeArgs::grad_on; k_ode_sym, GF): the fragment-cover kernels
-// of RK4 (VGPA_SYM_COVER=op, the outer-product experiment, has no helper waves)
+// of RK4
 inline bool fuses_grad(int method, int D) {
-#ifdef VGPA_EXPERIMENTS
-  static const bool op = [] { const char* e = getenv("VGPA_SYM_COVER"); return e && e[0] == 'o' && e[1] == 'p' && !e[2]; }();
-#else
-  const bool op = false;
-#endif
   static const bool off = [] { const char* e = getenv("VGPA_FUSED_GRAD"); return e && e[0] == '0'; }();
-  return method == VGPA_ODE_RK4 && stores_q(method, D) && !op && !off;
+  return method == VGPA_ODE_RK4 && stores_q(method, D) && !off;
 }
 }  // namespace sym
 }  // namespace vgpa
@@ -77,25 +67,6 @@ using vgpa::ldu;
 __device__ __forceinline__ void stg(double* base, unsigned off8, double v) {
   *reinterpret_cast<double*>(reinterpret_cast<char*>(base) + off8) = v;
 }
-
-// Diagnostic build only (tools/ubench/ode_pe_stamp.hip): per-segment cycle sums of one P wave and one E wave of workgroup 0.
-// Never defined in the product build, so no stamp executes there.
-#ifdef VGPA_STAMPS_ROLE
-__device__ long long g_stamp_role[4][16];
-#endif
-#ifdef VGPA_STAMPS
-__device__ long long g_stamp[4][8];
-#define VGPA_STAMP(role, i)                                                                   \
-  do {                                                                                        \
-    const long long t_ = clock64();                                                           \
-    if ((threadIdx.x & 63) == 0 && blockIdx.x == 0) g_stamp[role][i] += t_ - stamp_prev_;     \
-    stamp_prev_ = t_;                                                                         \
-  } while (0)
-#define VGPA_STAMP_DECL long long stamp_prev_ = clock64()
-#else
-#define VGPA_STAMP(role, i) do {} while (0)
-#define VGPA_STAMP_DECL do {} while (0)
-#endif
 
 // ---- dealing MFMA units to (P wave, slot) -----------------------------------------------------------------------
 // A "unit" is one MFMA accumulator = four 4x4 output blocks: (I, J = 4q..4q+3) for the full 16-column groups, and the
@@ -488,7 +459,6 @@ __device__ __forceinline__ void p_role(const OdeArgs& a, int prob, const Lds<NB>
 #pragma unroll
   for (int s = 0; s < g::MAXU; s++) { settle(fc[s]); settle(fn[s]); }
   __syncthreads();                       // prologue (X, R, xv, constant jump) published
-  VGPA_STAMP_DECL;
   for (int k = 0; k < n_steps; k++) {
 #pragma unroll
     for (int j = 0; j < NS; j++) {
@@ -498,13 +468,9 @@ __device__ __forceinline__ void p_role(const OdeArgs& a, int prob, const Lds<NB>
 #pragma unroll
         for (int s = 0; s < g::MAXU; s++) { fc[s] = fn[s]; fn[s] = ldg(G + nxt, T.gofs[s]); }
       }
-      VGPA_STAMP(0, 0);                  // product
       __syncthreads();
-      VGPA_STAMP(0, 1);                  // barrier
       p_stage_after<METHOD, FWD, NB>(j, k, n_steps, A, DD, Np, L, S, an, tp);
-      VGPA_STAMP(0, 2);                  // operand staging
       __syncthreads();
-      VGPA_STAMP(0, 3);                  // barrier (the element-wise phase)
     }
   }
 }
@@ -825,19 +791,14 @@ __device__ __forceinline__ void e_role(const OdeArgs& a, int prob, const Lds<NB>
   __syncthreads();                                         // LDS zero-filled
   R.prologue(S, prob, L, true);
   __syncthreads();                                         // prologue published
-  VGPA_STAMP_DECL;
   for (int k = 0; k < n_steps; k++) {
     R.head(S, k);
 #pragma unroll
     for (int j = 0; j < NS; j++) {
       R.chores(S, L, j, k);              // beside the product
-      VGPA_STAMP(1, 0);
       __syncthreads();
-      VGPA_STAMP(1, 1);
       R.elem(S, L, j, k);
-      VGPA_STAMP(1, 2);
       __syncthreads();
-      VGPA_STAMP(1, 4);
     }
     R.tail(S);
   }

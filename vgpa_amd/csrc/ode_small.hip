@@ -677,17 +677,10 @@ __global__ void __launch_bounds__(NTS) __attribute__((amdgpu_waves_per_eu(1, 1))
         esum += dt * (e_t + e_m) / 2.0;     // my_trapz, utilities.py:144 (interval [t-1, t])
         e_t = e_m;
         if (GRAD) {
-#ifndef VGPA_LANE_JUMP_PREFETCH
-#define VGPA_LANE_JUMP_PREFETCH 1
-#endif
           double js[DD];
-#if VGPA_LANE_JUMP_PREFETCH
           const double wj = n_cur >= 0 ? 1.0 : 0.0;
 #pragma unroll
           for (int e = 0; e < DD; e++) js[e] = wj * jsc[e];
-#else
-          load_jump<D>(a, prob, idx, js, jm_cur);
-#endif
           bwd_step<METHOD, D>(At, Am, gst, gsm, gmt, gmm, js, jm_cur, dt, pk, lk);
           double gA[DD], gB[D];
           grad_point<D>(Am, bm, mm, Sm, ef, edf, pk, lk, Iv, dt, gA, gB);
@@ -701,17 +694,13 @@ __global__ void __launch_bounds__(NTS) __attribute__((amdgpu_waves_per_eu(1, 1))
         for (int e = 0; e < DD; e++) { Sc[e] = Sn[e]; Sn[e] = Sn2[e]; }
 #pragma unroll
         for (int i = 0; i < D; i++) { mc[i] = mn[i]; mn[i] = mn2[i]; }
-#if VGPA_LANE_JUMP_PREFETCH
 #pragma unroll
         for (int i = 0; i < D; i++) jm_cur[i] = jm_nxt[i];
         n_cur = n_nxt; n_nxt = n_pre;
-#endif
         // ... and everything the steps after the next one need is requested behind it
         load_ms(idx > 2 ? idx - 3 : 0, Sn2, mn2);
-#if VGPA_LANE_JUMP_PREFETCH
         request_jump(n_nxt, jm_nxt);
         n_pre = obs_at(idx - 3);
-#endif
       }
     }
     if (GRAD) {
@@ -735,15 +724,6 @@ hipError_t launch_d(const OdeArgs& a, hipStream_t st) {
   if (FWD && a.msT) {
     if constexpr (D == 1 || D == 3) {      // (the models of the fused lane pass)
       constexpr int TT = D == 3 ? 6 : 16;
-#ifdef VGPA_LANE_T_EXPERIMENTS
-      if (D == 3 && METHOD == VGPA_ODE_RK4) {
-        const char* e = getenv("VGPA_LANE_T_FWD");
-        const int t = e ? atoi(e) : TT;
-        if (t == 4) { hipLaunchKernelGGL((k_fwd_lane<METHOD, D, 4, true>), grid, block, 0, st, a); return hipGetLastError(); }
-        if (t == 8) { hipLaunchKernelGGL((k_fwd_lane<METHOD, D, 8, true>), grid, block, 0, st, a); return hipGetLastError(); }
-        if (t == 12) { hipLaunchKernelGGL((k_fwd_lane<METHOD, D, 12, true>), grid, block, 0, st, a); return hipGetLastError(); }
-      }
-#endif
       hipLaunchKernelGGL((k_fwd_lane<METHOD, D, TT, true>), grid, block, 0, st, a);
       return hipGetLastError();
     }
@@ -771,17 +751,8 @@ hipError_t launch_sweep_mm(const LaneSweepArgs& q, hipStream_t st) {
   // Lorenz-63: chunks of 4 grid points.  6 (round 4, first version) keeps 108 registers of the next chunk in flight and, with the
   // moments and jumps of the steps ahead, spills 6-19 of the wave's 512 -- and every reload of a spilled value inside the step loop is
   // a vector memory operation the compiler waits for with vmcnt(0), i.e. together with every request in flight.  Same box, T = 4 | 6:
-  // 4.67 | 5.16-5.49 ms per 65536 problems (tools/lane_t_scan.sh).
+  // 4.67 | 5.16-5.49 ms per 65536 problems.
   constexpr int T = (MODEL == VGPA_MODEL_L63) ? 4 : 16;
-#ifdef VGPA_LANE_T_EXPERIMENTS
-  if (MODEL == VGPA_MODEL_L63 && METHOD == VGPA_ODE_RK4 && q.want_grad) {
-    const char* e = getenv("VGPA_LANE_T_BWD");
-    const int t = e ? atoi(e) : T;
-    if (t == 6) { hipLaunchKernelGGL((k_sweep_lane<METHOD, MODEL, true, 6>), grid, block, 0, st, q); return hipGetLastError(); }
-    if (t == 5) { hipLaunchKernelGGL((k_sweep_lane<METHOD, MODEL, true, 5>), grid, block, 0, st, q); return hipGetLastError(); }
-    if (t == 8) { hipLaunchKernelGGL((k_sweep_lane<METHOD, MODEL, true, 8>), grid, block, 0, st, q); return hipGetLastError(); }
-  }
-#endif
   if (q.want_grad) hipLaunchKernelGGL((k_sweep_lane<METHOD, MODEL, true, T>), grid, block, 0, st, q);
   else hipLaunchKernelGGL((k_sweep_lane<METHOD, MODEL, false, T>), grid, block, 0, st, q);
   return hipGetLastError();

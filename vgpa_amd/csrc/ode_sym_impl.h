@@ -49,35 +49,11 @@ using mfma::n_stages;
 using mfma::settle;
 using mfma::stage_op;
 using mfma::stg;
-#ifdef VGPA_STAMPS
-using mfma::g_stamp;
-#endif
 using mfma::OP_M;
 using mfma::OP_R;
 using mfma::OP_X;
 
 constexpr int kMaxNB = 16;          // D <= 64
-#ifndef VGPA_SYM_INTERLEAVE
-#define VGPA_SYM_INTERLEAVE 1          // fragment reads between the products (sched_group_barrier) instead of in blocks
-#endif
-#ifndef VGPA_SYM_TAILPRIO
-#define VGPA_SYM_TAILPRIO 1
-#endif
-#ifndef VGPA_ABL_NOFRAG
-#define VGPA_ABL_NOFRAG 0              // DIAGNOSTIC (wrong results): only the first pipeline step of a stage reads fragments -- what the LDS reads cost
-#endif
-#ifndef VGPA_ABL_NOSTORE
-#define VGPA_ABL_NOSTORE 0             // DIAGNOSTIC (wrong results): the stage state is not written to HBM
-#endif
-#ifndef VGPA_ABL_NOVEC
-#define VGPA_ABL_NOVEC 0               // DIAGNOSTIC (wrong results): no vector recursion (partial inner products, per-wave update)
-#endif
-#ifndef VGPA_SYM_OP_PIN
-#define VGPA_SYM_OP_PIN 0              // outer-product cover: 1 = the written order of products, rotations and reads is pinned (slower)
-#endif
-#ifndef VGPA_SYM_LOOP1
-#define VGPA_SYM_LOOP1 1               // cover kernels: the loop unit (diagonal blocks) runs one chain + an in-block transpose
-#endif
 
 // ---- runs: a cover of the unordered pairs {c, j} of super-block indices (loops included) by stars of <= 2 edges ---------
 // Run = super-row c with up to two partners.  Greedy: every loop (c, c) with the edge to c + 1; then, vertex by vertex, two
@@ -212,106 +188,10 @@ __host__ __device__ constexpr bool cover_diagonals_in_loop_units() {
 }
 static_assert(cover_diagonals_in_loop_units(), "single-chain loop units: every diagonal block in slot 2 of a triangle wave, slot 2 of the rectangle wave unused");
 
-// ---- outer-product cover (round 4): NSB = 5 (D = 33 .. 40) ------------------------------------------------------------------
-// The product phase of the fragment cover above is bound by its LDS fragment reads as much as by the matrix pipe (EXPERIMENTS.md
-// s.9): 8 (6) ds_read_b128 per k-pair and wave for 14 products.  A fragment register of a map m also holds, up to a rotation of
-// its four 4-lane block groups inside every 16-lane row, the fragment of every ROTATED map rot_r(m)[q] = m[(q - r) & 3] -- and a
-// rotation of lanes inside a row is what the DPP operand of a v_mov does (row_ror:4r, no LDS).  So a wave reads the fragments of
-// only TWO maps (P, Q) of both operand buffers -- 4 reads per k-pair -- and multiplies the units
-//   slot 0: (P, P)          the loop unit: four diagonal blocks, one chain + in-block transpose (as kCoverLoopSlot above)
-//   slot 1: (rot_1 P, P)    the 4-cycle P0-P1-P2-P3 of block pairs inside P
-//   slot 2: (rot_1 Q, Q)    ... inside Q
-//   slot 3: (P, Q)          P[q] with Q[q]
-// with ONE instruction stream for all four waves: 14 products per k-pair as before, 16 fragment reads per k-pair and workgroup
-// instead of 26, 16 v_mov_dpp per k-pair and wave for the rotated row sides.  The maps below were found by simulated annealing
-// (cover all 55 block pairs, every diagonal block in a loop unit; the ds_read_b128 bank condition (i) above on every map; as few
-// publish bank conflicts (ii)/(iii) as possible).
-struct OpUnit { int rmap, rot, cmap; };              // unit = (rot_rot(map rmap), map cmap); maps: 0 = P, 1 = Q
-constexpr OpUnit kOpUnits[4] = {{0, 0, 0}, {0, 1, 0}, {1, 1, 1}, {0, 0, 1}};
-constexpr int kOpLoopSlot = 0;
-constexpr int kOpMaps[4][2][4] = {                   // [wave][P, Q][block q]
-    {{7, 4, 6, 1}, {3, 8, 2, 9}},
-    {{8, 9, 8, 9}, {1, 5, 0, 4}},
-    {{5, 8, 6, 3}, {6, 7, 9, 0}},
-    {{2, 3, 1, 0}, {5, 4, 2, 7}}};
-__host__ __device__ constexpr int op_row_block(int w, int s, int q) { return kOpMaps[w][kOpUnits[s].rmap][(q - kOpUnits[s].rot) & 3]; }
-__host__ __device__ constexpr int op_col_block(int w, int s, int q) { return kOpMaps[w][kOpUnits[s].cmap][q]; }
-__host__ __device__ constexpr bool op_owner(int w, int s, int q) {      // first occurrence of the block pair in (w, s, q) order
-  const int I = op_row_block(w, s, q), J = op_col_block(w, s, q);
-  const int lo = I < J ? I : J, hi = I < J ? J : I;
-  for (int w2 = 0; w2 <= w; w2++)
-    for (int s2 = 0; s2 < 4; s2++)
-      for (int q2 = 0; q2 < 4; q2++) {
-        if (w2 == w && (s2 > s || (s2 == s && q2 >= q))) return true;
-        const int I2 = op_row_block(w2, s2, q2), J2 = op_col_block(w2, s2, q2);
-        if ((I2 < J2 ? I2 : J2) == lo && (I2 < J2 ? J2 : I2) == hi) return false;
-      }
-  return true;
-}
-__host__ __device__ constexpr CoverOwnerTab op_owner_tab() {
-  CoverOwnerTab t{};
-  for (int w = 0; w < 4; w++)
-    for (int s = 0; s < 4; s++) {
-      unsigned char bits = 0;
-      for (int q = 0; q < 4; q++)
-        if (op_owner(w, s, q)) bits = (unsigned char)(bits | (1u << q));
-      t.m[w][s] = bits;
-    }
-  return t;
-}
-__device__ constexpr CoverOwnerTab kOpOwner = op_owner_tab();
-__host__ __device__ constexpr int op_pairs_owned() {
-  int n = 0;
-  for (int w = 0; w < 4; w++)
-    for (int s = 0; s < 4; s++)
-      for (int q = 0; q < 4; q++) n += op_owner(w, s, q) ? 1 : 0;
-  return n;
-}
-__host__ __device__ constexpr bool op_pairs_in_range() {
-  for (int w = 0; w < 4; w++)
-    for (int m = 0; m < 2; m++)
-      for (int q = 0; q < 4; q++)
-        if (kOpMaps[w][m][q] < 0 || kOpMaps[w][m][q] > 9) return false;
-  return true;
-}
-// every diagonal block must be owned by a loop unit (the single-chain trick is applied to slot kOpLoopSlot and to nothing else;
-// a diagonal block in a two-chain unit would be right too, but the count below is what proves the 10 diagonals are covered)
-__host__ __device__ constexpr int op_diagonals_in_loop_units() {
-  int n = 0;
-  for (int w = 0; w < 4; w++)
-    for (int q = 0; q < 4; q++) n += op_owner(w, kOpLoopSlot, q) ? 1 : 0;
-  return n;
-}
-static_assert(op_pairs_in_range() && op_pairs_owned() == 55, "the outer-product cover must own every block pair of the 10 x 10 upper triangle exactly once");
-static_assert(kOpUnits[kOpLoopSlot].rmap == kOpUnits[kOpLoopSlot].cmap && kOpUnits[kOpLoopSlot].rot == 0 && op_diagonals_in_loop_units() == 10,
-              "the loop unit is (m, m) unrotated and the loop units own all ten diagonal blocks");
-
-template <int R>
-__device__ __forceinline__ double rot_d(double v) {          // one double of a fragment, rotated like rot_blocks below
-  typedef int i2_t __attribute__((ext_vector_type(2)));
-  i2_t x = __builtin_bit_cast(i2_t, v), y;
-  y[0] = __builtin_amdgcn_mov_dpp(x[0], 0x120 + 4 * R, 0xf, 0xf, false);
-  y[1] = __builtin_amdgcn_mov_dpp(x[1], 0x120 + 4 * R, 0xf, 0xf, false);
-  return __builtin_bit_cast(double, y);
-}
-// the four 4-lane block groups of every 16-lane row rotated by R: lane of block q receives the lane of block q - R
-// (v_mov_b32 ... row_ror:4R: destination lane l reads lane (l - 4R) mod 16 of its row, tools/ubench/dpp_ror.hip)
-template <int R>
-__device__ __forceinline__ d2_t rot_blocks(d2_t v) {
-  if constexpr (R == 0) return v;
-  else {
-    typedef int i4_t __attribute__((ext_vector_type(4)));
-    i4_t x = __builtin_bit_cast(i4_t, v), y;
-#pragma unroll
-    for (int i = 0; i < 4; i++) y[i] = __builtin_amdgcn_mov_dpp(x[i], 0x120 + 4 * R, 0xf, 0xf, false);
-    return __builtin_bit_cast(d2_t, y);
-  }
-}
-
-template <int NB_, int NW_ = 4>      // NW: waves per workgroup (4: two workgroups per CU; 8: one problem per CU, see k_ode_sym)
+template <int NB_>
 struct SGeo {
   static constexpr int NB = NB_;
-  static constexpr int NW = NW_, NT = 64 * NW_;
+  static constexpr int NW = 4, NT = 64 * NW;       // waves per workgroup: two workgroups per CU
   static constexpr int P = 4 * NB;                 // padded to 4x4 blocks
   static constexpr int NSB = (NB + 1) / 2;         // 8x8 super-blocks per dimension
   static constexpr int KKE = 2 * NSB;              // k-steps (4 rows each), even
@@ -352,18 +232,18 @@ __host__ __device__ constexpr int unit_off(int p, int c) {
 }
 
 // row-pair items, column fastest over the threads: the HBM side of the state stores and of the backward operand staging
-template <int NB, int NW = 4>
+template <int NB>
 struct ItemTab {
-  static constexpr int NIT = SGeo<NB, NW>::NIT;
+  static constexpr int NIT = SGeo<NB>::NIT;
   int lo[NIT];          // unit offset inside a buffer, or -1
   unsigned g0[NIT];     // byte offset of element (2p, c) in a D x D matrix
   unsigned g1[NIT];     // ... of element (2p+1, c); = g0 when that row does not exist (the value is dropped)
   bool two[NIT];        // row 2p+1 exists
   bool st0[NIT], st1[NIT];   // the state store writes element (2p, c) / (2p+1, c): all that exist, or -- packed lower triangle -- c <= row
 };
-template <int NB, int NW>
-__device__ __forceinline__ void build_items(int D, int tid, ItemTab<NB, NW>& T, bool packed_lower = false) {
-  using g = SGeo<NB, NW>;
+template <int NB>
+__device__ __forceinline__ void build_items(int D, int tid, ItemTab<NB>& T, bool packed_lower = false) {
+  using g = SGeo<NB>;
 #pragma unroll
   for (int q = 0; q < g::NIT; q++) {
     const int e = tid + g::NT * q;
@@ -386,20 +266,20 @@ __device__ __forceinline__ void build_items(int D, int tid, ItemTab<NB, NW>& T, 
 
 // forward operand staging (operand = A^T: unit (sp, so) = A[so][2sp], A[so][2sp+1]) in 8 x 8 tiles: the 8 lanes of a
 // ds_write_b128 group store 8 consecutive columns of one row pair (conflict-free), a wave reads 8 rows x 128 contiguous bytes
-template <int NB, int NW = 4>
+template <int NB>
 struct TileTab {
-  static constexpr int NIT = SGeo<NB, NW>::NITF;
+  static constexpr int NIT = SGeo<NB>::NITF;
   int lo[NIT];
   unsigned g0[NIT], g1[NIT];   // byte offsets of A[so][2sp], A[so][2sp+1] (g1 = g0 when column 2sp+1 does not exist)
   bool two[NIT];
 };
-template <int NB, int NW>
-__device__ __forceinline__ void build_tiles(int D, int wave, int lane, TileTab<NB, NW>& T) {
-  using g = SGeo<NB, NW>;
+template <int NB>
+__device__ __forceinline__ void build_tiles(int D, int wave, int lane, TileTab<NB>& T) {
+  using g = SGeo<NB>;
   constexpr int nsot = cdiv(g::P, 8);
 #pragma unroll
   for (int q = 0; q < g::NITF; q++) {
-    const int tile = wave + NW * q;
+    const int tile = wave + g::NW * q;
     const int spt = tile / nsot, sot = tile - spt * nsot;
     const int sp = 8 * spt + (lane >> 3), so = 8 * sot + (lane & 7);
     const bool ok = 2 * sp < D && so < D;
@@ -419,13 +299,6 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 // use of ANY value loaded in the previous iteration becomes s_waitcnt vmcnt(0) -- it waits for every load and store issued so
 // far.  So a step issues all its HBM loads at ONE point (behind the staging of stage min(1, NS-1): A, the forcing terms, the
 // jumps of two steps ahead) and consumes them at ONE point (the rotation at the top of the next step, >= 1 stage later).
-// NW = 8 (round 4 experiment; fragment cover only; opt-in, see eight_waves()): ONE problem per CU on EIGHT waves -- wave w and wave w + 4 (same SIMD) split the four units
-// of cover wave w at its half-step boundary: units (a0, b0), (a0, b1) | units (a1, b0), (a1, b1).  Each wave multiplies 40 instead of
-// 70 products per stage (both chains of every unit: the loop units' single-chain trick would make the two halves different
-// instruction streams), owns half the elements and does half the chores, so the per-stage latency chain of a lone problem --
-// products, stepper, publish, barrier, first fragments: ~2 300 cycles with four waves -- loses most of its product share.  For
-// batches up to one problem per CU (the reference's own use case is ONE optimisation); larger batches keep two four-wave
-// workgroups per CU, whose 256 registers per wave an eight-wave workgroup pair cannot have.
 // HLP (round 4; fragment cover, four product waves): FOUR HELPER WAVES beside the four product waves of a problem, one of each per SIMD.
 // A wave issues one instruction at a time and an fp64 product holds its issue slot for all 16 cycles (a v_mov between two products costs
 // its full 8 cycles, tools/ubench/mfma_dpp_overlap.hip), so everything of a stage that is not the product -- the vector recursion,
@@ -450,7 +323,7 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 //            dt (Q S - u m^T) into the out-buffer
 // Q''_t never goes to HBM (-25.6 KB per grid point), the separate assembly kernel and its launch are gone.  Why a third wave and not
 // the helpers: a helper's stage is a chain of dependent LDS round trips as long as the product waves' stage (measured: the product
-// waves WAIT for the helpers in stages 0 and 1, tools/ubench/ode_gf_loop.hip), so everything added to it lengthened the step by what it
+// waves WAIT for the helpers in stages 0 and 1), so everything added to it lengthened the step by what it
 // took (first version of this round: +1.7 ms per 256-problem launch); the SIMD's third wave runs its own chain beside the two.
 constexpr int kGradA[3][4] = {{0, 1, 3, 2}, {4, 5, 7, 6}, {8, 9, 8, 9}};      // row-side maps (block rows of Q); column-side map s: (s, s, s+1, s+1) mod 10
 __host__ __device__ constexpr int grad_bmap(int s, int q) { return (s + (q >> 1)) % 10; }
@@ -480,7 +353,7 @@ static_assert(grad_cover_exact(), "the gradient product's units must cover every
 // (Q^T and S_t of the grid point under construction / of the one being multiplied), the out-buffer, dt u and m_t per set, lam_t
 template <int NB>
 struct GradLds {
-  using g = SGeo<NB, 4>;
+  using g = SGeo<NB>;
   static constexpr int QT = 0, S = 2 * g::XS, O = 4 * g::XS, U = O + g::PP * g::PP, M = U + 2 * g::PP, LAM = M + 2 * g::PP;
   static constexpr int DOUBLES = LAM + g::PP;
 };
@@ -502,7 +375,7 @@ struct GradLds {
 template <int NB>
 __device__ __forceinline__ void grad_waves(const OdeArgs& a, double* __restrict__ smem, const int tid) {
 #pragma clang fp contract(fast)
-  using g = SGeo<NB, 4>;
+  using g = SGeo<NB>;
   using gl = GradLds<NB>;
   constexpr int NT = 256, LD = g::LD, NKP = g::NKP, PP = g::PP;
   static_assert(NKP == 5 && g::NSB == 5, "the gradient product's units are laid out for 33 <= D <= 40");
@@ -739,53 +612,30 @@ __device__ __forceinline__ void grad_waves(const OdeArgs& a, double* __restrict_
   using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
   using I4 = std::integral_constant<int, 4>; using I5 = std::integral_constant<int, 5>;
 
-#ifndef VGPA_GF_ABL
-#define VGPA_GF_ABL 0                    // DIAGNOSTIC (wrong results; tools/ubench/ode_gf_loop.hip only): bit 0 no product, 1 no band, 2 no build, 3 no out
-#endif
-#ifdef VGPA_STAMPS_ROLE
-  long long ts_prev_ = clock64();
-#define VGPA_GF_BARRIER(j)                                                                                               \
-  { const long long tsb_ = clock64(); lds_barrier(); const long long tsa_ = clock64();                                   \
-    if (lane == 0 && wave == 0 && blockIdx.x == 0) { mfma::g_stamp_role[2][2 * (j)] += tsb_ - ts_prev_; mfma::g_stamp_role[2][2 * (j) + 1] += tsa_ - tsb_; } \
-    ts_prev_ = tsa_; }
-#else
-#define VGPA_GF_BARRIER(j) lds_barrier()
-#endif
-#ifndef VGPA_GF_PRIO_G
-#define VGPA_GF_PRIO_G 3                 // (this role's few instructions first: 4.87 -> 4.60 ms per sweep direction of one problem)
-#endif
+  constexpr int kPrio = 3;               // (this role's few instructions first: 4.87 -> 4.60 ms per sweep direction of one problem)
   // one backward step: HP / HP2 = a previous / a second-previous grid point exists (compile time: the first two steps are peeled)
   auto step = [&](int k, auto set_, auto hp_, auto hp2_) {
     constexpr int SET = decltype(set_)::value;
     constexpr bool HP = decltype(hp_)::value, HP2 = decltype(hp2_)::value;
     using CUR = std::integral_constant<int, SET>; using PRV = std::integral_constant<int, SET ^ 1>;
-#ifndef VGPA_GF_OUT_TICK
-#define VGPA_GF_OUT_TICK 0
-#endif
-#ifndef VGPA_GF_PRIO_LOW
-#define VGPA_GF_PRIO_LOW VGPA_GF_PRIO_G
-#endif
     opaque_tables();
-    if (VGPA_GF_PRIO_LOW != VGPA_GF_PRIO_G) __builtin_amdgcn_s_setprio(VGPA_GF_PRIO_G);
     if (HP) settle_loads();              // (the one place that waits for this role's HBM loads)
     // (scheduling barriers between the phases: interleaved, their operands do not fit the 168 registers of three waves per SIMD)
-    if (VGPA_GF_OUT_TICK == 0 && HP2 && !(VGPA_GF_ABL & 8)) out(tidx(k - 2));
+    if (HP2) out(tidx(k - 2));
     __builtin_amdgcn_sched_barrier(0);
-    if (!(VGPA_GF_ABL & 4)) build(CUR{});
+    build(CUR{});
     __builtin_amdgcn_sched_barrier(0);
-    if (HP && !(VGPA_GF_ABL & 1)) prod(PRV{}, I0{}, I1{});
-    VGPA_GF_BARRIER(0);
-    if (VGPA_GF_PRIO_LOW != VGPA_GF_PRIO_G) __builtin_amdgcn_s_setprio(VGPA_GF_PRIO_LOW);
-    if (!(VGPA_GF_ABL & 2)) band_u(CUR{}, tidx(k));
+    if (HP) prod(PRV{}, I0{}, I1{});
+    lds_barrier();
+    band_u(CUR{}, tidx(k));
     prefetch(tidx(k + 1));
     __builtin_amdgcn_sched_barrier(0);
-    if (HP && !(VGPA_GF_ABL & 1)) prod(PRV{}, I1{}, I2{});
-    VGPA_GF_BARRIER(1);
-    if (VGPA_GF_OUT_TICK == 2 && HP2 && !(VGPA_GF_ABL & 8)) { out(tidx(k - 2)); __builtin_amdgcn_sched_barrier(0); }
-    if (HP && !(VGPA_GF_ABL & 1)) prod(PRV{}, I2{}, I4{});
-    VGPA_GF_BARRIER(2);
-    if (HP) { if (!(VGPA_GF_ABL & 1)) prod(PRV{}, I4{}, I5{}); __builtin_amdgcn_sched_barrier(0); epilogue(PRV{}); }
-    VGPA_GF_BARRIER(3);
+    if (HP) prod(PRV{}, I1{}, I2{});
+    lds_barrier();
+    if (HP) prod(PRV{}, I2{}, I4{});
+    lds_barrier();
+    if (HP) { prod(PRV{}, I4{}, I5{}); __builtin_amdgcn_sched_barrier(0); epilogue(PRV{}); }
+    lds_barrier();
   };
   // behind the loop: the last grid point (Psi in stage buffer 0, the end point's operand in R, lam from the helpers' last vector update)
   auto drain = [&](auto set_) {
@@ -807,7 +657,7 @@ __device__ __forceinline__ void grad_waves(const OdeArgs& a, double* __restrict_
     out(tidx(n_steps));
   };
 
-  __builtin_amdgcn_s_setprio(VGPA_GF_PRIO_G);
+  __builtin_amdgcn_s_setprio(kPrio);
   __syncthreads();                       // LDS zero-filled (by the other roles)
   prefetch(tidx(0));
   settle_loads();
@@ -824,25 +674,20 @@ __device__ __forceinline__ void grad_waves(const OdeArgs& a, double* __restrict_
 
 // H2 (round 5; helper-wave kernels without GF): TWO helper roles -- 768 threads, three waves per SIMD.  A helper's stage is a chain of
 // dependent LDS round trips (partial sums -> stage vector -> partial products; start-point operand -> mid-point; stage state -> HBM)
-// about as long as the product waves' stage, and the product waves wait for it in stages 0 and 1 (tools/ubench/ode_gf_loop.hip).  The
+// about as long as the product waves' stage, and the product waves wait for it in stages 0 and 1.  The
 // vector recursion (role 1) and the operand staging / state stores / operand loads (role 2) share nothing but the barriers: side by
 // side each chain is shorter than the products.
-template <int METHOD, bool FWD, int NB, bool DENSEJ, int GR, int WPE, bool QOUT = false, int NW = 4, bool HLP = false, bool GF = false, bool H2 = false>   // WPE: waves per SIMD the register budget allows for
-__global__ void __attribute__((amdgpu_flat_work_group_size(64 * NW * ((GF || H2) ? 3 : (HLP ? 2 : 1)), 64 * NW * ((GF || H2) ? 3 : (HLP ? 2 : 1))), amdgpu_waves_per_eu(WPE, WPE))) k_ode_sym(OdeArgs a) {
+template <int METHOD, bool FWD, int NB, bool DENSEJ, int GR, int WPE, bool QOUT = false, bool HLP = false, bool GF = false, bool H2 = false>   // WPE: waves per SIMD the register budget allows for
+__global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3 : (HLP ? 2 : 1)), 256 * ((GF || H2) ? 3 : (HLP ? 2 : 1))), amdgpu_waves_per_eu(WPE, WPE))) k_ode_sym(OdeArgs a) {
 #pragma clang fp contract(fast)
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  using g = SGeo<NB, NW>;
-  constexpr bool W8 = (NW == 8);
+  using g = SGeo<NB>;
   constexpr int NT = g::NT;
-  constexpr int NS = n_stages<METHOD>(), NR = g::NR, MAXS = W8 ? 2 : g::MAXS, LD = g::LD, NKP = g::NKP;
-  constexpr bool COVER = (GR <= 0);      // fragment cover (NSB = 5) instead of runs: see kCoverMaps
-  constexpr bool OPC = (GR == -1);       // ... the outer-product cover (two maps per wave, rotated row sides): see kOpMaps
-  constexpr bool LOOP1 = COVER && (OPC || VGPA_SYM_LOOP1) && !W8;      // single-chain loop units: see kCoverLoopSlot
-  constexpr int LSLOT = OPC ? kOpLoopSlot : kCoverLoopSlot;
-  static_assert(!OPC || !W8, "the outer-product cover runs on four waves");
+  constexpr int NS = n_stages<METHOD>(), NR = g::NR, MAXS = g::MAXS, LD = g::LD, NKP = g::NKP;
+  constexpr bool COVER = (GR == 0);      // fragment cover (NSB = 5) instead of runs: see kCoverMaps
+  // the cover's loop units (diagonal blocks) run one chain + an in-block transpose: see kCoverLoopSlot
   static_assert(!COVER || (g::NSB == 5 && g::MAXS == 4), "the fragment cover is built for 33 <= D <= 40");
-  static_assert(!W8 || COVER, "eight waves per problem: fragment-cover kernels only");
-  static_assert(!HLP || (COVER && NW == 4), "helper waves: fragment-cover kernels on four product waves");
+  static_assert(!HLP || COVER, "helper waves: fragment-cover kernels");
   static_assert(!GF || (HLP && QOUT && !FWD && !DENSEJ && METHOD == VGPA_ODE_RK4), "fused gradient assembly: backward RK4 helper-wave kernels with Q'' on");
   static_assert(!H2 || (HLP && !GF), "two helper roles: helper-wave kernels without the gradient waves");
   constexpr int NITS = FWD ? g::NITF : g::NIT;     // staging items per thread
@@ -850,15 +695,12 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(64 * NW * ((GF || H2)
   // the stage whose chores end with the requests for A_{t+2}, c_{t+2} (consumed at the top of the next step).  Helper-wave RK4 kernels:
   // the last stage -- same box, one problem: 7.82 -> 7.39 ms per sweep (forward 3.74 -> 3.43, backward 3.99 -> 3.87), the fused
   // backward kernel 9.77 -> 9.6 ms per 512 problems; the four-wave kernels (two workgroups per CU) measured no difference and keep JSEC
-#ifndef VGPA_SYM_LOADA_STAGE
-#define VGPA_SYM_LOADA_STAGE 3
-#endif
-  constexpr int LSTG = (NS == 4 && HLP) ? VGPA_SYM_LOADA_STAGE : JSEC;
+  constexpr int LSTG = (NS == 4 && HLP) ? 3 : JSEC;
   constexpr double sixth = 1.0 / 6.0;
-  const int role = HLP ? (int)threadIdx.x / (64 * NW) : 0;     // (wave-uniform) 0: products; 1: helper -- the chores of product wave `wave` (H2: its vector recursion); 2: gradient assembly (GF) / operand staging and state stores (H2)
+  const int role = HLP ? (int)threadIdx.x / NT : 0;     // (wave-uniform) 0: products; 1: helper -- the chores of product wave `wave` (H2: its vector recursion); 2: gradient assembly (GF) / operand staging and state stores (H2)
   const bool helper = role >= 1;
-  const int tid = (int)threadIdx.x - role * 64 * NW, lane = tid & 63, wave = tid >> 6;
-  const int wq = wave & 3, half = W8 ? (wave >> 2) : 0;      // cover wave whose units this wave multiplies; which half of them (W8)
+  const int tid = (int)threadIdx.x - role * NT, lane = tid & 63, wave = tid >> 6;
+  const int wq = wave & 3;               // cover wave whose units this wave multiplies
   const int prob = (int)blockIdx.x;
   const int D = a.D, Np = a.Np, DD = a.D * a.D, n_steps = a.Np - 1;
   const double dt = a.dt, h = 0.5 * a.dt;
@@ -867,14 +709,14 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(64 * NW * ((GF || H2)
   double* const Rb = Xb1 + g::XS;
   double* const Mb = Rb + g::XS;
   double* const xvw = Mb + g::XS + wave * g::XV;           // this wave's copy of the stage vector
-  double* const pvb = Mb + g::XS + NW * g::XV;             // [2][NPART][PP] partial inner products
+  double* const pvb = Mb + g::XS + g::NW * g::XV;             // [2][NPART][PP] partial inner products
   double* const trash = pvb + 2 * g::PV + 2 * tid;         // one 16-byte unit per thread
   // GF: the gradient waves (third set of four; grad_waves below) share nothing with this code but the barriers, the buffers they read
   // and lam_t, which the helpers leave for them
   using gl = GradLds<NB>;
   constexpr int GLDS = GF ? gl::DOUBLES : 0;
   if constexpr (GF) {
-    if (role == 2) { grad_waves<NB>(a, smem, (int)threadIdx.x - 2 * 64 * NW); return; }
+    if (role == 2) { grad_waves<NB>(a, smem, (int)threadIdx.x - 2 * NT); return; }
   }
   double* const gLam = smem + g::LDS_DOUBLES + gl::LAM;
   for (int i = tid; i < (int)g::LDS_DOUBLES + GLDS; i += NT) smem[i] = 0.0;
@@ -891,20 +733,18 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(64 * NW * ((GF || H2)
   int colm[4] = {0, 0, 0, 0};            // cover: LDS column offset of this lane's fragment element, per map
   unsigned gofs[MAXS];
   bool own[MAXS], wd[MAXS], wm[MAXS];
-  const int cov_used = OPC ? 0xF : (COVER ? kCoverUsed[wq] : 0);
+  const int cov_used = COVER ? kCoverUsed[wq] : 0;
   const bool loop_diag = r4 == c4;                     // diagonal element of a diagonal block (loop unit)
   const int loop_src = 16 * c4 + 4 * bq + r4;          // the lane that holds element (c4, r4) of the same block
   if constexpr (COVER) {
 #pragma unroll
-    for (int m = 0; m < 4; m++) colm[m] = 2 * ((4 * (OPC ? kOpMaps[wq][m & 1][bq] : kCoverMaps[wq][m][bq]) + c4) ^ r4);
+    for (int m = 0; m < 4; m++) colm[m] = 2 * ((4 * kCoverMaps[wq][m][bq] + c4) ^ r4);
 #pragma unroll
     for (int s = 0; s < MAXS; s++) {
-      const int so = W8 ? 2 * half + s : s;                       // unit slot of the cover wave
-      const int Ib = OPC ? kOpMaps[wq][kOpUnits[so].rmap][(bq - kOpUnits[so].rot) & 3] : kCoverMaps[wq][kCoverPat[so][0]][bq];
-      const int Jb = OPC ? kOpMaps[wq][kOpUnits[so].cmap][bq] : kCoverMaps[wq][kCoverPat[so][1]][bq];
+      const int Ib = kCoverMaps[wq][kCoverPat[s][0]][bq], Jb = kCoverMaps[wq][kCoverPat[s][1]][bq];
       const int row = 4 * Ib + r4, col = 4 * Jb + c4;
-      const bool first = ((OPC ? kOpOwner.m[wq][so] : kCoverOwner.m[wq][so]) >> bq) & 1u;      // (a compile-time table, looked up with the run-time wave / block)
-      const bool act = ((cov_used >> so) & 1) && first && (Ib != Jb || row <= col);     // diagonal blocks: the upper half represents
+      const bool first = (kCoverOwner.m[wq][s] >> bq) & 1u;      // (a compile-time table, looked up with the run-time wave / block)
+      const bool act = ((cov_used >> s) & 1) && first && (Ib != Jb || row <= col);     // diagonal blocks: the upper half represents
       offD[s] = elem_off<NB>(row, col);
       offM[s] = elem_off<NB>(col, row);
       wd[s] = act;
@@ -946,27 +786,19 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(64 * NW * ((GF || H2)
   }
   const bool spk = FWD && a.s_packed;                       // S_t leaves as its packed lower triangle (OdeArgs::s_packed)
   const int MS = spk ? D * (D + 1) / 2 : DD;                // doubles per stored matrix
-  ItemTab<NB, NW> IT;
-  build_items<NB, NW>(D, tid, IT, spk);
-  TileTab<NB, NW> TT;
-  if (FWD) build_tiles<NB, NW>(D, wave, lane, TT);
+  ItemTab<NB> IT;
+  build_items<NB>(D, tid, IT, spk);
+  TileTab<NB> TT;
+  if (FWD) build_tiles<NB>(D, wave, lane, TT);
 
   // ---- operand staging --------------------------------------------------------------------------------------------------
   const double* A = a.A + (size_t)prob * a.strideA;
   d2_t an[NITS];
-#ifndef VGPA_SYM_LOADA_NT
-#define VGPA_SYM_LOADA_NT 0
-#endif
   auto load_a = [&](const double* At) {
 #pragma unroll
     for (int q = 0; q < NITS; q++) {
-      if (VGPA_SYM_LOADA_NT) {
-        an[q][0] = __builtin_nontemporal_load(reinterpret_cast<const double*>(reinterpret_cast<const char*>(At) + (FWD ? TT.g0[q] : IT.g0[q])));
-        an[q][1] = __builtin_nontemporal_load(reinterpret_cast<const double*>(reinterpret_cast<const char*>(At) + (FWD ? TT.g1[q] : IT.g1[q])));
-      } else {
       an[q][0] = ldg(At, FWD ? TT.g0[q] : IT.g0[q]);
       an[q][1] = ldg(At, FWD ? TT.g1[q] : IT.g1[q]);
-      }
     }
   };
   auto unit_ptr = [&](double* buf, int q) -> d2_t* {
@@ -1035,11 +867,9 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(64 * NW * ((GF || H2)
 
   // S_k / Psi_t and m_k / lam_t of grid point t to HBM: the matrix from the stage buffer that holds it
   auto store_vector = [&](int t) {
-    if (VGPA_ABL_NOSTORE && t > 1) return;
     if (wave == 0 && vl) stg(vout + vec(t), lane8, vk);
   };
   auto store_items = [&](const d2_t (&v)[g::NIT], int t, bool with_vector = true) {
-    if (VGPA_ABL_NOSTORE && t > 1) return;
     double* so = mout + (size_t)t * MS;
 #pragma unroll
     for (int q = 0; q < g::NIT; q++) {
@@ -1055,25 +885,21 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(64 * NW * ((GF || H2)
 
   // every HBM load of a step, issued together (see "Memory waits"): what the step after the next one needs
   auto prefetch = [&](int step, auto helper_role) {
-#ifndef VGPA_ABL_NOLOAD
-#define VGPA_ABL_NOLOAD 0                // DIAGNOSTIC (wrong results; ubench only): behind the second step no loads of 1: A_t, c_t  2: G_t  4: jumps  8: obs index
-#endif
-    const bool late = step > 1;
     // role kind: 0 = product waves beside helpers (G_t), 1 = every chore (the one helper role; without helpers: everything),
     //            2 = the vector recursion's helper (H2), 3 = the staging helper (H2)
     constexpr int HK = decltype(helper_role)::value;
     constexpr bool ch_a = !HLP || HK == 1 || HK == 3, ch_v = !HLP || HK == 1 || HK == 2, units = !HLP || HK == 0;
-    if (!((VGPA_ABL_NOLOAD & 1) && late) && LSTG == JSEC) {
+    if (LSTG == JSEC) {
       if (ch_a) load_a(A + (size_t)tclamp(step + 2) * DD);
       if (ch_v) c2 = ldg(cin + vec(tclamp(step + 2)), lane8);
     }
     if (!FWD) {
-      if (units && !((VGPA_ABL_NOLOAD & 2) && late)) {
+      if (units) {
 #pragma unroll
         for (int s = 0; s < MAXS; s++) fnn[s] = ldg(G + (size_t)tclamp(step + 2) * GS, gofs[s]);
       }
-      if (ch_v && !((VGPA_ABL_NOLOAD & 4) && late)) jm_next = step + 2 <= n_steps ? jump_vector(tidx(step + 2), n_obs_next) : 0.0;
-      if (!((VGPA_ABL_NOLOAD & 8) && late)) n_obs_nn = (sparse_j && step + 3 <= n_steps) ? ldu(a.obs_idx, tidx(step + 3)) : -1;
+      if (ch_v) jm_next = step + 2 <= n_steps ? jump_vector(tidx(step + 2), n_obs_next) : 0.0;
+      n_obs_nn = (sparse_j && step + 3 <= n_steps) ? ldu(a.obs_idx, tidx(step + 3)) : -1;
     }
   };
 
@@ -1259,7 +1085,7 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(64 * NW * ((GF || H2)
   // the group boundary (the next group's first fragments are on their way while this group's stepper runs) and across the
   // STAGE boundary: product_begin requests step 0 of the next stage right behind the barrier, in front of the vector work.
   constexpr int GRR = COVER ? 1 : GR;            // (array extents of the run layout; unused under the cover)
-  constexpr int NG = COVER ? 1 : cdiv(NR, GRR), NSL = COVER ? (W8 ? 2 : 4) : 2 * GRR, NSTEP = NG * NKP;
+  constexpr int NG = COVER ? 1 : cdiv(NR, GRR), NSL = COVER ? 4 : 2 * GRR, NSTEP = NG * NKP;
   static_assert(COVER || NR % GRR == 0, "a group of runs must be complete (the clamped tail group is not parity-clean)");
   d2_t fa1[2][GRR], fa2[2][GRR], fb1[2][COVER ? 1 : NSL], fb2[2][COVER ? 1 : NSL];
   // cover: fragments of the row-side maps a0, a1 (ONE buffer each: a0 is dead behind the first half of a step, a1 is not needed
@@ -1267,37 +1093,11 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(64 * NW * ((GF || H2)
   // (HALF, backward: 48 fragment registers.  The forward kernel, whose lanes carry no G_t / G_{t-1}, can afford two buffers of
   // all four maps -- 64 registers, one block of eight reads per step -- and measured faster that way: 8.06 vs 8.36 ms per
   // 512-problem launch; the backward kernel spilled 22 registers with it and ran at 9.6 ms instead of 8.95.)
-#ifndef VGPA_SYM_HALF_FWD
-#define VGPA_SYM_HALF_FWD 0
-#endif
-#ifndef VGPA_SYM_HALF_BWD
-#define VGPA_SYM_HALF_BWD 1
-#endif
-  #ifndef VGPA_SYM_HALF_HLP
-#define VGPA_SYM_HALF_HLP 0            // helper-wave kernels: the product waves have the registers for two buffers of all four maps, backward too
-#endif
-  constexpr bool HALF = COVER && !OPC && !W8 && (HLP ? VGPA_SYM_HALF_HLP : (FWD ? VGPA_SYM_HALF_FWD : VGPA_SYM_HALF_BWD));
-  // W8: three maps per wave -- row side a0 (first half) or a1 (second half), column side b0, b1 -- of both operands, two buffers
-  d2_t fA8[2][W8 ? 3 : 1], fX8[2][W8 ? 3 : 1];
-  const int col8[3] = {half ? colm[1] : colm[0], colm[2], colm[3]};
-  auto frag8 = [&](int buf, int kp, const double* pa, const double* px) {
-#pragma unroll
-    for (int m = 0; m < 3; m++) {
-      fA8[buf][m] = *reinterpret_cast<const d2_t*>(pa + kp * 4 * LD + col8[m]);
-      fX8[buf][m] = *reinterpret_cast<const d2_t*>(px + kp * 4 * LD + col8[m]);
-    }
-  };
-  d2_t fAa[COVER ? 2 : 1], fXa[COVER ? 2 : 1], fAb[2][COVER ? 2 : 1], fXb[2][COVER ? 2 : 1];
-  d2_t fAa1[2], fXa1[2];                 // HALF + interleave: map a1 in two buffers (read half a step earlier than it is free)
-  d2_t fA[2][(COVER && !OPC && !HALF && !W8) ? 4 : 1], fX[2][(COVER && !OPC && !HALF && !W8) ? 4 : 1];
-  d2_t foA[2][2], foX[2][2];             // outer-product cover: maps P, Q of both operand buffers, two pipeline buffers
-  auto frag_op = [&](int buf, int kp, const double* pa, const double* px) {
-#pragma unroll
-    for (int m = 0; m < 2; m++) {
-      foA[buf][m] = *reinterpret_cast<const d2_t*>(pa + kp * 4 * LD + colm[m]);
-      foX[buf][m] = *reinterpret_cast<const d2_t*>(px + kp * 4 * LD + colm[m]);
-    }
-  };
+  // (Helper-wave kernels: the product waves have the registers for two buffers of all four maps, backward too.)
+  constexpr bool HALF = COVER && !HLP && !FWD;
+  d2_t fAa, fXa, fAb[2][COVER ? 2 : 1], fXb[2][COVER ? 2 : 1];
+  d2_t fAa1[2], fXa1[2];                 // HALF: map a1 in two buffers (read half a step earlier than it is free)
+  d2_t fA[2][(COVER && !HALF) ? 4 : 1], fX[2][(COVER && !HALF) ? 4 : 1];
   auto frag_all = [&](int buf, int kp, const double* pa, const double* px) {
 #pragma unroll
     for (int m = 0; m < 4; m++) {
@@ -1305,9 +1105,9 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(64 * NW * ((GF || H2)
       fX[buf][m] = *reinterpret_cast<const d2_t*>(px + kp * 4 * LD + colm[m]);
     }
   };
-  auto frag_a = [&](int m, int kp, const double* pa, const double* px) {
-    fAa[m] = *reinterpret_cast<const d2_t*>(pa + kp * 4 * LD + colm[m]);
-    fXa[m] = *reinterpret_cast<const d2_t*>(px + kp * 4 * LD + colm[m]);
+  auto frag_a0 = [&](int kp, const double* pa, const double* px) {
+    fAa = *reinterpret_cast<const d2_t*>(pa + kp * 4 * LD + colm[0]);
+    fXa = *reinterpret_cast<const d2_t*>(px + kp * 4 * LD + colm[0]);
   };
   auto frag_a1 = [&](int buf, int kp, const double* pa, const double* px) {
     fAa1[buf] = *reinterpret_cast<const d2_t*>(pa + kp * 4 * LD + colm[1]);
@@ -1324,15 +1124,10 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(64 * NW * ((GF || H2)
     if constexpr (COVER) {
       // (only the first step of a stage comes through here: every other fragment is requested inside the step before it)
       const int kp = t % NKP;
-      if constexpr (OPC) {
-        frag_op(buf, kp, pa, px);
-      } else if constexpr (W8) {
-        frag8(buf, kp, pa, px);
-      } else if constexpr (HALF) {
-        frag_a(0, kp, pa, px);
+      if constexpr (HALF) {
+        frag_a0(kp, pa, px);
         frag_b(buf, kp, pa, px);
-        if (VGPA_SYM_INTERLEAVE) frag_a1(buf, kp, pa, px);
-        else frag_a(1, kp, pa, px);
+        frag_a1(buf, kp, pa, px);
       } else {
         frag_all(buf, kp, pa, px);
       }
@@ -1354,9 +1149,6 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(64 * NW * ((GF || H2)
   };
   auto product_begin = [&](const double* Aop, const double* Xc) {
     frag_load(0, 0, Aop + r4 * LD, Xc + r4 * LD);
-#if VGPA_ABL_NOFRAG
-    if constexpr (COVER) frag_load(1, 1, Aop + r4 * LD, Xc + r4 * LD);
-#endif
   };
 
   // products (their step-0 fragments are in flight) + stepper + publish of stage j
@@ -1395,7 +1187,7 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(64 * NW * ((GF || H2)
             else if (METHOD == VGPA_ODE_RK2) f = j == 0 ? fc[s] : 0.5 * (fn[s] + fc[s]);
             else f = j == 0 ? fc[s] : (j == 3 ? fn[s] : 0.5 * (fn[s] + fc[s]));
             f = own[s] ? -f : 0.0;
-            if (LOOP1 && s == LSLOT) f = loop_diag ? 0.5 * f : f;     // (the in-block transpose below adds the diagonal to itself)
+            if (COVER && s == kCoverLoopSlot) f = loop_diag ? 0.5 * f : f;     // (the in-block transpose below adds the diagonal to itself)
           }
           w[u] = f;
         }
@@ -1413,87 +1205,20 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(64 * NW * ((GF || H2)
         // then X^T A of the first k-step of the pair, then of the second): same bits.  Straight-line code: a branch inside the
         // pipeline would end the scheduling region (the rectangle wave multiplies its unused fourth unit too; the triangle waves
         // read map a1 twice -- the LDS array is not what bounds this kernel, the exposed latency of its reads was).
-        if constexpr (OPC) {
-          // outer-product cover: the four reads of the next step between this step's fourteen products; the row sides of the
-          // rotated units come out of the fragments by DPP moves (kOpUnits)
-          // Pinned order (the scheduler, left alone, rotates every fragment at the top of the step -- behind a wait for the LAST
-          // read of the step before): the loop unit and the unrotated unit first, a rotation right in front of the product that
-          // needs it, the four reads of the next step behind the first four products.  Per unit the products keep the order
-          // A^T X, X^T A of the first k-step, then of the second.
-          static_assert(kOpUnits[0].rmap == 0 && kOpUnits[0].cmap == 0 && kOpUnits[1].rmap == 0 && kOpUnits[1].rot == 1 && kOpUnits[1].cmap == 0 &&
-                        kOpUnits[2].rmap == 1 && kOpUnits[2].rot == 1 && kOpUnits[2].cmap == 1 && kOpUnits[3].rmap == 0 && kOpUnits[3].rot == 0 &&
-                        kOpUnits[3].cmap == 1, "the product order below is written for the units (P,P) (rot1 P,P) (rot1 Q,Q) (P,Q)");
-          const bool more = t + 1 < NSTEP && !VGPA_ABL_NOFRAG;
-          const int kn = (t + 1) % NKP, nb = cur ^ 1;
-          const d2_t PA = foA[cur][0], PX = foX[cur][0], QA = foA[cur][1], QX = foX[cur][1];
-          auto SB = [] { if (VGPA_SYM_OP_PIN) __builtin_amdgcn_sched_barrier(0); };
-          auto MF = [&](int u, double ra, double rb) { w[u] = __builtin_amdgcn_mfma_f64_4x4x4f64(ra, rb, w[u], 0, 0, 0); };
-          double rPA[2], rPX[2], rQA[2], rQX[2];
+        if constexpr (!HALF) {
+          // forward: unit u = (row-side map u >> 1, column-side map 2 + (u & 1)); the next step's eight reads BETWEEN this
+          // step's products, one read behind every second product: a block of eight ds_read_b128 takes the LDS queue ~100
+          // cycles to accept when eight waves of the CU do the same, and an in-order wave that sits in it issues no products
+          // meanwhile
           __builtin_amdgcn_sched_barrier(0);
-          MF(0, PA[0], PX[0]); rPA[0] = rot_d<1>(PA[0]);
-          if (more) foA[nb][0] = *reinterpret_cast<const d2_t*>(pa + kn * 4 * LD + colm[0]);
-          SB();
-          MF(0, PA[1], PX[1]); rPX[0] = rot_d<1>(PX[0]);
-          if (more) foX[nb][0] = *reinterpret_cast<const d2_t*>(px + kn * 4 * LD + colm[0]);
-          SB();
-          MF(1, rPA[0], PX[0]); rPA[1] = rot_d<1>(PA[1]);
-          if (more) foX[nb][1] = *reinterpret_cast<const d2_t*>(px + kn * 4 * LD + colm[1]);
-          SB();
-          MF(3, PA[0], QX[0]); rPX[1] = rot_d<1>(PX[1]);
-          if (more) foA[nb][1] = *reinterpret_cast<const d2_t*>(pa + kn * 4 * LD + colm[1]);
-          SB();
-          MF(1, rPX[0], PA[0]); rQA[0] = rot_d<1>(QA[0]);
-          SB();
-          MF(3, PX[0], QA[0]); rQX[0] = rot_d<1>(QX[0]);
-          SB();
-          MF(1, rPA[1], PX[1]); rQA[1] = rot_d<1>(QA[1]);
-          SB();
-          MF(2, rQA[0], QX[0]); rQX[1] = rot_d<1>(QX[1]);
-          SB();
-          MF(3, PA[1], QX[1]);
-          MF(2, rQX[0], QA[0]);
-          MF(1, rPX[1], PA[1]);
-          MF(3, PX[1], QA[1]);
-          MF(2, rQA[1], QX[1]);
-          SB();
-          MF(2, rQX[1], QA[1]);
-          __builtin_amdgcn_sched_barrier(0);
-        } else if constexpr (W8) {
-          // eight waves: unit u = (this half's row-side map, column-side map b_u), both chains; the six reads of the next step
-          // between the eight products
-          __builtin_amdgcn_sched_barrier(0);
-          if (t + 1 < NSTEP) frag8(cur ^ 1, (t + 1) % NKP, pa, px);
-#pragma unroll
-          for (int hh = 0; hh < 2; hh++) {
-#pragma unroll
-            for (int u = 0; u < 2; u++) w[u] = __builtin_amdgcn_mfma_f64_4x4x4f64(fA8[cur][0][hh], fX8[cur][1 + u][hh], w[u], 0, 0, 0);
-#pragma unroll
-            for (int u = 0; u < 2; u++) w[u] = __builtin_amdgcn_mfma_f64_4x4x4f64(fX8[cur][0][hh], fA8[cur][1 + u][hh], w[u], 0, 0, 0);
-          }
-          if (t + 1 < NSTEP) {
-#pragma unroll
-            for (int i = 0; i < 6; i++) {
-              __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);     // one matrix-core product
-              __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);     // one LDS read
-            }
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        } else if constexpr (!HALF) {
-          // forward: unit u = (row-side map u >> 1, column-side map 2 + (u & 1)); eight products, the eight reads of the next
-          // step, eight products
-#if VGPA_SYM_INTERLEAVE
-          // the next step's eight reads BETWEEN this step's sixteen products, one read behind every second product: a block of
-          // eight ds_read_b128 takes the LDS queue ~100 cycles to accept when eight waves of the CU do the same, and an in-order
-          // wave that sits in it issues no products meanwhile
-          __builtin_amdgcn_sched_barrier(0);
-          if (t + 1 < NSTEP && !VGPA_ABL_NOFRAG) frag_all(cur ^ 1, (t + 1) % NKP, pa, px);
+          if (t + 1 < NSTEP) frag_all(cur ^ 1, (t + 1) % NKP, pa, px);
 #pragma unroll
           for (int hh = 0; hh < 2; hh++) {
 #pragma unroll
             for (int u = 0; u < 4; u++) w[u] = __builtin_amdgcn_mfma_f64_4x4x4f64(fA[cur][u >> 1][hh], fX[cur][2 + (u & 1)][hh], w[u], 0, 0, 0);
 #pragma unroll
             for (int u = 0; u < 4; u++)
-              if (!(LOOP1 && u == kCoverLoopSlot)) w[u] = __builtin_amdgcn_mfma_f64_4x4x4f64(fX[cur][u >> 1][hh], fA[cur][2 + (u & 1)][hh], w[u], 0, 0, 0);
+              if (u != kCoverLoopSlot) w[u] = __builtin_amdgcn_mfma_f64_4x4x4f64(fX[cur][u >> 1][hh], fA[cur][2 + (u & 1)][hh], w[u], 0, 0, 0);
           }
           if (t + 1 < NSTEP) {
 #pragma unroll
@@ -1502,40 +1227,23 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(64 * NW * ((GF || H2)
               __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);     // one LDS read
             }
 #pragma unroll
-            for (int i = 0; i < 2; i++) {                            // (14 products per step with single-chain loop units, 16 without)
-              if constexpr (LOOP1) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-              else __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+            for (int i = 0; i < 2; i++) {                            // (14 products per step: single-chain loop unit)
+              __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
               __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
             }
           }
           __builtin_amdgcn_sched_barrier(0);
-#else
-#pragma unroll
-          for (int hh = 0; hh < 2; hh++) {
-#pragma unroll
-            for (int u = 0; u < 4; u++) w[u] = __builtin_amdgcn_mfma_f64_4x4x4f64(fA[cur][u >> 1][hh], fX[cur][2 + (u & 1)][hh], w[u], 0, 0, 0);
-#pragma unroll
-            for (int u = 0; u < 4; u++)
-              if (!(LOOP1 && u == kCoverLoopSlot)) w[u] = __builtin_amdgcn_mfma_f64_4x4x4f64(fX[cur][u >> 1][hh], fA[cur][2 + (u & 1)][hh], w[u], 0, 0, 0);
-            if (hh == 0) {
-              __builtin_amdgcn_sched_barrier(0);
-              if (t + 1 < NSTEP) frag_all(cur ^ 1, (t + 1) % NKP, pa, px);
-              __builtin_amdgcn_sched_barrier(0);
-            }
-          }
-#endif
         } else {
-#if VGPA_SYM_INTERLEAVE
           // backward: first half = units (a0, b0), (a0, b1) with the next step's b0, b1, a1 reads between the products (a1 in
           // two buffers: 56 fragment registers), second half = units (a1, b0), (a1, b1) with the next step's a0 reads
           __builtin_amdgcn_sched_barrier(0);
-          if (t + 1 < NSTEP && !VGPA_ABL_NOFRAG) { frag_b(cur ^ 1, (t + 1) % NKP, pa, px); frag_a1(cur ^ 1, (t + 1) % NKP, pa, px); }
+          if (t + 1 < NSTEP) { frag_b(cur ^ 1, (t + 1) % NKP, pa, px); frag_a1(cur ^ 1, (t + 1) % NKP, pa, px); }
 #pragma unroll
           for (int hh = 0; hh < 2; hh++) {
 #pragma unroll
-            for (int m = 0; m < 2; m++) w[m] = __builtin_amdgcn_mfma_f64_4x4x4f64(fAa[0][hh], fXb[cur][m][hh], w[m], 0, 0, 0);
+            for (int m = 0; m < 2; m++) w[m] = __builtin_amdgcn_mfma_f64_4x4x4f64(fAa[hh], fXb[cur][m][hh], w[m], 0, 0, 0);
 #pragma unroll
-            for (int m = 0; m < 2; m++) w[m] = __builtin_amdgcn_mfma_f64_4x4x4f64(fXa[0][hh], fAb[cur][m][hh], w[m], 0, 0, 0);
+            for (int m = 0; m < 2; m++) w[m] = __builtin_amdgcn_mfma_f64_4x4x4f64(fXa[hh], fAb[cur][m][hh], w[m], 0, 0, 0);
           }
           if (t + 1 < NSTEP) {
 #pragma unroll
@@ -1545,19 +1253,12 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(64 * NW * ((GF || H2)
             }
           }
           __builtin_amdgcn_sched_barrier(0);
-          if (t + 1 < NSTEP && !VGPA_ABL_NOFRAG) frag_a(0, (t + 1) % NKP, pa, px);
+          if (t + 1 < NSTEP) frag_a0((t + 1) % NKP, pa, px);
 #pragma unroll
-          for (int hh = 0; hh < 2; hh++) {
-            if constexpr (LOOP1) {       // loop unit (slot 2): one chain; slot 3's two products are kept apart (dependent accumulator)
-              w[3] = __builtin_amdgcn_mfma_f64_4x4x4f64(fAa1[cur][hh], fXb[cur][1][hh], w[3], 0, 0, 0);
-              w[2] = __builtin_amdgcn_mfma_f64_4x4x4f64(fAa1[cur][hh], fXb[cur][0][hh], w[2], 0, 0, 0);
-              w[3] = __builtin_amdgcn_mfma_f64_4x4x4f64(fXa1[cur][hh], fAb[cur][1][hh], w[3], 0, 0, 0);
-            } else {
-#pragma unroll
-              for (int m = 0; m < 2; m++) w[2 + m] = __builtin_amdgcn_mfma_f64_4x4x4f64(fAa1[cur][hh], fXb[cur][m][hh], w[2 + m], 0, 0, 0);
-#pragma unroll
-              for (int m = 0; m < 2; m++) w[2 + m] = __builtin_amdgcn_mfma_f64_4x4x4f64(fXa1[cur][hh], fAb[cur][m][hh], w[2 + m], 0, 0, 0);
-            }
+          for (int hh = 0; hh < 2; hh++) {      // loop unit (slot 2): one chain; slot 3's two products are kept apart (dependent accumulator)
+            w[3] = __builtin_amdgcn_mfma_f64_4x4x4f64(fAa1[cur][hh], fXb[cur][1][hh], w[3], 0, 0, 0);
+            w[2] = __builtin_amdgcn_mfma_f64_4x4x4f64(fAa1[cur][hh], fXb[cur][0][hh], w[2], 0, 0, 0);
+            w[3] = __builtin_amdgcn_mfma_f64_4x4x4f64(fXa1[cur][hh], fAb[cur][1][hh], w[3], 0, 0, 0);
           }
           if (t + 1 < NSTEP) {
             __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
@@ -1566,25 +1267,6 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(64 * NW * ((GF || H2)
             __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
           }
           __builtin_amdgcn_sched_barrier(0);
-#else
-#pragma unroll
-        for (int half = 0; half < 2; half++) {
-#pragma unroll
-          for (int hh = 0; hh < 2; hh++) {
-#pragma unroll
-            for (int m = 0; m < 2; m++) w[2 * half + m] = __builtin_amdgcn_mfma_f64_4x4x4f64(fAa[half][hh], fXb[cur][m][hh], w[2 * half + m], 0, 0, 0);
-#pragma unroll
-            for (int m = 0; m < 2; m++)
-              if (!(LOOP1 && 2 * half + m == kCoverLoopSlot)) w[2 * half + m] = __builtin_amdgcn_mfma_f64_4x4x4f64(fXa[half][hh], fAb[cur][m][hh], w[2 * half + m], 0, 0, 0);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-          if (t + 1 < NSTEP) {
-            frag_a(half, (t + 1) % NKP, pa, px);
-            if (half == 0) frag_b(cur ^ 1, (t + 1) % NKP, pa, px);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        }
-#endif
         }
       } else {
 #pragma unroll
@@ -1597,8 +1279,8 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(64 * NW * ((GF || H2)
       }
       chore(t);                          // everything of the stage that is not the product rides between the products
       if (kp == NKP - 1) {
-        if constexpr (LOOP1) {           // Z = M + M^T - F on the diagonal blocks: element (r4, c4) of a block adds element (c4, r4)
-          w[LSLOT] += __shfl(w[LSLOT], loop_src, 64);
+        if constexpr (COVER) {           // Z = M + M^T - F on the diagonal blocks: element (r4, c4) of a block adds element (c4, r4)
+          w[kCoverLoopSlot] += __shfl(w[kCoverLoopSlot], loop_src, 64);
         }
 #pragma unroll
         for (int u = 0; u < NSL; u++) {
@@ -1624,7 +1306,6 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(64 * NW * ((GF || H2)
     return op == OP_X ? xcur(k, j) : (op == OP_M ? Mb : Rb);
   };
   if (role == 0) product_begin(aop(0, 0, true), xcur(0, 0));
-  VGPA_STAMP_DECL;
   // Chores between the products (round 3).  Nothing of a stage but the stepper depends on the stage's product, so everything
   // else is issued INSIDE the product pipeline, where its LDS and HBM latencies run under matrix-core work instead of behind it
   // (an in-order wave that does them after the products pays every round trip in full: ~1 700 of a stage's ~3 000 cycles):
@@ -1639,40 +1320,16 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(64 * NW * ((GF || H2)
   constexpr int LAST = NSTEP - 1;
   constexpr bool SPLIT = COVER;
   // which chores are split is a register question (256 per lane with two workgroups per CU; a spilled value costs more than an
-  // exposed LDS round trip): forward A and C, backward -- whose lanes also carry G_t, G_{t-1} -- A only, unless overridden
-#ifndef VGPA_SYM_SPLIT_A_FWD
-#define VGPA_SYM_SPLIT_A_FWD 1
-#endif
-#ifndef VGPA_SYM_SPLIT_A_BWD
-#define VGPA_SYM_SPLIT_A_BWD 1
-#endif
-#ifndef VGPA_SYM_SPLIT_B_FWD
-#define VGPA_SYM_SPLIT_B_FWD 0
-#endif
-#ifndef VGPA_SYM_SPLIT_B_BWD
-#define VGPA_SYM_SPLIT_B_BWD 0
-#endif
-#ifndef VGPA_SYM_SPLIT_C_FWD
-#define VGPA_SYM_SPLIT_C_FWD 1          // (measured with the single-chain loop units: forward 7.80 -> 7.65 ms, same box, no spills)
-#endif
-#ifndef VGPA_SYM_SPLIT_C_BWD
-#define VGPA_SYM_SPLIT_C_BWD 0
-#endif
-  constexpr bool SPA = SPLIT && (FWD ? VGPA_SYM_SPLIT_A_FWD : VGPA_SYM_SPLIT_A_BWD);
-  constexpr bool SPB = SPLIT && (FWD ? VGPA_SYM_SPLIT_B_FWD : VGPA_SYM_SPLIT_B_BWD);
-  constexpr bool SPC = SPLIT && (FWD ? VGPA_SYM_SPLIT_C_FWD : VGPA_SYM_SPLIT_C_BWD);
+  // exposed LDS round trip): forward A and C, backward -- whose lanes also carry G_t, G_{t-1} -- A only.  (Forward C was
+  // measured with the single-chain loop units: 7.80 -> 7.65 ms, same box, no spills.)
+  constexpr bool SPA = SPLIT, SPC = SPLIT && FWD;
   constexpr int TBU = NSTEP >= 5 ? NSTEP / 4 + 1 : (NSTEP > 1 ? 1 : 0), TCU = NSTEP >= 5 ? NSTEP / 2 + 1 : LAST;   // unsplit slots
-  // (W8: a pipeline step is eight products = 128 cycles, shorter than an LDS round trip under load: every chore's read and
-  //  finish are TWO steps apart, and the vector's partial products -- which read what the vector update wrote -- come last)
-  constexpr int SA_F = W8 ? cmin(1, LAST) : 0, SA_R = (SPA || W8) ? -1 : SA_F;
-  constexpr int SB_F = W8 ? LAST : (SPLIT ? cmin(1, LAST) : TBU), SB_R = W8 ? cmin(2, LAST) : (SPB ? 0 : SB_F);
-  constexpr int SC_F = W8 ? cmin(3, LAST) : (SPLIT ? cmin(2, LAST) : TCU), SC_R = W8 ? 0 : (SPC ? cmin(1, LAST) : SC_F);
+  constexpr int SA_F = 0, SA_R = SPA ? -1 : SA_F;
+  constexpr int SB_F = SPLIT ? cmin(1, LAST) : TBU, SB_R = SB_F;
+  constexpr int SC_F = SPLIT ? cmin(2, LAST) : TCU, SC_R = SPC ? cmin(1, LAST) : SC_F;
   // (helper waves: the loop exists twice, once per role, so that each role's loop carries only its own state -- one loop with a role
   //  branch inside keeps the union of both alive across the back-edge, and the backward instantiations spill)
   auto time_loop = [&](auto helper_role) {
-#ifdef VGPA_STAMPS_ROLE
-  long long ts_prev_ = clock64();
-#endif
   constexpr int HK = HLP ? decltype(helper_role)::value : 0;    // 0: product waves (or no helpers); 1: the helper role; 2 / 3 (H2): vector / staging helper
   constexpr bool HR = HK != 0;                                  // this copy is a helper role's
   for (int k = 0; k < n_steps; k++) {
@@ -1722,7 +1379,6 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(64 * NW * ((GF || H2)
           return;
         }
         if (SPLIT) __builtin_amdgcn_sched_barrier(0);
-        if (!VGPA_ABL_NOVEC) {
         if (t == SA_R && (j > 0 || k > 0)) vecA_read(pv_prev);
         if (t == SA_F) {
           if (j > 0) vecA_finish(j - 1);
@@ -1734,31 +1390,16 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(64 * NW * ((GF || H2)
         }
         if (t == SB_R) tailB_read(Aopv);
         if (t == SB_F) tailB_finish(pv);
-        }
         if (t == SC_R) tailC_read(j, Xc);
         if (t == SC_F) tailC_finish(j, k, K1{});
         if (SPLIT) __builtin_amdgcn_sched_barrier(0);
       });
-#ifdef VGPA_STAMPS_ROLE      // diagnostic build (tools/ubench/ode_gf_loop.hip): first wave of each role of workgroup 0, per stage: [busy | wait at the barrier]
-      const long long tsb_ = clock64();
-#endif
-      VGPA_STAMP(0, 0);
-      __builtin_amdgcn_s_setprio(VGPA_SYM_TAILPRIO);
+      __builtin_amdgcn_s_setprio(1);     // (raised across the barrier and the next stage's first fragment reads)
       lds_barrier();
-#ifdef VGPA_STAMPS_ROLE
-      { const long long tsa_ = clock64();
-        if (lane == 0 && wave == 0 && blockIdx.x == 0) { mfma::g_stamp_role[HK == 3 ? 2 : (HR ? 1 : 0)][2 * j] += tsb_ - ts_prev_; mfma::g_stamp_role[HK == 3 ? 2 : (HR ? 1 : 0)][2 * j + 1] += tsa_ - tsb_; }
-        ts_prev_ = tsa_; }
-#endif
-      VGPA_STAMP(0, 2);
       // the next stage's first fragments (Xn is complete now; past the last stage of the sweep they are read and dropped)
       const int kn = j + 1 < NS ? k : k + 1, jn = j + 1 < NS ? j + 1 : 0;
       if (!HR) product_begin(aop(kn, jn, true), Xn);
-#ifndef VGPA_HLP_PRIO
-#define VGPA_HLP_PRIO 0
-#endif
-      __builtin_amdgcn_s_setprio(HR ? VGPA_HLP_PRIO : 0);
-      VGPA_STAMP(0, 3);
+      __builtin_amdgcn_s_setprio(0);
     }
   }
   };
@@ -1794,67 +1435,40 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(64 * NW * ((GF || H2)
 }
 
 
-// Eight waves per problem (k_ode_sym, NW = 8) are an EXPERIMENT kept reachable: VGPA_SYM_WAVES=8 in the environment selects them
-// (tools/ab_waves.sh, tests).  They measured slower than four waves at every batch size -- the product phase is bound by the LDS
-// fragment traffic as much as by the matrix pipe, and the split raises the fragment reads per product from 0.5 to 0.75.
-inline bool eight_waves(int batch) {
-  (void)batch;
-#ifdef VGPA_EXPERIMENTS
-  static const int forced = [] { const char* e = getenv("VGPA_SYM_WAVES"); return e ? atoi(e) : 0; }();
-  return forced == 8;      // measured slower at every batch size (EXPERIMENTS.md s.9): opt-in only
-#else
-  return false;            // (not compiled into the product build)
-#endif
-}
-
-// The outer-product cover (kOpMaps: two maps per wave, rotated row sides by DPP) is an EXPERIMENT kept reachable: VGPA_SYM_COVER=op.
-// It measured slower than the round-3 fragment cover (EXPERIMENTS.md s.12): a rotated operand costs two v_mov_dpp, which do not
-// issue under a running fp64 product, where the fragment read it replaces costs LDS cycles beside the matrix pipe.
-inline bool old_cover() {
-#ifdef VGPA_EXPERIMENTS
-  static const bool op = [] { const char* e = getenv("VGPA_SYM_COVER"); return e && !strcmp(e, "op"); }();
-  return !op;
-#else
-  return true;             // (not compiled into the product build)
-#endif
-}
 // Helper-wave kernels: one helper role (512 threads) or two (768; VGPA_SYM_HELPERS=2 in the environment forces two, =1 one)
 inline bool two_helper_roles() {
   static const int forced = [] { const char* e = getenv("VGPA_SYM_HELPERS"); return e ? atoi(e) : -1; }();
-#ifndef VGPA_SYM_TWO_HELPERS
-#define VGPA_SYM_TWO_HELPERS 1
-#endif
-  return forced >= 0 ? forced == 2 : VGPA_SYM_TWO_HELPERS != 0;
+  return forced < 0 || forced == 2;
 }
-template <int METHOD, bool FWD, int NB, int GRC, bool HLP = false>
+template <int METHOD, bool FWD, int NB, bool HLP = false>
 hipError_t launch_cover(const OdeArgs& a, hipStream_t st, bool dense) {
   constexpr size_t lds_c = SGeo<NB>::LDS_DOUBLES * sizeof(double);
   constexpr int WPE_C = (HLP || 2 * lds_c <= 160 * 1024) ? 2 : 1;
   constexpr int threads = HLP ? 512 : 256;
-  if constexpr (!FWD && METHOD == VGPA_ODE_RK4 && HLP && GRC == 0) {
+  if constexpr (!FWD && METHOD == VGPA_ODE_RK4 && HLP) {
     if (a.grad_on) {                                   // the gradient assembly on the helper waves (k_ode_sym, GF)
       if (dense || !a.q_on || !a.s_packed || !a.g || !a.S || !a.m || !a.Ef || !a.Am || !a.b) return hipErrorInvalidValue;
       constexpr size_t lds_g = lds_c + GradLds<NB>::DOUBLES * sizeof(double);
       static_assert(lds_g <= 160 * 1024, "LDS budget");
-      auto kg = k_ode_sym<METHOD, FWD, NB, false, GRC, 3, true, 4, true, true>;      // 768 threads: three waves per SIMD, 168 registers each
+      auto kg = k_ode_sym<METHOD, FWD, NB, false, 0, 3, true, true, true>;      // 768 threads: three waves per SIMD, 168 registers each
       (void)hipFuncSetAttribute((const void*)kg, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_g);
       hipLaunchKernelGGL(kg, dim3(a.batch), dim3(768), lds_g, st, a);
       return hipGetLastError();
     }
   }
   if (a.grad_on) return hipErrorInvalidValue;          // (only the kernel above assembles the gradient)
-  if constexpr (HLP && GRC == 0) {                     // two helper roles (k_ode_sym, H2): 768 threads, three waves per SIMD
+  if constexpr (HLP) {                                 // two helper roles (k_ode_sym, H2): 768 threads, three waves per SIMD
     if (two_helper_roles()) {
       if constexpr (!FWD && (METHOD == VGPA_ODE_RK2 || METHOD == VGPA_ODE_RK4)) {
         if (a.q_on) {
           if (dense) return hipErrorInvalidValue;
-          auto kq2 = k_ode_sym<METHOD, FWD, NB, false, GRC, 3, true, 4, true, false, true>;
+          auto kq2 = k_ode_sym<METHOD, FWD, NB, false, 0, 3, true, true, false, true>;
           (void)hipFuncSetAttribute((const void*)kq2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c);
           hipLaunchKernelGGL(kq2, dim3(a.batch), dim3(768), lds_c, st, a);
           return hipGetLastError();
         }
       }
-      auto kc2 = dense ? k_ode_sym<METHOD, FWD, NB, true, GRC, 3, false, 4, true, false, true> : k_ode_sym<METHOD, FWD, NB, false, GRC, 3, false, 4, true, false, true>;
+      auto kc2 = dense ? k_ode_sym<METHOD, FWD, NB, true, 0, 3, false, true, false, true> : k_ode_sym<METHOD, FWD, NB, false, 0, 3, false, true, false, true>;
       (void)hipFuncSetAttribute((const void*)kc2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c);
       hipLaunchKernelGGL(kc2, dim3(a.batch), dim3(768), lds_c, st, a);
       return hipGetLastError();
@@ -1863,14 +1477,14 @@ hipError_t launch_cover(const OdeArgs& a, hipStream_t st, bool dense) {
   if constexpr (!FWD && (METHOD == VGPA_ODE_RK2 || METHOD == VGPA_ODE_RK4)) {
     if (a.q_on) {
       if (dense) return hipErrorInvalidValue;          // (the fused sweeps bring sparse jumps)
-      auto kq = k_ode_sym<METHOD, FWD, NB, false, GRC, WPE_C, true, 4, HLP>;
+      auto kq = k_ode_sym<METHOD, FWD, NB, false, 0, WPE_C, true, HLP>;
       if (lds_c > 48 * 1024)
         (void)hipFuncSetAttribute((const void*)kq, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c);
       hipLaunchKernelGGL(kq, dim3(a.batch), dim3(threads), lds_c, st, a);
       return hipGetLastError();
     }
   }
-  auto kc = dense ? k_ode_sym<METHOD, FWD, NB, true, GRC, WPE_C, false, 4, HLP> : k_ode_sym<METHOD, FWD, NB, false, GRC, WPE_C, false, 4, HLP>;
+  auto kc = dense ? k_ode_sym<METHOD, FWD, NB, true, 0, WPE_C, false, HLP> : k_ode_sym<METHOD, FWD, NB, false, 0, WPE_C, false, HLP>;
   if (lds_c > 48 * 1024)
     (void)hipFuncSetAttribute((const void*)kc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c);
   hipLaunchKernelGGL(kc, dim3(a.batch), dim3(threads), lds_c, st, a);
@@ -1894,46 +1508,22 @@ template <int METHOD, bool FWD, int NB>
 hipError_t launch_sym(const OdeArgs& a, hipStream_t st) {
   constexpr size_t lds = SGeo<NB>::LDS_DOUBLES * sizeof(double);
   static_assert(lds <= 160 * 1024, "LDS budget");
-  // runs per pipeline step.  Two (four accumulators in turn, 16 MFMAs per step) spill with 256 registers and were slower with
-  // 512 (D = 64: 22.0 vs 15.7 ms forward); the kernel is only exercised with one.
-  // NSB = 5 (33 <= D <= 40): the fragment cover (GR = 0; VGPA_SYM_RUNS=1 keeps the run layout for comparison)
-  const bool runs_only = runs_only_env();
-  constexpr bool can_cover = SGeo<NB>::NSB == 5;
-  constexpr int GR = 1;
   const bool dense = !FWD && a.js_dense;
-  if constexpr (can_cover) {
-#ifdef VGPA_EXPERIMENTS
-    if (!runs_only && !dense && eight_waves(a.batch) && !a.grad_on) {
-      // up to one problem per CU: eight waves per problem (k_ode_sym, NW = 8), two per SIMD, all 256 registers each
-      constexpr size_t lds_8 = SGeo<NB, 8>::LDS_DOUBLES * sizeof(double);
-      static_assert(lds_8 <= 160 * 1024, "LDS budget");
-      if constexpr (!FWD && (METHOD == VGPA_ODE_RK2 || METHOD == VGPA_ODE_RK4)) {
-        if (a.q_on) {
-          auto kq8 = k_ode_sym<METHOD, FWD, NB, false, 0, 2, true, 8>;
-          (void)hipFuncSetAttribute((const void*)kq8, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_8);
-          hipLaunchKernelGGL(kq8, dim3(a.batch), dim3(512), lds_8, st, a);
-          return hipGetLastError();
-        }
-      }
-      auto k8 = k_ode_sym<METHOD, FWD, NB, false, 0, 2, false, 8>;
-      (void)hipFuncSetAttribute((const void*)k8, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_8);
-      hipLaunchKernelGGL(k8, dim3(a.batch), dim3(512), lds_8, st, a);
-      return hipGetLastError();
-    }
-#endif
-    if (!runs_only && old_cover() && (helper_waves(a.batch) || (!FWD && a.grad_on))) return launch_cover<METHOD, FWD, NB, 0, true>(a, st, dense);
-#ifdef VGPA_EXPERIMENTS
-    if (!runs_only && !old_cover()) return launch_cover<METHOD, FWD, NB, -1>(a, st, dense);
-#endif
-    if (!runs_only) return launch_cover<METHOD, FWD, NB, 0>(a, st, dense);
+  if constexpr (SGeo<NB>::NSB == 5) {                  // 33 <= D <= 40: the fragment cover
+    if (helper_waves(a.batch) || (!FWD && a.grad_on)) return launch_cover<METHOD, FWD, NB, true>(a, st, dense);
+    return launch_cover<METHOD, FWD, NB>(a, st, dense);
+  } else {
+    // the run layout, one run per pipeline step.  Two (four accumulators in turn, 16 MFMAs per step) spill with 256 registers
+    // and were slower with 512 (D = 64: 22.0 vs 15.7 ms forward).
+    constexpr int GR = 1;
+    if (a.grad_on) return hipErrorInvalidValue;
+    constexpr int WPE = 2 * lds <= 160 * 1024 ? 2 : 1;     // two workgroups per CU when their LDS fits, else all 512 registers
+    auto kern = dense ? k_ode_sym<METHOD, FWD, NB, true, GR, WPE> : k_ode_sym<METHOD, FWD, NB, false, GR, WPE>;
+    if (lds > 48 * 1024)
+      (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(kern, dim3(a.batch), dim3(256), lds, st, a);
+    return hipGetLastError();
   }
-  if (a.grad_on) return hipErrorInvalidValue;
-  constexpr int WPE = 2 * lds <= 160 * 1024 ? 2 : 1;     // two workgroups per CU when their LDS fits, else all 512 registers
-  auto kern = dense ? k_ode_sym<METHOD, FWD, NB, true, GR, WPE> : k_ode_sym<METHOD, FWD, NB, false, GR, WPE>;
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(kern, dim3(a.batch), dim3(256), lds, st, a);
-  return hipGetLastError();
 }
 
 // D <= 44 has both kernel families.  Default: the role-specialised 8-wave kernels of ode_mfma_impl.h (faster for one problem

@@ -621,10 +621,9 @@ static int materialize_derived(vgpa_ctx* c) {
 
 // S_t as its packed lower triangle between the kernels of a fused sweep: exactly where the gradient assembly will be k_grad_mfma_q
 // (the condition of run_bwd's Q'' stream: fragment-cover kernels, 33 <= D <= 40, RK2 / RK4, Sigma = sigma^2 I, Lorenz-96) and the
-// energy terms come from k_energy_l96_r; VGPA_S_PACKED=0 in the environment keeps whole matrices (comparison runs)
+// energy terms come from k_energy_l96_r
 static bool s_packed_ok(vgpa_ctx* c) {
-  static const bool off = [] { const char* e = getenv("VGPA_S_PACKED"); return e && e[0] == '0'; }();
-  return !off && c->sym_units && !use_lane(c) && !use_wave(c) && use_mfma(c, false, c->sym_inputs) && use_mfma(c, true, c->sym_inputs) &&
+  return c->sym_units && !use_lane(c) && !use_wave(c) && use_mfma(c, false, c->sym_inputs) && use_mfma(c, true, c->sym_inputs) &&
          c->sigma_diag && c->isg_iso && c->cfg.model == VGPA_MODEL_L96 && !(c->cfg.flags & (VGPA_FLAG_KEEP_PSI | VGPA_FLAG_FORCE_GENERIC)) &&
          sym_stores_q(c->cfg.method, c->D) && !c->hyp_on && c->D <= kMaxSmallD;
 }
@@ -644,10 +643,9 @@ static bool grad_fused_now(vgpa_ctx* c) {
 }
 
 // dEsde_dS between the energy kernel and the backward cover kernel as packed lower triangles: wherever S_t is packed (the same two
-// kernels sit on either side); VGPA_DS_PACKED=0 in the environment keeps the upper triangles in whole matrices (comparison runs)
+// kernels sit on either side)
 static bool ds_packed_ok(vgpa_ctx* c) {
-  static const bool off = [] { const char* e = getenv("VGPA_DS_PACKED"); return e && e[0] == '0'; }();
-  return !off && c->s_packed && c->d_jscp != nullptr;
+  return c->s_packed && c->d_jscp != nullptr;
 }
 
 // consumers that want S_t whole (vgpa_fetch, the operator-level kernels): the unpacked copy
@@ -715,11 +713,7 @@ static int check_status(vgpa_ctx* c) {
 // =====================================================================================================
 extern "C" {
 
-#ifdef VGPA_EXPERIMENTS
-int vgpa_abi_version(void) { return VGPA_ABI_VERSION | VGPA_ABI_DIAGNOSTIC_BUILD; }
-#else
 int vgpa_abi_version(void) { return VGPA_ABI_VERSION; }
-#endif
 
 int vgpa_device_count(void) {
   int n = 0;
