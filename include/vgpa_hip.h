@@ -30,8 +30,10 @@
  *   - there is NO CPU fallback: without a HIP device vgpa_create fails with VGPA_ERR_DEVICE.
  *
  * Batching: a context may hold `batch` independent problems that share the configuration
- * (observations, m0, S0, ...) but have different variational parameters x.  All per-problem
- * arrays are then laid out problem-major: x[batch][len_x], mt[batch][Np][D], F[batch], ...
+ * (model, theta, Sigma, R, H, dt, Np, method, observation count M) but have different variational
+ * parameters x.  By default they also share the observations, m0, S0 and e0 of vgpa_config;
+ * vgpa_set_problem_data gives each problem its own (one dataset per problem).  All per-problem
+ * arrays are laid out problem-major: x[batch][len_x], mt[batch][Np][D], F[batch], ...
  */
 #ifndef VGPA_HIP_H
 #define VGPA_HIP_H
@@ -217,7 +219,22 @@ int vgpa_set_option(vgpa_ctx* ctx, int option, int64_t value);
 /* E0 = KL(q0||p0): constant in x, but the reference recomputes it from the prior's current attributes on EVERY free_energy
  * call (src/var_bayes/variational.py:185; prior_kl0.py:30-92 reads self.mu0 / self.tau0) -- the host mirror hands the
  * current value over before each objective call instead of baking it into the context. */
-int vgpa_set_prior_energy(vgpa_ctx* ctx, double e0);
+int vgpa_set_prior_energy(vgpa_ctx* ctx, double e0);   /* sets every problem of the batch to e0 */
+/* Per-problem inputs of a batched context.  Each pointer may be NULL (= the shared value from vgpa_config): every call states
+ * the whole set, so a NULL also takes back what an earlier call set for that input.
+ *   obs_t [batch][M]      observation indices, each row strictly increasing in [0, Np); M is the context's n_obs
+ *   obs_y [batch][M][D]   observation values
+ *   m0    [batch][D]      initial mean
+ *   s0    [batch][D][D]   initial covariance
+ *   e0    [batch]         KL(q0||p0) of each problem
+ * Rows that all equal the shared observation times keep the shared-time kernels.  On the 16-lane kernels (2 <= D <= 4, fewer than
+ * 512 problems) per-problem times take dense jump arrays of batch * Np * (D + D*D) doubles.
+ * Drops the cached state, like vgpa_release_x.  The additive constant of E_obs depends on M and R only and stays shared.
+ * VGPA_ERR_ARG: an obs_t row out of order or out of range; VGPA_ERR_STATE: an ODE-only context; VGPA_ERR_UNSUPPORTED:
+ * per-problem obs_t at D > 64, and any per-problem data in the time-chunked large-D sweep.  A non-positive-definite s0 row
+ * is reported by the sweep (VGPA_ERR_NOT_PD), as a shared one is.  vgpa_solve_fwd keeps its explicit m0 / s0. */
+int vgpa_set_problem_data(vgpa_ctx* ctx, const int64_t* obs_t, const double* obs_y, const double* m0, const double* s0,
+                          const double* e0);
 /* 1 if the context runs the time-chunked large-D sweep (VGPA_FLAG_STREAM_LARGE_D or chosen for lack of memory) */
 int vgpa_is_streaming(vgpa_ctx* ctx);
 

@@ -1,0 +1,108 @@
+"""
+Throughput of a batch of independent datasets (Context.set_problem_data) against the shared-data batch, one JSON line.
+
+Two configurations, each in three contexts alive in one process: "shared" (every problem on the dataset of vgpa_config), "data"
+(per-problem observation values, m0, S0, e0) and "data_t" (the same plus per-problem observation times).  The modes alternate
+round by round; each round times `--steps` sweeps of one mode with the context's phase events (device time of the fused sweep,
+vgpa_profile_begin / _end), and the median per round is reported.
+
+    python tools/bench_problem_batch.py [--rounds 5] [--steps 10]
+
+  l96   Lorenz-96, D = 40, RK4, Np = 1001, B = 512     (bench.py's headline configuration)
+  l63   Lorenz-63, D = 3, RK4, Np = 1001, B = 65536    (bench.py's config2 block: the lane-per-problem kernels)
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "tests")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+
+def datasets(name, d, n_pts, dt, nset, seed0):
+    from helpers import build_problem
+    return [build_problem(name, "RK4", (n_pts - 1) * dt, dt, d, seed=seed0 + j) for j in range(nset)]
+
+
+def make_contexts(name, d, n_pts, dt, B, nset=4):
+    import vgpa_amd as va
+    from helpers import SEED
+    ps = datasets(name, d, n_pts, dt, nset, SEED)
+    p0 = ps[0]
+    theta = p0["model"].theta
+    e0 = float(p0["kl0"](p0["m0"], p0["s0"]))
+    kw = dict(sigma=p0["model"].sigma, theta=theta, m0=p0["m0"], s0=p0["s0"], obs_t=p0["obs_t"], obs_y=p0["obs_y"],
+              obs_noise=p0["obs_noise"], e0=e0, batch=B)
+    m = len(p0["obs_t"])
+    j = np.arange(B) % nset
+    obs_y = np.stack([np.reshape(ps[i]["obs_y"], (m, d)) for i in j])
+    m0 = np.stack([np.asarray(ps[i]["m0"], dtype=float) + 0.01 * (k % 97) for k, i in enumerate(j)])
+    s0 = np.stack([np.asarray(ps[i]["s0"], dtype=float) for i in j])
+    e0s = np.array([float(ps[i]["kl0"](m0[k], s0[k])) for k, i in enumerate(j)])
+    obs_t = np.stack([np.minimum(np.asarray(p0["obs_t"], dtype=np.int64) + (i % 3), n_pts - 1) for i in j])
+    ctxs = {}
+    for mode in ("shared", "data", "data_t"):
+        c = va.Context(name, "RK4", d, n_pts, dt, **kw)
+        if mode != "shared":
+            c.set_problem_data(obs_t=obs_t if mode == "data_t" else None, obs_y=obs_y, m0=m0, s0=s0, e0=e0s)
+        ctxs[mode] = c
+    x0 = np.stack([ps[i]["vgp"].initialization() for i in range(nset)])
+    return ctxs, x0
+
+
+def run(name, d, n_pts, dt, B, rounds, steps):
+    ctxs, x0 = make_contexts(name, d, n_pts, dt, B)
+    len_x = x0.shape[1]
+    rng = np.random.default_rng(1)
+    rows = x0[np.arange(64) % x0.shape[0]] + 0.05 * rng.standard_normal((64, len_x))
+    bufs = {}
+    for mode, c in ctxs.items():
+        xb, gb = c.alloc(B * len_x), c.alloc(B * len_x)
+        for i0 in range(0, B, 64):
+            k = min(64, B - i0)
+            xb.upload_at(i0 * len_x, rows[:k])
+        bufs[mode] = (xb, gb)
+        for _ in range(2):                       # warm-up (first-use allocations)
+            c.sweep_enqueue(xb, gb)
+            c.fetch_f()
+    ms = {mode: [] for mode in ctxs}
+    for _ in range(rounds):
+        for mode, c in ctxs.items():
+            xb, gb = bufs[mode]
+            c.profile_begin()
+            for _ in range(steps):
+                c.sweep_enqueue(xb, gb)
+                f = c.fetch_f()
+            pr = c.profile_end()
+            sweeps = pr["n_sweeps"] / B
+            ms[mode].append((pr["fwd_ms"] + pr["energy_ms"] + pr["bwd_ms"] + pr["grad_ms"]) / sweeps)
+            assert np.all(np.isfinite(f))
+    for c in ctxs.values():
+        c.close()
+    med = {mode: float(np.median(v)) for mode, v in ms.items()}
+    return {"B": B, "D": d, "Np": n_pts,
+            "ms_per_sweep": {m: round(v, 4) for m, v in med.items()},
+            "sweeps_per_s": {m: round(B * 1e3 / v, 1) for m, v in med.items()},
+            "ratio_data": round(med["shared"] / med["data"], 4), "ratio_data_t": round(med["shared"] / med["data_t"], 4),
+            "rounds_ms": {m: [round(x, 4) for x in v] for m, v in ms.items()}}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--l63-batch", type=int, default=65536)
+    args = ap.parse_args()
+    out = {"tool": "bench_problem_batch",
+           "l96": run("L96", 40, 1001, 0.01, 512, args.rounds, args.steps),
+           "l63": run("L63", 3, 1001, 0.01, args.l63_batch, args.rounds, args.steps)}
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()

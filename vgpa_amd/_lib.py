@@ -33,6 +33,7 @@ SYMBOLS = ["vgpa_create", "vgpa_destroy", "vgpa_last_error", "vgpa_abi_version",
            "vgpa_fetch", "vgpa_sweep_dev", "vgpa_free_energy_dev", "vgpa_sweep_enqueue", "vgpa_fetch_f",
            "vgpa_dev_alloc", "vgpa_dev_free", "vgpa_memcpy_h2d", "vgpa_memcpy_d2h",
            "vgpa_profile_begin", "vgpa_profile_end", "vgpa_ld_gemm", "vgpa_ld_stage", "vgpa_gradient_dev", "vgpa_energy_full", "vgpa_set_option", "vgpa_is_streaming", "vgpa_set_prior_energy",
+           "vgpa_set_problem_data",
            "vgpa_vec_dot", "vgpa_vec_absmax", "vgpa_vec_asum", "vgpa_vec_axpby", "vgpa_release_x",
            "vgpa_shard_create", "vgpa_shard_destroy", "vgpa_shard_time_slice", "vgpa_shard_stream", "vgpa_shard_synchronize",
            "vgpa_shard_solve_fwd", "vgpa_shard_solve_bwd", "vgpa_shard_sweep", "vgpa_shard_sweep_sharded", "vgpa_shard_set_option",
@@ -166,6 +167,7 @@ def load():
     lib.vgpa_set_option.argtypes = [c_void_p, c_int, c_int64]
     lib.vgpa_is_streaming.argtypes = [c_void_p]
     lib.vgpa_set_prior_energy.argtypes = [c_void_p, c_double]
+    lib.vgpa_set_problem_data.argtypes = [c_void_p] + [c_void_p] * 5
     lib.vgpa_profile_begin.argtypes = [c_void_p]
     lib.vgpa_profile_end.argtypes = [c_void_p, P_DOUBLE, P_DOUBLE, P_DOUBLE, P_DOUBLE, POINTER(c_int64)]
     abi = lib.vgpa_abi_version()
@@ -493,6 +495,7 @@ class Context:
         return f, g.reshape(self.B, self.len_x)
 
     def energy_parts(self):
+        """(e0, E_sde, E_obs) of the cached state, each (B,) (floats at B = 1); e0 is every problem's own."""
         e0, es, eo = np.empty(self.B), np.empty(self.B), np.empty(self.B)
         self._check(self._lib.vgpa_energy_parts(self._h, _ptr(e0), _ptr(es), _ptr(eo)))
         if self.B == 1:
@@ -573,6 +576,31 @@ class Context:
     def set_prior_energy(self, e0):
         """E0 = KL(q0||p0) used by the following objective calls (the reference recomputes it per call, variational.py:185)."""
         self._check(self._lib.vgpa_set_prior_energy(self._h, float(e0)))
+
+    def set_problem_data(self, obs_t=None, obs_y=None, m0=None, s0=None, e0=None):
+        """
+        Gives every problem of the batch its own dataset: obs_t (B, M) grid indices, obs_y (B, M, D), m0 (B, D), s0 (B, D, D),
+        e0 (B,).  Every array carries the leading batch axis, also at B = 1 or D = 1.  None keeps the shared value the context
+        was created with; M is the context's observation count.  Drops the cached state.
+        """
+        B, M, D = self.B, self.n_obs, self.D
+
+        def shaped(a, shape, name, dtype=np.float64):
+            if a is None:
+                return None
+            a = np.asarray(a)
+            if a.shape != shape:
+                raise ValueError(f"{name} has shape {a.shape}, expected {shape}")
+            if dtype == np.int64 and a.size and not np.issubdtype(a.dtype, np.integer):
+                raise ValueError(f"{name} must hold integer grid indices")
+            return np.ascontiguousarray(a, dtype=dtype)
+
+        t = shaped(obs_t, (B, M), "obs_t", np.int64)
+        y = shaped(obs_y, (B, M, D), "obs_y")
+        m = shaped(m0, (B, D), "m0")
+        s = shaped(s0, (B, D, D), "s0")
+        e = shaped(e0, (B,), "e0")
+        self._check(self._lib.vgpa_set_problem_data(self._h, _ptr(t), _ptr(y), _ptr(m), _ptr(s), _ptr(e)))
 
     @property
     def streaming(self):

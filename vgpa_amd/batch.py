@@ -1,0 +1,166 @@
+"""
+ProblemBatch: many independent smoothing problems of one model in ONE batched device context.
+
+Each member is a `VarGP` wired on its own dataset (its own sample path, observations and initial moments, as
+`Simulation.setup` builds them).  The members must share everything a context shares -- the model class, theta, Sigma,
+dt, Np, the integration method, R, H and the observation count M -- and may differ in what `Context.set_problem_data`
+takes per problem: the observation times and values, m0, S0 and E0 = KL(q0||p0) (each computed with the member's own
+`kl0`).  The batch then runs at the throughput of the batched kernels instead of one context per dataset.
+
+    pb = ProblemBatch([vgp_a, vgp_b, ...])
+    x, f, stats = pb.optimise(pb.initialization(), {"max_it": 500})
+    out = pb.result(1)            # problem 1's result dictionary, as save_results writes it
+"""
+import numpy as np
+
+from ._lib import Context
+
+__all__ = ["ProblemBatch"]
+
+
+def _same(a, b):
+    if a is None or b is None:
+        return a is None and b is None
+    a, b = np.asarray(a), np.asarray(b)
+    return a.shape == b.shape and np.array_equal(a, b)
+
+
+class ProblemBatch(object):
+
+    def __init__(self, vgps, device=0, flags=0) -> None:
+        self.vgps = list(vgps)
+        if not self.vgps:
+            raise ValueError(" ProblemBatch: no problems given.")
+        self.device, self.flags = device, int(flags)
+        self.B = len(self.vgps)
+        self._check_shared()
+        first = self.vgps[0]
+        self.dim_n, self.dim_d = first.dim_n, first.dim_d
+        self.len_x = self.dim_n * self.dim_d * (self.dim_d + 1)
+        self._ctx, self._ctx_key = None, None
+        self._x = self._f = None
+        self._outputs = None        # (context key, x, F, {key: (B, ...) array}) of the last result() evaluation
+
+    # ------------------------------------------------------------------------------------------
+    def _shared(self, vgp):
+        """What one context holds for all of its problems, in the order the fields are compared."""
+        inp = vgp._inputs()
+        return [("model", type(vgp.model)), ("theta", inp["theta"]), ("sigma", inp["sigma"]), ("dt", float(vgp.fwd_ode.dt)),
+                ("Np", vgp.dim_n), ("method", vgp._method), ("R", inp["obs_noise"]), ("H", inp["obs_h"]),
+                ("M", int(inp["obs_t"].size))]
+
+    def _check_shared(self):
+        ref = self._shared(self.vgps[0])
+        for k, vgp in enumerate(self.vgps[1:], start=1):
+            for (name, a), (_, b) in zip(ref, self._shared(vgp)):
+                equal = (a is b) if name == "model" else (a == b if isinstance(a, (int, float, str)) else _same(a, b))
+                if not equal:
+                    raise ValueError(f" ProblemBatch: problem {k} differs from problem 0 in '{name}'; a batch shares "
+                                     f"the model class, theta, sigma, dt, Np, method, R, H and the observation count M.")
+
+    def _per_problem(self):
+        """The per-problem inputs of every member, read from the objects NOW, and the priors E0 depends on."""
+        rows = [vgp._inputs() for vgp in self.vgps]
+        obs_t = np.stack([r["obs_t"] for r in rows])
+        prior = tuple(np.asarray(getattr(v.kl0, k, 0.0), dtype=float).tobytes() for v in self.vgps for k in ("mu0", "tau0"))
+        return dict(obs_t=obs_t, obs_y=np.stack([r["obs_y"].reshape(obs_t.shape[1], -1) for r in rows]),
+                    m0=np.stack([r["m0"] for r in rows]), s0=np.stack([r["s0"] for r in rows])), prior
+
+    def _context(self):
+        # like VarGP._context: a context built from inputs that have changed since is rebuilt (the shared ones are checked again)
+        self._check_shared()
+        shared = self.vgps[0]._inputs()
+        pp, prior = self._per_problem()
+        key = (shared["theta"].tobytes(), shared["sigma"].tobytes(), shared["obs_noise"].tobytes(),
+               None if shared["obs_h"] is None else shared["obs_h"].tobytes(), prior) + tuple(pp[k].tobytes() for k in sorted(pp))
+        if self._ctx is not None and key == self._ctx_key:
+            return self._ctx
+        self.close()
+        pp["e0"] = np.array([float(np.asarray(v.kl0(v.output["m0"], v.output["s0"]))) for v in self.vgps])
+        # the shared fields of the context come from problem 0; every per-problem field is replaced below.  Observation
+        # times stay shared when every member observes at the same grid points (the only form above D = 64).
+        ctx = Context(self.vgps[0].model._model_id, self.vgps[0]._method, self.dim_d, self.dim_n, float(self.vgps[0].fwd_ode.dt),
+                      e0=float(pp["e0"][0]), batch=self.B, device=self.device, flags=self.flags, **shared)
+        same_t = bool(np.all(pp["obs_t"] == pp["obs_t"][:1]))
+        ctx.set_problem_data(obs_t=None if same_t else pp["obs_t"], obs_y=pp["obs_y"], m0=pp["m0"], s0=pp["s0"], e0=pp["e0"])
+        self._ctx, self._ctx_key = ctx, key
+        return ctx
+
+    def close(self):
+        if self._ctx is not None:
+            self._ctx.close()
+        self._ctx, self._ctx_key = None, None
+
+    # ------------------------------------------------------------------------------------------
+    def _stack(self, x):
+        x = np.asarray(x, dtype=float)
+        if x.size != self.B * self.len_x:
+            raise ValueError(f" ProblemBatch: x has {x.size} entries, expected {self.B} x {self.len_x}")
+        return x.reshape(self.B, self.len_x)
+
+    def initialization(self):
+        """(B, len_x): every member's own cubic-spline initial guess (VarGP.initialization)."""
+        return np.stack([vgp.initialization() for vgp in self.vgps])
+
+    def free_energy(self, x):
+        """(B,) free energies; leaves the state of every problem resident for gradient() / result()."""
+        f = self._context().free_energy(self._stack(x))
+        return np.atleast_1d(np.asarray(f, dtype=float))
+
+    def gradient(self, x=None):
+        """(B, len_x); x=None: from the state of the last free_energy (VarGP.gradient(x, eval_fun=False))."""
+        g = self._context().gradient(None if x is None else self._stack(x))
+        return np.asarray(g).reshape(self.B, self.len_x)
+
+    def sweep(self, x):
+        """(F (B,), gradient (B, len_x)) in one call."""
+        f, g = self._context().sweep(self._stack(x))
+        return np.atleast_1d(np.asarray(f, dtype=float)), np.asarray(g).reshape(self.B, self.len_x)
+
+    def optimise(self, x0, options=None):
+        """DeviceSCG over the whole batch in lock step: (x (B, len_x), f (B,), statistics)."""
+        from .scg import DeviceSCG
+        opt = DeviceSCG(self._context(), *(() if options is None else (options,)))
+        x, f = opt(self._stack(x0))
+        self._x = np.asarray(x, dtype=float).reshape(self.B, self.len_x)
+        self._f = np.atleast_1d(np.asarray(f, dtype=float))
+        return self._x, self._f, opt.statistics
+
+    def _outputs_at(self, x):
+        """F and the output arrays of every problem at x: one evaluation and one download per x, shared by the B result(k) calls."""
+        ctx = self._context()
+        c = self._outputs
+        if c is not None and c[0] == self._ctx_key and np.array_equal(c[1], x):
+            return c[2], c[3]
+        f = self.free_energy(x)
+        arrays = {}
+        for key in ("mt", "st", "Efx", "Edf", "lamt", "psit"):
+            val = np.asarray(ctx.fetch(key))
+            arrays[key] = val[None] if self.B == 1 else val
+        self._outputs = (self._ctx_key, x.copy(), f, arrays)
+        return f, arrays
+
+    def result(self, k, x=None, fx=None):
+        """Problem k's result dictionary in the form save_results writes (fx, at, bt, m0, s0, mt, st, lamt, psit, Efx, Edf),
+        at x (B, len_x) or, by default, at the point the last optimise() returned."""
+        if x is None:
+            if self._x is None:
+                raise RuntimeError(" ProblemBatch.result: no optimisation has run; pass x.")
+            x, fx = self._x, self._f
+        x = self._stack(x)
+        f, arrays = self._outputs_at(x)
+        vgp = self.vgps[k]
+        n, d = self.dim_n, self.dim_d
+        xk = x[k]
+        out = {"fx": float(f[k]) if fx is None else float(np.asarray(fx).ravel()[k])}
+        if vgp.model.single_dim:
+            out["at"], out["bt"] = xk[:n], xk[n:]
+        else:
+            out["at"], out["bt"] = xk[:n * d * d].reshape(n, d, d), xk[n * d * d:].reshape(n, d)
+        out["m0"], out["s0"] = vgp.output["m0"], vgp.output["s0"]
+        for key, arr in arrays.items():
+            val = arr[k].copy()
+            if vgp.model.single_dim:
+                val = val.reshape(n)
+            out[key] = val
+        return out

@@ -36,12 +36,14 @@ __global__ void __launch_bounds__(NT) k_obs(ObsArgs a) {
   const int MS = a.s_packed ? tri_off(D) : D * D;          // doubles per stored S_t (packed lower triangle: OdeArgs::s_packed)
   const double* S = a.S + (size_t)prob * a.Np * MS;
   double* jm = a.jm_sparse + (size_t)prob * M * D;
+  const int64_t* obs_t = a.obs_t + (size_t)prob * a.obs_t_stride;
+  const double* obs_y = a.obs_y + (size_t)prob * a.obs_y_stride;
   double part = 0.0;
   if (a.single) {
     const double rinv = a.Q[0];        // 1/r
     for (int n = tid; n < M; n += NT) {
-      const int64_t tn = a.obs_t[n];
-      const double y = a.obs_y[n], mm = m[tn], ss = S[tn];
+      const int64_t tn = obs_t[n];
+      const double y = obs_y[n], mm = m[tn], ss = S[tn];
       const double ex2 = mm * mm + ss;
       part += (y * y) - 2.0 * y * mm + ex2;       // gaussian_like.py:87-92 (divided by r below)
       jm[n] = -(y - a.K[0] * mm) * rinv;          // gradients_1d: -(y - H m)/r, H = 1
@@ -53,8 +55,8 @@ __global__ void __launch_bounds__(NT) k_obs(ObsArgs a) {
   // n-D: thread per (n, i)
   for (int u = tid; u < M * D; u += NT) {
     const int n = u / D, i = u - n * D;
-    const int64_t tn = a.obs_t[n];
-    const double* y = a.obs_y + (size_t)n * D;
+    const int64_t tn = obs_t[n];
+    const double* y = obs_y + (size_t)n * D;
     const double* mt = m + (size_t)tn * D;
     double qrow = 0.0, krow = 0.0;
     if (a.diag) {                                  // diagonal R^-1 and H^T R^-1 (the usual case): the other terms are exact zeros
@@ -80,8 +82,8 @@ __global__ void __launch_bounds__(NT) k_obs(ObsArgs a) {
 __global__ void __launch_bounds__(NT) k_obs_nd(ObsArgs a) {
   __shared__ double red[NT];
   const int D = a.D, M = a.n_obs, n = blockIdx.x, prob = blockIdx.y, tid = threadIdx.x;
-  const int64_t tn = a.obs_t[n];
-  const double* y = a.obs_y + (size_t)n * D;
+  const int64_t tn = a.obs_t[(size_t)prob * a.obs_t_stride + n];
+  const double* y = a.obs_y + (size_t)prob * a.obs_y_stride + (size_t)n * D;
   const double* mt = a.m + ((size_t)prob * a.Np + tn) * D;
   const double* S = a.S + (size_t)prob * a.Np * D * D;
   double* jm = a.jm_sparse + ((size_t)prob * M + n) * D;
@@ -125,7 +127,7 @@ __global__ void __launch_bounds__(NT) k_obs_fin(ObsArgs a) {
 // dense jump arrays for the operator-level API (zero off the observation rows)
 __global__ void __launch_bounds__(NT) k_obs_dense(ObsArgs a, const double* js_const, double* jm_dense, double* js_dense) {
   const int D = a.D, M = a.n_obs, prob = blockIdx.y, n = blockIdx.x;
-  const int64_t tn = a.obs_t[n];
+  const int64_t tn = a.obs_t[(size_t)prob * a.obs_t_stride + n];
   const double* jm = a.jm_sparse + ((size_t)prob * M + n) * D;
   for (int i = threadIdx.x; i < D; i += NT) jm_dense[((size_t)prob * a.Np + tn) * D + i] = jm[i];
   for (int e = threadIdx.x; e < D * D; e += NT) js_dense[((size_t)prob * a.Np + tn) * D * D + e] = js_const[e];
@@ -635,7 +637,7 @@ __global__ void __launch_bounds__(NT) k_reduce(ReduceArgs a) {
   if (tid == 0) {
     const double esde = a.pre * tot / a.div;
     a.esde[prob] = esde;
-    a.f[prob] = a.e0 + esde + a.eobs[prob];
+    a.f[prob] = (a.e0v ? a.e0v[prob] : a.e0) + esde + a.eobs[prob];
   }
 }
 

@@ -625,7 +625,7 @@ __global__ void __launch_bounds__(256) k_mid(const double* __restrict__ a0, cons
 // src/numerics/ode_solver.py:31-95, and ONE problem of that size leaves most of the chip idle).  The step / stage loops below
 // compute problem 0's pointers as always; which array a pointer belongs to -- hence its per-problem stride -- is looked up by
 // address in the ranges the API registered (x, the histories, the workspace ...); pointers outside every range (Sigma, the
-// constant jump, S0) are shared by the problems.
+// constant jump, a shared S0) are shared by the problems.
 thread_local BatchMap g_batch;
 void ld_set_batch(const BatchMap* m) { g_batch = m ? *m : BatchMap{}; }
 static inline size_t zs(const double* p) { return g_batch.nb > 1 ? g_batch.stride(p) : 0; }
@@ -774,8 +774,8 @@ hipError_t ld_solve_fwd(int method, double dt, int D, int Np, const double* A, c
   const Work w = carve_work(ws, D);
   const double h = 0.5 * dt;
   for (int p = 0; p < g_batch.nb; p++) {
-    LD_TRY(hipMemcpyAsync(S + p * zs(S), S0, DD * sizeof(double), hipMemcpyDeviceToDevice, st));
-    LD_TRY(hipMemcpyAsync(m + p * zs(m), m0, D * sizeof(double), hipMemcpyDeviceToDevice, st));
+    LD_TRY(hipMemcpyAsync(S + p * zs(S), S0 + p * zs(S0), DD * sizeof(double), hipMemcpyDeviceToDevice, st));   // (per-problem S0 / m0:
+    LD_TRY(hipMemcpyAsync(m + p * zs(m), m0 + p * zs(m0), D * sizeof(double), hipMemcpyDeviceToDevice, st));     //  registered ranges)
   }
   for (int k = 0; k < Np - 1; k++) {
     const double *Ak = A + k * DD, *Ak1 = Ak + DD, *bk = b + (size_t)k * D, *bk1 = bk + D;

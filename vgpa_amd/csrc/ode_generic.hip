@@ -116,14 +116,15 @@ __global__ void __launch_bounds__(NT) k_fwd_generic(OdeArgs a) {
 
   double sk[EPT], sig[EPT], r[EPT], acc1[EPT], acc2[EPT], tmp[EPT];
   double mk = 0.0;
+  const double* S0 = a.S0 + (size_t)prob * a.S0_stride;       // (strides: 0 unless per-problem data)
 #pragma unroll
   for (int q = 0; q < EPT; q++) {
     const int e = tid + q * NT;
-    sk[q] = (e < DD) ? a.S0[e] : 0.0;
+    sk[q] = (e < DD) ? S0[e] : 0.0;
     sig[q] = (e < DD) ? a.Sigma[e] : 0.0;
     if (e < DD) { st[e] = sk[q]; l.X[e] = sk[q]; }
   }
-  if (vth) { mk = a.m0[tid]; mt[tid] = mk; l.xv[tid] = mk; }
+  if (vth) { mk = a.m0[(size_t)prob * a.m0_stride + tid]; mt[tid] = mk; l.xv[tid] = mk; }
   __syncthreads();
 
   for (int k = 0; k < Np - 1; k++) {
@@ -247,7 +248,7 @@ __device__ __forceinline__ void load_jump(const OdeArgs& a, int prob, int t1, in
     for (int q = 0; q < EPT; q++) { const int e = tid + q * NT; js[q] = (e < DD) ? p[e] : 0.0; }
     jm = (tid < D) ? a.jm_dense[((size_t)prob * a.Np + t1) * D + tid] : 0.0;
   } else {
-    const int n = a.obs_idx ? ldu(a.obs_idx, t1) : -1;           // (scalar load: see vgpa_internal.h)
+    const int n = a.obs_idx ? ldu(a.obs_idx + (size_t)prob * a.obs_idx_stride, t1) : -1;     // (scalar load: see vgpa_internal.h)
 #pragma unroll
     for (int q = 0; q < EPT; q++) { const int e = tid + q * NT; js[q] = (n >= 0 && e < DD) ? a.js_const[e] : 0.0; }
     jm = (n >= 0 && tid < D) ? a.jm_sparse[((size_t)prob * a.n_obs + n) * D + tid] : 0.0;

@@ -653,8 +653,9 @@ struct ERole {
     for (int q = 0; q < NIT; q++) {
       S.xk[q] = d2_t{0.0, 0.0}; S.acc[q] = d2_t{0.0, 0.0};
       if (FWD && item(q)) {
-        S.xk[q][0] = ldg(a.S0, T.gofs[q]);
-        S.xk[q][1] = row2(q) ? ldg(a.S0, T.gofs[q] + D8) : 0.0;
+        const double* S0 = a.S0 + (size_t)prob * a.S0_stride;      // (strides: 0 unless per-problem data)
+        S.xk[q][0] = ldg(S0, T.gofs[q]);
+        S.xk[q][1] = row2(q) ? ldg(S0, T.gofs[q] + D8) : 0.0;
         *reinterpret_cast<d2_t*>(L.X + T.offX[q]) = S.xk[q];
       }
       if (!FWD && !DENSEJ && write_sig && item(q)) {     // the constant matrix jump, once per workgroup
@@ -663,12 +664,12 @@ struct ERole {
         *reinterpret_cast<d2_t*>(SIG + 2 * (te + q * NE)) = js;
       }
     }
-    if (FWD && vl) { S.vk = ldg(a.m0, te8); L.xv[te] = S.vk; }
+    if (FWD && vl) { S.vk = ldg(a.m0 + (size_t)prob * a.m0_stride, te8); L.xv[te] = S.vk; }
     store_state(S, tidx(0));
     S.c0 = vl ? ldg(S.cin + vec(tidx(0)), te8) : 0.0;
     S.c1 = (vl && n_steps >= 1) ? ldg(S.cin + vec(tidx(1)), te8) : 0.0;
     if (!FWD && n_steps >= 1) {
-      S.n_obs_cur = (!DENSEJ && a.obs_idx) ? ldu(a.obs_idx, tidx(1)) : -1;
+      S.n_obs_cur = (!DENSEJ && a.obs_idx) ? ldu(a.obs_idx + (size_t)prob * a.obs_idx_stride, tidx(1)) : -1;      // (one problem per workgroup: scalar)
       S.jm = jump_vector(S, tidx(1), S.n_obs_cur);
     }
 #pragma unroll
@@ -681,7 +682,7 @@ struct ERole {
     const int n_steps = a.Np - 1;
     S.c2 = (vl && i + 2 <= n_steps) ? ldg(S.cin + vec(tidx(i + 2)), te8) : 0.0;
     if (!FWD) {
-      S.n_obs_next = (!DENSEJ && a.obs_idx && i + 2 <= n_steps) ? ldu(a.obs_idx, tidx(i + 2)) : -1;
+      S.n_obs_next = (!DENSEJ && a.obs_idx && i + 2 <= n_steps) ? ldu(a.obs_idx + (size_t)S.prob * a.obs_idx_stride, tidx(i + 2)) : -1;
       S.jm_next = (i + 2 <= n_steps) ? jump_vector(S, tidx(i + 2), S.n_obs_next) : 0.0;
     }
   }

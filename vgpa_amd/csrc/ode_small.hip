@@ -302,7 +302,7 @@ __global__ void __launch_bounds__(NTS) __attribute__((amdgpu_waves_per_eu(1, 1))
   const size_t sS = (size_t)Np * DD, sm = (size_t)Np * D;
 
   double sk[DD], sig[DD], mk[D], A0[DD], b0[D];
-  ld_mat<D>(a.S0, sk); ld_mat<D>(a.Sigma, sig); ld_vec<D>(a.m0, mk);
+  ld_mat<D>(a.S0 + (size_t)prob * a.S0_stride, sk); ld_mat<D>(a.Sigma, sig); ld_vec<D>(a.m0 + (size_t)prob * a.m0_stride, mk);   // (strides: 0 unless per-problem data)
   ld_mat<D>(A, A0); ld_vec<D>(b, b0);
   // (S_t as its packed lower triangle, then m_t: D (D + 1) / 2 + D entries per grid point -- 9 instead of 12 at D = 3)
   constexpr int TRI = D * (D + 1) / 2, W = TRI + D;
@@ -372,6 +372,15 @@ __device__ __forceinline__ void load_jump(const OdeArgs& a, int prob, int t1, do
   if (a.js_dense) {
     ld_mat<D>(a.js_dense + ((size_t)prob * a.Np + t1) * DD, js);
     ld_vec<D>(a.jm_dense + ((size_t)prob * a.Np + t1) * D, jm);
+  } else if (a.obs_idx && a.obs_idx_stride) {
+    // per-problem observation times: the lane's own index; the loads are unconditional (from a clamped address) and selected
+    const int n = a.obs_idx[(size_t)prob * a.obs_idx_stride + t1];
+    const int nc = n >= 0 ? n : 0;
+    ld_vec<D>(a.jm_sparse + ((size_t)prob * a.n_obs + nc) * D, jm);
+#pragma unroll
+    for (int e = 0; e < DD; e++) js[e] = n >= 0 ? a.js_const[e] : 0.0;
+#pragma unroll
+    for (int i = 0; i < D; i++) jm[i] = n >= 0 ? jm[i] : 0.0;
   } else {
     const int n = a.obs_idx ? ldu(a.obs_idx, t1) : -1;           // (scalar load: see vgpa_internal.h)
     if (n >= 0) {
@@ -544,7 +553,8 @@ __device__ __forceinline__ void point_terms(const LaneSweepArgs& q, const double
 
 // The fused pass (see the head of this file).  Chunk c holds grid points [hi - T + 1, hi], hi = Np - 2 - c T; step s of the chunk
 // goes from t = hi - s + 1 to t - 1 = hi - s, whose operands sit in slot T - 1 - s; gLa / gLb of t - 1 take the slots of A / b.
-template <int METHOD, int MODEL, bool GRAD, int T>
+// PT: per-problem observation times (OdeArgs::obs_idx_stride): the observation index, and with it the jump, is the lane's own.
+template <int METHOD, int MODEL, bool GRAD, int T, bool PT = false>
 __global__ void __launch_bounds__(NTS) __attribute__((amdgpu_waves_per_eu(1, 1))) k_sweep_lane(LaneSweepArgs q) {
   constexpr int D = (MODEL == VGPA_MODEL_L63) ? 3 : 1, DD = D * D, NA = T * DD, NV = T * D;
   __shared__ double sA[ChunkMap<NA>::LDS];
@@ -631,8 +641,20 @@ __global__ void __launch_bounds__(NTS) __attribute__((amdgpu_waves_per_eu(1, 1))
   double jsc[DD];
 #pragma unroll
   for (int e = 0; e < DD; e++) jsc[e] = a.js_const ? lds_const(a.js_const, e) : 0.0;
-  auto obs_at = [&](int t1) -> int { return (a.obs_idx && t1 >= 0) ? ldu(a.obs_idx, t1) : -1; };
-  auto request_jump = [&](int n, double (&jm)[D]) {          // (n: wave-uniform)
+  auto obs_at = [&](int t1) -> int {
+    if constexpr (PT) return t1 >= 0 ? a.obs_idx[(size_t)prob * a.obs_idx_stride + t1] : -1;     // (a vector load, consumed three steps on)
+    return (a.obs_idx && t1 >= 0) ? ldu(a.obs_idx, t1) : -1;
+  };
+  auto request_jump = [&](int n, double (&jm)[D]) {          // (n: wave-uniform unless PT)
+    if constexpr (PT) {          // the lesson above: no conditional load -- a clamped address, the value selected once it is in
+      const int nc = n >= 0 ? n : 0;
+#pragma unroll
+      for (int i = 0; i < D; i++) {
+        const double v = a.jmT[((size_t)nc * D + i) * (size_t)a.bpad + prob];
+        jm[i] = n >= 0 ? v : 0.0;
+      }
+      return;
+    }
     if (n >= 0) {
       if (a.jmT) {
 #pragma unroll
@@ -713,7 +735,7 @@ __global__ void __launch_bounds__(NTS) __attribute__((amdgpu_waves_per_eu(1, 1))
   if (live) {
     const double esde = q.pre * esum / q.div;
     q.esde[prob] = esde;
-    q.f[prob] = q.e0 + esde + q.eobs[prob];
+    q.f[prob] = (q.e0v ? q.e0v[prob] : q.e0) + esde + q.eobs[prob];
   }
 }
 
@@ -753,7 +775,11 @@ hipError_t launch_sweep_mm(const LaneSweepArgs& q, hipStream_t st) {
   // a vector memory operation the compiler waits for with vmcnt(0), i.e. together with every request in flight.  Same box, T = 4 | 6:
   // 4.67 | 5.16-5.49 ms per 65536 problems.
   constexpr int T = (MODEL == VGPA_MODEL_L63) ? 4 : 16;
-  if (q.want_grad) hipLaunchKernelGGL((k_sweep_lane<METHOD, MODEL, true, T>), grid, block, 0, st, q);
+  if (q.o.obs_idx_stride) {
+    if (!q.o.jmT) return hipErrorInvalidValue;      // (per-problem times read the jumps from jmT)
+    if (q.want_grad) hipLaunchKernelGGL((k_sweep_lane<METHOD, MODEL, true, T, true>), grid, block, 0, st, q);
+    else hipLaunchKernelGGL((k_sweep_lane<METHOD, MODEL, false, T, true>), grid, block, 0, st, q);
+  } else if (q.want_grad) hipLaunchKernelGGL((k_sweep_lane<METHOD, MODEL, true, T>), grid, block, 0, st, q);
   else hipLaunchKernelGGL((k_sweep_lane<METHOD, MODEL, false, T>), grid, block, 0, st, q);
   return hipGetLastError();
 }
@@ -813,12 +839,14 @@ __global__ void __launch_bounds__(NTS) k_obs_lane(ObsArgs a, const double* __res
   const double* ms = msT + prob;
   double* jo = jmT + prob;
   const int M = a.n_obs;
+  const int64_t* obs_t = a.obs_t + (size_t)prob * a.obs_t_stride;      // (strides: 0 unless per-problem data)
+  const double* obs_y = a.obs_y + (size_t)prob * a.obs_y_stride;
   double part = 0.0;
   if (a.single) {
     const double rinv = a.Q[0], k0 = a.K[0];
     for (int n = 0; n < M; n++) {
-      const size_t tn = (size_t)a.obs_t[n];
-      const double y = a.obs_y[n], ss = ms[(tn * W) * bp], mm = ms[(tn * W + 1) * bp];
+      const size_t tn = (size_t)obs_t[n];
+      const double y = obs_y[n], ss = ms[(tn * W) * bp], mm = ms[(tn * W + 1) * bp];
       const double ex2 = mm * mm + ss;
       part += (y * y) - 2.0 * y * mm + ex2;
       jo[(size_t)n * bp] = -(y - k0 * mm) * rinv;
@@ -827,8 +855,8 @@ __global__ void __launch_bounds__(NTS) k_obs_lane(ObsArgs a, const double* __res
     return;
   }
   for (int n = 0; n < M; n++) {
-    const size_t tn = (size_t)a.obs_t[n];
-    const double* y = a.obs_y + (size_t)n * D;
+    const size_t tn = (size_t)obs_t[n];
+    const double* y = obs_y + (size_t)n * D;
     double w[D];
 #pragma unroll
     for (int j = 0; j < D; j++) w[j] = y[j] - ms[(tn * W + TRI + j) * bp];

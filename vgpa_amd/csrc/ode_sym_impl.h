@@ -823,7 +823,7 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3
     fc[s] = ldg(G + (FWD ? 0 : (size_t)tidx(0) * GS), gofs[s]);
     fn[s] = FWD ? 0.0 : ldg(G + (size_t)tclamp(1) * GS, gofs[s]);
     fnn[s] = 0.0;
-    xk[s] = (FWD && own[s]) ? ldg(a.S0, gofs[s]) : 0.0;
+    xk[s] = (FWD && own[s]) ? ldg(a.S0 + (size_t)prob * a.S0_stride, gofs[s]) : 0.0;     // (strides: 0 unless per-problem data)
     acc[s] = 0.0;
   }
 
@@ -835,15 +835,16 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3
   double* const vout = (FWD ? a.m : a.lam) + (size_t)prob * Np * D;
   auto vec = [&](int t) { return (size_t)t * D; };
   const bool sparse_j = !FWD && !DENSEJ && a.obs_idx && a.jm_sparse;
+  const int32_t* const obs_idx = a.obs_idx + (size_t)prob * a.obs_idx_stride;      // (prob is uniform: the loads stay scalar)
   // vector jump behind the step that ends at grid point t (n_obs: its observation index or -1)
   auto jump_vector = [&](int t, int n_obs) -> double {
     if (!FWD && DENSEJ) return ldg(a.jm_dense + ((size_t)prob * Np + t) * D, lane8);
     if (sparse_j && __builtin_amdgcn_readfirstlane(n_obs) >= 0) return ldg(a.jm_sparse + ((size_t)prob * a.n_obs + n_obs) * D, lane8);
     return 0.0;
   };
-  double vk = FWD ? ldg(a.m0, lane8) : 0.0, v1 = 0.0;      // v1: Heun's first slope / RK4's running sum k1 + 2 k2 + 2 k3
+  double vk = FWD ? ldg(a.m0 + (size_t)prob * a.m0_stride, lane8) : 0.0, v1 = 0.0;      // v1: Heun's first slope / RK4's running sum k1 + 2 k2 + 2 k3
   double c0 = ldg(cin + vec(tidx(0)), lane8), c1 = ldg(cin + vec(tclamp(1)), lane8), c2 = 0.0;
-  int n_obs_cur = sparse_j ? ldu(a.obs_idx, tclamp(1)) : -1, n_obs_next = sparse_j ? ldu(a.obs_idx, tclamp(2)) : -1, n_obs_nn = -1;
+  int n_obs_cur = sparse_j ? ldu(obs_idx, tclamp(1)) : -1, n_obs_next = sparse_j ? ldu(obs_idx, tclamp(2)) : -1, n_obs_nn = -1;
   double jm = n_steps >= 1 ? jump_vector(tidx(1), n_obs_cur) : 0.0, jm_next = 0.0;
 
   __syncthreads();                       // LDS zero-filled
@@ -899,7 +900,7 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3
         for (int s = 0; s < MAXS; s++) fnn[s] = ldg(G + (size_t)tclamp(step + 2) * GS, gofs[s]);
       }
       if (ch_v) jm_next = step + 2 <= n_steps ? jump_vector(tidx(step + 2), n_obs_next) : 0.0;
-      n_obs_nn = (sparse_j && step + 3 <= n_steps) ? ldu(a.obs_idx, tidx(step + 3)) : -1;
+      n_obs_nn = (sparse_j && step + 3 <= n_steps) ? ldu(obs_idx, tidx(step + 3)) : -1;
     }
   };
 

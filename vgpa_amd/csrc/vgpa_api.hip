@@ -76,6 +76,15 @@ struct vgpa_ctx {
   double* d_Sfull = nullptr;     // ... and their unpacked copy, made when vgpa_fetch (or a kernel that wants S_t whole) asks
   bool ms_valid = true;          // d_m / d_S hold the cached moments (false: only d_msT does; untransposed on demand)
   bool sym_units = false;        // stepping-kernel family of this context (pick_kernel_family)
+  // per-problem inputs (vgpa_set_problem_data): each replaces its shared counterpart once set
+  double *d_pp_m0 = nullptr, *d_pp_S0 = nullptr, *d_pp_e0 = nullptr, *d_pp_obs_y = nullptr;   // [B][D], [B][D][D], [B], [B][M][D]
+  int64_t* d_pp_obs_t = nullptr;     // [B][M]
+  int32_t* d_pp_obs_idx = nullptr;   // [B][Np] -> observation counter n, or -1
+  bool pp_m0 = false, pp_S0 = false, pp_e0 = false, pp_obs_y = false, pp_obs_t = false;
+  std::vector<double> h_pp_e0;       // host copy of the per-problem e0 (vgpa_energy_parts)
+  double *d_jm_pt = nullptr, *d_js_pt = nullptr;   // dense jumps [B][Np][D], [B][Np][D][D]: per-problem times on the 16-lane kernels
+  bool pt_dense_zeroed = false;      // ... zero off the observation rows of the current times (each sweep rewrites only those rows)
+  bool sym_inputs_shared = true;     // sym_inputs as vgpa_create found it (Sigma, the shared s0, the constant jump)
   // profiling
   bool prof = false;
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -170,6 +179,10 @@ static int ingest_ab(vgpa_ctx* c, const double* lin_a, const double* off_b) {
   return VGPA_OK;
 }
 
+// the initial moments of the sweeps: the per-problem rows once vgpa_set_problem_data has set them (run_fwd tells them by address)
+static inline const double* sweep_m0(vgpa_ctx* c) { return c->pp_m0 ? c->d_pp_m0 : c->d_m0; }
+static inline const double* sweep_S0(vgpa_ctx* c) { return c->pp_S0 ? c->d_pp_S0 : c->d_S0; }
+
 static void prof_mark(vgpa_ctx* c, int i) {
   if (c->prof) (void)hipEventRecord(c->ev[i], c->stream);
 }
@@ -252,6 +265,8 @@ struct LdBatch {
     m.add(c->d_dEm, NpD); m.add(c->d_dEs, NpDD);
     m.add(c->d_jm, (size_t)c->M * c->D); m.add(c->d_jm_dense, NpD); m.add(c->d_js_dense, NpDD);
     m.add(c->d_ld_ws, ld::ld_workspace_doubles(c->D));
+    if (c->pp_m0) m.add(c->d_pp_m0, c->D);
+    if (c->pp_S0) m.add(c->d_pp_S0, c->DD);
     ld::ld_set_batch(&m);
   }
   ~LdBatch() { if (on) ld::ld_set_batch(nullptr); }
@@ -276,6 +291,8 @@ static int run_fwd(vgpa_ctx* c, const double* m0, const double* S0, const double
   a.D = c->D; a.Np = c->Np; a.batch = c->B; a.dt = c->cfg.dt;
   a.strideA = a.strideB = c->len_x;
   a.A = ctx_A(c); a.b = ctx_b(c); a.m0 = m0; a.S0 = S0; a.Sigma = Sigma; a.m = c->d_m; a.S = c->d_S;
+  a.m0_stride = m0 == c->d_pp_m0 ? (size_t)c->D : 0;
+  a.S0_stride = S0 == c->d_pp_S0 ? c->DD : 0;
   a.s_packed = c->s_packed ? 1 : 0;
   hipError_t e = use_lane(c) ? launch_ode_small(c->cfg.method, true, a, c->stream)
                  : use_wave(c) ? launch_ode_wave(c->cfg.method, true, a, c->stream)
@@ -286,6 +303,7 @@ static int run_fwd(vgpa_ctx* c, const double* m0, const double* S0, const double
 }
 
 static bool grad_fused_ok(vgpa_ctx* c);
+static ObsArgs obs_args(vgpa_ctx* c);
 // g_fused: the backward kernel assembles the gradient into it (grad_fused_ok contexts; Psi_t is then not stored)
 static int run_bwd(vgpa_ctx* c, bool dense_jumps, bool sym, double* g_fused = nullptr) {
   ld::use_library_gemm = (c->cfg.flags & VGPA_FLAG_LIBRARY_GEMM) != 0;
@@ -313,7 +331,23 @@ static int run_bwd(vgpa_ctx* c, bool dense_jumps, bool sym, double* g_fused = nu
   a.strideA = a.strideB = c->len_x;
   a.A = ctx_A(c); a.dEm = c->d_dEm; a.dEs = c->d_dEs; a.lam = c->d_lam; a.psi = c->d_psi;
   if (dense_jumps) { a.jm_dense = c->d_jm_dense; a.js_dense = c->d_js_dense; }
-  else { a.obs_idx = c->d_obs_idx; a.jm_sparse = c->d_jm; a.js_const = c->des_packed ? c->d_jscp : c->d_jsc; a.n_obs = c->M; }
+  else if (c->pp_obs_t && use_wave(c)) {
+    // per-problem times on the 16-lane kernels (four problems per wave, whose jump index is wave-uniform): dense jump arrays
+    // (B Np (D + D^2) doubles, zeroed once per set of times; a sweep rewrites the B M (D + D^2) entries of the observation rows)
+    if ((rc = ensure(c, &c->d_jm_pt, (size_t)c->B * c->Np * c->D))) return rc;
+    if ((rc = ensure(c, &c->d_js_pt, (size_t)c->B * c->Np * c->DD))) return rc;
+    if (!c->pt_dense_zeroed) {
+      HIP_TRY(c, hipMemsetAsync(c->d_jm_pt, 0, sizeof(double) * c->B * c->Np * c->D, c->stream));
+      HIP_TRY(c, hipMemsetAsync(c->d_js_pt, 0, sizeof(double) * c->B * c->Np * c->DD, c->stream));
+      c->pt_dense_zeroed = true;
+    }
+    hipError_t e = launch_obs_dense(obs_args(c), c->d_jsc, c->d_jm_pt, c->d_js_pt, c->stream);
+    if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "obs dense launch failed: %s", hipGetErrorString(e));
+    a.jm_dense = c->d_jm_pt; a.js_dense = c->d_js_pt;
+  } else {
+    a.obs_idx = c->pp_obs_t ? c->d_pp_obs_idx : c->d_obs_idx; a.obs_idx_stride = c->pp_obs_t ? c->Np : 0;
+    a.jm_sparse = c->d_jm; a.js_const = c->des_packed ? c->d_jscp : c->d_jsc; a.n_obs = c->M;
+  }
   a.ds_packed = c->des_packed ? 1 : 0;
   // fused sweeps on the fragment-cover kernels: Q''_t instead of Psi_t (the gradient assembly then does not read A_t; see
   // VGPA_FLAG_KEEP_PSI).  Same condition as the kernel choice below and as run_grad's matrix-core assembly.
@@ -394,7 +428,8 @@ static int run_energy(vgpa_ctx* c, double* edf, bool ds_upper = false, bool ds_p
 static ObsArgs obs_args(vgpa_ctx* c) {
   ObsArgs a{};
   a.D = c->D; a.Np = c->Np; a.batch = c->B; a.n_obs = c->M; a.single = c->single ? 1 : 0;
-  a.obs_t = c->d_obs_t; a.obs_y = c->d_obs_y; a.Q = c->d_Q; a.K = c->d_K; a.rinv_diag = c->d_rinv;
+  a.obs_t = c->pp_obs_t ? c->d_pp_obs_t : c->d_obs_t; a.obs_y = c->pp_obs_y ? c->d_pp_obs_y : c->d_obs_y; a.Q = c->d_Q;
+  a.obs_t_stride = c->pp_obs_t ? (size_t)c->M : 0; a.obs_y_stride = c->pp_obs_y ? (size_t)c->M * c->D : 0; a.K = c->d_K; a.rinv_diag = c->d_rinv;
   a.obs_const = c->obs_const; a.m = c->d_m; a.S = c->d_S; a.jm_sparse = c->d_jm; a.eobs = c->d_eobs;
   a.diag = c->obs_diag ? 1 : 0; a.part = c->d_obs_part;
   a.s_packed = c->s_packed ? 1 : 0;
@@ -403,7 +438,7 @@ static ObsArgs obs_args(vgpa_ctx* c) {
 
 static int run_reduce(vgpa_ctx* c) {
   ReduceArgs r{};
-  r.Np = c->Np; r.batch = c->B; r.dt = c->cfg.dt; r.e0 = c->cfg.e0;
+  r.Np = c->Np; r.batch = c->B; r.dt = c->cfg.dt; r.e0 = c->cfg.e0; r.e0v = c->pp_e0 ? c->d_pp_e0 : nullptr;
   r.pre = c->single ? 0.5 : 1.0; r.div = c->single ? c->sigma1 : 1.0;
   r.e_t = c->d_et; r.eobs = c->d_eobs; r.esde = c->d_esde; r.f = c->d_f;
   hipError_t e = launch_reduce(r, c->stream);
@@ -518,7 +553,7 @@ static int enqueue_stream_sweep(vgpa_ctx* c, double* g_dev) {
   HIP_TRY(c, hipMemsetAsync(c->d_status, 0, sizeof(int32_t) * c->B, c->stream));
   c->s_packed = false;
   prof_mark(c, 0);
-  if ((rc = run_fwd(c, c->d_m0, c->d_S0, c->d_Sigma, c->sym_inputs))) return rc;
+  if ((rc = run_fwd(c, sweep_m0(c), sweep_S0(c), c->d_Sigma, c->sym_inputs))) return rc;
   prof_mark(c, 1);
   hipError_t e = launch_obs(obs_args(c), c->stream);
   if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "obs launch failed: %s", hipGetErrorString(e));
@@ -550,13 +585,14 @@ static int run_lane_pass(vgpa_ctx* c, double* g_dev) {
   a.strideA = a.strideB = c->len_x;
   a.A = ctx_A(c); a.b = ctx_b(c); a.m = c->d_m; a.S = c->d_S;
   a.msT = c->d_msT; a.bpad = c->bpad; a.jmT = c->d_jmT;
-  a.obs_idx = c->d_obs_idx; a.jm_sparse = c->d_jm; a.js_const = c->d_jsc; a.n_obs = c->M;
+  a.obs_idx = c->pp_obs_t ? c->d_pp_obs_idx : c->d_obs_idx; a.obs_idx_stride = c->pp_obs_t ? c->Np : 0;
+  a.jm_sparse = c->d_jm; a.js_const = c->d_jsc; a.n_obs = c->M;
   q.model = c->cfg.model; q.want_grad = g_dev ? 1 : 0;
   for (int i = 0; i < kMaxTheta; i++) q.theta[i] = c->theta[i];
   q.sigma1 = c->sigma1;
   for (int i = 0; i < c->D; i++) q.isg[i] = c->h_isig[(size_t)i * c->D + i];
   for (size_t e = 0; e < c->DD; e++) q.isig[e] = c->h_isig[e];
-  q.e0 = c->cfg.e0; q.pre = c->single ? 0.5 : 1.0; q.div = c->single ? c->sigma1 : 1.0;
+  q.e0 = c->cfg.e0; q.e0v = c->pp_e0 ? c->d_pp_e0 : nullptr; q.pre = c->single ? 0.5 : 1.0; q.div = c->single ? c->sigma1 : 1.0;
   q.eobs = c->d_eobs; q.esde = c->d_esde; q.f = c->d_f; q.g = g_dev;
   hipError_t e = launch_sweep_lane(c->cfg.method, q, c->stream);
   if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "fused lane pass launch failed: %s", hipGetErrorString(e));
@@ -578,7 +614,8 @@ static int enqueue_lane_sweep(vgpa_ctx* c, double* g_dev) {
     OdeArgs a{};
     a.D = c->D; a.Np = c->Np; a.batch = c->B; a.dt = c->cfg.dt;
     a.strideA = a.strideB = c->len_x;
-    a.A = ctx_A(c); a.b = ctx_b(c); a.m0 = c->d_m0; a.S0 = c->d_S0; a.Sigma = c->d_Sigma; a.m = c->d_m; a.S = c->d_S;
+    a.A = ctx_A(c); a.b = ctx_b(c); a.m0 = sweep_m0(c); a.S0 = sweep_S0(c); a.Sigma = c->d_Sigma; a.m = c->d_m; a.S = c->d_S;
+    a.m0_stride = c->pp_m0 ? (size_t)c->D : 0; a.S0_stride = c->pp_S0 ? c->DD : 0;
     a.msT = c->d_msT; a.bpad = c->bpad;
     hipError_t ef = launch_ode_small(c->cfg.method, true, a, c->stream);
     if (ef != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "forward lane kernel launch failed: %s", hipGetErrorString(ef));
@@ -672,7 +709,7 @@ static int enqueue_free_energy(vgpa_ctx* c) {
   HIP_TRY(c, hipMemsetAsync(c->d_status, 0, sizeof(int32_t) * c->B, c->stream));
   prof_mark(c, 0);
   for (int r = diag_repeat("fwd"); r > 0; r--)
-    if ((rc = run_fwd(c, c->d_m0, c->d_S0, c->d_Sigma, c->sym_inputs))) return rc;
+    if ((rc = run_fwd(c, sweep_m0(c), sweep_S0(c), c->d_Sigma, c->sym_inputs))) return rc;
   prof_mark(c, 1);
   hipError_t e = launch_obs(obs_args(c), c->stream);
   if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "obs launch failed: %s", hipGetErrorString(e));
@@ -941,6 +978,7 @@ int vgpa_create(vgpa_ctx** out, const vgpa_config* cfg) {
     TRY(upload(c, c->d_jscp, jp.data(), DD));
   }
   HTRY(hipStreamSynchronize(c->stream));
+  c->sym_inputs_shared = c->sym_inputs;
 #undef TRY
 #undef HTRY
   *out = c;
@@ -1234,7 +1272,7 @@ int vgpa_energy_parts(vgpa_ctx* c, double* e0, double* esde, double* eobs) {
   if (!c->have_state) return fail(c, VGPA_ERR_STATE, "no cached state");
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   int rc;
-  if (e0) for (int p = 0; p < c->B; p++) e0[p] = c->cfg.e0;
+  if (e0) for (int p = 0; p < c->B; p++) e0[p] = c->pp_e0 ? c->h_pp_e0[p] : c->cfg.e0;
   if (esde && (rc = download(c, esde, c->d_esde, (size_t)c->B))) return rc;
   if (eobs && (rc = download(c, eobs, c->d_eobs, (size_t)c->B))) return rc;
   return vgpa_synchronize(c);
@@ -1383,6 +1421,70 @@ int vgpa_set_option(vgpa_ctx* c, int option, int64_t value) {
 int vgpa_set_prior_energy(vgpa_ctx* c, double e0) {
   if (!c) return VGPA_ERR_ARG;
   c->cfg.e0 = e0;
+  c->pp_e0 = false;                 // (every problem of the batch: per-problem values set earlier are gone)
+  return VGPA_OK;
+}
+
+// Per-problem inputs of a batched context (see vgpa_hip.h).  Everything is validated before anything is uploaded.
+int vgpa_set_problem_data(vgpa_ctx* c, const int64_t* obs_t, const double* obs_y, const double* m0, const double* s0, const double* e0) {
+  if (!c) return VGPA_ERR_ARG;
+  if (!c->full) return fail(c, VGPA_ERR_STATE, "context was created without m0/s0/observations (ODE-only)");
+  if (c->stream_ld) return fail(c, VGPA_ERR_UNSUPPORTED, "the time-chunked large-D sweep holds one problem: no per-problem data");
+  const int D = c->D, M = c->M, Np = c->Np, B = c->B;
+  if (obs_t && M > 0) {
+    if (D > kMaxSmallD)
+      return fail(c, VGPA_ERR_UNSUPPORTED, "per-problem observation times exist for D <= %d (D = %d shares the times of vgpa_config)", kMaxSmallD, D);
+    for (int p = 0; p < B; p++)
+      for (int n = 0; n < M; n++) {
+        const int64_t tn = obs_t[(size_t)p * M + n];
+        if (tn < 0 || tn >= Np || (n > 0 && tn <= obs_t[(size_t)p * M + n - 1]))
+          return fail(c, VGPA_ERR_ARG, "problem %d: obs_t must be strictly increasing indices in [0, Np)", p);
+      }
+  }
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  int rc;
+  // every call states the whole per-problem set: an input passed as NULL is the shared one of vgpa_config again
+  c->pp_obs_t = c->pp_obs_y = c->pp_m0 = c->pp_S0 = c->pp_e0 = false;
+  c->sym_inputs = c->sym_inputs_shared && (!s0 || stack_symmetric(s0, (size_t)B, D));   // (a non-symmetric s0 row: both products literally)
+  c->pt_dense_zeroed = false;
+  if (obs_t && M > 0) {
+    std::vector<int32_t> idx((size_t)B * Np, -1);
+    for (int p = 0; p < B; p++)
+      for (int n = 0; n < M; n++) idx[(size_t)p * Np + obs_t[(size_t)p * M + n]] = n;
+    bool shared_t = true;          // every row at the shared times: keep the shared-time kernels (the same results, bit for bit)
+    for (int p = 0; p < B && shared_t; p++) shared_t = std::memcmp(idx.data() + (size_t)p * Np, c->h_obs_idx.data(), sizeof(int32_t) * Np) == 0;
+    if (!shared_t) {
+      if ((rc = ensure(c, &c->d_pp_obs_t, (size_t)B * M))) return rc;
+      if ((rc = ensure(c, &c->d_pp_obs_idx, (size_t)B * Np))) return rc;
+      if ((rc = upload(c, c->d_pp_obs_t, obs_t, (size_t)B * M))) return rc;
+      if ((rc = upload(c, c->d_pp_obs_idx, idx.data(), idx.size()))) return rc;
+      HIP_TRY(c, hipStreamSynchronize(c->stream));          // (idx lives on this stack frame)
+    }
+    c->pp_obs_t = !shared_t;
+  }
+  if (obs_y && M > 0) {
+    if ((rc = ensure(c, &c->d_pp_obs_y, (size_t)B * M * D))) return rc;
+    if ((rc = upload(c, c->d_pp_obs_y, obs_y, (size_t)B * M * D))) return rc;
+    c->pp_obs_y = true;
+  }
+  if (m0) {
+    if ((rc = ensure(c, &c->d_pp_m0, (size_t)B * D))) return rc;
+    if ((rc = upload(c, c->d_pp_m0, m0, (size_t)B * D))) return rc;
+    c->pp_m0 = true;
+  }
+  if (s0) {
+    if ((rc = ensure(c, &c->d_pp_S0, (size_t)B * c->DD))) return rc;
+    if ((rc = upload(c, c->d_pp_S0, s0, (size_t)B * c->DD))) return rc;
+    c->pp_S0 = true;
+  }
+  if (e0) {
+    if ((rc = ensure(c, &c->d_pp_e0, (size_t)B))) return rc;
+    c->h_pp_e0.assign(e0, e0 + B);
+    if ((rc = upload(c, c->d_pp_e0, c->h_pp_e0.data(), (size_t)B))) return rc;
+    c->pp_e0 = true;
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->have_state = false;            // (like vgpa_release_x: the cached state belongs to the old inputs)
   return VGPA_OK;
 }
 

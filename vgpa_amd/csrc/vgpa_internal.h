@@ -50,8 +50,8 @@ struct OdeArgs {
   // forward
   const double* A;       // [B][Np][D][D]
   const double* b;       // [B][Np][D]
-  const double* m0;      // [D]
-  const double* S0;      // [D][D]
+  const double* m0;      // [D], or [B][D] with m0_stride = D (per-problem data, vgpa_set_problem_data)
+  const double* S0;      // [D][D], or [B][D][D] with S0_stride = D*D
   const double* Sigma;   // [D][D]
   double* m;             // [B][Np][D]
   double* S;             // [B][Np][D][D]
@@ -60,7 +60,7 @@ struct OdeArgs {
   const double* dEs;     // [B][Np][D][D]
   const double* jm_dense;  // [B][Np][D]      or nullptr (then the sparse form is used)
   const double* js_dense;  // [B][Np][D][D]   or nullptr
-  const int32_t* obs_idx;  // [Np] -> observation counter n, or -1
+  const int32_t* obs_idx;  // [Np] -> observation counter n, or -1; [B][Np] with obs_idx_stride = Np (per-problem times)
   const double* jm_sparse; // [B][M][D]
   const double* js_const;  // [D][D]
   int n_obs;
@@ -88,6 +88,9 @@ struct OdeArgs {
   const double* Ef;      // [B][Np][D] <f>_t            (energy kernel)
   const double* Am;      // [B][Np][D] A_t m_t          (energy kernel)
   double* g;             // [B][strideA]: problem p's [Np][D][D] gLa, then [Np][D] gLb (the caller's x layout)
+  // per-problem data (vgpa_set_problem_data), last so that the kernel-argument offsets of everything above stay where they were
+  size_t m0_stride, S0_stride;   // elements between consecutive problems' m0 / S0; 0: shared by the batch
+  int obs_idx_stride;            // Np: obs_idx is [B][Np]; 0: the observation times are shared by the batch
 };
 
 // Fused lane-per-problem pass of the models with closed-form moments (OU, double well, Lorenz-63; ode_small.hip::k_sweep_lane):
@@ -105,6 +108,7 @@ struct LaneSweepArgs {
   double* esde;            // [B]
   double* f;               // [B]
   double* g;               // [B][Np*D*D + Np*D] (want_grad)
+  const double* e0v;       // [B] per-problem e0 instead of e0, or nullptr (last: the offsets above stay where they were)
 };
 
 struct EnergyArgs {
@@ -135,8 +139,8 @@ struct EnergyArgs {
 
 struct ObsArgs {
   int D, Np, batch, n_obs, single;
-  const int64_t* obs_t;     // [M]
-  const double* obs_y;      // [M][D]
+  const int64_t* obs_t;     // [M]     ([B][M] with obs_t_stride = M: per-problem times)
+  const double* obs_y;      // [M][D]  ([B][M][D] with obs_y_stride = M*D: per-problem values)
   const double* Q;          // [D][D]  H R^-1 H^T     (1-D: 1/r)
   const double* K;          // [D][D]  H^T R^-1 H^T   (1-D: H/r ... see obs kernel)
   const double* rinv_diag;  // [D]     diag(R^-1)
@@ -148,6 +152,7 @@ struct ObsArgs {
   int s_packed;             // S holds packed lower triangles (OdeArgs::s_packed)
   int diag;                 // Q and K are diagonal (diagonal R, H = I)
   double* part;             // [B][M] per-observation terms of the n-D energy (grid-parallel variant) or nullptr
+  size_t obs_t_stride, obs_y_stride;   // elements between consecutive problems' obs_t / obs_y; 0: shared by the batch
 };
 
 struct GradArgs {
@@ -175,6 +180,7 @@ struct ReduceArgs {
   const double* eobs;       // [B]
   double* esde;             // [B]
   double* f;                // [B]
+  const double* e0v;        // [B] per-problem e0 instead of e0, or nullptr
 };
 
 // launchers (each returns hipGetLastError()) -----------------------------------------------------
