@@ -32,7 +32,8 @@
  * Batching: a context may hold `batch` independent problems that share the configuration
  * (model, theta, Sigma, R, H, dt, Np, method, observation count M) but have different variational
  * parameters x.  By default they also share the observations, m0, S0 and e0 of vgpa_config;
- * vgpa_set_problem_data gives each problem its own (one dataset per problem).  All per-problem
+ * vgpa_set_problem_data gives each problem its own (one dataset per problem), and
+ * vgpa_set_problem_params its own theta and Sigma (one parameter point per problem).  All per-problem
  * arrays are laid out problem-major: x[batch][len_x], mt[batch][Np][D], F[batch], ...
  */
 #ifndef VGPA_HIP_H
@@ -140,7 +141,9 @@ typedef struct {
  *     dense Sigma / S0 / R / H, several problems per context (the per-stage kernels take them in grid.z: what fills the chip
  *     for 64 < D <= 512), the hyper-parameter members, non-symmetric operator-level inputs (both products of the slope
  *     formed literally; the fused sweep and the row-sharded drivers assume the symmetric S0 / Sigma every real run has);
- *   - VGPA_FETCH_PSIT / VGPA_FETCH_DESDE_DS in the time-chunked large-D sweep (they are never resident there).
+ *   - VGPA_FETCH_PSIT / VGPA_FETCH_DESDE_DS in the time-chunked large-D sweep (they are never resident there);
+ *   - per-problem parameters (vgpa_set_problem_params): a per-problem Sigma at D > 64 (per-problem theta is built there), and
+ *     any per-problem theta or Sigma in the time-chunked large-D sweep and the row-sharded drivers.
  * The matrix-core stepping kernels cover D <= 64 with symmetric inputs; non-symmetric operator-level inputs run on the
  * generic LDS kernels (same results, ~15x slower at D = 40). */
 
@@ -154,7 +157,8 @@ int vgpa_synchronize(vgpa_ctx* ctx);
 void* vgpa_stream(vgpa_ctx* ctx);                    /* the context's hipStream_t */
 
 /* operator level (host pointers; problem-major when batch > 1) ------------------------------ */
-/* (m_t, S_t) from (A, b, m0, S0, Sigma).  A:[Np,D,D] b:[Np,D] m0:[D] s0:[D,D] sigma:[D,D] */
+/* (m_t, S_t) from (A, b, m0, S0, Sigma).  A:[Np,D,D] b:[Np,D] m0:[D] s0:[D,D] sigma:[D,D]
+ * (the explicit m0 / s0 / sigma of this call serve every problem: per-problem data and parameters do not apply here) */
 int vgpa_solve_fwd(vgpa_ctx* ctx, const double* lin_a, const double* off_b, const double* m0,
                    const double* s0, const double* sigma, double* mt, double* st);
 /* (lam_t, Psi_t) from A, dEsde/dm [Np,D], dEsde/dS [Np,D,D] and the dense jump arrays of E_obs. */
@@ -235,6 +239,17 @@ int vgpa_set_prior_energy(vgpa_ctx* ctx, double e0);   /* sets every problem of 
  * is reported by the sweep (VGPA_ERR_NOT_PD), as a shared one is.  vgpa_solve_fwd keeps its explicit m0 / s0. */
 int vgpa_set_problem_data(vgpa_ctx* ctx, const int64_t* obs_t, const double* obs_y, const double* m0, const double* s0,
                           const double* e0);
+/* Per-problem drift parameters and system noise of a batched context, for parameter studies (one dataset at many (theta, Sigma)
+ * points in one context).  theta: [batch][n_theta]; sigma: [batch][D][D] (1-D models: [batch]).  NULL keeps vgpa_config's value;
+ * like vgpa_set_problem_data every call states the whole set, and neither call resets what the other one set.  Sigma^-1 of each
+ * row is computed as vgpa_create computes the shared one.  The kernel family (diagonal / isotropic Sigma, symmetric inputs) is the
+ * one every row allows; rows that all equal the shared parameters keep the shared kernels.  Drops the cached state.
+ * Seen by the fused objective (free_energy, gradient, sweep, sweep_enqueue), vgpa_energy_parts, vgpa_fetch (VGPA_FETCH_PSIT
+ * included) and the operator-level vgpa_energy / vgpa_energy_full (whose dEsde_dth / dEsde_dsig are then per problem).
+ * VGPA_ERR_ARG: a 1-D sigma row <= 0; VGPA_ERR_NOT_PD: a Sigma row that is not positive definite (the message names the row; the
+ * previous parameters stay in force after either); VGPA_ERR_STATE: an ODE-only context; VGPA_ERR_UNSUPPORTED: per-problem Sigma
+ * at D > 64, and any per-problem parameter in the time-chunked large-D sweep. */
+int vgpa_set_problem_params(vgpa_ctx* ctx, const double* theta, const double* sigma);
 /* 1 if the context runs the time-chunked large-D sweep (VGPA_FLAG_STREAM_LARGE_D or chosen for lack of memory) */
 int vgpa_is_streaming(vgpa_ctx* ctx);
 

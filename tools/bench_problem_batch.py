@@ -1,8 +1,10 @@
 """
-Throughput of a batch of independent datasets (Context.set_problem_data) against the shared-data batch, one JSON line.
+Throughput of a batch of independent datasets (Context.set_problem_data) or parameter points (Context.set_problem_params)
+against the shared batch, one JSON line.
 
-Two configurations, each in three contexts alive in one process: "shared" (every problem on the dataset of vgpa_config), "data"
-(per-problem observation values, m0, S0, e0) and "data_t" (the same plus per-problem observation times).  The modes alternate
+Two configurations, each in four contexts alive in one process: "shared" (every problem on the dataset of vgpa_config), "data"
+(per-problem observation values, m0, S0, e0), "data_t" (the same plus per-problem observation times) and "params" (the shared
+dataset at per-problem theta and Sigma = sigma_p^2 I, Context.set_problem_params).  The modes alternate
 round by round; each round times `--steps` sweeps of one mode with the context's phase events (device time of the fused sweep,
 vgpa_profile_begin / _end), and the median per round is reported.
 
@@ -45,11 +47,16 @@ def make_contexts(name, d, n_pts, dt, B, nset=4):
     s0 = np.stack([np.asarray(ps[i]["s0"], dtype=float) for i in j])
     e0s = np.array([float(ps[i]["kl0"](m0[k], s0[k])) for k, i in enumerate(j)])
     obs_t = np.stack([np.minimum(np.asarray(p0["obs_t"], dtype=np.int64) + (i % 3), n_pts - 1) for i in j])
+    k = np.arange(B)
+    th = np.atleast_1d(np.asarray(theta, dtype=float))[None, :] * (1.0 + 0.05 * (k % 5))[:, None]
+    sig = np.asarray(p0["model"].sigma, dtype=float)[None] * (1.0 + 0.1 * (k % 4))[:, None, None]      # sigma_p^2 I
     ctxs = {}
-    for mode in ("shared", "data", "data_t"):
+    for mode in ("shared", "data", "data_t", "params"):
         c = va.Context(name, "RK4", d, n_pts, dt, **kw)
-        if mode != "shared":
+        if mode in ("data", "data_t"):
             c.set_problem_data(obs_t=obs_t if mode == "data_t" else None, obs_y=obs_y, m0=m0, s0=s0, e0=e0s)
+        if mode == "params":
+            c.set_problem_params(theta=th, sigma=sig)
         ctxs[mode] = c
     x0 = np.stack([ps[i]["vgp"].initialization() for i in range(nset)])
     return ctxs, x0
@@ -89,6 +96,7 @@ def run(name, d, n_pts, dt, B, rounds, steps):
             "ms_per_sweep": {m: round(v, 4) for m, v in med.items()},
             "sweeps_per_s": {m: round(B * 1e3 / v, 1) for m, v in med.items()},
             "ratio_data": round(med["shared"] / med["data"], 4), "ratio_data_t": round(med["shared"] / med["data_t"], 4),
+            "ratio_params": round(med["shared"] / med["params"], 4),
             "rounds_ms": {m: [round(x, 4) for x in v] for m, v in ms.items()}}
 
 

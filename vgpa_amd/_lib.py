@@ -33,7 +33,7 @@ SYMBOLS = ["vgpa_create", "vgpa_destroy", "vgpa_last_error", "vgpa_abi_version",
            "vgpa_fetch", "vgpa_sweep_dev", "vgpa_free_energy_dev", "vgpa_sweep_enqueue", "vgpa_fetch_f",
            "vgpa_dev_alloc", "vgpa_dev_free", "vgpa_memcpy_h2d", "vgpa_memcpy_d2h",
            "vgpa_profile_begin", "vgpa_profile_end", "vgpa_ld_gemm", "vgpa_ld_stage", "vgpa_gradient_dev", "vgpa_energy_full", "vgpa_set_option", "vgpa_is_streaming", "vgpa_set_prior_energy",
-           "vgpa_set_problem_data",
+           "vgpa_set_problem_data", "vgpa_set_problem_params",
            "vgpa_vec_dot", "vgpa_vec_absmax", "vgpa_vec_asum", "vgpa_vec_axpby", "vgpa_release_x",
            "vgpa_shard_create", "vgpa_shard_destroy", "vgpa_shard_time_slice", "vgpa_shard_stream", "vgpa_shard_synchronize",
            "vgpa_shard_solve_fwd", "vgpa_shard_solve_bwd", "vgpa_shard_sweep", "vgpa_shard_sweep_sharded", "vgpa_shard_set_option",
@@ -168,6 +168,7 @@ def load():
     lib.vgpa_is_streaming.argtypes = [c_void_p]
     lib.vgpa_set_prior_energy.argtypes = [c_void_p, c_double]
     lib.vgpa_set_problem_data.argtypes = [c_void_p] + [c_void_p] * 5
+    lib.vgpa_set_problem_params.argtypes = [c_void_p] + [c_void_p] * 2
     lib.vgpa_profile_begin.argtypes = [c_void_p]
     lib.vgpa_profile_end.argtypes = [c_void_p, P_DOUBLE, P_DOUBLE, P_DOUBLE, P_DOUBLE, POINTER(c_int64)]
     abi = lib.vgpa_abi_version()
@@ -395,6 +396,7 @@ class Context:
             _raise(rc, self._lib.vgpa_last_error(None))
         self._h = h
         self.n_obs = n_obs
+        self.n_theta = cfg.n_theta
 
     # ------------------------------------------------------------------ plumbing
     def _check(self, rc):
@@ -601,6 +603,28 @@ class Context:
         s = shaped(s0, (B, D, D), "s0")
         e = shaped(e0, (B,), "e0")
         self._check(self._lib.vgpa_set_problem_data(self._h, _ptr(t), _ptr(y), _ptr(m), _ptr(s), _ptr(e)))
+
+    def set_problem_params(self, theta=None, sigma=None):
+        """
+        Gives every problem of the batch its own drift parameters theta (B, n_theta) and system noise sigma (B, D, D) -- one
+        parameter point per problem, e.g. a grid of (theta, sigma^2) over one dataset.  Both carry the leading batch axis, also at
+        B = 1 or D = 1.  None keeps the shared value the context was created with; independent of set_problem_data.  Drops the
+        cached state.  A non-positive-definite sigma row raises LinAlgError, a 1-D sigma <= 0 ValueError; the previous
+        parameters then stay in force.
+        """
+        B, D = self.B, self.D
+
+        def shaped(a, shape, name):
+            if a is None:
+                return None
+            a = np.asarray(a)
+            if a.shape != shape:
+                raise ValueError(f"{name} has shape {a.shape}, expected {shape}")
+            return np.ascontiguousarray(a, dtype=np.float64)
+
+        t = shaped(theta, (B, self.n_theta), "theta")
+        s = shaped(sigma, (B, D, D), "sigma")
+        self._check(self._lib.vgpa_set_problem_params(self._h, _ptr(t), _ptr(s)))
 
     @property
     def streaming(self):

@@ -6,6 +6,8 @@ Each member is a `VarGP` wired on its own dataset (its own sample path, observat
 dt, Np, the integration method, R, H and the observation count M -- and may differ in what `Context.set_problem_data`
 takes per problem: the observation times and values, m0, S0 and E0 = KL(q0||p0) (each computed with the member's own
 `kl0`).  The batch then runs at the throughput of the batched kernels instead of one context per dataset.
+With own_parameters=True theta and Sigma leave the shared list: each member's own model.theta / model.sigma goes to
+`Context.set_problem_params` (a parameter study: one dataset at many (theta, Sigma) points).
 
     pb = ProblemBatch([vgp_a, vgp_b, ...])
     x, f, stats = pb.optimise(pb.initialization(), {"max_it": 500})
@@ -27,11 +29,12 @@ def _same(a, b):
 
 class ProblemBatch(object):
 
-    def __init__(self, vgps, device=0, flags=0) -> None:
+    def __init__(self, vgps, device=0, flags=0, own_parameters=False) -> None:
         self.vgps = list(vgps)
         if not self.vgps:
             raise ValueError(" ProblemBatch: no problems given.")
         self.device, self.flags = device, int(flags)
+        self.own_parameters = bool(own_parameters)
         self.B = len(self.vgps)
         self._check_shared()
         first = self.vgps[0]
@@ -45,26 +48,35 @@ class ProblemBatch(object):
     def _shared(self, vgp):
         """What one context holds for all of its problems, in the order the fields are compared."""
         inp = vgp._inputs()
-        return [("model", type(vgp.model)), ("theta", inp["theta"]), ("sigma", inp["sigma"]), ("dt", float(vgp.fwd_ode.dt)),
-                ("Np", vgp.dim_n), ("method", vgp._method), ("R", inp["obs_noise"]), ("H", inp["obs_h"]),
-                ("M", int(inp["obs_t"].size))]
+        fields = [("model", type(vgp.model)), ("theta", inp["theta"]), ("sigma", inp["sigma"]), ("dt", float(vgp.fwd_ode.dt)),
+                  ("Np", vgp.dim_n), ("method", vgp._method), ("R", inp["obs_noise"]), ("H", inp["obs_h"]),
+                  ("M", int(inp["obs_t"].size))]
+        if self.own_parameters:     # (theta and sigma go to Context.set_problem_params instead)
+            fields = [f for f in fields if f[0] not in ("theta", "sigma")]
+        return fields
 
     def _check_shared(self):
         ref = self._shared(self.vgps[0])
+        label = {"model": "the model class", "M": "the observation count M"}
+        names = [label.get(name, name) for name, _ in ref]
+        shared = ", ".join(names[:-1]) + " and " + names[-1]
         for k, vgp in enumerate(self.vgps[1:], start=1):
             for (name, a), (_, b) in zip(ref, self._shared(vgp)):
                 equal = (a is b) if name == "model" else (a == b if isinstance(a, (int, float, str)) else _same(a, b))
                 if not equal:
-                    raise ValueError(f" ProblemBatch: problem {k} differs from problem 0 in '{name}'; a batch shares "
-                                     f"the model class, theta, sigma, dt, Np, method, R, H and the observation count M.")
+                    raise ValueError(f" ProblemBatch: problem {k} differs from problem 0 in '{name}'; a batch shares {shared}.")
 
     def _per_problem(self):
         """The per-problem inputs of every member, read from the objects NOW, and the priors E0 depends on."""
         rows = [vgp._inputs() for vgp in self.vgps]
         obs_t = np.stack([r["obs_t"] for r in rows])
         prior = tuple(np.asarray(getattr(v.kl0, k, 0.0), dtype=float).tobytes() for v in self.vgps for k in ("mu0", "tau0"))
-        return dict(obs_t=obs_t, obs_y=np.stack([r["obs_y"].reshape(obs_t.shape[1], -1) for r in rows]),
-                    m0=np.stack([r["m0"] for r in rows]), s0=np.stack([r["s0"] for r in rows])), prior
+        pp = dict(obs_t=obs_t, obs_y=np.stack([r["obs_y"].reshape(obs_t.shape[1], -1) for r in rows]),
+                  m0=np.stack([r["m0"] for r in rows]), s0=np.stack([r["s0"] for r in rows]))
+        if self.own_parameters:     # every member's own model.theta / model.sigma (and with them the context key)
+            pp["theta"] = np.stack([r["theta"] for r in rows])
+            pp["sigma"] = np.stack([r["sigma"] for r in rows])
+        return pp, prior
 
     def _context(self):
         # like VarGP._context: a context built from inputs that have changed since is rebuilt (the shared ones are checked again)
@@ -83,6 +95,8 @@ class ProblemBatch(object):
                       e0=float(pp["e0"][0]), batch=self.B, device=self.device, flags=self.flags, **shared)
         same_t = bool(np.all(pp["obs_t"] == pp["obs_t"][:1]))
         ctx.set_problem_data(obs_t=None if same_t else pp["obs_t"], obs_y=pp["obs_y"], m0=pp["m0"], s0=pp["s0"], e0=pp["e0"])
+        if self.own_parameters:
+            ctx.set_problem_params(theta=pp["theta"], sigma=pp["sigma"])
         self._ctx, self._ctx_key = ctx, key
         return ctx
 

@@ -185,16 +185,18 @@ __global__ void __launch_bounds__(NT) k_grad(GradArgs a) {
   const size_t len_x = (size_t)a.Np * DD + (size_t)a.Np * D;
   double* gA = a.g + (size_t)prob * len_x + (size_t)t * DD;
   double* gB = a.g + (size_t)prob * len_x + (size_t)a.Np * DD + (size_t)t * D;
+  const double* th = a.theta_v ? a.theta_v + (size_t)prob * kMaxTheta : a.theta;      // (per-problem parameters: the problem's row)
+  const double* isig = a.isig + (size_t)prob * a.isig_stride;
 
   if (tid < D) mv[tid] = a.m[o * D + tid];
   __syncthreads();
   const double s00 = St[0];
   for (int e = tid; e < DD; e += NT) {
     const int i = e / D, j = e - i * D;
-    const double ed = Edf ? Edf[e] : edf_entry(a.model, a.theta, D, i, j, mv, s00);
+    const double ed = Edf ? Edf[e] : edf_entry(a.model, th, D, i, j, mv, s00);
     const double pa = ed + At[e];
     Ss[i * LD + j] = St[e];
-    if (a.sigma_diag) Q[i * LD + j] = a.isig[i * D + i] * pa - 2.0 * Pt[e];
+    if (a.sigma_diag) Q[i * LD + j] = isig[i * D + i] * pa - 2.0 * Pt[e];
     else P[i * LD + j] = pa;
   }
   if (tid < D) {
@@ -207,14 +209,14 @@ __global__ void __launch_bounds__(NT) k_grad(GradArgs a) {
     for (int e = tid; e < DD; e += NT) {
       const int i = e / D, j = e - i * D;
       double s = 0.0;
-      for (int l = 0; l < D; l++) s = __builtin_fma(a.isig[i * D + l], P[l * LD + j], s);
+      for (int l = 0; l < D; l++) s = __builtin_fma(isig[i * D + l], P[l * LD + j], s);
       Q[i * LD + j] = s - 2.0 * Pt[e];
     }
   }
   if (tid < D) {
     double deb;
-    if (a.sigma_diag) deb = a.isig[tid * D + tid] * rv[tid];
-    else { deb = 0.0; for (int l = 0; l < D; l++) deb = __builtin_fma(a.isig[tid * D + l], rv[l], deb); }
+    if (a.sigma_diag) deb = isig[tid * D + tid] * rv[tid];
+    else { deb = 0.0; for (int l = 0; l < D; l++) deb = __builtin_fma(isig[tid * D + l], rv[l], deb); }
     const double u = deb + a.lam[o * D + tid];
     uv[tid] = u;
     gB[tid] = a.dt * u;
@@ -268,13 +270,15 @@ __global__ void __launch_bounds__(NT) k_grad_mfma(GradArgs a) {
   constexpr int EPT = (P * P + NT - 1) / NT;
   const unsigned magic = ((1u << 20) + (unsigned)D - 1u) / (unsigned)D;   // e / D for e < 4096, 5 <= D <= 64
   double sv[EPT], pv[EPT], av[EPT], ig[EPT], ev[EPT];
+  // (per-problem parameters: Sigma^-1 at the problem's stride; theta only reaches edf_entry, which Lorenz-96 -- the band below -- skips)
+  const double* isig = a.isig + (size_t)prob * a.isig_stride;
 #pragma unroll
   for (int q = 0; q < EPT; q++) {
     const int e = tid + q * NT;
     const bool in = e < DD;
     const int i = (int)(((unsigned)(in ? e : 0) * magic) >> 20);
     sv[q] = in ? St[e] : 0.0; pv[q] = in ? Pt[e] : 0.0; av[q] = (in && !a.psi_is_q) ? At[e] : 0.0;
-    ig[q] = in ? a.isig[i * D + i] : 0.0;
+    ig[q] = in ? isig[i * D + i] : 0.0;
     ev[q] = (in && Edf) ? Edf[e] : 0.0;
   }
   const double s00 = St[0];
@@ -283,7 +287,7 @@ __global__ void __launch_bounds__(NT) k_grad_mfma(GradArgs a) {
   const double v_am = (vt && a.Am) ? a.Am[o * D + tid] : 0.0;
   const double v_ef = vt ? a.Ef[o * D + tid] : 0.0;
   const double v_b = vt ? bt[tid] : 0.0;
-  const double v_ig = vt ? a.isig[tid * D + tid] : 0.0;
+  const double v_ig = vt ? isig[tid * D + tid] : 0.0;
   const double v_lam = vt ? a.lam[o * D + tid] : 0.0;
   const bool l96_band = !Edf && a.model == VGPA_MODEL_L96;
   if (tid < P) { mv[tid] = v_m; uv[tid] = 0.0; }
@@ -420,13 +424,15 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(3, 3)))
   double sv[EPT], pv[EPT], av[QMODE ? 1 : EPT], ig[QMODE ? 1 : EPT], ev[QMODE ? 1 : EPT];
   double v_m = 0.0, v_am = 0.0, v_ef = 0.0, v_b = 0.0, v_lam = 0.0;
   const bool vt = tid < D;
-  const double v_ig = vt ? a.isig[tid * D + tid] : 0.0;
+  // (per-problem parameters: the problem's Sigma^-1 -- QMODE reads its diagonal entry once, at a 32-bit offset)
+  const int io = prob * (int)a.isig_stride;
+  const double v_ig = vt ? a.isig[io + tid * D + tid] : 0.0;
   if constexpr (!QMODE) {
 #pragma unroll
     for (int q = 0; q < EPT; q++) {               // (the diagonal of Sigma^-1 of this thread's elements: the same for every grid point)
       const int e = tid + q * NT;
       const int i = (int)(((unsigned)(e < DD ? e : 0) * magic) >> 20);
-      ig[q] = e < DD ? a.isig[i * D + i] : 0.0;
+      ig[q] = e < DD ? a.isig[io + i * D + i] : 0.0;
     }
   }
   // packed S_t (GradArgs::s_packed): this thread's flat indices e = tid + q NT of the lower triangle and their (row, column)
@@ -602,9 +608,11 @@ __global__ void __launch_bounds__(64) k_grad_small(GradArgs a) {
   const double* Pt = a.psi + o * DD;
   // every operand of the grid point is requested before the first one is used (one memory round trip per thread)
   double Av[DD], Sv[DD], Pv[DD], Ev[DD], Iv[DD], mv[D], bv[D], ef[D], lm[D];
+  const double* th = a.theta_v ? a.theta_v + (size_t)prob * kMaxTheta : a.theta;      // (per-problem parameters: the problem's row)
+  const double* isig = a.isig + (size_t)prob * a.isig_stride;
 #pragma unroll
   for (int e = 0; e < DD; e++) {
-    Av[e] = At[e]; Sv[e] = St[e]; Pv[e] = Pt[e]; Iv[e] = a.isig[e];
+    Av[e] = At[e]; Sv[e] = St[e]; Pv[e] = Pt[e]; Iv[e] = isig[e];
     Ev[e] = a.Edf ? a.Edf[o * DD + e] : 0.0;
   }
 #pragma unroll
@@ -613,7 +621,7 @@ __global__ void __launch_bounds__(64) k_grad_small(GradArgs a) {
 #pragma unroll
     for (int i = 0; i < D; i++)
 #pragma unroll
-      for (int j = 0; j < D; j++) Ev[i * D + j] = edf_entry(a.model, a.theta, D, i, j, mv, Sv[0]);
+      for (int j = 0; j < D; j++) Ev[i * D + j] = edf_entry(a.model, th, D, i, j, mv, Sv[0]);
   }
   double gAv[DD], gBv[D];
   grad_point<D>(Av, bv, mv, Sv, ef, Ev, Pv, lm, Iv, a.dt, gAv, gBv);
@@ -635,7 +643,7 @@ __global__ void __launch_bounds__(NT) k_reduce(ReduceArgs a) {
   for (int i = tid; i < a.Np - 1; i += NT) part += a.dt * (e[i + 1] + e[i]) / 2.0;
   const double tot = block_sum(part, red);
   if (tid == 0) {
-    const double esde = a.pre * tot / a.div;
+    const double esde = a.pre * tot / (a.div_v ? a.div_v[prob] : a.div);
     a.esde[prob] = esde;
     a.f[prob] = (a.e0v ? a.e0v[prob] : a.e0) + esde + a.eobs[prob];
   }
@@ -676,9 +684,11 @@ hipError_t launch_obs_dense(const ObsArgs& a, const double* js_const, double* jm
 }
 
 // Psi_t back from Q''_t = diag(isg) A_t - 2 Psi_t (the fused batched sweeps, OdeArgs::q_isg), in place: VGPA_FETCH_PSIT
-__global__ void __launch_bounds__(NT) k_psi_from_q(int Np, int D, size_t strideA, const double* A, const double* isg, double* pq) {
+__global__ void __launch_bounds__(NT) k_psi_from_q(int Np, int D, size_t strideA, const double* A, const double* isg_all, size_t isg_stride,
+                                                   double* pq) {
   const int t = blockIdx.x, prob = blockIdx.y, DD = D * D;
   const double* At = A + (size_t)prob * strideA + (size_t)t * DD;
+  const double* isg = isg_all + (size_t)prob * isg_stride;      // (per-problem parameters: the problem's diag Sigma^-1)
   double* q = pq + ((size_t)prob * Np + t) * DD;
   for (int e = threadIdx.x; e < DD; e += NT) {
     const int i = e / D;
@@ -714,8 +724,9 @@ hipError_t launch_mirror_upper(size_t n_mat, int D, double* m, hipStream_t st) {
   return hipGetLastError();
 }
 
-hipError_t launch_psi_from_q(int batch, int Np, int D, size_t strideA, const double* A, const double* isg, double* psi_q, hipStream_t st) {
-  hipLaunchKernelGGL(k_psi_from_q, dim3(Np, batch), dim3(NT), 0, st, Np, D, strideA, A, isg, psi_q);
+hipError_t launch_psi_from_q(int batch, int Np, int D, size_t strideA, const double* A, const double* isg, size_t isg_stride,
+                             double* psi_q, hipStream_t st) {
+  hipLaunchKernelGGL(k_psi_from_q, dim3(Np, batch), dim3(NT), 0, st, Np, D, strideA, A, isg, isg_stride, psi_q);
   return hipGetLastError();
 }
 

@@ -29,8 +29,10 @@ __global__ void __launch_bounds__(NT) k_energy_1d(EnergyArgs a) {
   const size_t o = (size_t)prob * a.Np + t;
   const double la = a.A[(size_t)prob * a.strideA + t], ob = a.b[(size_t)prob * a.strideB + t], m = a.m[o], s = a.S[o];
   Energy1d r;
-  if (a.model == VGPA_MODEL_OU) energy_1d<VGPA_MODEL_OU>(a.theta[0], a.sigma1, la, ob, m, s, r);
-  else energy_1d<VGPA_MODEL_DW>(a.theta[0], a.sigma1, la, ob, m, s, r);
+  const double th = a.theta_v ? a.theta_v[(size_t)prob * kMaxTheta] : a.theta[0];      // (per-problem parameters: the problem's row)
+  const double sg = a.sigma1_v ? a.sigma1_v[prob] : a.sigma1;
+  if (a.model == VGPA_MODEL_OU) energy_1d<VGPA_MODEL_OU>(th, sg, la, ob, m, s, r);
+  else energy_1d<VGPA_MODEL_DW>(th, sg, la, ob, m, s, r);
   a.e_t[o] = r.e_t;
   a.Ef[o] = r.ef;
   if (a.Edf) a.Edf[o] = r.edf;
@@ -49,12 +51,14 @@ __global__ void __launch_bounds__(64) k_energy_l63(EnergyArgs a) {
   const double* mt = a.m + o * 3;
   const double* St = a.S + o * 9;
   double Av[9], bv[3], mv[3], Sv[9], isg[3];
+  const double* th = a.theta_v ? a.theta_v + (size_t)prob * kMaxTheta : a.theta;      // (per-problem parameters: the problem's row)
+  const double* isgp = a.isg + (size_t)prob * a.isg_stride;
 #pragma unroll
   for (int e = 0; e < 9; e++) { Av[e] = At[e]; Sv[e] = St[e]; }
 #pragma unroll
-  for (int i = 0; i < 3; i++) { bv[i] = bt[i]; mv[i] = mt[i]; isg[i] = a.isg[i]; }
+  for (int i = 0; i < 3; i++) { bv[i] = bt[i]; mv[i] = mt[i]; isg[i] = isgp[i]; }
   EnergyL63 r;
-  if (a.hyp) energy_l63<true>(a.theta, isg, Av, bv, mv, Sv, r); else energy_l63<false>(a.theta, isg, Av, bv, mv, Sv, r);
+  if (a.hyp) energy_l63<true>(th, isg, Av, bv, mv, Sv, r); else energy_l63<false>(th, isg, Av, bv, mv, Sv, r);
   a.e_t[o] = r.e_t;
   double* dm = a.dEm + o * 3;
   dm[0] = r.dm[0]; dm[1] = r.dm[1]; dm[2] = r.dm[2];
@@ -71,7 +75,7 @@ __global__ void __launch_bounds__(64) k_energy_l63(EnergyArgs a) {
   }
   if (a.Edf) {
     double* e = a.Edf + o * 9;
-    const double vS = a.theta[0], vR = a.theta[1], vB = a.theta[2];
+    const double vS = th[0], vR = th[1], vB = th[2];
     e[0] = -vS; e[1] = vS; e[2] = 0.0;
     e[3] = vR - mv[2]; e[4] = -1.0; e[5] = -mv[0];
     e[6] = mv[1]; e[7] = mv[0]; e[8] = -vB;
@@ -225,7 +229,7 @@ __global__ void __launch_bounds__(64) k_energy_l96(EnergyArgs a) {
   S.dl = S.sg + Dp; S.qq = S.dl + Dp; S.rd = S.qq + Dp; S.vv = S.rd + Dp;
   const double* At = a.A + (size_t)prob * a.strideA + (size_t)t * D * D;
   const double* St = a.S + o * D * D;
-  const double theta = a.theta[0];
+  const double theta = a.theta_v ? lds_const(a.theta_v, prob * kMaxTheta) : a.theta[0];     // (per-problem parameters: a scalar load)
   const double kappa = 1.05 * D, c = D + kappa;
   const bool act = l < D;                  // lane owns a real row / column
   const bool pad = l < Dp;                 // lane owns a row / column of the padded problem
@@ -263,7 +267,7 @@ __global__ void __launch_bounds__(64) k_energy_l96(EnergyArgs a) {
     }
   }
   if (l >= D && pad) S.Lm[l * LD + l] = 1.0;
-  if (act) { S.mv[l] = a.m[o * D + l]; S.bv[l] = a.b[(size_t)prob * a.strideB + (size_t)t * D + l]; S.sg[l] = a.isg[l]; }
+  if (act) { S.mv[l] = a.m[o * D + l]; S.bv[l] = a.b[(size_t)prob * a.strideB + (size_t)t * D + l]; S.sg[l] = a.isg[(size_t)prob * a.isg_stride + l]; }
   wave_sync();
 
   // ---- 1. Cholesky, left-looking in panels of four columns (numpy.linalg.cholesky reads the lower triangle); the
@@ -571,7 +575,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NB <= 1
   const bool spk = a.s_packed != 0;                // S_t as its packed lower triangle (OdeArgs::s_packed): all the factorisation reads
   const int PK = tri_off(D);
   const double* St = a.S + o * (spk ? PK : D * D);
-  const double theta = a.theta[0];
+  const double theta = a.theta_v ? lds_const(a.theta_v, prob * kMaxTheta) : a.theta[0];     // (per-problem parameters: a scalar load)
   const double kappa = 1.05 * D, c = D + kappa;
   const bool act = l < D;
   const bool pad = l < Dp;
@@ -597,7 +601,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NB <= 1
   double sxa = 0.0, sxb = 0.0, v_m = 0.0, v_b = 0.0, v_sg = 0.0;
   double nsxa = 0.0, nsxb = 0.0;          // packed path: the two entries of the grid point whose operands are in flight
   const int f_ip1 = wrap(l + 1, D), f_im1 = wrap(l - 1, D), f_im2 = wrap(l - 2, D);
-  if (act) v_sg = a.isg[l];
+  if (act) v_sg = a.isg[(size_t)prob * a.isg_stride + l];
   auto load_vectors = [&]() {
     if (act) {
       sxa = St[f_ip1 * D + f_im1];
@@ -1068,6 +1072,7 @@ __global__ void __launch_bounds__(NT) k_edf_dense(EnergyArgs a) {
   const size_t o = (size_t)prob * a.Np + t;
   const double* mv = a.m + o * D;
   double* ed = a.Edf + o * D * D;
+  const double* th = a.theta_v ? a.theta_v + (size_t)prob * kMaxTheta : a.theta;
   for (int e = threadIdx.x; e < D * D; e += NT) {
     const int k = e / D, j = e - k * D;
     double v = 0.0;
@@ -1078,13 +1083,13 @@ __global__ void __launch_bounds__(NT) k_edf_dense(EnergyArgs a) {
       if (j == km2) v = -mv[km1];
       if (j == km1) v = mv[kp1] - mv[km2];
     } else if (a.model == VGPA_MODEL_L63) {
-      const double vS = a.theta[0], vR = a.theta[1], vB = a.theta[2];
+      const double vS = th[0], vR = th[1], vB = th[2];
       const double tab[9] = {-vS, vS, 0.0, vR - mv[2], -1.0, -mv[0], mv[1], mv[0], -vB};
       v = tab[e];
     } else if (a.model == VGPA_MODEL_OU) {
-      v = -a.theta[0];
+      v = -th[0];
     } else {
-      v = 4.0 * (a.theta[0] - 3.0 * (mv[0] * mv[0] + a.S[o]));
+      v = 4.0 * (th[0] - 3.0 * (mv[0] * mv[0] + a.S[o]));
     }
     ed[e] = v;
   }

@@ -116,12 +116,13 @@ __global__ void __launch_bounds__(NT) k_fwd_generic(OdeArgs a) {
 
   double sk[EPT], sig[EPT], r[EPT], acc1[EPT], acc2[EPT], tmp[EPT];
   double mk = 0.0;
-  const double* S0 = a.S0 + (size_t)prob * a.S0_stride;       // (strides: 0 unless per-problem data)
+  const double* S0 = a.S0 + (size_t)prob * a.S0_stride;       // (strides: 0 unless per-problem data / parameters)
+  const double* Sigma = a.Sigma + (size_t)prob * a.Sigma_stride;
 #pragma unroll
   for (int q = 0; q < EPT; q++) {
     const int e = tid + q * NT;
     sk[q] = (e < DD) ? S0[e] : 0.0;
-    sig[q] = (e < DD) ? a.Sigma[e] : 0.0;
+    sig[q] = (e < DD) ? Sigma[e] : 0.0;
     if (e < DD) { st[e] = sk[q]; l.X[e] = sk[q]; }
   }
   if (vth) { mk = a.m0[(size_t)prob * a.m0_stride + tid]; mt[tid] = mk; l.xv[tid] = mk; }

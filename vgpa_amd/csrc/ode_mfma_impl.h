@@ -441,7 +441,7 @@ __device__ __forceinline__ void p_role(const OdeArgs& a, int prob, const Lds<NB>
   const double* A = a.A + (size_t)prob * a.strideA;
   d2_t an[g::NIT];
   // forcing term per accumulator slot: forward Sigma, backward G_t / G_{t-1}, requested from HBM one step ahead
-  const double* G = FWD ? a.Sigma : a.dEs + (size_t)prob * Np * DD;
+  const double* G = FWD ? a.Sigma + (size_t)prob * a.Sigma_stride : a.dEs + (size_t)prob * Np * DD;   // (Sigma_stride: 0 unless per-problem)
   double fc[g::MAXU], fn[g::MAXU];
 #pragma unroll
   for (int s = 0; s < g::MAXU; s++) {

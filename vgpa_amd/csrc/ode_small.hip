@@ -286,7 +286,8 @@ __device__ __forceinline__ void fwd_step(const double (&A0)[D * D], const double
 
 // Forward moments, one lane per problem, streams staged through LDS in chunks of T grid points.  Step k consumes the operands of
 // grid point k+1 (slot s of the chunk) and produces (m, S) of grid point k+1: the result takes the consumed slot.
-template <int METHOD, int D, int T, bool OUT_T = false>      // OUT_T: the moments go to OdeArgs::msT straight from the registers
+// OUT_T: the moments go to OdeArgs::msT straight from the registers; PS: per-problem Sigma (OdeArgs::Sigma_stride)
+template <int METHOD, int D, int T, bool OUT_T = false, bool PS = false>
 __global__ void __launch_bounds__(NTS) __attribute__((amdgpu_waves_per_eu(1, 1))) k_fwd_lane(OdeArgs a) {
   constexpr int DD = D * D, NA = T * DD, NB = T * D;
   __shared__ double sA[ChunkMap<NA>::LDS];
@@ -302,7 +303,9 @@ __global__ void __launch_bounds__(NTS) __attribute__((amdgpu_waves_per_eu(1, 1))
   const size_t sS = (size_t)Np * DD, sm = (size_t)Np * D;
 
   double sk[DD], sig[DD], mk[D], A0[DD], b0[D];
-  ld_mat<D>(a.S0 + (size_t)prob * a.S0_stride, sk); ld_mat<D>(a.Sigma, sig); ld_vec<D>(a.m0 + (size_t)prob * a.m0_stride, mk);   // (strides: 0 unless per-problem data)
+  // (strides: 0 unless per-problem data; PS: the lane's own Sigma, a separate instantiation -- the shared one keeps its scalar loads)
+  ld_mat<D>(a.S0 + (size_t)prob * a.S0_stride, sk); ld_mat<D>(PS ? a.Sigma + (size_t)prob * a.Sigma_stride : a.Sigma, sig);
+  ld_vec<D>(a.m0 + (size_t)prob * a.m0_stride, mk);
   ld_mat<D>(A, A0); ld_vec<D>(b, b0);
   // (S_t as its packed lower triangle, then m_t: D (D + 1) / 2 + D entries per grid point -- 9 instead of 12 at D = 3)
   constexpr int TRI = D * (D + 1) / 2, W = TRI + D;
@@ -525,8 +528,17 @@ __global__ void __launch_bounds__(NTS) k_bwd_small(OdeArgs a) {
 // ------------------------------------------------------------------------------------------------
 // E_sde terms of one grid point in the form the recursion and the gradient assembly take them: dEsde_dS as a full D x D matrix,
 // <df/dx> as a matrix (variational.py:263-281 adds it to A_t)
-template <int MODEL, int D>
-__device__ __forceinline__ void point_terms(const LaneSweepArgs& q, const double (&Av)[D * D], const double (&bv)[D], const double (&mv)[D],
+// (P: where the model parameters come from -- the kernel arguments (LaneSweepArgs), or the lane's own rows under per-problem
+//  parameters (LaneParams); both have theta, sigma1 and isg)
+template <int D>
+struct LaneParams {
+  double theta[kMaxTheta];
+  double sigma1;           // 1-D models: sigma
+  double isg[D];           // diagonal of Sigma^-1
+};
+
+template <int MODEL, int D, class P>
+__device__ __forceinline__ void point_terms(const P& q, const double (&Av)[D * D], const double (&bv)[D], const double (&mv)[D],
                                             const double (&Sv)[D * D], double (&gs)[D * D], double (&gm)[D], double& e_t, double (&ef)[D],
                                             double (&edf)[D * D]) {
 #pragma clang fp contract(fast)
@@ -554,7 +566,8 @@ __device__ __forceinline__ void point_terms(const LaneSweepArgs& q, const double
 // The fused pass (see the head of this file).  Chunk c holds grid points [hi - T + 1, hi], hi = Np - 2 - c T; step s of the chunk
 // goes from t = hi - s + 1 to t - 1 = hi - s, whose operands sit in slot T - 1 - s; gLa / gLb of t - 1 take the slots of A / b.
 // PT: per-problem observation times (OdeArgs::obs_idx_stride): the observation index, and with it the jump, is the lane's own.
-template <int METHOD, int MODEL, bool GRAD, int T, bool PT = false>
+// PP: per-problem parameters (LaneSweepArgs::theta_v ...): each lane loads its own theta, sigma and Sigma^-1 once, before the time loop.
+template <int METHOD, int MODEL, bool GRAD, int T, bool PT = false, bool PP = false>
 __global__ void __launch_bounds__(NTS) __attribute__((amdgpu_waves_per_eu(1, 1))) k_sweep_lane(LaneSweepArgs q) {
   constexpr int D = (MODEL == VGPA_MODEL_L63) ? 3 : 1, DD = D * D, NA = T * DD, NV = T * D;
   __shared__ double sA[ChunkMap<NA>::LDS];
@@ -586,8 +599,19 @@ __global__ void __launch_bounds__(NTS) __attribute__((amdgpu_waves_per_eu(1, 1))
   };
 
   double Iv[DD];
+  LaneParams<D> own;       // (PP only; the shared path reads the kernel arguments as before)
+  if constexpr (PP) {
 #pragma unroll
-  for (int e = 0; e < DD; e++) Iv[e] = q.isig[e];
+    for (int i = 0; i < kMaxTheta; i++) own.theta[i] = q.theta_v[(size_t)prob * kMaxTheta + i];
+    own.sigma1 = q.sigma1_v[prob];
+#pragma unroll
+    for (int e = 0; e < DD; e++) Iv[e] = q.isig_v[(size_t)prob * DD + e];
+#pragma unroll
+    for (int i = 0; i < D; i++) own.isg[i] = Iv[i * D + i];
+  } else {
+#pragma unroll
+    for (int e = 0; e < DD; e++) Iv[e] = q.isig[e];
+  }
 
   // grid point Np - 1: operands straight from HBM (once), Psi = 0, lam = 0
   double At[DD], gst[DD], gmt[D], e_t, pk[DD], lk[D];
@@ -596,7 +620,8 @@ __global__ void __launch_bounds__(NTS) __attribute__((amdgpu_waves_per_eu(1, 1))
     ld_mat<D>(a.A + (size_t)prob * a.strideA + (size_t)(Np - 1) * DD, At);
     ld_vec<D>(a.b + (size_t)prob * a.strideB + (size_t)(Np - 1) * D, bt);
     load_ms(Np - 1, St, mt);
-    point_terms<MODEL, D>(q, At, bt, mt, St, gst, gmt, e_t, ef, edf);
+    if constexpr (PP) point_terms<MODEL, D>(own, At, bt, mt, St, gst, gmt, e_t, ef, edf);
+    else point_terms<MODEL, D>(q, At, bt, mt, St, gst, gmt, e_t, ef, edf);
 #pragma unroll
     for (int e = 0; e < DD; e++) pk[e] = 0.0;
 #pragma unroll
@@ -695,7 +720,8 @@ __global__ void __launch_bounds__(NTS) __attribute__((amdgpu_waves_per_eu(1, 1))
         for (int e = 0; e < DD; e++) { Am[e] = rowA[slot * DD + e]; Sm[e] = Sc[e]; }
 #pragma unroll
         for (int i = 0; i < D; i++) { bm[i] = rowB[slot * D + i]; mm[i] = mc[i]; }
-        point_terms<MODEL, D>(q, Am, bm, mm, Sm, gsm, gmm, e_m, ef, edf);
+        if constexpr (PP) point_terms<MODEL, D>(own, Am, bm, mm, Sm, gsm, gmm, e_m, ef, edf);
+        else point_terms<MODEL, D>(q, Am, bm, mm, Sm, gsm, gmm, e_m, ef, edf);
         esum += dt * (e_t + e_m) / 2.0;     // my_trapz, utilities.py:144 (interval [t-1, t])
         e_t = e_m;
         if (GRAD) {
@@ -733,7 +759,9 @@ __global__ void __launch_bounds__(NTS) __attribute__((amdgpu_waves_per_eu(1, 1))
     wave_sync();
   }
   if (live) {
-    const double esde = q.pre * esum / q.div;
+    double esde;
+    if constexpr (PP && D == 1) esde = q.pre * esum / own.sigma1;      // (1-D models divide E_sde by the lane's own sigma)
+    else esde = q.pre * esum / q.div;
     q.esde[prob] = esde;
     q.f[prob] = (q.e0v ? q.e0v[prob] : q.e0) + esde + q.eobs[prob];
   }
@@ -746,12 +774,14 @@ hipError_t launch_d(const OdeArgs& a, hipStream_t st) {
   if (FWD && a.msT) {
     if constexpr (D == 1 || D == 3) {      // (the models of the fused lane pass)
       constexpr int TT = D == 3 ? 6 : 16;
-      hipLaunchKernelGGL((k_fwd_lane<METHOD, D, TT, true>), grid, block, 0, st, a);
+      if (a.Sigma_stride) hipLaunchKernelGGL((k_fwd_lane<METHOD, D, TT, true, true>), grid, block, 0, st, a);
+      else hipLaunchKernelGGL((k_fwd_lane<METHOD, D, TT, true>), grid, block, 0, st, a);
       return hipGetLastError();
     }
     return hipErrorInvalidValue;
   }
-  if (FWD) hipLaunchKernelGGL((k_fwd_lane<METHOD, D, T>), grid, block, 0, st, a);
+  if (FWD && a.Sigma_stride) hipLaunchKernelGGL((k_fwd_lane<METHOD, D, T, false, true>), grid, block, 0, st, a);
+  else if (FWD) hipLaunchKernelGGL((k_fwd_lane<METHOD, D, T>), grid, block, 0, st, a);
   else hipLaunchKernelGGL((k_bwd_small<METHOD, D>), grid, block, 0, st, a);
   return hipGetLastError();
 }
@@ -767,6 +797,12 @@ hipError_t launch_m(const OdeArgs& a, hipStream_t st) {
   return hipErrorInvalidValue;
 }
 
+template <int METHOD, int MODEL, int T, bool PT, bool PP>
+void launch_sweep_lane_k(const LaneSweepArgs& q, dim3 grid, dim3 block, hipStream_t st) {
+  if (q.want_grad) hipLaunchKernelGGL((k_sweep_lane<METHOD, MODEL, true, T, PT, PP>), grid, block, 0, st, q);
+  else hipLaunchKernelGGL((k_sweep_lane<METHOD, MODEL, false, T, PT, PP>), grid, block, 0, st, q);
+}
+
 template <int METHOD, int MODEL>
 hipError_t launch_sweep_mm(const LaneSweepArgs& q, hipStream_t st) {
   dim3 grid((q.o.batch + NTS - 1) / NTS), block(NTS);
@@ -775,12 +811,13 @@ hipError_t launch_sweep_mm(const LaneSweepArgs& q, hipStream_t st) {
   // a vector memory operation the compiler waits for with vmcnt(0), i.e. together with every request in flight.  Same box, T = 4 | 6:
   // 4.67 | 5.16-5.49 ms per 65536 problems.
   constexpr int T = (MODEL == VGPA_MODEL_L63) ? 4 : 16;
-  if (q.o.obs_idx_stride) {
-    if (!q.o.jmT) return hipErrorInvalidValue;      // (per-problem times read the jumps from jmT)
-    if (q.want_grad) hipLaunchKernelGGL((k_sweep_lane<METHOD, MODEL, true, T, true>), grid, block, 0, st, q);
-    else hipLaunchKernelGGL((k_sweep_lane<METHOD, MODEL, false, T, true>), grid, block, 0, st, q);
-  } else if (q.want_grad) hipLaunchKernelGGL((k_sweep_lane<METHOD, MODEL, true, T>), grid, block, 0, st, q);
-  else hipLaunchKernelGGL((k_sweep_lane<METHOD, MODEL, false, T>), grid, block, 0, st, q);
+  if (q.o.obs_idx_stride && !q.o.jmT) return hipErrorInvalidValue;      // (per-problem times read the jumps from jmT)
+  if (q.theta_v) {
+    if (!q.sigma1_v || !q.isig_v) return hipErrorInvalidValue;
+    if (q.o.obs_idx_stride) launch_sweep_lane_k<METHOD, MODEL, T, true, true>(q, grid, block, st);
+    else launch_sweep_lane_k<METHOD, MODEL, T, false, true>(q, grid, block, st);
+  } else if (q.o.obs_idx_stride) launch_sweep_lane_k<METHOD, MODEL, T, true, false>(q, grid, block, st);
+  else launch_sweep_lane_k<METHOD, MODEL, T, false, false>(q, grid, block, st);
   return hipGetLastError();
 }
 

@@ -386,7 +386,8 @@ __device__ __forceinline__ void grad_waves(const OdeArgs& a, double* __restrict_
   const int lane = tid & 63, wave = tid >> 6;
   const int r4 = lane >> 4, bq = (lane >> 2) & 3, c4 = lane & 3;
   const int prob = (int)blockIdx.x, D = a.D, Np = a.Np, DD = a.D * a.D, n_steps = a.Np - 1, PK = a.D * (a.D + 1) / 2;
-  const double dt = a.dt, hq = -0.5 * a.q_scale, m2dt = -2.0 * a.dt;
+  // (per-problem parameters: the problem's 1 / sigma_p^2, a scalar load -- prob is uniform)
+  const double dt = a.dt, hq = -0.5 * (a.q_scale_v ? lds_const(a.q_scale_v, prob) : a.q_scale), m2dt = -2.0 * a.dt;
   char* const lds = reinterpret_cast<char*>(smem);
   auto rd2 = [&](unsigned off) -> d2_t { return *reinterpret_cast<const d2_t*>(lds + off); };
   auto rd1 = [&](unsigned off) -> double { return *reinterpret_cast<const double*>(lds + off); };
@@ -704,6 +705,8 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3
   const int prob = (int)blockIdx.x;
   const int D = a.D, Np = a.Np, DD = a.D * a.D, n_steps = a.Np - 1;
   const double dt = a.dt, h = 0.5 * a.dt;
+  // QOUT's factor: the problem's own 1 / sigma_p^2 under per-problem parameters (a scalar load at entry -- prob is uniform)
+  const double q_scale = a.q_scale_v ? lds_const(a.q_scale_v, prob) : a.q_scale;
   double* const Xb0 = smem;
   double* const Xb1 = Xb0 + g::XS;
   double* const Rb = Xb1 + g::XS;
@@ -815,7 +818,7 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3
   };
   // ---- matrix state -----------------------------------------------------------------------------------------------------
   const int GS = (!FWD && a.ds_packed) ? D * (D + 1) / 2 : DD;      // doubles per matrix of the forcing-term stream
-  const double* G = FWD ? a.Sigma : a.dEs + (size_t)prob * Np * GS;
+  const double* G = FWD ? a.Sigma + (size_t)prob * a.Sigma_stride : a.dEs + (size_t)prob * Np * GS;   // (Sigma_stride: 0 unless per-problem)
   double* const mout = (FWD ? a.S : a.psi) + (size_t)prob * Np * (spk ? D * (D + 1) / 2 : DD);
   double xk[MAXS], acc[MAXS], fc[MAXS], fn[MAXS], fnn[MAXS];
 #pragma unroll
@@ -988,7 +991,7 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3
   // QOUT: items of Psi_t -> items of Q''_t, with the start-point operand A_t in the same row-pair items
   auto to_q = [&](d2_t (&items)[g::NIT], const d2_t (&a0)[NITS]) {
     if constexpr (QOUT) {
-      const double qs = a.q_scale;
+      const double qs = q_scale;
 #pragma unroll
       for (int q = 0; q < g::NIT; q++) {
         items[q][0] = __builtin_fma(qs, a0[q][0], -2.0 * items[q][0]);

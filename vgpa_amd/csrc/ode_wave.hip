@@ -94,7 +94,8 @@ __global__ void __launch_bounds__(NTW) k_fwd_wave(OdeArgs a) {
   const double dt = a.dt, h = 0.5 * a.dt;
   const bool wm = live && mat, wv = live && vec;
 
-  double sk = a.S0[(size_t)prob * a.S0_stride + em], sig = a.Sigma[em], mk = a.m0[(size_t)prob * a.m0_stride + ev];   // (strides: 0 unless per-problem data)
+  double sk = a.S0[(size_t)prob * a.S0_stride + em], sig = a.Sigma[(size_t)prob * a.Sigma_stride + em],
+         mk = a.m0[(size_t)prob * a.m0_stride + ev];   // (strides: 0 unless per-problem data / parameters)
   if (wm) st[0] = sk;
   if (wv) mt[0] = mk;
   double a0 = A[0], b0 = b[0];

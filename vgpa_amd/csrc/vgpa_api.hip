@@ -85,6 +85,16 @@ struct vgpa_ctx {
   double *d_jm_pt = nullptr, *d_js_pt = nullptr;   // dense jumps [B][Np][D], [B][Np][D][D]: per-problem times on the 16-lane kernels
   bool pt_dense_zeroed = false;      // ... zero off the observation rows of the current times (each sweep rewrites only those rows)
   bool sym_inputs_shared = true;     // sym_inputs as vgpa_create found it (Sigma, the shared s0, the constant jump)
+  bool pp_s0_sym = true;             // ... and of the per-problem s0 rows / Sigma rows (sym_inputs is the conjunction)
+  // per-problem parameters (vgpa_set_problem_params): once set, every row of each array below is in force (a row the caller left
+  // shared holds the shared value); rows that all equal the shared parameters keep the shared kernels
+  bool pp_par = false, pp_sigma_sym = true;
+  double* d_pp_theta = nullptr;      // [B][kMaxTheta]
+  double *d_pp_Sigma = nullptr, *d_pp_isig = nullptr, *d_pp_isg = nullptr;   // [B][D][D], [B][D][D] Sigma^-1, [B][D] its diagonal
+  double *d_pp_sig1 = nullptr, *d_pp_qs = nullptr;                           // [B] 1-D sigma, [B] 1 / sigma_p^2 of an isotropic row
+  std::vector<double> h_pp_theta, h_pp_isig, h_pp_sig1;                      // host copies (energy_full, the D > 64 energy terms)
+  std::vector<double> h_sigma;       // host copy of the shared Sigma [D][D]
+  bool sigma_diag_shared = true, isg_iso_shared = false;   // the kernel-family flags of the shared Sigma
   // profiling
   bool prof = false;
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -182,6 +192,8 @@ static int ingest_ab(vgpa_ctx* c, const double* lin_a, const double* off_b) {
 // the initial moments of the sweeps: the per-problem rows once vgpa_set_problem_data has set them (run_fwd tells them by address)
 static inline const double* sweep_m0(vgpa_ctx* c) { return c->pp_m0 ? c->d_pp_m0 : c->d_m0; }
 static inline const double* sweep_S0(vgpa_ctx* c) { return c->pp_S0 ? c->d_pp_S0 : c->d_S0; }
+// ... and the forcing term Sigma: the per-problem rows once vgpa_set_problem_params has set them (run_fwd tells them by address)
+static inline const double* sweep_Sigma(vgpa_ctx* c) { return c->pp_par ? c->d_pp_Sigma : c->d_Sigma; }
 
 static void prof_mark(vgpa_ctx* c, int i) {
   if (c->prof) (void)hipEventRecord(c->ev[i], c->stream);
@@ -293,6 +305,7 @@ static int run_fwd(vgpa_ctx* c, const double* m0, const double* S0, const double
   a.A = ctx_A(c); a.b = ctx_b(c); a.m0 = m0; a.S0 = S0; a.Sigma = Sigma; a.m = c->d_m; a.S = c->d_S;
   a.m0_stride = m0 == c->d_pp_m0 ? (size_t)c->D : 0;
   a.S0_stride = S0 == c->d_pp_S0 ? c->DD : 0;
+  a.Sigma_stride = Sigma == c->d_pp_Sigma ? c->DD : 0;
   a.s_packed = c->s_packed ? 1 : 0;
   hipError_t e = use_lane(c) ? launch_ode_small(c->cfg.method, true, a, c->stream)
                  : use_wave(c) ? launch_ode_wave(c->cfg.method, true, a, c->stream)
@@ -355,6 +368,7 @@ static int run_bwd(vgpa_ctx* c, bool dense_jumps, bool sym, double* g_fused = nu
                 c->cfg.model == VGPA_MODEL_L96 && !(c->cfg.flags & VGPA_FLAG_KEEP_PSI) && sym_stores_q(c->cfg.method, c->D);
   a.q_on = c->psi_is_q ? 1 : 0;
   a.q_scale = c->isg0;
+  a.q_scale_v = c->pp_par ? c->d_pp_qs : nullptr;      // (read only by the Q'' kernels: every row isotropic then)
   if (g_fused) {                           // the gradient assembly on the kernel's helper waves (k_ode_sym, GF)
     if (!c->psi_is_q) return fail(c, VGPA_ERR_STATE, "fused gradient assembly: the backward kernel is not the Q'' one");
     a.grad_on = 1; a.g = g_fused; a.s_packed = 1;
@@ -377,6 +391,7 @@ static EnergyArgs energy_args(vgpa_ctx* c, double* edf, bool ds_upper = false) {
   a.model = c->cfg.model; a.D = c->D; a.Np = c->Np; a.batch = c->B; a.dt = c->cfg.dt;
   for (int i = 0; i < kMaxTheta; i++) a.theta[i] = c->theta[i];
   a.sigma1 = c->sigma1; a.isg = c->d_isg;
+  if (c->pp_par) { a.theta_v = c->d_pp_theta; a.sigma1_v = c->d_pp_sig1; a.isg = c->d_pp_isg; a.isg_stride = (size_t)c->D; }
   a.strideA = a.strideB = c->len_x;
   a.A = ctx_A(c); a.b = ctx_b(c); a.m = c->d_m; a.S = c->d_S;
   a.e_t = c->d_et; a.Ef = c->d_Ef; a.Edf = edf; a.dEm = c->d_dEm; a.dEs = c->d_dEs; a.status = c->d_status;
@@ -406,8 +421,9 @@ static int run_energy(vgpa_ctx* c, double* edf, bool ds_upper = false, bool ds_p
     if (rc) return rc;
     // the energy terms are batched over grid points already: problem by problem
     const size_t NpD = (size_t)c->Np * c->D, NpDD = (size_t)c->Np * c->DD;
-    for (int p = 0; p < c->B; p++) {
-      hipError_t e = ld::lde_energy(c->D, c->Np, c->theta[0], c->d_isg, ctx_A(c) + p * c->len_x, ctx_b(c) + p * c->len_x, c->d_m + p * NpD,
+    for (int p = 0; p < c->B; p++) {      // (per-problem parameters: the problem's theta; Sigma is shared above D = 64)
+      const double th = c->pp_par ? c->h_pp_theta[(size_t)p * kMaxTheta] : c->theta[0];
+      hipError_t e = ld::lde_energy(c->D, c->Np, th, c->d_isg, ctx_A(c) + p * c->len_x, ctx_b(c) + p * c->len_x, c->d_m + p * NpD,
                                     c->d_S + p * NpDD, c->d_et + (size_t)p * c->Np, c->d_Ef + p * NpD, edf ? edf + p * NpDD : nullptr,
                                     c->d_dEm + p * NpD, c->d_dEs + p * NpDD, c->d_status + p, c->d_lde_ws, c->lde_nb, c->stream,
                                     c->hyp_on ? c->d_hyp + (size_t)p * c->Np * 2 * c->D : nullptr, c->stream2);
@@ -440,6 +456,7 @@ static int run_reduce(vgpa_ctx* c) {
   ReduceArgs r{};
   r.Np = c->Np; r.batch = c->B; r.dt = c->cfg.dt; r.e0 = c->cfg.e0; r.e0v = c->pp_e0 ? c->d_pp_e0 : nullptr;
   r.pre = c->single ? 0.5 : 1.0; r.div = c->single ? c->sigma1 : 1.0;
+  r.div_v = (c->single && c->pp_par) ? c->d_pp_sig1 : nullptr;
   r.e_t = c->d_et; r.eobs = c->d_eobs; r.esde = c->d_esde; r.f = c->d_f;
   hipError_t e = launch_reduce(r, c->stream);
   if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "reduce launch failed: %s", hipGetErrorString(e));
@@ -468,6 +485,7 @@ static int run_grad(vgpa_ctx* c, double* g_dev) {
   for (int i = 0; i < kMaxTheta; i++) a.theta[i] = c->theta[i];
   a.strideA = a.strideB = c->len_x;
   a.isig = c->d_isig; a.A = ctx_A(c); a.b = ctx_b(c); a.m = c->d_m; a.S = c->d_S; a.lam = c->d_lam; a.psi = c->d_psi;
+  if (c->pp_par) { a.theta_v = c->d_pp_theta; a.isig = c->d_pp_isig; a.isig_stride = c->DD; }
   a.Ef = c->d_Ef; a.Edf = nullptr; a.g = g_dev;
   a.psi_is_q = c->psi_is_q ? 1 : 0;
   a.s_packed = (c->s_packed && c->psi_is_q) ? 1 : 0;
@@ -553,7 +571,7 @@ static int enqueue_stream_sweep(vgpa_ctx* c, double* g_dev) {
   HIP_TRY(c, hipMemsetAsync(c->d_status, 0, sizeof(int32_t) * c->B, c->stream));
   c->s_packed = false;
   prof_mark(c, 0);
-  if ((rc = run_fwd(c, sweep_m0(c), sweep_S0(c), c->d_Sigma, c->sym_inputs))) return rc;
+  if ((rc = run_fwd(c, sweep_m0(c), sweep_S0(c), sweep_Sigma(c), c->sym_inputs))) return rc;
   prof_mark(c, 1);
   hipError_t e = launch_obs(obs_args(c), c->stream);
   if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "obs launch failed: %s", hipGetErrorString(e));
@@ -593,6 +611,7 @@ static int run_lane_pass(vgpa_ctx* c, double* g_dev) {
   for (int i = 0; i < c->D; i++) q.isg[i] = c->h_isig[(size_t)i * c->D + i];
   for (size_t e = 0; e < c->DD; e++) q.isig[e] = c->h_isig[e];
   q.e0 = c->cfg.e0; q.e0v = c->pp_e0 ? c->d_pp_e0 : nullptr; q.pre = c->single ? 0.5 : 1.0; q.div = c->single ? c->sigma1 : 1.0;
+  if (c->pp_par) { q.theta_v = c->d_pp_theta; q.sigma1_v = c->d_pp_sig1; q.isig_v = c->d_pp_isig; }
   q.eobs = c->d_eobs; q.esde = c->d_esde; q.f = c->d_f; q.g = g_dev;
   hipError_t e = launch_sweep_lane(c->cfg.method, q, c->stream);
   if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "fused lane pass launch failed: %s", hipGetErrorString(e));
@@ -614,8 +633,8 @@ static int enqueue_lane_sweep(vgpa_ctx* c, double* g_dev) {
     OdeArgs a{};
     a.D = c->D; a.Np = c->Np; a.batch = c->B; a.dt = c->cfg.dt;
     a.strideA = a.strideB = c->len_x;
-    a.A = ctx_A(c); a.b = ctx_b(c); a.m0 = sweep_m0(c); a.S0 = sweep_S0(c); a.Sigma = c->d_Sigma; a.m = c->d_m; a.S = c->d_S;
-    a.m0_stride = c->pp_m0 ? (size_t)c->D : 0; a.S0_stride = c->pp_S0 ? c->DD : 0;
+    a.A = ctx_A(c); a.b = ctx_b(c); a.m0 = sweep_m0(c); a.S0 = sweep_S0(c); a.Sigma = sweep_Sigma(c); a.m = c->d_m; a.S = c->d_S;
+    a.m0_stride = c->pp_m0 ? (size_t)c->D : 0; a.S0_stride = c->pp_S0 ? c->DD : 0; a.Sigma_stride = c->pp_par ? c->DD : 0;
     a.msT = c->d_msT; a.bpad = c->bpad;
     hipError_t ef = launch_ode_small(c->cfg.method, true, a, c->stream);
     if (ef != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "forward lane kernel launch failed: %s", hipGetErrorString(ef));
@@ -709,7 +728,7 @@ static int enqueue_free_energy(vgpa_ctx* c) {
   HIP_TRY(c, hipMemsetAsync(c->d_status, 0, sizeof(int32_t) * c->B, c->stream));
   prof_mark(c, 0);
   for (int r = diag_repeat("fwd"); r > 0; r--)
-    if ((rc = run_fwd(c, sweep_m0(c), sweep_S0(c), c->d_Sigma, c->sym_inputs))) return rc;
+    if ((rc = run_fwd(c, sweep_m0(c), sweep_S0(c), sweep_Sigma(c), c->sym_inputs))) return rc;
   prof_mark(c, 1);
   hipError_t e = launch_obs(obs_args(c), c->stream);
   if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "obs launch failed: %s", hipGetErrorString(e));
@@ -880,6 +899,7 @@ int vgpa_create(vgpa_ctx** out, const vgpa_config* cfg) {
   HTRY(hipMemsetAsync(c->d_jsc, 0, sizeof(double) * DD, c->stream));
 
   TRY(upload(c, c->d_Sigma, sigma.data(), DD));
+  c->h_sigma = sigma;
   c->h_isig = isig;
   TRY(upload(c, c->d_isig, isig.data(), DD));
   TRY(upload(c, c->d_isg, isg.data(), (size_t)D));
@@ -979,6 +999,8 @@ int vgpa_create(vgpa_ctx** out, const vgpa_config* cfg) {
   }
   HTRY(hipStreamSynchronize(c->stream));
   c->sym_inputs_shared = c->sym_inputs;
+  c->sigma_diag_shared = c->sigma_diag;
+  c->isg_iso_shared = c->isg_iso;
 #undef TRY
 #undef HTRY
   *out = c;
@@ -1091,11 +1113,12 @@ int vgpa_energy_full(vgpa_ctx* c, const double* lin_a, const double* off_b, cons
   for (int p = 0; p < c->B; p++) {
     const double* Tp = T.data() + (size_t)p * H;
     if (c->single) {
-      desde_dth[p] = (c->cfg.model == VGPA_MODEL_DW ? 4.0 : 1.0) * Tp[0] / c->sigma1;
-      desde_dsig[p] = -esde[p] / c->sigma1;
+      const double s1 = c->pp_par ? c->h_pp_sig1[p] : c->sigma1;      // (per-problem parameters: the problem's own)
+      desde_dth[p] = (c->cfg.model == VGPA_MODEL_DW ? 4.0 : 1.0) * Tp[0] / s1;
+      desde_dsig[p] = -esde[p] / s1;
       continue;
     }
-    const double* is = c->h_isig.data();
+    const double* is = c->pp_par ? c->h_pp_isig.data() + (size_t)p * c->DD : c->h_isig.data();
     for (int i = 0; i < D; i++) desde_dth[(size_t)p * D + i] = is[(size_t)i * D + i] * Tp[i];
     double* out = desde_dsig + (size_t)p * D * D;          // -0.5 * Sigma^-1 diag(v) Sigma^-1
     for (int i = 0; i < D; i++)
@@ -1299,7 +1322,8 @@ int vgpa_fetch(vgpa_ctx* c, int which, double* out) {
     case VGPA_FETCH_PSIT:
       if (!c->d_psi || c->stream_ld) return fail(c, VGPA_ERR_UNSUPPORTED, "Psi_t is not kept by the time-chunked large-D sweep");
       if (c->psi_is_q) {               // recover Psi_t = (Sigma^-1 A_t - Q''_t) / 2 in place: from here on d_psi holds Psi_t again
-        hipError_t e = launch_psi_from_q(c->B, c->Np, c->D, c->len_x, ctx_A(c), c->d_isg, c->d_psi, c->stream);
+        hipError_t e = launch_psi_from_q(c->B, c->Np, c->D, c->len_x, ctx_A(c), c->pp_par ? c->d_pp_isg : c->d_isg,
+                                         c->pp_par ? (size_t)c->D : 0, c->d_psi, c->stream);
         if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "Psi_t recovery launch failed: %s", hipGetErrorString(e));
         c->psi_is_q = false;
       }
@@ -1445,7 +1469,8 @@ int vgpa_set_problem_data(vgpa_ctx* c, const int64_t* obs_t, const double* obs_y
   int rc;
   // every call states the whole per-problem set: an input passed as NULL is the shared one of vgpa_config again
   c->pp_obs_t = c->pp_obs_y = c->pp_m0 = c->pp_S0 = c->pp_e0 = false;
-  c->sym_inputs = c->sym_inputs_shared && (!s0 || stack_symmetric(s0, (size_t)B, D));   // (a non-symmetric s0 row: both products literally)
+  c->pp_s0_sym = !s0 || stack_symmetric(s0, (size_t)B, D);       // (a non-symmetric s0 row: both products literally)
+  c->sym_inputs = c->sym_inputs_shared && c->pp_s0_sym && c->pp_sigma_sym;
   c->pt_dense_zeroed = false;
   if (obs_t && M > 0) {
     std::vector<int32_t> idx((size_t)B * Np, -1);
@@ -1485,6 +1510,86 @@ int vgpa_set_problem_data(vgpa_ctx* c, const int64_t* obs_t, const double* obs_y
   }
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->have_state = false;            // (like vgpa_release_x: the cached state belongs to the old inputs)
+  return VGPA_OK;
+}
+
+// Per-problem parameters of a batched context (see vgpa_hip.h).  Every row is validated and its constants computed on the host, as
+// vgpa_create computes the shared ones, before anything changes: after an error the previous parameters stay in force.
+int vgpa_set_problem_params(vgpa_ctx* c, const double* theta, const double* sigma) {
+  if (!c) return VGPA_ERR_ARG;
+  if (c->cfg.model == VGPA_MODEL_NONE) return fail(c, VGPA_ERR_STATE, "context has no stochastic model (ODE-only): no parameters to set");
+  if (c->stream_ld && (theta || sigma))
+    return fail(c, VGPA_ERR_UNSUPPORTED, "the time-chunked large-D sweep holds one problem: no per-problem parameters");
+  const int D = c->D, B = c->B, nth = c->cfg.n_theta;
+  const size_t DD = c->DD;
+  std::vector<double> th((size_t)B * kMaxTheta), sg((size_t)B * DD), is((size_t)B * DD, 0.0), ig((size_t)B * D, 0.0), s1(B, 1.0), qs(B, 1.0);
+  bool diag = true, iso = true, sym = true, same_theta = true, same_sigma = true;
+  for (int p = 0; p < B; p++) {
+    double* tp = th.data() + (size_t)p * kMaxTheta;
+    for (int i = 0; i < kMaxTheta; i++) tp[i] = (theta && i < nth) ? theta[(size_t)p * nth + i] : c->theta[i];
+    same_theta = same_theta && std::memcmp(tp, c->theta, sizeof(double) * kMaxTheta) == 0;
+    double* sp = sg.data() + p * DD;
+    std::memcpy(sp, sigma ? sigma + p * DD : c->h_sigma.data(), sizeof(double) * DD);
+    same_sigma = same_sigma && std::memcmp(sp, c->h_sigma.data(), sizeof(double) * DD) == 0;
+    double* ip = is.data() + p * DD;
+    double* gp = ig.data() + (size_t)p * D;
+    if (c->single) {
+      if (!(sp[0] > 0.0)) return fail(c, VGPA_ERR_ARG, "problem %d: the diffusion noise value: %g, should be strictly positive.", p, sp[0]);
+      s1[p] = sp[0]; ip[0] = 1.0 / sp[0]; gp[0] = ip[0];
+    } else {
+      bool rd = true;
+      for (int i = 0; i < D && rd; i++)
+        for (int j = 0; j < D; j++)
+          if (i != j && sp[(size_t)i * D + j] != 0.0) { rd = false; break; }
+      if (rd) {        // (vgpa_create's diagonal shortcut)
+        for (int i = 0; i < D; i++) {
+          const double sii = sp[(size_t)i * D + i];
+          if (!(sii > 0.0)) return fail(c, VGPA_ERR_NOT_PD, "problem %d: noise matrix is not positive definite.", p);
+          const double ci = 1.0 / std::sqrt(sii);
+          ip[(size_t)i * D + i] = ci * ci;
+          gp[i] = ci * ci;
+        }
+      } else {
+        if (!host_spd_inverse(D, sp, ip, nullptr)) return fail(c, VGPA_ERR_NOT_PD, "problem %d: noise matrix is not positive definite.", p);
+        for (int i = 0; i < D; i++) gp[i] = ip[(size_t)i * D + i];
+      }
+      diag = diag && rd;
+      for (int i = 1; i < D; i++) iso = iso && gp[i] == gp[0];
+      sym = sym && is_symmetric(sp, D);
+    }
+    qs[p] = gp[0];
+  }
+  if (D > kMaxSmallD && !same_sigma)
+    return fail(c, VGPA_ERR_UNSUPPORTED, "per-problem Sigma exists for D <= %d (D = %d shares the Sigma of vgpa_config)", kMaxSmallD, D);
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  c->have_state = false;            // (like vgpa_set_problem_data: the cached state belongs to the old parameters)
+  if (same_theta && same_sigma) {   // every row at the shared parameters: the shared kernels (the same results, bit for bit)
+    c->pp_par = false;
+    c->sigma_diag = c->sigma_diag_shared; c->isg_iso = c->isg_iso_shared; c->pp_sigma_sym = true;
+    c->sym_inputs = c->sym_inputs_shared && c->pp_s0_sym;
+    return VGPA_OK;
+  }
+  int rc;
+  if ((rc = ensure(c, &c->d_pp_theta, (size_t)B * kMaxTheta))) return rc;
+  if ((rc = ensure(c, &c->d_pp_Sigma, (size_t)B * DD))) return rc;
+  if ((rc = ensure(c, &c->d_pp_isig, (size_t)B * DD))) return rc;
+  if ((rc = ensure(c, &c->d_pp_isg, (size_t)B * D))) return rc;
+  if ((rc = ensure(c, &c->d_pp_sig1, (size_t)B))) return rc;
+  if ((rc = ensure(c, &c->d_pp_qs, (size_t)B))) return rc;
+  if ((rc = upload(c, c->d_pp_theta, th.data(), th.size()))) return rc;
+  if ((rc = upload(c, c->d_pp_Sigma, sg.data(), sg.size()))) return rc;
+  if ((rc = upload(c, c->d_pp_isig, is.data(), is.size()))) return rc;
+  if ((rc = upload(c, c->d_pp_isg, ig.data(), ig.size()))) return rc;
+  if ((rc = upload(c, c->d_pp_sig1, s1.data(), s1.size()))) return rc;
+  if ((rc = upload(c, c->d_pp_qs, qs.data(), qs.size()))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));          // (the host rows live on this stack frame)
+  c->h_pp_theta = std::move(th); c->h_pp_isig = std::move(is); c->h_pp_sig1 = std::move(s1);
+  c->pp_par = true;
+  // the kernel family: the conjunction over the rows (isotropic: every row sigma_p^2 I with its own sigma_p)
+  c->sigma_diag = c->single || diag;
+  c->isg_iso = c->single || (diag && iso);
+  c->pp_sigma_sym = sym;
+  c->sym_inputs = c->sym_inputs_shared && c->pp_s0_sym && c->pp_sigma_sym;
   return VGPA_OK;
 }
 

@@ -91,6 +91,9 @@ struct OdeArgs {
   // per-problem data (vgpa_set_problem_data), last so that the kernel-argument offsets of everything above stay where they were
   size_t m0_stride, S0_stride;   // elements between consecutive problems' m0 / S0; 0: shared by the batch
   int obs_idx_stride;            // Np: obs_idx is [B][Np]; 0: the observation times are shared by the batch
+  // per-problem parameters (vgpa_set_problem_params), last for the same reason
+  size_t Sigma_stride;           // D*D: Sigma is [B][D][D]; 0: shared by the batch
+  const double* q_scale_v;       // [B] 1 / sigma_p^2 instead of q_scale, or nullptr
 };
 
 // Fused lane-per-problem pass of the models with closed-form moments (OU, double well, Lorenz-63; ode_small.hip::k_sweep_lane):
@@ -109,6 +112,10 @@ struct LaneSweepArgs {
   double* f;               // [B]
   double* g;               // [B][Np*D*D + Np*D] (want_grad)
   const double* e0v;       // [B] per-problem e0 instead of e0, or nullptr (last: the offsets above stay where they were)
+  // per-problem parameters (vgpa_set_problem_params): all three set or all nullptr; each lane loads its own row before the time loop
+  const double* theta_v;   // [B][kMaxTheta]
+  const double* sigma1_v;  // [B] 1-D models: sigma (also the divisor of E_sde)
+  const double* isig_v;    // [B][D][D] Sigma^-1
 };
 
 struct EnergyArgs {
@@ -135,6 +142,10 @@ struct EnergyArgs {
   double* hyp;              // [B][Np][H] per-grid-point integrands of dEsde/dtheta, dEsde/dSigma (nullptr: skipped)
   double* Am;               // [B][Np][D] A_t m_t, a by-product the gradient assembly reuses (L96 kernel; may be nullptr)
   int32_t* status;          // [B] device status word (bit0: S_t not positive definite)
+  // per-problem parameters (vgpa_set_problem_params), last so that the offsets above stay where they were
+  const double* theta_v;    // [B][kMaxTheta] instead of theta, or nullptr
+  const double* sigma1_v;   // [B] instead of sigma1, or nullptr
+  size_t isg_stride;        // D: isg is [B][D]; 0: shared by the batch
 };
 
 struct ObsArgs {
@@ -171,6 +182,9 @@ struct GradArgs {
   const double* Am;         // [B][Np][D] A_t m_t left by the energy kernel, or nullptr (then recomputed)
   const double* Edf;        // dense [B][Np][D][D] or nullptr (then recomputed from the model)
   double* g;                // [B][Np*D*D + Np*D]
+  // per-problem parameters (vgpa_set_problem_params)
+  const double* theta_v;    // [B][kMaxTheta] instead of theta, or nullptr (read where <df/dx> is recomputed)
+  size_t isig_stride;       // D*D: isig is [B][D][D]; 0: shared by the batch
 };
 
 struct ReduceArgs {
@@ -181,6 +195,7 @@ struct ReduceArgs {
   double* esde;             // [B]
   double* f;                // [B]
   const double* e0v;        // [B] per-problem e0 instead of e0, or nullptr
+  const double* div_v;      // [B] per-problem div (1-D models: sigma_p), or nullptr
 };
 
 // launchers (each returns hipGetLastError()) -----------------------------------------------------
@@ -202,7 +217,8 @@ bool sym_fuses_grad(int method, int D);    // ... and OdeArgs::grad_on (the grad
 hipError_t launch_mirror_upper(size_t n_mat, int D, double* m, hipStream_t st);
 // n_mat packed lower triangles [D (D + 1) / 2] -> full symmetric D x D matrices
 hipError_t launch_unpack_lower(size_t n_mat, int D, const double* packed, double* full, hipStream_t st);
-hipError_t launch_psi_from_q(int batch, int Np, int D, size_t strideA, const double* A, const double* isg, double* psi_q, hipStream_t st);
+hipError_t launch_psi_from_q(int batch, int Np, int D, size_t strideA, const double* A, const double* isg, size_t isg_stride,
+                             double* psi_q, hipStream_t st);   // (isg_stride: D for a per-problem [B][D] isg, else 0)
 hipError_t launch_energy(const EnergyArgs& a, hipStream_t st);
 hipError_t launch_obs(const ObsArgs& a, hipStream_t st);   // uses the grid-parallel variant when a.part != nullptr
 hipError_t launch_obs_dense(const ObsArgs& a, const double* js_const, double* jm_dense, double* js_dense,
