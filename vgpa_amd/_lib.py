@@ -204,6 +204,18 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(c_void_p)
 
 
+def _shaped(a, shape, name, dtype=np.float64):
+    """A per-problem input as a contiguous array of exactly `shape`, or None; int64 inputs must hold integer grid indices."""
+    if a is None:
+        return None
+    a = np.asarray(a)
+    if a.shape != shape:
+        raise ValueError(f"{name} has shape {a.shape}, expected {shape}")
+    if dtype == np.int64 and a.size and not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"{name} must hold integer grid indices")
+    return np.ascontiguousarray(a, dtype=dtype)
+
+
 class DeviceBuffer:
     """A caller-owned device allocation (fp64) on the context's device."""
 
@@ -586,22 +598,11 @@ class Context:
         was created with; M is the context's observation count.  Drops the cached state.
         """
         B, M, D = self.B, self.n_obs, self.D
-
-        def shaped(a, shape, name, dtype=np.float64):
-            if a is None:
-                return None
-            a = np.asarray(a)
-            if a.shape != shape:
-                raise ValueError(f"{name} has shape {a.shape}, expected {shape}")
-            if dtype == np.int64 and a.size and not np.issubdtype(a.dtype, np.integer):
-                raise ValueError(f"{name} must hold integer grid indices")
-            return np.ascontiguousarray(a, dtype=dtype)
-
-        t = shaped(obs_t, (B, M), "obs_t", np.int64)
-        y = shaped(obs_y, (B, M, D), "obs_y")
-        m = shaped(m0, (B, D), "m0")
-        s = shaped(s0, (B, D, D), "s0")
-        e = shaped(e0, (B,), "e0")
+        t = _shaped(obs_t, (B, M), "obs_t", np.int64)
+        y = _shaped(obs_y, (B, M, D), "obs_y")
+        m = _shaped(m0, (B, D), "m0")
+        s = _shaped(s0, (B, D, D), "s0")
+        e = _shaped(e0, (B,), "e0")
         self._check(self._lib.vgpa_set_problem_data(self._h, _ptr(t), _ptr(y), _ptr(m), _ptr(s), _ptr(e)))
 
     def set_problem_params(self, theta=None, sigma=None):
@@ -613,17 +614,8 @@ class Context:
         parameters then stay in force.
         """
         B, D = self.B, self.D
-
-        def shaped(a, shape, name):
-            if a is None:
-                return None
-            a = np.asarray(a)
-            if a.shape != shape:
-                raise ValueError(f"{name} has shape {a.shape}, expected {shape}")
-            return np.ascontiguousarray(a, dtype=np.float64)
-
-        t = shaped(theta, (B, self.n_theta), "theta")
-        s = shaped(sigma, (B, D, D), "sigma")
+        t = _shaped(theta, (B, self.n_theta), "theta")
+        s = _shaped(sigma, (B, D, D), "sigma")
         self._check(self._lib.vgpa_set_problem_params(self._h, _ptr(t), _ptr(s)))
 
     @property

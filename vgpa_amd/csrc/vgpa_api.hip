@@ -1,4 +1,5 @@
 // C ABI of libvgpa_hip.so (see include/vgpa_hip.h for the contract and the reference interfaces).
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -12,7 +13,24 @@ using namespace vgpa;
 
 namespace {
 thread_local std::string g_create_error;
-}
+
+// one input of a batched context: problem p reads of(p) = rows + p * stride (stride 0: one row, shared by the batch)
+template <typename T> struct Rows { const T* rows = nullptr; size_t stride = 0; const T* of(int p) const { return rows + (size_t)p * stride; } };
+
+// Where every problem reads every batch input.  vgpa_create points it at the shared values, vgpa_set_problem_data /
+// vgpa_set_problem_params / vgpa_set_prior_energy at per-problem rows; nothing else writes it, and the argument builders copy from it.
+// theta, sigma1, e0 and 1 / sigma^2 have no shared device row: null rows, and the kernels take the shared value (vgpa_ctx).
+struct BatchInputs {
+  Rows<double> m0, S0, obs_y, e0;      // [B][D], [B][D][D], [B][M][D], [B]
+  Rows<int64_t> obs_t;                 // [B][M]
+  Rows<int32_t> obs_idx;               // [B][Np] -> observation counter n, or -1
+  Rows<double> theta, Sigma, isig, isg;   // [B][kMaxTheta], [B][D][D], [B][D][D] Sigma^-1, [B][D] its diagonal (above D = 64: theta only)
+  Rows<double> sig1, qs;               // [B] 1-D sigma, [B] 1 / sigma_p^2 of an isotropic row
+  std::vector<double> h_theta, h_isig, h_sig1, h_e0;  // host copies of the per-problem values (theta_of, isig_of, sigma1_of, e0_of)
+};
+
+struct SigmaForm { bool diag = true, iso = true, sym = true; };   // of one Sigma: diagonal, sigma^2 I, symmetric
+}  // namespace
 
 struct vgpa_ctx {
   vgpa_config cfg{};
@@ -76,25 +94,16 @@ struct vgpa_ctx {
   double* d_Sfull = nullptr;     // ... and their unpacked copy, made when vgpa_fetch (or a kernel that wants S_t whole) asks
   bool ms_valid = true;          // d_m / d_S hold the cached moments (false: only d_msT does; untransposed on demand)
   bool sym_units = false;        // stepping-kernel family of this context (pick_kernel_family)
-  // per-problem inputs (vgpa_set_problem_data): each replaces its shared counterpart once set
-  double *d_pp_m0 = nullptr, *d_pp_S0 = nullptr, *d_pp_e0 = nullptr, *d_pp_obs_y = nullptr;   // [B][D], [B][D][D], [B], [B][M][D]
-  int64_t* d_pp_obs_t = nullptr;     // [B][M]
-  int32_t* d_pp_obs_idx = nullptr;   // [B][Np] -> observation counter n, or -1
-  bool pp_m0 = false, pp_S0 = false, pp_e0 = false, pp_obs_y = false, pp_obs_t = false;
-  std::vector<double> h_pp_e0;       // host copy of the per-problem e0 (vgpa_energy_parts)
+  BatchInputs in;                // where each problem reads each batch input
+  // the per-problem rows the setters upload, allocated on first use (the record points at them)
+  double *d_pp_m0 = nullptr, *d_pp_S0 = nullptr, *d_pp_e0 = nullptr, *d_pp_obs_y = nullptr, *d_pp_theta = nullptr, *d_pp_Sigma = nullptr;
+  double *d_pp_isig = nullptr, *d_pp_isg = nullptr, *d_pp_sig1 = nullptr, *d_pp_qs = nullptr;
+  int64_t* d_pp_obs_t = nullptr; int32_t* d_pp_obs_idx = nullptr;
   double *d_jm_pt = nullptr, *d_js_pt = nullptr;   // dense jumps [B][Np][D], [B][Np][D][D]: per-problem times on the 16-lane kernels
   bool pt_dense_zeroed = false;      // ... zero off the observation rows of the current times (each sweep rewrites only those rows)
-  bool sym_inputs_shared = true;     // sym_inputs as vgpa_create found it (Sigma, the shared s0, the constant jump)
-  bool pp_s0_sym = true;             // ... and of the per-problem s0 rows / Sigma rows (sym_inputs is the conjunction)
-  // per-problem parameters (vgpa_set_problem_params): once set, every row of each array below is in force (a row the caller left
-  // shared holds the shared value); rows that all equal the shared parameters keep the shared kernels
-  bool pp_par = false, pp_sigma_sym = true;
-  double* d_pp_theta = nullptr;      // [B][kMaxTheta]
-  double *d_pp_Sigma = nullptr, *d_pp_isig = nullptr, *d_pp_isg = nullptr;   // [B][D][D], [B][D][D] Sigma^-1, [B][D] its diagonal
-  double *d_pp_sig1 = nullptr, *d_pp_qs = nullptr;                           // [B] 1-D sigma, [B] 1 / sigma_p^2 of an isotropic row
-  std::vector<double> h_pp_theta, h_pp_isig, h_pp_sig1;                      // host copies (energy_full, the D > 64 energy terms)
   std::vector<double> h_sigma;       // host copy of the shared Sigma [D][D]
-  bool sigma_diag_shared = true, isg_iso_shared = false;   // the kernel-family flags of the shared Sigma
+  SigmaForm sigma_form, rows_form;            // kernel_family's inputs: the form of the shared Sigma, of the per-problem rows in force,
+  bool inputs_sym = true, s0_rows_sym = true;  // ... the shared s0 and constant jump symmetric, the per-problem s0 rows symmetric
   // profiling
   bool prof = false;
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -142,6 +151,14 @@ int upload(vgpa_ctx* c, T* dst, const T* src, size_t count) {
   return VGPA_OK;
 }
 
+// the setters' per-problem rows: B rows of `stride` elements into *buf (allocated on first use); the record's entry then points there
+template <typename T>
+int upload_rows(vgpa_ctx* c, T** buf, const T* src, size_t stride, Rows<T>* entry) {
+  int rc = ensure(c, buf, (size_t)c->B * stride);
+  if (rc == VGPA_OK && (rc = upload(c, *buf, src, (size_t)c->B * stride)) == VGPA_OK) *entry = {*buf, stride};
+  return rc;
+}
+
 template <typename T>
 int download(vgpa_ctx* c, T* dst, const T* src, size_t count) {
   HIP_TRY(c, hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyDeviceToHost, c->stream));
@@ -161,6 +178,44 @@ bool is_symmetric(const double* a, int n) {
 bool stack_symmetric(const double* a, size_t count, int n) {
   for (size_t t = 0; t < count; t++)
     if (!is_symmetric(a + t * n * n, n)) return false;
+  return true;
+}
+
+// Sigma^-1 [D][D], its diagonal isg [D] and the form of one Sigma [D][D]; 1-D models: sigma1 = Sigma, Sigma^-1 = 1 / sigma1.
+// VGPA_ERR_ARG: a 1-D sigma that is not positive; VGPA_ERR_NOT_PD: an n-D Sigma that is not positive definite.
+int invert_sigma(int D, bool single, const double* sigma, double* isig, double* isg, double* sigma1, SigmaForm* f) {
+  std::fill(isig, isig + (size_t)D * D, 0.0); *f = SigmaForm{};
+  *sigma1 = single ? sigma[0] : 1.0;
+  if (single && !(sigma[0] > 0.0)) return VGPA_ERR_ARG;
+  if (single) { isig[0] = isg[0] = 1.0 / sigma[0]; return VGPA_OK; }
+  for (int i = 0; i < D && f->diag; i++)
+    for (int j = 0; j < D; j++)
+      if (i != j && sigma[(size_t)i * D + j] != 0.0) { f->diag = false; break; }
+  if (f->diag) {   // chol_inv of a diagonal matrix: C = diag(1/sqrt(s)), C^T C = diag(C_ii * C_ii)
+    for (int i = 0; i < D; i++) {
+      const double sii = sigma[(size_t)i * D + i];
+      if (!(sii > 0.0)) return VGPA_ERR_NOT_PD;
+      const double ci = 1.0 / std::sqrt(sii);
+      isg[i] = isig[(size_t)i * D + i] = ci * ci;
+    }
+  } else {
+    if (!host_spd_inverse(D, sigma, isig, nullptr)) return VGPA_ERR_NOT_PD;
+    for (int i = 0; i < D; i++) isg[i] = isig[(size_t)i * D + i];
+  }
+  f->iso = f->diag;
+  for (int i = 1; i < D; i++) f->iso = f->iso && isg[i] == isg[0];
+  f->sym = is_symmetric(sigma, D);
+  return VGPA_OK;
+}
+
+// one row of observation times: false unless strictly increasing indices in [0, Np); idx [Np] -> observation counter n, or -1
+bool index_obs_times(const int64_t* obs_t, int M, int Np, int32_t* idx) {
+  std::fill(idx, idx + Np, -1);
+  for (int n = 0; n < M; n++) {
+    const int64_t tn = obs_t[n];
+    if (tn < 0 || tn >= Np || (n > 0 && tn <= obs_t[n - 1])) return false;
+    idx[tn] = n;
+  }
   return true;
 }
 
@@ -189,11 +244,19 @@ static int ingest_ab(vgpa_ctx* c, const double* lin_a, const double* off_b) {
   return VGPA_OK;
 }
 
-// the initial moments of the sweeps: the per-problem rows once vgpa_set_problem_data has set them (run_fwd tells them by address)
-static inline const double* sweep_m0(vgpa_ctx* c) { return c->pp_m0 ? c->d_pp_m0 : c->d_m0; }
-static inline const double* sweep_S0(vgpa_ctx* c) { return c->pp_S0 ? c->d_pp_S0 : c->d_S0; }
-// ... and the forcing term Sigma: the per-problem rows once vgpa_set_problem_params has set them (run_fwd tells them by address)
-static inline const double* sweep_Sigma(vgpa_ctx* c) { return c->pp_par ? c->d_pp_Sigma : c->d_Sigma; }
+// problem p's values on the host: its own rows once a setter has set them, else the shared ones
+static const double* theta_of(const vgpa_ctx* c, int p) { return c->in.theta.rows ? c->in.h_theta.data() + (size_t)p * kMaxTheta : c->theta; }
+static const double* isig_of(const vgpa_ctx* c, int p) { return c->in.isig.stride ? c->in.h_isig.data() + p * c->DD : c->h_isig.data(); }
+static double sigma1_of(const vgpa_ctx* c, int p) { return c->in.sig1.rows ? c->in.h_sig1[p] : c->sigma1; }
+static double e0_of(const vgpa_ctx* c, int p) { return c->in.e0.rows ? c->in.h_e0[p] : c->cfg.e0; }
+
+// the kernel-family flags of the inputs in force: the form of the shared Sigma or of the per-problem rows (isotropic: every row
+// sigma_p^2 I with its own sigma_p); symmetric: every s0 / Sigma and the constant jump (else both products of the slope literally)
+static void kernel_family(vgpa_ctx* c) {
+  const SigmaForm& f = c->in.Sigma.stride ? c->rows_form : c->sigma_form;
+  c->sigma_diag = f.diag; c->isg_iso = f.iso;
+  c->sym_inputs = c->inputs_sym && c->s0_rows_sym && c->sigma_form.sym && f.sym;
+}
 
 static void prof_mark(vgpa_ctx* c, int i) {
   if (c->prof) (void)hipEventRecord(c->ev[i], c->stream);
@@ -277,15 +340,30 @@ struct LdBatch {
     m.add(c->d_dEm, NpD); m.add(c->d_dEs, NpDD);
     m.add(c->d_jm, (size_t)c->M * c->D); m.add(c->d_jm_dense, NpD); m.add(c->d_js_dense, NpDD);
     m.add(c->d_ld_ws, ld::ld_workspace_doubles(c->D));
-    if (c->pp_m0) m.add(c->d_pp_m0, c->D);
-    if (c->pp_S0) m.add(c->d_pp_S0, c->DD);
+    m.add(c->in.m0.rows, c->in.m0.stride); m.add(c->in.S0.rows, c->in.S0.stride); m.add(c->in.Sigma.rows, c->in.Sigma.stride);
     ld::ld_set_batch(&m);
   }
   ~LdBatch() { if (on) ld::ld_set_batch(nullptr); }
   bool on;
 };
 
-static int run_fwd(vgpa_ctx* c, const double* m0, const double* S0, const double* Sigma, bool sym) {
+// the forward sweep's OdeArgs: x, the moment histories, the initial moments and the forcing term
+static OdeArgs fwd_args(vgpa_ctx* c, Rows<double> m0, Rows<double> S0, Rows<double> Sigma) {
+  OdeArgs a{};
+  a.D = c->D; a.Np = c->Np; a.batch = c->B; a.dt = c->cfg.dt;
+  a.strideA = a.strideB = c->len_x;
+  a.A = ctx_A(c); a.b = ctx_b(c); a.m = c->d_m; a.S = c->d_S;
+  a.m0 = m0.rows; a.m0_stride = m0.stride; a.S0 = S0.rows; a.S0_stride = S0.stride; a.Sigma = Sigma.rows; a.Sigma_stride = Sigma.stride;
+  return a;
+}
+
+// the sparse observation jumps of the backward recursion (des_packed is never set behind the lane pass: js_const = d_jsc there)
+static void sparse_jumps(vgpa_ctx* c, OdeArgs& a) {
+  a.obs_idx = c->in.obs_idx.rows; a.obs_idx_stride = (int)c->in.obs_idx.stride;
+  a.jm_sparse = c->d_jm; a.js_const = c->des_packed ? c->d_jscp : c->d_jsc; a.n_obs = c->M;
+}
+
+static int run_fwd(vgpa_ctx* c, Rows<double> m0, Rows<double> S0, Rows<double> Sigma, bool sym) {
   ld::use_library_gemm = (c->cfg.flags & VGPA_FLAG_LIBRARY_GEMM) != 0;
   c->ms_valid = true;                  // (every path below writes the [B][Np] arrays m / S)
   if (c->D > kMaxSmallD) {
@@ -293,19 +371,13 @@ static int run_fwd(vgpa_ctx* c, const double* m0, const double* S0, const double
     if (rc) return rc;
     LdBatch batch(c);
     LdLiteral literal(!sym);             // non-symmetric s0 / sigma: both products of the slope literally (ode_solver.py:60)
-    hipError_t e = ld::ld_solve_fwd(c->cfg.method, c->cfg.dt, c->D, c->Np, ctx_A(c), ctx_b(c), m0, S0, Sigma, c->d_m, c->d_S,
-                                    c->d_ld_ws, c->stream);
+    hipError_t e = ld::ld_solve_fwd(c->cfg.method, c->cfg.dt, c->D, c->Np, ctx_A(c), ctx_b(c), m0.rows, S0.rows, Sigma.rows, c->d_m,
+                                    c->d_S, c->d_ld_ws, c->stream);
     if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "large-D forward sweep failed: %s", hipGetErrorString(e));
     return VGPA_OK;
   }
-  OdeArgs a{};
+  OdeArgs a = fwd_args(c, m0, S0, Sigma);
   a.sym_units = use_sym_units(c) ? 1 : 0;
-  a.D = c->D; a.Np = c->Np; a.batch = c->B; a.dt = c->cfg.dt;
-  a.strideA = a.strideB = c->len_x;
-  a.A = ctx_A(c); a.b = ctx_b(c); a.m0 = m0; a.S0 = S0; a.Sigma = Sigma; a.m = c->d_m; a.S = c->d_S;
-  a.m0_stride = m0 == c->d_pp_m0 ? (size_t)c->D : 0;
-  a.S0_stride = S0 == c->d_pp_S0 ? c->DD : 0;
-  a.Sigma_stride = Sigma == c->d_pp_Sigma ? c->DD : 0;
   a.s_packed = c->s_packed ? 1 : 0;
   hipError_t e = use_lane(c) ? launch_ode_small(c->cfg.method, true, a, c->stream)
                  : use_wave(c) ? launch_ode_wave(c->cfg.method, true, a, c->stream)
@@ -344,7 +416,7 @@ static int run_bwd(vgpa_ctx* c, bool dense_jumps, bool sym, double* g_fused = nu
   a.strideA = a.strideB = c->len_x;
   a.A = ctx_A(c); a.dEm = c->d_dEm; a.dEs = c->d_dEs; a.lam = c->d_lam; a.psi = c->d_psi;
   if (dense_jumps) { a.jm_dense = c->d_jm_dense; a.js_dense = c->d_js_dense; }
-  else if (c->pp_obs_t && use_wave(c)) {
+  else if (c->in.obs_idx.stride && use_wave(c)) {
     // per-problem times on the 16-lane kernels (four problems per wave, whose jump index is wave-uniform): dense jump arrays
     // (B Np (D + D^2) doubles, zeroed once per set of times; a sweep rewrites the B M (D + D^2) entries of the observation rows)
     if ((rc = ensure(c, &c->d_jm_pt, (size_t)c->B * c->Np * c->D))) return rc;
@@ -358,8 +430,7 @@ static int run_bwd(vgpa_ctx* c, bool dense_jumps, bool sym, double* g_fused = nu
     if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "obs dense launch failed: %s", hipGetErrorString(e));
     a.jm_dense = c->d_jm_pt; a.js_dense = c->d_js_pt;
   } else {
-    a.obs_idx = c->pp_obs_t ? c->d_pp_obs_idx : c->d_obs_idx; a.obs_idx_stride = c->pp_obs_t ? c->Np : 0;
-    a.jm_sparse = c->d_jm; a.js_const = c->des_packed ? c->d_jscp : c->d_jsc; a.n_obs = c->M;
+    sparse_jumps(c, a);
   }
   a.ds_packed = c->des_packed ? 1 : 0;
   // fused sweeps on the fragment-cover kernels: Q''_t instead of Psi_t (the gradient assembly then does not read A_t; see
@@ -368,7 +439,7 @@ static int run_bwd(vgpa_ctx* c, bool dense_jumps, bool sym, double* g_fused = nu
                 c->cfg.model == VGPA_MODEL_L96 && !(c->cfg.flags & VGPA_FLAG_KEEP_PSI) && sym_stores_q(c->cfg.method, c->D);
   a.q_on = c->psi_is_q ? 1 : 0;
   a.q_scale = c->isg0;
-  a.q_scale_v = c->pp_par ? c->d_pp_qs : nullptr;      // (read only by the Q'' kernels: every row isotropic then)
+  a.q_scale_v = c->in.qs.rows;               // (read only by the Q'' kernels: every row isotropic then)
   if (g_fused) {                           // the gradient assembly on the kernel's helper waves (k_ode_sym, GF)
     if (!c->psi_is_q) return fail(c, VGPA_ERR_STATE, "fused gradient assembly: the backward kernel is not the Q'' one");
     a.grad_on = 1; a.g = g_fused; a.s_packed = 1;
@@ -390,8 +461,8 @@ static EnergyArgs energy_args(vgpa_ctx* c, double* edf, bool ds_upper = false) {
   a.s_packed = c->s_packed ? 1 : 0;
   a.model = c->cfg.model; a.D = c->D; a.Np = c->Np; a.batch = c->B; a.dt = c->cfg.dt;
   for (int i = 0; i < kMaxTheta; i++) a.theta[i] = c->theta[i];
-  a.sigma1 = c->sigma1; a.isg = c->d_isg;
-  if (c->pp_par) { a.theta_v = c->d_pp_theta; a.sigma1_v = c->d_pp_sig1; a.isg = c->d_pp_isg; a.isg_stride = (size_t)c->D; }
+  a.sigma1 = c->sigma1; a.isg = c->in.isg.rows; a.isg_stride = c->in.isg.stride;
+  a.theta_v = c->in.theta.rows; a.sigma1_v = c->in.sig1.rows;
   a.strideA = a.strideB = c->len_x;
   a.A = ctx_A(c); a.b = ctx_b(c); a.m = c->d_m; a.S = c->d_S;
   a.e_t = c->d_et; a.Ef = c->d_Ef; a.Edf = edf; a.dEm = c->d_dEm; a.dEs = c->d_dEs; a.status = c->d_status;
@@ -421,11 +492,11 @@ static int run_energy(vgpa_ctx* c, double* edf, bool ds_upper = false, bool ds_p
     if (rc) return rc;
     // the energy terms are batched over grid points already: problem by problem
     const size_t NpD = (size_t)c->Np * c->D, NpDD = (size_t)c->Np * c->DD;
-    for (int p = 0; p < c->B; p++) {      // (per-problem parameters: the problem's theta; Sigma is shared above D = 64)
-      const double th = c->pp_par ? c->h_pp_theta[(size_t)p * kMaxTheta] : c->theta[0];
-      hipError_t e = ld::lde_energy(c->D, c->Np, th, c->d_isg, ctx_A(c) + p * c->len_x, ctx_b(c) + p * c->len_x, c->d_m + p * NpD,
-                                    c->d_S + p * NpDD, c->d_et + (size_t)p * c->Np, c->d_Ef + p * NpD, edf ? edf + p * NpDD : nullptr,
-                                    c->d_dEm + p * NpD, c->d_dEs + p * NpDD, c->d_status + p, c->d_lde_ws, c->lde_nb, c->stream,
+    for (int p = 0; p < c->B; p++) {
+      hipError_t e = ld::lde_energy(c->D, c->Np, theta_of(c, p)[0], c->in.isg.of(p), ctx_A(c) + p * c->len_x,
+                                    ctx_b(c) + p * c->len_x, c->d_m + p * NpD, c->d_S + p * NpDD, c->d_et + (size_t)p * c->Np,
+                                    c->d_Ef + p * NpD, edf ? edf + p * NpDD : nullptr, c->d_dEm + p * NpD, c->d_dEs + p * NpDD,
+                                    c->d_status + p, c->d_lde_ws, c->lde_nb, c->stream,
                                     c->hyp_on ? c->d_hyp + (size_t)p * c->Np * 2 * c->D : nullptr, c->stream2);
       if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "large-D energy failed: %s", hipGetErrorString(e));
     }
@@ -444,8 +515,8 @@ static int run_energy(vgpa_ctx* c, double* edf, bool ds_upper = false, bool ds_p
 static ObsArgs obs_args(vgpa_ctx* c) {
   ObsArgs a{};
   a.D = c->D; a.Np = c->Np; a.batch = c->B; a.n_obs = c->M; a.single = c->single ? 1 : 0;
-  a.obs_t = c->pp_obs_t ? c->d_pp_obs_t : c->d_obs_t; a.obs_y = c->pp_obs_y ? c->d_pp_obs_y : c->d_obs_y; a.Q = c->d_Q;
-  a.obs_t_stride = c->pp_obs_t ? (size_t)c->M : 0; a.obs_y_stride = c->pp_obs_y ? (size_t)c->M * c->D : 0; a.K = c->d_K; a.rinv_diag = c->d_rinv;
+  a.obs_t = c->in.obs_t.rows; a.obs_t_stride = c->in.obs_t.stride; a.obs_y = c->in.obs_y.rows; a.obs_y_stride = c->in.obs_y.stride;
+  a.Q = c->d_Q; a.K = c->d_K; a.rinv_diag = c->d_rinv;
   a.obs_const = c->obs_const; a.m = c->d_m; a.S = c->d_S; a.jm_sparse = c->d_jm; a.eobs = c->d_eobs;
   a.diag = c->obs_diag ? 1 : 0; a.part = c->d_obs_part;
   a.s_packed = c->s_packed ? 1 : 0;
@@ -454,9 +525,8 @@ static ObsArgs obs_args(vgpa_ctx* c) {
 
 static int run_reduce(vgpa_ctx* c) {
   ReduceArgs r{};
-  r.Np = c->Np; r.batch = c->B; r.dt = c->cfg.dt; r.e0 = c->cfg.e0; r.e0v = c->pp_e0 ? c->d_pp_e0 : nullptr;
-  r.pre = c->single ? 0.5 : 1.0; r.div = c->single ? c->sigma1 : 1.0;
-  r.div_v = (c->single && c->pp_par) ? c->d_pp_sig1 : nullptr;
+  r.Np = c->Np; r.batch = c->B; r.dt = c->cfg.dt; r.e0 = c->cfg.e0; r.e0v = c->in.e0.rows;
+  r.pre = c->single ? 0.5 : 1.0; r.div = c->single ? c->sigma1 : 1.0; r.div_v = c->single ? c->in.sig1.rows : nullptr;
   r.e_t = c->d_et; r.eobs = c->d_eobs; r.esde = c->d_esde; r.f = c->d_f;
   hipError_t e = launch_reduce(r, c->stream);
   if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "reduce launch failed: %s", hipGetErrorString(e));
@@ -472,9 +542,9 @@ static int run_grad(vgpa_ctx* c, double* g_dev) {
     const size_t NpD = (size_t)c->Np * c->D, NpDD = (size_t)c->Np * c->DD;
     for (int p = 0; p < c->B; p++) {
       double* gp = g_dev + p * c->len_x;
-      hipError_t e = ld::lde_grad(c->D, c->Np, c->cfg.dt, c->d_isg, ctx_A(c) + p * c->len_x, ctx_b(c) + p * c->len_x, c->d_m + p * NpD,
+      hipError_t e = ld::lde_grad(c->D, c->Np, c->cfg.dt, c->in.isg.of(p), ctx_A(c) + p * c->len_x, ctx_b(c) + p * c->len_x, c->d_m + p * NpD,
                                   c->d_S + p * NpDD, c->d_lam + p * NpD, c->d_psi + p * NpDD, c->d_Ef + p * NpD, gp, gp + NpDD, c->d_lde_ws,
-                                  c->lde_nb, c->stream, c->sigma_diag ? nullptr : c->d_isig);
+                                  c->lde_nb, c->stream, c->sigma_diag ? nullptr : c->in.isig.of(p));
       if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "large-D gradient failed: %s", hipGetErrorString(e));
     }
     return VGPA_OK;
@@ -484,8 +554,8 @@ static int run_grad(vgpa_ctx* c, double* g_dev) {
   a.dt = c->cfg.dt;
   for (int i = 0; i < kMaxTheta; i++) a.theta[i] = c->theta[i];
   a.strideA = a.strideB = c->len_x;
-  a.isig = c->d_isig; a.A = ctx_A(c); a.b = ctx_b(c); a.m = c->d_m; a.S = c->d_S; a.lam = c->d_lam; a.psi = c->d_psi;
-  if (c->pp_par) { a.theta_v = c->d_pp_theta; a.isig = c->d_pp_isig; a.isig_stride = c->DD; }
+  a.A = ctx_A(c); a.b = ctx_b(c); a.m = c->d_m; a.S = c->d_S; a.lam = c->d_lam; a.psi = c->d_psi;
+  a.isig = c->in.isig.rows; a.isig_stride = c->in.isig.stride; a.theta_v = c->in.theta.rows;
   a.Ef = c->d_Ef; a.Edf = nullptr; a.g = g_dev;
   a.psi_is_q = c->psi_is_q ? 1 : 0;
   a.s_packed = (c->s_packed && c->psi_is_q) ? 1 : 0;
@@ -571,7 +641,7 @@ static int enqueue_stream_sweep(vgpa_ctx* c, double* g_dev) {
   HIP_TRY(c, hipMemsetAsync(c->d_status, 0, sizeof(int32_t) * c->B, c->stream));
   c->s_packed = false;
   prof_mark(c, 0);
-  if ((rc = run_fwd(c, sweep_m0(c), sweep_S0(c), sweep_Sigma(c), c->sym_inputs))) return rc;
+  if ((rc = run_fwd(c, c->in.m0, c->in.S0, c->in.Sigma, c->sym_inputs))) return rc;
   prof_mark(c, 1);
   hipError_t e = launch_obs(obs_args(c), c->stream);
   if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "obs launch failed: %s", hipGetErrorString(e));
@@ -603,15 +673,14 @@ static int run_lane_pass(vgpa_ctx* c, double* g_dev) {
   a.strideA = a.strideB = c->len_x;
   a.A = ctx_A(c); a.b = ctx_b(c); a.m = c->d_m; a.S = c->d_S;
   a.msT = c->d_msT; a.bpad = c->bpad; a.jmT = c->d_jmT;
-  a.obs_idx = c->pp_obs_t ? c->d_pp_obs_idx : c->d_obs_idx; a.obs_idx_stride = c->pp_obs_t ? c->Np : 0;
-  a.jm_sparse = c->d_jm; a.js_const = c->d_jsc; a.n_obs = c->M;
+  sparse_jumps(c, a);
   q.model = c->cfg.model; q.want_grad = g_dev ? 1 : 0;
   for (int i = 0; i < kMaxTheta; i++) q.theta[i] = c->theta[i];
   q.sigma1 = c->sigma1;
   for (int i = 0; i < c->D; i++) q.isg[i] = c->h_isig[(size_t)i * c->D + i];
   for (size_t e = 0; e < c->DD; e++) q.isig[e] = c->h_isig[e];
-  q.e0 = c->cfg.e0; q.e0v = c->pp_e0 ? c->d_pp_e0 : nullptr; q.pre = c->single ? 0.5 : 1.0; q.div = c->single ? c->sigma1 : 1.0;
-  if (c->pp_par) { q.theta_v = c->d_pp_theta; q.sigma1_v = c->d_pp_sig1; q.isig_v = c->d_pp_isig; }
+  q.e0 = c->cfg.e0; q.e0v = c->in.e0.rows; q.pre = c->single ? 0.5 : 1.0; q.div = c->single ? c->sigma1 : 1.0;
+  q.theta_v = c->in.theta.rows; q.sigma1_v = c->in.sig1.rows; q.isig_v = c->in.isig.stride ? c->in.isig.rows : nullptr;
   q.eobs = c->d_eobs; q.esde = c->d_esde; q.f = c->d_f; q.g = g_dev;
   hipError_t e = launch_sweep_lane(c->cfg.method, q, c->stream);
   if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "fused lane pass launch failed: %s", hipGetErrorString(e));
@@ -630,11 +699,7 @@ static int enqueue_lane_sweep(vgpa_ctx* c, double* g_dev) {
     if ((rc = dev_alloc(c, &c->d_jmT, (size_t)(c->M > 0 ? c->M : 1) * c->D * c->bpad))) return rc;
   }
   {
-    OdeArgs a{};
-    a.D = c->D; a.Np = c->Np; a.batch = c->B; a.dt = c->cfg.dt;
-    a.strideA = a.strideB = c->len_x;
-    a.A = ctx_A(c); a.b = ctx_b(c); a.m0 = sweep_m0(c); a.S0 = sweep_S0(c); a.Sigma = sweep_Sigma(c); a.m = c->d_m; a.S = c->d_S;
-    a.m0_stride = c->pp_m0 ? (size_t)c->D : 0; a.S0_stride = c->pp_S0 ? c->DD : 0; a.Sigma_stride = c->pp_par ? c->DD : 0;
+    OdeArgs a = fwd_args(c, c->in.m0, c->in.S0, c->in.Sigma);
     a.msT = c->d_msT; a.bpad = c->bpad;
     hipError_t ef = launch_ode_small(c->cfg.method, true, a, c->stream);
     if (ef != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "forward lane kernel launch failed: %s", hipGetErrorString(ef));
@@ -728,7 +793,7 @@ static int enqueue_free_energy(vgpa_ctx* c) {
   HIP_TRY(c, hipMemsetAsync(c->d_status, 0, sizeof(int32_t) * c->B, c->stream));
   prof_mark(c, 0);
   for (int r = diag_repeat("fwd"); r > 0; r--)
-    if ((rc = run_fwd(c, sweep_m0(c), sweep_S0(c), sweep_Sigma(c), c->sym_inputs))) return rc;
+    if ((rc = run_fwd(c, c->in.m0, c->in.S0, c->in.Sigma, c->sym_inputs))) return rc;
   prof_mark(c, 1);
   hipError_t e = launch_obs(obs_args(c), c->stream);
   if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "obs launch failed: %s", hipGetErrorString(e));
@@ -829,8 +894,10 @@ int vgpa_create(vgpa_ctx** out, const vgpa_config* cfg) {
   const int D = c->D;
   const size_t DD = c->DD;
   int rc = VGPA_OK;
-#define TRY(expr) do { rc = (expr); if (rc != VGPA_OK) { g_create_error = c->err; vgpa_destroy(c); return rc; } } while (0)
-#define HTRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { fail(nullptr, VGPA_ERR_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); vgpa_destroy(c); return VGPA_ERR_DEVICE; } } while (0)
+  // every error exit: the message, then everything allocated so far goes back
+#define FAIL(code, ...) do { const int code_ = fail(nullptr, (code), __VA_ARGS__); vgpa_destroy(c); return code_; } while (0)
+#define TRY(expr) do { if ((rc = (expr)) != VGPA_OK) FAIL(rc, "%s", c->err.c_str()); } while (0)
+#define HTRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) FAIL(VGPA_ERR_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); } while (0)
   HTRY(hipSetDevice(cfg->device));
   HTRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   pick_kernel_family(c);
@@ -839,31 +906,16 @@ int vgpa_create(vgpa_ctx** out, const vgpa_config* cfg) {
   for (auto& e : c->ev) HTRY(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
 
   // ---- host-side constants -------------------------------------------------------------------
-  std::vector<double> sigma(cfg->sigma, cfg->sigma + DD), isig(DD, 0.0), isg(D, 0.0);
-  if (single) {
-    if (!(sigma[0] > 0.0)) { fail(nullptr, VGPA_ERR_ARG, "The diffusion noise value: %g, should be strictly positive.", sigma[0]); vgpa_destroy(c); return VGPA_ERR_ARG; }
-    c->sigma1 = sigma[0]; isig[0] = 1.0 / sigma[0]; isg[0] = isig[0];
-  } else if (cfg->model == VGPA_MODEL_NONE) {
-    for (int i = 0; i < D; i++) { isig[(size_t)i * D + i] = 1.0; isg[i] = 1.0; }   // ODE-only: Sigma^-1 is not used
+  std::vector<double> sigma(cfg->sigma, cfg->sigma + DD), isig(DD, 0.0), isg(D, 1.0);
+  if (cfg->model == VGPA_MODEL_NONE && !single) {   // ODE-only: Sigma^-1 = I is not used
+    for (int i = 0; i < D; i++) isig[(size_t)i * D + i] = 1.0;
+    c->sigma_form.sym = is_symmetric(sigma.data(), D);
   } else {
-    c->sigma_diag = true;
-    for (int i = 0; i < D && c->sigma_diag; i++)
-      for (int j = 0; j < D; j++)
-        if (i != j && sigma[(size_t)i * D + j] != 0.0) { c->sigma_diag = false; break; }
-    if (c->sigma_diag) {   // chol_inv of a diagonal matrix: C = diag(1/sqrt(s)), C^T C = diag(C_ii * C_ii)
-      for (int i = 0; i < D; i++) {
-        const double sii = sigma[(size_t)i * D + i];
-        if (!(sii > 0.0)) { fail(nullptr, VGPA_ERR_NOT_PD, "Noise matrix is not positive definite."); vgpa_destroy(c); return VGPA_ERR_NOT_PD; }
-        const double ci = 1.0 / std::sqrt(sii);
-        isig[(size_t)i * D + i] = ci * ci;
-        isg[i] = ci * ci;
-      }
-    } else {
-      if (!host_spd_inverse(D, sigma.data(), isig.data(), nullptr)) { fail(nullptr, VGPA_ERR_NOT_PD, "Noise matrix is not positive definite."); vgpa_destroy(c); return VGPA_ERR_NOT_PD; }
-      for (int i = 0; i < D; i++) isg[i] = isig[(size_t)i * D + i];
-    }
+    rc = invert_sigma(D, single, sigma.data(), isig.data(), isg.data(), &c->sigma1, &c->sigma_form);
+    if (rc == VGPA_ERR_ARG) FAIL(rc, "The diffusion noise value: %g, should be strictly positive.", sigma[0]);
+    if (rc) FAIL(rc, "Noise matrix is not positive definite.");
   }
-  c->sym_inputs = is_symmetric(sigma.data(), D) && (!cfg->s0 || is_symmetric(cfg->s0, D));
+  c->inputs_sym = !cfg->s0 || is_symmetric(cfg->s0, D);
 
   const size_t BN = (size_t)c->B * c->Np;
   TRY(dev_alloc(c, &c->d_m, BN * D));
@@ -904,22 +956,16 @@ int vgpa_create(vgpa_ctx** out, const vgpa_config* cfg) {
   TRY(upload(c, c->d_isig, isig.data(), DD));
   TRY(upload(c, c->d_isg, isg.data(), (size_t)D));
   c->isg0 = isg[0];
-  c->isg_iso = true;
-  for (int i = 1; i < D; i++) c->isg_iso = c->isg_iso && isg[i] == isg[0];
   if (cfg->m0) TRY(upload(c, c->d_m0, cfg->m0, (size_t)D));
   if (cfg->s0) TRY(upload(c, c->d_S0, cfg->s0, DD));
 
   std::vector<int32_t> obs_idx(c->Np, -1);
   std::vector<double> Q(DD, 0.0), K(DD, 0.0), rinv(D, 0.0), jsc(DD, 0.0);
   if (c->M > 0 && cfg->obs_t && cfg->obs_y && cfg->obs_noise) {
-    for (int n = 0; n < c->M; n++) {
-      const int64_t tn = cfg->obs_t[n];
-      if (tn < 0 || tn >= c->Np || (n > 0 && tn <= cfg->obs_t[n - 1])) { fail(nullptr, VGPA_ERR_ARG, "obs_t must be strictly increasing indices in [0, Np)"); vgpa_destroy(c); return VGPA_ERR_ARG; }
-      obs_idx[tn] = n;
-    }
+    if (!index_obs_times(cfg->obs_t, c->M, c->Np, obs_idx.data())) FAIL(VGPA_ERR_ARG, "obs_t must be strictly increasing indices in [0, Np)");
     if (single) {
       const double r = cfg->obs_noise[0];
-      if (!(r > 0.0)) { fail(nullptr, VGPA_ERR_NOT_PD, "observation noise must be positive"); vgpa_destroy(c); return VGPA_ERR_NOT_PD; }
+      if (!(r > 0.0)) FAIL(VGPA_ERR_NOT_PD, "observation noise must be positive");
       const double h = cfg->obs_h ? cfg->obs_h[0] : 1.0;
       Q[0] = 1.0 / r; K[0] = h; rinv[0] = 1.0 / r; jsc[0] = 0.5 / r;
       c->obs_const = 0.5 * c->M * (std::log(2.0 * M_PI) + std::log(r));
@@ -940,7 +986,7 @@ int vgpa_create(vgpa_ctx** out, const vgpa_config* cfg) {
       if (r_diag) {
         for (int i = 0; i < D; i++) {
           const double rii = cfg->obs_noise[(size_t)i * D + i];
-          if (!(rii > 0.0)) { fail(nullptr, VGPA_ERR_NOT_PD, "observation noise matrix is not positive definite"); vgpa_destroy(c); return VGPA_ERR_NOT_PD; }
+          if (!(rii > 0.0)) FAIL(VGPA_ERR_NOT_PD, "observation noise matrix is not positive definite");
           const double ci = 1.0 / std::sqrt(rii);
           const double ri = ci * ci;
           Q[(size_t)i * D + i] = ri; K[(size_t)i * D + i] = ri; jsc[(size_t)i * D + i] = 0.5 * ri; rinv[i] = ri;
@@ -948,7 +994,9 @@ int vgpa_create(vgpa_ctx** out, const vgpa_config* cfg) {
         }
         logdet *= 2.0;
         c->obs_const = c->M * (D * std::log(2.0 * M_PI) + logdet);
-      } else if (!host_spd_inverse(D, cfg->obs_noise, Rinv.data(), &logdet)) { fail(nullptr, VGPA_ERR_NOT_PD, "observation noise matrix is not positive definite"); vgpa_destroy(c); return VGPA_ERR_NOT_PD; }
+      } else if (!host_spd_inverse(D, cfg->obs_noise, Rinv.data(), &logdet)) {
+        FAIL(VGPA_ERR_NOT_PD, "observation noise matrix is not positive definite");
+      }
       if (!r_diag) {
       if (cfg->obs_h && !h_identity) H.assign(cfg->obs_h, cfg->obs_h + DD); else for (int i = 0; i < D; i++) H[(size_t)i * D + i] = 1.0;
       host_matmul(D, H.data(), Rinv.data(), T.data(), false, false);      // H R^-1
@@ -960,7 +1008,7 @@ int vgpa_create(vgpa_ctx** out, const vgpa_config* cfg) {
       for (int i = 0; i < D; i++) rinv[i] = Rinv[(size_t)i * D + i];
       c->obs_const = c->M * (D * std::log(2.0 * M_PI) + logdet);
       }
-      c->sym_inputs = c->sym_inputs && is_symmetric(jsc.data(), D);
+      c->inputs_sym = c->inputs_sym && is_symmetric(jsc.data(), D);
       c->obs_diag = r_diag;
       if (D > kMaxSmallD) TRY(dev_alloc(c, &c->d_obs_part, (size_t)c->B * c->M));   // one workgroup per observation
     }
@@ -976,11 +1024,8 @@ int vgpa_create(vgpa_ctx** out, const vgpa_config* cfg) {
     HTRY(hipMemGetInfo(&free_b, &total_b));
     const double need = 8.0 * (double)BN * (double)DD * 4.0;        // dEs + Psi + the caller's x and g still to come
     c->stream_ld = (cfg->flags & VGPA_FLAG_STREAM_LARGE_D) != 0 || need > 0.9 * (double)free_b;
-    if (c->stream_ld && c->B > 1) {      // (everything allocated so far goes back: this fires exactly when memory is short)
-      const int nb_ = c->B;
-      vgpa_destroy(c);
-      return fail(nullptr, VGPA_ERR_UNSUPPORTED, "the time-chunked large-D sweep holds one problem (a batch of %d does not fit resident)", nb_);
-    }
+    if (c->stream_ld && c->B > 1)      // (everything allocated so far goes back: this fires exactly when memory is short)
+      FAIL(VGPA_ERR_UNSUPPORTED, "the time-chunked large-D sweep holds one problem (a batch of %d does not fit resident)", c->B);
     c->lde_budget = std::fmin(16.0e9, std::fmax(1.0e9, 0.05 * (double)free_b));   // workspace of the batched energy terms
     c->ld_chunk = ld::lde_batch(D, c->lde_budget) - 1;   // a chunk evaluates ld_chunk + 1 grid points: exactly one energy batch
     if (c->ld_chunk > c->Np - 1) c->ld_chunk = c->Np - 1;
@@ -998,9 +1043,11 @@ int vgpa_create(vgpa_ctx** out, const vgpa_config* cfg) {
     TRY(upload(c, c->d_jscp, jp.data(), DD));
   }
   HTRY(hipStreamSynchronize(c->stream));
-  c->sym_inputs_shared = c->sym_inputs;
-  c->sigma_diag_shared = c->sigma_diag;
-  c->isg_iso_shared = c->isg_iso;
+  BatchInputs& in = c->in;       // every problem on the inputs of vgpa_config
+  in.m0 = {c->d_m0, 0}; in.S0 = {c->d_S0, 0}; in.obs_y = {c->d_obs_y, 0}; in.obs_t = {c->d_obs_t, 0}; in.obs_idx = {c->d_obs_idx, 0};
+  in.Sigma = {c->d_Sigma, 0}; in.isig = {c->d_isig, 0}; in.isg = {c->d_isg, 0};
+  kernel_family(c);
+#undef FAIL
 #undef TRY
 #undef HTRY
   *out = c;
@@ -1029,7 +1076,7 @@ int vgpa_solve_fwd(vgpa_ctx* c, const double* lin_a, const double* off_b, const 
   if ((rc = upload(c, c->d_op_Sigma, sigma, c->DD))) return rc;
   const bool sym = is_symmetric(s0, c->D) && is_symmetric(sigma, c->D);
   c->s_packed = false;                 // operator-level results are whole matrices
-  if ((rc = run_fwd(c, c->d_op_m0, c->d_op_S0, c->d_op_Sigma, sym))) return rc;
+  if ((rc = run_fwd(c, {c->d_op_m0, 0}, {c->d_op_S0, 0}, {c->d_op_Sigma, 0}, sym))) return rc;
   if ((rc = download(c, mt, c->d_m, BN * c->D))) return rc;
   if ((rc = download(c, st, c->d_S, BN * c->DD))) return rc;
   c->have_state = false;
@@ -1113,12 +1160,12 @@ int vgpa_energy_full(vgpa_ctx* c, const double* lin_a, const double* off_b, cons
   for (int p = 0; p < c->B; p++) {
     const double* Tp = T.data() + (size_t)p * H;
     if (c->single) {
-      const double s1 = c->pp_par ? c->h_pp_sig1[p] : c->sigma1;      // (per-problem parameters: the problem's own)
+      const double s1 = sigma1_of(c, p);
       desde_dth[p] = (c->cfg.model == VGPA_MODEL_DW ? 4.0 : 1.0) * Tp[0] / s1;
       desde_dsig[p] = -esde[p] / s1;
       continue;
     }
-    const double* is = c->pp_par ? c->h_pp_isig.data() + (size_t)p * c->DD : c->h_isig.data();
+    const double* is = isig_of(c, p);
     for (int i = 0; i < D; i++) desde_dth[(size_t)p * D + i] = is[(size_t)i * D + i] * Tp[i];
     double* out = desde_dsig + (size_t)p * D * D;          // -0.5 * Sigma^-1 diag(v) Sigma^-1
     for (int i = 0; i < D; i++)
@@ -1295,7 +1342,7 @@ int vgpa_energy_parts(vgpa_ctx* c, double* e0, double* esde, double* eobs) {
   if (!c->have_state) return fail(c, VGPA_ERR_STATE, "no cached state");
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   int rc;
-  if (e0) for (int p = 0; p < c->B; p++) e0[p] = c->pp_e0 ? c->h_pp_e0[p] : c->cfg.e0;
+  if (e0) for (int p = 0; p < c->B; p++) e0[p] = e0_of(c, p);
   if (esde && (rc = download(c, esde, c->d_esde, (size_t)c->B))) return rc;
   if (eobs && (rc = download(c, eobs, c->d_eobs, (size_t)c->B))) return rc;
   return vgpa_synchronize(c);
@@ -1322,8 +1369,7 @@ int vgpa_fetch(vgpa_ctx* c, int which, double* out) {
     case VGPA_FETCH_PSIT:
       if (!c->d_psi || c->stream_ld) return fail(c, VGPA_ERR_UNSUPPORTED, "Psi_t is not kept by the time-chunked large-D sweep");
       if (c->psi_is_q) {               // recover Psi_t = (Sigma^-1 A_t - Q''_t) / 2 in place: from here on d_psi holds Psi_t again
-        hipError_t e = launch_psi_from_q(c->B, c->Np, c->D, c->len_x, ctx_A(c), c->pp_par ? c->d_pp_isg : c->d_isg,
-                                         c->pp_par ? (size_t)c->D : 0, c->d_psi, c->stream);
+        hipError_t e = launch_psi_from_q(c->B, c->Np, c->D, c->len_x, ctx_A(c), c->in.isg.rows, c->in.isg.stride, c->d_psi, c->stream);
         if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "Psi_t recovery launch failed: %s", hipGetErrorString(e));
         c->psi_is_q = false;
       }
@@ -1445,7 +1491,7 @@ int vgpa_set_option(vgpa_ctx* c, int option, int64_t value) {
 int vgpa_set_prior_energy(vgpa_ctx* c, double e0) {
   if (!c) return VGPA_ERR_ARG;
   c->cfg.e0 = e0;
-  c->pp_e0 = false;                 // (every problem of the batch: per-problem values set earlier are gone)
+  c->in.e0 = {};                    // (every problem of the batch: per-problem values set earlier are gone)
   return VGPA_OK;
 }
 
@@ -1455,60 +1501,37 @@ int vgpa_set_problem_data(vgpa_ctx* c, const int64_t* obs_t, const double* obs_y
   if (!c->full) return fail(c, VGPA_ERR_STATE, "context was created without m0/s0/observations (ODE-only)");
   if (c->stream_ld) return fail(c, VGPA_ERR_UNSUPPORTED, "the time-chunked large-D sweep holds one problem: no per-problem data");
   const int D = c->D, M = c->M, Np = c->Np, B = c->B;
+  std::vector<int32_t> idx(obs_t && M > 0 ? (size_t)B * Np : 0);
+  bool shared_t = true;             // every row at the shared times: keep the shared-time kernels (the same results, bit for bit)
   if (obs_t && M > 0) {
     if (D > kMaxSmallD)
       return fail(c, VGPA_ERR_UNSUPPORTED, "per-problem observation times exist for D <= %d (D = %d shares the times of vgpa_config)", kMaxSmallD, D);
-    for (int p = 0; p < B; p++)
-      for (int n = 0; n < M; n++) {
-        const int64_t tn = obs_t[(size_t)p * M + n];
-        if (tn < 0 || tn >= Np || (n > 0 && tn <= obs_t[(size_t)p * M + n - 1]))
-          return fail(c, VGPA_ERR_ARG, "problem %d: obs_t must be strictly increasing indices in [0, Np)", p);
-      }
+    for (int p = 0; p < B; p++) {
+      int32_t* row = idx.data() + (size_t)p * Np;
+      if (!index_obs_times(obs_t + (size_t)p * M, M, Np, row))
+        return fail(c, VGPA_ERR_ARG, "problem %d: obs_t must be strictly increasing indices in [0, Np)", p);
+      shared_t = shared_t && std::memcmp(row, c->h_obs_idx.data(), sizeof(int32_t) * Np) == 0;
+    }
   }
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   int rc;
   // every call states the whole per-problem set: an input passed as NULL is the shared one of vgpa_config again
-  c->pp_obs_t = c->pp_obs_y = c->pp_m0 = c->pp_S0 = c->pp_e0 = false;
-  c->pp_s0_sym = !s0 || stack_symmetric(s0, (size_t)B, D);       // (a non-symmetric s0 row: both products literally)
-  c->sym_inputs = c->sym_inputs_shared && c->pp_s0_sym && c->pp_sigma_sym;
-  c->pt_dense_zeroed = false;
-  if (obs_t && M > 0) {
-    std::vector<int32_t> idx((size_t)B * Np, -1);
-    for (int p = 0; p < B; p++)
-      for (int n = 0; n < M; n++) idx[(size_t)p * Np + obs_t[(size_t)p * M + n]] = n;
-    bool shared_t = true;          // every row at the shared times: keep the shared-time kernels (the same results, bit for bit)
-    for (int p = 0; p < B && shared_t; p++) shared_t = std::memcmp(idx.data() + (size_t)p * Np, c->h_obs_idx.data(), sizeof(int32_t) * Np) == 0;
-    if (!shared_t) {
-      if ((rc = ensure(c, &c->d_pp_obs_t, (size_t)B * M))) return rc;
-      if ((rc = ensure(c, &c->d_pp_obs_idx, (size_t)B * Np))) return rc;
-      if ((rc = upload(c, c->d_pp_obs_t, obs_t, (size_t)B * M))) return rc;
-      if ((rc = upload(c, c->d_pp_obs_idx, idx.data(), idx.size()))) return rc;
-      HIP_TRY(c, hipStreamSynchronize(c->stream));          // (idx lives on this stack frame)
-    }
-    c->pp_obs_t = !shared_t;
-  }
-  if (obs_y && M > 0) {
-    if ((rc = ensure(c, &c->d_pp_obs_y, (size_t)B * M * D))) return rc;
-    if ((rc = upload(c, c->d_pp_obs_y, obs_y, (size_t)B * M * D))) return rc;
-    c->pp_obs_y = true;
-  }
-  if (m0) {
-    if ((rc = ensure(c, &c->d_pp_m0, (size_t)B * D))) return rc;
-    if ((rc = upload(c, c->d_pp_m0, m0, (size_t)B * D))) return rc;
-    c->pp_m0 = true;
-  }
-  if (s0) {
-    if ((rc = ensure(c, &c->d_pp_S0, (size_t)B * c->DD))) return rc;
-    if ((rc = upload(c, c->d_pp_S0, s0, (size_t)B * c->DD))) return rc;
-    c->pp_S0 = true;
-  }
+  BatchInputs& in = c->in;
+  in.obs_t = {c->d_obs_t, 0}; in.obs_idx = {c->d_obs_idx, 0}; in.obs_y = {c->d_obs_y, 0}; in.m0 = {c->d_m0, 0}; in.S0 = {c->d_S0, 0};
+  in.e0 = {};
+  if (!shared_t && (rc = upload_rows(c, &c->d_pp_obs_t, obs_t, M, &in.obs_t))) return rc;
+  if (!shared_t && (rc = upload_rows(c, &c->d_pp_obs_idx, idx.data(), Np, &in.obs_idx))) return rc;
+  if (obs_y && M > 0 && (rc = upload_rows(c, &c->d_pp_obs_y, obs_y, (size_t)M * D, &in.obs_y))) return rc;
+  if (m0 && (rc = upload_rows(c, &c->d_pp_m0, m0, D, &in.m0))) return rc;
+  if (s0 && (rc = upload_rows(c, &c->d_pp_S0, s0, c->DD, &in.S0))) return rc;
   if (e0) {
-    if ((rc = ensure(c, &c->d_pp_e0, (size_t)B))) return rc;
-    c->h_pp_e0.assign(e0, e0 + B);
-    if ((rc = upload(c, c->d_pp_e0, c->h_pp_e0.data(), (size_t)B))) return rc;
-    c->pp_e0 = true;
+    in.h_e0.assign(e0, e0 + B);
+    if ((rc = upload_rows(c, &c->d_pp_e0, in.h_e0.data(), 1, &in.e0))) return rc;
   }
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));          // (idx lives on this stack frame)
+  c->s0_rows_sym = !s0 || stack_symmetric(s0, (size_t)B, D);       // (a non-symmetric s0 row: both products literally)
+  kernel_family(c);
+  c->pt_dense_zeroed = false;
   c->have_state = false;            // (like vgpa_release_x: the cached state belongs to the old inputs)
   return VGPA_OK;
 }
@@ -1522,8 +1545,9 @@ int vgpa_set_problem_params(vgpa_ctx* c, const double* theta, const double* sigm
     return fail(c, VGPA_ERR_UNSUPPORTED, "the time-chunked large-D sweep holds one problem: no per-problem parameters");
   const int D = c->D, B = c->B, nth = c->cfg.n_theta;
   const size_t DD = c->DD;
-  std::vector<double> th((size_t)B * kMaxTheta), sg((size_t)B * DD), is((size_t)B * DD, 0.0), ig((size_t)B * D, 0.0), s1(B, 1.0), qs(B, 1.0);
-  bool diag = true, iso = true, sym = true, same_theta = true, same_sigma = true;
+  std::vector<double> th((size_t)B * kMaxTheta), sg((size_t)B * DD), is((size_t)B * DD), ig((size_t)B * D), s1(B), qs(B);
+  bool same_theta = true, same_sigma = true;
+  SigmaForm rows;                   // the conjunction over the rows
   for (int p = 0; p < B; p++) {
     double* tp = th.data() + (size_t)p * kMaxTheta;
     for (int i = 0; i < kMaxTheta; i++) tp[i] = (theta && i < nth) ? theta[(size_t)p * nth + i] : c->theta[i];
@@ -1531,65 +1555,37 @@ int vgpa_set_problem_params(vgpa_ctx* c, const double* theta, const double* sigm
     double* sp = sg.data() + p * DD;
     std::memcpy(sp, sigma ? sigma + p * DD : c->h_sigma.data(), sizeof(double) * DD);
     same_sigma = same_sigma && std::memcmp(sp, c->h_sigma.data(), sizeof(double) * DD) == 0;
-    double* ip = is.data() + p * DD;
-    double* gp = ig.data() + (size_t)p * D;
-    if (c->single) {
-      if (!(sp[0] > 0.0)) return fail(c, VGPA_ERR_ARG, "problem %d: the diffusion noise value: %g, should be strictly positive.", p, sp[0]);
-      s1[p] = sp[0]; ip[0] = 1.0 / sp[0]; gp[0] = ip[0];
-    } else {
-      bool rd = true;
-      for (int i = 0; i < D && rd; i++)
-        for (int j = 0; j < D; j++)
-          if (i != j && sp[(size_t)i * D + j] != 0.0) { rd = false; break; }
-      if (rd) {        // (vgpa_create's diagonal shortcut)
-        for (int i = 0; i < D; i++) {
-          const double sii = sp[(size_t)i * D + i];
-          if (!(sii > 0.0)) return fail(c, VGPA_ERR_NOT_PD, "problem %d: noise matrix is not positive definite.", p);
-          const double ci = 1.0 / std::sqrt(sii);
-          ip[(size_t)i * D + i] = ci * ci;
-          gp[i] = ci * ci;
-        }
-      } else {
-        if (!host_spd_inverse(D, sp, ip, nullptr)) return fail(c, VGPA_ERR_NOT_PD, "problem %d: noise matrix is not positive definite.", p);
-        for (int i = 0; i < D; i++) gp[i] = ip[(size_t)i * D + i];
-      }
-      diag = diag && rd;
-      for (int i = 1; i < D; i++) iso = iso && gp[i] == gp[0];
-      sym = sym && is_symmetric(sp, D);
-    }
-    qs[p] = gp[0];
+    SigmaForm f;
+    const int rc = invert_sigma(D, c->single, sp, is.data() + p * DD, ig.data() + (size_t)p * D, &s1[p], &f);
+    if (rc == VGPA_ERR_ARG) return fail(c, rc, "problem %d: the diffusion noise value: %g, should be strictly positive.", p, sp[0]);
+    if (rc) return fail(c, rc, "problem %d: noise matrix is not positive definite.", p);
+    rows.diag = rows.diag && f.diag; rows.iso = rows.iso && f.iso; rows.sym = rows.sym && f.sym;
+    qs[p] = ig[(size_t)p * D];
   }
   if (D > kMaxSmallD && !same_sigma)
     return fail(c, VGPA_ERR_UNSUPPORTED, "per-problem Sigma exists for D <= %d (D = %d shares the Sigma of vgpa_config)", kMaxSmallD, D);
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   c->have_state = false;            // (like vgpa_set_problem_data: the cached state belongs to the old parameters)
-  if (same_theta && same_sigma) {   // every row at the shared parameters: the shared kernels (the same results, bit for bit)
-    c->pp_par = false;
-    c->sigma_diag = c->sigma_diag_shared; c->isg_iso = c->isg_iso_shared; c->pp_sigma_sym = true;
-    c->sym_inputs = c->sym_inputs_shared && c->pp_s0_sym;
-    return VGPA_OK;
+  BatchInputs& in = c->in;
+  in.theta = in.sig1 = in.qs = {}; in.Sigma = {c->d_Sigma, 0}; in.isig = {c->d_isig, 0}; in.isg = {c->d_isg, 0};
+  // every row at the shared parameters: the shared kernels (the same results, bit for bit); else every row is in force -- above D = 64
+  // theta's only (Sigma is the shared one there)
+  if (!same_theta || !same_sigma) {
+    int rc;
+    in.h_theta = std::move(th);
+    if ((rc = upload_rows(c, &c->d_pp_theta, in.h_theta.data(), kMaxTheta, &in.theta))) return rc;
+    if (D <= kMaxSmallD) {
+      in.h_isig = std::move(is); in.h_sig1 = std::move(s1);
+      if ((rc = upload_rows(c, &c->d_pp_Sigma, sg.data(), DD, &in.Sigma))) return rc;
+      if ((rc = upload_rows(c, &c->d_pp_isig, in.h_isig.data(), DD, &in.isig))) return rc;
+      if ((rc = upload_rows(c, &c->d_pp_isg, ig.data(), D, &in.isg))) return rc;
+      if ((rc = upload_rows(c, &c->d_pp_sig1, in.h_sig1.data(), 1, &in.sig1))) return rc;
+      if ((rc = upload_rows(c, &c->d_pp_qs, qs.data(), 1, &in.qs))) return rc;
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));          // (the host rows live on this stack frame)
   }
-  int rc;
-  if ((rc = ensure(c, &c->d_pp_theta, (size_t)B * kMaxTheta))) return rc;
-  if ((rc = ensure(c, &c->d_pp_Sigma, (size_t)B * DD))) return rc;
-  if ((rc = ensure(c, &c->d_pp_isig, (size_t)B * DD))) return rc;
-  if ((rc = ensure(c, &c->d_pp_isg, (size_t)B * D))) return rc;
-  if ((rc = ensure(c, &c->d_pp_sig1, (size_t)B))) return rc;
-  if ((rc = ensure(c, &c->d_pp_qs, (size_t)B))) return rc;
-  if ((rc = upload(c, c->d_pp_theta, th.data(), th.size()))) return rc;
-  if ((rc = upload(c, c->d_pp_Sigma, sg.data(), sg.size()))) return rc;
-  if ((rc = upload(c, c->d_pp_isig, is.data(), is.size()))) return rc;
-  if ((rc = upload(c, c->d_pp_isg, ig.data(), ig.size()))) return rc;
-  if ((rc = upload(c, c->d_pp_sig1, s1.data(), s1.size()))) return rc;
-  if ((rc = upload(c, c->d_pp_qs, qs.data(), qs.size()))) return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));          // (the host rows live on this stack frame)
-  c->h_pp_theta = std::move(th); c->h_pp_isig = std::move(is); c->h_pp_sig1 = std::move(s1);
-  c->pp_par = true;
-  // the kernel family: the conjunction over the rows (isotropic: every row sigma_p^2 I with its own sigma_p)
-  c->sigma_diag = c->single || diag;
-  c->isg_iso = c->single || (diag && iso);
-  c->pp_sigma_sym = sym;
-  c->sym_inputs = c->sym_inputs_shared && c->pp_s0_sym && c->pp_sigma_sym;
+  c->rows_form = rows;
+  kernel_family(c);
   return VGPA_OK;
 }
 
