@@ -30,13 +30,46 @@ struct BatchInputs {
 };
 
 struct SigmaForm { bool diag = true, iso = true, sym = true; };   // of one Sigma: diagonal, sigma^2 I, symmetric
+
+// the stepping kernels of one sweep direction: ld::ld_solve_* (D > 64), one lane per problem (ode_small.hip), 16 lanes per problem
+// (ode_wave.hip), the matrix-core kernels (launch_ode_mfma, which takes Plan::sym_units), one workgroup per problem (ode_generic.hip)
+enum class Stepper { LargeD, Lane, Wave, Mfma, Generic };
+
+// Which kernels a context's fused sweep runs, and in which layout the arrays travel between them.  make_plan() derives it from cfg, D,
+// B, the CU count, the form of the inputs in force and the environment -- in vgpa_create and again when vgpa_set_problem_data /
+// vgpa_set_problem_params change the inputs; nothing else writes it.  (DESIGN.md s.4.0 has the table.)
+struct Plan {
+  bool sigma_diag = true, isg_iso = false, sym_inputs = true;   // the inputs in force: Sigma diagonal, sigma^2 I; every s0 / Sigma / constant jump symmetric
+  bool sym_units = false;       // matrix-core family: symmetric-unit kernels, not the role-specialised ones (OdeArgs::sym_units)
+  Stepper fwd = Stepper::Generic, bwd = Stepper::Generic;
+  bool lane_pass = false;      // the objective is the fused lane pass (enqueue_lane_sweep)
+  // the layout chain of the fragment-cover kernels, each step implying the one before:
+  bool bwd_upper = false;       // the backward kernel reads the upper triangle of dEsde_dS only: the energy kernel writes nothing else
+  bool store_q = false;         // ... and stores Q''_t instead of Psi_t (OdeArgs::q_on)
+  bool packed = false;          // ... S_t and dEsde_dS travel as packed lower triangles (OdeArgs::s_packed, EnergyArgs::ds_packed)
+  bool grad_in_bwd = false;     // ... the backward kernel can assemble the gradient (OdeArgs::grad_on): F-only evaluations skip the recursion
+  bool grad_in_bwd_now = false; // ... and does, at this batch size
+};
 }  // namespace
 
 struct vgpa_ctx {
   vgpa_config cfg{};
   int D = 0, Np = 0, B = 1, M = 0;
   size_t DD = 0, len_x = 0;
-  bool single = false, full = false, sigma_diag = true, sym_inputs = true;
+  bool single = false, full = false;
+  Plan plan;                          // which kernels run and in which layouts (make_plan)
+  int n_cu = 256; bool keep_pe = false;   // make_plan's inputs read once, in vgpa_create: the CU count, VGPA_ODE_KERNEL=pe
+  // What the buffers hold right now.  Each sweep sets these from the plan; operator-level calls and vgpa_fetch change them in between.
+  bool have_state = false;       // a fused sweep's state is cached
+  bool ms_valid = true;          // d_m / d_S hold the cached moments (false: only d_msT does; untransposed on demand)
+  bool derived_valid = true;     // dEsde_dm / dEsde_dS / <f> / E_sde(t) / lam / Psi belong to the cached (m, S): false behind a fused lane pass
+  bool bwd_stored = true;        // d_lam / d_psi hold the backward recursion of the cached state (false: F-only evaluation of a context whose backward
+                                 // kernel assembles the gradient -- Plan::grad_in_bwd -- or that kernel, which keeps Psi_t to itself; vgpa_fetch materialises)
+  bool s_packed = false;         // d_S holds packed lower triangles (OdeArgs::s_packed): the fused batched sweeps of the cover kernels
+  bool psi_is_q = false;         // d_psi holds Q''_t = A_t / sigma^2 - 2 Psi_t (fused batched sweeps, OdeArgs::q_on)
+  bool des_upper = false;        // d_dEs holds the upper triangles only (EnergyArgs::ds_upper)
+  bool des_packed = false;       // d_dEs holds packed lower triangles (EnergyArgs::ds_packed); d_jscp = the constant matrix jump in the same layout
+  bool pt_dense_zeroed = false;  // d_jm_pt / d_js_pt are zero off the observation rows of the current times (each sweep rewrites only those rows)
   hipStream_t stream = nullptr;
   hipStream_t stream2 = nullptr;      // side stream of the D > 64 energy terms (lde_energy's look-ahead), created on first use
   std::string err;
@@ -56,13 +89,9 @@ struct vgpa_ctx {
   bool stream_ld = false;
   int ld_chunk = 0;
   double *d_dEs_c = nullptr, *d_psi_c = nullptr;
-  bool psi_is_q = false;       // d_psi holds Q''_t = A_t / sigma^2 - 2 Psi_t (fused batched sweeps, OdeArgs::q_on)
-  bool des_upper = false;      // d_dEs holds the upper triangles only (EnergyArgs::ds_upper)
   void* h_fs = nullptr;        // pinned host block [B doubles | B status words]: F and the status words come back in one round trip (vgpa_fetch_f)
-  bool des_packed = false;     // d_dEs holds packed lower triangles (EnergyArgs::ds_packed); d_jscp = the constant matrix jump in the same layout
-  double* d_jscp = nullptr;
-  bool isg_iso = false;        // Sigma = sigma^2 I
-  double isg0 = 1.0;           // 1 / sigma^2 then
+  double* d_jscp = nullptr;    // the constant matrix jump as a packed lower triangle (des_packed)
+  double isg0 = 1.0;           // 1 / sigma^2 of a shared Sigma = sigma^2 I (Plan::isg_iso)
   std::vector<int32_t> h_obs_idx; // host copy of obs_idx [Np]
   bool obs_diag = false;          // diagonal R and H = I: Q, K are diagonal
   double* d_obs_part = nullptr;   // [B][M] per-observation energy terms (large-D observation kernel)
@@ -83,26 +112,18 @@ struct vgpa_ctx {
   int64_t* d_obs_t = nullptr;
   int32_t *d_obs_idx = nullptr, *d_status = nullptr;
   double obs_const = 0.0, sigma1 = 1.0;
-  bool have_state = false;
-  bool bwd_stored = true;        // d_lam / d_psi hold the backward recursion of the cached state (false: F-only evaluation of a context whose backward
-                                 // kernel assembles the gradient -- grad_fused_ok -- or that kernel, which keeps Psi_t to itself; vgpa_fetch materialises)
-  bool derived_valid = true;     // dEsde_dm / dEsde_dS / <f> / E_sde(t) / lam / Psi belong to the cached (m, S): false behind a fused lane pass
   double* d_msT = nullptr;       // fused lane pass: the moments time-major, problem fastest (OdeArgs::msT), [Np][D(D+1)/2 + D][bpad]: packed lower triangle of S_t, then m_t
   double* d_jmT = nullptr;       // ... and its sparse vector jumps, [M][D][bpad]
   int bpad = 0;
-  bool s_packed = false;         // d_S holds packed lower triangles (OdeArgs::s_packed): the fused batched sweeps of the cover kernels
-  double* d_Sfull = nullptr;     // ... and their unpacked copy, made when vgpa_fetch (or a kernel that wants S_t whole) asks
-  bool ms_valid = true;          // d_m / d_S hold the cached moments (false: only d_msT does; untransposed on demand)
-  bool sym_units = false;        // stepping-kernel family of this context (pick_kernel_family)
+  double* d_Sfull = nullptr;     // the unpacked copy of a packed d_S, made when vgpa_fetch (or a kernel that wants S_t whole) asks
   BatchInputs in;                // where each problem reads each batch input
   // the per-problem rows the setters upload, allocated on first use (the record points at them)
   double *d_pp_m0 = nullptr, *d_pp_S0 = nullptr, *d_pp_e0 = nullptr, *d_pp_obs_y = nullptr, *d_pp_theta = nullptr, *d_pp_Sigma = nullptr;
   double *d_pp_isig = nullptr, *d_pp_isg = nullptr, *d_pp_sig1 = nullptr, *d_pp_qs = nullptr;
   int64_t* d_pp_obs_t = nullptr; int32_t* d_pp_obs_idx = nullptr;
-  double *d_jm_pt = nullptr, *d_js_pt = nullptr;   // dense jumps [B][Np][D], [B][Np][D][D]: per-problem times on the 16-lane kernels
-  bool pt_dense_zeroed = false;      // ... zero off the observation rows of the current times (each sweep rewrites only those rows)
+  double *d_jm_pt = nullptr, *d_js_pt = nullptr;   // dense jumps [B][Np][D], [B][Np][D][D]: per-problem times on the 16-lane kernels (pt_dense_zeroed)
   std::vector<double> h_sigma;       // host copy of the shared Sigma [D][D]
-  SigmaForm sigma_form, rows_form;            // kernel_family's inputs: the form of the shared Sigma, of the per-problem rows in force,
+  SigmaForm sigma_form, rows_form;            // make_plan's inputs: the form of the shared Sigma, of the per-problem rows in force,
   bool inputs_sym = true, s0_rows_sym = true;  // ... the shared s0 and constant jump symmetric, the per-problem s0 rows symmetric
   // profiling
   bool prof = false;
@@ -128,6 +149,12 @@ int fail(vgpa_ctx* c, int code, const char* fmt, ...) {
   do {                                                                                              \
     hipError_t e_ = (expr);                                                                         \
     if (e_ != hipSuccess) return fail((c), VGPA_ERR_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); \
+  } while (0)
+// a launcher's status: "<what> failed: <error>"
+#define LAUNCH_TRY(c, what, expr)                                                                   \
+  do {                                                                                              \
+    hipError_t e_ = (expr);                                                                         \
+    if (e_ != hipSuccess) return fail((c), VGPA_ERR_DEVICE, what " failed: %s", hipGetErrorString(e_)); \
   } while (0)
 
 template <typename T>
@@ -208,6 +235,61 @@ int invert_sigma(int D, bool single, const double* sigma, double* isig, double* 
   return VGPA_OK;
 }
 
+// The observation terms' constants from R = obs_noise and H = obs_h (null: the identity), into arrays that are zero on entry:
+// Q = H R^-1 H^T, K = H^T R^-1 H^T, rinv = diag(R^-1), jsc = H^T R^-1 H / 2 (the constant matrix jump), obs_const = the Gaussian
+// normalisation of the M observations; diag: diagonal R and H = I, so that Q and K are diagonal.  1-D models: the scalars r and h.
+// VGPA_ERR_NOT_PD: R is not positive (definite).
+int obs_constants(int D, int M, bool single, const double* obs_noise, const double* obs_h, double* Q, double* K, double* rinv, double* jsc,
+                  double* obs_const, bool* diag) {
+  *diag = false;
+  if (single) {
+    const double r = obs_noise[0];
+    if (!(r > 0.0)) return VGPA_ERR_NOT_PD;
+    const double h = obs_h ? obs_h[0] : 1.0;
+    Q[0] = 1.0 / r; K[0] = h; rinv[0] = 1.0 / r; jsc[0] = 0.5 / r;
+    *obs_const = 0.5 * M * (std::log(2.0 * M_PI) + std::log(r));
+    return VGPA_OK;
+  }
+  const size_t DD = (size_t)D * D;
+  double logdet = 0.0;
+  // fast path: diagonal R and H = I (no O(D^3) host work at large D).  An explicitly passed identity counts as
+  // "no operator" (the reference's Likelihood materialises np.eye(d) when the operator is None, likelihood.py:33-40).
+  bool h_identity = true;
+  if (obs_h)
+    for (int i = 0; i < D && h_identity; i++)
+      for (int j = 0; j < D; j++)
+        if (obs_h[(size_t)i * D + j] != (i == j ? 1.0 : 0.0)) { h_identity = false; break; }
+  bool r_diag = h_identity;
+  for (int i = 0; i < D && r_diag; i++)
+    for (int j = 0; j < D; j++)
+      if (i != j && obs_noise[(size_t)i * D + j] != 0.0) { r_diag = false; break; }
+  *diag = r_diag;
+  if (r_diag) {
+    for (int i = 0; i < D; i++) {
+      const double rii = obs_noise[(size_t)i * D + i];
+      if (!(rii > 0.0)) return VGPA_ERR_NOT_PD;
+      const double ci = 1.0 / std::sqrt(rii);
+      const double ri = ci * ci;
+      Q[(size_t)i * D + i] = ri; K[(size_t)i * D + i] = ri; jsc[(size_t)i * D + i] = 0.5 * ri; rinv[i] = ri;
+      logdet += std::log(std::sqrt(rii));
+    }
+    logdet *= 2.0;
+  } else {
+    std::vector<double> Rinv(DD, 0.0), H(DD, 0.0), T(DD);
+    if (!host_spd_inverse(D, obs_noise, Rinv.data(), &logdet)) return VGPA_ERR_NOT_PD;
+    if (obs_h && !h_identity) H.assign(obs_h, obs_h + DD); else for (int i = 0; i < D; i++) H[(size_t)i * D + i] = 1.0;
+    host_matmul(D, H.data(), Rinv.data(), T.data(), false, false);      // H R^-1
+    host_matmul(D, T.data(), H.data(), Q, false, true);                 // H R^-1 H^T
+    host_matmul(D, H.data(), Rinv.data(), T.data(), true, false);       // H^T R^-1
+    host_matmul(D, T.data(), H.data(), K, false, true);                 // H^T R^-1 H^T
+    host_matmul(D, T.data(), H.data(), jsc, false, false);              // H^T R^-1 H
+    for (size_t e = 0; e < DD; e++) jsc[e] *= 0.5;
+    for (int i = 0; i < D; i++) rinv[i] = Rinv[(size_t)i * D + i];
+  }
+  *obs_const = M * (D * std::log(2.0 * M_PI) + logdet);
+  return VGPA_OK;
+}
+
 // one row of observation times: false unless strictly increasing indices in [0, Np); idx [Np] -> observation counter n, or -1
 bool index_obs_times(const int64_t* obs_t, int M, int Np, int32_t* idx) {
   std::fill(idx, idx + Np, -1);
@@ -250,14 +332,6 @@ static const double* isig_of(const vgpa_ctx* c, int p) { return c->in.isig.strid
 static double sigma1_of(const vgpa_ctx* c, int p) { return c->in.sig1.rows ? c->in.h_sig1[p] : c->sigma1; }
 static double e0_of(const vgpa_ctx* c, int p) { return c->in.e0.rows ? c->in.h_e0[p] : c->cfg.e0; }
 
-// the kernel-family flags of the inputs in force: the form of the shared Sigma or of the per-problem rows (isotropic: every row
-// sigma_p^2 I with its own sigma_p); symmetric: every s0 / Sigma and the constant jump (else both products of the slope literally)
-static void kernel_family(vgpa_ctx* c) {
-  const SigmaForm& f = c->in.Sigma.stride ? c->rows_form : c->sigma_form;
-  c->sigma_diag = f.diag; c->isg_iso = f.iso;
-  c->sym_inputs = c->inputs_sym && c->s0_rows_sym && c->sigma_form.sym && f.sym;
-}
-
 static void prof_mark(vgpa_ctx* c, int i) {
   if (c->prof) (void)hipEventRecord(c->ev[i], c->stream);
 }
@@ -273,48 +347,90 @@ static void prof_collect(vgpa_ctx* c) {
   c->prof_pending = false;
 }
 
+// a gradient is behind everything enqueued so far: close the profile's last phase
+static int prof_end(vgpa_ctx* c, int rc) {
+  if (rc == VGPA_OK && c->prof) { prof_mark(c, 4); c->prof_pending = true; }
+  return rc;
+}
+
+// The stepper of one sweep direction; sym: the caller's matrices are symmetric (Plan::sym_inputs for the fused sweep, the symmetry of
+// the arrays it brought for an operator-level call).
 // D <= 4: one lane per problem (any inputs) -- always at D = 1, from 512 problems at D = 2..4 (below that a problem per
 // workgroup has the shorter latency: Lorenz-63 RK4 Np = 1001 forward 1.2 ms vs 1.6 ms; at 65536 problems 108 ms vs
-// 6 ms).  VGPA_FLAG_FORCE_GENERIC keeps the workgroup-per-problem kernels.
-static bool use_lane(vgpa_ctx* c) {
-  // (the lane kernels address a wave's 64 problems with 32-bit byte offsets from a wave-uniform base)
-  return c->D <= kMaxLaneD && !(c->cfg.flags & VGPA_FLAG_FORCE_GENERIC) && (c->D == 1 || c->B >= 512) && c->len_x < ((size_t)1 << 22);
-}
-// the fused lane pass (ode_small.hip::k_sweep_lane): forward kernel -> observations -> ONE kernel for the E_sde terms, the backward
-// recursion, the gradient and F
-static bool lane_fused(vgpa_ctx* c) {
-  // (msT carries S_t as its lower triangle: a non-symmetric s0 / Sigma keeps the four-kernel path, which handles both halves literally)
-  return use_lane(c) && c->full && sweep_lane_supported(c->cfg.model, c->D) && !(c->cfg.flags & VGPA_FLAG_MATERIALIZE) &&
-         (c->D == 1 || c->sym_inputs);
-}
-// D = 2..4 below that: 16 lanes per problem, operands exchanged by ds_bpermute (ode_wave.hip)
-static bool use_wave(vgpa_ctx* c) {
-  return c->D >= 2 && c->D <= kMaxLaneD && !(c->cfg.flags & VGPA_FLAG_FORCE_GENERIC) && !use_lane(c);
+// 6 ms); D = 2..4 below that: 16 lanes per problem, operands exchanged by ds_bpermute (ode_wave.hip).
+// VGPA_FLAG_FORCE_GENERIC keeps the workgroup-per-problem kernels.
+static Stepper stepper(const vgpa_ctx* c, bool fwd, bool sym) {
+  if (c->D > kMaxSmallD) return Stepper::LargeD;
+  if (c->cfg.flags & VGPA_FLAG_FORCE_GENERIC) return Stepper::Generic;
+  if (c->D <= kMaxLaneD) {
+    // (the lane kernels address a wave's 64 problems with 32-bit byte offsets from a wave-uniform base)
+    if ((c->D == 1 || c->B >= 512) && c->len_x < ((size_t)1 << 22)) return Stepper::Lane;
+    if (c->D >= 2) return Stepper::Wave;
+  }
+  return sym && ode_mfma_supported(c->cfg.method, fwd, c->D) ? Stepper::Mfma : Stepper::Generic;
 }
 
-// D <= 44 has two families of matrix-core stepping kernels: the symmetric-unit ones (two problems per CU, 4 waves each) win
-// once there are more problems than CUs, the role-specialised ones (one problem per CU, 8 waves) below that and for one
-// problem.  (D = 41 .. 44: one symmetric-unit workgroup per CU only -- its LDS -- so the role-specialised kernels stay.)
-// 33 <= D <= 40 (round 3): the fragment-cover kernels win at every batch size -- a lone workgroup steps 4 % faster than the
-// role-specialised pair (4.45 / 4.93 against 4.65 / 4.97 ms per forward / backward sweep of one problem), and the Q'' stream and
-// the pipelined gradient assembly come with them; VGPA_ODE_KERNEL=pe in the environment keeps the role-specialised family there
-// (comparison runs, tests).
-static bool use_sym_units(vgpa_ctx* c) { return c->sym_units; }   // decided once in vgpa_create (pick_kernel_family)
+// ... from kFusedGradMinBatch problems on (VGPA_FUSED_GRAD=1 in the environment: always).  The third wave set costs the recursion
+// ~0.4-0.5 ms per launch round (its matrix-core and vector-ALU instructions share the SIMDs' issue port with the product waves), the
+// separate assembly ~7 us per problem: below ~70 problems the backward kernel followed by k_grad_mfma_q is the shorter way.
+constexpr int kFusedGradMinBatch = 64;
+static bool fused_grad_always() {
+  static const bool always = [] { const char* e = getenv("VGPA_FUSED_GRAD"); return e && e[0] == '1'; }();
+  return always;
+}
 
-static void pick_kernel_family(vgpa_ctx* c) {
-  int n_cu = 0;
-  if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->cfg.device) != hipSuccess || n_cu <= 0) n_cu = 256;
-  const char* fam = getenv("VGPA_ODE_KERNEL");
-  const bool keep_pe = fam && !strcmp(fam, "pe");
-  const int nb = (c->D + 3) / 4;
+// The one place that decides a context's kernels (Plan).  Reads cfg, D, B, len_x, full, n_cu, keep_pe and the forms of the inputs.
+static void make_plan(vgpa_ctx* c) {
+  Plan p;
+  // the form of the shared Sigma or of the per-problem rows (isotropic: every row sigma_p^2 I with its own sigma_p); symmetric: every
+  // s0 / Sigma and the constant jump (else both products of the slope literally)
+  const SigmaForm& f = c->in.Sigma.stride ? c->rows_form : c->sigma_form;
+  p.sigma_diag = f.diag; p.isg_iso = f.iso;
+  p.sym_inputs = c->inputs_sym && c->s0_rows_sym && c->sigma_form.sym && f.sym;
+  // D <= 44 has two families of matrix-core stepping kernels: the symmetric-unit ones (two problems per CU, 4 waves each) win
+  // once there are more problems than CUs, the role-specialised ones (one problem per CU, 8 waves) below that and for one
+  // problem.  (D = 41 .. 44: one symmetric-unit workgroup per CU only -- its LDS -- so the role-specialised kernels stay.)
+  // 33 <= D <= 40 (round 3): the fragment-cover kernels win at every batch size -- a lone workgroup steps 4 % faster than the
+  // role-specialised pair (4.45 / 4.93 against 4.65 / 4.97 ms per forward / backward sweep of one problem), and the Q'' stream and
+  // the pipelined gradient assembly come with them; VGPA_ODE_KERNEL=pe in the environment keeps the role-specialised family there
+  // (comparison runs, tests).
   // (D > 44 has no other matrix-core stepper: launch_ode_mfma always takes the symmetric-unit kernels there, so the context
   //  says so too and the energy kernel writes dEsde_dS as the upper triangle those kernels read)
-  c->sym_units = (c->cfg.flags & VGPA_FLAG_SYM_UNITS) != 0 || (c->B > n_cu && nb <= 10) || ((nb == 9 || nb == 10) && !keep_pe) ||
-                 (nb >= 12 && c->D <= kMaxSmallD);
+  const int nb = (c->D + 3) / 4;
+  p.sym_units = (c->cfg.flags & VGPA_FLAG_SYM_UNITS) != 0 || (c->B > c->n_cu && nb <= 10) || ((nb == 9 || nb == 10) && !c->keep_pe) ||
+                (nb >= 12 && c->D <= kMaxSmallD);
+  p.fwd = stepper(c, true, p.sym_inputs);
+  p.bwd = stepper(c, false, p.sym_inputs);
+  // the fused lane pass (ode_small.hip::k_sweep_lane): forward kernel -> observations -> ONE kernel for the E_sde terms, the backward
+  // recursion, the gradient and F
+  // (msT carries S_t as its lower triangle: a non-symmetric s0 / Sigma keeps the four-kernel path, which handles both halves literally)
+  p.lane_pass = p.fwd == Stepper::Lane && c->full && sweep_lane_supported(c->cfg.model, c->D) && !(c->cfg.flags & VGPA_FLAG_MATERIALIZE) &&
+                 (c->D == 1 || p.sym_inputs);
+  // (a symmetric-unit backward kernel reads the upper triangle of dEsde_dS only; VGPA_FLAG_KEEP_PSI keeps whole matrices and Psi_t)
+  p.bwd_upper = p.sym_units && p.bwd == Stepper::Mfma && !(c->cfg.flags & VGPA_FLAG_KEEP_PSI);
+  // Q''_t instead of Psi_t on the fragment-cover kernels (33 <= D <= 40, RK2 / RK4) with Sigma = sigma^2 I and Lorenz-96: the gradient
+  // assembly (k_grad_mfma_q) then does not read A_t
+  p.store_q = p.bwd_upper && p.sigma_diag && p.isg_iso && c->cfg.model == VGPA_MODEL_L96 && sym_stores_q(c->cfg.method, c->D);
+  // S_t as its packed lower triangle between the kernels of a fused sweep: exactly where the gradient assembly will be k_grad_mfma_q
+  // and the energy terms come from k_energy_l96_r; dEsde_dS between that kernel and the backward cover kernel likewise
+  p.packed = p.store_q && p.fwd == Stepper::Mfma;
+  // the backward kernel assembles the gradient itself: wherever S_t is packed and the stepper's kernel can.  F-only evaluations of
+  // such a context skip the backward recursion altogether (F does not depend on it); gradient(x, eval_fun=False) runs it.
+  p.grad_in_bwd = p.packed && sym_fuses_grad(c->cfg.method, c->D);
+  p.grad_in_bwd_now = p.grad_in_bwd && (fused_grad_always() || c->B >= kFusedGradMinBatch);
+  c->plan = p;
 }
 
-static bool use_mfma(vgpa_ctx* c, bool fwd, bool sym) {
-  return sym && !(c->cfg.flags & VGPA_FLAG_FORCE_GENERIC) && ode_mfma_supported(c->cfg.method, fwd, c->D);
+// the small-D steppers share OdeArgs (the large-D drivers take their arrays one by one: run_fwd / run_bwd call them)
+static hipError_t launch_stepper(Stepper k, int method, bool fwd, const OdeArgs& a, hipStream_t st) {
+  switch (k) {
+    case Stepper::Lane: return launch_ode_small(method, fwd, a, st);
+    case Stepper::Wave: return launch_ode_wave(method, fwd, a, st);
+    case Stepper::Mfma: return launch_ode_mfma(method, fwd, a, st);
+    case Stepper::Generic: return launch_ode_generic(method, fwd, a, st);
+    case Stepper::LargeD: break;
+  }
+  return hipErrorInvalidValue;
 }
 
 static int ensure_ld_ws(vgpa_ctx* c) {
@@ -347,14 +463,24 @@ struct LdBatch {
   bool on;
 };
 
-// the forward sweep's OdeArgs: x, the moment histories, the initial moments and the forcing term
-static OdeArgs fwd_args(vgpa_ctx* c, Rows<double> m0, Rows<double> S0, Rows<double> Sigma) {
+// what every stepping kernel's OdeArgs starts with: the sizes, x and the moment histories
+static OdeArgs ode_args(vgpa_ctx* c) {
   OdeArgs a{};
   a.D = c->D; a.Np = c->Np; a.batch = c->B; a.dt = c->cfg.dt;
   a.strideA = a.strideB = c->len_x;
   a.A = ctx_A(c); a.b = ctx_b(c); a.m = c->d_m; a.S = c->d_S;
+  return a;
+}
+
+// the forward sweep's OdeArgs: ... with the initial moments and the forcing term
+static OdeArgs fwd_args(vgpa_ctx* c, Rows<double> m0, Rows<double> S0, Rows<double> Sigma) {
+  OdeArgs a = ode_args(c);
   a.m0 = m0.rows; a.m0_stride = m0.stride; a.S0 = S0.rows; a.S0_stride = S0.stride; a.Sigma = Sigma.rows; a.Sigma_stride = Sigma.stride;
   return a;
+}
+
+static void copy_theta(const vgpa_ctx* c, double* theta) {
+  for (int i = 0; i < kMaxTheta; i++) theta[i] = c->theta[i];
 }
 
 // the sparse observation jumps of the backward recursion (des_packed is never set behind the lane pass: js_const = d_jsc there)
@@ -363,60 +489,55 @@ static void sparse_jumps(vgpa_ctx* c, OdeArgs& a) {
   a.jm_sparse = c->d_jm; a.js_const = c->des_packed ? c->d_jscp : c->d_jsc; a.n_obs = c->M;
 }
 
+// sym: Plan::sym_inputs for the fused sweep (the stepper is then Plan::fwd), the symmetry of the caller's arrays for vgpa_solve_fwd
 static int run_fwd(vgpa_ctx* c, Rows<double> m0, Rows<double> S0, Rows<double> Sigma, bool sym) {
   ld::use_library_gemm = (c->cfg.flags & VGPA_FLAG_LIBRARY_GEMM) != 0;
   c->ms_valid = true;                  // (every path below writes the [B][Np] arrays m / S)
-  if (c->D > kMaxSmallD) {
+  const Stepper k = stepper(c, true, sym);
+  if (k == Stepper::LargeD) {
     int rc = ensure_ld_ws(c);
     if (rc) return rc;
     LdBatch batch(c);
     LdLiteral literal(!sym);             // non-symmetric s0 / sigma: both products of the slope literally (ode_solver.py:60)
-    hipError_t e = ld::ld_solve_fwd(c->cfg.method, c->cfg.dt, c->D, c->Np, ctx_A(c), ctx_b(c), m0.rows, S0.rows, Sigma.rows, c->d_m,
-                                    c->d_S, c->d_ld_ws, c->stream);
-    if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "large-D forward sweep failed: %s", hipGetErrorString(e));
+    LAUNCH_TRY(c, "large-D forward sweep", ld::ld_solve_fwd(c->cfg.method, c->cfg.dt, c->D, c->Np, ctx_A(c), ctx_b(c), m0.rows, S0.rows,
+                                                            Sigma.rows, c->d_m, c->d_S, c->d_ld_ws, c->stream));
     return VGPA_OK;
   }
   OdeArgs a = fwd_args(c, m0, S0, Sigma);
-  a.sym_units = use_sym_units(c) ? 1 : 0;
+  a.sym_units = c->plan.sym_units ? 1 : 0;
   a.s_packed = c->s_packed ? 1 : 0;
-  hipError_t e = use_lane(c) ? launch_ode_small(c->cfg.method, true, a, c->stream)
-                 : use_wave(c) ? launch_ode_wave(c->cfg.method, true, a, c->stream)
-                 : use_mfma(c, true, sym) ? launch_ode_mfma(c->cfg.method, true, a, c->stream)
-                                          : launch_ode_generic(c->cfg.method, true, a, c->stream);
-  if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "forward sweep launch failed: %s", hipGetErrorString(e));
+  LAUNCH_TRY(c, "forward sweep launch", launch_stepper(k, c->cfg.method, true, a, c->stream));
   return VGPA_OK;
 }
 
-static bool grad_fused_ok(vgpa_ctx* c);
 static ObsArgs obs_args(vgpa_ctx* c);
-// g_fused: the backward kernel assembles the gradient into it (grad_fused_ok contexts; Psi_t is then not stored)
+// sym: as in run_fwd (dense_jumps: vgpa_solve_bwd's call, with the caller's arrays).  g_fused: the backward kernel assembles the
+// gradient into it (Plan::grad_in_bwd contexts; Psi_t is then not stored)
 static int run_bwd(vgpa_ctx* c, bool dense_jumps, bool sym, double* g_fused = nullptr) {
   ld::use_library_gemm = (c->cfg.flags & VGPA_FLAG_LIBRARY_GEMM) != 0;
   int rc;
-  if (g_fused && (dense_jumps || !grad_fused_ok(c) || !c->s_packed)) return fail(c, VGPA_ERR_STATE, "fused gradient assembly asked of a context without it");
+  if (g_fused && (dense_jumps || !c->plan.grad_in_bwd || !c->s_packed)) return fail(c, VGPA_ERR_STATE, "fused gradient assembly asked of a context without it");
   if ((rc = ensure(c, &c->d_psi, (size_t)c->B * c->Np * c->DD))) return rc;
   if ((rc = ensure(c, &c->d_dEs, (size_t)c->B * c->Np * c->DD))) return rc;
   c->psi_is_q = false;
-  if (c->D > kMaxSmallD) {
+  const Stepper k = stepper(c, false, sym);
+  if (k == Stepper::LargeD) {
     if ((rc = ensure_ld_ws(c))) return rc;
     LdBatch batch(c);
     LdLiteral literal(!sym);             // non-symmetric dEsde_ds / dEobs_ds (ode_solver.py:94)
     // operator-level calls bring dense jump arrays; the fused sweep uses the sparse ones (obs index on the host)
-    hipError_t e = dense_jumps
+    LAUNCH_TRY(c, "large-D backward sweep", dense_jumps
         ? ld::ld_solve_bwd(c->cfg.method, c->cfg.dt, c->D, c->Np, ctx_A(c), c->d_dEm, c->d_dEs, c->d_jm_dense, c->d_js_dense,
                            c->d_lam, c->d_psi, c->d_ld_ws, c->stream)
         : ld::ld_solve_bwd(c->cfg.method, c->cfg.dt, c->D, c->Np, ctx_A(c), c->d_dEm, c->d_dEs, c->d_jm, c->d_jsc,
-                           c->d_lam, c->d_psi, c->d_ld_ws, c->stream, c->h_obs_idx.data());
-    if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "large-D backward sweep failed: %s", hipGetErrorString(e));
+                           c->d_lam, c->d_psi, c->d_ld_ws, c->stream, c->h_obs_idx.data()));
     return VGPA_OK;
   }
-  OdeArgs a{};
-  a.sym_units = use_sym_units(c) ? 1 : 0;
-  a.D = c->D; a.Np = c->Np; a.batch = c->B; a.dt = c->cfg.dt;
-  a.strideA = a.strideB = c->len_x;
-  a.A = ctx_A(c); a.dEm = c->d_dEm; a.dEs = c->d_dEs; a.lam = c->d_lam; a.psi = c->d_psi;
+  OdeArgs a = ode_args(c);   // (b, m, S: read only with grad_on)
+  a.sym_units = c->plan.sym_units ? 1 : 0;
+  a.dEm = c->d_dEm; a.dEs = c->d_dEs; a.lam = c->d_lam; a.psi = c->d_psi;
   if (dense_jumps) { a.jm_dense = c->d_jm_dense; a.js_dense = c->d_js_dense; }
-  else if (c->in.obs_idx.stride && use_wave(c)) {
+  else if (c->in.obs_idx.stride && k == Stepper::Wave) {
     // per-problem times on the 16-lane kernels (four problems per wave, whose jump index is wave-uniform): dense jump arrays
     // (B Np (D + D^2) doubles, zeroed once per set of times; a sweep rewrites the B M (D + D^2) entries of the observation rows)
     if ((rc = ensure(c, &c->d_jm_pt, (size_t)c->B * c->Np * c->D))) return rc;
@@ -426,32 +547,25 @@ static int run_bwd(vgpa_ctx* c, bool dense_jumps, bool sym, double* g_fused = nu
       HIP_TRY(c, hipMemsetAsync(c->d_js_pt, 0, sizeof(double) * c->B * c->Np * c->DD, c->stream));
       c->pt_dense_zeroed = true;
     }
-    hipError_t e = launch_obs_dense(obs_args(c), c->d_jsc, c->d_jm_pt, c->d_js_pt, c->stream);
-    if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "obs dense launch failed: %s", hipGetErrorString(e));
+    LAUNCH_TRY(c, "obs dense launch", launch_obs_dense(obs_args(c), c->d_jsc, c->d_jm_pt, c->d_js_pt, c->stream));
     a.jm_dense = c->d_jm_pt; a.js_dense = c->d_js_pt;
   } else {
     sparse_jumps(c, a);
   }
   a.ds_packed = c->des_packed ? 1 : 0;
-  // fused sweeps on the fragment-cover kernels: Q''_t instead of Psi_t (the gradient assembly then does not read A_t; see
-  // VGPA_FLAG_KEEP_PSI).  Same condition as the kernel choice below and as run_grad's matrix-core assembly.
-  c->psi_is_q = !dense_jumps && a.sym_units && !use_lane(c) && !use_wave(c) && use_mfma(c, false, sym) && c->sigma_diag && c->isg_iso &&
-                c->cfg.model == VGPA_MODEL_L96 && !(c->cfg.flags & VGPA_FLAG_KEEP_PSI) && sym_stores_q(c->cfg.method, c->D);
+  // (the fused sweep's call: the stepper is Plan::bwd then.  An operator-level call wants Psi_t itself)
+  c->psi_is_q = !dense_jumps && c->plan.store_q;
   a.q_on = c->psi_is_q ? 1 : 0;
   a.q_scale = c->isg0;
   a.q_scale_v = c->in.qs.rows;               // (read only by the Q'' kernels: every row isotropic then)
   if (g_fused) {                           // the gradient assembly on the kernel's helper waves (k_ode_sym, GF)
     if (!c->psi_is_q) return fail(c, VGPA_ERR_STATE, "fused gradient assembly: the backward kernel is not the Q'' one");
     a.grad_on = 1; a.g = g_fused; a.s_packed = 1;
-    a.S = c->d_S; a.m = c->d_m; a.b = ctx_b(c); a.Ef = c->d_Ef; a.Am = c->d_Am;
+    a.Ef = c->d_Ef; a.Am = c->d_Am;
     c->psi_is_q = false;                   // (nothing is stored in d_psi)
   }
   c->bwd_stored = !g_fused;
-  hipError_t e = use_lane(c) ? launch_ode_small(c->cfg.method, false, a, c->stream)
-                 : use_wave(c) ? launch_ode_wave(c->cfg.method, false, a, c->stream)
-                 : use_mfma(c, false, sym) ? launch_ode_mfma(c->cfg.method, false, a, c->stream)
-                                           : launch_ode_generic(c->cfg.method, false, a, c->stream);
-  if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "backward sweep launch failed: %s", hipGetErrorString(e));
+  LAUNCH_TRY(c, "backward sweep launch", launch_stepper(k, c->cfg.method, false, a, c->stream));
   return VGPA_OK;
 }
 
@@ -460,7 +574,7 @@ static EnergyArgs energy_args(vgpa_ctx* c, double* edf, bool ds_upper = false) {
   a.ds_upper = ds_upper ? 1 : 0;
   a.s_packed = c->s_packed ? 1 : 0;
   a.model = c->cfg.model; a.D = c->D; a.Np = c->Np; a.batch = c->B; a.dt = c->cfg.dt;
-  for (int i = 0; i < kMaxTheta; i++) a.theta[i] = c->theta[i];
+  copy_theta(c, a.theta);
   a.sigma1 = c->sigma1; a.isg = c->in.isg.rows; a.isg_stride = c->in.isg.stride;
   a.theta_v = c->in.theta.rows; a.sigma1_v = c->in.sig1.rows;
   a.strideA = a.strideB = c->len_x;
@@ -493,12 +607,11 @@ static int run_energy(vgpa_ctx* c, double* edf, bool ds_upper = false, bool ds_p
     // the energy terms are batched over grid points already: problem by problem
     const size_t NpD = (size_t)c->Np * c->D, NpDD = (size_t)c->Np * c->DD;
     for (int p = 0; p < c->B; p++) {
-      hipError_t e = ld::lde_energy(c->D, c->Np, theta_of(c, p)[0], c->in.isg.of(p), ctx_A(c) + p * c->len_x,
-                                    ctx_b(c) + p * c->len_x, c->d_m + p * NpD, c->d_S + p * NpDD, c->d_et + (size_t)p * c->Np,
-                                    c->d_Ef + p * NpD, edf ? edf + p * NpDD : nullptr, c->d_dEm + p * NpD, c->d_dEs + p * NpDD,
-                                    c->d_status + p, c->d_lde_ws, c->lde_nb, c->stream,
-                                    c->hyp_on ? c->d_hyp + (size_t)p * c->Np * 2 * c->D : nullptr, c->stream2);
-      if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "large-D energy failed: %s", hipGetErrorString(e));
+      LAUNCH_TRY(c, "large-D energy", ld::lde_energy(c->D, c->Np, theta_of(c, p)[0], c->in.isg.of(p), ctx_A(c) + p * c->len_x,
+                                                     ctx_b(c) + p * c->len_x, c->d_m + p * NpD, c->d_S + p * NpDD, c->d_et + (size_t)p * c->Np,
+                                                     c->d_Ef + p * NpD, edf ? edf + p * NpDD : nullptr, c->d_dEm + p * NpD, c->d_dEs + p * NpDD,
+                                                     c->d_status + p, c->d_lde_ws, c->lde_nb, c->stream,
+                                                     c->hyp_on ? c->d_hyp + (size_t)p * c->Np * 2 * c->D : nullptr, c->stream2));
     }
     return VGPA_OK;
   }
@@ -507,8 +620,7 @@ static int run_energy(vgpa_ctx* c, double* edf, bool ds_upper = false, bool ds_p
   if (c->des_packed) c->des_upper = false;
   EnergyArgs a = energy_args(c, edf, c->des_upper);
   a.ds_packed = c->des_packed ? 1 : 0;
-  hipError_t e = launch_energy(a, c->stream);
-  if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "energy launch failed: %s", hipGetErrorString(e));
+  LAUNCH_TRY(c, "energy launch", launch_energy(a, c->stream));
   return VGPA_OK;
 }
 
@@ -528,8 +640,7 @@ static int run_reduce(vgpa_ctx* c) {
   r.Np = c->Np; r.batch = c->B; r.dt = c->cfg.dt; r.e0 = c->cfg.e0; r.e0v = c->in.e0.rows;
   r.pre = c->single ? 0.5 : 1.0; r.div = c->single ? c->sigma1 : 1.0; r.div_v = c->single ? c->in.sig1.rows : nullptr;
   r.e_t = c->d_et; r.eobs = c->d_eobs; r.esde = c->d_esde; r.f = c->d_f;
-  hipError_t e = launch_reduce(r, c->stream);
-  if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "reduce launch failed: %s", hipGetErrorString(e));
+  LAUNCH_TRY(c, "reduce launch", launch_reduce(r, c->stream));
   return VGPA_OK;
 }
 
@@ -542,17 +653,16 @@ static int run_grad(vgpa_ctx* c, double* g_dev) {
     const size_t NpD = (size_t)c->Np * c->D, NpDD = (size_t)c->Np * c->DD;
     for (int p = 0; p < c->B; p++) {
       double* gp = g_dev + p * c->len_x;
-      hipError_t e = ld::lde_grad(c->D, c->Np, c->cfg.dt, c->in.isg.of(p), ctx_A(c) + p * c->len_x, ctx_b(c) + p * c->len_x, c->d_m + p * NpD,
-                                  c->d_S + p * NpDD, c->d_lam + p * NpD, c->d_psi + p * NpDD, c->d_Ef + p * NpD, gp, gp + NpDD, c->d_lde_ws,
-                                  c->lde_nb, c->stream, c->sigma_diag ? nullptr : c->in.isig.of(p));
-      if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "large-D gradient failed: %s", hipGetErrorString(e));
+      LAUNCH_TRY(c, "large-D gradient", ld::lde_grad(c->D, c->Np, c->cfg.dt, c->in.isg.of(p), ctx_A(c) + p * c->len_x, ctx_b(c) + p * c->len_x, c->d_m + p * NpD,
+                                                     c->d_S + p * NpDD, c->d_lam + p * NpD, c->d_psi + p * NpDD, c->d_Ef + p * NpD, gp, gp + NpDD, c->d_lde_ws,
+                                                     c->lde_nb, c->stream, c->plan.sigma_diag ? nullptr : c->in.isig.of(p)));
     }
     return VGPA_OK;
   }
   GradArgs a{};
-  a.model = c->cfg.model; a.D = c->D; a.Np = c->Np; a.batch = c->B; a.sigma_diag = c->sigma_diag ? 1 : 0;
+  a.model = c->cfg.model; a.D = c->D; a.Np = c->Np; a.batch = c->B; a.sigma_diag = c->plan.sigma_diag ? 1 : 0;
   a.dt = c->cfg.dt;
-  for (int i = 0; i < kMaxTheta; i++) a.theta[i] = c->theta[i];
+  copy_theta(c, a.theta);
   a.strideA = a.strideB = c->len_x;
   a.A = ctx_A(c); a.b = ctx_b(c); a.m = c->d_m; a.S = c->d_S; a.lam = c->d_lam; a.psi = c->d_psi;
   a.isig = c->in.isig.rows; a.isig_stride = c->in.isig.stride; a.theta_v = c->in.theta.rows;
@@ -567,8 +677,7 @@ static int run_grad(vgpa_ctx* c, double* g_dev) {
   }
   a.Am = c->d_Am;                                  // written by the L96 energy kernel of the same sweep (else null)
   a.scalar_product = (c->cfg.flags & VGPA_FLAG_FORCE_GENERIC) ? 1 : 0;
-  hipError_t e = launch_grad(a, c->stream);
-  if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "gradient launch failed: %s", hipGetErrorString(e));
+  LAUNCH_TRY(c, "gradient launch", launch_grad(a, c->stream));
   return VGPA_OK;
 }
 
@@ -595,32 +704,29 @@ static int stream_pass(vgpa_ctx* c, double* g_dev) {
   while (true) {
     const int t0 = (t1 - C > 0) ? (t1 - C) : 0;
     const int n = t1 - t0 + 1;
-    hipError_t e = ld::lde_energy(D, n, c->theta[0], c->d_isg, A + (size_t)t0 * DD, b + (size_t)t0 * D, c->d_m + (size_t)t0 * D,
-                                  c->d_S + (size_t)t0 * DD, c->d_et + t0, c->d_Ef + (size_t)t0 * D, nullptr,
-                                  c->d_dEm + (size_t)t0 * D, c->d_dEs_c, c->d_status, c->d_lde_ws, c->lde_nb, st, nullptr, c->stream2);
-    if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "large-D energy failed: %s", hipGetErrorString(e));
+    LAUNCH_TRY(c, "large-D energy", ld::lde_energy(D, n, c->theta[0], c->d_isg, A + (size_t)t0 * DD, b + (size_t)t0 * D, c->d_m + (size_t)t0 * D,
+                                                   c->d_S + (size_t)t0 * DD, c->d_et + t0, c->d_Ef + (size_t)t0 * D, nullptr,
+                                                   c->d_dEm + (size_t)t0 * D, c->d_dEs_c, c->d_status, c->d_lde_ws, c->lde_nb, st, nullptr, c->stream2));
     if (g_dev) {
       // Psi_{t1} sits in slot n-1: zero at the very end of the grid, else carried over from slot 0 of the previous chunk
       if (first) HIP_TRY(c, hipMemsetAsync(c->d_psi_c + (size_t)(n - 1) * DD, 0, sizeof(double) * DD, st));
       for (int t = t1; t > t0; t--) {
         const int k = t - t0;
         const int nobs = c->h_obs_idx[t - 1];
-        e = ld::ld_bwd_step(c->cfg.method, c->cfg.dt, D, A + (size_t)t * DD, A + (size_t)(t - 1) * DD,
-                            c->d_dEs_c + (size_t)k * DD, c->d_dEs_c + (size_t)(k - 1) * DD, c->d_dEm + (size_t)t * D,
-                            c->d_dEm + (size_t)(t - 1) * D, c->d_psi_c + (size_t)k * DD, c->d_lam + (size_t)t * D,
-                            c->d_psi_c + (size_t)(k - 1) * DD, c->d_lam + (size_t)(t - 1) * D,
-                            nobs >= 0 ? c->d_jsc : nullptr, nobs >= 0 ? c->d_jm + (size_t)nobs * D : nullptr, c->d_ld_ws, st);
-        if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "large-D backward step failed: %s", hipGetErrorString(e));
+        LAUNCH_TRY(c, "large-D backward step", ld::ld_bwd_step(c->cfg.method, c->cfg.dt, D, A + (size_t)t * DD, A + (size_t)(t - 1) * DD,
+                                                               c->d_dEs_c + (size_t)k * DD, c->d_dEs_c + (size_t)(k - 1) * DD, c->d_dEm + (size_t)t * D,
+                                                               c->d_dEm + (size_t)(t - 1) * D, c->d_psi_c + (size_t)k * DD, c->d_lam + (size_t)t * D,
+                                                               c->d_psi_c + (size_t)(k - 1) * DD, c->d_lam + (size_t)(t - 1) * D,
+                                                               nobs >= 0 ? c->d_jsc : nullptr, nobs >= 0 ? c->d_jm + (size_t)nobs * D : nullptr, c->d_ld_ws, st));
       }
       // gradient of (t0, t1] -- and of t0 itself once the grid start is reached
       const int g0 = (t0 == 0) ? 0 : t0 + 1;
       const int gn = t1 - g0 + 1;
       double* gA = g_dev + (size_t)g0 * DD;
       double* gB = g_dev + (size_t)Np * DD + (size_t)g0 * D;
-      e = ld::lde_grad(D, gn, c->cfg.dt, c->d_isg, A + (size_t)g0 * DD, b + (size_t)g0 * D, c->d_m + (size_t)g0 * D,
-                       c->d_S + (size_t)g0 * DD, c->d_lam + (size_t)g0 * D, c->d_psi_c + (size_t)(g0 - t0) * DD,
-                       c->d_Ef + (size_t)g0 * D, gA, gB, c->d_lde_ws, c->lde_nb, st, c->sigma_diag ? nullptr : c->d_isig);
-      if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "large-D gradient failed: %s", hipGetErrorString(e));
+      LAUNCH_TRY(c, "large-D gradient", ld::lde_grad(D, gn, c->cfg.dt, c->d_isg, A + (size_t)g0 * DD, b + (size_t)g0 * D, c->d_m + (size_t)g0 * D,
+                                                     c->d_S + (size_t)g0 * DD, c->d_lam + (size_t)g0 * D, c->d_psi_c + (size_t)(g0 - t0) * DD,
+                                                     c->d_Ef + (size_t)g0 * D, gA, gB, c->d_lde_ws, c->lde_nb, st, c->plan.sigma_diag ? nullptr : c->d_isig));
     }
     if (t0 == 0) break;
     if (g_dev) {   // Psi_{t0} becomes Psi_{t1} of the next chunk: slot 0 -> slot (t0 - t0_next)
@@ -641,17 +747,15 @@ static int enqueue_stream_sweep(vgpa_ctx* c, double* g_dev) {
   HIP_TRY(c, hipMemsetAsync(c->d_status, 0, sizeof(int32_t) * c->B, c->stream));
   c->s_packed = false;
   prof_mark(c, 0);
-  if ((rc = run_fwd(c, c->in.m0, c->in.S0, c->in.Sigma, c->sym_inputs))) return rc;
+  if ((rc = run_fwd(c, c->in.m0, c->in.S0, c->in.Sigma, c->plan.sym_inputs))) return rc;
   prof_mark(c, 1);
-  hipError_t e = launch_obs(obs_args(c), c->stream);
-  if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "obs launch failed: %s", hipGetErrorString(e));
+  LAUNCH_TRY(c, "obs launch", launch_obs(obs_args(c), c->stream));
   prof_mark(c, 2);
   if ((rc = stream_pass(c, g_dev))) return rc;
   prof_mark(c, 3);
   if ((rc = run_reduce(c))) return rc;
   c->have_state = true;
-  if (g_dev && c->prof) { prof_mark(c, 4); c->prof_pending = true; }
-  return VGPA_OK;
+  return g_dev ? prof_end(c, VGPA_OK) : VGPA_OK;
 }
 
 // DIAGNOSTIC (tools/power_per_kernel.sh): VGPA_DIAG_REPEAT="<fwd|energy|bwd|grad>:<n>" launches that phase of the fused sweep n times
@@ -669,21 +773,18 @@ static int diag_repeat(const char* phase) {
 static int run_lane_pass(vgpa_ctx* c, double* g_dev) {
   LaneSweepArgs q{};
   OdeArgs& a = q.o;
-  a.D = c->D; a.Np = c->Np; a.batch = c->B; a.dt = c->cfg.dt;
-  a.strideA = a.strideB = c->len_x;
-  a.A = ctx_A(c); a.b = ctx_b(c); a.m = c->d_m; a.S = c->d_S;
+  a = ode_args(c);
   a.msT = c->d_msT; a.bpad = c->bpad; a.jmT = c->d_jmT;
   sparse_jumps(c, a);
   q.model = c->cfg.model; q.want_grad = g_dev ? 1 : 0;
-  for (int i = 0; i < kMaxTheta; i++) q.theta[i] = c->theta[i];
+  copy_theta(c, q.theta);
   q.sigma1 = c->sigma1;
   for (int i = 0; i < c->D; i++) q.isg[i] = c->h_isig[(size_t)i * c->D + i];
   for (size_t e = 0; e < c->DD; e++) q.isig[e] = c->h_isig[e];
   q.e0 = c->cfg.e0; q.e0v = c->in.e0.rows; q.pre = c->single ? 0.5 : 1.0; q.div = c->single ? c->sigma1 : 1.0;
   q.theta_v = c->in.theta.rows; q.sigma1_v = c->in.sig1.rows; q.isig_v = c->in.isig.stride ? c->in.isig.rows : nullptr;
   q.eobs = c->d_eobs; q.esde = c->d_esde; q.f = c->d_f; q.g = g_dev;
-  hipError_t e = launch_sweep_lane(c->cfg.method, q, c->stream);
-  if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "fused lane pass launch failed: %s", hipGetErrorString(e));
+  LAUNCH_TRY(c, "fused lane pass launch", launch_sweep_lane(c->cfg.method, q, c->stream));
   return VGPA_OK;
 }
 
@@ -701,27 +802,23 @@ static int enqueue_lane_sweep(vgpa_ctx* c, double* g_dev) {
   {
     OdeArgs a = fwd_args(c, c->in.m0, c->in.S0, c->in.Sigma);
     a.msT = c->d_msT; a.bpad = c->bpad;
-    hipError_t ef = launch_ode_small(c->cfg.method, true, a, c->stream);
-    if (ef != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "forward lane kernel launch failed: %s", hipGetErrorString(ef));
+    LAUNCH_TRY(c, "forward lane kernel launch", launch_ode_small(c->cfg.method, true, a, c->stream));
   }
   c->ms_valid = false;
   prof_mark(c, 1);
-  hipError_t e = launch_obs_lane(obs_args(c), c->d_msT, c->bpad, c->d_jmT, c->stream);
-  if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "obs launch failed: %s", hipGetErrorString(e));
+  LAUNCH_TRY(c, "obs launch", launch_obs_lane(obs_args(c), c->d_msT, c->bpad, c->d_jmT, c->stream));
   prof_mark(c, 2);
   if ((rc = run_lane_pass(c, g_dev))) return rc;
   prof_mark(c, 3);
   c->have_state = true;
   c->derived_valid = false;
-  if (g_dev && c->prof) { prof_mark(c, 4); c->prof_pending = true; }
-  return VGPA_OK;
+  return g_dev ? prof_end(c, VGPA_OK) : VGPA_OK;
 }
 
 // what vgpa_fetch wants of the arrays the fused lane pass never wrote: the separate kernels over the cached (m, S)
 static int materialize_moments(vgpa_ctx* c) {
   if (c->ms_valid) return VGPA_OK;
-  hipError_t e = launch_ms_untranspose(c->D, c->Np, c->B, c->bpad, c->d_msT, c->d_m, c->d_S, c->stream);
-  if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "moment untranspose launch failed: %s", hipGetErrorString(e));
+  LAUNCH_TRY(c, "moment untranspose launch", launch_ms_untranspose(c->D, c->Np, c->B, c->bpad, c->d_msT, c->d_m, c->d_S, c->stream));
   c->ms_valid = true;
   return VGPA_OK;
 }
@@ -730,43 +827,12 @@ static int materialize_derived(vgpa_ctx* c) {
   if (c->derived_valid) return VGPA_OK;
   int rc;
   if ((rc = materialize_moments(c))) return rc;
-  {      // the separate backward kernel reads the jumps in the [B][M][D] layout: the observation kernel over the [B][Np] moments
-    hipError_t e = launch_obs(obs_args(c), c->stream);
-    if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "obs launch failed: %s", hipGetErrorString(e));
-  }
+  // the separate backward kernel reads the jumps in the [B][M][D] layout: the observation kernel over the [B][Np] moments
+  LAUNCH_TRY(c, "obs launch", launch_obs(obs_args(c), c->stream));
   if ((rc = run_energy(c, nullptr, false))) return rc;
-  if ((rc = run_bwd(c, false, c->sym_inputs))) return rc;
+  if ((rc = run_bwd(c, false, c->plan.sym_inputs))) return rc;
   c->derived_valid = true;
   return VGPA_OK;
-}
-
-// S_t as its packed lower triangle between the kernels of a fused sweep: exactly where the gradient assembly will be k_grad_mfma_q
-// (the condition of run_bwd's Q'' stream: fragment-cover kernels, 33 <= D <= 40, RK2 / RK4, Sigma = sigma^2 I, Lorenz-96) and the
-// energy terms come from k_energy_l96_r
-static bool s_packed_ok(vgpa_ctx* c) {
-  return c->sym_units && !use_lane(c) && !use_wave(c) && use_mfma(c, false, c->sym_inputs) && use_mfma(c, true, c->sym_inputs) &&
-         c->sigma_diag && c->isg_iso && c->cfg.model == VGPA_MODEL_L96 && !(c->cfg.flags & (VGPA_FLAG_KEEP_PSI | VGPA_FLAG_FORCE_GENERIC)) &&
-         sym_stores_q(c->cfg.method, c->D) && !c->hyp_on && c->D <= kMaxSmallD;
-}
-
-// the backward kernel assembles the gradient itself (OdeArgs::grad_on): wherever S_t is packed and the stepper's kernel can.  F-only
-// evaluations of such a context skip the backward recursion altogether (F does not depend on it); gradient(x, eval_fun=False) runs it.
-static bool grad_fused_ok(vgpa_ctx* c) {
-  return s_packed_ok(c) && sym_fuses_grad(c->cfg.method, c->D) && c->d_Am != nullptr;
-}
-// ... from kFusedGradMinBatch problems on (VGPA_FUSED_GRAD=1 in the environment: always).  The third wave set costs the recursion
-// ~0.4-0.5 ms per launch round (its matrix-core and vector-ALU instructions share the SIMDs' issue port with the product waves), the
-// separate assembly ~7 us per problem: below ~70 problems the backward kernel followed by k_grad_mfma_q is the shorter way.
-constexpr int kFusedGradMinBatch = 64;
-static bool grad_fused_now(vgpa_ctx* c) {
-  static const bool always = [] { const char* e = getenv("VGPA_FUSED_GRAD"); return e && e[0] == '1'; }();
-  return grad_fused_ok(c) && c->s_packed && (always || c->B >= kFusedGradMinBatch);
-}
-
-// dEsde_dS between the energy kernel and the backward cover kernel as packed lower triangles: wherever S_t is packed (the same two
-// kernels sit on either side)
-static bool ds_packed_ok(vgpa_ctx* c) {
-  return c->s_packed && c->d_jscp != nullptr;
 }
 
 // consumers that want S_t whole (vgpa_fetch, the operator-level kernels): the unpacked copy
@@ -776,8 +842,7 @@ static int unpack_S(vgpa_ctx* c, const double** full) {
   const size_t BN = (size_t)c->B * c->Np;
   int rc;
   if ((rc = ensure(c, &c->d_Sfull, BN * c->DD))) return rc;
-  hipError_t e = launch_unpack_lower(BN, c->D, c->d_S, c->d_Sfull, c->stream);
-  if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "unpack launch failed: %s", hipGetErrorString(e));
+  LAUNCH_TRY(c, "unpack launch", launch_unpack_lower(BN, c->D, c->d_S, c->d_Sfull, c->stream));
   *full = c->d_Sfull;
   return VGPA_OK;
 }
@@ -786,24 +851,20 @@ static int unpack_S(vgpa_ctx* c, const double** full) {
 static int enqueue_free_energy(vgpa_ctx* c) {
   if (c->stream_ld) return enqueue_stream_sweep(c, nullptr);
   if (!c->full) return fail(c, VGPA_ERR_STATE, "context was created without m0/s0/observations (ODE-only)");
-  if (lane_fused(c)) return enqueue_lane_sweep(c, nullptr);
+  if (c->plan.lane_pass) return enqueue_lane_sweep(c, nullptr);
   int rc;
   prof_collect(c);
-  c->s_packed = s_packed_ok(c);
+  c->s_packed = c->plan.packed;
   HIP_TRY(c, hipMemsetAsync(c->d_status, 0, sizeof(int32_t) * c->B, c->stream));
   prof_mark(c, 0);
   for (int r = diag_repeat("fwd"); r > 0; r--)
-    if ((rc = run_fwd(c, c->in.m0, c->in.S0, c->in.Sigma, c->sym_inputs))) return rc;
+    if ((rc = run_fwd(c, c->in.m0, c->in.S0, c->in.Sigma, c->plan.sym_inputs))) return rc;
   prof_mark(c, 1);
-  hipError_t e = launch_obs(obs_args(c), c->stream);
-  if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "obs launch failed: %s", hipGetErrorString(e));
-  // (a symmetric-unit backward kernel reads the upper triangle of dEsde_dS only: the energy kernel writes nothing else then)
-  const bool sym_bwd = use_sym_units(c) && !use_lane(c) && !use_wave(c) && use_mfma(c, false, c->sym_inputs) && c->D <= kMaxSmallD &&
-                       !(c->cfg.flags & VGPA_FLAG_KEEP_PSI);
+  LAUNCH_TRY(c, "obs launch", launch_obs(obs_args(c), c->stream));
   for (int r = diag_repeat("energy"); r > 0; r--)
-    if ((rc = run_energy(c, nullptr, sym_bwd, ds_packed_ok(c)))) return rc;
+    if ((rc = run_energy(c, nullptr, c->plan.bwd_upper, c->plan.packed))) return rc;
   prof_mark(c, 2);
-  if (grad_fused_ok(c)) {                  // F needs no backward recursion; the gradient's comes with its assembly (finish_gradient)
+  if (c->plan.grad_in_bwd) {               // F needs no backward recursion; the gradient's comes with its assembly (finish_gradient)
     if ((rc = run_reduce(c))) return rc;
     c->bwd_stored = false;
     c->psi_is_q = false;
@@ -812,7 +873,7 @@ static int enqueue_free_energy(vgpa_ctx* c) {
     return VGPA_OK;
   }
   for (int r = diag_repeat("bwd"); r > 0; r--)
-    if ((rc = run_bwd(c, false, c->sym_inputs))) return rc;
+    if ((rc = run_bwd(c, false, c->plan.sym_inputs))) return rc;
   prof_mark(c, 3);
   if ((rc = run_reduce(c))) return rc;
   c->have_state = true;
@@ -820,15 +881,20 @@ static int enqueue_free_energy(vgpa_ctx* c) {
   return VGPA_OK;
 }
 
-static int check_status(vgpa_ctx* c) {
-  std::vector<int32_t> st(c->B);
-  HIP_TRY(c, hipMemcpyAsync(st.data(), c->d_status, sizeof(int32_t) * c->B, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+// a sweep's status words, on the host: bit 0 of problem p's says that its S_t lost positive definiteness
+static int report_status(vgpa_ctx* c, const int32_t* st) {
   for (int p = 0; p < c->B; p++)
     if (st[p] & 1)
       return fail(c, VGPA_ERR_NOT_PD, "problem %d: marginal covariance S_t is not positive definite "
                   "(reference: LinAlgError from chol_inv, variational.py:380)", p);
   return VGPA_OK;
+}
+
+static int check_status(vgpa_ctx* c) {
+  std::vector<int32_t> st(c->B);
+  HIP_TRY(c, hipMemcpyAsync(st.data(), c->d_status, sizeof(int32_t) * c->B, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return report_status(c, st.data());
 }
 
 // =====================================================================================================
@@ -900,7 +966,8 @@ int vgpa_create(vgpa_ctx** out, const vgpa_config* cfg) {
 #define HTRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) FAIL(VGPA_ERR_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); } while (0)
   HTRY(hipSetDevice(cfg->device));
   HTRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-  pick_kernel_family(c);
+  if (hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, cfg->device) != hipSuccess || c->n_cu <= 0) c->n_cu = 256;
+  { const char* fam = getenv("VGPA_ODE_KERNEL"); c->keep_pe = fam && !strcmp(fam, "pe"); }
   // (phase events: no system-scope fence behind them -- nothing on the host reads device memory at a phase boundary; with the default
   //  flags five events cost a batched Ornstein-Uhlenbeck step 0.4 of its 1.4 ms)
   for (auto& e : c->ev) HTRY(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
@@ -963,55 +1030,10 @@ int vgpa_create(vgpa_ctx** out, const vgpa_config* cfg) {
   std::vector<double> Q(DD, 0.0), K(DD, 0.0), rinv(D, 0.0), jsc(DD, 0.0);
   if (c->M > 0 && cfg->obs_t && cfg->obs_y && cfg->obs_noise) {
     if (!index_obs_times(cfg->obs_t, c->M, c->Np, obs_idx.data())) FAIL(VGPA_ERR_ARG, "obs_t must be strictly increasing indices in [0, Np)");
-    if (single) {
-      const double r = cfg->obs_noise[0];
-      if (!(r > 0.0)) FAIL(VGPA_ERR_NOT_PD, "observation noise must be positive");
-      const double h = cfg->obs_h ? cfg->obs_h[0] : 1.0;
-      Q[0] = 1.0 / r; K[0] = h; rinv[0] = 1.0 / r; jsc[0] = 0.5 / r;
-      c->obs_const = 0.5 * c->M * (std::log(2.0 * M_PI) + std::log(r));
-    } else {
-      std::vector<double> Rinv(DD, 0.0), H(DD, 0.0), T(DD);
-      double logdet = 0.0;
-      // fast path: diagonal R and H = I (no O(D^3) host work at large D).  An explicitly passed identity counts as
-      // "no operator" (the reference's Likelihood materialises np.eye(d) when the operator is None, likelihood.py:33-40).
-      bool h_identity = true;
-      if (cfg->obs_h)
-        for (int i = 0; i < D && h_identity; i++)
-          for (int j = 0; j < D; j++)
-            if (cfg->obs_h[(size_t)i * D + j] != (i == j ? 1.0 : 0.0)) { h_identity = false; break; }
-      bool r_diag = h_identity;
-      for (int i = 0; i < D && r_diag; i++)
-        for (int j = 0; j < D; j++)
-          if (i != j && cfg->obs_noise[(size_t)i * D + j] != 0.0) { r_diag = false; break; }
-      if (r_diag) {
-        for (int i = 0; i < D; i++) {
-          const double rii = cfg->obs_noise[(size_t)i * D + i];
-          if (!(rii > 0.0)) FAIL(VGPA_ERR_NOT_PD, "observation noise matrix is not positive definite");
-          const double ci = 1.0 / std::sqrt(rii);
-          const double ri = ci * ci;
-          Q[(size_t)i * D + i] = ri; K[(size_t)i * D + i] = ri; jsc[(size_t)i * D + i] = 0.5 * ri; rinv[i] = ri;
-          logdet += std::log(std::sqrt(rii));
-        }
-        logdet *= 2.0;
-        c->obs_const = c->M * (D * std::log(2.0 * M_PI) + logdet);
-      } else if (!host_spd_inverse(D, cfg->obs_noise, Rinv.data(), &logdet)) {
-        FAIL(VGPA_ERR_NOT_PD, "observation noise matrix is not positive definite");
-      }
-      if (!r_diag) {
-      if (cfg->obs_h && !h_identity) H.assign(cfg->obs_h, cfg->obs_h + DD); else for (int i = 0; i < D; i++) H[(size_t)i * D + i] = 1.0;
-      host_matmul(D, H.data(), Rinv.data(), T.data(), false, false);      // H R^-1
-      host_matmul(D, T.data(), H.data(), Q.data(), false, true);          // H R^-1 H^T
-      host_matmul(D, H.data(), Rinv.data(), T.data(), true, false);       // H^T R^-1
-      host_matmul(D, T.data(), H.data(), K.data(), false, true);          // H^T R^-1 H^T
-      host_matmul(D, T.data(), H.data(), jsc.data(), false, false);       // H^T R^-1 H
-      for (auto& v : jsc) v *= 0.5;
-      for (int i = 0; i < D; i++) rinv[i] = Rinv[(size_t)i * D + i];
-      c->obs_const = c->M * (D * std::log(2.0 * M_PI) + logdet);
-      }
-      c->inputs_sym = c->inputs_sym && is_symmetric(jsc.data(), D);
-      c->obs_diag = r_diag;
-      if (D > kMaxSmallD) TRY(dev_alloc(c, &c->d_obs_part, (size_t)c->B * c->M));   // one workgroup per observation
-    }
+    rc = obs_constants(D, c->M, single, cfg->obs_noise, cfg->obs_h, Q.data(), K.data(), rinv.data(), jsc.data(), &c->obs_const, &c->obs_diag);
+    if (rc) FAIL(rc, single ? "observation noise must be positive" : "observation noise matrix is not positive definite");
+    c->inputs_sym = c->inputs_sym && is_symmetric(jsc.data(), D);
+    if (D > kMaxSmallD) TRY(dev_alloc(c, &c->d_obs_part, (size_t)c->B * c->M));   // one workgroup per observation
     TRY(upload(c, c->d_obs_t, cfg->obs_t, (size_t)c->M));
     TRY(upload(c, c->d_obs_y, cfg->obs_y, (size_t)c->M * D));
   }
@@ -1046,7 +1068,7 @@ int vgpa_create(vgpa_ctx** out, const vgpa_config* cfg) {
   BatchInputs& in = c->in;       // every problem on the inputs of vgpa_config
   in.m0 = {c->d_m0, 0}; in.S0 = {c->d_S0, 0}; in.obs_y = {c->d_obs_y, 0}; in.obs_t = {c->d_obs_t, 0}; in.obs_idx = {c->d_obs_idx, 0};
   in.Sigma = {c->d_Sigma, 0}; in.isig = {c->d_isig, 0}; in.isg = {c->d_isg, 0};
-  kernel_family(c);
+  make_plan(c);
 #undef FAIL
 #undef TRY
 #undef HTRY
@@ -1089,10 +1111,8 @@ int vgpa_solve_bwd(vgpa_ctx* c, const double* lin_a, const double* desde_dm, con
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   const size_t BN = (size_t)c->B * c->Np;
   int rc;
-  if (!c->d_jm_dense) {
-    if ((rc = dev_alloc(c, &c->d_jm_dense, BN * c->D))) return rc;
-    if ((rc = dev_alloc(c, &c->d_js_dense, BN * c->DD))) return rc;
-  }
+  if ((rc = ensure(c, &c->d_jm_dense, BN * c->D))) return rc;
+  if ((rc = ensure(c, &c->d_js_dense, BN * c->DD))) return rc;
   if ((rc = ingest_ab(c, lin_a, nullptr))) return rc;
   if ((rc = upload(c, c->d_dEm, desde_dm, BN * c->D))) return rc;
   if ((rc = ensure(c, &c->d_dEs, BN * c->DD))) return rc;
@@ -1125,7 +1145,7 @@ int vgpa_energy_full(vgpa_ctx* c, const double* lin_a, const double* off_b, cons
   const int H = c->single ? 1 : 2 * D;
   const size_t BN = (size_t)c->B * c->Np;
   int rc;
-  if (edf && !c->d_Edf && (rc = dev_alloc(c, &c->d_Edf, BN * c->DD))) return rc;
+  if (edf && (rc = ensure(c, &c->d_Edf, BN * c->DD))) return rc;
   if (hyper && !c->d_hyp) {
     if ((rc = dev_alloc(c, &c->d_hyp, BN * H))) return rc;
     if ((rc = dev_alloc(c, &c->d_hypT, (size_t)c->B * H))) return rc;
@@ -1142,8 +1162,7 @@ int vgpa_energy_full(vgpa_ctx* c, const double* lin_a, const double* off_b, cons
   if (rc) return rc;
   if ((rc = run_reduce(c))) return rc;
   if (hyper) {
-    hipError_t e = launch_trapz_multi(c->d_hyp, c->Np, H, c->B, c->cfg.dt, c->d_hypT, c->stream);
-    if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "trapezoid launch failed: %s", hipGetErrorString(e));
+    LAUNCH_TRY(c, "trapezoid launch", launch_trapz_multi(c->d_hyp, c->Np, H, c->B, c->cfg.dt, c->d_hypT, c->stream));
   }
   if ((rc = check_status(c))) return rc;
   std::vector<double> T(hyper ? (size_t)c->B * H : 0), esde(c->B);
@@ -1194,18 +1213,14 @@ int vgpa_obs_energy(vgpa_ctx* c, const double* mt, const double* st, double* eob
   if ((rc = upload(c, c->d_m, mt, BN * c->D))) return rc;
   if ((rc = upload(c, c->d_S, st, BN * c->DD))) return rc;
   ObsArgs a = obs_args(c);
-  hipError_t e = launch_obs(a, c->stream);
-  if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "obs launch failed: %s", hipGetErrorString(e));
+  LAUNCH_TRY(c, "obs launch", launch_obs(a, c->stream));
   if (eobs && (rc = download(c, eobs, c->d_eobs, (size_t)c->B))) return rc;
   if (deobs_dm || deobs_ds) {
-    if (!c->d_jm_dense) {
-      if ((rc = dev_alloc(c, &c->d_jm_dense, BN * c->D))) return rc;
-      if ((rc = dev_alloc(c, &c->d_js_dense, BN * c->DD))) return rc;
-    }
+    if ((rc = ensure(c, &c->d_jm_dense, BN * c->D))) return rc;
+    if ((rc = ensure(c, &c->d_js_dense, BN * c->DD))) return rc;
     HIP_TRY(c, hipMemsetAsync(c->d_jm_dense, 0, sizeof(double) * BN * c->D, c->stream));
     HIP_TRY(c, hipMemsetAsync(c->d_js_dense, 0, sizeof(double) * BN * c->DD, c->stream));
-    e = launch_obs_dense(a, c->d_jsc, c->d_jm_dense, c->d_js_dense, c->stream);
-    if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "obs dense launch failed: %s", hipGetErrorString(e));
+    LAUNCH_TRY(c, "obs dense launch", launch_obs_dense(a, c->d_jsc, c->d_jm_dense, c->d_js_dense, c->stream));
     if (deobs_dm && (rc = download(c, deobs_dm, c->d_jm_dense, BN * c->D))) return rc;
     if (deobs_ds && (rc = download(c, deobs_ds, c->d_js_dense, BN * c->DD))) return rc;
   }
@@ -1214,23 +1229,16 @@ int vgpa_obs_energy(vgpa_ctx* c, const double* mt, const double* st, double* eob
 }
 
 // ---- fused objective --------------------------------------------------------------------------------
-int vgpa_free_energy(vgpa_ctx* c, const double* x, double* f) {
-  if (!c || !x || !f) return fail(c, VGPA_ERR_ARG, "null argument");
+static int free_energy(vgpa_ctx* c, const double* x, bool on_device, double* f_host) {
+  if (!c || !x || !f_host) return fail(c, VGPA_ERR_ARG, "null argument");
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   int rc;
-  if ((rc = ingest_x(c, x, false))) return rc;
-  if ((rc = enqueue_free_energy(c))) return rc;
-  return vgpa_fetch_f(c, f);
-}
-
-int vgpa_free_energy_dev(vgpa_ctx* c, const double* x_dev, double* f_host) {
-  if (!c || !x_dev || !f_host) return fail(c, VGPA_ERR_ARG, "null argument");
-  HIP_TRY(c, hipSetDevice(c->cfg.device));
-  int rc;
-  if ((rc = ingest_x(c, x_dev, true))) return rc;
+  if ((rc = ingest_x(c, x, on_device))) return rc;
   if ((rc = enqueue_free_energy(c))) return rc;
   return vgpa_fetch_f(c, f_host);
 }
+int vgpa_free_energy(vgpa_ctx* c, const double* x, double* f) { return free_energy(c, x, false, f); }
+int vgpa_free_energy_dev(vgpa_ctx* c, const double* x_dev, double* f_host) { return free_energy(c, x_dev, true, f_host); }
 
 int vgpa_fetch_f(vgpa_ctx* c, double* f_host) {
   if (!c || !f_host) return fail(c, VGPA_ERR_ARG, "null argument");
@@ -1251,11 +1259,7 @@ int vgpa_fetch_f(vgpa_ctx* c, double* f_host) {
   HIP_TRY(c, hipMemcpyAsync(hs, c->d_status, B * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   std::memcpy(f_host, hf, B * sizeof(double));
-  for (size_t p = 0; p < B; p++)
-    if (hs[p] & 1)
-      return fail(c, VGPA_ERR_NOT_PD, "problem %d: marginal covariance S_t is not positive definite "
-                  "(reference: LinAlgError from chol_inv, variational.py:380)", (int)p);
-  return VGPA_OK;
+  return report_status(c, hs);
 }
 
 static int finish_gradient(vgpa_ctx* c, double* g_dev);
@@ -1263,36 +1267,28 @@ static int finish_gradient(vgpa_ctx* c, double* g_dev);
 // F and the gradient in one go (df(x, eval_fun=True)): the streamed context folds both into one chunked pass
 static int enqueue_sweep(vgpa_ctx* c, double* g_dev) {
   if (c->stream_ld) return enqueue_stream_sweep(c, g_dev);
-  if (c->full && lane_fused(c)) return enqueue_lane_sweep(c, g_dev);
+  if (c->plan.lane_pass) return enqueue_lane_sweep(c, g_dev);
   int rc = enqueue_free_energy(c);
   return rc ? rc : finish_gradient(c, g_dev);
 }
 
 static int finish_gradient(vgpa_ctx* c, double* g_dev) {
-  if (c->stream_ld) {            // cached state = (m, S): the chunked pass recomputes the energy terms on its way back
-    int rc = stream_pass(c, g_dev);
-    if (rc == VGPA_OK && c->prof) { prof_mark(c, 4); c->prof_pending = true; }
-    return rc;
-  }
-  if (lane_fused(c) && !c->derived_valid) {      // gradient(x, eval_fun=False) behind a fused F: the pass again, now with the recursion
-    int rc = run_lane_pass(c, g_dev);
-    if (rc == VGPA_OK && c->prof) { prof_mark(c, 4); c->prof_pending = true; }
-    return rc;
-  }
+  // cached state = (m, S): the chunked pass recomputes the energy terms on its way back
+  if (c->stream_ld) return prof_end(c, stream_pass(c, g_dev));
+  // gradient(x, eval_fun=False) behind a fused F: the pass again, now with the recursion
+  if (c->plan.lane_pass && !c->derived_valid) return prof_end(c, run_lane_pass(c, g_dev));
   int rc = VGPA_OK;
-  if (grad_fused_now(c)) {                 // backward recursion + gradient assembly in one kernel (phase "bwd"; "grad" is empty)
-    for (int r = diag_repeat("bwd"); r > 0 && rc == VGPA_OK; r--) rc = run_bwd(c, false, c->sym_inputs, g_dev);
+  if (c->plan.grad_in_bwd_now && c->s_packed) {   // backward recursion + gradient assembly in one kernel (phase "bwd"; "grad" is empty)
+    for (int r = diag_repeat("bwd"); r > 0 && rc == VGPA_OK; r--) rc = run_bwd(c, false, c->plan.sym_inputs, g_dev);
     prof_mark(c, 3);
-    if (rc == VGPA_OK && c->prof) { prof_mark(c, 4); c->prof_pending = true; }
-    return rc;
+    return prof_end(c, rc);
   }
   if (!c->bwd_stored) {                    // (F-only evaluation before: the recursion now, with Q''_t for the assembly kernel)
-    for (int r = diag_repeat("bwd"); r > 0 && rc == VGPA_OK; r--) rc = run_bwd(c, false, c->sym_inputs);
+    for (int r = diag_repeat("bwd"); r > 0 && rc == VGPA_OK; r--) rc = run_bwd(c, false, c->plan.sym_inputs);
     prof_mark(c, 3);
   }
   for (int r = diag_repeat("grad"); r > 0 && rc == VGPA_OK; r--) rc = run_grad(c, g_dev);
-  if (rc == VGPA_OK && c->prof) { prof_mark(c, 4); c->prof_pending = true; }
-  return rc;
+  return prof_end(c, rc);
 }
 
 int vgpa_gradient(vgpa_ctx* c, const double* x_or_null, double* g) {
@@ -1356,7 +1352,7 @@ int vgpa_fetch(vgpa_ctx* c, int which, double* out) {
   int rc = VGPA_OK;
   if ((rc = materialize_moments(c))) return rc;
   if (which != VGPA_FETCH_MT && which != VGPA_FETCH_ST && which != VGPA_FETCH_EDF && (rc = materialize_derived(c))) return rc;
-  if ((which == VGPA_FETCH_LAMT || which == VGPA_FETCH_PSIT) && !c->bwd_stored && !c->stream_ld && (rc = run_bwd(c, false, c->sym_inputs))) return rc;
+  if ((which == VGPA_FETCH_LAMT || which == VGPA_FETCH_PSIT) && !c->bwd_stored && !c->stream_ld && (rc = run_bwd(c, false, c->plan.sym_inputs))) return rc;
   switch (which) {
     case VGPA_FETCH_MT: rc = download(c, out, c->d_m, BN * c->D); break;
     case VGPA_FETCH_ST: {
@@ -1369,8 +1365,7 @@ int vgpa_fetch(vgpa_ctx* c, int which, double* out) {
     case VGPA_FETCH_PSIT:
       if (!c->d_psi || c->stream_ld) return fail(c, VGPA_ERR_UNSUPPORTED, "Psi_t is not kept by the time-chunked large-D sweep");
       if (c->psi_is_q) {               // recover Psi_t = (Sigma^-1 A_t - Q''_t) / 2 in place: from here on d_psi holds Psi_t again
-        hipError_t e = launch_psi_from_q(c->B, c->Np, c->D, c->len_x, ctx_A(c), c->in.isg.rows, c->in.isg.stride, c->d_psi, c->stream);
-        if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "Psi_t recovery launch failed: %s", hipGetErrorString(e));
+        LAUNCH_TRY(c, "Psi_t recovery launch", launch_psi_from_q(c->B, c->Np, c->D, c->len_x, ctx_A(c), c->in.isg.rows, c->in.isg.stride, c->d_psi, c->stream));
         c->psi_is_q = false;
       }
       rc = download(c, out, c->d_psi, BN * c->DD); break;
@@ -1380,23 +1375,20 @@ int vgpa_fetch(vgpa_ctx* c, int which, double* out) {
       if (!c->d_dEs || c->stream_ld) return fail(c, VGPA_ERR_UNSUPPORTED, "dEsde_dS is not kept by the time-chunked large-D sweep");
       if (c->des_packed) {             // whole matrices into the scratch copy the unpacked S_t uses too (the packed stream stays as it is)
         if ((rc = ensure(c, &c->d_Sfull, BN * c->DD))) return rc;
-        hipError_t e = launch_unpack_lower(BN, c->D, c->d_dEs, c->d_Sfull, c->stream);
-        if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "unpack launch failed: %s", hipGetErrorString(e));
+        LAUNCH_TRY(c, "unpack launch", launch_unpack_lower(BN, c->D, c->d_dEs, c->d_Sfull, c->stream));
         rc = download(c, out, c->d_Sfull, BN * c->DD);
         break;
       }
       if (c->des_upper) {
-        hipError_t e = launch_mirror_upper(BN, c->D, c->d_dEs, c->stream);
-        if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "mirror launch failed: %s", hipGetErrorString(e));
+        LAUNCH_TRY(c, "mirror launch", launch_mirror_upper(BN, c->D, c->d_dEs, c->stream));
         c->des_upper = false;
       }
       rc = download(c, out, c->d_dEs, BN * c->DD); break;
     case VGPA_FETCH_ESDE_T: rc = download(c, out, c->d_et, BN); break;
     case VGPA_FETCH_EDF: {
-      if (!c->d_Edf && (rc = dev_alloc(c, &c->d_Edf, BN * c->DD))) return rc;
+      if ((rc = ensure(c, &c->d_Edf, BN * c->DD))) return rc;
       EnergyArgs a = energy_args(c, c->d_Edf);
-      hipError_t e = launch_edf(a, c->stream);
-      if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "edf launch failed: %s", hipGetErrorString(e));
+      LAUNCH_TRY(c, "edf launch", launch_edf(a, c->stream));
       rc = download(c, out, c->d_Edf, BN * c->DD);
       break;
     }
@@ -1436,8 +1428,7 @@ static int vec_reduce_host(vgpa_ctx* c, int mode, const double* a, const double*
   int rc;
   if ((rc = vec_scratch(c, seglen))) return rc;
   double* red = c->d_vec_scratch + 2 * (size_t)c->B;    // [0,2B) holds the axpby coefficients
-  hipError_t e = vec_reduce(mode, a, b, c->B, (long long)seglen, red, c->stream);
-  if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "vector reduction failed: %s", hipGetErrorString(e));
+  LAUNCH_TRY(c, "vector reduction", vec_reduce(mode, a, b, c->B, (long long)seglen, red, c->stream));
   HIP_TRY(c, hipMemcpyAsync(out, red, sizeof(double) * c->B, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return VGPA_OK;
@@ -1469,8 +1460,7 @@ int vgpa_vec_axpby(vgpa_ctx* c, uint64_t seglen, const double* alpha, const doub
   if (beta) std::memcpy(h + B, beta, sizeof(double) * B);
   HIP_TRY(c, hipMemcpyAsync(c->d_vec_scratch, h, sizeof(double) * (beta ? 2 * B : B), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipEventRecord(c->ev_coef[slot], c->stream));
-  hipError_t e = vec_axpby(c->B, (long long)seglen, c->d_vec_scratch, x, c->d_vec_scratch + c->B, y, out, c->stream);
-  if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "axpby failed: %s", hipGetErrorString(e));
+  LAUNCH_TRY(c, "axpby", vec_axpby(c->B, (long long)seglen, c->d_vec_scratch, x, c->d_vec_scratch + c->B, y, out, c->stream));
   return VGPA_OK;
 }
 
@@ -1530,7 +1520,7 @@ int vgpa_set_problem_data(vgpa_ctx* c, const int64_t* obs_t, const double* obs_y
   }
   HIP_TRY(c, hipStreamSynchronize(c->stream));          // (idx lives on this stack frame)
   c->s0_rows_sym = !s0 || stack_symmetric(s0, (size_t)B, D);       // (a non-symmetric s0 row: both products literally)
-  kernel_family(c);
+  make_plan(c);
   c->pt_dense_zeroed = false;
   c->have_state = false;            // (like vgpa_release_x: the cached state belongs to the old inputs)
   return VGPA_OK;
@@ -1585,7 +1575,7 @@ int vgpa_set_problem_params(vgpa_ctx* c, const double* theta, const double* sigm
     HIP_TRY(c, hipStreamSynchronize(c->stream));          // (the host rows live on this stack frame)
   }
   c->rows_form = rows;
-  kernel_family(c);
+  make_plan(c);
   return VGPA_OK;
 }
 
