@@ -143,7 +143,8 @@ typedef struct {
  *     formed literally; the fused sweep and the row-sharded drivers assume the symmetric S0 / Sigma every real run has);
  *   - VGPA_FETCH_PSIT / VGPA_FETCH_DESDE_DS in the time-chunked large-D sweep (they are never resident there);
  *   - per-problem parameters (vgpa_set_problem_params): a per-problem Sigma at D > 64 (per-problem theta is built there), and
- *     any per-problem theta or Sigma in the time-chunked large-D sweep and the row-sharded drivers.
+ *     any per-problem theta or Sigma in the time-chunked large-D sweep and the row-sharded drivers;
+ *   - vgpa_theta_gradient in the time-chunked large-D sweep (and the row-sharded drivers have no such entry point).
  * The matrix-core stepping kernels cover D <= 64 with symmetric inputs; non-symmetric operator-level inputs run on the
  * generic LDS kernels (same results, ~15x slower at D = 40). */
 
@@ -178,6 +179,17 @@ int vgpa_gradient(vgpa_ctx* ctx, const double* x_or_null, double* g);  /* NULL: 
 int vgpa_sweep(vgpa_ctx* ctx, const double* x, double* f, double* g);  /* df(x, eval_fun=True) */
 int vgpa_energy_parts(vgpa_ctx* ctx, double* e0, double* esde, double* eobs); /* each [batch] */
 int vgpa_fetch(vgpa_ctx* ctx, int which, double* out);
+/* dF/dtheta at fixed (A_t, b_t), from the state the last fused evaluation (free_energy, sweep, sweep_enqueue + fetch_f)
+ * left resident.  out: [batch][n_theta], host.  Per-problem theta / Sigma / data in force are honoured.  The cached state
+ * survives: vgpa_gradient(NULL), vgpa_gradient_dev, vgpa_fetch and vgpa_energy_parts return afterwards what they return
+ * without this call.  (m_t, S_t, E0 and E_obs do not depend on theta, so this is the integral of
+ * sum_i (Sigma^-1)_ii <(f - g)_i df_i/dtheta>.  OU, double well, Lorenz-63: equal to the reference's dEsde_dth.  Lorenz-96: the
+ * unscented mean of the residual, with the flat roll of the energy -- the derivative of the F this library computes, which the
+ * reference's dEsde_dth, built from the closed-form mean drift, is not.)  F is exactly quadratic in theta with a diagonal
+ * Hessian at fixed (A_t, b_t): h = g(theta + 1) - g(theta) is the curvature, theta - g / h the minimiser.
+ * VGPA_ERR_STATE: no cached state (also after vgpa_release_x, vgpa_set_problem_data, vgpa_set_problem_params), ODE-only
+ * contexts; VGPA_ERR_UNSUPPORTED: the time-chunked large-D sweep. */
+int vgpa_theta_gradient(vgpa_ctx* ctx, double* out);
 
 /* device-pointer variants (x, g on the context's device; f written to HOST after a sync) ------ */
 int vgpa_sweep_dev(vgpa_ctx* ctx, const double* x_dev, double* f_host, double* g_dev);

@@ -9,9 +9,14 @@ round by round; each round times `--steps` sweeps of one mode with the context's
 vgpa_profile_begin / _end), and the median per round is reported.
 
     python tools/bench_problem_batch.py [--rounds 5] [--steps 10]
+    python tools/bench_problem_batch.py --mode theta [--rounds 5] [--steps 10]
 
   l96   Lorenz-96, D = 40, RK4, Np = 1001, B = 512     (bench.py's headline configuration)
   l63   Lorenz-63, D = 3, RK4, Np = 1001, B = 65536    (bench.py's config2 block: the lane-per-problem kernels)
+
+--mode theta: the time of Context.theta_gradient() behind a free_energy, beside the time of that free_energy, on the same contexts
+(and on one more: l96_ld, Lorenz-96, D = 1024, RK4, Np = 33, B = 1).  Both are timed with a pair of device events on the context's
+stream around the call (each call ends with its own synchronisation: F, resp. the B n_theta results, come back to the host).
 """
 import argparse
 import json
@@ -31,7 +36,7 @@ def datasets(name, d, n_pts, dt, nset, seed0):
     return [build_problem(name, "RK4", (n_pts - 1) * dt, dt, d, seed=seed0 + j) for j in range(nset)]
 
 
-def make_contexts(name, d, n_pts, dt, B, nset=4):
+def make_contexts(name, d, n_pts, dt, B, nset=4, modes=("shared", "data", "data_t", "params")):
     import vgpa_amd as va
     from helpers import SEED
     ps = datasets(name, d, n_pts, dt, nset, SEED)
@@ -51,7 +56,7 @@ def make_contexts(name, d, n_pts, dt, B, nset=4):
     th = np.atleast_1d(np.asarray(theta, dtype=float))[None, :] * (1.0 + 0.05 * (k % 5))[:, None]
     sig = np.asarray(p0["model"].sigma, dtype=float)[None] * (1.0 + 0.1 * (k % 4))[:, None, None]      # sigma_p^2 I
     ctxs = {}
-    for mode in ("shared", "data", "data_t", "params"):
+    for mode in modes:
         c = va.Context(name, "RK4", d, n_pts, dt, **kw)
         if mode in ("data", "data_t"):
             c.set_problem_data(obs_t=obs_t if mode == "data_t" else None, obs_y=obs_y, m0=m0, s0=s0, e0=e0s)
@@ -100,12 +105,85 @@ def run(name, d, n_pts, dt, B, rounds, steps):
             "rounds_ms": {m: [round(x, 4) for x in v] for m, v in ms.items()}}
 
 
+class StreamTimer(object):
+    """Device time of what a call enqueues on a context's stream: two HIP events around it (the runtime the library brought in)."""
+
+    def __init__(self, ctx):
+        import ctypes
+        hip = ctypes.CDLL(None)
+        if not hasattr(hip, "hipEventCreate"):
+            hip = ctypes.CDLL("libamdhip64.so")
+        self.hip, self.ct = hip, ctypes
+        self.stream = ctypes.c_void_p(ctx._lib.vgpa_stream(ctx._h))
+        self.ev = [ctypes.c_void_p(), ctypes.c_void_p()]
+        for e in self.ev:
+            assert hip.hipEventCreate(ctypes.byref(e)) == 0
+        hip.hipEventRecord.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        hip.hipEventSynchronize.argtypes = [ctypes.c_void_p]
+        hip.hipEventElapsedTime.argtypes = [ctypes.POINTER(ctypes.c_float), ctypes.c_void_p, ctypes.c_void_p]
+        hip.hipEventDestroy.argtypes = [ctypes.c_void_p]
+
+    def ms(self, call):
+        assert self.hip.hipEventRecord(self.ev[0], self.stream) == 0
+        call()
+        assert self.hip.hipEventRecord(self.ev[1], self.stream) == 0
+        assert self.hip.hipEventSynchronize(self.ev[1]) == 0
+        out = self.ct.c_float()
+        assert self.hip.hipEventElapsedTime(self.ct.byref(out), self.ev[0], self.ev[1]) == 0
+        return float(out.value)
+
+    def close(self):
+        for e in self.ev:
+            self.hip.hipEventDestroy(e)
+
+
+def run_theta(name, d, n_pts, dt, B, rounds, steps, modes=("shared", "data", "data_t", "params"), nset=4):
+    ctxs, x0 = make_contexts(name, d, n_pts, dt, B, nset=nset, modes=modes)
+    len_x = x0.shape[1]
+    rng = np.random.default_rng(1)
+    rows = x0[np.arange(min(64, B)) % x0.shape[0]] + 0.05 * rng.standard_normal((min(64, B), len_x))
+    bufs, timers = {}, {}
+    for mode, c in ctxs.items():
+        xb = c.alloc(B * len_x)
+        for i0 in range(0, B, 64):
+            xb.upload_at(i0 * len_x, rows[:min(64, B - i0)])
+        bufs[mode], timers[mode] = xb, StreamTimer(c)
+        for _ in range(2):                       # warm-up (first-use allocations)
+            c.free_energy_dev(xb)
+            g = c.theta_gradient()
+        assert np.all(np.isfinite(g))
+    ms = {mode: {"free_energy": [], "theta_gradient": []} for mode in ctxs}
+    for _ in range(rounds):
+        for mode, c in ctxs.items():
+            xb, tm = bufs[mode], timers[mode]
+            tf = [tm.ms(lambda: c.free_energy_dev(xb)) for _ in range(steps)]
+            tg = [tm.ms(c.theta_gradient) for _ in range(steps)]
+            ms[mode]["free_energy"].append(float(np.median(tf)))
+            ms[mode]["theta_gradient"].append(float(np.median(tg)))
+    for mode, c in ctxs.items():
+        timers[mode].close()
+        c.close()
+    out = {"B": B, "D": d, "Np": n_pts}
+    for mode, v in ms.items():
+        out[mode] = {k: round(float(np.median(t)), 4) for k, t in v.items()}
+        out[mode]["rounds_ms"] = {k: [round(x, 4) for x in t] for k, t in v.items()}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--mode", choices=("sweep", "theta"), default="sweep")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--l63-batch", type=int, default=65536)
     args = ap.parse_args()
+    if args.mode == "theta":
+        out = {"tool": "bench_problem_batch", "mode": "theta", "unit": "ms per call (device events)",
+               "l96": run_theta("L96", 40, 1001, 0.01, 512, args.rounds, args.steps),
+               "l63": run_theta("L63", 3, 1001, 0.01, args.l63_batch, args.rounds, args.steps),
+               "l96_ld": run_theta("L96", 1024, 33, 0.01, 1, args.rounds, args.steps, modes=("shared",), nset=1)}
+        print(json.dumps(out), flush=True)
+        return
     out = {"tool": "bench_problem_batch",
            "l96": run("L96", 40, 1001, 0.01, 512, args.rounds, args.steps),
            "l63": run("L63", 3, 1001, 0.01, args.l63_batch, args.rounds, args.steps)}

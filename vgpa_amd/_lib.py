@@ -30,7 +30,7 @@ OPT_LD_CHUNK = 1
 SYMBOLS = ["vgpa_create", "vgpa_destroy", "vgpa_last_error", "vgpa_abi_version", "vgpa_device_count",
            "vgpa_synchronize", "vgpa_stream", "vgpa_solve_fwd", "vgpa_solve_bwd", "vgpa_energy",
            "vgpa_obs_energy", "vgpa_free_energy", "vgpa_gradient", "vgpa_sweep", "vgpa_energy_parts",
-           "vgpa_fetch", "vgpa_sweep_dev", "vgpa_free_energy_dev", "vgpa_sweep_enqueue", "vgpa_fetch_f",
+           "vgpa_fetch", "vgpa_theta_gradient", "vgpa_sweep_dev", "vgpa_free_energy_dev", "vgpa_sweep_enqueue", "vgpa_fetch_f",
            "vgpa_dev_alloc", "vgpa_dev_free", "vgpa_memcpy_h2d", "vgpa_memcpy_d2h",
            "vgpa_profile_begin", "vgpa_profile_end", "vgpa_ld_gemm", "vgpa_ld_stage", "vgpa_gradient_dev", "vgpa_energy_full", "vgpa_set_option", "vgpa_is_streaming", "vgpa_set_prior_energy",
            "vgpa_set_problem_data", "vgpa_set_problem_params",
@@ -117,6 +117,7 @@ def load():
     lib.vgpa_sweep.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vgpa_energy_parts.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vgpa_fetch.argtypes = [c_void_p, c_int, c_void_p]
+    lib.vgpa_theta_gradient.argtypes = [c_void_p, c_void_p]
     lib.vgpa_sweep_dev.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vgpa_free_energy_dev.argtypes = [c_void_p, c_void_p, c_void_p]
     lib.vgpa_sweep_enqueue.argtypes = [c_void_p, c_void_p, c_void_p]
@@ -515,6 +516,14 @@ class Context:
         if self.B == 1:
             return float(e0[0]), float(es[0]), float(eo[0])
         return e0, es, eo
+
+    def theta_gradient(self):
+        """dF/dtheta at fixed (A_t, b_t) from the state the last fused evaluation left resident: (n_theta,) at B = 1, else
+        (B, n_theta).  The cached state survives (gradient(None), fetch, energy_parts afterwards are unchanged).  RuntimeError
+        without a cached state, NotImplementedError in the time-chunked large-D sweep."""
+        out = np.empty((self.B, max(self.n_theta, 1)))
+        self._check(self._lib.vgpa_theta_gradient(self._h, _ptr(out)))
+        return out[0] if self.B == 1 else out
 
     def fetch(self, key):
         which = FETCH_IDS[key]

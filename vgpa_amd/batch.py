@@ -17,7 +17,23 @@ import numpy as np
 
 from ._lib import Context
 
-__all__ = ["ProblemBatch"]
+__all__ = ["ProblemBatch", "theta_mstep"]
+
+
+def theta_mstep(theta, g0, g1, pooled=False):
+    """
+    The exact M-step in theta at fixed (A_t, b_t).  F is quadratic in theta there with a diagonal Hessian, so with g0 = dF/dtheta at
+    theta and g1 = dF/dtheta at theta + 1 (every component raised by one) the curvature is h = g1 - g0 and the minimiser
+    theta - g0 / h, component-wise.  theta, g0, g1: (B, n_theta).  pooled=True: the B problems share one theta (many datasets of
+    one system), the objective is the sum of their F, and every row moves by sum_p g0 / sum_p h.  Returns (B, n_theta).
+    """
+    theta, g0, g1 = (np.atleast_2d(np.asarray(v, dtype=float)) for v in (theta, g0, g1))
+    h = g1 - g0
+    if pooled:
+        step = np.broadcast_to(g0.sum(axis=0) / h.sum(axis=0), theta.shape)
+    else:
+        step = g0 / h
+    return theta - step
 
 
 def _same(a, b):
@@ -130,6 +146,57 @@ class ProblemBatch(object):
         """(F (B,), gradient (B, len_x)) in one call."""
         f, g = self._context().sweep(self._stack(x))
         return np.atleast_1d(np.asarray(f, dtype=float)), np.asarray(g).reshape(self.B, self.len_x)
+
+    def theta_gradient(self, x=None):
+        """(B, n_theta) dF/dtheta at fixed (A_t, b_t); x=None: from the state of the last free_energy, else F is evaluated at x
+        first.  Every member's own theta / Sigma / data are honoured."""
+        if x is not None:
+            self.free_energy(x)
+        return np.asarray(self._context().theta_gradient(), dtype=float).reshape(self.B, -1)
+
+    def _theta_rows(self):
+        return np.stack([np.atleast_1d(np.asarray(v.model.theta, dtype=float)) for v in self.vgps])
+
+    def fit_theta(self, x0, rounds, options=None):
+        """
+        Variational EM for the drift parameters.  Per round: (1) optimise (A_t, b_t) from the current x at the current theta;
+        (2) g0 = dF/dtheta at the returned x; (3) g1 = the same at theta + 1 (a probe on the live context); (4) theta_mstep.
+        own_parameters=True: every problem moves its own theta; otherwise the batch shares one theta and the step is pooled.
+        The new theta is written to every member's model.theta (the models' own checks apply; nothing is clipped).
+        Returns (x (B, len_x), F (B,), theta (B, n_theta), trace) with trace["F"] (rounds, 2, B): F after the E-step and after the
+        M-step, trace["theta"] (rounds, B, n_theta): theta after each M-step, trace["g0"] / trace["g1"] (rounds, B, n_theta): the two
+        gradients each M-step was computed from.
+        """
+        x = self._stack(x0).copy()
+        trace = {"F": np.zeros((int(rounds), 2, self.B)), "theta": [], "g0": [], "g1": []}
+        f = None
+        for r in range(int(rounds)):
+            x, _, _ = self.optimise(x, options)
+            x = np.array(x, dtype=float)
+            # (the state SCG leaves resident may belong to a rejected trial point: F and g0 at the returned x)
+            trace["F"][r, 0] = self.free_energy(x)
+            g0 = self.theta_gradient()
+            theta = self._theta_rows()
+            ctx = self._context()
+            sigma = self._per_problem()[0]["sigma"] if self.own_parameters else None
+            try:
+                ctx.set_problem_params(theta=theta + 1.0, sigma=sigma)
+                ctx.free_energy(x)
+                g1 = np.asarray(ctx.theta_gradient(), dtype=float).reshape(self.B, -1)
+            finally:
+                self.close()            # (the probe's parameters are in force on that context: the next call builds a fresh one)
+            new = theta_mstep(theta, g0, g1, pooled=not self.own_parameters)
+            for vgp, row in zip(self.vgps, new):
+                vgp.model.theta = float(row[0]) if row.size == 1 else row.copy()
+            trace["theta"].append(new)
+            trace["g0"].append(g0)
+            trace["g1"].append(g1)
+            f = self.free_energy(x)
+            trace["F"][r, 1] = f
+        for key in ("theta", "g0", "g1"):
+            trace[key] = np.asarray(trace[key])
+        self._x, self._f = x, f
+        return x, f, self._theta_rows(), trace
 
     def optimise(self, x0, options=None):
         """DeviceSCG over the whole batch in lock step: (x (B, len_x), f (B,), statistics)."""

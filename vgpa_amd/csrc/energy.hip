@@ -33,6 +33,7 @@ __global__ void __launch_bounds__(NT) k_energy_1d(EnergyArgs a) {
   const double sg = a.sigma1_v ? a.sigma1_v[prob] : a.sigma1;
   if (a.model == VGPA_MODEL_OU) energy_1d<VGPA_MODEL_OU>(th, sg, la, ob, m, s, r);
   else energy_1d<VGPA_MODEL_DW>(th, sg, la, ob, m, s, r);
+  if (a.hyp_only) { a.hyp[o] = r.hyp; return; }      // (vgpa_theta_gradient: the cached energy arrays stay as they are)
   a.e_t[o] = r.e_t;
   a.Ef[o] = r.ef;
   if (a.Edf) a.Edf[o] = r.edf;
@@ -59,6 +60,12 @@ __global__ void __launch_bounds__(64) k_energy_l63(EnergyArgs a) {
   for (int i = 0; i < 3; i++) { bv[i] = bt[i]; mv[i] = mt[i]; isg[i] = isgp[i]; }
   EnergyL63 r;
   if (a.hyp) energy_l63<true>(th, isg, Av, bv, mv, Sv, r); else energy_l63<false>(th, isg, Av, bv, mv, Sv, r);
+  if (a.hyp_only) {                                  // (vgpa_theta_gradient: the cached energy arrays stay as they are)
+    double* hp = a.hyp + o * 6;
+#pragma unroll
+    for (int i = 0; i < 6; i++) hp[i] = r.hyp[i];
+    return;
+  }
   a.e_t[o] = r.e_t;
   double* dm = a.dEm + o * 3;
   dm[0] = r.dm[0]; dm[1] = r.dm[1]; dm[2] = r.dm[2];
@@ -547,7 +554,10 @@ __device__ __constant__ TriRowTab kTriRow = make_tri_row_tab();
 // (One grid point per wave.  Persistent waves over several grid points, with the next point's operands requested under the current
 //  one's phases, measured 11.2 ms against 5.5 ms per 512-problem launch: with a loop around the body the register allocator spills
 //  ~90 values at the 168-register budget of three waves per SIMD -- EXPERIMENTS.md s.10.)
-template <int NB>
+// TG (vgpa_theta_gradient): the integrand of dF/dtheta, sum_i isg_i (w0 r0_i + w1 sum_j (ra_ij + rb_ij)) -- the residuals of step 3 summed
+// BEFORE squaring -- goes to a.tg[o] and the kernel ends behind step 3: no other array is written (the cached state survives), G = A.L is
+// not formed (it cancels in ra + rb = 2 E).  A template parameter, not a run-time switch: the TG = false kernel is the one it was.
+template <int NB, bool TG = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NB <= 10 ? 3 : 2, NB <= 10 ? 3 : 2))) k_energy_l96_r(EnergyArgs a) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int D = a.D, M = 2 * D + 1;
@@ -764,13 +774,15 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NB <= 1
 #pragma unroll
   for (int u = 0; u < NUU; u++) {
     const int i = 16 * u + 4 * b + r4;
-    if (c4 == 0 && i < D) { S.am[i] = amr[u]; if (a.Am) a.Am[o * D + i] = amr[u]; }
+    if (c4 == 0 && i < D) { S.am[i] = amr[u]; if (!TG && a.Am) a.Am[o * D + i] = amr[u]; }
   }
+  if constexpr (TG) wave_sync();                   // A m of every row is in LDS (rows 0, 1, D-1 and the mean point read it below)
 
   // ---- 3. residuals of the sigma points m +- L[:, j] in accumulator layout, rows 2 .. D-2
   // park rows 0, 1, D-1 of G for the boundary pass first (only the units that can hold them: compile-time test), so
   // that the residual loop below is ONE basic block (with branches in between, the compiler sinks all the arithmetic
   // below the last branch and keeps 8 NB NUU registers of LDS reads alive)
+  if constexpr (!TG) {
 #pragma unroll
   for (int u = 0; u < NUU; u++) {
     if (u == 0 || (16 * u <= Dp - 1 && 16 * u + 15 >= Dp - 4)) {
@@ -788,6 +800,47 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NB <= 1
       }
     }
   }
+  }
+  // TG: rows 0, 1, D-1 (lane = column, as in the boundary pass below) and the mean point (lane = row) FIRST -- ra + rb of a sigma-point
+  // pair needs no G, and in front of the residual loop these reads meet few live registers (behind it the kernel spilled 364 bytes)
+  double tg_edge = 0.0;
+  if constexpr (TG) {
+    const double w0 = kappa / c, w1 = 1.0 / (2.0 * c);
+    auto col_of = [&](int q) { return q == 0 ? 0 : (q <= D ? q - 1 : q - 1 - D); };
+    auto sgn_of = [&](int q) { return q == 0 ? 0.0 : (q <= D ? 1.0 : -1.0); };
+    auto chi = [&](int q, int i) { return S.mv[i] + sgn_of(q) * S.Lm[i * LD + col_of(q)]; };
+    const int jc = act ? l : 0;
+    const int pP = 1 + jc, pM = 1 + D + jc;
+    const int pPm = pP - 1, pPp = pP + 1;
+    const int pMm = pM - 1, pMp = wrap(pM + 1, M);
+    const double P0 = chi(pPm, D - 2), P1 = chi(pPm, D - 1), P2 = chi(pP, 0), P3 = chi(pP, 1), P4 = chi(pP, 2);
+    const double N0 = chi(pMm, D - 2), N1 = chi(pMm, D - 1), N2 = chi(pM, 0), N3 = chi(pM, 1), N4 = chi(pM, 2);
+    const double Q0 = chi(pP, D - 3), Q1 = chi(pP, D - 2), Q2 = chi(pP, D - 1), Q3 = chi(pPp, 0);
+    const double R0 = chi(pM, D - 3), R1 = chi(pM, D - 2), R2 = chi(pM, D - 1), R3 = chi(pMp, 0);
+    double bsum = 0.0;
+    {
+      const double lin = S.am[0] - S.bv[0];
+      bsum += lane_value(v_sg, 0) * ((((P3 - P0) * P1 - P2 + theta) + lin) + (((N3 - N0) * N1 - N2 + theta) + lin));
+    }
+    {
+      const double lin = S.am[1] - S.bv[1];
+      bsum += lane_value(v_sg, 1) * ((((P4 - P1) * P2 - P3 + theta) + lin) + (((N4 - N1) * N2 - N3 + theta) + lin));
+    }
+    {
+      const double lin = S.am[D - 1] - S.bv[D - 1];
+      bsum += lane_value(v_sg, D - 1) * ((((Q3 - Q0) * Q1 - Q2 + theta) + lin) + (((R3 - R0) * R1 - R2 + theta) + lin));
+    }
+    double part = 0.0;
+    if (act) {
+      const int i = l;
+      const double xm2 = (i >= 2) ? S.mv[i - 2] : chi(M - 1, D - 2 + i);
+      const double xm1 = (i >= 1) ? S.mv[i - 1] : chi(M - 1, D - 1);
+      const double x1 = (i + 1 < D) ? S.mv[i + 1] : chi(1, 0);
+      const double r0 = ((x1 - xm2) * xm1 - S.mv[i] + theta) + S.am[i] - S.bv[i];
+      part += w1 * bsum + w0 * (v_sg * r0);
+    }
+    tg_edge = part;
+  }
   // (round 3) The residuals of the sigma-point PAIR m +- L[:, j] are evaluated as E +- O: with dm = m_{i+1} - m_{i-2},
   // dl = l_{i+1} - l_{i-2} (l = L[:, j]) the drift's product (dm +- dl)(m_{i-1} +- l_{i-1}) splits into an even part
   // dm m_{i-1} + dl l_{i-1} and an odd part dm l_{i-1} + dl m_{i-1}, so
@@ -797,6 +850,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NB <= 1
   // grid point, 6 k of them fp64 vector arithmetic), and v_+ - v_- no longer comes from the difference of two large sums.  The
   // contraction a*b+c -> fma is allowed in this block (tolerance 1e-6 asked, 1e-9 tested; the build's default is off).
   double vp[NB], vm[NB];                                          // S1, S2 of the interior rows
+  double tgi = 0.0;                                               // TG: this lane's sum of s_i E over its interior rows and real columns
 #pragma unroll
   for (int J = 0; J < NB; J++) { vp[J] = 0.0; vm[J] = 0.0; }
   {
@@ -821,9 +875,15 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NB <= 1
       const double od = dm * e1 + (dl * mm1 + (gi - e0));
       vp[J] = vp[J] + sgi * (ev * ev + od * od);
       vm[J] = vm[J] + sgi * (ev * od);
+      if constexpr (TG) tgi = tgi + ((4 * J + c4 < D) ? sgi : 0.0) * ev;      // (padding columns of L are zero: their E is not a sigma point's)
       if (J == NB / 2 - 1 || J == NB - 1) __builtin_amdgcn_sched_barrier(0);    // keep the scheduler from hoisting all 4 NB LDS reads (registers)
     }
   }
+  }
+  if constexpr (TG) {
+    const double part = wave_sum(tg_edge + 2.0 * (1.0 / (2.0 * c)) * tgi);
+    if (l == 0) a.tg[o] = part;
+    return;
   }
   // sum over the rows: ones-MFMA adds the four r4 of a block slot, the four block slots b go through LDS
   {
@@ -1110,6 +1170,7 @@ hipError_t launch_energy(const EnergyArgs& a, hipStream_t st) {
   } else if (a.model == VGPA_MODEL_L96) {
     if (a.D < 4 || a.D > kMaxSmallD) return hipErrorInvalidValue;
     const bool one_matrix = (a.hyp == nullptr);      // the hyper-parameter integrands need the second LDS matrix
+    if (a.tg && !one_matrix) return hipErrorInvalidValue;
     size_t lds = (one_matrix ? l96r_lds_doubles(a.D) : l96_lds_doubles(a.D)) * sizeof(double);
     const long long nwaves = (long long)a.Np * a.batch;
     if (nwaves > 0x7fffffffLL) return hipErrorInvalidValue;
@@ -1118,6 +1179,11 @@ hipError_t launch_energy(const EnergyArgs& a, hipStream_t st) {
     if (lds > 48 * 1024)                                                                                            \
       (void)hipFuncSetAttribute(one_matrix ? (const void*)k_energy_l96_r<NBV> : (const void*)k_energy_l96<NBV>,       \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                \
+    if (a.tg) {                                                                                                     \
+      if (lds > 48 * 1024)                                                                                          \
+        (void)hipFuncSetAttribute((const void*)k_energy_l96_r<NBV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+      hipLaunchKernelGGL((k_energy_l96_r<NBV, true>), dim3((unsigned)nwaves), dim3(64), lds, st, a);                  \
+    } else                                                                                                          \
     if (one_matrix) hipLaunchKernelGGL(k_energy_l96_r<NBV>, dim3((unsigned)nwaves), dim3(64), lds, st, a);          \
     else hipLaunchKernelGGL(k_energy_l96<NBV>, dim3((unsigned)nwaves), dim3(64), lds, st, a);                        \
     break;

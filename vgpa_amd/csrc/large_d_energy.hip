@@ -649,6 +649,49 @@ __global__ void __launch_bounds__(NT) k_hyper(int D, double theta, const double*
   h[D + i] = acc;
 }
 
+// Integrand of dF/dtheta (vgpa_theta_gradient): u_p = sum_i isg_i (f_i(chi_p) + (A m)_i - b_i) for every sigma point p -- the residuals of
+// k_resid summed BEFORE squaring, without the G term, which cancels between the points m + L[:, j] and m - L[:, j] -- thread = sigma
+// point, sliding window over the components (flat roll, quirk Q1, as in k_resid); k_theta_fin then forms tg[t] = w0 u_0 + w1 sum_p u_p.
+__global__ void __launch_bounds__(NT) k_theta_resid(int D, double theta, const double* L, long long sW, const double* m, const double* b,
+                                                    long long sb, const double* am, const double* isg, double* u, long long su) {
+  const int M = 2 * D + 1;
+  const int p = blockIdx.x * NT + threadIdx.x;
+  if (p >= M) return;
+  const int t = blockIdx.y;
+  const double* Lm = L + (long long)t * sW;
+  const double* mv = m + (long long)t * D;
+  const double* bv = b + (long long)t * sb;
+  const double* av = am + (long long)t * D;
+  auto col_of = [&](int q) { return q == 0 ? 0 : (q <= D ? q - 1 : q - 1 - D); };
+  auto sgn_of = [&](int q) { return q == 0 ? 0.0 : (q <= D ? 1.0 : -1.0); };
+  auto chi = [&](int q, int i) { return mv[i] + sgn_of(q) * Lm[(long long)i * D + col_of(q)]; };
+  const int pm = wrapi(p - 1, M), pp = wrapi(p + 1, M);
+  auto at = [&](int i) { return i < 0 ? chi(pm, i + D) : (i < D ? chi(p, i) : chi(pp, i - D)); };
+  double xm2 = at(-2), xm1 = at(-1), x0 = at(0), x1 = at(1);
+  double acc = 0.0;
+  for (int i = 0; i < D; i++) {
+    const double res = ((x1 - xm2) * xm1 - x0 + theta) + av[i] - bv[i];
+    acc = __builtin_fma(isg[i], res, acc);
+    xm2 = xm1; xm1 = x0; x0 = x1;
+    const int in = i + 2;
+    x1 = (in < D) ? chi(p, in) : chi(pp, in - D);
+  }
+  u[(long long)t * su + p] = acc;
+}
+
+__global__ void __launch_bounds__(NT) k_theta_fin(int D, const double* u, long long su, double* tg) {
+  __shared__ double red[NT];
+  const int t = blockIdx.x, tid = threadIdx.x;
+  const double kappa = 1.05 * D, c = D + kappa, w0 = kappa / c, w1 = 1.0 / (2.0 * c);
+  const double* uu = u + (long long)t * su;
+  double part = 0.0;
+  for (int r = tid; r < D; r += NT) part += uu[1 + r] + uu[1 + D + r];
+  red[tid] = part;
+  __syncthreads();
+  for (int s = NT / 2; s > 0; s >>= 1) { if (tid < s) red[tid] += red[tid + s]; __syncthreads(); }
+  if (tid == 0) tg[t] = w0 * uu[0] + w1 * red[0];
+}
+
 // Y[k][j] = q_k X[k][j]
 __global__ void __launch_bounds__(NT) k_scale_rows(int D, const double* X, const double* q, double* Y, long long sW) {
   const double* x = X + (long long)blockIdx.y * sW;
@@ -779,9 +822,11 @@ int lde_batch(int D, double budget_bytes) {
 #define LDE_TRY_FORKED(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { if (nh == 2) (void)hipStreamSynchronize(side); return e_; } } while (0)
 
 // Energy terms of Np grid points of ONE problem.  Edf may be nullptr.
-hipError_t lde_energy(int D, int Np, double theta, const double* isg, const double* A, const double* b, const double* m,
-                      const double* S, double* e_t, double* Ef, double* Edf, double* dEm, double* dEs, int32_t* status,
-                      double* ws, int nbmax, hipStream_t st, double* hyp, hipStream_t side) {
+// tg != nullptr (lde_theta_integrand): the factorisation and A m only, then the integrand of dF/dtheta into tg -- none of the output arrays
+// is touched, L^-1 and G = A L are not formed.
+static hipError_t lde_energy_impl(int D, int Np, double theta, const double* isg, const double* A, const double* b, const double* m,
+                                  const double* S, double* e_t, double* Ef, double* Edf, double* dEm, double* dEs, int32_t* status,
+                                  double* ws, int nbmax, hipStream_t st, double* hyp, hipStream_t side, double* tg) {
   using namespace lde;
   const long long DD = (long long)D * D;
   const int T = (D + NBLK - 1) / NBLK, M = 2 * D + 1;
@@ -869,7 +914,7 @@ hipError_t lde_energy(int D, int Np, double theta, const double* isg, const doub
     // neighbouring groups of h blocks; the groups of a level are independent and go into ONE launch per product (second batch level of
     // GemmB), so D / 64 = 16 | 64 takes 8 | 12 launches of growing products instead of 30 | 126 of one 64-row block each.  The
     // intermediate L_21 X_11 sits in G (free until G = A L) at the place of X_21.
-    for (int h = 1; h < T; h *= 2) {
+    for (int h = 1; h < T && !tg; h *= 2) {
       const int hs = h * NBLK;
       const int ngr = (T - h + 2 * h - 1) / (2 * h);           // groups whose second half exists
       const long long step2 = (long long)2 * hs * (D + 1);     // from one group's blocks to the next group's
@@ -900,6 +945,14 @@ hipError_t lde_energy(int D, int Np, double theta, const double* isg, const doub
     if (nh == 2) {
       LDE_TRY_FORKED(hipEventRecord(evB, side));               // join
       LDE_TRY_FORKED(hipStreamWaitEvent(st, evB, 0));
+    }
+    if (tg) {
+      hipLaunchKernelGGL(k_matvec, dim3((D + 3) / 4, nb), dim3(NT), 0, st, D, 0, At, DD, mt, (long long)D, am, (long long)D, 1.0);
+      hipLaunchKernelGGL(k_theta_resid, dim3((M + NT - 1) / NT, nb), dim3(NT), 0, st, D, theta, C, DD, mt, bt, (long long)D, am, isg, vv,
+                         (long long)M);
+      hipLaunchKernelGGL(k_theta_fin, dim3(nb), dim3(NT), 0, st, D, vv, (long long)M, tg + t0);
+      LDE_TRY(hipGetLastError());
+      continue;
     }
     // ---- G = A L ; A m
     GemmB gg{};
@@ -938,6 +991,18 @@ hipError_t lde_energy(int D, int Np, double theta, const double* isg, const doub
     LDE_TRY(hipGetLastError());
   }
   return hipSuccess;
+}
+
+hipError_t lde_energy(int D, int Np, double theta, const double* isg, const double* A, const double* b, const double* m,
+                      const double* S, double* e_t, double* Ef, double* Edf, double* dEm, double* dEs, int32_t* status,
+                      double* ws, int nbmax, hipStream_t st, double* hyp, hipStream_t side) {
+  return lde_energy_impl(D, Np, theta, isg, A, b, m, S, e_t, Ef, Edf, dEm, dEs, status, ws, nbmax, st, hyp, side, nullptr);
+}
+
+hipError_t lde_theta_integrand(int D, int Np, double theta, const double* isg, const double* A, const double* b, const double* m,
+                               const double* S, double* tg, int32_t* status, double* ws, int nbmax, hipStream_t st) {
+  if (!tg) return hipErrorInvalidValue;
+  return lde_energy_impl(D, Np, theta, isg, A, b, m, S, nullptr, nullptr, nullptr, nullptr, nullptr, status, ws, nbmax, st, nullptr, nullptr, tg);
 }
 
 // Gradient w.r.t. (A_t, b_t) for D > 64 (src/var_bayes/variational.py:263-288), diagonal Sigma^-1:

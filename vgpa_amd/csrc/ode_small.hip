@@ -767,6 +767,105 @@ __global__ void __launch_bounds__(NTS) __attribute__((amdgpu_waves_per_eu(1, 1))
   }
 }
 
+// Integrands of dF/dtheta at fixed (A, b) from the resident state of a fused lane pass (vgpa_theta_gradient): one lane per problem,
+// FORWARD in time.  A_t, b_t come from x through the chunked LDS staging above (chunk c = grid points [c T, c T + T)), the moments
+// from the time-major msT (coalesced, requested two steps ahead); the closed-form integrand <(f - g) . df/dtheta> (energy_small.h:
+// Energy1d::hyp, EnergyL63::hyp[0..2]) is evaluated in registers, the trapezoid is carried in registers, and the only store is
+// out[prob][0..H).  Traffic: ONE read of x and of the moments, B H doubles written; nothing of size B Np is allocated or written.
+template <int MODEL, int T, bool PP>
+__global__ void __launch_bounds__(NTS) __attribute__((amdgpu_waves_per_eu(1, 1))) k_theta_lane(ThetaLaneArgs q) {
+  constexpr int D = (MODEL == VGPA_MODEL_L63) ? 3 : 1, DD = D * D, NA = T * DD, NV = T * D, H = D;
+  __shared__ double sA[ChunkMap<NA>::LDS];
+  __shared__ double sB[ChunkMap<NV>::LDS];
+  const int lane = threadIdx.x, prob0 = blockIdx.x * NTS;
+  const int nvalid = (q.batch - prob0) < NTS ? (q.batch - prob0) : NTS;
+  const bool live = lane < nvalid;
+  const int prob = prob0 + (live ? lane : nvalid - 1);
+  const int Np = q.Np;
+  const double dt = q.dt;
+  const long limA = (long)Np * DD, limV = (long)Np * D;
+  constexpr int TRI = D * (D + 1) / 2, W = TRI + D;
+  const double* const msT = q.msT + prob;
+  const size_t bp = (size_t)q.bpad;
+  auto load_ms = [&](int t, double (&Sv)[DD], double (&mv)[D]) {
+#pragma unroll
+    for (int i = 0; i < D; i++)
+#pragma unroll
+      for (int j = 0; j <= i; j++) {
+        const double v = msT[((size_t)t * W + tri_off(i) + j) * bp];
+        Sv[i * D + j] = v; Sv[j * D + i] = v;
+      }
+#pragma unroll
+    for (int i = 0; i < D; i++) mv[i] = msT[((size_t)t * W + TRI + i) * bp];
+  };
+  double th[kMaxTheta];
+#pragma unroll
+  for (int i = 0; i < kMaxTheta; i++) th[i] = PP ? q.theta_v[(size_t)prob * kMaxTheta + i] : q.theta[i];
+
+  const int nchunks = (Np + T - 1) / T;
+  double pa[ChunkMap<NA>::NI], pb[ChunkMap<NV>::NI];
+  const double* Au = q.A + (size_t)prob0 * q.stride_x;        // wave-uniform stream bases
+  const double* bu = q.b + (size_t)prob0 * q.stride_x;
+  const unsigned strx = (unsigned)q.stride_x;
+  chunk_request<NA>(Au, strx, nvalid, 0, limA, pa);
+  chunk_request<NV>(bu, strx, nvalid, 0, limV, pb);
+  double Sc[DD], mc[D], Sn[DD], mn[D], Sn2[DD], mn2[D];
+  load_ms(0, Sc, mc);
+  load_ms(Np > 1 ? 1 : Np - 1, Sn, mn);
+  load_ms(Np > 2 ? 2 : Np - 1, Sn2, mn2);
+  double acc[H], prev[H];
+#pragma unroll
+  for (int h = 0; h < H; h++) { acc[h] = 0.0; prev[h] = 0.0; }
+  const double* rowA = sA + lane * row_stride<NA>();
+  const double* rowB = sB + lane * row_stride<NV>();
+  for (int c = 0; c < nchunks; c++) {
+    chunk_to_lds<NA>(sA, pa);
+    chunk_to_lds<NV>(sB, pb);
+    wave_sync();
+    if (c + 1 < nchunks) {      // the next chunk travels while this one is stepped through
+      const long lon = (long)(c + 1) * T;
+      chunk_request<NA>(Au, strx, nvalid, lon * DD, limA, pa);
+      chunk_request<NV>(bu, strx, nvalid, lon * D, limV, pb);
+    }
+#pragma unroll 1
+    for (int s = 0; s < T; s++) {
+      const int t = c * T + s;
+      if (t < Np) {
+        double Am[DD], bm[D], cur[H];
+#pragma unroll
+        for (int e = 0; e < DD; e++) Am[e] = rowA[s * DD + e];
+#pragma unroll
+        for (int i = 0; i < D; i++) bm[i] = rowB[s * D + i];
+        if constexpr (MODEL == VGPA_MODEL_L63) {
+          EnergyL63 r;
+          const double one[3] = {1.0, 1.0, 1.0};       // (the integrands do not depend on Sigma; the caller scales by its diagonal)
+          energy_l63<true>(th, one, Am, bm, mc, Sc, r);
+          cur[0] = r.hyp[0]; cur[1] = r.hyp[1]; cur[2] = r.hyp[2];
+        } else {
+          Energy1d r;
+          energy_1d<MODEL>(th[0], 1.0, Am[0], bm[0], mc[0], Sc[0], r);
+          cur[0] = r.hyp;
+        }
+#pragma unroll
+        for (int h = 0; h < H; h++) {
+          if (t > 0) acc[h] += dt * (prev[h] + cur[h]) / 2.0;     // my_trapz, utilities.py:144 (interval [t-1, t])
+          prev[h] = cur[h];
+        }
+#pragma unroll
+        for (int e = 0; e < DD; e++) { Sc[e] = Sn[e]; Sn[e] = Sn2[e]; }
+#pragma unroll
+        for (int i = 0; i < D; i++) { mc[i] = mn[i]; mn[i] = mn2[i]; }
+        load_ms(t + 3 < Np ? t + 3 : Np - 1, Sn2, mn2);
+      }
+    }
+    wave_sync();                  // every lane is done with its rows before the next chunk overwrites them
+  }
+  if (live) {
+#pragma unroll
+    for (int h = 0; h < H; h++) q.out[(size_t)prob * H + h] = acc[h];
+  }
+}
+
 template <int METHOD, bool FWD, int D>
 hipError_t launch_d(const OdeArgs& a, hipStream_t st) {
   dim3 grid((a.batch + NTS - 1) / NTS), block(NTS);
@@ -934,6 +1033,28 @@ hipError_t launch_obs_lane(const ObsArgs& a, const double* msT, int bpad, double
 
 bool sweep_lane_supported(int model, int D) {
   return (model == VGPA_MODEL_L63 && D == 3) || ((model == VGPA_MODEL_OU || model == VGPA_MODEL_DW) && D == 1);
+}
+
+namespace {
+template <int MODEL>
+hipError_t launch_theta_lane_m(const ThetaLaneArgs& q, hipStream_t st) {
+  const dim3 grid((q.batch + NTS - 1) / NTS), block(NTS);
+  constexpr int T = (MODEL == VGPA_MODEL_L63) ? 4 : 16;      // (the chunk sizes of k_sweep_lane)
+  if (q.theta_v) hipLaunchKernelGGL((k_theta_lane<MODEL, T, true>), grid, block, 0, st, q);
+  else hipLaunchKernelGGL((k_theta_lane<MODEL, T, false>), grid, block, 0, st, q);
+  return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_theta_lane(const ThetaLaneArgs& q, hipStream_t st) {
+  // (32-bit byte offsets inside a wave's 64 problems, like every lane kernel: the stepper's choice of this path guarantees it)
+  if (!sweep_lane_supported(q.model, q.D) || q.Np < 2 || !q.msT || !q.out || q.stride_x >= ((size_t)1 << 22)) return hipErrorInvalidValue;
+  switch (q.model) {
+    case VGPA_MODEL_OU: return launch_theta_lane_m<VGPA_MODEL_OU>(q, st);
+    case VGPA_MODEL_DW: return launch_theta_lane_m<VGPA_MODEL_DW>(q, st);
+    case VGPA_MODEL_L63: return launch_theta_lane_m<VGPA_MODEL_L63>(q, st);
+  }
+  return hipErrorInvalidValue;
 }
 
 hipError_t launch_sweep_lane(int method, const LaneSweepArgs& q, hipStream_t st) {

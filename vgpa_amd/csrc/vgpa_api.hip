@@ -98,6 +98,8 @@ struct vgpa_ctx {
   double* d_hyp = nullptr;        // [B][Np][H] integrands of the hyper-parameter gradients (vgpa_energy_hyper only)
   double* d_hypT = nullptr;       // [B][H] their trapezoids
   bool hyp_on = false;
+  double* d_tg = nullptr;         // [B][Np] integrand of dF/dtheta (vgpa_theta_gradient, Lorenz-96)
+  double* d_thT = nullptr;        // [B][kMaxTheta] ... its trapezoids / the lane kernel's results
   std::vector<double> h_isig;     // host copy of Sigma^-1 [D][D]
   double* d_vec_scratch = nullptr; // [2B coefficients | B results | B*bps partials] of the vector algebra
   size_t vec_scratch_n = 0;
@@ -1342,6 +1344,70 @@ int vgpa_energy_parts(vgpa_ctx* c, double* e0, double* esde, double* eobs) {
   if (esde && (rc = download(c, esde, c->d_esde, (size_t)c->B))) return rc;
   if (eobs && (rc = download(c, eobs, c->d_eobs, (size_t)c->B))) return rc;
   return vgpa_synchronize(c);
+}
+
+// dF/dtheta at fixed (A_t, b_t) from the cached state.  In all four models the drift is affine in theta and E_sde takes the diagonal of
+// Sigma^-1 only, so dF/dtheta_k = sum_i (Sigma^-1)_ii int <(f - g)_i d f_i / d theta_k> dt: the residuals the energy kernels form, summed
+// before squaring.  OU / double well / Lorenz-63: the closed forms of <model>.energy (dEsde_dth).  Lorenz-96: the UNSCENTED mean of the
+// residual with the flat roll of the energy itself -- not the reference's dEsde_dth, which is built from the closed-form mean drift and
+// is not the derivative of the F computed here.  Nothing of the cached state is written.
+int vgpa_theta_gradient(vgpa_ctx* c, double* out) {
+  if (!c || !out) return fail(c, VGPA_ERR_ARG, "null argument");
+  if (!c->full) return fail(c, VGPA_ERR_STATE, "context was created without m0/s0/observations (ODE-only)");
+  if (c->stream_ld) return fail(c, VGPA_ERR_UNSUPPORTED, "dF/dtheta is not built for the time-chunked large-D sweep");
+  if (!c->have_state) return fail(c, VGPA_ERR_STATE, "no cached state: theta_gradient needs the state cached by a previous free_energy / sweep");
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  const int D = c->D, B = c->B, Np = c->Np, nth = c->cfg.n_theta;
+  const size_t BN = (size_t)B * Np;
+  int rc, H = 1;                       // H: doubles per problem in the result buffer
+  const double* res = nullptr;
+  if ((rc = ensure(c, &c->d_thT, (size_t)B * kMaxTheta))) return rc;
+  if (c->plan.lane_pass) {             // one lane per problem over x and the time-major moments; nothing per grid point is written
+    ThetaLaneArgs q{};
+    q.model = c->cfg.model; q.D = D; q.Np = Np; q.batch = B; q.bpad = c->bpad; q.dt = c->cfg.dt; q.stride_x = c->len_x;
+    q.A = ctx_A(c); q.b = ctx_b(c); q.msT = c->d_msT;
+    copy_theta(c, q.theta);
+    q.theta_v = c->in.theta.rows; q.out = c->d_thT;
+    LAUNCH_TRY(c, "theta lane kernel launch", launch_theta_lane(q, c->stream));
+    H = D; res = c->d_thT;
+  } else if (c->cfg.model == VGPA_MODEL_L96) {
+    if ((rc = ensure(c, &c->d_tg, BN))) return rc;
+    if (D > kMaxSmallD) {
+      if ((rc = ensure_lde_ws(c))) return rc;
+      ld::use_library_gemm = (c->cfg.flags & VGPA_FLAG_LIBRARY_GEMM) != 0;
+      const size_t NpD = (size_t)Np * D, NpDD = (size_t)Np * c->DD;
+      for (int p = 0; p < B; p++)
+        LAUNCH_TRY(c, "large-D theta integrand", ld::lde_theta_integrand(D, Np, theta_of(c, p)[0], c->in.isg.of(p), ctx_A(c) + p * c->len_x,
+                                                                         ctx_b(c) + p * c->len_x, c->d_m + p * NpD, c->d_S + p * NpDD,
+                                                                         c->d_tg + (size_t)p * Np, c->d_status + p, c->d_lde_ws, c->lde_nb, c->stream));
+    } else {                           // the energy kernel over the resident (m_t, S_t) in the layout they are in, integrand only
+      EnergyArgs a = energy_args(c, nullptr);
+      a.hyp = nullptr; a.tg = c->d_tg;
+      LAUNCH_TRY(c, "theta integrand launch", launch_energy(a, c->stream));
+    }
+    LAUNCH_TRY(c, "trapezoid launch", launch_trapz_multi(c->d_tg, Np, 1, B, c->cfg.dt, c->d_thT, c->stream));
+    H = 1; res = c->d_thT;
+  } else {                             // wave / workgroup contexts of the small models: the hyp integrands of the energy kernels
+    H = c->single ? 1 : 2 * D;
+    if ((rc = materialize_moments(c))) return rc;
+    if ((rc = ensure(c, &c->d_hyp, BN * H))) return rc;
+    if ((rc = ensure(c, &c->d_hypT, (size_t)B * H))) return rc;
+    EnergyArgs a = energy_args(c, nullptr);
+    a.hyp = c->d_hyp; a.hyp_only = 1;
+    LAUNCH_TRY(c, "theta integrand launch", launch_energy(a, c->stream));
+    LAUNCH_TRY(c, "trapezoid launch", launch_trapz_multi(c->d_hyp, Np, H, B, c->cfg.dt, c->d_hypT, c->stream));
+    res = c->d_hypT;
+  }
+  std::vector<double> T((size_t)B * H);
+  if ((rc = download(c, T.data(), res, T.size()))) return rc;
+  if ((rc = vgpa_synchronize(c))) return rc;
+  for (int p = 0; p < B; p++) {
+    const double* Tp = T.data() + (size_t)p * H;
+    if (c->single) out[p] = (c->cfg.model == VGPA_MODEL_DW ? 4.0 : 1.0) * Tp[0] / sigma1_of(c, p);      // (the factors of vgpa_energy_full)
+    else if (c->cfg.model == VGPA_MODEL_L96) out[p] = Tp[0];                                              // (Sigma^-1 is in the integrand)
+    else for (int i = 0; i < nth; i++) out[(size_t)p * nth + i] = isig_of(c, p)[(size_t)i * D + i] * Tp[i];
+  }
+  return VGPA_OK;
 }
 
 int vgpa_fetch(vgpa_ctx* c, int which, double* out) {

@@ -146,6 +146,23 @@ struct EnergyArgs {
   const double* theta_v;    // [B][kMaxTheta] instead of theta, or nullptr
   const double* sigma1_v;   // [B] instead of sigma1, or nullptr
   size_t isg_stride;        // D: isg is [B][D]; 0: shared by the batch
+  // dF/dtheta from the resident state (vgpa_theta_gradient), last for the same reason
+  double* tg;               // L96, D <= 64: [B][Np] integrand sum_i isg_i UT-mean(f_i(chi) + (A chi)_i - b_i); set: k_energy_l96_r computes this and
+                            // NOTHING else (no other array is written).  nullptr: skipped
+  int hyp_only;             // 1-D models, Lorenz-63: write `hyp` and nothing else (the cached energy arrays stay as they are)
+};
+
+// dF/dtheta integrands of the lane-per-problem contexts (ode_small.hip::k_theta_lane): x and the time-major moments in, [B][H] out
+struct ThetaLaneArgs {
+  int model, D, Np, batch, bpad;
+  double dt;
+  size_t stride_x;          // elements between consecutive problems in A / b (len_x)
+  const double* A;          // [B][Np][D][D]
+  const double* b;          // [B][Np][D]
+  const double* msT;        // OdeArgs::msT
+  double theta[kMaxTheta];
+  const double* theta_v;    // [B][kMaxTheta] instead of theta, or nullptr
+  double* out;              // [B][H] trapezoids of the integrands, H = 1 (OU, double well) or 3 (Lorenz-63); unscaled (vgpa_theta_gradient)
 };
 
 struct ObsArgs {
@@ -203,6 +220,7 @@ hipError_t launch_ode_generic(int method, bool fwd, const OdeArgs& a, hipStream_
 hipError_t launch_ode_small(int method, bool fwd, const OdeArgs& a, hipStream_t st);     // D <= kMaxLaneD
 bool sweep_lane_supported(int model, int D);
 hipError_t launch_sweep_lane(int method, const LaneSweepArgs& a, hipStream_t st);
+hipError_t launch_theta_lane(const ThetaLaneArgs& a, hipStream_t st);
 // msT -> the [B][Np] arrays: all grid points (vgpa_fetch, the separate kernels) or only what the observation terms read
 hipError_t launch_ms_untranspose(int D, int Np, int batch, int bpad, const double* msT, double* m, double* S, hipStream_t st);
 // observation terms (E_obs, sparse vector jumps) of the fused lane pass: one lane per problem, moments from msT, jumps to jmT
@@ -264,6 +282,9 @@ int lde_batch(int D, double budget_bytes);
 hipError_t lde_energy(int D, int Np, double theta, const double* isg, const double* A, const double* b, const double* m,
                       const double* S, double* e_t, double* Ef, double* Edf, double* dEm, double* dEs, int32_t* status,
                       double* ws, int nbmax, hipStream_t st, double* hyp = nullptr, hipStream_t side = nullptr)   /* hyp: [Np][2 D] integrands of dEsde_dtheta | dEsde_dSigma, or nullptr */;
+// tg[t] = sum_i isg_i UT-mean(f_i(chi) + (A chi)_i - b_i), the integrand of dF/dtheta, of Np grid points of one problem; writes tg and ws only
+hipError_t lde_theta_integrand(int D, int Np, double theta, const double* isg, const double* A, const double* b, const double* m,
+                               const double* S, double* tg, int32_t* status, double* ws, int nbmax, hipStream_t st);
 hipError_t lde_grad(int D, int Np, double dt, const double* isg, const double* A, const double* b, const double* m,
                     const double* S, const double* lam, const double* psi, const double* Ef, double* gA, double* gB,
                     double* ws, int nbmax, hipStream_t st, const double* isig_dense = nullptr);   // [D][D] Sigma^-1 when it is not diagonal

@@ -6,8 +6,9 @@ Each model keeps the reference's constructor, properties (`sigma`, `inverse_sigm
 
     energy(linear_a, offset_b, m, s, obs_t) -> (Esde, (Ef, Edf), (dEsde_dm, dEsde_ds, dEsde_dth, dEsde_dSig))
 
-but `energy` runs on the GPU through libvgpa_hip.so (vgpa_energy).  The hyper-parameter gradients
-(`dEsde_dth`, `dEsde_dSig`; unused by VarGP) are returned as None.
+but `energy` runs on the GPU through libvgpa_hip.so (vgpa_energy_full), the hyper-parameter members (`dEsde_dth`, `dEsde_dSig`)
+included: they come back with the reference's values.  For Lorenz-96 the reference's `dEsde_dth` is not the derivative of the free
+energy it computes; `VarGP.theta_gradient` / `ProblemBatch.theta_gradient` return dF/dtheta itself.
 
 The synthetic-data generators (`make_trajectory`, `collect_obs`) are one-off host-side input builders
 (numpy); they consume the random stream in exactly the reference's order, so that a given seed yields the

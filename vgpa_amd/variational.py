@@ -135,6 +135,29 @@ class VarGP(object):
             return g
         return ctx.gradient(None)
 
+    def theta_gradient(self, x=None):
+        """dF/dtheta at fixed (A_t, b_t), in the shape of model.theta (a float for OU / DW / L96, (3,) for L63; with batch > 1 a
+        leading batch axis).  x=None: from the state of the last free_energy (like gradient(x, eval_fun=False)); else F is
+        evaluated at x first."""
+        if x is not None:
+            self.free_energy(x)
+        g = np.asarray(self._context().theta_gradient())
+        if g.shape[-1] == 1:
+            g = g[..., 0]
+        return float(g) if g.ndim == 0 else g
+
+    def fit_theta(self, x0, rounds, options=None):
+        """Variational EM for the drift parameters (ProblemBatch.fit_theta on a batch of one): (x, F, theta, trace), theta in the
+        shape of model.theta, trace["F"] of shape (rounds, 2, 1)."""
+        from .batch import ProblemBatch
+        pb = ProblemBatch([self], device=self.device, flags=self.flags)
+        try:
+            x, f, theta, trace = pb.fit_theta(np.asarray(x0, dtype=float).reshape(1, -1), rounds, options)
+        finally:
+            pb.close()
+        theta = theta[0]
+        return x[0], float(f[0]), (float(theta[0]) if theta.size == 1 else theta), trace
+
     def sweep(self, x):
         """(F, grad) in one call: what SCG's df(x, eval_fun=True) evaluates."""
         f, g = self._context().sweep(np.asarray(x, dtype=float))
