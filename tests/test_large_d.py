@@ -552,25 +552,44 @@ def test_non_symmetric_operator_inputs_above_64(d, method):
     assert rel_err(lam, lam_o) < TOL and rel_err(psi, psi_o) < TOL
 
 
-@pytest.mark.gpu
-def test_batched_operators_above_64():
-    """Operator-level calls (FwdOde / BwdOde contract) with three problems at D = 96: problem-major inputs, every problem
-    against the oracle."""
+def _batched_operators_above_64(symmetric):
     import vgpa_amd as va
     d, n, nb = 96, 7, 3
     sets = [make_inputs(d, n, seed=11 + i) for i in range(nb)]
     ctx = va.Context("NONE", "rk4", d, n, 0.01, sigma=sets[0][4], batch=nb)
     a = np.stack([s_[0] for s_ in sets]); b = np.stack([s_[1] for s_ in sets])
-    mt, st = ctx.solve_fwd(a, b, sets[0][2], sets[0][3], sets[0][4])
+    s0 = sets[0][3]
     gm = np.stack([s_[5] for s_ in sets]); gs = np.stack([s_[6] for s_ in sets])
     jm = np.stack([s_[7] for s_ in sets]); js = np.stack([s_[8] for s_ in sets])
+    if not symmetric:                      # a shared non-symmetric s0; per-problem non-symmetric dEsde_dS and matrix jumps
+        rng = np.random.default_rng(7)
+        s0 = 0.2 * np.eye(d) + 0.02 * rng.standard_normal((d, d)) / np.sqrt(d)
+        gs = rng.standard_normal((nb, n, d, d)) / np.sqrt(d)
+        js = np.zeros((nb, n, d, d)); js[:, 3] = rng.standard_normal((nb, d, d)) / np.sqrt(d)
+    mt, st = ctx.solve_fwd(a, b, sets[0][2], s0, sets[0][4])
     lam, psi = ctx.solve_bwd(a, gm, gs, jm, js)
     for i in range(nb):
-        mt_o, st_o = vo.solve_fwd("rk4", 0.01, False, a[i], b[i], sets[0][2], sets[0][3], sets[0][4])
+        mt_o, st_o = vo.solve_fwd("rk4", 0.01, False, a[i], b[i], sets[0][2], s0, sets[0][4])
         lam_o, psi_o = vo.solve_bwd("rk4", 0.01, False, a[i], gm[i], gs[i], jm[i], js[i])
         assert rel_err(mt[i], mt_o) < TOL and rel_err(st[i], st_o) < TOL
         assert rel_err(lam[i], lam_o) < TOL and rel_err(psi[i], psi_o) < TOL
+        if not symmetric:                  # the results really are non-symmetric
+            assert rel_err(st[i], np.swapaxes(st[i], 1, 2)) > 1e-6 and rel_err(psi[i], np.swapaxes(psi[i], 1, 2)) > 1e-6
     ctx.close()
+
+
+@pytest.mark.gpu
+def test_batched_operators_above_64():
+    """Operator-level calls (FwdOde / BwdOde contract) with three problems at D = 96: problem-major inputs, every problem
+    against the oracle."""
+    _batched_operators_above_64(symmetric=True)
+
+
+@pytest.mark.gpu
+def test_batched_operators_above_64_non_symmetric():
+    """... with non-symmetric inputs: the batch on the literal-product path (the transposed copy of the stage state and the
+    second product run over all three problems, each in its own slice of the workspace)."""
+    _batched_operators_above_64(symmetric=False)
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -611,7 +611,7 @@ hipError_t launch_stage(const StageArgs& a, hipStream_t st) {
 
 // ---------------------------------------------------------------------------------------------------------------
 // Single-rank drivers (one GPU owns every row): the per-step / per-stage loop of the four steppers, all launches on
-// one stream.  `ws` is a workspace of at least ld_workspace_doubles(D) doubles.
+// one stream.  LdCall::ws is a workspace of at least ld_workspace_doubles(D) doubles per problem.
 // mid-point operand 0.5 (A_k + A_{k+1}) (runge_kutta2.py:74, runge_kutta4.py:74): formed ONCE per step and shared by
 // the two stages that use it; the GEMM that averages while staging its A tile streams both operands and is ~2.3x
 // slower at D = 1024 (measured: 156 us vs 67 us) -- that variant stays for the row-sharded driver.
@@ -622,20 +622,13 @@ __global__ void __launch_bounds__(256) k_mid(const double* __restrict__ a0, cons
 }
 
 // Batched single-rank drivers (64 < D <= 512 with several problems per context: the reference treats every D alike,
-// src/numerics/ode_solver.py:31-95, and ONE problem of that size leaves most of the chip idle).  The step / stage loops below
-// compute problem 0's pointers as always; which array a pointer belongs to -- hence its per-problem stride -- is looked up by
-// address in the ranges the API registered (x, the histories, the workspace ...); pointers outside every range (Sigma, the
-// constant jump, a shared S0) are shared by the problems.
-thread_local BatchMap g_batch;
-void ld_set_batch(const BatchMap* m) { g_batch = m ? *m : BatchMap{}; }
-static inline size_t zs(const double* p) { return g_batch.nb > 1 ? g_batch.stride(p) : 0; }
-
-thread_local bool use_library_gemm = false;
-// Non-symmetric operator-level inputs (S0, dEsde_dS, jumps that are not symmetric): the shortcut S A^T = (A S)^T does not hold,
-// so the second product of ode_solver.py:60,94 is formed literally -- Z = A_s X^T (forward) / A_s^T Psi^T (backward) from a
+// src/numerics/ode_solver.py:31-95, and ONE problem of that size leaves most of the chip idle).  Every operand of the drivers below is
+// an In / Out (vgpa_internal.h): problem 0's pointer and the per-problem stride its caller states -- 0 for what the problems share
+// (Sigma, the constant jump, a shared S0).  The step / stage loops offset operands as they always offset pointers; the stride travels
+// along into StageArgs / GemmArgs.  How many problems, and which products, is in the LdCall every driver takes.
+// LdCall::literal -- non-symmetric operator-level inputs (S0, dEsde_dS, jumps that are not symmetric): the shortcut S A^T = (A S)^T does
+// not hold, so the second product of ode_solver.py:60,94 is formed literally -- Z = A_s X^T (forward) / A_s^T Psi^T (backward) from a
 // transposed copy of the stage state, handed to the stage kernel as its column operand: Z[j][r] = (X A^T)[r][j] / (Psi A)[r][j].
-thread_local bool literal_products = false;
-void ld_set_literal_products(bool on) { literal_products = on; }
 
 size_t ld_workspace_doubles(int D) { return (size_t)8 * D * D + 4 * (size_t)D; }
 
@@ -658,15 +651,16 @@ __global__ void __launch_bounds__(256) k_transpose(const double* __restrict__ X,
 }
 
 namespace {
+const In none{};                   // an operand a stage does not have
 struct Work {
-  double *W, *K1, *K23, *XA, *XB, *AM, *XT, *W2, *xvA, *xvB, *k1v, *k23v;
+  Out W, K1, K23, XA, XB, AM, XT, W2, xvA, xvB, k1v, k23v;
 };
 // which pair of operands the mid-point buffer AM currently averages (valid inside one step)
-struct MidCache { const double* a0 = nullptr; const double* a1 = nullptr; };
-Work carve_work(double* ws, int D) {
+struct MidCache { In a0, a1; };
+Work carve_work(double* ws, int D) {             // (every problem's slices sit at the same offsets of its own workspace)
   const size_t DD = (size_t)D * D;
   Work w;
-  w.W = ws; w.K1 = w.W + DD; w.K23 = w.K1 + DD; w.XA = w.K23 + DD; w.XB = w.XA + DD;
+  w.W = {ws, ld_workspace_doubles(D)}; w.K1 = w.W + DD; w.K23 = w.K1 + DD; w.XA = w.K23 + DD; w.XB = w.XA + DD;
   w.AM = w.XB + DD; w.XT = w.AM + DD; w.W2 = w.XT + DD;
   w.xvA = w.W2 + DD; w.xvB = w.xvA + D; w.k1v = w.xvB + D; w.k23v = w.k1v + D;
   return w;
@@ -674,35 +668,37 @@ Work carve_work(double* ws, int D) {
 
 struct StageSpec {
   bool fwd;
-  const double *Am0, *Am1;   // A operand of the matrix product (Am1: mid-point partner or nullptr)
-  const double *Av0, *Av1;   // A of the vector recursion
-  const double* X; const double* xv;
-  const double *E0, *E1; const double *e0, *e1;
-  const double* J; const double* jv;
-  const double* base; const double* vbase;
-  double* out; double* vout;
+  In Am0, Am1;   // A operand of the matrix product (Am1: mid-point partner or none)
+  In Av0, Av1;   // A of the vector recursion
+  In X, xv;
+  In E0, E1, e0, e1;
+  In J, jv;
+  In base, vbase;
+  Out out, vout;
   int kstore, final_mode; double cx, cf;
 };
 
-StageArgs stage_args(int D, const Work& w, const StageSpec& s) {
+StageArgs stage_args(const LdCall& c, const Work& w, const StageSpec& s) {
   StageArgs a{};
+  const int D = c.D;
   a.D = D; a.row0 = 0; a.Mp = D; a.cw = D; a.fwd = s.fwd ? 1 : 0; a.kstore = s.kstore; a.final = s.final_mode;
-  a.sym_ok = literal_products ? 0 : 1;
-  a.mid_e = s.E1 != nullptr; a.has_j = s.J != nullptr; a.cx = s.cx; a.cf = s.cf;
-  a.W = w.W; a.Wcol = literal_products ? w.W2 : w.W; a.E0 = s.E0; a.E1 = s.E1; a.J = s.J; a.base = s.base; a.K1 = w.K1; a.K23 = w.K23; a.out = s.out;
-  a.A0 = s.Av0; a.A1 = s.Av1; a.lda = D; a.mid_a = s.Av1 != nullptr; a.x = s.xv;
-  a.e0 = s.e0; a.e1 = s.e1; a.mid_ev = s.e1 != nullptr; a.jv = s.jv; a.vbase = s.vbase;
-  a.k1v = w.k1v; a.k23v = w.k23v; a.vout = s.vout;
-  if (g_batch.nb > 1) {
-    a.nb = g_batch.nb;
-    a.zW = zs(a.W); a.zE = zs(a.E0); a.zJ = zs(a.J); a.zBase = zs(a.base); a.zK = zs(a.K1); a.zOut = zs(a.out);
-    a.zA = zs(a.A0); a.zX = zs(a.x); a.zEv = zs(a.e0); a.zJv = zs(a.jv); a.zVb = zs(a.vbase); a.zKv = zs(a.k1v); a.zVo = zs(a.vout);
-  }
+  a.sym_ok = c.literal ? 0 : 1;
+  a.mid_e = s.E1.rows != nullptr; a.has_j = s.J.rows != nullptr; a.cx = s.cx; a.cf = s.cf;
+  a.W = w.W.rows; a.Wcol = c.literal ? w.W2.rows : w.W.rows; a.E0 = s.E0.rows; a.E1 = s.E1.rows; a.J = s.J.rows; a.base = s.base.rows;
+  a.K1 = w.K1.rows; a.K23 = w.K23.rows; a.out = s.out.rows;
+  a.A0 = s.Av0.rows; a.A1 = s.Av1.rows; a.lda = D; a.mid_a = s.Av1.rows != nullptr; a.x = s.xv.rows;
+  a.e0 = s.e0.rows; a.e1 = s.e1.rows; a.mid_ev = s.e1.rows != nullptr; a.jv = s.jv.rows; a.vbase = s.vbase.rows;
+  a.k1v = w.k1v.rows; a.k23v = w.k23v.rows; a.vout = s.vout.rows;
+  a.nb = c.nb;         // (the partner of a mid-point pair, and W2 beside W, have their operand's stride)
+  a.zW = w.W.stride; a.zE = s.E0.stride; a.zJ = s.J.stride; a.zBase = s.base.stride; a.zK = w.K1.stride; a.zOut = s.out.stride;
+  a.zA = s.Av0.stride; a.zX = s.xv.stride; a.zEv = s.e0.stride; a.zJv = s.jv.stride; a.zVb = s.vbase.stride; a.zKv = w.k1v.stride; a.zVo = s.vout.stride;
   return a;
 }
 
-hipError_t run_stage(int D, const Work& w, const StageSpec& s, hipStream_t st, MidCache* mc = nullptr) {
-  const double *ga0 = s.Am0, *ga1 = s.Am1;
+hipError_t run_stage(const LdCall& c, const Work& w, const StageSpec& s, MidCache* mc = nullptr) {
+  const int D = c.D;
+  hipStream_t st = c.st;
+  In ga0 = s.Am0, ga1 = s.Am1;
   // Which implementation of the stage (measured on one box, fused sweep, ms: two kernels / k_stage_prod / k_stage_wide,
   // profiles/r05d_stage_versions_ab.txt -- D = 72: 40.4 / 25.4 / 38.4; 128: 39.9 / 29.7 / 36.9; 200: 63.5 / 43.3 / 52.9; 256: 54.1 / 47.9 /
   // 50.7; 384: 35.1 / - / 34.4; 512: 44.0 / - / 44.0; 8 x D = 128: 57.0 / - / 51.3; 640: 26.3 / - / 27.8; 768: 39.5 / - / 38.3; 1000:
@@ -712,159 +708,152 @@ hipError_t run_stage(int D, const Work& w, const StageSpec& s, hipStream_t st, M
   // throughput version leads there by 2-3 % at D = 384 and 768 only and trails by 4-8 % at ten other sizes -- and the throughput
   // version for everything else that is eligible: ragged D, whose product is the bounds-checked 8-byte kernel, and batched contexts
   // of mid-size problems.
-  const bool fused_ok = !use_library_gemm && !literal_products;
+  const bool fused_ok = !c.library_gemm && !c.literal;
   const int nt_ = (D + TS - 1) / TS;
   const bool wide = fused_ok && D % 2 == 0 && D <= stage_wide_max_d() && (D % 64 != 0 || D < kStageWideFullTileD || getenv("VGPA_STAGE_WIDE")) && (size_t)D * D * 8 < 0x7ff00000u &&
-                    (reinterpret_cast<uintptr_t>(s.X) & 15u) == 0 && (reinterpret_cast<uintptr_t>(s.Am0) & 15u) == 0 &&
-                    (!s.Am1 || (reinterpret_cast<uintptr_t>(s.Am1) & 15u) == 0) && zs(s.X) % 2 == 0 && zs(s.Am0) % 2 == 0;
+                    (reinterpret_cast<uintptr_t>(s.X.rows) & 15u) == 0 && (reinterpret_cast<uintptr_t>(s.Am0.rows) & 15u) == 0 &&
+                    (!s.Am1.rows || (reinterpret_cast<uintptr_t>(s.Am1.rows) & 15u) == 0) && s.X.stride % 2 == 0 && s.Am0.stride % 2 == 0;
   // (more pairs than that and no throughput version -- odd D: the latency version still beats the bounds-checked product)
-  if (fused_ok && D <= stage_prod_max_d() && ((long long)nt_ * (nt_ + 1) / 2 * g_batch.nb <= kStageProdMaxPairs || (!wide && D % 64 != 0))) {
-    StageArgs a = stage_args(D, w, s);
-    a.M0 = s.Am0; a.M1 = s.Am1; a.Xm = s.X; a.zM = zs(s.Am0); a.zXm = zs(s.X);
+  if (fused_ok && D <= stage_prod_max_d() && ((long long)nt_ * (nt_ + 1) / 2 * c.nb <= kStageProdMaxPairs || (!wide && D % 64 != 0))) {
+    StageArgs a = stage_args(c, w, s);
+    a.M0 = s.Am0.rows; a.M1 = s.Am1.rows; a.Xm = s.X.rows; a.zM = s.Am0.stride; a.zXm = s.X.stride;
     return launch_stage_fused(0, a, st);
   }
-  if (ga1 && mc) {
-    if (mc->a0 != ga0 || mc->a1 != ga1) {
+  if (ga1.rows && mc) {
+    if (mc->a0.rows != ga0.rows || mc->a1.rows != ga1.rows) {
       const size_t n = (size_t)D * D;
       const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-      hipLaunchKernelGGL(k_mid, dim3(blocks, g_batch.nb), dim3(256), 0, st, ga0, ga1, w.AM, n, zs(ga0), zs(w.AM));
+      hipLaunchKernelGGL(k_mid, dim3(blocks, c.nb), dim3(256), 0, st, ga0.rows, ga1.rows, w.AM.rows, n, ga0.stride, w.AM.stride);
       mc->a0 = ga0; mc->a1 = ga1;
     }
-    ga0 = w.AM; ga1 = nullptr;
+    ga0 = w.AM; ga1 = none;
   }
-  if (wide && !ga1) {                     // products + element-wise stage in one kernel (the mid-point operand formed above)
-    StageArgs a = stage_args(D, w, s);
-    a.M0 = ga0; a.Xm = s.X; a.zM = zs(ga0); a.zXm = zs(s.X);
+  if (wide && !ga1.rows) {                // products + element-wise stage in one kernel (the mid-point operand formed above)
+    StageArgs a = stage_args(c, w, s);
+    a.M0 = ga0.rows; a.Xm = s.X.rows; a.zM = ga0.stride; a.zXm = s.X.stride;
     return launch_stage_fused(1, a, st);
   }
   hipError_t e;
-  if (use_library_gemm && !ga1 && g_batch.nb == 1 && !literal_products) {
+  if (c.library_gemm && !ga1.rows && c.nb == 1 && !c.literal) {
     // plain GEMM, one rank: cw = D is plain row-major.  Backward: W' = A^T.Psi would be a transposed-A product (slow in
     // the library at D = 1024); Psi is symmetric, so Z = Psi.A = W'^T is computed instead -- the stage kernel uses W'
     // and W'^T symmetrically (R = -G + W' + W'^T), only the order of its two additions changes.
     // (measured: the library's transposed-A product runs at 31 / 66 / 74 TFLOP/s for D = 1024 / 2048 / 4096, its plain
     // product at 50 / 60 / 67 -- the detour pays below D = 2048 only)
-    e = s.fwd ? library_gemm(false, D, D, D, ga0, D, s.X, D, w.W, D, st)
-              : (D < 2048 ? library_gemm(false, D, D, D, s.X, D, ga0, D, w.W, D, st)
-                          : library_gemm(true, D, D, D, ga0, D, s.X, D, w.W, D, st));
+    e = s.fwd ? library_gemm(false, D, D, D, ga0.rows, D, s.X.rows, D, w.W.rows, D, st)
+              : (D < 2048 ? library_gemm(false, D, D, D, s.X.rows, D, ga0.rows, D, w.W.rows, D, st)
+                          : library_gemm(true, D, D, D, ga0.rows, D, s.X.rows, D, w.W.rows, D, st));
   } else {
-    GemmArgs g{D, D, D, ga0, ga1, D, s.X, D, w.W, D};
-    g.nb = g_batch.nb; g.zA = zs(ga0); g.zB = zs(s.X); g.zC = zs(w.W);
+    GemmArgs g{D, D, D, ga0.rows, ga1.rows, D, s.X.rows, D, w.W.rows, D};
+    g.nb = c.nb; g.zA = ga0.stride; g.zB = s.X.stride; g.zC = w.W.stride;
     e = launch_gemm(!s.fwd, g, st);
   }
   if (e != hipSuccess) return e;
-  if (literal_products) {
+  if (c.literal) {
     const int nt = (D + 31) / 32;
-    hipLaunchKernelGGL(k_transpose, dim3(nt, nt, g_batch.nb), dim3(256), 0, st, s.X, w.XT, D, zs(s.X), zs(w.XT));
-    GemmArgs g2{D, D, D, ga0, ga1, D, w.XT, D, w.W2, D};
-    g2.nb = g_batch.nb; g2.zA = zs(ga0); g2.zB = zs(w.XT); g2.zC = zs(w.W2);
+    hipLaunchKernelGGL(k_transpose, dim3(nt, nt, c.nb), dim3(256), 0, st, s.X.rows, w.XT.rows, D, s.X.stride, w.XT.stride);
+    GemmArgs g2{D, D, D, ga0.rows, ga1.rows, D, w.XT.rows, D, w.W2.rows, D};
+    g2.nb = c.nb; g2.zA = ga0.stride; g2.zB = w.XT.stride; g2.zC = w.W2.stride;
     e = launch_gemm(!s.fwd, g2, st);
     if (e != hipSuccess) return e;
   }
-  const StageArgs a = stage_args(D, w, s);
+  const StageArgs a = stage_args(c, w, s);
   return launch_stage(a, st);
 }
 }  // namespace
 
 #define LD_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return e_; } while (0)
 
-hipError_t ld_solve_fwd(int method, double dt, int D, int Np, const double* A, const double* b, const double* m0,
-                        const double* S0, const double* Sigma, double* m, double* S, double* ws, hipStream_t st) {
+hipError_t ld_solve_fwd(const LdCall& c, int Np, In A, In b, In m0, In S0, In Sigma, Out m, Out S) {
+  const int method = c.method, D = c.D;
   const size_t DD = (size_t)D * D;
-  const Work w = carve_work(ws, D);
-  const double h = 0.5 * dt;
-  for (int p = 0; p < g_batch.nb; p++) {
-    LD_TRY(hipMemcpyAsync(S + p * zs(S), S0 + p * zs(S0), DD * sizeof(double), hipMemcpyDeviceToDevice, st));   // (per-problem S0 / m0:
-    LD_TRY(hipMemcpyAsync(m + p * zs(m), m0 + p * zs(m0), D * sizeof(double), hipMemcpyDeviceToDevice, st));     //  registered ranges)
+  const Work w = carve_work(c.ws, D);
+  const double dt = c.dt, h = 0.5 * dt;
+  for (int p = 0; p < c.nb; p++) {
+    LD_TRY(hipMemcpyAsync(S.of(p), S0.of(p), DD * sizeof(double), hipMemcpyDeviceToDevice, c.st));
+    LD_TRY(hipMemcpyAsync(m.of(p), m0.of(p), D * sizeof(double), hipMemcpyDeviceToDevice, c.st));
   }
   for (int k = 0; k < Np - 1; k++) {
-    const double *Ak = A + k * DD, *Ak1 = Ak + DD, *bk = b + (size_t)k * D, *bk1 = bk + D;
-    const double *Sk = S + k * DD, *mk = m + (size_t)k * D;
-    double *Sn = S + (k + 1) * DD, *mn = m + (size_t)(k + 1) * D;
+    const In Ak = A + k * DD, Ak1 = Ak + DD, bk = b + (size_t)k * D, bk1 = bk + D;
+    const In Sk = S + k * DD, mk = m + (size_t)k * D;
+    const Out Sn = S + (k + 1) * DD, mn = m + (size_t)(k + 1) * D;
     StageSpec s{};
     MidCache mc{};
     s.fwd = true; s.E0 = Sigma; s.base = Sk; s.vbase = mk;
-    auto set = [&](const double* am0, const double* am1, const double* av0, const double* av1, const double* X,
-                   const double* xv, const double* e0, const double* e1, double* out, double* vout, int ks, int fin,
-                   double cx, double cf) {
+    auto set = [&](In am0, In am1, In av0, In av1, In X, In xv, In e0, In e1, Out out, Out vout, int ks, int fin, double cx, double cf) {
       s.Am0 = am0; s.Am1 = am1; s.Av0 = av0; s.Av1 = av1; s.X = X; s.xv = xv; s.e0 = e0; s.e1 = e1; s.out = out;
       s.vout = vout; s.kstore = ks; s.final_mode = fin; s.cx = cx; s.cf = cf;
     };
     if (method == VGPA_ODE_EULER) {
-      set(Ak, nullptr, Ak, nullptr, Sk, mk, bk, nullptr, Sn, mn, 0, 1, 0.0, dt); LD_TRY(run_stage(D, w, s, st, &mc));
+      set(Ak, none, Ak, none, Sk, mk, bk, none, Sn, mn, 0, 1, 0.0, dt); LD_TRY(run_stage(c, w, s, &mc));
     } else if (method == VGPA_ODE_HEUN) {
-      set(Ak, nullptr, Ak, nullptr, Sk, mk, bk, nullptr, w.XA, w.xvA, 1, 0, dt, 0.0); LD_TRY(run_stage(D, w, s, st, &mc));
-      set(Ak1, nullptr, Ak1, nullptr, w.XA, w.xvA, bk1, nullptr, Sn, mn, 0, 2, 0.0, h); LD_TRY(run_stage(D, w, s, st, &mc));
+      set(Ak, none, Ak, none, Sk, mk, bk, none, w.XA, w.xvA, 1, 0, dt, 0.0); LD_TRY(run_stage(c, w, s, &mc));
+      set(Ak1, none, Ak1, none, w.XA, w.xvA, bk1, none, Sn, mn, 0, 2, 0.0, h); LD_TRY(run_stage(c, w, s, &mc));
     } else if (method == VGPA_ODE_RK2) {
       // covariance predictor: S_k stands in for A_k (reference quirk, runge_kutta2.py:96); mean predictor: A_k
-      set(Sk, nullptr, Ak, nullptr, Sk, mk, bk, nullptr, w.XA, w.xvA, 0, 0, h, 0.0); LD_TRY(run_stage(D, w, s, st, &mc));
-      set(Ak, Ak1, Ak, Ak1, w.XA, w.xvA, bk1, bk, Sn, mn, 0, 1, 0.0, dt); LD_TRY(run_stage(D, w, s, st, &mc));
+      set(Sk, none, Ak, none, Sk, mk, bk, none, w.XA, w.xvA, 0, 0, h, 0.0); LD_TRY(run_stage(c, w, s, &mc));
+      set(Ak, Ak1, Ak, Ak1, w.XA, w.xvA, bk1, bk, Sn, mn, 0, 1, 0.0, dt); LD_TRY(run_stage(c, w, s, &mc));
     } else {
-      set(Ak, nullptr, Ak, nullptr, Sk, mk, bk, nullptr, w.XA, w.xvA, 1, 0, h, 0.0); LD_TRY(run_stage(D, w, s, st, &mc));
-      set(Ak, Ak1, Ak, Ak1, w.XA, w.xvA, bk1, bk, w.XB, w.xvB, 2, 0, h, 0.0); LD_TRY(run_stage(D, w, s, st, &mc));
-      set(Ak, Ak1, Ak, Ak1, w.XB, w.xvB, bk1, bk, w.XA, w.xvA, 3, 0, dt, 0.0); LD_TRY(run_stage(D, w, s, st, &mc));
-      set(Ak1, nullptr, Ak1, nullptr, w.XA, w.xvA, bk1, nullptr, Sn, mn, 0, 3, 0.0, dt); LD_TRY(run_stage(D, w, s, st, &mc));
+      set(Ak, none, Ak, none, Sk, mk, bk, none, w.XA, w.xvA, 1, 0, h, 0.0); LD_TRY(run_stage(c, w, s, &mc));
+      set(Ak, Ak1, Ak, Ak1, w.XA, w.xvA, bk1, bk, w.XB, w.xvB, 2, 0, h, 0.0); LD_TRY(run_stage(c, w, s, &mc));
+      set(Ak, Ak1, Ak, Ak1, w.XB, w.xvB, bk1, bk, w.XA, w.xvA, 3, 0, dt, 0.0); LD_TRY(run_stage(c, w, s, &mc));
+      set(Ak1, none, Ak1, none, w.XA, w.xvA, bk1, none, Sn, mn, 0, 3, 0.0, dt); LD_TRY(run_stage(c, w, s, &mc));
     }
   }
   return hipSuccess;
 }
 
 // One backward step t -> t-1.  At/Am = A_t / A_{t-1}, Gt/Gm = dEsde_dS at t / t-1, gt/gmm = dEsde_dm at t / t-1,
-// (Pt, lt) = (Psi_t, lam_t), (Pn, ln) = where (Psi_{t-1}, lam_{t-1}) go, (Jn, jn) = jump of index t-1 or nullptr.
-hipError_t ld_bwd_step(int method, double dt, int D, const double* At, const double* Am, const double* Gt, const double* Gm,
-                       const double* gt, const double* gmm, const double* Pt, const double* lt, double* Pn, double* ln,
-                       const double* Jn, const double* jn, double* ws, hipStream_t st) {
-  const Work w = carve_work(ws, D);
-  const double h = 0.5 * dt;
+// (Pt, lt) = (Psi_t, lam_t), (Pn, ln) = where (Psi_{t-1}, lam_{t-1}) go, (Jn, jn) = jump of index t-1 or none.
+hipError_t ld_bwd_step(const LdCall& c, In At, In Am, In Gt, In Gm, In gt, In gmm, In Pt, In lt, Out Pn, Out ln, In Jn, In jn) {
+  const int method = c.method;
+  const Work w = carve_work(c.ws, c.D);
+  const double dt = c.dt, h = 0.5 * dt;
   StageSpec s{};
   MidCache mc{};
   s.fwd = false; s.base = Pt; s.vbase = lt;
-  auto set = [&](const double* a0, const double* a1, const double* X, const double* xv, const double* E0,
-                 const double* E1, const double* e0, const double* e1, double* out, double* vout, int ks, int fin,
-                 double cx, double cf, bool jump) {
+  auto set = [&](In a0, In a1, In X, In xv, In E0, In E1, In e0, In e1, Out out, Out vout, int ks, int fin, double cx, double cf, bool jump) {
     s.Am0 = a0; s.Am1 = a1; s.Av0 = a0; s.Av1 = a1; s.X = X; s.xv = xv; s.E0 = E0; s.E1 = E1; s.e0 = e0; s.e1 = e1;
     s.out = out; s.vout = vout; s.kstore = ks; s.final_mode = fin; s.cx = cx; s.cf = cf;
-    s.J = jump ? Jn : nullptr; s.jv = jump ? jn : nullptr;
+    s.J = jump ? Jn : none; s.jv = jump ? jn : none;
   };
   if (method == VGPA_ODE_EULER) {
-    set(At, nullptr, Pt, lt, Gt, nullptr, gt, nullptr, Pn, ln, 0, 1, 0.0, dt, true); LD_TRY(run_stage(D, w, s, st, &mc));
+    set(At, none, Pt, lt, Gt, none, gt, none, Pn, ln, 0, 1, 0.0, dt, true); LD_TRY(run_stage(c, w, s, &mc));
   } else if (method == VGPA_ODE_HEUN) {
-    set(At, nullptr, Pt, lt, Gt, nullptr, gt, nullptr, w.XA, w.xvA, 1, 0, dt, 0.0, false); LD_TRY(run_stage(D, w, s, st, &mc));
-    set(Am, nullptr, w.XA, w.xvA, Gm, nullptr, gmm, nullptr, Pn, ln, 0, 2, 0.0, h, true); LD_TRY(run_stage(D, w, s, st, &mc));
+    set(At, none, Pt, lt, Gt, none, gt, none, w.XA, w.xvA, 1, 0, dt, 0.0, false); LD_TRY(run_stage(c, w, s, &mc));
+    set(Am, none, w.XA, w.xvA, Gm, none, gmm, none, Pn, ln, 0, 2, 0.0, h, true); LD_TRY(run_stage(c, w, s, &mc));
   } else if (method == VGPA_ODE_RK2) {
-    set(At, nullptr, Pt, lt, Gt, nullptr, gt, nullptr, w.XA, w.xvA, 0, 0, h, 0.0, false); LD_TRY(run_stage(D, w, s, st, &mc));
-    set(Am, At, w.XA, w.xvA, Gt, Gm, gt, gmm, Pn, ln, 0, 1, 0.0, dt, true); LD_TRY(run_stage(D, w, s, st, &mc));
+    set(At, none, Pt, lt, Gt, none, gt, none, w.XA, w.xvA, 0, 0, h, 0.0, false); LD_TRY(run_stage(c, w, s, &mc));
+    set(Am, At, w.XA, w.xvA, Gt, Gm, gt, gmm, Pn, ln, 0, 1, 0.0, dt, true); LD_TRY(run_stage(c, w, s, &mc));
   } else {
-    set(At, nullptr, Pt, lt, Gt, nullptr, gt, nullptr, w.XA, w.xvA, 1, 0, h, 0.0, false); LD_TRY(run_stage(D, w, s, st, &mc));
-    set(Am, At, w.XA, w.xvA, Gt, Gm, gt, gmm, w.XB, w.xvB, 2, 0, h, 0.0, false); LD_TRY(run_stage(D, w, s, st, &mc));
-    set(Am, At, w.XB, w.xvB, Gt, Gm, gt, gmm, w.XA, w.xvA, 3, 0, dt, 0.0, false); LD_TRY(run_stage(D, w, s, st, &mc));
-    set(Am, nullptr, w.XA, w.xvA, Gm, nullptr, gmm, nullptr, Pn, ln, 0, 3, 0.0, dt, true); LD_TRY(run_stage(D, w, s, st, &mc));
+    set(At, none, Pt, lt, Gt, none, gt, none, w.XA, w.xvA, 1, 0, h, 0.0, false); LD_TRY(run_stage(c, w, s, &mc));
+    set(Am, At, w.XA, w.xvA, Gt, Gm, gt, gmm, w.XB, w.xvB, 2, 0, h, 0.0, false); LD_TRY(run_stage(c, w, s, &mc));
+    set(Am, At, w.XB, w.xvB, Gt, Gm, gt, gmm, w.XA, w.xvA, 3, 0, dt, 0.0, false); LD_TRY(run_stage(c, w, s, &mc));
+    set(Am, none, w.XA, w.xvA, Gm, none, gmm, none, Pn, ln, 0, 3, 0.0, dt, true); LD_TRY(run_stage(c, w, s, &mc));
   }
   return hipSuccess;
 }
 
-// Whole backward recursion with every Psi_t stored.  Jumps: dense arrays (jm, js: [Np][D], [Np][D][D]) or, when
-// obs_idx != nullptr, sparse ones (obs_idx[t] = n >= 0: jump vector jm[n][:] and the constant matrix js).
-hipError_t ld_solve_bwd(int method, double dt, int D, int Np, const double* A, const double* gm, const double* gs,
-                        const double* jm, const double* js, double* lam, double* psi, double* ws, hipStream_t st,
-                        const int32_t* obs_idx) {
+// Whole backward recursion with every Psi_t stored, the jump of each step from LdJumps: its dense row t - 1, or the sparse one of
+// the observation at grid point t - 1 (none where obs_idx[t - 1] < 0).
+hipError_t ld_solve_bwd(const LdCall& c, int Np, In A, In gm, In gs, const LdJumps& jumps, Out lam, Out psi) {
+  const int D = c.D;
   const size_t DD = (size_t)D * D;
-  for (int p = 0; p < g_batch.nb; p++) {
-    LD_TRY(hipMemsetAsync(psi + p * zs(psi) + (size_t)(Np - 1) * DD, 0, DD * sizeof(double), st));
-    LD_TRY(hipMemsetAsync(lam + p * zs(lam) + (size_t)(Np - 1) * D, 0, D * sizeof(double), st));
+  for (int p = 0; p < c.nb; p++) {
+    LD_TRY(hipMemsetAsync(psi.of(p) + (size_t)(Np - 1) * DD, 0, DD * sizeof(double), c.st));
+    LD_TRY(hipMemsetAsync(lam.of(p) + (size_t)(Np - 1) * D, 0, D * sizeof(double), c.st));
   }
   for (int t = Np - 1; t > 0; t--) {
-    const double *Jn, *jn;
-    if (obs_idx) {
-      const int n = obs_idx[t - 1];
-      Jn = n >= 0 ? js : nullptr;
-      jn = n >= 0 ? jm + (size_t)n * D : nullptr;
+    In Jn, jn;
+    if (jumps.obs_idx) {
+      const int n = jumps.obs_idx[t - 1];
+      Jn = n >= 0 ? jumps.js : none;
+      jn = n >= 0 ? jumps.jm + (size_t)n * D : none;
     } else {
-      Jn = js + (size_t)(t - 1) * DD; jn = jm + (size_t)(t - 1) * D;
+      Jn = jumps.js + (size_t)(t - 1) * DD; jn = jumps.jm + (size_t)(t - 1) * D;
     }
-    LD_TRY(ld_bwd_step(method, dt, D, A + t * DD, A + (t - 1) * DD, gs + t * DD, gs + (t - 1) * DD, gm + (size_t)t * D,
-                       gm + (size_t)(t - 1) * D, psi + t * DD, lam + (size_t)t * D, psi + (t - 1) * DD,
-                       lam + (size_t)(t - 1) * D, Jn, jn, ws, st));
+    LD_TRY(ld_bwd_step(c, A + t * DD, A + (t - 1) * DD, gs + t * DD, gs + (t - 1) * DD, gm + (size_t)t * D, gm + (size_t)(t - 1) * D,
+                       psi + t * DD, lam + (size_t)t * D, psi + (t - 1) * DD, lam + (size_t)(t - 1) * D, Jn, jn));
   }
   return hipSuccess;
 }

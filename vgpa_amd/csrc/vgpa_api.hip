@@ -14,10 +14,7 @@ using namespace vgpa;
 namespace {
 thread_local std::string g_create_error;
 
-// one input of a batched context: problem p reads of(p) = rows + p * stride (stride 0: one row, shared by the batch)
-template <typename T> struct Rows { const T* rows = nullptr; size_t stride = 0; const T* of(int p) const { return rows + (size_t)p * stride; } };
-
-// Where every problem reads every batch input.  vgpa_create points it at the shared values, vgpa_set_problem_data /
+// Where every problem reads every batch input (Rows: vgpa_internal.h).  vgpa_create points it at the shared values, vgpa_set_problem_data /
 // vgpa_set_problem_params / vgpa_set_prior_energy at per-problem rows; nothing else writes it, and the argument builders copy from it.
 // theta, sigma1, e0 and 1 / sigma^2 have no shared device row: null rows, and the kernels take the shared value (vgpa_ctx).
 struct BatchInputs {
@@ -423,7 +420,7 @@ static void make_plan(vgpa_ctx* c) {
   c->plan = p;
 }
 
-// the small-D steppers share OdeArgs (the large-D drivers take their arrays one by one: run_fwd / run_bwd call them)
+// the small-D steppers share OdeArgs (the large-D drivers take their arrays one by one, each with its stride: run_fwd / run_bwd call them)
 static hipError_t launch_stepper(Stepper k, int method, bool fwd, const OdeArgs& a, hipStream_t st) {
   switch (k) {
     case Stepper::Lane: return launch_ode_small(method, fwd, a, st);
@@ -440,30 +437,11 @@ static int ensure_ld_ws(vgpa_ctx* c) {
   return dev_alloc(c, &c->d_ld_ws, (size_t)c->B * ld::ld_workspace_doubles(c->D));
 }
 
-// D > 64 with several problems per context: the per-stage kernels take the batch in grid.z; the drivers look every pointer's
-// per-problem stride up by address (ld::BatchMap).  RAII: the map is thread-local state of large_d.hip.
-struct LdLiteral {
-  explicit LdLiteral(bool on_) : on(on_) { if (on) ld::ld_set_literal_products(true); }
-  ~LdLiteral() { if (on) ld::ld_set_literal_products(false); }
-  bool on;
-};
-struct LdBatch {
-  explicit LdBatch(vgpa_ctx* c) : on(c->B > 1) {
-    if (!on) return;
-    ld::BatchMap m;
-    m.nb = c->B;
-    const size_t NpD = (size_t)c->Np * c->D, NpDD = (size_t)c->Np * c->DD;
-    m.add(c->xcur, c->len_x);
-    m.add(c->d_m, NpD); m.add(c->d_S, NpDD); m.add(c->d_lam, NpD); m.add(c->d_psi, NpDD);
-    m.add(c->d_dEm, NpD); m.add(c->d_dEs, NpDD);
-    m.add(c->d_jm, (size_t)c->M * c->D); m.add(c->d_jm_dense, NpD); m.add(c->d_js_dense, NpDD);
-    m.add(c->d_ld_ws, ld::ld_workspace_doubles(c->D));
-    m.add(c->in.m0.rows, c->in.m0.stride); m.add(c->in.S0.rows, c->in.S0.stride); m.add(c->in.Sigma.rows, c->in.Sigma.stride);
-    ld::ld_set_batch(&m);
-  }
-  ~LdBatch() { if (on) ld::ld_set_batch(nullptr); }
-  bool on;
-};
+// One call of the D > 64 drivers (ld::LdCall): the whole batch in grid.z of the per-stage kernels, every array handed over with its
+// per-problem stride.  literal: non-symmetric inputs, both products of the slope formed literally (ode_solver.py:60,94).
+static ld::LdCall ld_call(vgpa_ctx* c, bool literal) {
+  return {c->cfg.method, c->cfg.dt, c->D, c->B, literal, (c->cfg.flags & VGPA_FLAG_LIBRARY_GEMM) != 0, c->d_ld_ws, c->stream};
+}
 
 // what every stepping kernel's OdeArgs starts with: the sizes, x and the moment histories
 static OdeArgs ode_args(vgpa_ctx* c) {
@@ -493,16 +471,14 @@ static void sparse_jumps(vgpa_ctx* c, OdeArgs& a) {
 
 // sym: Plan::sym_inputs for the fused sweep (the stepper is then Plan::fwd), the symmetry of the caller's arrays for vgpa_solve_fwd
 static int run_fwd(vgpa_ctx* c, Rows<double> m0, Rows<double> S0, Rows<double> Sigma, bool sym) {
-  ld::use_library_gemm = (c->cfg.flags & VGPA_FLAG_LIBRARY_GEMM) != 0;
   c->ms_valid = true;                  // (every path below writes the [B][Np] arrays m / S)
   const Stepper k = stepper(c, true, sym);
   if (k == Stepper::LargeD) {
     int rc = ensure_ld_ws(c);
     if (rc) return rc;
-    LdBatch batch(c);
-    LdLiteral literal(!sym);             // non-symmetric s0 / sigma: both products of the slope literally (ode_solver.py:60)
-    LAUNCH_TRY(c, "large-D forward sweep", ld::ld_solve_fwd(c->cfg.method, c->cfg.dt, c->D, c->Np, ctx_A(c), ctx_b(c), m0.rows, S0.rows,
-                                                            Sigma.rows, c->d_m, c->d_S, c->d_ld_ws, c->stream));
+    const size_t NpD = (size_t)c->Np * c->D, NpDD = (size_t)c->Np * c->DD;
+    LAUNCH_TRY(c, "large-D forward sweep", ld::ld_solve_fwd(ld_call(c, !sym), c->Np, {ctx_A(c), c->len_x}, {ctx_b(c), c->len_x}, m0, S0, Sigma,
+                                                            {c->d_m, NpD}, {c->d_S, NpDD}));
     return VGPA_OK;
   }
   OdeArgs a = fwd_args(c, m0, S0, Sigma);
@@ -516,7 +492,6 @@ static ObsArgs obs_args(vgpa_ctx* c);
 // sym: as in run_fwd (dense_jumps: vgpa_solve_bwd's call, with the caller's arrays).  g_fused: the backward kernel assembles the
 // gradient into it (Plan::grad_in_bwd contexts; Psi_t is then not stored)
 static int run_bwd(vgpa_ctx* c, bool dense_jumps, bool sym, double* g_fused = nullptr) {
-  ld::use_library_gemm = (c->cfg.flags & VGPA_FLAG_LIBRARY_GEMM) != 0;
   int rc;
   if (g_fused && (dense_jumps || !c->plan.grad_in_bwd || !c->s_packed)) return fail(c, VGPA_ERR_STATE, "fused gradient assembly asked of a context without it");
   if ((rc = ensure(c, &c->d_psi, (size_t)c->B * c->Np * c->DD))) return rc;
@@ -525,14 +500,12 @@ static int run_bwd(vgpa_ctx* c, bool dense_jumps, bool sym, double* g_fused = nu
   const Stepper k = stepper(c, false, sym);
   if (k == Stepper::LargeD) {
     if ((rc = ensure_ld_ws(c))) return rc;
-    LdBatch batch(c);
-    LdLiteral literal(!sym);             // non-symmetric dEsde_ds / dEobs_ds (ode_solver.py:94)
-    // operator-level calls bring dense jump arrays; the fused sweep uses the sparse ones (obs index on the host)
-    LAUNCH_TRY(c, "large-D backward sweep", dense_jumps
-        ? ld::ld_solve_bwd(c->cfg.method, c->cfg.dt, c->D, c->Np, ctx_A(c), c->d_dEm, c->d_dEs, c->d_jm_dense, c->d_js_dense,
-                           c->d_lam, c->d_psi, c->d_ld_ws, c->stream)
-        : ld::ld_solve_bwd(c->cfg.method, c->cfg.dt, c->D, c->Np, ctx_A(c), c->d_dEm, c->d_dEs, c->d_jm, c->d_jsc,
-                           c->d_lam, c->d_psi, c->d_ld_ws, c->stream, c->h_obs_idx.data()));
+    const size_t NpD = (size_t)c->Np * c->D, NpDD = (size_t)c->Np * c->DD;
+    // operator-level calls bring dense jump arrays; the fused sweep uses the sparse ones (obs index on the host, one constant matrix)
+    const ld::LdJumps jumps = dense_jumps ? ld::LdJumps::dense({c->d_jm_dense, NpD}, {c->d_js_dense, NpDD})
+                                          : ld::LdJumps::sparse({c->d_jm, (size_t)c->M * c->D}, {c->d_jsc, 0}, c->h_obs_idx.data());
+    LAUNCH_TRY(c, "large-D backward sweep", ld::ld_solve_bwd(ld_call(c, !sym), c->Np, {ctx_A(c), c->len_x}, {c->d_dEm, NpD}, {c->d_dEs, NpDD}, jumps,
+                                                             {c->d_lam, NpD}, {c->d_psi, NpDD}));
     return VGPA_OK;
   }
   OdeArgs a = ode_args(c);   // (b, m, S: read only with grad_on)
@@ -690,7 +663,6 @@ static int run_grad(vgpa_ctx* c, double* g_dev) {
 // g_dev == nullptr: energy integrand only (what F needs).  Same kernels, same per-grid-point arithmetic as the
 // resident path, so the results are identical.
 static int stream_pass(vgpa_ctx* c, double* g_dev) {
-  ld::use_library_gemm = (c->cfg.flags & VGPA_FLAG_LIBRARY_GEMM) != 0;
   const int D = c->D, Np = c->Np, C = c->ld_chunk;
   const size_t DD = c->DD;
   int rc;
@@ -700,6 +672,7 @@ static int stream_pass(vgpa_ctx* c, double* g_dev) {
   if (g_dev && (rc = ensure(c, &c->d_psi_c, (size_t)(C + 1) * DD))) return rc;
   const double *A = ctx_A(c), *b = ctx_b(c);
   hipStream_t st = c->stream;
+  const ld::LdCall step = ld_call(c, false);      // (one problem: every operand of ld_bwd_step below has stride 0)
   int t1 = Np - 1;
   if (g_dev) HIP_TRY(c, hipMemsetAsync(c->d_lam + (size_t)t1 * D, 0, sizeof(double) * D, st));
   bool first = true;
@@ -715,11 +688,11 @@ static int stream_pass(vgpa_ctx* c, double* g_dev) {
       for (int t = t1; t > t0; t--) {
         const int k = t - t0;
         const int nobs = c->h_obs_idx[t - 1];
-        LAUNCH_TRY(c, "large-D backward step", ld::ld_bwd_step(c->cfg.method, c->cfg.dt, D, A + (size_t)t * DD, A + (size_t)(t - 1) * DD,
-                                                               c->d_dEs_c + (size_t)k * DD, c->d_dEs_c + (size_t)(k - 1) * DD, c->d_dEm + (size_t)t * D,
-                                                               c->d_dEm + (size_t)(t - 1) * D, c->d_psi_c + (size_t)k * DD, c->d_lam + (size_t)t * D,
-                                                               c->d_psi_c + (size_t)(k - 1) * DD, c->d_lam + (size_t)(t - 1) * D,
-                                                               nobs >= 0 ? c->d_jsc : nullptr, nobs >= 0 ? c->d_jm + (size_t)nobs * D : nullptr, c->d_ld_ws, st));
+        LAUNCH_TRY(c, "large-D backward step", ld::ld_bwd_step(step, {A + (size_t)t * DD}, {A + (size_t)(t - 1) * DD},
+                                                               {c->d_dEs_c + (size_t)k * DD}, {c->d_dEs_c + (size_t)(k - 1) * DD}, {c->d_dEm + (size_t)t * D},
+                                                               {c->d_dEm + (size_t)(t - 1) * D}, {c->d_psi_c + (size_t)k * DD}, {c->d_lam + (size_t)t * D},
+                                                               {c->d_psi_c + (size_t)(k - 1) * DD}, {c->d_lam + (size_t)(t - 1) * D},
+                                                               {nobs >= 0 ? c->d_jsc : nullptr}, {nobs >= 0 ? c->d_jm + (size_t)nobs * D : nullptr}));
       }
       // gradient of (t0, t1] -- and of t0 itself once the grid start is reached
       const int g0 = (t0 == 0) ? 0 : t0 + 1;
@@ -1374,7 +1347,6 @@ int vgpa_theta_gradient(vgpa_ctx* c, double* out) {
     if ((rc = ensure(c, &c->d_tg, BN))) return rc;
     if (D > kMaxSmallD) {
       if ((rc = ensure_lde_ws(c))) return rc;
-      ld::use_library_gemm = (c->cfg.flags & VGPA_FLAG_LIBRARY_GEMM) != 0;
       const size_t NpD = (size_t)Np * D, NpDD = (size_t)Np * c->DD;
       for (int p = 0; p < B; p++)
         LAUNCH_TRY(c, "large-D theta integrand", ld::lde_theta_integrand(D, Np, theta_of(c, p)[0], c->in.isg.of(p), ctx_A(c) + p * c->len_x,

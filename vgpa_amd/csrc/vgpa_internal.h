@@ -247,36 +247,49 @@ hipError_t launch_reduce(const ReduceArgs& a, hipStream_t st);
 hipError_t launch_trapz_multi(const double* e, int Np, int H, int batch, double dt, double* out, hipStream_t st);
 hipError_t launch_edf(const EnergyArgs& a, hipStream_t st);   // dense <df/dx> on request
 
+// One array of a batched context with its per-problem stride: problem p's row is of(p) = rows + p * stride (stride 0: one row, shared by
+// the batch).  `+ k` moves into every problem's row alike and keeps the stride.  OutRows: the same for an array the kernels write.
+template <typename T> struct Rows {
+  const T* rows = nullptr; size_t stride = 0;
+  const T* of(int p) const { return rows + (size_t)p * stride; }
+  Rows operator+(size_t k) const { return {rows + k, stride}; }
+};
+template <typename T> struct OutRows {
+  T* rows = nullptr; size_t stride = 0;
+  T* of(int p) const { return rows + (size_t)p * stride; }
+  OutRows operator+(size_t k) const { return {rows + k, stride}; }
+  operator Rows<T>() const { return {rows, stride}; }
+};
+
 // large-D (per-stage GEMM) single-rank drivers, large_d.hip
 namespace ld {
-// address ranges of the arrays of a batched context and their per-problem strides (ld_set_batch; see large_d.hip)
-struct BatchMap {
-  int nb = 1, n = 0;
-  struct R { const double* lo; const double* hi; size_t stride; } r[16];
-  void add(const double* base, size_t per_problem) {
-    if (base && per_problem && n < 16) { r[n].lo = base; r[n].hi = base + (size_t)nb * per_problem; r[n].stride = per_problem; n++; }
-  }
-  size_t stride(const double* p) const {
-    for (int i = 0; i < n; i++) if (p >= r[i].lo && p < r[i].hi) return r[i].stride;
-    return 0;
-  }
+// operands of the single-rank drivers: every array comes with its per-problem stride, stated by the caller (0: shared by the batch)
+using In = Rows<double>;
+using Out = OutRows<double>;
+// One call of the single-rank drivers.  nb problems run side by side in grid.z of every launch; problem p's workspace is
+// ws + p * ld_workspace_doubles(D).
+struct LdCall {
+  int method; double dt; int D, nb;
+  bool literal;        // non-symmetric inputs: both products of the slope are formed literally (large_d.hip, run_stage)
+  bool library_gemm;   // the plain stage GEMM goes to rocBLAS (lib_gemm.cpp) where it can: one problem, symmetric inputs
+  double* ws;
+  hipStream_t st;
 };
-void ld_set_batch(const BatchMap* map_or_null);      // thread-local; nullptr = one problem
-void ld_set_literal_products(bool on);               // thread-local: non-symmetric inputs, both products of the slope literally
+// jumps of the backward recursion: dense arrays over the grid (operator level), or the sparse ones of the observations
+struct LdJumps {
+  In jm, js;                          // dense: [Np][D], [Np][D][D]; sparse: [M][D] and the constant matrix [D][D]
+  const int32_t* obs_idx = nullptr;   // sparse only, on the host: obs_idx[t] = n >= 0: grid point t takes jm[n][:] and js
+  static LdJumps dense(In jm, In js) { return {jm, js, nullptr}; }
+  static LdJumps sparse(In jm, In js_const, const int32_t* obs_idx_host) { return {jm, js_const, obs_idx_host}; }
+};
 size_t ld_workspace_doubles(int D);
-hipError_t ld_solve_fwd(int method, double dt, int D, int Np, const double* A, const double* b, const double* m0,
-                        const double* S0, const double* Sigma, double* m, double* S, double* ws, hipStream_t st);
-hipError_t ld_solve_bwd(int method, double dt, int D, int Np, const double* A, const double* gm, const double* gs,
-                        const double* jm, const double* js, double* lam, double* psi, double* ws, hipStream_t st,
-                        const int32_t* obs_idx_host = nullptr);
-// optional rocBLAS backend of the plain stage GEMM (lib_gemm.cpp); `use_library_gemm` is read by the single-rank drivers
+hipError_t ld_solve_fwd(const LdCall& c, int Np, In A, In b, In m0, In S0, In Sigma, Out m, Out S);
+hipError_t ld_solve_bwd(const LdCall& c, int Np, In A, In gm, In gs, const LdJumps& jumps, Out lam, Out psi);
+hipError_t ld_bwd_step(const LdCall& c, In At, In Am, In Gt, In Gm, In gt, In gmm, In Pt, In lt, Out Pn, Out ln, In Jn, In jn);
+// optional rocBLAS backend of the plain stage GEMM (lib_gemm.cpp), used when LdCall::library_gemm asks for it
 bool library_gemm_available();
 hipError_t library_gemm(bool transa, int M, int N, int K, const double* A, int lda, const double* B, int ldb, double* C, int ldc,
                         hipStream_t st);
-extern thread_local bool use_library_gemm;
-hipError_t ld_bwd_step(int method, double dt, int D, const double* At, const double* Am, const double* Gt, const double* Gm,
-                       const double* gt, const double* gmm, const double* Pt, const double* lt, double* Pn, double* ln,
-                       const double* Jn, const double* jn, double* ws, hipStream_t st);
 size_t lde_workspace_doubles(int D, int nb);
 int lde_batch(int D, double budget_bytes);
 hipError_t lde_energy(int D, int Np, double theta, const double* isg, const double* A, const double* b, const double* m,
