@@ -500,3 +500,88 @@ def test_fused_lane_pass(model, method, n, nb):
     # and a gradient behind the fetch (derived arrays valid: either route) still equals the sweep's
     assert rel_err(np.atleast_2d(ctx.gradient()), g) < 1e-11
     ctx.close(); ref.close()
+
+
+def _walk_context(case):
+    """One small context per path that keeps state between calls: (context factory, x of the whole batch)."""
+    model, d, n, batch, flags, method, per_problem_times, isotropic = case
+    p, x0 = make_problem(model, d, n, method=method)
+    if isotropic:                                          # Sigma = sigma^2 I: what the Q'' stream and the packed layouts take
+        p.sigma = 3.5 * np.eye(d)
+    x = x0 if batch == 1 else x0[None, :] + 0.02 * np.random.default_rng(41).standard_normal((batch, x0.size))
+
+    def fresh():
+        ctx = gpu_context(p, batch=batch, flags=flags)
+        if per_problem_times:                              # every problem observes at its own grid points
+            ctx.set_problem_data(obs_t=np.stack([p.obs_t + (i % 3) - 1 for i in range(batch)]))
+        return ctx
+    return p, fresh, x
+
+
+WALKS = {  # model, D, Np, batch, flags, method, per-problem observation times, Sigma = sigma^2 I
+    "fused_lane_pass": ("L63", 3, 12, 520, 0, "rk4", False, False),
+    "16_lane_kernels_per_problem_times": ("L63", 3, 12, 6, 0, "rk4", True, False),
+    "cover_gradient_in_backward_kernel": ("L96", 40, 6, 64, 0, "rk4", False, True),      # packed S_t / dEsde_dS, nothing stored in d_psi
+    "cover_q_stream_separate_assembly": ("L96", 40, 6, 3, 0, "rk4", False, True),        # packed, Q''_t stored
+    "cover_upper_triangle": ("L96", 40, 6, 3, 0, "rk4", False, False),                   # a diagonal Sigma: upper triangle of dEsde_dS, Psi_t stored
+    "cover_keep_psi": ("L96", 40, 6, 3, FLAG_KEEP_PSI, "rk4", False, True),              # whole matrices, Psi_t stored
+    "role_specialised": ("L96", 24, 7, 1, 0, "rk4", False, False),
+    "generic": ("L96", 12, 7, 2, FLAG_FORCE_GENERIC, "rk4", False, False),
+    "resident_above_64": ("L96", 72, 5, 1, 0, "rk4", False, False),
+}
+FETCH_ORDER = ("dEsde_ds", "mt", "psit", "Esde_t", "lamt", "Edf", "st", "dEsde_dm", "Efx")       # every vgpa_fetch key, scrambled
+
+
+@pytest.mark.parametrize("name", list(WALKS))
+def test_buffer_state_walks(name):
+    """What the device buffers hold between calls (layouts of S_t / dEsde_dS, Psi_t or Q''_t, row- or time-major moments, the cache
+    itself), walked through every transition on one context per state-bearing path: sweep -> every fetch key twice (the in-place
+    conversions happen once; the second pass is bit-equal) -> gradient(None) -> free_energy + gradient(None) against a fresh
+    context's sweep -> the four operator-level calls, which take the buffers over -> the state error of everything that needs the
+    cache -> the first sweep again, bit for bit.  Expected values are the same library's on a fresh context; bit-equal except
+      * the gradient assembled from a Psi_t that VGPA_FETCH_PSIT recovered from Q''_t: 1e-13 relative, the tolerance of
+        test_q_stream_of_the_batched_sweeps for exactly that (4.9e-17 measured here);
+      * the fused lane pass, as test_fused_lane_pass states it: behind the fetches the gradient comes from the four separate kernels
+        (1e-11 there; 4.7e-16 measured here), and F of free_energy alone is another instantiation of the pass than the sweep's
+        (1e-13 there; 1.5e-16 measured here).
+    The library before the record of the buffers' contents existed passes the same walk."""
+    p, fresh, x = _walk_context(WALKS[name])
+    d, n, batch = WALKS[name][1:4]
+    ctx = fresh()
+    f, g = ctx.sweep(x)
+    first = {key: ctx.fetch(key) for key in FETCH_ORDER}
+    for key in FETCH_ORDER:
+        assert np.array_equal(ctx.fetch(key), first[key]), key
+    g_again = ctx.gradient(None)
+    if name == "cover_q_stream_separate_assembly":
+        assert rel_err(g_again, g) < 1e-13
+    elif name == "fused_lane_pass":
+        assert rel_err(g_again, g) < 1e-11
+    else:
+        assert np.array_equal(g_again, g)
+    x2 = x + 0.01 * np.random.default_rng(43).standard_normal(np.shape(x))
+    other = fresh()
+    f_want, g_want = other.sweep(x2)
+    other.close()
+    f2 = ctx.free_energy(x2)
+    g2 = ctx.gradient(None)
+    if name == "fused_lane_pass":
+        assert rel_err(np.atleast_1d(f2), np.atleast_1d(f_want)) < 1e-13
+    else:
+        assert np.array_equal(f2, f_want)
+    assert np.array_equal(g2, g_want)
+    # one operator-level call of each kind, on the arrays of the first sweep
+    xs = np.reshape(x, (batch, -1))
+    a, b = xs[:, :n * d * d].reshape(batch, n, d, d), xs[:, n * d * d:].reshape(batch, n, d)
+    mt, st = np.reshape(first["mt"], (batch, n, d)), np.reshape(first["st"], (batch, n, d, d))
+    _, jm, js = ctx.obs_energy(mt, st)
+    ctx.energy(a, b, mt, st, want_edf=False)
+    lam, psi = ctx.solve_bwd(a, first["dEsde_dm"], first["dEsde_ds"], jm, js)
+    m_op, s_op = ctx.solve_fwd(a, b, p.m0, p.s0, p.sigma)
+    assert all(np.all(np.isfinite(v)) for v in (jm, js, lam, psi, m_op, s_op))
+    for needs_the_cache in (lambda: ctx.gradient(None), lambda: ctx.fetch("st"), ctx.theta_gradient):
+        with pytest.raises(RuntimeError, match="error -4"):
+            needs_the_cache()
+    f3, g3 = ctx.sweep(x)
+    assert np.array_equal(f3, f) and np.array_equal(g3, g)
+    ctx.close()

@@ -41,10 +41,7 @@ inline bool stores_q(int method, int D) {
 }
 // the backward kernel that assembles the gradient on its helper waves (OdeArgs::grad_on; k_ode_sym, GF): the fragment-cover kernels
 // of RK4
-inline bool fuses_grad(int method, int D) {
-  static const bool off = [] { const char* e = getenv("VGPA_FUSED_GRAD"); return e && e[0] == '0'; }();
-  return method == VGPA_ODE_RK4 && stores_q(method, D) && !off;
-}
+inline bool fuses_grad(int method, int D) { return method == VGPA_ODE_RK4 && stores_q(method, D); }
 }  // namespace sym
 }  // namespace vgpa
 

@@ -1,5 +1,5 @@
 // Instantiations of the symmetric fp64-MFMA stepping kernels for stepper 3: D <= 44 on the role-specialised kernels of
-// ode_mfma_impl.h (VGPA_ODE_KERNEL=sym selects the symmetric-unit ones), 44 < D <= 64 on the symmetric-unit kernels of
+// ode_mfma_impl.h or the symmetric-unit ones, as OdeArgs::sym_units says, 44 < D <= 64 on the symmetric-unit kernels of
 // ode_sym_impl.h.
 #include "ode_sym_impl.h"
 namespace vgpa {

@@ -1530,15 +1530,11 @@ hipError_t launch_sym(const OdeArgs& a, hipStream_t st) {
   }
 }
 
-// D <= 44 has both kernel families.  Default: the role-specialised 8-wave kernels of ode_mfma_impl.h (faster for one problem
-// per CU and for a single problem); VGPA_ODE_KERNEL=sym selects the symmetric-unit kernels (faster from two problems per CU on).
-inline bool use_sym_kernels() {
-  static const bool sym = [] { const char* e = getenv("VGPA_ODE_KERNEL"); return e && !strcmp(e, "sym"); }();
-  return sym;
-}
+// D <= 44 has both kernel families: the role-specialised 8-wave kernels of ode_mfma_impl.h (faster for one problem per CU and for a
+// single problem) and the symmetric-unit kernels (faster from two problems per CU on).  The caller says which: OdeArgs::sym_units.
 template <int METHOD, bool FWD, int NB>
 hipError_t launch_any(const OdeArgs& a, hipStream_t st) {
-  if (a.sym_units || use_sym_kernels()) return launch_sym<METHOD, FWD, NB>(a, st);
+  if (a.sym_units) return launch_sym<METHOD, FWD, NB>(a, st);
   return mfma::launch_nb<METHOD, FWD, NB>(a, st);
 }
 

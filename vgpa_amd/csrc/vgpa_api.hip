@@ -37,7 +37,8 @@ enum class Stepper { LargeD, Lane, Wave, Mfma, Generic };
 // vgpa_set_problem_params change the inputs; nothing else writes it.  (DESIGN.md s.4.0 has the table.)
 struct Plan {
   bool sigma_diag = true, isg_iso = false, sym_inputs = true;   // the inputs in force: Sigma diagonal, sigma^2 I; every s0 / Sigma / constant jump symmetric
-  bool sym_units = false;       // matrix-core family: symmetric-unit kernels, not the role-specialised ones (OdeArgs::sym_units)
+  bool sym_units = false;       // matrix-core family: symmetric-unit kernels, not the role-specialised ones; heads the layout chain below
+  bool launch_sym_units = false;   // what launch_ode_mfma is told (OdeArgs::sym_units): sym_units, or VGPA_ODE_KERNEL=sym, which leaves the layouts alone
   Stepper fwd = Stepper::Generic, bwd = Stepper::Generic;
   bool lane_pass = false;      // the objective is the fused lane pass (enqueue_lane_sweep)
   // the layout chain of the fragment-cover kernels, each step implying the one before:
@@ -47,6 +48,31 @@ struct Plan {
   bool grad_in_bwd = false;     // ... the backward kernel can assemble the gradient (OdeArgs::grad_on): F-only evaluations skip the recursion
   bool grad_in_bwd_now = false; // ... and does, at this batch size
 };
+
+// What the device buffers hold right now (the plan says what a sweep WILL produce).  Written through the transitions below and nowhere
+// else; the argument builders take their layout fields from it, everything else reads it behind `cached`.  (DESIGN.md s.4.0 has the table.)
+struct Resident {
+  bool cached = false;       // a fused sweep's state is cached
+  enum class Moments { RowMajor, TimeMajor } moments = Moments::RowMajor;   // in d_m / d_S; in d_msT alone (fused lane pass: untransposed on demand)
+  enum class SLayout { Whole, Packed } S = SLayout::Whole;                  // d_S: whole matrices; packed lower triangles (the s_packed of every argument struct)
+  // d_dEs: whole matrices; the upper triangles alone (EnergyArgs::ds_upper); packed lower triangles (ds_packed; the constant jump is then d_jscp)
+  enum class DesLayout { Whole, Upper, Packed } dEs = DesLayout::Whole;
+  // d_lam / d_psi: nothing of this state (an F-only evaluation, or a backward kernel that assembled the gradient and kept Psi_t to itself:
+  // vgpa_fetch materialises); lam_t and Psi_t; lam_t and Q''_t = A_t / sigma^2 - 2 Psi_t (OdeArgs::q_on, GradArgs::psi_is_q)
+  enum class Bwd { None, Psi, Q } bwd = Bwd::None;
+  bool terms = false;        // dEsde_dm / dEsde_dS / <f> / E_sde(t) belong to the cached moments (false behind a fused lane pass)
+  void sweep_begins(const Plan& p) { *this = Resident{}; S = p.packed ? SLayout::Packed : SLayout::Whole; }   // the only copy of the plan
+  void forward_wrote(Moments where) { moments = where; }
+  void energy_wrote(DesLayout how) { dEs = how; terms = true; }
+  void backward_stored(Bwd what) { bwd = what; }
+  void sweep_cached() { cached = true; }
+  void lane_pass_cached() { terms = false; cached = true; }     // (the pass keeps the per-grid-point terms to itself)
+  void moments_untransposed() { moments = Moments::RowMajor; }  // vgpa_fetch's conversions in place ...
+  void psi_recovered() { bwd = Bwd::Psi; }
+  void des_mirrored() { dEs = DesLayout::Whole; }
+  void taken_over() { *this = Resident{}; }   // an operator-level call: the caller's whole matrices and row-major moments, no cache
+  void cache_dropped() { cached = false; }    // the inputs or the caller's x behind the cached state are gone
+};
 }  // namespace
 
 struct vgpa_ctx {
@@ -55,18 +81,8 @@ struct vgpa_ctx {
   size_t DD = 0, len_x = 0;
   bool single = false, full = false;
   Plan plan;                          // which kernels run and in which layouts (make_plan)
-  int n_cu = 256; bool keep_pe = false;   // make_plan's inputs read once, in vgpa_create: the CU count, VGPA_ODE_KERNEL=pe
-  // What the buffers hold right now.  Each sweep sets these from the plan; operator-level calls and vgpa_fetch change them in between.
-  bool have_state = false;       // a fused sweep's state is cached
-  bool ms_valid = true;          // d_m / d_S hold the cached moments (false: only d_msT does; untransposed on demand)
-  bool derived_valid = true;     // dEsde_dm / dEsde_dS / <f> / E_sde(t) / lam / Psi belong to the cached (m, S): false behind a fused lane pass
-  bool bwd_stored = true;        // d_lam / d_psi hold the backward recursion of the cached state (false: F-only evaluation of a context whose backward
-                                 // kernel assembles the gradient -- Plan::grad_in_bwd -- or that kernel, which keeps Psi_t to itself; vgpa_fetch materialises)
-  bool s_packed = false;         // d_S holds packed lower triangles (OdeArgs::s_packed): the fused batched sweeps of the cover kernels
-  bool psi_is_q = false;         // d_psi holds Q''_t = A_t / sigma^2 - 2 Psi_t (fused batched sweeps, OdeArgs::q_on)
-  bool des_upper = false;        // d_dEs holds the upper triangles only (EnergyArgs::ds_upper)
-  bool des_packed = false;       // d_dEs holds packed lower triangles (EnergyArgs::ds_packed); d_jscp = the constant matrix jump in the same layout
-  bool pt_dense_zeroed = false;  // d_jm_pt / d_js_pt are zero off the observation rows of the current times (each sweep rewrites only those rows)
+  int n_cu = 256; bool keep_pe = false, force_sym = false;   // make_plan's inputs read once, in vgpa_create: the CU count, VGPA_ODE_KERNEL=pe / =sym
+  Resident res;                       // what the device buffers hold right now
   hipStream_t stream = nullptr;
   hipStream_t stream2 = nullptr;      // side stream of the D > 64 energy terms (lde_energy's look-ahead), created on first use
   std::string err;
@@ -87,14 +103,13 @@ struct vgpa_ctx {
   int ld_chunk = 0;
   double *d_dEs_c = nullptr, *d_psi_c = nullptr;
   void* h_fs = nullptr;        // pinned host block [B doubles | B status words]: F and the status words come back in one round trip (vgpa_fetch_f)
-  double* d_jscp = nullptr;    // the constant matrix jump as a packed lower triangle (des_packed)
+  double* d_jscp = nullptr;    // the constant matrix jump as a packed lower triangle (Resident::DesLayout::Packed)
   double isg0 = 1.0;           // 1 / sigma^2 of a shared Sigma = sigma^2 I (Plan::isg_iso)
   std::vector<int32_t> h_obs_idx; // host copy of obs_idx [Np]
   bool obs_diag = false;          // diagonal R and H = I: Q, K are diagonal
   double* d_obs_part = nullptr;   // [B][M] per-observation energy terms (large-D observation kernel)
   double* d_hyp = nullptr;        // [B][Np][H] integrands of the hyper-parameter gradients (vgpa_energy_hyper only)
   double* d_hypT = nullptr;       // [B][H] their trapezoids
-  bool hyp_on = false;
   double* d_tg = nullptr;         // [B][Np] integrand of dF/dtheta (vgpa_theta_gradient, Lorenz-96)
   double* d_thT = nullptr;        // [B][kMaxTheta] ... its trapezoids / the lane kernel's results
   std::vector<double> h_isig;     // host copy of Sigma^-1 [D][D]
@@ -120,7 +135,8 @@ struct vgpa_ctx {
   double *d_pp_m0 = nullptr, *d_pp_S0 = nullptr, *d_pp_e0 = nullptr, *d_pp_obs_y = nullptr, *d_pp_theta = nullptr, *d_pp_Sigma = nullptr;
   double *d_pp_isig = nullptr, *d_pp_isg = nullptr, *d_pp_sig1 = nullptr, *d_pp_qs = nullptr;
   int64_t* d_pp_obs_t = nullptr; int32_t* d_pp_obs_idx = nullptr;
-  double *d_jm_pt = nullptr, *d_js_pt = nullptr;   // dense jumps [B][Np][D], [B][Np][D][D]: per-problem times on the 16-lane kernels (pt_dense_zeroed)
+  double *d_jm_pt = nullptr, *d_js_pt = nullptr;   // dense jumps [B][Np][D], [B][Np][D][D]: per-problem times on the 16-lane kernels
+  bool pt_dense_zeroed = false;  // ... which are zero off the observation rows of the current times (each sweep rewrites only those rows)
   std::vector<double> h_sigma;       // host copy of the shared Sigma [D][D]
   SigmaForm sigma_form, rows_form;            // make_plan's inputs: the form of the shared Sigma, of the per-problem rows in force,
   bool inputs_sym = true, s0_rows_sym = true;  // ... the shared s0 and constant jump symmetric, the per-problem s0 rows symmetric
@@ -369,16 +385,13 @@ static Stepper stepper(const vgpa_ctx* c, bool fwd, bool sym) {
   return sym && ode_mfma_supported(c->cfg.method, fwd, c->D) ? Stepper::Mfma : Stepper::Generic;
 }
 
-// ... from kFusedGradMinBatch problems on (VGPA_FUSED_GRAD=1 in the environment: always).  The third wave set costs the recursion
+// ... from kFusedGradMinBatch problems on (VGPA_FUSED_GRAD in the environment: 1 always, 0 never).  The third wave set costs the recursion
 // ~0.4-0.5 ms per launch round (its matrix-core and vector-ALU instructions share the SIMDs' issue port with the product waves), the
 // separate assembly ~7 us per problem: below ~70 problems the backward kernel followed by k_grad_mfma_q is the shorter way.
 constexpr int kFusedGradMinBatch = 64;
-static bool fused_grad_always() {
-  static const bool always = [] { const char* e = getenv("VGPA_FUSED_GRAD"); return e && e[0] == '1'; }();
-  return always;
-}
+static char fused_grad_switch() { static const char v = [] { const char* e = getenv("VGPA_FUSED_GRAD"); return e ? e[0] : '\0'; }(); return v; }
 
-// The one place that decides a context's kernels (Plan).  Reads cfg, D, B, len_x, full, n_cu, keep_pe and the forms of the inputs.
+// The one place that decides a context's kernels (Plan).  Reads cfg, D, B, len_x, full, n_cu, keep_pe, force_sym and the forms of the inputs.
 static void make_plan(vgpa_ctx* c) {
   Plan p;
   // the form of the shared Sigma or of the per-problem rows (isotropic: every row sigma_p^2 I with its own sigma_p); symmetric: every
@@ -398,6 +411,7 @@ static void make_plan(vgpa_ctx* c) {
   const int nb = (c->D + 3) / 4;
   p.sym_units = (c->cfg.flags & VGPA_FLAG_SYM_UNITS) != 0 || (c->B > c->n_cu && nb <= 10) || ((nb == 9 || nb == 10) && !c->keep_pe) ||
                 (nb >= 12 && c->D <= kMaxSmallD);
+  p.launch_sym_units = p.sym_units || c->force_sym;   // (VGPA_ODE_KERNEL=sym: that family at D <= 44 too, in the layouts sym_units itself implies below)
   p.fwd = stepper(c, true, p.sym_inputs);
   p.bwd = stepper(c, false, p.sym_inputs);
   // the fused lane pass (ode_small.hip::k_sweep_lane): forward kernel -> observations -> ONE kernel for the E_sde terms, the backward
@@ -415,8 +429,8 @@ static void make_plan(vgpa_ctx* c) {
   p.packed = p.store_q && p.fwd == Stepper::Mfma;
   // the backward kernel assembles the gradient itself: wherever S_t is packed and the stepper's kernel can.  F-only evaluations of
   // such a context skip the backward recursion altogether (F does not depend on it); gradient(x, eval_fun=False) runs it.
-  p.grad_in_bwd = p.packed && sym_fuses_grad(c->cfg.method, c->D);
-  p.grad_in_bwd_now = p.grad_in_bwd && (fused_grad_always() || c->B >= kFusedGradMinBatch);
+  p.grad_in_bwd = p.packed && sym_fuses_grad(c->cfg.method, c->D) && fused_grad_switch() != '0';
+  p.grad_in_bwd_now = p.grad_in_bwd && (fused_grad_switch() == '1' || c->B >= kFusedGradMinBatch);
   c->plan = p;
 }
 
@@ -443,10 +457,11 @@ static ld::LdCall ld_call(vgpa_ctx* c, bool literal) {
   return {c->cfg.method, c->cfg.dt, c->D, c->B, literal, (c->cfg.flags & VGPA_FLAG_LIBRARY_GEMM) != 0, c->d_ld_ws, c->stream};
 }
 
-// what every stepping kernel's OdeArgs starts with: the sizes, x and the moment histories
+// what every stepping kernel's OdeArgs starts with: the sizes, x, the moment histories and the matrix-core family
 static OdeArgs ode_args(vgpa_ctx* c) {
   OdeArgs a{};
   a.D = c->D; a.Np = c->Np; a.batch = c->B; a.dt = c->cfg.dt;
+  a.sym_units = c->plan.launch_sym_units ? 1 : 0;
   a.strideA = a.strideB = c->len_x;
   a.A = ctx_A(c); a.b = ctx_b(c); a.m = c->d_m; a.S = c->d_S;
   return a;
@@ -463,15 +478,15 @@ static void copy_theta(const vgpa_ctx* c, double* theta) {
   for (int i = 0; i < kMaxTheta; i++) theta[i] = c->theta[i];
 }
 
-// the sparse observation jumps of the backward recursion (des_packed is never set behind the lane pass: js_const = d_jsc there)
+// the sparse observation jumps of the backward recursion (dEsde_dS is never packed behind the lane pass: js_const = d_jsc there)
 static void sparse_jumps(vgpa_ctx* c, OdeArgs& a) {
   a.obs_idx = c->in.obs_idx.rows; a.obs_idx_stride = (int)c->in.obs_idx.stride;
-  a.jm_sparse = c->d_jm; a.js_const = c->des_packed ? c->d_jscp : c->d_jsc; a.n_obs = c->M;
+  a.jm_sparse = c->d_jm; a.js_const = c->res.dEs == Resident::DesLayout::Packed ? c->d_jscp : c->d_jsc; a.n_obs = c->M;
 }
 
 // sym: Plan::sym_inputs for the fused sweep (the stepper is then Plan::fwd), the symmetry of the caller's arrays for vgpa_solve_fwd
 static int run_fwd(vgpa_ctx* c, Rows<double> m0, Rows<double> S0, Rows<double> Sigma, bool sym) {
-  c->ms_valid = true;                  // (every path below writes the [B][Np] arrays m / S)
+  c->res.forward_wrote(Resident::Moments::RowMajor);   // (every path below writes the [B][Np] arrays m / S)
   const Stepper k = stepper(c, true, sym);
   if (k == Stepper::LargeD) {
     int rc = ensure_ld_ws(c);
@@ -482,8 +497,7 @@ static int run_fwd(vgpa_ctx* c, Rows<double> m0, Rows<double> S0, Rows<double> S
     return VGPA_OK;
   }
   OdeArgs a = fwd_args(c, m0, S0, Sigma);
-  a.sym_units = c->plan.sym_units ? 1 : 0;
-  a.s_packed = c->s_packed ? 1 : 0;
+  a.s_packed = c->res.S == Resident::SLayout::Packed ? 1 : 0;
   LAUNCH_TRY(c, "forward sweep launch", launch_stepper(k, c->cfg.method, true, a, c->stream));
   return VGPA_OK;
 }
@@ -493,13 +507,13 @@ static ObsArgs obs_args(vgpa_ctx* c);
 // gradient into it (Plan::grad_in_bwd contexts; Psi_t is then not stored)
 static int run_bwd(vgpa_ctx* c, bool dense_jumps, bool sym, double* g_fused = nullptr) {
   int rc;
-  if (g_fused && (dense_jumps || !c->plan.grad_in_bwd || !c->s_packed)) return fail(c, VGPA_ERR_STATE, "fused gradient assembly asked of a context without it");
+  if (g_fused && (dense_jumps || !c->plan.grad_in_bwd || c->res.S != Resident::SLayout::Packed)) return fail(c, VGPA_ERR_STATE, "fused gradient assembly asked of a context without it");
   if ((rc = ensure(c, &c->d_psi, (size_t)c->B * c->Np * c->DD))) return rc;
   if ((rc = ensure(c, &c->d_dEs, (size_t)c->B * c->Np * c->DD))) return rc;
-  c->psi_is_q = false;
   const Stepper k = stepper(c, false, sym);
   if (k == Stepper::LargeD) {
     if ((rc = ensure_ld_ws(c))) return rc;
+    c->res.backward_stored(Resident::Bwd::Psi);
     const size_t NpD = (size_t)c->Np * c->D, NpDD = (size_t)c->Np * c->DD;
     // operator-level calls bring dense jump arrays; the fused sweep uses the sparse ones (obs index on the host, one constant matrix)
     const ld::LdJumps jumps = dense_jumps ? ld::LdJumps::dense({c->d_jm_dense, NpD}, {c->d_js_dense, NpDD})
@@ -509,7 +523,6 @@ static int run_bwd(vgpa_ctx* c, bool dense_jumps, bool sym, double* g_fused = nu
     return VGPA_OK;
   }
   OdeArgs a = ode_args(c);   // (b, m, S: read only with grad_on)
-  a.sym_units = c->plan.sym_units ? 1 : 0;
   a.dEm = c->d_dEm; a.dEs = c->d_dEs; a.lam = c->d_lam; a.psi = c->d_psi;
   if (dense_jumps) { a.jm_dense = c->d_jm_dense; a.js_dense = c->d_js_dense; }
   else if (c->in.obs_idx.stride && k == Stepper::Wave) {
@@ -527,27 +540,25 @@ static int run_bwd(vgpa_ctx* c, bool dense_jumps, bool sym, double* g_fused = nu
   } else {
     sparse_jumps(c, a);
   }
-  a.ds_packed = c->des_packed ? 1 : 0;
+  a.ds_packed = c->res.dEs == Resident::DesLayout::Packed ? 1 : 0;
   // (the fused sweep's call: the stepper is Plan::bwd then.  An operator-level call wants Psi_t itself)
-  c->psi_is_q = !dense_jumps && c->plan.store_q;
-  a.q_on = c->psi_is_q ? 1 : 0;
+  const bool q = !dense_jumps && c->plan.store_q;
+  a.q_on = q ? 1 : 0;
   a.q_scale = c->isg0;
   a.q_scale_v = c->in.qs.rows;               // (read only by the Q'' kernels: every row isotropic then)
   if (g_fused) {                           // the gradient assembly on the kernel's helper waves (k_ode_sym, GF)
-    if (!c->psi_is_q) return fail(c, VGPA_ERR_STATE, "fused gradient assembly: the backward kernel is not the Q'' one");
-    a.grad_on = 1; a.g = g_fused; a.s_packed = 1;
+    if (!q) return fail(c, VGPA_ERR_STATE, "fused gradient assembly: the backward kernel is not the Q'' one");
+    a.grad_on = 1; a.g = g_fused; a.s_packed = 1;      // (S_t is packed: checked on entry)
     a.Ef = c->d_Ef; a.Am = c->d_Am;
-    c->psi_is_q = false;                   // (nothing is stored in d_psi)
   }
-  c->bwd_stored = !g_fused;
+  c->res.backward_stored(g_fused ? Resident::Bwd::None : q ? Resident::Bwd::Q : Resident::Bwd::Psi);   // (g_fused: nothing is stored in d_psi)
   LAUNCH_TRY(c, "backward sweep launch", launch_stepper(k, c->cfg.method, false, a, c->stream));
   return VGPA_OK;
 }
 
-static EnergyArgs energy_args(vgpa_ctx* c, double* edf, bool ds_upper = false) {
-  EnergyArgs a{};
-  a.ds_upper = ds_upper ? 1 : 0;
-  a.s_packed = c->s_packed ? 1 : 0;
+static EnergyArgs energy_args(vgpa_ctx* c, double* edf, bool hyper = false) {
+  EnergyArgs a{};         // (ds_upper / ds_packed = 0: run_energy, the one caller that has dEsde_dS written, sets them)
+  a.s_packed = c->res.S == Resident::SLayout::Packed ? 1 : 0;
   a.model = c->cfg.model; a.D = c->D; a.Np = c->Np; a.batch = c->B; a.dt = c->cfg.dt;
   copy_theta(c, a.theta);
   a.sigma1 = c->sigma1; a.isg = c->in.isg.rows; a.isg_stride = c->in.isg.stride;
@@ -556,7 +567,7 @@ static EnergyArgs energy_args(vgpa_ctx* c, double* edf, bool ds_upper = false) {
   a.A = ctx_A(c); a.b = ctx_b(c); a.m = c->d_m; a.S = c->d_S;
   a.e_t = c->d_et; a.Ef = c->d_Ef; a.Edf = edf; a.dEm = c->d_dEm; a.dEs = c->d_dEs; a.status = c->d_status;
   a.Am = (c->cfg.model == VGPA_MODEL_L96) ? c->d_Am : nullptr;
-  a.hyp = c->hyp_on ? c->d_hyp : nullptr;
+  a.hyp = hyper ? c->d_hyp : nullptr;
   return a;
 }
 
@@ -571,9 +582,16 @@ static int ensure_lde_ws(vgpa_ctx* c) {
   return dev_alloc(c, &c->d_lde_ws, ld::lde_workspace_doubles(c->D, c->lde_nb));
 }
 
-static int run_energy(vgpa_ctx* c, double* edf, bool ds_upper = false, bool ds_packed = false) {
-  c->des_upper = false;
-  c->des_packed = false;
+// The layout the energy kernels write dEsde_dS in when asked for `want`: the L96 kernels of 5 <= D <= 64 honour the upper triangle, and
+// k_energy_l96_r, the kernel that reads packed S_t, the packed lower one; everything else writes whole matrices.
+static Resident::DesLayout des_layout(const vgpa_ctx* c, Resident::DesLayout want) {
+  using L = Resident::DesLayout;
+  if (want == L::Whole || c->cfg.model != VGPA_MODEL_L96 || c->D < 5 || c->D > kMaxSmallD) return L::Whole;
+  return want == L::Packed && c->res.S == Resident::SLayout::Packed ? L::Packed : L::Upper;
+}
+// want: the plan's layout for a fused sweep (enqueue_free_energy), whole matrices for everything else; hyper: the integrands of d_hyp as well
+static int run_energy(vgpa_ctx* c, double* edf, Resident::DesLayout want = Resident::DesLayout::Whole, bool hyper = false) {
+  c->res.energy_wrote(des_layout(c, want));
   { int rc = ensure(c, &c->d_dEs, (size_t)c->B * c->Np * c->DD); if (rc) return rc; }
   if (c->D > kMaxSmallD) {
     if (c->cfg.model != VGPA_MODEL_L96) return fail(c, VGPA_ERR_UNSUPPORTED, "large-D energy terms exist for Lorenz-96 only");
@@ -586,15 +604,13 @@ static int run_energy(vgpa_ctx* c, double* edf, bool ds_upper = false, bool ds_p
                                                      ctx_b(c) + p * c->len_x, c->d_m + p * NpD, c->d_S + p * NpDD, c->d_et + (size_t)p * c->Np,
                                                      c->d_Ef + p * NpD, edf ? edf + p * NpDD : nullptr, c->d_dEm + p * NpD, c->d_dEs + p * NpDD,
                                                      c->d_status + p, c->d_lde_ws, c->lde_nb, c->stream,
-                                                     c->hyp_on ? c->d_hyp + (size_t)p * c->Np * 2 * c->D : nullptr, c->stream2));
+                                                     hyper ? c->d_hyp + (size_t)p * c->Np * 2 * c->D : nullptr, c->stream2));
     }
     return VGPA_OK;
   }
-  c->des_upper = ds_upper && c->cfg.model == VGPA_MODEL_L96 && c->D >= 5;       // (the L96 kernels of 5 <= D <= 64 honour it)
-  c->des_packed = c->des_upper && ds_packed && c->s_packed;                     // (k_energy_l96_r, the kernel that reads packed S_t, does)
-  if (c->des_packed) c->des_upper = false;
-  EnergyArgs a = energy_args(c, edf, c->des_upper);
-  a.ds_packed = c->des_packed ? 1 : 0;
+  EnergyArgs a = energy_args(c, edf, hyper);
+  a.ds_upper = c->res.dEs == Resident::DesLayout::Upper ? 1 : 0;
+  a.ds_packed = c->res.dEs == Resident::DesLayout::Packed ? 1 : 0;
   LAUNCH_TRY(c, "energy launch", launch_energy(a, c->stream));
   return VGPA_OK;
 }
@@ -606,7 +622,7 @@ static ObsArgs obs_args(vgpa_ctx* c) {
   a.Q = c->d_Q; a.K = c->d_K; a.rinv_diag = c->d_rinv;
   a.obs_const = c->obs_const; a.m = c->d_m; a.S = c->d_S; a.jm_sparse = c->d_jm; a.eobs = c->d_eobs;
   a.diag = c->obs_diag ? 1 : 0; a.part = c->d_obs_part;
-  a.s_packed = c->s_packed ? 1 : 0;
+  a.s_packed = c->res.S == Resident::SLayout::Packed ? 1 : 0;
   return a;
 }
 
@@ -642,9 +658,10 @@ static int run_grad(vgpa_ctx* c, double* g_dev) {
   a.A = ctx_A(c); a.b = ctx_b(c); a.m = c->d_m; a.S = c->d_S; a.lam = c->d_lam; a.psi = c->d_psi;
   a.isig = c->in.isig.rows; a.isig_stride = c->in.isig.stride; a.theta_v = c->in.theta.rows;
   a.Ef = c->d_Ef; a.Edf = nullptr; a.g = g_dev;
-  a.psi_is_q = c->psi_is_q ? 1 : 0;
-  a.s_packed = (c->s_packed && c->psi_is_q) ? 1 : 0;
-  if (c->s_packed && !c->psi_is_q) {      // (an assembly kernel that wants S_t whole: behind VGPA_FETCH_PSIT, which recovers Psi_t in place and clears psi_is_q)
+  const bool q = c->res.bwd == Resident::Bwd::Q, packed = c->res.S == Resident::SLayout::Packed;
+  a.psi_is_q = q ? 1 : 0;
+  a.s_packed = (packed && q) ? 1 : 0;
+  if (packed && !q) {        // (an assembly kernel that wants S_t whole: behind VGPA_FETCH_PSIT, which recovers Psi_t in place)
     const double* full = nullptr;
     int rc = unpack_S(c, &full);
     if (rc) return rc;
@@ -711,6 +728,7 @@ static int stream_pass(vgpa_ctx* c, double* g_dev) {
     t1 = t0;
     first = false;
   }
+  c->res.energy_wrote(Resident::DesLayout::Whole);   // (the per-grid-point vectors; dEsde_dS_t itself chunk by chunk only: vgpa_fetch refuses it)
   return VGPA_OK;
 }
 
@@ -720,7 +738,7 @@ static int enqueue_stream_sweep(vgpa_ctx* c, double* g_dev) {
   int rc;
   prof_collect(c);
   HIP_TRY(c, hipMemsetAsync(c->d_status, 0, sizeof(int32_t) * c->B, c->stream));
-  c->s_packed = false;
+  c->res.sweep_begins(c->plan);
   prof_mark(c, 0);
   if ((rc = run_fwd(c, c->in.m0, c->in.S0, c->in.Sigma, c->plan.sym_inputs))) return rc;
   prof_mark(c, 1);
@@ -729,7 +747,7 @@ static int enqueue_stream_sweep(vgpa_ctx* c, double* g_dev) {
   if ((rc = stream_pass(c, g_dev))) return rc;
   prof_mark(c, 3);
   if ((rc = run_reduce(c))) return rc;
-  c->have_state = true;
+  c->res.sweep_cached();
   return g_dev ? prof_end(c, VGPA_OK) : VGPA_OK;
 }
 
@@ -768,6 +786,7 @@ static int enqueue_lane_sweep(vgpa_ctx* c, double* g_dev) {
   int rc;
   prof_collect(c);
   HIP_TRY(c, hipMemsetAsync(c->d_status, 0, sizeof(int32_t) * c->B, c->stream));
+  c->res.sweep_begins(c->plan);
   prof_mark(c, 0);
   if (!c->d_msT) {
     c->bpad = 64 * ((c->B + 63) / 64);
@@ -779,41 +798,38 @@ static int enqueue_lane_sweep(vgpa_ctx* c, double* g_dev) {
     a.msT = c->d_msT; a.bpad = c->bpad;
     LAUNCH_TRY(c, "forward lane kernel launch", launch_ode_small(c->cfg.method, true, a, c->stream));
   }
-  c->ms_valid = false;
+  c->res.forward_wrote(Resident::Moments::TimeMajor);
   prof_mark(c, 1);
   LAUNCH_TRY(c, "obs launch", launch_obs_lane(obs_args(c), c->d_msT, c->bpad, c->d_jmT, c->stream));
   prof_mark(c, 2);
   if ((rc = run_lane_pass(c, g_dev))) return rc;
   prof_mark(c, 3);
-  c->have_state = true;
-  c->derived_valid = false;
+  c->res.lane_pass_cached();
   return g_dev ? prof_end(c, VGPA_OK) : VGPA_OK;
 }
 
 // what vgpa_fetch wants of the arrays the fused lane pass never wrote: the separate kernels over the cached (m, S)
 static int materialize_moments(vgpa_ctx* c) {
-  if (c->ms_valid) return VGPA_OK;
+  if (c->res.moments == Resident::Moments::RowMajor) return VGPA_OK;
   LAUNCH_TRY(c, "moment untranspose launch", launch_ms_untranspose(c->D, c->Np, c->B, c->bpad, c->d_msT, c->d_m, c->d_S, c->stream));
-  c->ms_valid = true;
+  c->res.moments_untransposed();
   return VGPA_OK;
 }
 
 static int materialize_derived(vgpa_ctx* c) {
-  if (c->derived_valid) return VGPA_OK;
+  if (c->res.terms) return VGPA_OK;
   int rc;
   if ((rc = materialize_moments(c))) return rc;
   // the separate backward kernel reads the jumps in the [B][M][D] layout: the observation kernel over the [B][Np] moments
   LAUNCH_TRY(c, "obs launch", launch_obs(obs_args(c), c->stream));
-  if ((rc = run_energy(c, nullptr, false))) return rc;
-  if ((rc = run_bwd(c, false, c->plan.sym_inputs))) return rc;
-  c->derived_valid = true;
-  return VGPA_OK;
+  if ((rc = run_energy(c, nullptr))) return rc;
+  return run_bwd(c, false, c->plan.sym_inputs);
 }
 
 // consumers that want S_t whole (vgpa_fetch, the operator-level kernels): the unpacked copy
 static int unpack_S(vgpa_ctx* c, const double** full) {
   *full = c->d_S;
-  if (!c->s_packed) return VGPA_OK;
+  if (c->res.S == Resident::SLayout::Whole) return VGPA_OK;
   const size_t BN = (size_t)c->B * c->Np;
   int rc;
   if ((rc = ensure(c, &c->d_Sfull, BN * c->DD))) return rc;
@@ -829,30 +845,25 @@ static int enqueue_free_energy(vgpa_ctx* c) {
   if (c->plan.lane_pass) return enqueue_lane_sweep(c, nullptr);
   int rc;
   prof_collect(c);
-  c->s_packed = c->plan.packed;
+  c->res.sweep_begins(c->plan);
   HIP_TRY(c, hipMemsetAsync(c->d_status, 0, sizeof(int32_t) * c->B, c->stream));
   prof_mark(c, 0);
   for (int r = diag_repeat("fwd"); r > 0; r--)
     if ((rc = run_fwd(c, c->in.m0, c->in.S0, c->in.Sigma, c->plan.sym_inputs))) return rc;
   prof_mark(c, 1);
   LAUNCH_TRY(c, "obs launch", launch_obs(obs_args(c), c->stream));
+  using L = Resident::DesLayout;
+  const L des = c->plan.packed ? L::Packed : c->plan.bwd_upper ? L::Upper : L::Whole;
   for (int r = diag_repeat("energy"); r > 0; r--)
-    if ((rc = run_energy(c, nullptr, c->plan.bwd_upper, c->plan.packed))) return rc;
+    if ((rc = run_energy(c, nullptr, des))) return rc;
   prof_mark(c, 2);
-  if (c->plan.grad_in_bwd) {               // F needs no backward recursion; the gradient's comes with its assembly (finish_gradient)
-    if ((rc = run_reduce(c))) return rc;
-    c->bwd_stored = false;
-    c->psi_is_q = false;
-    c->have_state = true;
-    c->derived_valid = true;
-    return VGPA_OK;
+  if (!c->plan.grad_in_bwd) {              // (else F needs no backward recursion; the gradient's comes with its assembly: finish_gradient)
+    for (int r = diag_repeat("bwd"); r > 0; r--)
+      if ((rc = run_bwd(c, false, c->plan.sym_inputs))) return rc;
+    prof_mark(c, 3);
   }
-  for (int r = diag_repeat("bwd"); r > 0; r--)
-    if ((rc = run_bwd(c, false, c->plan.sym_inputs))) return rc;
-  prof_mark(c, 3);
   if ((rc = run_reduce(c))) return rc;
-  c->have_state = true;
-  c->derived_valid = true;
+  c->res.sweep_cached();
   return VGPA_OK;
 }
 
@@ -942,7 +953,7 @@ int vgpa_create(vgpa_ctx** out, const vgpa_config* cfg) {
   HTRY(hipSetDevice(cfg->device));
   HTRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   if (hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, cfg->device) != hipSuccess || c->n_cu <= 0) c->n_cu = 256;
-  { const char* fam = getenv("VGPA_ODE_KERNEL"); c->keep_pe = fam && !strcmp(fam, "pe"); }
+  { const char* fam = getenv("VGPA_ODE_KERNEL"); c->keep_pe = fam && !strcmp(fam, "pe"); c->force_sym = fam && !strcmp(fam, "sym"); }
   // (phase events: no system-scope fence behind them -- nothing on the host reads device memory at a phase boundary; with the default
   //  flags five events cost a batched Ornstein-Uhlenbeck step 0.4 of its 1.4 ms)
   for (auto& e : c->ev) HTRY(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
@@ -1067,16 +1078,15 @@ int vgpa_solve_fwd(vgpa_ctx* c, const double* lin_a, const double* off_b, const 
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   const size_t BN = (size_t)c->B * c->Np;
   int rc;
+  c->res.taken_over();
   if ((rc = ingest_ab(c, lin_a, off_b))) return rc;
   if ((rc = upload(c, c->d_op_m0, m0, (size_t)c->D))) return rc;
   if ((rc = upload(c, c->d_op_S0, s0, c->DD))) return rc;
   if ((rc = upload(c, c->d_op_Sigma, sigma, c->DD))) return rc;
   const bool sym = is_symmetric(s0, c->D) && is_symmetric(sigma, c->D);
-  c->s_packed = false;                 // operator-level results are whole matrices
   if ((rc = run_fwd(c, {c->d_op_m0, 0}, {c->d_op_S0, 0}, {c->d_op_Sigma, 0}, sym))) return rc;
   if ((rc = download(c, mt, c->d_m, BN * c->D))) return rc;
   if ((rc = download(c, st, c->d_S, BN * c->DD))) return rc;
-  c->have_state = false;
   return vgpa_synchronize(c);
 }
 
@@ -1086,6 +1096,7 @@ int vgpa_solve_bwd(vgpa_ctx* c, const double* lin_a, const double* desde_dm, con
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   const size_t BN = (size_t)c->B * c->Np;
   int rc;
+  c->res.taken_over();
   if ((rc = ensure(c, &c->d_jm_dense, BN * c->D))) return rc;
   if ((rc = ensure(c, &c->d_js_dense, BN * c->DD))) return rc;
   if ((rc = ingest_ab(c, lin_a, nullptr))) return rc;
@@ -1093,15 +1104,12 @@ int vgpa_solve_bwd(vgpa_ctx* c, const double* lin_a, const double* desde_dm, con
   if ((rc = ensure(c, &c->d_dEs, BN * c->DD))) return rc;
   if ((rc = ensure(c, &c->d_psi, BN * c->DD))) return rc;
   if ((rc = upload(c, c->d_dEs, desde_ds, BN * c->DD))) return rc;
-  c->des_upper = false;                  // the caller's array is complete
-  c->des_packed = false;
   if ((rc = upload(c, c->d_jm_dense, deobs_dm, BN * c->D))) return rc;
   if ((rc = upload(c, c->d_js_dense, deobs_ds, BN * c->DD))) return rc;
   const bool sym = stack_symmetric(desde_ds, BN, c->D) && stack_symmetric(deobs_ds, BN, c->D);
   if ((rc = run_bwd(c, true, sym))) return rc;
   if ((rc = download(c, lam, c->d_lam, BN * c->D))) return rc;
   if ((rc = download(c, psi, c->d_psi, BN * c->DD))) return rc;
-  c->have_state = false;
   return vgpa_synchronize(c);
 }
 
@@ -1120,25 +1128,19 @@ int vgpa_energy_full(vgpa_ctx* c, const double* lin_a, const double* off_b, cons
   const int H = c->single ? 1 : 2 * D;
   const size_t BN = (size_t)c->B * c->Np;
   int rc;
+  c->res.taken_over();
   if (edf && (rc = ensure(c, &c->d_Edf, BN * c->DD))) return rc;
   if (hyper && !c->d_hyp) {
     if ((rc = dev_alloc(c, &c->d_hyp, BN * H))) return rc;
     if ((rc = dev_alloc(c, &c->d_hypT, (size_t)c->B * H))) return rc;
   }
   if ((rc = ingest_ab(c, lin_a, off_b))) return rc;
-  c->ms_valid = true;
-  c->s_packed = false;
   if ((rc = upload(c, c->d_m, mt, BN * c->D))) return rc;
   if ((rc = upload(c, c->d_S, st, BN * c->DD))) return rc;
   HIP_TRY(c, hipMemsetAsync(c->d_status, 0, sizeof(int32_t) * c->B, c->stream));
-  c->hyp_on = hyper;
-  rc = run_energy(c, edf ? c->d_Edf : nullptr);
-  c->hyp_on = false;
-  if (rc) return rc;
+  if ((rc = run_energy(c, edf ? c->d_Edf : nullptr, Resident::DesLayout::Whole, hyper))) return rc;
   if ((rc = run_reduce(c))) return rc;
-  if (hyper) {
-    LAUNCH_TRY(c, "trapezoid launch", launch_trapz_multi(c->d_hyp, c->Np, H, c->B, c->cfg.dt, c->d_hypT, c->stream));
-  }
+  if (hyper) LAUNCH_TRY(c, "trapezoid launch", launch_trapz_multi(c->d_hyp, c->Np, H, c->B, c->cfg.dt, c->d_hypT, c->stream));
   if ((rc = check_status(c))) return rc;
   std::vector<double> T(hyper ? (size_t)c->B * H : 0), esde(c->B);
   if ((rc = download(c, esde.data(), c->d_esde, esde.size()))) return rc;
@@ -1147,7 +1149,6 @@ int vgpa_energy_full(vgpa_ctx* c, const double* lin_a, const double* off_b, cons
   if (edf && (rc = download(c, edf, c->d_Edf, BN * c->DD))) return rc;
   if (desde_dm && (rc = download(c, desde_dm, c->d_dEm, BN * c->D))) return rc;
   if (desde_ds && (rc = download(c, desde_ds, c->d_dEs, BN * c->DD))) return rc;
-  c->have_state = false;
   if ((rc = vgpa_synchronize(c))) return rc;
   if (esde_out) for (int p = 0; p < c->B; p++) esde_out[p] = esde[p];
   if (!hyper) return VGPA_OK;
@@ -1183,8 +1184,7 @@ int vgpa_obs_energy(vgpa_ctx* c, const double* mt, const double* st, double* eob
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   const size_t BN = (size_t)c->B * c->Np;
   int rc;
-  c->ms_valid = true;
-  c->s_packed = false;
+  c->res.taken_over();
   if ((rc = upload(c, c->d_m, mt, BN * c->D))) return rc;
   if ((rc = upload(c, c->d_S, st, BN * c->DD))) return rc;
   ObsArgs a = obs_args(c);
@@ -1199,7 +1199,6 @@ int vgpa_obs_energy(vgpa_ctx* c, const double* mt, const double* st, double* eob
     if (deobs_dm && (rc = download(c, deobs_dm, c->d_jm_dense, BN * c->D))) return rc;
     if (deobs_ds && (rc = download(c, deobs_ds, c->d_js_dense, BN * c->DD))) return rc;
   }
-  c->have_state = false;
   return vgpa_synchronize(c);
 }
 
@@ -1251,14 +1250,14 @@ static int finish_gradient(vgpa_ctx* c, double* g_dev) {
   // cached state = (m, S): the chunked pass recomputes the energy terms on its way back
   if (c->stream_ld) return prof_end(c, stream_pass(c, g_dev));
   // gradient(x, eval_fun=False) behind a fused F: the pass again, now with the recursion
-  if (c->plan.lane_pass && !c->derived_valid) return prof_end(c, run_lane_pass(c, g_dev));
+  if (c->plan.lane_pass && !c->res.terms) return prof_end(c, run_lane_pass(c, g_dev));
   int rc = VGPA_OK;
-  if (c->plan.grad_in_bwd_now && c->s_packed) {   // backward recursion + gradient assembly in one kernel (phase "bwd"; "grad" is empty)
+  if (c->plan.grad_in_bwd_now && c->res.S == Resident::SLayout::Packed) {   // backward recursion + gradient assembly in one kernel (phase "bwd"; "grad" is empty)
     for (int r = diag_repeat("bwd"); r > 0 && rc == VGPA_OK; r--) rc = run_bwd(c, false, c->plan.sym_inputs, g_dev);
     prof_mark(c, 3);
     return prof_end(c, rc);
   }
-  if (!c->bwd_stored) {                    // (F-only evaluation before: the recursion now, with Q''_t for the assembly kernel)
+  if (c->res.bwd == Resident::Bwd::None) {   // (F-only evaluation before: the recursion now, with Q''_t for the assembly kernel)
     for (int r = diag_repeat("bwd"); r > 0 && rc == VGPA_OK; r--) rc = run_bwd(c, false, c->plan.sym_inputs);
     prof_mark(c, 3);
   }
@@ -1274,7 +1273,7 @@ int vgpa_gradient(vgpa_ctx* c, const double* x_or_null, double* g) {
   if (x_or_null) {
     if ((rc = ingest_x(c, x_or_null, false))) return rc;
     if ((rc = enqueue_sweep(c, c->d_g))) return rc;
-  } else if (!c->have_state) {
+  } else if (!c->res.cached) {
     return fail(c, VGPA_ERR_STATE, "gradient(x, eval_fun=False) needs the state cached by a previous free_energy");
   } else if ((rc = finish_gradient(c, c->d_g))) return rc;
   if ((rc = download(c, g, c->d_g, (size_t)c->B * c->len_x))) return rc;
@@ -1310,7 +1309,7 @@ int vgpa_sweep_dev(vgpa_ctx* c, const double* x_dev, double* f_host, double* g_d
 
 int vgpa_energy_parts(vgpa_ctx* c, double* e0, double* esde, double* eobs) {
   if (!c) return VGPA_ERR_ARG;
-  if (!c->have_state) return fail(c, VGPA_ERR_STATE, "no cached state");
+  if (!c->res.cached) return fail(c, VGPA_ERR_STATE, "no cached state");
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   int rc;
   if (e0) for (int p = 0; p < c->B; p++) e0[p] = e0_of(c, p);
@@ -1328,7 +1327,7 @@ int vgpa_theta_gradient(vgpa_ctx* c, double* out) {
   if (!c || !out) return fail(c, VGPA_ERR_ARG, "null argument");
   if (!c->full) return fail(c, VGPA_ERR_STATE, "context was created without m0/s0/observations (ODE-only)");
   if (c->stream_ld) return fail(c, VGPA_ERR_UNSUPPORTED, "dF/dtheta is not built for the time-chunked large-D sweep");
-  if (!c->have_state) return fail(c, VGPA_ERR_STATE, "no cached state: theta_gradient needs the state cached by a previous free_energy / sweep");
+  if (!c->res.cached) return fail(c, VGPA_ERR_STATE, "no cached state: theta_gradient needs the state cached by a previous free_energy / sweep");
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   const int D = c->D, B = c->B, Np = c->Np, nth = c->cfg.n_theta;
   const size_t BN = (size_t)B * Np;
@@ -1384,13 +1383,13 @@ int vgpa_theta_gradient(vgpa_ctx* c, double* out) {
 
 int vgpa_fetch(vgpa_ctx* c, int which, double* out) {
   if (!c || !out) return fail(c, VGPA_ERR_ARG, "null argument");
-  if (!c->have_state) return fail(c, VGPA_ERR_STATE, "no cached state: call free_energy first");
+  if (!c->res.cached) return fail(c, VGPA_ERR_STATE, "no cached state: call free_energy first");
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   const size_t BN = (size_t)c->B * c->Np;
   int rc = VGPA_OK;
   if ((rc = materialize_moments(c))) return rc;
   if (which != VGPA_FETCH_MT && which != VGPA_FETCH_ST && which != VGPA_FETCH_EDF && (rc = materialize_derived(c))) return rc;
-  if ((which == VGPA_FETCH_LAMT || which == VGPA_FETCH_PSIT) && !c->bwd_stored && !c->stream_ld && (rc = run_bwd(c, false, c->plan.sym_inputs))) return rc;
+  if ((which == VGPA_FETCH_LAMT || which == VGPA_FETCH_PSIT) && c->res.bwd == Resident::Bwd::None && !c->stream_ld && (rc = run_bwd(c, false, c->plan.sym_inputs))) return rc;
   switch (which) {
     case VGPA_FETCH_MT: rc = download(c, out, c->d_m, BN * c->D); break;
     case VGPA_FETCH_ST: {
@@ -1402,24 +1401,24 @@ int vgpa_fetch(vgpa_ctx* c, int which, double* out) {
     case VGPA_FETCH_LAMT: rc = download(c, out, c->d_lam, BN * c->D); break;
     case VGPA_FETCH_PSIT:
       if (!c->d_psi || c->stream_ld) return fail(c, VGPA_ERR_UNSUPPORTED, "Psi_t is not kept by the time-chunked large-D sweep");
-      if (c->psi_is_q) {               // recover Psi_t = (Sigma^-1 A_t - Q''_t) / 2 in place: from here on d_psi holds Psi_t again
+      if (c->res.bwd == Resident::Bwd::Q) {   // recover Psi_t = (Sigma^-1 A_t - Q''_t) / 2 in place: from here on d_psi holds Psi_t again
         LAUNCH_TRY(c, "Psi_t recovery launch", launch_psi_from_q(c->B, c->Np, c->D, c->len_x, ctx_A(c), c->in.isg.rows, c->in.isg.stride, c->d_psi, c->stream));
-        c->psi_is_q = false;
+        c->res.psi_recovered();
       }
       rc = download(c, out, c->d_psi, BN * c->DD); break;
     case VGPA_FETCH_EFX: rc = download(c, out, c->d_Ef, BN * c->D); break;
     case VGPA_FETCH_DESDE_DM: rc = download(c, out, c->d_dEm, BN * c->D); break;
     case VGPA_FETCH_DESDE_DS:
       if (!c->d_dEs || c->stream_ld) return fail(c, VGPA_ERR_UNSUPPORTED, "dEsde_dS is not kept by the time-chunked large-D sweep");
-      if (c->des_packed) {             // whole matrices into the scratch copy the unpacked S_t uses too (the packed stream stays as it is)
+      if (c->res.dEs == Resident::DesLayout::Packed) {   // whole matrices into the scratch copy the unpacked S_t uses too (the packed stream stays as it is)
         if ((rc = ensure(c, &c->d_Sfull, BN * c->DD))) return rc;
         LAUNCH_TRY(c, "unpack launch", launch_unpack_lower(BN, c->D, c->d_dEs, c->d_Sfull, c->stream));
         rc = download(c, out, c->d_Sfull, BN * c->DD);
         break;
       }
-      if (c->des_upper) {
+      if (c->res.dEs == Resident::DesLayout::Upper) {
         LAUNCH_TRY(c, "mirror launch", launch_mirror_upper(BN, c->D, c->d_dEs, c->stream));
-        c->des_upper = false;
+        c->res.des_mirrored();
       }
       rc = download(c, out, c->d_dEs, BN * c->DD); break;
     case VGPA_FETCH_ESDE_T: rc = download(c, out, c->d_et, BN); break;
@@ -1438,7 +1437,7 @@ int vgpa_fetch(vgpa_ctx* c, int which, double* out) {
 
 int vgpa_gradient_dev(vgpa_ctx* c, double* g_dev) {
   if (!c || !g_dev) return fail(c, VGPA_ERR_ARG, "null argument");
-  if (!c->have_state) return fail(c, VGPA_ERR_STATE, "gradient(x, eval_fun=False) needs the state cached by a previous free_energy");
+  if (!c->res.cached) return fail(c, VGPA_ERR_STATE, "gradient(x, eval_fun=False) needs the state cached by a previous free_energy");
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   int rc;
   if ((rc = finish_gradient(c, g_dev))) return rc;
@@ -1450,7 +1449,7 @@ int vgpa_gradient_dev(vgpa_ctx* c, double* g_dev) {
 // instead of reading freed memory.
 int vgpa_release_x(vgpa_ctx* c) {
   if (!c) return VGPA_ERR_ARG;
-  if (c->xcur != c->d_x) { c->xcur = nullptr; c->have_state = false; }
+  if (c->xcur != c->d_x) { c->xcur = nullptr; c->res.cache_dropped(); }
   return VGPA_OK;
 }
 
@@ -1560,7 +1559,7 @@ int vgpa_set_problem_data(vgpa_ctx* c, const int64_t* obs_t, const double* obs_y
   c->s0_rows_sym = !s0 || stack_symmetric(s0, (size_t)B, D);       // (a non-symmetric s0 row: both products literally)
   make_plan(c);
   c->pt_dense_zeroed = false;
-  c->have_state = false;            // (like vgpa_release_x: the cached state belongs to the old inputs)
+  c->res.cache_dropped();           // (like vgpa_release_x: the cached state belongs to the old inputs)
   return VGPA_OK;
 }
 
@@ -1593,7 +1592,7 @@ int vgpa_set_problem_params(vgpa_ctx* c, const double* theta, const double* sigm
   if (D > kMaxSmallD && !same_sigma)
     return fail(c, VGPA_ERR_UNSUPPORTED, "per-problem Sigma exists for D <= %d (D = %d shares the Sigma of vgpa_config)", kMaxSmallD, D);
   HIP_TRY(c, hipSetDevice(c->cfg.device));
-  c->have_state = false;            // (like vgpa_set_problem_data: the cached state belongs to the old parameters)
+  c->res.cache_dropped();           // (like vgpa_set_problem_data: the cached state belongs to the old parameters)
   BatchInputs& in = c->in;
   in.theta = in.sig1 = in.qs = {}; in.Sigma = {c->d_Sigma, 0}; in.isig = {c->d_isig, 0}; in.isg = {c->d_isg, 0};
   // every row at the shared parameters: the shared kernels (the same results, bit for bit); else every row is in force -- above D = 64
@@ -1636,7 +1635,7 @@ int vgpa_dev_free(vgpa_ctx* c, void* ptr) {
   struct Restore { int d; ~Restore() { if (d >= 0) (void)hipSetDevice(d); } } restore{prev};
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (ptr == (const void*)c->xcur) { c->xcur = nullptr; c->have_state = false; }
+  if (ptr == (const void*)c->xcur) { c->xcur = nullptr; c->res.cache_dropped(); }
   for (size_t i = 0; i < c->user_allocs.size(); i++)
     if (c->user_allocs[i] == ptr) { c->user_allocs[i] = c->user_allocs.back(); c->user_allocs.pop_back(); break; }
   HIP_TRY(c, hipFree(ptr));
