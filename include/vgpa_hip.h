@@ -265,6 +265,43 @@ int vgpa_set_problem_params(vgpa_ctx* ctx, const double* theta, const double* si
 /* 1 if the context runs the time-chunked large-D sweep (VGPA_FLAG_STREAM_LARGE_D or chosen for lack of memory) */
 int vgpa_is_streaming(vgpa_ctx* ctx);
 
+/* Which kernels the context's fused sweep runs and what its device buffers hold right now -- for TESTS AND DIAGNOSTICS: a test
+ * that names a kernel path asserts here that it is on it.  Read-only: the call changes nothing, launches nothing, and nothing on
+ * the hot path calls it.  The fields are the library's host-side plan (decided in vgpa_create, again when vgpa_set_problem_data /
+ * vgpa_set_problem_params change the form of the inputs) and its record of the buffers (DESIGN.md s.4.0 has both tables). */
+enum { VGPA_STEPPER_LARGE_D = 0,  /* D > 64: the per-stage drivers                                   */
+       VGPA_STEPPER_LANE = 1,     /* D <= 4: one lane per problem                                    */
+       VGPA_STEPPER_WAVE = 2,     /* 2 <= D <= 4: 16 lanes per problem                               */
+       VGPA_STEPPER_MFMA = 3,     /* 5 <= D <= 64, symmetric inputs: the matrix-core kernels         */
+       VGPA_STEPPER_GENERIC = 4   /* one workgroup per problem, no symmetry assumed                  */ };
+enum { VGPA_MOMENTS_ROW_MAJOR = 0, VGPA_MOMENTS_TIME_MAJOR = 1 };   /* m_t / S_t: the [B][Np] arrays; the lane pass's own layout alone */
+enum { VGPA_LAYOUT_WHOLE = 0,     /* whole D x D matrices                                            */
+       VGPA_LAYOUT_UPPER = 1,     /* whole matrices of which only the upper triangle is written      */
+       VGPA_LAYOUT_PACKED = 2     /* packed lower triangles, D (D + 1) / 2 each                      */ };
+enum { VGPA_BWD_NONE = 0,         /* nothing of the cached state is in lam_t / Psi_t's buffers       */
+       VGPA_BWD_PSI = 1,          /* lam_t and Psi_t                                                 */
+       VGPA_BWD_Q = 2             /* lam_t and Q''_t = Sigma^-1 A_t - 2 Psi_t                        */ };
+typedef struct {
+  /* the plan: what a fused sweep WILL run */
+  int32_t fwd, bwd;               /* VGPA_STEPPER_* of the two sweep directions                      */
+  int32_t sym_units;              /* matrix-core family: symmetric-unit / fragment-cover kernels     */
+  int32_t launch_sym_units;       /* ... what the launcher is told (sym_units, or VGPA_ODE_KERNEL=sym) */
+  int32_t lane_pass;              /* the objective is the fused lane pass                            */
+  int32_t bwd_upper;              /* the backward kernel reads the upper triangle of dEsde_dS only   */
+  int32_t store_q;                /* ... and stores Q''_t where Psi_t would be                       */
+  int32_t packed;                 /* ... S_t and dEsde_dS travel as packed lower triangles           */
+  int32_t grad_in_bwd;            /* ... the backward kernel can assemble the gradient               */
+  int32_t grad_in_bwd_now;        /* ... and does, at this batch size                                */
+  /* the record: what the buffers DO hold */
+  int32_t cached;                 /* a fused sweep's state is cached                                 */
+  int32_t moments;                /* VGPA_MOMENTS_*                                                  */
+  int32_t S;                      /* VGPA_LAYOUT_WHOLE or _PACKED: S_t                               */
+  int32_t dEs;                    /* VGPA_LAYOUT_*: dEsde_dS                                         */
+  int32_t bwd_holds;              /* VGPA_BWD_*                                                      */
+  int32_t terms;                  /* dEsde_dm / dEsde_dS / <f> / E_sde(t) belong to the cached moments */
+} vgpa_path;
+int vgpa_path_info(vgpa_ctx* ctx, vgpa_path* out);   /* VGPA_ERR_ARG for a null argument */
+
 /* raw device memory helpers so that hosts without a HIP binding can own device buffers; whatever has not been returned
  * through vgpa_dev_free when the context is destroyed is freed with it */
 int vgpa_dev_alloc(vgpa_ctx* ctx, uint64_t bytes, void** out);

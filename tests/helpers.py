@@ -75,3 +75,13 @@ def split_x(x, n, d):
     if d == 1:
         return x[:n], x[n:]
     return x[:n * d * d].reshape(n, d, d), x[n * d * d:].reshape(n, d)
+
+
+def block_rel_errs(g, g_ref, n, d):
+    """(gLa, gLb) errors of one problem's gradient [gLa (n, d, d) | gLb (n, d)], each max-norm relative to ITS OWN block of the
+    reference: conftest.rel_err over the whole vector scales gLb by max|gLa|, which is ten times larger on the Lorenz-96 problems."""
+    from conftest import rel_err
+    g, g_ref = np.ravel(g), np.ravel(g_ref)
+    k = n * d * d
+    assert g.size == g_ref.size == k + n * d
+    return rel_err(g[:k], g_ref[:k]), rel_err(g[k:], g_ref[k:])

@@ -5,6 +5,8 @@ GPU suite (-m gpu): edge cases of the hot path through the C ABI, all against th
   * shortest grids (Np = 2, 3), a single observation, observations at the first / last index
   * odd batches, the four-waves-per-problem variant of the MFMA steppers, very small dt
 """
+import os
+
 import numpy as np
 import pytest
 
@@ -22,7 +24,12 @@ def spd(rng, d, scale=1.0, jitter=0.3):
     return scale * (np.eye(d) + jitter * (q + q.T) / 2.0 + jitter * q.dot(q.T))
 
 
-def make_problem(model, d, n_pts, method="rk4", dt=0.01, seed=5, dense=False, obs_at=None, h_op=None):
+def make_problem(model, d, n_pts, method="rk4", dt=0.01, seed=5, dense=False, obs_at=None, h_op=None, sigma="diag"):
+    """sigma: the form of the system noise of the n-D models -- "diag" (distinct diagonal entries: the default), "iso" (3.5 I: what
+    the Q'' stream, the packed layouts and the gradient waves of the backward kernel take) or "dense"; every other input is the same
+    for the three.  dense=True: dense Sigma, s0 and R."""
+    assert sigma in ("diag", "iso", "dense")
+    form = "dense" if dense else sigma
     rng = np.random.default_rng(seed)
     single = model in ("OU", "DW")
     if single:
@@ -31,7 +38,9 @@ def make_problem(model, d, n_pts, method="rk4", dt=0.01, seed=5, dense=False, ob
         r = 0.04
     else:
         theta = np.array([10.0, 28.0, 2.667]) if model == "L63" else 8.0
-        sigma = spd(rng, d, 4.0) if dense else np.diag(3.0 + rng.random(d))
+        sigma = spd(rng, d, 4.0) if form == "dense" else np.diag(3.0 + rng.random(d))
+        if form == "iso":
+            sigma = 3.5 * np.eye(d)
         m0 = (8.0 if model == "L96" else 1.0) + rng.standard_normal(d)
         s0 = spd(rng, d, 0.2, 0.1) if dense else 0.2 * np.eye(d)
         mu0, tau0 = np.ones(d), 0.5 * np.eye(d)
@@ -49,6 +58,17 @@ def make_problem(model, d, n_pts, method="rk4", dt=0.01, seed=5, dense=False, ob
         b = 8.0 * m0 + rng.standard_normal((n_pts, d))
         x = np.concatenate((a.ravel(), b.ravel()))
     return p, x
+
+
+def fused_grad_switch():
+    """VGPA_FUSED_GRAD as the library reads it: "" (the backward kernel assembles the gradient from 64 problems on), "0" never, "1"
+    always -- so that the path assertions also hold in a run of the whole suite under either value."""
+    return os.environ.get("VGPA_FUSED_GRAD", "")[:1]
+
+
+def with_sigma_forms(cases, ids):
+    """Every case with the default diagonal Sigma under the id it always had, then again with Sigma = sigma^2 I (id + "-iso")."""
+    return [pytest.param(*c, form, id=i + tail) for form, tail in (("diag", ""), ("iso", "-iso")) for c, i in zip(cases, ids)]
 
 
 def gpu_context(p, batch=1, flags=0):
@@ -125,20 +145,35 @@ def test_symmetric_unit_steppers_dense_inputs_and_batches(model, d):
     ctx.close()
 
 
-@pytest.mark.parametrize("d,method", [(40, "rk4"), (36, "rk2"), (33, "rk4")])
-def test_q_stream_of_the_batched_sweeps(d, method):
-    """33 <= D <= 40, RK2 / RK4 on the symmetric-unit kernels: the backward kernel leaves Q''_t = Sigma^-1 A_t - 2 Psi_t where Psi_t
-    would be (the gradient assembly then reads one matrix stream less) and VGPA_FETCH_PSIT recovers Psi_t.  Against the same
-    sweep with VGPA_FLAG_KEEP_PSI (Psi_t stored, A_t re-read): F identical, gradient and Psi_t equal to rounding; a second fetch
-    and a gradient(eval_fun=False) after the recovery still see consistent data."""
-    p, x = make_problem("L96", d, 21, method=method)
+@pytest.mark.parametrize("d,method,sigma", with_sigma_forms([(40, "rk4"), (36, "rk2"), (33, "rk4")], ["40-rk4", "36-rk2", "33-rk4"]))
+def test_q_stream_of_the_batched_sweeps(d, method, sigma):
+    """33 <= D <= 40, RK2 / RK4 on the symmetric-unit kernels with Sigma = sigma^2 I ("iso"): the backward kernel leaves
+    Q''_t = Sigma^-1 A_t - 2 Psi_t where Psi_t would be (the gradient assembly then reads one matrix stream less), S_t and dEsde_dS
+    travel as packed lower triangles, and VGPA_FETCH_PSIT recovers Psi_t.  Against the same sweep with VGPA_FLAG_KEEP_PSI (Psi_t
+    stored, A_t re-read, whole matrices): F identical, gradient and Psi_t equal to rounding; a second fetch and a
+    gradient(eval_fun=False) after the recovery still see consistent data.  The path is asserted before the numbers (Context.plan,
+    Context.resident).  "diag": a diagonal Sigma that is not isotropic -- the same comparison where the flag only switches the
+    dEsde_dS layout (upper triangle / whole) and Psi_t is stored on both contexts."""
+    p, x = make_problem("L96", d, 21, method=method, sigma=sigma)
     ctx_q = gpu_context(p, flags=FLAG_SYM_UNITS)
     ctx_k = gpu_context(p, flags=FLAG_SYM_UNITS | FLAG_KEEP_PSI)
+    iso = sigma == "iso"
+    plan_q, plan_k = ctx_q.plan(), ctx_k.plan()
+    assert plan_q["fwd"] == plan_q["bwd"] == plan_k["fwd"] == plan_k["bwd"] == "mfma" and plan_q["sym_units"] and plan_k["sym_units"]
+    assert plan_q["bwd_upper"] and plan_q["store_q"] == plan_q["packed"] == iso
+    assert not (plan_k["bwd_upper"] or plan_k["store_q"] or plan_k["packed"])
+    fused = iso and method == "rk4" and fused_grad_switch() == "1"
+    assert plan_q["grad_in_bwd_now"] == fused                              # (one problem: backward kernel, then k_grad_mfma_q)
     f_q, g_q = ctx_q.sweep(x)
     f_k, g_k = ctx_k.sweep(x)
     assert f_q == f_k
     assert rel_err(g_q, g_k) < 1e-13
+    res_q, res_k = ctx_q.resident(), ctx_k.resident()
+    assert res_q["cached"] and res_q["bwd"] == ("none" if fused else "q" if iso else "psi") and res_q["S"] == ("packed" if iso else "whole")
+    assert res_q["dEs"] == ("packed" if iso else "upper")
+    assert res_k["cached"] and (res_k["bwd"], res_k["S"], res_k["dEs"]) == ("psi", "whole", "whole")
     psi_q, psi_k = ctx_q.fetch("psit"), ctx_k.fetch("psit")
+    assert ctx_q.resident()["bwd"] == "psi" and ctx_k.resident()["bwd"] == "psi"      # Q''_t -> Psi_t across the first fetch
     assert rel_err(psi_q, psi_k) < 1e-13
     assert np.array_equal(ctx_q.fetch("psit"), psi_q)                      # recovered once, in place
     # dEsde_dS: ctx_q's energy kernel writes packed lower triangles (unpacked on the way out), ctx_k's the upper triangle of whole
@@ -147,26 +182,40 @@ def test_q_stream_of_the_batched_sweeps(d, method):
     assert np.array_equal(ds_q, np.swapaxes(ds_q, 1, 2))
     assert rel_err(ds_q, ds_k) < 1e-13
     assert np.array_equal(ctx_q.fetch("dEsde_ds"), ds_q)                     # (the packed stream is left as it is: a second fetch sees the same)
+    assert ctx_q.resident()["dEs"] == ("packed" if iso else "whole")      # (... an upper triangle is mirrored in place, once)
     assert rel_err(ctx_q.gradient(None), g_k) < 1e-13                      # assembled from the recovered Psi_t now
     _, g_ref, st = vo.sweep(p, x, faithful=False)
     assert rel_err(g_q, g_ref) < TOL and rel_err(np.asarray(psi_q).reshape(np.shape(st["psit"])), st["psit"]) < TOL
     ctx_q.close(); ctx_k.close()
 
 
-@pytest.mark.parametrize("d,n_pts,obs", [(40, 2, [1]), (40, 3, [0]), (40, 4, [1, 2]), (40, 5, [3]), (40, 24, None), (33, 3, [1]), (33, 11, None),
-                                         (36, 4, [2]), (37, 9, None), (39, 2, [0])])
-def test_gradient_waves_of_the_backward_kernel(d, n_pts, obs):
-    """Batches of >= 64 Lorenz-96 problems with 33 <= D <= 40 under RK4: the backward kernel assembles the gradient on a third set
+WAVE_CASES = [(40, 2, [1]), (40, 3, [0]), (40, 4, [1, 2]), (40, 5, [3]), (40, 24, None), (33, 3, [1]), (33, 11, None), (36, 4, [2]), (37, 9, None),
+              (39, 2, [0])]
+
+
+@pytest.mark.parametrize("d,n_pts,obs,sigma", with_sigma_forms(WAVE_CASES, ["%d-%d-%s" % (d, n, "None" if obs is None else "obs%d" % i)
+                                                                            for i, (d, n, obs) in enumerate(WAVE_CASES)]))
+def test_gradient_waves_of_the_backward_kernel(d, n_pts, obs, sigma):
+    """Batches of >= 64 Lorenz-96 problems with 33 <= D <= 40 and Sigma = sigma^2 I ("iso") under RK4: the backward kernel assembles the gradient on a third set
     of waves (k_ode_sym, GF; grad_waves) -- a two-step pipeline per grid point with its own first / second / last steps, so every
     short grid is a case of its own, and every D < 40 exercises the padding.  Every problem against the same sweep with
     VGPA_FLAG_KEEP_PSI (backward kernel + separate assembly), some against the oracle; lam_t / Psi_t, which the fused kernel keeps to
-    itself, as vgpa_fetch materialises them; free_energy (no backward recursion at all) followed by gradient(None)."""
+    itself, as vgpa_fetch materialises them; free_energy (no backward recursion at all) followed by gradient(None).  The path is
+    asserted first.  "diag": a diagonal Sigma that is not isotropic -- the same checks on the backward kernel that reads the upper
+    triangle of dEsde_dS and stores Psi_t, followed by the separate assembly."""
     batch = 67
-    p, x = make_problem("L96", d, n_pts, method="rk4", obs_at=obs)
+    p, x = make_problem("L96", d, n_pts, method="rk4", obs_at=obs, sigma=sigma)
     rng = np.random.default_rng(23)
     xb = x[None, :] + 0.02 * rng.standard_normal((batch, x.size))
     ctx, ctx_k = gpu_context(p, batch=batch), gpu_context(p, batch=batch, flags=FLAG_KEEP_PSI)
+    iso = sigma == "iso"
+    plan, plan_k = ctx.plan(), ctx_k.plan()
+    assert plan["bwd"] == "mfma" and plan["sym_units"] and plan["bwd_upper"]
+    fused = iso and fused_grad_switch() != "0"
+    assert plan["store_q"] == plan["packed"] == iso and plan["grad_in_bwd"] == plan["grad_in_bwd_now"] == fused
+    assert not (plan_k["bwd_upper"] or plan_k["store_q"] or plan_k["packed"] or plan_k["grad_in_bwd_now"])
     fb, gb = ctx.sweep(xb)
+    assert ctx.resident()["bwd"] == ("none" if fused else "q" if iso else "psi")          # (the gradient waves keep Psi_t to themselves)
     fk, gk = ctx_k.sweep(xb)
     assert np.array_equal(fb, fk)
     assert max(rel_err(gb[i], gk[i]) for i in range(batch)) < 1e-12
@@ -184,12 +233,12 @@ def test_gradient_waves_of_the_backward_kernel(d, n_pts, obs):
     ctx.close(); ctx_k.close()
 
 
-def test_fused_gradient_kernel_below_its_default_batch_size():
+def test_fused_gradient_kernel_below_its_default_batch_size(sigma="diag"):
     """Below 64 problems per context the default is the backward kernel followed by the separate assembly; VGPA_FUSED_GRAD=1 forces the
-    kernel with the gradient waves (read once per process: a child process).  One problem, three problems and a padded dimension
-    against the default path of this process and the oracle."""
+    kernel with the gradient waves where the plan has it (Sigma = sigma^2 I, "iso"; read once per process: a child process, which
+    prints its plan).  One problem, three problems and a padded dimension against the default path of this process and the
+    oracle.  "diag": the switch has nothing to select, and the child must say so."""
     import json
-    import os
     import subprocess
     import sys
     cases = ((40, 9, 1), (40, 14, 3), (35, 6, 2))
@@ -199,23 +248,30 @@ def test_fused_gradient_kernel_below_its_default_batch_size():
         "import test_gpu_edge_cases as t\n"
         "out = []\n"
         "for d, n, batch in %r:\n"
-        "    p, x = t.make_problem('L96', d, n, method='rk4')\n"
+        "    p, x = t.make_problem('L96', d, n, method='rk4', sigma=%r)\n"
         "    ctx = t.gpu_context(p, batch=batch)\n"
         "    xb = np.stack([x + 0.01 * i for i in range(batch)]) if batch > 1 else x\n"
         "    f, g = ctx.sweep(xb)\n"
-        "    out.append({'f': [float(v) for v in np.atleast_1d(f)], 'g': np.asarray(g).ravel().tolist()})\n"
+        "    out.append({'f': [float(v) for v in np.atleast_1d(f)], 'g': np.asarray(g).ravel().tolist(), 'plan': ctx.plan(),\n"
+        "                'bwd': ctx.resident()['bwd']})\n"
         "    ctx.close()\n"
-        "print(json.dumps(out))\n" % (os.path.dirname(__file__), cases))
+        "print(json.dumps(out))\n" % (os.path.dirname(__file__), cases, sigma))
     env = dict(os.environ)
     env["VGPA_FUSED_GRAD"] = "1"
     r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     fused = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("[")][-1])
+    iso = sigma == "iso"
+    forced_here = fused_grad_switch() == "1"          # (a run of the whole suite under the switch)
     for (d, n, batch), got in zip(cases, fused):
-        p, x = make_problem("L96", d, n, method="rk4")
+        p, x = make_problem("L96", d, n, method="rk4", sigma=sigma)
         ctx = gpu_context(p, batch=batch)
+        assert got["plan"]["packed"] == got["plan"]["grad_in_bwd"] == got["plan"]["grad_in_bwd_now"] == iso
+        assert got["bwd"] == ("none" if iso else "psi")
+        assert ctx.plan()["packed"] == iso and ctx.plan()["grad_in_bwd_now"] == (iso and forced_here)
         xb = np.stack([x + 0.01 * i for i in range(batch)]) if batch > 1 else x
         f, g = ctx.sweep(xb)
+        assert ctx.resident()["bwd"] == ("none" if iso and forced_here else "q" if iso else "psi")
         ctx.close()
         assert np.array_equal(np.atleast_1d(f), np.asarray(got["f"]))                   # F: the same kernels either way
         assert rel_err(np.asarray(got["g"]), np.asarray(g).ravel()) < 1e-12              # the gradient: another product order
@@ -223,17 +279,28 @@ def test_fused_gradient_kernel_below_its_default_batch_size():
         assert rel_err(np.asarray(got["g"]).reshape(batch, -1)[0], g_ref) < TOL
 
 
-@pytest.mark.parametrize("method", ["rk4", "heun"])
-def test_more_problems_than_compute_units(method):
+def test_fused_gradient_kernel_below_its_default_batch_size_with_isotropic_sigma():
+    """The same with Sigma = sigma^2 I: the paths the docstring above names, asserted there."""
+    test_fused_gradient_kernel_below_its_default_batch_size("iso")
+
+
+@pytest.mark.parametrize("method,sigma", with_sigma_forms([("rk4",), ("heun",)], ["rk4", "heun"]))
+def test_more_problems_than_compute_units(method, sigma):
     """bench.py's regime: a batch larger than twice the CU count, so that the default dispatch picks the symmetric-unit steppers and
-    two (in the last round of the grid: one) workgroups share a CU.  EVERY problem's F and gradient against the oracle."""
+    two (in the last round of the grid: one) workgroups share a CU.  EVERY problem's F and gradient against the oracle.  "iso" is
+    bench.py's Sigma = sigma^2 I: under RK4 the packed layouts, the Q'' kernels and the backward kernel that assembles the gradient
+    (asserted); Heun has neither there.  "diag": the upper-triangle layout of dEsde_dS, Psi_t stored, separate assembly."""
     import torch
     n_cu = torch.cuda.get_device_properties(0).multi_processor_count
     batch = 2 * n_cu + 37
-    p, x = make_problem("L96", 40, 12, method=method)
+    p, x = make_problem("L96", 40, 12, method=method, sigma=sigma)
     rng = np.random.default_rng(17)
     xb = x[None, :] + 0.02 * rng.standard_normal((batch, x.size))
     ctx = gpu_context(p, batch=batch)
+    plan = ctx.plan()
+    assert plan["fwd"] == plan["bwd"] == "mfma" and plan["sym_units"] and plan["bwd_upper"]
+    q = sigma == "iso" and method == "rk4"
+    assert plan["store_q"] == plan["packed"] == q and plan["grad_in_bwd_now"] == (q and fused_grad_switch() != "0")
     fb, gb = ctx.sweep(xb)
     worst = 0.0
     for i in range(batch):
@@ -397,22 +464,23 @@ def test_lane_pass_with_a_non_symmetric_initial_covariance():
     ctx.close(); ref.close()
 
 
-def test_diagnostic_phase_repeat_leaves_the_results_alone():
+def test_diagnostic_phase_repeat_leaves_the_results_alone(sigma="diag"):
     """VGPA_DIAG_REPEAT=<phase>:<n> (tools/power_per_kernel.sh: one kernel of the fused sweep held on the chip for clock / power
     samples) launches a phase n times; every phase is a pure function of its inputs, so F and the gradient must not move in any
-    bit.  The variable is read once per process: child processes."""
+    bit.  The variable is read once per process: child processes.  "iso": the packed layouts and the Q'' kernels of Sigma = sigma^2 I
+    (each child prints its plan); "diag": whole matrices, the upper triangle of dEsde_dS."""
     import json
-    import os
     import subprocess
     import sys
     code = (
         "import sys, json, numpy as np\n"
         "sys.path.insert(0, %r)\n"
         "import test_gpu_edge_cases as t\n"
-        "p, x = t.make_problem('L96', 40, 30)\n"
+        "p, x = t.make_problem('L96', 40, 30, sigma=%r)\n"
         "ctx = t.gpu_context(p, batch=2)\n"
         "f, g = ctx.sweep(np.stack([x, x + 0.01]))\n"
-        "print(json.dumps({'f': [float(v).hex() for v in f], 'g': float(np.abs(g).sum()).hex()}))\n" % os.path.dirname(__file__))
+        "print(json.dumps({'f': [float(v).hex() for v in f], 'g': float(np.abs(g).sum()).hex(), 'plan': ctx.plan(),\n"
+        "                  'resident': ctx.resident()}))\n" % (os.path.dirname(__file__), sigma))
     outs = []
     for spec in ("", "fwd:3", "energy:2", "bwd:3", "grad:2"):
         env = dict(os.environ)
@@ -423,15 +491,26 @@ def test_diagnostic_phase_repeat_leaves_the_results_alone():
         assert r.returncode == 0, r.stderr[-2000:]
         outs.append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]))
     assert all(o == outs[0] for o in outs[1:]), outs
+    iso = sigma == "iso"
+    plan, res = outs[0]["plan"], outs[0]["resident"]
+    assert plan["bwd_upper"] and plan["store_q"] == plan["packed"] == iso and plan["grad_in_bwd"] == (iso and fused_grad_switch() != "0")
+    if fused_grad_switch() != "1":
+        assert not plan["grad_in_bwd_now"]                # (two problems: every phase is a kernel of its own)
+        assert (res["S"], res["dEs"], res["bwd"]) == (("packed", "packed", "q") if iso else ("whole", "upper", "psi"))
 
 
-def test_stepper_variants_of_the_fragment_cover_agree():
+def test_diagnostic_phase_repeat_leaves_the_results_alone_with_isotropic_sigma():
+    """The same with Sigma = sigma^2 I: the paths the docstring above names, asserted there."""
+    test_diagnostic_phase_repeat_leaves_the_results_alone("iso")
+
+
+def test_stepper_variants_of_the_fragment_cover_agree(sigma="diag"):
     """33 <= D <= 40 on the fragment-cover steppers: with four or eight helper waves beside the four product waves of a workgroup (the
     default up to one problem per CU: the chores of a stage off the product waves' issue slots) and without them the same operations run in the same
     order -- F and the gradient must not differ in any bit.  The switch is read once per process: child processes;
-    RK4 and Heun, an unpadded and a padded dimension, one problem and a small batch."""
+    RK4, Heun and RK2, an unpadded and two padded dimensions, one problem and small batches.  "iso": Sigma = sigma^2 I, the packed
+    layouts and Q''_t of the RK4 / RK2 cases (each child prints its plans); "diag": whole matrices."""
     import json
-    import os
     import subprocess
     import sys
     code = (
@@ -440,13 +519,14 @@ def test_stepper_variants_of_the_fragment_cover_agree():
         "import test_gpu_edge_cases as t\n"
         "out = {}\n"
         "for d, method, batch in ((40, 'rk4', 1), (37, 'heun', 3), (33, 'rk2', 2)):\n"
-        "    p, x = t.make_problem('L96', d, 14, method=method)\n"
+        "    p, x = t.make_problem('L96', d, 14, method=method, sigma=%r)\n"
         "    ctx = t.gpu_context(p, batch=batch)\n"
         "    xb = np.stack([x + 0.01 * i for i in range(batch)]) if batch > 1 else x\n"
         "    f, g = ctx.sweep(xb)\n"
-        "    out['%%d %%s' %% (d, method)] = {'f': [float(v) for v in np.atleast_1d(f)], 'g': np.asarray(g).ravel().tolist()}\n"
+        "    out['%%d %%s' %% (d, method)] = {'f': [float(v) for v in np.atleast_1d(f)], 'g': np.asarray(g).ravel().tolist(),\n"
+        "                                   'packed': ctx.plan()['packed'], 'S': ctx.resident()['S']}\n"
         "    ctx.close()\n"
-        "print(json.dumps(out))\n" % os.path.dirname(__file__))
+        "print(json.dumps(out))\n" % (os.path.dirname(__file__), sigma))
     outs = {}
     for name, env_set in (("helpers", {"VGPA_SYM_HELPERS": "1"}), ("two", {"VGPA_SYM_HELPERS": "2"}), ("plain", {"VGPA_SYM_HELPERS": "0"})):
         env = dict(os.environ)
@@ -456,8 +536,15 @@ def test_stepper_variants_of_the_fragment_cover_agree():
         assert r.returncode == 0, r.stderr[-2000:]
         outs[name] = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     for key, ref in outs["plain"].items():
+        packed = sigma == "iso" and not key.endswith("heun")
+        assert ref["packed"] == packed and ref["S"] == ("packed" if packed else "whole"), key
         assert outs["helpers"][key] == ref, key                      # bit for bit
         assert outs["two"][key] == ref, key                          # (two helper roles: vector recursion and staging on waves of their own)
+
+
+def test_stepper_variants_of_the_fragment_cover_agree_with_isotropic_sigma():
+    """The same with Sigma = sigma^2 I: the paths the docstring above names, asserted there."""
+    test_stepper_variants_of_the_fragment_cover_agree("iso")
 
 
 @pytest.mark.parametrize("model,method,n,nb", [("L63", "rk4", 37, 520), ("L63", "rk4", 6, 576), ("L63", "heun", 22, 513), ("L63", "rk2", 9, 640),
@@ -505,9 +592,7 @@ def test_fused_lane_pass(model, method, n, nb):
 def _walk_context(case):
     """One small context per path that keeps state between calls: (context factory, x of the whole batch)."""
     model, d, n, batch, flags, method, per_problem_times, isotropic = case
-    p, x0 = make_problem(model, d, n, method=method)
-    if isotropic:                                          # Sigma = sigma^2 I: what the Q'' stream and the packed layouts take
-        p.sigma = 3.5 * np.eye(d)
+    p, x0 = make_problem(model, d, n, method=method, sigma="iso" if isotropic else "diag")   # (iso: what the Q'' stream and the packed layouts take)
     x = x0 if batch == 1 else x0[None, :] + 0.02 * np.random.default_rng(41).standard_normal((batch, x0.size))
 
     def fresh():
@@ -529,6 +614,37 @@ WALKS = {  # model, D, Np, batch, flags, method, per-problem observation times, 
     "generic": ("L96", 12, 7, 2, FLAG_FORCE_GENERIC, "rk4", False, False),
     "resident_above_64": ("L96", 72, 5, 1, 0, "rk4", False, False),
 }
+# What each name claims: (plan fields, the record after the sweep, after every fetch key) -- the fields that tell the paths apart; what
+# is not listed after the fetches stays as the sweep left it.  After the four operator-level calls every walk holds TAKEN_OVER.
+WALK_STATES = {
+    "fused_lane_pass": (dict(fwd="lane", bwd="lane", lane_pass=True, packed=False),
+                        dict(moments="time_major", S="whole", dEs="whole", bwd="none", terms=False),
+                        dict(moments="row_major", bwd="psi", terms=True)),             # (the separate kernels materialise them)
+    "16_lane_kernels_per_problem_times": (dict(fwd="wave", bwd="wave", lane_pass=False),
+                                          dict(moments="row_major", S="whole", dEs="whole", bwd="psi", terms=True), {}),
+    "cover_gradient_in_backward_kernel": (dict(fwd="mfma", bwd="mfma", sym_units=True, bwd_upper=True, store_q=True, packed=True, grad_in_bwd_now=True),
+                                          dict(moments="row_major", S="packed", dEs="packed", bwd="none", terms=True),
+                                          dict(bwd="psi")),                           # (the Q'' kernel for the fetch, then the recovery)
+    "cover_q_stream_separate_assembly": (dict(fwd="mfma", bwd="mfma", sym_units=True, store_q=True, packed=True, grad_in_bwd=True, grad_in_bwd_now=False),
+                                         dict(moments="row_major", S="packed", dEs="packed", bwd="q", terms=True), dict(bwd="psi")),
+    "cover_upper_triangle": (dict(fwd="mfma", bwd="mfma", sym_units=True, bwd_upper=True, store_q=False, packed=False, grad_in_bwd=False),
+                             dict(moments="row_major", S="whole", dEs="upper", bwd="psi", terms=True), dict(dEs="whole")),   # (mirrored in place)
+    "cover_keep_psi": (dict(fwd="mfma", bwd="mfma", sym_units=True, bwd_upper=False, store_q=False, packed=False, grad_in_bwd=False),
+                       dict(moments="row_major", S="whole", dEs="whole", bwd="psi", terms=True), {}),
+    "role_specialised": (dict(fwd="mfma", bwd="mfma", sym_units=False, launch_sym_units=False, bwd_upper=False, packed=False),
+                         dict(moments="row_major", S="whole", dEs="whole", bwd="psi", terms=True), {}),
+    "generic": (dict(fwd="generic", bwd="generic", bwd_upper=False, packed=False),
+                dict(moments="row_major", S="whole", dEs="whole", bwd="psi", terms=True), {}),
+    "resident_above_64": (dict(fwd="large_d", bwd="large_d", bwd_upper=False, packed=False),
+                          dict(moments="row_major", S="whole", dEs="whole", bwd="psi", terms=True), {}),
+}
+TAKEN_OVER = dict(cached=False, moments="row_major", S="whole", dEs="whole", bwd="none", terms=False)
+
+
+def _holds(got, want):
+    return {k: got[k] for k in want} == want
+
+
 FETCH_ORDER = ("dEsde_ds", "mt", "psit", "Esde_t", "lamt", "Edf", "st", "dEsde_dm", "Efx")       # every vgpa_fetch key, scrambled
 
 
@@ -544,14 +660,24 @@ def test_buffer_state_walks(name):
       * the fused lane pass, as test_fused_lane_pass states it: behind the fetches the gradient comes from the four separate kernels
         (1e-11 there; 4.7e-16 measured here), and F of free_energy alone is another instantiation of the pass than the sweep's
         (1e-13 there; 1.5e-16 measured here).
-    The library before the record of the buffers' contents existed passes the same walk."""
+    The plan and the record of the buffers (Context.plan, Context.resident) are asserted to be what the walk's name claims
+    (WALK_STATES): after the sweep, after the fetch round and after the operator-level take-over."""
     p, fresh, x = _walk_context(WALKS[name])
     d, n, batch = WALKS[name][1:4]
+    want_plan, after_sweep, after_fetches = WALK_STATES[name]
+    if want_plan.get("packed") and fused_grad_switch():       # (a run under VGPA_FUSED_GRAD: the switch, not the batch size, picks the assembly)
+        on = fused_grad_switch() == "1"
+        want_plan = dict(want_plan, grad_in_bwd=on, grad_in_bwd_now=on)
+        after_sweep = dict(after_sweep, bwd="none" if on else "q")
     ctx = fresh()
+    assert _holds(ctx.plan(), want_plan), ctx.plan()
+    assert not ctx.resident()["cached"]
     f, g = ctx.sweep(x)
+    assert _holds(ctx.plan(), want_plan) and _holds(ctx.resident(), dict(after_sweep, cached=True)), ctx.resident()
     first = {key: ctx.fetch(key) for key in FETCH_ORDER}
     for key in FETCH_ORDER:
         assert np.array_equal(ctx.fetch(key), first[key]), key
+    assert _holds(ctx.resident(), dict(after_sweep, cached=True, **after_fetches)), ctx.resident()
     g_again = ctx.gradient(None)
     if name == "cover_q_stream_separate_assembly":
         assert rel_err(g_again, g) < 1e-13
@@ -579,6 +705,7 @@ def test_buffer_state_walks(name):
     lam, psi = ctx.solve_bwd(a, first["dEsde_dm"], first["dEsde_ds"], jm, js)
     m_op, s_op = ctx.solve_fwd(a, b, p.m0, p.s0, p.sigma)
     assert all(np.all(np.isfinite(v)) for v in (jm, js, lam, psi, m_op, s_op))
+    assert ctx.resident() == TAKEN_OVER and _holds(ctx.plan(), want_plan)      # (the plan belongs to the context, not to a call)
     for needs_the_cache in (lambda: ctx.gradient(None), lambda: ctx.fetch("st"), ctx.theta_gradient):
         with pytest.raises(RuntimeError, match="error -4"):
             needs_the_cache()

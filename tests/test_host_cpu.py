@@ -37,6 +37,15 @@ def test_python_constants_agree_with_the_header():
     assert len({enums[k] for k in enums if k.startswith("VGPA_FLAG_")}) == 6          # distinct bits
     assert _lib.SHARD_OPT_GATHER_CHUNKS == enums["VGPA_SHARD_OPT_GATHER_CHUNKS"]
     assert _lib.SHARD_OPT_TIMEOUT_MS == enums["VGPA_SHARD_OPT_TIMEOUT_MS"]
+    # vgpa_path_info: every value of its four enums has a name on the Python side, and no other
+    for prefix, ids in (("STEPPER", _lib.STEPPER_IDS), ("MOMENTS", _lib.MOMENTS_IDS), ("LAYOUT", _lib.LAYOUT_IDS), ("BWD", _lib.BWD_IDS)):
+        declared = {k[len("VGPA_" + prefix + "_"):].lower(): v for k, v in enums.items() if k.startswith("VGPA_" + prefix + "_")}
+        assert declared == ids, prefix
+    # ... and the struct has the header's fields in the header's order, all int32_t
+    body = re.search(r"typedef struct \{([^}]*)\} vgpa_path;", header).group(1)
+    fields = [f.strip() for decl in re.findall(r"int32_t\s+([^;]+);", body) for f in decl.split(",")]
+    assert fields == [name for name, _ in _lib.VgpaPath._fields_]
+    assert len(re.findall(r";", re.sub(r"/\*.*?\*/", "", body, flags=re.S))) == len(re.findall(r"int32_t\s+[^;]+;", body))
 
 
 def test_no_silent_cpu_fallback():

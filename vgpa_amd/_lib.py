@@ -25,6 +25,11 @@ FLAG_SYM_UNITS = 16
 FLAG_KEEP_PSI = 32
 FLAG_MATERIALIZE = 64
 OPT_LD_CHUNK = 1
+# vgpa_path_info: the values of its enum fields by name
+STEPPER_IDS = {"large_d": 0, "lane": 1, "wave": 2, "mfma": 3, "generic": 4}
+MOMENTS_IDS = {"row_major": 0, "time_major": 1}
+LAYOUT_IDS = {"whole": 0, "upper": 1, "packed": 2}
+BWD_IDS = {"none": 0, "psi": 1, "q": 2}
 
 # exported symbols, checked by the CPU test-suite against include/vgpa_hip.h
 SYMBOLS = ["vgpa_create", "vgpa_destroy", "vgpa_last_error", "vgpa_abi_version", "vgpa_device_count",
@@ -32,7 +37,7 @@ SYMBOLS = ["vgpa_create", "vgpa_destroy", "vgpa_last_error", "vgpa_abi_version",
            "vgpa_obs_energy", "vgpa_free_energy", "vgpa_gradient", "vgpa_sweep", "vgpa_energy_parts",
            "vgpa_fetch", "vgpa_theta_gradient", "vgpa_sweep_dev", "vgpa_free_energy_dev", "vgpa_sweep_enqueue", "vgpa_fetch_f",
            "vgpa_dev_alloc", "vgpa_dev_free", "vgpa_memcpy_h2d", "vgpa_memcpy_d2h",
-           "vgpa_profile_begin", "vgpa_profile_end", "vgpa_ld_gemm", "vgpa_ld_stage", "vgpa_gradient_dev", "vgpa_energy_full", "vgpa_set_option", "vgpa_is_streaming", "vgpa_set_prior_energy",
+           "vgpa_profile_begin", "vgpa_profile_end", "vgpa_ld_gemm", "vgpa_ld_stage", "vgpa_gradient_dev", "vgpa_energy_full", "vgpa_set_option", "vgpa_is_streaming", "vgpa_path_info", "vgpa_set_prior_energy",
            "vgpa_set_problem_data", "vgpa_set_problem_params",
            "vgpa_vec_dot", "vgpa_vec_absmax", "vgpa_vec_asum", "vgpa_vec_axpby", "vgpa_release_x",
            "vgpa_shard_create", "vgpa_shard_destroy", "vgpa_shard_time_slice", "vgpa_shard_stream", "vgpa_shard_synchronize",
@@ -72,6 +77,14 @@ class VgpaShardProblem(ctypes.Structure):
     _fields_ = [("theta", c_double), ("inv_sigma_diag", c_void_p), ("m0", c_void_p), ("s0", c_void_p), ("sigma", c_void_p),
                 ("n_obs", c_int32), ("obs_t", POINTER(c_int64)), ("obs_y", c_void_p), ("obs_rinv_diag", c_void_p),
                 ("obs_const", c_double), ("e0", c_double)]
+
+
+class VgpaPath(ctypes.Structure):
+    """vgpa_path (include/vgpa_hip.h): the context's plan, then its record of what the buffers hold."""
+    PLAN = ("fwd", "bwd", "sym_units", "launch_sym_units", "lane_pass", "bwd_upper", "store_q", "packed", "grad_in_bwd",
+            "grad_in_bwd_now")
+    RESIDENT = ("cached", "moments", "S", "dEs", "bwd_holds", "terms")
+    _fields_ = [(name, c_int32) for name in PLAN + RESIDENT]
 
 
 class VgpaConfig(ctypes.Structure):
@@ -167,6 +180,7 @@ def load():
     lib.vgpa_vec_axpby.argtypes = [c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vgpa_set_option.argtypes = [c_void_p, c_int, c_int64]
     lib.vgpa_is_streaming.argtypes = [c_void_p]
+    lib.vgpa_path_info.argtypes = [c_void_p, POINTER(VgpaPath)]
     lib.vgpa_set_prior_energy.argtypes = [c_void_p, c_double]
     lib.vgpa_set_problem_data.argtypes = [c_void_p] + [c_void_p] * 5
     lib.vgpa_set_problem_params.argtypes = [c_void_p] + [c_void_p] * 2
@@ -630,6 +644,27 @@ class Context:
     @property
     def streaming(self):
         return bool(self._lib.vgpa_is_streaming(self._h))
+
+    def _path(self):
+        out = VgpaPath()
+        self._check(self._lib.vgpa_path_info(self._h, byref(out)))
+        return out
+
+    def plan(self):
+        """Which kernels this context's fused sweep runs (tests, diagnostics; read-only): the steppers `fwd` / `bwd` by name
+        ("large_d", "lane", "wave", "mfma", "generic"), every other field of the library's plan as a bool."""
+        v, names = self._path(), {i: k for k, i in STEPPER_IDS.items()}
+        return {k: names[getattr(v, k)] if k in ("fwd", "bwd") else bool(getattr(v, k)) for k in VgpaPath.PLAN}
+
+    def resident(self):
+        """What the device buffers hold right now (tests, diagnostics; read-only): `cached` and `terms` as bools, `moments`
+        ("row_major", "time_major"), `S` and `dEs` ("whole", "upper", "packed"), `bwd` ("none", "psi", "q")."""
+        v = self._path()
+
+        def name(ids, i):
+            return {j: k for k, j in ids.items()}[i]
+        return {"cached": bool(v.cached), "moments": name(MOMENTS_IDS, v.moments), "S": name(LAYOUT_IDS, v.S),
+                "dEs": name(LAYOUT_IDS, v.dEs), "bwd": name(BWD_IDS, v.bwd_holds), "terms": bool(v.terms)}
 
     def synchronize(self):
         self._check(self._lib.vgpa_synchronize(self._h))

@@ -1618,6 +1618,27 @@ int vgpa_set_problem_params(vgpa_ctx* c, const double* theta, const double* sigm
 
 int vgpa_is_streaming(vgpa_ctx* c) { return (c && c->stream_ld) ? 1 : 0; }
 
+// Plan and Resident as plain integers (tests, diagnostics): reads the two records and nothing else
+int vgpa_path_info(vgpa_ctx* c, vgpa_path* out) {
+  if (!c || !out) return VGPA_ERR_ARG;     // (no fail(): the context's error message is state too)
+  static_assert((int)Stepper::LargeD == VGPA_STEPPER_LARGE_D && (int)Stepper::Lane == VGPA_STEPPER_LANE && (int)Stepper::Wave == VGPA_STEPPER_WAVE &&
+                (int)Stepper::Mfma == VGPA_STEPPER_MFMA && (int)Stepper::Generic == VGPA_STEPPER_GENERIC, "Stepper and VGPA_STEPPER_*");
+  static_assert((int)Resident::Moments::RowMajor == VGPA_MOMENTS_ROW_MAJOR && (int)Resident::Moments::TimeMajor == VGPA_MOMENTS_TIME_MAJOR, "VGPA_MOMENTS_*");
+  static_assert((int)Resident::DesLayout::Whole == VGPA_LAYOUT_WHOLE && (int)Resident::DesLayout::Upper == VGPA_LAYOUT_UPPER &&
+                (int)Resident::DesLayout::Packed == VGPA_LAYOUT_PACKED, "VGPA_LAYOUT_*");
+  static_assert((int)Resident::Bwd::None == VGPA_BWD_NONE && (int)Resident::Bwd::Psi == VGPA_BWD_PSI && (int)Resident::Bwd::Q == VGPA_BWD_Q, "VGPA_BWD_*");
+  const Plan& p = c->plan;
+  const Resident& r = c->res;
+  out->fwd = (int32_t)p.fwd; out->bwd = (int32_t)p.bwd;
+  out->sym_units = p.sym_units; out->launch_sym_units = p.launch_sym_units; out->lane_pass = p.lane_pass;
+  out->bwd_upper = p.bwd_upper; out->store_q = p.store_q; out->packed = p.packed;
+  out->grad_in_bwd = p.grad_in_bwd; out->grad_in_bwd_now = p.grad_in_bwd_now;
+  out->cached = r.cached; out->moments = (int32_t)r.moments;
+  out->S = r.S == Resident::SLayout::Packed ? VGPA_LAYOUT_PACKED : VGPA_LAYOUT_WHOLE;
+  out->dEs = (int32_t)r.dEs; out->bwd_holds = (int32_t)r.bwd; out->terms = r.terms;
+  return VGPA_OK;
+}
+
 // ---- raw device memory ------------------------------------------------------------------------------
 int vgpa_dev_alloc(vgpa_ctx* c, uint64_t bytes, void** out) {
   if (!c || !out) return VGPA_ERR_ARG;
