@@ -421,13 +421,7 @@ __global__ void __launch_bounds__(NT) k_stage(StageArgs a) {
         const double wt = tile[tx][rr];
         const double e = a.mid_e ? 0.5 * (a.E1[o] + a.E0[o]) : a.E0[o];
         const double rv = a.fwd ? ((-w - wt) + e) : ((-e + wt) + w);
-        const double k1 = (a.final >= 2) ? a.K1[o] : 0.0;
-        const double k23 = (a.final == 3) ? a.K23[o] : 0.0;
-        if (a.kstore == 1) a.K1[o] = rv;
-        else if (a.kstore == 2) a.K23[o] = rv;
-        else if (a.kstore == 3) a.K23[o] = a.K23[o] + rv;
-        const double jump = (a.final && a.has_j) ? a.J[o] : 0.0;
-        a.out[o] = stage_combine(rv, a.base[o], k1, k23, a.final, a.cx, a.cf, sgn, jump);
+        a.out[o] = stage_slots(a, rv, sgn, a.base, a.K1, a.K23, a.has_j, a.J, o);
       }
     }
     return;
@@ -557,13 +551,7 @@ __global__ void __launch_bounds__(NT) k_stage_sym(StageArgs a) {
         const double wt = diag ? ta[tx][rr] : tb[tx][rr];
         const double e = a.mid_e ? 0.5 * (a.E1[o] + a.E0[o]) : a.E0[o];
         const double rv = a.fwd ? ((-w - wt) + e) : ((-e + wt) + w);
-        const double k1 = (a.final >= 2) ? a.K1[o] : 0.0;
-        const double k23 = (a.final == 3) ? a.K23[o] : 0.0;
-        if (a.kstore == 1) a.K1[o] = rv;
-        else if (a.kstore == 2) a.K23[o] = rv;
-        else if (a.kstore == 3) a.K23[o] = a.K23[o] + rv;
-        const double jump = (a.final && a.has_j) ? a.J[o] : 0.0;
-        res = stage_combine(rv, a.base[o], k1, k23, a.final, a.cx, a.cf, sgn, jump);
+        res = stage_slots(a, rv, sgn, a.base, a.K1, a.K23, a.has_j, a.J, o);
         a.out[o] = res;
       }
       if (!diag) tc[rr][tx] = res;
@@ -675,20 +663,20 @@ struct StageSpec {
   In J, jv;
   In base, vbase;
   Out out, vout;
-  int kstore, final_mode; double cx, cf;
+  StageRow row; double dt;   // slot, combination and coefficients: the schedule's row (large_d_stage.h)
 };
 
 StageArgs stage_args(const LdCall& c, const Work& w, const StageSpec& s) {
   StageArgs a{};
   const int D = c.D;
-  a.D = D; a.row0 = 0; a.Mp = D; a.cw = D; a.fwd = s.fwd ? 1 : 0; a.kstore = s.kstore; a.final = s.final_mode;
+  a.D = D; a.row0 = 0; a.Mp = D; a.cw = D;
   a.sym_ok = c.literal ? 0 : 1;
-  a.mid_e = s.E1.rows != nullptr; a.has_j = s.J.rows != nullptr; a.cx = s.cx; a.cf = s.cf;
   a.W = w.W.rows; a.Wcol = c.literal ? w.W2.rows : w.W.rows; a.E0 = s.E0.rows; a.E1 = s.E1.rows; a.J = s.J.rows; a.base = s.base.rows;
   a.K1 = w.K1.rows; a.K23 = w.K23.rows; a.out = s.out.rows;
-  a.A0 = s.Av0.rows; a.A1 = s.Av1.rows; a.lda = D; a.mid_a = s.Av1.rows != nullptr; a.x = s.xv.rows;
-  a.e0 = s.e0.rows; a.e1 = s.e1.rows; a.mid_ev = s.e1.rows != nullptr; a.jv = s.jv.rows; a.vbase = s.vbase.rows;
+  a.A0 = s.Av0.rows; a.A1 = s.Av1.rows; a.lda = D; a.x = s.xv.rows;
+  a.e0 = s.e0.rows; a.e1 = s.e1.rows; a.jv = s.jv.rows; a.vbase = s.vbase.rows;
   a.k1v = w.k1v.rows; a.k23v = w.k23v.rows; a.vout = s.vout.rows;
+  stage_row_args(a, s.fwd, s.row, s.dt);
   a.nb = c.nb;         // (the partner of a mid-point pair, and W2 beside W, have their operand's stride)
   a.zW = w.W.stride; a.zE = s.E0.stride; a.zJ = s.J.stride; a.zBase = s.base.stride; a.zK = w.K1.stride; a.zOut = s.out.stride;
   a.zA = s.Av0.stride; a.zX = s.xv.stride; a.zEv = s.e0.stride; a.zJv = s.jv.stride; a.zVb = s.vbase.stride; a.zKv = w.k1v.stride; a.zVo = s.vout.stride;
@@ -768,7 +756,7 @@ hipError_t ld_solve_fwd(const LdCall& c, int Np, In A, In b, In m0, In S0, In Si
   const int method = c.method, D = c.D;
   const size_t DD = (size_t)D * D;
   const Work w = carve_work(c.ws, D);
-  const double dt = c.dt, h = 0.5 * dt;
+  const Stepper& sch = kSteppers[method];
   for (int p = 0; p < c.nb; p++) {
     LD_TRY(hipMemcpyAsync(S.of(p), S0.of(p), DD * sizeof(double), hipMemcpyDeviceToDevice, c.st));
     LD_TRY(hipMemcpyAsync(m.of(p), m0.of(p), D * sizeof(double), hipMemcpyDeviceToDevice, c.st));
@@ -777,27 +765,18 @@ hipError_t ld_solve_fwd(const LdCall& c, int Np, In A, In b, In m0, In S0, In Si
     const In Ak = A + k * DD, Ak1 = Ak + DD, bk = b + (size_t)k * D, bk1 = bk + D;
     const In Sk = S + k * DD, mk = m + (size_t)k * D;
     const Out Sn = S + (k + 1) * DD, mn = m + (size_t)(k + 1) * D;
-    StageSpec s{};
     MidCache mc{};
-    s.fwd = true; s.E0 = Sigma; s.base = Sk; s.vbase = mk;
-    auto set = [&](In am0, In am1, In av0, In av1, In X, In xv, In e0, In e1, Out out, Out vout, int ks, int fin, double cx, double cf) {
-      s.Am0 = am0; s.Am1 = am1; s.Av0 = av0; s.Av1 = av1; s.X = X; s.xv = xv; s.e0 = e0; s.e1 = e1; s.out = out;
-      s.vout = vout; s.kstore = ks; s.final_mode = fin; s.cx = cx; s.cf = cf;
-    };
-    if (method == VGPA_ODE_EULER) {
-      set(Ak, none, Ak, none, Sk, mk, bk, none, Sn, mn, 0, 1, 0.0, dt); LD_TRY(run_stage(c, w, s, &mc));
-    } else if (method == VGPA_ODE_HEUN) {
-      set(Ak, none, Ak, none, Sk, mk, bk, none, w.XA, w.xvA, 1, 0, dt, 0.0); LD_TRY(run_stage(c, w, s, &mc));
-      set(Ak1, none, Ak1, none, w.XA, w.xvA, bk1, none, Sn, mn, 0, 2, 0.0, h); LD_TRY(run_stage(c, w, s, &mc));
-    } else if (method == VGPA_ODE_RK2) {
-      // covariance predictor: S_k stands in for A_k (reference quirk, runge_kutta2.py:96); mean predictor: A_k
-      set(Sk, none, Ak, none, Sk, mk, bk, none, w.XA, w.xvA, 0, 0, h, 0.0); LD_TRY(run_stage(c, w, s, &mc));
-      set(Ak, Ak1, Ak, Ak1, w.XA, w.xvA, bk1, bk, Sn, mn, 0, 1, 0.0, dt); LD_TRY(run_stage(c, w, s, &mc));
-    } else {
-      set(Ak, none, Ak, none, Sk, mk, bk, none, w.XA, w.xvA, 1, 0, h, 0.0); LD_TRY(run_stage(c, w, s, &mc));
-      set(Ak, Ak1, Ak, Ak1, w.XA, w.xvA, bk1, bk, w.XB, w.xvB, 2, 0, h, 0.0); LD_TRY(run_stage(c, w, s, &mc));
-      set(Ak, Ak1, Ak, Ak1, w.XB, w.xvB, bk1, bk, w.XA, w.xvA, 3, 0, dt, 0.0); LD_TRY(run_stage(c, w, s, &mc));
-      set(Ak1, none, Ak1, none, w.XA, w.xvA, bk1, none, Sn, mn, 0, 3, 0.0, dt); LD_TRY(run_stage(c, w, s, &mc));
+    for (int i = 0; i < sch.n; i++) {
+      const StageRow& r = sch.row[i];
+      const bool mid = r.at == Where::Mid;
+      StageSpec s{};
+      s.fwd = true; s.row = r; s.dt = c.dt; s.E0 = Sigma; s.base = Sk; s.vbase = mk;
+      s.X = pick<In>(r.in, Sk, w.XA, w.XB, none); s.xv = pick<In>(r.in, mk, w.xvA, w.xvB, none);
+      s.out = pick<Out>(r.out, Out{}, w.XA, w.XB, Sn); s.vout = pick<Out>(r.out, Out{}, w.xvA, w.xvB, mn);
+      s.Av0 = r.at == Where::End ? Ak1 : Ak; s.Av1 = mid ? Ak1 : none;       // mid-point pair: A (start, end), b (end, start)
+      s.Am0 = r.fwd_state_for_a ? s.X : s.Av0; s.Am1 = s.Av1;
+      s.e0 = r.at == Where::Start ? bk : bk1; s.e1 = mid ? bk : none;
+      LD_TRY(run_stage(c, w, s, &mc));
     }
   }
   return hipSuccess;
@@ -808,28 +787,20 @@ hipError_t ld_solve_fwd(const LdCall& c, int Np, In A, In b, In m0, In S0, In Si
 hipError_t ld_bwd_step(const LdCall& c, In At, In Am, In Gt, In Gm, In gt, In gmm, In Pt, In lt, Out Pn, Out ln, In Jn, In jn) {
   const int method = c.method;
   const Work w = carve_work(c.ws, c.D);
-  const double dt = c.dt, h = 0.5 * dt;
-  StageSpec s{};
+  const Stepper& sch = kSteppers[method];
   MidCache mc{};
-  s.fwd = false; s.base = Pt; s.vbase = lt;
-  auto set = [&](In a0, In a1, In X, In xv, In E0, In E1, In e0, In e1, Out out, Out vout, int ks, int fin, double cx, double cf, bool jump) {
-    s.Am0 = a0; s.Am1 = a1; s.Av0 = a0; s.Av1 = a1; s.X = X; s.xv = xv; s.E0 = E0; s.E1 = E1; s.e0 = e0; s.e1 = e1;
-    s.out = out; s.vout = vout; s.kstore = ks; s.final_mode = fin; s.cx = cx; s.cf = cf;
+  for (int i = 0; i < sch.n; i++) {
+    const StageRow& r = sch.row[i];
+    const bool mid = r.at == Where::Mid, jump = r.out == Buf::Next;
+    StageSpec s{};
+    s.fwd = false; s.row = r; s.dt = c.dt; s.base = Pt; s.vbase = lt;
+    s.X = pick<In>(r.in, Pt, w.XA, w.XB, none); s.xv = pick<In>(r.in, lt, w.xvA, w.xvB, none);
+    s.out = pick<Out>(r.out, Out{}, w.XA, w.XB, Pn); s.vout = pick<Out>(r.out, Out{}, w.xvA, w.xvB, ln);
+    s.Am0 = s.Av0 = r.at == Where::Start ? At : Am; s.Am1 = s.Av1 = mid ? At : none;      // mid-point pair: A (end, start), G and g (start, end)
+    s.E0 = r.at == Where::End ? Gm : Gt; s.E1 = mid ? Gm : none;
+    s.e0 = r.at == Where::End ? gmm : gt; s.e1 = mid ? gmm : none;
     s.J = jump ? Jn : none; s.jv = jump ? jn : none;
-  };
-  if (method == VGPA_ODE_EULER) {
-    set(At, none, Pt, lt, Gt, none, gt, none, Pn, ln, 0, 1, 0.0, dt, true); LD_TRY(run_stage(c, w, s, &mc));
-  } else if (method == VGPA_ODE_HEUN) {
-    set(At, none, Pt, lt, Gt, none, gt, none, w.XA, w.xvA, 1, 0, dt, 0.0, false); LD_TRY(run_stage(c, w, s, &mc));
-    set(Am, none, w.XA, w.xvA, Gm, none, gmm, none, Pn, ln, 0, 2, 0.0, h, true); LD_TRY(run_stage(c, w, s, &mc));
-  } else if (method == VGPA_ODE_RK2) {
-    set(At, none, Pt, lt, Gt, none, gt, none, w.XA, w.xvA, 0, 0, h, 0.0, false); LD_TRY(run_stage(c, w, s, &mc));
-    set(Am, At, w.XA, w.xvA, Gt, Gm, gt, gmm, Pn, ln, 0, 1, 0.0, dt, true); LD_TRY(run_stage(c, w, s, &mc));
-  } else {
-    set(At, none, Pt, lt, Gt, none, gt, none, w.XA, w.xvA, 1, 0, h, 0.0, false); LD_TRY(run_stage(c, w, s, &mc));
-    set(Am, At, w.XA, w.xvA, Gt, Gm, gt, gmm, w.XB, w.xvB, 2, 0, h, 0.0, false); LD_TRY(run_stage(c, w, s, &mc));
-    set(Am, At, w.XB, w.xvB, Gt, Gm, gt, gmm, w.XA, w.xvA, 3, 0, dt, 0.0, false); LD_TRY(run_stage(c, w, s, &mc));
-    set(Am, none, w.XA, w.xvA, Gm, none, gmm, none, Pn, ln, 0, 3, 0.0, dt, true); LD_TRY(run_stage(c, w, s, &mc));
+    LD_TRY(run_stage(c, w, s, &mc));
   }
   return hipSuccess;
 }
@@ -1007,7 +978,7 @@ struct ShardStage {
   const double* J; const double* jv;     // rows / entries I_p of the jump, or nullptr
   const double* base; const double* vbase;   // complete buffers of S_k / Psi_t, m_k / lam_t (the row block is taken here)
   double* out; double* vout;             // complete buffers of the next stage state
-  int kstore, final_mode; double cx, cf;
+  StageRow row; double dt;               // slot, combination and coefficients: the schedule's row (large_d_stage.h)
 };
 
 static hipError_t shard_gather(ShardCtx& c, double* out, double* vout) {
@@ -1078,16 +1049,16 @@ static hipError_t shard_stage(ShardCtx& c, const ShardStage& s) {
     wcol = w.Wcol;
   }
   StageArgs a{};
-  a.D = D; a.row0 = 0; a.Mp = Mp; a.cw = Mp; a.fwd = s.fwd ? 1 : 0; a.kstore = s.kstore; a.final = s.final_mode;
+  a.D = D; a.row0 = 0; a.Mp = Mp; a.cw = Mp;
   a.sym_ok = 1;
-  a.mid_e = s.E1 != nullptr; a.has_j = s.J != nullptr; a.cx = s.cx; a.cf = s.cf;
   a.W = w.Wp; a.Wcol = wcol;
   a.E0 = s.E0; a.E1 = s.E1; a.J = s.J;
   a.base = s.base + (size_t)row0 * D; a.K1 = w.K1; a.K23 = w.K23; a.out = s.out + (size_t)row0 * D;
-  a.A0 = s.Av0; a.A1 = s.Av1; a.lda = s.ldav; a.mid_a = s.Av1 != nullptr; a.x = s.xv;
-  a.e0 = s.e0; a.e1 = s.e1; a.mid_ev = s.e1 != nullptr;
+  a.A0 = s.Av0; a.A1 = s.Av1; a.lda = s.ldav; a.x = s.xv;
+  a.e0 = s.e0; a.e1 = s.e1;
   a.jv = s.jv; a.vbase = s.vbase + row0;
   a.k1v = w.k1v; a.k23v = w.k23v; a.vout = s.vout + row0;
+  stage_row_args(a, s.fwd, s.row, s.dt);
   LD_TRY(launch_stage(a, c.st));
   if (c.world > 1 && !c.skip_comm) LD_TRY(shard_gather(c, s.out, s.vout));
   return hipSuccess;
@@ -1129,7 +1100,7 @@ hipError_t shard_solve_fwd(ShardCtx& c, int Np, const AView& av, const double* b
                            const double* Sigma, double* m_own, double* S_own) {
   const int D = c.D, row0 = c.row0;
   const size_t DD = (size_t)D * D;
-  const double dt = c.dt, h = 0.5 * dt;
+  const Stepper& sch = kSteppers[c.method];
   ShardWork& w = c.w;
   int lo, hi;
   time_slice(Np, c.rank, c.world, &lo, &hi);
@@ -1147,29 +1118,18 @@ hipError_t shard_solve_fwd(ShardCtx& c, int Np, const AView& av, const double* b
     const double *bk = b + (size_t)k * D + row0, *bk1 = bk + D;
     const double *Sk = w.cur, *mk = w.vcur;
     double *Sn = w.nxt, *mn = w.vnxt;
-    ShardStage s{};
-    s.fwd = true; s.E0 = Sigma + (size_t)row0 * D; s.base = Sk; s.vbase = mk; s.ldag = av.rows_ld; s.ldav = av.rows_ld;
-    auto set = [&](const double* ag0, const double* ag1, int ldag, const double* av0, const double* av1, const double* X,
-                   const double* xv, const double* e0, const double* e1, double* out, double* vout, int ks, int fin,
-                   double cx, double cf) {
-      s.Ag0 = ag0; s.Ag1 = ag1; s.ldag = ldag; s.Av0 = av0; s.Av1 = av1; s.X = X; s.xv = xv; s.e0 = e0; s.e1 = e1; s.out = out;
-      s.vout = vout; s.kstore = ks; s.final_mode = fin; s.cx = cx; s.cf = cf;
-    };
-    const int la = av.rows_ld;
-    if (c.method == VGPA_ODE_EULER) {
-      set(Ar, nullptr, la, Ar, nullptr, Sk, mk, bk, nullptr, Sn, mn, 0, 1, 0.0, dt); LD_TRY(shard_stage(c, s));
-    } else if (c.method == VGPA_ODE_HEUN) {
-      set(Ar, nullptr, la, Ar, nullptr, Sk, mk, bk, nullptr, w.XA, w.xvA, 1, 0, dt, 0.0); LD_TRY(shard_stage(c, s));
-      set(Ar1, nullptr, la, Ar1, nullptr, w.XA, w.xvA, bk1, nullptr, Sn, mn, 0, 2, 0.0, h); LD_TRY(shard_stage(c, s));
-    } else if (c.method == VGPA_ODE_RK2) {
-      // covariance predictor: S_k stands in for A_k (reference quirk, runge_kutta2.py:96); mean predictor: A_k
-      set(Sk + (size_t)row0 * D, nullptr, D, Ar, nullptr, Sk, mk, bk, nullptr, w.XA, w.xvA, 0, 0, h, 0.0); LD_TRY(shard_stage(c, s));
-      set(Ar, Ar1, la, Ar, Ar1, w.XA, w.xvA, bk1, bk, Sn, mn, 0, 1, 0.0, dt); LD_TRY(shard_stage(c, s));
-    } else {
-      set(Ar, nullptr, la, Ar, nullptr, Sk, mk, bk, nullptr, w.XA, w.xvA, 1, 0, h, 0.0); LD_TRY(shard_stage(c, s));
-      set(Ar, Ar1, la, Ar, Ar1, w.XA, w.xvA, bk1, bk, w.XB, w.xvB, 2, 0, h, 0.0); LD_TRY(shard_stage(c, s));
-      set(Ar, Ar1, la, Ar, Ar1, w.XB, w.xvB, bk1, bk, w.XA, w.xvA, 3, 0, dt, 0.0); LD_TRY(shard_stage(c, s));
-      set(Ar1, nullptr, la, Ar1, nullptr, w.XA, w.xvA, bk1, nullptr, Sn, mn, 0, 3, 0.0, dt); LD_TRY(shard_stage(c, s));
+    for (int i = 0; i < sch.n; i++) {
+      const StageRow& r = sch.row[i];
+      const bool mid = r.at == Where::Mid;
+      ShardStage s{};
+      s.fwd = true; s.row = r; s.dt = c.dt; s.E0 = Sigma + (size_t)row0 * D; s.base = Sk; s.vbase = mk;
+      s.X = pick<const double*>(r.in, Sk, w.XA, w.XB, nullptr); s.xv = pick<const double*>(r.in, mk, w.xvA, w.xvB, nullptr);
+      s.out = pick<double*>(r.out, nullptr, w.XA, w.XB, Sn); s.vout = pick<double*>(r.out, nullptr, w.xvA, w.xvB, mn);
+      s.Av0 = r.at == Where::End ? Ar1 : Ar; s.Av1 = mid ? Ar1 : nullptr; s.ldav = av.rows_ld;      // mid-point pair: A (start, end), b (end, start)
+      s.Ag0 = s.Av0; s.Ag1 = s.Av1; s.ldag = av.rows_ld;
+      if (r.fwd_state_for_a) { s.Ag0 = s.X + (size_t)row0 * D; s.ldag = D; }
+      s.e0 = r.at == Where::Start ? bk : bk1; s.e1 = mid ? bk : nullptr;
+      LD_TRY(shard_stage(c, s));
     }
     LD_TRY(keep(k + 1, Sn, mn));
     double* t1 = w.cur; w.cur = w.nxt; w.nxt = t1;
@@ -1193,7 +1153,7 @@ struct BwdIn {
 hipError_t shard_solve_bwd(ShardCtx& c, int Np, const AView& av, const BwdIn& in, double* lam_own, double* psi_own) {
   const int D = c.D, row0 = c.row0;
   const size_t DD = (size_t)D * D;
-  const double dt = c.dt, h = 0.5 * dt;
+  const Stepper& sch = kSteppers[c.method];
   ShardWork& w = c.w;
   int lo, hi;
   time_slice(Np, c.rank, c.world, &lo, &hi);
@@ -1217,28 +1177,19 @@ hipError_t shard_solve_bwd(ShardCtx& c, int Np, const AView& av, const BwdIn& in
     const double* jn = (in.obs_idx ? in.jm_sparse + (size_t)(nobs >= 0 ? nobs : 0) * D : in.jm_dense + (size_t)(t - 1) * D) + row0;
     const double *Pt = w.cur, *lt = w.vcur;
     double *Pn = w.nxt, *ln = w.vnxt;
-    ShardStage s{};
-    s.fwd = false; s.base = Pt; s.vbase = lt; s.ldag = av.cols_ld; s.ldav = av.rows_ld;
-    auto set = [&](const double* ag0, const double* ag1, const double* av0, const double* av1, const double* X, const double* xv,
-                   const double* E0, const double* E1, const double* e0, const double* e1, double* out, double* vout, int ks,
-                   int fin, double cx, double cf, bool jump) {
-      s.Ag0 = ag0; s.Ag1 = ag1; s.Av0 = av0; s.Av1 = av1; s.X = X; s.xv = xv; s.E0 = E0; s.E1 = E1; s.e0 = e0; s.e1 = e1;
-      s.out = out; s.vout = vout; s.kstore = ks; s.final_mode = fin; s.cx = cx; s.cf = cf;
-      s.J = (jump && has_jump) ? Jn : nullptr; s.jv = (jump && has_jump) ? jn : nullptr;
-    };
-    if (c.method == VGPA_ODE_EULER) {
-      set(Act, nullptr, Art, nullptr, Pt, lt, Gt, nullptr, gt, nullptr, Pn, ln, 0, 1, 0.0, dt, true); LD_TRY(shard_stage(c, s));
-    } else if (c.method == VGPA_ODE_HEUN) {
-      set(Act, nullptr, Art, nullptr, Pt, lt, Gt, nullptr, gt, nullptr, w.XA, w.xvA, 1, 0, dt, 0.0, false); LD_TRY(shard_stage(c, s));
-      set(Acm, nullptr, Arm, nullptr, w.XA, w.xvA, Gm, nullptr, gmm, nullptr, Pn, ln, 0, 2, 0.0, h, true); LD_TRY(shard_stage(c, s));
-    } else if (c.method == VGPA_ODE_RK2) {
-      set(Act, nullptr, Art, nullptr, Pt, lt, Gt, nullptr, gt, nullptr, w.XA, w.xvA, 0, 0, h, 0.0, false); LD_TRY(shard_stage(c, s));
-      set(Acm, Act, Arm, Art, w.XA, w.xvA, Gt, Gm, gt, gmm, Pn, ln, 0, 1, 0.0, dt, true); LD_TRY(shard_stage(c, s));
-    } else {
-      set(Act, nullptr, Art, nullptr, Pt, lt, Gt, nullptr, gt, nullptr, w.XA, w.xvA, 1, 0, h, 0.0, false); LD_TRY(shard_stage(c, s));
-      set(Acm, Act, Arm, Art, w.XA, w.xvA, Gt, Gm, gt, gmm, w.XB, w.xvB, 2, 0, h, 0.0, false); LD_TRY(shard_stage(c, s));
-      set(Acm, Act, Arm, Art, w.XB, w.xvB, Gt, Gm, gt, gmm, w.XA, w.xvA, 3, 0, dt, 0.0, false); LD_TRY(shard_stage(c, s));
-      set(Acm, nullptr, Arm, nullptr, w.XA, w.xvA, Gm, nullptr, gmm, nullptr, Pn, ln, 0, 3, 0.0, dt, true); LD_TRY(shard_stage(c, s));
+    for (int i = 0; i < sch.n; i++) {
+      const StageRow& r = sch.row[i];
+      const bool mid = r.at == Where::Mid, jump = r.out == Buf::Next && has_jump;
+      ShardStage s{};
+      s.fwd = false; s.row = r; s.dt = c.dt; s.base = Pt; s.vbase = lt; s.ldag = av.cols_ld; s.ldav = av.rows_ld;
+      s.X = pick<const double*>(r.in, Pt, w.XA, w.XB, nullptr); s.xv = pick<const double*>(r.in, lt, w.xvA, w.xvB, nullptr);
+      s.out = pick<double*>(r.out, nullptr, w.XA, w.XB, Pn); s.vout = pick<double*>(r.out, nullptr, w.xvA, w.xvB, ln);
+      s.Ag0 = r.at == Where::Start ? Act : Acm; s.Ag1 = mid ? Act : nullptr;      // mid-point pair: A (end, start), G and g (start, end)
+      s.Av0 = r.at == Where::Start ? Art : Arm; s.Av1 = mid ? Art : nullptr;
+      s.E0 = r.at == Where::End ? Gm : Gt; s.E1 = mid ? Gm : nullptr;
+      s.e0 = r.at == Where::End ? gmm : gt; s.e1 = mid ? gmm : nullptr;
+      s.J = jump ? Jn : nullptr; s.jv = jump ? jn : nullptr;
+      LD_TRY(shard_stage(c, s));
     }
     LD_TRY(keep(t - 1, Pn, ln));
     double* t1 = w.cur; w.cur = w.nxt; w.nxt = t1;
@@ -1872,7 +1823,8 @@ int vgpa_shard_time_stage(vgpa_shard* s, int reps, int with_collectives, double*
     st.E0 = w.cur + r0; st.e0 = w.vcur + c.row0;
     st.base = w.cur; st.vbase = w.vcur;
     st.out = (it & 1) ? w.XA : w.XB; st.vout = (it & 1) ? w.xvA : w.xvB;
-    st.kstore = 1; st.final_mode = 0; st.cx = 0.0; st.cf = 0.0;          // out = base + 0 * slope: the data stay what they are
+    st.row = ld::StageRow{ld::Where::Start, ld::Buf::Base, ld::Buf::XA, 1, 0, ld::Dt::Zero, ld::Dt::Zero};   // not a stepper's stage:
+    st.dt = 0.0;                                                          // out = base + 0 * slope: the data stay what they are
     if (ld::shard_stage(c, st) != hipSuccess) rc = c.failed ? VGPA_ERR_COMM : VGPA_ERR_DEVICE;
   }
   c.skip_comm = false;

@@ -58,6 +58,71 @@ struct StageArgs {
   size_t zM = 0, zXm = 0;
 };
 
+// ---------------------------------------------------------------------------------------------------------------
+// The stage schedule of the four steppers, once (DESIGN.md s.4.4 shows it as a table).  A step runs from its `Start` grid point
+// to its `End` one: k -> k + 1 forward, t -> t - 1 backward.  Per stage: whose A and forcing it reads, which buffer holds the
+// state it multiplies, where the result goes, the slot it stores and how the last stage combines the slots (kstore / final
+// above), and the two coefficients in units of dt.  The four drivers of large_d.hip walk these rows and only resolve the symbols
+// to their own operands; the backward ones add the jump on the row that writes `Next`.
+enum class Where { Start, Mid, End };       // Mid: 0.5 (start + end) of A and of the forcing (runge_kutta2.py:74, runge_kutta4.py:74)
+enum class Buf { Base, XA, XB, Next };      // Base: S_k / Psi_t; XA, XB: stage buffers; Next: S_{k+1} / Psi_{t-1}
+enum class Dt { Zero, Half, Full };
+struct StageRow {
+  Where at; Buf in, out; int kstore, final; Dt cx, cf;
+  // forward only: the product operand of the covariance slope is the stage's input state instead of A (the reference's quirk in
+  // its RK2 predictor, runge_kutta2.py:96: S_k stands in for A_k; the mean predictor and the backward recursion use A)
+  bool fwd_state_for_a = false;
+};
+constexpr int kMaxStages = 4;
+struct Stepper { int n; StageRow row[kMaxStages]; };
+constexpr Stepper kSteppers[4] = {                // indexed by VGPA_ODE_*
+    {1, {{Where::Start, Buf::Base, Buf::Next, 0, 1, Dt::Zero, Dt::Full}}},                 // Euler
+    {2, {{Where::Start, Buf::Base, Buf::XA, 1, 0, Dt::Full, Dt::Zero},                     // Heun
+         {Where::End, Buf::XA, Buf::Next, 0, 2, Dt::Zero, Dt::Half}}},
+    {2, {{Where::Start, Buf::Base, Buf::XA, 0, 0, Dt::Half, Dt::Zero, true},               // RK2 (mid-point)
+         {Where::Mid, Buf::XA, Buf::Next, 0, 1, Dt::Zero, Dt::Full}}},
+    {4, {{Where::Start, Buf::Base, Buf::XA, 1, 0, Dt::Half, Dt::Zero},                     // RK4
+         {Where::Mid, Buf::XA, Buf::XB, 2, 0, Dt::Half, Dt::Zero},
+         {Where::Mid, Buf::XB, Buf::XA, 3, 0, Dt::Full, Dt::Zero},
+         {Where::End, Buf::XA, Buf::Next, 0, 3, Dt::Zero, Dt::Full}}},
+};
+static_assert(VGPA_ODE_EULER == 0 && VGPA_ODE_HEUN == 1 && VGPA_ODE_RK2 == 2 && VGPA_ODE_RK4 == 3, "kSteppers is indexed by VGPA_ODE_*");
+static_assert(kSteppers[VGPA_ODE_EULER].n == 1 && kSteppers[VGPA_ODE_HEUN].n == 2 && kSteppers[VGPA_ODE_RK2].n == 2 &&
+              kSteppers[VGPA_ODE_RK4].n == 4, "stage counts");
+
+constexpr bool stepper_ok(const Stepper& s) {
+  if (s.n < 1 || s.n > kMaxStages) return false;
+  bool wrote[4] = {true, false, false, false};    // by Buf: Base holds the step's input
+  int slots = 0;                                  // the kstore values seen so far must read 1, 2, 3 in that order: 0, 1, 12, 123
+  for (int i = 0; i < s.n; i++) {
+    const StageRow& r = s.row[i];
+    const bool last = i == s.n - 1;
+    if ((r.out == Buf::Next) != last || (r.final != 0) != last) return false;     // exactly the last row writes Next and combines
+    if (r.in == Buf::Next || r.out == Buf::Base || r.in == r.out) return false;   // no row reads and writes one buffer
+    if (!wrote[(int)r.in]) return false;                                          // XA / XB only after a row of this step wrote it
+    if (r.final == 2 && slots != 1) return false;                                 // K1 + R needs K1
+    if (r.final == 3 && slots != 123) return false;                               // K1 + 2 K23 + R needs K1, K23 = R2, K23 += R3
+    if (r.final < 0 || r.final > 3 || r.kstore < 0 || r.kstore > 3) return false;
+    if (r.kstore) slots = slots * 10 + r.kstore;
+    if (last ? (r.cx != Dt::Zero || r.cf == Dt::Zero) : (r.cf != Dt::Zero || r.cx == Dt::Zero)) return false;
+    wrote[(int)r.out] = true;
+  }
+  return true;
+}
+static_assert(stepper_ok(kSteppers[VGPA_ODE_EULER]) && stepper_ok(kSteppers[VGPA_ODE_HEUN]) && stepper_ok(kSteppers[VGPA_ODE_RK2]) &&
+              stepper_ok(kSteppers[VGPA_ODE_RK4]), "stage schedule: see stepper_ok");
+
+constexpr double dt_times(Dt c, double dt) { return c == Dt::Zero ? 0.0 : c == Dt::Half ? 0.5 * dt : dt; }
+template <typename T> constexpr T pick(Buf b, T base, T xa, T xb, T next) {
+  return b == Buf::Base ? base : b == Buf::XA ? xa : b == Buf::XB ? xb : next;
+}
+
+// What a row states of a stage's arguments; the mid-point and jump flags follow the operands the driver resolved.
+inline void stage_row_args(StageArgs& a, bool fwd, const StageRow& r, double dt) {
+  a.fwd = fwd ? 1 : 0; a.kstore = r.kstore; a.final = r.final; a.cx = dt_times(r.cx, dt); a.cf = dt_times(r.cf, dt);
+  a.mid_e = a.E1 != nullptr; a.mid_a = a.A1 != nullptr; a.mid_ev = a.e1 != nullptr; a.has_j = a.J != nullptr;
+}
+
 constexpr int TS = 32;
 
 __device__ __forceinline__ double stage_combine(double r, double base, double k1, double k23, int fin, double cx,
@@ -67,6 +132,21 @@ __device__ __forceinline__ double stage_combine(double r, double base, double k1
   if (fin == 2) comb = k1 + r;
   if (fin == 3) comb = (k1 + 2.0 * k23 + r) / 6.0;
   return base + sgn * (cf * comb) + jump;
+}
+
+// The slot logic of one element (matrix element o of the row block, or vector entry o) behind its slope r: reads K1 / K23 as
+// `final` requires, stores per `kstore`, returns the element's new state.  Loads happen here, at their use; the tile pairs of the
+// one-kernel stages (large_d_stage.hip) request the same operands ahead of their k loop / first use and keep their own statement of
+// this logic on registers: routed through a helper, k_stage_prod<false, false> is allocated 141 instead of 142 registers.
+__device__ __forceinline__ double stage_slots(const StageArgs& a, double r, double sgn, const double* base, double* K1, double* K23,
+                                              bool has_jump, const double* J, size_t o) {
+  const double k1 = (a.final >= 2) ? K1[o] : 0.0;
+  const double k23 = (a.final == 3) ? K23[o] : 0.0;
+  if (a.kstore == 1) K1[o] = r;
+  else if (a.kstore == 2) K23[o] = r;
+  else if (a.kstore == 3) K23[o] = K23[o] + r;
+  const double jump = (a.final && has_jump) ? J[o] : 0.0;
+  return stage_combine(r, base[o], k1, k23, a.final, a.cx, a.cf, sgn, jump);
 }
 
 __device__ __forceinline__ void stage_batch_offsets(StageArgs& a) {
@@ -102,13 +182,7 @@ __device__ __forceinline__ void stage_vector_rows(const StageArgs& a, int blk) {
   if (lane == 0) {
     const double e = a.mid_ev ? 0.5 * (a.e1[r] + a.e0[r]) : a.e0[r];
     const double rv = a.fwd ? (-s + e) : (-e + s);
-    const double k1 = (a.final >= 2) ? a.k1v[r] : 0.0;
-    const double k23 = (a.final == 3) ? a.k23v[r] : 0.0;
-    if (a.kstore == 1) a.k1v[r] = rv;
-    else if (a.kstore == 2) a.k23v[r] = rv;
-    else if (a.kstore == 3) a.k23v[r] = a.k23v[r] + rv;
-    const double jump = (a.final && a.jv) ? a.jv[r] : 0.0;
-    a.vout[r] = stage_combine(rv, a.vbase[r], k1, k23, a.final, a.cx, a.cf, sgn, jump);
+    a.vout[r] = stage_slots(a, rv, sgn, a.vbase, a.k1v, a.k23v, a.jv != nullptr, a.jv, r);
   }
 }
 

@@ -349,13 +349,7 @@ __global__ void __launch_bounds__(NT) k_stage_wide(StageArgs a) {
     const size_t o = (size_t)r * D + j;
     const double e = a.mid_e ? 0.5 * (a.E1[o] + a.E0[o]) : a.E0[o];
     const double rv = a.fwd ? ((-w - wt) + e) : ((-e + wt) + w);
-    const double k1 = (a.final >= 2) ? a.K1[o] : 0.0;
-    const double k23 = (a.final == 3) ? a.K23[o] : 0.0;
-    if (a.kstore == 1) a.K1[o] = rv;
-    else if (a.kstore == 2) a.K23[o] = rv;
-    else if (a.kstore == 3) a.K23[o] = a.K23[o] + rv;
-    const double jump = (a.final && a.has_j) ? a.J[o] : 0.0;
-    const double res = stage_combine(rv, a.base[o], k1, k23, a.final, a.cx, a.cf, sgn, jump);
+    const double res = stage_slots(a, rv, sgn, a.base, a.K1, a.K23, a.has_j, a.J, o);
     if (direct) a.out[o] = res;
     return res;
   };
