@@ -30,10 +30,11 @@
  *   - there is NO CPU fallback: without a HIP device vgpa_create fails with VGPA_ERR_DEVICE.
  *
  * Batching: a context may hold `batch` independent problems that share the configuration
- * (model, theta, Sigma, R, H, dt, Np, method, observation count M) but have different variational
- * parameters x.  By default they also share the observations, m0, S0 and e0 of vgpa_config;
- * vgpa_set_problem_data gives each problem its own (one dataset per problem), and
- * vgpa_set_problem_params its own theta and Sigma (one parameter point per problem).  All per-problem
+ * (model, dt, Np, method) but have different variational parameters x.  By default they also share
+ * theta, Sigma, R, H, the observation count M, the observations, m0, S0 and e0 of vgpa_config;
+ * vgpa_set_problem_data gives each problem its own observations, m0, S0 and e0 (one dataset per problem),
+ * vgpa_set_problem_params its own theta and Sigma (one parameter point per problem), and
+ * vgpa_set_problem_obs_model its own observation count, R and H (one instrument per problem).  All per-problem
  * arrays are laid out problem-major: x[batch][len_x], mt[batch][Np][D], F[batch], ...
  */
 #ifndef VGPA_HIP_H
@@ -144,7 +145,9 @@ typedef struct {
  *   - VGPA_FETCH_PSIT / VGPA_FETCH_DESDE_DS in the time-chunked large-D sweep (they are never resident there);
  *   - per-problem parameters (vgpa_set_problem_params): a per-problem Sigma at D > 64 (per-problem theta is built there), and
  *     any per-problem theta or Sigma in the time-chunked large-D sweep and the row-sharded drivers;
- *   - vgpa_theta_gradient in the time-chunked large-D sweep (and the row-sharded drivers have no such entry point).
+ *   - vgpa_theta_gradient in the time-chunked large-D sweep (and the row-sharded drivers have no such entry point);
+ *   - a per-problem observation model (vgpa_set_problem_obs_model) at D > 64, in the time-chunked large-D sweep and in the
+ *     row-sharded drivers: they share the observation count, R and H.
  * The matrix-core stepping kernels cover D <= 64 with symmetric inputs; non-symmetric operator-level inputs run on the
  * generic LDS kernels (same results, ~15x slower at D = 40). */
 
@@ -245,7 +248,10 @@ int vgpa_set_prior_energy(vgpa_ctx* ctx, double e0);   /* sets every problem of 
  *   e0    [batch]         KL(q0||p0) of each problem
  * Rows that all equal the shared observation times keep the shared-time kernels.  On the 16-lane kernels (2 <= D <= 4, fewer than
  * 512 problems) per-problem times take dense jump arrays of batch * Np * (D + D*D) doubles.
- * Drops the cached state, like vgpa_release_x.  The additive constant of E_obs depends on M and R only and stays shared.
+ * Drops the cached state, like vgpa_release_x.  The additive constant of E_obs depends on M and R only and stays shared
+ * (vgpa_set_problem_obs_model makes it per problem).  With per-problem observation counts in force only the first n_obs[p] entries of
+ * problem p's obs_t / obs_y row are validated and read; with none in force every row is validated whole.  The context keeps a host
+ * copy of the obs_t rows, so this call and vgpa_set_problem_obs_model give the same state in either order.
  * VGPA_ERR_ARG: an obs_t row out of order or out of range; VGPA_ERR_STATE: an ODE-only context; VGPA_ERR_UNSUPPORTED:
  * per-problem obs_t at D > 64, and any per-problem data in the time-chunked large-D sweep.  A non-positive-definite s0 row
  * is reported by the sweep (VGPA_ERR_NOT_PD), as a shared one is.  vgpa_solve_fwd keeps its explicit m0 / s0. */
@@ -262,13 +268,35 @@ int vgpa_set_problem_data(vgpa_ctx* ctx, const int64_t* obs_t, const double* obs
  * previous parameters stay in force after either); VGPA_ERR_STATE: an ODE-only context; VGPA_ERR_UNSUPPORTED: per-problem Sigma
  * at D > 64, and any per-problem parameter in the time-chunked large-D sweep. */
 int vgpa_set_problem_params(vgpa_ctx* ctx, const double* theta, const double* sigma);
+/* Per-problem observation model of a batched context.  Each pointer may be NULL (= vgpa_config's value); every call states the whole set.
+ *   n_obs     [batch]        observations of problem p: 1 <= n_obs[p] <= M (M = vgpa_config.n_obs, now the CAPACITY of a row)
+ *   obs_noise [batch][D][D]  R_p   (1-D models: [batch])
+ *   obs_h     [batch][D][D]  H_p   (1-D models: NULL only)
+ * Problem p uses entries 0 .. n_obs[p] - 1 of its obs_t / obs_y row (the shared row or its own one of vgpa_set_problem_data); the entries
+ * from n_obs[p] on are never read and never validated -- callers may leave anything there (-1, NaN).  vgpa_set_problem_data validates
+ * the prefixes the counts in force select; a call here that lengthens a prefix onto an invalid stored entry fails with VGPA_ERR_ARG.
+ * Q = H R^-1 H^T, K, diag R^-1, the constant matrix jump H^T R^-1 H / 2 (whole and as a packed lower triangle) and the additive
+ * constant of E_obs, which depends on n_obs[p] and R_p, become per problem; each row's are computed on the host as vgpa_create
+ * computes the shared ones.  The kernel family is the one every row allows: diagonal R with H = I in every row takes the diagonal
+ * observation kernels, anything else the dense ones.  Rows that all equal the shared values (counts all M, R rows bit-equal to R, H
+ * rows bit-equal to H or NULL) keep the shared kernels and buffers: bit-identical to a context that never made the call.  Differing
+ * counts take a per-problem observation index map [batch][Np] even with shared times; on the 16-lane kernels (2 <= D <= 4, fewer than
+ * 512 problems) that is the dense-jump path of per-problem times, and the lane-per-problem kernels take the map for every per-problem model.
+ * Drops the cached state.  Seen by the fused objective (free_energy, gradient, sweep, sweep_enqueue), vgpa_energy_parts, vgpa_fetch,
+ * vgpa_theta_gradient and vgpa_obs_energy.  The reference's E_obs is kept per problem, its quirk included: the covariance diagonal of
+ * observation n is taken at grid index n.
+ * VGPA_ERR_ARG: a count outside [1, M], a 1-D obs_noise <= 0, an obs_h on a 1-D model; VGPA_ERR_NOT_PD: an R row that is not positive
+ * definite (the message names the row); the previous model stays in force after either.  n_obs[p] = 0 is an error on purpose: the
+ * multi-dimensional reference cannot evaluate it.  VGPA_ERR_STATE: an ODE-only context; VGPA_ERR_UNSUPPORTED: D > 64 (the time-chunked
+ * sweep included; the row-sharded drivers have no such entry point). */
+int vgpa_set_problem_obs_model(vgpa_ctx* ctx, const int32_t* n_obs, const double* obs_noise, const double* obs_h);
 /* 1 if the context runs the time-chunked large-D sweep (VGPA_FLAG_STREAM_LARGE_D or chosen for lack of memory) */
 int vgpa_is_streaming(vgpa_ctx* ctx);
 
 /* Which kernels the context's fused sweep runs and what its device buffers hold right now -- for TESTS AND DIAGNOSTICS: a test
  * that names a kernel path asserts here that it is on it.  Read-only: the call changes nothing, launches nothing, and nothing on
  * the hot path calls it.  The fields are the library's host-side plan (decided in vgpa_create, again when vgpa_set_problem_data /
- * vgpa_set_problem_params change the form of the inputs) and its record of the buffers (DESIGN.md s.4.0 has both tables). */
+ * vgpa_set_problem_params / vgpa_set_problem_obs_model change the form of the inputs) and its record of the buffers (DESIGN.md s.4.0 has both tables). */
 enum { VGPA_STEPPER_LARGE_D = 0,  /* D > 64: the per-stage drivers                                   */
        VGPA_STEPPER_LANE = 1,     /* D <= 4: one lane per problem                                    */
        VGPA_STEPPER_WAVE = 2,     /* 2 <= D <= 4: 16 lanes per problem                               */

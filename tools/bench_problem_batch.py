@@ -10,9 +10,15 @@ vgpa_profile_begin / _end), and the median per round is reported.
 
     python tools/bench_problem_batch.py [--rounds 5] [--steps 10]
     python tools/bench_problem_batch.py --mode theta [--rounds 5] [--steps 10]
+    python tools/bench_problem_batch.py --mode obs [--rounds 5] [--steps 10] [--variants shared,obs_model,obs_counts]
 
   l96   Lorenz-96, D = 40, RK4, Np = 1001, B = 512     (bench.py's headline configuration)
   l63   Lorenz-63, D = 3, RK4, Np = 1001, B = 65536    (bench.py's config2 block: the lane-per-problem kernels)
+
+--mode obs: the cost of a per-problem observation model (Context.set_problem_obs_model), timed like the default mode, in three
+contexts: "shared" (the model of vgpa_config), "obs_model" (per-problem R_p = R (1 + 0.1 (p mod 4)) and H_p, a 0/1 mask that drops
+component i when (i + p) mod 3 = 0; equal counts) and "obs_counts" (the same with per-problem counts cycling through M, M - 1, 1).
+All three on the dataset of vgpa_config, so that the difference is the observation model alone.  --variants picks a subset (the shared one alone also runs on a library without the entry point).
 
 --mode theta: the time of Context.theta_gradient() behind a free_energy, beside the time of that free_energy, on the same contexts
 (and on one more: l96_ld, Lorenz-96, D = 1024, RK4, Np = 33, B = 1).  Both are timed with a pair of device events on the context's
@@ -55,9 +61,16 @@ def make_contexts(name, d, n_pts, dt, B, nset=4, modes=("shared", "data", "data_
     k = np.arange(B)
     th = np.atleast_1d(np.asarray(theta, dtype=float))[None, :] * (1.0 + 0.05 * (k % 5))[:, None]
     sig = np.asarray(p0["model"].sigma, dtype=float)[None] * (1.0 + 0.1 * (k % 4))[:, None, None]      # sigma_p^2 I
+    # per-problem observation models (--mode obs)
+    r0 = np.reshape(np.asarray(p0["obs_noise"], dtype=float), (d, d))
+    obs_r = r0[None] * (1.0 + 0.1 * (k % 4))[:, None, None]
+    obs_h = np.stack([np.diag(((np.arange(d) + p) % 3 != 0).astype(float)) for p in range(B)]) if d > 1 else None
+    counts = np.array([(m, m - 1, 1)[p % 3] for p in range(B)], dtype=np.int32)
     ctxs = {}
     for mode in modes:
         c = va.Context(name, "RK4", d, n_pts, dt, **kw)
+        if mode in ("obs_model", "obs_counts"):
+            c.set_problem_obs_model(n_obs=counts if mode == "obs_counts" else None, obs_noise=obs_r, obs_h=obs_h)
         if mode in ("data", "data_t"):
             c.set_problem_data(obs_t=obs_t if mode == "data_t" else None, obs_y=obs_y, m0=m0, s0=s0, e0=e0s)
         if mode == "params":
@@ -67,8 +80,8 @@ def make_contexts(name, d, n_pts, dt, B, nset=4, modes=("shared", "data", "data_
     return ctxs, x0
 
 
-def run(name, d, n_pts, dt, B, rounds, steps):
-    ctxs, x0 = make_contexts(name, d, n_pts, dt, B)
+def run(name, d, n_pts, dt, B, rounds, steps, modes=("shared", "data", "data_t", "params")):
+    ctxs, x0 = make_contexts(name, d, n_pts, dt, B, modes=modes)
     len_x = x0.shape[1]
     rng = np.random.default_rng(1)
     rows = x0[np.arange(64) % x0.shape[0]] + 0.05 * rng.standard_normal((64, len_x))
@@ -97,12 +110,13 @@ def run(name, d, n_pts, dt, B, rounds, steps):
     for c in ctxs.values():
         c.close()
     med = {mode: float(np.median(v)) for mode, v in ms.items()}
-    return {"B": B, "D": d, "Np": n_pts,
-            "ms_per_sweep": {m: round(v, 4) for m, v in med.items()},
-            "sweeps_per_s": {m: round(B * 1e3 / v, 1) for m, v in med.items()},
-            "ratio_data": round(med["shared"] / med["data"], 4), "ratio_data_t": round(med["shared"] / med["data_t"], 4),
-            "ratio_params": round(med["shared"] / med["params"], 4),
-            "rounds_ms": {m: [round(x, 4) for x in v] for m, v in ms.items()}}
+    out = {"B": B, "D": d, "Np": n_pts,
+           "ms_per_sweep": {m: round(v, 4) for m, v in med.items()},
+           "sweeps_per_s": {m: round(B * 1e3 / v, 1) for m, v in med.items()}}
+    if "shared" in med:
+        out.update({"ratio_" + m: round(med["shared"] / v, 4) for m, v in med.items() if m != "shared"})
+    out["rounds_ms"] = {m: [round(x, 4) for x in v] for m, v in ms.items()}
+    return out
 
 
 class StreamTimer(object):
@@ -172,7 +186,8 @@ def run_theta(name, d, n_pts, dt, B, rounds, steps, modes=("shared", "data", "da
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--mode", choices=("sweep", "theta"), default="sweep")
+    ap.add_argument("--mode", choices=("sweep", "theta", "obs"), default="sweep")
+    ap.add_argument("--variants", default="shared,obs_model,obs_counts", help="--mode obs: the contexts to time")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--l63-batch", type=int, default=65536)
@@ -182,6 +197,13 @@ def main():
                "l96": run_theta("L96", 40, 1001, 0.01, 512, args.rounds, args.steps),
                "l63": run_theta("L63", 3, 1001, 0.01, args.l63_batch, args.rounds, args.steps),
                "l96_ld": run_theta("L96", 1024, 33, 0.01, 1, args.rounds, args.steps, modes=("shared",), nset=1)}
+        print(json.dumps(out), flush=True)
+        return
+    if args.mode == "obs":
+        modes = tuple(v for v in args.variants.split(",") if v)
+        out = {"tool": "bench_problem_batch", "mode": "obs",
+               "l96": run("L96", 40, 1001, 0.01, 512, args.rounds, args.steps, modes=modes),
+               "l63": run("L63", 3, 1001, 0.01, args.l63_batch, args.rounds, args.steps, modes=modes)}
         print(json.dumps(out), flush=True)
         return
     out = {"tool": "bench_problem_batch",

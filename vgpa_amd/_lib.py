@@ -38,7 +38,7 @@ SYMBOLS = ["vgpa_create", "vgpa_destroy", "vgpa_last_error", "vgpa_abi_version",
            "vgpa_fetch", "vgpa_theta_gradient", "vgpa_sweep_dev", "vgpa_free_energy_dev", "vgpa_sweep_enqueue", "vgpa_fetch_f",
            "vgpa_dev_alloc", "vgpa_dev_free", "vgpa_memcpy_h2d", "vgpa_memcpy_d2h",
            "vgpa_profile_begin", "vgpa_profile_end", "vgpa_ld_gemm", "vgpa_ld_stage", "vgpa_gradient_dev", "vgpa_energy_full", "vgpa_set_option", "vgpa_is_streaming", "vgpa_path_info", "vgpa_set_prior_energy",
-           "vgpa_set_problem_data", "vgpa_set_problem_params",
+           "vgpa_set_problem_data", "vgpa_set_problem_params", "vgpa_set_problem_obs_model",
            "vgpa_vec_dot", "vgpa_vec_absmax", "vgpa_vec_asum", "vgpa_vec_axpby", "vgpa_release_x",
            "vgpa_shard_create", "vgpa_shard_destroy", "vgpa_shard_time_slice", "vgpa_shard_stream", "vgpa_shard_synchronize",
            "vgpa_shard_solve_fwd", "vgpa_shard_solve_bwd", "vgpa_shard_sweep", "vgpa_shard_sweep_sharded", "vgpa_shard_set_option",
@@ -184,6 +184,7 @@ def load():
     lib.vgpa_set_prior_energy.argtypes = [c_void_p, c_double]
     lib.vgpa_set_problem_data.argtypes = [c_void_p] + [c_void_p] * 5
     lib.vgpa_set_problem_params.argtypes = [c_void_p] + [c_void_p] * 2
+    lib.vgpa_set_problem_obs_model.argtypes = [c_void_p] + [c_void_p] * 3
     lib.vgpa_profile_begin.argtypes = [c_void_p]
     lib.vgpa_profile_end.argtypes = [c_void_p, P_DOUBLE, P_DOUBLE, P_DOUBLE, P_DOUBLE, POINTER(c_int64)]
     abi = lib.vgpa_abi_version()
@@ -640,6 +641,22 @@ class Context:
         t = _shaped(theta, (B, self.n_theta), "theta")
         s = _shaped(sigma, (B, D, D), "sigma")
         self._check(self._lib.vgpa_set_problem_params(self._h, _ptr(t), _ptr(s)))
+
+    def set_problem_obs_model(self, n_obs=None, obs_noise=None, obs_h=None):
+        """
+        Gives every problem of the batch its own observation model: n_obs (B,) observation counts in [1, M] -- problem p then uses
+        the first n_obs[p] entries of its obs_t / obs_y row and nothing behind them, so rows may be padded with anything --, obs_noise
+        (B, D, D) and obs_h (B, D, D; not for 1-D models).  All carry the leading batch axis, also at B = 1 or D = 1.  None keeps the
+        shared value the context was created with; M, the context's observation count, is the capacity of a row.  Drops the cached
+        state.  A non-positive-definite obs_noise row raises LinAlgError, a count outside [1, M] or a 1-D obs_noise <= 0 ValueError;
+        the previous model then stays in force.
+        """
+        B, D = self.B, self.D
+        n = _shaped(n_obs, (B,), "n_obs", np.int64)
+        n = None if n is None else np.ascontiguousarray(n, dtype=np.int32)
+        r = _shaped(obs_noise, (B, D, D), "obs_noise")
+        h = _shaped(obs_h, (B, D, D), "obs_h")
+        self._check(self._lib.vgpa_set_problem_obs_model(self._h, _ptr(n), _ptr(r), _ptr(h)))
 
     @property
     def streaming(self):

@@ -8,6 +8,9 @@ takes per problem: the observation times and values, m0, S0 and E0 = KL(q0||p0) 
 `kl0`).  The batch then runs at the throughput of the batched kernels instead of one context per dataset.
 With own_parameters=True theta and Sigma leave the shared list: each member's own model.theta / model.sigma goes to
 `Context.set_problem_params` (a parameter study: one dataset at many (theta, Sigma) points).
+With own_observations=True the observation count M, R and H leave it too: the context holds rows of max_p M_p observations,
+shorter datasets are padded, and each member's own count, R and H go to `Context.set_problem_obs_model` (recordings of
+different length, instruments of different noise, sensors that see different components).
 
     pb = ProblemBatch([vgp_a, vgp_b, ...])
     x, f, stats = pb.optimise(pb.initialization(), {"max_it": 500})
@@ -17,7 +20,7 @@ import numpy as np
 
 from ._lib import Context
 
-__all__ = ["ProblemBatch", "theta_mstep"]
+__all__ = ["ProblemBatch", "theta_mstep", "stack_observations"]
 
 
 def theta_mstep(theta, g0, g1, pooled=False):
@@ -43,14 +46,39 @@ def _same(a, b):
     return a.shape == b.shape and np.array_equal(a, b)
 
 
+def stack_observations(rows):
+    """
+    The observation inputs of B members with their own counts, as one context takes them.  rows: B dictionaries with obs_t (M_p,),
+    obs_y (M_p, D) or (M_p,), obs_noise (D, D) and obs_h (D, D) or None.  Returns a dictionary: n_obs (B,) int32, obs_t (B, M) int64 and
+    obs_y (B, M, D) with M = max_p M_p -- the entries beyond a member's count hold -1 and NaN, which no kernel may read --, obs_noise
+    (B, D, D), obs_h (B, D, D) or None when no member has an operator (a member without one among others gets the identity).
+    """
+    n_obs = np.array([np.asarray(r["obs_t"]).size for r in rows], dtype=np.int32)
+    if n_obs.min() < 1:
+        raise ValueError(" ProblemBatch: every problem needs at least one observation.")
+    B, M = len(rows), int(n_obs.max())
+    D = np.asarray(rows[0]["obs_noise"]).shape[-1] if np.asarray(rows[0]["obs_noise"]).ndim else 1
+    obs_t = np.full((B, M), -1, dtype=np.int64)
+    obs_y = np.full((B, M, D), np.nan)
+    for p, r in enumerate(rows):
+        obs_t[p, :n_obs[p]] = np.asarray(r["obs_t"], dtype=np.int64).ravel()
+        obs_y[p, :n_obs[p]] = np.asarray(r["obs_y"], dtype=float).reshape(n_obs[p], D)
+    obs_noise = np.stack([np.asarray(r["obs_noise"], dtype=float).reshape(D, D) for r in rows])
+    obs_h = None
+    if any(r["obs_h"] is not None for r in rows):
+        obs_h = np.stack([np.eye(D) if r["obs_h"] is None else np.asarray(r["obs_h"], dtype=float).reshape(D, D) for r in rows])
+    return dict(n_obs=n_obs, obs_t=obs_t, obs_y=obs_y, obs_noise=obs_noise, obs_h=obs_h)
+
+
 class ProblemBatch(object):
 
-    def __init__(self, vgps, device=0, flags=0, own_parameters=False) -> None:
+    def __init__(self, vgps, device=0, flags=0, own_parameters=False, own_observations=False) -> None:
         self.vgps = list(vgps)
         if not self.vgps:
             raise ValueError(" ProblemBatch: no problems given.")
         self.device, self.flags = device, int(flags)
         self.own_parameters = bool(own_parameters)
+        self.own_observations = bool(own_observations)
         self.B = len(self.vgps)
         self._check_shared()
         first = self.vgps[0]
@@ -69,6 +97,8 @@ class ProblemBatch(object):
                   ("M", int(inp["obs_t"].size))]
         if self.own_parameters:     # (theta and sigma go to Context.set_problem_params instead)
             fields = [f for f in fields if f[0] not in ("theta", "sigma")]
+        if self.own_observations:   # (R, H and the count go to Context.set_problem_obs_model instead)
+            fields = [f for f in fields if f[0] not in ("R", "H", "M")]
         return fields
 
     def _check_shared(self):
@@ -85,10 +115,13 @@ class ProblemBatch(object):
     def _per_problem(self):
         """The per-problem inputs of every member, read from the objects NOW, and the priors E0 depends on."""
         rows = [vgp._inputs() for vgp in self.vgps]
-        obs_t = np.stack([r["obs_t"] for r in rows])
         prior = tuple(np.asarray(getattr(v.kl0, k, 0.0), dtype=float).tobytes() for v in self.vgps for k in ("mu0", "tau0"))
-        pp = dict(obs_t=obs_t, obs_y=np.stack([r["obs_y"].reshape(obs_t.shape[1], -1) for r in rows]),
-                  m0=np.stack([r["m0"] for r in rows]), s0=np.stack([r["s0"] for r in rows]))
+        if self.own_observations:   # padded rows of max_p M_p observations, every member's own count, R and H
+            pp = {k: v for k, v in stack_observations(rows).items() if v is not None}
+        else:
+            obs_t = np.stack([r["obs_t"] for r in rows])
+            pp = dict(obs_t=obs_t, obs_y=np.stack([r["obs_y"].reshape(obs_t.shape[1], -1) for r in rows]))
+        pp.update(m0=np.stack([r["m0"] for r in rows]), s0=np.stack([r["s0"] for r in rows]))
         if self.own_parameters:     # every member's own model.theta / model.sigma (and with them the context key)
             pp["theta"] = np.stack([r["theta"] for r in rows])
             pp["sigma"] = np.stack([r["sigma"] for r in rows])
@@ -97,8 +130,9 @@ class ProblemBatch(object):
     def _context(self):
         # like VarGP._context: a context built from inputs that have changed since is rebuilt (the shared ones are checked again)
         self._check_shared()
-        shared = self.vgps[0]._inputs()
         pp, prior = self._per_problem()
+        # (own observations: the member with the most observations lends the shared row, which vgpa_create validates whole)
+        shared = self.vgps[int(np.argmax(pp["n_obs"])) if self.own_observations else 0]._inputs()
         key = (shared["theta"].tobytes(), shared["sigma"].tobytes(), shared["obs_noise"].tobytes(),
                None if shared["obs_h"] is None else shared["obs_h"].tobytes(), prior) + tuple(pp[k].tobytes() for k in sorted(pp))
         if self._ctx is not None and key == self._ctx_key:
@@ -109,6 +143,8 @@ class ProblemBatch(object):
         # times stay shared when every member observes at the same grid points (the only form above D = 64).
         ctx = Context(self.vgps[0].model._model_id, self.vgps[0]._method, self.dim_d, self.dim_n, float(self.vgps[0].fwd_ode.dt),
                       e0=float(pp["e0"][0]), batch=self.B, device=self.device, flags=self.flags, **shared)
+        if self.own_observations:   # (the counts first: the padded rows below are then validated up to each member's own count)
+            ctx.set_problem_obs_model(n_obs=pp["n_obs"], obs_noise=pp["obs_noise"], obs_h=pp.get("obs_h"))
         same_t = bool(np.all(pp["obs_t"] == pp["obs_t"][:1]))
         ctx.set_problem_data(obs_t=None if same_t else pp["obs_t"], obs_y=pp["obs_y"], m0=pp["m0"], s0=pp["s0"], e0=pp["e0"])
         if self.own_parameters:

@@ -28,28 +28,48 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
   return r;
 }
 
+// The observation model of problem `prob` (PM: per-problem, vgpa_set_problem_obs_model -- the strides, obs_const_v and n_obs_v of ObsArgs are
+// set; else the shared one, read exactly as before).  prob is the block index: the offsets are wave-uniform address arithmetic.
+template <bool PM>
+struct ObsModel {
+  const double *Q, *K, *rinv;
+  double obs_const;
+  int n;                  // the problem's own observation count (<= a.n_obs, the capacity of its rows)
+  __device__ __forceinline__ ObsModel(const ObsArgs& a, int prob) {
+    if constexpr (PM) {
+      Q = a.Q + (size_t)prob * a.Q_stride; K = a.K + (size_t)prob * a.K_stride; rinv = a.rinv_diag + (size_t)prob * a.rinv_stride;
+      obs_const = a.obs_const_v[prob]; n = a.n_obs_v[prob];
+    } else {
+      Q = a.Q; K = a.K; rinv = a.rinv_diag; obs_const = a.obs_const; n = a.n_obs;
+    }
+  }
+};
+
 // One workgroup per problem.  jm_sparse[n][i] = -(K (y_n - m[t_n]))_i ; eobs = 0.5*(sum_n term_n + const)
+template <bool PM>
 __global__ void __launch_bounds__(NT) k_obs(ObsArgs a) {
   __shared__ double red[NT];
-  const int D = a.D, M = a.n_obs, prob = blockIdx.x, tid = threadIdx.x;
+  const int D = a.D, prob = blockIdx.x, tid = threadIdx.x;
+  const ObsModel<PM> om(a, prob);
+  const int M = om.n;                                      // (rows of a.n_obs entries; the problem's first M are read)
   const double* m = a.m + (size_t)prob * a.Np * D;
   const int MS = a.s_packed ? tri_off(D) : D * D;          // doubles per stored S_t (packed lower triangle: OdeArgs::s_packed)
   const double* S = a.S + (size_t)prob * a.Np * MS;
-  double* jm = a.jm_sparse + (size_t)prob * M * D;
+  double* jm = a.jm_sparse + (size_t)prob * a.n_obs * D;
   const int64_t* obs_t = a.obs_t + (size_t)prob * a.obs_t_stride;
   const double* obs_y = a.obs_y + (size_t)prob * a.obs_y_stride;
   double part = 0.0;
   if (a.single) {
-    const double rinv = a.Q[0];        // 1/r
+    const double rinv = om.Q[0];        // 1/r
     for (int n = tid; n < M; n += NT) {
       const int64_t tn = obs_t[n];
       const double y = obs_y[n], mm = m[tn], ss = S[tn];
       const double ex2 = mm * mm + ss;
       part += (y * y) - 2.0 * y * mm + ex2;       // gaussian_like.py:87-92 (divided by r below)
-      jm[n] = -(y - a.K[0] * mm) * rinv;          // gradients_1d: -(y - H m)/r, H = 1
+      jm[n] = -(y - om.K[0] * mm) * rinv;         // gradients_1d: -(y - H m)/r, H = 1
     }
     const double tot = block_sum(part, red);
-    if (tid == 0) a.eobs[prob] = 0.5 * tot * rinv + a.obs_const;
+    if (tid == 0) a.eobs[prob] = 0.5 * tot * rinv + om.obs_const;
     return;
   }
   // n-D: thread per (n, i)
@@ -61,27 +81,29 @@ __global__ void __launch_bounds__(NT) k_obs(ObsArgs a) {
     double qrow = 0.0, krow = 0.0;
     if (a.diag) {                                  // diagonal R^-1 and H^T R^-1 (the usual case): the other terms are exact zeros
       const double w = y[i] - mt[i];
-      qrow = __builtin_fma(a.Q[i * D + i], w, qrow);
-      krow = __builtin_fma(a.K[i * D + i], w, krow);
+      qrow = __builtin_fma(om.Q[i * D + i], w, qrow);
+      krow = __builtin_fma(om.K[i * D + i], w, krow);
     } else {
       for (int j = 0; j < D; j++) {
         const double w = y[j] - mt[j];
-        qrow = __builtin_fma(a.Q[i * D + j], w, qrow);
-        krow = __builtin_fma(a.K[i * D + j], w, krow);
+        qrow = __builtin_fma(om.Q[i * D + j], w, qrow);
+        krow = __builtin_fma(om.K[i * D + j], w, krow);
       }
     }
     jm[u] = -krow;
     // Q4: the covariance diagonal is taken at index n (observation counter), not at t_n
-    part += (y[i] - mt[i]) * qrow + a.rinv_diag[i] * S[(size_t)n * MS + (a.s_packed ? tri_off(i) + i : i * D + i)];
+    part += (y[i] - mt[i]) * qrow + om.rinv[i] * S[(size_t)n * MS + (a.s_packed ? tri_off(i) + i : i * D + i)];
   }
   const double tot = block_sum(part, red);
-  if (tid == 0) a.eobs[prob] = 0.5 * (tot + a.obs_const);
+  if (tid == 0) a.eobs[prob] = 0.5 * (tot + om.obs_const);
 }
 
 // n-D, one workgroup per (observation, problem): the variant for large D / many observations.  part[prob][n] = term_n.
+// (D > 64 only, where the observation model is the shared one)
 __global__ void __launch_bounds__(NT) k_obs_nd(ObsArgs a) {
   __shared__ double red[NT];
   const int D = a.D, M = a.n_obs, n = blockIdx.x, prob = blockIdx.y, tid = threadIdx.x;
+  const ObsModel<false> om(a, prob);
   const int64_t tn = a.obs_t[(size_t)prob * a.obs_t_stride + n];
   const double* y = a.obs_y + (size_t)prob * a.obs_y_stride + (size_t)n * D;
   const double* mt = a.m + ((size_t)prob * a.Np + tn) * D;
@@ -91,8 +113,8 @@ __global__ void __launch_bounds__(NT) k_obs_nd(ObsArgs a) {
   if (a.diag) {
     for (int i = tid; i < D; i += NT) {
       const double w = y[i] - mt[i];
-      jm[i] = -(a.K[(size_t)i * D + i] * w);
-      part += w * (a.Q[(size_t)i * D + i] * w) + a.rinv_diag[i] * S[((size_t)n * D + i) * D + i];   // Q4: S[n], not S[t_n]
+      jm[i] = -(om.K[(size_t)i * D + i] * w);
+      part += w * (om.Q[(size_t)i * D + i] * w) + om.rinv[i] * S[((size_t)n * D + i) * D + i];   // Q4: S[n], not S[t_n]
     }
   } else {
     // one wave per row i: coalesced reads of row i of Q and K
@@ -101,13 +123,13 @@ __global__ void __launch_bounds__(NT) k_obs_nd(ObsArgs a) {
       double qrow = 0.0, krow = 0.0;
       for (int j = lane; j < D; j += 64) {
         const double w = y[j] - mt[j];
-        qrow = __builtin_fma(a.Q[(size_t)i * D + j], w, qrow);
-        krow = __builtin_fma(a.K[(size_t)i * D + j], w, krow);
+        qrow = __builtin_fma(om.Q[(size_t)i * D + j], w, qrow);
+        krow = __builtin_fma(om.K[(size_t)i * D + j], w, krow);
       }
       for (int o = 32; o > 0; o >>= 1) { qrow += __shfl_xor(qrow, o, 64); krow += __shfl_xor(krow, o, 64); }
       if (lane == 0) {
         jm[i] = -krow;
-        part += (y[i] - mt[i]) * qrow + a.rinv_diag[i] * S[((size_t)n * D + i) * D + i];
+        part += (y[i] - mt[i]) * qrow + om.rinv[i] * S[((size_t)n * D + i) * D + i];
       }
     }
   }
@@ -124,9 +146,14 @@ __global__ void __launch_bounds__(NT) k_obs_fin(ObsArgs a) {
   if (tid == 0) a.eobs[prob] = 0.5 * (tot + a.obs_const);
 }
 
-// dense jump arrays for the operator-level API (zero off the observation rows)
+// dense jump arrays for the operator-level API (zero off the observation rows); grid (capacity of a row, batch)
+template <bool PM>
 __global__ void __launch_bounds__(NT) k_obs_dense(ObsArgs a, const double* js_const, double* jm_dense, double* js_dense) {
   const int D = a.D, M = a.n_obs, prob = blockIdx.y, n = blockIdx.x;
+  if constexpr (PM) {
+    if (n >= a.n_obs_v[prob]) return;
+    js_const += (size_t)prob * a.js_const_stride;
+  }
   const int64_t tn = a.obs_t[(size_t)prob * a.obs_t_stride + n];
   const double* jm = a.jm_sparse + ((size_t)prob * M + n) * D;
   for (int i = threadIdx.x; i < D; i += NT) jm_dense[((size_t)prob * a.Np + tn) * D + i] = jm[i];
@@ -668,18 +695,23 @@ hipError_t launch_trapz_multi(const double* e, int Np, int H, int batch, double 
 }
 
 hipError_t launch_obs(const ObsArgs& a, hipStream_t st) {
+  const bool pm = a.n_obs_v != nullptr;      // per-problem observation model: every field of the set, or none
+  if (pm && (!a.obs_const_v || !a.Q_stride || !a.K_stride || !a.rinv_stride)) return hipErrorInvalidValue;
   if (a.part && !a.single && a.n_obs > 0) {
+    if (pm) return hipErrorInvalidValue;     // (the grid-parallel variant serves D > 64, which shares the observation model)
     hipLaunchKernelGGL(k_obs_nd, dim3(a.n_obs, a.batch), dim3(NT), 0, st, a);
     hipLaunchKernelGGL(k_obs_fin, dim3(a.batch), dim3(NT), 0, st, a);
     return hipGetLastError();
   }
-  hipLaunchKernelGGL(k_obs, dim3(a.batch), dim3(NT), 0, st, a);
+  if (pm) hipLaunchKernelGGL(k_obs<true>, dim3(a.batch), dim3(NT), 0, st, a);
+  else hipLaunchKernelGGL(k_obs<false>, dim3(a.batch), dim3(NT), 0, st, a);
   return hipGetLastError();
 }
 
 hipError_t launch_obs_dense(const ObsArgs& a, const double* js_const, double* jm_dense, double* js_dense,
                             hipStream_t st) {
-  if (a.n_obs > 0) hipLaunchKernelGGL(k_obs_dense, dim3(a.n_obs, a.batch), dim3(NT), 0, st, a, js_const, jm_dense, js_dense);
+  if (a.n_obs > 0 && a.n_obs_v) hipLaunchKernelGGL(k_obs_dense<true>, dim3(a.n_obs, a.batch), dim3(NT), 0, st, a, js_const, jm_dense, js_dense);
+  else if (a.n_obs > 0) hipLaunchKernelGGL(k_obs_dense<false>, dim3(a.n_obs, a.batch), dim3(NT), 0, st, a, js_const, jm_dense, js_dense);
   return hipGetLastError();
 }
 

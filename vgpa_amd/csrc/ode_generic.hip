@@ -239,7 +239,8 @@ __global__ void __launch_bounds__(NT) k_fwd_generic(OdeArgs a) {
 }
 
 // jump (dE_obs) added after the step at index t-1
-template <int EPT>
+// PJ: per-problem constant matrix jump (OdeArgs::js_const_stride): the problem's own row -- prob is the block index, so the offset is uniform
+template <int EPT, bool PJ>
 __device__ __forceinline__ void load_jump(const OdeArgs& a, int prob, int t1, int D, int DD, double (&js)[EPT],
                                           double& jm) {
   const int tid = threadIdx.x;
@@ -250,13 +251,14 @@ __device__ __forceinline__ void load_jump(const OdeArgs& a, int prob, int t1, in
     jm = (tid < D) ? a.jm_dense[((size_t)prob * a.Np + t1) * D + tid] : 0.0;
   } else {
     const int n = a.obs_idx ? ldu(a.obs_idx + (size_t)prob * a.obs_idx_stride, t1) : -1;     // (scalar load: see vgpa_internal.h)
+    const double* jsc = PJ ? a.js_const + (size_t)prob * a.js_const_stride : a.js_const;
 #pragma unroll
-    for (int q = 0; q < EPT; q++) { const int e = tid + q * NT; js[q] = (n >= 0 && e < DD) ? a.js_const[e] : 0.0; }
+    for (int q = 0; q < EPT; q++) { const int e = tid + q * NT; js[q] = (n >= 0 && e < DD) ? jsc[e] : 0.0; }
     jm = (n >= 0 && tid < D) ? a.jm_sparse[((size_t)prob * a.n_obs + n) * D + tid] : 0.0;
   }
 }
 
-template <int METHOD, int EPT>
+template <int METHOD, int EPT, bool PJ = false>
 __global__ void __launch_bounds__(NT) k_bwd_generic(OdeArgs a) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int D = a.D, DD = D * D, Np = a.Np;
@@ -290,7 +292,7 @@ __global__ void __launch_bounds__(NT) k_bwd_generic(OdeArgs a) {
     const double* gsm = gst - DD;
     const double* gmt = gm + (size_t)t * D;
     const double* gmm = gmt - D;
-    load_jump<EPT>(a, prob, t - 1, D, DD, js, jm);
+    load_jump<EPT, PJ>(a, prob, t - 1, D, DD, js, jm);
     double lnew = 0.0;
     if (METHOD == VGPA_ODE_EULER) {
       fill_ab<false>(l.AB, At, At, DD);
@@ -413,7 +415,7 @@ hipError_t launch_m(const OdeArgs& a, hipStream_t st) {
   dim3 grid(a.batch), block(NT);
 #define VGPA_LAUNCH(E)                                                                       \
   do {                                                                                       \
-    auto kern = FWD ? k_fwd_generic<METHOD, E> : k_bwd_generic<METHOD, E>;                    \
+    auto kern = FWD ? k_fwd_generic<METHOD, E> : a.js_const_stride ? k_bwd_generic<METHOD, E, true> : k_bwd_generic<METHOD, E>; \
     if (lds > 48 * 1024)                                                                      \
       (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
     hipLaunchKernelGGL(kern, grid, block, lds, st, a);                                        \

@@ -598,7 +598,8 @@ struct EState {
   int prob;
 };
 
-template <int METHOD, bool FWD, int NB, int NE, bool DENSEJ>
+// PJ: per-problem constant matrix jump (OdeArgs::js_const_stride): the problem's own row, read once in the prologue
+template <int METHOD, bool FWD, int NB, int NE, bool DENSEJ, bool PJ = false>
 struct ERole {
   using g = Geo<NB>;
   static constexpr int NIT = EGeo<NB, NE>::NIT, NS = n_stages<METHOD>();
@@ -657,7 +658,8 @@ struct ERole {
       }
       if (!FWD && !DENSEJ && write_sig && item(q)) {     // the constant matrix jump, once per workgroup
         d2_t js{0.0, 0.0};
-        if (a.js_const) { js[0] = ldg(a.js_const, T.gofs[q]); js[1] = row2(q) ? ldg(a.js_const, T.gofs[q] + D8) : 0.0; }
+        const double* jsc = PJ ? a.js_const + (size_t)prob * a.js_const_stride : a.js_const;
+        if (a.js_const) { js[0] = ldg(jsc, T.gofs[q]); js[1] = row2(q) ? ldg(jsc, T.gofs[q] + D8) : 0.0; }
         *reinterpret_cast<d2_t*>(SIG + 2 * (te + q * NE)) = js;
       }
     }
@@ -774,9 +776,9 @@ struct ERole {
 };
 
 // One workgroup integrates one problem: the phases alternate product / element-wise stage, one workgroup barrier each.
-template <int METHOD, bool FWD, int NB, bool DENSEJ>
+template <int METHOD, bool FWD, int NB, bool DENSEJ, bool PJ>
 __device__ __forceinline__ void e_role(const OdeArgs& a, int prob, const Lds<NB>& L, double* __restrict__ SIG, int te) {
-  using Role = ERole<METHOD, FWD, NB, kNE, DENSEJ>;
+  using Role = ERole<METHOD, FWD, NB, kNE, DENSEJ, PJ>;
   constexpr int NS = Role::NS;
   const int n_steps = a.Np - 1;
   // The E waves issue few instructions, all on the critical path; the P wave of the same SIMD has MFMAs in flight when the
@@ -805,7 +807,7 @@ __device__ __forceinline__ void e_role(const OdeArgs& a, int prob, const Lds<NB>
 
 // =================================================================================================================
 // Workgroup = 8 waves = 4 P waves + 4 E waves, one problem.
-template <int METHOD, bool FWD, int NB, bool DENSEJ>
+template <int METHOD, bool FWD, int NB, bool DENSEJ, bool PJ = false>
 __global__ void __launch_bounds__(64 * kNPW + kNE) k_ode_pe(OdeArgs a) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   using g = Geo<NB>;
@@ -817,7 +819,7 @@ __global__ void __launch_bounds__(64 * kNPW + kNE) k_ode_pe(OdeArgs a) {
   double* SIG = smem + g::PROB;
   for (int i = tid; i < (int)g::LDS_DOUBLES; i += NT) smem[i] = 0.0;
   if (wave < kNPW) p_role<METHOD, FWD, NB>(a, prob, L, wave, lane);
-  else e_role<METHOD, FWD, NB, DENSEJ>(a, prob, L, SIG, tid - 64 * kNPW);
+  else e_role<METHOD, FWD, NB, DENSEJ, PJ>(a, prob, L, SIG, tid - 64 * kNPW);
 }
 
 template <int METHOD, bool FWD, int NB>
@@ -825,7 +827,8 @@ hipError_t launch_nb(const OdeArgs& a, hipStream_t st) {
   constexpr size_t lds = Geo<NB>::LDS_DOUBLES * sizeof(double);
   static_assert(lds <= 160 * 1024, "LDS budget");
   const bool dense = !FWD && a.js_dense;
-  auto kern = dense ? k_ode_pe<METHOD, FWD, NB, true> : k_ode_pe<METHOD, FWD, NB, false>;
+  constexpr bool PJ = !FWD;                           // (the per-problem constant jump belongs to the backward kernels with sparse jumps)
+  auto kern = dense ? k_ode_pe<METHOD, FWD, NB, true> : (!FWD && a.js_const_stride) ? k_ode_pe<METHOD, FWD, NB, false, PJ> : k_ode_pe<METHOD, FWD, NB, false>;
   if (lds > 48 * 1024)
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL(kern, dim3(a.batch), dim3(64 * kNPW + kNE), lds, st, a);

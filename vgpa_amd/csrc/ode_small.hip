@@ -369,7 +369,8 @@ __global__ void __launch_bounds__(NTS) __attribute__((amdgpu_waves_per_eu(1, 1))
 }
 
 // jump (dE_obs) added after the step at index t1
-template <int D>
+// PJ: per-problem constant matrix jump (OdeArgs::js_const_stride, always with per-problem observation indices): the lane's own row
+template <int D, bool PJ>
 __device__ __forceinline__ void load_jump(const OdeArgs& a, int prob, int t1, double (&js)[D * D], double (&jm)[D]) {
   constexpr int DD = D * D;
   if (a.js_dense) {
@@ -381,7 +382,7 @@ __device__ __forceinline__ void load_jump(const OdeArgs& a, int prob, int t1, do
     const int nc = n >= 0 ? n : 0;
     ld_vec<D>(a.jm_sparse + ((size_t)prob * a.n_obs + nc) * D, jm);
 #pragma unroll
-    for (int e = 0; e < DD; e++) js[e] = n >= 0 ? a.js_const[e] : 0.0;
+    for (int e = 0; e < DD; e++) js[e] = n >= 0 ? a.js_const[(PJ ? (size_t)prob * a.js_const_stride : 0) + e] : 0.0;
 #pragma unroll
     for (int i = 0; i < D; i++) jm[i] = n >= 0 ? jm[i] : 0.0;
   } else {
@@ -481,7 +482,7 @@ __device__ __forceinline__ void bwd_step(const double (&At)[D * D], const double
   }
 }
 
-template <int METHOD, int D>
+template <int METHOD, int D, bool PJ = false>
 __global__ void __launch_bounds__(NTS) k_bwd_small(OdeArgs a) {
   constexpr int DD = D * D;
   const int prob = blockIdx.x * NTS + threadIdx.x;
@@ -513,7 +514,7 @@ __global__ void __launch_bounds__(NTS) k_bwd_small(OdeArgs a) {
     const int tn = (t >= 2) ? t - 2 : 0;
     ld_mat<D>(A + (size_t)tn * DD, An); ld_mat<D>(gs + (size_t)tn * DD, gsn); ld_vec<D>(gm + (size_t)tn * D, gmn);
     double js[DD], jm[D];
-    load_jump<D>(a, prob, t - 1, js, jm);
+    load_jump<D, PJ>(a, prob, t - 1, js, jm);
 
     bwd_step<METHOD, D>(At, Am, gst, gsm, gmt, gmm, js, jm, dt, pk, lk);
     st_mat<D>(psi + (size_t)(t - 1) * DD, pk);
@@ -567,7 +568,8 @@ __device__ __forceinline__ void point_terms(const P& q, const double (&Av)[D * D
 // goes from t = hi - s + 1 to t - 1 = hi - s, whose operands sit in slot T - 1 - s; gLa / gLb of t - 1 take the slots of A / b.
 // PT: per-problem observation times (OdeArgs::obs_idx_stride): the observation index, and with it the jump, is the lane's own.
 // PP: per-problem parameters (LaneSweepArgs::theta_v ...): each lane loads its own theta, sigma and Sigma^-1 once, before the time loop.
-template <int METHOD, int MODEL, bool GRAD, int T, bool PT = false, bool PP = false>
+// PJ: per-problem observation model (OdeArgs::js_const_stride; with PT only): each lane loads its own constant matrix jump there too.
+template <int METHOD, int MODEL, bool GRAD, int T, bool PT = false, bool PP = false, bool PJ = false>
 __global__ void __launch_bounds__(NTS) __attribute__((amdgpu_waves_per_eu(1, 1))) k_sweep_lane(LaneSweepArgs q) {
   constexpr int D = (MODEL == VGPA_MODEL_L63) ? 3 : 1, DD = D * D, NA = T * DD, NV = T * D;
   __shared__ double sA[ChunkMap<NA>::LDS];
@@ -665,7 +667,10 @@ __global__ void __launch_bounds__(NTS) __attribute__((amdgpu_waves_per_eu(1, 1))
   // The constant matrix jump comes through scalar loads, once; w = 1 behind an observation, else 0.
   double jsc[DD];
 #pragma unroll
-  for (int e = 0; e < DD; e++) jsc[e] = a.js_const ? lds_const(a.js_const, e) : 0.0;
+  for (int e = 0; e < DD; e++) {
+    if constexpr (PJ) jsc[e] = a.js_const[(size_t)prob * a.js_const_stride + e];
+    else jsc[e] = a.js_const ? lds_const(a.js_const, e) : 0.0;
+  }
   auto obs_at = [&](int t1) -> int {
     if constexpr (PT) return t1 >= 0 ? a.obs_idx[(size_t)prob * a.obs_idx_stride + t1] : -1;     // (a vector load, consumed three steps on)
     return (a.obs_idx && t1 >= 0) ? ldu(a.obs_idx, t1) : -1;
@@ -881,7 +886,10 @@ hipError_t launch_d(const OdeArgs& a, hipStream_t st) {
   }
   if (FWD && a.Sigma_stride) hipLaunchKernelGGL((k_fwd_lane<METHOD, D, T, false, true>), grid, block, 0, st, a);
   else if (FWD) hipLaunchKernelGGL((k_fwd_lane<METHOD, D, T>), grid, block, 0, st, a);
-  else hipLaunchKernelGGL((k_bwd_small<METHOD, D>), grid, block, 0, st, a);
+  else if (a.js_const_stride) {
+    if (!a.obs_idx_stride || a.js_dense) return hipErrorInvalidValue;      // (the lane's own jump row comes with the lane's own observation index)
+    hipLaunchKernelGGL((k_bwd_small<METHOD, D, true>), grid, block, 0, st, a);
+  } else hipLaunchKernelGGL((k_bwd_small<METHOD, D>), grid, block, 0, st, a);
   return hipGetLastError();
 }
 
@@ -896,10 +904,10 @@ hipError_t launch_m(const OdeArgs& a, hipStream_t st) {
   return hipErrorInvalidValue;
 }
 
-template <int METHOD, int MODEL, int T, bool PT, bool PP>
+template <int METHOD, int MODEL, int T, bool PT, bool PP, bool PJ = false>
 void launch_sweep_lane_k(const LaneSweepArgs& q, dim3 grid, dim3 block, hipStream_t st) {
-  if (q.want_grad) hipLaunchKernelGGL((k_sweep_lane<METHOD, MODEL, true, T, PT, PP>), grid, block, 0, st, q);
-  else hipLaunchKernelGGL((k_sweep_lane<METHOD, MODEL, false, T, PT, PP>), grid, block, 0, st, q);
+  if (q.want_grad) hipLaunchKernelGGL((k_sweep_lane<METHOD, MODEL, true, T, PT, PP, PJ>), grid, block, 0, st, q);
+  else hipLaunchKernelGGL((k_sweep_lane<METHOD, MODEL, false, T, PT, PP>), grid, block, 0, st, q);      // (F alone takes no jump)
 }
 
 template <int METHOD, int MODEL>
@@ -911,6 +919,14 @@ hipError_t launch_sweep_mm(const LaneSweepArgs& q, hipStream_t st) {
   // 4.67 | 5.16-5.49 ms per 65536 problems.
   constexpr int T = (MODEL == VGPA_MODEL_L63) ? 4 : 16;
   if (q.o.obs_idx_stride && !q.o.jmT) return hipErrorInvalidValue;      // (per-problem times read the jumps from jmT)
+  if (q.o.js_const_stride) {      // per-problem observation model: on the per-problem-times kernels
+    if (!q.o.obs_idx_stride || !q.o.js_const) return hipErrorInvalidValue;
+    if (q.theta_v) {
+      if (!q.sigma1_v || !q.isig_v) return hipErrorInvalidValue;
+      launch_sweep_lane_k<METHOD, MODEL, T, true, true, true>(q, grid, block, st);
+    } else launch_sweep_lane_k<METHOD, MODEL, T, true, false, true>(q, grid, block, st);
+    return hipGetLastError();
+  }
   if (q.theta_v) {
     if (!q.sigma1_v || !q.isig_v) return hipErrorInvalidValue;
     if (q.o.obs_idx_stride) launch_sweep_lane_k<METHOD, MODEL, T, true, true>(q, grid, block, st);
@@ -966,10 +982,62 @@ __global__ void __launch_bounds__(NTS) k_ms_untranspose(int D, int Np, int batch
 // looping over the observations): E_obs and the sparse vector jumps, moments read from msT, jumps written to jmT -- both with the
 // problem fastest, so every access of a wave is one coalesced 512-byte transaction.  (Quirk Q4 kept: the covariance diagonal of
 // observation n is taken at grid index n, not at t_n; the 1-D models use S[t_n].)
-template <int D>
+// PM: per-problem observation model (ObsArgs::n_obs_v ...): the lane's own count, Q, K, diag R^-1 and additive constant, loaded once.
+template <int D, bool PM = false>
 __global__ void __launch_bounds__(NTS) k_obs_lane(ObsArgs a, const double* __restrict__ msT, int bpad, double* __restrict__ jmT) {
   const int prob = blockIdx.x * NTS + threadIdx.x;
   if (prob >= a.batch) return;
+  if constexpr (PM) {
+    const int M = a.n_obs_v[prob];
+    const size_t bp = (size_t)bpad;
+    constexpr int TRI = D * (D + 1) / 2, W = TRI + D, DD = D * D;
+    const double* ms = msT + prob;
+    double* jo = jmT + prob;
+    const int64_t* obs_t = a.obs_t + (size_t)prob * a.obs_t_stride;
+    const double* obs_y = a.obs_y + (size_t)prob * a.obs_y_stride;
+    const double oc = a.obs_const_v[prob];
+    double Q[DD], K[DD], rd[D], part = 0.0;
+#pragma unroll
+    for (int e = 0; e < DD; e++) { Q[e] = a.Q[(size_t)prob * a.Q_stride + e]; K[e] = a.K[(size_t)prob * a.K_stride + e]; }
+#pragma unroll
+    for (int i = 0; i < D; i++) rd[i] = a.rinv_diag[(size_t)prob * a.rinv_stride + i];
+    if (a.single) {      // (the expressions of the shared path below, on the lane's own constants)
+      for (int n = 0; n < M; n++) {
+        const size_t tn = (size_t)obs_t[n];
+        const double y = obs_y[n], ss = ms[(tn * W) * bp], mm = ms[(tn * W + 1) * bp];
+        const double ex2 = mm * mm + ss;
+        part += (y * y) - 2.0 * y * mm + ex2;
+        jo[(size_t)n * bp] = -(y - K[0] * mm) * Q[0];
+      }
+      a.eobs[prob] = 0.5 * part * Q[0] + oc;
+      return;
+    }
+    for (int n = 0; n < M; n++) {
+      const size_t tn = (size_t)obs_t[n];
+      const double* y = obs_y + (size_t)n * D;
+      double w[D];
+#pragma unroll
+      for (int j = 0; j < D; j++) w[j] = y[j] - ms[(tn * W + TRI + j) * bp];
+#pragma unroll
+      for (int i = 0; i < D; i++) {
+        double qrow = 0.0, krow = 0.0;
+        if (a.diag) {
+          qrow = __builtin_fma(Q[i * D + i], w[i], qrow);
+          krow = __builtin_fma(K[i * D + i], w[i], krow);
+        } else {
+#pragma unroll
+          for (int j = 0; j < D; j++) {
+            qrow = __builtin_fma(Q[i * D + j], w[j], qrow);
+            krow = __builtin_fma(K[i * D + j], w[j], krow);
+          }
+        }
+        jo[((size_t)n * D + i) * bp] = -krow;
+        part += w[i] * qrow + rd[i] * ms[((size_t)n * W + tri_off(i) + i) * bp];
+      }
+    }
+    a.eobs[prob] = 0.5 * (part + oc);
+    return;
+  }
   constexpr int TRI = D * (D + 1) / 2, W = TRI + D;
   const size_t bp = (size_t)bpad;
   const double* ms = msT + prob;
@@ -1025,7 +1093,10 @@ hipError_t launch_ms_untranspose(int D, int Np, int batch, int bpad, const doubl
 
 hipError_t launch_obs_lane(const ObsArgs& a, const double* msT, int bpad, double* jmT, hipStream_t st) {
   const dim3 grid((a.batch + NTS - 1) / NTS), block(NTS);
-  if (a.D == 1) hipLaunchKernelGGL(k_obs_lane<1>, grid, block, 0, st, a, msT, bpad, jmT);
+  if (a.n_obs_v && (!a.obs_const_v || !a.Q_stride || !a.K_stride || !a.rinv_stride)) return hipErrorInvalidValue;
+  if (a.D == 1 && a.n_obs_v) hipLaunchKernelGGL((k_obs_lane<1, true>), grid, block, 0, st, a, msT, bpad, jmT);
+  else if (a.D == 3 && a.n_obs_v) hipLaunchKernelGGL((k_obs_lane<3, true>), grid, block, 0, st, a, msT, bpad, jmT);
+  else if (a.D == 1) hipLaunchKernelGGL(k_obs_lane<1>, grid, block, 0, st, a, msT, bpad, jmT);
   else if (a.D == 3) hipLaunchKernelGGL(k_obs_lane<3>, grid, block, 0, st, a, msT, bpad, jmT);
   else return hipErrorInvalidValue;
   return hipGetLastError();

@@ -678,7 +678,7 @@ __device__ __forceinline__ void grad_waves(const OdeArgs& a, double* __restrict_
 // about as long as the product waves' stage, and the product waves wait for it in stages 0 and 1.  The
 // vector recursion (role 1) and the operand staging / state stores / operand loads (role 2) share nothing but the barriers: side by
 // side each chain is shorter than the products.
-template <int METHOD, bool FWD, int NB, bool DENSEJ, int GR, int WPE, bool QOUT = false, bool HLP = false, bool GF = false, bool H2 = false>   // WPE: waves per SIMD the register budget allows for
+template <int METHOD, bool FWD, int NB, bool DENSEJ, int GR, int WPE, bool QOUT = false, bool HLP = false, bool GF = false, bool H2 = false, bool PJ = false>   // WPE: waves per SIMD the register budget allows for
 __global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3 : (HLP ? 2 : 1)), 256 * ((GF || H2) ? 3 : (HLP ? 2 : 1))), amdgpu_waves_per_eu(WPE, WPE))) k_ode_sym(OdeArgs a) {
 #pragma clang fp contract(fast)
   extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -691,6 +691,7 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3
   static_assert(!HLP || COVER, "helper waves: fragment-cover kernels");
   static_assert(!GF || (HLP && QOUT && !FWD && !DENSEJ && METHOD == VGPA_ODE_RK4), "fused gradient assembly: backward RK4 helper-wave kernels with Q'' on");
   static_assert(!H2 || (HLP && !GF), "two helper roles: helper-wave kernels without the gradient waves");
+  static_assert(!PJ || (!FWD && !DENSEJ), "per-problem constant matrix jump: backward kernels with sparse jumps");
   constexpr int NITS = FWD ? g::NITF : g::NIT;     // staging items per thread
   constexpr int JSEC = NS > 1 ? 1 : 0;
   // the stage whose chores end with the requests for A_{t+2}, c_{t+2} (consumed at the top of the next step).  Helper-wave RK4 kernels:
@@ -1171,7 +1172,7 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3
       for (int s = 0; s < MAXS; s++) jsd[s] = 0.0;
       if (jump_now && a.js_const) {
 #pragma unroll
-        for (int s = 0; s < MAXS; s++) jsd[s] = ldg(a.js_const, gofs[s]);
+        for (int s = 0; s < MAXS; s++) jsd[s] = ldg(PJ ? a.js_const + (size_t)prob * a.js_const_stride : a.js_const, gofs[s]);      // (PJ: the problem's own row, OdeArgs::js_const_stride; prob is uniform)
       }
     }
     double w[NSL];
@@ -1449,12 +1450,14 @@ hipError_t launch_cover(const OdeArgs& a, hipStream_t st, bool dense) {
   constexpr size_t lds_c = SGeo<NB>::LDS_DOUBLES * sizeof(double);
   constexpr int WPE_C = (HLP || 2 * lds_c <= 160 * 1024) ? 2 : 1;
   constexpr int threads = HLP ? 512 : 256;
+  constexpr bool PJ = !FWD;                            // (the per-problem constant jump belongs to the backward kernels with sparse jumps)
+  const bool pj = !FWD && a.js_const_stride != 0;     // OdeArgs::js_const_stride: the kernels' PJ instantiations
   if constexpr (!FWD && METHOD == VGPA_ODE_RK4 && HLP) {
     if (a.grad_on) {                                   // the gradient assembly on the helper waves (k_ode_sym, GF)
       if (dense || !a.q_on || !a.s_packed || !a.g || !a.S || !a.m || !a.Ef || !a.Am || !a.b) return hipErrorInvalidValue;
       constexpr size_t lds_g = lds_c + GradLds<NB>::DOUBLES * sizeof(double);
       static_assert(lds_g <= 160 * 1024, "LDS budget");
-      auto kg = k_ode_sym<METHOD, FWD, NB, false, 0, 3, true, true, true>;      // 768 threads: three waves per SIMD, 168 registers each
+      auto kg = pj ? k_ode_sym<METHOD, FWD, NB, false, 0, 3, true, true, true, false, PJ> : k_ode_sym<METHOD, FWD, NB, false, 0, 3, true, true, true>;      // 768 threads: three waves per SIMD, 168 registers each
       (void)hipFuncSetAttribute((const void*)kg, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_g);
       hipLaunchKernelGGL(kg, dim3(a.batch), dim3(768), lds_g, st, a);
       return hipGetLastError();
@@ -1466,13 +1469,13 @@ hipError_t launch_cover(const OdeArgs& a, hipStream_t st, bool dense) {
       if constexpr (!FWD && (METHOD == VGPA_ODE_RK2 || METHOD == VGPA_ODE_RK4)) {
         if (a.q_on) {
           if (dense) return hipErrorInvalidValue;
-          auto kq2 = k_ode_sym<METHOD, FWD, NB, false, 0, 3, true, true, false, true>;
+          auto kq2 = pj ? k_ode_sym<METHOD, FWD, NB, false, 0, 3, true, true, false, true, PJ> : k_ode_sym<METHOD, FWD, NB, false, 0, 3, true, true, false, true>;
           (void)hipFuncSetAttribute((const void*)kq2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c);
           hipLaunchKernelGGL(kq2, dim3(a.batch), dim3(768), lds_c, st, a);
           return hipGetLastError();
         }
       }
-      auto kc2 = dense ? k_ode_sym<METHOD, FWD, NB, true, 0, 3, false, true, false, true> : k_ode_sym<METHOD, FWD, NB, false, 0, 3, false, true, false, true>;
+      auto kc2 = dense ? k_ode_sym<METHOD, FWD, NB, true, 0, 3, false, true, false, true> : pj ? k_ode_sym<METHOD, FWD, NB, false, 0, 3, false, true, false, true, PJ> : k_ode_sym<METHOD, FWD, NB, false, 0, 3, false, true, false, true>;
       (void)hipFuncSetAttribute((const void*)kc2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c);
       hipLaunchKernelGGL(kc2, dim3(a.batch), dim3(768), lds_c, st, a);
       return hipGetLastError();
@@ -1481,14 +1484,14 @@ hipError_t launch_cover(const OdeArgs& a, hipStream_t st, bool dense) {
   if constexpr (!FWD && (METHOD == VGPA_ODE_RK2 || METHOD == VGPA_ODE_RK4)) {
     if (a.q_on) {
       if (dense) return hipErrorInvalidValue;          // (the fused sweeps bring sparse jumps)
-      auto kq = k_ode_sym<METHOD, FWD, NB, false, 0, WPE_C, true, HLP>;
+      auto kq = pj ? k_ode_sym<METHOD, FWD, NB, false, 0, WPE_C, true, HLP, false, false, PJ> : k_ode_sym<METHOD, FWD, NB, false, 0, WPE_C, true, HLP>;
       if (lds_c > 48 * 1024)
         (void)hipFuncSetAttribute((const void*)kq, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c);
       hipLaunchKernelGGL(kq, dim3(a.batch), dim3(threads), lds_c, st, a);
       return hipGetLastError();
     }
   }
-  auto kc = dense ? k_ode_sym<METHOD, FWD, NB, true, 0, WPE_C, false, HLP> : k_ode_sym<METHOD, FWD, NB, false, 0, WPE_C, false, HLP>;
+  auto kc = dense ? k_ode_sym<METHOD, FWD, NB, true, 0, WPE_C, false, HLP> : pj ? k_ode_sym<METHOD, FWD, NB, false, 0, WPE_C, false, HLP, false, false, PJ> : k_ode_sym<METHOD, FWD, NB, false, 0, WPE_C, false, HLP>;
   if (lds_c > 48 * 1024)
     (void)hipFuncSetAttribute((const void*)kc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c);
   hipLaunchKernelGGL(kc, dim3(a.batch), dim3(threads), lds_c, st, a);
@@ -1522,7 +1525,8 @@ hipError_t launch_sym(const OdeArgs& a, hipStream_t st) {
     constexpr int GR = 1;
     if (a.grad_on) return hipErrorInvalidValue;
     constexpr int WPE = 2 * lds <= 160 * 1024 ? 2 : 1;     // two workgroups per CU when their LDS fits, else all 512 registers
-    auto kern = dense ? k_ode_sym<METHOD, FWD, NB, true, GR, WPE> : k_ode_sym<METHOD, FWD, NB, false, GR, WPE>;
+    constexpr bool PJ = !FWD;                          // (as in launch_cover)
+    auto kern = dense ? k_ode_sym<METHOD, FWD, NB, true, GR, WPE> : (!FWD && a.js_const_stride) ? k_ode_sym<METHOD, FWD, NB, false, GR, WPE, false, false, false, false, PJ> : k_ode_sym<METHOD, FWD, NB, false, GR, WPE>;
     if (lds > 48 * 1024)
       (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(kern, dim3(a.batch), dim3(256), lds, st, a);

@@ -154,7 +154,8 @@ __global__ void __launch_bounds__(NTW) k_fwd_wave(OdeArgs a) {
   }
 }
 
-template <int METHOD, int D, bool DENSEJ>
+// PJ: per-problem constant matrix jump (OdeArgs::js_const_stride, sparse jumps at shared observation times): each lane's own row, once
+template <int METHOD, int D, bool DENSEJ, bool PJ = false>
 __global__ void __launch_bounds__(NTW) k_bwd_wave(OdeArgs a) {
   constexpr int DD = D * D;
   const int lane = threadIdx.x;
@@ -184,7 +185,7 @@ __global__ void __launch_bounds__(NTW) k_bwd_wave(OdeArgs a) {
   // jumps of index t-1 (js, jm) and t-2 (requested inside the step); sparse: constant matrix jump at observation
   // indices, the index itself fetched two steps ahead through a VGPR (see ode_mfma_impl.h)
   const bool sparse = !DENSEJ && a.obs_idx;
-  const double jsc = (!DENSEJ && a.js_const) ? a.js_const[em] : 0.0;
+  const double jsc = (!DENSEJ && a.js_const) ? a.js_const[(PJ ? (size_t)prob * a.js_const_stride : 0) + em] : 0.0;
   int n_cur = (sparse && Np > 1) ? a.obs_idx[Np - 2] : -1;
   int n_next = (sparse && Np > 2) ? a.obs_idx[Np - 3] : -1;
   int vzero;
@@ -273,6 +274,7 @@ hipError_t launch_d(const OdeArgs& a, hipStream_t st) {
   dim3 grid((a.batch + 3) / 4), block(NTW);
   if (FWD) hipLaunchKernelGGL((k_fwd_wave<METHOD, D>), grid, block, 0, st, a);
   else if (a.js_dense) hipLaunchKernelGGL((k_bwd_wave<METHOD, D, true>), grid, block, 0, st, a);
+  else if (a.js_const_stride) hipLaunchKernelGGL((k_bwd_wave<METHOD, D, false, true>), grid, block, 0, st, a);
   else hipLaunchKernelGGL((k_bwd_wave<METHOD, D, false>), grid, block, 0, st, a);
   return hipGetLastError();
 }

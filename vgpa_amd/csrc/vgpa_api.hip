@@ -23,6 +23,10 @@ struct BatchInputs {
   Rows<int32_t> obs_idx;               // [B][Np] -> observation counter n, or -1
   Rows<double> theta, Sigma, isig, isg;   // [B][kMaxTheta], [B][D][D], [B][D][D] Sigma^-1, [B][D] its diagonal (above D = 64: theta only)
   Rows<double> sig1, qs;               // [B] 1-D sigma, [B] 1 / sigma_p^2 of an isotropic row
+  // the observation model (vgpa_set_problem_obs_model): Q = H R^-1 H^T, K, diag R^-1, the constant matrix jump whole and as a packed lower
+  // triangle (rows of D*D doubles both), the additive constant of E_obs and the observation count -- the last two null while shared
+  Rows<double> Q, K, rinv, jsc, jscp, obs_const;   // [B][D][D] x2, [B][D], [B][D][D] x2, [B]
+  Rows<int32_t> n_obs;                 // [B]
   std::vector<double> h_theta, h_isig, h_sig1, h_e0;  // host copies of the per-problem values (theta_of, isig_of, sigma1_of, e0_of)
 };
 
@@ -138,6 +142,15 @@ struct vgpa_ctx {
   double *d_jm_pt = nullptr, *d_js_pt = nullptr;   // dense jumps [B][Np][D], [B][Np][D][D]: per-problem times on the 16-lane kernels
   bool pt_dense_zeroed = false;  // ... which are zero off the observation rows of the current times (each sweep rewrites only those rows)
   std::vector<double> h_sigma;       // host copy of the shared Sigma [D][D]
+  // per-problem observation model (vgpa_set_problem_obs_model)
+  double *d_pp_Q = nullptr, *d_pp_K = nullptr, *d_pp_rinv = nullptr, *d_pp_jsc = nullptr, *d_pp_jscp = nullptr, *d_pp_obsc = nullptr;
+  int32_t* d_pp_nobs = nullptr;
+  std::vector<double> h_R, h_H;       // host copies of the shared R and H [D][D] (H: the identity when vgpa_config gave none)
+  std::vector<int64_t> h_obs_t;       // host copy of the shared observation times [M] ...
+  std::vector<int64_t> h_pp_obs_t;    // ... and of the per-problem rows in force [B][M] (empty: the shared row), so that either setter validates against the other's state
+  std::vector<int32_t> h_nobs;        // the per-problem counts in force [B] (empty: M each)
+  bool obs_model_rows = false;        // a per-problem observation model is in force
+  bool shared_obs_diag = false, jsc_rows_sym = true;   // obs_diag of vgpa_config's model; every per-problem constant jump symmetric
   SigmaForm sigma_form, rows_form;            // make_plan's inputs: the form of the shared Sigma, of the per-problem rows in force,
   bool inputs_sym = true, s0_rows_sym = true;  // ... the shared s0 and constant jump symmetric, the per-problem s0 rows symmetric
   // profiling
@@ -398,7 +411,7 @@ static void make_plan(vgpa_ctx* c) {
   // s0 / Sigma and the constant jump (else both products of the slope literally)
   const SigmaForm& f = c->in.Sigma.stride ? c->rows_form : c->sigma_form;
   p.sigma_diag = f.diag; p.isg_iso = f.iso;
-  p.sym_inputs = c->inputs_sym && c->s0_rows_sym && c->sigma_form.sym && f.sym;
+  p.sym_inputs = c->inputs_sym && c->s0_rows_sym && c->jsc_rows_sym && c->sigma_form.sym && f.sym;
   // D <= 44 has two families of matrix-core stepping kernels: the symmetric-unit ones (two problems per CU, 4 waves each) win
   // once there are more problems than CUs, the role-specialised ones (one problem per CU, 8 waves) below that and for one
   // problem.  (D = 41 .. 44: one symmetric-unit workgroup per CU only -- its LDS -- so the role-specialised kernels stay.)
@@ -481,7 +494,8 @@ static void copy_theta(const vgpa_ctx* c, double* theta) {
 // the sparse observation jumps of the backward recursion (dEsde_dS is never packed behind the lane pass: js_const = d_jsc there)
 static void sparse_jumps(vgpa_ctx* c, OdeArgs& a) {
   a.obs_idx = c->in.obs_idx.rows; a.obs_idx_stride = (int)c->in.obs_idx.stride;
-  a.jm_sparse = c->d_jm; a.js_const = c->res.dEs == Resident::DesLayout::Packed ? c->d_jscp : c->d_jsc; a.n_obs = c->M;
+  a.jm_sparse = c->d_jm; a.js_const = c->res.dEs == Resident::DesLayout::Packed ? c->in.jscp.rows : c->in.jsc.rows; a.n_obs = c->M;
+  a.js_const_stride = c->in.jsc.stride;      // (the packed copy's rows are D*D apart too)
 }
 
 // sym: Plan::sym_inputs for the fused sweep (the stepper is then Plan::fwd), the symmetry of the caller's arrays for vgpa_solve_fwd
@@ -535,7 +549,7 @@ static int run_bwd(vgpa_ctx* c, bool dense_jumps, bool sym, double* g_fused = nu
       HIP_TRY(c, hipMemsetAsync(c->d_js_pt, 0, sizeof(double) * c->B * c->Np * c->DD, c->stream));
       c->pt_dense_zeroed = true;
     }
-    LAUNCH_TRY(c, "obs dense launch", launch_obs_dense(obs_args(c), c->d_jsc, c->d_jm_pt, c->d_js_pt, c->stream));
+    LAUNCH_TRY(c, "obs dense launch", launch_obs_dense(obs_args(c), c->in.jsc.rows, c->d_jm_pt, c->d_js_pt, c->stream));
     a.jm_dense = c->d_jm_pt; a.js_dense = c->d_js_pt;
   } else {
     sparse_jumps(c, a);
@@ -619,7 +633,9 @@ static ObsArgs obs_args(vgpa_ctx* c) {
   ObsArgs a{};
   a.D = c->D; a.Np = c->Np; a.batch = c->B; a.n_obs = c->M; a.single = c->single ? 1 : 0;
   a.obs_t = c->in.obs_t.rows; a.obs_t_stride = c->in.obs_t.stride; a.obs_y = c->in.obs_y.rows; a.obs_y_stride = c->in.obs_y.stride;
-  a.Q = c->d_Q; a.K = c->d_K; a.rinv_diag = c->d_rinv;
+  a.Q = c->in.Q.rows; a.Q_stride = c->in.Q.stride; a.K = c->in.K.rows; a.K_stride = c->in.K.stride;
+  a.rinv_diag = c->in.rinv.rows; a.rinv_stride = c->in.rinv.stride; a.js_const_stride = c->in.jsc.stride;
+  a.obs_const_v = c->in.obs_const.rows; a.n_obs_v = c->in.n_obs.rows;
   a.obs_const = c->obs_const; a.m = c->d_m; a.S = c->d_S; a.jm_sparse = c->d_jm; a.eobs = c->d_eobs;
   a.diag = c->obs_diag ? 1 : 0; a.part = c->d_obs_part;
   a.s_packed = c->res.S == Resident::SLayout::Packed ? 1 : 0;
@@ -1019,6 +1035,12 @@ int vgpa_create(vgpa_ctx** out, const vgpa_config* cfg) {
     rc = obs_constants(D, c->M, single, cfg->obs_noise, cfg->obs_h, Q.data(), K.data(), rinv.data(), jsc.data(), &c->obs_const, &c->obs_diag);
     if (rc) FAIL(rc, single ? "observation noise must be positive" : "observation noise matrix is not positive definite");
     c->inputs_sym = c->inputs_sym && is_symmetric(jsc.data(), D);
+    c->shared_obs_diag = c->obs_diag;
+    c->h_obs_t.assign(cfg->obs_t, cfg->obs_t + c->M);
+    c->h_R.assign(cfg->obs_noise, cfg->obs_noise + (single ? 1 : DD));
+    c->h_H.assign(DD, 0.0);
+    for (int i = 0; i < D; i++) c->h_H[(size_t)i * D + i] = 1.0;
+    if (cfg->obs_h) c->h_H.assign(cfg->obs_h, cfg->obs_h + (single ? 1 : DD));
     if (D > kMaxSmallD) TRY(dev_alloc(c, &c->d_obs_part, (size_t)c->B * c->M));   // one workgroup per observation
     TRY(upload(c, c->d_obs_t, cfg->obs_t, (size_t)c->M));
     TRY(upload(c, c->d_obs_y, cfg->obs_y, (size_t)c->M * D));
@@ -1054,6 +1076,7 @@ int vgpa_create(vgpa_ctx** out, const vgpa_config* cfg) {
   BatchInputs& in = c->in;       // every problem on the inputs of vgpa_config
   in.m0 = {c->d_m0, 0}; in.S0 = {c->d_S0, 0}; in.obs_y = {c->d_obs_y, 0}; in.obs_t = {c->d_obs_t, 0}; in.obs_idx = {c->d_obs_idx, 0};
   in.Sigma = {c->d_Sigma, 0}; in.isig = {c->d_isig, 0}; in.isg = {c->d_isg, 0};
+  in.Q = {c->d_Q, 0}; in.K = {c->d_K, 0}; in.rinv = {c->d_rinv, 0}; in.jsc = {c->d_jsc, 0}; in.jscp = {c->d_jscp, 0};
   make_plan(c);
 #undef FAIL
 #undef TRY
@@ -1195,7 +1218,7 @@ int vgpa_obs_energy(vgpa_ctx* c, const double* mt, const double* st, double* eob
     if ((rc = ensure(c, &c->d_js_dense, BN * c->DD))) return rc;
     HIP_TRY(c, hipMemsetAsync(c->d_jm_dense, 0, sizeof(double) * BN * c->D, c->stream));
     HIP_TRY(c, hipMemsetAsync(c->d_js_dense, 0, sizeof(double) * BN * c->DD, c->stream));
-    LAUNCH_TRY(c, "obs dense launch", launch_obs_dense(a, c->d_jsc, c->d_jm_dense, c->d_js_dense, c->stream));
+    LAUNCH_TRY(c, "obs dense launch", launch_obs_dense(a, c->in.jsc.rows, c->d_jm_dense, c->d_js_dense, c->stream));
     if (deobs_dm && (rc = download(c, deobs_dm, c->d_jm_dense, BN * c->D))) return rc;
     if (deobs_ds && (rc = download(c, deobs_ds, c->d_js_dense, BN * c->DD))) return rc;
   }
@@ -1522,32 +1545,60 @@ int vgpa_set_prior_energy(vgpa_ctx* c, double e0) {
   return VGPA_OK;
 }
 
+// The observation index maps [B][Np] of candidate inputs: obs_t rows [B][M] (null: the shared row for every problem) under counts [B] (null:
+// M each).  Only the first counts[p] entries of a row are read.  model_rows: a per-problem observation model is (about to be) in force.
+// *shared: every map equals the shared one, so that the shared-time kernels stay -- unless the stepper is the lane one and model_rows, whose
+// kernels take a per-problem model on their per-problem-times instantiations.  false: the context's message names the row.
+static bool index_batch_times(vgpa_ctx* c, const int64_t* rows, const int32_t* counts, bool model_rows, std::vector<int32_t>* idx, bool* shared) {
+  const int M = c->M, Np = c->Np, B = c->B;
+  const bool lane_rows = model_rows && stepper(c, false, true) == Stepper::Lane;
+  *shared = !lane_rows;
+  idx->clear();
+  if (!rows && !counts && !lane_rows) return true;
+  idx->resize((size_t)B * Np);
+  for (int p = 0; p < B; p++) {
+    int32_t* row = idx->data() + (size_t)p * Np;
+    if (!index_obs_times(rows ? rows + (size_t)p * M : c->h_obs_t.data(), counts ? counts[p] : M, Np, row)) {
+      fail(c, VGPA_ERR_ARG, "problem %d: obs_t must be strictly increasing indices in [0, Np)", p);
+      return false;
+    }
+    *shared = *shared && std::memcmp(row, c->h_obs_idx.data(), sizeof(int32_t) * Np) == 0;
+  }
+  return true;
+}
+
+// ... and what index_batch_times found, put in force: the per-problem maps (and the rows of c->h_pp_obs_t, if any) unless shared.  Synchronous.
+static int commit_times(vgpa_ctx* c, const std::vector<int32_t>& idx, bool shared) {
+  BatchInputs& in = c->in;
+  int rc;
+  in.obs_t = {c->d_obs_t, 0}; in.obs_idx = {c->d_obs_idx, 0};
+  if (shared) return VGPA_OK;
+  if (!c->h_pp_obs_t.empty() && (rc = upload_rows(c, &c->d_pp_obs_t, c->h_pp_obs_t.data(), c->M, &in.obs_t))) return rc;
+  if ((rc = upload_rows(c, &c->d_pp_obs_idx, idx.data(), c->Np, &in.obs_idx))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));          // (idx lives on the caller's stack frame)
+  return VGPA_OK;
+}
+
 // Per-problem inputs of a batched context (see vgpa_hip.h).  Everything is validated before anything is uploaded.
 int vgpa_set_problem_data(vgpa_ctx* c, const int64_t* obs_t, const double* obs_y, const double* m0, const double* s0, const double* e0) {
   if (!c) return VGPA_ERR_ARG;
   if (!c->full) return fail(c, VGPA_ERR_STATE, "context was created without m0/s0/observations (ODE-only)");
   if (c->stream_ld) return fail(c, VGPA_ERR_UNSUPPORTED, "the time-chunked large-D sweep holds one problem: no per-problem data");
-  const int D = c->D, M = c->M, Np = c->Np, B = c->B;
-  std::vector<int32_t> idx(obs_t && M > 0 ? (size_t)B * Np : 0);
+  const int D = c->D, M = c->M, B = c->B;
+  std::vector<int32_t> idx;
   bool shared_t = true;             // every row at the shared times: keep the shared-time kernels (the same results, bit for bit)
-  if (obs_t && M > 0) {
-    if (D > kMaxSmallD)
-      return fail(c, VGPA_ERR_UNSUPPORTED, "per-problem observation times exist for D <= %d (D = %d shares the times of vgpa_config)", kMaxSmallD, D);
-    for (int p = 0; p < B; p++) {
-      int32_t* row = idx.data() + (size_t)p * Np;
-      if (!index_obs_times(obs_t + (size_t)p * M, M, Np, row))
-        return fail(c, VGPA_ERR_ARG, "problem %d: obs_t must be strictly increasing indices in [0, Np)", p);
-      shared_t = shared_t && std::memcmp(row, c->h_obs_idx.data(), sizeof(int32_t) * Np) == 0;
-    }
-  }
+  if (obs_t && M > 0 && D > kMaxSmallD)
+    return fail(c, VGPA_ERR_UNSUPPORTED, "per-problem observation times exist for D <= %d (D = %d shares the times of vgpa_config)", kMaxSmallD, D);
+  // (only the prefix that the counts in force select is read: vgpa_set_problem_obs_model)
+  if (M > 0 && !index_batch_times(c, obs_t, c->h_nobs.empty() ? nullptr : c->h_nobs.data(), c->obs_model_rows, &idx, &shared_t)) return VGPA_ERR_ARG;
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   int rc;
   // every call states the whole per-problem set: an input passed as NULL is the shared one of vgpa_config again
   BatchInputs& in = c->in;
-  in.obs_t = {c->d_obs_t, 0}; in.obs_idx = {c->d_obs_idx, 0}; in.obs_y = {c->d_obs_y, 0}; in.m0 = {c->d_m0, 0}; in.S0 = {c->d_S0, 0};
+  in.obs_y = {c->d_obs_y, 0}; in.m0 = {c->d_m0, 0}; in.S0 = {c->d_S0, 0};
   in.e0 = {};
-  if (!shared_t && (rc = upload_rows(c, &c->d_pp_obs_t, obs_t, M, &in.obs_t))) return rc;
-  if (!shared_t && (rc = upload_rows(c, &c->d_pp_obs_idx, idx.data(), Np, &in.obs_idx))) return rc;
+  if (obs_t && M > 0) c->h_pp_obs_t.assign(obs_t, obs_t + (size_t)B * M); else c->h_pp_obs_t.clear();
+  if ((rc = commit_times(c, idx, shared_t))) return rc;
   if (obs_y && M > 0 && (rc = upload_rows(c, &c->d_pp_obs_y, obs_y, (size_t)M * D, &in.obs_y))) return rc;
   if (m0 && (rc = upload_rows(c, &c->d_pp_m0, m0, D, &in.m0))) return rc;
   if (s0 && (rc = upload_rows(c, &c->d_pp_S0, s0, c->DD, &in.S0))) return rc;
@@ -1555,7 +1606,7 @@ int vgpa_set_problem_data(vgpa_ctx* c, const int64_t* obs_t, const double* obs_y
     in.h_e0.assign(e0, e0 + B);
     if ((rc = upload_rows(c, &c->d_pp_e0, in.h_e0.data(), 1, &in.e0))) return rc;
   }
-  HIP_TRY(c, hipStreamSynchronize(c->stream));          // (idx lives on this stack frame)
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->s0_rows_sym = !s0 || stack_symmetric(s0, (size_t)B, D);       // (a non-symmetric s0 row: both products literally)
   make_plan(c);
   c->pt_dense_zeroed = false;
@@ -1613,6 +1664,74 @@ int vgpa_set_problem_params(vgpa_ctx* c, const double* theta, const double* sigm
   }
   c->rows_form = rows;
   make_plan(c);
+  return VGPA_OK;
+}
+
+// Per-problem observation model of a batched context (see vgpa_hip.h).  Every row's constants come from obs_constants, as vgpa_create computes
+// the shared ones; everything is validated before anything changes: after an error the previous model stays in force.
+int vgpa_set_problem_obs_model(vgpa_ctx* c, const int32_t* n_obs, const double* obs_noise, const double* obs_h) {
+  if (!c) return VGPA_ERR_ARG;
+  if (!c->full) return fail(c, VGPA_ERR_STATE, "context was created without m0/s0/observations (ODE-only)");
+  if (c->D > kMaxSmallD || c->stream_ld)
+    return fail(c, VGPA_ERR_UNSUPPORTED, "a per-problem observation model exists for D <= %d (D = %d shares the model of vgpa_config)", kMaxSmallD, c->D);
+  const int D = c->D, M = c->M, B = c->B;
+  const size_t DD = c->DD, RS = c->single ? 1 : DD;      // doubles per R row
+  if (M < 1) return fail(c, VGPA_ERR_ARG, "the context has no observations");
+  if (c->single && obs_h) return fail(c, VGPA_ERR_ARG, "1-D models take no observation operator");
+  bool same = true;                 // every row at the shared model: the shared kernels and buffers (the same results, bit for bit)
+  for (int p = 0; p < B; p++) {
+    if (n_obs && (n_obs[p] < 1 || n_obs[p] > M)) return fail(c, VGPA_ERR_ARG, "problem %d: %d observations, outside [1, %d]", p, n_obs[p], M);
+    same = same && (!n_obs || n_obs[p] == M) && (!obs_noise || std::memcmp(obs_noise + p * RS, c->h_R.data(), sizeof(double) * RS) == 0) &&
+           (!obs_h || std::memcmp(obs_h + p * DD, c->h_H.data(), sizeof(double) * DD) == 0);
+  }
+  std::vector<double> Q, K, rinv, jsc, jscp, oc;
+  bool all_diag = true, all_sym = true;
+  if (!same) {
+    Q.assign(B * DD, 0.0); K.assign(B * DD, 0.0); rinv.assign((size_t)B * D, 0.0); jsc.assign(B * DD, 0.0); jscp.assign(B * DD, 0.0); oc.assign(B, 0.0);
+    for (int p = 0; p < B; p++) {
+      const double* Rp = obs_noise ? obs_noise + p * RS : c->h_R.data();
+      if (c->single && !(Rp[0] > 0.0)) return fail(c, VGPA_ERR_ARG, "problem %d: observation noise must be positive, got %g", p, Rp[0]);
+      bool diag = false;
+      double* jp = jsc.data() + p * DD;
+      const int rc = obs_constants(D, n_obs ? n_obs[p] : M, c->single, Rp, obs_h ? obs_h + p * DD : c->h_H.data(), Q.data() + p * DD, K.data() + p * DD,
+                                   rinv.data() + (size_t)p * D, jp, &oc[p], &diag);
+      if (rc) return fail(c, rc, "problem %d: observation noise matrix is not positive definite", p);
+      all_diag = all_diag && diag; all_sym = all_sym && is_symmetric(jp, D);
+      for (int r = 0; r < D; r++)      // the packed-triangle copy, as vgpa_create makes the shared one
+        for (int q = 0; q <= r; q++) jscp[p * DD + (size_t)r * (r + 1) / 2 + q] = jp[(size_t)r * D + q];
+    }
+  }
+  // the index maps of the new counts over the observation times in force; a prefix that now reaches an invalid stored entry fails here
+  std::vector<int32_t> idx;
+  bool shared_t = true;
+  if (!index_batch_times(c, c->h_pp_obs_t.empty() ? nullptr : c->h_pp_obs_t.data(), (same || !n_obs) ? nullptr : n_obs, !same, &idx, &shared_t)) return VGPA_ERR_ARG;
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  int rc;
+  BatchInputs& in = c->in;
+  if (!same) {      // (uploads first: a failed allocation leaves the record on the previous rows)
+    Rows<double> rQ, rK, rr, rj, rjp, roc; Rows<int32_t> rn;
+    std::vector<int32_t> cnt(B, M);
+    if (n_obs) cnt.assign(n_obs, n_obs + B);
+    if ((rc = upload_rows(c, &c->d_pp_Q, Q.data(), DD, &rQ)) || (rc = upload_rows(c, &c->d_pp_K, K.data(), DD, &rK)) ||
+        (rc = upload_rows(c, &c->d_pp_rinv, rinv.data(), D, &rr)) || (rc = upload_rows(c, &c->d_pp_jsc, jsc.data(), DD, &rj)) ||
+        (rc = upload_rows(c, &c->d_pp_jscp, jscp.data(), DD, &rjp)) || (rc = upload_rows(c, &c->d_pp_obsc, oc.data(), 1, &roc)) ||
+        (rc = upload_rows(c, &c->d_pp_nobs, cnt.data(), 1, &rn)))
+      return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));          // (the host rows live on this stack frame)
+    in.Q = rQ; in.K = rK; in.rinv = rr; in.jsc = rj; in.jscp = rjp; in.obs_const = roc; in.n_obs = rn;
+    c->h_nobs = n_obs ? cnt : std::vector<int32_t>();
+  } else {
+    in.Q = {c->d_Q, 0}; in.K = {c->d_K, 0}; in.rinv = {c->d_rinv, 0}; in.jsc = {c->d_jsc, 0}; in.jscp = {c->d_jscp, 0};
+    in.obs_const = {}; in.n_obs = {};
+    c->h_nobs.clear();
+  }
+  c->obs_model_rows = !same;
+  c->obs_diag = same ? c->shared_obs_diag : all_diag;      // the kernel family every row allows
+  c->jsc_rows_sym = same || all_sym;
+  if ((rc = commit_times(c, idx, shared_t))) return rc;
+  make_plan(c);
+  c->pt_dense_zeroed = false;
+  c->res.cache_dropped();           // (like the other setters: the cached state belongs to the old model)
   return VGPA_OK;
 }
 

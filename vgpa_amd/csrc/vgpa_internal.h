@@ -94,6 +94,8 @@ struct OdeArgs {
   // per-problem parameters (vgpa_set_problem_params), last for the same reason
   size_t Sigma_stride;           // D*D: Sigma is [B][D][D]; 0: shared by the batch
   const double* q_scale_v;       // [B] 1 / sigma_p^2 instead of q_scale, or nullptr
+  // per-problem observation model (vgpa_set_problem_obs_model), last for the same reason
+  size_t js_const_stride;        // D*D: js_const is [B][D][D] (packed copy: the first D (D + 1) / 2 of each row); 0: shared by the batch
 };
 
 // Fused lane-per-problem pass of the models with closed-form moments (OU, double well, Lorenz-63; ode_small.hip::k_sweep_lane):
@@ -181,6 +183,11 @@ struct ObsArgs {
   int diag;                 // Q and K are diagonal (diagonal R, H = I)
   double* part;             // [B][M] per-observation terms of the n-D energy (grid-parallel variant) or nullptr
   size_t obs_t_stride, obs_y_stride;   // elements between consecutive problems' obs_t / obs_y; 0: shared by the batch
+  // per-problem observation model (vgpa_set_problem_obs_model), last so that the offsets above stay where they were: all set or all 0 / nullptr
+  size_t Q_stride, K_stride, rinv_stride;   // D*D, D*D, D: Q / K / rinv_diag are [B][D][D] / [B][D][D] / [B][D]; 0: shared by the batch
+  const double* obs_const_v;     // [B] instead of obs_const, or nullptr
+  const int32_t* n_obs_v;        // [B] observations of problem p (<= n_obs, the capacity of a row) instead of n_obs, or nullptr
+  size_t js_const_stride;        // launch_obs_dense: D*D when its js_const is [B][D][D]; 0: shared by the batch
 };
 
 struct GradArgs {
