@@ -191,7 +191,8 @@ int vgpa_fetch(vgpa_ctx* ctx, int which, double* out);
  * reference's dEsde_dth, built from the closed-form mean drift, is not.)  F is exactly quadratic in theta with a diagonal
  * Hessian at fixed (A_t, b_t): h = g(theta + 1) - g(theta) is the curvature, theta - g / h the minimiser.
  * VGPA_ERR_STATE: no cached state (also after vgpa_release_x, vgpa_set_problem_data, vgpa_set_problem_params), ODE-only
- * contexts; VGPA_ERR_UNSUPPORTED: the time-chunked large-D sweep. */
+ * contexts; VGPA_ERR_UNSUPPORTED: the time-chunked large-D sweep; VGPA_ERR_NOT_PD: the evaluation that left the state failed with
+ * it (an S_t of the named problem is not positive definite) -- nothing is written to out then. */
 int vgpa_theta_gradient(vgpa_ctx* ctx, double* out);
 
 /* device-pointer variants (x, g on the context's device; f written to HOST after a sync) ------ */

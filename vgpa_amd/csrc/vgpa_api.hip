@@ -1394,7 +1394,9 @@ int vgpa_theta_gradient(vgpa_ctx* c, double* out) {
   }
   std::vector<double> T((size_t)B * H);
   if ((rc = download(c, T.data(), res, T.size()))) return rc;
-  if ((rc = vgpa_synchronize(c))) return rc;
+  // the status words of the resident state (set by the sweep that cached it, and by the Lorenz-96 integrand kernels above, which end at a
+  // bad pivot without writing their integrand): behind an evaluation that failed with VGPA_ERR_NOT_PD this fails the same way
+  if ((rc = check_status(c))) return rc;
   for (int p = 0; p < B; p++) {
     const double* Tp = T.data() + (size_t)p * H;
     if (c->single) out[p] = (c->cfg.model == VGPA_MODEL_DW ? 4.0 : 1.0) * Tp[0] / sigma1_of(c, p);      // (the factors of vgpa_energy_full)
