@@ -53,7 +53,8 @@ extern "C" {
    result beyond rounding; tests use them to reach paths the defaults take only at other sizes.  Nothing in vgpa_amd/ sets any of them.
 
    VGPA_ODE_KERNEL=pe|sym     33 <= D <= 44 / D <= 44: keep the role-specialised steppers (pe) / take the symmetric-unit ones (sym)
-   VGPA_SYM_HELPERS=0|1       fragment-cover steppers: helper waves off / on at every batch size (default: up to one problem per CU)
+   VGPA_SYM_HELPERS=0|1|2     fragment-cover steppers: no helper waves / one helper role / two at every batch size (default: two up to
+                              one problem per CU, none beyond); read by vgpa_create, like VGPA_ODE_KERNEL
    VGPA_FUSED_GRAD=0|1        backward RK4 fragment-cover kernel: never / always assemble the gradient on its third wave set
                               (default: from 64 problems per context on)
    VGPA_SHARD_CHUNKS=<n>      row-sharded recursion: sub-blocks of the pipelined gather (default 4; 0 = the serial schedule);
@@ -310,6 +311,7 @@ enum { VGPA_LAYOUT_WHOLE = 0,     /* whole D x D matrices                       
 enum { VGPA_BWD_NONE = 0,         /* nothing of the cached state is in lam_t / Psi_t's buffers       */
        VGPA_BWD_PSI = 1,          /* lam_t and Psi_t                                                 */
        VGPA_BWD_Q = 2             /* lam_t and Q''_t = Sigma^-1 A_t - 2 Psi_t                        */ };
+/* (The struct only ever grows at its end: a field added later follows the last one, whichever of the two groups it belongs to.) */
 typedef struct {
   /* the plan: what a fused sweep WILL run */
   int32_t fwd, bwd;               /* VGPA_STEPPER_* of the two sweep directions                      */
@@ -328,6 +330,8 @@ typedef struct {
   int32_t dEs;                    /* VGPA_LAYOUT_*: dEsde_dS                                         */
   int32_t bwd_holds;              /* VGPA_BWD_*                                                      */
   int32_t terms;                  /* dEsde_dm / dEsde_dS / <f> / E_sde(t) belong to the cached moments */
+  /* the plan again (added at the end) */
+  int32_t helper_roles;           /* fragment-cover steppers: sets of helper waves, 0 / 1 / 2 (0 on every other stepper) */
 } vgpa_path;
 int vgpa_path_info(vgpa_ctx* ctx, vgpa_path* out);   /* VGPA_ERR_ARG for a null argument */
 

@@ -66,6 +66,13 @@ def fused_grad_switch():
     return os.environ.get("VGPA_FUSED_GRAD", "")[:1]
 
 
+def helper_switch():
+    """VGPA_SYM_HELPERS as the library reads it: None when it is not set (two helper roles up to one problem per CU, none beyond), else the
+    "0" / "1" / "2" that force that many at every batch size -- so that the path assertions also hold in a run of the whole suite
+    under either value."""
+    return os.environ.get("VGPA_SYM_HELPERS")
+
+
 def with_sigma_forms(cases, ids):
     """Every case with the default diagonal Sigma under the id it always had, then again with Sigma = sigma^2 I (id + "-iso")."""
     return [pytest.param(*c, form, id=i + tail) for form, tail in (("diag", ""), ("iso", "-iso")) for c, i in zip(cases, ids)]
@@ -507,7 +514,8 @@ def test_diagnostic_phase_repeat_leaves_the_results_alone_with_isotropic_sigma()
 def test_stepper_variants_of_the_fragment_cover_agree(sigma="diag"):
     """33 <= D <= 40 on the fragment-cover steppers: with four or eight helper waves beside the four product waves of a workgroup (the
     default up to one problem per CU: the chores of a stage off the product waves' issue slots) and without them the same operations run in the same
-    order -- F and the gradient must not differ in any bit.  The switch is read once per process: child processes;
+    order -- F and the gradient must not differ in any bit.  The switch is read when a context is created: child processes, each of
+    which prints the helper roles of its plans (1, 2, 0: the three runs did take different kernels);
     RK4, Heun and RK2, an unpadded and two padded dimensions, one problem and small batches.  "iso": Sigma = sigma^2 I, the packed
     layouts and Q''_t of the RK4 / RK2 cases (each child prints its plans); "diag": whole matrices."""
     import json
@@ -525,16 +533,18 @@ def test_stepper_variants_of_the_fragment_cover_agree(sigma="diag"):
         "    f, g = ctx.sweep(xb)\n"
         "    out['%%d %%s' %% (d, method)] = {'f': [float(v) for v in np.atleast_1d(f)], 'g': np.asarray(g).ravel().tolist(),\n"
         "                                   'packed': ctx.plan()['packed'], 'S': ctx.resident()['S']}\n"
+        "    out.setdefault('helper_roles', []).append(ctx.plan()['helper_roles'])\n"
         "    ctx.close()\n"
         "print(json.dumps(out))\n" % (os.path.dirname(__file__), sigma))
     outs = {}
-    for name, env_set in (("helpers", {"VGPA_SYM_HELPERS": "1"}), ("two", {"VGPA_SYM_HELPERS": "2"}), ("plain", {"VGPA_SYM_HELPERS": "0"})):
+    for name, env_set, roles in (("helpers", {"VGPA_SYM_HELPERS": "1"}, 1), ("two", {"VGPA_SYM_HELPERS": "2"}, 2), ("plain", {"VGPA_SYM_HELPERS": "0"}, 0)):
         env = dict(os.environ)
         env.pop("VGPA_SYM_HELPERS", None)
         env.update(env_set)
         r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, r.stderr[-2000:]
         outs[name] = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert outs[name].pop("helper_roles") == [roles] * 3, name          # (before any bits are compared: the runs differ in their kernels)
     for key, ref in outs["plain"].items():
         packed = sigma == "iso" and not key.endswith("heun")
         assert ref["packed"] == packed and ref["S"] == ("packed" if packed else "whole"), key

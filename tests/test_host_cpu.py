@@ -1,4 +1,5 @@
 """CPU suite: host logic of vgpa_amd (no GPU compute) and the C-ABI library surface."""
+import ctypes
 import os
 import re
 import json
@@ -45,6 +46,8 @@ def test_python_constants_agree_with_the_header():
     body = re.search(r"typedef struct \{([^}]*)\} vgpa_path;", header).group(1)
     fields = [f.strip() for decl in re.findall(r"int32_t\s+([^;]+);", body) for f in decl.split(",")]
     assert fields == [name for name, _ in _lib.VgpaPath._fields_]
+    assert len(_lib.VgpaPath._fields_) == len(fields) and ctypes.sizeof(_lib.VgpaPath) == 4 * len(fields)      # as many members as the header's struct
+    assert fields[-1] == "helper_roles"            # (the struct grows at its end only)
     assert len(re.findall(r";", re.sub(r"/\*.*?\*/", "", body, flags=re.S))) == len(re.findall(r"int32_t\s+[^;]+;", body))
 
 

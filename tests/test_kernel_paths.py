@@ -19,7 +19,7 @@ from vgpa_amd._lib import FLAG_FORCE_GENERIC, FLAG_KEEP_PSI, FLAG_MATERIALIZE, F
 from conftest import rel_err
 from helpers import block_rel_errs
 from oracle import vgpa_oracle as vo
-from test_gpu_edge_cases import fused_grad_switch, gpu_context, make_problem
+from test_gpu_edge_cases import fused_grad_switch, gpu_context, helper_switch, make_problem
 from test_theta_gradient_cpu import fd_theta_gradient
 
 pytestmark = pytest.mark.gpu
@@ -28,9 +28,10 @@ TOL = 1e-9
 
 # ---- the plan table ---------------------------------------------------------------------------------------------------------
 
-def expected_plan(model, d, method, batch, flags=0, sigma="iso", n_cu=256, n_pts=4, ode_kernel=None, fused_grad="", sym_s0=True):
+def expected_plan(model, d, method, batch, flags=0, sigma="iso", n_cu=256, n_pts=4, ode_kernel=None, fused_grad="", sym_s0=True, helpers=None):
     """DESIGN.md s.4.0, row by row, written from the table and not from make_plan.  sigma: "iso", "diag", "dense" (symmetric) or
-    "nonsym"; ode_kernel: VGPA_ODE_KERNEL; fused_grad: the first character of VGPA_FUSED_GRAD."""
+    "nonsym"; ode_kernel: VGPA_ODE_KERNEL; fused_grad: the first character of VGPA_FUSED_GRAD; helpers: VGPA_SYM_HELPERS ("0", "1", "2") or
+    None when it is not set."""
     sym_inputs = sigma != "nonsym" and sym_s0
     len_x = n_pts * d * (d + 1)
 
@@ -51,7 +52,11 @@ def expected_plan(model, d, method, batch, flags=0, sigma="iso", n_cu=256, n_pts
     store_q = bwd_upper and sigma == "iso" and model == "L96" and method in ("rk2", "rk4") and 33 <= d <= 40
     packed = store_q and fwd == "mfma"
     grad_in_bwd = packed and method == "rk4" and fused_grad != "0"
-    return dict(fwd=fwd, bwd=bwd, sym_units=sym_units, launch_sym_units=sym_units or ode_kernel == "sym", lane_pass=lane_pass,
+    launch_sym_units = sym_units or ode_kernel == "sym"
+    helper_roles = 0
+    if launch_sym_units and 33 <= d <= 40:
+        helper_roles = (2 if batch <= n_cu else 0) if helpers is None else {"0": 0, "1": 1, "2": 2}[helpers]
+    return dict(fwd=fwd, bwd=bwd, sym_units=sym_units, launch_sym_units=launch_sym_units, helper_roles=helper_roles, lane_pass=lane_pass,
                 bwd_upper=bwd_upper, store_q=store_q, packed=packed, grad_in_bwd=grad_in_bwd,
                 grad_in_bwd_now=grad_in_bwd and (batch >= 64 or fused_grad == "1"))
 
@@ -109,7 +114,7 @@ def test_plan_table():
     for row in rows:
         model, d, method, batch, flags, form = row
         ctx = plan_context(*row)
-        got, want = ctx.plan(), expected_plan(model, d, method, batch, flags, form, n_cu, fused_grad=fused_grad_switch())
+        got, want = ctx.plan(), expected_plan(model, d, method, batch, flags, form, n_cu, fused_grad=fused_grad_switch(), helpers=helper_switch())
         res = ctx.resident()
         ctx.close()
         assert got == want, (row, {k: (got[k], want[k]) for k in want if got[k] != want[k]})
@@ -129,7 +134,7 @@ def test_plan_under_the_stepper_family_switch(family, monkeypatch):
                 ctx = plan_context("L96", d, "rk4", batch, flags)
                 got = ctx.plan()
                 ctx.close()
-                want = expected_plan("L96", d, "rk4", batch, flags, "iso", n_cu, ode_kernel=family, fused_grad=fused_grad_switch())
+                want = expected_plan("L96", d, "rk4", batch, flags, "iso", n_cu, ode_kernel=family, fused_grad=fused_grad_switch(), helpers=helper_switch())
                 assert got == want, (d, batch, flags, {k: (got[k], want[k]) for k in want if got[k] != want[k]})
     if family == "pe":                 # what the switch is for
         ctx = plan_context("L96", 36, "rk4", 1)
@@ -159,9 +164,36 @@ def test_plan_under_the_fused_gradient_switch():
         assert r.returncode == 0, r.stderr[-2000:]
         plans = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("[")][-1])
         for (d, m, b, fl, form), got in zip(rows, plans):
-            want = expected_plan("L96", d, m, b, fl, form, n_cu, fused_grad=value)
+            want = expected_plan("L96", d, m, b, fl, form, n_cu, fused_grad=value, helpers=helper_switch())
             assert got == want, (value, d, m, b, fl, form, {k: (got[k], want[k]) for k in want if got[k] != want[k]})
         assert any(p["grad_in_bwd_now"] for p in plans) == (value == "1")
+
+
+def test_plan_under_the_helper_switch():
+    """VGPA_SYM_HELPERS (read at vgpa_create: one child process per value): 0 / 1 / 2 give the fragment-cover steppers that many helper
+    roles at every batch size -- at 33 <= D <= 40, and nowhere else; nothing else of the plan moves.  D on both sides of 32 | 33 and
+    40 | 41, batches on both sides of the CU count.  Contexts only: no kernel runs."""
+    n_cu = _n_cu()
+    rows = [(d, b) for d in (32, 33, 40, 41) for b in (1, n_cu, n_cu + 1)]
+    code = ("import sys, json\n"
+            "sys.path.insert(0, %r)\n"
+            "import test_kernel_paths as t\n"
+            "out = []\n"
+            "for d, b in %r:\n"
+            "    ctx = t.plan_context('L96', d, 'rk4', b)\n"
+            "    out.append(ctx.plan())\n"
+            "    ctx.close()\n"
+            "print(json.dumps(out))\n" % (os.path.dirname(__file__), rows))
+    for value in ("0", "1", "2"):
+        env = dict(os.environ)
+        env["VGPA_SYM_HELPERS"] = value
+        r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        plans = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("[")][-1])
+        for (d, b), got in zip(rows, plans):
+            want = expected_plan("L96", d, "rk4", b, 0, "iso", n_cu, fused_grad=fused_grad_switch(), helpers=value)
+            assert got == want, (value, d, b, {k: (got[k], want[k]) for k in want if got[k] != want[k]})
+            assert got["helper_roles"] == (int(value) if d in (33, 40) else 0), (value, d, b)
 
 
 def test_plan_follows_the_per_problem_inputs():
@@ -171,7 +203,7 @@ def test_plan_follows_the_per_problem_inputs():
     n_cu, d, batch = _n_cu(), 40, 67
     fused = fused_grad_switch()
     ctx = plan_context("L96", d, "rk4", batch)
-    iso, diag = (expected_plan("L96", d, "rk4", batch, 0, form, n_cu, fused_grad=fused) for form in ("iso", "diag"))
+    iso, diag = (expected_plan("L96", d, "rk4", batch, 0, form, n_cu, fused_grad=fused, helpers=helper_switch()) for form in ("iso", "diag"))
     assert iso["packed"] and not diag["packed"] and diag["bwd_upper"]
     assert ctx.plan() == iso
     own = np.stack([(3.0 + 0.01 * k) * np.eye(d) for k in range(batch)])
@@ -192,7 +224,7 @@ def test_plan_follows_the_per_problem_inputs():
     assert ctx.plan() == iso
     s0[3, 0, 1] += 0.01
     ctx.set_problem_data(s0=s0)
-    assert ctx.plan() == expected_plan("L96", d, "rk4", batch, 0, "iso", n_cu, fused_grad=fused, sym_s0=False)
+    assert ctx.plan() == expected_plan("L96", d, "rk4", batch, 0, "iso", n_cu, fused_grad=fused, sym_s0=False, helpers=helper_switch())
     assert ctx.plan()["fwd"] == "generic" and not ctx.plan()["packed"]
     ctx.set_problem_data()
     assert ctx.plan() == iso

@@ -84,7 +84,8 @@ class VgpaPath(ctypes.Structure):
     PLAN = ("fwd", "bwd", "sym_units", "launch_sym_units", "lane_pass", "bwd_upper", "store_q", "packed", "grad_in_bwd",
             "grad_in_bwd_now")
     RESIDENT = ("cached", "moments", "S", "dEs", "bwd_holds", "terms")
-    _fields_ = [(name, c_int32) for name in PLAN + RESIDENT]
+    PLAN_TAIL = ("helper_roles",)      # (the struct only ever grows at its end)
+    _fields_ = [(name, c_int32) for name in PLAN + RESIDENT + PLAN_TAIL]
 
 
 class VgpaConfig(ctypes.Structure):
@@ -669,9 +670,10 @@ class Context:
 
     def plan(self):
         """Which kernels this context's fused sweep runs (tests, diagnostics; read-only): the steppers `fwd` / `bwd` by name
-        ("large_d", "lane", "wave", "mfma", "generic"), every other field of the library's plan as a bool."""
+        ("large_d", "lane", "wave", "mfma", "generic"), `helper_roles` as its count, every other field of the library's plan as a bool."""
         v, names = self._path(), {i: k for k, i in STEPPER_IDS.items()}
-        return {k: names[getattr(v, k)] if k in ("fwd", "bwd") else bool(getattr(v, k)) for k in VgpaPath.PLAN}
+        plan = {k: names[getattr(v, k)] if k in ("fwd", "bwd") else bool(getattr(v, k)) for k in VgpaPath.PLAN}
+        return dict(plan, helper_roles=int(v.helper_roles))
 
     def resident(self):
         """What the device buffers hold right now (tests, diagnostics; read-only): `cached` and `terms` as bools, `moments`

@@ -19,12 +19,12 @@ bool ode_mfma_supported(int method, bool, int D) {
 bool sym_stores_q(int method, int D) { return sym::stores_q(method, D); }
 bool sym_fuses_grad(int method, int D) { return sym::fuses_grad(method, D); }
 
-hipError_t launch_ode_mfma(int method, bool fwd, const OdeArgs& a, hipStream_t st) {
+hipError_t launch_ode_mfma(int method, bool fwd, const OdeArgs& a, int helper_roles, hipStream_t st) {
   switch (method) {
-    case VGPA_ODE_EULER: return mfma_method_launch<VGPA_ODE_EULER>(fwd, a, st);
-    case VGPA_ODE_HEUN: return mfma_method_launch<VGPA_ODE_HEUN>(fwd, a, st);
-    case VGPA_ODE_RK2: return mfma_method_launch<VGPA_ODE_RK2>(fwd, a, st);
-    case VGPA_ODE_RK4: return mfma_method_launch<VGPA_ODE_RK4>(fwd, a, st);
+    case VGPA_ODE_EULER: return mfma_method_launch<VGPA_ODE_EULER>(fwd, a, helper_roles, st);
+    case VGPA_ODE_HEUN: return mfma_method_launch<VGPA_ODE_HEUN>(fwd, a, helper_roles, st);
+    case VGPA_ODE_RK2: return mfma_method_launch<VGPA_ODE_RK2>(fwd, a, helper_roles, st);
+    case VGPA_ODE_RK4: return mfma_method_launch<VGPA_ODE_RK4>(fwd, a, helper_roles, st);
   }
   return hipErrorInvalidValue;
 }

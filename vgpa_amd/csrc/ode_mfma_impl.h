@@ -30,18 +30,17 @@
 // + vectors + the constant matrix jump 13 KB: 82 KB.
 #pragma once
 #include "vgpa_internal.h"
-#include <cstdlib>
 
 namespace vgpa {
 namespace sym {
 // the backward kernels that can store Q''_t = Sigma^-1 A_t - 2 Psi_t instead of Psi_t (OdeArgs::q_on): the fragment-cover
 // kernels (ode_sym_impl.h, 33 <= D <= 40) of the mid-point methods with sparse jumps
-inline bool stores_q(int method, int D) {
+constexpr bool stores_q(int method, int D) {
   return (method == VGPA_ODE_RK2 || method == VGPA_ODE_RK4) && D >= 33 && D <= 40;
 }
 // the backward kernel that assembles the gradient on its helper waves (OdeArgs::grad_on; k_ode_sym, GF): the fragment-cover kernels
-// of RK4
-inline bool fuses_grad(int method, int D) { return method == VGPA_ODE_RK4 && stores_q(method, D); }
+// of RK4.  (ode_sym_impl.h asserts that both say what sym_variant_exists, the statement of the kernels that are built, says.)
+constexpr bool fuses_grad(int method, int D) { return method == VGPA_ODE_RK4 && stores_q(method, D); }
 }  // namespace sym
 }  // namespace vgpa
 
@@ -822,23 +821,34 @@ __global__ void __launch_bounds__(64 * kNPW + kNE) k_ode_pe(OdeArgs a) {
   else e_role<METHOD, FWD, NB, DENSEJ, PJ>(a, prob, L, SIG, tid - 64 * kNPW);
 }
 
-template <int METHOD, bool FWD, int NB>
-hipError_t launch_nb(const OdeArgs& a, hipStream_t st) {
+// The one place that spells k_ode_pe out.
+template <int METHOD, bool FWD, int NB, bool DENSEJ, bool PJ>
+hipError_t launch_pe(const OdeArgs& a, hipStream_t st) {
+  static_assert(!FWD || (!DENSEJ && !PJ), "dense jumps and the per-problem constant jump belong to the backward kernels");
+  static_assert(!(DENSEJ && PJ), "the per-problem constant jump belongs to the kernels with sparse jumps");
   constexpr size_t lds = Geo<NB>::LDS_DOUBLES * sizeof(double);
   static_assert(lds <= 160 * 1024, "LDS budget");
-  const bool dense = !FWD && a.js_dense;
-  constexpr bool PJ = !FWD;                           // (the per-problem constant jump belongs to the backward kernels with sparse jumps)
-  auto kern = dense ? k_ode_pe<METHOD, FWD, NB, true> : (!FWD && a.js_const_stride) ? k_ode_pe<METHOD, FWD, NB, false, PJ> : k_ode_pe<METHOD, FWD, NB, false>;
+  auto kern = k_ode_pe<METHOD, FWD, NB, DENSEJ, PJ>;
   if (lds > 48 * 1024)
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL(kern, dim3(a.batch), dim3(64 * kNPW + kNE), lds, st, a);
   return hipGetLastError();
 }
 
+template <int METHOD, bool FWD, int NB>
+hipError_t launch_nb(const OdeArgs& a, hipStream_t st) {
+  if (a.q_on || a.grad_on) return hipErrorInvalidValue;       // (this family stores Psi_t and leaves the gradient to the assembly kernels)
+  if constexpr (!FWD) {
+    if (a.js_dense) return launch_pe<METHOD, FWD, NB, true, false>(a, st);
+    if (a.js_const_stride) return launch_pe<METHOD, FWD, NB, false, true>(a, st);
+  }
+  return launch_pe<METHOD, FWD, NB, false, false>(a, st);
+}
+
 }  // namespace mfma
 
-// One instantiation set per stepper (defined in ode_mfma_m<METHOD>.hip).
+// One instantiation set per stepper (defined in ode_sym_impl.h, instantiated in ode_mfma_m<METHOD>.hip).
 template <int METHOD> bool mfma_method_supported(int nb);
-template <int METHOD> hipError_t mfma_method_launch(bool fwd, const OdeArgs& a, hipStream_t st);
+template <int METHOD> hipError_t mfma_method_launch(bool fwd, const OdeArgs& a, int helper_roles, hipStream_t st);
 
 }  // namespace vgpa

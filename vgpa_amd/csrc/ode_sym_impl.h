@@ -32,9 +32,8 @@
 // Measurements, what was tried and what bounds the kernel: DESIGN.md s.4.1, s.7, EXPERIMENTS.md s.2, s.9, s.11; micro-benchmark tools/ubench/sym_product.hip.
 #pragma once
 #include <type_traits>
+#include <utility>
 #include "ode_mfma_impl.h"
-#include <cstdlib>
-#include <cstring>
 
 namespace vgpa {
 namespace sym {
@@ -1440,107 +1439,127 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3
 }
 
 
-// Helper-wave kernels: one helper role (512 threads) or two (768; VGPA_SYM_HELPERS=2 in the environment forces two, =1 one)
-inline bool two_helper_roles() {
-  static const int forced = [] { const char* e = getenv("VGPA_SYM_HELPERS"); return e ? atoi(e) : -1; }();
-  return forced < 0 || forced == 2;
-}
-template <int METHOD, bool FWD, int NB, bool HLP = false>
-hipError_t launch_cover(const OdeArgs& a, hipStream_t st, bool dense) {
-  constexpr size_t lds_c = SGeo<NB>::LDS_DOUBLES * sizeof(double);
-  constexpr int WPE_C = (HLP || 2 * lds_c <= 160 * 1024) ? 2 : 1;
-  constexpr int threads = HLP ? 512 : 256;
-  constexpr bool PJ = !FWD;                            // (the per-problem constant jump belongs to the backward kernels with sparse jumps)
-  const bool pj = !FWD && a.js_const_stride != 0;     // OdeArgs::js_const_stride: the kernels' PJ instantiations
-  if constexpr (!FWD && METHOD == VGPA_ODE_RK4 && HLP) {
-    if (a.grad_on) {                                   // the gradient assembly on the helper waves (k_ode_sym, GF)
-      if (dense || !a.q_on || !a.s_packed || !a.g || !a.S || !a.m || !a.Ef || !a.Am || !a.b) return hipErrorInvalidValue;
-      constexpr size_t lds_g = lds_c + GradLds<NB>::DOUBLES * sizeof(double);
-      static_assert(lds_g <= 160 * 1024, "LDS budget");
-      auto kg = pj ? k_ode_sym<METHOD, FWD, NB, false, 0, 3, true, true, true, false, PJ> : k_ode_sym<METHOD, FWD, NB, false, 0, 3, true, true, true>;      // 768 threads: three waves per SIMD, 168 registers each
-      (void)hipFuncSetAttribute((const void*)kg, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_g);
-      hipLaunchKernelGGL(kg, dim3(a.batch), dim3(768), lds_g, st, a);
-      return hipGetLastError();
-    }
-  }
-  if (a.grad_on) return hipErrorInvalidValue;          // (only the kernel above assembles the gradient)
-  if constexpr (HLP) {                                 // two helper roles (k_ode_sym, H2): 768 threads, three waves per SIMD
-    if (two_helper_roles()) {
-      if constexpr (!FWD && (METHOD == VGPA_ODE_RK2 || METHOD == VGPA_ODE_RK4)) {
-        if (a.q_on) {
-          if (dense) return hipErrorInvalidValue;
-          auto kq2 = pj ? k_ode_sym<METHOD, FWD, NB, false, 0, 3, true, true, false, true, PJ> : k_ode_sym<METHOD, FWD, NB, false, 0, 3, true, true, false, true>;
-          (void)hipFuncSetAttribute((const void*)kq2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c);
-          hipLaunchKernelGGL(kq2, dim3(a.batch), dim3(768), lds_c, st, a);
-          return hipGetLastError();
-        }
-      }
-      auto kc2 = dense ? k_ode_sym<METHOD, FWD, NB, true, 0, 3, false, true, false, true> : pj ? k_ode_sym<METHOD, FWD, NB, false, 0, 3, false, true, false, true, PJ> : k_ode_sym<METHOD, FWD, NB, false, 0, 3, false, true, false, true>;
-      (void)hipFuncSetAttribute((const void*)kc2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c);
-      hipLaunchKernelGGL(kc2, dim3(a.batch), dim3(768), lds_c, st, a);
-      return hipGetLastError();
-    }
-  }
-  if constexpr (!FWD && (METHOD == VGPA_ODE_RK2 || METHOD == VGPA_ODE_RK4)) {
-    if (a.q_on) {
-      if (dense) return hipErrorInvalidValue;          // (the fused sweeps bring sparse jumps)
-      auto kq = pj ? k_ode_sym<METHOD, FWD, NB, false, 0, WPE_C, true, HLP, false, false, PJ> : k_ode_sym<METHOD, FWD, NB, false, 0, WPE_C, true, HLP>;
-      if (lds_c > 48 * 1024)
-        (void)hipFuncSetAttribute((const void*)kq, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c);
-      hipLaunchKernelGGL(kq, dim3(a.batch), dim3(threads), lds_c, st, a);
-      return hipGetLastError();
-    }
-  }
-  auto kc = dense ? k_ode_sym<METHOD, FWD, NB, true, 0, WPE_C, false, HLP> : pj ? k_ode_sym<METHOD, FWD, NB, false, 0, WPE_C, false, HLP, false, false, PJ> : k_ode_sym<METHOD, FWD, NB, false, 0, WPE_C, false, HLP>;
-  if (lds_c > 48 * 1024)
-    (void)hipFuncSetAttribute((const void*)kc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c);
-  hipLaunchKernelGGL(kc, dim3(a.batch), dim3(threads), lds_c, st, a);
-  return hipGetLastError();
-}
-
-// Helper waves (k_ode_sym, HLP): up to one problem per CU.  VGPA_SYM_HELPERS=0 / 1 in the environment forces them off / on for
-// every batch size (comparison runs, tests).
-inline bool helper_waves(int batch) {
-  static const int forced = [] { const char* e = getenv("VGPA_SYM_HELPERS"); return e ? atoi(e) : -1; }();
-  if (forced >= 0) return forced != 0;
-  static const int n_cu = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 256;
-    return n;
-  }();
-  return batch <= n_cu;
-}
+// ---- which k_ode_sym instantiations exist, and their launch ---------------------------------------------------------------------------
+// What the run-time arguments choose of k_ode_sym<METHOD, FWD, NB, ...>.  sym_variant_exists is the one statement of the combinations that
+// are built; sym_launch_shape derives a variant's launch geometry; launch_variant is the one place that spells the kernel out.
+struct SymVariant {
+  bool dense;        // dense jumps (OdeArgs::js_dense; DENSEJ)
+  bool q_out;        // stores Q''_t instead of Psi_t (OdeArgs::q_on; QOUT)
+  bool own_jump;     // per-problem constant matrix jump (OdeArgs::js_const_stride; PJ)
+  bool grad;         // the gradient waves (OdeArgs::grad_on; GF): a third set of four waves beside ONE helper role
+  int helper_roles;  // sets of helper waves beside the product waves: 0, 1 (HLP), 2 (HLP, H2)
+};
 
 template <int METHOD, bool FWD, int NB>
-hipError_t launch_sym(const OdeArgs& a, hipStream_t st) {
-  constexpr size_t lds = SGeo<NB>::LDS_DOUBLES * sizeof(double);
-  static_assert(lds <= 160 * 1024, "LDS budget");
-  const bool dense = !FWD && a.js_dense;
-  if constexpr (SGeo<NB>::NSB == 5) {                  // 33 <= D <= 40: the fragment cover
-    if (helper_waves(a.batch) || (!FWD && a.grad_on)) return launch_cover<METHOD, FWD, NB, true>(a, st, dense);
-    return launch_cover<METHOD, FWD, NB>(a, st, dense);
-  } else {
-    // the run layout, one run per pipeline step.  Two (four accumulators in turn, 16 MFMAs per step) spill with 256 registers
-    // and were slower with 512 (D = 64: 22.0 vs 15.7 ms forward).
-    constexpr int GR = 1;
-    if (a.grad_on) return hipErrorInvalidValue;
-    constexpr int WPE = 2 * lds <= 160 * 1024 ? 2 : 1;     // two workgroups per CU when their LDS fits, else all 512 registers
-    constexpr bool PJ = !FWD;                          // (as in launch_cover)
-    auto kern = dense ? k_ode_sym<METHOD, FWD, NB, true, GR, WPE> : (!FWD && a.js_const_stride) ? k_ode_sym<METHOD, FWD, NB, false, GR, WPE, false, false, false, false, PJ> : k_ode_sym<METHOD, FWD, NB, false, GR, WPE>;
-    if (lds > 48 * 1024)
-      (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kern, dim3(a.batch), dim3(256), lds, st, a);
-    return hipGetLastError();
+constexpr bool sym_variant_exists(SymVariant v) {
+  constexpr bool cover = SGeo<NB>::NSB == 5;           // 33 <= D <= 40: the fragment cover
+  constexpr bool midpoint = METHOD == VGPA_ODE_RK2 || METHOD == VGPA_ODE_RK4;
+  if (FWD && (v.dense || v.q_out || v.own_jump || v.grad)) return false;      // all four belong to the backward kernels
+  if (v.dense && (v.q_out || v.own_jump || v.grad)) return false;             // (the fused sweeps bring sparse jumps)
+  if (v.q_out && !(midpoint && cover)) return false;
+  if (v.grad && !(METHOD == VGPA_ODE_RK4 && v.q_out && v.helper_roles == 1)) return false;
+  return v.helper_roles == 0 || (cover && (v.helper_roles == 1 || v.helper_roles == 2));
+}
+
+// The rules above, checked against themselves and against what the plan asks (stores_q, fuses_grad) for every stepper and every NB.
+template <int METHOD, int NB>
+constexpr bool sym_variant_rules_hold() {
+  constexpr bool cover = SGeo<NB>::NSB == 5, midpoint = METHOD == VGPA_ODE_RK2 || METHOD == VGPA_ODE_RK4;
+  for (int bits = 0; bits < 16; bits++)
+    for (int roles = 0; roles <= 2; roles++) {
+      const SymVariant v{(bits & 1) != 0, (bits & 2) != 0, (bits & 4) != 0, (bits & 8) != 0, roles};
+      if (sym_variant_exists<METHOD, true, NB>(v) && (v.dense || v.q_out || v.own_jump || v.grad)) return false;
+      if (!sym_variant_exists<METHOD, false, NB>(v)) continue;
+      if (v.grad && !v.q_out) return false;
+      if (v.q_out && !(midpoint && cover)) return false;
+      if (roles > 0 && !cover) return false;
+    }
+  for (int D = 4 * NB - 3; D <= 4 * NB; D++) {
+    if (stores_q(METHOD, D) != sym_variant_exists<METHOD, false, NB>(SymVariant{false, true, false, false, 0})) return false;
+    if (fuses_grad(METHOD, D) != sym_variant_exists<METHOD, false, NB>(SymVariant{false, true, false, true, 1})) return false;
   }
+  return true;
+}
+template <int... I>
+constexpr bool sym_variant_rules_hold_everywhere(std::integer_sequence<int, I...>) {
+  return (... && sym_variant_rules_hold<I / kMaxNB, I % kMaxNB + 1>());
+}
+static_assert(sym_variant_rules_hold_everywhere(std::make_integer_sequence<int, 4 * kMaxNB>{}),
+              "k_ode_sym variants: forward kernels take no backward option, grad => q_out, q_out => RK2 / RK4 on the cover, helper roles => "
+              "the cover, and stores_q / fuses_grad say the same");
+
+struct SymLaunchShape { int threads, gr, wpe; size_t lds; };
+template <int NB>
+constexpr SymLaunchShape sym_launch_shape(SymVariant v) {
+  const int sets = 1 + v.helper_roles + (v.grad ? 1 : 0);       // sets of four waves: product, helper role(s), gradient -- 256 / 512 / 768 threads
+  const size_t lds = (SGeo<NB>::LDS_DOUBLES + (v.grad ? GradLds<NB>::DOUBLES : 0)) * sizeof(double);
+  // GR: the run layout, one run per pipeline step (two -- four accumulators in turn, 16 MFMAs per step -- spill with 256 registers and were
+  // slower with 512, D = 64: 22.0 vs 15.7 ms forward); 0: the fragment cover.  WPE: one wave per SIMD and set (768 threads: 168 registers
+  // each); a lone set: two workgroups per CU when their LDS fits, else all 512 registers
+  return {256 * sets, SGeo<NB>::NSB == 5 ? 0 : 1, sets > 1 ? sets : (2 * lds <= 160 * 1024 ? 2 : 1), lds};
+}
+
+template <int METHOD, bool FWD, int NB, bool DENSE, bool QOUT, bool PJ, bool GRAD, int ROLES>
+hipError_t launch_variant(const OdeArgs& a, hipStream_t st) {
+  constexpr SymVariant V{DENSE, QOUT, PJ, GRAD, ROLES};
+  if constexpr (sym_variant_exists<METHOD, FWD, NB>(V)) {
+    constexpr SymLaunchShape L = sym_launch_shape<NB>(V);
+    static_assert(L.lds <= 160 * 1024, "LDS budget");
+    auto kern = k_ode_sym<METHOD, FWD, NB, DENSE, L.gr, L.wpe, QOUT, (ROLES > 0), GRAD, (ROLES == 2), PJ>;
+    if (L.lds > 48 * 1024)
+      (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds);
+    hipLaunchKernelGGL(kern, dim3(a.batch), dim3(L.threads), L.lds, st, a);
+    return hipGetLastError();
+  } else {
+    return hipErrorInvalidValue;
+  }
+}
+
+// a run-time flag as a compile-time one: f(std::true_type) or f(std::false_type)
+template <class F>
+hipError_t with_flag(bool on, F f) { return on ? f(std::true_type{}) : f(std::false_type{}); }
+
+// helper_roles: Plan::helper_roles (vgpa_api.hip).  The gradient-wave kernel has its one helper role whatever the count says.
+template <int METHOD, bool FWD, int NB>
+hipError_t launch_sym(const OdeArgs& a, int helper_roles, hipStream_t st) {
+  const bool dense = !FWD && a.js_dense;               // (the per-problem constant jump belongs to the backward kernels with sparse jumps)
+  const SymVariant v{dense, a.q_on != 0, !FWD && !dense && a.js_const_stride != 0, a.grad_on != 0, a.grad_on ? 1 : helper_roles};
+  if (!sym_variant_exists<METHOD, FWD, NB>(v)) return hipErrorInvalidValue;      // (q_on / grad_on asked of a kernel without them included)
+  if (v.grad && (!a.s_packed || !a.g || !a.S || !a.m || !a.Ef || !a.Am || !a.b)) return hipErrorInvalidValue;
+  return with_flag(v.dense, [&](auto dj) { return with_flag(v.q_out, [&](auto qo) { return with_flag(v.own_jump, [&](auto pj) {
+    return with_flag(v.grad, [&](auto gf) {
+      constexpr bool DJ = decltype(dj)::value, QO = decltype(qo)::value, PJ = decltype(pj)::value, GF = decltype(gf)::value;
+      switch (v.helper_roles) {
+        case 1: return launch_variant<METHOD, FWD, NB, DJ, QO, PJ, GF, 1>(a, st);
+        case 2: return launch_variant<METHOD, FWD, NB, DJ, QO, PJ, GF, 2>(a, st);
+        default: return launch_variant<METHOD, FWD, NB, DJ, QO, PJ, GF, 0>(a, st);
+      }
+    }); }); }); });
 }
 
 // D <= 44 has both kernel families: the role-specialised 8-wave kernels of ode_mfma_impl.h (faster for one problem per CU and for a
 // single problem) and the symmetric-unit kernels (faster from two problems per CU on).  The caller says which: OdeArgs::sym_units.
 template <int METHOD, bool FWD, int NB>
-hipError_t launch_any(const OdeArgs& a, hipStream_t st) {
-  if (a.sym_units) return launch_sym<METHOD, FWD, NB>(a, st);
-  return mfma::launch_nb<METHOD, FWD, NB>(a, st);
+hipError_t launch_any(const OdeArgs& a, int helper_roles, hipStream_t st) {
+  if constexpr (NB <= mfma::kMaxNB) {
+    if (!a.sym_units) return mfma::launch_nb<METHOD, FWD, NB>(a, st);
+  }
+  return launch_sym<METHOD, FWD, NB>(a, helper_roles, st);
 }
 
 }  // namespace sym
+
+// One instantiation set per stepper: ode_mfma_m<METHOD>.hip instantiates these two, so that the steppers compile in parallel.
+template <int METHOD> bool mfma_method_supported(int nb) { return nb >= 1 && nb <= sym::kMaxNB; }
+template <int METHOD> hipError_t mfma_method_launch(bool fwd, const OdeArgs& a, int helper_roles, hipStream_t st) {
+  switch ((a.D + 3) / 4) {
+#define VGPA_NB_CASE(NB) \
+  case NB: return fwd ? sym::launch_any<METHOD, true, NB>(a, helper_roles, st) : sym::launch_any<METHOD, false, NB>(a, helper_roles, st);
+    VGPA_NB_CASE(1) VGPA_NB_CASE(2) VGPA_NB_CASE(3) VGPA_NB_CASE(4) VGPA_NB_CASE(5) VGPA_NB_CASE(6) VGPA_NB_CASE(7) VGPA_NB_CASE(8)
+    VGPA_NB_CASE(9) VGPA_NB_CASE(10) VGPA_NB_CASE(11) VGPA_NB_CASE(12) VGPA_NB_CASE(13) VGPA_NB_CASE(14) VGPA_NB_CASE(15) VGPA_NB_CASE(16)
+#undef VGPA_NB_CASE
+    default: return hipErrorNotSupported;
+  }
+}
+
 }  // namespace vgpa

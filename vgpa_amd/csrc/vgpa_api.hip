@@ -43,6 +43,10 @@ struct Plan {
   bool sigma_diag = true, isg_iso = false, sym_inputs = true;   // the inputs in force: Sigma diagonal, sigma^2 I; every s0 / Sigma / constant jump symmetric
   bool sym_units = false;       // matrix-core family: symmetric-unit kernels, not the role-specialised ones; heads the layout chain below
   bool launch_sym_units = false;   // what launch_ode_mfma is told (OdeArgs::sym_units): sym_units, or VGPA_ODE_KERNEL=sym, which leaves the layouts alone
+  // ... and the sets of helper waves it is told to put beside the product waves of the fragment-cover steppers (k_ode_sym, HLP / H2): 0, 1 or
+  // 2; 0 wherever launch_ode_mfma's steppers are not those.  (The backward kernel with the gradient waves keeps its fixed 768-thread shape
+  // -- one helper role and the gradient waves -- whatever the count says.)
+  int helper_roles = 0;
   Stepper fwd = Stepper::Generic, bwd = Stepper::Generic;
   bool lane_pass = false;      // the objective is the fused lane pass (enqueue_lane_sweep)
   // the layout chain of the fragment-cover kernels, each step implying the one before:
@@ -86,6 +90,7 @@ struct vgpa_ctx {
   bool single = false, full = false;
   Plan plan;                          // which kernels run and in which layouts (make_plan)
   int n_cu = 256; bool keep_pe = false, force_sym = false;   // make_plan's inputs read once, in vgpa_create: the CU count, VGPA_ODE_KERNEL=pe / =sym
+  int forced_helpers = -1;                                   // ... and VGPA_SYM_HELPERS (-1: not set)
   Resident res;                       // what the device buffers hold right now
   hipStream_t stream = nullptr;
   hipStream_t stream2 = nullptr;      // side stream of the D > 64 energy terms (lde_energy's look-ahead), created on first use
@@ -404,7 +409,8 @@ static Stepper stepper(const vgpa_ctx* c, bool fwd, bool sym) {
 constexpr int kFusedGradMinBatch = 64;
 static char fused_grad_switch() { static const char v = [] { const char* e = getenv("VGPA_FUSED_GRAD"); return e ? e[0] : '\0'; }(); return v; }
 
-// The one place that decides a context's kernels (Plan).  Reads cfg, D, B, len_x, full, n_cu, keep_pe, force_sym and the forms of the inputs.
+// The one place that decides a context's kernels (Plan).  Reads cfg, D, B, len_x, full, n_cu, keep_pe, force_sym, forced_helpers and the forms
+// of the inputs.
 static void make_plan(vgpa_ctx* c) {
   Plan p;
   // the form of the shared Sigma or of the per-problem rows (isotropic: every row sigma_p^2 I with its own sigma_p); symmetric: every
@@ -425,6 +431,10 @@ static void make_plan(vgpa_ctx* c) {
   p.sym_units = (c->cfg.flags & VGPA_FLAG_SYM_UNITS) != 0 || (c->B > c->n_cu && nb <= 10) || ((nb == 9 || nb == 10) && !c->keep_pe) ||
                 (nb >= 12 && c->D <= kMaxSmallD);
   p.launch_sym_units = p.sym_units || c->force_sym;   // (VGPA_ODE_KERNEL=sym: that family at D <= 44 too, in the layouts sym_units itself implies below)
+  // Helper waves beside the cover kernels' product waves: two roles up to one problem per CU (a workgroup has the CU to itself), none
+  // beyond; VGPA_SYM_HELPERS=0 / 1 / 2 in the environment forces none / one role / two roles at every batch size (comparison runs, tests)
+  if (p.launch_sym_units && (nb == 9 || nb == 10))
+    p.helper_roles = c->forced_helpers < 0 ? (c->B <= c->n_cu ? 2 : 0) : c->forced_helpers == 0 ? 0 : c->forced_helpers == 2 ? 2 : 1;
   p.fwd = stepper(c, true, p.sym_inputs);
   p.bwd = stepper(c, false, p.sym_inputs);
   // the fused lane pass (ode_small.hip::k_sweep_lane): forward kernel -> observations -> ONE kernel for the E_sde terms, the backward
@@ -448,11 +458,13 @@ static void make_plan(vgpa_ctx* c) {
 }
 
 // the small-D steppers share OdeArgs (the large-D drivers take their arrays one by one, each with its stride: run_fwd / run_bwd call them)
-static hipError_t launch_stepper(Stepper k, int method, bool fwd, const OdeArgs& a, hipStream_t st) {
+static hipError_t launch_stepper(const vgpa_ctx* c, Stepper k, bool fwd, const OdeArgs& a) {
+  const int method = c->cfg.method;
+  hipStream_t st = c->stream;
   switch (k) {
     case Stepper::Lane: return launch_ode_small(method, fwd, a, st);
     case Stepper::Wave: return launch_ode_wave(method, fwd, a, st);
-    case Stepper::Mfma: return launch_ode_mfma(method, fwd, a, st);
+    case Stepper::Mfma: return launch_ode_mfma(method, fwd, a, c->plan.helper_roles, st);
     case Stepper::Generic: return launch_ode_generic(method, fwd, a, st);
     case Stepper::LargeD: break;
   }
@@ -512,7 +524,7 @@ static int run_fwd(vgpa_ctx* c, Rows<double> m0, Rows<double> S0, Rows<double> S
   }
   OdeArgs a = fwd_args(c, m0, S0, Sigma);
   a.s_packed = c->res.S == Resident::SLayout::Packed ? 1 : 0;
-  LAUNCH_TRY(c, "forward sweep launch", launch_stepper(k, c->cfg.method, true, a, c->stream));
+  LAUNCH_TRY(c, "forward sweep launch", launch_stepper(c, k, true, a));
   return VGPA_OK;
 }
 
@@ -566,7 +578,7 @@ static int run_bwd(vgpa_ctx* c, bool dense_jumps, bool sym, double* g_fused = nu
     a.Ef = c->d_Ef; a.Am = c->d_Am;
   }
   c->res.backward_stored(g_fused ? Resident::Bwd::None : q ? Resident::Bwd::Q : Resident::Bwd::Psi);   // (g_fused: nothing is stored in d_psi)
-  LAUNCH_TRY(c, "backward sweep launch", launch_stepper(k, c->cfg.method, false, a, c->stream));
+  LAUNCH_TRY(c, "backward sweep launch", launch_stepper(c, k, false, a));
   return VGPA_OK;
 }
 
@@ -970,6 +982,7 @@ int vgpa_create(vgpa_ctx** out, const vgpa_config* cfg) {
   HTRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   if (hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, cfg->device) != hipSuccess || c->n_cu <= 0) c->n_cu = 256;
   { const char* fam = getenv("VGPA_ODE_KERNEL"); c->keep_pe = fam && !strcmp(fam, "pe"); c->force_sym = fam && !strcmp(fam, "sym"); }
+  { const char* hlp = getenv("VGPA_SYM_HELPERS"); c->forced_helpers = hlp ? atoi(hlp) : -1; }
   // (phase events: no system-scope fence behind them -- nothing on the host reads device memory at a phase boundary; with the default
   //  flags five events cost a batched Ornstein-Uhlenbeck step 0.4 of its 1.4 ms)
   for (auto& e : c->ev) HTRY(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
@@ -1757,6 +1770,7 @@ int vgpa_path_info(vgpa_ctx* c, vgpa_path* out) {
   out->cached = r.cached; out->moments = (int32_t)r.moments;
   out->S = r.S == Resident::SLayout::Packed ? VGPA_LAYOUT_PACKED : VGPA_LAYOUT_WHOLE;
   out->dEs = (int32_t)r.dEs; out->bwd_holds = (int32_t)r.bwd; out->terms = r.terms;
+  out->helper_roles = p.helper_roles;
   return VGPA_OK;
 }
 

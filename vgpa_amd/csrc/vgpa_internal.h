@@ -234,7 +234,8 @@ hipError_t launch_ms_untranspose(int D, int Np, int batch, int bpad, const doubl
 hipError_t launch_obs_lane(const ObsArgs& a, const double* msT, int bpad, double* jmT, hipStream_t st);
 hipError_t launch_ode_wave(int method, bool fwd, const OdeArgs& a, hipStream_t st);      // 2 <= D <= kMaxLaneD, few problems
 bool ode_mfma_supported(int method, bool fwd, int D);
-hipError_t launch_ode_mfma(int method, bool fwd, const OdeArgs& a, hipStream_t st);
+// helper_roles: sets of helper waves of the fragment-cover kernels (the context's Plan::helper_roles; host-only, like OdeArgs::sym_units)
+hipError_t launch_ode_mfma(int method, bool fwd, const OdeArgs& a, int helper_roles, hipStream_t st);
 bool sym_stores_q(int method, int D);      // the backward kernel launch_ode_mfma picks for sym_units honours OdeArgs::q_on
 bool sym_fuses_grad(int method, int D);    // ... and OdeArgs::grad_on (the gradient assembly on its helper waves)
 // Psi_t = (diag(isg) A_t - Q''_t) / 2 in place (A: problem stride strideA, grid-point stride D*D)
