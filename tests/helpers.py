@@ -28,11 +28,17 @@ def make_model(name, dim_d=None, seed=SEED):
     return quiet(cls, *args, seed)
 
 
-def build_problem(name, method, tf, dt=0.01, dim_d=None, seed=SEED, device=0, flags=0):
-    """Same wiring as Simulation.setup/run (simulation.py:134-212) with vgpa_amd's classes."""
+def build_problem(name, method, tf, dt=0.01, dim_d=None, seed=SEED, device=0, flags=0, obs_at=None):
+    """Same wiring as Simulation.setup/run (simulation.py:134-212) with vgpa_amd's classes.  obs_at: explicit observation indices as
+    tools/gen_golden.py places them (the equidistant ones are drawn first, then replaced: the sample path at obs_at plus noise from a
+    generator of its own)."""
     model = make_model(name, dim_d, seed)
     model.make_trajectory(0.0, tf, dt)
     obs_t, obs_y, obs_noise = model.collect_obs(MODEL_SETUP[name][1], MODEL_SETUP[name][2], None)
+    if obs_at is not None:
+        obs_t = [int(t) for t in obs_at]
+        path = np.take(model.sample_path, obs_t, axis=0)
+        obs_y = path + np.sqrt(MODEL_SETUP[name][2]) * np.random.default_rng(seed).standard_normal(path.shape)
     single = model.single_dim
     if single:
         m0 = model.sample_path[0] + 0.1 * model.rng.standard_normal()
@@ -45,8 +51,14 @@ def build_problem(name, method, tf, dt=0.01, dim_d=None, seed=SEED, device=0, fl
     lik = va.GaussianLikelihood(obs_y, obs_t, obs_noise, None, single)
     kl0 = va.PriorKL0(mu0, tau0, single)
     vgp = va.VarGP(model, m0, s0, fwd, bwd, lik, kl0, obs_y, obs_t, device=device, flags=flags)
+    init = vgp.initialization
+    if obs_at is not None:          # as tools/gen_golden.py: the initial guess of the interior observations (an observed end repeats a spline knot)
+        keep = [k for k, t in enumerate(obs_t) if 0 < t < model.time_window.size - 1]
+        t_in, y_in = [obs_t[k] for k in keep], np.asarray(obs_y)[keep]
+        init = va.VarGP(model, m0, s0, fwd, bwd, va.GaussianLikelihood(y_in, t_in, obs_noise, None, single), kl0, y_in, t_in,
+                        device=device, flags=flags).initialization
     return dict(model=model, vgp=vgp, lik=lik, kl0=kl0, fwd=fwd, bwd=bwd, m0=m0, s0=s0, mu0=mu0, tau0=tau0,
-                obs_t=obs_t, obs_y=obs_y, obs_noise=obs_noise)
+                obs_t=obs_t, obs_y=obs_y, obs_noise=obs_noise, init=init)
 
 
 def problem_from_golden(z, flags=0):

@@ -98,13 +98,13 @@ def test_input_generators_reproduce_reference_streams(golden):
     """make_trajectory / collect_obs / m0 draw / initialization consume the seeded stream like the reference."""
     name = str(golden["model"])
     d = None if name in ("OU", "DW", "L63") else int(golden["m0"].size)
-    p = build_problem(name, str(golden["method"]), float(golden["tf"]), float(golden["dt"]), d)
+    p = build_problem(name, str(golden["method"]), float(golden["tf"]), float(golden["dt"]), d, obs_at=golden.get("obs_at"))
     assert np.array_equal(p["model"].time_window, golden["time_window"])
     assert rel_err(p["model"].sample_path, golden["sample_path"]) < 1e-14
     assert np.array_equal(np.asarray(p["obs_t"]), golden["obs_t"])
     assert rel_err(p["obs_y"], golden["obs_y"]) < 1e-14
     assert rel_err(p["m0"], golden["m0"]) < 1e-14
-    x0 = p["vgp"].initialization()
+    x0 = p["init"]()                            # (vgp.initialization; of a fixture with explicit observations: of its interior ones)
     assert x0.shape == golden["x0"].shape
     assert rel_err(x0, golden["x0"]) < 1e-13
     assert rel_err(p["kl0"](p["m0"], p["s0"]), golden["E0"]) < 1e-13

@@ -16,6 +16,8 @@ Only data is written: no reference source, bytecode or pickled reference
 objects ever leave this container.
 
 Usage:  PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden.py [--skip-full]
+        ... --patterns-only                                   only the PATTERN_CASES fixtures (tests/obs_patterns.py)
+        ... --obs-at TAG MODEL METHOD TF DIM_D PERTURB I,J,K   one fixture observed at the grid indices I,J,K
 """
 import io
 import os
@@ -56,8 +58,18 @@ from src.dynamics.double_well import DoubleWell               # noqa: E402
 from src.dynamics.ornstein_uhlenbeck import OrnsteinUhlenbeck  # noqa: E402
 
 
-def build(model_name, method, tf, dt=0.01, dim_d=None, perturb=0.0, seed=SEED):
-    """Replicates Simulation.setup/run wiring (simulation.py:134-212) up to VarGP."""
+def explicit_obs(model, obs_at, r_obs, seed=SEED):
+    """Observations at the given grid indices instead of collect_obs' equidistant ones: the sample path there plus N(0, r_obs)
+    noise from a generator of its own (tests/helpers.py:build_problem draws the same)."""
+    obs_t = [int(t) for t in obs_at]
+    assert obs_t == sorted(set(obs_t)) and 0 <= obs_t[0] and obs_t[-1] < model.time_window.size
+    path = np.take(model.sample_path, obs_t, axis=0)
+    return obs_t, path + np.sqrt(r_obs) * np.random.default_rng(seed).standard_normal(path.shape)
+
+
+def build(model_name, method, tf, dt=0.01, dim_d=None, perturb=0.0, seed=SEED, obs_at=None):
+    """Replicates Simulation.setup/run wiring (simulation.py:134-212) up to VarGP.  obs_at: explicit observation indices (the
+    equidistant ones are still drawn first, so the seeded stream and the noise matrix stay what they are without them)."""
     with contextlib.redirect_stdout(io.StringIO()):
         if model_name == "OU":
             model, n_obs, r_obs = OrnsteinUhlenbeck(0.8, 1.0, seed), 2, 0.04
@@ -72,6 +84,9 @@ def build(model_name, method, tf, dt=0.01, dim_d=None, perturb=0.0, seed=SEED):
             raise ValueError(model_name)
     model.make_trajectory(0.0, tf, dt)
     obs_t, obs_y, obs_noise = model.collect_obs(n_obs, r_obs, None)
+    if obs_at is not None:
+        obs_at = obs_at(model.time_window.size) if callable(obs_at) else obs_at       # (a pattern: indices as a function of Np)
+        obs_t, obs_y = explicit_obs(model, obs_at, r_obs, seed)
     single = model.single_dim
     if single:
         m0 = model.sample_path[0] + 0.1 * model.rng.standard_normal()
@@ -87,14 +102,21 @@ def build(model_name, method, tf, dt=0.01, dim_d=None, perturb=0.0, seed=SEED):
     lik = GaussianLikelihood(obs_y, obs_t, obs_noise, None, single)
     kl0 = PriorKL0(mu0, tau0, single)
     vgp = VarGP(model, m0, s0, fwd, bwd, lik, kl0, obs_y, obs_t)
-    x0 = vgp.initialization()
+    if obs_at is None:
+        x0 = vgp.initialization()
+    else:
+        # VarGP.initialization (variational.py:87-109) splines through the first grid point, the observations and the last grid point: an
+        # observation AT either end repeats a knot and scipy refuses it.  x0 is only an input: take it from the interior observations.
+        keep = [k for k, t in enumerate(obs_t) if 0 < t < model.time_window.size - 1]
+        t_in, y_in = [obs_t[k] for k in keep], np.asarray(obs_y)[keep]
+        x0 = VarGP(model, m0, s0, fwd, bwd, GaussianLikelihood(y_in, t_in, obs_noise, None, single), kl0, y_in, t_in).initialization()
     x = x0.copy()
     if perturb > 0.0:
         x = x0 + perturb * np.random.default_rng(0).standard_normal(x0.size)
     return dict(model=model, vgp=vgp, lik=lik, kl0=kl0, fwd=fwd, bwd=bwd, x0=x0, x=x,
                 m0=m0, s0=s0, mu0=mu0, tau0=tau0, obs_t=obs_t, obs_y=obs_y,
                 obs_noise=obs_noise, dt=dt, tf=tf, method=method, name=model_name,
-                n_obs=n_obs, r_obs=r_obs)
+                n_obs=n_obs, r_obs=r_obs, obs_at=obs_at)
 
 
 def evaluate(c):
@@ -120,8 +142,9 @@ def evaluate(c):
 
 def dump_case(tag, c, r):
     model = c["model"]
+    extra = {} if c.get("obs_at") is None else {"obs_at": np.asarray(c["obs_at"], dtype=np.int64)}     # (the explicit indices, as asked for)
     np.savez_compressed(
-        os.path.join(OUT, f"{tag}.npz"),
+        os.path.join(OUT, f"{tag}.npz"), **extra,
         # ---- inputs
         model=np.array(c["name"]), method=np.array(c["method"]), dt=np.array(c["dt"]),
         tf=np.array(c["tf"]), seed=np.array(SEED), n_obs=np.array(c["n_obs"]), r_obs=np.array(c["r_obs"]),
@@ -163,6 +186,31 @@ SHORT_CASES = [
     ("l96d40_rk4", "L96", "RK4", 0.25, 40, 0.0),
     ("l96d40_rk4_p", "L96", "RK4", 0.25, 40, 0.05),
 ]
+
+# Observation placements the equidistant collect_obs never produces (tests/obs_patterns.py names them): every grid point observed,
+# and the second half of the grid (observation counter n and grid index t_n far apart).  (tag, model, method, tf, dim_d, perturb, pattern)
+PATTERN_CASES = [
+    ("l63_rk4_every_p", "L63", "RK4", 0.12, None, 0.05, "every"),
+    ("l63_rk4_late_p", "L63", "RK4", 0.12, None, 0.05, "late"),
+    ("l96d12_rk4_every_p", "L96", "RK4", 0.12, 12, 0.05, "every"),
+    ("l96d12_rk4_late_p", "L96", "RK4", 0.12, 12, 0.05, "late"),
+]
+
+
+def dump_one(tag, name, method, tf, dd, pert, obs_at):
+    c = build(name, method, tf, dim_d=dd, perturb=pert, obs_at=obs_at)
+    r = evaluate(c)
+    dump_case(tag, c, r)
+    print(f"{tag:18s} Np={c['vgp'].dim_n:5d} D={c['vgp'].dim_d:3d} M={len(c['obs_t']):3d}  F={r['F']:.12e}  |g|={np.linalg.norm(r['grad']):.12e}")
+    return c, r
+
+
+def dump_pattern_cases():
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    from obs_patterns import patterns
+    for tag, name, method, tf, dd, pert, pattern in PATTERN_CASES:
+        dump_one(tag, name, method, tf, dd, pert, lambda n_pts, pattern=pattern: patterns(n_pts)[pattern])
+
 
 # Full-size anchors: (tag, model, method, tf, dim_d)
 FULL_CASES = [
@@ -231,7 +279,15 @@ def main():
     if "--host-terms-only" in sys.argv:
         dump_host_terms()
         return
+    if "--obs-at" in sys.argv:
+        tag, name, method, tf, dd, pert, idx = sys.argv[sys.argv.index("--obs-at") + 1:][:7]
+        dump_one(tag, name, method, float(tf), None if dd in ("0", "None") else int(dd), float(pert), [int(v) for v in idx.split(",")])
+        return
+    if "--patterns-only" in sys.argv:
+        dump_pattern_cases()
+        return
     dump_host_terms()
+    dump_pattern_cases()
     anchors = {}
     for tag, name, method, tf, dd, pert in SHORT_CASES:
         c = build(name, method, tf, dim_d=dd, perturb=pert)
