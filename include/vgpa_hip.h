@@ -148,7 +148,9 @@ typedef struct {
  *     any per-problem theta or Sigma in the time-chunked large-D sweep and the row-sharded drivers;
  *   - vgpa_theta_gradient in the time-chunked large-D sweep (and the row-sharded drivers have no such entry point);
  *   - a per-problem observation model (vgpa_set_problem_obs_model) at D > 64, in the time-chunked large-D sweep and in the
- *     row-sharded drivers: they share the observation count, R and H.
+ *     row-sharded drivers: they share the observation count, R and H;
+ *   - vgpa_sample_paths at D > 64 (the time-chunked large-D sweep included): the sampler keeps a block of paths of one problem
+ *     next to A_t in one workgroup, which is what D <= 64 allows.
  * The matrix-core stepping kernels cover D <= 64 with symmetric inputs; non-symmetric operator-level inputs run on the
  * generic LDS kernels (same results, ~15x slower at D = 40). */
 
@@ -195,6 +197,35 @@ int vgpa_fetch(vgpa_ctx* ctx, int which, double* out);
  * contexts; VGPA_ERR_UNSUPPORTED: the time-chunked large-D sweep; VGPA_ERR_NOT_PD: the evaluation that left the state failed with
  * it (an S_t of the named problem is not positive definite) -- nothing is written to out then. */
 int vgpa_theta_gradient(vgpa_ctx* ctx, double* out);
+
+/* Sample paths on the context's grid by Euler-Maruyama: n_paths independent paths of every problem, of the posterior process
+ * dx = (-A_t x + b_t) dt + Sigma^1/2 dW (VGPA_PATHS_POSTERIOR: what the moments m_t, S_t are the moments of) or of the model SDE
+ * dx = f_theta(x) dt + Sigma^1/2 dW (VGPA_PATHS_MODEL: what a data set is a noisy record of; the reference's
+ * StochasticProcess.make_trajectory, src/dynamics/stochastic_process.py, one path at a time).
+ *   x_k = x_{k-1} + dt drift_{k-1}(x_{k-1}) + R_p xi_k,   R_p = chol_lower(Sigma_p dt)   (1-D models: sqrt(sigma dt)),
+ * with the Sigma in force (per-problem rows of vgpa_set_problem_params honoured).  For a dense Sigma the LOWER factor is used on purpose:
+ * the reference's _noise_increments multiplies by scipy's upper factor, whose increments do not have covariance Sigma dt; for a diagonal
+ * Sigma the two coincide.
+ *   out        host, [batch][n_paths][n_keep][D]: the grid points k = 0, stride, 2 stride, ... < Np, n_keep = (Np - 1) / stride + 1
+ *   x0_or_null host, [batch][D]: every path of problem p starts at x0[p].  NULL: x_0 = m0_p + chol_lower(S0_p) xi_0, from the problem's
+ *              own row if vgpa_set_problem_data gave one (VGPA_ERR_STATE for a context created without m0 / s0)
+ *   VGPA_PATHS_POSTERIOR: drift_k(x) = -A_k x + b_k of problem p's own x.  x_or_null given (host, [batch][len_x]): uploaded like every
+ *              other x; the cached sweep state is dropped.  NULL: the x of the cached evaluation is read and nothing of the cached
+ *              state is written -- vgpa_gradient(NULL), vgpa_fetch, vgpa_energy_parts and vgpa_theta_gradient return afterwards bit
+ *              for bit what they return without this call (VGPA_ERR_STATE without a cached state)
+ *   VGPA_PATHS_MODEL: the model's drift with the theta in force (per-problem rows honoured): OU -theta x (the mu = 0 the energy kernel
+ *              assumes), double well 4 x (theta - x^2), Lorenz-63, Lorenz-96 (x_{i+1} - x_{i-2}) x_{i-1} - x_i + theta, circular on each
+ *              path's own state vector.  x_or_null must be NULL.
+ * The normals are counter-based -- a draw depends on (seed, problem, path, grid index, component) and on nothing else, so a result does
+ * not change with the batch size, n_paths or the launch geometry: Philox4x32-10, key (seed & 0xffffffff, seed >> 32), counter
+ * (k, path, problem, j) with k the grid index the draw arrives at (0: the initial draw) and j the component pair;
+ * u1 = (((r0 >> 5) 2^26 + (r1 >> 6)) + 0.5) 2^-53, u2 likewise from r2, r3, each capped at 1 - 2^-53 (the one rounding of fp64 that
+ * would reach 1); xi_2j = sqrt(-2 ln u1) cos(2 pi u2), xi_2j+1 = sqrt(-2 ln u1) sin(2 pi u2) (odd D: the last one is dropped).
+ * VGPA_ERR_ARG: n_paths < 1, stride < 1, an unknown kind, a null out, an x for the model kind, the model kind on VGPA_MODEL_NONE;
+ * VGPA_ERR_UNSUPPORTED: D > 64; VGPA_ERR_NOT_PD: a Sigma dt (or, for a drawn start, an S0) that has no Cholesky factor. */
+enum { VGPA_PATHS_POSTERIOR = 0, VGPA_PATHS_MODEL = 1 };
+int vgpa_sample_paths(vgpa_ctx* ctx, int kind, const double* x_or_null, const double* x0_or_null,
+                      int32_t n_paths, int32_t stride, uint64_t seed, double* out);
 
 /* device-pointer variants (x, g on the context's device; f written to HOST after a sync) ------ */
 int vgpa_sweep_dev(vgpa_ctx* ctx, const double* x_dev, double* f_host, double* g_dev);

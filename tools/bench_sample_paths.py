@@ -1,0 +1,113 @@
+"""
+Time of Context.sample_paths (vgpa_sample_paths) on three jobs, one JSON line.
+
+    python tools/bench_sample_paths.py [--rounds 3] [--calls 5] [--jobs a,b,c]
+
+  a   posterior kind, Lorenz-96, D = 40, Np = 1001, B = 512:   64 paths per problem, stride 100
+  b   posterior kind, Lorenz-63, Np = 1001, B = 65536:          1 path per problem,  stride 100
+  c   model kind on the context of b:                           1 path per problem,  stride 1
+
+The posterior jobs read the x a free_energy_dev left cached (x=None: nothing is uploaded); every job draws its start from (m0, S0).  A call
+is timed with a pair of device events on the context's stream around it -- the host work of the call (the Cholesky factors), the kernel and
+the copy of the result to the host; the median over the calls of a round, then the median over the rounds.  Beside each time:
+
+  numpy_ms   the same job in the numpy restatement of tests/test_sample_paths_cpu.py on one host core, run on `--numpy-problems` problems
+             and scaled linearly to B
+  floor_ms   the bytes that must move in device memory -- x once per workgroup (a: one workgroup per 64 paths of a problem) or per lane
+             (b), the stored points -- at the 8 TB/s DESIGN.md s.5 uses; d2h_mb is the result that travels to the host on top of it
+"""
+import argparse
+import json
+import os
+import sys
+import time
+import types
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+HBM_BYTES_PER_S = 8.0e12
+JOBS = {"a": ("L96", 40, 512, "posterior", 64, 100), "b": ("L63", 3, 65536, "posterior", 1, 100), "c": ("L63", 3, 65536, "model", 1, 1)}
+N_PTS, DT = 1001, 0.01
+
+
+def tree():
+    """the commit of the measured tree: tools/stamp_tree.sh's file (the GPU box has no .git), VGPA_HEAD, or git itself"""
+    path = os.path.join(ROOT, "vgpa_amd", "_tree.txt")
+    if os.path.exists(path):
+        with open(path) as fh:
+            return fh.read().strip()
+    if os.environ.get("VGPA_HEAD"):
+        return os.environ["VGPA_HEAD"]
+    try:
+        import subprocess
+        return subprocess.check_output(["git", "-C", ROOT, "rev-parse", "--short=12", "HEAD"], text=True).strip()
+    except Exception:
+        return "unknown"
+
+
+def numpy_ms(p0, x_row, d, kind, n_paths, stride, n_problems, B):
+    from test_sample_paths_cpu import sample_paths_numpy
+    m = p0["model"]
+    q = types.SimpleNamespace(model=m._model_id, dim_d=d, n_pts=N_PTS, dt=DT, theta=m.theta, sigma=m.sigma, m0=p0["m0"], s0=p0["s0"])
+    t0 = time.perf_counter()
+    for k in range(n_problems):
+        sample_paths_numpy(q, kind, x_row, None, n_paths, stride, 1, index=k)
+    return (time.perf_counter() - t0) * 1e3 / n_problems * B
+
+
+def run(job, rounds, calls, numpy_problems, cache):
+    from bench_problem_batch import StreamTimer, make_contexts
+    name, d, B, kind, n_paths, stride = JOBS[job]
+    if (name, B) not in cache:                        # (b and c share a context)
+        from helpers import SEED, build_problem
+        ctxs, x0 = make_contexts(name, d, N_PTS, DT, B, modes=("shared",))
+        c = ctxs["shared"]
+        len_x = x0.shape[1]
+        rows = x0[np.arange(64) % x0.shape[0]] + 0.05 * np.random.default_rng(1).standard_normal((64, len_x))
+        xb = c.alloc(B * len_x)
+        for i0 in range(0, B, 64):
+            xb.upload_at(i0 * len_x, rows[:min(64, B - i0)])
+        c.free_energy_dev(xb)
+        cache[(name, B)] = (c, xb, rows[0], build_problem(name, "RK4", (N_PTS - 1) * DT, DT, d, seed=SEED), StreamTimer(c))
+    c, xb, x_row, p0, tm = cache[(name, B)]
+    len_x = N_PTS * d * (d + 1)
+    n_keep = (N_PTS - 1) // stride + 1
+    call = lambda: c.sample_paths(kind, n_paths, 1, stride=stride)      # noqa: E731
+    out = call()                                      # warm-up (first-use allocations)
+    assert out.shape == (B, n_paths, n_keep, d) and np.all(np.isfinite(out))
+    del out
+    per_round = [float(np.median([tm.ms(call) for _ in range(calls)])) for _ in range(rounds)]
+    out_bytes = 8.0 * B * n_paths * n_keep * d
+    readers = B * ((n_paths + 63) // 64 if d > 4 else n_paths)
+    x_bytes = 8.0 * readers * len_x if kind == "posterior" else 0.0
+    return {"job": job, "model": name, "D": d, "Np": N_PTS, "B": B, "kind": kind, "n_paths": n_paths, "stride": stride,
+            "ms_per_call": round(float(np.median(per_round)), 4), "rounds_ms": [round(v, 4) for v in per_round],
+            "numpy_ms": round(numpy_ms(p0, x_row, d, kind, n_paths, stride, numpy_problems, B), 1), "numpy_problems": numpy_problems,
+            "floor_ms": round((x_bytes + out_bytes) / HBM_BYTES_PER_S * 1e3, 4), "x_gb": round(x_bytes / 1e9, 3),
+            "d2h_mb": round(out_bytes / 1e6, 1)}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--calls", type=int, default=5)
+    ap.add_argument("--jobs", default="a,b,c")
+    ap.add_argument("--numpy-problems", type=int, default=2)
+    args = ap.parse_args()
+    cache = {}
+    out = {"tool": "bench_sample_paths", "tree": tree(), "unit": "ms per call (device events around the call)", "jobs": []}
+    for job in [j for j in args.jobs.split(",") if j]:
+        out["jobs"].append(run(job, args.rounds, args.calls, args.numpy_problems, cache))
+    for c, _, _, _, tm in cache.values():
+        tm.close()
+        c.close()
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("VGPA_LIB") or os.path.join(os.path.dirname(os.path.ab
 
 MODEL_IDS = {"NONE": -1, "OU": 0, "DW": 1, "L63": 2, "L96": 3}
 METHOD_IDS = {"euler": 0, "heun": 1, "rk2": 2, "rk4": 3}
+PATH_KINDS = {"posterior": 0, "model": 1}
 FETCH_IDS = {"mt": 0, "st": 1, "lamt": 2, "psit": 3, "Efx": 4, "Edf": 5, "dEsde_dm": 6, "dEsde_ds": 7, "Esde_t": 8}
 FLAG_FORCE_GENERIC = 1
 FLAG_STREAM_LARGE_D = 4
@@ -35,7 +36,7 @@ BWD_IDS = {"none": 0, "psi": 1, "q": 2}
 SYMBOLS = ["vgpa_create", "vgpa_destroy", "vgpa_last_error", "vgpa_abi_version", "vgpa_device_count",
            "vgpa_synchronize", "vgpa_stream", "vgpa_solve_fwd", "vgpa_solve_bwd", "vgpa_energy",
            "vgpa_obs_energy", "vgpa_free_energy", "vgpa_gradient", "vgpa_sweep", "vgpa_energy_parts",
-           "vgpa_fetch", "vgpa_theta_gradient", "vgpa_sweep_dev", "vgpa_free_energy_dev", "vgpa_sweep_enqueue", "vgpa_fetch_f",
+           "vgpa_fetch", "vgpa_theta_gradient", "vgpa_sample_paths", "vgpa_sweep_dev", "vgpa_free_energy_dev", "vgpa_sweep_enqueue", "vgpa_fetch_f",
            "vgpa_dev_alloc", "vgpa_dev_free", "vgpa_memcpy_h2d", "vgpa_memcpy_d2h",
            "vgpa_profile_begin", "vgpa_profile_end", "vgpa_ld_gemm", "vgpa_ld_stage", "vgpa_gradient_dev", "vgpa_energy_full", "vgpa_set_option", "vgpa_is_streaming", "vgpa_path_info", "vgpa_set_prior_energy",
            "vgpa_set_problem_data", "vgpa_set_problem_params", "vgpa_set_problem_obs_model",
@@ -132,6 +133,7 @@ def load():
     lib.vgpa_energy_parts.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vgpa_fetch.argtypes = [c_void_p, c_int, c_void_p]
     lib.vgpa_theta_gradient.argtypes = [c_void_p, c_void_p]
+    lib.vgpa_sample_paths.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_int32, c_int32, c_uint64, c_void_p]
     lib.vgpa_sweep_dev.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vgpa_free_energy_dev.argtypes = [c_void_p, c_void_p, c_void_p]
     lib.vgpa_sweep_enqueue.argtypes = [c_void_p, c_void_p, c_void_p]
@@ -540,6 +542,24 @@ class Context:
         out = np.empty((self.B, max(self.n_theta, 1)))
         self._check(self._lib.vgpa_theta_gradient(self._h, _ptr(out)))
         return out[0] if self.B == 1 else out
+
+    def sample_paths(self, kind, n_paths, seed, stride=1, x=None, x0=None):
+        """Euler-Maruyama paths on the context's grid: kind "posterior" (dx = (-A_t x + b_t) dt + Sigma^1/2 dW, from x or, x=None, the x of
+        the cached evaluation, which stays as it is) or "model" (the model SDE at the theta in force; takes no x).  x0 (B, D): the start of every
+        path of a problem; None: x_0 ~ N(m0, S0).  Returns (B, n_paths, n_keep, D), the grid points 0, stride, 2 stride, ...  The draws
+        depend on (seed, problem, path, grid index, component) alone."""
+        if kind not in PATH_KINDS:
+            raise ValueError(f" Unknown kind of paths -> {kind}")
+        n_paths, stride = int(n_paths), int(stride)
+        xx = None if x is None else _c64(x)
+        if xx is not None and xx.size != self.B * self.len_x:
+            raise ValueError(f"x has {xx.size} entries, expected {self.B * self.len_x}")
+        s0 = None if x0 is None else _c64(np.broadcast_to(np.asarray(x0, dtype=np.float64).reshape(-1, self.D), (self.B, self.D)))
+        n_keep = (self.Np - 1) // stride + 1 if stride >= 1 else 0
+        out = np.empty((self.B, max(n_paths, 0), n_keep, self.D))
+        self._check(self._lib.vgpa_sample_paths(self._h, PATH_KINDS[kind], _ptr(xx), _ptr(s0), n_paths, stride,
+                                                int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(out)))
+        return out
 
     def fetch(self, key):
         which = FETCH_IDS[key]

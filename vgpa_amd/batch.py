@@ -190,6 +190,13 @@ class ProblemBatch(object):
             self.free_energy(x)
         return np.asarray(self._context().theta_gradient(), dtype=float).reshape(self.B, -1)
 
+    def sample_paths(self, n_paths, seed, stride=1, x=None, x0=None, kind="posterior"):
+        """(B, n_paths, n_keep, D) Euler-Maruyama paths of every member's posterior process (kind="model": of its model SDE, which takes no
+        x), each with its own data, prior, theta and Sigma.  x=None: the x of the last free_energy, whose cached state stays as it is.
+        x0 (B, D): given starts; None: x_0 ~ N(m0_p, S0_p).  Problem p's draws do not depend on the rest of the batch."""
+        xx = None if x is None else self._stack(x)
+        return self._context().sample_paths(kind, n_paths, seed, stride=stride, x=xx, x0=x0)
+
     def _theta_rows(self):
         return np.stack([np.atleast_1d(np.asarray(v.model.theta, dtype=float)) for v in self.vgps])
 

@@ -1,0 +1,416 @@
+// Euler-Maruyama sample paths of the posterior process dx = (-A_t x + b_t) dt + Sigma^1/2 dW and of the model SDE (vgpa_sample_paths,
+// DESIGN.md s.4.8):  x_k = x_{k-1} + dt drift_{k-1}(x_{k-1}) + R xi_k,  R = chol_lower(Sigma dt).
+//   k_sample_small<D>   D <= 4, both kinds: one lane per path, the state in registers
+//   k_sample_mfma<NT>   5 <= D <= 64, posterior kind: a workgroup owns one problem and 64 paths (4 waves x 16 paths); A_k X (and R Xi for a dense
+//                       R) on v_mfma_f64_16x16x4_f64 with the 16 paths of a wave as the N side, D padded to NT = 16, 32, 48, 64
+//   k_sample_l96        5 <= D <= 64, model kind (Lorenz-96): one lane per path, the state in LDS
+// The normals are counter-based (Philox4x32-10 + Box-Muller, vgpa_hip.h): every lane generates exactly the draws it consumes, so no result
+// depends on the launch geometry.
+#include "vgpa_internal.h"
+
+namespace vgpa {
+namespace {
+
+typedef double d4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t* r) {
+#pragma unroll
+  for (int i = 0; i < 10; i++) {
+    const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+    const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+    c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
+}
+
+__device__ __forceinline__ double unit_open(uint32_t hi, uint32_t lo) {
+  const double u = (((double)(hi >> 5) * 67108864.0 + (double)(lo >> 6)) + 0.5) * 0x1.0p-53;
+  return fmin(u, 0x1.fffffffffffffp-1);     // (2^53 - 1 + 0.5 rounds to 2^53 in fp64: the one value that would reach 1)
+}
+
+// the pair (xi_2j, xi_2j+1) of grid index k, path `path`, problem p
+__device__ __forceinline__ void normal_pair(uint32_t k0, uint32_t k1, uint32_t k, uint32_t path, uint32_t p, uint32_t j, double* z0, double* z1) {
+  uint32_t r[4];
+  philox4x32_10(k, path, p, j, k0, k1, r);
+  const double u1 = unit_open(r[0], r[1]), u2 = unit_open(r[2], r[3]);
+  const double rho = sqrt(-2.0 * log(u1));
+  double s, c;
+  sincos(6.283185307179586 * u2, &s, &c);
+  *z0 = rho * c; *z1 = rho * s;
+}
+
+// ---- D <= 4: one lane per (problem, path) -----------------------------------------------------------------------------------------
+template <int D>
+__device__ __forceinline__ void model_drift(int model, const double* th, const double* x, double* f) {
+  if (model == VGPA_MODEL_OU) { f[0] = -th[0] * x[0]; }
+  else if (model == VGPA_MODEL_DW) { f[0] = 4.0 * x[0] * (th[0] - x[0] * x[0]); }
+  else if (model == VGPA_MODEL_L63) {
+    if constexpr (D == 3) {
+      f[0] = th[0] * (x[1] - x[0]);
+      f[1] = (th[1] - x[2]) * x[0] - x[1];
+      f[2] = x[0] * x[1] - th[2] * x[2];
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < D; i++) f[i] = (x[(i + 1) % D] - x[(i + D - 2) % D]) * x[(i + D - 1) % D] - x[i] + th[0];
+  }
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
+  const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (gid >= (size_t)a.batch * a.n_paths) return;
+  const uint32_t p = (uint32_t)(gid / a.n_paths), path = (uint32_t)(gid % a.n_paths);
+  const uint32_t k0 = (uint32_t)(a.seed & 0xffffffffu), k1 = (uint32_t)(a.seed >> 32);
+  constexpr int NP = (D + 1) / 2;
+  // kept points wait in LDS (slot-major, thread fastest: no conflicts) until NBUF of them -- 16 doubles for D = 1, 2, 4, 15 for D = 3 -- go out as
+  // one run of consecutive stores into the lane's row: whole 128-byte lines once the row has reached a line boundary
+  constexpr int NBUF = 16 / D;
+  __shared__ double stage[NBUF * D * 256];
+  double* sg = stage + threadIdx.x;
+  double R[D * D], th[kMaxTheta], x[D], z[2 * NP];
+  {
+    const double* Rp = a.R + (size_t)p * a.R_stride;
+#pragma unroll
+    for (int e = 0; e < D * D; e++) R[e] = Rp[e];
+#pragma unroll
+    for (int i = 0; i < kMaxTheta; i++) th[i] = a.theta_v ? a.theta_v[(size_t)p * kMaxTheta + i] : a.theta[i];
+  }
+  if (a.x0) {
+#pragma unroll
+    for (int i = 0; i < D; i++) x[i] = a.x0[(size_t)p * D + i];
+  } else {
+    const double* m0 = a.m0 + (size_t)p * a.m0_stride;
+    const double* L0 = a.L0 + (size_t)p * a.L0_stride;
+#pragma unroll
+    for (int j = 0; j < NP; j++) normal_pair(k0, k1, 0u, path, p, (uint32_t)j, &z[2 * j], &z[2 * j + 1]);
+#pragma unroll
+    for (int i = 0; i < D; i++) {
+      double s = 0.0;
+#pragma unroll
+      for (int j = 0; j <= i; j++) s += L0[i * D + j] * z[j];
+      x[i] = m0[i] + s;
+    }
+  }
+  double* o = a.out + gid * (size_t)a.n_keep * D;
+#pragma unroll
+  for (int i = 0; i < D; i++) o[i] = x[i];
+  o += D;
+  const double* A = a.A + (size_t)p * a.stride_x;
+  const double* bv = a.b + (size_t)p * a.stride_x;
+  int until = a.stride, slot = 0;
+  for (int k = 1; k < a.Np; k++) {
+    double f[D];
+    if (a.kind == VGPA_PATHS_POSTERIOR) {
+      const double* Ak = A + (size_t)(k - 1) * D * D;
+      const double* bk = bv + (size_t)(k - 1) * D;
+#pragma unroll
+      for (int i = 0; i < D; i++) {
+        double s = 0.0;
+#pragma unroll
+        for (int j = 0; j < D; j++) s += Ak[i * D + j] * x[j];
+        f[i] = bk[i] - s;
+      }
+    } else {
+      model_drift<D>(a.model, th, x, f);
+    }
+#pragma unroll
+    for (int j = 0; j < NP; j++) normal_pair(k0, k1, (uint32_t)k, path, p, (uint32_t)j, &z[2 * j], &z[2 * j + 1]);
+#pragma unroll
+    for (int i = 0; i < D; i++) {
+      double s = 0.0;
+#pragma unroll
+      for (int j = 0; j <= i; j++) s += R[i * D + j] * z[j];
+      x[i] = (x[i] + a.dt * f[i]) + s;
+    }
+    if (--until == 0) {
+      until = a.stride;
+#pragma unroll
+      for (int i = 0; i < D; i++) sg[(slot * D + i) * 256] = x[i];
+      if (++slot == NBUF) {
+        slot = 0;
+#pragma unroll
+        for (int e = 0; e < NBUF * D; e++) o[e] = sg[e * 256];
+        o += NBUF * D;
+      }
+    }
+  }
+  for (int e = 0; e < slot * D; e++) o[e] = sg[e * 256];
+}
+
+// ---- 5 <= D <= 64, posterior kind ---------------------------------------------------------------------------------------------------
+// v_mfma_f64_16x16x4_f64: lane l gives A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15] and holds C[(l >> 4) + 4 r][l & 15] in r = 0..3.
+// LDS: As [NT][LDA] A_{k-1} row-major, zero beyond D (LDA = 2 mod 32 doubles: the 16 rows x 2 columns a half wave reads fall into
+// 32 different bank pairs); bs [NT]; Rs [NT][LDA] (dense R); Xs / Zs [4 waves][NT][16]: the state / the normals as the B operand reads them.
+template <int NT> struct MfmaShape {
+  static constexpr int LDA = NT <= 32 ? 34 : 66;
+  static constexpr int MT = NT / 16, KT = NT / 4;
+  static constexpr int NPF = (NT * NT + 255) / 256;      // doubles of A_k a thread carries from its load to the LDS write
+  static constexpr size_t lds_doubles(bool dense) { return (size_t)NT * LDA * (dense ? 2 : 1) + NT + 2 * 4 * NT * 16; }
+};
+
+// the normals of grid index k in the C layout of this lane: rows mt * 16 + q + 4 r.  A pair (2j, 2j + 1) spans the lanes q and q ^ 1: the even one
+// draws the pairs of r = 0, 1, the odd one those of r = 2, 3, and each hands the half it does not use to its partner.
+template <int NT>
+__device__ __forceinline__ void normals_c(uint32_t k0, uint32_t k1, uint32_t k, uint32_t path, uint32_t p, int D, int q, double (*z)[4]) {
+  const int odd = q & 1, qe = q & ~1;
+#pragma unroll
+  for (int mt = 0; mt < NT / 16; mt++) {
+    double mine[2], other[2];
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+      const int row = mt * 16 + qe + 4 * (2 * odd + h);      // the even row of the pair
+      double c = 0.0, s = 0.0;
+      if (row < D) normal_pair(k0, k1, k, path, p, (uint32_t)(row >> 1), &c, &s);
+      mine[h] = odd ? s : c;
+      other[h] = __shfl_xor(odd ? c : s, 16);
+    }
+    z[mt][0] = odd ? other[0] : mine[0]; z[mt][1] = odd ? other[1] : mine[1];
+    z[mt][2] = odd ? mine[0] : other[0]; z[mt][3] = odd ? mine[1] : other[1];
+  }
+}
+
+template <int NT>
+__global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
+  using Sh = MfmaShape<NT>;
+  constexpr int LDA = Sh::LDA, MT = Sh::MT, KT = Sh::KT, NPF = Sh::NPF;
+  extern __shared__ double lds[];
+  const int D = a.D, DD = D * D, tid = threadIdx.x, w = tid >> 6, lane = tid & 63, j16 = lane & 15, q = lane >> 4;
+  const bool dense = !a.R_diag;
+  double* As = lds;
+  double* bs = As + NT * LDA;
+  double* Rs = bs + NT;
+  double* Xs = Rs + (dense ? NT * LDA : 0) + w * NT * 16;
+  double* Zs = Xs + 4 * NT * 16;
+  const uint32_t p = blockIdx.x, path = blockIdx.y * 64 + w * 16 + j16;
+  const uint32_t k0 = (uint32_t)(a.seed & 0xffffffffu), k1 = (uint32_t)(a.seed >> 32);
+  const double* A = a.A + (size_t)p * a.stride_x;
+  const double* bv = a.b + (size_t)p * a.stride_x;
+  const double* Rp = a.R + (size_t)p * a.R_stride;
+
+  for (int e = tid; e < NT * LDA * (dense ? 2 : 1) + NT; e += 256) lds[e] = 0.0;
+  __syncthreads();
+  for (int e = tid; e < DD; e += 256) {
+    As[(e / D) * LDA + e % D] = A[e];
+    if (dense) Rs[(e / D) * LDA + e % D] = Rp[e];
+  }
+  if (tid < D) bs[tid] = bv[tid];
+
+  double x[MT][4], rd[MT][4], z[MT][4];
+#pragma unroll
+  for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const int row = mt * 16 + q + 4 * r;
+      rd[mt][r] = (!dense && row < D) ? Rp[row * D + row] : 0.0;
+    }
+  if (a.x0) {
+#pragma unroll
+    for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const int row = mt * 16 + q + 4 * r;
+        x[mt][r] = row < D ? a.x0[(size_t)p * D + row] : 0.0;
+      }
+  } else {
+    const double* m0 = a.m0 + (size_t)p * a.m0_stride;
+    const double* L0 = a.L0 + (size_t)p * a.L0_stride;
+    normals_c<NT>(k0, k1, 0u, path, p, D, q, z);
+#pragma unroll
+    for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) Zs[(mt * 16 + q + 4 * r) * 16 + j16] = z[mt][r];
+    __syncthreads();
+#pragma unroll
+    for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const int row = mt * 16 + q + 4 * r;
+        double s = 0.0;
+        if (row < D)
+          for (int c = 0; c <= row; c++) s += L0[row * D + c] * Zs[c * 16 + j16];
+        x[mt][r] = row < D ? m0[row] + s : 0.0;
+      }
+  }
+  // A kept point leaves from Xs, where the wave's 16 states lie as [row][path]: element e = lane + 64 i of the 16 rows of `out` (path e / D,
+  // component e % D), so that one store instruction writes runs of D consecutive doubles instead of 4 per path
+  const uint32_t path0 = blockIdx.y * 64 + w * 16;
+  double* o = a.out + ((size_t)p * a.n_paths + path0) * (size_t)a.n_keep * D;
+  const size_t row_len = (size_t)a.n_keep * D;
+  auto keep = [&]() {
+#pragma unroll
+    for (int i = 0; i < NT / 4; i++) {
+      const int e = lane + 64 * i;
+      if (e < 16 * D) {
+        const int pl = e / D, cmp = e - pl * D;
+        if (path0 + pl < (uint32_t)a.n_paths) o[pl * row_len + cmp] = Xs[cmp * 16 + pl];
+      }
+    }
+    o += D;
+  };
+#pragma unroll
+  for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+    for (int r = 0; r < 4; r++) Xs[(mt * 16 + q + 4 * r) * 16 + j16] = x[mt][r];
+  __syncthreads();
+  keep();
+
+  int until = a.stride;
+  for (int k = 1; k < a.Np; k++) {
+    // A_k, b_k for the next step: requested now, written to LDS behind this step's products
+    double pa[NPF], pb = 0.0;
+    const bool more = k + 1 < a.Np;
+    if (more) {
+      const double* Ak = A + (size_t)k * DD;
+#pragma unroll
+      for (int n = 0; n < NPF; n++) { const int e = tid + 256 * n; pa[n] = e < DD ? Ak[e] : 0.0; }
+      if (tid < D) pb = bv[(size_t)k * D + tid];
+    }
+    double xb[KT];
+#pragma unroll
+    for (int kk = 0; kk < KT; kk++) xb[kk] = Xs[(kk * 4 + q) * 16 + j16];
+    normals_c<NT>(k0, k1, (uint32_t)k, path, p, D, q, z);
+    if (dense) {
+#pragma unroll
+      for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) Zs[(mt * 16 + q + 4 * r) * 16 + j16] = z[mt][r];
+      __syncthreads();
+    }
+#pragma unroll
+    for (int mt = 0; mt < MT; mt++) {
+      d4 acc = {0.0, 0.0, 0.0, 0.0};
+      const double* ar = As + (mt * 16 + j16) * LDA + q;
+#pragma unroll
+      for (int kk = 0; kk < KT; kk++) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(ar[kk * 4], xb[kk], acc, 0, 0, 0);
+      d4 nz = {rd[mt][0] * z[mt][0], rd[mt][1] * z[mt][1], rd[mt][2] * z[mt][2], rd[mt][3] * z[mt][3]};
+      if (dense) {
+        nz = d4{0.0, 0.0, 0.0, 0.0};
+        const double* rr = Rs + (mt * 16 + j16) * LDA + q;
+#pragma unroll
+        for (int kk = 0; kk < KT; kk++) nz = __builtin_amdgcn_mfma_f64_16x16x4f64(rr[kk * 4], Zs[(kk * 4 + q) * 16 + j16], nz, 0, 0, 0);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; r++) x[mt][r] = (x[mt][r] + a.dt * (bs[mt * 16 + q + 4 * r] - acc[r])) + nz[r];
+    }
+    __syncthreads();
+    if (more) {
+#pragma unroll
+      for (int n = 0; n < NPF; n++) { const int e = tid + 256 * n; if (e < DD) As[(e / D) * LDA + e % D] = pa[n]; }
+      if (tid < D) bs[tid] = pb;
+    }
+#pragma unroll
+    for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) Xs[(mt * 16 + q + 4 * r) * 16 + j16] = x[mt][r];
+    __syncthreads();
+    if (--until == 0) { until = a.stride; keep(); }
+  }
+}
+
+// ---- 5 <= D <= 64, model kind: Lorenz-96 ------------------------------------------------------------------------------------------
+// One lane per (problem, path); xs [D][64] in LDS, component-major so that a wave's 64 lanes touch 64 consecutive doubles.  The drift is
+// evaluated in place behind three rolling registers of old values.  zs [D][64]: the normals, when a dense factor needs all of them at once.
+__global__ __launch_bounds__(64) void k_sample_l96(SampleArgs a) {
+  extern __shared__ double lds[];
+  const int D = a.D, lane = threadIdx.x;
+  double* xs = lds + lane;
+  double* zs = lds + (size_t)D * 64 + lane;
+  const size_t gid = (size_t)blockIdx.x * 64 + lane;
+  if (gid >= (size_t)a.batch * a.n_paths) return;      // (no barrier below: a lane reads and writes its own column only)
+  const uint32_t p = (uint32_t)(gid / a.n_paths), path = (uint32_t)(gid % a.n_paths);
+  const uint32_t k0 = (uint32_t)(a.seed & 0xffffffffu), k1 = (uint32_t)(a.seed >> 32);
+  const double* Rp = a.R + (size_t)p * a.R_stride;
+  const double th = a.theta_v ? a.theta_v[(size_t)p * kMaxTheta] : a.theta[0];
+  const bool dense = !a.R_diag;
+  if (a.x0) {
+    for (int i = 0; i < D; i++) xs[i * 64] = a.x0[(size_t)p * D + i];
+  } else {
+    const double* m0 = a.m0 + (size_t)p * a.m0_stride;
+    const double* L0 = a.L0 + (size_t)p * a.L0_stride;
+    for (int j = 0; 2 * j < D; j++) {
+      double c, s;
+      normal_pair(k0, k1, 0u, path, p, (uint32_t)j, &c, &s);
+      zs[2 * j * 64] = c;
+      if (2 * j + 1 < D) zs[(2 * j + 1) * 64] = s;
+    }
+    for (int i = 0; i < D; i++) {
+      double s = 0.0;
+      for (int j = 0; j <= i; j++) s += L0[i * D + j] * zs[j * 64];
+      xs[i * 64] = m0[i] + s;
+    }
+  }
+  double* o = a.out + gid * (size_t)a.n_keep * D;
+  for (int i = 0; i < D; i++) o[i] = xs[i * 64];
+  o += D;
+  int until = a.stride;
+  for (int k = 1; k < a.Np; k++) {
+    if (dense)
+      for (int j = 0; 2 * j < D; j++) {
+        double c, s;
+        normal_pair(k0, k1, (uint32_t)k, path, p, (uint32_t)j, &c, &s);
+        zs[2 * j * 64] = c;
+        if (2 * j + 1 < D) zs[(2 * j + 1) * 64] = s;
+      }
+    const double x_first = xs[0];
+    double om2 = xs[(D - 2) * 64], om1 = xs[(D - 1) * 64], cur = x_first, zc = 0.0, zn = 0.0;
+    for (int i = 0; i < D; i++) {
+      const double nxt = i + 1 < D ? xs[(i + 1) * 64] : x_first;
+      const double f = (nxt - om2) * om1 - cur + th;
+      double nz;
+      if (dense) {
+        nz = 0.0;
+        for (int j = 0; j <= i; j++) nz += Rp[i * D + j] * zs[j * 64];
+      } else {
+        if (!(i & 1)) normal_pair(k0, k1, (uint32_t)k, path, p, (uint32_t)(i >> 1), &zc, &zn);
+        nz = Rp[i * D + i] * ((i & 1) ? zn : zc);
+      }
+      xs[i * 64] = (cur + a.dt * f) + nz;
+      om2 = om1; om1 = cur; cur = nxt;
+    }
+    if (--until == 0) {
+      until = a.stride;
+      for (int i = 0; i < D; i++) o[i] = xs[i * 64];
+      o += D;
+    }
+  }
+}
+
+template <int NT>
+hipError_t launch_mfma(const SampleArgs& a, hipStream_t st) {
+  const size_t lds = MfmaShape<NT>::lds_doubles(!a.R_diag) * sizeof(double);
+  if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k_sample_mfma<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if ((a.n_paths + 63) / 64 > 65535) return hipErrorInvalidValue;      // (grid.y)
+  hipLaunchKernelGGL(k_sample_mfma<NT>, dim3(a.batch, (a.n_paths + 63) / 64), dim3(256), lds, st, a);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_sample_paths(const SampleArgs& a, hipStream_t st) {
+  const size_t lanes = (size_t)a.batch * a.n_paths;
+  if (a.D < 1 || a.D > kMaxSmallD || a.n_paths < 1 || a.stride < 1) return hipErrorInvalidValue;
+  if (a.D <= kMaxLaneD) {
+    const dim3 grid((unsigned)((lanes + 255) / 256)), block(256);
+    switch (a.D) {
+      case 1: hipLaunchKernelGGL(k_sample_small<1>, grid, block, 0, st, a); break;
+      case 2: hipLaunchKernelGGL(k_sample_small<2>, grid, block, 0, st, a); break;
+      case 3: hipLaunchKernelGGL(k_sample_small<3>, grid, block, 0, st, a); break;
+      default: hipLaunchKernelGGL(k_sample_small<4>, grid, block, 0, st, a); break;
+    }
+    return hipGetLastError();
+  }
+  if (a.kind == VGPA_PATHS_MODEL) {
+    if (a.model != VGPA_MODEL_L96) return hipErrorInvalidValue;
+    const size_t lds = (size_t)a.D * 64 * sizeof(double) * ((!a.R_diag || !a.x0) ? 2 : 1);
+    hipLaunchKernelGGL(k_sample_l96, dim3((unsigned)((lanes + 63) / 64)), dim3(64), lds, st, a);
+    return hipGetLastError();
+  }
+  if (a.D <= 16) return launch_mfma<16>(a, st);
+  if (a.D <= 32) return launch_mfma<32>(a, st);
+  if (a.D <= 48) return launch_mfma<48>(a, st);
+  return launch_mfma<64>(a, st);
+}
+
+}  // namespace vgpa

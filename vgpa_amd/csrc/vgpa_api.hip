@@ -28,6 +28,7 @@ struct BatchInputs {
   Rows<double> Q, K, rinv, jsc, jscp, obs_const;   // [B][D][D] x2, [B][D], [B][D][D] x2, [B]
   Rows<int32_t> n_obs;                 // [B]
   std::vector<double> h_theta, h_isig, h_sig1, h_e0;  // host copies of the per-problem values (theta_of, isig_of, sigma1_of, e0_of)
+  std::vector<double> h_Sigma, h_S0;   // ... and of the Sigma / S0 rows in force (empty: the shared one), which vgpa_sample_paths factorises
 };
 
 struct SigmaForm { bool diag = true, iso = true, sym = true; };   // of one Sigma: diagonal, sigma^2 I, symmetric
@@ -146,7 +147,7 @@ struct vgpa_ctx {
   int64_t* d_pp_obs_t = nullptr; int32_t* d_pp_obs_idx = nullptr;
   double *d_jm_pt = nullptr, *d_js_pt = nullptr;   // dense jumps [B][Np][D], [B][Np][D][D]: per-problem times on the 16-lane kernels
   bool pt_dense_zeroed = false;  // ... which are zero off the observation rows of the current times (each sweep rewrites only those rows)
-  std::vector<double> h_sigma;       // host copy of the shared Sigma [D][D]
+  std::vector<double> h_sigma, h_s0; // host copies of the shared Sigma and S0 [D][D] (h_s0 empty: vgpa_config gave none)
   // per-problem observation model (vgpa_set_problem_obs_model)
   double *d_pp_Q = nullptr, *d_pp_K = nullptr, *d_pp_rinv = nullptr, *d_pp_jsc = nullptr, *d_pp_jscp = nullptr, *d_pp_obsc = nullptr;
   int32_t* d_pp_nobs = nullptr;
@@ -158,6 +159,9 @@ struct vgpa_ctx {
   bool shared_obs_diag = false, jsc_rows_sym = true;   // obs_diag of vgpa_config's model; every per-problem constant jump symmetric
   SigmaForm sigma_form, rows_form;            // make_plan's inputs: the form of the shared Sigma, of the per-problem rows in force,
   bool inputs_sym = true, s0_rows_sym = true;  // ... the shared s0 and constant jump symmetric, the per-problem s0 rows symmetric
+  // vgpa_sample_paths: the result, the noise factors R, the factors of S0 and the given starts; grown on demand, freed in vgpa_destroy
+  double *d_sp_out = nullptr, *d_sp_R = nullptr, *d_sp_L0 = nullptr, *d_sp_x0 = nullptr;
+  size_t sp_out_n = 0, sp_R_n = 0, sp_L0_n = 0, sp_x0_n = 0;
   // profiling
   bool prof = false;
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -930,6 +934,7 @@ void vgpa_destroy(vgpa_ctx* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   for (void* p : c->allocs) (void)hipFree(p);
   for (void* p : c->user_allocs) (void)hipFree(p);
+  for (double* p : {c->d_sp_out, c->d_sp_R, c->d_sp_L0, c->d_sp_x0}) if (p) (void)hipFree(p);
   if (c->h_coef) (void)hipHostFree(c->h_coef);
   if (c->h_fs) (void)hipHostFree(c->h_fs);
   for (auto& e : c->ev_coef) if (e) (void)hipEventDestroy(e);
@@ -1039,7 +1044,7 @@ int vgpa_create(vgpa_ctx** out, const vgpa_config* cfg) {
   TRY(upload(c, c->d_isg, isg.data(), (size_t)D));
   c->isg0 = isg[0];
   if (cfg->m0) TRY(upload(c, c->d_m0, cfg->m0, (size_t)D));
-  if (cfg->s0) TRY(upload(c, c->d_S0, cfg->s0, DD));
+  if (cfg->s0) { TRY(upload(c, c->d_S0, cfg->s0, DD)); c->h_s0.assign(cfg->s0, cfg->s0 + DD); }
 
   std::vector<int32_t> obs_idx(c->Np, -1);
   std::vector<double> Q(DD, 0.0), K(DD, 0.0), rinv(D, 0.0), jsc(DD, 0.0);
@@ -1419,6 +1424,91 @@ int vgpa_theta_gradient(vgpa_ctx* c, double* out) {
   return VGPA_OK;
 }
 
+// a buffer of vgpa_sample_paths that grows on demand: at least `count` doubles behind *p
+static int grow(vgpa_ctx* c, double** p, size_t* have, size_t count) {
+  if (*p && *have >= count) return VGPA_OK;
+  if (*p) { (void)hipStreamSynchronize(c->stream); (void)hipFree(*p); *p = nullptr; *have = 0; }
+  void* q = nullptr;
+  hipError_t e = hipMalloc(&q, (count ? count : 1) * sizeof(double));
+  if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "hipMalloc(%zu bytes) failed: %s", count * sizeof(double), hipGetErrorString(e));
+  *p = static_cast<double*>(q); *have = count;
+  return VGPA_OK;
+}
+
+// The lower Cholesky factors of `scale` times n host matrices D x D (n = 1: shared by the batch, else one per problem), uploaded into *buf;
+// *diag: every factor is diagonal.  VGPA_ERR_NOT_PD names the row.
+static int factor_rows(vgpa_ctx* c, const double* src, int n, double scale, const char* what, double** buf, size_t* have, Rows<double>* out, bool* diag) {
+  const int D = c->D;
+  const size_t DD = c->DD;
+  std::vector<double> a(DD), l((size_t)n * DD);
+  int rc;
+  *diag = true;
+  for (int p = 0; p < n; p++) {
+    for (size_t e = 0; e < DD; e++) a[e] = src[p * DD + e] * scale;
+    if (!host_cholesky_lower(D, a.data(), l.data() + p * DD)) return fail(c, VGPA_ERR_NOT_PD, "problem %d: %s is not positive definite.", p, what);
+    for (int i = 0; i < D; i++)
+      for (int j = 0; j < i; j++) *diag = *diag && l[p * DD + (size_t)i * D + j] == 0.0;
+  }
+  if ((rc = grow(c, buf, have, l.size()))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(*buf, l.data(), l.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));      // (the host rows live on this stack frame)
+  *out = {*buf, n > 1 ? DD : 0};
+  return VGPA_OK;
+}
+
+// Euler-Maruyama paths of the posterior process or of the model SDE (see vgpa_hip.h).  Reads x and the inputs in force; of the
+// cached state nothing is written.
+int vgpa_sample_paths(vgpa_ctx* c, int kind, const double* x, const double* x0, int32_t n_paths, int32_t stride, uint64_t seed, double* out) {
+  if (!c) return VGPA_ERR_ARG;
+  if (!out) return fail(c, VGPA_ERR_ARG, "null argument");
+  if (kind != VGPA_PATHS_POSTERIOR && kind != VGPA_PATHS_MODEL) return fail(c, VGPA_ERR_ARG, "unknown kind of paths -> %d", kind);
+  if (n_paths < 1 || stride < 1) return fail(c, VGPA_ERR_ARG, "n_paths and stride must be at least 1 (n_paths = %d, stride = %d)", n_paths, stride);
+  if (kind == VGPA_PATHS_MODEL && x) return fail(c, VGPA_ERR_ARG, "paths of the model SDE take no x");
+  if (kind == VGPA_PATHS_MODEL && c->cfg.model == VGPA_MODEL_NONE) return fail(c, VGPA_ERR_ARG, "context has no stochastic model (ODE-only): no model SDE to sample");
+  if (c->D > kMaxSmallD) return fail(c, VGPA_ERR_UNSUPPORTED, "sample paths are built for D <= %d (D = %d)", kMaxSmallD, c->D);
+  if (kind == VGPA_PATHS_POSTERIOR && !x && !c->res.cached)
+    return fail(c, VGPA_ERR_STATE, "no cached state: sample_paths without x needs the state cached by a previous free_energy / sweep");
+  if (!x0 && !(c->cfg.m0 && c->cfg.s0)) return fail(c, VGPA_ERR_STATE, "context was created without m0/s0: the paths need a start x0");
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  const int D = c->D, B = c->B;
+  int rc;
+  SampleArgs a{};
+  a.kind = kind; a.model = c->cfg.model; a.D = D; a.Np = c->Np; a.batch = B; a.n_paths = n_paths; a.stride = stride;
+  a.n_keep = (c->Np - 1) / stride + 1; a.dt = c->cfg.dt; a.seed = seed;
+  Rows<double> R, L0;
+  bool diag = true, l0_diag = true;
+  const bool own_Sigma = !c->in.h_Sigma.empty(), own_S0 = !c->in.h_S0.empty();     // (the host copies of the rows in force)
+  if ((rc = factor_rows(c, own_Sigma ? c->in.h_Sigma.data() : c->h_sigma.data(), own_Sigma ? B : 1, c->cfg.dt, "noise matrix times dt",
+                        &c->d_sp_R, &c->sp_R_n, &R, &diag))) return rc;
+  a.R = R.rows; a.R_stride = R.stride; a.R_diag = diag ? 1 : 0;
+  if (x0) {
+    if ((rc = grow(c, &c->d_sp_x0, &c->sp_x0_n, (size_t)B * D))) return rc;
+    if ((rc = upload(c, c->d_sp_x0, x0, (size_t)B * D))) return rc;
+    a.x0 = c->d_sp_x0;
+  } else {
+    if ((rc = factor_rows(c, own_S0 ? c->in.h_S0.data() : c->h_s0.data(), own_S0 ? B : 1, 1.0, "initial covariance", &c->d_sp_L0, &c->sp_L0_n,
+                          &L0, &l0_diag))) return rc;
+    a.m0 = c->in.m0.rows; a.m0_stride = c->in.m0.stride; a.L0 = L0.rows; a.L0_stride = L0.stride;
+  }
+  if (kind == VGPA_PATHS_POSTERIOR) {
+    if (x) {
+      if ((rc = ingest_x(c, x, false))) return rc;
+      c->res.cache_dropped();           // (d_x no longer holds the x of the cached state)
+    }
+    a.A = ctx_A(c); a.b = ctx_b(c); a.stride_x = c->len_x;
+  } else {
+    copy_theta(c, a.theta);
+    a.theta_v = c->in.theta.rows;
+  }
+  const size_t n_out = (size_t)B * n_paths * a.n_keep * D;
+  if ((rc = grow(c, &c->d_sp_out, &c->sp_out_n, n_out))) return rc;
+  a.out = c->d_sp_out;
+  LAUNCH_TRY(c, "sample paths launch", launch_sample_paths(a, c->stream));
+  if ((rc = download(c, out, c->d_sp_out, n_out))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return VGPA_OK;
+}
+
 int vgpa_fetch(vgpa_ctx* c, int which, double* out) {
   if (!c || !out) return fail(c, VGPA_ERR_ARG, "null argument");
   if (!c->res.cached) return fail(c, VGPA_ERR_STATE, "no cached state: call free_energy first");
@@ -1617,6 +1707,7 @@ int vgpa_set_problem_data(vgpa_ctx* c, const int64_t* obs_t, const double* obs_y
   if (obs_y && M > 0 && (rc = upload_rows(c, &c->d_pp_obs_y, obs_y, (size_t)M * D, &in.obs_y))) return rc;
   if (m0 && (rc = upload_rows(c, &c->d_pp_m0, m0, D, &in.m0))) return rc;
   if (s0 && (rc = upload_rows(c, &c->d_pp_S0, s0, c->DD, &in.S0))) return rc;
+  if (s0) in.h_S0.assign(s0, s0 + (size_t)B * c->DD); else in.h_S0.clear();
   if (e0) {
     in.h_e0.assign(e0, e0 + B);
     if ((rc = upload_rows(c, &c->d_pp_e0, in.h_e0.data(), 1, &in.e0))) return rc;
@@ -1660,6 +1751,7 @@ int vgpa_set_problem_params(vgpa_ctx* c, const double* theta, const double* sigm
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   c->res.cache_dropped();           // (like vgpa_set_problem_data: the cached state belongs to the old parameters)
   BatchInputs& in = c->in;
+  in.h_Sigma.clear();
   in.theta = in.sig1 = in.qs = {}; in.Sigma = {c->d_Sigma, 0}; in.isig = {c->d_isig, 0}; in.isg = {c->d_isg, 0};
   // every row at the shared parameters: the shared kernels (the same results, bit for bit); else every row is in force -- above D = 64
   // theta's only (Sigma is the shared one there)
@@ -1670,6 +1762,7 @@ int vgpa_set_problem_params(vgpa_ctx* c, const double* theta, const double* sigm
     if (D <= kMaxSmallD) {
       in.h_isig = std::move(is); in.h_sig1 = std::move(s1);
       if ((rc = upload_rows(c, &c->d_pp_Sigma, sg.data(), DD, &in.Sigma))) return rc;
+      in.h_Sigma = sg;
       if ((rc = upload_rows(c, &c->d_pp_isig, in.h_isig.data(), DD, &in.isig))) return rc;
       if ((rc = upload_rows(c, &c->d_pp_isg, ig.data(), D, &in.isg))) return rc;
       if ((rc = upload_rows(c, &c->d_pp_sig1, in.h_sig1.data(), 1, &in.sig1))) return rc;

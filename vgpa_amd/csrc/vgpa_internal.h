@@ -222,6 +222,27 @@ struct ReduceArgs {
   const double* div_v;      // [B] per-problem div (1-D models: sigma_p), or nullptr
 };
 
+// Euler-Maruyama sample paths (sample.hip; vgpa_sample_paths): x_k = x_{k-1} + dt drift_{k-1}(x_{k-1}) + R xi_k on the context's grid
+struct SampleArgs {
+  int kind, model, D, Np, batch, n_paths, stride, n_keep;
+  double dt;
+  uint64_t seed;
+  const double* A;          // posterior kind: [B][Np][D][D] (problem stride stride_x)
+  const double* b;          // ... [B][Np][D]
+  size_t stride_x;
+  double theta[kMaxTheta];  // model kind
+  const double* theta_v;    // [B][kMaxTheta] instead of theta, or nullptr
+  const double* R;          // [D][D] lower factor of Sigma dt, row-major; [B][D][D] with R_stride = D*D
+  size_t R_stride;
+  int R_diag;               // every R is diagonal: the noise is a scale
+  const double* x0;         // [B][D] given start, or nullptr: x_0 = m0 + L0 xi_0
+  const double* m0;         // [D], or [B][D] with m0_stride = D
+  const double* L0;         // [D][D] lower factor of S0, or [B][D][D] with L0_stride = D*D
+  size_t m0_stride, L0_stride;
+  double* out;              // [B][n_paths][n_keep][D]
+};
+hipError_t launch_sample_paths(const SampleArgs& a, hipStream_t st);
+
 // launchers (each returns hipGetLastError()) -----------------------------------------------------
 hipError_t launch_ode_generic(int method, bool fwd, const OdeArgs& a, hipStream_t st);
 hipError_t launch_ode_small(int method, bool fwd, const OdeArgs& a, hipStream_t st);     // D <= kMaxLaneD

@@ -34,6 +34,7 @@ class StochasticProcess(object):
         self.xt = None
         self.tk = None
         self._energy_ctx = {}
+        self._paths_ctx = None         # (key, Context) of sample_trajectories
         self.device = 0
 
     # -- accessors ---------------------------------------------------------------------------
@@ -114,10 +115,33 @@ class StochasticProcess(object):
             self._energy_ctx[key] = ctx
         return ctx
 
+    def sample_trajectories(self, x0, n_paths, t0: float, tf: float, dt: float = 0.01, seed=0, stride=1):
+        """n_paths Euler-Maruyama trajectories of the model SDE from x0 on the GPU (vgpa_sample_paths, model kind): (tk_kept, paths) with
+        paths (n_paths, n_keep, D), or (n_paths, n_keep) for the 1-D models, at the grid points 0, stride, 2 stride, ... of
+        arange(t0, tf + dt, dt).  Counter-based normals of `seed`: make_trajectory and its numpy stream are not involved, and
+        sample_path / time_window stay as they are."""
+        tk = np.arange(t0, tf + dt, dt)
+        d = 1 if self.single_dim else int(self.dim_d)
+        key = (tk.size, d, float(dt), self.device)
+        if self._paths_ctx is None or self._paths_ctx[0] != key:       # one context of this kind at a time: the old one goes with its buffers
+            self._close_paths_ctx()
+            sigma = np.array([[self.sigma]], dtype=float) if self.single_dim else np.asarray(self.sigma, dtype=float)
+            self._paths_ctx = (key, Context(self._model_id, "euler", d, tk.size, float(dt), sigma=sigma, theta=self._theta_vec(),
+                                            device=self.device))
+        ctx = self._paths_ctx[1]
+        paths = ctx.sample_paths("model", n_paths, seed, stride=stride, x0=np.asarray(x0, dtype=float).reshape(1, d))[0]
+        return tk[::int(stride)], (paths[..., 0] if self.single_dim else paths)
+
+    def _close_paths_ctx(self):
+        if self._paths_ctx is not None:
+            self._paths_ctx[1].close()
+        self._paths_ctx = None
+
     def _invalidate(self):
         for c in self._energy_ctx.values():
             c.close()
         self._energy_ctx.clear()
+        self._close_paths_ctx()
 
     def energy(self, linear_a, offset_b, m, s, obs_t):
         """E_sde and related quantities on the GPU.  `obs_t` is accepted for signature parity: the piecewise

@@ -146,6 +146,17 @@ class VarGP(object):
             g = g[..., 0]
         return float(g) if g.ndim == 0 else g
 
+    def sample_paths(self, n_paths, seed, stride=1, x=None, x0=None):
+        """Draws from the posterior process dx = (-A_t x + b_t) dt + Sigma^1/2 dW by Euler-Maruyama on the grid: (n_paths, n_keep, D), or
+        (n_paths, n_keep) for the 1-D models (with batch > 1 a leading batch axis), the grid points 0, stride, 2 stride, ...  x=None: the
+        (A_t, b_t) of the last free_energy (like theta_gradient(); the cached state stays as it is).  x0=None: x_0 ~ N(m0, S0); else every
+        path starts at x0.  The draws depend on (seed, problem, path, grid index, component) alone."""
+        xx = None if x is None else np.asarray(x, dtype=float)
+        out = self._context().sample_paths("posterior", n_paths, seed, stride=stride, x=xx, x0=x0)
+        if self.model.single_dim:
+            out = out[..., 0]
+        return out[0] if self.batch == 1 else out
+
     def fit_theta(self, x0, rounds, options=None):
         """Variational EM for the drift parameters (ProblemBatch.fit_theta on a batch of one): (x, F, theta, trace), theta in the
         shape of model.theta, trace["F"] of shape (rounds, 2, 1)."""
