@@ -227,6 +227,28 @@ enum { VGPA_PATHS_POSTERIOR = 0, VGPA_PATHS_MODEL = 1 };
 int vgpa_sample_paths(vgpa_ctx* ctx, int kind, const double* x_or_null, const double* x0_or_null,
                       int32_t n_paths, int32_t stride, uint64_t seed, double* out);
 
+/* The paths of vgpa_sample_paths(VGPA_PATHS_POSTERIOR) with the same arguments -- the same counters, the same recursion -- and, summed where each
+ * path is made, the logarithm of its importance weight against the model SDE and the data: what turns draws from the approximation into an
+ * estimate of log p(y | theta, Sigma), an effective sample size and reweighted smoothing expectations.  With g = -A_{k-1} x_{k-1} + b_{k-1},
+ * f = f_theta(x_{k-1}) the model drift of VGPA_PATHS_MODEL, d = g - f and eta_k = R_p xi_k the step's noise increment, both chains have
+ * Gaussian transitions of covariance Sigma dt, and the log-ratio of the discrete path densities is exactly
+ *   path term = sum_{k=1}^{Np-1} [ -d^T Sigma^-1 eta_k - dt d^T Sigma^-1 d / 2 ]
+ *   obs term  = sum_n [ -(y_n - x_{t_n})^T Q (y_n - x_{t_n}) / 2 ] - the additive constant of E_obs,   Q = H R^-1 H^T (1-D models: 1 / r)
+ * with the theta, Sigma, observation times, values, count, R and H in force (per-problem rows honoured).  An observation at grid index 0
+ * applies to x_0, one at Np - 1 to the last state.  The third term of log w = init + path + obs,
+ *   init term = log N(x_0; mu0, tau0) - log N(x_0; m0, S0)   (0 for a given x0),
+ * is the caller's: the prior (mu0, tau0) is not an input of the context, and `start` holds the x_0 it needs.  These are the true Gaussian
+ * densities: the reference's quirks in E0 and E_obs are not reproduced, so -mean(log w) is not F (DESIGN.md s.4.9 says which parts differ).
+ *   logw          host, [batch][n_paths][2]: the path term, the obs term
+ *   start_or_null host, [batch][n_paths][D]: x_0 of every path
+ *   out_or_null   as `out` of vgpa_sample_paths; NULL: no path is stored or copied (many paths, a tiny result)
+ *   x_or_null, x0_or_null, n_paths, stride, seed: as in vgpa_sample_paths; with x NULL the cached state is read and not written
+ * Sigma^-1 is 1 / Sigma_ii: built for an isotropic or diagonal Sigma, shared or per problem.
+ * VGPA_ERR_ARG: a null logw, n_paths < 1, stride < 1, VGPA_MODEL_NONE; VGPA_ERR_STATE: an ODE-only context, no cached state with x NULL;
+ * VGPA_ERR_UNSUPPORTED: D > 64, a dense Sigma in force; VGPA_ERR_NOT_PD: as in vgpa_sample_paths. */
+int vgpa_sample_paths_weighted(vgpa_ctx* ctx, const double* x_or_null, const double* x0_or_null, int32_t n_paths, int32_t stride,
+                               uint64_t seed, double* out_or_null, double* start_or_null, double* logw);
+
 /* device-pointer variants (x, g on the context's device; f written to HOST after a sync) ------ */
 int vgpa_sweep_dev(vgpa_ctx* ctx, const double* x_dev, double* f_host, double* g_dev);
 int vgpa_free_energy_dev(vgpa_ctx* ctx, const double* x_dev, double* f_host);

@@ -1,11 +1,13 @@
 """
-Time of Context.sample_paths (vgpa_sample_paths) on three jobs, one JSON line.
+Time of Context.sample_paths (vgpa_sample_paths) and Context.sample_paths_weighted (vgpa_sample_paths_weighted) on their jobs, one JSON line.
 
-    python tools/bench_sample_paths.py [--rounds 3] [--calls 5] [--jobs a,b,c]
+    python tools/bench_sample_paths.py [--rounds 3] [--calls 5] [--jobs a,b,c,aw,aw0,bw,bw0]
 
   a   posterior kind, Lorenz-96, D = 40, Np = 1001, B = 512:   64 paths per problem, stride 100
   b   posterior kind, Lorenz-63, Np = 1001, B = 65536:          1 path per problem,  stride 100
   c   model kind on the context of b:                           1 path per problem,  stride 1
+  aw, bw     the weighted twins of a and b: the same paths stored, and the two sums and x_0 of every path
+  aw0, bw0   ... weights only: no path is stored or copied
 
 The posterior jobs read the x a free_energy_dev left cached (x=None: nothing is uploaded); every job draws its start from (m0, S0).  A call
 is timed with a pair of device events on the context's stream around it -- the host work of the call (the Cholesky factors), the kernel and
@@ -32,6 +34,7 @@ for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")):
 
 HBM_BYTES_PER_S = 8.0e12
 JOBS = {"a": ("L96", 40, 512, "posterior", 64, 100), "b": ("L63", 3, 65536, "posterior", 1, 100), "c": ("L63", 3, 65536, "model", 1, 1)}
+WEIGHTED = {"aw": ("a", True), "aw0": ("a", False), "bw": ("b", True), "bw0": ("b", False)}      # job -> (its unweighted twin, paths stored)
 N_PTS, DT = 1001, 0.01
 
 
@@ -62,7 +65,9 @@ def numpy_ms(p0, x_row, d, kind, n_paths, stride, n_problems, B):
 
 def run(job, rounds, calls, numpy_problems, cache):
     from bench_problem_batch import StreamTimer, make_contexts
-    name, d, B, kind, n_paths, stride = JOBS[job]
+    twin, stored = WEIGHTED.get(job, (job, True))
+    weighted = job in WEIGHTED
+    name, d, B, kind, n_paths, stride = JOBS[twin]
     if (name, B) not in cache:                        # (b and c share a context)
         from helpers import SEED, build_problem
         ctxs, x0 = make_contexts(name, d, N_PTS, DT, B, modes=("shared",))
@@ -77,19 +82,30 @@ def run(job, rounds, calls, numpy_problems, cache):
     c, xb, x_row, p0, tm = cache[(name, B)]
     len_x = N_PTS * d * (d + 1)
     n_keep = (N_PTS - 1) // stride + 1
-    call = lambda: c.sample_paths(kind, n_paths, 1, stride=stride)      # noqa: E731
-    out = call()                                      # warm-up (first-use allocations)
-    assert out.shape == (B, n_paths, n_keep, d) and np.all(np.isfinite(out))
-    del out
+    if weighted:
+        call = lambda: c.sample_paths_weighted(n_paths, 1, stride=stride, paths=stored)      # noqa: E731
+        out, logw, start = call()                     # warm-up (first-use allocations)
+        assert logw.shape == (B, n_paths, 2) and start.shape == (B, n_paths, d) and np.all(np.isfinite(logw)) and np.all(np.isfinite(start))
+        assert (out is None) if not stored else (out.shape == (B, n_paths, n_keep, d) and bool(np.all(np.isfinite(out))))
+        del out, logw, start
+    else:
+        call = lambda: c.sample_paths(kind, n_paths, 1, stride=stride)      # noqa: E731
+        out = call()                                  # warm-up (first-use allocations)
+        assert out.shape == (B, n_paths, n_keep, d) and np.all(np.isfinite(out))
+        del out
     per_round = [float(np.median([tm.ms(call) for _ in range(calls)])) for _ in range(rounds)]
-    out_bytes = 8.0 * B * n_paths * n_keep * d
+    out_bytes = 8.0 * B * n_paths * ((n_keep * d if stored else 0) + ((2 + d) if weighted else 0))
     readers = B * ((n_paths + 63) // 64 if d > 4 else n_paths)
     x_bytes = 8.0 * readers * len_x if kind == "posterior" else 0.0
-    return {"job": job, "model": name, "D": d, "Np": N_PTS, "B": B, "kind": kind, "n_paths": n_paths, "stride": stride,
-            "ms_per_call": round(float(np.median(per_round)), 4), "rounds_ms": [round(v, 4) for v in per_round],
-            "numpy_ms": round(numpy_ms(p0, x_row, d, kind, n_paths, stride, numpy_problems, B), 1), "numpy_problems": numpy_problems,
-            "floor_ms": round((x_bytes + out_bytes) / HBM_BYTES_PER_S * 1e3, 4), "x_gb": round(x_bytes / 1e9, 3),
-            "d2h_mb": round(out_bytes / 1e6, 1)}
+    res = {"job": job, "model": name, "D": d, "Np": N_PTS, "B": B, "kind": kind, "n_paths": n_paths, "stride": stride,
+           "ms_per_call": round(float(np.median(per_round)), 4), "rounds_ms": [round(v, 4) for v in per_round]}
+    if weighted:                                      # (no host-loop time: the twin's row has the paths' one)
+        res.update(weighted=True, paths_stored=stored)
+    else:
+        res.update(numpy_ms=round(numpy_ms(p0, x_row, d, kind, n_paths, stride, numpy_problems, B), 1), numpy_problems=numpy_problems)
+    res.update({"floor_ms": round((x_bytes + out_bytes) / HBM_BYTES_PER_S * 1e3, 4), "x_gb": round(x_bytes / 1e9, 3),
+                "d2h_mb": round(out_bytes / 1e6, 1)})
+    return res
 
 
 def main():

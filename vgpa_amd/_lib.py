@@ -36,7 +36,7 @@ BWD_IDS = {"none": 0, "psi": 1, "q": 2}
 SYMBOLS = ["vgpa_create", "vgpa_destroy", "vgpa_last_error", "vgpa_abi_version", "vgpa_device_count",
            "vgpa_synchronize", "vgpa_stream", "vgpa_solve_fwd", "vgpa_solve_bwd", "vgpa_energy",
            "vgpa_obs_energy", "vgpa_free_energy", "vgpa_gradient", "vgpa_sweep", "vgpa_energy_parts",
-           "vgpa_fetch", "vgpa_theta_gradient", "vgpa_sample_paths", "vgpa_sweep_dev", "vgpa_free_energy_dev", "vgpa_sweep_enqueue", "vgpa_fetch_f",
+           "vgpa_fetch", "vgpa_theta_gradient", "vgpa_sample_paths", "vgpa_sample_paths_weighted", "vgpa_sweep_dev", "vgpa_free_energy_dev", "vgpa_sweep_enqueue", "vgpa_fetch_f",
            "vgpa_dev_alloc", "vgpa_dev_free", "vgpa_memcpy_h2d", "vgpa_memcpy_d2h",
            "vgpa_profile_begin", "vgpa_profile_end", "vgpa_ld_gemm", "vgpa_ld_stage", "vgpa_gradient_dev", "vgpa_energy_full", "vgpa_set_option", "vgpa_is_streaming", "vgpa_path_info", "vgpa_set_prior_energy",
            "vgpa_set_problem_data", "vgpa_set_problem_params", "vgpa_set_problem_obs_model",
@@ -134,6 +134,7 @@ def load():
     lib.vgpa_fetch.argtypes = [c_void_p, c_int, c_void_p]
     lib.vgpa_theta_gradient.argtypes = [c_void_p, c_void_p]
     lib.vgpa_sample_paths.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_int32, c_int32, c_uint64, c_void_p]
+    lib.vgpa_sample_paths_weighted.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_uint64, c_void_p, c_void_p, c_void_p]
     lib.vgpa_sweep_dev.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vgpa_free_energy_dev.argtypes = [c_void_p, c_void_p, c_void_p]
     lib.vgpa_sweep_enqueue.argtypes = [c_void_p, c_void_p, c_void_p]
@@ -560,6 +561,22 @@ class Context:
         self._check(self._lib.vgpa_sample_paths(self._h, PATH_KINDS[kind], _ptr(xx), _ptr(s0), n_paths, stride,
                                                 int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(out)))
         return out
+
+    def sample_paths_weighted(self, n_paths, seed, stride=1, x=None, x0=None, paths=True):
+        """The posterior paths of sample_paths with the same arguments and, per path, the two sums of its importance weight against the
+        model SDE and the data (vgpa_sample_paths_weighted): (paths (B, n_paths, n_keep, D) or None, logw (B, n_paths, 2): the path term and
+        the observation term, start (B, n_paths, D): every x_0).  paths=False: no path is stored or copied."""
+        n_paths, stride = int(n_paths), int(stride)
+        xx = None if x is None else _c64(x)
+        if xx is not None and xx.size != self.B * self.len_x:
+            raise ValueError(f"x has {xx.size} entries, expected {self.B * self.len_x}")
+        s0 = None if x0 is None else _c64(np.broadcast_to(np.asarray(x0, dtype=np.float64).reshape(-1, self.D), (self.B, self.D)))
+        n_keep = (self.Np - 1) // stride + 1 if stride >= 1 else 0
+        out = np.empty((self.B, max(n_paths, 0), n_keep, self.D)) if paths else None
+        logw, start = np.empty((self.B, max(n_paths, 0), 2)), np.empty((self.B, max(n_paths, 0), self.D))
+        self._check(self._lib.vgpa_sample_paths_weighted(self._h, _ptr(xx), _ptr(s0), n_paths, stride, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                         _ptr(out), _ptr(start), _ptr(logw)))
+        return out, logw, start
 
     def fetch(self, key):
         which = FETCH_IDS[key]

@@ -197,6 +197,15 @@ class ProblemBatch(object):
         xx = None if x is None else self._stack(x)
         return self._context().sample_paths(kind, n_paths, seed, stride=stride, x=xx, x0=x0)
 
+    def importance_weights(self, n_paths, seed, x=None, x0=None, stride=None):
+        """One weights.PathWeights per member: n_paths draws of its posterior process weighted against its own model SDE and data
+        (VarGP.importance_weights), the init term from the member's own prior (mu0, tau0) and (m0, S0); 0 when x0 (B, D) is given.
+        stride=None: no path is stored."""
+        xx = None if x is None else self._stack(x)
+        paths, logw, start = self._context().sample_paths_weighted(n_paths, seed, stride=1 if stride is None else stride, x=xx, x0=x0,
+                                                                   paths=stride is not None)
+        return [v._path_weights(logw[k], start[k], None if paths is None else paths[k], x0 is None) for k, v in enumerate(self.vgps)]
+
     def _theta_rows(self):
         return np.stack([np.atleast_1d(np.asarray(v.model.theta, dtype=float)) for v in self.vgps])
 

@@ -6,6 +6,8 @@
 //   k_sample_l96        5 <= D <= 64, model kind (Lorenz-96): one lane per path, the state in LDS
 // The normals are counter-based (Philox4x32-10 + Box-Muller, vgpa_hip.h): every lane generates exactly the draws it consumes, so no result
 // depends on the launch geometry.
+// k_sample_small<D, true> and k_sample_mfma<NT, true> (vgpa_sample_paths_weighted) walk the same paths and sum, where the path
+// is made, the log-ratio of the model SDE's path density to the posterior process's and the Gaussian log-likelihood of the observations.
 #include "vgpa_internal.h"
 
 namespace vgpa {
@@ -57,7 +59,41 @@ __device__ __forceinline__ void model_drift(int model, const double* th, const d
   }
 }
 
+// the observation row of one problem as a weighted kernel walks it: next = the grid index of the next observation, or -1 behind the last one
+struct ObsCursor {
+  const int64_t* t;
+  int n, cur, next;
+  __device__ __forceinline__ ObsCursor() : t(nullptr), n(0), cur(0), next(-1) {}
+  __device__ __forceinline__ ObsCursor(const SampleArgs& a, uint32_t p)
+      : t(a.obs_t + (size_t)p * a.obs_t_stride), n(a.n_obs_v ? a.n_obs_v[p] : a.n_obs), cur(0) { next = n > 0 ? (int)t[0] : -1; }
+  __device__ __forceinline__ void advance() { next = ++cur < n ? (int)t[cur] : -1; }
+};
+
+// (y_n - x)^T Q (y_n - x) of problem p
 template <int D>
+__device__ __forceinline__ double obs_form(const SampleArgs& a, uint32_t p, int n, const double* x) {
+  const double* y = a.obs_y + (size_t)p * a.obs_y_stride + (size_t)n * D;
+  const double* Q = a.Q + (size_t)p * a.Q_stride;
+  double r[D], s = 0.0;
+#pragma unroll
+  for (int i = 0; i < D; i++) r[i] = y[i] - x[i];
+#pragma unroll
+  for (int i = 0; i < D; i++) {
+    double qr = 0.0;
+#pragma unroll
+    for (int j = 0; j < D; j++) qr += Q[i * D + j] * r[j];
+    s += r[i] * qr;
+  }
+  return s;
+}
+
+__device__ __forceinline__ double obs_constant(const SampleArgs& a, uint32_t p) {
+  return a.obs_const_scale * (a.obs_const_v ? a.obs_const_v[p] : a.obs_const);
+}
+
+// W: the weighted instantiation (posterior kind, diagonal R): both drifts at x_{k-1}, d = g - f, and per step
+// -sum_i d_i (eta_i + dt d_i / 2) / Sigma_ii with 1 / Sigma_ii = dt / R_ii^2; the observation term at the lane's own problem's times
+template <int D, bool W>
 __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
   const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (gid >= (size_t)a.batch * a.n_paths) return;
@@ -93,16 +129,28 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
       x[i] = m0[i] + s;
     }
   }
-  double* o = a.out + gid * (size_t)a.n_keep * D;
+  const bool store = !W || a.out != nullptr;
+  double* o = store ? a.out + gid * (size_t)a.n_keep * D : nullptr;
+  if (store) {
 #pragma unroll
-  for (int i = 0; i < D; i++) o[i] = x[i];
-  o += D;
+    for (int i = 0; i < D; i++) o[i] = x[i];
+    o += D;
+  }
+  double isg[D], pw = 0.0, ow = 0.0;
+  ObsCursor oc;
+  if constexpr (W) {
+    oc = ObsCursor(a, p);
+#pragma unroll
+    for (int i = 0; i < D; i++) { isg[i] = a.dt / (R[i * D + i] * R[i * D + i]); a.start[gid * D + i] = x[i]; }
+    if (oc.next == 0) { ow += obs_form<D>(a, p, oc.cur, x); oc.advance(); }
+  }
   const double* A = a.A + (size_t)p * a.stride_x;
   const double* bv = a.b + (size_t)p * a.stride_x;
   int until = a.stride, slot = 0;
   for (int k = 1; k < a.Np; k++) {
-    double f[D];
-    if (a.kind == VGPA_PATHS_POSTERIOR) {
+    double f[D], fm[D];
+    if constexpr (W) model_drift<D>(a.model, th, x, fm);
+    if (W || a.kind == VGPA_PATHS_POSTERIOR) {
       const double* Ak = A + (size_t)(k - 1) * D * D;
       const double* bk = bv + (size_t)(k - 1) * D;
 #pragma unroll
@@ -122,9 +170,13 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
       double s = 0.0;
 #pragma unroll
       for (int j = 0; j <= i; j++) s += R[i * D + j] * z[j];
+      if constexpr (W) { const double d = f[i] - fm[i]; pw -= isg[i] * d * (s + 0.5 * a.dt * d); }
       x[i] = (x[i] + a.dt * f[i]) + s;
     }
-    if (--until == 0) {
+    if constexpr (W) {
+      if (k == oc.next) { ow += obs_form<D>(a, p, oc.cur, x); oc.advance(); }
+    }
+    if (store && --until == 0) {
       until = a.stride;
 #pragma unroll
       for (int i = 0; i < D; i++) sg[(slot * D + i) * 256] = x[i];
@@ -137,6 +189,7 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
     }
   }
   for (int e = 0; e < slot * D; e++) o[e] = sg[e * 256];
+  if constexpr (W) { a.logw[2 * gid] = pw; a.logw[2 * gid + 1] = -0.5 * ow - obs_constant(a, p); }
 }
 
 // ---- 5 <= D <= 64, posterior kind ---------------------------------------------------------------------------------------------------
@@ -171,13 +224,17 @@ __device__ __forceinline__ void normals_c(uint32_t k0, uint32_t k1, uint32_t k, 
   }
 }
 
-template <int NT>
+// W: the weighted instantiation (Lorenz-96, diagonal R).  At step k the lane holds rows mt * 16 + q + 4 r of x_{k-1}, of g = bs - acc and of
+// eta = nz; the model drift f_i reads rows (i + 1) mod D, (i - 2) mod D, (i - 1) mod D of the path's column of Xs.  Each lane sums its rows over
+// time; the four q-lanes of a path are added once at the end.  The observation term is evaluated from Xs at the problem's observation times,
+// which a workgroup walks with one cursor.
+template <int NT, bool W>
 __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
   using Sh = MfmaShape<NT>;
   constexpr int LDA = Sh::LDA, MT = Sh::MT, KT = Sh::KT, NPF = Sh::NPF;
   extern __shared__ double lds[];
   const int D = a.D, DD = D * D, tid = threadIdx.x, w = tid >> 6, lane = tid & 63, j16 = lane & 15, q = lane >> 4;
-  const bool dense = !a.R_diag;
+  const bool dense = !W && !a.R_diag;      // (the weighted instantiation is launched with diagonal factors only)
   double* As = lds;
   double* bs = As + NT * LDA;
   double* Rs = bs + NT;
@@ -236,25 +293,62 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
   // A kept point leaves from Xs, where the wave's 16 states lie as [row][path]: element e = lane + 64 i of the 16 rows of `out` (path e / D,
   // component e % D), so that one store instruction writes runs of D consecutive doubles instead of 4 per path
   const uint32_t path0 = blockIdx.y * 64 + w * 16;
-  double* o = a.out + ((size_t)p * a.n_paths + path0) * (size_t)a.n_keep * D;
+  const bool store = !W || a.out != nullptr;
+  double* o = store ? a.out + ((size_t)p * a.n_paths + path0) * (size_t)a.n_keep * D : nullptr;
   const size_t row_len = (size_t)a.n_keep * D;
-  auto keep = [&]() {
+  auto put = [&](double* dst, size_t len) {
 #pragma unroll
     for (int i = 0; i < NT / 4; i++) {
       const int e = lane + 64 * i;
       if (e < 16 * D) {
         const int pl = e / D, cmp = e - pl * D;
-        if (path0 + pl < (uint32_t)a.n_paths) o[pl * row_len + cmp] = Xs[cmp * 16 + pl];
+        if (path0 + pl < (uint32_t)a.n_paths) dst[pl * len + cmp] = Xs[cmp * 16 + pl];
       }
     }
-    o += D;
   };
+  auto keep = [&]() {
+    if (store) { put(o, row_len); o += D; }
+  };
+  // weighted: 1 / Sigma_ii of the lane's rows, the two sums, theta, the observation cursor
+  double isg[W ? MT : 1][4], pw = 0.0, ow = 0.0, th = 0.0;
+  ObsCursor oc;
+  if constexpr (W) oc = ObsCursor(a, p);
+  auto observe = [&]() {      // x_k is in x and, whole, in the path's column of Xs
+    const double* y = a.obs_y + (size_t)p * a.obs_y_stride + (size_t)oc.cur * D;
+    const double* Qp = a.Q + (size_t)p * a.Q_stride;
+#pragma unroll
+    for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const int row = mt * 16 + q + 4 * r;
+        if (row < D) {
+          const double ri = y[row] - x[mt][r];
+          double qr = 0.0;
+          if (a.Q_diag) qr = Qp[row * D + row] * ri;
+          else
+            for (int c = 0; c < D; c++) qr += Qp[row * D + c] * (y[c] - Xs[c * 16 + j16]);
+          ow += ri * qr;
+        }
+      }
+    oc.advance();
+  };
+  if constexpr (W) {
+    th = a.theta_v ? a.theta_v[(size_t)p * kMaxTheta] : a.theta[0];
+#pragma unroll
+    for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) isg[mt][r] = mt * 16 + q + 4 * r < D ? a.dt / (rd[mt][r] * rd[mt][r]) : 0.0;
+  }
 #pragma unroll
   for (int mt = 0; mt < MT; mt++)
 #pragma unroll
     for (int r = 0; r < 4; r++) Xs[(mt * 16 + q + 4 * r) * 16 + j16] = x[mt][r];
   __syncthreads();
   keep();
+  if constexpr (W) {
+    put(a.start + ((size_t)p * a.n_paths + path0) * D, (size_t)D);
+    if (oc.next == 0) observe();
+  }
 
   int until = a.stride;
   for (int k = 1; k < a.Np; k++) {
@@ -278,6 +372,10 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
         for (int r = 0; r < 4; r++) Zs[(mt * 16 + q + 4 * r) * 16 + j16] = z[mt][r];
       __syncthreads();
     }
+    // weighted: the rows of x_{k-1} that the circular drift reaches by wrapping around -- 0, D - 1, D - 2 -- once per step
+    const double* xq = Xs + q * 16 + j16;
+    double w0 = 0.0, wl1 = 0.0, wl2 = 0.0;
+    if constexpr (W) { w0 = Xs[j16]; wl1 = Xs[(D - 1) * 16 + j16]; wl2 = Xs[(D - 2) * 16 + j16]; }
 #pragma unroll
     for (int mt = 0; mt < MT; mt++) {
       d4 acc = {0.0, 0.0, 0.0, 0.0};
@@ -290,6 +388,26 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
         const double* rr = Rs + (mt * 16 + j16) * LDA + q;
 #pragma unroll
         for (int kk = 0; kk < KT; kk++) nz = __builtin_amdgcn_mfma_f64_16x16x4f64(rr[kk * 4], Zs[(kk * 4 + q) * 16 + j16], nz, 0, 0, 0);
+      }
+      if constexpr (W) {
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+          const int row = mt * 16 + q + 4 * r;
+          if (row < D) {
+            // the neighbours at fixed offsets from the lane's own row (one address register); only rows 0, 1 and D - 1 wrap
+            const double* xr = xq + (mt * 16 + 4 * r) * 16;
+            const double xu = row + 1 < D ? xr[16] : w0;
+            double xd1 = wl1, xd2 = wl2;
+            if (mt > 0 || r > 0) { xd1 = xr[-16]; xd2 = xr[-32]; }
+            else {
+              if (q >= 1) xd1 = xr[-16];
+              if (q >= 2) xd2 = xr[-32]; else if (q == 1) xd2 = wl1;
+            }
+            const double f = (xu - xd2) * xd1 - x[mt][r] + th;
+            const double d = (bs[row] - acc[r]) - f;
+            pw -= isg[mt][r] * d * (nz[r] + 0.5 * a.dt * d);
+          }
+        }
       }
 #pragma unroll
       for (int r = 0; r < 4; r++) x[mt][r] = (x[mt][r] + a.dt * (bs[mt * 16 + q + 4 * r] - acc[r])) + nz[r];
@@ -306,6 +424,17 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
       for (int r = 0; r < 4; r++) Xs[(mt * 16 + q + 4 * r) * 16 + j16] = x[mt][r];
     __syncthreads();
     if (--until == 0) { until = a.stride; keep(); }
+    if constexpr (W) {
+      if (k == oc.next) observe();
+    }
+  }
+  if constexpr (W) {
+    pw += __shfl_xor(pw, 16); pw += __shfl_xor(pw, 32);
+    ow += __shfl_xor(ow, 16); ow += __shfl_xor(ow, 32);
+    if (q == 0 && path < (uint32_t)a.n_paths) {
+      double* lw = a.logw + 2 * ((size_t)p * a.n_paths + path);
+      lw[0] = pw; lw[1] = -0.5 * ow - obs_constant(a, p);
+    }
   }
 }
 
@@ -377,13 +506,32 @@ __global__ __launch_bounds__(64) void k_sample_l96(SampleArgs a) {
   }
 }
 
-template <int NT>
+template <int NT, bool W>
 hipError_t launch_mfma(const SampleArgs& a, hipStream_t st) {
   const size_t lds = MfmaShape<NT>::lds_doubles(!a.R_diag) * sizeof(double);
-  if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k_sample_mfma<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k_sample_mfma<NT, W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if ((a.n_paths + 63) / 64 > 65535) return hipErrorInvalidValue;      // (grid.y)
-  hipLaunchKernelGGL(k_sample_mfma<NT>, dim3(a.batch, (a.n_paths + 63) / 64), dim3(256), lds, st, a);
+  hipLaunchKernelGGL((k_sample_mfma<NT, W>), dim3(a.batch, (a.n_paths + 63) / 64), dim3(256), lds, st, a);
   return hipGetLastError();
+}
+
+template <bool W>
+hipError_t launch_posterior(const SampleArgs& a, hipStream_t st) {
+  const size_t lanes = (size_t)a.batch * a.n_paths;
+  if (a.D <= kMaxLaneD) {
+    const dim3 grid((unsigned)((lanes + 255) / 256)), block(256);
+    switch (a.D) {
+      case 1: hipLaunchKernelGGL((k_sample_small<1, W>), grid, block, 0, st, a); break;
+      case 2: hipLaunchKernelGGL((k_sample_small<2, W>), grid, block, 0, st, a); break;
+      case 3: hipLaunchKernelGGL((k_sample_small<3, W>), grid, block, 0, st, a); break;
+      default: hipLaunchKernelGGL((k_sample_small<4, W>), grid, block, 0, st, a); break;
+    }
+    return hipGetLastError();
+  }
+  if (a.D <= 16) return launch_mfma<16, W>(a, st);
+  if (a.D <= 32) return launch_mfma<32, W>(a, st);
+  if (a.D <= 48) return launch_mfma<48, W>(a, st);
+  return launch_mfma<64, W>(a, st);
 }
 
 }  // namespace
@@ -391,26 +539,16 @@ hipError_t launch_mfma(const SampleArgs& a, hipStream_t st) {
 hipError_t launch_sample_paths(const SampleArgs& a, hipStream_t st) {
   const size_t lanes = (size_t)a.batch * a.n_paths;
   if (a.D < 1 || a.D > kMaxSmallD || a.n_paths < 1 || a.stride < 1) return hipErrorInvalidValue;
-  if (a.D <= kMaxLaneD) {
-    const dim3 grid((unsigned)((lanes + 255) / 256)), block(256);
-    switch (a.D) {
-      case 1: hipLaunchKernelGGL(k_sample_small<1>, grid, block, 0, st, a); break;
-      case 2: hipLaunchKernelGGL(k_sample_small<2>, grid, block, 0, st, a); break;
-      case 3: hipLaunchKernelGGL(k_sample_small<3>, grid, block, 0, st, a); break;
-      default: hipLaunchKernelGGL(k_sample_small<4>, grid, block, 0, st, a); break;
-    }
-    return hipGetLastError();
+  if (a.logw) {      // the weighted instantiations: the posterior kind against the model's drift, diagonal factors; above D = 4 the model is Lorenz-96
+    if (a.kind != VGPA_PATHS_POSTERIOR || !a.R_diag || !a.start || (a.D > kMaxLaneD && a.model != VGPA_MODEL_L96)) return hipErrorInvalidValue;
+    if (a.model != VGPA_MODEL_OU && a.model != VGPA_MODEL_DW && a.model != VGPA_MODEL_L63 && a.model != VGPA_MODEL_L96) return hipErrorInvalidValue;
+    return launch_posterior<true>(a, st);
   }
-  if (a.kind == VGPA_PATHS_MODEL) {
-    if (a.model != VGPA_MODEL_L96) return hipErrorInvalidValue;
-    const size_t lds = (size_t)a.D * 64 * sizeof(double) * ((!a.R_diag || !a.x0) ? 2 : 1);
-    hipLaunchKernelGGL(k_sample_l96, dim3((unsigned)((lanes + 63) / 64)), dim3(64), lds, st, a);
-    return hipGetLastError();
-  }
-  if (a.D <= 16) return launch_mfma<16>(a, st);
-  if (a.D <= 32) return launch_mfma<32>(a, st);
-  if (a.D <= 48) return launch_mfma<48>(a, st);
-  return launch_mfma<64>(a, st);
+  if (a.D <= kMaxLaneD || a.kind == VGPA_PATHS_POSTERIOR) return launch_posterior<false>(a, st);
+  if (a.model != VGPA_MODEL_L96) return hipErrorInvalidValue;
+  const size_t lds = (size_t)a.D * 64 * sizeof(double) * ((!a.R_diag || !a.x0) ? 2 : 1);
+  hipLaunchKernelGGL(k_sample_l96, dim3((unsigned)((lanes + 63) / 64)), dim3(64), lds, st, a);
+  return hipGetLastError();
 }
 
 }  // namespace vgpa

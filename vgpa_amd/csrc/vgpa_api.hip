@@ -162,6 +162,8 @@ struct vgpa_ctx {
   // vgpa_sample_paths: the result, the noise factors R, the factors of S0 and the given starts; grown on demand, freed in vgpa_destroy
   double *d_sp_out = nullptr, *d_sp_R = nullptr, *d_sp_L0 = nullptr, *d_sp_x0 = nullptr;
   size_t sp_out_n = 0, sp_R_n = 0, sp_L0_n = 0, sp_x0_n = 0;
+  double *d_sp_logw = nullptr, *d_sp_start = nullptr;      // vgpa_sample_paths_weighted: the two sums and x_0 of every path
+  size_t sp_logw_n = 0, sp_start_n = 0;
   // profiling
   bool prof = false;
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -934,7 +936,7 @@ void vgpa_destroy(vgpa_ctx* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   for (void* p : c->allocs) (void)hipFree(p);
   for (void* p : c->user_allocs) (void)hipFree(p);
-  for (double* p : {c->d_sp_out, c->d_sp_R, c->d_sp_L0, c->d_sp_x0}) if (p) (void)hipFree(p);
+  for (double* p : {c->d_sp_out, c->d_sp_R, c->d_sp_L0, c->d_sp_x0, c->d_sp_logw, c->d_sp_start}) if (p) (void)hipFree(p);
   if (c->h_coef) (void)hipHostFree(c->h_coef);
   if (c->h_fs) (void)hipHostFree(c->h_fs);
   for (auto& e : c->ev_coef) if (e) (void)hipEventDestroy(e);
@@ -1456,15 +1458,11 @@ static int factor_rows(vgpa_ctx* c, const double* src, int n, double scale, cons
   return VGPA_OK;
 }
 
-// Euler-Maruyama paths of the posterior process or of the model SDE (see vgpa_hip.h).  Reads x and the inputs in force; of the
-// cached state nothing is written.
-int vgpa_sample_paths(vgpa_ctx* c, int kind, const double* x, const double* x0, int32_t n_paths, int32_t stride, uint64_t seed, double* out) {
-  if (!c) return VGPA_ERR_ARG;
-  if (!out) return fail(c, VGPA_ERR_ARG, "null argument");
-  if (kind != VGPA_PATHS_POSTERIOR && kind != VGPA_PATHS_MODEL) return fail(c, VGPA_ERR_ARG, "unknown kind of paths -> %d", kind);
-  if (n_paths < 1 || stride < 1) return fail(c, VGPA_ERR_ARG, "n_paths and stride must be at least 1 (n_paths = %d, stride = %d)", n_paths, stride);
-  if (kind == VGPA_PATHS_MODEL && x) return fail(c, VGPA_ERR_ARG, "paths of the model SDE take no x");
-  if (kind == VGPA_PATHS_MODEL && c->cfg.model == VGPA_MODEL_NONE) return fail(c, VGPA_ERR_ARG, "context has no stochastic model (ODE-only): no model SDE to sample");
+// Euler-Maruyama paths of the posterior process or of the model SDE (see vgpa_hip.h), and -- logw set: vgpa_sample_paths_weighted,
+// DESIGN.md s.4.9 -- the weights of the posterior paths against the model SDE and the data, with `out` optional and every x_0 to `start`.  Reads x
+// and the inputs in force; of the cached state nothing is written.  The arguments have been checked by the two entry points.
+static int sample_paths(vgpa_ctx* c, int kind, const double* x, const double* x0, int32_t n_paths, int32_t stride, uint64_t seed, double* out,
+                        double* start, double* logw) {
   if (c->D > kMaxSmallD) return fail(c, VGPA_ERR_UNSUPPORTED, "sample paths are built for D <= %d (D = %d)", kMaxSmallD, c->D);
   if (kind == VGPA_PATHS_POSTERIOR && !x && !c->res.cached)
     return fail(c, VGPA_ERR_STATE, "no cached state: sample_paths without x needs the state cached by a previous free_energy / sweep");
@@ -1481,6 +1479,7 @@ int vgpa_sample_paths(vgpa_ctx* c, int kind, const double* x, const double* x0, 
   if ((rc = factor_rows(c, own_Sigma ? c->in.h_Sigma.data() : c->h_sigma.data(), own_Sigma ? B : 1, c->cfg.dt, "noise matrix times dt",
                         &c->d_sp_R, &c->sp_R_n, &R, &diag))) return rc;
   a.R = R.rows; a.R_stride = R.stride; a.R_diag = diag ? 1 : 0;
+  if (logw && !diag) return fail(c, VGPA_ERR_UNSUPPORTED, "the weights of sampled paths are built for a diagonal Sigma (a dense Sigma is in force)");
   if (x0) {
     if ((rc = grow(c, &c->d_sp_x0, &c->sp_x0_n, (size_t)B * D))) return rc;
     if ((rc = upload(c, c->d_sp_x0, x0, (size_t)B * D))) return rc;
@@ -1500,13 +1499,48 @@ int vgpa_sample_paths(vgpa_ctx* c, int kind, const double* x, const double* x0, 
     copy_theta(c, a.theta);
     a.theta_v = c->in.theta.rows;
   }
-  const size_t n_out = (size_t)B * n_paths * a.n_keep * D;
-  if ((rc = grow(c, &c->d_sp_out, &c->sp_out_n, n_out))) return rc;
-  a.out = c->d_sp_out;
+  const size_t n_out = (size_t)B * n_paths * a.n_keep * D, n_start = (size_t)B * n_paths * D, n_logw = (size_t)B * n_paths * 2;
+  if (out) {
+    if ((rc = grow(c, &c->d_sp_out, &c->sp_out_n, n_out))) return rc;
+    a.out = c->d_sp_out;
+  }
+  if (logw) {      // both drifts, and the observation model in force as obs_args hands it to the E_obs kernels
+    if ((rc = grow(c, &c->d_sp_logw, &c->sp_logw_n, n_logw)) || (rc = grow(c, &c->d_sp_start, &c->sp_start_n, n_start))) return rc;
+    a.logw = c->d_sp_logw; a.start = c->d_sp_start;
+    copy_theta(c, a.theta);
+    a.theta_v = c->in.theta.rows;
+    const ObsArgs o = obs_args(c);
+    a.obs_t = o.obs_t; a.obs_t_stride = o.obs_t_stride; a.obs_y = o.obs_y; a.obs_y_stride = o.obs_y_stride;
+    a.Q = o.Q; a.Q_stride = o.Q_stride; a.Q_diag = o.diag; a.n_obs = o.n_obs; a.n_obs_v = o.n_obs_v;
+    a.obs_const = o.obs_const; a.obs_const_v = o.obs_const_v; a.obs_const_scale = c->single ? 1.0 : 0.5;
+  }
   LAUNCH_TRY(c, "sample paths launch", launch_sample_paths(a, c->stream));
-  if ((rc = download(c, out, c->d_sp_out, n_out))) return rc;
+  if (out && (rc = download(c, out, c->d_sp_out, n_out))) return rc;
+  if (logw && (rc = download(c, logw, c->d_sp_logw, n_logw))) return rc;
+  if (logw && start && (rc = download(c, start, c->d_sp_start, n_start))) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return VGPA_OK;
+}
+
+int vgpa_sample_paths(vgpa_ctx* c, int kind, const double* x, const double* x0, int32_t n_paths, int32_t stride, uint64_t seed, double* out) {
+  if (!c) return VGPA_ERR_ARG;
+  if (!out) return fail(c, VGPA_ERR_ARG, "null argument");
+  if (kind != VGPA_PATHS_POSTERIOR && kind != VGPA_PATHS_MODEL) return fail(c, VGPA_ERR_ARG, "unknown kind of paths -> %d", kind);
+  if (n_paths < 1 || stride < 1) return fail(c, VGPA_ERR_ARG, "n_paths and stride must be at least 1 (n_paths = %d, stride = %d)", n_paths, stride);
+  if (kind == VGPA_PATHS_MODEL && x) return fail(c, VGPA_ERR_ARG, "paths of the model SDE take no x");
+  if (kind == VGPA_PATHS_MODEL && c->cfg.model == VGPA_MODEL_NONE) return fail(c, VGPA_ERR_ARG, "context has no stochastic model (ODE-only): no model SDE to sample");
+  return sample_paths(c, kind, x, x0, n_paths, stride, seed, out, nullptr, nullptr);
+}
+
+// Posterior paths with their importance weights against the model SDE and the data (see vgpa_hip.h)
+int vgpa_sample_paths_weighted(vgpa_ctx* c, const double* x, const double* x0, int32_t n_paths, int32_t stride, uint64_t seed, double* out,
+                               double* start, double* logw) {
+  if (!c) return VGPA_ERR_ARG;
+  if (!logw) return fail(c, VGPA_ERR_ARG, "null argument");
+  if (n_paths < 1 || stride < 1) return fail(c, VGPA_ERR_ARG, "n_paths and stride must be at least 1 (n_paths = %d, stride = %d)", n_paths, stride);
+  if (c->cfg.model == VGPA_MODEL_NONE) return fail(c, VGPA_ERR_ARG, "context has no stochastic model: no model SDE to weigh the paths against");
+  if (!c->full) return fail(c, VGPA_ERR_STATE, "context was created without m0/s0/observations (ODE-only)");
+  return sample_paths(c, VGPA_PATHS_POSTERIOR, x, x0, n_paths, stride, seed, out, start, logw);
 }
 
 int vgpa_fetch(vgpa_ctx* c, int which, double* out) {

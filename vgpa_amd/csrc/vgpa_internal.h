@@ -240,6 +240,21 @@ struct SampleArgs {
   const double* L0;         // [D][D] lower factor of S0, or [B][D][D] with L0_stride = D*D
   size_t m0_stride, L0_stride;
   double* out;              // [B][n_paths][n_keep][D]
+  // importance weights of the posterior paths against the model SDE (vgpa_sample_paths_weighted), last so that the offsets
+  // above stay where they were.  logw set: the weighted instantiations run (posterior kind, diagonal R, theta / theta_v set), `out` may be
+  // nullptr (no path is stored), and every path's x_0 goes to `start`
+  double* logw;             // [B][n_paths][2]: the path term, the observation term; or nullptr
+  double* start;            // [B][n_paths][D]
+  const int64_t* obs_t;     // [M] grid indices, strictly increasing ([B][M] with obs_t_stride = M), as ObsArgs has them
+  const double* obs_y;      // [M][D] ([B][M][D] with obs_y_stride = M*D)
+  const double* Q;          // [D][D] H R^-1 H^T ([B][D][D] with Q_stride = D*D); 1-D: 1 / r
+  size_t obs_t_stride, obs_y_stride, Q_stride;
+  int Q_diag;               // every Q is diagonal
+  int n_obs;                // observations of a problem ...
+  const int32_t* n_obs_v;   // ... [B] instead of n_obs, or nullptr
+  double obs_const;         // the additive constant of E_obs as ObsArgs has it ...
+  const double* obs_const_v;   // ... [B] instead of obs_const, or nullptr
+  double obs_const_scale;   // ... and the factor E_obs gives it: 1/2 (n-D), 1 (1-D models, whose constant is halved already)
 };
 hipError_t launch_sample_paths(const SampleArgs& a, hipStream_t st);
 

@@ -157,6 +157,27 @@ class VarGP(object):
             out = out[..., 0]
         return out[0] if self.batch == 1 else out
 
+    def _path_weights(self, logw, start, paths, drawn):
+        """One problem's record from its rows of Context.sample_paths_weighted: logw (n, 2), start (n, D), paths (n, n_keep, D) or None"""
+        from .weights import PathWeights, init_term
+        init = np.zeros(logw.shape[0])
+        if drawn:
+            init = init_term(start, self.kl0.mu0, self.kl0.tau0, self.output["m0"], self.output["s0"])
+        if paths is not None and self.model.single_dim:
+            paths = paths[..., 0]
+        return PathWeights(init, logw[:, 0], logw[:, 1], paths)
+
+    def importance_weights(self, n_paths, seed, x=None, x0=None, stride=None):
+        """n_paths draws of the posterior process (sample_paths with the same arguments) weighted against the model SDE and the data: a
+        weights.PathWeights (with batch > 1 a list, one per problem).  log w = init + path + obs; init = log N(x_0; mu0, tau0) -
+        log N(x_0; m0, S0) with the prior of kl0, 0 when x0 is given.  stride=None: no path is stored -- the evidence-estimation mode, many
+        paths and a tiny result; else the record carries the kept grid points.  x=None: the (A_t, b_t) of the last free_energy."""
+        xx = None if x is None else np.asarray(x, dtype=float)
+        paths, logw, start = self._context().sample_paths_weighted(n_paths, seed, stride=1 if stride is None else stride, x=xx, x0=x0,
+                                                                   paths=stride is not None)
+        out = [self._path_weights(logw[k], start[k], None if paths is None else paths[k], x0 is None) for k in range(logw.shape[0])]
+        return out[0] if self.batch == 1 else out
+
     def fit_theta(self, x0, rounds, options=None):
         """Variational EM for the drift parameters (ProblemBatch.fit_theta on a batch of one): (x, F, theta, trace), theta in the
         shape of model.theta, trace["F"] of shape (rounds, 2, 1)."""
