@@ -249,6 +249,37 @@ int vgpa_sample_paths(vgpa_ctx* ctx, int kind, const double* x_or_null, const do
 int vgpa_sample_paths_weighted(vgpa_ctx* ctx, const double* x_or_null, const double* x0_or_null, int32_t n_paths, int32_t stride,
                                uint64_t seed, double* out_or_null, double* start_or_null, double* logw);
 
+/* A guided particle filter with the posterior process as its proposal: the walk of vgpa_sample_paths_weighted with the
+ * weights taken in observation by observation and the particle cloud resampled whenever its effective sample size drops.  Per problem p, n =
+ * n_paths particles in slots i = 0 .. n-1, each a state x_i and an unnormalised log-weight lw_i:
+ *   start    x_i = x0[p], or m0_p + chol_lower(S0_p) xi_0 with the sampler's counter (0, i, p, j);  lw_i = init_i - c_p, c_p the additive
+ *            constant of the obs term above, init_i = log N(x_i; mu0, tau0) - log N(x_i; m0, S0) when a prior is passed and the start is
+ *            drawn, else 0
+ *   steps    k = 1 .. Np-1 as in vgpa_sample_paths_weighted: the same recursion, slot i drawing with counter (k, i, p, j) whatever its
+ *            ancestry, the step's path increment added to lw_i
+ *   at every observation of the problem (grid index 0 applies to x_0): -(y - x_i)^T Q (y - x_i) / 2 is added to lw_i; then
+ *            w_i = exp(lw_i - max lw), S = sum w_i, ESS = S^2 / sum w_i^2, and the cloud is resampled iff ESS < ess_fraction n and k < Np - 1
+ *   systematic resampling: U = the first uniform of Philox counter (k, 0, p, 0xffffffff) under the seed's key (the normals use j < 32),
+ *            u_i = (U + i) / n S, cum = the inclusive prefix sums of w in slot order, anc_i = min(#{m: cum_m <= u_i}, n - 1);
+ *            x_i <- x_{anc_i}, every lw_i <- max lw + log S - log n
+ * The mean weight is preserved, so logsumexp(lw) - log n of the final lw estimates log p(y | theta, Sigma) with or without resampling.
+ * A problem's schedule depends on its own observation times, count, R, H, theta and Sigma (the rows in force are honoured as above); its
+ * result does not change with the batch around it.  It does change with n_paths from the first resampling on.
+ *   x_or_null, x0_or_null, n_paths, seed: as in vgpa_sample_paths_weighted; with x NULL the cached state is read and not written
+ *   ess_fraction      in [0, 1]; 0: never resample (the weights of vgpa_sample_paths_weighted)
+ *   prior_mu_or_null  host, [batch][D], and prior_tau_or_null, host, [batch][D][D]: both or neither
+ *   logw    host, [batch][n_paths]: the final lw;  state  host, [batch][n_paths][D]: the final particles
+ *   histories over the observation counter j < M (M the context's n_obs), each may be NULL:
+ *   ess_or_null [batch][M];  resampled_or_null [batch][M] int32;  ancestors_or_null [batch][M][n_paths] int32 (the identity where the cloud
+ *   was carried on);  clouds_or_null [batch][M][n_paths][D]: the states at observation j before the resampling decision.
+ *   Rows j at or beyond a problem's own count: ess 0, flag 0, ancestors -1, clouds untouched.
+ * VGPA_ERR_ARG: a null logw or state, n_paths < 1, ess_fraction outside [0, 1] or NaN, one prior pointer without the other, VGPA_MODEL_NONE;
+ * VGPA_ERR_STATE: an ODE-only context, no cached state with x NULL, a drawn start without m0 / s0; VGPA_ERR_UNSUPPORTED: D > 64, a dense
+ * Sigma in force; VGPA_ERR_NOT_PD: as in vgpa_sample_paths, and a prior covariance without a Cholesky factor. */
+int vgpa_particle_filter(vgpa_ctx* ctx, const double* x_or_null, const double* x0_or_null, int32_t n_paths, uint64_t seed, double ess_fraction,
+                         const double* prior_mu_or_null, const double* prior_tau_or_null, double* logw, double* state, double* ess_or_null,
+                         int32_t* resampled_or_null, int32_t* ancestors_or_null, double* clouds_or_null);
+
 /* device-pointer variants (x, g on the context's device; f written to HOST after a sync) ------ */
 int vgpa_sweep_dev(vgpa_ctx* ctx, const double* x_dev, double* f_host, double* g_dev);
 int vgpa_free_energy_dev(vgpa_ctx* ctx, const double* x_dev, double* f_host);

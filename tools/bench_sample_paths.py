@@ -1,13 +1,17 @@
 """
-Time of Context.sample_paths (vgpa_sample_paths) and Context.sample_paths_weighted (vgpa_sample_paths_weighted) on their jobs, one JSON line.
+Time of Context.sample_paths (vgpa_sample_paths), Context.sample_paths_weighted (vgpa_sample_paths_weighted) and Context.particle_filter
+(vgpa_particle_filter) on their jobs, one JSON line.
 
-    python tools/bench_sample_paths.py [--rounds 3] [--calls 5] [--jobs a,b,c,aw,aw0,bw,bw0]
+    python tools/bench_sample_paths.py [--rounds 3] [--calls 5] [--jobs a,b,c,aw,aw0,bw,bw0,af64_0,af64_5,af1024_0,af1024_5,bf64_0,...]
 
   a   posterior kind, Lorenz-96, D = 40, Np = 1001, B = 512:   64 paths per problem, stride 100
   b   posterior kind, Lorenz-63, Np = 1001, B = 65536:          1 path per problem,  stride 100
   c   model kind on the context of b:                           1 path per problem,  stride 1
   aw, bw     the weighted twins of a and b: the same paths stored, and the two sums and x_0 of every path
   aw0, bw0   ... weights only: no path is stored or copied
+  af<n>_<f>, bf<n>_<f>   the particle filter on the contexts of a and b: n = 64 or 1024 particles per problem, ess_fraction f = 0 (never
+             resampled: the weights of aw0 / bw0, cut at the observations) or 5 (0.5), histories off; --filter-problems caps B of the
+             b context's filter jobs (1024 particles on 65536 problems are 1.6 GB of final states to copy)
 
 The posterior jobs read the x a free_energy_dev left cached (x=None: nothing is uploaded); every job draws its start from (m0, S0).  A call
 is timed with a pair of device events on the context's stream around it -- the host work of the call (the Cholesky factors), the kernel and
@@ -35,6 +39,7 @@ for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")):
 HBM_BYTES_PER_S = 8.0e12
 JOBS = {"a": ("L96", 40, 512, "posterior", 64, 100), "b": ("L63", 3, 65536, "posterior", 1, 100), "c": ("L63", 3, 65536, "model", 1, 1)}
 WEIGHTED = {"aw": ("a", True), "aw0": ("a", False), "bw": ("b", True), "bw0": ("b", False)}      # job -> (its unweighted twin, paths stored)
+FILTER = {f"{t}f{n}_{f}": (t, n, 0.1 * f) for t in "ab" for n in (64, 1024) for f in (0, 5)}      # job -> (context of, particles, ess_fraction)
 N_PTS, DT = 1001, 0.01
 
 
@@ -63,11 +68,15 @@ def numpy_ms(p0, x_row, d, kind, n_paths, stride, n_problems, B):
     return (time.perf_counter() - t0) * 1e3 / n_problems * B
 
 
-def run(job, rounds, calls, numpy_problems, cache):
+def run(job, rounds, calls, numpy_problems, cache, filter_problems=0):
     from bench_problem_batch import StreamTimer, make_contexts
     twin, stored = WEIGHTED.get(job, (job, True))
     weighted = job in WEIGHTED
+    if job in FILTER:
+        twin = FILTER[job][0]
     name, d, B, kind, n_paths, stride = JOBS[twin]
+    if job in FILTER and twin == "b" and filter_problems:
+        B = min(B, filter_problems)
     if (name, B) not in cache:                        # (b and c share a context)
         from helpers import SEED, build_problem
         ctxs, x0 = make_contexts(name, d, N_PTS, DT, B, modes=("shared",))
@@ -82,6 +91,17 @@ def run(job, rounds, calls, numpy_problems, cache):
     c, xb, x_row, p0, tm = cache[(name, B)]
     len_x = N_PTS * d * (d + 1)
     n_keep = (N_PTS - 1) // stride + 1
+    if job in FILTER:
+        _, n_paths, frac = FILTER[job]
+        call = lambda: c.particle_filter(n_paths, 1, ess_fraction=frac)      # noqa: E731
+        res0 = call()                                 # warm-up (first-use allocations)
+        assert res0["log_w"].shape == (B, n_paths) and np.all(np.isfinite(res0["log_w"])) and np.all(np.isfinite(res0["state"]))
+        resampled = float(res0["resampled"].mean())
+        per_round = [float(np.median([tm.ms(call) for _ in range(calls)])) for _ in range(rounds)]
+        return {"job": job, "model": name, "D": d, "Np": N_PTS, "B": B, "kind": "filter", "n_paths": n_paths, "ess_fraction": frac,
+                "ms_per_call": round(float(np.median(per_round)), 4), "rounds_ms": [round(v, 4) for v in per_round],
+                "observations": int(c.n_obs), "resampled_share": round(resampled, 3),
+                "d2h_mb": round(8.0 * B * n_paths * (1 + d) / 1e6, 1)}
     if weighted:
         call = lambda: c.sample_paths_weighted(n_paths, 1, stride=stride, paths=stored)      # noqa: E731
         out, logw, start = call()                     # warm-up (first-use allocations)
@@ -114,11 +134,12 @@ def main():
     ap.add_argument("--calls", type=int, default=5)
     ap.add_argument("--jobs", default="a,b,c")
     ap.add_argument("--numpy-problems", type=int, default=2)
+    ap.add_argument("--filter-problems", type=int, default=0, help="cap on B of the b context's filter jobs (0: none)")
     args = ap.parse_args()
     cache = {}
     out = {"tool": "bench_sample_paths", "tree": tree(), "unit": "ms per call (device events around the call)", "jobs": []}
     for job in [j for j in args.jobs.split(",") if j]:
-        out["jobs"].append(run(job, args.rounds, args.calls, args.numpy_problems, cache))
+        out["jobs"].append(run(job, args.rounds, args.calls, args.numpy_problems, cache, args.filter_problems))
     for c, _, _, _, tm in cache.values():
         tm.close()
         c.close()

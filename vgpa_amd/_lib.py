@@ -36,7 +36,7 @@ BWD_IDS = {"none": 0, "psi": 1, "q": 2}
 SYMBOLS = ["vgpa_create", "vgpa_destroy", "vgpa_last_error", "vgpa_abi_version", "vgpa_device_count",
            "vgpa_synchronize", "vgpa_stream", "vgpa_solve_fwd", "vgpa_solve_bwd", "vgpa_energy",
            "vgpa_obs_energy", "vgpa_free_energy", "vgpa_gradient", "vgpa_sweep", "vgpa_energy_parts",
-           "vgpa_fetch", "vgpa_theta_gradient", "vgpa_sample_paths", "vgpa_sample_paths_weighted", "vgpa_sweep_dev", "vgpa_free_energy_dev", "vgpa_sweep_enqueue", "vgpa_fetch_f",
+           "vgpa_fetch", "vgpa_theta_gradient", "vgpa_sample_paths", "vgpa_sample_paths_weighted", "vgpa_particle_filter", "vgpa_sweep_dev", "vgpa_free_energy_dev", "vgpa_sweep_enqueue", "vgpa_fetch_f",
            "vgpa_dev_alloc", "vgpa_dev_free", "vgpa_memcpy_h2d", "vgpa_memcpy_d2h",
            "vgpa_profile_begin", "vgpa_profile_end", "vgpa_ld_gemm", "vgpa_ld_stage", "vgpa_gradient_dev", "vgpa_energy_full", "vgpa_set_option", "vgpa_is_streaming", "vgpa_path_info", "vgpa_set_prior_energy",
            "vgpa_set_problem_data", "vgpa_set_problem_params", "vgpa_set_problem_obs_model",
@@ -135,6 +135,8 @@ def load():
     lib.vgpa_theta_gradient.argtypes = [c_void_p, c_void_p]
     lib.vgpa_sample_paths.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_int32, c_int32, c_uint64, c_void_p]
     lib.vgpa_sample_paths_weighted.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_uint64, c_void_p, c_void_p, c_void_p]
+    lib.vgpa_particle_filter.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_uint64, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vgpa_sweep_dev.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vgpa_free_energy_dev.argtypes = [c_void_p, c_void_p, c_void_p]
     lib.vgpa_sweep_enqueue.argtypes = [c_void_p, c_void_p, c_void_p]
@@ -577,6 +579,31 @@ class Context:
         self._check(self._lib.vgpa_sample_paths_weighted(self._h, _ptr(xx), _ptr(s0), n_paths, stride, int(seed) & 0xFFFFFFFFFFFFFFFF,
                                                          _ptr(out), _ptr(start), _ptr(logw)))
         return out, logw, start
+
+    def particle_filter(self, n_paths, seed, ess_fraction=0.5, x=None, x0=None, prior=None, history=False):
+        """The guided particle filter (vgpa_particle_filter): the walk of sample_paths_weighted with the weights taken in observation by
+        observation and the cloud resampled (systematic) whenever ESS < ess_fraction n_paths.  prior: (mu0 (B, D), tau0 (B, D, D)) for the
+        initial term of a drawn start, or None.  Returns a dict: log_w (B, n_paths), state (B, n_paths, D), ess (B, M), resampled (B, M) int32
+        and, history=True, ancestors (B, M, n_paths) int32 and clouds (B, M, n_paths, D) (else None), M = the context's n_obs.  Rows at or
+        beyond a problem's own observation count: ess 0, resampled 0, ancestors -1, clouds NaN."""
+        n_paths, m = int(n_paths), self.n_obs
+        xx = None if x is None else _c64(x)
+        if xx is not None and xx.size != self.B * self.len_x:
+            raise ValueError(f"x has {xx.size} entries, expected {self.B * self.len_x}")
+        s0 = None if x0 is None else _c64(np.broadcast_to(np.asarray(x0, dtype=np.float64).reshape(-1, self.D), (self.B, self.D)))
+        mu = tau = None
+        if prior is not None:
+            mu = _c64(np.broadcast_to(np.asarray(prior[0], dtype=np.float64).reshape(-1, self.D), (self.B, self.D)))
+            tau = _c64(np.broadcast_to(np.asarray(prior[1], dtype=np.float64).reshape(-1, self.D, self.D), (self.B, self.D, self.D)))
+        n = max(n_paths, 0)
+        log_w, state = np.empty((self.B, n)), np.empty((self.B, n, self.D))
+        ess, flags = np.zeros((self.B, m)), np.zeros((self.B, m), dtype=np.int32)
+        anc = np.full((self.B, m, n), -1, dtype=np.int32) if history else None
+        clouds = np.full((self.B, m, n, self.D), np.nan) if history else None
+        self._check(self._lib.vgpa_particle_filter(self._h, _ptr(xx), _ptr(s0), n_paths, int(seed) & 0xFFFFFFFFFFFFFFFF, float(ess_fraction),
+                                                   _ptr(mu), _ptr(tau), _ptr(log_w), _ptr(state), _ptr(ess), _ptr(flags), _ptr(anc),
+                                                   _ptr(clouds)))
+        return {"log_w": log_w, "state": state, "ess": ess, "resampled": flags, "ancestors": anc, "clouds": clouds}
 
     def fetch(self, key):
         which = FETCH_IDS[key]

@@ -206,6 +206,16 @@ class ProblemBatch(object):
                                                                    paths=stride is not None)
         return [v._path_weights(logw[k], start[k], None if paths is None else paths[k], x0 is None) for k, v in enumerate(self.vgps)]
 
+    def particle_filter(self, n_paths, seed, ess_fraction=0.5, x=None, x0=None, history=False):
+        """One particles.ParticleFilterResult per member (VarGP.particle_filter): each with its own data, observation times and count,
+        prior, theta and Sigma; the histories are cut to the member's own observation count.  A member's result does not depend on the
+        rest of the batch."""
+        xx = None if x is None else self._stack(x)
+        d = self.vgps[0].dim_d
+        prior = (np.stack([v._prior()[0][0] for v in self.vgps]), np.stack([v._prior()[1][0] for v in self.vgps]).reshape(self.B, d, d))
+        res = self._context().particle_filter(n_paths, seed, ess_fraction=ess_fraction, x=xx, x0=x0, prior=prior, history=history)
+        return [v._particle_record(res, k, np.asarray(v._inputs()["obs_t"]).size) for k, v in enumerate(self.vgps)]
+
     def _theta_rows(self):
         return np.stack([np.atleast_1d(np.asarray(v.model.theta, dtype=float)) for v in self.vgps])
 

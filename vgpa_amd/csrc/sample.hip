@@ -8,6 +8,9 @@
 // depends on the launch geometry.
 // k_sample_small<D, true> and k_sample_mfma<NT, true> (vgpa_sample_paths_weighted) walk the same paths and sum, where the path
 // is made, the log-ratio of the model SDE's path density to the posterior process's and the Gaussian log-likelihood of the observations.
+// k_sample_small<D, true, true> and k_sample_mfma<NT, true, true> (vgpa_particle_filter) are their segment twins: the grid
+// steps k_begin < k <= k_end from the particle states in SampleArgs::pf_x, the increments added to the log-weights in pf_lw, the end states
+// written back.  k_pf_start draws the particles and their initial term; k_pf_resample is the step between two segments.
 #include "vgpa_internal.h"
 
 namespace vgpa {
@@ -67,6 +70,7 @@ struct ObsCursor {
   __device__ __forceinline__ ObsCursor(const SampleArgs& a, uint32_t p)
       : t(a.obs_t + (size_t)p * a.obs_t_stride), n(a.n_obs_v ? a.n_obs_v[p] : a.n_obs), cur(0) { next = n > 0 ? (int)t[0] : -1; }
   __device__ __forceinline__ void advance() { next = ++cur < n ? (int)t[cur] : -1; }
+  __device__ __forceinline__ void skip_through(int k) { while (next >= 0 && next <= k) advance(); }      // to the first index > k
 };
 
 // (y_n - x)^T Q (y_n - x) of problem p
@@ -93,8 +97,10 @@ __device__ __forceinline__ double obs_constant(const SampleArgs& a, uint32_t p) 
 
 // W: the weighted instantiation (posterior kind, diagonal R): both drifts at x_{k-1}, d = g - f, and per step
 // -sum_i d_i (eta_i + dt d_i / 2) / Sigma_ii with 1 / Sigma_ii = dt / R_ii^2; the observation term at the lane's own problem's times
-template <int D, bool W>
+// SEG: a segment of the weighted walk (k_begin, k_end] from and to pf_x, the sums added to pf_lw; nothing else is stored
+template <int D, bool W, bool SEG = false>
 __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
+  static_assert(W || !SEG, "a segment is a weighted walk");
   const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (gid >= (size_t)a.batch * a.n_paths) return;
   const uint32_t p = (uint32_t)(gid / a.n_paths), path = (uint32_t)(gid % a.n_paths);
@@ -113,7 +119,10 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
 #pragma unroll
     for (int i = 0; i < kMaxTheta; i++) th[i] = a.theta_v ? a.theta_v[(size_t)p * kMaxTheta + i] : a.theta[i];
   }
-  if (a.x0) {
+  if constexpr (SEG) {
+#pragma unroll
+    for (int i = 0; i < D; i++) x[i] = a.pf_x[gid * D + i];
+  } else if (a.x0) {
 #pragma unroll
     for (int i = 0; i < D; i++) x[i] = a.x0[(size_t)p * D + i];
   } else {
@@ -129,7 +138,7 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
       x[i] = m0[i] + s;
     }
   }
-  const bool store = !W || a.out != nullptr;
+  const bool store = !SEG && (!W || a.out != nullptr);
   double* o = store ? a.out + gid * (size_t)a.n_keep * D : nullptr;
   if (store) {
 #pragma unroll
@@ -141,13 +150,18 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
   if constexpr (W) {
     oc = ObsCursor(a, p);
 #pragma unroll
-    for (int i = 0; i < D; i++) { isg[i] = a.dt / (R[i * D + i] * R[i * D + i]); a.start[gid * D + i] = x[i]; }
+    for (int i = 0; i < D; i++) {
+      isg[i] = a.dt / (R[i * D + i] * R[i * D + i]);
+      if constexpr (!SEG) a.start[gid * D + i] = x[i];
+    }
+    if constexpr (SEG) { if (!a.seg_first) oc.skip_through(a.k_begin); }
     if (oc.next == 0) { ow += obs_form<D>(a, p, oc.cur, x); oc.advance(); }
   }
   const double* A = a.A + (size_t)p * a.stride_x;
   const double* bv = a.b + (size_t)p * a.stride_x;
   int until = a.stride, slot = 0;
-  for (int k = 1; k < a.Np; k++) {
+  const int k_first = SEG ? a.k_begin + 1 : 1, k_stop = SEG ? a.k_end + 1 : a.Np;
+  for (int k = k_first; k < k_stop; k++) {
     double f[D], fm[D];
     if constexpr (W) model_drift<D>(a.model, th, x, fm);
     if (W || a.kind == VGPA_PATHS_POSTERIOR) {
@@ -189,7 +203,11 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
     }
   }
   for (int e = 0; e < slot * D; e++) o[e] = sg[e * 256];
-  if constexpr (W) { a.logw[2 * gid] = pw; a.logw[2 * gid + 1] = -0.5 * ow - obs_constant(a, p); }
+  if constexpr (SEG) {
+    a.pf_lw[gid] += pw - 0.5 * ow;
+#pragma unroll
+    for (int i = 0; i < D; i++) a.pf_x[gid * D + i] = x[i];
+  } else if constexpr (W) { a.logw[2 * gid] = pw; a.logw[2 * gid + 1] = -0.5 * ow - obs_constant(a, p); }
 }
 
 // ---- 5 <= D <= 64, posterior kind ---------------------------------------------------------------------------------------------------
@@ -228,8 +246,10 @@ __device__ __forceinline__ void normals_c(uint32_t k0, uint32_t k1, uint32_t k, 
 // eta = nz; the model drift f_i reads rows (i + 1) mod D, (i - 2) mod D, (i - 1) mod D of the path's column of Xs.  Each lane sums its rows over
 // time; the four q-lanes of a path are added once at the end.  The observation term is evaluated from Xs at the problem's observation times,
 // which a workgroup walks with one cursor.
-template <int NT, bool W>
+// SEG: as in k_sample_small; A_{k_begin} is the first matrix loaded, and the end states leave through `put` as [path][D].
+template <int NT, bool W, bool SEG = false>
 __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
+  static_assert(W || !SEG, "a segment is a weighted walk");
   using Sh = MfmaShape<NT>;
   constexpr int LDA = Sh::LDA, MT = Sh::MT, KT = Sh::KT, NPF = Sh::NPF;
   extern __shared__ double lds[];
@@ -245,14 +265,15 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
   const double* A = a.A + (size_t)p * a.stride_x;
   const double* bv = a.b + (size_t)p * a.stride_x;
   const double* Rp = a.R + (size_t)p * a.R_stride;
+  const int k_first = SEG ? a.k_begin + 1 : 1, k_stop = SEG ? a.k_end + 1 : a.Np;
 
   for (int e = tid; e < NT * LDA * (dense ? 2 : 1) + NT; e += 256) lds[e] = 0.0;
   __syncthreads();
   for (int e = tid; e < DD; e += 256) {
-    As[(e / D) * LDA + e % D] = A[e];
+    As[(e / D) * LDA + e % D] = A[(size_t)(k_first - 1) * DD + e];
     if (dense) Rs[(e / D) * LDA + e % D] = Rp[e];
   }
-  if (tid < D) bs[tid] = bv[tid];
+  if (tid < D) bs[tid] = bv[(size_t)(k_first - 1) * D + tid];
 
   double x[MT][4], rd[MT][4], z[MT][4];
 #pragma unroll
@@ -262,7 +283,16 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
       const int row = mt * 16 + q + 4 * r;
       rd[mt][r] = (!dense && row < D) ? Rp[row * D + row] : 0.0;
     }
-  if (a.x0) {
+  if constexpr (SEG) {
+    const bool live = path < (uint32_t)a.n_paths;      // (a lane behind the last path walks zeros and stores nothing)
+#pragma unroll
+    for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const int row = mt * 16 + q + 4 * r;
+        x[mt][r] = live && row < D ? a.pf_x[((size_t)p * a.n_paths + path) * D + row] : 0.0;
+      }
+  } else if (a.x0) {
 #pragma unroll
     for (int mt = 0; mt < MT; mt++)
 #pragma unroll
@@ -293,7 +323,7 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
   // A kept point leaves from Xs, where the wave's 16 states lie as [row][path]: element e = lane + 64 i of the 16 rows of `out` (path e / D,
   // component e % D), so that one store instruction writes runs of D consecutive doubles instead of 4 per path
   const uint32_t path0 = blockIdx.y * 64 + w * 16;
-  const bool store = !W || a.out != nullptr;
+  const bool store = !SEG && (!W || a.out != nullptr);
   double* o = store ? a.out + ((size_t)p * a.n_paths + path0) * (size_t)a.n_keep * D : nullptr;
   const size_t row_len = (size_t)a.n_keep * D;
   auto put = [&](double* dst, size_t len) {
@@ -313,6 +343,7 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
   double isg[W ? MT : 1][4], pw = 0.0, ow = 0.0, th = 0.0;
   ObsCursor oc;
   if constexpr (W) oc = ObsCursor(a, p);
+  if constexpr (SEG) { if (!a.seg_first) oc.skip_through(a.k_begin); }
   auto observe = [&]() {      // x_k is in x and, whole, in the path's column of Xs
     const double* y = a.obs_y + (size_t)p * a.obs_y_stride + (size_t)oc.cur * D;
     const double* Qp = a.Q + (size_t)p * a.Q_stride;
@@ -346,15 +377,15 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
   __syncthreads();
   keep();
   if constexpr (W) {
-    put(a.start + ((size_t)p * a.n_paths + path0) * D, (size_t)D);
+    if constexpr (!SEG) put(a.start + ((size_t)p * a.n_paths + path0) * D, (size_t)D);
     if (oc.next == 0) observe();
   }
 
   int until = a.stride;
-  for (int k = 1; k < a.Np; k++) {
+  for (int k = k_first; k < k_stop; k++) {
     // A_k, b_k for the next step: requested now, written to LDS behind this step's products
     double pa[NPF], pb = 0.0;
-    const bool more = k + 1 < a.Np;
+    const bool more = k + 1 < k_stop;
     if (more) {
       const double* Ak = A + (size_t)k * DD;
 #pragma unroll
@@ -431,7 +462,10 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
   if constexpr (W) {
     pw += __shfl_xor(pw, 16); pw += __shfl_xor(pw, 32);
     ow += __shfl_xor(ow, 16); ow += __shfl_xor(ow, 32);
-    if (q == 0 && path < (uint32_t)a.n_paths) {
+    if constexpr (SEG) {
+      if (q == 0 && path < (uint32_t)a.n_paths) a.pf_lw[(size_t)p * a.n_paths + path] += pw - 0.5 * ow;
+      put(a.pf_x + ((size_t)p * a.n_paths + path0) * D, (size_t)D);      // (Xs holds x_{k_end} behind the loop's last barrier)
+    } else if (q == 0 && path < (uint32_t)a.n_paths) {
       double* lw = a.logw + 2 * ((size_t)p * a.n_paths + path);
       lw[0] = pw; lw[1] = -0.5 * ow - obs_constant(a, p);
     }
@@ -515,6 +549,164 @@ hipError_t launch_mfma(const SampleArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
+// ---- the particle filter: the start, the segments, the resampling step between them ------------------------------------------------
+template <int NT>
+hipError_t launch_mfma_segment(const SampleArgs& a, hipStream_t st) {
+  const size_t lds = MfmaShape<NT>::lds_doubles(false) * sizeof(double);
+  if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k_sample_mfma<NT, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if ((a.n_paths + 63) / 64 > 65535) return hipErrorInvalidValue;      // (grid.y)
+  hipLaunchKernelGGL((k_sample_mfma<NT, true, true>), dim3(a.batch, (a.n_paths + 63) / 64), dim3(256), lds, st, a);
+  return hipGetLastError();
+}
+
+// One lane per particle: x_0 (given, or m0 + L0 xi_0 summed as the samplers sum it) to a.x, and lw = init - c_p with
+// init = log N(x_0; mu0, tau0) - log N(x_0; m0, S0) for a drawn start under a prior (the two triangular solves against the factors in global
+// memory; a.ws [B][n][D] holds the lane's normals, then its solutions), else 0.  Runs once per call.
+__global__ __launch_bounds__(256) void k_pf_start(PfArgs a) {
+  const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (gid >= (size_t)a.batch * a.n_paths) return;
+  const int D = a.D;
+  const uint32_t p = (uint32_t)(gid / a.n_paths), path = (uint32_t)(gid % a.n_paths);
+  const uint32_t k0 = (uint32_t)(a.seed & 0xffffffffu), k1 = (uint32_t)(a.seed >> 32);
+  double* x = a.x + gid * D;
+  double* u = a.ws + gid * D;
+  double init = 0.0;
+  if (a.x0) {
+    for (int i = 0; i < D; i++) x[i] = a.x0[(size_t)p * D + i];
+  } else {
+    const double* m0 = a.m0 + (size_t)p * a.m0_stride;
+    const double* L0 = a.L0 + (size_t)p * a.L0_stride;
+    for (int j = 0; 2 * j < D; j++) {
+      double c, s;
+      normal_pair(k0, k1, 0u, path, p, (uint32_t)j, &c, &s);
+      u[2 * j] = c;
+      if (2 * j + 1 < D) u[2 * j + 1] = s;
+    }
+    for (int i = 0; i < D; i++) {
+      double s = 0.0;
+      for (int j = 0; j <= i; j++) s += L0[i * D + j] * u[j];
+      x[i] = m0[i] + s;
+    }
+    if (a.mu0) {
+      const double* mu = a.mu0 + (size_t)p * D;
+      const double* Lt = a.Lt + (size_t)p * D * D;
+      double q0 = 0.0, ld0 = 0.0, q1 = 0.0, ld1 = 0.0;
+      for (int i = 0; i < D; i++) {      // L0 v = x_0 - m0 (v overwrites the normals it is, up to rounding)
+        double s = x[i] - m0[i];
+        for (int j = 0; j < i; j++) s -= L0[i * D + j] * u[j];
+        u[i] = s / L0[i * D + i];
+        q0 += u[i] * u[i]; ld0 += log(L0[i * D + i]);
+      }
+      for (int i = 0; i < D; i++) {      // Lt v = x_0 - mu0
+        double s = x[i] - mu[i];
+        for (int j = 0; j < i; j++) s -= Lt[i * D + j] * u[j];
+        u[i] = s / Lt[i * D + i];
+        q1 += u[i] * u[i]; ld1 += log(Lt[i * D + i]);
+      }
+      init = (-0.5 * q1 - ld1) - (-0.5 * q0 - ld0);
+    }
+  }
+  a.lw[gid] = init - a.obs_const_scale * (a.obs_const_v ? a.obs_const_v[p] : a.obs_const);
+}
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+  return v;
+}
+
+// The step between two segments, one workgroup per problem, at grid index a.k.  A problem without an observation at a.k
+// copies its particles through.  Otherwise: w_i = exp(lw_i - max lw), S = sum w, ESS = S^2 / sum w^2, cum = the inclusive prefix sums of w in
+// slot order (256 slots per pass: a shuffle scan per wave, the waves' totals and the carry through LDS); resampled iff ESS < ess_fraction n and
+// a.k is not the last grid index: anc_i = min(#{m: cum_m <= (U + i) / n S}, n - 1) by bisection, U from Philox counter (k, 0, p, 0xffffffff),
+// x_out_i = x_in_{anc_i}, lw_i = max lw + log S - log n; else anc_i = i and lw stays.  The histories of observation j (t_j = a.k) are
+// written where asked for; the cloud is x_in.
+__global__ __launch_bounds__(256) void k_pf_resample(PfArgs a) {
+  __shared__ double tot[4], red[4];
+  const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6, n = a.n_paths, D = a.D;
+  const int64_t* t = a.obs_t + (size_t)p * a.obs_t_stride;
+  const int cnt = a.n_obs_v ? a.n_obs_v[p] : a.n_obs;
+  int j = -1;
+  for (int m = 0; m < cnt; m++) if (t[m] == (int64_t)a.k) j = m;
+  const size_t nD = (size_t)n * D;
+  const double* xin = a.x_in + (size_t)p * nD;
+  double* xout = a.x_out + (size_t)p * nD;
+  if (j < 0) {      // (uniform over the workgroup)
+    for (size_t e = tid; e < nD; e += 256) xout[e] = xin[e];
+    return;
+  }
+  double* lw = a.lw + (size_t)p * n;
+  double* cum = a.cum + (size_t)p * n;
+  int32_t* anc = a.anc + (size_t)p * n;
+  double mx = -INFINITY;
+  for (int i = tid; i < n; i += 256) mx = fmax(mx, lw[i]);
+  mx = wave_max(mx);
+  if (lane == 0) red[w] = mx;
+  __syncthreads();
+  mx = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+  double carry = 0.0, s2 = 0.0;
+  for (int base = 0; base < n; base += 256) {
+    const int i = base + tid;
+    const double wi = i < n ? exp(lw[i] - mx) : 0.0;
+    s2 += wi * wi;
+    double sc = wi;      // inclusive scan over the wave
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const double up = __shfl_up(sc, o); if (lane >= o) sc += up; }
+    __syncthreads();      // (tot of the pass before has been read)
+    if (lane == 63) tot[w] = sc;
+    __syncthreads();
+    double before = carry;
+    for (int v = 0; v < w; v++) before += tot[v];
+    if (i < n) cum[i] = before + sc;
+    carry = (((carry + tot[0]) + tot[1]) + tot[2]) + tot[3];      // (the association of the last slot's own sum)
+  }
+  // S is what the last slot's prefix sum is, to the last bit: every threshold lies below cum_{n-1} as the exact ones do
+  __syncthreads();      // (cum is written; red has been read)
+  const double S = cum[n - 1];
+  s2 = wave_sum(s2);
+  if (lane == 0) red[w] = s2;
+  __syncthreads();
+  s2 = (red[0] + red[1]) + (red[2] + red[3]);
+  const double ess = S * S / s2;
+  const bool go = ess < a.ess_fraction * (double)n && !a.last;
+  const size_t hj = (size_t)p * a.M + j;
+  if (tid == 0) { a.h_ess[hj] = ess; a.h_flag[hj] = go ? 1 : 0; }
+  if (a.h_clouds)
+    for (size_t e = tid; e < nD; e += 256) a.h_clouds[hj * nD + e] = xin[e];
+  double U = 0.0;
+  if (go) {
+    uint32_t r[4];
+    philox4x32_10((uint32_t)a.k, 0u, (uint32_t)p, 0xffffffffu, (uint32_t)(a.seed & 0xffffffffu), (uint32_t)(a.seed >> 32), r);
+    U = unit_open(r[0], r[1]);
+  }
+  const double lw_new = mx + log(S) - log((double)n);
+  for (int i = tid; i < n; i += 256) {
+    int from = i;
+    if (go) {
+      const double ui = (U + (double)i) / (double)n * S;
+      int lo = 0, hi = n;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (cum[mid] <= ui) lo = mid + 1; else hi = mid;
+      }
+      from = lo < n - 1 ? lo : n - 1;
+      lw[i] = lw_new;
+    }
+    anc[i] = from;
+    if (a.h_anc) a.h_anc[hj * n + i] = from;
+  }
+  __syncthreads();
+  for (size_t e = tid; e < nD; e += 256) {
+    const size_t i = e / D;
+    xout[e] = xin[(size_t)anc[i] * D + (e - i * D)];
+  }
+}
+
 template <bool W>
 hipError_t launch_posterior(const SampleArgs& a, hipStream_t st) {
   const size_t lanes = (size_t)a.batch * a.n_paths;
@@ -535,6 +727,39 @@ hipError_t launch_posterior(const SampleArgs& a, hipStream_t st) {
 }
 
 }  // namespace
+
+hipError_t launch_sample_segment(const SampleArgs& a, hipStream_t st) {
+  if (a.D < 1 || a.D > kMaxSmallD || a.n_paths < 1 || a.kind != VGPA_PATHS_POSTERIOR || !a.R_diag || !a.pf_x || !a.pf_lw) return hipErrorInvalidValue;
+  if (a.k_begin < 0 || a.k_end < a.k_begin || a.k_end >= a.Np) return hipErrorInvalidValue;
+  if (a.model != VGPA_MODEL_OU && a.model != VGPA_MODEL_DW && a.model != VGPA_MODEL_L63 && a.model != VGPA_MODEL_L96) return hipErrorInvalidValue;
+  if (a.D > kMaxLaneD && a.model != VGPA_MODEL_L96) return hipErrorInvalidValue;
+  if (a.D <= kMaxLaneD) {
+    const dim3 grid((unsigned)(((size_t)a.batch * a.n_paths + 255) / 256)), block(256);
+    switch (a.D) {
+      case 1: hipLaunchKernelGGL((k_sample_small<1, true, true>), grid, block, 0, st, a); break;
+      case 2: hipLaunchKernelGGL((k_sample_small<2, true, true>), grid, block, 0, st, a); break;
+      case 3: hipLaunchKernelGGL((k_sample_small<3, true, true>), grid, block, 0, st, a); break;
+      default: hipLaunchKernelGGL((k_sample_small<4, true, true>), grid, block, 0, st, a); break;
+    }
+    return hipGetLastError();
+  }
+  if (a.D <= 16) return launch_mfma_segment<16>(a, st);
+  if (a.D <= 32) return launch_mfma_segment<32>(a, st);
+  if (a.D <= 48) return launch_mfma_segment<48>(a, st);
+  return launch_mfma_segment<64>(a, st);
+}
+
+hipError_t launch_pf_start(const PfArgs& a, hipStream_t st) {
+  if (a.D < 1 || a.D > kMaxSmallD || a.n_paths < 1 || !a.x || !a.ws || !a.lw || (!a.x0 && !(a.m0 && a.L0)) || (a.mu0 && !a.Lt)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_pf_start, dim3((unsigned)(((size_t)a.batch * a.n_paths + 255) / 256)), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_pf_resample(const PfArgs& a, hipStream_t st) {
+  if (a.D < 1 || a.n_paths < 1 || !a.x_in || !a.x_out || a.x_in == a.x_out || !a.lw || !a.cum || !a.anc || !a.h_ess || !a.h_flag) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_pf_resample, dim3(a.batch), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
 
 hipError_t launch_sample_paths(const SampleArgs& a, hipStream_t st) {
   const size_t lanes = (size_t)a.batch * a.n_paths;

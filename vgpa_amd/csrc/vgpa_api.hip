@@ -164,6 +164,11 @@ struct vgpa_ctx {
   size_t sp_out_n = 0, sp_R_n = 0, sp_L0_n = 0, sp_x0_n = 0;
   double *d_sp_logw = nullptr, *d_sp_start = nullptr;      // vgpa_sample_paths_weighted: the two sums and x_0 of every path
   size_t sp_logw_n = 0, sp_start_n = 0;
+  // vgpa_particle_filter: the two particle buffers, log-weights, prefix sums, ancestors of a step (int32), the histories (ess, flags and
+  // ancestors as int32, clouds), the prior's mean and factor
+  enum { PF_XA, PF_XB, PF_LW, PF_CUM, PF_ANC, PF_ESS, PF_FLAG, PF_HANC, PF_CLOUDS, PF_MU, PF_LT, PF_COUNT };
+  double* d_pf[PF_COUNT] = {};
+  size_t pf_n[PF_COUNT] = {};
   // profiling
   bool prof = false;
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -937,6 +942,7 @@ void vgpa_destroy(vgpa_ctx* c) {
   for (void* p : c->allocs) (void)hipFree(p);
   for (void* p : c->user_allocs) (void)hipFree(p);
   for (double* p : {c->d_sp_out, c->d_sp_R, c->d_sp_L0, c->d_sp_x0, c->d_sp_logw, c->d_sp_start}) if (p) (void)hipFree(p);
+  for (double* p : c->d_pf) if (p) (void)hipFree(p);
   if (c->h_coef) (void)hipHostFree(c->h_coef);
   if (c->h_fs) (void)hipHostFree(c->h_fs);
   for (auto& e : c->ev_coef) if (e) (void)hipEventDestroy(e);
@@ -1460,9 +1466,11 @@ static int factor_rows(vgpa_ctx* c, const double* src, int n, double scale, cons
 
 // Euler-Maruyama paths of the posterior process or of the model SDE (see vgpa_hip.h), and -- logw set: vgpa_sample_paths_weighted,
 // DESIGN.md s.4.9 -- the weights of the posterior paths against the model SDE and the data, with `out` optional and every x_0 to `start`.  Reads x
-// and the inputs in force; of the cached state nothing is written.  The arguments have been checked by the two entry points.
-static int sample_paths(vgpa_ctx* c, int kind, const double* x, const double* x0, int32_t n_paths, int32_t stride, uint64_t seed, double* out,
-                        double* start, double* logw) {
+// and the inputs in force; of the cached state nothing is written.  The arguments have been checked by the entry points.
+// sample_args: everything of SampleArgs but the result buffers -- the factors, the start, x ingested and, weighted, the model's theta and the
+// observation model in force; shared with vgpa_particle_filter.
+static int sample_args(vgpa_ctx* c, int kind, const double* x, const double* x0, int32_t n_paths, int32_t stride, uint64_t seed, bool weighted,
+                       SampleArgs* args) {
   if (c->D > kMaxSmallD) return fail(c, VGPA_ERR_UNSUPPORTED, "sample paths are built for D <= %d (D = %d)", kMaxSmallD, c->D);
   if (kind == VGPA_PATHS_POSTERIOR && !x && !c->res.cached)
     return fail(c, VGPA_ERR_STATE, "no cached state: sample_paths without x needs the state cached by a previous free_energy / sweep");
@@ -1470,7 +1478,8 @@ static int sample_paths(vgpa_ctx* c, int kind, const double* x, const double* x0
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   const int D = c->D, B = c->B;
   int rc;
-  SampleArgs a{};
+  SampleArgs& a = *args;
+  a = SampleArgs{};
   a.kind = kind; a.model = c->cfg.model; a.D = D; a.Np = c->Np; a.batch = B; a.n_paths = n_paths; a.stride = stride;
   a.n_keep = (c->Np - 1) / stride + 1; a.dt = c->cfg.dt; a.seed = seed;
   Rows<double> R, L0;
@@ -1479,7 +1488,7 @@ static int sample_paths(vgpa_ctx* c, int kind, const double* x, const double* x0
   if ((rc = factor_rows(c, own_Sigma ? c->in.h_Sigma.data() : c->h_sigma.data(), own_Sigma ? B : 1, c->cfg.dt, "noise matrix times dt",
                         &c->d_sp_R, &c->sp_R_n, &R, &diag))) return rc;
   a.R = R.rows; a.R_stride = R.stride; a.R_diag = diag ? 1 : 0;
-  if (logw && !diag) return fail(c, VGPA_ERR_UNSUPPORTED, "the weights of sampled paths are built for a diagonal Sigma (a dense Sigma is in force)");
+  if (weighted && !diag) return fail(c, VGPA_ERR_UNSUPPORTED, "the weights of sampled paths are built for a diagonal Sigma (a dense Sigma is in force)");
   if (x0) {
     if ((rc = grow(c, &c->d_sp_x0, &c->sp_x0_n, (size_t)B * D))) return rc;
     if ((rc = upload(c, c->d_sp_x0, x0, (size_t)B * D))) return rc;
@@ -1499,20 +1508,31 @@ static int sample_paths(vgpa_ctx* c, int kind, const double* x, const double* x0
     copy_theta(c, a.theta);
     a.theta_v = c->in.theta.rows;
   }
-  const size_t n_out = (size_t)B * n_paths * a.n_keep * D, n_start = (size_t)B * n_paths * D, n_logw = (size_t)B * n_paths * 2;
-  if (out) {
-    if ((rc = grow(c, &c->d_sp_out, &c->sp_out_n, n_out))) return rc;
-    a.out = c->d_sp_out;
-  }
-  if (logw) {      // both drifts, and the observation model in force as obs_args hands it to the E_obs kernels
-    if ((rc = grow(c, &c->d_sp_logw, &c->sp_logw_n, n_logw)) || (rc = grow(c, &c->d_sp_start, &c->sp_start_n, n_start))) return rc;
-    a.logw = c->d_sp_logw; a.start = c->d_sp_start;
+  if (weighted) {      // both drifts, and the observation model in force as obs_args hands it to the E_obs kernels
     copy_theta(c, a.theta);
     a.theta_v = c->in.theta.rows;
     const ObsArgs o = obs_args(c);
     a.obs_t = o.obs_t; a.obs_t_stride = o.obs_t_stride; a.obs_y = o.obs_y; a.obs_y_stride = o.obs_y_stride;
     a.Q = o.Q; a.Q_stride = o.Q_stride; a.Q_diag = o.diag; a.n_obs = o.n_obs; a.n_obs_v = o.n_obs_v;
     a.obs_const = o.obs_const; a.obs_const_v = o.obs_const_v; a.obs_const_scale = c->single ? 1.0 : 0.5;
+  }
+  return VGPA_OK;
+}
+
+static int sample_paths(vgpa_ctx* c, int kind, const double* x, const double* x0, int32_t n_paths, int32_t stride, uint64_t seed, double* out,
+                        double* start, double* logw) {
+  SampleArgs a;
+  int rc;
+  if ((rc = sample_args(c, kind, x, x0, n_paths, stride, seed, logw != nullptr, &a))) return rc;
+  const int D = c->D, B = c->B;
+  const size_t n_out = (size_t)B * n_paths * a.n_keep * D, n_start = (size_t)B * n_paths * D, n_logw = (size_t)B * n_paths * 2;
+  if (out) {
+    if ((rc = grow(c, &c->d_sp_out, &c->sp_out_n, n_out))) return rc;
+    a.out = c->d_sp_out;
+  }
+  if (logw) {
+    if ((rc = grow(c, &c->d_sp_logw, &c->sp_logw_n, n_logw)) || (rc = grow(c, &c->d_sp_start, &c->sp_start_n, n_start))) return rc;
+    a.logw = c->d_sp_logw; a.start = c->d_sp_start;
   }
   LAUNCH_TRY(c, "sample paths launch", launch_sample_paths(a, c->stream));
   if (out && (rc = download(c, out, c->d_sp_out, n_out))) return rc;
@@ -1541,6 +1561,84 @@ int vgpa_sample_paths_weighted(vgpa_ctx* c, const double* x, const double* x0, i
   if (c->cfg.model == VGPA_MODEL_NONE) return fail(c, VGPA_ERR_ARG, "context has no stochastic model: no model SDE to weigh the paths against");
   if (!c->full) return fail(c, VGPA_ERR_STATE, "context was created without m0/s0/observations (ODE-only)");
   return sample_paths(c, VGPA_PATHS_POSTERIOR, x, x0, n_paths, stride, seed, out, start, logw);
+}
+
+// The guided particle filter (see vgpa_hip.h): the weighted walk of vgpa_sample_paths_weighted cut at the observation
+// indices of the batch, the particles resident between the cuts, a resampling step behind every cut that is an observation of some problem.
+int vgpa_particle_filter(vgpa_ctx* c, const double* x, const double* x0, int32_t n_paths, uint64_t seed, double ess_fraction,
+                         const double* prior_mu, const double* prior_tau, double* logw, double* state, double* ess, int32_t* resampled,
+                         int32_t* ancestors, double* clouds) {
+  if (!c) return VGPA_ERR_ARG;
+  if (!logw || !state) return fail(c, VGPA_ERR_ARG, "null argument");
+  if (n_paths < 1) return fail(c, VGPA_ERR_ARG, "n_paths must be at least 1 (n_paths = %d)", n_paths);
+  if (!(ess_fraction >= 0.0 && ess_fraction <= 1.0)) return fail(c, VGPA_ERR_ARG, "ess_fraction must lie in [0, 1] (ess_fraction = %g)", ess_fraction);
+  if ((prior_mu == nullptr) != (prior_tau == nullptr)) return fail(c, VGPA_ERR_ARG, "the prior is a mean and a covariance: both or neither");
+  if (c->cfg.model == VGPA_MODEL_NONE) return fail(c, VGPA_ERR_ARG, "context has no stochastic model: no model SDE to weigh the particles against");
+  if (!c->full) return fail(c, VGPA_ERR_STATE, "context was created without m0/s0/observations (ODE-only)");
+  SampleArgs a;
+  int rc;
+  if ((rc = sample_args(c, VGPA_PATHS_POSTERIOR, x, x0, n_paths, 1, seed, true, &a))) return rc;
+  const int D = c->D, B = c->B, M = c->M, Np = c->Np, M1 = M > 0 ? M : 1;
+  const size_t n = (size_t)n_paths, BnD = (size_t)B * n * D, Bn = (size_t)B * n, BM = (size_t)B * M1;
+  auto buf = [&](int which, size_t count) { return grow(c, &c->d_pf[which], &c->pf_n[which], count); };
+  auto ints = [](size_t count) { return (count + 1) / 2; };      // int32 entries in a buffer of doubles
+  if ((rc = buf(vgpa_ctx::PF_XA, BnD)) || (rc = buf(vgpa_ctx::PF_XB, BnD)) || (rc = buf(vgpa_ctx::PF_LW, Bn)) || (rc = buf(vgpa_ctx::PF_CUM, Bn)) ||
+      (rc = buf(vgpa_ctx::PF_ANC, ints(Bn))) || (rc = buf(vgpa_ctx::PF_ESS, BM)) || (rc = buf(vgpa_ctx::PF_FLAG, ints(BM)))) return rc;
+  if (ancestors && (rc = buf(vgpa_ctx::PF_HANC, ints(BM * n)))) return rc;
+  if (clouds && (rc = buf(vgpa_ctx::PF_CLOUDS, BM * n * D))) return rc;
+  PfArgs f{};
+  f.D = D; f.batch = B; f.n_paths = n_paths; f.M = M1; f.seed = seed; f.ess_fraction = ess_fraction;
+  f.x0 = a.x0; f.m0 = a.m0; f.L0 = a.L0; f.m0_stride = a.m0_stride; f.L0_stride = a.L0_stride;
+  f.obs_const = a.obs_const; f.obs_const_v = a.obs_const_v; f.obs_const_scale = a.obs_const_scale;
+  f.obs_t = a.obs_t; f.obs_t_stride = a.obs_t_stride; f.n_obs = a.n_obs; f.n_obs_v = a.n_obs_v;
+  if (prior_mu && !x0) {
+    Rows<double> Lt;
+    bool lt_diag = true;
+    if ((rc = factor_rows(c, prior_tau, B, 1.0, "prior covariance", &c->d_pf[vgpa_ctx::PF_LT], &c->pf_n[vgpa_ctx::PF_LT], &Lt, &lt_diag))) return rc;
+    if ((rc = buf(vgpa_ctx::PF_MU, (size_t)B * D)) || (rc = upload(c, c->d_pf[vgpa_ctx::PF_MU], prior_mu, (size_t)B * D))) return rc;
+    f.mu0 = c->d_pf[vgpa_ctx::PF_MU]; f.Lt = c->d_pf[vgpa_ctx::PF_LT];
+  }
+  double* cur = c->d_pf[vgpa_ctx::PF_XA];
+  double* other = c->d_pf[vgpa_ctx::PF_XB];
+  f.x = cur; f.ws = other; f.lw = c->d_pf[vgpa_ctx::PF_LW]; f.cum = c->d_pf[vgpa_ctx::PF_CUM];
+  f.anc = reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_ANC]);
+  f.h_ess = c->d_pf[vgpa_ctx::PF_ESS]; f.h_flag = reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_FLAG]);
+  f.h_anc = ancestors ? reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_HANC]) : nullptr;
+  f.h_clouds = clouds ? c->d_pf[vgpa_ctx::PF_CLOUDS] : nullptr;
+  HIP_TRY(c, hipMemsetAsync(f.h_ess, 0, BM * sizeof(double), c->stream));
+  HIP_TRY(c, hipMemsetAsync(f.h_flag, 0, BM * sizeof(int32_t), c->stream));
+  if (f.h_anc) HIP_TRY(c, hipMemsetAsync(f.h_anc, 0xff, BM * n * sizeof(int32_t), c->stream));      // (-1 beyond a problem's own count)
+  LAUNCH_TRY(c, "particle start launch", launch_pf_start(f, c->stream));
+  // the cuts: the observation indices the kernels will see (each problem's own row and count in force), and the last grid index
+  std::vector<char> is_obs((size_t)Np, 0);
+  std::vector<int> count((size_t)B, M);
+  const bool own_t = c->in.obs_t.stride != 0;
+  for (int p = 0; p < B; p++) {
+    if (!c->h_nobs.empty()) count[p] = c->h_nobs[p];
+    const int64_t* t = own_t ? c->h_pp_obs_t.data() + (size_t)p * M : c->h_obs_t.data();
+    for (int m = 0; m < count[p]; m++) is_obs[(size_t)t[m]] = 1;
+  }
+  a.pf_lw = f.lw; a.seg_first = 1;
+  int prev = 0;
+  for (int k = 0; k < Np; k++) {
+    if (!is_obs[k] && k != Np - 1) continue;
+    a.k_begin = prev; a.k_end = k; a.pf_x = cur;
+    LAUNCH_TRY(c, "particle segment launch", launch_sample_segment(a, c->stream));
+    a.seg_first = 0; prev = k;
+    if (!is_obs[k]) continue;
+    f.k = k; f.last = k == Np - 1 ? 1 : 0; f.x_in = cur; f.x_out = other;
+    LAUNCH_TRY(c, "particle resampling launch", launch_pf_resample(f, c->stream));
+    std::swap(cur, other);
+  }
+  if ((rc = download(c, logw, f.lw, Bn)) || (rc = download(c, state, cur, BnD))) return rc;
+  if (ess && (rc = download(c, ess, f.h_ess, (size_t)B * M))) return rc;
+  if (resampled && M > 0) HIP_TRY(c, hipMemcpyAsync(resampled, f.h_flag, (size_t)B * M * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  if (ancestors && M > 0) HIP_TRY(c, hipMemcpyAsync(ancestors, f.h_anc, (size_t)B * M * n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  if (clouds)      // (only the rows below a problem's own count: the rest of the caller's array stays as it is)
+    for (int p = 0; p < B; p++)
+      if (count[p] > 0 && (rc = download(c, clouds + (size_t)p * M * n * D, f.h_clouds + (size_t)p * M * n * D, (size_t)count[p] * n * D))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return VGPA_OK;
 }
 
 int vgpa_fetch(vgpa_ctx* c, int which, double* out) {

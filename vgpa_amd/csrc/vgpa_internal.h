@@ -255,8 +255,43 @@ struct SampleArgs {
   double obs_const;         // the additive constant of E_obs as ObsArgs has it ...
   const double* obs_const_v;   // ... [B] instead of obs_const, or nullptr
   double obs_const_scale;   // ... and the factor E_obs gives it: 1/2 (n-D), 1 (1-D models, whose constant is halved already)
+  // a segment of the weighted walk (vgpa_particle_filter; launch_sample_segment): the grid steps k_begin < k <= k_end from
+  // and to pf_x, the path and observation increments added to pf_lw.  The observation cursor starts at 0 in the first segment (an
+  // observation at grid index 0 applies to the start), else behind k_begin.  x0 / m0 / L0 / out / logw / start are not read.
+  int seg_first, k_begin, k_end;
+  double* pf_x;             // [B][n_paths][D]
+  double* pf_lw;            // [B][n_paths]
 };
 hipError_t launch_sample_paths(const SampleArgs& a, hipStream_t st);
+hipError_t launch_sample_segment(const SampleArgs& a, hipStream_t st);
+
+// the start and the resampling step of the particle filter (sample.hip: k_pf_start, k_pf_resample)
+struct PfArgs {
+  int D, batch, n_paths, M;   // M: rows of the histories (the context's observation capacity)
+  uint64_t seed;
+  // start
+  const double* x0;         // [B][D] given start, or nullptr: m0 + L0 xi_0 as in SampleArgs
+  const double* m0; const double* L0;
+  size_t m0_stride, L0_stride;
+  const double* mu0;        // [B][D] prior mean and
+  const double* Lt;         // ... [B][D][D] lower factor of the prior covariance: init is evaluated; or nullptr (init = 0)
+  double obs_const; const double* obs_const_v; double obs_const_scale;   // as in SampleArgs
+  double* x;                // [B][n_paths][D] the particles
+  double* ws;               // [B][n_paths][D] work space
+  double* lw;               // [B][n_paths] log-weights (both kernels)
+  // resampling at grid index k
+  int k, last;              // last: k = Np - 1, where nothing is resampled
+  double ess_fraction;
+  const int64_t* obs_t; size_t obs_t_stride; int n_obs; const int32_t* n_obs_v;   // as in SampleArgs
+  const double* x_in; double* x_out;   // [B][n_paths][D] each
+  double* cum;              // [B][n_paths] prefix sums
+  int32_t* anc;             // [B][n_paths] ancestors of this step
+  double* h_ess; int32_t* h_flag;      // [B][M] each
+  int32_t* h_anc;           // [B][M][n_paths], or nullptr
+  double* h_clouds;         // [B][M][n_paths][D], or nullptr
+};
+hipError_t launch_pf_start(const PfArgs& a, hipStream_t st);
+hipError_t launch_pf_resample(const PfArgs& a, hipStream_t st);
 
 // launchers (each returns hipGetLastError()) -----------------------------------------------------
 hipError_t launch_ode_generic(int method, bool fwd, const OdeArgs& a, hipStream_t st);

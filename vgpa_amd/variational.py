@@ -178,6 +178,32 @@ class VarGP(object):
         out = [self._path_weights(logw[k], start[k], None if paths is None else paths[k], x0 is None) for k in range(logw.shape[0])]
         return out[0] if self.batch == 1 else out
 
+    def _particle_record(self, res, k, n_obs=None):
+        """One problem's ParticleFilterResult from row k of Context.particle_filter's dict, cut to its own n_obs observations"""
+        from .particles import ParticleFilterResult
+        m = res["ess"].shape[1] if n_obs is None else int(n_obs)
+        cut = lambda a: None if a is None else a[k, :m]      # noqa: E731
+        state, clouds = res["state"][k], cut(res["clouds"])
+        if self.model.single_dim:
+            state, clouds = state[..., 0], None if clouds is None else clouds[..., 0]
+        return ParticleFilterResult(res["log_w"][k], state, cut(res["ess"]), cut(res["resampled"]), cut(res["ancestors"]), clouds)
+
+    def _prior(self):
+        d = self.dim_d
+        return np.reshape(np.asarray(self.kl0.mu0, dtype=float), (1, d)), np.reshape(np.asarray(self.kl0.tau0, dtype=float), (1, d, d))
+
+    def particle_filter(self, n_paths, seed, ess_fraction=0.5, x=None, x0=None, history=False):
+        """A guided particle filter with the posterior process as its proposal: n_paths particles walk the recursion of sample_paths,
+        take in their weight against the model SDE and the data observation by observation, and are resampled (systematic) whenever
+        ESS < ess_fraction n_paths: a particles.ParticleFilterResult (with batch > 1 a list, one per problem).  The initial term uses the
+        prior of kl0 (0 when x0 is given).  ess_fraction=0 never resamples: the weights of importance_weights().  history=True keeps the
+        ancestors and the clouds at the observations (lineages()).  x=None: the (A_t, b_t) of the last free_energy.  From the first
+        resampling on a particle depends on n_paths."""
+        xx = None if x is None else np.asarray(x, dtype=float)
+        res = self._context().particle_filter(n_paths, seed, ess_fraction=ess_fraction, x=xx, x0=x0, prior=self._prior(), history=history)
+        out = [self._particle_record(res, k) for k in range(res["log_w"].shape[0])]
+        return out[0] if self.batch == 1 else out
+
     def fit_theta(self, x0, rounds, options=None):
         """Variational EM for the drift parameters (ProblemBatch.fit_theta on a batch of one): (x, F, theta, trace), theta in the
         shape of model.theta, trace["F"] of shape (rounds, 2, 1)."""
