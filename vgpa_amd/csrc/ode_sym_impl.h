@@ -294,6 +294,14 @@ __device__ __forceinline__ void build_tiles(int D, int wave, int lane, TileTab<N
 // HBM round trip in front of two of the four barriers of a step.  The waves of a workgroup exchange nothing through HBM.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// HBM accesses of the time loop: ldg / stg with the per-lane offset made opaque AT the access.  The offsets are table entries computed
+// before the loop; left alone, their zero-extension lives in another basic block than the access, instruction selection no longer sees
+// "wave-uniform base + 32-bit offset" and every access takes a 64-bit per-lane address (one v_lshl_add_u64 each, on the issue slots
+// the products need: see "What this role costs" at grad_waves).  Opaque here, the access is base in SGPRs + offset in one VGPR.  The
+// table entry itself is made opaque, in place (by reference): on a copy the compiler keeps the entry and moves it first, one v_mov each.
+__device__ __forceinline__ double ldgo(const double* base, unsigned& off8) { asm volatile("" : "+v"(off8)); return ldg(base, off8); }
+__device__ __forceinline__ void stgo(double* base, unsigned& off8, double v) { asm volatile("" : "+v"(off8)); stg(base, off8, v); }
+
 // Memory waits.  The compiler's wait-count pass cannot tell, across the loop back-edge, how old a loaded value is: the first
 // use of ANY value loaded in the previous iteration becomes s_waitcnt vmcnt(0) -- it waits for every load and store issued so
 // far.  So a step issues all its HBM loads at ONE point (behind the staging of stage min(1, NS-1): A, the forcing terms, the
@@ -378,7 +386,13 @@ __device__ __forceinline__ void grad_waves(const OdeArgs& a, double* __restrict_
   using gl = GradLds<NB>;
   constexpr int NT = 256, LD = g::LD, NKP = g::NKP, PP = g::PP;
   static_assert(NKP == 5 && g::NSB == 5, "the gradient product's units are laid out for 33 <= D <= 40");
-  constexpr unsigned GB = 8u * (unsigned)g::LDS_DOUBLES;       // byte offset of this role's LDS
+  // LDS addresses are 32-bit integers that INCLUDE the address of smem (the dynamic LDS symbol: zero, but not before the code is
+  // laid out -- as "smem + offset" every access carried a v_add_u32 of that zero, 67 per step): L0 goes into the tables, once.
+  typedef __attribute__((address_space(3))) char lds_char;
+  typedef __attribute__((address_space(3))) double lds_double;
+  typedef __attribute__((address_space(3))) d2_t lds_d2;
+  const unsigned L0 = (unsigned)(size_t)(lds_char*)reinterpret_cast<char*>(smem);
+  const unsigned GB = L0 + 8u * (unsigned)g::LDS_DOUBLES;      // address of this role's LDS
   constexpr unsigned SETB = 8u * (unsigned)g::XS;              // bytes between the two operand sets (Q^T, S)
   constexpr unsigned SETV = 8u * (unsigned)PP;                 // ... between the two vector sets (dt u, m)
   constexpr unsigned RB = 8u * 2u * (unsigned)g::XS;           // the start-point operand R (stage buffer 0 is at 0)
@@ -387,10 +401,9 @@ __device__ __forceinline__ void grad_waves(const OdeArgs& a, double* __restrict_
   const int prob = (int)blockIdx.x, D = a.D, Np = a.Np, DD = a.D * a.D, n_steps = a.Np - 1, PK = a.D * (a.D + 1) / 2;
   // (per-problem parameters: the problem's 1 / sigma_p^2, a scalar load -- prob is uniform)
   const double dt = a.dt, hq = -0.5 * (a.q_scale_v ? lds_const(a.q_scale_v, prob) : a.q_scale), m2dt = -2.0 * a.dt;
-  char* const lds = reinterpret_cast<char*>(smem);
-  auto rd2 = [&](unsigned off) -> d2_t { return *reinterpret_cast<const d2_t*>(lds + off); };
-  auto rd1 = [&](unsigned off) -> double { return *reinterpret_cast<const double*>(lds + off); };
-  auto wr1 = [&](unsigned off, double v) { *reinterpret_cast<double*>(lds + off) = v; };
+  auto rd2 = [&](unsigned adr) -> d2_t { return *(const lds_d2*)(size_t)adr; };
+  auto rd1 = [&](unsigned adr) -> double { return *(const lds_double*)(size_t)adr; };
+  auto wr1 = [&](unsigned adr, double v) { *(lds_double*)(size_t)adr = v; };
   auto tidx = [&](int i) { return Np - 1 - i; };
   const bool vl = lane < D;
   unsigned lane8 = vl ? 8u * (unsigned)lane : 0u;
@@ -407,7 +420,7 @@ __device__ __forceinline__ void grad_waves(const OdeArgs& a, double* __restrict_
     const int e = tid + NT * q;
     int p = e / g::P, c = e - p * g::P;
     if (!(2 * p < D && c < D)) { p = 0; c = 0; }         // (a duplicate of item (0, 0): same values to the same addresses)
-    it_rd[q] = 8u * (unsigned)unit_off<NB>(p, c);
+    it_rd[q] = L0 + 8u * (unsigned)unit_off<NB>(p, c);
     qt_w0[q] = GB + 8u * (unsigned)(gl::QT + elem_off<NB>(c, 2 * p));
     qt_w1[q] = GB + 8u * (unsigned)(gl::QT + elem_off<NB>(c, 2 * p + 1));      // (row 2p + 1 = D, D odd: a zero of the padding)
   }
@@ -463,9 +476,13 @@ __device__ __forceinline__ void grad_waves(const OdeArgs& a, double* __restrict_
       eo_o[u] = GB + 8u * (unsigned)(gl::O + ((row < D && col < D) ? row * D + col : PP * PP - 1));
     }
   }
-  unsigned oo[NOUT];                                     // the out-buffer's element tid + 256 q: the same offset in LDS and in gLa_t
+  unsigned oo[NOUT], ol[NOUT];                           // the out-buffer's element tid + 256 q: its offset in gLa_t, its LDS address
 #pragma unroll
-  for (int q = 0; q < NOUT; q++) { const int e = tid + NT * q; oo[q] = 8u * (unsigned)(e < DD ? e : DD - 1); }      // (beyond the matrix: a duplicate of its last element)
+  for (int q = 0; q < NOUT; q++) {
+    const int e = tid + NT * q;
+    oo[q] = 8u * (unsigned)(e < DD ? e : DD - 1);        // (beyond the matrix: a duplicate of its last element)
+    ol[q] = GB + 8u * (unsigned)gl::O + oo[q];           // (beyond the 16 bits of an LDS instruction's immediate: a table of its own)
+  }
 
   // The tables are all this role keeps across a step.  Left alone, the compiler hoists every address it can derive from them out of
   // the time loop and spills at the 168 registers of three waves per SIMD (and turns wave-uniform base + 32-bit offset into 64-bit
@@ -485,7 +502,7 @@ __device__ __forceinline__ void grad_waves(const OdeArgs& a, double* __restrict_
 #pragma unroll
     for (int u = 0; u < 7; u++) op(eo_o[u]);
 #pragma unroll
-    for (int q = 0; q < NOUT; q++) op(oo[q]);
+    for (int q = 0; q < NOUT; q++) { op(oo[q]); op(ol[q]); }
     op(m_w); op(blam); op(bu); op(lane8);
   };
 
@@ -496,11 +513,11 @@ __device__ __forceinline__ void grad_waves(const OdeArgs& a, double* __restrict_
     const size_t o = (size_t)prob * Np + tg;
     const double* Sp = a.S + o * PK;
 #pragma unroll
-    for (int q = 0; q < NPKI; q++) gsv[q] = ldg(Sp, s_g[q]);
-    gvm = ldg(a.m + o * D, lane8);
-    gvef = ldg(a.Ef + o * D, lane8);
-    gvam = ldg(a.Am + o * D, lane8);
-    gvb = ldg(a.b + (size_t)prob * a.strideB + (size_t)tg * D, lane8);
+    for (int q = 0; q < NPKI; q++) gsv[q] = ldgo(Sp, s_g[q]);
+    gvm = ldgo(a.m + o * D, lane8);
+    gvef = ldgo(a.Ef + o * D, lane8);
+    gvam = ldgo(a.Am + o * D, lane8);
+    gvb = ldgo(a.b + (size_t)prob * a.strideB + (size_t)tg * D, lane8);
   };
   auto settle_loads = [&]() {
 #pragma unroll
@@ -535,7 +552,7 @@ __device__ __forceinline__ void grad_waves(const OdeArgs& a, double* __restrict_
       const double r = -gvef - gvam + gvb;                     // -<f> - A m + b        (variational.py:325-337)
       const double udt = dt * __builtin_fma(-2.0 * hq, r, lam);      // dt (dEsde_db + lam)
       wr1(bu + SV, udt);
-      stg(gbase + (size_t)Np * DD + (size_t)tg * D, lane8, udt);
+      stgo(gbase + (size_t)Np * DD + (size_t)tg * D, lane8, udt);
     }
   };
   // k-pairs [KP0, KP1) of the product from operand set SET; unit = (row-side map, column-side map), accumulators carried across the barriers
@@ -605,9 +622,9 @@ __device__ __forceinline__ void grad_waves(const OdeArgs& a, double* __restrict_
     double* gA = gbase + (size_t)tg * DD;
     double v[NOUT];
 #pragma unroll
-    for (int q = 0; q < NOUT; q++) v[q] = rd1(oo[q] + GB + 8u * (unsigned)gl::O);
+    for (int q = 0; q < NOUT; q++) v[q] = rd1(ol[q]);
 #pragma unroll
-    for (int q = 0; q < NOUT; q++) stg(gA, oo[q], v[q]);
+    for (int q = 0; q < NOUT; q++) stgo(gA, oo[q], v[q]);
   };
   using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
   using I4 = std::integral_constant<int, 4>; using I5 = std::integral_constant<int, 5>;
@@ -800,21 +817,25 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3
   auto load_a = [&](const double* At) {
 #pragma unroll
     for (int q = 0; q < NITS; q++) {
-      an[q][0] = ldg(At, FWD ? TT.g0[q] : IT.g0[q]);
-      an[q][1] = ldg(At, FWD ? TT.g1[q] : IT.g1[q]);
+      an[q][0] = ldgo(At, FWD ? TT.g0[q] : IT.g0[q]);
+      an[q][1] = ldgo(At, FWD ? TT.g1[q] : IT.g1[q]);
     }
   };
   auto unit_ptr = [&](double* buf, int q) -> d2_t* {
     const int lo = FWD ? TT.lo[q] : IT.lo[q];
     return reinterpret_cast<d2_t*>(lo >= 0 ? buf + lo : trash);
   };
+  // The second element of a unit whose row 2p + 1 does not exist (D odd) is zero in LDS.  Decided ONCE per operand, where its loads
+  // are settled, not at every store: the mid-point 0.5 (R + an) of two masked units is +0.0 there as well (R was stored from a
+  // masked an), so store_a writes what it is given.
+  auto mask_a = [&]() {
+#pragma unroll
+    for (int q = 0; q < NITS; q++)
+      if (!(FWD ? TT.two[q] : IT.two[q])) an[q][1] = 0.0;
+  };
   auto store_a = [&](double* buf, const d2_t (&v)[NITS]) {
 #pragma unroll
-    for (int q = 0; q < NITS; q++) {
-      d2_t o = v[q];
-      if (!(FWD ? TT.two[q] : IT.two[q])) o[1] = 0.0;
-      *unit_ptr(buf, q) = o;
-    }
+    for (int q = 0; q < NITS; q++) *unit_ptr(buf, q) = v[q];
   };
   // ---- matrix state -----------------------------------------------------------------------------------------------------
   const int GS = (!FWD && a.ds_packed) ? D * (D + 1) / 2 : DD;      // doubles per matrix of the forcing-term stream
@@ -832,7 +853,7 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3
 
   // ---- vector state: every wave keeps the whole vector in its lanes < D (the other lanes compute along on element 0) ----
   const bool vl = lane < D;
-  const unsigned lane8 = vl ? 8u * (unsigned)lane : 0u;
+  unsigned lane8 = vl ? 8u * (unsigned)lane : 0u;        // (not const: ldgo / stgo make it opaque in place)
   double* const xv_mine = vl ? xvw + lane : trash;
   const double* cin = FWD ? a.b + (size_t)prob * a.strideB : a.dEm + (size_t)prob * Np * D;
   double* const vout = (FWD ? a.m : a.lam) + (size_t)prob * Np * D;
@@ -860,6 +881,7 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3
   }
   *xv_mine = vk;
   load_a(A + (size_t)tidx(0) * DD);
+  mask_a();
   store_a(Rb, an);
   load_a(A + (size_t)tclamp(1) * DD);
 #pragma unroll
@@ -867,18 +889,29 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3
   settle(c0); settle(c1); settle(vk); settle(jm);
 #pragma unroll
   for (int q = 0; q < NITS; q++) settle(an[q]);
+  mask_a();
+  // The forcing terms are kept as the accumulators start from them: minus the term on the lanes that own an element, zero on
+  // the others (their loads read element 0: finite, dropped here), halved on the diagonal of a loop unit (the in-block transpose adds
+  // the diagonal to itself).  Decided once per loaded term instead of once per stage; negation and the factor 0.5 commute exactly with
+  // the mid-point 0.5 (fn + fc) (powers of two, no underflow at the magnitudes of Sigma / dEsde_dS), so the bits are the same.
+  auto mask_f = [&](int s, double v) -> double {
+    if (COVER && s == kCoverLoopSlot) v *= loop_diag ? 0.5 : 1.0;
+    return own[s] ? -v : 0.0;
+  };
+#pragma unroll
+  for (int s = 0; s < MAXS; s++) { fc[s] = mask_f(s, fc[s]); if (!FWD) fn[s] = mask_f(s, fn[s]); }
   __syncthreads();                       // prologue published
 
   // S_k / Psi_t and m_k / lam_t of grid point t to HBM: the matrix from the stage buffer that holds it
   auto store_vector = [&](int t) {
-    if (wave == 0 && vl) stg(vout + vec(t), lane8, vk);
+    if (wave == 0 && vl) stgo(vout + vec(t), lane8, vk);
   };
   auto store_items = [&](const d2_t (&v)[g::NIT], int t, bool with_vector = true) {
     double* so = mout + (size_t)t * MS;
 #pragma unroll
     for (int q = 0; q < g::NIT; q++) {
-      if (IT.st0[q]) stg(so, IT.g0[q], v[q][0]);
-      if (IT.st1[q]) stg(so, IT.g1[q], v[q][1]);
+      if (IT.st0[q]) stgo(so, IT.g0[q], v[q][0]);
+      if (IT.st1[q]) stgo(so, IT.g1[q], v[q][1]);
     }
     if (with_vector) store_vector(t);
   };
@@ -895,12 +928,12 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3
     constexpr bool ch_a = !HLP || HK == 1 || HK == 3, ch_v = !HLP || HK == 1 || HK == 2, units = !HLP || HK == 0;
     if (LSTG == JSEC) {
       if (ch_a) load_a(A + (size_t)tclamp(step + 2) * DD);
-      if (ch_v) c2 = ldg(cin + vec(tclamp(step + 2)), lane8);
+      if (ch_v) c2 = ldgo(cin + vec(tclamp(step + 2)), lane8);
     }
     if (!FWD) {
       if (units) {
 #pragma unroll
-        for (int s = 0; s < MAXS; s++) fnn[s] = ldg(G + (size_t)tclamp(step + 2) * GS, gofs[s]);
+        for (int s = 0; s < MAXS; s++) fnn[s] = ldgo(G + (size_t)tclamp(step + 2) * GS, gofs[s]);
       }
       if (ch_v) jm_next = step + 2 <= n_steps ? jump_vector(tidx(step + 2), n_obs_next) : 0.0;
       n_obs_nn = (sparse_j && step + 3 <= n_steps) ? ldu(obs_idx, tidx(step + 3)) : -1;
@@ -926,6 +959,9 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3
   const int tb_part0 = tid / pdiv, tb_idx = tid - tb_part0 * pdiv;      // forward: idx = column i; backward: idx = row pair ip
   const bool tb_act = tb_part0 < (FWD ? g::NPF : g::NPARTB);
   const int tb_part = tb_act ? tb_part0 : 0;
+  // the parts tile the row pairs / column blocks exactly (every fragment-cover kernel): no entry of tailB is beyond the operand, and
+  // the guard that zeroes such entries is not compiled (tb_part < NPF, r < RPP => tb_part RPP + r < RP; backward alike)
+  constexpr bool TB_FULL = FWD ? (g::NPF * g::RPP == g::RP) : (g::NPARTB * g::CBP == g::NCB);
   // B: partial inner products of the vector recursion -> pv
   auto tailB_read = [&](const double* Aop) {
     if (FWD) {
@@ -955,7 +991,7 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3
     if (FWD) {
 #pragma unroll
       for (int r = 0; r < g::RPP; r++) {
-        const bool in = tb_part * g::RPP + r < g::RP;
+        const bool in = TB_FULL || tb_part * g::RPP + r < g::RP;
         s0 = __builtin_fma(tb_av[r][0], in ? tb_xqf[r][0] : 0.0, s0);
         s0 = __builtin_fma(tb_av[r][1], in ? tb_xqf[r][1] : 0.0, s0);
       }
@@ -963,7 +999,7 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3
     } else {
 #pragma unroll
       for (int q = 0; q < g::CBP; q++) {
-        const bool in = tb_part + q * g::NPARTB < g::NCB;
+        const bool in = TB_FULL || tb_part + q * g::NPARTB < g::NCB;
 #pragma unroll
         for (int kk = 0; kk < 4; kk++) {
           const double xv = in ? tb_xqb[4 * q + kk] : 0.0;
@@ -1014,7 +1050,7 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3
         store_a(dst, an);
       }
       if constexpr (GF) {                 // (Psi_t / Q''_t stay in the kernel; lam_t also goes to the gradient waves)
-        if (wave == 0 && vl) { stg(vout + vec(tidx(step)), lane8, vk); gLam[lane] = vk; }
+        if (wave == 0 && vl) { stgo(vout + vec(tidx(step)), lane8, vk); gLam[lane] = vk; }
       } else if (!(KIND == 3 && NS > 1)) store_items(tc_items, tidx(step), KIND == 1);
     }
     // (H2's staging helper is the longest chain of stage 0 -- units in, mid-point, operand out, state out -- and nearly idle in stages 1
@@ -1026,14 +1062,14 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3
     if (j == JSEC) prefetch(step, kind_);                  // (overwrites an[]: behind its last use of the step; with helper waves: their part)
     if (LSTG != JSEC && j == LSTG) {     // (helper-wave RK4 kernels: the next operand's loads behind the LAST stage's chores)
       load_a(A + (size_t)tclamp(step + 2) * DD);
-      if (KIND == 1) c2 = ldg(cin + vec(tclamp(step + 2)), lane8);
+      if (KIND == 1) c2 = ldgo(cin + vec(tclamp(step + 2)), lane8);
     }
   };
   // H2, role 1: what tailC does for the vector -- its way to HBM (stage 0) and its HBM loads
   auto vec_chores = [&](int j, int step) {
     if (j == 0) store_vector(tidx(step));
     if (j == JSEC) prefetch(step, K2{});
-    if (LSTG != JSEC && j == LSTG) c2 = ldg(cin + vec(tclamp(step + 2)), lane8);
+    if (LSTG != JSEC && j == LSTG) c2 = ldgo(cin + vec(tclamp(step + 2)), lane8);
   };
 
   // behind the barrier of stage j: every wave sums the partial products and advances its copy of the vector
@@ -1164,14 +1200,14 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3
     double jsd[MAXS];
     if (!FWD && last && DENSEJ) {        // dense matrix jump behind the step (euler.py:139-149): requested before the products
 #pragma unroll
-      for (int s = 0; s < MAXS; s++) jsd[s] = ldg(a.js_dense + ((size_t)prob * Np + tidx(step + 1)) * DD, gofs[s]);
+      for (int s = 0; s < MAXS; s++) jsd[s] = ldgo(a.js_dense + ((size_t)prob * Np + tidx(step + 1)) * DD, gofs[s]);
     }
     if (!FWD && last && !DENSEJ) {       // the constant matrix jump 0.5 H^T R^-1 H, only behind a step that ends at an observation:
 #pragma unroll                           // fetched (L2) when it is needed instead of riding in eight registers through every step
       for (int s = 0; s < MAXS; s++) jsd[s] = 0.0;
       if (jump_now && a.js_const) {
 #pragma unroll
-        for (int s = 0; s < MAXS; s++) jsd[s] = ldg(PJ ? a.js_const + (size_t)prob * a.js_const_stride : a.js_const, gofs[s]);      // (PJ: the problem's own row, OdeArgs::js_const_stride; prob is uniform)
+        for (int s = 0; s < MAXS; s++) jsd[s] = ldgo(PJ ? a.js_const + (size_t)prob * a.js_const_stride : a.js_const, gofs[s]);      // (PJ: the problem's own row, OdeArgs::js_const_stride; prob is uniform)
       }
     }
     double w[NSL];
@@ -1190,8 +1226,7 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3
             else if (METHOD == VGPA_ODE_HEUN) f = j == 0 ? fc[s] : fn[s];
             else if (METHOD == VGPA_ODE_RK2) f = j == 0 ? fc[s] : 0.5 * (fn[s] + fc[s]);
             else f = j == 0 ? fc[s] : (j == 3 ? fn[s] : 0.5 * (fn[s] + fc[s]));
-            f = own[s] ? -f : 0.0;
-            if (COVER && s == kCoverLoopSlot) f = loop_diag ? 0.5 * f : f;     // (the in-block transpose below adds the diagonal to itself)
+            // (fc / fn are minus the term, masked to the owners, halved on a loop unit's diagonal: mask_f)
           }
           w[u] = f;
         }
@@ -1341,11 +1376,12 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3
       if (!HLP || HK == 1 || HK == 3) {
 #pragma unroll
         for (int q = 0; q < NITS; q++) settle(an[q]);
+        mask_a();
       }
       if (!FWD) {
         if (!HR) {
 #pragma unroll
-          for (int s = 0; s < MAXS; s++) { fc[s] = fn[s]; fn[s] = fnn[s]; }
+          for (int s = 0; s < MAXS; s++) { fc[s] = fn[s]; fn[s] = mask_f(s, fnn[s]); }
         }
         n_obs_cur = n_obs_next; n_obs_next = n_obs_nn;
       }
@@ -1423,7 +1459,7 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3
   }
   if (H2 && role == 1) { store_vector(tidx(n_steps)); return; }
   if constexpr (GF) {
-    if (wave == 0 && vl) { stg(vout + vec(tidx(n_steps)), lane8, vk); gLam[lane] = vk; }
+    if (wave == 0 && vl) { stgo(vout + vec(tidx(n_steps)), lane8, vk); gLam[lane] = vk; }
     lds_barrier(); lds_barrier(); lds_barrier(); lds_barrier();
   } else {
     d2_t items[g::NIT];
