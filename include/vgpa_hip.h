@@ -280,6 +280,26 @@ int vgpa_particle_filter(vgpa_ctx* ctx, const double* x_or_null, const double* x
                          const double* prior_mu_or_null, const double* prior_tau_or_null, double* logw, double* state, double* ess_or_null,
                          int32_t* resampled_or_null, int32_t* ancestors_or_null, double* clouds_or_null);
 
+/* The path statistics of the particle filter's lineages: the complete-data sufficient statistics of (theta, Sigma) of the
+ * Euler-discretised model, whose weighted mean is, by Fisher's identity, the score and the exact EM step in theta under the smoothing
+ * distribution of the particles.  The walk, the counters and the resampling decisions are those of vgpa_particle_filter; every slot i carries
+ * a row [3][D] = (Q, G, H) that starts at 0 and to which every step k = 1 .. Np-1 adds, per component j < D,
+ *   Q_j += r_j^2 / dt,   G_j += phi_j r_j,   H_j += dt phi_j^2
+ *   r = x_k - x_{k-1} - dt f_theta(x_{k-1}) = dt (g - f_theta(x_{k-1})) + eta_k, with the g, f and eta of the weighted walk
+ *   phi_j = d f_j / d theta_a(j) at x_{k-1}:  OU -x;  double well 4 x;  Lorenz-63 (y - x, x, -z) for (sigma, rho, beta);  Lorenz-96 1
+ *            (5 <= D: H_j = dt (Np - 1) is a constant, written and not summed)
+ * At a resampling slot i takes the row of its ancestor, as it takes x.  The observation and initial terms add nothing.  theta, Sigma, the
+ * data and the observation model are the rows in force.
+ *   stats_or_null  host, [batch][n_paths][3][D]: the final rows, in the order (Q, G, H)
+ *   mean_or_null   host, [batch][3][D]: sum_i w_i row_i / sum_i w_i with w_i = exp(lw_i - max lw), reduced on the device
+ *   at least one of the two must be given
+ *   logw, state, ess_or_null, resampled_or_null and every other argument: as in vgpa_particle_filter, and bit-identical to its results with
+ *   the same arguments; with x NULL the cached state is read and not written
+ * Errors: as vgpa_particle_filter, and VGPA_ERR_ARG when stats and mean are both NULL. */
+int vgpa_particle_statistics(vgpa_ctx* ctx, const double* x_or_null, const double* x0_or_null, int32_t n_paths, uint64_t seed, double ess_fraction,
+                             const double* prior_mu_or_null, const double* prior_tau_or_null, double* logw, double* state,
+                             double* stats_or_null, double* mean_or_null, double* ess_or_null, int32_t* resampled_or_null);
+
 /* device-pointer variants (x, g on the context's device; f written to HOST after a sync) ------ */
 int vgpa_sweep_dev(vgpa_ctx* ctx, const double* x_dev, double* f_host, double* g_dev);
 int vgpa_free_energy_dev(vgpa_ctx* ctx, const double* x_dev, double* f_host);

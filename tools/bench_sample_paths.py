@@ -1,8 +1,9 @@
 """
-Time of Context.sample_paths (vgpa_sample_paths), Context.sample_paths_weighted (vgpa_sample_paths_weighted) and Context.particle_filter
-(vgpa_particle_filter) on their jobs, one JSON line.
+Time of Context.sample_paths (vgpa_sample_paths), Context.sample_paths_weighted (vgpa_sample_paths_weighted), Context.particle_filter
+(vgpa_particle_filter) and Context.particle_statistics (vgpa_particle_statistics) on their jobs, one JSON line.
 
     python tools/bench_sample_paths.py [--rounds 3] [--calls 5] [--jobs a,b,c,aw,aw0,bw,bw0,af64_0,af64_5,af1024_0,af1024_5,bf64_0,...]
+    python tools/bench_sample_paths.py --statistics [--filter-problems 4096]      # the as* and bs* jobs
 
   a   posterior kind, Lorenz-96, D = 40, Np = 1001, B = 512:   64 paths per problem, stride 100
   b   posterior kind, Lorenz-63, Np = 1001, B = 65536:          1 path per problem,  stride 100
@@ -12,6 +13,10 @@ Time of Context.sample_paths (vgpa_sample_paths), Context.sample_paths_weighted 
   af<n>_<f>, bf<n>_<f>   the particle filter on the contexts of a and b: n = 64 or 1024 particles per problem, ess_fraction f = 0 (never
              resampled: the weights of aw0 / bw0, cut at the observations) or 5 (0.5), histories off; --filter-problems caps B of the
              b context's filter jobs (1024 particles on 65536 problems are 1.6 GB of final states to copy)
+
+  as<n>_<f>, bs<n>_<f>   (--statistics selects all eight) particle_statistics with the arguments of af<n>_<f> / bf<n>_<f>, the mean reduced on
+             the device and no rows copied, and particle_filter itself, the two calls alternating inside every round: both times and their
+             ratio
 
 The posterior jobs read the x a free_energy_dev left cached (x=None: nothing is uploaded); every job draws its start from (m0, S0).  A call
 is timed with a pair of device events on the context's stream around it -- the host work of the call (the Cholesky factors), the kernel and
@@ -40,6 +45,7 @@ HBM_BYTES_PER_S = 8.0e12
 JOBS = {"a": ("L96", 40, 512, "posterior", 64, 100), "b": ("L63", 3, 65536, "posterior", 1, 100), "c": ("L63", 3, 65536, "model", 1, 1)}
 WEIGHTED = {"aw": ("a", True), "aw0": ("a", False), "bw": ("b", True), "bw0": ("b", False)}      # job -> (its unweighted twin, paths stored)
 FILTER = {f"{t}f{n}_{f}": (t, n, 0.1 * f) for t in "ab" for n in (64, 1024) for f in (0, 5)}      # job -> (context of, particles, ess_fraction)
+STATS = {f"{t}s{n}_{f}": (t, n, 0.1 * f) for t in "ab" for n in (64, 1024) for f in (0, 5)}       # job -> as FILTER
 N_PTS, DT = 1001, 0.01
 
 
@@ -72,10 +78,10 @@ def run(job, rounds, calls, numpy_problems, cache, filter_problems=0):
     from bench_problem_batch import StreamTimer, make_contexts
     twin, stored = WEIGHTED.get(job, (job, True))
     weighted = job in WEIGHTED
-    if job in FILTER:
-        twin = FILTER[job][0]
+    if job in FILTER or job in STATS:
+        twin = (FILTER.get(job) or STATS[job])[0]
     name, d, B, kind, n_paths, stride = JOBS[twin]
-    if job in FILTER and twin == "b" and filter_problems:
+    if (job in FILTER or job in STATS) and twin == "b" and filter_problems:
         B = min(B, filter_problems)
     if (name, B) not in cache:                        # (b and c share a context)
         from helpers import SEED, build_problem
@@ -91,6 +97,29 @@ def run(job, rounds, calls, numpy_problems, cache, filter_problems=0):
     c, xb, x_row, p0, tm = cache[(name, B)]
     len_x = N_PTS * d * (d + 1)
     n_keep = (N_PTS - 1) // stride + 1
+    if job in STATS:
+        _, n_paths, frac = STATS[job]
+        calls_of = {"filter": lambda: c.particle_filter(n_paths, 1, ess_fraction=frac),
+                    "statistics": lambda: c.particle_statistics(n_paths, 1, ess_fraction=frac)}
+        res0 = {k: f() for k, f in calls_of.items()}      # warm-up (first-use allocations)
+        assert all(np.array_equal(res0["filter"][k], res0["statistics"][k]) for k in ("log_w", "state", "ess", "resampled"))
+        assert res0["statistics"]["mean"].shape == (B, 3, d) and np.all(np.isfinite(res0["statistics"]["mean"]))
+        per_round = {k: [] for k in calls_of}
+        for _ in range(rounds):
+            ms = {k: [] for k in calls_of}
+            for _ in range(calls):
+                for k, f in calls_of.items():
+                    ms[k].append(tm.ms(f))
+            for k in calls_of:
+                per_round[k].append(float(np.median(ms[k])))
+        med = {k: float(np.median(v)) for k, v in per_round.items()}
+        return {"job": job, "model": name, "D": d, "Np": N_PTS, "B": B, "kind": "statistics", "n_paths": n_paths, "ess_fraction": frac,
+                "statistics_ms_per_call": round(med["statistics"], 4), "filter_ms_per_call": round(med["filter"], 4),
+                "ratio": round(med["statistics"] / med["filter"], 4),
+                "statistics_rounds_ms": [round(v, 4) for v in per_round["statistics"]],
+                "filter_rounds_ms": [round(v, 4) for v in per_round["filter"]],
+                "observations": int(c.n_obs), "resampled_share": round(float(res0["filter"]["resampled"].mean()), 3),
+                "d2h_mb": round(8.0 * B * (n_paths * (1 + d) + 3 * d) / 1e6, 1)}
     if job in FILTER:
         _, n_paths, frac = FILTER[job]
         call = lambda: c.particle_filter(n_paths, 1, ess_fraction=frac)      # noqa: E731
@@ -135,7 +164,10 @@ def main():
     ap.add_argument("--jobs", default="a,b,c")
     ap.add_argument("--numpy-problems", type=int, default=2)
     ap.add_argument("--filter-problems", type=int, default=0, help="cap on B of the b context's filter jobs (0: none)")
+    ap.add_argument("--statistics", action="store_true", help="run the as* and bs* jobs (particle_statistics beside particle_filter)")
     args = ap.parse_args()
+    if args.statistics:
+        args.jobs = ",".join(sorted(STATS))
     cache = {}
     out = {"tool": "bench_sample_paths", "tree": tree(), "unit": "ms per call (device events around the call)", "jobs": []}
     for job in [j for j in args.jobs.split(",") if j]:

@@ -36,7 +36,7 @@ BWD_IDS = {"none": 0, "psi": 1, "q": 2}
 SYMBOLS = ["vgpa_create", "vgpa_destroy", "vgpa_last_error", "vgpa_abi_version", "vgpa_device_count",
            "vgpa_synchronize", "vgpa_stream", "vgpa_solve_fwd", "vgpa_solve_bwd", "vgpa_energy",
            "vgpa_obs_energy", "vgpa_free_energy", "vgpa_gradient", "vgpa_sweep", "vgpa_energy_parts",
-           "vgpa_fetch", "vgpa_theta_gradient", "vgpa_sample_paths", "vgpa_sample_paths_weighted", "vgpa_particle_filter", "vgpa_sweep_dev", "vgpa_free_energy_dev", "vgpa_sweep_enqueue", "vgpa_fetch_f",
+           "vgpa_fetch", "vgpa_theta_gradient", "vgpa_sample_paths", "vgpa_sample_paths_weighted", "vgpa_particle_filter", "vgpa_particle_statistics", "vgpa_sweep_dev", "vgpa_free_energy_dev", "vgpa_sweep_enqueue", "vgpa_fetch_f",
            "vgpa_dev_alloc", "vgpa_dev_free", "vgpa_memcpy_h2d", "vgpa_memcpy_d2h",
            "vgpa_profile_begin", "vgpa_profile_end", "vgpa_ld_gemm", "vgpa_ld_stage", "vgpa_gradient_dev", "vgpa_energy_full", "vgpa_set_option", "vgpa_is_streaming", "vgpa_path_info", "vgpa_set_prior_energy",
            "vgpa_set_problem_data", "vgpa_set_problem_params", "vgpa_set_problem_obs_model",
@@ -137,6 +137,8 @@ def load():
     lib.vgpa_sample_paths_weighted.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_uint64, c_void_p, c_void_p, c_void_p]
     lib.vgpa_particle_filter.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_uint64, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.vgpa_particle_statistics.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_uint64, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vgpa_sweep_dev.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vgpa_free_energy_dev.argtypes = [c_void_p, c_void_p, c_void_p]
     lib.vgpa_sweep_enqueue.argtypes = [c_void_p, c_void_p, c_void_p]
@@ -604,6 +606,30 @@ class Context:
                                                    _ptr(mu), _ptr(tau), _ptr(log_w), _ptr(state), _ptr(ess), _ptr(flags), _ptr(anc),
                                                    _ptr(clouds)))
         return {"log_w": log_w, "state": state, "ess": ess, "resampled": flags, "ancestors": anc, "clouds": clouds}
+
+    def particle_statistics(self, n_paths, seed, ess_fraction=0.5, x=None, x0=None, prior=None, per_particle=False):
+        """The path statistics of particle_filter's lineages (vgpa_particle_statistics): the same walk and resampling decisions, every slot
+        carrying its row (Q, G, H) of sum_k r^2 / dt, sum_k phi r, sum_k dt phi^2.  Returns a dict: log_w, state, ess, resampled as
+        particle_filter (bit for bit), mean (B, 3, D): the self-normalised weighted mean of the rows, reduced on the device, and stats
+        (B, n_paths, 3, D): the rows themselves (per_particle=True, else None)."""
+        n_paths, m = int(n_paths), self.n_obs
+        xx = None if x is None else _c64(x)
+        if xx is not None and xx.size != self.B * self.len_x:
+            raise ValueError(f"x has {xx.size} entries, expected {self.B * self.len_x}")
+        s0 = None if x0 is None else _c64(np.broadcast_to(np.asarray(x0, dtype=np.float64).reshape(-1, self.D), (self.B, self.D)))
+        mu = tau = None
+        if prior is not None:
+            mu = _c64(np.broadcast_to(np.asarray(prior[0], dtype=np.float64).reshape(-1, self.D), (self.B, self.D)))
+            tau = _c64(np.broadcast_to(np.asarray(prior[1], dtype=np.float64).reshape(-1, self.D, self.D), (self.B, self.D, self.D)))
+        n = max(n_paths, 0)
+        log_w, state = np.empty((self.B, n)), np.empty((self.B, n, self.D))
+        ess, flags = np.zeros((self.B, m)), np.zeros((self.B, m), dtype=np.int32)
+        mean = np.empty((self.B, 3, self.D))
+        stats = np.empty((self.B, n, 3, self.D)) if per_particle else None
+        self._check(self._lib.vgpa_particle_statistics(self._h, _ptr(xx), _ptr(s0), n_paths, int(seed) & 0xFFFFFFFFFFFFFFFF, float(ess_fraction),
+                                                       _ptr(mu), _ptr(tau), _ptr(log_w), _ptr(state), _ptr(stats), _ptr(mean), _ptr(ess),
+                                                       _ptr(flags)))
+        return {"log_w": log_w, "state": state, "ess": ess, "resampled": flags, "mean": mean, "stats": stats}
 
     def fetch(self, key):
         which = FETCH_IDS[key]

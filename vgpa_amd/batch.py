@@ -216,6 +216,55 @@ class ProblemBatch(object):
         res = self._context().particle_filter(n_paths, seed, ess_fraction=ess_fraction, x=xx, x0=x0, prior=prior, history=history)
         return [v._particle_record(res, k, np.asarray(v._inputs()["obs_t"]).size) for k, v in enumerate(self.vgps)]
 
+    def particle_statistics(self, n_paths, seed, ess_fraction=0.5, x=None, x0=None, per_particle=False):
+        """One particles.PathStatistics per member (VarGP.particle_statistics): the filter of particle_filter with the same arguments, each
+        particle carrying the path statistics of its lineage under the member's own theta, Sigma, data and observation model."""
+        xx = None if x is None else self._stack(x)
+        d = self.vgps[0].dim_d
+        prior = (np.stack([v._prior()[0][0] for v in self.vgps]), np.stack([v._prior()[1][0] for v in self.vgps]).reshape(self.B, d, d))
+        res = self._context().particle_statistics(n_paths, seed, ess_fraction=ess_fraction, x=xx, x0=x0, prior=prior, per_particle=per_particle)
+        return [v._statistics_record(res, k, np.asarray(v._inputs()["obs_t"]).size) for k, v in enumerate(self.vgps)]
+
+    def particle_fit_theta(self, n_paths, seed, iters, ess_fraction=0.5, refit=True, pooled=False, x0=None, options=None):
+        """
+        Particle EM for the drift parameters under the smoothing distribution of the Euler-discretised model, free of the variational
+        bias of fit_theta.  Per iteration i: (1) refit=True: optimise (A_t, b_t) from the current x at the current theta -- the posterior
+        process is the proposal, the better it fits the fewer particles are needed; (2) particle_statistics(n_paths, seed + i); (3)
+        theta <- theta + score / information (PathStatistics.theta_step), each member with its own Sigma.  pooled=True: the members share
+        one theta and move by sum_p score / sum_p information, as theta_mstep(pooled=True).  x0 (B, len_x): the first (A_t, b_t),
+        initialization() by default.  The new theta is written to every member's model.theta.
+        There is no Sigma step: paths imputed at a fixed Sigma have quadratic variation Sigma T as dt -> 0, so Sigma <- E[Q] / n_steps
+        barely moves (particles.py).
+        Returns (theta (B, n_theta), trace) with trace["theta"] (iters + 1, B, n_theta): theta before the first and after every step,
+        trace["log_evidence"] (iters, B): the evidence estimate at the theta each step started from, trace["score"] and
+        trace["information"] (iters, B, n_theta), trace["x"] (iters, B, len_x): the (A_t, b_t) each step's particles were proposed from.
+        """
+        if self.B > 1 and not pooled and not self.own_parameters:
+            raise ValueError(" ProblemBatch.particle_fit_theta: a batch that shares one theta moves it by the pooled step (pooled=True), "
+                             "or every member keeps its own (own_parameters=True).")
+        x = self.initialization() if x0 is None else self._stack(x0).copy()
+        trace = {"theta": [self._theta_rows()], "x": [], "log_evidence": [], "score": [], "information": []}
+        for it in range(int(iters)):
+            if refit:
+                x, _, _ = self.optimise(x, options)
+                x = np.array(x, dtype=float)
+            recs = self.particle_statistics(n_paths, int(seed) + it, ess_fraction=ess_fraction, x=x)
+            sig = [np.asarray(v._inputs()["sigma"], dtype=float).reshape(self.dim_d, self.dim_d).diagonal() for v in self.vgps]
+            trace["x"].append(x.copy())
+            score = np.stack([r.score(s) for r, s in zip(recs, sig)])
+            info = np.stack([r.information(s) for r, s in zip(recs, sig)])
+            step = np.broadcast_to(score.sum(axis=0) / info.sum(axis=0), score.shape) if pooled else score / info
+            new = self._theta_rows() + step
+            for vgp, row in zip(self.vgps, new):
+                vgp.model.theta = float(row[0]) if row.size == 1 else row.copy()
+            trace["theta"].append(new)
+            trace["log_evidence"].append([r.log_evidence() for r in recs])
+            trace["score"].append(score)
+            trace["information"].append(info)
+        for key in trace:
+            trace[key] = np.asarray(trace[key])
+        return self._theta_rows(), trace
+
     def _theta_rows(self):
         return np.stack([np.atleast_1d(np.asarray(v.model.theta, dtype=float)) for v in self.vgps])
 

@@ -11,6 +11,9 @@
 // k_sample_small<D, true, true> and k_sample_mfma<NT, true, true> (vgpa_particle_filter) are their segment twins: the grid
 // steps k_begin < k <= k_end from the particle states in SampleArgs::pf_x, the increments added to the log-weights in pf_lw, the end states
 // written back.  k_pf_start draws the particles and their initial term; k_pf_resample is the step between two segments.
+// k_sample_small<D, true, true, true> and k_sample_mfma<NT, true, true, true> (vgpa_particle_statistics) are the segments
+// that also carry each slot's [3][D] row of path statistics (SampleArgs::pf_stats); k_pf_resample<true> gathers the rows by ancestor with
+// the states, k_pf_stats_mean reduces them to their self-normalised weighted mean.
 #include "vgpa_internal.h"
 
 namespace vgpa {
@@ -62,6 +65,19 @@ __device__ __forceinline__ void model_drift(int model, const double* th, const d
   }
 }
 
+// phi_j = d f_j / d theta_a(j) at x, a(j) the one parameter component j's drift depends on
+template <int D>
+__device__ __forceinline__ void model_phi(int model, const double* x, double* phi) {
+  if (model == VGPA_MODEL_OU) { phi[0] = -x[0]; }
+  else if (model == VGPA_MODEL_DW) { phi[0] = 4.0 * x[0]; }
+  else if (model == VGPA_MODEL_L63) {
+    if constexpr (D == 3) { phi[0] = x[1] - x[0]; phi[1] = x[0]; phi[2] = -x[2]; }
+  } else {
+#pragma unroll
+    for (int i = 0; i < D; i++) phi[i] = 1.0;
+  }
+}
+
 // the observation row of one problem as a weighted kernel walks it: next = the grid index of the next observation, or -1 behind the last one
 struct ObsCursor {
   const int64_t* t;
@@ -98,9 +114,11 @@ __device__ __forceinline__ double obs_constant(const SampleArgs& a, uint32_t p) 
 // W: the weighted instantiation (posterior kind, diagonal R): both drifts at x_{k-1}, d = g - f, and per step
 // -sum_i d_i (eta_i + dt d_i / 2) / Sigma_ii with 1 / Sigma_ii = dt / R_ii^2; the observation term at the lane's own problem's times
 // SEG: a segment of the weighted walk (k_begin, k_end] from and to pf_x, the sums added to pf_lw; nothing else is stored
-template <int D, bool W, bool SEG = false>
+// ST: a segment that adds its steps to the slot's row of pf_stats: Q_i += r^2 / dt, G_i += phi_i r, H_i += dt phi_i^2 with r = dt d + eta
+template <int D, bool W, bool SEG = false, bool ST = false>
 __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
   static_assert(W || !SEG, "a segment is a weighted walk");
+  static_assert(SEG || !ST, "the statistics are carried by the segments");
   const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (gid >= (size_t)a.batch * a.n_paths) return;
   const uint32_t p = (uint32_t)(gid / a.n_paths), path = (uint32_t)(gid % a.n_paths);
@@ -157,6 +175,13 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
     if constexpr (SEG) { if (!a.seg_first) oc.skip_through(a.k_begin); }
     if (oc.next == 0) { ow += obs_form<D>(a, p, oc.cur, x); oc.advance(); }
   }
+  double sq[ST ? D : 1], sg1[ST ? D : 1], sh[ST ? D : 1], phi[ST ? D : 1];
+  if constexpr (ST) {
+#pragma unroll
+    for (int i = 0; i < D; i++) {
+      sq[i] = a.pf_stats[gid * 3 * D + i]; sg1[i] = a.pf_stats[gid * 3 * D + D + i]; sh[i] = a.pf_stats[gid * 3 * D + 2 * D + i];
+    }
+  }
   const double* A = a.A + (size_t)p * a.stride_x;
   const double* bv = a.b + (size_t)p * a.stride_x;
   int until = a.stride, slot = 0;
@@ -179,12 +204,17 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
     }
 #pragma unroll
     for (int j = 0; j < NP; j++) normal_pair(k0, k1, (uint32_t)k, path, p, (uint32_t)j, &z[2 * j], &z[2 * j + 1]);
+    if constexpr (ST) model_phi<D>(a.model, x, phi);
 #pragma unroll
     for (int i = 0; i < D; i++) {
       double s = 0.0;
 #pragma unroll
       for (int j = 0; j <= i; j++) s += R[i * D + j] * z[j];
       if constexpr (W) { const double d = f[i] - fm[i]; pw -= isg[i] * d * (s + 0.5 * a.dt * d); }
+      if constexpr (ST) {
+        const double r = a.dt * (f[i] - fm[i]) + s;
+        sq[i] += r * r / a.dt; sg1[i] += phi[i] * r; sh[i] += a.dt * (phi[i] * phi[i]);
+      }
       x[i] = (x[i] + a.dt * f[i]) + s;
     }
     if constexpr (W) {
@@ -207,6 +237,12 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
     a.pf_lw[gid] += pw - 0.5 * ow;
 #pragma unroll
     for (int i = 0; i < D; i++) a.pf_x[gid * D + i] = x[i];
+    if constexpr (ST) {
+#pragma unroll
+      for (int i = 0; i < D; i++) {
+        a.pf_stats[gid * 3 * D + i] = sq[i]; a.pf_stats[gid * 3 * D + D + i] = sg1[i]; a.pf_stats[gid * 3 * D + 2 * D + i] = sh[i];
+      }
+    }
   } else if constexpr (W) { a.logw[2 * gid] = pw; a.logw[2 * gid + 1] = -0.5 * ow - obs_constant(a, p); }
 }
 
@@ -247,9 +283,12 @@ __device__ __forceinline__ void normals_c(uint32_t k0, uint32_t k1, uint32_t k, 
 // time; the four q-lanes of a path are added once at the end.  The observation term is evaluated from Xs at the problem's observation times,
 // which a workgroup walks with one cursor.
 // SEG: as in k_sample_small; A_{k_begin} is the first matrix loaded, and the end states leave through `put` as [path][D].
-template <int NT, bool W, bool SEG = false>
+// ST: the lane adds r^2 / dt and r = dt d + eta (phi = 1: Lorenz-96) of its own rows to Q and G of the path's row of pf_stats, read at the
+// segment's entry and written at its exit; H_j = dt k_end, the constant dt times the steps walked so far, is written and not summed.
+template <int NT, bool W, bool SEG = false, bool ST = false>
 __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
   static_assert(W || !SEG, "a segment is a weighted walk");
+  static_assert(SEG || !ST, "the statistics are carried by the segments");
   using Sh = MfmaShape<NT>;
   constexpr int LDA = Sh::LDA, MT = Sh::MT, KT = Sh::KT, NPF = Sh::NPF;
   extern __shared__ double lds[];
@@ -341,6 +380,18 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
   };
   // weighted: 1 / Sigma_ii of the lane's rows, the two sums, theta, the observation cursor
   double isg[W ? MT : 1][4], pw = 0.0, ow = 0.0, th = 0.0;
+  double sq[ST ? MT : 1][4], sg1[ST ? MT : 1][4];
+  if constexpr (ST) {
+    const double* row0 = a.pf_stats + ((size_t)p * a.n_paths + path) * 3 * D;
+#pragma unroll
+    for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const int row = mt * 16 + q + 4 * r;
+        const bool mine = path < (uint32_t)a.n_paths && row < D;
+        sq[mt][r] = mine ? row0[row] : 0.0; sg1[mt][r] = mine ? row0[D + row] : 0.0;
+      }
+  }
   ObsCursor oc;
   if constexpr (W) oc = ObsCursor(a, p);
   if constexpr (SEG) { if (!a.seg_first) oc.skip_through(a.k_begin); }
@@ -437,6 +488,7 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
             const double f = (xu - xd2) * xd1 - x[mt][r] + th;
             const double d = (bs[row] - acc[r]) - f;
             pw -= isg[mt][r] * d * (nz[r] + 0.5 * a.dt * d);
+            if constexpr (ST) { const double res = a.dt * d + nz[r]; sq[mt][r] += res * res / a.dt; sg1[mt][r] += res; }
           }
         }
       }
@@ -465,6 +517,19 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
     if constexpr (SEG) {
       if (q == 0 && path < (uint32_t)a.n_paths) a.pf_lw[(size_t)p * a.n_paths + path] += pw - 0.5 * ow;
       put(a.pf_x + ((size_t)p * a.n_paths + path0) * D, (size_t)D);      // (Xs holds x_{k_end} behind the loop's last barrier)
+      if constexpr (ST) {
+        if (path < (uint32_t)a.n_paths) {
+          double* row0 = a.pf_stats + ((size_t)p * a.n_paths + path) * 3 * D;
+          const double h = a.dt * (double)a.k_end;
+#pragma unroll
+          for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+              const int row = mt * 16 + q + 4 * r;
+              if (row < D) { row0[row] = sq[mt][r]; row0[D + row] = sg1[mt][r]; row0[2 * D + row] = h; }
+            }
+        }
+      }
     } else if (q == 0 && path < (uint32_t)a.n_paths) {
       double* lw = a.logw + 2 * ((size_t)p * a.n_paths + path);
       lw[0] = pw; lw[1] = -0.5 * ow - obs_constant(a, p);
@@ -550,12 +615,12 @@ hipError_t launch_mfma(const SampleArgs& a, hipStream_t st) {
 }
 
 // ---- the particle filter: the start, the segments, the resampling step between them ------------------------------------------------
-template <int NT>
+template <int NT, bool ST = false>
 hipError_t launch_mfma_segment(const SampleArgs& a, hipStream_t st) {
   const size_t lds = MfmaShape<NT>::lds_doubles(false) * sizeof(double);
-  if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k_sample_mfma<NT, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k_sample_mfma<NT, true, true, ST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if ((a.n_paths + 63) / 64 > 65535) return hipErrorInvalidValue;      // (grid.y)
-  hipLaunchKernelGGL((k_sample_mfma<NT, true, true>), dim3(a.batch, (a.n_paths + 63) / 64), dim3(256), lds, st, a);
+  hipLaunchKernelGGL((k_sample_mfma<NT, true, true, ST>), dim3(a.batch, (a.n_paths + 63) / 64), dim3(256), lds, st, a);
   return hipGetLastError();
 }
 
@@ -626,6 +691,9 @@ __device__ __forceinline__ double wave_max(double v) {
 // a.k is not the last grid index: anc_i = min(#{m: cum_m <= (U + i) / n S}, n - 1) by bisection, U from Philox counter (k, 0, p, 0xffffffff),
 // x_out_i = x_in_{anc_i}, lw_i = max lw + log S - log n; else anc_i = i and lw stays.  The histories of observation j (t_j = a.k) are
 // written where asked for; the cloud is x_in.
+// ST: the [3][D] rows of path statistics go from st_in to st_out by the same ancestors (two buffers, as for x: no slot is read after it is
+// written).
+template <bool ST>
 __global__ __launch_bounds__(256) void k_pf_resample(PfArgs a) {
   __shared__ double tot[4], red[4];
   const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6, n = a.n_paths, D = a.D;
@@ -638,6 +706,8 @@ __global__ __launch_bounds__(256) void k_pf_resample(PfArgs a) {
   double* xout = a.x_out + (size_t)p * nD;
   if (j < 0) {      // (uniform over the workgroup)
     for (size_t e = tid; e < nD; e += 256) xout[e] = xin[e];
+    if constexpr (ST)
+      for (size_t e = tid; e < 3 * nD; e += 256) a.st_out[(size_t)p * 3 * nD + e] = a.st_in[(size_t)p * 3 * nD + e];
     return;
   }
   double* lw = a.lw + (size_t)p * n;
@@ -705,6 +775,44 @@ __global__ __launch_bounds__(256) void k_pf_resample(PfArgs a) {
     const size_t i = e / D;
     xout[e] = xin[(size_t)anc[i] * D + (e - i * D)];
   }
+  if constexpr (ST) {
+    const size_t D3 = 3 * (size_t)D;
+    for (size_t e = tid; e < 3 * nD; e += 256) {
+      const size_t i = e / D3;
+      a.st_out[(size_t)p * 3 * nD + e] = a.st_in[(size_t)p * 3 * nD + (size_t)anc[i] * D3 + (e - i * D3)];
+    }
+  }
+}
+
+// The self-normalised weighted mean of the rows of path statistics: workgroup (p, s) sums statistic s of problem p over the slots,
+// mean[p][s][j] = sum_i w_i stats[p][i][s][j] / sum_i w_i with w_i = exp(lw_i - max lw).  Thread t takes component t mod D of the slots
+// t / D, t / D + G, ... (G = 256 / D slots at a time), the G partial sums of a component are added in order through LDS.
+__global__ __launch_bounds__(256) void k_pf_stats_mean(int D, int n, const double* lw_all, const double* stats, double* mean) {
+  __shared__ double part[256], wpart[256], red[4];
+  const int p = blockIdx.x, s = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const double* lw = lw_all + (size_t)p * n;
+  const double* rows = stats + (size_t)p * n * 3 * D + (size_t)s * D;
+  double mx = -INFINITY;
+  for (int i = tid; i < n; i += 256) mx = fmax(mx, lw[i]);
+  mx = wave_max(mx);
+  if (lane == 0) red[w] = mx;
+  __syncthreads();
+  mx = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+  const int G = 256 / D, g = tid / D, j = tid - g * D;
+  double acc = 0.0, sw = 0.0;
+  if (g < G)
+    for (int i = g; i < n; i += G) {
+      const double wi = exp(lw[i] - mx);
+      acc += wi * rows[(size_t)i * 3 * D + j];
+      sw += wi;
+    }
+  part[tid] = acc; wpart[tid] = sw;
+  __syncthreads();
+  if (tid < D) {
+    double num = 0.0, den = 0.0;
+    for (int v = 0; v < G; v++) { num += part[v * D + tid]; den += wpart[v * D + tid]; }
+    mean[((size_t)p * 3 + s) * D + tid] = num / den;
+  }
 }
 
 template <bool W>
@@ -733,6 +841,22 @@ hipError_t launch_sample_segment(const SampleArgs& a, hipStream_t st) {
   if (a.k_begin < 0 || a.k_end < a.k_begin || a.k_end >= a.Np) return hipErrorInvalidValue;
   if (a.model != VGPA_MODEL_OU && a.model != VGPA_MODEL_DW && a.model != VGPA_MODEL_L63 && a.model != VGPA_MODEL_L96) return hipErrorInvalidValue;
   if (a.D > kMaxLaneD && a.model != VGPA_MODEL_L96) return hipErrorInvalidValue;
+  if (a.pf_stats) {      // the segments that carry the path statistics (vgpa_particle_statistics)
+    if (a.D <= kMaxLaneD) {
+      const dim3 grid((unsigned)(((size_t)a.batch * a.n_paths + 255) / 256)), block(256);
+      switch (a.D) {
+        case 1: hipLaunchKernelGGL((k_sample_small<1, true, true, true>), grid, block, 0, st, a); break;
+        case 2: hipLaunchKernelGGL((k_sample_small<2, true, true, true>), grid, block, 0, st, a); break;
+        case 3: hipLaunchKernelGGL((k_sample_small<3, true, true, true>), grid, block, 0, st, a); break;
+        default: hipLaunchKernelGGL((k_sample_small<4, true, true, true>), grid, block, 0, st, a); break;
+      }
+      return hipGetLastError();
+    }
+    if (a.D <= 16) return launch_mfma_segment<16, true>(a, st);
+    if (a.D <= 32) return launch_mfma_segment<32, true>(a, st);
+    if (a.D <= 48) return launch_mfma_segment<48, true>(a, st);
+    return launch_mfma_segment<64, true>(a, st);
+  }
   if (a.D <= kMaxLaneD) {
     const dim3 grid((unsigned)(((size_t)a.batch * a.n_paths + 255) / 256)), block(256);
     switch (a.D) {
@@ -757,7 +881,15 @@ hipError_t launch_pf_start(const PfArgs& a, hipStream_t st) {
 
 hipError_t launch_pf_resample(const PfArgs& a, hipStream_t st) {
   if (a.D < 1 || a.n_paths < 1 || !a.x_in || !a.x_out || a.x_in == a.x_out || !a.lw || !a.cum || !a.anc || !a.h_ess || !a.h_flag) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_pf_resample, dim3(a.batch), dim3(256), 0, st, a);
+  if ((a.st_in == nullptr) != (a.st_out == nullptr) || (a.st_in && a.st_in == a.st_out)) return hipErrorInvalidValue;
+  if (a.st_in) hipLaunchKernelGGL(k_pf_resample<true>, dim3(a.batch), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(k_pf_resample<false>, dim3(a.batch), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_pf_stats_mean(int D, int batch, int n_paths, const double* lw, const double* stats, double* mean, hipStream_t st) {
+  if (D < 1 || D > kMaxSmallD || batch < 1 || n_paths < 1 || !lw || !stats || !mean) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_pf_stats_mean, dim3(batch, 3), dim3(256), 0, st, D, n_paths, lw, stats, mean);
   return hipGetLastError();
 }
 

@@ -165,8 +165,8 @@ struct vgpa_ctx {
   double *d_sp_logw = nullptr, *d_sp_start = nullptr;      // vgpa_sample_paths_weighted: the two sums and x_0 of every path
   size_t sp_logw_n = 0, sp_start_n = 0;
   // vgpa_particle_filter: the two particle buffers, log-weights, prefix sums, ancestors of a step (int32), the histories (ess, flags and
-  // ancestors as int32, clouds), the prior's mean and factor
-  enum { PF_XA, PF_XB, PF_LW, PF_CUM, PF_ANC, PF_ESS, PF_FLAG, PF_HANC, PF_CLOUDS, PF_MU, PF_LT, PF_COUNT };
+  // ancestors as int32, clouds), the prior's mean and factor; vgpa_particle_statistics: the two buffers of rows and their mean
+  enum { PF_XA, PF_XB, PF_LW, PF_CUM, PF_ANC, PF_ESS, PF_FLAG, PF_HANC, PF_CLOUDS, PF_MU, PF_LT, PF_STA, PF_STB, PF_MEAN, PF_COUNT };
   double* d_pf[PF_COUNT] = {};
   size_t pf_n[PF_COUNT] = {};
   // profiling
@@ -1565,11 +1565,14 @@ int vgpa_sample_paths_weighted(vgpa_ctx* c, const double* x, const double* x0, i
 
 // The guided particle filter (see vgpa_hip.h): the weighted walk of vgpa_sample_paths_weighted cut at the observation
 // indices of the batch, the particles resident between the cuts, a resampling step behind every cut that is an observation of some problem.
-int vgpa_particle_filter(vgpa_ctx* c, const double* x, const double* x0, int32_t n_paths, uint64_t seed, double ess_fraction,
-                         const double* prior_mu, const double* prior_tau, double* logw, double* state, double* ess, int32_t* resampled,
-                         int32_t* ancestors, double* clouds) {
+// with_stats: vgpa_particle_statistics -- the same walk, counters and resampling decisions, every slot's [3][D] row of
+// path statistics carried along its lineage; stats / mean: where the final rows and their weighted mean go.
+static int particle_run(vgpa_ctx* c, const double* x, const double* x0, int32_t n_paths, uint64_t seed, double ess_fraction,
+                        const double* prior_mu, const double* prior_tau, double* logw, double* state, double* ess, int32_t* resampled,
+                        int32_t* ancestors, double* clouds, bool with_stats, double* stats, double* mean) {
   if (!c) return VGPA_ERR_ARG;
   if (!logw || !state) return fail(c, VGPA_ERR_ARG, "null argument");
+  if (with_stats && !stats && !mean) return fail(c, VGPA_ERR_ARG, "at least one of stats and mean must be given");
   if (n_paths < 1) return fail(c, VGPA_ERR_ARG, "n_paths must be at least 1 (n_paths = %d)", n_paths);
   if (!(ess_fraction >= 0.0 && ess_fraction <= 1.0)) return fail(c, VGPA_ERR_ARG, "ess_fraction must lie in [0, 1] (ess_fraction = %g)", ess_fraction);
   if ((prior_mu == nullptr) != (prior_tau == nullptr)) return fail(c, VGPA_ERR_ARG, "the prior is a mean and a covariance: both or neither");
@@ -1586,6 +1589,7 @@ int vgpa_particle_filter(vgpa_ctx* c, const double* x, const double* x0, int32_t
       (rc = buf(vgpa_ctx::PF_ANC, ints(Bn))) || (rc = buf(vgpa_ctx::PF_ESS, BM)) || (rc = buf(vgpa_ctx::PF_FLAG, ints(BM)))) return rc;
   if (ancestors && (rc = buf(vgpa_ctx::PF_HANC, ints(BM * n)))) return rc;
   if (clouds && (rc = buf(vgpa_ctx::PF_CLOUDS, BM * n * D))) return rc;
+  if (with_stats && ((rc = buf(vgpa_ctx::PF_STA, 3 * BnD)) || (rc = buf(vgpa_ctx::PF_STB, 3 * BnD)) || (rc = buf(vgpa_ctx::PF_MEAN, (size_t)B * 3 * D)))) return rc;
   PfArgs f{};
   f.D = D; f.batch = B; f.n_paths = n_paths; f.M = M1; f.seed = seed; f.ess_fraction = ess_fraction;
   f.x0 = a.x0; f.m0 = a.m0; f.L0 = a.L0; f.m0_stride = a.m0_stride; f.L0_stride = a.L0_stride;
@@ -1619,17 +1623,26 @@ int vgpa_particle_filter(vgpa_ctx* c, const double* x, const double* x0, int32_t
     for (int m = 0; m < count[p]; m++) is_obs[(size_t)t[m]] = 1;
   }
   a.pf_lw = f.lw; a.seg_first = 1;
+  double* st_cur = with_stats ? c->d_pf[vgpa_ctx::PF_STA] : nullptr;
+  double* st_other = with_stats ? c->d_pf[vgpa_ctx::PF_STB] : nullptr;
+  if (with_stats) HIP_TRY(c, hipMemsetAsync(st_cur, 0, 3 * BnD * sizeof(double), c->stream));
   int prev = 0;
   for (int k = 0; k < Np; k++) {
     if (!is_obs[k] && k != Np - 1) continue;
-    a.k_begin = prev; a.k_end = k; a.pf_x = cur;
+    a.k_begin = prev; a.k_end = k; a.pf_x = cur; a.pf_stats = st_cur;
     LAUNCH_TRY(c, "particle segment launch", launch_sample_segment(a, c->stream));
     a.seg_first = 0; prev = k;
     if (!is_obs[k]) continue;
-    f.k = k; f.last = k == Np - 1 ? 1 : 0; f.x_in = cur; f.x_out = other;
+    f.k = k; f.last = k == Np - 1 ? 1 : 0; f.x_in = cur; f.x_out = other; f.st_in = st_cur; f.st_out = st_other;
     LAUNCH_TRY(c, "particle resampling launch", launch_pf_resample(f, c->stream));
     std::swap(cur, other);
+    std::swap(st_cur, st_other);
   }
+  if (with_stats && mean) {
+    LAUNCH_TRY(c, "path statistics mean launch", launch_pf_stats_mean(D, B, n_paths, f.lw, st_cur, c->d_pf[vgpa_ctx::PF_MEAN], c->stream));
+    if ((rc = download(c, mean, c->d_pf[vgpa_ctx::PF_MEAN], (size_t)B * 3 * D))) return rc;
+  }
+  if (with_stats && stats && (rc = download(c, stats, st_cur, 3 * BnD))) return rc;
   if ((rc = download(c, logw, f.lw, Bn)) || (rc = download(c, state, cur, BnD))) return rc;
   if (ess && (rc = download(c, ess, f.h_ess, (size_t)B * M))) return rc;
   if (resampled && M > 0) HIP_TRY(c, hipMemcpyAsync(resampled, f.h_flag, (size_t)B * M * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
@@ -1639,6 +1652,20 @@ int vgpa_particle_filter(vgpa_ctx* c, const double* x, const double* x0, int32_t
       if (count[p] > 0 && (rc = download(c, clouds + (size_t)p * M * n * D, f.h_clouds + (size_t)p * M * n * D, (size_t)count[p] * n * D))) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return VGPA_OK;
+}
+
+int vgpa_particle_filter(vgpa_ctx* c, const double* x, const double* x0, int32_t n_paths, uint64_t seed, double ess_fraction,
+                         const double* prior_mu, const double* prior_tau, double* logw, double* state, double* ess, int32_t* resampled,
+                         int32_t* ancestors, double* clouds) {
+  return particle_run(c, x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled, ancestors, clouds, false, nullptr,
+                      nullptr);
+}
+
+// The path statistics of the particle filter's lineages (see vgpa_hip.h)
+int vgpa_particle_statistics(vgpa_ctx* c, const double* x, const double* x0, int32_t n_paths, uint64_t seed, double ess_fraction,
+                             const double* prior_mu, const double* prior_tau, double* logw, double* state, double* stats, double* mean,
+                             double* ess, int32_t* resampled) {
+  return particle_run(c, x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled, nullptr, nullptr, true, stats, mean);
 }
 
 int vgpa_fetch(vgpa_ctx* c, int which, double* out) {

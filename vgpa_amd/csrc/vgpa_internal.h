@@ -261,6 +261,9 @@ struct SampleArgs {
   int seg_first, k_begin, k_end;
   double* pf_x;             // [B][n_paths][D]
   double* pf_lw;            // [B][n_paths]
+  // the path statistics of a lineage (vgpa_particle_statistics): set, the ST instantiations run and add every step's
+  // Q_j += r_j^2 / dt, G_j += phi_j r_j, H_j += dt phi_j^2 (r = dt (g - f) + eta, phi_j = df_j / dtheta_a(j) at x_{k-1}) to the slot's row
+  double* pf_stats;         // [B][n_paths][3][D], or nullptr
 };
 hipError_t launch_sample_paths(const SampleArgs& a, hipStream_t st);
 hipError_t launch_sample_segment(const SampleArgs& a, hipStream_t st);
@@ -289,9 +292,13 @@ struct PfArgs {
   double* h_ess; int32_t* h_flag;      // [B][M] each
   int32_t* h_anc;           // [B][M][n_paths], or nullptr
   double* h_clouds;         // [B][M][n_paths][D], or nullptr
+  // the rows of vgpa_particle_statistics, gathered by ancestor together with x; both or neither
+  const double* st_in; double* st_out;   // [B][n_paths][3][D] each
 };
 hipError_t launch_pf_start(const PfArgs& a, hipStream_t st);
 hipError_t launch_pf_resample(const PfArgs& a, hipStream_t st);
+// mean [B][3][D] = sum_i w_i stats[.][i] / sum_i w_i, w_i = exp(lw_i - max lw) (sample.hip: k_pf_stats_mean)
+hipError_t launch_pf_stats_mean(int D, int batch, int n_paths, const double* lw, const double* stats, double* mean, hipStream_t st);
 
 // launchers (each returns hipGetLastError()) -----------------------------------------------------
 hipError_t launch_ode_generic(int method, bool fwd, const OdeArgs& a, hipStream_t st);

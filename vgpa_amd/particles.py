@@ -7,10 +7,20 @@ sample size drops below ess_fraction n.  Resampling preserves the mean weight, s
 ess_fraction = 0 the record holds exactly the weights of importance_weights(); with resampling the estimate stays unbiased and its variance
 grows linearly, not exponentially, with the number of observations.  Resampling couples the particles of a problem: from the first
 resampling on, particle i depends on n (the prefix property of sample_paths ends there).
+
+PathStatistics: one problem's record of vgpa_particle_statistics -- the same filter, every particle carrying along its
+lineage the complete-data sufficient statistics of the Euler-discretised model,
+    Q_j = sum_k r_j^2 / dt,  G_j = sum_k phi_j r_j,  H_j = sum_k dt phi_j^2,  r = x_k - x_{k-1} - dt f_theta(x_{k-1}),  phi_j = df_j / dtheta_a(j).
+The complete-data log-likelihood at theta + delta, Sigma' is -1/2 sum_j [(Q_j - 2 delta_a(j) G_j + delta_a(j)^2 H_j) / Sigma'_jj +
+n_steps log(2 pi Sigma'_jj dt)]: quadratic in delta with a diagonal Hessian.  By Fisher's identity the weighted mean of G / Sigma over the
+smoothing distribution is the score of log p(y | theta, Sigma), and score / information is the exact EM step in theta.
+There is no Sigma step: the paths are imputed at the Sigma in force, their quadratic variation is Sigma T as dt -> 0 whatever the data
+say, so Sigma <- E[Q] / n_steps barely moves (0.77 .. 0.79 from Sigma = 0.8 on the fixtures at dt = 0.01).  Q serves the Q-function and as a
+diagnostic.
 """
 import numpy as np
 
-__all__ = ["ParticleFilterResult"]
+__all__ = ["ParticleFilterResult", "PathStatistics"]
 
 
 class ParticleFilterResult(object):
@@ -67,3 +77,74 @@ class ParticleFilterResult(object):
             slot = self.ancestors[j, slot]
             out[:, j] = self.clouds[j, slot]
         return out
+
+
+class PathStatistics(object):
+    """log_w (n,): the final unnormalised log-weights; mean (3, D): the self-normalised weighted mean of the rows (Q, G, H); rows
+    (n, 3, D): the rows themselves, or None; ess, resampled over the problem's observations; dt, n_steps = Np - 1 and model ("OU", "DW",
+    "L63", "L96") say how the rows were made.  sigma_diag below: the diagonal of Sigma, (D,) or a scalar."""
+
+    def __init__(self, log_w, mean, dt, n_steps, model, ess=(), resampled=(), rows=None) -> None:
+        self.log_w = np.asarray(log_w, dtype=float).ravel()
+        if self.log_w.size < 1:
+            raise ValueError(" PathStatistics: at least one particle.")
+        self.mean = np.asarray(mean, dtype=float)
+        if self.mean.ndim != 2 or self.mean.shape[0] != 3:
+            raise ValueError(" PathStatistics: mean must be (3, D).")
+        if model not in ("OU", "DW", "L63", "L96"):
+            raise ValueError(f" PathStatistics: unknown model -> {model}")
+        if model == "L63" and self.mean.shape[1] != 3:
+            raise ValueError(" PathStatistics: Lorenz-63 has three components.")
+        self.dt, self.n_steps, self.model = float(dt), int(n_steps), model
+        self.ess = np.asarray(ess, dtype=float).ravel()
+        self.resampled = np.asarray(resampled).astype(bool).ravel()
+        self.rows = None if rows is None else np.asarray(rows, dtype=float)
+        if self.rows is not None and self.rows.shape != (self.log_w.size,) + self.mean.shape:
+            raise ValueError(" PathStatistics: rows must be (particles, 3, D).")
+        if self.ess.size != self.resampled.size:
+            raise ValueError(" PathStatistics: ess and resampled do not belong together.")
+
+    def __len__(self):
+        return self.log_w.size
+
+    @property
+    def dim_d(self):
+        return self.mean.shape[1]
+
+    @property
+    def n_theta(self):
+        return 3 if self.model == "L63" else 1
+
+    def log_evidence(self):
+        """logsumexp(log_w) - log n, as ParticleFilterResult.log_evidence()"""
+        top = np.max(self.log_w)
+        return float(top + np.log(np.sum(np.exp(self.log_w - top))) - np.log(self.log_w.size))
+
+    def expected(self):
+        """(E[Q], E[G], E[H]), each (D,)"""
+        return self.mean[0].copy(), self.mean[1].copy(), self.mean[2].copy()
+
+    def _over_sigma(self, row, sigma_diag):
+        v = row / np.broadcast_to(np.asarray(sigma_diag, dtype=float).ravel(), row.shape)
+        return v.copy() if self.model == "L63" else np.array([v.sum()])
+
+    def score(self, sigma_diag):
+        """(n_theta,): sum_{j in a} E[G_j] / Sigma_jj, the estimate of grad_theta log p(y | theta, Sigma) of the Euler-discretised model"""
+        return self._over_sigma(self.mean[1], sigma_diag)
+
+    def information(self, sigma_diag):
+        """(n_theta,): sum_{j in a} E[H_j] / Sigma_jj, minus the (diagonal) Hessian of the Q-function in theta"""
+        return self._over_sigma(self.mean[2], sigma_diag)
+
+    def theta_step(self, sigma_diag):
+        """(n_theta,): score / information; theta + step is the exact EM update (for Lorenz-63 it does not depend on Sigma)"""
+        return self.score(sigma_diag) / self.information(sigma_diag)
+
+    def expected_loglik(self, theta_new, sigma_diag_new, theta_old):
+        """The EM Q-function at (theta_new, Sigma_new) from the statistics taken at theta_old:
+        -1/2 sum_j [(E[Q_j] - 2 delta_a E[G_j] + delta_a^2 E[H_j]) / Sigma'_jj + n_steps log(2 pi Sigma'_jj dt)], delta = theta_new - theta_old"""
+        delta = np.atleast_1d(np.asarray(theta_new, dtype=float)) - np.atleast_1d(np.asarray(theta_old, dtype=float))
+        delta = np.broadcast_to(delta, (self.dim_d,)) if self.model != "L63" else delta.reshape(3)
+        sg = np.broadcast_to(np.asarray(sigma_diag_new, dtype=float).ravel(), (self.dim_d,))
+        q, g, h = self.mean
+        return float(-0.5 * np.sum((q - 2.0 * delta * g + delta * delta * h) / sg + self.n_steps * np.log(2.0 * np.pi * sg * self.dt)))

@@ -204,6 +204,37 @@ class VarGP(object):
         out = [self._particle_record(res, k) for k in range(res["log_w"].shape[0])]
         return out[0] if self.batch == 1 else out
 
+    def _statistics_record(self, res, k, n_obs=None):
+        """One problem's PathStatistics from row k of Context.particle_statistics' dict, cut to its own n_obs observations"""
+        from .particles import PathStatistics
+        m = res["ess"].shape[1] if n_obs is None else int(n_obs)
+        rows = None if res["stats"] is None else res["stats"][k]
+        return PathStatistics(res["log_w"][k], res["mean"][k], float(self.fwd_ode.dt), self.dim_n - 1, self.model._model_id, res["ess"][k, :m],
+                              res["resampled"][k, :m], rows)
+
+    def particle_statistics(self, n_paths, seed, ess_fraction=0.5, x=None, x0=None, per_particle=False):
+        """particle_filter with the same arguments, every particle carrying the path statistics (Q, G, H) of its lineage: a
+        particles.PathStatistics (with batch > 1 a list, one per problem) with the weighted mean of the rows, reduced on the device, and
+        -- per_particle=True -- the rows.  Its score(), theta_step() and expected_loglik() are the score of log p(y | theta, Sigma), the
+        exact EM step in theta and the EM Q-function under the particles' smoothing distribution."""
+        xx = None if x is None else np.asarray(x, dtype=float)
+        res = self._context().particle_statistics(n_paths, seed, ess_fraction=ess_fraction, x=xx, x0=x0, prior=self._prior(),
+                                                  per_particle=per_particle)
+        out = [self._statistics_record(res, k) for k in range(res["log_w"].shape[0])]
+        return out[0] if self.batch == 1 else out
+
+    def particle_fit_theta(self, n_paths, seed, iters, ess_fraction=0.5, refit=True, pooled=False):
+        """Particle EM for the drift parameters (ProblemBatch.particle_fit_theta on a batch of one): (theta, trace), theta in the shape of
+        model.theta."""
+        from .batch import ProblemBatch
+        pb = ProblemBatch([self], device=self.device, flags=self.flags)
+        try:
+            theta, trace = pb.particle_fit_theta(n_paths, seed, iters, ess_fraction=ess_fraction, refit=refit, pooled=pooled)
+        finally:
+            pb.close()
+        theta = theta[0]
+        return (float(theta[0]) if theta.size == 1 else theta), trace
+
     def fit_theta(self, x0, rounds, options=None):
         """Variational EM for the drift parameters (ProblemBatch.fit_theta on a batch of one): (x, F, theta, trace), theta in the
         shape of model.theta, trace["F"] of shape (rounds, 2, 1)."""
