@@ -300,6 +300,30 @@ int vgpa_particle_statistics(vgpa_ctx* ctx, const double* x_or_null, const doubl
                              const double* prior_mu_or_null, const double* prior_tau_or_null, double* logw, double* state,
                              double* stats_or_null, double* mean_or_null, double* ess_or_null, int32_t* resampled_or_null);
 
+/* The smoothing moments on the time grid under the genealogy of the particle filter: E[x_k | y] and E[x_k^2 | y] of the
+ * Euler-discretised model as the filter's surviving lineages estimate them, with O(n D) state per problem -- no path is stored or copied.
+ * Three steps on the device: the filter of vgpa_particle_filter with its ancestors kept; the final weights pushed backwards through the
+ * ancestors; the walk once more from the same counters, reduced where the states are made.
+ *   stretches   problem p has its own observation indices t_0 < ... < t_{c-1} in force.  Stretch j = 0 .. c holds the grid indices
+ *               t_{j-1} < k <= t_j with t_{-1} = -1 and t_c = Np-1 (stretch c is empty when t_{c-1} = Np-1)
+ *   x_i(k)      the state of slot i as the walk arrives at k, before a resampling decision at k
+ *   W^c_i       = w_i / sum w,  w_i = exp(lw_i - max lw) of the final log-weights
+ *   W^j_a       for j = c-1 .. 0: where the cloud was resampled at observation j with ancestors anc, the sum of W^{j+1}_i over the slots i
+ *               with anc_i = a, added in increasing i (anc is non-decreasing: a contiguous run; 0 for a slot without descendant); else W^{j+1}_a
+ *   moments          host, [batch][n_keep][2][D], n_keep = (Np-1) / stride + 1: for the kept grid indices k = 0, stride, 2 stride, ... in
+ *                    stretch j(k), M1[k][d] = sum_i W^{j(k)}_i x_i(k)[d] and M2[k][d] = sum_i W^{j(k)}_i x_i(k)[d]^2.  The raw moments: the
+ *                    variance M2 - M1^2 is the caller's to form.  Two calls with the same arguments give the same bits
+ *   lineage_ess_or_null  host, [batch][M+1]: 1 / sum_i (W^j_i)^2 for j = 0 .. c, the number of distinct lineages that carry stretch j's
+ *                    estimate in effect; rows beyond a problem's own count + 1: 0
+ *   logw, ess_or_null, resampled_or_null and every other argument: as in vgpa_particle_filter, and bit-identical to its results with the
+ *   same arguments.  state is copied behind the second walk and is bit-identical as well: the replay arrived at the filter's particles.
+ *   With x NULL the cached state is read and not written
+ * Errors: as vgpa_particle_filter, and VGPA_ERR_ARG for a NULL moments or stride < 1; VGPA_ERR_UNSUPPORTED, before any work, for more
+ * than 65535 workgroups per problem (256 particles each at D <= 4, 64 above) or more than 2^39 - 256 entries of moments. */
+int vgpa_particle_moments(vgpa_ctx* ctx, const double* x_or_null, const double* x0_or_null, int32_t n_paths, int32_t stride, uint64_t seed,
+                          double ess_fraction, const double* prior_mu_or_null, const double* prior_tau_or_null, double* logw, double* state,
+                          double* moments, double* lineage_ess_or_null, double* ess_or_null, int32_t* resampled_or_null);
+
 /* device-pointer variants (x, g on the context's device; f written to HOST after a sync) ------ */
 int vgpa_sweep_dev(vgpa_ctx* ctx, const double* x_dev, double* f_host, double* g_dev);
 int vgpa_free_energy_dev(vgpa_ctx* ctx, const double* x_dev, double* f_host);

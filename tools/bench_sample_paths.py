@@ -1,9 +1,11 @@
 """
 Time of Context.sample_paths (vgpa_sample_paths), Context.sample_paths_weighted (vgpa_sample_paths_weighted), Context.particle_filter
-(vgpa_particle_filter) and Context.particle_statistics (vgpa_particle_statistics) on their jobs, one JSON line.
+(vgpa_particle_filter), Context.particle_statistics (vgpa_particle_statistics) and Context.particle_moments (vgpa_particle_moments) on their
+jobs, one JSON line.
 
     python tools/bench_sample_paths.py [--rounds 3] [--calls 5] [--jobs a,b,c,aw,aw0,bw,bw0,af64_0,af64_5,af1024_0,af1024_5,bf64_0,...]
     python tools/bench_sample_paths.py --statistics [--filter-problems 4096]      # the as* and bs* jobs
+    python tools/bench_sample_paths.py --moments [--filter-problems 4096]         # the am* and bm* jobs
 
   a   posterior kind, Lorenz-96, D = 40, Np = 1001, B = 512:   64 paths per problem, stride 100
   b   posterior kind, Lorenz-63, Np = 1001, B = 65536:          1 path per problem,  stride 100
@@ -17,6 +19,11 @@ Time of Context.sample_paths (vgpa_sample_paths), Context.sample_paths_weighted 
   as<n>_<f>, bs<n>_<f>   (--statistics selects all eight) particle_statistics with the arguments of af<n>_<f> / bf<n>_<f>, the mean reduced on
              the device and no rows copied, and particle_filter itself, the two calls alternating inside every round: both times and their
              ratio
+
+  am<n>_<s>, bm<n>_<s>   (--moments selects all twelve) particle_moments on the contexts of a and b: n = 64 or 1024 particles per problem,
+             ess_fraction 0.5, every s-th grid index kept (s = 1, 10 or 1004: beyond the grid, index 0 alone is reduced -- the replay
+             without its reductions), and particle_filter with the same arguments, the two calls alternating inside every round: both
+             times, their ratio, the partial-sum buffer on the device and the result copied
 
 The posterior jobs read the x a free_energy_dev left cached (x=None: nothing is uploaded); every job draws its start from (m0, S0).  A call
 is timed with a pair of device events on the context's stream around it -- the host work of the call (the Cholesky factors), the kernel and
@@ -42,11 +49,12 @@ for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")):
         sys.path.insert(0, p)
 
 HBM_BYTES_PER_S = 8.0e12
+N_PTS, DT = 1001, 0.01
 JOBS = {"a": ("L96", 40, 512, "posterior", 64, 100), "b": ("L63", 3, 65536, "posterior", 1, 100), "c": ("L63", 3, 65536, "model", 1, 1)}
 WEIGHTED = {"aw": ("a", True), "aw0": ("a", False), "bw": ("b", True), "bw0": ("b", False)}      # job -> (its unweighted twin, paths stored)
 FILTER = {f"{t}f{n}_{f}": (t, n, 0.1 * f) for t in "ab" for n in (64, 1024) for f in (0, 5)}      # job -> (context of, particles, ess_fraction)
 STATS = {f"{t}s{n}_{f}": (t, n, 0.1 * f) for t in "ab" for n in (64, 1024) for f in (0, 5)}       # job -> as FILTER
-N_PTS, DT = 1001, 0.01
+MOMENTS = {f"{t}m{n}_{s}": (t, n, s) for t in "ab" for n in (64, 1024) for s in (1, 10, N_PTS + 3)}          # job -> (context of, particles, stride)
 
 
 def tree():
@@ -78,10 +86,10 @@ def run(job, rounds, calls, numpy_problems, cache, filter_problems=0):
     from bench_problem_batch import StreamTimer, make_contexts
     twin, stored = WEIGHTED.get(job, (job, True))
     weighted = job in WEIGHTED
-    if job in FILTER or job in STATS:
-        twin = (FILTER.get(job) or STATS[job])[0]
+    if job in FILTER or job in STATS or job in MOMENTS:
+        twin = (FILTER.get(job) or STATS.get(job) or MOMENTS[job])[0]
     name, d, B, kind, n_paths, stride = JOBS[twin]
-    if (job in FILTER or job in STATS) and twin == "b" and filter_problems:
+    if (job in FILTER or job in STATS or job in MOMENTS) and twin == "b" and filter_problems:
         B = min(B, filter_problems)
     if (name, B) not in cache:                        # (b and c share a context)
         from helpers import SEED, build_problem
@@ -120,6 +128,36 @@ def run(job, rounds, calls, numpy_problems, cache, filter_problems=0):
                 "filter_rounds_ms": [round(v, 4) for v in per_round["filter"]],
                 "observations": int(c.n_obs), "resampled_share": round(float(res0["filter"]["resampled"].mean()), 3),
                 "d2h_mb": round(8.0 * B * (n_paths * (1 + d) + 3 * d) / 1e6, 1)}
+    if job in MOMENTS:
+        _, n_paths, stride = MOMENTS[job]
+        calls_of = {"filter": lambda: c.particle_filter(n_paths, 1, ess_fraction=0.5),
+                    "moments": lambda: c.particle_moments(n_paths, 1, stride=stride, ess_fraction=0.5)}
+        res0 = {k: f() for k, f in calls_of.items()}      # warm-up (first-use allocations)
+        n_keep = (N_PTS - 1) // stride + 1
+        assert all(np.array_equal(res0["filter"][k], res0["moments"][k]) for k in ("log_w", "state", "ess", "resampled"))
+        assert res0["moments"]["moments"].shape == (B, n_keep, 2, d) and np.all(np.isfinite(res0["moments"]["moments"]))
+        lineage = res0["moments"]["lineage_ess"]
+        del res0["moments"]["moments"]
+        per_round = {k: [] for k in calls_of}
+        for _ in range(rounds):
+            ms = {k: [] for k in calls_of}
+            for _ in range(calls):
+                for k, f in calls_of.items():
+                    ms[k].append(tm.ms(f))
+            for k in calls_of:
+                per_round[k].append(float(np.median(ms[k])))
+        med = {k: float(np.median(v)) for k, v in per_round.items()}
+        blocks = (n_paths + 63) // 64 if d > 4 else (n_paths + 255) // 256
+        return {"job": job, "model": name, "D": d, "Np": N_PTS, "B": B, "kind": "moments", "n_paths": n_paths, "ess_fraction": 0.5,
+                "stride": stride, "moments_ms_per_call": round(med["moments"], 4), "filter_ms_per_call": round(med["filter"], 4),
+                "ratio": round(med["moments"] / med["filter"], 4),
+                "moments_rounds_ms": [round(v, 4) for v in per_round["moments"]],
+                "filter_rounds_ms": [round(v, 4) for v in per_round["filter"]],
+                "observations": int(c.n_obs), "resampled_share": round(float(res0["filter"]["resampled"].mean()), 3),
+                "lineage_ess_first_stretch_median": round(float(np.median(lineage[:, 0])), 2),
+                "lineage_ess_last_stretch_median": round(float(np.median(lineage[:, -1])), 2),
+                "partial_buffer_mb": round(8.0 * B * blocks * n_keep * 2 * d / 1e6, 1),
+                "d2h_mb": round(8.0 * B * (n_paths * (1 + d) + n_keep * 2 * d) / 1e6, 1)}
     if job in FILTER:
         _, n_paths, frac = FILTER[job]
         call = lambda: c.particle_filter(n_paths, 1, ess_fraction=frac)      # noqa: E731
@@ -165,9 +203,12 @@ def main():
     ap.add_argument("--numpy-problems", type=int, default=2)
     ap.add_argument("--filter-problems", type=int, default=0, help="cap on B of the b context's filter jobs (0: none)")
     ap.add_argument("--statistics", action="store_true", help="run the as* and bs* jobs (particle_statistics beside particle_filter)")
+    ap.add_argument("--moments", action="store_true", help="run the am* and bm* jobs (particle_moments beside particle_filter)")
     args = ap.parse_args()
     if args.statistics:
         args.jobs = ",".join(sorted(STATS))
+    if args.moments:
+        args.jobs = ",".join(sorted(MOMENTS))
     cache = {}
     out = {"tool": "bench_sample_paths", "tree": tree(), "unit": "ms per call (device events around the call)", "jobs": []}
     for job in [j for j in args.jobs.split(",") if j]:

@@ -36,7 +36,7 @@ BWD_IDS = {"none": 0, "psi": 1, "q": 2}
 SYMBOLS = ["vgpa_create", "vgpa_destroy", "vgpa_last_error", "vgpa_abi_version", "vgpa_device_count",
            "vgpa_synchronize", "vgpa_stream", "vgpa_solve_fwd", "vgpa_solve_bwd", "vgpa_energy",
            "vgpa_obs_energy", "vgpa_free_energy", "vgpa_gradient", "vgpa_sweep", "vgpa_energy_parts",
-           "vgpa_fetch", "vgpa_theta_gradient", "vgpa_sample_paths", "vgpa_sample_paths_weighted", "vgpa_particle_filter", "vgpa_particle_statistics", "vgpa_sweep_dev", "vgpa_free_energy_dev", "vgpa_sweep_enqueue", "vgpa_fetch_f",
+           "vgpa_fetch", "vgpa_theta_gradient", "vgpa_sample_paths", "vgpa_sample_paths_weighted", "vgpa_particle_filter", "vgpa_particle_statistics", "vgpa_particle_moments", "vgpa_sweep_dev", "vgpa_free_energy_dev", "vgpa_sweep_enqueue", "vgpa_fetch_f",
            "vgpa_dev_alloc", "vgpa_dev_free", "vgpa_memcpy_h2d", "vgpa_memcpy_d2h",
            "vgpa_profile_begin", "vgpa_profile_end", "vgpa_ld_gemm", "vgpa_ld_stage", "vgpa_gradient_dev", "vgpa_energy_full", "vgpa_set_option", "vgpa_is_streaming", "vgpa_path_info", "vgpa_set_prior_energy",
            "vgpa_set_problem_data", "vgpa_set_problem_params", "vgpa_set_problem_obs_model",
@@ -139,6 +139,8 @@ def load():
                                          c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vgpa_particle_statistics.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_uint64, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.vgpa_particle_moments.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_uint64, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vgpa_sweep_dev.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vgpa_free_energy_dev.argtypes = [c_void_p, c_void_p, c_void_p]
     lib.vgpa_sweep_enqueue.argtypes = [c_void_p, c_void_p, c_void_p]
@@ -630,6 +632,32 @@ class Context:
                                                        _ptr(mu), _ptr(tau), _ptr(log_w), _ptr(state), _ptr(stats), _ptr(mean), _ptr(ess),
                                                        _ptr(flags)))
         return {"log_w": log_w, "state": state, "ess": ess, "resampled": flags, "mean": mean, "stats": stats}
+
+    def particle_moments(self, n_paths, seed, stride=1, ess_fraction=0.5, x=None, x0=None, prior=None):
+        """The smoothing moments on the grid under particle_filter's genealogy (vgpa_particle_moments): the filter, its final weights pushed
+        back through the ancestors, and the walk once more with the weighted sums taken on the device.  Returns a dict: log_w, state, ess,
+        resampled as particle_filter (bit for bit), moments (B, n_keep, 2, D): sum W x and sum W x^2 at the grid indices 0, stride, ...,
+        and lineage_ess (B, M + 1): 1 / sum W^2 of every stretch between two observations (0 beyond a problem's own count + 1)."""
+        n_paths, stride, m = int(n_paths), int(stride), self.n_obs
+        if not -2 ** 31 <= stride < 2 ** 31 or not -2 ** 31 <= n_paths < 2 ** 31:      # (the C ABI takes int32: nothing may wrap on its way there)
+            raise ValueError(f"n_paths and stride must fit into 32 bits (n_paths = {n_paths}, stride = {stride})")
+        xx = None if x is None else _c64(x)
+        if xx is not None and xx.size != self.B * self.len_x:
+            raise ValueError(f"x has {xx.size} entries, expected {self.B * self.len_x}")
+        s0 = None if x0 is None else _c64(np.broadcast_to(np.asarray(x0, dtype=np.float64).reshape(-1, self.D), (self.B, self.D)))
+        mu = tau = None
+        if prior is not None:
+            mu = _c64(np.broadcast_to(np.asarray(prior[0], dtype=np.float64).reshape(-1, self.D), (self.B, self.D)))
+            tau = _c64(np.broadcast_to(np.asarray(prior[1], dtype=np.float64).reshape(-1, self.D, self.D), (self.B, self.D, self.D)))
+        n = max(n_paths, 0)
+        log_w, state = np.empty((self.B, n)), np.empty((self.B, n, self.D))
+        ess, flags = np.zeros((self.B, m)), np.zeros((self.B, m), dtype=np.int32)
+        moments = np.empty((self.B, (self.Np - 1) // max(stride, 1) + 1, 2, self.D))
+        lineage_ess = np.zeros((self.B, m + 1))
+        self._check(self._lib.vgpa_particle_moments(self._h, _ptr(xx), _ptr(s0), n_paths, stride, int(seed) & 0xFFFFFFFFFFFFFFFF, float(ess_fraction),
+                                                    _ptr(mu), _ptr(tau), _ptr(log_w), _ptr(state), _ptr(moments), _ptr(lineage_ess), _ptr(ess),
+                                                    _ptr(flags)))
+        return {"log_w": log_w, "state": state, "ess": ess, "resampled": flags, "moments": moments, "lineage_ess": lineage_ess}
 
     def fetch(self, key):
         which = FETCH_IDS[key]

@@ -225,6 +225,15 @@ class ProblemBatch(object):
         res = self._context().particle_statistics(n_paths, seed, ess_fraction=ess_fraction, x=xx, x0=x0, prior=prior, per_particle=per_particle)
         return [v._statistics_record(res, k, np.asarray(v._inputs()["obs_t"]).size) for k, v in enumerate(self.vgps)]
 
+    def particle_moments(self, n_paths, seed, stride=1, ess_fraction=0.5, x=None, x0=None):
+        """One particles.SmoothingMoments per member (VarGP.particle_moments): the smoothing mean and second moment on the grid under the
+        genealogy of the member's own filter, with its own data, observation times and count, prior, theta and Sigma."""
+        xx = None if x is None else self._stack(x)
+        d = self.vgps[0].dim_d
+        prior = (np.stack([v._prior()[0][0] for v in self.vgps]), np.stack([v._prior()[1][0] for v in self.vgps]).reshape(self.B, d, d))
+        res = self._context().particle_moments(n_paths, seed, stride=stride, ess_fraction=ess_fraction, x=xx, x0=x0, prior=prior)
+        return [v._moments_record(res, k, stride) for k, v in enumerate(self.vgps)]
+
     def particle_fit_theta(self, n_paths, seed, iters, ess_fraction=0.5, refit=True, pooled=False, x0=None, options=None):
         """
         Particle EM for the drift parameters under the smoothing distribution of the Euler-discretised model, free of the variational

@@ -14,6 +14,10 @@
 // k_sample_small<D, true, true, true> and k_sample_mfma<NT, true, true, true> (vgpa_particle_statistics) are the segments
 // that also carry each slot's [3][D] row of path statistics (SampleArgs::pf_stats); k_pf_resample<true> gathers the rows by ancestor with
 // the states, k_pf_stats_mean reduces them to their self-normalised weighted mean.
+// k_sample_small<D, true, true, false, true> and k_sample_mfma<NT, true, true, false, true> (vgpa_particle_moments) are the
+// segments of the replay: the same states from the same counters, no weight sums, and at every kept grid index the workgroup's sums of
+// W x and W x^2 with the descendant weights W that k_pf_descend pushed back through the stored ancestors; k_pf_gather is the step between
+// two segments of the replay, k_pf_moments_sum adds the workgroups' sums in block order.
 #include "vgpa_internal.h"
 
 namespace vgpa {
@@ -111,17 +115,44 @@ __device__ __forceinline__ double obs_constant(const SampleArgs& a, uint32_t p) 
   return a.obs_const_scale * (a.obs_const_v ? a.obs_const_v[p] : a.obs_const);
 }
 
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+  return v;
+}
+
 // W: the weighted instantiation (posterior kind, diagonal R): both drifts at x_{k-1}, d = g - f, and per step
 // -sum_i d_i (eta_i + dt d_i / 2) / Sigma_ii with 1 / Sigma_ii = dt / R_ii^2; the observation term at the lane's own problem's times
 // SEG: a segment of the weighted walk (k_begin, k_end] from and to pf_x, the sums added to pf_lw; nothing else is stored
 // ST: a segment that adds its steps to the slot's row of pf_stats: Q_i += r^2 / dt, G_i += phi_i r, H_i += dt phi_i^2 with r = dt d + eta
-template <int D, bool W, bool SEG = false, bool ST = false>
+// MO: a segment of the replay, launched with the problem in blockIdx.x and 256 slots per workgroup.  The states only (no model drift, no
+// sums, pf_lw untouched); at a kept k the lanes' W x_i and (W x_i) x_i are added over the wave by a butterfly and over the four waves
+// through four LDS words per value (two sets, alternating: one barrier per kept k), in that fixed order.  A lane behind the last slot
+// walks from 0 with the last slot's counters and weight 0 and stores nothing.
+template <int D, bool W, bool SEG = false, bool ST = false, bool MO = false>
 __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
   static_assert(W || !SEG, "a segment is a weighted walk");
   static_assert(SEG || !ST, "the statistics are carried by the segments");
-  const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (gid >= (size_t)a.batch * a.n_paths) return;
-  const uint32_t p = (uint32_t)(gid / a.n_paths), path = (uint32_t)(gid % a.n_paths);
+  static_assert(!MO || (SEG && !ST), "the replay is a segment without statistics");
+  constexpr bool WS = W && !MO;      // the weight sums are formed
+  size_t gid;
+  uint32_t p, path;
+  bool live = true;
+  if constexpr (MO) {
+    const uint32_t slot = blockIdx.y * 256 + threadIdx.x;
+    live = slot < (uint32_t)a.n_paths;
+    p = blockIdx.x; path = live ? slot : (uint32_t)a.n_paths - 1;
+    gid = (size_t)p * a.n_paths + path;
+  } else {
+    gid = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= (size_t)a.batch * a.n_paths) return;
+    p = (uint32_t)(gid / a.n_paths); path = (uint32_t)(gid % a.n_paths);
+  }
   const uint32_t k0 = (uint32_t)(a.seed & 0xffffffffu), k1 = (uint32_t)(a.seed >> 32);
   constexpr int NP = (D + 1) / 2;
   // kept points wait in LDS (slot-major, thread fastest: no conflicts) until NBUF of them -- 16 doubles for D = 1, 2, 4, 15 for D = 3 -- go out as
@@ -137,7 +168,10 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
 #pragma unroll
     for (int i = 0; i < kMaxTheta; i++) th[i] = a.theta_v ? a.theta_v[(size_t)p * kMaxTheta + i] : a.theta[i];
   }
-  if constexpr (SEG) {
+  if constexpr (MO) {
+#pragma unroll
+    for (int i = 0; i < D; i++) x[i] = live ? a.pf_x[gid * D + i] : 0.0;
+  } else if constexpr (SEG) {
 #pragma unroll
     for (int i = 0; i < D; i++) x[i] = a.pf_x[gid * D + i];
   } else if (a.x0) {
@@ -165,7 +199,7 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
   }
   double isg[D], pw = 0.0, ow = 0.0;
   ObsCursor oc;
-  if constexpr (W) {
+  if constexpr (WS) {
     oc = ObsCursor(a, p);
 #pragma unroll
     for (int i = 0; i < D; i++) {
@@ -175,6 +209,38 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
     if constexpr (SEG) { if (!a.seg_first) oc.skip_through(a.k_begin); }
     if (oc.next == 0) { ow += obs_form<D>(a, p, oc.cur, x); oc.advance(); }
   }
+  // MO: the segment lies in one stretch of its problem -- the observations behind it are oc.cur, the row of the weights
+  double wt = 0.0;
+  double* red = nullptr;
+  int par = 0;
+  long long keep_k = 0, keep_slot = 0;
+  if constexpr (MO) {
+    __shared__ double red_lds[2 * 2 * D * 4];
+    red = red_lds;
+    oc = ObsCursor(a, p);
+    if (!a.seg_first) oc.skip_through(a.k_begin);
+    wt = live ? a.pf_wtab[((size_t)p * a.pf_rows + oc.cur) * a.n_paths + path] : 0.0;
+    keep_slot = ((long long)a.k_begin + a.stride) / a.stride;      // the first kept index behind k_begin
+    keep_k = keep_slot * a.stride;
+  }
+  auto reduce = [&](long long slot) {
+    double v[2 * D];
+#pragma unroll
+    for (int i = 0; i < D; i++) { v[i] = wt * x[i]; v[D + i] = v[i] * x[i]; }
+    double* r = red + par * 8 * D;
+#pragma unroll
+    for (int e = 0; e < 2 * D; e++) {
+      v[e] = wave_sum(v[e]);
+      if ((threadIdx.x & 63) == 0) r[e * 4 + (threadIdx.x >> 6)] = v[e];
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * D) {
+      const double* q4 = r + threadIdx.x * 4;
+      a.pf_part[(((size_t)p * gridDim.y + blockIdx.y) * a.n_keep + (size_t)slot) * 2 * D + threadIdx.x] = ((q4[0] + q4[1]) + q4[2]) + q4[3];
+    }
+    par ^= 1;
+  };
+  if constexpr (MO) { if (a.seg_first) reduce(0); }
   double sq[ST ? D : 1], sg1[ST ? D : 1], sh[ST ? D : 1], phi[ST ? D : 1];
   if constexpr (ST) {
 #pragma unroll
@@ -188,7 +254,7 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
   const int k_first = SEG ? a.k_begin + 1 : 1, k_stop = SEG ? a.k_end + 1 : a.Np;
   for (int k = k_first; k < k_stop; k++) {
     double f[D], fm[D];
-    if constexpr (W) model_drift<D>(a.model, th, x, fm);
+    if constexpr (WS) model_drift<D>(a.model, th, x, fm);
     if (W || a.kind == VGPA_PATHS_POSTERIOR) {
       const double* Ak = A + (size_t)(k - 1) * D * D;
       const double* bk = bv + (size_t)(k - 1) * D;
@@ -210,15 +276,18 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
       double s = 0.0;
 #pragma unroll
       for (int j = 0; j <= i; j++) s += R[i * D + j] * z[j];
-      if constexpr (W) { const double d = f[i] - fm[i]; pw -= isg[i] * d * (s + 0.5 * a.dt * d); }
+      if constexpr (WS) { const double d = f[i] - fm[i]; pw -= isg[i] * d * (s + 0.5 * a.dt * d); }
       if constexpr (ST) {
         const double r = a.dt * (f[i] - fm[i]) + s;
         sq[i] += r * r / a.dt; sg1[i] += phi[i] * r; sh[i] += a.dt * (phi[i] * phi[i]);
       }
       x[i] = (x[i] + a.dt * f[i]) + s;
     }
-    if constexpr (W) {
+    if constexpr (WS) {
       if (k == oc.next) { ow += obs_form<D>(a, p, oc.cur, x); oc.advance(); }
+    }
+    if constexpr (MO) {
+      if (k == keep_k) { reduce(keep_slot++); keep_k += a.stride; }
     }
     if (store && --until == 0) {
       until = a.stride;
@@ -233,7 +302,12 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
     }
   }
   for (int e = 0; e < slot * D; e++) o[e] = sg[e * 256];
-  if constexpr (SEG) {
+  if constexpr (MO) {
+    if (live) {
+#pragma unroll
+      for (int i = 0; i < D; i++) a.pf_x[gid * D + i] = x[i];
+    }
+  } else if constexpr (SEG) {
     a.pf_lw[gid] += pw - 0.5 * ow;
 #pragma unroll
     for (int i = 0; i < D; i++) a.pf_x[gid * D + i] = x[i];
@@ -285,10 +359,16 @@ __device__ __forceinline__ void normals_c(uint32_t k0, uint32_t k1, uint32_t k, 
 // SEG: as in k_sample_small; A_{k_begin} is the first matrix loaded, and the end states leave through `put` as [path][D].
 // ST: the lane adds r^2 / dt and r = dt d + eta (phi = 1: Lorenz-96) of its own rows to Q and G of the path's row of pf_stats, read at the
 // segment's entry and written at its exit; H_j = dt k_end, the constant dt times the steps walked so far, is written and not summed.
-template <int NT, bool W, bool SEG = false, bool ST = false>
+// MO: a segment of the replay: the states only.  At a kept k every lane multiplies its rows of x_k by its path's weight (0 behind the last
+// path), four cross-lane steps add the 16 paths of the wave, the lanes of path column 0 put their rows into red [4 waves][2][NT] -- the
+// Zs region, which a segment does not use --, and behind the next barrier the walk has anyway (the first of the next step, or one behind
+// the loop) thread t < 2 D adds the four waves in order and stores moment t / D of component t mod D.
+template <int NT, bool W, bool SEG = false, bool ST = false, bool MO = false>
 __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
   static_assert(W || !SEG, "a segment is a weighted walk");
   static_assert(SEG || !ST, "the statistics are carried by the segments");
+  static_assert(!MO || (SEG && !ST), "the replay is a segment without statistics");
+  constexpr bool WS = W && !MO;      // the weight sums are formed
   using Sh = MfmaShape<NT>;
   constexpr int LDA = Sh::LDA, MT = Sh::MT, KT = Sh::KT, NPF = Sh::NPF;
   extern __shared__ double lds[];
@@ -379,7 +459,7 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
     if (store) { put(o, row_len); o += D; }
   };
   // weighted: 1 / Sigma_ii of the lane's rows, the two sums, theta, the observation cursor
-  double isg[W ? MT : 1][4], pw = 0.0, ow = 0.0, th = 0.0;
+  double isg[WS ? MT : 1][4], pw = 0.0, ow = 0.0, th = 0.0;
   double sq[ST ? MT : 1][4], sg1[ST ? MT : 1][4];
   if constexpr (ST) {
     const double* row0 = a.pf_stats + ((size_t)p * a.n_paths + path) * 3 * D;
@@ -414,7 +494,7 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
       }
     oc.advance();
   };
-  if constexpr (W) {
+  if constexpr (WS) {
     th = a.theta_v ? a.theta_v[(size_t)p * kMaxTheta] : a.theta[0];
 #pragma unroll
     for (int mt = 0; mt < MT; mt++)
@@ -427,10 +507,43 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
     for (int r = 0; r < 4; r++) Xs[(mt * 16 + q + 4 * r) * 16 + j16] = x[mt][r];
   __syncthreads();
   keep();
-  if constexpr (W) {
+  if constexpr (WS) {
     if constexpr (!SEG) put(a.start + ((size_t)p * a.n_paths + path0) * D, (size_t)D);
     if (oc.next == 0) observe();
   }
+  // MO: the segment lies in one stretch of its problem -- the observations behind it are oc.cur, the row of the weights
+  double wt = 0.0;
+  double* red = lds + NT * LDA + NT + 4 * NT * 16;
+  long long keep_k = 0, keep_slot = 0, pending = -1;
+  if constexpr (MO) {
+    wt = path < (uint32_t)a.n_paths ? a.pf_wtab[((size_t)p * a.pf_rows + oc.cur) * a.n_paths + path] : 0.0;
+    keep_slot = ((long long)a.k_begin + a.stride) / a.stride;      // the first kept index behind k_begin
+    keep_k = keep_slot * a.stride;
+  }
+  auto reduce = [&](long long slot) {
+#pragma unroll
+    for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        double v1 = wt * x[mt][r], v2 = v1 * x[mt][r];
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) { v1 += __shfl_xor(v1, o); v2 += __shfl_xor(v2, o); }
+        if (j16 == 0) { red[(w * 2 + 0) * NT + mt * 16 + q + 4 * r] = v1; red[(w * 2 + 1) * NT + mt * 16 + q + 4 * r] = v2; }
+      }
+    pending = slot;
+  };
+  auto flush = [&]() {      // (behind a barrier that follows reduce)
+    if (pending >= 0) {
+      if (tid < 2 * D) {
+        const int m = tid >= D ? 1 : 0, row = tid - m * D;
+        const double* r0 = red + m * NT + row;
+        a.pf_part[(((size_t)p * gridDim.y + blockIdx.y) * a.n_keep + (size_t)pending) * 2 * D + tid] =
+            ((r0[0] + r0[2 * NT]) + r0[4 * NT]) + r0[6 * NT];
+      }
+      pending = -1;
+    }
+  };
+  if constexpr (MO) { if (a.seg_first) reduce(0); }
 
   int until = a.stride;
   for (int k = k_first; k < k_stop; k++) {
@@ -457,7 +570,7 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
     // weighted: the rows of x_{k-1} that the circular drift reaches by wrapping around -- 0, D - 1, D - 2 -- once per step
     const double* xq = Xs + q * 16 + j16;
     double w0 = 0.0, wl1 = 0.0, wl2 = 0.0;
-    if constexpr (W) { w0 = Xs[j16]; wl1 = Xs[(D - 1) * 16 + j16]; wl2 = Xs[(D - 2) * 16 + j16]; }
+    if constexpr (WS) { w0 = Xs[j16]; wl1 = Xs[(D - 1) * 16 + j16]; wl2 = Xs[(D - 2) * 16 + j16]; }
 #pragma unroll
     for (int mt = 0; mt < MT; mt++) {
       d4 acc = {0.0, 0.0, 0.0, 0.0};
@@ -471,7 +584,7 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
 #pragma unroll
         for (int kk = 0; kk < KT; kk++) nz = __builtin_amdgcn_mfma_f64_16x16x4f64(rr[kk * 4], Zs[(kk * 4 + q) * 16 + j16], nz, 0, 0, 0);
       }
-      if constexpr (W) {
+      if constexpr (WS) {
 #pragma unroll
         for (int r = 0; r < 4; r++) {
           const int row = mt * 16 + q + 4 * r;
@@ -496,6 +609,7 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
       for (int r = 0; r < 4; r++) x[mt][r] = (x[mt][r] + a.dt * (bs[mt * 16 + q + 4 * r] - acc[r])) + nz[r];
     }
     __syncthreads();
+    if constexpr (MO) flush();
     if (more) {
 #pragma unroll
       for (int n = 0; n < NPF; n++) { const int e = tid + 256 * n; if (e < DD) As[(e / D) * LDA + e % D] = pa[n]; }
@@ -507,11 +621,18 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
       for (int r = 0; r < 4; r++) Xs[(mt * 16 + q + 4 * r) * 16 + j16] = x[mt][r];
     __syncthreads();
     if (--until == 0) { until = a.stride; keep(); }
-    if constexpr (W) {
+    if constexpr (WS) {
       if (k == oc.next) observe();
     }
+    if constexpr (MO) {
+      if (k == keep_k) { reduce(keep_slot++); keep_k += a.stride; }
+    }
   }
-  if constexpr (W) {
+  if constexpr (MO) {
+    __syncthreads();
+    flush();
+    put(a.pf_x + ((size_t)p * a.n_paths + path0) * D, (size_t)D);      // (Xs holds x_{k_end} behind the loop's last barrier)
+  } else if constexpr (W) {
     pw += __shfl_xor(pw, 16); pw += __shfl_xor(pw, 32);
     ow += __shfl_xor(ow, 16); ow += __shfl_xor(ow, 32);
     if constexpr (SEG) {
@@ -615,12 +736,12 @@ hipError_t launch_mfma(const SampleArgs& a, hipStream_t st) {
 }
 
 // ---- the particle filter: the start, the segments, the resampling step between them ------------------------------------------------
-template <int NT, bool ST = false>
+template <int NT, bool ST = false, bool MO = false>
 hipError_t launch_mfma_segment(const SampleArgs& a, hipStream_t st) {
   const size_t lds = MfmaShape<NT>::lds_doubles(false) * sizeof(double);
-  if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k_sample_mfma<NT, true, true, ST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k_sample_mfma<NT, true, true, ST, MO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if ((a.n_paths + 63) / 64 > 65535) return hipErrorInvalidValue;      // (grid.y)
-  hipLaunchKernelGGL((k_sample_mfma<NT, true, true, ST>), dim3(a.batch, (a.n_paths + 63) / 64), dim3(256), lds, st, a);
+  hipLaunchKernelGGL((k_sample_mfma<NT, true, true, ST, MO>), dim3(a.batch, (a.n_paths + 63) / 64), dim3(256), lds, st, a);
   return hipGetLastError();
 }
 
@@ -672,17 +793,6 @@ __global__ __launch_bounds__(256) void k_pf_start(PfArgs a) {
     }
   }
   a.lw[gid] = init - a.obs_const_scale * (a.obs_const_v ? a.obs_const_v[p] : a.obs_const);
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-  return v;
 }
 
 // The step between two segments, one workgroup per problem, at grid index a.k.  A problem without an observation at a.k
@@ -815,6 +925,106 @@ __global__ __launch_bounds__(256) void k_pf_stats_mean(int D, int n, const doubl
   }
 }
 
+// ---- the smoothing moments: the descendant weights, the gather of the replay, the sum of the workgroups' partial sums -----------------
+// v summed over the workgroup in a fixed order: the butterfly of each wave, then the four waves through `red`
+__device__ __forceinline__ double block_sum(double v, double* red) {
+  v = wave_sum(v);
+  __syncthreads();      // (red of the sum before has been read)
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// The descendant weights, one workgroup per problem with c observations of its own: row c of wtab [rows][n] is
+// W_i = w_i / sum w, w_i = exp(lw_i - max lw); for j = c-1 .. 0 row j is row j+1 where the cloud was carried on at observation j, else
+// W^j_a = the sum of W^{j+1}_i over the slots i with anc_i = a.  Systematic resampling makes anc non-decreasing, so these slots are the run
+// [first i with anc_i >= a, first i with anc_i >= a + 1), found by two bisections and added in increasing i by slot a's own thread: no
+// atomics, and no order that depends on the launch.  less[j] = 1 / sum_i (W^j_i)^2.
+__global__ __launch_bounds__(256) void k_pf_descend(PfArgs a, int rows, double* wtab_all, double* less_all) {
+  __shared__ double red[4];
+  const int p = blockIdx.x, tid = threadIdx.x, n = a.n_paths;
+  const int cnt = a.n_obs_v ? a.n_obs_v[p] : a.n_obs;
+  const double* lw = a.lw + (size_t)p * n;
+  double* wtab = wtab_all + (size_t)p * rows * n;
+  double* less = less_all + (size_t)p * rows;
+  double mx = -INFINITY;
+  for (int i = tid; i < n; i += 256) mx = fmax(mx, lw[i]);
+  mx = wave_max(mx);
+  if ((tid & 63) == 0) red[tid >> 6] = mx;
+  __syncthreads();
+  mx = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+  double s = 0.0;
+  for (int i = tid; i < n; i += 256) s += exp(lw[i] - mx);
+  s = block_sum(s, red);
+  double* row = wtab + (size_t)cnt * n;
+  double s2 = 0.0;
+  for (int i = tid; i < n; i += 256) { const double wi = exp(lw[i] - mx) / s; row[i] = wi; s2 += wi * wi; }
+  s2 = block_sum(s2, red);      // (its barriers also order the row's stores before the reads below)
+  if (tid == 0) less[cnt] = 1.0 / s2;
+  for (int j = cnt - 1; j >= 0; j--) {
+    const double* next = row;
+    row = wtab + (size_t)j * n;
+    const size_t hj = (size_t)p * a.M + j;
+    const int32_t* anc = a.h_anc + hj * n;
+    const bool gathered = a.h_flag[hj] != 0;      // (uniform over the workgroup)
+    s2 = 0.0;
+    for (int i = tid; i < n; i += 256) {
+      double wi = next[i];
+      if (gathered) {
+        int lo = 0, hi = n;
+        while (lo < hi) { const int mid = (lo + hi) >> 1; if (anc[mid] < i) lo = mid + 1; else hi = mid; }
+        int end = lo;
+        hi = n;
+        while (end < hi) { const int mid = (end + hi) >> 1; if (anc[mid] <= i) end = mid + 1; else hi = mid; }
+        wi = 0.0;
+        int m = lo;
+        for (; m + 8 <= end; m += 8) {      // (eight loads in flight, the additions in slot order)
+          double t8[8];
+#pragma unroll
+          for (int u = 0; u < 8; u++) t8[u] = next[m + u];
+#pragma unroll
+          for (int u = 0; u < 8; u++) wi += t8[u];
+        }
+        for (; m < end; m++) wi += next[m];
+      }
+      row[i] = wi;
+      s2 += wi * wi;
+    }
+    s2 = block_sum(s2, red);
+    if (tid == 0) less[j] = 1.0 / s2;
+  }
+}
+
+// The step between two segments of the replay at grid index a.k: workgroup (p, y) moves its share of problem p's particles from x_in to
+// x_out by the ancestors the filter stored for the problem's observation at a.k (the identity where the cloud was carried on), or
+// unchanged where the problem has no observation there.
+__global__ __launch_bounds__(256) void k_pf_gather(PfArgs a) {
+  const int p = blockIdx.x, n = a.n_paths, D = a.D;
+  const int64_t* t = a.obs_t + (size_t)p * a.obs_t_stride;
+  const int cnt = a.n_obs_v ? a.n_obs_v[p] : a.n_obs;
+  int j = -1;
+  for (int m = 0; m < cnt; m++) if (t[m] == (int64_t)a.k) j = m;
+  const size_t nD = (size_t)n * D;
+  const double* xin = a.x_in + (size_t)p * nD;
+  double* xout = a.x_out + (size_t)p * nD;
+  const int32_t* anc = j < 0 ? nullptr : a.h_anc + ((size_t)p * a.M + j) * n;
+  for (size_t e = (size_t)blockIdx.y * 256 + threadIdx.x; e < nD; e += (size_t)gridDim.y * 256) {
+    const size_t i = e / D;
+    xout[e] = anc ? xin[(size_t)anc[i] * D + (e - i * D)] : xin[e];
+  }
+}
+
+// out [B][len] = the sum over the workgroups blk = 0 .. n_blocks-1 of part [B][n_blocks][len], added in that order
+__global__ __launch_bounds__(256) void k_pf_moments_sum(int n_blocks, size_t len, size_t total, const double* part, double* out) {
+  const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;      // (one thread per entry of out, the problems behind one another)
+  if (g >= total) return;
+  const size_t p = g / len, e = g - p * len;
+  const double* src = part + p * n_blocks * len + e;
+  double s = 0.0;
+  for (int blk = 0; blk < n_blocks; blk++) s += src[(size_t)blk * len];
+  out[g] = s;
+}
+
 template <bool W>
 hipError_t launch_posterior(const SampleArgs& a, hipStream_t st) {
   const size_t lanes = (size_t)a.batch * a.n_paths;
@@ -841,6 +1051,23 @@ hipError_t launch_sample_segment(const SampleArgs& a, hipStream_t st) {
   if (a.k_begin < 0 || a.k_end < a.k_begin || a.k_end >= a.Np) return hipErrorInvalidValue;
   if (a.model != VGPA_MODEL_OU && a.model != VGPA_MODEL_DW && a.model != VGPA_MODEL_L63 && a.model != VGPA_MODEL_L96) return hipErrorInvalidValue;
   if (a.D > kMaxLaneD && a.model != VGPA_MODEL_L96) return hipErrorInvalidValue;
+  if (a.pf_wtab) {       // the segments of the replay (vgpa_particle_moments)
+    if (a.pf_stats || !a.pf_part || a.stride < 1 || a.pf_rows < 1 || sample_segment_blocks(a.D, a.n_paths) > 65535) return hipErrorInvalidValue;
+    if (a.D <= kMaxLaneD) {
+      const dim3 grid(a.batch, sample_segment_blocks(a.D, a.n_paths)), block(256);
+      switch (a.D) {
+        case 1: hipLaunchKernelGGL((k_sample_small<1, true, true, false, true>), grid, block, 0, st, a); break;
+        case 2: hipLaunchKernelGGL((k_sample_small<2, true, true, false, true>), grid, block, 0, st, a); break;
+        case 3: hipLaunchKernelGGL((k_sample_small<3, true, true, false, true>), grid, block, 0, st, a); break;
+        default: hipLaunchKernelGGL((k_sample_small<4, true, true, false, true>), grid, block, 0, st, a); break;
+      }
+      return hipGetLastError();
+    }
+    if (a.D <= 16) return launch_mfma_segment<16, false, true>(a, st);
+    if (a.D <= 32) return launch_mfma_segment<32, false, true>(a, st);
+    if (a.D <= 48) return launch_mfma_segment<48, false, true>(a, st);
+    return launch_mfma_segment<64, false, true>(a, st);
+  }
   if (a.pf_stats) {      // the segments that carry the path statistics (vgpa_particle_statistics)
     if (a.D <= kMaxLaneD) {
       const dim3 grid((unsigned)(((size_t)a.batch * a.n_paths + 255) / 256)), block(256);
@@ -884,6 +1111,29 @@ hipError_t launch_pf_resample(const PfArgs& a, hipStream_t st) {
   if ((a.st_in == nullptr) != (a.st_out == nullptr) || (a.st_in && a.st_in == a.st_out)) return hipErrorInvalidValue;
   if (a.st_in) hipLaunchKernelGGL(k_pf_resample<true>, dim3(a.batch), dim3(256), 0, st, a);
   else hipLaunchKernelGGL(k_pf_resample<false>, dim3(a.batch), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+int sample_segment_blocks(int D, int n_paths) { return D <= kMaxLaneD ? (n_paths + 255) / 256 : (n_paths + 63) / 64; }
+
+hipError_t launch_pf_descend(const PfArgs& a, int rows, double* wtab, double* less, hipStream_t st) {
+  if (a.batch < 1 || a.n_paths < 1 || a.M < 1 || rows < a.M + 1 || !a.lw || !a.h_flag || !a.h_anc || !wtab || !less) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_pf_descend, dim3(a.batch), dim3(256), 0, st, a, rows, wtab, less);
+  return hipGetLastError();
+}
+
+hipError_t launch_pf_gather(const PfArgs& a, hipStream_t st) {
+  if (a.D < 1 || a.batch < 1 || a.n_paths < 1 || !a.x_in || !a.x_out || a.x_in == a.x_out || !a.h_anc) return hipErrorInvalidValue;
+  const size_t nD = (size_t)a.n_paths * a.D;
+  const unsigned shares = (unsigned)((nD + 1023) / 1024 < 64 ? (nD + 1023) / 1024 : 64);
+  hipLaunchKernelGGL(k_pf_gather, dim3(a.batch, shares), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_pf_moments_sum(int batch, int n_blocks, size_t len, const double* part, double* out, hipStream_t st) {
+  const size_t total = (size_t)batch * len;
+  if (batch < 1 || n_blocks < 1 || len < 1 || (total + 255) / 256 > 0x7fffffffu || !part || !out) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_pf_moments_sum, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, n_blocks, len, total, part, out);
   return hipGetLastError();
 }
 

@@ -165,8 +165,10 @@ struct vgpa_ctx {
   double *d_sp_logw = nullptr, *d_sp_start = nullptr;      // vgpa_sample_paths_weighted: the two sums and x_0 of every path
   size_t sp_logw_n = 0, sp_start_n = 0;
   // vgpa_particle_filter: the two particle buffers, log-weights, prefix sums, ancestors of a step (int32), the histories (ess, flags and
-  // ancestors as int32, clouds), the prior's mean and factor; vgpa_particle_statistics: the two buffers of rows and their mean
-  enum { PF_XA, PF_XB, PF_LW, PF_CUM, PF_ANC, PF_ESS, PF_FLAG, PF_HANC, PF_CLOUDS, PF_MU, PF_LT, PF_STA, PF_STB, PF_MEAN, PF_COUNT };
+  // ancestors as int32, clouds), the prior's mean and factor; vgpa_particle_statistics: the two buffers of rows and their mean;
+  // vgpa_particle_moments: the descendant weights, the lineage ESS, the workgroups' partial sums, the moments
+  enum { PF_XA, PF_XB, PF_LW, PF_CUM, PF_ANC, PF_ESS, PF_FLAG, PF_HANC, PF_CLOUDS, PF_MU, PF_LT, PF_STA, PF_STB, PF_MEAN, PF_WTAB, PF_LESS, PF_PART,
+         PF_MOM, PF_COUNT };
   double* d_pf[PF_COUNT] = {};
   size_t pf_n[PF_COUNT] = {};
   // profiling
@@ -1567,27 +1569,44 @@ int vgpa_sample_paths_weighted(vgpa_ctx* c, const double* x, const double* x0, i
 // indices of the batch, the particles resident between the cuts, a resampling step behind every cut that is an observation of some problem.
 // with_stats: vgpa_particle_statistics -- the same walk, counters and resampling decisions, every slot's [3][D] row of
 // path statistics carried along its lineage; stats / mean: where the final rows and their weighted mean go.
+// moments set: vgpa_particle_moments -- behind the filter, whose ancestor history stays on the device, the descendant
+// weights, then the walk once more from the same counters (the stored ancestors in place of the resampling decisions) with the weighted
+// sums taken at every stride-th grid index; `state` is then what the replay arrived at.
 static int particle_run(vgpa_ctx* c, const double* x, const double* x0, int32_t n_paths, uint64_t seed, double ess_fraction,
                         const double* prior_mu, const double* prior_tau, double* logw, double* state, double* ess, int32_t* resampled,
-                        int32_t* ancestors, double* clouds, bool with_stats, double* stats, double* mean) {
+                        int32_t* ancestors, double* clouds, bool with_stats, double* stats, double* mean, int32_t stride = 1,
+                        double* moments = nullptr, double* lineage_ess = nullptr) {
   if (!c) return VGPA_ERR_ARG;
   if (!logw || !state) return fail(c, VGPA_ERR_ARG, "null argument");
+  if (stride < 1) return fail(c, VGPA_ERR_ARG, "stride must be at least 1 (stride = %d)", stride);
   if (with_stats && !stats && !mean) return fail(c, VGPA_ERR_ARG, "at least one of stats and mean must be given");
   if (n_paths < 1) return fail(c, VGPA_ERR_ARG, "n_paths must be at least 1 (n_paths = %d)", n_paths);
   if (!(ess_fraction >= 0.0 && ess_fraction <= 1.0)) return fail(c, VGPA_ERR_ARG, "ess_fraction must lie in [0, 1] (ess_fraction = %g)", ess_fraction);
   if ((prior_mu == nullptr) != (prior_tau == nullptr)) return fail(c, VGPA_ERR_ARG, "the prior is a mean and a covariance: both or neither");
   if (c->cfg.model == VGPA_MODEL_NONE) return fail(c, VGPA_ERR_ARG, "context has no stochastic model: no model SDE to weigh the particles against");
   if (!c->full) return fail(c, VGPA_ERR_STATE, "context was created without m0/s0/observations (ODE-only)");
+  const int D = c->D, B = c->B, M = c->M, Np = c->Np, M1 = M > 0 ? M : 1;
+  if (moments && D <= kMaxSmallD) {      // the launch limits of the replay and of the final sum, before any work: grid.y of the segments, grid.x of the sum
+    if (sample_segment_blocks(D, n_paths) > 65535)
+      return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing moments are built for at most %d particles per problem at D = %d (n_paths = %d)",
+                  65535 * (D <= kMaxLaneD ? 256 : 64), D, n_paths);
+    if (((size_t)B * ((size_t)((Np - 1) / stride + 1) * 2 * D) + 255) / 256 > 0x7fffffffu)
+      return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing moments are built for at most 2^39 entries (batch %d, %d kept grid indices, D = %d): use a larger stride",
+                  B, (Np - 1) / stride + 1, D);
+  }
   SampleArgs a;
   int rc;
   if ((rc = sample_args(c, VGPA_PATHS_POSTERIOR, x, x0, n_paths, 1, seed, true, &a))) return rc;
-  const int D = c->D, B = c->B, M = c->M, Np = c->Np, M1 = M > 0 ? M : 1;
   const size_t n = (size_t)n_paths, BnD = (size_t)B * n * D, Bn = (size_t)B * n, BM = (size_t)B * M1;
   auto buf = [&](int which, size_t count) { return grow(c, &c->d_pf[which], &c->pf_n[which], count); };
   auto ints = [](size_t count) { return (count + 1) / 2; };      // int32 entries in a buffer of doubles
   if ((rc = buf(vgpa_ctx::PF_XA, BnD)) || (rc = buf(vgpa_ctx::PF_XB, BnD)) || (rc = buf(vgpa_ctx::PF_LW, Bn)) || (rc = buf(vgpa_ctx::PF_CUM, Bn)) ||
       (rc = buf(vgpa_ctx::PF_ANC, ints(Bn))) || (rc = buf(vgpa_ctx::PF_ESS, BM)) || (rc = buf(vgpa_ctx::PF_FLAG, ints(BM)))) return rc;
-  if (ancestors && (rc = buf(vgpa_ctx::PF_HANC, ints(BM * n)))) return rc;
+  if ((ancestors || moments) && (rc = buf(vgpa_ctx::PF_HANC, ints(BM * n)))) return rc;
+  const int rows = M1 + 1, n_blocks = sample_segment_blocks(D, n_paths);
+  const size_t mom_len = (size_t)((Np - 1) / stride + 1) * 2 * D;
+  if (moments && ((rc = buf(vgpa_ctx::PF_WTAB, (size_t)B * rows * n)) || (rc = buf(vgpa_ctx::PF_LESS, (size_t)B * rows)) ||
+                  (rc = buf(vgpa_ctx::PF_PART, (size_t)B * n_blocks * mom_len)) || (rc = buf(vgpa_ctx::PF_MOM, (size_t)B * mom_len)))) return rc;
   if (clouds && (rc = buf(vgpa_ctx::PF_CLOUDS, BM * n * D))) return rc;
   if (with_stats && ((rc = buf(vgpa_ctx::PF_STA, 3 * BnD)) || (rc = buf(vgpa_ctx::PF_STB, 3 * BnD)) || (rc = buf(vgpa_ctx::PF_MEAN, (size_t)B * 3 * D)))) return rc;
   PfArgs f{};
@@ -1607,7 +1626,7 @@ static int particle_run(vgpa_ctx* c, const double* x, const double* x0, int32_t 
   f.x = cur; f.ws = other; f.lw = c->d_pf[vgpa_ctx::PF_LW]; f.cum = c->d_pf[vgpa_ctx::PF_CUM];
   f.anc = reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_ANC]);
   f.h_ess = c->d_pf[vgpa_ctx::PF_ESS]; f.h_flag = reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_FLAG]);
-  f.h_anc = ancestors ? reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_HANC]) : nullptr;
+  f.h_anc = (ancestors || moments) ? reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_HANC]) : nullptr;
   f.h_clouds = clouds ? c->d_pf[vgpa_ctx::PF_CLOUDS] : nullptr;
   HIP_TRY(c, hipMemsetAsync(f.h_ess, 0, BM * sizeof(double), c->stream));
   HIP_TRY(c, hipMemsetAsync(f.h_flag, 0, BM * sizeof(int32_t), c->stream));
@@ -1638,6 +1657,36 @@ static int particle_run(vgpa_ctx* c, const double* x, const double* x0, int32_t 
     std::swap(cur, other);
     std::swap(st_cur, st_other);
   }
+  if (moments) {
+    double* wtab = c->d_pf[vgpa_ctx::PF_WTAB];
+    double* less = c->d_pf[vgpa_ctx::PF_LESS];
+    HIP_TRY(c, hipMemsetAsync(less, 0, (size_t)B * rows * sizeof(double), c->stream));
+    LAUNCH_TRY(c, "descendant weights launch", launch_pf_descend(f, rows, wtab, less, c->stream));
+    // the replay: the start and the segments once more; the start's log-weights go to the prefix sums' buffer, which nothing reads any more
+    cur = c->d_pf[vgpa_ctx::PF_XA]; other = c->d_pf[vgpa_ctx::PF_XB];
+    PfArgs g = f;
+    g.x = cur; g.ws = other; g.lw = c->d_pf[vgpa_ctx::PF_CUM]; g.st_in = nullptr; g.st_out = nullptr;
+    LAUNCH_TRY(c, "particle start launch", launch_pf_start(g, c->stream));
+    SampleArgs r = a;
+    r.stride = stride; r.n_keep = (Np - 1) / stride + 1; r.seg_first = 1; r.pf_stats = nullptr;
+    r.pf_wtab = wtab; r.pf_part = c->d_pf[vgpa_ctx::PF_PART]; r.pf_rows = rows;
+    prev = 0;
+    for (int k = 0; k < Np; k++) {
+      if (!is_obs[k] && k != Np - 1) continue;
+      r.k_begin = prev; r.k_end = k; r.pf_x = cur;
+      LAUNCH_TRY(c, "replay segment launch", launch_sample_segment(r, c->stream));
+      r.seg_first = 0; prev = k;
+      if (!is_obs[k]) continue;
+      g.k = k; g.x_in = cur; g.x_out = other;
+      LAUNCH_TRY(c, "replay gather launch", launch_pf_gather(g, c->stream));
+      std::swap(cur, other);
+    }
+    LAUNCH_TRY(c, "moments sum launch", launch_pf_moments_sum(B, n_blocks, mom_len, r.pf_part, c->d_pf[vgpa_ctx::PF_MOM], c->stream));
+    if ((rc = download(c, moments, c->d_pf[vgpa_ctx::PF_MOM], (size_t)B * mom_len))) return rc;
+    if (lineage_ess)      // (the device's rows are M1 + 1 = M + 1, but for a context of capacity 0)
+      for (int p = 0; p < (rows == M + 1 ? 1 : B); p++)
+        if ((rc = download(c, lineage_ess + (size_t)p * (M + 1), less + (size_t)p * rows, rows == M + 1 ? (size_t)B * rows : (size_t)M + 1))) return rc;
+  }
   if (with_stats && mean) {
     LAUNCH_TRY(c, "path statistics mean launch", launch_pf_stats_mean(D, B, n_paths, f.lw, st_cur, c->d_pf[vgpa_ctx::PF_MEAN], c->stream));
     if ((rc = download(c, mean, c->d_pf[vgpa_ctx::PF_MEAN], (size_t)B * 3 * D))) return rc;
@@ -1666,6 +1715,16 @@ int vgpa_particle_statistics(vgpa_ctx* c, const double* x, const double* x0, int
                              const double* prior_mu, const double* prior_tau, double* logw, double* state, double* stats, double* mean,
                              double* ess, int32_t* resampled) {
   return particle_run(c, x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled, nullptr, nullptr, true, stats, mean);
+}
+
+// The smoothing moments on the grid under the particles' genealogy (see vgpa_hip.h)
+int vgpa_particle_moments(vgpa_ctx* c, const double* x, const double* x0, int32_t n_paths, int32_t stride, uint64_t seed, double ess_fraction,
+                          const double* prior_mu, const double* prior_tau, double* logw, double* state, double* moments, double* lineage_ess,
+                          double* ess, int32_t* resampled) {
+  if (!c) return VGPA_ERR_ARG;
+  if (!moments) return fail(c, VGPA_ERR_ARG, "null argument");
+  return particle_run(c, x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled, nullptr, nullptr, false, nullptr,
+                      nullptr, stride, moments, lineage_ess);
 }
 
 int vgpa_fetch(vgpa_ctx* c, int which, double* out) {

@@ -264,9 +264,17 @@ struct SampleArgs {
   // the path statistics of a lineage (vgpa_particle_statistics): set, the ST instantiations run and add every step's
   // Q_j += r_j^2 / dt, G_j += phi_j r_j, H_j += dt phi_j^2 (r = dt (g - f) + eta, phi_j = df_j / dtheta_a(j) at x_{k-1}) to the slot's row
   double* pf_stats;         // [B][n_paths][3][D], or nullptr
+  // the replay of vgpa_particle_moments: pf_wtab set, the MO instantiations run -- the walk of the segment without its
+  // weight sums (pf_lw is not touched); at every kept grid index k = 0 mod stride of the segment (k = 0: the first segment) workgroup
+  // (p, blk) stores sum_i W_i x_i(k) and sum_i W_i x_i(k)^2 over its own slots, W = the row of pf_wtab of the problem's stretch
+  const double* pf_wtab;    // [B][pf_rows][n_paths] descendant weights, or nullptr
+  double* pf_part;          // [B][sample_segment_blocks()][n_keep][2][D]
+  int pf_rows;
 };
 hipError_t launch_sample_paths(const SampleArgs& a, hipStream_t st);
 hipError_t launch_sample_segment(const SampleArgs& a, hipStream_t st);
+// workgroups per problem of a segment launch: the blocks of the MO instantiations' partial sums
+int sample_segment_blocks(int D, int n_paths);
 
 // the start and the resampling step of the particle filter (sample.hip: k_pf_start, k_pf_resample)
 struct PfArgs {
@@ -299,6 +307,14 @@ hipError_t launch_pf_start(const PfArgs& a, hipStream_t st);
 hipError_t launch_pf_resample(const PfArgs& a, hipStream_t st);
 // mean [B][3][D] = sum_i w_i stats[.][i] / sum_i w_i, w_i = exp(lw_i - max lw) (sample.hip: k_pf_stats_mean)
 hipError_t launch_pf_stats_mean(int D, int batch, int n_paths, const double* lw, const double* stats, double* mean, hipStream_t st);
+// vgpa_particle_moments (sample.hip: k_pf_descend, k_pf_gather, k_pf_moments_sum).  Of PfArgs, descend reads lw, h_flag, h_anc, M and the
+// observation counts: wtab [B][rows][n_paths] gets row c = the normalised final weights and rows c-1 .. 0 by the backward recursion
+// through the stored ancestors, less [B][rows] the lineage ESS of the rows written (the others stay as they are); gather is the step
+// between two segments of the replay, x_out_i = x_in_{h_anc[p][j][i]} at the problem's observation j with t_j = k, a copy without one
+hipError_t launch_pf_descend(const PfArgs& a, int rows, double* wtab, double* less, hipStream_t st);
+hipError_t launch_pf_gather(const PfArgs& a, hipStream_t st);
+// out [B][len] = sum over blk, in block order, of part [B][n_blocks][len]
+hipError_t launch_pf_moments_sum(int batch, int n_blocks, size_t len, const double* part, double* out, hipStream_t st);
 
 // launchers (each returns hipGetLastError()) -----------------------------------------------------
 hipError_t launch_ode_generic(int method, bool fwd, const OdeArgs& a, hipStream_t st);

@@ -17,10 +17,35 @@ smoothing distribution is the score of log p(y | theta, Sigma), and score / info
 There is no Sigma step: the paths are imputed at the Sigma in force, their quadratic variation is Sigma T as dt -> 0 whatever the data
 say, so Sigma <- E[Q] / n_steps barely moves (0.77 .. 0.79 from Sigma = 0.8 on the fixtures at dt = 0.01).  Q serves the Q-function and as a
 diagnostic.
+
+SmoothingMoments: one problem's record of vgpa_particle_moments -- the smoothing mean and second moment on the time grid
+under the filter's genealogy.  The final weights are pushed backwards through the ancestors (descendant_weights): the weight of slot a in
+the stretch between observations j-1 and j is the total final weight of the slots that descend from it, and
+    E[x_k | y] ~ sum_i W^{j(k)}_i x_i(k)
+with x_i(k) the state of slot i as the walk arrives at k.  These are the marginals of the forward genealogical smoother: exact in the limit
+of many particles for the Euler-discretised model, but early stretches rest on few distinct lineages -- lineage_ess says how few.
 """
 import numpy as np
 
-__all__ = ["ParticleFilterResult", "PathStatistics"]
+__all__ = ["ParticleFilterResult", "PathStatistics", "SmoothingMoments", "descendant_weights"]
+
+
+def descendant_weights(log_w, ancestors, resampled):
+    """(M + 1, n): row M is w / sum w with w = exp(log_w - max log_w); row j < M is row j + 1 where the cloud was carried on at observation
+    j (resampled[j] false), else W^j_a = sum of W^{j+1}_i over the slots i with ancestors[j, i] = a, added in increasing i; a slot without
+    descendant gets 0.  Every row sums to 1 up to rounding.  Row j weighs the cloud at observation j (the states before its resampling
+    decision): with ParticleFilterResult.clouds, W[j] @ clouds[j] is the smoothing mean at that observation."""
+    log_w = np.asarray(log_w, dtype=float).ravel()
+    anc = np.asarray(ancestors, dtype=np.int64).reshape(-1, log_w.size)
+    flags = np.asarray(resampled).astype(bool).ravel()
+    if flags.size != anc.shape[0]:
+        raise ValueError(" descendant_weights: ancestors and resampled do not belong together.")
+    w = np.exp(log_w - np.max(log_w))
+    out = np.empty((flags.size + 1, log_w.size))
+    out[-1] = w / np.sum(w)
+    for j in range(flags.size - 1, -1, -1):
+        out[j] = np.bincount(anc[j], weights=out[j + 1], minlength=log_w.size) if flags[j] else out[j + 1]
+    return out
 
 
 class ParticleFilterResult(object):
@@ -77,6 +102,13 @@ class ParticleFilterResult(object):
             slot = self.ancestors[j, slot]
             out[:, j] = self.clouds[j, slot]
         return out
+
+    def smoothing_weights(self):
+        """(M_p + 1, n): descendant_weights of the record -- row j weighs clouds[j], so that the smoothing mean at observation j is
+        smoothing_weights()[j] @ clouds[j], equal to mean(lineages())[j] up to rounding without tracing a lineage.  Needs the ancestors."""
+        if self.ancestors is None:
+            raise ValueError(" ParticleFilterResult: smoothing_weights() needs the histories (particle_filter(..., history=True)).")
+        return descendant_weights(self.log_w, self.ancestors, self.resampled)
 
 
 class PathStatistics(object):
@@ -148,3 +180,66 @@ class PathStatistics(object):
         sg = np.broadcast_to(np.asarray(sigma_diag_new, dtype=float).ravel(), (self.dim_d,))
         q, g, h = self.mean
         return float(-0.5 * np.sum((q - 2.0 * delta * g + delta * delta * h) / sg + self.n_steps * np.log(2.0 * np.pi * sg * self.dt)))
+
+
+class SmoothingMoments(object):
+    """log_w (n,): the final unnormalised log-weights; moments (n_keep, 2, D): sum_i W_i x_i(k) and sum_i W_i x_i(k)^2 at the grid indices
+    k = 0, stride, 2 stride, ... < n_pts; obs_t: the problem's own observation indices; lineage_ess (M_p + 1,): 1 / sum W^2 of every stretch;
+    ess, resampled over the problem's observations.  single_dim: a 1-D model, the last axis of mean / second / var / std is dropped."""
+
+    def __init__(self, log_w, moments, stride, n_pts, obs_t, lineage_ess, ess=(), resampled=(), single_dim=False) -> None:
+        self.log_w = np.asarray(log_w, dtype=float).ravel()
+        if self.log_w.size < 1:
+            raise ValueError(" SmoothingMoments: at least one particle.")
+        self.stride, self.n_pts = int(stride), int(n_pts)
+        if self.stride < 1 or self.n_pts < 1:
+            raise ValueError(" SmoothingMoments: stride and n_pts must be at least 1.")
+        self.moments = np.asarray(moments, dtype=float)
+        if self.moments.ndim != 3 or self.moments.shape[:2] != ((self.n_pts - 1) // self.stride + 1, 2):
+            raise ValueError(" SmoothingMoments: moments must be (n_keep, 2, D).")
+        self.obs_t = np.asarray(obs_t, dtype=np.int64).ravel()
+        self.lineage_ess = np.asarray(lineage_ess, dtype=float).ravel()
+        self.ess = np.asarray(ess, dtype=float).ravel()
+        self.resampled = np.asarray(resampled).astype(bool).ravel()
+        if self.lineage_ess.size != self.obs_t.size + 1 or self.ess.size != self.resampled.size:
+            raise ValueError(" SmoothingMoments: obs_t, lineage_ess, ess and resampled do not belong together.")
+        self.single_dim = bool(single_dim)
+
+    def __len__(self):
+        return self.log_w.size
+
+    def _shape(self, a):
+        return a[..., 0] if self.single_dim else a
+
+    @property
+    def grid(self):
+        """the kept grid indices 0, stride, 2 stride, ..."""
+        return np.arange(0, self.n_pts, self.stride)
+
+    @property
+    def mean(self):
+        """E[x_k | y] on the grid"""
+        return self._shape(self.moments[:, 0].copy())
+
+    @property
+    def second(self):
+        """E[x_k^2 | y], component by component"""
+        return self._shape(self.moments[:, 1].copy())
+
+    @property
+    def var(self):
+        """second - mean^2, as it comes: where a stretch rests on one lineage the difference is rounding noise of either sign"""
+        return self._shape(self.moments[:, 1] - self.moments[:, 0] ** 2)
+
+    @property
+    def std(self):
+        return np.sqrt(np.maximum(self.var, 0.0))
+
+    def lineage_ess_on_grid(self):
+        """lineage_ess of the stretch each kept grid index lies in: index k belongs to stretch #{observations before k}"""
+        return self.lineage_ess[np.searchsorted(self.obs_t, self.grid, side="left")]
+
+    def log_evidence(self):
+        """logsumexp(log_w) - log n, as ParticleFilterResult.log_evidence()"""
+        top = np.max(self.log_w)
+        return float(top + np.log(np.sum(np.exp(self.log_w - top))) - np.log(self.log_w.size))

@@ -223,6 +223,23 @@ class VarGP(object):
         out = [self._statistics_record(res, k) for k in range(res["log_w"].shape[0])]
         return out[0] if self.batch == 1 else out
 
+    def _moments_record(self, res, k, stride, obs_t=None):
+        """One problem's SmoothingMoments from row k of Context.particle_moments' dict, cut to its own observations obs_t"""
+        from .particles import SmoothingMoments
+        t = np.asarray(self._inputs()["obs_t"] if obs_t is None else obs_t).ravel()
+        return SmoothingMoments(res["log_w"][k], res["moments"][k], stride, self.dim_n, t, res["lineage_ess"][k, :t.size + 1],
+                                res["ess"][k, :t.size], res["resampled"][k, :t.size], self.model.single_dim)
+
+    def particle_moments(self, n_paths, seed, stride=1, ess_fraction=0.5, x=None, x0=None):
+        """The smoothing mean and variance on the time grid from particle_filter with the same arguments: a particles.SmoothingMoments
+        (with batch > 1 a list, one per problem) -- mean, second, var, std at the grid indices 0, stride, ... under the filter's
+        genealogy, reduced on the device (no path is stored or copied), and lineage_ess, the number of distinct lineages each stretch
+        between two observations rests on in effect.  What to hold m_t and S_t against."""
+        xx = None if x is None else np.asarray(x, dtype=float)
+        res = self._context().particle_moments(n_paths, seed, stride=stride, ess_fraction=ess_fraction, x=xx, x0=x0, prior=self._prior())
+        out = [self._moments_record(res, k, stride) for k in range(res["log_w"].shape[0])]
+        return out[0] if self.batch == 1 else out
+
     def particle_fit_theta(self, n_paths, seed, iters, ess_fraction=0.5, refit=True, pooled=False):
         """Particle EM for the drift parameters (ProblemBatch.particle_fit_theta on a batch of one): (theta, trace), theta in the shape of
         model.theta."""
