@@ -324,6 +324,37 @@ int vgpa_particle_moments(vgpa_ctx* ctx, const double* x_or_null, const double* 
                           double ess_fraction, const double* prior_mu_or_null, const double* prior_tau_or_null, double* logw, double* state,
                           double* moments, double* lineage_ess_or_null, double* ess_or_null, int32_t* resampled_or_null);
 
+/* Whole smoothing trajectories on the time grid, drawn from the genealogy of the particle filter: K = n_draw complete
+ * paths of the Euler-discretised model as the filter's surviving lineages hold them, for path functionals that are no mean or variance.
+ * Three steps on the device behind the filter of vgpa_particle_filter, which runs unchanged with its ancestors kept: the final slots; their
+ * genealogy; one walk of the K trajectories alone.  The normals are counter-based and the state update is one instruction sequence, so a
+ * lineage is re-walked by a single lane that draws with the counter word of the slot the lineage sat in; nothing else is replayed.
+ *   stretches   as in vgpa_particle_moments: problem p has its own observation indices t_0 < ... < t_{c-1} in force; stretch j = 0 .. c
+ *               holds the grid indices t_{j-1} < k <= t_j with t_{-1} = -1 and t_c = Np-1
+ *   s_c[m]      the final slots, m = 0 .. K-1: final_slots_or_null (host int32, [batch][K], each in [0, n_paths)), or drawn by systematic
+ *               resampling from the final weights: w_i = exp(lw_i - max lw), cum = the inclusive prefix sums in slot order (associated as
+ *               the filter's resampling step associates them), S = cum_{n-1}, U = the first uniform of Philox counter (Np, 0, p, 0xffffffff)
+ *               under the seed's key (the filter draws with grid indices <= Np-1), u_m = (U + m) / K S,
+ *               s_c[m] = min(#{i: cum_i <= u_m}, n_paths-1).  Drawn trajectories are equally weighted; given ones carry the weights of
+ *               their final slots, which are the caller's to apply
+ *   s_j[m]      for j = c-1 .. 0: anc_j[s_{j+1}[m]] where the cloud was resampled at observation j, else s_{j+1}[m]
+ *   the walk    trajectory m starts at x0[p], or at m0_p + chol_lower(S0_p) xi_0 drawn with counter (0, s_0[m], p, .), and runs the
+ *               posterior recursion of vgpa_sample_paths(VGPA_PATHS_POSTERIOR) for k = 1 .. Np-1, the step to k drawing with counter
+ *               (k, s_{j(k)}[m], p, .), j(k) the stretch of k (an observation at grid index 0 makes stretch 0 the single index 0)
+ *   paths            host, [batch][K][n_keep][D], n_keep = (Np-1) / stride + 1, in the layout and with the stride of vgpa_sample_paths.
+ *                    At stride 1, paths[p][m][t_j] is bit for bit the filter's clouds[p][j][s_j[m]] and paths[p][m][Np-1] is bit for bit
+ *                    state[p][s_c[m]].  On collapsing clouds the early stretches of all K trajectories coincide (the rows of slots say so)
+ *   slots_or_null    host int32, [batch][M+1][K]: s_j[m] for j = 0 .. c; rows beyond a problem's own count + 1: -1
+ *   logw, state, ess_or_null, resampled_or_null and every other argument: as in vgpa_particle_filter, and bit-identical to its results with
+ *   the same arguments.  K > n_paths is legal.  With x NULL the cached state is read and not written
+ * Errors: as vgpa_particle_filter, and VGPA_ERR_ARG for n_draw < 1, a NULL paths, stride < 1 or a given slot outside [0, n_paths);
+ * VGPA_ERR_UNSUPPORTED, before any work, for more than 65535 * 64 trajectories per problem above D = 4 (2^31 - 1 workgroups of 256 lanes
+ * over the batch at D <= 4) or more than 2^35 entries of paths. */
+int vgpa_particle_paths(vgpa_ctx* ctx, const double* x_or_null, const double* x0_or_null, int32_t n_paths, int32_t n_draw,
+                        const int32_t* final_slots_or_null, int32_t stride, uint64_t seed, double ess_fraction,
+                        const double* prior_mu_or_null, const double* prior_tau_or_null, double* logw, double* state, double* paths,
+                        int32_t* slots_or_null, double* ess_or_null, int32_t* resampled_or_null);
+
 /* device-pointer variants (x, g on the context's device; f written to HOST after a sync) ------ */
 int vgpa_sweep_dev(vgpa_ctx* ctx, const double* x_dev, double* f_host, double* g_dev);
 int vgpa_free_energy_dev(vgpa_ctx* ctx, const double* x_dev, double* f_host);

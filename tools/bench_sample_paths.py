@@ -1,11 +1,12 @@
 """
 Time of Context.sample_paths (vgpa_sample_paths), Context.sample_paths_weighted (vgpa_sample_paths_weighted), Context.particle_filter
-(vgpa_particle_filter), Context.particle_statistics (vgpa_particle_statistics) and Context.particle_moments (vgpa_particle_moments) on their
-jobs, one JSON line.
+(vgpa_particle_filter), Context.particle_statistics (vgpa_particle_statistics), Context.particle_moments (vgpa_particle_moments) and
+Context.particle_paths (vgpa_particle_paths) on their jobs, one JSON line.
 
     python tools/bench_sample_paths.py [--rounds 3] [--calls 5] [--jobs a,b,c,aw,aw0,bw,bw0,af64_0,af64_5,af1024_0,af1024_5,bf64_0,...]
     python tools/bench_sample_paths.py --statistics [--filter-problems 4096]      # the as* and bs* jobs
     python tools/bench_sample_paths.py --moments [--filter-problems 4096]         # the am* and bm* jobs
+    python tools/bench_sample_paths.py --paths [--filter-problems 4096] [--paths-strides 1,10]      # the ap* and bp* jobs, once per stride
 
   a   posterior kind, Lorenz-96, D = 40, Np = 1001, B = 512:   64 paths per problem, stride 100
   b   posterior kind, Lorenz-63, Np = 1001, B = 65536:          1 path per problem,  stride 100
@@ -24,6 +25,11 @@ jobs, one JSON line.
              ess_fraction 0.5, every s-th grid index kept (s = 1, 10 or 1004: beyond the grid, index 0 alone is reduced -- the replay
              without its reductions), and particle_filter with the same arguments, the two calls alternating inside every round: both
              times, their ratio, the partial-sum buffer on the device and the result copied
+
+  ap<n>_<K>, bp<n>_<K>   (--paths selects all eight, each once per stride of --paths-strides) particle_paths on the contexts of a and b:
+             n = 64 or 1024 particles per problem, ess_fraction 0.5, K = 16 or 64 trajectories per problem drawn from the final weights,
+             and particle_filter with the same arguments, the two calls alternating inside every round: both times, their ratio, the
+             trajectories copied and how many different paths the K trajectories have in the first and in the last stretch
 
 The posterior jobs read the x a free_energy_dev left cached (x=None: nothing is uploaded); every job draws its start from (m0, S0).  A call
 is timed with a pair of device events on the context's stream around it -- the host work of the call (the Cholesky factors), the kernel and
@@ -55,6 +61,7 @@ WEIGHTED = {"aw": ("a", True), "aw0": ("a", False), "bw": ("b", True), "bw0": ("
 FILTER = {f"{t}f{n}_{f}": (t, n, 0.1 * f) for t in "ab" for n in (64, 1024) for f in (0, 5)}      # job -> (context of, particles, ess_fraction)
 STATS = {f"{t}s{n}_{f}": (t, n, 0.1 * f) for t in "ab" for n in (64, 1024) for f in (0, 5)}       # job -> as FILTER
 MOMENTS = {f"{t}m{n}_{s}": (t, n, s) for t in "ab" for n in (64, 1024) for s in (1, 10, N_PTS + 3)}          # job -> (context of, particles, stride)
+PATHS = {f"{t}p{n}_{k}": (t, n, k) for t in "ab" for n in (64, 1024) for k in (16, 64)}           # job -> (context of, particles, trajectories)
 
 
 def tree():
@@ -82,14 +89,14 @@ def numpy_ms(p0, x_row, d, kind, n_paths, stride, n_problems, B):
     return (time.perf_counter() - t0) * 1e3 / n_problems * B
 
 
-def run(job, rounds, calls, numpy_problems, cache, filter_problems=0):
+def run(job, rounds, calls, numpy_problems, cache, filter_problems=0, paths_stride=1):
     from bench_problem_batch import StreamTimer, make_contexts
     twin, stored = WEIGHTED.get(job, (job, True))
     weighted = job in WEIGHTED
-    if job in FILTER or job in STATS or job in MOMENTS:
-        twin = (FILTER.get(job) or STATS.get(job) or MOMENTS[job])[0]
+    if job in FILTER or job in STATS or job in MOMENTS or job in PATHS:
+        twin = (FILTER.get(job) or STATS.get(job) or MOMENTS.get(job) or PATHS[job])[0]
     name, d, B, kind, n_paths, stride = JOBS[twin]
-    if (job in FILTER or job in STATS or job in MOMENTS) and twin == "b" and filter_problems:
+    if (job in FILTER or job in STATS or job in MOMENTS or job in PATHS) and twin == "b" and filter_problems:
         B = min(B, filter_problems)
     if (name, B) not in cache:                        # (b and c share a context)
         from helpers import SEED, build_problem
@@ -158,6 +165,37 @@ def run(job, rounds, calls, numpy_problems, cache, filter_problems=0):
                 "lineage_ess_last_stretch_median": round(float(np.median(lineage[:, -1])), 2),
                 "partial_buffer_mb": round(8.0 * B * blocks * n_keep * 2 * d / 1e6, 1),
                 "d2h_mb": round(8.0 * B * (n_paths * (1 + d) + n_keep * 2 * d) / 1e6, 1)}
+    if job in PATHS:
+        _, n_paths, n_draw = PATHS[job]
+        stride = paths_stride
+        calls_of = {"filter": lambda: c.particle_filter(n_paths, 1, ess_fraction=0.5),
+                    "paths": lambda: c.particle_paths(n_paths, 1, n_draw, stride=stride, ess_fraction=0.5)}
+        res0 = {k: f() for k, f in calls_of.items()}      # warm-up (first-use allocations)
+        n_keep = (N_PTS - 1) // stride + 1
+        assert all(np.array_equal(res0["filter"][k], res0["paths"][k]) for k in ("log_w", "state", "ess", "resampled"))
+        assert res0["paths"]["paths"].shape == (B, n_draw, n_keep, d) and np.all(np.isfinite(res0["paths"]["paths"]))
+        table = res0["paths"]["slots"]
+        if stride == 1:                                   # (the last point of every trajectory is its final slot's particle)
+            assert np.array_equal(res0["paths"]["paths"][:, :, -1], np.take_along_axis(res0["paths"]["state"], table[:, -1, :, None].astype(np.int64), axis=1))
+        distinct = [float(np.median([np.unique(row).size for row in table[:, j]])) for j in (0, table.shape[1] - 1)]
+        del res0["paths"]["paths"]
+        per_round = {k: [] for k in calls_of}
+        for _ in range(rounds):
+            ms = {k: [] for k in calls_of}
+            for _ in range(calls):
+                for k, f in calls_of.items():
+                    ms[k].append(tm.ms(f))
+            for k in calls_of:
+                per_round[k].append(float(np.median(ms[k])))
+        med = {k: float(np.median(v)) for k, v in per_round.items()}
+        return {"job": job, "model": name, "D": d, "Np": N_PTS, "B": B, "kind": "paths", "n_paths": n_paths, "n_draw": n_draw, "ess_fraction": 0.5,
+                "stride": stride, "paths_ms_per_call": round(med["paths"], 4), "filter_ms_per_call": round(med["filter"], 4),
+                "ratio": round(med["paths"] / med["filter"], 4),
+                "paths_rounds_ms": [round(v, 4) for v in per_round["paths"]],
+                "filter_rounds_ms": [round(v, 4) for v in per_round["filter"]],
+                "observations": int(c.n_obs), "resampled_share": round(float(res0["filter"]["resampled"].mean()), 3),
+                "distinct_first_stretch_median": distinct[0], "distinct_last_stretch_median": distinct[1],
+                "d2h_mb": round(8.0 * B * (n_paths * (1 + d) + n_draw * n_keep * d) / 1e6, 1)}
     if job in FILTER:
         _, n_paths, frac = FILTER[job]
         call = lambda: c.particle_filter(n_paths, 1, ess_fraction=frac)      # noqa: E731
@@ -204,15 +242,21 @@ def main():
     ap.add_argument("--filter-problems", type=int, default=0, help="cap on B of the b context's filter jobs (0: none)")
     ap.add_argument("--statistics", action="store_true", help="run the as* and bs* jobs (particle_statistics beside particle_filter)")
     ap.add_argument("--moments", action="store_true", help="run the am* and bm* jobs (particle_moments beside particle_filter)")
+    ap.add_argument("--paths", action="store_true", help="run the ap* and bp* jobs (particle_paths beside particle_filter)")
+    ap.add_argument("--paths-strides", default="1,10", help="strides of the ap* and bp* jobs: each job runs once per stride")
     args = ap.parse_args()
     if args.statistics:
         args.jobs = ",".join(sorted(STATS))
     if args.moments:
         args.jobs = ",".join(sorted(MOMENTS))
+    if args.paths:
+        args.jobs = ",".join(sorted(PATHS))
+    strides = [int(v) for v in args.paths_strides.split(",") if v]
     cache = {}
     out = {"tool": "bench_sample_paths", "tree": tree(), "unit": "ms per call (device events around the call)", "jobs": []}
     for job in [j for j in args.jobs.split(",") if j]:
-        out["jobs"].append(run(job, args.rounds, args.calls, args.numpy_problems, cache, args.filter_problems))
+        for stride in (strides if job in PATHS else [1]):
+            out["jobs"].append(run(job, args.rounds, args.calls, args.numpy_problems, cache, args.filter_problems, stride))
     for c, _, _, _, tm in cache.values():
         tm.close()
         c.close()

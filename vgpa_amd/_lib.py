@@ -36,7 +36,7 @@ BWD_IDS = {"none": 0, "psi": 1, "q": 2}
 SYMBOLS = ["vgpa_create", "vgpa_destroy", "vgpa_last_error", "vgpa_abi_version", "vgpa_device_count",
            "vgpa_synchronize", "vgpa_stream", "vgpa_solve_fwd", "vgpa_solve_bwd", "vgpa_energy",
            "vgpa_obs_energy", "vgpa_free_energy", "vgpa_gradient", "vgpa_sweep", "vgpa_energy_parts",
-           "vgpa_fetch", "vgpa_theta_gradient", "vgpa_sample_paths", "vgpa_sample_paths_weighted", "vgpa_particle_filter", "vgpa_particle_statistics", "vgpa_particle_moments", "vgpa_sweep_dev", "vgpa_free_energy_dev", "vgpa_sweep_enqueue", "vgpa_fetch_f",
+           "vgpa_fetch", "vgpa_theta_gradient", "vgpa_sample_paths", "vgpa_sample_paths_weighted", "vgpa_particle_filter", "vgpa_particle_statistics", "vgpa_particle_moments", "vgpa_particle_paths", "vgpa_sweep_dev", "vgpa_free_energy_dev", "vgpa_sweep_enqueue", "vgpa_fetch_f",
            "vgpa_dev_alloc", "vgpa_dev_free", "vgpa_memcpy_h2d", "vgpa_memcpy_d2h",
            "vgpa_profile_begin", "vgpa_profile_end", "vgpa_ld_gemm", "vgpa_ld_stage", "vgpa_gradient_dev", "vgpa_energy_full", "vgpa_set_option", "vgpa_is_streaming", "vgpa_path_info", "vgpa_set_prior_energy",
            "vgpa_set_problem_data", "vgpa_set_problem_params", "vgpa_set_problem_obs_model",
@@ -141,6 +141,8 @@ def load():
                                              c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vgpa_particle_moments.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_uint64, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.vgpa_particle_paths.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_uint64, c_double, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vgpa_sweep_dev.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vgpa_free_energy_dev.argtypes = [c_void_p, c_void_p, c_void_p]
     lib.vgpa_sweep_enqueue.argtypes = [c_void_p, c_void_p, c_void_p]
@@ -658,6 +660,39 @@ class Context:
                                                     _ptr(mu), _ptr(tau), _ptr(log_w), _ptr(state), _ptr(moments), _ptr(lineage_ess), _ptr(ess),
                                                     _ptr(flags)))
         return {"log_w": log_w, "state": state, "ess": ess, "resampled": flags, "moments": moments, "lineage_ess": lineage_ess}
+
+    def particle_paths(self, n_paths, seed, n_draw, stride=1, ess_fraction=0.5, x=None, x0=None, prior=None, slots=None):
+        """n_draw whole smoothing trajectories per problem from particle_filter's genealogy (vgpa_particle_paths): the filter, the final
+        slots (slots (B, n_draw) or (n_draw,), each in [0, n_paths); None: drawn from the final weights by systematic resampling, equally
+        weighted), their slot in every stretch traced back through the ancestors, and one walk of the trajectories alone.  Returns a dict:
+        log_w, state, ess, resampled as particle_filter (bit for bit), paths (B, n_draw, n_keep, D) at the grid indices 0, stride, ..., and
+        slots (B, M + 1, n_draw) int32: the slot of every trajectory in every stretch (-1 beyond a problem's own count + 1)."""
+        n_paths, n_draw, stride, m = int(n_paths), int(n_draw), int(stride), self.n_obs
+        if not all(-2 ** 31 <= v < 2 ** 31 for v in (n_paths, n_draw, stride)):      # (the C ABI takes int32: nothing may wrap on its way there)
+            raise ValueError(f"n_paths, n_draw and stride must fit into 32 bits (n_paths = {n_paths}, n_draw = {n_draw}, stride = {stride})")
+        xx = None if x is None else _c64(x)
+        if xx is not None and xx.size != self.B * self.len_x:
+            raise ValueError(f"x has {xx.size} entries, expected {self.B * self.len_x}")
+        s0 = None if x0 is None else _c64(np.broadcast_to(np.asarray(x0, dtype=np.float64).reshape(-1, self.D), (self.B, self.D)))
+        mu = tau = None
+        if prior is not None:
+            mu = _c64(np.broadcast_to(np.asarray(prior[0], dtype=np.float64).reshape(-1, self.D), (self.B, self.D)))
+            tau = _c64(np.broadcast_to(np.asarray(prior[1], dtype=np.float64).reshape(-1, self.D, self.D), (self.B, self.D, self.D)))
+        n, k = max(n_paths, 0), max(n_draw, 0)
+        given = None
+        if slots is not None:
+            wide = np.asarray(slots)
+            if wide.dtype.kind not in "iu" or wide.size == 0 or wide.min() < -2 ** 31 or wide.max() >= 2 ** 31:
+                raise ValueError("slots must be integers that fit into 32 bits")
+            given = np.ascontiguousarray(np.broadcast_to(wide.reshape(-1, k), (self.B, k)), dtype=np.int32)
+        log_w, state = np.empty((self.B, n)), np.empty((self.B, n, self.D))
+        ess, flags = np.zeros((self.B, m)), np.zeros((self.B, m), dtype=np.int32)
+        paths = np.empty((self.B, k, (self.Np - 1) // max(stride, 1) + 1, self.D))
+        table = np.full((self.B, m + 1, k), -1, dtype=np.int32)
+        self._check(self._lib.vgpa_particle_paths(self._h, _ptr(xx), _ptr(s0), n_paths, n_draw, _ptr(given), stride, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                  float(ess_fraction), _ptr(mu), _ptr(tau), _ptr(log_w), _ptr(state), _ptr(paths), _ptr(table),
+                                                  _ptr(ess), _ptr(flags)))
+        return {"log_w": log_w, "state": state, "ess": ess, "resampled": flags, "paths": paths, "slots": table}
 
     def fetch(self, key):
         which = FETCH_IDS[key]

@@ -18,6 +18,10 @@
 // segments of the replay: the same states from the same counters, no weight sums, and at every kept grid index the workgroup's sums of
 // W x and W x^2 with the descendant weights W that k_pf_descend pushed back through the stored ancestors; k_pf_gather is the step between
 // two segments of the replay, k_pf_moments_sum adds the workgroups' sums in block order.
+// k_sample_small<D, false, false, false, false, true> and k_sample_mfma<NT, false, false, false, false, true> (vgpa_particle_paths, DESIGN.md
+// s.4.13) walk K smoothing trajectories of the filter's genealogy in one launch: the unweighted posterior walk, stored as vgpa_sample_paths
+// stores it, each lane drawing with the counter word of the slot its lineage sat in -- one word per stretch between two observations of
+// its problem, from the table k_pf_trace wrote behind k_pf_pick (or behind the caller's final slots).
 #include "vgpa_internal.h"
 
 namespace vgpa {
@@ -134,11 +138,15 @@ __device__ __forceinline__ double wave_max(double v) {
 // sums, pf_lw untouched); at a kept k the lanes' W x_i and (W x_i) x_i are added over the wave by a butterfly and over the four waves
 // through four LDS words per value (two sets, alternating: one barrier per kept k), in that fixed order.  A lane behind the last slot
 // walks from 0 with the last slot's counters and weight 0 and stores nothing.
-template <int D, bool W, bool SEG = false, bool ST = false, bool MO = false>
+// LN: the lineage walk: the unweighted posterior walk of lane m = `path`, whose counter word is not m but the entry of its column of
+// pf_slots for the stretch it is in: row 0 for the start, the next row each time the walk has completed an observation index of the lane's
+// own problem (an observation at index 0: before step 1).  No model drift, no sums.
+template <int D, bool W, bool SEG = false, bool ST = false, bool MO = false, bool LN = false>
 __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
   static_assert(W || !SEG, "a segment is a weighted walk");
   static_assert(SEG || !ST, "the statistics are carried by the segments");
   static_assert(!MO || (SEG && !ST), "the replay is a segment without statistics");
+  static_assert(!LN || !W, "the lineage walk is unweighted");
   constexpr bool WS = W && !MO;      // the weight sums are formed
   size_t gid;
   uint32_t p, path;
@@ -153,6 +161,9 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
     if (gid >= (size_t)a.batch * a.n_paths) return;
     p = (uint32_t)(gid / a.n_paths); path = (uint32_t)(gid % a.n_paths);
   }
+  uint32_t word = path;      // the counter word of the lane's draws
+  const int32_t* lin = nullptr;
+  if constexpr (LN) { lin = a.pf_slots + (size_t)p * a.pf_slot_rows * a.n_paths + path; word = (uint32_t)lin[0]; }
   const uint32_t k0 = (uint32_t)(a.seed & 0xffffffffu), k1 = (uint32_t)(a.seed >> 32);
   constexpr int NP = (D + 1) / 2;
   // kept points wait in LDS (slot-major, thread fastest: no conflicts) until NBUF of them -- 16 doubles for D = 1, 2, 4, 15 for D = 3 -- go out as
@@ -181,7 +192,7 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
     const double* m0 = a.m0 + (size_t)p * a.m0_stride;
     const double* L0 = a.L0 + (size_t)p * a.L0_stride;
 #pragma unroll
-    for (int j = 0; j < NP; j++) normal_pair(k0, k1, 0u, path, p, (uint32_t)j, &z[2 * j], &z[2 * j + 1]);
+    for (int j = 0; j < NP; j++) normal_pair(k0, k1, 0u, word, p, (uint32_t)j, &z[2 * j], &z[2 * j + 1]);
 #pragma unroll
     for (int i = 0; i < D; i++) {
       double s = 0.0;
@@ -208,6 +219,10 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
     }
     if constexpr (SEG) { if (!a.seg_first) oc.skip_through(a.k_begin); }
     if (oc.next == 0) { ow += obs_form<D>(a, p, oc.cur, x); oc.advance(); }
+  }
+  if constexpr (LN) {
+    oc = ObsCursor(a, p);
+    if (oc.next == 0) { oc.advance(); word = (uint32_t)lin[(size_t)oc.cur * a.n_paths]; }
   }
   // MO: the segment lies in one stretch of its problem -- the observations behind it are oc.cur, the row of the weights
   double wt = 0.0;
@@ -255,7 +270,7 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
   for (int k = k_first; k < k_stop; k++) {
     double f[D], fm[D];
     if constexpr (WS) model_drift<D>(a.model, th, x, fm);
-    if (W || a.kind == VGPA_PATHS_POSTERIOR) {
+    if (W || LN || a.kind == VGPA_PATHS_POSTERIOR) {
       const double* Ak = A + (size_t)(k - 1) * D * D;
       const double* bk = bv + (size_t)(k - 1) * D;
 #pragma unroll
@@ -269,7 +284,7 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
       model_drift<D>(a.model, th, x, f);
     }
 #pragma unroll
-    for (int j = 0; j < NP; j++) normal_pair(k0, k1, (uint32_t)k, path, p, (uint32_t)j, &z[2 * j], &z[2 * j + 1]);
+    for (int j = 0; j < NP; j++) normal_pair(k0, k1, (uint32_t)k, word, p, (uint32_t)j, &z[2 * j], &z[2 * j + 1]);
     if constexpr (ST) model_phi<D>(a.model, x, phi);
 #pragma unroll
     for (int i = 0; i < D; i++) {
@@ -288,6 +303,9 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
     }
     if constexpr (MO) {
       if (k == keep_k) { reduce(keep_slot++); keep_k += a.stride; }
+    }
+    if constexpr (LN) {
+      if (k == oc.next) { oc.advance(); word = (uint32_t)lin[(size_t)oc.cur * a.n_paths]; }
     }
     if (store && --until == 0) {
       until = a.stride;
@@ -363,23 +381,32 @@ __device__ __forceinline__ void normals_c(uint32_t k0, uint32_t k1, uint32_t k, 
 // path), four cross-lane steps add the 16 paths of the wave, the lanes of path column 0 put their rows into red [4 waves][2][NT] -- the
 // Zs region, which a segment does not use --, and behind the next barrier the walk has anyway (the first of the next step, or one behind
 // the loop) thread t < 2 D adds the four waves in order and stores moment t / D of component t mod D.
-template <int NT, bool W, bool SEG = false, bool ST = false, bool MO = false>
+// LN: the lineage walk, as in k_sample_small (diagonal R): every lane of a workgroup belongs to one problem, so all of them change their
+// counter words behind the same steps.  A lane behind the last lineage walks the last one again and stores nothing.
+template <int NT, bool W, bool SEG = false, bool ST = false, bool MO = false, bool LN = false>
 __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
   static_assert(W || !SEG, "a segment is a weighted walk");
   static_assert(SEG || !ST, "the statistics are carried by the segments");
   static_assert(!MO || (SEG && !ST), "the replay is a segment without statistics");
+  static_assert(!LN || !W, "the lineage walk is unweighted");
   constexpr bool WS = W && !MO;      // the weight sums are formed
   using Sh = MfmaShape<NT>;
   constexpr int LDA = Sh::LDA, MT = Sh::MT, KT = Sh::KT, NPF = Sh::NPF;
   extern __shared__ double lds[];
   const int D = a.D, DD = D * D, tid = threadIdx.x, w = tid >> 6, lane = tid & 63, j16 = lane & 15, q = lane >> 4;
-  const bool dense = !W && !a.R_diag;      // (the weighted instantiation is launched with diagonal factors only)
+  const bool dense = !W && !LN && !a.R_diag;      // (the weighted instantiation and the lineage walk are launched with diagonal factors only)
   double* As = lds;
   double* bs = As + NT * LDA;
   double* Rs = bs + NT;
   double* Xs = Rs + (dense ? NT * LDA : 0) + w * NT * 16;
   double* Zs = Xs + 4 * NT * 16;
   const uint32_t p = blockIdx.x, path = blockIdx.y * 64 + w * 16 + j16;
+  uint32_t word = path;      // the counter word of the lane's draws
+  const int32_t* lin = nullptr;
+  if constexpr (LN) {
+    lin = a.pf_slots + (size_t)p * a.pf_slot_rows * a.n_paths + (path < (uint32_t)a.n_paths ? path : (uint32_t)a.n_paths - 1);
+    word = (uint32_t)lin[0];
+  }
   const uint32_t k0 = (uint32_t)(a.seed & 0xffffffffu), k1 = (uint32_t)(a.seed >> 32);
   const double* A = a.A + (size_t)p * a.stride_x;
   const double* bv = a.b + (size_t)p * a.stride_x;
@@ -422,7 +449,7 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
   } else {
     const double* m0 = a.m0 + (size_t)p * a.m0_stride;
     const double* L0 = a.L0 + (size_t)p * a.L0_stride;
-    normals_c<NT>(k0, k1, 0u, path, p, D, q, z);
+    normals_c<NT>(k0, k1, 0u, word, p, D, q, z);
 #pragma unroll
     for (int mt = 0; mt < MT; mt++)
 #pragma unroll
@@ -473,7 +500,7 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
       }
   }
   ObsCursor oc;
-  if constexpr (W) oc = ObsCursor(a, p);
+  if constexpr (W || LN) oc = ObsCursor(a, p);
   if constexpr (SEG) { if (!a.seg_first) oc.skip_through(a.k_begin); }
   auto observe = [&]() {      // x_k is in x and, whole, in the path's column of Xs
     const double* y = a.obs_y + (size_t)p * a.obs_y_stride + (size_t)oc.cur * D;
@@ -510,6 +537,9 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
   if constexpr (WS) {
     if constexpr (!SEG) put(a.start + ((size_t)p * a.n_paths + path0) * D, (size_t)D);
     if (oc.next == 0) observe();
+  }
+  if constexpr (LN) {
+    if (oc.next == 0) { oc.advance(); word = (uint32_t)lin[(size_t)oc.cur * a.n_paths]; }
   }
   // MO: the segment lies in one stretch of its problem -- the observations behind it are oc.cur, the row of the weights
   double wt = 0.0;
@@ -559,7 +589,7 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
     double xb[KT];
 #pragma unroll
     for (int kk = 0; kk < KT; kk++) xb[kk] = Xs[(kk * 4 + q) * 16 + j16];
-    normals_c<NT>(k0, k1, (uint32_t)k, path, p, D, q, z);
+    normals_c<NT>(k0, k1, (uint32_t)k, word, p, D, q, z);
     if (dense) {
 #pragma unroll
       for (int mt = 0; mt < MT; mt++)
@@ -626,6 +656,9 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
     }
     if constexpr (MO) {
       if (k == keep_k) { reduce(keep_slot++); keep_k += a.stride; }
+    }
+    if constexpr (LN) {
+      if (k == oc.next) { oc.advance(); word = (uint32_t)lin[(size_t)oc.cur * a.n_paths]; }
     }
   }
   if constexpr (MO) {
@@ -726,12 +759,13 @@ __global__ __launch_bounds__(64) void k_sample_l96(SampleArgs a) {
   }
 }
 
-template <int NT, bool W>
+template <int NT, bool W, bool LN = false>
 hipError_t launch_mfma(const SampleArgs& a, hipStream_t st) {
   const size_t lds = MfmaShape<NT>::lds_doubles(!a.R_diag) * sizeof(double);
-  if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k_sample_mfma<NT, W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (lds > 64 * 1024)
+    (void)hipFuncSetAttribute((const void*)k_sample_mfma<NT, W, false, false, false, LN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if ((a.n_paths + 63) / 64 > 65535) return hipErrorInvalidValue;      // (grid.y)
-  hipLaunchKernelGGL((k_sample_mfma<NT, W>), dim3(a.batch, (a.n_paths + 63) / 64), dim3(256), lds, st, a);
+  hipLaunchKernelGGL((k_sample_mfma<NT, W, false, false, false, LN>), dim3(a.batch, (a.n_paths + 63) / 64), dim3(256), lds, st, a);
   return hipGetLastError();
 }
 
@@ -795,6 +829,40 @@ __global__ __launch_bounds__(256) void k_pf_start(PfArgs a) {
   a.lw[gid] = init - a.obs_const_scale * (a.obs_const_v ? a.obs_const_v[p] : a.obs_const);
 }
 
+// What k_pf_resample and k_pf_pick share, a workgroup of 256 threads on the n log-weights of one problem.
+// pf_max: max lw (red: 4 doubles of LDS).
+// pf_prefix_sums: cum_i = the inclusive prefix sums of w_i = exp(lw_i - mx) in slot order, 256 slots per pass: a shuffle scan per wave, the
+// waves' totals and the carry through LDS (tot: 4 doubles); returns the thread's share of sum w^2.  No barrier behind the last store of cum.
+// (The bisection that follows is written out in either kernel: as a shared function it costs k_pf_resample two SGPRs.)
+__device__ __forceinline__ double pf_max(const double* lw, int n, double* red) {
+  double mx = -INFINITY;
+  for (int i = threadIdx.x; i < n; i += 256) mx = fmax(mx, lw[i]);
+  mx = wave_max(mx);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+  __syncthreads();
+  return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+}
+__device__ __forceinline__ double pf_prefix_sums(const double* lw, int n, double mx, double* cum, double* tot) {
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  double carry = 0.0, s2 = 0.0;
+  for (int base = 0; base < n; base += 256) {
+    const int i = base + tid;
+    const double wi = i < n ? exp(lw[i] - mx) : 0.0;
+    s2 += wi * wi;
+    double sc = wi;      // inclusive scan over the wave
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const double up = __shfl_up(sc, o); if (lane >= o) sc += up; }
+    __syncthreads();      // (tot of the pass before has been read)
+    if (lane == 63) tot[w] = sc;
+    __syncthreads();
+    double before = carry;
+    for (int v = 0; v < w; v++) before += tot[v];
+    if (i < n) cum[i] = before + sc;
+    carry = (((carry + tot[0]) + tot[1]) + tot[2]) + tot[3];      // (the association of the last slot's own sum)
+  }
+  return s2;
+}
+
 // The step between two segments, one workgroup per problem, at grid index a.k.  A problem without an observation at a.k
 // copies its particles through.  Otherwise: w_i = exp(lw_i - max lw), S = sum w, ESS = S^2 / sum w^2, cum = the inclusive prefix sums of w in
 // slot order (256 slots per pass: a shuffle scan per wave, the waves' totals and the carry through LDS); resampled iff ESS < ess_fraction n and
@@ -823,28 +891,8 @@ __global__ __launch_bounds__(256) void k_pf_resample(PfArgs a) {
   double* lw = a.lw + (size_t)p * n;
   double* cum = a.cum + (size_t)p * n;
   int32_t* anc = a.anc + (size_t)p * n;
-  double mx = -INFINITY;
-  for (int i = tid; i < n; i += 256) mx = fmax(mx, lw[i]);
-  mx = wave_max(mx);
-  if (lane == 0) red[w] = mx;
-  __syncthreads();
-  mx = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-  double carry = 0.0, s2 = 0.0;
-  for (int base = 0; base < n; base += 256) {
-    const int i = base + tid;
-    const double wi = i < n ? exp(lw[i] - mx) : 0.0;
-    s2 += wi * wi;
-    double sc = wi;      // inclusive scan over the wave
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const double up = __shfl_up(sc, o); if (lane >= o) sc += up; }
-    __syncthreads();      // (tot of the pass before has been read)
-    if (lane == 63) tot[w] = sc;
-    __syncthreads();
-    double before = carry;
-    for (int v = 0; v < w; v++) before += tot[v];
-    if (i < n) cum[i] = before + sc;
-    carry = (((carry + tot[0]) + tot[1]) + tot[2]) + tot[3];      // (the association of the last slot's own sum)
-  }
+  const double mx = pf_max(lw, n, red);
+  double s2 = pf_prefix_sums(lw, n, mx, cum, tot);
   // S is what the last slot's prefix sum is, to the last bit: every threshold lies below cum_{n-1} as the exact ones do
   __syncthreads();      // (cum is written; red has been read)
   const double S = cum[n - 1];
@@ -1025,6 +1073,52 @@ __global__ __launch_bounds__(256) void k_pf_moments_sum(int n_blocks, size_t len
   out[g] = s;
 }
 
+// ---- the smoothing trajectories: the final slots, their genealogy (the lineage walk is an instantiation of the samplers above) ----------
+// The final slots of K equally weighted trajectories, one workgroup per problem with c observations of its own:
+// systematic resampling from the final weights as k_pf_resample does it -- w_i = exp(lw_i - max lw), cum and S = cum_{n-1} by the same
+// code -- with K thresholds u_m = (U + m) / K S, U from Philox counter (Np, 0, p, 0xffffffff): the filter's own draws have grid indices
+// below Np.  table [B][rows][K]: row c gets min(#{i: cum_i <= u_m}, n - 1).
+__global__ __launch_bounds__(256) void k_pf_pick(PfArgs a, int Np, int K, int rows, int32_t* table) {
+  __shared__ double tot[4], red[4];
+  const int p = blockIdx.x, n = a.n_paths;
+  const int cnt = a.n_obs_v ? a.n_obs_v[p] : a.n_obs;
+  const double* lw = a.lw + (size_t)p * n;
+  double* cum = a.cum + (size_t)p * n;
+  const double mx = pf_max(lw, n, red);
+  (void)pf_prefix_sums(lw, n, mx, cum, tot);
+  __syncthreads();      // (cum is written)
+  const double S = cum[n - 1];
+  uint32_t r[4];
+  philox4x32_10((uint32_t)Np, 0u, (uint32_t)p, 0xffffffffu, (uint32_t)(a.seed & 0xffffffffu), (uint32_t)(a.seed >> 32), r);
+  const double U = unit_open(r[0], r[1]);
+  int32_t* row = table + ((size_t)p * rows + cnt) * K;
+  for (int m = threadIdx.x; m < K; m += 256) {
+    const double um = (U + (double)m) / (double)K * S;
+    int lo = 0, hi = n;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (cum[mid] <= um) lo = mid + 1; else hi = mid;
+    }
+    row[m] = lo < n - 1 ? lo : n - 1;
+  }
+}
+
+// The genealogy of the final slots, one thread per (problem, trajectory): from row c of table [B][rows][K] backwards, s_j = anc_j[s_{j+1}]
+// where the cloud was resampled at the problem's observation j (h_anc, h_flag: the filter's histories), else s_{j+1}.
+__global__ __launch_bounds__(256) void k_pf_trace(PfArgs a, int K, int rows, int32_t* table) {
+  const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= (size_t)a.batch * K) return;
+  const int p = (int)(g / K), m = (int)(g - (size_t)p * K), n = a.n_paths;
+  const int cnt = a.n_obs_v ? a.n_obs_v[p] : a.n_obs;
+  int32_t* col = table + (size_t)p * rows * K + m;
+  int s = col[(size_t)cnt * K];
+  for (int j = cnt - 1; j >= 0; j--) {
+    const size_t hj = (size_t)p * a.M + j;
+    if (a.h_flag[hj]) s = a.h_anc[hj * n + s];
+    col[(size_t)j * K] = s;
+  }
+}
+
 template <bool W>
 hipError_t launch_posterior(const SampleArgs& a, hipStream_t st) {
   const size_t lanes = (size_t)a.batch * a.n_paths;
@@ -1135,6 +1229,44 @@ hipError_t launch_pf_moments_sum(int batch, int n_blocks, size_t len, const doub
   if (batch < 1 || n_blocks < 1 || len < 1 || (total + 255) / 256 > 0x7fffffffu || !part || !out) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_pf_moments_sum, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, n_blocks, len, total, part, out);
   return hipGetLastError();
+}
+
+hipError_t launch_pf_pick(const PfArgs& a, int Np, int K, int rows, int32_t* table, hipStream_t st) {
+  if (a.batch < 1 || a.n_paths < 1 || Np < 1 || K < 1 || rows < 1 || !a.lw || !a.cum || !table) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_pf_pick, dim3(a.batch), dim3(256), 0, st, a, Np, K, rows, table);
+  return hipGetLastError();
+}
+
+hipError_t launch_pf_trace(const PfArgs& a, int K, int rows, int32_t* table, hipStream_t st) {
+  const size_t lanes = (size_t)a.batch * (K > 0 ? K : 0);
+  if (a.batch < 1 || a.n_paths < 1 || a.M < 1 || K < 1 || rows < 1 || (lanes + 255) / 256 > 0x7fffffffu || !a.h_flag || !a.h_anc || !table)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_pf_trace, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, a, K, rows, table);
+  return hipGetLastError();
+}
+
+bool sample_lineages_fit(int D, int batch, int K) {
+  if (D <= kMaxLaneD) return ((size_t)batch * K + 255) / 256 <= 0x7fffffffu;      // (grid.x)
+  return (K + 63) / 64 <= 65535;                                                    // (grid.y)
+}
+
+hipError_t launch_sample_lineages(const SampleArgs& a, hipStream_t st) {
+  if (a.D < 1 || a.D > kMaxSmallD || a.n_paths < 1 || a.stride < 1 || a.kind != VGPA_PATHS_POSTERIOR || !a.R_diag || !a.out) return hipErrorInvalidValue;
+  if (!a.pf_slots || a.pf_slot_rows < 1 || a.logw || !sample_lineages_fit(a.D, a.batch, a.n_paths)) return hipErrorInvalidValue;
+  if (a.D <= kMaxLaneD) {
+    const dim3 grid((unsigned)(((size_t)a.batch * a.n_paths + 255) / 256)), block(256);
+    switch (a.D) {
+      case 1: hipLaunchKernelGGL((k_sample_small<1, false, false, false, false, true>), grid, block, 0, st, a); break;
+      case 2: hipLaunchKernelGGL((k_sample_small<2, false, false, false, false, true>), grid, block, 0, st, a); break;
+      case 3: hipLaunchKernelGGL((k_sample_small<3, false, false, false, false, true>), grid, block, 0, st, a); break;
+      default: hipLaunchKernelGGL((k_sample_small<4, false, false, false, false, true>), grid, block, 0, st, a); break;
+    }
+    return hipGetLastError();
+  }
+  if (a.D <= 16) return launch_mfma<16, false, true>(a, st);
+  if (a.D <= 32) return launch_mfma<32, false, true>(a, st);
+  if (a.D <= 48) return launch_mfma<48, false, true>(a, st);
+  return launch_mfma<64, false, true>(a, st);
 }
 
 hipError_t launch_pf_stats_mean(int D, int batch, int n_paths, const double* lw, const double* stats, double* mean, hipStream_t st) {

@@ -166,9 +166,10 @@ struct vgpa_ctx {
   size_t sp_logw_n = 0, sp_start_n = 0;
   // vgpa_particle_filter: the two particle buffers, log-weights, prefix sums, ancestors of a step (int32), the histories (ess, flags and
   // ancestors as int32, clouds), the prior's mean and factor; vgpa_particle_statistics: the two buffers of rows and their mean;
-  // vgpa_particle_moments: the descendant weights, the lineage ESS, the workgroups' partial sums, the moments
+  // vgpa_particle_moments: the descendant weights, the lineage ESS, the workgroups' partial sums, the moments; vgpa_particle_paths: the
+  // slot table (int32; the trajectories themselves go through d_sp_out)
   enum { PF_XA, PF_XB, PF_LW, PF_CUM, PF_ANC, PF_ESS, PF_FLAG, PF_HANC, PF_CLOUDS, PF_MU, PF_LT, PF_STA, PF_STB, PF_MEAN, PF_WTAB, PF_LESS, PF_PART,
-         PF_MOM, PF_COUNT };
+         PF_MOM, PF_SLOTS, PF_COUNT };
   double* d_pf[PF_COUNT] = {};
   size_t pf_n[PF_COUNT] = {};
   // profiling
@@ -1572,15 +1573,23 @@ int vgpa_sample_paths_weighted(vgpa_ctx* c, const double* x, const double* x0, i
 // moments set: vgpa_particle_moments -- behind the filter, whose ancestor history stays on the device, the descendant
 // weights, then the walk once more from the same counters (the stored ancestors in place of the resampling decisions) with the weighted
 // sums taken at every stride-th grid index; `state` is then what the replay arrived at.
+// paths set: vgpa_particle_paths -- behind the filter, whose ancestor history stays on the device, the final slots of
+// n_draw trajectories (final_slots, or drawn from the final weights), their slots in every stretch traced back through the ancestors, and
+// one launch of the lineage walk over the n_draw trajectories alone; slots_out: where the table goes.
 static int particle_run(vgpa_ctx* c, const double* x, const double* x0, int32_t n_paths, uint64_t seed, double ess_fraction,
                         const double* prior_mu, const double* prior_tau, double* logw, double* state, double* ess, int32_t* resampled,
                         int32_t* ancestors, double* clouds, bool with_stats, double* stats, double* mean, int32_t stride = 1,
-                        double* moments = nullptr, double* lineage_ess = nullptr) {
+                        double* moments = nullptr, double* lineage_ess = nullptr, int32_t n_draw = 0, const int32_t* final_slots = nullptr,
+                        double* paths = nullptr, int32_t* slots_out = nullptr) {
   if (!c) return VGPA_ERR_ARG;
   if (!logw || !state) return fail(c, VGPA_ERR_ARG, "null argument");
   if (stride < 1) return fail(c, VGPA_ERR_ARG, "stride must be at least 1 (stride = %d)", stride);
   if (with_stats && !stats && !mean) return fail(c, VGPA_ERR_ARG, "at least one of stats and mean must be given");
   if (n_paths < 1) return fail(c, VGPA_ERR_ARG, "n_paths must be at least 1 (n_paths = %d)", n_paths);
+  if (paths && final_slots)
+    for (size_t e = 0; e < (size_t)c->B * n_draw; e++)
+      if (final_slots[e] < 0 || final_slots[e] >= n_paths)
+        return fail(c, VGPA_ERR_ARG, "problem %zu: final slot %d of trajectory %zu does not lie in [0, %d)", e / n_draw, final_slots[e], e % n_draw, n_paths);
   if (!(ess_fraction >= 0.0 && ess_fraction <= 1.0)) return fail(c, VGPA_ERR_ARG, "ess_fraction must lie in [0, 1] (ess_fraction = %g)", ess_fraction);
   if ((prior_mu == nullptr) != (prior_tau == nullptr)) return fail(c, VGPA_ERR_ARG, "the prior is a mean and a covariance: both or neither");
   if (c->cfg.model == VGPA_MODEL_NONE) return fail(c, VGPA_ERR_ARG, "context has no stochastic model: no model SDE to weigh the particles against");
@@ -1594,6 +1603,14 @@ static int particle_run(vgpa_ctx* c, const double* x, const double* x0, int32_t 
       return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing moments are built for at most 2^39 entries (batch %d, %d kept grid indices, D = %d): use a larger stride",
                   B, (Np - 1) / stride + 1, D);
   }
+  const size_t n_traj = (size_t)B * (size_t)n_draw * ((size_t)((Np - 1) / stride + 1) * D);      // (used behind the check below only)
+  if (paths && D <= kMaxSmallD) {        // the launch limits of the lineage walk and the size of its result, before any work
+    if (!sample_lineages_fit(D, B, n_draw))
+      return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing trajectories are built for at most %d per problem at D = %d (n_draw = %d)", 65535 * 64, D, n_draw);
+    if ((double)B * (double)n_draw * (double)((Np - 1) / stride + 1) * (double)D > 34359738368.0)
+      return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing trajectories are built for at most 2^35 entries (batch %d, %d trajectories, %d kept grid indices, D = %d): use a larger stride",
+                  B, n_draw, (Np - 1) / stride + 1, D);
+  }
   SampleArgs a;
   int rc;
   if ((rc = sample_args(c, VGPA_PATHS_POSTERIOR, x, x0, n_paths, 1, seed, true, &a))) return rc;
@@ -1602,7 +1619,10 @@ static int particle_run(vgpa_ctx* c, const double* x, const double* x0, int32_t 
   auto ints = [](size_t count) { return (count + 1) / 2; };      // int32 entries in a buffer of doubles
   if ((rc = buf(vgpa_ctx::PF_XA, BnD)) || (rc = buf(vgpa_ctx::PF_XB, BnD)) || (rc = buf(vgpa_ctx::PF_LW, Bn)) || (rc = buf(vgpa_ctx::PF_CUM, Bn)) ||
       (rc = buf(vgpa_ctx::PF_ANC, ints(Bn))) || (rc = buf(vgpa_ctx::PF_ESS, BM)) || (rc = buf(vgpa_ctx::PF_FLAG, ints(BM)))) return rc;
-  if ((ancestors || moments) && (rc = buf(vgpa_ctx::PF_HANC, ints(BM * n)))) return rc;
+  if ((ancestors || moments || paths) && (rc = buf(vgpa_ctx::PF_HANC, ints(BM * n)))) return rc;
+  const int slot_rows = M + 1;
+  const size_t n_table = (size_t)B * slot_rows * (size_t)n_draw;
+  if (paths && ((rc = buf(vgpa_ctx::PF_SLOTS, ints(n_table))) || (rc = grow(c, &c->d_sp_out, &c->sp_out_n, n_traj)))) return rc;
   const int rows = M1 + 1, n_blocks = sample_segment_blocks(D, n_paths);
   const size_t mom_len = (size_t)((Np - 1) / stride + 1) * 2 * D;
   if (moments && ((rc = buf(vgpa_ctx::PF_WTAB, (size_t)B * rows * n)) || (rc = buf(vgpa_ctx::PF_LESS, (size_t)B * rows)) ||
@@ -1626,7 +1646,7 @@ static int particle_run(vgpa_ctx* c, const double* x, const double* x0, int32_t 
   f.x = cur; f.ws = other; f.lw = c->d_pf[vgpa_ctx::PF_LW]; f.cum = c->d_pf[vgpa_ctx::PF_CUM];
   f.anc = reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_ANC]);
   f.h_ess = c->d_pf[vgpa_ctx::PF_ESS]; f.h_flag = reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_FLAG]);
-  f.h_anc = (ancestors || moments) ? reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_HANC]) : nullptr;
+  f.h_anc = (ancestors || moments || paths) ? reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_HANC]) : nullptr;
   f.h_clouds = clouds ? c->d_pf[vgpa_ctx::PF_CLOUDS] : nullptr;
   HIP_TRY(c, hipMemsetAsync(f.h_ess, 0, BM * sizeof(double), c->stream));
   HIP_TRY(c, hipMemsetAsync(f.h_flag, 0, BM * sizeof(int32_t), c->stream));
@@ -1687,6 +1707,27 @@ static int particle_run(vgpa_ctx* c, const double* x, const double* x0, int32_t 
       for (int p = 0; p < (rows == M + 1 ? 1 : B); p++)
         if ((rc = download(c, lineage_ess + (size_t)p * (M + 1), less + (size_t)p * rows, rows == M + 1 ? (size_t)B * rows : (size_t)M + 1))) return rc;
   }
+  std::vector<int32_t> h_table;      // (given final slots: the table as it is uploaded, alive until the stream has been synchronised)
+  if (paths) {
+    int32_t* table = reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_SLOTS]);
+    if (final_slots) {               // rows beyond a problem's own count: -1; row c: the caller's slots
+      h_table.assign(n_table, -1);
+      for (int p = 0; p < B; p++)
+        for (int m = 0; m < n_draw; m++) h_table[((size_t)p * slot_rows + count[p]) * n_draw + m] = final_slots[(size_t)p * n_draw + m];
+      if ((rc = upload(c, table, h_table.data(), n_table))) return rc;
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+    } else {
+      HIP_TRY(c, hipMemsetAsync(table, 0xff, n_table * sizeof(int32_t), c->stream));
+      LAUNCH_TRY(c, "final slots launch", launch_pf_pick(f, Np, n_draw, slot_rows, table, c->stream));
+    }
+    LAUNCH_TRY(c, "genealogy launch", launch_pf_trace(f, n_draw, slot_rows, table, c->stream));
+    SampleArgs r = a;                // the unweighted walk of n_draw lanes per problem from the same start, factors and counters
+    r.n_paths = n_draw; r.stride = stride; r.n_keep = (Np - 1) / stride + 1; r.out = c->d_sp_out;
+    r.pf_x = nullptr; r.pf_lw = nullptr; r.pf_stats = nullptr; r.pf_slots = table; r.pf_slot_rows = slot_rows;
+    LAUNCH_TRY(c, "lineage walk launch", launch_sample_lineages(r, c->stream));
+    if ((rc = download(c, paths, c->d_sp_out, n_traj))) return rc;
+    if (slots_out) HIP_TRY(c, hipMemcpyAsync(slots_out, table, n_table * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  }
   if (with_stats && mean) {
     LAUNCH_TRY(c, "path statistics mean launch", launch_pf_stats_mean(D, B, n_paths, f.lw, st_cur, c->d_pf[vgpa_ctx::PF_MEAN], c->stream));
     if ((rc = download(c, mean, c->d_pf[vgpa_ctx::PF_MEAN], (size_t)B * 3 * D))) return rc;
@@ -1725,6 +1766,17 @@ int vgpa_particle_moments(vgpa_ctx* c, const double* x, const double* x0, int32_
   if (!moments) return fail(c, VGPA_ERR_ARG, "null argument");
   return particle_run(c, x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled, nullptr, nullptr, false, nullptr,
                       nullptr, stride, moments, lineage_ess);
+}
+
+// Whole smoothing trajectories on the grid from the particles' genealogy (see vgpa_hip.h)
+int vgpa_particle_paths(vgpa_ctx* c, const double* x, const double* x0, int32_t n_paths, int32_t n_draw, const int32_t* final_slots, int32_t stride,
+                        uint64_t seed, double ess_fraction, const double* prior_mu, const double* prior_tau, double* logw, double* state,
+                        double* paths, int32_t* slots, double* ess, int32_t* resampled) {
+  if (!c) return VGPA_ERR_ARG;
+  if (!paths) return fail(c, VGPA_ERR_ARG, "null argument");
+  if (n_draw < 1) return fail(c, VGPA_ERR_ARG, "n_draw must be at least 1 (n_draw = %d)", n_draw);
+  return particle_run(c, x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled, nullptr, nullptr, false, nullptr,
+                      nullptr, stride, nullptr, nullptr, n_draw, final_slots, paths, slots);
 }
 
 int vgpa_fetch(vgpa_ctx* c, int which, double* out) {

@@ -270,9 +270,15 @@ struct SampleArgs {
   const double* pf_wtab;    // [B][pf_rows][n_paths] descendant weights, or nullptr
   double* pf_part;          // [B][sample_segment_blocks()][n_keep][2][D]
   int pf_rows;
+  // the lineage walk of vgpa_particle_paths (launch_sample_lineages): the unweighted posterior walk of n_paths = K lanes
+  // per problem, stored as vgpa_sample_paths stores it, in which lane m draws with the counter word pf_slots[p][j][m] while it is in
+  // stretch j of its problem's own observation row (obs_t / n_obs as above): row 0 for the start, the next row behind every observation
+  const int32_t* pf_slots;  // [B][pf_slot_rows][n_paths], or nullptr
+  int pf_slot_rows;
 };
 hipError_t launch_sample_paths(const SampleArgs& a, hipStream_t st);
 hipError_t launch_sample_segment(const SampleArgs& a, hipStream_t st);
+hipError_t launch_sample_lineages(const SampleArgs& a, hipStream_t st);
 // workgroups per problem of a segment launch: the blocks of the MO instantiations' partial sums
 int sample_segment_blocks(int D, int n_paths);
 
@@ -313,6 +319,13 @@ hipError_t launch_pf_stats_mean(int D, int batch, int n_paths, const double* lw,
 // between two segments of the replay, x_out_i = x_in_{h_anc[p][j][i]} at the problem's observation j with t_j = k, a copy without one
 hipError_t launch_pf_descend(const PfArgs& a, int rows, double* wtab, double* less, hipStream_t st);
 hipError_t launch_pf_gather(const PfArgs& a, hipStream_t st);
+// vgpa_particle_paths (sample.hip: k_pf_pick, k_pf_trace).  table [B][rows][K] int32, rows > every problem's observation count c.  pick
+// reads lw, seed and the counts and overwrites cum: row c gets the final slots of K trajectories, by systematic resampling from the final
+// weights with the uniform of Philox counter (Np, 0, p, 0xffffffff).  trace reads row c, h_flag, h_anc and M and writes rows c-1 .. 0: the
+// slot each trajectory sat in during every stretch.  sample_lineages_fit: launch_sample_lineages can launch K lanes per problem
+hipError_t launch_pf_pick(const PfArgs& a, int Np, int K, int rows, int32_t* table, hipStream_t st);
+hipError_t launch_pf_trace(const PfArgs& a, int K, int rows, int32_t* table, hipStream_t st);
+bool sample_lineages_fit(int D, int batch, int K);
 // out [B][len] = sum over blk, in block order, of part [B][n_blocks][len]
 hipError_t launch_pf_moments_sum(int batch, int n_blocks, size_t len, const double* part, double* out, hipStream_t st);
 

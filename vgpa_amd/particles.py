@@ -24,10 +24,16 @@ the stretch between observations j-1 and j is the total final weight of the slot
     E[x_k | y] ~ sum_i W^{j(k)}_i x_i(k)
 with x_i(k) the state of slot i as the walk arrives at k.  These are the marginals of the forward genealogical smoother: exact in the limit
 of many particles for the Euler-discretised model, but early stretches rest on few distinct lineages -- lineage_ess says how few.
+
+SmoothingPaths: one problem's record of vgpa_particle_paths -- K whole trajectories on the time grid from the same
+genealogy, for what is no mean or variance: exceedance and first-passage probabilities, plots of posterior draws, predictive checks.  A
+trajectory is the lineage of one final slot; the final slots are drawn from the final weights by systematic resampling (equally weighted
+draws) or given by the caller (weighted by their final weights).  The same caveat holds: on collapsing clouds the early stretches of all K
+trajectories are one and the same path -- distinct() counts how many different ones each stretch has.
 """
 import numpy as np
 
-__all__ = ["ParticleFilterResult", "PathStatistics", "SmoothingMoments", "descendant_weights"]
+__all__ = ["ParticleFilterResult", "PathStatistics", "SmoothingMoments", "SmoothingPaths", "descendant_weights"]
 
 
 def descendant_weights(log_w, ancestors, resampled):
@@ -238,6 +244,89 @@ class SmoothingMoments(object):
     def lineage_ess_on_grid(self):
         """lineage_ess of the stretch each kept grid index lies in: index k belongs to stretch #{observations before k}"""
         return self.lineage_ess[np.searchsorted(self.obs_t, self.grid, side="left")]
+
+    def log_evidence(self):
+        """logsumexp(log_w) - log n, as ParticleFilterResult.log_evidence()"""
+        top = np.max(self.log_w)
+        return float(top + np.log(np.sum(np.exp(self.log_w - top))) - np.log(self.log_w.size))
+
+
+class SmoothingPaths(object):
+    """log_w (n,): the filter's final unnormalised log-weights; paths (K, n_keep, D): the trajectories at the grid indices k = 0, stride,
+    2 stride, ... < n_pts; slots (M_p + 1, K): the slot trajectory m sat in during stretch j (row M_p: its final slot); obs_t: the problem's
+    own observation indices; ess, resampled over them.  drawn: the final slots were drawn from the final weights, the trajectories are
+    equally weighted; else they are the caller's, and mean() / var() take weights.  single_dim: a 1-D model, the last axis of paths is
+    dropped.
+
+    The trajectories are lineages of one genealogy: where the clouds collapsed, all K of them share their early stretches, and a sample
+    mean over them has there the variance of a single draw.  distinct() says how many different paths each stretch holds."""
+
+    def __init__(self, log_w, paths, slots, stride, n_pts, obs_t, ess=(), resampled=(), drawn=True, single_dim=False) -> None:
+        self.log_w = np.asarray(log_w, dtype=float).ravel()
+        if self.log_w.size < 1:
+            raise ValueError(" SmoothingPaths: at least one particle.")
+        self.stride, self.n_pts = int(stride), int(n_pts)
+        if self.stride < 1 or self.n_pts < 1:
+            raise ValueError(" SmoothingPaths: stride and n_pts must be at least 1.")
+        full = np.asarray(paths, dtype=float)
+        if full.ndim != 3 or full.shape[0] < 1 or full.shape[1] != (self.n_pts - 1) // self.stride + 1:
+            raise ValueError(" SmoothingPaths: paths must be (K, n_keep, D).")
+        self.single_dim = bool(single_dim)
+        self.paths = full[..., 0] if self.single_dim else full
+        self.obs_t = np.asarray(obs_t, dtype=np.int64).ravel()
+        self.slots = np.asarray(slots, dtype=np.int64)
+        if self.slots.shape != (self.obs_t.size + 1, full.shape[0]):
+            raise ValueError(" SmoothingPaths: slots must be (M + 1, K).")
+        if self.slots.min() < 0 or self.slots.max() >= self.log_w.size:
+            raise ValueError(" SmoothingPaths: a slot outside [0, n).")
+        self.ess = np.asarray(ess, dtype=float).ravel()
+        self.resampled = np.asarray(resampled).astype(bool).ravel()
+        if self.ess.size != self.resampled.size:
+            raise ValueError(" SmoothingPaths: ess and resampled do not belong together.")
+        self.drawn = bool(drawn)
+
+    def __len__(self):
+        return self.paths.shape[0]
+
+    @property
+    def grid(self):
+        """the kept grid indices 0, stride, 2 stride, ..."""
+        return np.arange(0, self.n_pts, self.stride)
+
+    def _weights(self, weights):
+        if weights is None:
+            if not self.drawn:
+                raise ValueError(" SmoothingPaths: the final slots were given: pass weights= (final_weights() are those of the filter).")
+            return np.full(len(self), 1.0 / len(self))
+        w = np.asarray(weights, dtype=float).ravel()
+        if w.size != len(self) or np.any(w < 0.0) or not np.sum(w) > 0.0:
+            raise ValueError(" SmoothingPaths: weights must be K non-negative numbers with a positive sum.")
+        return w / np.sum(w)
+
+    def final_weights(self):
+        """the filter's normalised final weights of the trajectories' final slots, renormalised over the K trajectories: the weights of
+        given final slots that are all different"""
+        w = np.exp(self.log_w - np.max(self.log_w))[self.slots[-1]]
+        return w / np.sum(w)
+
+    def mean(self, weights=None):
+        """the mean over the trajectories on the grid, (n_keep, D): equal weights for drawn final slots, `weights` (K,) for given ones"""
+        return np.tensordot(self._weights(weights), self.paths, axes=(0, 0))
+
+    def var(self, weights=None):
+        """the variance over the trajectories on the grid, sum w (x - mean)^2"""
+        w = self._weights(weights)
+        dev = self.paths - np.tensordot(w, self.paths, axes=(0, 0))[None]
+        return np.tensordot(w, dev * dev, axes=(0, 0))
+
+    def distinct(self):
+        """(M_p + 1,): the number of different slots among the K trajectories in every stretch -- the number of different paths there.
+        Non-decreasing in time; 1 where the genealogy has coalesced."""
+        return np.array([np.unique(row).size for row in self.slots])
+
+    def distinct_on_grid(self):
+        """distinct() of the stretch each kept grid index lies in: index k belongs to stretch #{observations before k}"""
+        return self.distinct()[np.searchsorted(self.obs_t, self.grid, side="left")]
 
     def log_evidence(self):
         """logsumexp(log_w) - log n, as ParticleFilterResult.log_evidence()"""

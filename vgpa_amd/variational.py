@@ -240,6 +240,25 @@ class VarGP(object):
         out = [self._moments_record(res, k, stride) for k in range(res["log_w"].shape[0])]
         return out[0] if self.batch == 1 else out
 
+    def _paths_record(self, res, k, stride, drawn, obs_t=None):
+        """One problem's SmoothingPaths from row k of Context.particle_paths' dict, cut to its own observations obs_t"""
+        from .particles import SmoothingPaths
+        t = np.asarray(self._inputs()["obs_t"] if obs_t is None else obs_t).ravel()
+        return SmoothingPaths(res["log_w"][k], res["paths"][k], res["slots"][k, :t.size + 1], stride, self.dim_n, t, res["ess"][k, :t.size],
+                              res["resampled"][k, :t.size], drawn, self.model.single_dim)
+
+    def particle_paths(self, n_paths, seed, n_draw, stride=1, ess_fraction=0.5, x=None, x0=None, slots=None):
+        """n_draw whole smoothing trajectories on the time grid from particle_filter with the same arguments: a particles.SmoothingPaths
+        (with batch > 1 a list, one per problem) -- paths (n_draw, n_keep, D) at the grid indices 0, stride, ..., equally weighted draws
+        from the filter's genealogy (slots=None) or the lineages of the given final slots, and the slot of every trajectory in every
+        stretch.  Only the n_draw trajectories are walked again and copied.  On collapsing clouds the early stretches of all
+        trajectories coincide: distinct() says how many are left."""
+        xx = None if x is None else np.asarray(x, dtype=float)
+        res = self._context().particle_paths(n_paths, seed, n_draw, stride=stride, ess_fraction=ess_fraction, x=xx, x0=x0, prior=self._prior(),
+                                             slots=slots)
+        out = [self._paths_record(res, k, stride, slots is None) for k in range(res["log_w"].shape[0])]
+        return out[0] if self.batch == 1 else out
+
     def particle_fit_theta(self, n_paths, seed, iters, ess_fraction=0.5, refit=True, pooled=False):
         """Particle EM for the drift parameters (ProblemBatch.particle_fit_theta on a batch of one): (theta, trace), theta in the shape of
         model.theta."""
