@@ -17,14 +17,13 @@ from helpers import build_problem
 from test_gpu_edge_cases import gpu_context, make_problem
 from test_problem_batch import _context, _datasets
 from test_path_weights import _fields
-from test_path_weights_cpu import FIXTURES
+from test_path_weights_cpu import TAGS
 from test_particle_filter_cpu import (BATCH_TIMES, FRACTIONS, OU_BIG, PLACEMENTS, QUIET, SEED, SEED_BATCH, batch_case, case, log_mean_exp,
                                       particle_filter_numpy, placement_case, reference)
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-9
-TAGS = FIXTURES + ["l96d5", "l96d64"]
 
 
 def _prior(q):

@@ -33,7 +33,7 @@ from vgpa_amd.weights import init_term
 from conftest import ROOT, load_golden
 from oracle import vgpa_oracle as vo
 from test_gpu_edge_cases import make_problem
-from test_path_weights_cpu import FIXTURES, _sigma_diag, _split, obs_model, path_weights_numpy
+from test_path_weights_cpu import FIXTURES, TAGS, _sigma_diag, _split, obs_model, path_weights_numpy
 from test_sample_paths_cpu import model_drift, normals, philox4x32_10, unit_open
 
 SEED = 7                         # (seed 5 leaves l96d5 and two quiet cases a margin of 2.5e-8 .. 6.6e-8 at n = 300: another seed, the same bound)
@@ -120,7 +120,7 @@ def _given(q):
 
 @functools.lru_cache(maxsize=None)
 def case(tag):
-    """(problem, x, given start) of a tag: a fixture, "l96d5" / "l96d64" of test_path_weights.py, or a quiet case -- a Lorenz-96 fixture's
+    """(problem, x, given start) of a tag: a fixture, "l96d4" / "l96d5" / "l96d64" of test_path_weights.py, or a quiet case -- a Lorenz-96 fixture's
     grid with theta = 0, observations 0, A_t = I, b_t = 0 and every particle started at 0: the weights stay comparable, so that the clouds
     are partly resampled and partly carried on"""
     if tag in FIXTURES:
@@ -139,8 +139,8 @@ def case(tag):
         x = v.initialization() + 0.05 * np.random.default_rng(3).standard_normal(v.dim_n * 64 * 65)
         q = _fields(v)
         return q, x, _given(q)
-    assert tag == "l96d5", tag
-    q, x = make_problem("L96", 5, 41, method="euler")
+    assert tag in ("l96d4", "l96d5"), tag
+    q, x = make_problem("L96", int(tag[4:]), 41, method="euler")
     return q, x, _given(q)
 
 
@@ -182,7 +182,7 @@ def batch_case(model, d, first):
 def gpu_runs():
     """every restatement the GPU tests compare ancestors with, as (label, thunk)"""
     runs = []
-    for tag in FIXTURES + ["l96d5", "l96d64"] + QUIET:
+    for tag in TAGS + QUIET:
         for start in (("given",) if tag in QUIET else ("given", "drawn")):
             for n in SIZES:
                 for frac in FRACTIONS:

@@ -19,7 +19,7 @@ from helpers import build_problem
 from test_gpu_edge_cases import gpu_context, make_problem
 from test_problem_batch import _context, _datasets
 from test_path_weights import _fields
-from test_path_weights_cpu import FIXTURES
+from test_path_weights_cpu import FIXTURES, TAGS
 from test_particle_filter import CACHE_CASES, _batch_context, _ctx, _prior
 from test_particle_filter_cpu import (FRACTIONS, OU_BIG, PLACEMENTS, QUIET, SEED, SEED_BATCH, batch_case, case, placement_case)
 from test_particle_moments_cpu import particle_moments_numpy, reference
@@ -27,7 +27,6 @@ from test_particle_moments_cpu import particle_moments_numpy, reference
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-9
-TAGS = FIXTURES + ["l96d5", "l96d64"]
 WALK = ("log_w", "state", "ess", "resampled")
 WORST = {"m1": 0.0, "m2": 0.0, "lineage_ess": 0.0}      # over the module, printed by the last test
 

@@ -32,10 +32,9 @@ from conftest import ROOT
 from test_particle_filter_cpu import FRACTIONS, MARGIN, QUIET, SEED, case, particle_filter_numpy
 from test_particle_filter_cpu import reference as filter_reference
 from test_particle_moments_cpu import particle_moments_numpy, rts_marginals
-from test_path_weights_cpu import FIXTURES, _sigma_diag, _split, obs_model
+from test_path_weights_cpu import TAGS, _sigma_diag, _split, obs_model
 from test_sample_paths_cpu import model_drift, normals, philox4x32_10, unit_open
 
-TAGS = FIXTURES + ["l96d5", "l96d64"]
 CASES = [(t, s) for t in TAGS for s in ("given", "drawn")] + [(t, "given") for t in QUIET]
 # (particles, trajectories) of the GPU tests in drawn mode: one particle; more trajectories than particles and a second workgroup above
 # D = 4; a partial wave; one trajectory; a partial 64-path block behind a full one

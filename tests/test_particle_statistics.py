@@ -17,7 +17,7 @@ from helpers import build_problem
 from test_gpu_edge_cases import gpu_context, make_problem
 from test_problem_batch import _context, _datasets
 from test_path_weights import _fields
-from test_path_weights_cpu import FIXTURES, _sigma_diag
+from test_path_weights_cpu import FIXTURES, TAGS, _sigma_diag
 from test_particle_filter import CACHE_CASES, _batch_context, _ctx, _prior
 from test_particle_filter_cpu import (FRACTIONS, OU_BIG, PLACEMENTS, QUIET, SEED, SEED_BATCH, batch_case, case, placement_case)
 from test_particle_filter_cpu import reference as filter_reference
@@ -28,7 +28,6 @@ pytestmark = pytest.mark.gpu
 
 TOL = 1e-9
 TINY = float(np.finfo(float).tiny)
-TAGS = FIXTURES + ["l96d5", "l96d64"]
 WALK = ("log_w", "state", "ess", "resampled")
 
 

@@ -19,7 +19,7 @@ from conftest import load_golden, rel_err
 from helpers import build_problem, problem_from_golden
 from test_gpu_edge_cases import gpu_context, make_problem, spd
 from test_problem_batch import _context, _datasets
-from test_path_weights_cpu import FIXTURES, independent_form, path_weights_numpy
+from test_path_weights_cpu import FIXTURES, TAGS, independent_form, path_weights_numpy
 
 pytestmark = pytest.mark.gpu
 
@@ -63,8 +63,8 @@ def _case(cache, tag):
             v = build_problem("L96", "euler", 0.5, dim_d=64)["vgp"]
             x = v.initialization() + 0.05 * np.random.default_rng(3).standard_normal(v.dim_n * 64 * 65)
             cache[tag] = (v, _fields(v), x)
-        else:                                       # "l96d5": an oracle problem on a bare context
-            q, x = make_problem("L96", 5, 41, method="euler")
+        else:                                       # "l96d4", "l96d5": an oracle problem on a bare context
+            q, x = make_problem("L96", int(tag[4:]), 41, method="euler")
             cache[tag] = (None, q, x)
     return cache[tag]
 
@@ -100,7 +100,7 @@ def _weights(v, q, x, n_paths, seed, x0):
 
 @pytest.mark.parametrize("start", ["given", "drawn"])
 @pytest.mark.parametrize("n_paths", [1, 17, 65])
-@pytest.mark.parametrize("tag", FIXTURES + ["l96d5", "l96d64"])
+@pytest.mark.parametrize("tag", TAGS)
 def test_against_numpy(cases, tag, n_paths, start):
     v, q, x = _case(cases, tag)
     want = _reference(cases, tag, start)

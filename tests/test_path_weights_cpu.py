@@ -24,6 +24,9 @@ from oracle import vgpa_oracle as vo
 from test_sample_paths_cpu import model_drift, normals, sample_paths_numpy
 
 FIXTURES = ["ou_euler", "dw_euler_p", "l63_euler_p", "l96d12_euler_p", "l96d17_rk4_p", "l96d40_rk4_p"]
+# the tags of the sampler tests: the fixtures, "l96d<D>" = make_problem("L96", D, 41, method="euler") on a bare context (D = 4: the widest
+# one-lane-per-path kernel, D = 5: the narrowest matrix-core one) and "l96d64", a built problem at the widest
+TAGS = FIXTURES + ["l96d4", "l96d5", "l96d64"]
 
 
 def _split(problem, x):

@@ -18,12 +18,12 @@ from conftest import load_golden, rel_err
 from helpers import SEED, build_problem, make_model, problem_from_golden
 from test_gpu_edge_cases import gpu_context, make_problem
 from test_problem_batch import _context, _datasets
+from test_path_weights_cpu import FIXTURES, TAGS
 from test_sample_paths_cpu import em_moments, n_keep, normals, sample_paths_numpy
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-9
-FIXTURES = ["ou_euler", "dw_euler_p", "l63_euler_p", "l96d12_euler_p", "l96d17_rk4_p", "l96d40_rk4_p"]
 
 
 @pytest.fixture(scope="module")
@@ -56,8 +56,14 @@ def _posterior_case(cache, tag):
             v = p["vgp"]
             x = v.initialization() + 0.05 * np.random.default_rng(3).standard_normal(v.dim_n * 64 * 65)
             cache[tag] = (v, _fields(v), x)
-        else:                                       # "l96d5": an oracle problem on a bare context
-            q, x = make_problem("L96", 5, 41, method="euler")
+        elif tag == "none_d2":                      # no stochastic model: the one way to D = 2, and to the posterior kind alone
+            rng = np.random.default_rng(5)
+            q = types.SimpleNamespace(model="NONE", dim_d=2, n_pts=41, dt=0.01, theta=0.0, sigma=np.diag(3.0 + rng.random(2)),
+                                      m0=1.0 + rng.standard_normal(2), s0=np.array([[0.2, 0.05], [0.05, 0.3]]))
+            x = np.concatenate(((2.0 * np.eye(2) + 0.05 * rng.standard_normal((41, 2, 2))).ravel(), rng.standard_normal(41 * 2)))
+            cache[tag] = (None, q, x)
+        else:                                       # "l96d4", "l96d5": an oracle problem on a bare context
+            q, x = make_problem("L96", int(tag[4:]), 41, method="euler")
             cache[tag] = (None, q, x)
     return cache[tag]
 
@@ -65,7 +71,7 @@ def _posterior_case(cache, tag):
 def _draw(v, q, x, n_paths, seed, stride, x0):
     if v is not None:
         return np.asarray(v.sample_paths(n_paths, seed, stride=stride, x=x, x0=x0)).reshape(n_paths, -1, q.dim_d)
-    ctx = gpu_context(q)
+    ctx = gpu_context(q) if q.model != "NONE" else va.Context("NONE", "euler", q.dim_d, q.n_pts, q.dt, sigma=q.sigma, m0=q.m0, s0=q.s0)
     out = ctx.sample_paths("posterior", n_paths, seed, stride=stride, x=x, x0=x0)[0]
     ctx.close()
     return out
@@ -90,7 +96,7 @@ def test_generator_on_the_device():
 
 
 @pytest.mark.parametrize("n_paths", [1, 16, 17, 65])
-@pytest.mark.parametrize("tag", FIXTURES + ["l96d5", "l96d64"])
+@pytest.mark.parametrize("tag", TAGS + ["none_d2"])
 def test_posterior_paths_against_numpy(cases, tag, n_paths):
     v, q, x = _posterior_case(cases, tag)
     d, n = q.dim_d, q.n_pts

@@ -1,28 +1,31 @@
-// Euler-Maruyama sample paths of the posterior process dx = (-A_t x + b_t) dt + Sigma^1/2 dW and of the model SDE (vgpa_sample_paths,
-// DESIGN.md s.4.8):  x_k = x_{k-1} + dt drift_{k-1}(x_{k-1}) + R xi_k,  R = chol_lower(Sigma dt).
-//   k_sample_small<D>   D <= 4, both kinds: one lane per path, the state in registers
-//   k_sample_mfma<NT>   5 <= D <= 64, posterior kind: a workgroup owns one problem and 64 paths (4 waves x 16 paths); A_k X (and R Xi for a dense
-//                       R) on v_mfma_f64_16x16x4_f64 with the 16 paths of a wave as the N side, D padded to NT = 16, 32, 48, 64
-//   k_sample_l96        5 <= D <= 64, model kind (Lorenz-96): one lane per path, the state in LDS
+// Euler-Maruyama sample paths of the posterior process dx = (-A_t x + b_t) dt + Sigma^1/2 dW and of the model SDE:
+//   x_k = x_{k-1} + dt drift_{k-1}(x_{k-1}) + R xi_k,  R = chol_lower(Sigma dt).
+// Three kernels walk the grid:
+//   k_sample_small<D, K>   D <= 4, both kinds: one lane per path, the state in registers
+//   k_sample_mfma<NT, K>   5 <= D <= 64, posterior kind: a workgroup owns one problem and 64 paths (4 waves x 16 paths); A_k X (and R Xi for a dense
+//                          R) on v_mfma_f64_16x16x4_f64 with the 16 paths of a wave as the N side, D padded to NT = 16, 32, 48, 64
+//   k_sample_l96           5 <= D <= 64, model kind (Lorenz-96): one lane per path, the state in LDS
 // The normals are counter-based (Philox4x32-10 + Box-Muller, vgpa_hip.h): every lane generates exactly the draws it consumes, so no result
 // depends on the launch geometry.
-// k_sample_small<D, true> and k_sample_mfma<NT, true> (vgpa_sample_paths_weighted) walk the same paths and sum, where the path
-// is made, the log-ratio of the model SDE's path density to the posterior process's and the Gaussian log-likelihood of the observations.
-// k_sample_small<D, true, true> and k_sample_mfma<NT, true, true> (vgpa_particle_filter) are their segment twins: the grid
-// steps k_begin < k <= k_end from the particle states in SampleArgs::pf_x, the increments added to the log-weights in pf_lw, the end states
-// written back.  k_pf_start draws the particles and their initial term; k_pf_resample is the step between two segments.
-// k_sample_small<D, true, true, true> and k_sample_mfma<NT, true, true, true> (vgpa_particle_statistics) are the segments
-// that also carry each slot's [3][D] row of path statistics (SampleArgs::pf_stats); k_pf_resample<true> gathers the rows by ancestor with
-// the states, k_pf_stats_mean reduces them to their self-normalised weighted mean.
-// k_sample_small<D, true, true, false, true> and k_sample_mfma<NT, true, true, false, true> (vgpa_particle_moments) are the
-// segments of the replay: the same states from the same counters, no weight sums, and at every kept grid index the workgroup's sums of
-// W x and W x^2 with the descendant weights W that k_pf_descend pushed back through the stored ancestors; k_pf_gather is the step between
-// two segments of the replay, k_pf_moments_sum adds the workgroups' sums in block order.
-// k_sample_small<D, false, false, false, false, true> and k_sample_mfma<NT, false, false, false, false, true> (vgpa_particle_paths, DESIGN.md
-// s.4.13) walk K smoothing trajectories of the filter's genealogy in one launch: the unweighted posterior walk, stored as vgpa_sample_paths
-// stores it, each lane drawing with the counter word of the slot its lineage sat in -- one word per stretch between two observations of
-// its problem, from the table k_pf_trace wrote behind k_pf_pick (or behind the caller's final slots).
+// K is the walk (vgpa_internal.h), stated by the host at every launch_sample_walk; every walk runs on k_sample_small and k_sample_mfma:
+//   walk         | what it computes; [the kernels and k_pf_* steps that serve it besides those two]                                 | DESIGN.md
+//   Plain        | the paths, every stride-th point stored  [k_sample_l96]                                                          | s.4.8
+//   Weighted     | the same paths and, summed where the path is made, the log-ratio of the model SDE's path density to the          | s.4.9
+//                | posterior process's and the Gaussian log-likelihood of the observations                                          |
+//   Segment      | the grid steps k_begin < k <= k_end of the weighted walk from the particle states in pf_x, the increments added  | s.4.10
+//                | to pf_lw, the end states written back  [k_pf_start: the particles and their initial term; k_pf_resample<false>:  |
+//                | the step between two segments]                                                                                   |
+//   SegmentStats | a segment that also carries each slot's [3][D] row of path statistics  [k_pf_resample<true> gathers the rows by  | s.4.11
+//                | ancestor with the states, k_pf_stats_mean reduces them to their self-normalised weighted mean]                   |
+//   Replay       | a segment once more: the same states from the same counters, no weight sums, and at every kept grid index the    | s.4.12
+//                | workgroup's sums of W x and W x^2 with the descendant weights W  [k_pf_descend pushes the weights back through   |
+//                | the stored ancestors, k_pf_gather: the step between two segments, k_pf_moments_sum adds the sums in block order] |
+//   Lineage      | K smoothing trajectories of the filter's genealogy in one launch: the unweighted posterior walk, stored as Plain | s.4.13
+//                | stores it, each lane drawing with the counter word of the slot its lineage sat in -- one word per stretch between |
+//                | two observations of its problem  [k_pf_trace writes the table behind k_pf_pick or the caller's final slots]      |
 #include "vgpa_internal.h"
+
+#include <type_traits>
 
 namespace vgpa {
 namespace {
@@ -130,24 +133,37 @@ __device__ __forceinline__ double wave_max(double v) {
   return v;
 }
 
-// W: the weighted instantiation (posterior kind, diagonal R): both drifts at x_{k-1}, d = g - f, and per step
-// -sum_i d_i (eta_i + dt d_i / 2) / Sigma_ii with 1 / Sigma_ii = dt / R_ii^2; the observation term at the lane's own problem's times
-// SEG: a segment of the weighted walk (k_begin, k_end] from and to pf_x, the sums added to pf_lw; nothing else is stored
-// ST: a segment that adds its steps to the slot's row of pf_stats: Q_i += r^2 / dt, G_i += phi_i r, H_i += dt phi_i^2 with r = dt d + eta
-// MO: a segment of the replay, launched with the problem in blockIdx.x and 256 slots per workgroup.  The states only (no model drift, no
-// sums, pf_lw untouched); at a kept k the lanes' W x_i and (W x_i) x_i are added over the wave by a butterfly and over the four waves
-// through four LDS words per value (two sets, alternating: one barrier per kept k), in that fixed order.  A lane behind the last slot
-// walks from 0 with the last slot's counters and weight 0 and stores nothing.
-// LN: the lineage walk: the unweighted posterior walk of lane m = `path`, whose counter word is not m but the entry of its column of
-// pf_slots for the stretch it is in: row 0 for the start, the next row each time the walk has completed an observation index of the lane's
-// own problem (an observation at index 0: before step 1).  No model drift, no sums.
-template <int D, bool W, bool SEG = false, bool ST = false, bool MO = false, bool LN = false>
+// What the two kernels branch on, per walk: W the walk of the weighted kind (posterior drift, diagonal R), SEG it runs (k_begin, k_end] from
+// and to pf_x, ST it carries the rows of pf_stats, MO it takes the moments of the replay, LN the counter words come from pf_slots;
+// WS: the weight sums are formed.  The six rows are all there is: no other combination can be instantiated.
+struct WalkTraits {
+  bool W, SEG, ST, MO, LN;
+  constexpr bool WS() const { return W && !MO; }
+};
+constexpr WalkTraits kWalkTraits[] = {      // in the order of Walk
+    {false, false, false, false, false},    // Plain
+    {true,  false, false, false, false},    // Weighted
+    {true,  true,  false, false, false},    // Segment
+    {true,  true,  true,  false, false},    // SegmentStats
+    {true,  true,  false, true,  false},    // Replay
+    {false, false, false, false, true}};    // Lineage
+
+// Weighted: posterior kind, diagonal R: both drifts at x_{k-1}, d = g - f, and per step -sum_i d_i (eta_i + dt d_i / 2) / Sigma_ii with
+// 1 / Sigma_ii = dt / R_ii^2; the observation term at the lane's own problem's times.
+// Segment: the weighted walk over (k_begin, k_end] from and to pf_x, the sums added to pf_lw; nothing else is stored.
+// SegmentStats: a segment that adds its steps to the slot's row of pf_stats: Q_i += r^2 / dt, G_i += phi_i r, H_i += dt phi_i^2 with
+// r = dt d + eta.
+// Replay: a segment launched with the problem in blockIdx.x and 256 slots per workgroup.  The states only (no model drift, no sums, pf_lw
+// untouched); at a kept k the lanes' W x_i and (W x_i) x_i are added over the wave by a butterfly and over the four waves through four
+// LDS words per value (two sets, alternating: one barrier per kept k), in that fixed order.  A lane behind the last slot walks from 0
+// with the last slot's counters and weight 0 and stores nothing.
+// Lineage: the unweighted posterior walk of lane m = `path`, whose counter word is not m but the entry of its column of pf_slots for the
+// stretch it is in: row 0 for the start, the next row each time the walk has completed an observation index of the lane's own problem (an
+// observation at index 0: before step 1).  No model drift, no sums.
+template <int D, Walk K>
 __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
-  static_assert(W || !SEG, "a segment is a weighted walk");
-  static_assert(SEG || !ST, "the statistics are carried by the segments");
-  static_assert(!MO || (SEG && !ST), "the replay is a segment without statistics");
-  static_assert(!LN || !W, "the lineage walk is unweighted");
-  constexpr bool WS = W && !MO;      // the weight sums are formed
+  constexpr WalkTraits T = kWalkTraits[(int)K];
+  constexpr bool W = T.W, SEG = T.SEG, ST = T.ST, MO = T.MO, LN = T.LN, WS = T.WS();
   size_t gid;
   uint32_t p, path;
   bool live = true;
@@ -224,7 +240,7 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
     oc = ObsCursor(a, p);
     if (oc.next == 0) { oc.advance(); word = (uint32_t)lin[(size_t)oc.cur * a.n_paths]; }
   }
-  // MO: the segment lies in one stretch of its problem -- the observations behind it are oc.cur, the row of the weights
+  // Replay: the segment lies in one stretch of its problem -- the observations behind it are oc.cur, the row of the weights
   double wt = 0.0;
   double* red = nullptr;
   int par = 0;
@@ -370,31 +386,29 @@ __device__ __forceinline__ void normals_c(uint32_t k0, uint32_t k1, uint32_t k, 
   }
 }
 
-// W: the weighted instantiation (Lorenz-96, diagonal R).  At step k the lane holds rows mt * 16 + q + 4 r of x_{k-1}, of g = bs - acc and of
-// eta = nz; the model drift f_i reads rows (i + 1) mod D, (i - 2) mod D, (i - 1) mod D of the path's column of Xs.  Each lane sums its rows over
-// time; the four q-lanes of a path are added once at the end.  The observation term is evaluated from Xs at the problem's observation times,
-// which a workgroup walks with one cursor.
-// SEG: as in k_sample_small; A_{k_begin} is the first matrix loaded, and the end states leave through `put` as [path][D].
-// ST: the lane adds r^2 / dt and r = dt d + eta (phi = 1: Lorenz-96) of its own rows to Q and G of the path's row of pf_stats, read at the
-// segment's entry and written at its exit; H_j = dt k_end, the constant dt times the steps walked so far, is written and not summed.
-// MO: a segment of the replay: the states only.  At a kept k every lane multiplies its rows of x_k by its path's weight (0 behind the last
-// path), four cross-lane steps add the 16 paths of the wave, the lanes of path column 0 put their rows into red [4 waves][2][NT] -- the
-// Zs region, which a segment does not use --, and behind the next barrier the walk has anyway (the first of the next step, or one behind
-// the loop) thread t < 2 D adds the four waves in order and stores moment t / D of component t mod D.
-// LN: the lineage walk, as in k_sample_small (diagonal R): every lane of a workgroup belongs to one problem, so all of them change their
-// counter words behind the same steps.  A lane behind the last lineage walks the last one again and stores nothing.
-template <int NT, bool W, bool SEG = false, bool ST = false, bool MO = false, bool LN = false>
+// Weighted: Lorenz-96, diagonal R.  At step k the lane holds rows mt * 16 + q + 4 r of x_{k-1}, of g = bs - acc and of eta = nz; the model
+// drift f_i reads rows (i + 1) mod D, (i - 2) mod D, (i - 1) mod D of the path's column of Xs.  Each lane sums its rows over time; the four
+// q-lanes of a path are added once at the end.  The observation term is evaluated from Xs at the problem's observation times, which a
+// workgroup walks with one cursor.
+// Segment: as in k_sample_small; A_{k_begin} is the first matrix loaded, and the end states leave through `put` as [path][D].
+// SegmentStats: the lane adds r^2 / dt and r = dt d + eta (phi = 1: Lorenz-96) of its own rows to Q and G of the path's row of pf_stats,
+// read at the segment's entry and written at its exit; H_j = dt k_end, the constant dt times the steps walked so far, is written and not
+// summed.
+// Replay: the states only.  At a kept k every lane multiplies its rows of x_k by its path's weight (0 behind the last path), four
+// cross-lane steps add the 16 paths of the wave, the lanes of path column 0 put their rows into red [4 waves][2][NT] -- the Zs region,
+// which a segment does not use --, and behind the next barrier the walk has anyway (the first of the next step, or one behind the loop)
+// thread t < 2 D adds the four waves in order and stores moment t / D of component t mod D.
+// Lineage: as in k_sample_small (diagonal R): every lane of a workgroup belongs to one problem, so all of them change their counter words
+// behind the same steps.  A lane behind the last lineage walks the last one again and stores nothing.
+template <int NT, Walk K>
 __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
-  static_assert(W || !SEG, "a segment is a weighted walk");
-  static_assert(SEG || !ST, "the statistics are carried by the segments");
-  static_assert(!MO || (SEG && !ST), "the replay is a segment without statistics");
-  static_assert(!LN || !W, "the lineage walk is unweighted");
-  constexpr bool WS = W && !MO;      // the weight sums are formed
+  constexpr WalkTraits T = kWalkTraits[(int)K];
+  constexpr bool W = T.W, SEG = T.SEG, ST = T.ST, MO = T.MO, LN = T.LN, WS = T.WS();
   using Sh = MfmaShape<NT>;
   constexpr int LDA = Sh::LDA, MT = Sh::MT, KT = Sh::KT, NPF = Sh::NPF;
   extern __shared__ double lds[];
   const int D = a.D, DD = D * D, tid = threadIdx.x, w = tid >> 6, lane = tid & 63, j16 = lane & 15, q = lane >> 4;
-  const bool dense = !W && !LN && !a.R_diag;      // (the weighted instantiation and the lineage walk are launched with diagonal factors only)
+  const bool dense = !W && !LN && !a.R_diag;      // (the weighted walks and the lineage walk are launched with diagonal factors only)
   double* As = lds;
   double* bs = As + NT * LDA;
   double* Rs = bs + NT;
@@ -541,7 +555,7 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
   if constexpr (LN) {
     if (oc.next == 0) { oc.advance(); word = (uint32_t)lin[(size_t)oc.cur * a.n_paths]; }
   }
-  // MO: the segment lies in one stretch of its problem -- the observations behind it are oc.cur, the row of the weights
+  // Replay: the segment lies in one stretch of its problem -- the observations behind it are oc.cur, the row of the weights
   double wt = 0.0;
   double* red = lds + NT * LDA + NT + 4 * NT * 16;
   long long keep_k = 0, keep_slot = 0, pending = -1;
@@ -711,7 +725,7 @@ __global__ __launch_bounds__(64) void k_sample_l96(SampleArgs a) {
   } else {
     const double* m0 = a.m0 + (size_t)p * a.m0_stride;
     const double* L0 = a.L0 + (size_t)p * a.L0_stride;
-    for (int j = 0; 2 * j < D; j++) {
+    for (int j = 0; 2 * j < D; j++) {      // (the start draw is written out here and in k_pf_start: as a shared function it changes k_pf_start's code)
       double c, s;
       normal_pair(k0, k1, 0u, path, p, (uint32_t)j, &c, &s);
       zs[2 * j * 64] = c;
@@ -759,26 +773,7 @@ __global__ __launch_bounds__(64) void k_sample_l96(SampleArgs a) {
   }
 }
 
-template <int NT, bool W, bool LN = false>
-hipError_t launch_mfma(const SampleArgs& a, hipStream_t st) {
-  const size_t lds = MfmaShape<NT>::lds_doubles(!a.R_diag) * sizeof(double);
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute((const void*)k_sample_mfma<NT, W, false, false, false, LN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if ((a.n_paths + 63) / 64 > 65535) return hipErrorInvalidValue;      // (grid.y)
-  hipLaunchKernelGGL((k_sample_mfma<NT, W, false, false, false, LN>), dim3(a.batch, (a.n_paths + 63) / 64), dim3(256), lds, st, a);
-  return hipGetLastError();
-}
-
 // ---- the particle filter: the start, the segments, the resampling step between them ------------------------------------------------
-template <int NT, bool ST = false, bool MO = false>
-hipError_t launch_mfma_segment(const SampleArgs& a, hipStream_t st) {
-  const size_t lds = MfmaShape<NT>::lds_doubles(false) * sizeof(double);
-  if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k_sample_mfma<NT, true, true, ST, MO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if ((a.n_paths + 63) / 64 > 65535) return hipErrorInvalidValue;      // (grid.y)
-  hipLaunchKernelGGL((k_sample_mfma<NT, true, true, ST, MO>), dim3(a.batch, (a.n_paths + 63) / 64), dim3(256), lds, st, a);
-  return hipGetLastError();
-}
-
 // One lane per particle: x_0 (given, or m0 + L0 xi_0 summed as the samplers sum it) to a.x, and lw = init - c_p with
 // init = log N(x_0; mu0, tau0) - log N(x_0; m0, S0) for a drawn start under a prior (the two triangular solves against the factors in global
 // memory; a.ws [B][n][D] holds the lane's normals, then its solutions), else 0.  Runs once per call.
@@ -829,7 +824,7 @@ __global__ __launch_bounds__(256) void k_pf_start(PfArgs a) {
   a.lw[gid] = init - a.obs_const_scale * (a.obs_const_v ? a.obs_const_v[p] : a.obs_const);
 }
 
-// What k_pf_resample and k_pf_pick share, a workgroup of 256 threads on the n log-weights of one problem.
+// What k_pf_resample, k_pf_pick and k_pf_descend share, a workgroup of 256 threads on the n log-weights of one problem.
 // pf_max: max lw (red: 4 doubles of LDS).
 // pf_prefix_sums: cum_i = the inclusive prefix sums of w_i = exp(lw_i - mx) in slot order, 256 slots per pass: a shuffle scan per wave, the
 // waves' totals and the carry through LDS (tot: 4 doubles); returns the thread's share of sum w^2.  No barrier behind the last store of cum.
@@ -877,7 +872,7 @@ __global__ __launch_bounds__(256) void k_pf_resample(PfArgs a) {
   const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6, n = a.n_paths, D = a.D;
   const int64_t* t = a.obs_t + (size_t)p * a.obs_t_stride;
   const int cnt = a.n_obs_v ? a.n_obs_v[p] : a.n_obs;
-  int j = -1;
+  int j = -1;      // the problem's observation at a.k (written out here and in the other step between segments: a shared function changes the code of both)
   for (int m = 0; m < cnt; m++) if (t[m] == (int64_t)a.k) j = m;
   const size_t nD = (size_t)n * D;
   const double* xin = a.x_in + (size_t)p * nD;
@@ -950,7 +945,7 @@ __global__ __launch_bounds__(256) void k_pf_stats_mean(int D, int n, const doubl
   const int p = blockIdx.x, s = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const double* lw = lw_all + (size_t)p * n;
   const double* rows = stats + (size_t)p * n * 3 * D + (size_t)s * D;
-  double mx = -INFINITY;
+  double mx = -INFINITY;      // (pf_max, written out: the call changes this kernel's schedule)
   for (int i = tid; i < n; i += 256) mx = fmax(mx, lw[i]);
   mx = wave_max(mx);
   if (lane == 0) red[w] = mx;
@@ -995,12 +990,7 @@ __global__ __launch_bounds__(256) void k_pf_descend(PfArgs a, int rows, double* 
   const double* lw = a.lw + (size_t)p * n;
   double* wtab = wtab_all + (size_t)p * rows * n;
   double* less = less_all + (size_t)p * rows;
-  double mx = -INFINITY;
-  for (int i = tid; i < n; i += 256) mx = fmax(mx, lw[i]);
-  mx = wave_max(mx);
-  if ((tid & 63) == 0) red[tid >> 6] = mx;
-  __syncthreads();
-  mx = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+  const double mx = pf_max(lw, n, red);
   double s = 0.0;
   for (int i = tid; i < n; i += 256) s += exp(lw[i] - mx);
   s = block_sum(s, red);
@@ -1050,7 +1040,7 @@ __global__ __launch_bounds__(256) void k_pf_gather(PfArgs a) {
   const int p = blockIdx.x, n = a.n_paths, D = a.D;
   const int64_t* t = a.obs_t + (size_t)p * a.obs_t_stride;
   const int cnt = a.n_obs_v ? a.n_obs_v[p] : a.n_obs;
-  int j = -1;
+  int j = -1;      // the problem's observation at a.k (written out here and in the other step between segments: a shared function changes the code of both)
   for (int m = 0; m < cnt; m++) if (t[m] == (int64_t)a.k) j = m;
   const size_t nD = (size_t)n * D;
   const double* xin = a.x_in + (size_t)p * nD;
@@ -1119,80 +1109,40 @@ __global__ __launch_bounds__(256) void k_pf_trace(PfArgs a, int K, int rows, int
   }
 }
 
-template <bool W>
-hipError_t launch_posterior(const SampleArgs& a, hipStream_t st) {
-  const size_t lanes = (size_t)a.batch * a.n_paths;
+// One walk at the D of the arguments: k_sample_small<D, K> up to D = 4 (one lane per path; the replay: the problem in grid.x, 256 slots per
+// workgroup in grid.y), above it k_sample_mfma<NT, K> with NT the next multiple of 16 (grid: problems x 64 paths).  D = 2 exists for the
+// plain walk only: every other walk needs a stochastic model, and none has D = 2.
+template <Walk K>
+hipError_t launch_walk(const SampleArgs& a, hipStream_t st) {
   if (a.D <= kMaxLaneD) {
-    const dim3 grid((unsigned)((lanes + 255) / 256)), block(256);
+    const dim3 grid = kWalkTraits[(int)K].MO ? dim3(a.batch, sample_segment_blocks(a.D, a.n_paths))
+                                        : dim3((unsigned)(((size_t)a.batch * a.n_paths + 255) / 256));
+    const dim3 block(256);
     switch (a.D) {
-      case 1: hipLaunchKernelGGL((k_sample_small<1, W>), grid, block, 0, st, a); break;
-      case 2: hipLaunchKernelGGL((k_sample_small<2, W>), grid, block, 0, st, a); break;
-      case 3: hipLaunchKernelGGL((k_sample_small<3, W>), grid, block, 0, st, a); break;
-      default: hipLaunchKernelGGL((k_sample_small<4, W>), grid, block, 0, st, a); break;
+      case 1: hipLaunchKernelGGL((k_sample_small<1, K>), grid, block, 0, st, a); break;
+      case 2:
+        if constexpr (K == Walk::Plain) { hipLaunchKernelGGL((k_sample_small<2, K>), grid, block, 0, st, a); break; }
+        else return hipErrorInvalidValue;
+      case 3: hipLaunchKernelGGL((k_sample_small<3, K>), grid, block, 0, st, a); break;
+      default: hipLaunchKernelGGL((k_sample_small<4, K>), grid, block, 0, st, a); break;
     }
     return hipGetLastError();
   }
-  if (a.D <= 16) return launch_mfma<16, W>(a, st);
-  if (a.D <= 32) return launch_mfma<32, W>(a, st);
-  if (a.D <= 48) return launch_mfma<48, W>(a, st);
-  return launch_mfma<64, W>(a, st);
+  auto mfma = [&](auto nt) {
+    constexpr int NT = decltype(nt)::value;
+    const size_t lds = MfmaShape<NT>::lds_doubles(!a.R_diag) * sizeof(double);
+    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k_sample_mfma<NT, K>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if ((a.n_paths + 63) / 64 > 65535) return hipErrorInvalidValue;      // (grid.y)
+    hipLaunchKernelGGL((k_sample_mfma<NT, K>), dim3(a.batch, (a.n_paths + 63) / 64), dim3(256), lds, st, a);
+    return hipGetLastError();
+  };
+  if (a.D <= 16) return mfma(std::integral_constant<int, 16>{});
+  if (a.D <= 32) return mfma(std::integral_constant<int, 32>{});
+  if (a.D <= 48) return mfma(std::integral_constant<int, 48>{});
+  return mfma(std::integral_constant<int, 64>{});
 }
 
 }  // namespace
-
-hipError_t launch_sample_segment(const SampleArgs& a, hipStream_t st) {
-  if (a.D < 1 || a.D > kMaxSmallD || a.n_paths < 1 || a.kind != VGPA_PATHS_POSTERIOR || !a.R_diag || !a.pf_x || !a.pf_lw) return hipErrorInvalidValue;
-  if (a.k_begin < 0 || a.k_end < a.k_begin || a.k_end >= a.Np) return hipErrorInvalidValue;
-  if (a.model != VGPA_MODEL_OU && a.model != VGPA_MODEL_DW && a.model != VGPA_MODEL_L63 && a.model != VGPA_MODEL_L96) return hipErrorInvalidValue;
-  if (a.D > kMaxLaneD && a.model != VGPA_MODEL_L96) return hipErrorInvalidValue;
-  if (a.pf_wtab) {       // the segments of the replay (vgpa_particle_moments)
-    if (a.pf_stats || !a.pf_part || a.stride < 1 || a.pf_rows < 1 || sample_segment_blocks(a.D, a.n_paths) > 65535) return hipErrorInvalidValue;
-    if (a.D <= kMaxLaneD) {
-      const dim3 grid(a.batch, sample_segment_blocks(a.D, a.n_paths)), block(256);
-      switch (a.D) {
-        case 1: hipLaunchKernelGGL((k_sample_small<1, true, true, false, true>), grid, block, 0, st, a); break;
-        case 2: hipLaunchKernelGGL((k_sample_small<2, true, true, false, true>), grid, block, 0, st, a); break;
-        case 3: hipLaunchKernelGGL((k_sample_small<3, true, true, false, true>), grid, block, 0, st, a); break;
-        default: hipLaunchKernelGGL((k_sample_small<4, true, true, false, true>), grid, block, 0, st, a); break;
-      }
-      return hipGetLastError();
-    }
-    if (a.D <= 16) return launch_mfma_segment<16, false, true>(a, st);
-    if (a.D <= 32) return launch_mfma_segment<32, false, true>(a, st);
-    if (a.D <= 48) return launch_mfma_segment<48, false, true>(a, st);
-    return launch_mfma_segment<64, false, true>(a, st);
-  }
-  if (a.pf_stats) {      // the segments that carry the path statistics (vgpa_particle_statistics)
-    if (a.D <= kMaxLaneD) {
-      const dim3 grid((unsigned)(((size_t)a.batch * a.n_paths + 255) / 256)), block(256);
-      switch (a.D) {
-        case 1: hipLaunchKernelGGL((k_sample_small<1, true, true, true>), grid, block, 0, st, a); break;
-        case 2: hipLaunchKernelGGL((k_sample_small<2, true, true, true>), grid, block, 0, st, a); break;
-        case 3: hipLaunchKernelGGL((k_sample_small<3, true, true, true>), grid, block, 0, st, a); break;
-        default: hipLaunchKernelGGL((k_sample_small<4, true, true, true>), grid, block, 0, st, a); break;
-      }
-      return hipGetLastError();
-    }
-    if (a.D <= 16) return launch_mfma_segment<16, true>(a, st);
-    if (a.D <= 32) return launch_mfma_segment<32, true>(a, st);
-    if (a.D <= 48) return launch_mfma_segment<48, true>(a, st);
-    return launch_mfma_segment<64, true>(a, st);
-  }
-  if (a.D <= kMaxLaneD) {
-    const dim3 grid((unsigned)(((size_t)a.batch * a.n_paths + 255) / 256)), block(256);
-    switch (a.D) {
-      case 1: hipLaunchKernelGGL((k_sample_small<1, true, true>), grid, block, 0, st, a); break;
-      case 2: hipLaunchKernelGGL((k_sample_small<2, true, true>), grid, block, 0, st, a); break;
-      case 3: hipLaunchKernelGGL((k_sample_small<3, true, true>), grid, block, 0, st, a); break;
-      default: hipLaunchKernelGGL((k_sample_small<4, true, true>), grid, block, 0, st, a); break;
-    }
-    return hipGetLastError();
-  }
-  if (a.D <= 16) return launch_mfma_segment<16>(a, st);
-  if (a.D <= 32) return launch_mfma_segment<32>(a, st);
-  if (a.D <= 48) return launch_mfma_segment<48>(a, st);
-  return launch_mfma_segment<64>(a, st);
-}
 
 hipError_t launch_pf_start(const PfArgs& a, hipStream_t st) {
   if (a.D < 1 || a.D > kMaxSmallD || a.n_paths < 1 || !a.x || !a.ws || !a.lw || (!a.x0 && !(a.m0 && a.L0)) || (a.mu0 && !a.Lt)) return hipErrorInvalidValue;
@@ -1250,44 +1200,47 @@ bool sample_lineages_fit(int D, int batch, int K) {
   return (K + 63) / 64 <= 65535;                                                    // (grid.y)
 }
 
-hipError_t launch_sample_lineages(const SampleArgs& a, hipStream_t st) {
-  if (a.D < 1 || a.D > kMaxSmallD || a.n_paths < 1 || a.stride < 1 || a.kind != VGPA_PATHS_POSTERIOR || !a.R_diag || !a.out) return hipErrorInvalidValue;
-  if (!a.pf_slots || a.pf_slot_rows < 1 || a.logw || !sample_lineages_fit(a.D, a.batch, a.n_paths)) return hipErrorInvalidValue;
-  if (a.D <= kMaxLaneD) {
-    const dim3 grid((unsigned)(((size_t)a.batch * a.n_paths + 255) / 256)), block(256);
-    switch (a.D) {
-      case 1: hipLaunchKernelGGL((k_sample_small<1, false, false, false, false, true>), grid, block, 0, st, a); break;
-      case 2: hipLaunchKernelGGL((k_sample_small<2, false, false, false, false, true>), grid, block, 0, st, a); break;
-      case 3: hipLaunchKernelGGL((k_sample_small<3, false, false, false, false, true>), grid, block, 0, st, a); break;
-      default: hipLaunchKernelGGL((k_sample_small<4, false, false, false, false, true>), grid, block, 0, st, a); break;
-    }
-    return hipGetLastError();
-  }
-  if (a.D <= 16) return launch_mfma<16, false, true>(a, st);
-  if (a.D <= 32) return launch_mfma<32, false, true>(a, st);
-  if (a.D <= 48) return launch_mfma<48, false, true>(a, st);
-  return launch_mfma<64, false, true>(a, st);
-}
-
 hipError_t launch_pf_stats_mean(int D, int batch, int n_paths, const double* lw, const double* stats, double* mean, hipStream_t st) {
   if (D < 1 || D > kMaxSmallD || batch < 1 || n_paths < 1 || !lw || !stats || !mean) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_pf_stats_mean, dim3(batch, 3), dim3(256), 0, st, D, n_paths, lw, stats, mean);
   return hipGetLastError();
 }
 
-hipError_t launch_sample_paths(const SampleArgs& a, hipStream_t st) {
-  const size_t lanes = (size_t)a.batch * a.n_paths;
-  if (a.D < 1 || a.D > kMaxSmallD || a.n_paths < 1 || a.stride < 1) return hipErrorInvalidValue;
-  if (a.logw) {      // the weighted instantiations: the posterior kind against the model's drift, diagonal factors; above D = 4 the model is Lorenz-96
-    if (a.kind != VGPA_PATHS_POSTERIOR || !a.R_diag || !a.start || (a.D > kMaxLaneD && a.model != VGPA_MODEL_L96)) return hipErrorInvalidValue;
-    if (a.model != VGPA_MODEL_OU && a.model != VGPA_MODEL_DW && a.model != VGPA_MODEL_L63 && a.model != VGPA_MODEL_L96) return hipErrorInvalidValue;
-    return launch_posterior<true>(a, st);
+// The walk is what the caller says it is; the fields that walk reads must be set, and the fields that would have meant another walk must not.
+hipError_t launch_sample_walk(Walk w, const SampleArgs& a, hipStream_t st) {
+  if (a.D < 1 || a.D > kMaxSmallD || a.n_paths < 1) return hipErrorInvalidValue;
+  const bool known_model = a.model == VGPA_MODEL_OU || a.model == VGPA_MODEL_DW || a.model == VGPA_MODEL_L63 || a.model == VGPA_MODEL_L96;
+  // the weighted kind: the posterior process with diagonal factors against the model's drift; above D = 4 the model is Lorenz-96
+  const bool weighable = a.kind == VGPA_PATHS_POSTERIOR && a.R_diag && known_model && (a.D <= kMaxLaneD || a.model == VGPA_MODEL_L96);
+  const bool segment = weighable && a.pf_x && a.pf_lw && a.k_begin >= 0 && a.k_end >= a.k_begin && a.k_end < a.Np;
+  switch (w) {
+    case Walk::Plain: {
+      if (a.stride < 1 || a.logw) return hipErrorInvalidValue;
+      if (a.D <= kMaxLaneD || a.kind == VGPA_PATHS_POSTERIOR) return launch_walk<Walk::Plain>(a, st);
+      if (a.model != VGPA_MODEL_L96) return hipErrorInvalidValue;
+      const size_t lanes = (size_t)a.batch * a.n_paths, lds = (size_t)a.D * 64 * sizeof(double) * ((!a.R_diag || !a.x0) ? 2 : 1);
+      hipLaunchKernelGGL(k_sample_l96, dim3((unsigned)((lanes + 63) / 64)), dim3(64), lds, st, a);
+      return hipGetLastError();
+    }
+    case Walk::Weighted:
+      if (a.stride < 1 || !a.logw || !a.start || !weighable) return hipErrorInvalidValue;
+      return launch_walk<Walk::Weighted>(a, st);
+    case Walk::Segment:
+      if (!segment || a.pf_stats || a.pf_wtab) return hipErrorInvalidValue;
+      return launch_walk<Walk::Segment>(a, st);
+    case Walk::SegmentStats:
+      if (!segment || !a.pf_stats || a.pf_wtab) return hipErrorInvalidValue;
+      return launch_walk<Walk::SegmentStats>(a, st);
+    case Walk::Replay:
+      if (!segment || !a.pf_wtab || a.pf_stats || !a.pf_part || a.stride < 1 || a.pf_rows < 1) return hipErrorInvalidValue;
+      if (sample_segment_blocks(a.D, a.n_paths) > 65535) return hipErrorInvalidValue;      // (grid.y)
+      return launch_walk<Walk::Replay>(a, st);
+    case Walk::Lineage:
+      if (a.stride < 1 || a.kind != VGPA_PATHS_POSTERIOR || !a.R_diag || !a.out || !a.pf_slots || a.pf_slot_rows < 1 || a.logw) return hipErrorInvalidValue;
+      if (!sample_lineages_fit(a.D, a.batch, a.n_paths)) return hipErrorInvalidValue;
+      return launch_walk<Walk::Lineage>(a, st);
   }
-  if (a.D <= kMaxLaneD || a.kind == VGPA_PATHS_POSTERIOR) return launch_posterior<false>(a, st);
-  if (a.model != VGPA_MODEL_L96) return hipErrorInvalidValue;
-  const size_t lds = (size_t)a.D * 64 * sizeof(double) * ((!a.R_diag || !a.x0) ? 2 : 1);
-  hipLaunchKernelGGL(k_sample_l96, dim3((unsigned)((lanes + 63) / 64)), dim3(64), lds, st, a);
-  return hipGetLastError();
+  return hipErrorInvalidValue;
 }
 
 }  // namespace vgpa

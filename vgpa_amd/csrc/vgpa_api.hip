@@ -4,6 +4,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -1537,7 +1538,7 @@ static int sample_paths(vgpa_ctx* c, int kind, const double* x, const double* x0
     if ((rc = grow(c, &c->d_sp_logw, &c->sp_logw_n, n_logw)) || (rc = grow(c, &c->d_sp_start, &c->sp_start_n, n_start))) return rc;
     a.logw = c->d_sp_logw; a.start = c->d_sp_start;
   }
-  LAUNCH_TRY(c, "sample paths launch", launch_sample_paths(a, c->stream));
+  LAUNCH_TRY(c, "sample paths launch", launch_sample_walk(logw ? Walk::Weighted : Walk::Plain, a, c->stream));
   if (out && (rc = download(c, out, c->d_sp_out, n_out))) return rc;
   if (logw && (rc = download(c, logw, c->d_sp_logw, n_logw))) return rc;
   if (logw && start && (rc = download(c, start, c->d_sp_start, n_start))) return rc;
@@ -1568,116 +1569,118 @@ int vgpa_sample_paths_weighted(vgpa_ctx* c, const double* x, const double* x0, i
 
 // The guided particle filter (see vgpa_hip.h): the weighted walk of vgpa_sample_paths_weighted cut at the observation
 // indices of the batch, the particles resident between the cuts, a resampling step behind every cut that is an observation of some problem.
-// with_stats: vgpa_particle_statistics -- the same walk, counters and resampling decisions, every slot's [3][D] row of
-// path statistics carried along its lineage; stats / mean: where the final rows and their weighted mean go.
-// moments set: vgpa_particle_moments -- behind the filter, whose ancestor history stays on the device, the descendant
-// weights, then the walk once more from the same counters (the stored ancestors in place of the resampling decisions) with the weighted
-// sums taken at every stride-th grid index; `state` is then what the replay arrived at.
-// paths set: vgpa_particle_paths -- behind the filter, whose ancestor history stays on the device, the final slots of
-// n_draw trajectories (final_slots, or drawn from the final weights), their slots in every stretch traced back through the ancestors, and
-// one launch of the lineage walk over the n_draw trajectories alone; slots_out: where the table goes.
-static int particle_run(vgpa_ctx* c, const double* x, const double* x0, int32_t n_paths, uint64_t seed, double ess_fraction,
-                        const double* prior_mu, const double* prior_tau, double* logw, double* state, double* ess, int32_t* resampled,
-                        int32_t* ancestors, double* clouds, bool with_stats, double* stats, double* mean, int32_t stride = 1,
-                        double* moments = nullptr, double* lineage_ess = nullptr, int32_t n_draw = 0, const int32_t* final_slots = nullptr,
-                        double* paths = nullptr, int32_t* slots_out = nullptr) {
-  if (!c) return VGPA_ERR_ARG;
-  if (!logw || !state) return fail(c, VGPA_ERR_ARG, "null argument");
-  if (stride < 1) return fail(c, VGPA_ERR_ARG, "stride must be at least 1 (stride = %d)", stride);
-  if (with_stats && !stats && !mean) return fail(c, VGPA_ERR_ARG, "at least one of stats and mean must be given");
-  if (n_paths < 1) return fail(c, VGPA_ERR_ARG, "n_paths must be at least 1 (n_paths = %d)", n_paths);
-  if (paths && final_slots)
-    for (size_t e = 0; e < (size_t)c->B * n_draw; e++)
-      if (final_slots[e] < 0 || final_slots[e] >= n_paths)
-        return fail(c, VGPA_ERR_ARG, "problem %zu: final slot %d of trajectory %zu does not lie in [0, %d)", e / n_draw, final_slots[e], e % n_draw, n_paths);
-  if (!(ess_fraction >= 0.0 && ess_fraction <= 1.0)) return fail(c, VGPA_ERR_ARG, "ess_fraction must lie in [0, 1] (ess_fraction = %g)", ess_fraction);
-  if ((prior_mu == nullptr) != (prior_tau == nullptr)) return fail(c, VGPA_ERR_ARG, "the prior is a mean and a covariance: both or neither");
-  if (c->cfg.model == VGPA_MODEL_NONE) return fail(c, VGPA_ERR_ARG, "context has no stochastic model: no model SDE to weigh the particles against");
-  if (!c->full) return fail(c, VGPA_ERR_STATE, "context was created without m0/s0/observations (ODE-only)");
-  const int D = c->D, B = c->B, M = c->M, Np = c->Np, M1 = M > 0 ? M : 1;
-  if (moments && D <= kMaxSmallD) {      // the launch limits of the replay and of the final sum, before any work: grid.y of the segments, grid.x of the sum
-    if (sample_segment_blocks(D, n_paths) > 65535)
-      return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing moments are built for at most %d particles per problem at D = %d (n_paths = %d)",
-                  65535 * (D <= kMaxLaneD ? 256 : 64), D, n_paths);
-    if (((size_t)B * ((size_t)((Np - 1) / stride + 1) * 2 * D) + 255) / 256 > 0x7fffffffu)
-      return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing moments are built for at most 2^39 entries (batch %d, %d kept grid indices, D = %d): use a larger stride",
-                  B, (Np - 1) / stride + 1, D);
+// ParticleRequest: what one of the four entry points wants from it and where the results go (nullptr: not wanted).
+struct ParticleRequest {
+  const double* x; const double* x0; int32_t n_paths; uint64_t seed; double ess_fraction; const double* prior_mu; const double* prior_tau;
+  double* logw; double* state; double* ess; int32_t* resampled;      // (up to here: what every entry point has, filled in this order)
+  int32_t* ancestors; double* clouds;                                // vgpa_particle_filter: the histories
+  bool with_stats; double* stats; double* mean;                      // vgpa_particle_statistics: the final rows, their weighted mean
+  int32_t stride = 1;                                                // of the grid indices the two smoothers keep
+  double* moments; double* lineage_ess;                              // vgpa_particle_moments
+  int32_t n_draw; const int32_t* final_slots; double* paths; int32_t* slots_out;      // vgpa_particle_paths; slots_out: where the table goes
+};
+
+// One run: the filter, then what the request puts behind it.  The passes share the kernels' arguments, the cuts and where the particles are.
+struct ParticleRun {
+  vgpa_ctx* c; const ParticleRequest& q;
+  SampleArgs a; PfArgs f;              // of the filter's segments; of the start and the steps between the segments
+  std::vector<char> is_obs;            // [Np] the grid index is an observation of some problem
+  std::vector<int> count;              // [B] each problem's own observation count
+  double* cur; double* other;          // the particles: where they are, where the next step puts them
+  double* st_cur; double* st_other;    // ... and their rows of path statistics (with_stats)
+  int n_keep, rows, slot_rows, n_blocks; size_t mom_len, n_table, n_traj;
+
+  // For each cut -- an observation index of some problem, and the last grid index --: the segment launch up to it, then, at an
+  // observation, the step between two segments (from cur to other), and the particle buffers swap.
+  int cuts(Walk walk, const char* what, SampleArgs& s, const char* step_what, const std::function<hipError_t(int)>& step) {
+    int prev = 0;
+    for (int k = 0; k < c->Np; k++) {
+      if (!is_obs[k] && k != c->Np - 1) continue;
+      s.k_begin = prev; s.k_end = k; s.pf_x = cur;
+      hipError_t e = launch_sample_walk(walk, s, c->stream);
+      if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "%s failed: %s", what, hipGetErrorString(e));
+      s.seg_first = 0; prev = k;
+      if (!is_obs[k]) continue;
+      if ((e = step(k)) != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "%s failed: %s", step_what, hipGetErrorString(e));
+      std::swap(cur, other);
+    }
+    return VGPA_OK;
   }
-  const size_t n_traj = (size_t)B * (size_t)n_draw * ((size_t)((Np - 1) / stride + 1) * D);      // (used behind the check below only)
-  if (paths && D <= kMaxSmallD) {        // the launch limits of the lineage walk and the size of its result, before any work
-    if (!sample_lineages_fit(D, B, n_draw))
-      return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing trajectories are built for at most %d per problem at D = %d (n_draw = %d)", 65535 * 64, D, n_draw);
-    if ((double)B * (double)n_draw * (double)((Np - 1) / stride + 1) * (double)D > 34359738368.0)
-      return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing trajectories are built for at most 2^35 entries (batch %d, %d trajectories, %d kept grid indices, D = %d): use a larger stride",
-                  B, n_draw, (Np - 1) / stride + 1, D);
+
+  // The arguments of the kernels, the buffers of d_pf[] the request needs, the prior, the cuts
+  int setup() {
+    const int D = c->D, B = c->B, M = c->M, M1 = M > 0 ? M : 1;
+    int rc;
+    if ((rc = sample_args(c, VGPA_PATHS_POSTERIOR, q.x, q.x0, q.n_paths, 1, q.seed, true, &a))) return rc;
+    const size_t n = (size_t)q.n_paths, BnD = (size_t)B * n * D, Bn = (size_t)B * n, BM = (size_t)B * M1;
+    const bool history = q.ancestors || q.moments || q.paths;
+    auto buf = [&](int which, size_t count) { return grow(c, &c->d_pf[which], &c->pf_n[which], count); };
+    auto ints = [](size_t count) { return (count + 1) / 2; };      // int32 entries in a buffer of doubles
+    if ((rc = buf(vgpa_ctx::PF_XA, BnD)) || (rc = buf(vgpa_ctx::PF_XB, BnD)) || (rc = buf(vgpa_ctx::PF_LW, Bn)) || (rc = buf(vgpa_ctx::PF_CUM, Bn)) ||
+        (rc = buf(vgpa_ctx::PF_ANC, ints(Bn))) || (rc = buf(vgpa_ctx::PF_ESS, BM)) || (rc = buf(vgpa_ctx::PF_FLAG, ints(BM)))) return rc;
+    if (history && (rc = buf(vgpa_ctx::PF_HANC, ints(BM * n)))) return rc;
+    n_keep = (c->Np - 1) / q.stride + 1; slot_rows = M + 1; rows = M1 + 1; n_blocks = sample_segment_blocks(D, q.n_paths);
+    n_table = (size_t)B * slot_rows * (size_t)q.n_draw; n_traj = (size_t)B * (size_t)q.n_draw * ((size_t)n_keep * D); mom_len = (size_t)n_keep * 2 * D;
+    if (q.paths && ((rc = buf(vgpa_ctx::PF_SLOTS, ints(n_table))) || (rc = grow(c, &c->d_sp_out, &c->sp_out_n, n_traj)))) return rc;
+    if (q.moments && ((rc = buf(vgpa_ctx::PF_WTAB, (size_t)B * rows * n)) || (rc = buf(vgpa_ctx::PF_LESS, (size_t)B * rows)) ||
+                      (rc = buf(vgpa_ctx::PF_PART, (size_t)B * n_blocks * mom_len)) || (rc = buf(vgpa_ctx::PF_MOM, (size_t)B * mom_len)))) return rc;
+    if (q.clouds && (rc = buf(vgpa_ctx::PF_CLOUDS, BM * n * D))) return rc;
+    if (q.with_stats && ((rc = buf(vgpa_ctx::PF_STA, 3 * BnD)) || (rc = buf(vgpa_ctx::PF_STB, 3 * BnD)) || (rc = buf(vgpa_ctx::PF_MEAN, (size_t)B * 3 * D)))) return rc;
+    f = PfArgs{};
+    f.D = D; f.batch = B; f.n_paths = q.n_paths; f.M = M1; f.seed = q.seed; f.ess_fraction = q.ess_fraction;
+    f.x0 = a.x0; f.m0 = a.m0; f.L0 = a.L0; f.m0_stride = a.m0_stride; f.L0_stride = a.L0_stride;
+    f.obs_const = a.obs_const; f.obs_const_v = a.obs_const_v; f.obs_const_scale = a.obs_const_scale;
+    f.obs_t = a.obs_t; f.obs_t_stride = a.obs_t_stride; f.n_obs = a.n_obs; f.n_obs_v = a.n_obs_v;
+    if (q.prior_mu && !q.x0) {
+      Rows<double> Lt;
+      bool lt_diag = true;
+      if ((rc = factor_rows(c, q.prior_tau, B, 1.0, "prior covariance", &c->d_pf[vgpa_ctx::PF_LT], &c->pf_n[vgpa_ctx::PF_LT], &Lt, &lt_diag))) return rc;
+      if ((rc = buf(vgpa_ctx::PF_MU, (size_t)B * D)) || (rc = upload(c, c->d_pf[vgpa_ctx::PF_MU], q.prior_mu, (size_t)B * D))) return rc;
+      f.mu0 = c->d_pf[vgpa_ctx::PF_MU]; f.Lt = c->d_pf[vgpa_ctx::PF_LT];
+    }
+    cur = c->d_pf[vgpa_ctx::PF_XA]; other = c->d_pf[vgpa_ctx::PF_XB];
+    st_cur = q.with_stats ? c->d_pf[vgpa_ctx::PF_STA] : nullptr; st_other = q.with_stats ? c->d_pf[vgpa_ctx::PF_STB] : nullptr;
+    f.x = cur; f.ws = other; f.lw = c->d_pf[vgpa_ctx::PF_LW]; f.cum = c->d_pf[vgpa_ctx::PF_CUM];
+    f.anc = reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_ANC]);
+    f.h_ess = c->d_pf[vgpa_ctx::PF_ESS]; f.h_flag = reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_FLAG]);
+    f.h_anc = history ? reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_HANC]) : nullptr;
+    f.h_clouds = q.clouds ? c->d_pf[vgpa_ctx::PF_CLOUDS] : nullptr;
+    // the cuts: the observation indices the kernels will see (each problem's own row and count in force), and the last grid index
+    is_obs.assign((size_t)c->Np, 0);
+    count.assign((size_t)B, M);
+    const bool own_t = c->in.obs_t.stride != 0;
+    for (int p = 0; p < B; p++) {
+      if (!c->h_nobs.empty()) count[p] = c->h_nobs[p];
+      const int64_t* t = own_t ? c->h_pp_obs_t.data() + (size_t)p * M : c->h_obs_t.data();
+      for (int m = 0; m < count[p]; m++) is_obs[(size_t)t[m]] = 1;
+    }
+    return VGPA_OK;
   }
-  SampleArgs a;
-  int rc;
-  if ((rc = sample_args(c, VGPA_PATHS_POSTERIOR, x, x0, n_paths, 1, seed, true, &a))) return rc;
-  const size_t n = (size_t)n_paths, BnD = (size_t)B * n * D, Bn = (size_t)B * n, BM = (size_t)B * M1;
-  auto buf = [&](int which, size_t count) { return grow(c, &c->d_pf[which], &c->pf_n[which], count); };
-  auto ints = [](size_t count) { return (count + 1) / 2; };      // int32 entries in a buffer of doubles
-  if ((rc = buf(vgpa_ctx::PF_XA, BnD)) || (rc = buf(vgpa_ctx::PF_XB, BnD)) || (rc = buf(vgpa_ctx::PF_LW, Bn)) || (rc = buf(vgpa_ctx::PF_CUM, Bn)) ||
-      (rc = buf(vgpa_ctx::PF_ANC, ints(Bn))) || (rc = buf(vgpa_ctx::PF_ESS, BM)) || (rc = buf(vgpa_ctx::PF_FLAG, ints(BM)))) return rc;
-  if ((ancestors || moments || paths) && (rc = buf(vgpa_ctx::PF_HANC, ints(BM * n)))) return rc;
-  const int slot_rows = M + 1;
-  const size_t n_table = (size_t)B * slot_rows * (size_t)n_draw;
-  if (paths && ((rc = buf(vgpa_ctx::PF_SLOTS, ints(n_table))) || (rc = grow(c, &c->d_sp_out, &c->sp_out_n, n_traj)))) return rc;
-  const int rows = M1 + 1, n_blocks = sample_segment_blocks(D, n_paths);
-  const size_t mom_len = (size_t)((Np - 1) / stride + 1) * 2 * D;
-  if (moments && ((rc = buf(vgpa_ctx::PF_WTAB, (size_t)B * rows * n)) || (rc = buf(vgpa_ctx::PF_LESS, (size_t)B * rows)) ||
-                  (rc = buf(vgpa_ctx::PF_PART, (size_t)B * n_blocks * mom_len)) || (rc = buf(vgpa_ctx::PF_MOM, (size_t)B * mom_len)))) return rc;
-  if (clouds && (rc = buf(vgpa_ctx::PF_CLOUDS, BM * n * D))) return rc;
-  if (with_stats && ((rc = buf(vgpa_ctx::PF_STA, 3 * BnD)) || (rc = buf(vgpa_ctx::PF_STB, 3 * BnD)) || (rc = buf(vgpa_ctx::PF_MEAN, (size_t)B * 3 * D)))) return rc;
-  PfArgs f{};
-  f.D = D; f.batch = B; f.n_paths = n_paths; f.M = M1; f.seed = seed; f.ess_fraction = ess_fraction;
-  f.x0 = a.x0; f.m0 = a.m0; f.L0 = a.L0; f.m0_stride = a.m0_stride; f.L0_stride = a.L0_stride;
-  f.obs_const = a.obs_const; f.obs_const_v = a.obs_const_v; f.obs_const_scale = a.obs_const_scale;
-  f.obs_t = a.obs_t; f.obs_t_stride = a.obs_t_stride; f.n_obs = a.n_obs; f.n_obs_v = a.n_obs_v;
-  if (prior_mu && !x0) {
-    Rows<double> Lt;
-    bool lt_diag = true;
-    if ((rc = factor_rows(c, prior_tau, B, 1.0, "prior covariance", &c->d_pf[vgpa_ctx::PF_LT], &c->pf_n[vgpa_ctx::PF_LT], &Lt, &lt_diag))) return rc;
-    if ((rc = buf(vgpa_ctx::PF_MU, (size_t)B * D)) || (rc = upload(c, c->d_pf[vgpa_ctx::PF_MU], prior_mu, (size_t)B * D))) return rc;
-    f.mu0 = c->d_pf[vgpa_ctx::PF_MU]; f.Lt = c->d_pf[vgpa_ctx::PF_LT];
+
+  // The filter: the start, then the segments with the resampling step between them.  with_stats: the same walk, counters
+  // and resampling decisions, every slot's [3][D] row of path statistics carried along its lineage.
+  int filter() {
+    const size_t n = (size_t)q.n_paths, BM = (size_t)c->B * f.M;
+    HIP_TRY(c, hipMemsetAsync(f.h_ess, 0, BM * sizeof(double), c->stream));
+    HIP_TRY(c, hipMemsetAsync(f.h_flag, 0, BM * sizeof(int32_t), c->stream));
+    if (f.h_anc) HIP_TRY(c, hipMemsetAsync(f.h_anc, 0xff, BM * n * sizeof(int32_t), c->stream));      // (-1 beyond a problem's own count)
+    LAUNCH_TRY(c, "particle start launch", launch_pf_start(f, c->stream));
+    a.pf_lw = f.lw; a.seg_first = 1; a.pf_stats = st_cur;
+    if (q.with_stats) HIP_TRY(c, hipMemsetAsync(st_cur, 0, 3 * (size_t)c->B * n * c->D * sizeof(double), c->stream));
+    return cuts(q.with_stats ? Walk::SegmentStats : Walk::Segment, "particle segment launch", a, "particle resampling launch", [&](int k) {
+      f.k = k; f.last = k == c->Np - 1 ? 1 : 0; f.x_in = cur; f.x_out = other; f.st_in = st_cur; f.st_out = st_other;
+      std::swap(st_cur, st_other);      // (the next segment carries the rows the step is about to write)
+      a.pf_stats = st_cur;
+      return launch_pf_resample(f, c->stream);
+    });
   }
-  double* cur = c->d_pf[vgpa_ctx::PF_XA];
-  double* other = c->d_pf[vgpa_ctx::PF_XB];
-  f.x = cur; f.ws = other; f.lw = c->d_pf[vgpa_ctx::PF_LW]; f.cum = c->d_pf[vgpa_ctx::PF_CUM];
-  f.anc = reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_ANC]);
-  f.h_ess = c->d_pf[vgpa_ctx::PF_ESS]; f.h_flag = reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_FLAG]);
-  f.h_anc = (ancestors || moments || paths) ? reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_HANC]) : nullptr;
-  f.h_clouds = clouds ? c->d_pf[vgpa_ctx::PF_CLOUDS] : nullptr;
-  HIP_TRY(c, hipMemsetAsync(f.h_ess, 0, BM * sizeof(double), c->stream));
-  HIP_TRY(c, hipMemsetAsync(f.h_flag, 0, BM * sizeof(int32_t), c->stream));
-  if (f.h_anc) HIP_TRY(c, hipMemsetAsync(f.h_anc, 0xff, BM * n * sizeof(int32_t), c->stream));      // (-1 beyond a problem's own count)
-  LAUNCH_TRY(c, "particle start launch", launch_pf_start(f, c->stream));
-  // the cuts: the observation indices the kernels will see (each problem's own row and count in force), and the last grid index
-  std::vector<char> is_obs((size_t)Np, 0);
-  std::vector<int> count((size_t)B, M);
-  const bool own_t = c->in.obs_t.stride != 0;
-  for (int p = 0; p < B; p++) {
-    if (!c->h_nobs.empty()) count[p] = c->h_nobs[p];
-    const int64_t* t = own_t ? c->h_pp_obs_t.data() + (size_t)p * M : c->h_obs_t.data();
-    for (int m = 0; m < count[p]; m++) is_obs[(size_t)t[m]] = 1;
-  }
-  a.pf_lw = f.lw; a.seg_first = 1;
-  double* st_cur = with_stats ? c->d_pf[vgpa_ctx::PF_STA] : nullptr;
-  double* st_other = with_stats ? c->d_pf[vgpa_ctx::PF_STB] : nullptr;
-  if (with_stats) HIP_TRY(c, hipMemsetAsync(st_cur, 0, 3 * BnD * sizeof(double), c->stream));
-  int prev = 0;
-  for (int k = 0; k < Np; k++) {
-    if (!is_obs[k] && k != Np - 1) continue;
-    a.k_begin = prev; a.k_end = k; a.pf_x = cur; a.pf_stats = st_cur;
-    LAUNCH_TRY(c, "particle segment launch", launch_sample_segment(a, c->stream));
-    a.seg_first = 0; prev = k;
-    if (!is_obs[k]) continue;
-    f.k = k; f.last = k == Np - 1 ? 1 : 0; f.x_in = cur; f.x_out = other; f.st_in = st_cur; f.st_out = st_other;
-    LAUNCH_TRY(c, "particle resampling launch", launch_pf_resample(f, c->stream));
-    std::swap(cur, other);
-    std::swap(st_cur, st_other);
-  }
-  if (moments) {
+
+  // The smoothing moments, behind the filter, whose ancestor history stays on the device: the descendant weights, then
+  // the walk once more from the same counters (the stored ancestors in place of the resampling decisions) with the weighted sums taken at
+  // every stride-th grid index, their sum over the workgroups, the downloads; `state` is then what the replay arrived at.
+  int moments() {
+    const int B = c->B, M = c->M;
+    int rc;
     double* wtab = c->d_pf[vgpa_ctx::PF_WTAB];
     double* less = c->d_pf[vgpa_ctx::PF_LESS];
     HIP_TRY(c, hipMemsetAsync(less, 0, (size_t)B * rows * sizeof(double), c->stream));
@@ -1687,59 +1690,96 @@ static int particle_run(vgpa_ctx* c, const double* x, const double* x0, int32_t 
     PfArgs g = f;
     g.x = cur; g.ws = other; g.lw = c->d_pf[vgpa_ctx::PF_CUM]; g.st_in = nullptr; g.st_out = nullptr;
     LAUNCH_TRY(c, "particle start launch", launch_pf_start(g, c->stream));
-    SampleArgs r = a;
-    r.stride = stride; r.n_keep = (Np - 1) / stride + 1; r.seg_first = 1; r.pf_stats = nullptr;
-    r.pf_wtab = wtab; r.pf_part = c->d_pf[vgpa_ctx::PF_PART]; r.pf_rows = rows;
-    prev = 0;
-    for (int k = 0; k < Np; k++) {
-      if (!is_obs[k] && k != Np - 1) continue;
-      r.k_begin = prev; r.k_end = k; r.pf_x = cur;
-      LAUNCH_TRY(c, "replay segment launch", launch_sample_segment(r, c->stream));
-      r.seg_first = 0; prev = k;
-      if (!is_obs[k]) continue;
-      g.k = k; g.x_in = cur; g.x_out = other;
-      LAUNCH_TRY(c, "replay gather launch", launch_pf_gather(g, c->stream));
-      std::swap(cur, other);
-    }
-    LAUNCH_TRY(c, "moments sum launch", launch_pf_moments_sum(B, n_blocks, mom_len, r.pf_part, c->d_pf[vgpa_ctx::PF_MOM], c->stream));
-    if ((rc = download(c, moments, c->d_pf[vgpa_ctx::PF_MOM], (size_t)B * mom_len))) return rc;
-    if (lineage_ess)      // (the device's rows are M1 + 1 = M + 1, but for a context of capacity 0)
+    SampleArgs w = a;
+    w.stride = q.stride; w.n_keep = n_keep; w.seg_first = 1; w.pf_stats = nullptr;
+    w.pf_wtab = wtab; w.pf_part = c->d_pf[vgpa_ctx::PF_PART]; w.pf_rows = rows;
+    if ((rc = cuts(Walk::Replay, "replay segment launch", w, "replay gather launch", [&](int k) {
+          g.k = k; g.x_in = cur; g.x_out = other;
+          return launch_pf_gather(g, c->stream);
+        }))) return rc;
+    LAUNCH_TRY(c, "moments sum launch", launch_pf_moments_sum(B, n_blocks, mom_len, w.pf_part, c->d_pf[vgpa_ctx::PF_MOM], c->stream));
+    if ((rc = download(c, q.moments, c->d_pf[vgpa_ctx::PF_MOM], (size_t)B * mom_len))) return rc;
+    if (q.lineage_ess)      // (the device's rows are M1 + 1 = M + 1, but for a context of capacity 0)
       for (int p = 0; p < (rows == M + 1 ? 1 : B); p++)
-        if ((rc = download(c, lineage_ess + (size_t)p * (M + 1), less + (size_t)p * rows, rows == M + 1 ? (size_t)B * rows : (size_t)M + 1))) return rc;
+        if ((rc = download(c, q.lineage_ess + (size_t)p * (M + 1), less + (size_t)p * rows, rows == M + 1 ? (size_t)B * rows : (size_t)M + 1))) return rc;
+    return VGPA_OK;
   }
-  std::vector<int32_t> h_table;      // (given final slots: the table as it is uploaded, alive until the stream has been synchronised)
-  if (paths) {
+
+  // The smoothing trajectories, behind the filter, whose ancestor history stays on the device: the final slots of n_draw
+  // trajectories (final_slots, or drawn from the final weights), their slots in every stretch traced back through the ancestors, one
+  // launch of the lineage walk over the n_draw trajectories alone, the downloads.
+  int trajectories() {
+    const int B = c->B, n_draw = q.n_draw;
+    int rc;
     int32_t* table = reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_SLOTS]);
-    if (final_slots) {               // rows beyond a problem's own count: -1; row c: the caller's slots
-      h_table.assign(n_table, -1);
+    if (q.final_slots) {             // rows beyond a problem's own count: -1; row c: the caller's slots
+      std::vector<int32_t> h_table(n_table, -1);      // (the table as it is uploaded, alive until the stream has been synchronised)
       for (int p = 0; p < B; p++)
-        for (int m = 0; m < n_draw; m++) h_table[((size_t)p * slot_rows + count[p]) * n_draw + m] = final_slots[(size_t)p * n_draw + m];
+        for (int m = 0; m < n_draw; m++) h_table[((size_t)p * slot_rows + count[p]) * n_draw + m] = q.final_slots[(size_t)p * n_draw + m];
       if ((rc = upload(c, table, h_table.data(), n_table))) return rc;
       HIP_TRY(c, hipStreamSynchronize(c->stream));
     } else {
       HIP_TRY(c, hipMemsetAsync(table, 0xff, n_table * sizeof(int32_t), c->stream));
-      LAUNCH_TRY(c, "final slots launch", launch_pf_pick(f, Np, n_draw, slot_rows, table, c->stream));
+      LAUNCH_TRY(c, "final slots launch", launch_pf_pick(f, c->Np, n_draw, slot_rows, table, c->stream));
     }
     LAUNCH_TRY(c, "genealogy launch", launch_pf_trace(f, n_draw, slot_rows, table, c->stream));
-    SampleArgs r = a;                // the unweighted walk of n_draw lanes per problem from the same start, factors and counters
-    r.n_paths = n_draw; r.stride = stride; r.n_keep = (Np - 1) / stride + 1; r.out = c->d_sp_out;
-    r.pf_x = nullptr; r.pf_lw = nullptr; r.pf_stats = nullptr; r.pf_slots = table; r.pf_slot_rows = slot_rows;
-    LAUNCH_TRY(c, "lineage walk launch", launch_sample_lineages(r, c->stream));
-    if ((rc = download(c, paths, c->d_sp_out, n_traj))) return rc;
-    if (slots_out) HIP_TRY(c, hipMemcpyAsync(slots_out, table, n_table * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    SampleArgs w = a;                // the unweighted walk of n_draw lanes per problem from the same start, factors and counters
+    w.n_paths = n_draw; w.stride = q.stride; w.n_keep = n_keep; w.out = c->d_sp_out;
+    w.pf_x = nullptr; w.pf_lw = nullptr; w.pf_stats = nullptr; w.pf_slots = table; w.pf_slot_rows = slot_rows;
+    LAUNCH_TRY(c, "lineage walk launch", launch_sample_walk(Walk::Lineage, w, c->stream));
+    if ((rc = download(c, q.paths, c->d_sp_out, n_traj))) return rc;
+    if (q.slots_out) HIP_TRY(c, hipMemcpyAsync(q.slots_out, table, n_table * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    return VGPA_OK;
   }
-  if (with_stats && mean) {
-    LAUNCH_TRY(c, "path statistics mean launch", launch_pf_stats_mean(D, B, n_paths, f.lw, st_cur, c->d_pf[vgpa_ctx::PF_MEAN], c->stream));
-    if ((rc = download(c, mean, c->d_pf[vgpa_ctx::PF_MEAN], (size_t)B * 3 * D))) return rc;
+};
+
+static int particle_run(vgpa_ctx* c, const ParticleRequest& q) {
+  if (!c) return VGPA_ERR_ARG;
+  if (!q.logw || !q.state) return fail(c, VGPA_ERR_ARG, "null argument");
+  if (q.stride < 1) return fail(c, VGPA_ERR_ARG, "stride must be at least 1 (stride = %d)", q.stride);
+  if (q.with_stats && !q.stats && !q.mean) return fail(c, VGPA_ERR_ARG, "at least one of stats and mean must be given");
+  const int32_t n_paths = q.n_paths, n_draw = q.n_draw, stride = q.stride;
+  if (n_paths < 1) return fail(c, VGPA_ERR_ARG, "n_paths must be at least 1 (n_paths = %d)", n_paths);
+  if (q.paths && q.final_slots)
+    for (size_t e = 0; e < (size_t)c->B * n_draw; e++)
+      if (q.final_slots[e] < 0 || q.final_slots[e] >= n_paths)
+        return fail(c, VGPA_ERR_ARG, "problem %zu: final slot %d of trajectory %zu does not lie in [0, %d)", e / n_draw, q.final_slots[e], e % n_draw, n_paths);
+  if (!(q.ess_fraction >= 0.0 && q.ess_fraction <= 1.0)) return fail(c, VGPA_ERR_ARG, "ess_fraction must lie in [0, 1] (ess_fraction = %g)", q.ess_fraction);
+  if ((q.prior_mu == nullptr) != (q.prior_tau == nullptr)) return fail(c, VGPA_ERR_ARG, "the prior is a mean and a covariance: both or neither");
+  if (c->cfg.model == VGPA_MODEL_NONE) return fail(c, VGPA_ERR_ARG, "context has no stochastic model: no model SDE to weigh the particles against");
+  if (!c->full) return fail(c, VGPA_ERR_STATE, "context was created without m0/s0/observations (ODE-only)");
+  const int D = c->D, B = c->B, M = c->M, Np = c->Np;
+  if (q.moments && D <= kMaxSmallD) {      // the launch limits of the replay and of the final sum, before any work: grid.y of the segments, grid.x of the sum
+    if (sample_segment_blocks(D, n_paths) > 65535)
+      return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing moments are built for at most %d particles per problem at D = %d (n_paths = %d)",
+                  65535 * (D <= kMaxLaneD ? 256 : 64), D, n_paths);
+    if (((size_t)B * ((size_t)((Np - 1) / stride + 1) * 2 * D) + 255) / 256 > 0x7fffffffu)
+      return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing moments are built for at most 2^39 entries (batch %d, %d kept grid indices, D = %d): use a larger stride",
+                  B, (Np - 1) / stride + 1, D);
   }
-  if (with_stats && stats && (rc = download(c, stats, st_cur, 3 * BnD))) return rc;
-  if ((rc = download(c, logw, f.lw, Bn)) || (rc = download(c, state, cur, BnD))) return rc;
-  if (ess && (rc = download(c, ess, f.h_ess, (size_t)B * M))) return rc;
-  if (resampled && M > 0) HIP_TRY(c, hipMemcpyAsync(resampled, f.h_flag, (size_t)B * M * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  if (ancestors && M > 0) HIP_TRY(c, hipMemcpyAsync(ancestors, f.h_anc, (size_t)B * M * n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  if (clouds)      // (only the rows below a problem's own count: the rest of the caller's array stays as it is)
+  if (q.paths && D <= kMaxSmallD) {        // the launch limits of the lineage walk and the size of its result, before any work
+    if (!sample_lineages_fit(D, B, n_draw))
+      return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing trajectories are built for at most %d per problem at D = %d (n_draw = %d)", 65535 * 64, D, n_draw);
+    if ((double)B * (double)n_draw * (double)((Np - 1) / stride + 1) * (double)D > 34359738368.0)
+      return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing trajectories are built for at most 2^35 entries (batch %d, %d trajectories, %d kept grid indices, D = %d): use a larger stride",
+                  B, n_draw, (Np - 1) / stride + 1, D);
+  }
+  ParticleRun r{c, q};
+  int rc;
+  if ((rc = r.setup()) || (rc = r.filter()) || (q.moments && (rc = r.moments())) || (q.paths && (rc = r.trajectories()))) return rc;
+  const size_t n = (size_t)n_paths, BnD = (size_t)B * n * D;
+  if (q.with_stats && q.mean) {
+    LAUNCH_TRY(c, "path statistics mean launch", launch_pf_stats_mean(D, B, n_paths, r.f.lw, r.st_cur, c->d_pf[vgpa_ctx::PF_MEAN], c->stream));
+    if ((rc = download(c, q.mean, c->d_pf[vgpa_ctx::PF_MEAN], (size_t)B * 3 * D))) return rc;
+  }
+  if (q.with_stats && q.stats && (rc = download(c, q.stats, r.st_cur, 3 * BnD))) return rc;
+  if ((rc = download(c, q.logw, r.f.lw, (size_t)B * n)) || (rc = download(c, q.state, r.cur, BnD))) return rc;
+  if (q.ess && (rc = download(c, q.ess, r.f.h_ess, (size_t)B * M))) return rc;
+  if (q.resampled && M > 0) HIP_TRY(c, hipMemcpyAsync(q.resampled, r.f.h_flag, (size_t)B * M * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  if (q.ancestors && M > 0) HIP_TRY(c, hipMemcpyAsync(q.ancestors, r.f.h_anc, (size_t)B * M * n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  if (q.clouds)      // (only the rows below a problem's own count: the rest of the caller's array stays as it is)
     for (int p = 0; p < B; p++)
-      if (count[p] > 0 && (rc = download(c, clouds + (size_t)p * M * n * D, f.h_clouds + (size_t)p * M * n * D, (size_t)count[p] * n * D))) return rc;
+      if (r.count[p] > 0 && (rc = download(c, q.clouds + (size_t)p * M * n * D, r.f.h_clouds + (size_t)p * M * n * D, (size_t)r.count[p] * n * D))) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return VGPA_OK;
 }
@@ -1747,15 +1787,18 @@ static int particle_run(vgpa_ctx* c, const double* x, const double* x0, int32_t 
 int vgpa_particle_filter(vgpa_ctx* c, const double* x, const double* x0, int32_t n_paths, uint64_t seed, double ess_fraction,
                          const double* prior_mu, const double* prior_tau, double* logw, double* state, double* ess, int32_t* resampled,
                          int32_t* ancestors, double* clouds) {
-  return particle_run(c, x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled, ancestors, clouds, false, nullptr,
-                      nullptr);
+  ParticleRequest q{x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled};
+  q.ancestors = ancestors; q.clouds = clouds;
+  return particle_run(c, q);
 }
 
 // The path statistics of the particle filter's lineages (see vgpa_hip.h)
 int vgpa_particle_statistics(vgpa_ctx* c, const double* x, const double* x0, int32_t n_paths, uint64_t seed, double ess_fraction,
                              const double* prior_mu, const double* prior_tau, double* logw, double* state, double* stats, double* mean,
                              double* ess, int32_t* resampled) {
-  return particle_run(c, x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled, nullptr, nullptr, true, stats, mean);
+  ParticleRequest q{x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled};
+  q.with_stats = true; q.stats = stats; q.mean = mean;
+  return particle_run(c, q);
 }
 
 // The smoothing moments on the grid under the particles' genealogy (see vgpa_hip.h)
@@ -1764,8 +1807,9 @@ int vgpa_particle_moments(vgpa_ctx* c, const double* x, const double* x0, int32_
                           double* ess, int32_t* resampled) {
   if (!c) return VGPA_ERR_ARG;
   if (!moments) return fail(c, VGPA_ERR_ARG, "null argument");
-  return particle_run(c, x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled, nullptr, nullptr, false, nullptr,
-                      nullptr, stride, moments, lineage_ess);
+  ParticleRequest q{x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled};
+  q.stride = stride; q.moments = moments; q.lineage_ess = lineage_ess;
+  return particle_run(c, q);
 }
 
 // Whole smoothing trajectories on the grid from the particles' genealogy (see vgpa_hip.h)
@@ -1775,8 +1819,9 @@ int vgpa_particle_paths(vgpa_ctx* c, const double* x, const double* x0, int32_t 
   if (!c) return VGPA_ERR_ARG;
   if (!paths) return fail(c, VGPA_ERR_ARG, "null argument");
   if (n_draw < 1) return fail(c, VGPA_ERR_ARG, "n_draw must be at least 1 (n_draw = %d)", n_draw);
-  return particle_run(c, x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled, nullptr, nullptr, false, nullptr,
-                      nullptr, stride, nullptr, nullptr, n_draw, final_slots, paths, slots);
+  ParticleRequest q{x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled};
+  q.stride = stride; q.n_draw = n_draw; q.final_slots = final_slots; q.paths = paths; q.slots_out = slots;
+  return particle_run(c, q);
 }
 
 int vgpa_fetch(vgpa_ctx* c, int which, double* out) {

@@ -222,7 +222,9 @@ struct ReduceArgs {
   const double* div_v;      // [B] per-problem div (1-D models: sigma_p), or nullptr
 };
 
-// Euler-Maruyama sample paths (sample.hip; vgpa_sample_paths): x_k = x_{k-1} + dt drift_{k-1}(x_{k-1}) + R xi_k on the context's grid
+// Euler-Maruyama sample paths (sample.hip): x_k = x_{k-1} + dt drift_{k-1}(x_{k-1}) + R xi_k on the context's grid.  The six things a launch
+// can do with them (the table at the top of sample.hip); the host names one at every launch_sample_walk, and SampleArgs says what each reads
+enum class Walk { Plain, Weighted, Segment, SegmentStats, Replay, Lineage };
 struct SampleArgs {
   int kind, model, D, Np, batch, n_paths, stride, n_keep;
   double dt;
@@ -241,9 +243,9 @@ struct SampleArgs {
   size_t m0_stride, L0_stride;
   double* out;              // [B][n_paths][n_keep][D]
   // importance weights of the posterior paths against the model SDE (vgpa_sample_paths_weighted), last so that the offsets
-  // above stay where they were.  logw set: the weighted instantiations run (posterior kind, diagonal R, theta / theta_v set), `out` may be
-  // nullptr (no path is stored), and every path's x_0 goes to `start`
-  double* logw;             // [B][n_paths][2]: the path term, the observation term; or nullptr
+  // above stay where they were.  Walk::Weighted reads them (posterior kind, diagonal R, theta / theta_v set): `out` may be nullptr (no
+  // path is stored), and every path's x_0 goes to `start`
+  double* logw;             // [B][n_paths][2]: the path term, the observation term; nullptr for every other walk
   double* start;            // [B][n_paths][D]
   const int64_t* obs_t;     // [M] grid indices, strictly increasing ([B][M] with obs_t_stride = M), as ObsArgs has them
   const double* obs_y;      // [M][D] ([B][M][D] with obs_y_stride = M*D)
@@ -255,31 +257,31 @@ struct SampleArgs {
   double obs_const;         // the additive constant of E_obs as ObsArgs has it ...
   const double* obs_const_v;   // ... [B] instead of obs_const, or nullptr
   double obs_const_scale;   // ... and the factor E_obs gives it: 1/2 (n-D), 1 (1-D models, whose constant is halved already)
-  // a segment of the weighted walk (vgpa_particle_filter; launch_sample_segment): the grid steps k_begin < k <= k_end from
-  // and to pf_x, the path and observation increments added to pf_lw.  The observation cursor starts at 0 in the first segment (an
-  // observation at grid index 0 applies to the start), else behind k_begin.  x0 / m0 / L0 / out / logw / start are not read.
+  // Walk::Segment, SegmentStats and Replay (vgpa_particle_filter): the grid steps k_begin < k <= k_end of the weighted
+  // walk from and to pf_x, the path and observation increments added to pf_lw.  The observation cursor starts at 0 in the first segment
+  // (an observation at grid index 0 applies to the start), else behind k_begin.  x0 / m0 / L0 / out / logw / start are not read.
   int seg_first, k_begin, k_end;
   double* pf_x;             // [B][n_paths][D]
   double* pf_lw;            // [B][n_paths]
-  // the path statistics of a lineage (vgpa_particle_statistics): set, the ST instantiations run and add every step's
+  // the path statistics of a lineage (vgpa_particle_statistics): Walk::SegmentStats adds every step's
   // Q_j += r_j^2 / dt, G_j += phi_j r_j, H_j += dt phi_j^2 (r = dt (g - f) + eta, phi_j = df_j / dtheta_a(j) at x_{k-1}) to the slot's row
-  double* pf_stats;         // [B][n_paths][3][D], or nullptr
-  // the replay of vgpa_particle_moments: pf_wtab set, the MO instantiations run -- the walk of the segment without its
-  // weight sums (pf_lw is not touched); at every kept grid index k = 0 mod stride of the segment (k = 0: the first segment) workgroup
-  // (p, blk) stores sum_i W_i x_i(k) and sum_i W_i x_i(k)^2 over its own slots, W = the row of pf_wtab of the problem's stretch
-  const double* pf_wtab;    // [B][pf_rows][n_paths] descendant weights, or nullptr
+  double* pf_stats;         // [B][n_paths][3][D]; nullptr for every other walk
+  // the replay of vgpa_particle_moments: Walk::Replay is the walk of the segment without its weight sums (pf_lw is
+  // not touched); at every kept grid index k = 0 mod stride of the segment (k = 0: the first segment) workgroup (p, blk) stores
+  // sum_i W_i x_i(k) and sum_i W_i x_i(k)^2 over its own slots, W = the row of pf_wtab of the problem's stretch
+  const double* pf_wtab;    // [B][pf_rows][n_paths] descendant weights; nullptr for every other walk
   double* pf_part;          // [B][sample_segment_blocks()][n_keep][2][D]
   int pf_rows;
-  // the lineage walk of vgpa_particle_paths (launch_sample_lineages): the unweighted posterior walk of n_paths = K lanes
+  // Walk::Lineage (vgpa_particle_paths): the unweighted posterior walk of n_paths = K lanes
   // per problem, stored as vgpa_sample_paths stores it, in which lane m draws with the counter word pf_slots[p][j][m] while it is in
   // stretch j of its problem's own observation row (obs_t / n_obs as above): row 0 for the start, the next row behind every observation
-  const int32_t* pf_slots;  // [B][pf_slot_rows][n_paths], or nullptr
+  const int32_t* pf_slots;  // [B][pf_slot_rows][n_paths]
   int pf_slot_rows;
 };
-hipError_t launch_sample_paths(const SampleArgs& a, hipStream_t st);
-hipError_t launch_sample_segment(const SampleArgs& a, hipStream_t st);
-hipError_t launch_sample_lineages(const SampleArgs& a, hipStream_t st);
-// workgroups per problem of a segment launch: the blocks of the MO instantiations' partial sums
+// hipErrorInvalidValue where a field the walk reads is missing or out of range, where a field that belongs to another walk is set, and for
+// D = 2 in every walk but Plain (no stochastic model has D = 2)
+hipError_t launch_sample_walk(Walk w, const SampleArgs& a, hipStream_t st);
+// workgroups per problem of a segment launch: the blocks of the replay's partial sums
 int sample_segment_blocks(int D, int n_paths);
 
 // the start and the resampling step of the particle filter (sample.hip: k_pf_start, k_pf_resample)
@@ -322,7 +324,7 @@ hipError_t launch_pf_gather(const PfArgs& a, hipStream_t st);
 // vgpa_particle_paths (sample.hip: k_pf_pick, k_pf_trace).  table [B][rows][K] int32, rows > every problem's observation count c.  pick
 // reads lw, seed and the counts and overwrites cum: row c gets the final slots of K trajectories, by systematic resampling from the final
 // weights with the uniform of Philox counter (Np, 0, p, 0xffffffff).  trace reads row c, h_flag, h_anc and M and writes rows c-1 .. 0: the
-// slot each trajectory sat in during every stretch.  sample_lineages_fit: launch_sample_lineages can launch K lanes per problem
+// slot each trajectory sat in during every stretch.  sample_lineages_fit: Walk::Lineage can be launched with K lanes per problem
 hipError_t launch_pf_pick(const PfArgs& a, int Np, int K, int rows, int32_t* table, hipStream_t st);
 hipError_t launch_pf_trace(const PfArgs& a, int K, int rows, int32_t* table, hipStream_t st);
 bool sample_lineages_fit(int D, int batch, int K);
