@@ -355,6 +355,45 @@ int vgpa_particle_paths(vgpa_ctx* ctx, const double* x_or_null, const double* x0
                         const double* prior_mu_or_null, const double* prior_tau_or_null, double* logw, double* state, double* paths,
                         int32_t* slots_or_null, double* ess_or_null, int32_t* resampled_or_null);
 
+/* The particle forecast: a weighted cloud carried past the window under the model SDE, with its mean and spread on the
+ * forecast grid and a handful of member trajectories; the cloud never leaves the device between the filter and the forecast.
+ * Per problem p: n = n_paths particles x_i with log-weights lw_i at the absolute grid index k0.
+ *   forecast steps   for h = 1 .. H (= horizon):  x_i <- (x_i + dt f(x_i; theta_p)) + R_p,jj xi_j,  R_p = chol_lower(Sigma_p dt), Sigma diagonal.
+ *               f is the model drift of vgpa_sample_paths(VGPA_PATHS_MODEL) (Lorenz-96 circular on the particle's own state above D = 4),
+ *               theta_p and Sigma_p the ones in force; the normals come from Philox counter (k0 + h, i, p, j) under the seed's key: the
+ *               samplers' generator, the absolute grid index continuing past the window; the association is the one shown.  No
+ *               observations, no resampling: the weights do not change
+ *   kept steps  h = 0, stride, 2 stride, ... <= H: h_keep = H / stride + 1.  H = 0 is legal
+ *   moments          host, [batch][h_keep][2][D]: M1 = sum_i W_i x_i and M2 = sum_i W_i x_i^2 at the kept steps, W_i = w_i / sum w with
+ *                    w_i = exp(lw_i - max lw).  The raw moments, as in vgpa_particle_moments.  Two calls with the same arguments give the
+ *                    same bits
+ *   members_or_null  host, [batch][K][h_keep][D], K = n_draw >= 0: the trajectories of the slots s[m] in the layout of vgpa_sample_paths.
+ *                    s = final_slots_or_null (host int32, [batch][K], each in [0, n)), or drawn by the rule of vgpa_particle_paths:
+ *                    systematic resampling from lw with U from counter (k0 + 1, 0, p, 0xffffffff).  Member m draws with the counter word
+ *                    of its slot: it is bit for bit what slot s[m] of the whole cloud does.  Behind the filter (k0 = Np-1) with the same
+ *                    arguments, member m at h = 0 is bit for bit the last point of trajectory m of vgpa_particle_paths, which the
+ *                    forecast continues
+ *   slots_or_null    host int32, [batch][K]: s[m]
+ *   state_end_or_null  host, [batch][n][D]: the cloud at k0 + H
+ *   the cloud   cloud_or_null NULL: the filter of vgpa_particle_filter runs unchanged on x_or_null, x0_or_null, n_paths, seed, ess_fraction
+ *               and the prior; logw, state, ess_or_null, resampled_or_null are bit-identical to that entry point's; its final particles
+ *               are taken from the device buffer they are in, and k0 = Np-1.  With x NULL the cached state is read and not written.
+ *               Otherwise cloud_or_null (host, [batch][n][D]), cloud_logw_or_null (host, [batch][n]; NULL: equal weights) and
+ *               index0 >= 0 (= k0) give them: no filter runs; x, x0, ess_fraction, the prior, logw, state, ess and resampled are not
+ *               touched, no cached evaluation is needed, and the context needs a stochastic model with theta, Sigma and dt only.
+ *               A forecast of H steps equals one of H1 steps followed by one of H - H1 steps from its state_end with index0 + H1: the
+ *               states are equal bit for bit
+ * Errors: VGPA_ERR_ARG for a context without a stochastic model, horizon < 0, stride < 1, n_paths < 1, a NULL moments, n_draw < 0,
+ * index0 < 0, a given slot outside [0, n), or k0 + H (slots drawn: k0 + 1) beyond 2^31 - 1; VGPA_ERR_UNSUPPORTED, before any work, for
+ * D > 64, a dense Sigma in force, more than 65535 workgroups per problem (256 particles or members each at D <= 4, 64 above), more than
+ * 2^39 - 256 entries of moments or more than 2^35 entries of members; the filter's errors as in vgpa_particle_filter. */
+int vgpa_particle_forecast(vgpa_ctx* ctx, const double* x_or_null, const double* x0_or_null, int32_t n_paths, uint64_t seed,
+                           double ess_fraction, const double* prior_mu_or_null, const double* prior_tau_or_null,
+                           const double* cloud_or_null, const double* cloud_logw_or_null, int32_t index0, int32_t horizon, int32_t stride,
+                           int32_t n_draw, const int32_t* final_slots_or_null, double* logw, double* state, double* ess_or_null,
+                           int32_t* resampled_or_null, double* moments, double* members_or_null, int32_t* slots_or_null,
+                           double* state_end_or_null);
+
 /* device-pointer variants (x, g on the context's device; f written to HOST after a sync) ------ */
 int vgpa_sweep_dev(vgpa_ctx* ctx, const double* x_dev, double* f_host, double* g_dev);
 int vgpa_free_energy_dev(vgpa_ctx* ctx, const double* x_dev, double* f_host);

@@ -1,12 +1,13 @@
 """
 Time of Context.sample_paths (vgpa_sample_paths), Context.sample_paths_weighted (vgpa_sample_paths_weighted), Context.particle_filter
-(vgpa_particle_filter), Context.particle_statistics (vgpa_particle_statistics), Context.particle_moments (vgpa_particle_moments) and
-Context.particle_paths (vgpa_particle_paths) on their jobs, one JSON line.
+(vgpa_particle_filter), Context.particle_statistics (vgpa_particle_statistics), Context.particle_moments (vgpa_particle_moments),
+Context.particle_paths (vgpa_particle_paths) and Context.particle_forecast (vgpa_particle_forecast) on their jobs, one JSON line.
 
     python tools/bench_sample_paths.py [--rounds 3] [--calls 5] [--jobs a,b,c,aw,aw0,bw,bw0,af64_0,af64_5,af1024_0,af1024_5,bf64_0,...]
     python tools/bench_sample_paths.py --statistics [--filter-problems 4096]      # the as* and bs* jobs
     python tools/bench_sample_paths.py --moments [--filter-problems 4096]         # the am* and bm* jobs
     python tools/bench_sample_paths.py --paths [--filter-problems 4096] [--paths-strides 1,10]      # the ap* and bp* jobs, once per stride
+    python tools/bench_sample_paths.py --forecast [--forecast-problems 512] [--forecast-particles 4096] [--forecast-horizon 1000]
 
   a   posterior kind, Lorenz-96, D = 40, Np = 1001, B = 512:   64 paths per problem, stride 100
   b   posterior kind, Lorenz-63, Np = 1001, B = 65536:          1 path per problem,  stride 100
@@ -30,6 +31,14 @@ Context.particle_paths (vgpa_particle_paths) on their jobs, one JSON line.
              n = 64 or 1024 particles per problem, ess_fraction 0.5, K = 16 or 64 trajectories per problem drawn from the final weights,
              and particle_filter with the same arguments, the two calls alternating inside every round: both times, their ratio, the
              trajectories copied and how many different paths the K trajectories have in the first and in the last stretch
+
+  --forecast   particle_forecast from a given cloud on a bare Lorenz-96 context (a model, theta, Sigma and dt: nothing evaluated), D = 40,
+             B = 512, n = 4096 equally weighted particles, H = 1000 steps, no members, once with stride H (the sums at h = 0 and H alone)
+             and once with stride 1 (the sums at every step), and beside them the model-kind sampler on the same lanes -- sample_paths(
+             "model", n, stride H, x0) on a grid of H + 1 points: the same steps without a reduction.  The three calls alternate inside
+             every round; the excess of stride 1 over the sampler is what the reductions cost.  up_mb / d2h_mb: what each call copies.  (dt is
+             a tenth of the other jobs': the explicit Euler step of Lorenz-96 at dt = 0.01 sends a few of 2 million noisy paths to
+             infinity within 1000 steps, and the time of a step does not depend on dt)
 
 The posterior jobs read the x a free_energy_dev left cached (x=None: nothing is uploaded); every job draws its start from (m0, S0).  A call
 is timed with a pair of device events on the context's stream around it -- the host work of the call (the Cholesky factors), the kernel and
@@ -87,6 +96,51 @@ def numpy_ms(p0, x_row, d, kind, n_paths, stride, n_problems, B):
     for k in range(n_problems):
         sample_paths_numpy(q, kind, x_row, None, n_paths, stride, 1, index=k)
     return (time.perf_counter() - t0) * 1e3 / n_problems * B
+
+
+def run_forecast(B, n, horizon, rounds, calls):
+    import vgpa_amd as va
+    d = 40
+    rng = np.random.default_rng(1)
+    c = va.Context("L96", "euler", d, horizon + 1, 0.1 * DT, sigma=np.diag(3.0 + rng.random(d)), theta=[8.0], batch=B)
+    from bench_problem_batch import StreamTimer
+    tm = StreamTimer(c)
+    x0 = 8.0 + rng.standard_normal((B, d))
+    cloud = np.ascontiguousarray(x0[:, None, :] + 0.5 * rng.standard_normal((B, n, d)))
+    calls_of = {"sampler": lambda: c.sample_paths("model", n, 1, stride=horizon, x0=x0),
+                "forecast_stride_h": lambda: c.particle_forecast(horizon, seed=1, stride=horizon, cloud=cloud, index0=0),
+                "forecast_stride_1": lambda: c.particle_forecast(horizon, seed=1, stride=1, cloud=cloud, index0=0)}
+    res0 = {k: f() for k, f in calls_of.items()}      # warm-up (first-use allocations)
+    far, near = res0["forecast_stride_h"], res0["forecast_stride_1"]
+    assert res0["sampler"].shape == (B, n, 2, d) and np.all(np.isfinite(res0["sampler"]))
+    assert near["moments"].shape == (B, horizon + 1, 2, d) and np.all(np.isfinite(near["moments"]))
+    assert np.array_equal(far["state_end"], near["state_end"]) and np.array_equal(far["moments"], near["moments"][:, ::horizon])
+    assert np.allclose(near["moments"][:, 0, 0], cloud.mean(axis=1), rtol=1e-12, atol=0.0)
+    spread = float(np.median(np.sqrt(np.maximum(near["moments"][:, -1, 1] - near["moments"][:, -1, 0] ** 2, 0.0))))
+    del res0, far, near
+    per_round = {k: [] for k in calls_of}
+    for _ in range(rounds):
+        ms = {k: [] for k in calls_of}
+        for _ in range(calls):
+            for k, f in calls_of.items():
+                ms[k].append(tm.ms(f))
+        for k in calls_of:
+            per_round[k].append(float(np.median(ms[k])))
+    med = {k: float(np.median(v)) for k, v in per_round.items()}
+    tm.close()
+    c.close()
+    out = {"job": "forecast", "model": "L96", "D": d, "B": B, "kind": "forecast", "n_paths": n, "horizon": horizon}
+    for k in calls_of:
+        out[k + "_ms_per_call"] = round(med[k], 3)
+        out[k + "_rounds_ms"] = [round(v, 3) for v in per_round[k]]
+    cloud_mb = 8.0 * B * n * d / 1e6
+    out.update(stride_1_over_sampler=round(med["forecast_stride_1"] / med["sampler"], 4),
+               stride_h_over_sampler=round(med["forecast_stride_h"] / med["sampler"], 4), median_spread_at_h=round(spread, 4),
+               sampler_d2h_mb=round(2 * cloud_mb, 1), forecast_up_mb=round(cloud_mb, 1),
+               forecast_stride_h_d2h_mb=round(cloud_mb + 8.0 * B * 2 * 2 * d / 1e6, 1),
+               forecast_stride_1_d2h_mb=round(cloud_mb + 8.0 * B * (horizon + 1) * 2 * d / 1e6, 1),
+               partial_buffer_stride_1_mb=round(8.0 * B * ((n + 63) // 64) * (horizon + 1) * 2 * d / 1e6, 1))
+    return out
 
 
 def run(job, rounds, calls, numpy_problems, cache, filter_problems=0, paths_stride=1):
@@ -244,7 +298,16 @@ def main():
     ap.add_argument("--moments", action="store_true", help="run the am* and bm* jobs (particle_moments beside particle_filter)")
     ap.add_argument("--paths", action="store_true", help="run the ap* and bp* jobs (particle_paths beside particle_filter)")
     ap.add_argument("--paths-strides", default="1,10", help="strides of the ap* and bp* jobs: each job runs once per stride")
+    ap.add_argument("--forecast", action="store_true", help="run the forecast job (particle_forecast from a given cloud beside the model-kind sampler)")
+    ap.add_argument("--forecast-problems", type=int, default=512)
+    ap.add_argument("--forecast-particles", type=int, default=4096)
+    ap.add_argument("--forecast-horizon", type=int, default=1000)
     args = ap.parse_args()
+    if args.forecast:
+        out = {"tool": "bench_sample_paths", "tree": tree(), "unit": "ms per call (device events around the call)",
+               "jobs": [run_forecast(args.forecast_problems, args.forecast_particles, args.forecast_horizon, args.rounds, args.calls)]}
+        print(json.dumps(out), flush=True)
+        return
     if args.statistics:
         args.jobs = ",".join(sorted(STATS))
     if args.moments:

@@ -36,7 +36,7 @@ BWD_IDS = {"none": 0, "psi": 1, "q": 2}
 SYMBOLS = ["vgpa_create", "vgpa_destroy", "vgpa_last_error", "vgpa_abi_version", "vgpa_device_count",
            "vgpa_synchronize", "vgpa_stream", "vgpa_solve_fwd", "vgpa_solve_bwd", "vgpa_energy",
            "vgpa_obs_energy", "vgpa_free_energy", "vgpa_gradient", "vgpa_sweep", "vgpa_energy_parts",
-           "vgpa_fetch", "vgpa_theta_gradient", "vgpa_sample_paths", "vgpa_sample_paths_weighted", "vgpa_particle_filter", "vgpa_particle_statistics", "vgpa_particle_moments", "vgpa_particle_paths", "vgpa_sweep_dev", "vgpa_free_energy_dev", "vgpa_sweep_enqueue", "vgpa_fetch_f",
+           "vgpa_fetch", "vgpa_theta_gradient", "vgpa_sample_paths", "vgpa_sample_paths_weighted", "vgpa_particle_filter", "vgpa_particle_statistics", "vgpa_particle_moments", "vgpa_particle_paths", "vgpa_particle_forecast", "vgpa_sweep_dev", "vgpa_free_energy_dev", "vgpa_sweep_enqueue", "vgpa_fetch_f",
            "vgpa_dev_alloc", "vgpa_dev_free", "vgpa_memcpy_h2d", "vgpa_memcpy_d2h",
            "vgpa_profile_begin", "vgpa_profile_end", "vgpa_ld_gemm", "vgpa_ld_stage", "vgpa_gradient_dev", "vgpa_energy_full", "vgpa_set_option", "vgpa_is_streaming", "vgpa_path_info", "vgpa_set_prior_energy",
            "vgpa_set_problem_data", "vgpa_set_problem_params", "vgpa_set_problem_obs_model",
@@ -143,6 +143,9 @@ def load():
                                           c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vgpa_particle_paths.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_uint64, c_double, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.vgpa_particle_forecast.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_uint64, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                           c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p]
     lib.vgpa_sweep_dev.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vgpa_free_energy_dev.argtypes = [c_void_p, c_void_p, c_void_p]
     lib.vgpa_sweep_enqueue.argtypes = [c_void_p, c_void_p, c_void_p]
@@ -693,6 +696,69 @@ class Context:
                                                   float(ess_fraction), _ptr(mu), _ptr(tau), _ptr(log_w), _ptr(state), _ptr(paths), _ptr(table),
                                                   _ptr(ess), _ptr(flags)))
         return {"log_w": log_w, "state": state, "ess": ess, "resampled": flags, "paths": paths, "slots": table}
+
+    def particle_forecast(self, horizon, n_paths=None, seed=0, stride=1, n_draw=0, ess_fraction=0.5, x=None, x0=None, cloud=None, log_w=None,
+                          index0=None, slots=None, prior=None):
+        """A weighted cloud carried `horizon` steps past its grid index under the model SDE (vgpa_particle_forecast), on the device.
+        cloud=None: the cloud is the final one of particle_filter(n_paths, seed, ess_fraction, x, x0, prior) at grid index Np - 1, taken
+        from the device buffer it is in.  Else cloud (B, n, D) or (n, D), log_w (B, n) or (n,) (None: equal weights) and index0 (the
+        absolute grid index of the cloud; None: Np - 1): no filter runs and the context need not have evaluated anything.  Step h draws at
+        the absolute grid index index0 + h with the counter word of the particle's slot; the weights do not change.  n_draw members per
+        problem are the trajectories of the slots `slots` ((B, n_draw) or (n_draw,); n_draw may then be left 0), or of slots drawn from the weights as particle_paths
+        draws its final slots.  Returns a dict: moments (B, h_keep, 2, D): sum W x and sum W x^2 at the steps 0, stride, ... <= horizon,
+        members (B, n_draw, h_keep, D), slots (B, n_draw) int32, state_end (B, n, D): the cloud at index0 + horizon, index0, and log_w,
+        state: the cloud the forecast started from (behind the filter bit for bit particle_filter's, with its ess and resampled)."""
+        horizon, stride, n_draw = int(horizon), int(stride), int(n_draw)
+        if slots is not None and n_draw == 0:      # (given slots say how many they are)
+            n_draw = int(np.shape(slots)[-1]) if np.ndim(slots) else 0
+        given_cloud = cloud is not None
+        if given_cloud:
+            cl = np.asarray(cloud, dtype=np.float64)
+            if cl.ndim < 2 or cl.shape[-1] != self.D or cl.size == 0:
+                raise ValueError(f"cloud must be (B, n, {self.D}) or (n, {self.D})")
+            cl = _c64(np.broadcast_to(cl.reshape((-1,) + cl.shape[-2:]), (self.B,) + cl.shape[-2:]))
+            if n_paths is not None and int(n_paths) != cl.shape[1]:
+                raise ValueError(f"n_paths = {n_paths}, but the cloud has {cl.shape[1]} particles")
+            n_paths = cl.shape[1]
+            lw = None if log_w is None else _c64(np.broadcast_to(np.asarray(log_w, dtype=np.float64).reshape(-1, n_paths), (self.B, n_paths)))
+            k0 = self.Np - 1 if index0 is None else int(index0)
+        else:
+            if n_paths is None:
+                raise ValueError("n_paths is needed where no cloud is given")
+            if log_w is not None or index0 is not None:
+                raise ValueError("log_w and index0 belong to a given cloud")
+            cl, lw, k0 = None, None, self.Np - 1
+        n_paths = int(n_paths)
+        if not all(-2 ** 31 <= v < 2 ** 31 for v in (n_paths, n_draw, stride, horizon, k0)):      # (the C ABI takes int32: nothing may wrap on its way there)
+            raise ValueError("n_paths, n_draw, stride, horizon and index0 must fit into 32 bits")
+        xx = None if x is None else _c64(x)
+        if xx is not None and xx.size != self.B * self.len_x:
+            raise ValueError(f"x has {xx.size} entries, expected {self.B * self.len_x}")
+        s0 = None if x0 is None else _c64(np.broadcast_to(np.asarray(x0, dtype=np.float64).reshape(-1, self.D), (self.B, self.D)))
+        mu = tau = None
+        if prior is not None:
+            mu = _c64(np.broadcast_to(np.asarray(prior[0], dtype=np.float64).reshape(-1, self.D), (self.B, self.D)))
+            tau = _c64(np.broadcast_to(np.asarray(prior[1], dtype=np.float64).reshape(-1, self.D, self.D), (self.B, self.D, self.D)))
+        n, k, m = max(n_paths, 0), max(n_draw, 0), self.n_obs
+        given = None
+        if slots is not None:
+            wide = np.asarray(slots)
+            if wide.dtype.kind not in "iu" or wide.size == 0 or wide.min() < -2 ** 31 or wide.max() >= 2 ** 31:
+                raise ValueError("slots must be integers that fit into 32 bits")
+            given = np.ascontiguousarray(np.broadcast_to(wide.reshape(-1, k), (self.B, k)), dtype=np.int32)
+        h_keep = max(horizon, 0) // max(stride, 1) + 1
+        out_lw, state = np.empty((self.B, n)), np.empty((self.B, n, self.D))
+        ess, flags = np.zeros((self.B, m)), np.zeros((self.B, m), dtype=np.int32)
+        moments, members = np.empty((self.B, h_keep, 2, self.D)), np.empty((self.B, k, h_keep, self.D))
+        table, state_end = np.full((self.B, k), -1, dtype=np.int32), np.empty((self.B, n, self.D))
+        self._check(self._lib.vgpa_particle_forecast(self._h, _ptr(xx), _ptr(s0), n_paths, int(seed) & 0xFFFFFFFFFFFFFFFF, float(ess_fraction),
+                                                     _ptr(mu), _ptr(tau), _ptr(cl), _ptr(lw), k0 if given_cloud else 0, horizon, stride, n_draw,
+                                                     _ptr(given), _ptr(out_lw), _ptr(state), _ptr(ess), _ptr(flags), _ptr(moments),
+                                                     _ptr(members), _ptr(table), _ptr(state_end)))
+        if given_cloud:
+            out_lw, state, ess, flags = (np.zeros((self.B, n)) if lw is None else lw), cl, None, None
+        return {"log_w": out_lw, "state": state, "ess": ess, "resampled": flags, "moments": moments, "members": members, "slots": table,
+                "state_end": state_end, "index0": k0}
 
     def fetch(self, key):
         which = FETCH_IDS[key]

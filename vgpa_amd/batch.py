@@ -243,6 +243,32 @@ class ProblemBatch(object):
         res = self._context().particle_paths(n_paths, seed, n_draw, stride=stride, ess_fraction=ess_fraction, x=xx, x0=x0, prior=prior, slots=slots)
         return [v._paths_record(res, k, stride, slots is None) for k, v in enumerate(self.vgps)]
 
+    def forecast(self, horizon, n_paths=None, seed=0, stride=1, n_draw=0, ess_fraction=0.5, x=None, x0=None, source="filter", cloud=None,
+                 log_w=None, index0=None, slots=None):
+        """One particles.Forecast per member (VarGP.forecast): every member's cloud -- its own filter's final one, the end points of its
+        posterior process's paths (source="posterior") or the given cloud (B, n, D) with log_w (B, n) at index0 -- carried `horizon` steps
+        forward under its own theta and Sigma."""
+        xx = None if x is None else self._stack(x)
+        v0 = self.vgps[0]
+        if source == "posterior":
+            if cloud is not None or n_paths is None:
+                raise ValueError(" forecast: source='posterior' draws its own cloud of n_paths particles.")
+            ends = self._context().sample_paths("posterior", n_paths, seed, stride=v0.dim_n - 1 if v0.dim_n > 1 else 1, x=xx, x0=x0)
+            cloud, log_w, index0 = ends[:, :, -1, :], None, v0.dim_n - 1
+        elif source != "filter":
+            raise ValueError(f" Unknown source of the forecast -> {source}")
+        if cloud is not None:
+            cloud = np.asarray(cloud, dtype=float)
+            cloud = cloud.reshape(cloud.shape + (1,)) if v0.model.single_dim and cloud.shape[-1:] != (1,) else cloud
+            res = self._context().particle_forecast(horizon, seed=seed, stride=stride, n_draw=n_draw, cloud=cloud, log_w=log_w, index0=index0,
+                                                    slots=slots)
+        else:
+            d = v0.dim_d
+            prior = (np.stack([v._prior()[0][0] for v in self.vgps]), np.stack([v._prior()[1][0] for v in self.vgps]).reshape(self.B, d, d))
+            res = self._context().particle_forecast(horizon, n_paths, seed, stride=stride, n_draw=n_draw, ess_fraction=ess_fraction, x=xx, x0=x0,
+                                                    slots=slots, prior=prior)
+        return [v._forecast_record(res, k, horizon, stride, slots is None) for k, v in enumerate(self.vgps)]
+
     def particle_fit_theta(self, n_paths, seed, iters, ess_fraction=0.5, refit=True, pooled=False, x0=None, options=None):
         """
         Particle EM for the drift parameters under the smoothing distribution of the Euler-discretised model, free of the variational

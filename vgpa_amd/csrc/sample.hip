@@ -1,13 +1,16 @@
 // Euler-Maruyama sample paths of the posterior process dx = (-A_t x + b_t) dt + Sigma^1/2 dW and of the model SDE:
 //   x_k = x_{k-1} + dt drift_{k-1}(x_{k-1}) + R xi_k,  R = chol_lower(Sigma dt).
-// Three kernels walk the grid:
+// Four kernels walk the grid:
 //   k_sample_small<D, K>   D <= 4, both kinds: one lane per path, the state in registers
 //   k_sample_mfma<NT, K>   5 <= D <= 64, posterior kind: a workgroup owns one problem and 64 paths (4 waves x 16 paths); A_k X (and R Xi for a dense
 //                          R) on v_mfma_f64_16x16x4_f64 with the 16 paths of a wave as the N side, D padded to NT = 16, 32, 48, 64
 //   k_sample_l96           5 <= D <= 64, model kind (Lorenz-96): one lane per path, the state in LDS
+//   k_forecast_l96         5 <= D <= 64, the forecast (Lorenz-96): k_sample_l96's lanes and step from a cloud of particles, one wave per
+//                          workgroup, the weighted sums of the wave's D x 64 tile of states taken in LDS
 // The normals are counter-based (Philox4x32-10 + Box-Muller, vgpa_hip.h): every lane generates exactly the draws it consumes, so no result
 // depends on the launch geometry.
-// K is the walk (vgpa_internal.h), stated by the host at every launch_sample_walk; every walk runs on k_sample_small and k_sample_mfma:
+// K is the walk (vgpa_internal.h), stated by the host at every launch_sample_walk; every walk but the last runs on k_sample_small and
+// k_sample_mfma:
 //   walk         | what it computes; [the kernels and k_pf_* steps that serve it besides those two]                                 | DESIGN.md
 //   Plain        | the paths, every stride-th point stored  [k_sample_l96]                                                          | s.4.8
 //   Weighted     | the same paths and, summed where the path is made, the log-ratio of the model SDE's path density to the          | s.4.9
@@ -23,6 +26,11 @@
 //   Lineage      | K smoothing trajectories of the filter's genealogy in one launch: the unweighted posterior walk, stored as Plain | s.4.13
 //                | stores it, each lane drawing with the counter word of the slot its lineage sat in -- one word per stretch between |
 //                | two observations of its problem  [k_pf_trace writes the table behind k_pf_pick or the caller's final slots]      |
+//   Forecast     | the model SDE carried from the cloud in pf_x at the absolute grid index k_begin to k_end, no weight changing: the | s.4.15
+//                | cloud launch sums W x and W x^2 at every kept step as Replay does and writes the end states back; the member      |
+//                | launch walks K slots alone, each from its slot's state with its slot's counter word, stored as Plain stores      |
+//                | [k_sample_small and k_forecast_l96; k_pf_normalise: W from the log-weights, k_pf_pick: drawn slots,              |
+//                | k_pf_moments_sum]                                                                                                |
 #include "vgpa_internal.h"
 
 #include <type_traits>
@@ -135,18 +143,20 @@ __device__ __forceinline__ double wave_max(double v) {
 
 // What the two kernels branch on, per walk: W the walk of the weighted kind (posterior drift, diagonal R), SEG it runs (k_begin, k_end] from
 // and to pf_x, ST it carries the rows of pf_stats, MO it takes the moments of the replay, LN the counter words come from pf_slots;
-// WS: the weight sums are formed.  The six rows are all there is: no other combination can be instantiated.
+// FC it is the forecast (the model's drift from the cloud in pf_x, k_sample_small only); WS: the weight sums are formed.  The seven rows are
+// all there is: no other combination can be instantiated.
 struct WalkTraits {
-  bool W, SEG, ST, MO, LN;
+  bool W, SEG, ST, MO, LN, FC;
   constexpr bool WS() const { return W && !MO; }
 };
 constexpr WalkTraits kWalkTraits[] = {      // in the order of Walk
-    {false, false, false, false, false},    // Plain
-    {true,  false, false, false, false},    // Weighted
-    {true,  true,  false, false, false},    // Segment
-    {true,  true,  true,  false, false},    // SegmentStats
-    {true,  true,  false, true,  false},    // Replay
-    {false, false, false, false, true}};    // Lineage
+    {false, false, false, false, false, false},    // Plain
+    {true,  false, false, false, false, false},    // Weighted
+    {true,  true,  false, false, false, false},    // Segment
+    {true,  true,  true,  false, false, false},    // SegmentStats
+    {true,  true,  false, true,  false, false},    // Replay
+    {false, false, false, false, true,  false},    // Lineage
+    {false, false, false, false, false, true}};    // Forecast
 
 // Weighted: posterior kind, diagonal R: both drifts at x_{k-1}, d = g - f, and per step -sum_i d_i (eta_i + dt d_i / 2) / Sigma_ii with
 // 1 / Sigma_ii = dt / R_ii^2; the observation term at the lane's own problem's times.
@@ -160,14 +170,19 @@ constexpr WalkTraits kWalkTraits[] = {      // in the order of Walk
 // Lineage: the unweighted posterior walk of lane m = `path`, whose counter word is not m but the entry of its column of pf_slots for the
 // stretch it is in: row 0 for the start, the next row each time the walk has completed an observation index of the lane's own problem (an
 // observation at index 0: before step 1).  No model drift, no sums.
+// Forecast: launched as the replay is (the problem in blockIdx.x, 256 lanes per workgroup).  The model's drift alone, step h = 1 .. k_end -
+// k_begin drawn at the absolute grid index k_begin + h, from the slot's state in pf_x.  The cloud launch (pf_part set): lane = slot, the
+// replay's sums with W = pf_wtab at h = 0, stride, ..., the end state back to pf_x.  The member launch (out, pf_slots set): lane m starts from
+// slot pf_slots[p][m], draws with that slot's word and stores as Plain stores.  A lane behind the last one walks the last one again with
+// weight 0 and stores nothing.
 template <int D, Walk K>
 __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
   constexpr WalkTraits T = kWalkTraits[(int)K];
-  constexpr bool W = T.W, SEG = T.SEG, ST = T.ST, MO = T.MO, LN = T.LN, WS = T.WS();
+  constexpr bool W = T.W, SEG = T.SEG, ST = T.ST, MO = T.MO, LN = T.LN, FC = T.FC, WS = T.WS();
   size_t gid;
   uint32_t p, path;
   bool live = true;
-  if constexpr (MO) {
+  if constexpr (MO || FC) {
     const uint32_t slot = blockIdx.y * 256 + threadIdx.x;
     live = slot < (uint32_t)a.n_paths;
     p = blockIdx.x; path = live ? slot : (uint32_t)a.n_paths - 1;
@@ -180,6 +195,7 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
   uint32_t word = path;      // the counter word of the lane's draws
   const int32_t* lin = nullptr;
   if constexpr (LN) { lin = a.pf_slots + (size_t)p * a.pf_slot_rows * a.n_paths + path; word = (uint32_t)lin[0]; }
+  if constexpr (FC) { if (a.pf_slots) word = (uint32_t)a.pf_slots[gid]; }
   const uint32_t k0 = (uint32_t)(a.seed & 0xffffffffu), k1 = (uint32_t)(a.seed >> 32);
   constexpr int NP = (D + 1) / 2;
   // kept points wait in LDS (slot-major, thread fastest: no conflicts) until NBUF of them -- 16 doubles for D = 1, 2, 4, 15 for D = 3 -- go out as
@@ -195,7 +211,10 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
 #pragma unroll
     for (int i = 0; i < kMaxTheta; i++) th[i] = a.theta_v ? a.theta_v[(size_t)p * kMaxTheta + i] : a.theta[i];
   }
-  if constexpr (MO) {
+  if constexpr (FC) {
+#pragma unroll
+    for (int i = 0; i < D; i++) x[i] = a.pf_x[((size_t)p * a.pf_n + word) * D + i];
+  } else if constexpr (MO) {
 #pragma unroll
     for (int i = 0; i < D; i++) x[i] = live ? a.pf_x[gid * D + i] : 0.0;
   } else if constexpr (SEG) {
@@ -217,7 +236,7 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
       x[i] = m0[i] + s;
     }
   }
-  const bool store = !SEG && (!W || a.out != nullptr);
+  const bool store = FC ? live && a.out != nullptr : !SEG && (!W || a.out != nullptr);
   double* o = store ? a.out + gid * (size_t)a.n_keep * D : nullptr;
   if (store) {
 #pragma unroll
@@ -254,6 +273,12 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
     keep_slot = ((long long)a.k_begin + a.stride) / a.stride;      // the first kept index behind k_begin
     keep_k = keep_slot * a.stride;
   }
+  if constexpr (FC) {      // (keep_k counts steps: h = k + 1 behind step k of the loop below)
+    __shared__ double red_lds[2 * 2 * D * 4];
+    red = red_lds;
+    wt = live && a.pf_wtab ? a.pf_wtab[gid] : 0.0;
+    keep_slot = 1; keep_k = a.stride;
+  }
   auto reduce = [&](long long slot) {
     double v[2 * D];
 #pragma unroll
@@ -272,6 +297,7 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
     par ^= 1;
   };
   if constexpr (MO) { if (a.seg_first) reduce(0); }
+  if constexpr (FC) { if (a.pf_part) reduce(0); }
   double sq[ST ? D : 1], sg1[ST ? D : 1], sh[ST ? D : 1], phi[ST ? D : 1];
   if constexpr (ST) {
 #pragma unroll
@@ -282,11 +308,12 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
   const double* A = a.A + (size_t)p * a.stride_x;
   const double* bv = a.b + (size_t)p * a.stride_x;
   int until = a.stride, slot = 0;
-  const int k_first = SEG ? a.k_begin + 1 : 1, k_stop = SEG ? a.k_end + 1 : a.Np;
+  // (the forecast counts its steps from 0: k_begin + h may be the last index an int holds)
+  const int k_first = FC ? 0 : SEG ? a.k_begin + 1 : 1, k_stop = FC ? a.k_end - a.k_begin : SEG ? a.k_end + 1 : a.Np;
   for (int k = k_first; k < k_stop; k++) {
     double f[D], fm[D];
     if constexpr (WS) model_drift<D>(a.model, th, x, fm);
-    if (W || LN || a.kind == VGPA_PATHS_POSTERIOR) {
+    if (!FC && (W || LN || a.kind == VGPA_PATHS_POSTERIOR)) {
       const double* Ak = A + (size_t)(k - 1) * D * D;
       const double* bk = bv + (size_t)(k - 1) * D;
 #pragma unroll
@@ -300,7 +327,7 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
       model_drift<D>(a.model, th, x, f);
     }
 #pragma unroll
-    for (int j = 0; j < NP; j++) normal_pair(k0, k1, (uint32_t)k, word, p, (uint32_t)j, &z[2 * j], &z[2 * j + 1]);
+    for (int j = 0; j < NP; j++) normal_pair(k0, k1, FC ? (uint32_t)a.k_begin + (uint32_t)k + 1u : (uint32_t)k, word, p, (uint32_t)j, &z[2 * j], &z[2 * j + 1]);
     if constexpr (ST) model_phi<D>(a.model, x, phi);
 #pragma unroll
     for (int i = 0; i < D; i++) {
@@ -323,6 +350,9 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
     if constexpr (LN) {
       if (k == oc.next) { oc.advance(); word = (uint32_t)lin[(size_t)oc.cur * a.n_paths]; }
     }
+    if constexpr (FC) {
+      if (a.pf_part && k + 1 == keep_k) { reduce(keep_slot++); keep_k += a.stride; }
+    }
     if (store && --until == 0) {
       until = a.stride;
 #pragma unroll
@@ -336,7 +366,12 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
     }
   }
   for (int e = 0; e < slot * D; e++) o[e] = sg[e * 256];
-  if constexpr (MO) {
+  if constexpr (FC) {
+    if (live && a.pf_part) {
+#pragma unroll
+      for (int i = 0; i < D; i++) a.pf_x[gid * D + i] = x[i];
+    }
+  } else if constexpr (MO) {
     if (live) {
 #pragma unroll
       for (int i = 0; i < D; i++) a.pf_x[gid * D + i] = x[i];
@@ -773,6 +808,84 @@ __global__ __launch_bounds__(64) void k_sample_l96(SampleArgs a) {
   }
 }
 
+// ---- 5 <= D <= 64, the forecast: Lorenz-96 from a cloud ---------------------------------------------------------------------------------
+// Walk::Forecast above D = 4: workgroup (p, blk) is one wave, lane = slot blk * 64 + lane of problem p (the member launch:
+// lane m, which starts from slot pf_slots[p][m] and draws with that slot's word), the state in LDS as in k_sample_l96, whose diagonal step
+// this is, drawn at the absolute grid index k_begin + h.  At a kept h of the cloud launch the wave owns the D x 64 tile xs and the 64 weights
+// ws: lane l < D adds row l of W x and (W x) x over the 64 columns in the order l, l + 1, ..., 63, 0, ..., l - 1.  (A wave's 64-bit LDS read is
+// served in two groups of 32 lanes; with a row stride of 64 doubles every lane of an unskewed read would sit on one bank pair, the skew puts
+// the 32 lanes of a group on 32 different pairs.)  One order, whatever the launch: the sums are reproducible.  A lane behind the last one
+// walks the last one again with weight 0 and stores nothing.
+__global__ __launch_bounds__(64) void k_forecast_l96(SampleArgs a) {
+  extern __shared__ double lds[];
+  const int D = a.D, lane = threadIdx.x;
+  double* xs = lds + lane;
+  double* ws = lds + (size_t)D * 64;
+  const uint32_t p = blockIdx.x, slot = blockIdx.y * 64 + lane;
+  const bool live = slot < (uint32_t)a.n_paths;
+  const size_t gid = (size_t)p * a.n_paths + (live ? slot : (uint32_t)a.n_paths - 1);
+  const uint32_t word = a.pf_slots ? (uint32_t)a.pf_slots[gid] : (uint32_t)(gid - (size_t)p * a.n_paths);
+  const uint32_t k0 = (uint32_t)(a.seed & 0xffffffffu), k1 = (uint32_t)(a.seed >> 32);
+  const double* Rp = a.R + (size_t)p * a.R_stride;
+  const double th = a.theta_v ? a.theta_v[(size_t)p * kMaxTheta] : a.theta[0];
+  {
+    const double* x0 = a.pf_x + ((size_t)p * a.pf_n + word) * D;
+    for (int i = 0; i < D; i++) xs[i * 64] = x0[i];
+  }
+  const bool sums = a.pf_part != nullptr, store = live && a.out != nullptr;
+  ws[lane] = live && sums ? a.pf_wtab[gid] : 0.0;
+  double* part = sums ? a.pf_part + ((size_t)p * gridDim.y + blockIdx.y) * a.n_keep * 2 * D : nullptr;
+  auto reduce = [&]() {
+    __syncthreads();      // (the tile and the weights are written)
+    if (lane < D) {
+      const double* row = lds + (size_t)lane * 64;
+      double s1 = 0.0, s2 = 0.0;
+#pragma unroll 8
+      for (int c = 0; c < 64; c++) {
+        const int col = (lane + c) & 63;
+        const double v = ws[col] * row[col];
+        s1 += v; s2 += v * row[col];
+      }
+      part[lane] = s1; part[D + lane] = s2;
+    }
+    part += 2 * D;
+    __syncthreads();      // (the tile has been read)
+  };
+  double* o = store ? a.out + gid * (size_t)a.n_keep * D : nullptr;
+  if (store) {
+    for (int i = 0; i < D; i++) o[i] = xs[i * 64];
+    o += D;
+  }
+  if (sums) reduce();
+  int until = a.stride;
+  const int H = a.k_end - a.k_begin;
+  for (int h = 0; h < H; h++) {      // (step h + 1; k_begin + h + 1 may be the last index an int holds)
+    const uint32_t k = (uint32_t)a.k_begin + (uint32_t)h + 1u;
+    const double x_first = xs[0];
+    double om2 = xs[(D - 2) * 64], om1 = xs[(D - 1) * 64], cur = x_first, zc = 0.0, zn = 0.0;
+    for (int i = 0; i < D; i++) {
+      const double nxt = i + 1 < D ? xs[(i + 1) * 64] : x_first;
+      const double f = (nxt - om2) * om1 - cur + th;
+      if (!(i & 1)) normal_pair(k0, k1, k, word, p, (uint32_t)(i >> 1), &zc, &zn);
+      const double nz = Rp[i * D + i] * ((i & 1) ? zn : zc);
+      xs[i * 64] = (cur + a.dt * f) + nz;
+      om2 = om1; om1 = cur; cur = nxt;
+    }
+    if (--until == 0) {
+      until = a.stride;
+      if (sums) reduce();
+      if (store) {
+        for (int i = 0; i < D; i++) o[i] = xs[i * 64];
+        o += D;
+      }
+    }
+  }
+  if (live && sums) {
+    double* xe = a.pf_x + gid * D;
+    for (int i = 0; i < D; i++) xe[i] = xs[i * 64];
+  }
+}
+
 // ---- the particle filter: the start, the segments, the resampling step between them ------------------------------------------------
 // One lane per particle: x_0 (given, or m0 + L0 xi_0 summed as the samplers sum it) to a.x, and lw = init - c_p with
 // init = log N(x_0; mu0, tau0) - log N(x_0; m0, S0) for a drawn start under a prior (the two triangular solves against the factors in global
@@ -1033,6 +1146,19 @@ __global__ __launch_bounds__(256) void k_pf_descend(PfArgs a, int rows, double* 
   }
 }
 
+// The forecast's weights, one workgroup per problem: W_i = w_i / sum w with w_i = exp(lw_i - max lw), the sum in the fixed order of block_sum.
+__global__ __launch_bounds__(256) void k_pf_normalise(int n, const double* lw_all, double* w_all) {
+  __shared__ double red[4];
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const double* lw = lw_all + (size_t)p * n;
+  double* w = w_all + (size_t)p * n;
+  const double mx = pf_max(lw, n, red);
+  double s = 0.0;
+  for (int i = tid; i < n; i += 256) s += exp(lw[i] - mx);
+  s = block_sum(s, red);
+  for (int i = tid; i < n; i += 256) w[i] = exp(lw[i] - mx) / s;
+}
+
 // The step between two segments of the replay at grid index a.k: workgroup (p, y) moves its share of problem p's particles from x_in to
 // x_out by the ancestors the filter stored for the problem's observation at a.k (the identity where the cloud was carried on), or
 // unchanged where the problem has no observation there.
@@ -1115,7 +1241,7 @@ __global__ __launch_bounds__(256) void k_pf_trace(PfArgs a, int K, int rows, int
 template <Walk K>
 hipError_t launch_walk(const SampleArgs& a, hipStream_t st) {
   if (a.D <= kMaxLaneD) {
-    const dim3 grid = kWalkTraits[(int)K].MO ? dim3(a.batch, sample_segment_blocks(a.D, a.n_paths))
+    const dim3 grid = kWalkTraits[(int)K].MO || kWalkTraits[(int)K].FC ? dim3(a.batch, sample_segment_blocks(a.D, a.n_paths))
                                         : dim3((unsigned)(((size_t)a.batch * a.n_paths + 255) / 256));
     const dim3 block(256);
     switch (a.D) {
@@ -1128,18 +1254,23 @@ hipError_t launch_walk(const SampleArgs& a, hipStream_t st) {
     }
     return hipGetLastError();
   }
-  auto mfma = [&](auto nt) {
-    constexpr int NT = decltype(nt)::value;
-    const size_t lds = MfmaShape<NT>::lds_doubles(!a.R_diag) * sizeof(double);
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k_sample_mfma<NT, K>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if ((a.n_paths + 63) / 64 > 65535) return hipErrorInvalidValue;      // (grid.y)
-    hipLaunchKernelGGL((k_sample_mfma<NT, K>), dim3(a.batch, (a.n_paths + 63) / 64), dim3(256), lds, st, a);
+  if constexpr (K == Walk::Forecast) {      // (the matrix-core kernel is posterior kind only: above D = 4 the forecast is Lorenz-96's own kernel)
+    hipLaunchKernelGGL(k_forecast_l96, dim3(a.batch, sample_segment_blocks(a.D, a.n_paths)), dim3(64), ((size_t)a.D + 1) * 64 * sizeof(double), st, a);
     return hipGetLastError();
-  };
-  if (a.D <= 16) return mfma(std::integral_constant<int, 16>{});
-  if (a.D <= 32) return mfma(std::integral_constant<int, 32>{});
-  if (a.D <= 48) return mfma(std::integral_constant<int, 48>{});
-  return mfma(std::integral_constant<int, 64>{});
+  } else {
+    auto mfma = [&](auto nt) {
+      constexpr int NT = decltype(nt)::value;
+      const size_t lds = MfmaShape<NT>::lds_doubles(!a.R_diag) * sizeof(double);
+      if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k_sample_mfma<NT, K>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if ((a.n_paths + 63) / 64 > 65535) return hipErrorInvalidValue;      // (grid.y)
+      hipLaunchKernelGGL((k_sample_mfma<NT, K>), dim3(a.batch, (a.n_paths + 63) / 64), dim3(256), lds, st, a);
+      return hipGetLastError();
+    };
+    if (a.D <= 16) return mfma(std::integral_constant<int, 16>{});
+    if (a.D <= 32) return mfma(std::integral_constant<int, 32>{});
+    if (a.D <= 48) return mfma(std::integral_constant<int, 48>{});
+    return mfma(std::integral_constant<int, 64>{});
+  }
 }
 
 }  // namespace
@@ -1195,6 +1326,12 @@ hipError_t launch_pf_trace(const PfArgs& a, int K, int rows, int32_t* table, hip
   return hipGetLastError();
 }
 
+hipError_t launch_pf_normalise(int batch, int n_paths, const double* lw, double* w, hipStream_t st) {
+  if (batch < 1 || n_paths < 1 || !lw || !w) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_pf_normalise, dim3(batch), dim3(256), 0, st, n_paths, lw, w);
+  return hipGetLastError();
+}
+
 bool sample_lineages_fit(int D, int batch, int K) {
   if (D <= kMaxLaneD) return ((size_t)batch * K + 255) / 256 <= 0x7fffffffu;      // (grid.x)
   return (K + 63) / 64 <= 65535;                                                    // (grid.y)
@@ -1239,6 +1376,14 @@ hipError_t launch_sample_walk(Walk w, const SampleArgs& a, hipStream_t st) {
       if (a.stride < 1 || a.kind != VGPA_PATHS_POSTERIOR || !a.R_diag || !a.out || !a.pf_slots || a.pf_slot_rows < 1 || a.logw) return hipErrorInvalidValue;
       if (!sample_lineages_fit(a.D, a.batch, a.n_paths)) return hipErrorInvalidValue;
       return launch_walk<Walk::Lineage>(a, st);
+    case Walk::Forecast: {
+      const bool cloud = a.pf_part && a.pf_wtab && !a.out && !a.pf_slots && a.n_paths == a.pf_n;
+      const bool members = a.out && a.pf_slots && a.pf_slot_rows == 1 && !a.pf_part && !a.pf_wtab;
+      if (a.stride < 1 || a.kind != VGPA_PATHS_MODEL || !a.R_diag || !known_model || (a.D > kMaxLaneD && a.model != VGPA_MODEL_L96)) return hipErrorInvalidValue;
+      if (!a.pf_x || a.pf_n < 1 || a.k_begin < 0 || a.k_end < a.k_begin || cloud == members || a.logw || a.pf_lw || a.pf_stats) return hipErrorInvalidValue;
+      if (a.n_keep != (a.k_end - a.k_begin) / a.stride + 1 || sample_segment_blocks(a.D, a.n_paths) > 65535) return hipErrorInvalidValue;      // (grid.y)
+      return launch_walk<Walk::Forecast>(a, st);
+    }
   }
   return hipErrorInvalidValue;
 }

@@ -168,7 +168,8 @@ struct vgpa_ctx {
   // vgpa_particle_filter: the two particle buffers, log-weights, prefix sums, ancestors of a step (int32), the histories (ess, flags and
   // ancestors as int32, clouds), the prior's mean and factor; vgpa_particle_statistics: the two buffers of rows and their mean;
   // vgpa_particle_moments: the descendant weights, the lineage ESS, the workgroups' partial sums, the moments; vgpa_particle_paths: the
-  // slot table (int32; the trajectories themselves go through d_sp_out)
+  // slot table (int32; the trajectories themselves go through d_sp_out); vgpa_particle_forecast: of these the particles, log-weights, prefix
+  // sums, normalised weights (PF_WTAB), partial sums, moments and slot table
   enum { PF_XA, PF_XB, PF_LW, PF_CUM, PF_ANC, PF_ESS, PF_FLAG, PF_HANC, PF_CLOUDS, PF_MU, PF_LT, PF_STA, PF_STB, PF_MEAN, PF_WTAB, PF_LESS, PF_PART,
          PF_MOM, PF_SLOTS, PF_COUNT };
   double* d_pf[PF_COUNT] = {};
@@ -1578,6 +1579,10 @@ struct ParticleRequest {
   int32_t stride = 1;                                                // of the grid indices the two smoothers keep
   double* moments; double* lineage_ess;                              // vgpa_particle_moments
   int32_t n_draw; const int32_t* final_slots; double* paths; int32_t* slots_out;      // vgpa_particle_paths; slots_out: where the table goes
+  // vgpa_particle_forecast: horizon steps behind the filter, or from `cloud` at index0; stride, n_draw, final_slots, slots_out as above;
+  // moments is then fc_moments
+  bool forecast; int32_t horizon; const double* cloud; const double* cloud_logw; int32_t index0;
+  double* fc_moments; double* members; double* state_end;
 };
 
 // One run: the filter, then what the request puts behind it.  The passes share the kernels' arguments, the cuts and where the particles are.
@@ -1589,6 +1594,7 @@ struct ParticleRun {
   double* cur; double* other;          // the particles: where they are, where the next step puts them
   double* st_cur; double* st_other;    // ... and their rows of path statistics (with_stats)
   int n_keep, rows, slot_rows, n_blocks; size_t mom_len, n_table, n_traj;
+  int k0 = 0;                          // the forecast: the absolute grid index of the cloud
 
   // For each cut -- an observation index of some problem, and the last grid index --: the segment launch up to it, then, at an
   // observation, the step between two segments (from cur to other), and the particle buffers swap.
@@ -1731,7 +1737,89 @@ struct ParticleRun {
     if (q.slots_out) HIP_TRY(c, hipMemcpyAsync(q.slots_out, table, n_table * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     return VGPA_OK;
   }
+
+  // The forecast from a given cloud in place of setup() and filter(): of the kernels' arguments the model's -- the factors
+  // of Sigma dt and theta in force --, the cloud and its log-weights (none given: equal) uploaded to where the filter would have left them.
+  // No x, no observation and nothing of the cached state is read or written.
+  int given_cloud() {
+    const int D = c->D, B = c->B;
+    int rc;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    a = SampleArgs{};
+    a.model = c->cfg.model; a.D = D; a.Np = c->Np; a.batch = B; a.n_paths = q.n_paths; a.dt = c->cfg.dt; a.seed = q.seed;
+    Rows<double> R;
+    bool diag = true;
+    const bool own_Sigma = !c->in.h_Sigma.empty();
+    if ((rc = factor_rows(c, own_Sigma ? c->in.h_Sigma.data() : c->h_sigma.data(), own_Sigma ? B : 1, c->cfg.dt, "noise matrix times dt",
+                          &c->d_sp_R, &c->sp_R_n, &R, &diag))) return rc;
+    if (!diag) return fail(c, VGPA_ERR_UNSUPPORTED, "the particle forecast is built for a diagonal Sigma (a dense Sigma is in force)");
+    a.R = R.rows; a.R_stride = R.stride; a.R_diag = 1;
+    copy_theta(c, a.theta);
+    a.theta_v = c->in.theta.rows;
+    const size_t Bn = (size_t)B * q.n_paths;
+    auto buf = [&](int which, size_t count) { return grow(c, &c->d_pf[which], &c->pf_n[which], count); };
+    if ((rc = buf(vgpa_ctx::PF_XA, Bn * D)) || (rc = buf(vgpa_ctx::PF_LW, Bn)) || (rc = buf(vgpa_ctx::PF_CUM, Bn))) return rc;
+    f = PfArgs{};
+    f.D = D; f.batch = B; f.n_paths = q.n_paths; f.M = 1; f.seed = q.seed;
+    cur = c->d_pf[vgpa_ctx::PF_XA]; other = nullptr; st_cur = nullptr; st_other = nullptr;
+    f.lw = c->d_pf[vgpa_ctx::PF_LW]; f.cum = c->d_pf[vgpa_ctx::PF_CUM];
+    if ((rc = upload(c, cur, q.cloud, Bn * D))) return rc;
+    if (q.cloud_logw) { if ((rc = upload(c, f.lw, q.cloud_logw, Bn))) return rc; }
+    else HIP_TRY(c, hipMemsetAsync(f.lw, 0, Bn * sizeof(double), c->stream));
+    k0 = q.index0;
+    return VGPA_OK;
+  }
+
+  // The forecast behind the filter or behind given_cloud(): the particles in `cur` at grid index k0 with the log-weights
+  // f.lw.  The n_draw members first -- their slots (final_slots, or drawn from the weights as trajectories() draws them, the uniform from
+  // grid index k0 + 1), one launch of the forecast walk over them alone --, then the walk of the whole cloud with the weighted sums at every
+  // stride-th step, which leaves the cloud of k0 + horizon in `cur`; the sum over the workgroups, the downloads.
+  int forecast() {
+    const int D = c->D, B = c->B, n_draw = q.n_draw, h_keep = q.horizon / q.stride + 1;
+    const size_t n = (size_t)q.n_paths, n_slots = (size_t)B * n_draw, n_mem = n_slots * h_keep * D, len = (size_t)h_keep * 2 * D;
+    const int blocks = sample_segment_blocks(D, q.n_paths);
+    int rc;
+    auto buf = [&](int which, size_t count) { return grow(c, &c->d_pf[which], &c->pf_n[which], count); };
+    if ((rc = buf(vgpa_ctx::PF_WTAB, (size_t)B * n)) || (rc = buf(vgpa_ctx::PF_PART, (size_t)B * blocks * len)) || (rc = buf(vgpa_ctx::PF_MOM, (size_t)B * len))) return rc;
+    SampleArgs w = SampleArgs{};      // the model's walk: of the filter's arguments the factors and theta
+    w.kind = VGPA_PATHS_MODEL; w.model = a.model; w.D = D; w.Np = a.Np; w.batch = B; w.dt = a.dt; w.seed = q.seed;
+    w.R = a.R; w.R_stride = a.R_stride; w.R_diag = a.R_diag; w.theta_v = a.theta_v;
+    for (int i = 0; i < kMaxTheta; i++) w.theta[i] = a.theta[i];
+    w.stride = q.stride; w.n_keep = h_keep; w.k_begin = k0; w.k_end = k0 + q.horizon; w.pf_x = cur; w.pf_n = q.n_paths;
+    if (n_draw > 0) {
+      if ((rc = buf(vgpa_ctx::PF_SLOTS, (n_slots + 1) / 2)) || (rc = grow(c, &c->d_sp_out, &c->sp_out_n, n_mem))) return rc;
+      int32_t* table = reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_SLOTS]);
+      if (q.final_slots) {
+        if ((rc = upload(c, table, q.final_slots, n_slots))) return rc;
+      } else {
+        PfArgs g = f;      // (one row: the table of a problem without observations)
+        g.n_obs = 0; g.n_obs_v = nullptr;
+        LAUNCH_TRY(c, "forecast slots launch", launch_pf_pick(g, k0 + 1, n_draw, 1, table, c->stream));
+      }
+      SampleArgs m = w;
+      m.n_paths = n_draw; m.out = c->d_sp_out; m.pf_slots = table; m.pf_slot_rows = 1;
+      LAUNCH_TRY(c, "forecast members launch", launch_sample_walk(Walk::Forecast, m, c->stream));
+      if (q.members && (rc = download(c, q.members, c->d_sp_out, n_mem))) return rc;
+      if (q.slots_out) HIP_TRY(c, hipMemcpyAsync(q.slots_out, table, n_slots * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    }
+    LAUNCH_TRY(c, "forecast weights launch", launch_pf_normalise(B, q.n_paths, f.lw, c->d_pf[vgpa_ctx::PF_WTAB], c->stream));
+    w.n_paths = q.n_paths; w.pf_wtab = c->d_pf[vgpa_ctx::PF_WTAB]; w.pf_part = c->d_pf[vgpa_ctx::PF_PART];
+    LAUNCH_TRY(c, "forecast launch", launch_sample_walk(Walk::Forecast, w, c->stream));
+    LAUNCH_TRY(c, "moments sum launch", launch_pf_moments_sum(B, blocks, len, w.pf_part, c->d_pf[vgpa_ctx::PF_MOM], c->stream));
+    if ((rc = download(c, q.fc_moments, c->d_pf[vgpa_ctx::PF_MOM], (size_t)B * len))) return rc;
+    if (q.state_end && (rc = download(c, q.state_end, cur, (size_t)B * n * D))) return rc;
+    return VGPA_OK;
+  }
 };
+
+// vgpa_particle_forecast from a given cloud: no filter runs
+static int forecast_run(vgpa_ctx* c, const ParticleRequest& q) {
+  ParticleRun r{c, q};
+  int rc;
+  if ((rc = r.given_cloud()) || (rc = r.forecast())) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return VGPA_OK;
+}
 
 static int particle_run(vgpa_ctx* c, const ParticleRequest& q) {
   if (!c) return VGPA_ERR_ARG;
@@ -1768,12 +1856,17 @@ static int particle_run(vgpa_ctx* c, const ParticleRequest& q) {
   int rc;
   if ((rc = r.setup()) || (rc = r.filter()) || (q.moments && (rc = r.moments())) || (q.paths && (rc = r.trajectories()))) return rc;
   const size_t n = (size_t)n_paths, BnD = (size_t)B * n * D;
+  if (q.forecast) {      // (the filter's final cloud leaves before the forecast carries it on in place)
+    if ((rc = download(c, q.state, r.cur, BnD))) return rc;
+    r.k0 = Np - 1;
+    if ((rc = r.forecast())) return rc;
+  }
   if (q.with_stats && q.mean) {
     LAUNCH_TRY(c, "path statistics mean launch", launch_pf_stats_mean(D, B, n_paths, r.f.lw, r.st_cur, c->d_pf[vgpa_ctx::PF_MEAN], c->stream));
     if ((rc = download(c, q.mean, c->d_pf[vgpa_ctx::PF_MEAN], (size_t)B * 3 * D))) return rc;
   }
   if (q.with_stats && q.stats && (rc = download(c, q.stats, r.st_cur, 3 * BnD))) return rc;
-  if ((rc = download(c, q.logw, r.f.lw, (size_t)B * n)) || (rc = download(c, q.state, r.cur, BnD))) return rc;
+  if ((rc = download(c, q.logw, r.f.lw, (size_t)B * n)) || (!q.forecast && (rc = download(c, q.state, r.cur, BnD)))) return rc;
   if (q.ess && (rc = download(c, q.ess, r.f.h_ess, (size_t)B * M))) return rc;
   if (q.resampled && M > 0) HIP_TRY(c, hipMemcpyAsync(q.resampled, r.f.h_flag, (size_t)B * M * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   if (q.ancestors && M > 0) HIP_TRY(c, hipMemcpyAsync(q.ancestors, r.f.h_anc, (size_t)B * M * n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
@@ -1821,6 +1914,45 @@ int vgpa_particle_paths(vgpa_ctx* c, const double* x, const double* x0, int32_t 
   if (n_draw < 1) return fail(c, VGPA_ERR_ARG, "n_draw must be at least 1 (n_draw = %d)", n_draw);
   ParticleRequest q{x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled};
   q.stride = stride; q.n_draw = n_draw; q.final_slots = final_slots; q.paths = paths; q.slots_out = slots;
+  return particle_run(c, q);
+}
+
+// The filtered cloud, or a given one, carried forward under the model SDE (see vgpa_hip.h)
+int vgpa_particle_forecast(vgpa_ctx* c, const double* x, const double* x0, int32_t n_paths, uint64_t seed, double ess_fraction,
+                           const double* prior_mu, const double* prior_tau, const double* cloud, const double* cloud_logw, int32_t index0,
+                           int32_t horizon, int32_t stride, int32_t n_draw, const int32_t* final_slots, double* logw, double* state, double* ess,
+                           int32_t* resampled, double* moments, double* members, int32_t* slots, double* state_end) {
+  if (!c) return VGPA_ERR_ARG;
+  if (!moments) return fail(c, VGPA_ERR_ARG, "null argument");
+  if (c->cfg.model == VGPA_MODEL_NONE) return fail(c, VGPA_ERR_ARG, "context has no stochastic model: no model SDE to carry the particles forward");
+  if (horizon < 0 || stride < 1) return fail(c, VGPA_ERR_ARG, "horizon must be at least 0 and stride at least 1 (horizon = %d, stride = %d)", horizon, stride);
+  if (n_draw < 0) return fail(c, VGPA_ERR_ARG, "n_draw must be at least 0 (n_draw = %d)", n_draw);
+  if (n_paths < 1) return fail(c, VGPA_ERR_ARG, "n_paths must be at least 1 (n_paths = %d)", n_paths);
+  if (cloud && index0 < 0) return fail(c, VGPA_ERR_ARG, "index0 must be at least 0 (index0 = %d)", index0);
+  const int D = c->D, B = c->B;
+  const int64_t k0 = cloud ? (int64_t)index0 : (int64_t)c->Np - 1;
+  // (the uniform of drawn slots comes from grid index k0 + 1, which must be one as well)
+  if (k0 + (int64_t)horizon > 0x7fffffffLL || (n_draw > 0 && !final_slots && k0 + 1 > 0x7fffffffLL))
+    return fail(c, VGPA_ERR_ARG, "the forecast ends beyond grid index 2^31 - 1 (it starts at %lld, horizon = %d)", (long long)k0, horizon);
+  if (n_draw > 0 && final_slots)
+    for (size_t e = 0; e < (size_t)B * n_draw; e++)
+      if (final_slots[e] < 0 || final_slots[e] >= n_paths)
+        return fail(c, VGPA_ERR_ARG, "problem %zu: slot %d of member %zu does not lie in [0, %d)", e / n_draw, final_slots[e], e % n_draw, n_paths);
+  if (D > kMaxSmallD) return fail(c, VGPA_ERR_UNSUPPORTED, "the particle forecast is built for D <= %d (D = %d)", kMaxSmallD, D);
+  const int h_keep = horizon / stride + 1;      // the launch limits of the two walks and of the final sum, the size of the members: before any work
+  if (sample_segment_blocks(D, n_paths) > 65535 || sample_segment_blocks(D, n_draw) > 65535)
+    return fail(c, VGPA_ERR_UNSUPPORTED, "the particle forecast is built for at most %d particles and members per problem at D = %d (n_paths = %d, n_draw = %d)",
+                65535 * (D <= kMaxLaneD ? 256 : 64), D, n_paths, n_draw);
+  if (((size_t)B * ((size_t)h_keep * 2 * D) + 255) / 256 > 0x7fffffffu)
+    return fail(c, VGPA_ERR_UNSUPPORTED, "the forecast moments are built for at most 2^39 entries (batch %d, %d kept steps, D = %d): use a larger stride", B, h_keep, D);
+  if ((double)B * (double)n_draw * (double)h_keep * (double)D > 34359738368.0)
+    return fail(c, VGPA_ERR_UNSUPPORTED, "the forecast members are built for at most 2^35 entries (batch %d, %d members, %d kept steps, D = %d): use a larger stride",
+                B, n_draw, h_keep, D);
+  ParticleRequest q{x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled};
+  q.stride = stride; q.n_draw = n_draw; q.final_slots = final_slots; q.slots_out = slots;
+  q.forecast = true; q.horizon = horizon; q.cloud = cloud; q.cloud_logw = cloud_logw; q.index0 = index0;
+  q.fc_moments = moments; q.members = members; q.state_end = state_end;
+  if (cloud) return forecast_run(c, q);
   return particle_run(c, q);
 }
 

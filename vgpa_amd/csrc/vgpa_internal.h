@@ -222,9 +222,9 @@ struct ReduceArgs {
   const double* div_v;      // [B] per-problem div (1-D models: sigma_p), or nullptr
 };
 
-// Euler-Maruyama sample paths (sample.hip): x_k = x_{k-1} + dt drift_{k-1}(x_{k-1}) + R xi_k on the context's grid.  The six things a launch
+// Euler-Maruyama sample paths (sample.hip): x_k = x_{k-1} + dt drift_{k-1}(x_{k-1}) + R xi_k on the context's grid.  The seven things a launch
 // can do with them (the table at the top of sample.hip); the host names one at every launch_sample_walk, and SampleArgs says what each reads
-enum class Walk { Plain, Weighted, Segment, SegmentStats, Replay, Lineage };
+enum class Walk { Plain, Weighted, Segment, SegmentStats, Replay, Lineage, Forecast };
 struct SampleArgs {
   int kind, model, D, Np, batch, n_paths, stride, n_keep;
   double dt;
@@ -277,6 +277,13 @@ struct SampleArgs {
   // stretch j of its problem's own observation row (obs_t / n_obs as above): row 0 for the start, the next row behind every observation
   const int32_t* pf_slots;  // [B][pf_slot_rows][n_paths]
   int pf_slot_rows;
+  // Walk::Forecast (vgpa_particle_forecast): the model SDE (model kind, diagonal R, theta / theta_v) carried from the
+  // cloud pf_x [B][pf_n][D] at absolute grid index k_begin to k_end, lane i drawing from the counters (k_begin + h, word, p, j).  One of
+  // two launches.  The cloud: n_paths = pf_n lanes per problem, word = the slot, pf_part set: at h = 0, stride, 2 stride, ... workgroup
+  // (p, blk) stores sum_i W_i x_i and sum_i W_i x_i^2 over its own slots with W = pf_wtab [B][pf_n] (n_keep rows), and x(k_end) goes back
+  // to pf_x.  The members: n_paths = K lanes per problem, out and pf_slots [B][1][K] set: lane m starts from slot s = pf_slots[p][0][m] of
+  // the cloud, draws with word s and stores as Walk::Plain stores; pf_x is read only
+  int pf_n;
 };
 // hipErrorInvalidValue where a field the walk reads is missing or out of range, where a field that belongs to another walk is set, and for
 // D = 2 in every walk but Plain (no stochastic model has D = 2)
@@ -328,6 +335,8 @@ hipError_t launch_pf_gather(const PfArgs& a, hipStream_t st);
 hipError_t launch_pf_pick(const PfArgs& a, int Np, int K, int rows, int32_t* table, hipStream_t st);
 hipError_t launch_pf_trace(const PfArgs& a, int K, int rows, int32_t* table, hipStream_t st);
 bool sample_lineages_fit(int D, int batch, int K);
+// vgpa_particle_forecast (sample.hip: k_pf_normalise): w [B][n_paths] = exp(lw - max lw) / the sum of these, per problem
+hipError_t launch_pf_normalise(int batch, int n_paths, const double* lw, double* w, hipStream_t st);
 // out [B][len] = sum over blk, in block order, of part [B][n_blocks][len]
 hipError_t launch_pf_moments_sum(int batch, int n_blocks, size_t len, const double* part, double* out, hipStream_t st);
 

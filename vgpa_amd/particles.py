@@ -30,10 +30,15 @@ genealogy, for what is no mean or variance: exceedance and first-passage probabi
 trajectory is the lineage of one final slot; the final slots are drawn from the final weights by systematic resampling (equally weighted
 draws) or given by the caller (weighted by their final weights).  The same caveat holds: on collapsing clouds the early stretches of all K
 trajectories are one and the same path -- distinct() counts how many different ones each stretch has.
+
+Forecast: one problem's record of vgpa_particle_forecast -- a weighted cloud (the filter's final one, or a given one)
+carried past the window under the model SDE: mean and variance on the forecast grid, reduced on the device, a handful of member
+trajectories, and the cloud at the end of the horizon, from which the next forecast can go on (cloud=state, log_w=log_w,
+index0=grid[-1] when the last step is kept).  The weights do not change: there is nothing to weigh the particles against.
 """
 import numpy as np
 
-__all__ = ["ParticleFilterResult", "PathStatistics", "SmoothingMoments", "SmoothingPaths", "descendant_weights"]
+__all__ = ["ParticleFilterResult", "PathStatistics", "SmoothingMoments", "SmoothingPaths", "Forecast", "descendant_weights"]
 
 
 def descendant_weights(log_w, ancestors, resampled):
@@ -332,3 +337,59 @@ class SmoothingPaths(object):
         """logsumexp(log_w) - log n, as ParticleFilterResult.log_evidence()"""
         top = np.max(self.log_w)
         return float(top + np.log(np.sum(np.exp(self.log_w - top))) - np.log(self.log_w.size))
+
+
+class Forecast(object):
+    """log_w (n,): the unnormalised log-weights of the cloud, unchanged by the forecast; moments (h_keep, 2, D): sum_i W_i x_i and
+    sum_i W_i x_i^2 at the steps h = 0, stride, 2 stride, ... <= horizon behind the absolute grid index index0; members (K, h_keep, D): the
+    trajectories of the slots `slots` (K,) on the same steps (K may be 0); state (n, D): the cloud at index0 + horizon; t0, dt: the time of
+    grid index 0 and the grid's step.  drawn: the slots were drawn from the weights (equally weighted members), else given.  single_dim: a
+    1-D model, the last axis of mean / var / members / state is dropped."""
+
+    def __init__(self, log_w, moments, members, slots, state, index0, horizon, stride, dt, t0=0.0, drawn=True, single_dim=False) -> None:
+        self.log_w = np.asarray(log_w, dtype=float).ravel()
+        if self.log_w.size < 1:
+            raise ValueError(" Forecast: at least one particle.")
+        self.index0, self.horizon, self.stride = int(index0), int(horizon), int(stride)
+        if self.index0 < 0 or self.horizon < 0 or self.stride < 1:
+            raise ValueError(" Forecast: index0 and horizon must be at least 0, stride at least 1.")
+        h_keep = self.horizon // self.stride + 1
+        self.moments = np.asarray(moments, dtype=float)
+        if self.moments.ndim != 3 or self.moments.shape[:2] != (h_keep, 2):
+            raise ValueError(" Forecast: moments must be (h_keep, 2, D).")
+        d = self.moments.shape[2]
+        full, cloud = np.asarray(members, dtype=float), np.asarray(state, dtype=float)
+        if full.ndim != 3 or full.shape[1:] != (h_keep, d):
+            raise ValueError(" Forecast: members must be (K, h_keep, D).")
+        if cloud.shape != (self.log_w.size, d):
+            raise ValueError(" Forecast: state must be (n, D).")
+        self.slots = np.asarray(slots, dtype=np.int64).ravel()
+        if self.slots.size != full.shape[0] or (self.slots.size and (self.slots.min() < 0 or self.slots.max() >= self.log_w.size)):
+            raise ValueError(" Forecast: slots must be K slots in [0, n).")
+        self.single_dim = bool(single_dim)
+        self.members = full[..., 0] if self.single_dim else full
+        self.state = cloud[..., 0] if self.single_dim else cloud
+        self.dt, self.t0, self.drawn = float(dt), float(t0), bool(drawn)
+
+    def __len__(self):
+        return self.log_w.size
+
+    @property
+    def grid(self):
+        """the absolute grid indices of the kept steps: index0, index0 + stride, ..."""
+        return self.index0 + np.arange(0, self.horizon + 1, self.stride)
+
+    @property
+    def times(self):
+        return self.t0 + self.dt * self.grid
+
+    @property
+    def mean(self):
+        m = self.moments[:, 0].copy()
+        return m[..., 0] if self.single_dim else m
+
+    @property
+    def var(self):
+        """second moment - mean^2, clipped at 0"""
+        v = np.maximum(self.moments[:, 1] - self.moments[:, 0] ** 2, 0.0)
+        return v[..., 0] if self.single_dim else v

@@ -259,6 +259,44 @@ class VarGP(object):
         out = [self._paths_record(res, k, stride, slots is None) for k in range(res["log_w"].shape[0])]
         return out[0] if self.batch == 1 else out
 
+    def _forecast_record(self, res, k, horizon, stride, drawn):
+        """One problem's Forecast from row k of Context.particle_forecast's dict"""
+        from .particles import Forecast
+        return Forecast(res["log_w"][k], res["moments"][k], res["members"][k], res["slots"][k], res["state_end"][k], res["index0"], horizon, stride,
+                        float(self.fwd_ode.dt), float(np.ravel(self.model.time_window)[0]), drawn, self.model.single_dim)
+
+    def _forecast_source(self, source, n_paths, seed, xx, x0, cloud, log_w, index0):
+        """The cloud of forecast(): (cloud, log_w, index0) as Context.particle_forecast takes them; cloud None: the filter's"""
+        if source not in ("filter", "posterior"):
+            raise ValueError(f" Unknown source of the forecast -> {source}")
+        if source == "posterior":      # the end points of the posterior process's paths, equally weighted, at the last grid index
+            if cloud is not None or n_paths is None:
+                raise ValueError(" forecast: source='posterior' draws its own cloud of n_paths particles.")
+            ends = self._context().sample_paths("posterior", n_paths, seed, stride=self.dim_n - 1 if self.dim_n > 1 else 1, x=xx, x0=x0)
+            return ends[:, :, -1, :], None, self.dim_n - 1
+        return cloud, log_w, index0
+
+    def forecast(self, horizon, n_paths=None, seed=0, stride=1, n_draw=0, ess_fraction=0.5, x=None, x0=None, source="filter", cloud=None,
+                 log_w=None, index0=None, slots=None):
+        """The forecast past the window: a weighted cloud carried `horizon` steps forward under the model SDE on the device, a
+        particles.Forecast (with batch > 1 a list, one per problem) with mean and var on the forecast grid, n_draw member trajectories
+        (slots=None: of slots drawn from the weights) and the cloud at the end.  source="filter": the final cloud of particle_filter with
+        the same n_paths, seed, ess_fraction, x, x0, taken where it lies on the device; source="posterior": the end points of
+        sample_paths(n_paths, seed, x=x, x0=x0), equally weighted.  cloud (n, D), log_w (n,), index0: a given cloud at that absolute grid
+        index (None: the last one of the window) -- the state and log_w of an earlier forecast continue it."""
+        xx = None if x is None else np.asarray(x, dtype=float)
+        cloud, log_w, index0 = self._forecast_source(source, n_paths, seed, xx, x0, cloud, log_w, index0)
+        if cloud is not None:
+            cloud = np.asarray(cloud, dtype=float)
+            cloud = cloud.reshape(cloud.shape + (1,)) if self.model.single_dim and cloud.shape[-1:] != (1,) else cloud
+            res = self._context().particle_forecast(horizon, seed=seed, stride=stride, n_draw=n_draw, cloud=cloud, log_w=log_w, index0=index0,
+                                                    slots=slots)
+        else:
+            res = self._context().particle_forecast(horizon, n_paths, seed, stride=stride, n_draw=n_draw, ess_fraction=ess_fraction, x=xx, x0=x0,
+                                                    slots=slots, prior=self._prior())
+        out = [self._forecast_record(res, k, horizon, stride, slots is None) for k in range(res["moments"].shape[0])]
+        return out[0] if self.batch == 1 else out
+
     def particle_fit_theta(self, n_paths, seed, iters, ess_fraction=0.5, refit=True, pooled=False):
         """Particle EM for the drift parameters (ProblemBatch.particle_fit_theta on a batch of one): (theta, trace), theta in the shape of
         model.theta."""
