@@ -324,6 +324,27 @@ int vgpa_particle_moments(vgpa_ctx* ctx, const double* x_or_null, const double* 
                           double ess_fraction, const double* prior_mu_or_null, const double* prior_tau_or_null, double* logw, double* state,
                           double* moments, double* lineage_ess_or_null, double* ess_or_null, int32_t* resampled_or_null);
 
+/* The smoothing mean and the full second-moment matrices on the time grid under the genealogy of the particle filter:
+ * what vgpa_particle_moments estimates, with every cross moment E[x_k x_k^T | y] in place of its diagonal -- the estimate the matrices S_t of
+ * the variational posterior are held against.  The same three steps on the device; the second walk forms, per kept grid index, X diag(W) X^T
+ * of the particle states (5 <= D <= 64: on the fp64 matrix cores).  Stretches, x_i(k), W^j_i and the kept grid indices are those of
+ * vgpa_particle_moments.
+ *   mean             host, [batch][n_keep][D], n_keep = (Np-1) / stride + 1: mean[k][a] = sum_i W^{j(k)}_i x_i(k)[a]
+ *   second           host, [batch][n_keep][D][D]: second[k][a][b] = sum_i W^{j(k)}_i x_i(k)[a] x_i(k)[b], the raw moment -- the covariance
+ *                    second - mean mean^T is the caller's to form.  One triangle is computed and mirrored: (a, b) and (b, a) hold the same
+ *                    bits.  Two calls with the same arguments give the same bits
+ *   lineage_ess_or_null  as in vgpa_particle_moments, and bit-identical to its result with the same arguments
+ *   logw, state, ess_or_null, resampled_or_null and every other argument: as in vgpa_particle_filter, and bit-identical to its results with
+ *   the same arguments.  With x NULL the cached state is read and not written
+ * Device memory: the workgroups' partial sums take batch * G * n_keep * (D + D (D + 1) / 2) doubles, G = ceil(n_paths / 256) workgroups per
+ * problem at D <= 4 and ceil(n_paths / 64) above; their sum batch * n_keep * (D + D (D + 1) / 2), the results batch * n_keep * D (D + 1).
+ * The first grows with D^2 and with n_paths: a larger stride is the remedy.
+ * Errors: as vgpa_particle_moments, with VGPA_ERR_ARG for a NULL mean or second; VGPA_ERR_UNSUPPORTED, before any work, for more than 65535
+ * workgroups per problem or more than 2^39 - 256 entries of second; D > 64 and a dense Sigma are refused as in vgpa_particle_filter. */
+int vgpa_particle_covariance(vgpa_ctx* ctx, const double* x_or_null, const double* x0_or_null, int32_t n_paths, int32_t stride, uint64_t seed,
+                             double ess_fraction, const double* prior_mu_or_null, const double* prior_tau_or_null, double* logw, double* state,
+                             double* mean, double* second, double* lineage_ess_or_null, double* ess_or_null, int32_t* resampled_or_null);
+
 /* Whole smoothing trajectories on the time grid, drawn from the genealogy of the particle filter: K = n_draw complete
  * paths of the Euler-discretised model as the filter's surviving lineages hold them, for path functionals that are no mean or variance.
  * Three steps on the device behind the filter of vgpa_particle_filter, which runs unchanged with its ancestors kept: the final slots; their

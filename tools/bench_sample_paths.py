@@ -1,11 +1,12 @@
 """
 Time of Context.sample_paths (vgpa_sample_paths), Context.sample_paths_weighted (vgpa_sample_paths_weighted), Context.particle_filter
 (vgpa_particle_filter), Context.particle_statistics (vgpa_particle_statistics), Context.particle_moments (vgpa_particle_moments),
-Context.particle_paths (vgpa_particle_paths) and Context.particle_forecast (vgpa_particle_forecast) on their jobs, one JSON line.
+Context.particle_covariance (vgpa_particle_covariance), Context.particle_paths (vgpa_particle_paths) and Context.particle_forecast (vgpa_particle_forecast) on their jobs, one JSON line.
 
     python tools/bench_sample_paths.py [--rounds 3] [--calls 5] [--jobs a,b,c,aw,aw0,bw,bw0,af64_0,af64_5,af1024_0,af1024_5,bf64_0,...]
     python tools/bench_sample_paths.py --statistics [--filter-problems 4096]      # the as* and bs* jobs
     python tools/bench_sample_paths.py --moments [--filter-problems 4096]         # the am* and bm* jobs
+    python tools/bench_sample_paths.py --covariance [--filter-problems 4096]      # the ac* and bc* jobs
     python tools/bench_sample_paths.py --paths [--filter-problems 4096] [--paths-strides 1,10]      # the ap* and bp* jobs, once per stride
     python tools/bench_sample_paths.py --forecast [--forecast-problems 512] [--forecast-particles 4096] [--forecast-horizon 1000]
 
@@ -26,6 +27,12 @@ Context.particle_paths (vgpa_particle_paths) and Context.particle_forecast (vgpa
              ess_fraction 0.5, every s-th grid index kept (s = 1, 10 or 1004: beyond the grid, index 0 alone is reduced -- the replay
              without its reductions), and particle_filter with the same arguments, the two calls alternating inside every round: both
              times, their ratio, the partial-sum buffer on the device and the result copied
+
+  ac<n>_<s>, bc<n>_<s>   (--covariance selects all ten) particle_covariance on the contexts of a and b: n = 64 or 1024 particles per problem,
+             ess_fraction 0.5, every s-th grid index kept -- s = 10 or 1004, and on the context of b also 1 (on a, D = 40, the partial
+             sums of stride 1 take 3.5 GB at n = 64 and 56 GB at n = 1024, the matrices 6.6 GB to copy) --, and particle_moments and
+             particle_filter with the same arguments, the three calls alternating inside every round: the three times, the ratios to
+             particle_moments and to particle_filter, the partial-sum buffer on the device and the result copied
 
   ap<n>_<K>, bp<n>_<K>   (--paths selects all eight, each once per stride of --paths-strides) particle_paths on the contexts of a and b:
              n = 64 or 1024 particles per problem, ess_fraction 0.5, K = 16 or 64 trajectories per problem drawn from the final weights,
@@ -70,6 +77,7 @@ WEIGHTED = {"aw": ("a", True), "aw0": ("a", False), "bw": ("b", True), "bw0": ("
 FILTER = {f"{t}f{n}_{f}": (t, n, 0.1 * f) for t in "ab" for n in (64, 1024) for f in (0, 5)}      # job -> (context of, particles, ess_fraction)
 STATS = {f"{t}s{n}_{f}": (t, n, 0.1 * f) for t in "ab" for n in (64, 1024) for f in (0, 5)}       # job -> as FILTER
 MOMENTS = {f"{t}m{n}_{s}": (t, n, s) for t in "ab" for n in (64, 1024) for s in (1, 10, N_PTS + 3)}          # job -> (context of, particles, stride)
+COV = {f"{t}c{n}_{s}": (t, n, s) for t in "ab" for n in (64, 1024) for s in (1, 10, N_PTS + 3) if t == "b" or s > 1}          # job -> as MOMENTS
 PATHS = {f"{t}p{n}_{k}": (t, n, k) for t in "ab" for n in (64, 1024) for k in (16, 64)}           # job -> (context of, particles, trajectories)
 
 
@@ -147,10 +155,10 @@ def run(job, rounds, calls, numpy_problems, cache, filter_problems=0, paths_stri
     from bench_problem_batch import StreamTimer, make_contexts
     twin, stored = WEIGHTED.get(job, (job, True))
     weighted = job in WEIGHTED
-    if job in FILTER or job in STATS or job in MOMENTS or job in PATHS:
-        twin = (FILTER.get(job) or STATS.get(job) or MOMENTS.get(job) or PATHS[job])[0]
+    if job in FILTER or job in STATS or job in MOMENTS or job in COV or job in PATHS:
+        twin = (FILTER.get(job) or STATS.get(job) or MOMENTS.get(job) or COV.get(job) or PATHS[job])[0]
     name, d, B, kind, n_paths, stride = JOBS[twin]
-    if (job in FILTER or job in STATS or job in MOMENTS or job in PATHS) and twin == "b" and filter_problems:
+    if (job in FILTER or job in STATS or job in MOMENTS or job in COV or job in PATHS) and twin == "b" and filter_problems:
         B = min(B, filter_problems)
     if (name, B) not in cache:                        # (b and c share a context)
         from helpers import SEED, build_problem
@@ -219,6 +227,47 @@ def run(job, rounds, calls, numpy_problems, cache, filter_problems=0, paths_stri
                 "lineage_ess_last_stretch_median": round(float(np.median(lineage[:, -1])), 2),
                 "partial_buffer_mb": round(8.0 * B * blocks * n_keep * 2 * d / 1e6, 1),
                 "d2h_mb": round(8.0 * B * (n_paths * (1 + d) + n_keep * 2 * d) / 1e6, 1)}
+    if job in COV:
+        _, n_paths, stride = COV[job]
+        calls_of = {"covariance": lambda: c.particle_covariance(n_paths, 1, stride=stride, ess_fraction=0.5),
+                    "moments": lambda: c.particle_moments(n_paths, 1, stride=stride, ess_fraction=0.5),
+                    "filter": lambda: c.particle_filter(n_paths, 1, ess_fraction=0.5)}
+        res0 = {k: f() for k, f in calls_of.items()}      # warm-up (first-use allocations)
+        n_keep = (N_PTS - 1) // stride + 1
+        cov, mom = res0["covariance"], res0["moments"]
+        assert all(np.array_equal(res0["filter"][k], cov[k]) for k in ("log_w", "state", "ess", "resampled"))
+        assert np.array_equal(cov["lineage_ess"], mom["lineage_ess"])
+        assert cov["second"].shape == (B, n_keep, d, d) and cov["mean"].shape == (B, n_keep, d) and np.all(np.isfinite(cov["second"]))
+        assert np.array_equal(cov["second"], np.swapaxes(cov["second"], 2, 3))
+        big = mom["moments"][:, :, 1]
+        assert np.all(np.abs(np.diagonal(cov["second"], axis1=2, axis2=3) - big) <= 1e-9 * big)
+        lineage = cov["lineage_ess"]
+        del cov, mom, big, res0["covariance"]["second"], res0["moments"]["moments"]
+        per_round = {k: [] for k in calls_of}
+        for _ in range(rounds):
+            ms = {k: [] for k in calls_of}
+            for _ in range(calls):
+                for k, f in calls_of.items():
+                    ms[k].append(tm.ms(f))
+            for k in calls_of:
+                per_round[k].append(float(np.median(ms[k])))
+        med = {k: float(np.median(v)) for k, v in per_round.items()}
+        blocks = (n_paths + 63) // 64 if d > 4 else (n_paths + 255) // 256
+        packed = d + d * (d + 1) // 2
+        return {"job": job, "model": name, "D": d, "Np": N_PTS, "B": B, "kind": "covariance", "n_paths": n_paths, "ess_fraction": 0.5,
+                "stride": stride, "covariance_ms_per_call": round(med["covariance"], 4), "moments_ms_per_call": round(med["moments"], 4),
+                "filter_ms_per_call": round(med["filter"], 4),
+                "ratio_to_moments": round(med["covariance"] / med["moments"], 4), "ratio_to_filter": round(med["covariance"] / med["filter"], 4),
+                "covariance_rounds_ms": [round(v, 4) for v in per_round["covariance"]],
+                "moments_rounds_ms": [round(v, 4) for v in per_round["moments"]],
+                "filter_rounds_ms": [round(v, 4) for v in per_round["filter"]],
+                "observations": int(c.n_obs), "resampled_share": round(float(res0["filter"]["resampled"].mean()), 3),
+                "lineage_ess_first_stretch_median": round(float(np.median(lineage[:, 0])), 2),
+                "lineage_ess_last_stretch_median": round(float(np.median(lineage[:, -1])), 2),
+                "partial_buffer_mb": round(8.0 * B * blocks * n_keep * packed / 1e6, 1),
+                "moments_partial_buffer_mb": round(8.0 * B * blocks * n_keep * 2 * d / 1e6, 1),
+                "d2h_mb": round(8.0 * B * (n_paths * (1 + d) + n_keep * d * (d + 1)) / 1e6, 1),
+                "moments_d2h_mb": round(8.0 * B * (n_paths * (1 + d) + n_keep * 2 * d) / 1e6, 1)}
     if job in PATHS:
         _, n_paths, n_draw = PATHS[job]
         stride = paths_stride
@@ -296,6 +345,7 @@ def main():
     ap.add_argument("--filter-problems", type=int, default=0, help="cap on B of the b context's filter jobs (0: none)")
     ap.add_argument("--statistics", action="store_true", help="run the as* and bs* jobs (particle_statistics beside particle_filter)")
     ap.add_argument("--moments", action="store_true", help="run the am* and bm* jobs (particle_moments beside particle_filter)")
+    ap.add_argument("--covariance", action="store_true", help="run the ac* and bc* jobs (particle_covariance beside particle_moments and particle_filter)")
     ap.add_argument("--paths", action="store_true", help="run the ap* and bp* jobs (particle_paths beside particle_filter)")
     ap.add_argument("--paths-strides", default="1,10", help="strides of the ap* and bp* jobs: each job runs once per stride")
     ap.add_argument("--forecast", action="store_true", help="run the forecast job (particle_forecast from a given cloud beside the model-kind sampler)")
@@ -312,6 +362,8 @@ def main():
         args.jobs = ",".join(sorted(STATS))
     if args.moments:
         args.jobs = ",".join(sorted(MOMENTS))
+    if args.covariance:
+        args.jobs = ",".join(sorted(COV))
     if args.paths:
         args.jobs = ",".join(sorted(PATHS))
     strides = [int(v) for v in args.paths_strides.split(",") if v]

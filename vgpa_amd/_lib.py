@@ -36,7 +36,7 @@ BWD_IDS = {"none": 0, "psi": 1, "q": 2}
 SYMBOLS = ["vgpa_create", "vgpa_destroy", "vgpa_last_error", "vgpa_abi_version", "vgpa_device_count",
            "vgpa_synchronize", "vgpa_stream", "vgpa_solve_fwd", "vgpa_solve_bwd", "vgpa_energy",
            "vgpa_obs_energy", "vgpa_free_energy", "vgpa_gradient", "vgpa_sweep", "vgpa_energy_parts",
-           "vgpa_fetch", "vgpa_theta_gradient", "vgpa_sample_paths", "vgpa_sample_paths_weighted", "vgpa_particle_filter", "vgpa_particle_statistics", "vgpa_particle_moments", "vgpa_particle_paths", "vgpa_particle_forecast", "vgpa_sweep_dev", "vgpa_free_energy_dev", "vgpa_sweep_enqueue", "vgpa_fetch_f",
+           "vgpa_fetch", "vgpa_theta_gradient", "vgpa_sample_paths", "vgpa_sample_paths_weighted", "vgpa_particle_filter", "vgpa_particle_statistics", "vgpa_particle_moments", "vgpa_particle_covariance", "vgpa_particle_paths", "vgpa_particle_forecast", "vgpa_sweep_dev", "vgpa_free_energy_dev", "vgpa_sweep_enqueue", "vgpa_fetch_f",
            "vgpa_dev_alloc", "vgpa_dev_free", "vgpa_memcpy_h2d", "vgpa_memcpy_d2h",
            "vgpa_profile_begin", "vgpa_profile_end", "vgpa_ld_gemm", "vgpa_ld_stage", "vgpa_gradient_dev", "vgpa_energy_full", "vgpa_set_option", "vgpa_is_streaming", "vgpa_path_info", "vgpa_set_prior_energy",
            "vgpa_set_problem_data", "vgpa_set_problem_params", "vgpa_set_problem_obs_model",
@@ -141,6 +141,8 @@ def load():
                                              c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vgpa_particle_moments.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_uint64, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.vgpa_particle_covariance.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_uint64, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vgpa_particle_paths.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_uint64, c_double, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vgpa_particle_forecast.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_uint64, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
@@ -663,6 +665,32 @@ class Context:
                                                     _ptr(mu), _ptr(tau), _ptr(log_w), _ptr(state), _ptr(moments), _ptr(lineage_ess), _ptr(ess),
                                                     _ptr(flags)))
         return {"log_w": log_w, "state": state, "ess": ess, "resampled": flags, "moments": moments, "lineage_ess": lineage_ess}
+
+    def particle_covariance(self, n_paths, seed, stride=1, ess_fraction=0.5, x=None, x0=None, prior=None):
+        """The smoothing mean and the full second-moment matrices on the grid under particle_filter's genealogy (vgpa_particle_covariance):
+        particle_moments with every cross moment.  Returns a dict: log_w, state, ess, resampled as particle_filter (bit for bit), lineage_ess
+        as particle_moments (bit for bit), mean (B, n_keep, D): sum W x, and second (B, n_keep, D, D): sum W x x^T, symmetric to the bit,
+        at the grid indices 0, stride, ...  The covariance is second - mean mean^T (SmoothingCovariance.cov)."""
+        n_paths, stride, m = int(n_paths), int(stride), self.n_obs
+        if not -2 ** 31 <= stride < 2 ** 31 or not -2 ** 31 <= n_paths < 2 ** 31:      # (the C ABI takes int32: nothing may wrap on its way there)
+            raise ValueError(f"n_paths and stride must fit into 32 bits (n_paths = {n_paths}, stride = {stride})")
+        xx = None if x is None else _c64(x)
+        if xx is not None and xx.size != self.B * self.len_x:
+            raise ValueError(f"x has {xx.size} entries, expected {self.B * self.len_x}")
+        s0 = None if x0 is None else _c64(np.broadcast_to(np.asarray(x0, dtype=np.float64).reshape(-1, self.D), (self.B, self.D)))
+        mu = tau = None
+        if prior is not None:
+            mu = _c64(np.broadcast_to(np.asarray(prior[0], dtype=np.float64).reshape(-1, self.D), (self.B, self.D)))
+            tau = _c64(np.broadcast_to(np.asarray(prior[1], dtype=np.float64).reshape(-1, self.D, self.D), (self.B, self.D, self.D)))
+        n, n_keep = max(n_paths, 0), (self.Np - 1) // max(stride, 1) + 1
+        log_w, state = np.empty((self.B, n)), np.empty((self.B, n, self.D))
+        ess, flags = np.zeros((self.B, m)), np.zeros((self.B, m), dtype=np.int32)
+        mean, second = np.empty((self.B, n_keep, self.D)), np.empty((self.B, n_keep, self.D, self.D))
+        lineage_ess = np.zeros((self.B, m + 1))
+        self._check(self._lib.vgpa_particle_covariance(self._h, _ptr(xx), _ptr(s0), n_paths, stride, int(seed) & 0xFFFFFFFFFFFFFFFF, float(ess_fraction),
+                                                       _ptr(mu), _ptr(tau), _ptr(log_w), _ptr(state), _ptr(mean), _ptr(second), _ptr(lineage_ess),
+                                                       _ptr(ess), _ptr(flags)))
+        return {"log_w": log_w, "state": state, "ess": ess, "resampled": flags, "mean": mean, "second": second, "lineage_ess": lineage_ess}
 
     def particle_paths(self, n_paths, seed, n_draw, stride=1, ess_fraction=0.5, x=None, x0=None, prior=None, slots=None):
         """n_draw whole smoothing trajectories per problem from particle_filter's genealogy (vgpa_particle_paths): the filter, the final

@@ -234,6 +234,15 @@ class ProblemBatch(object):
         res = self._context().particle_moments(n_paths, seed, stride=stride, ess_fraction=ess_fraction, x=xx, x0=x0, prior=prior)
         return [v._moments_record(res, k, stride) for k, v in enumerate(self.vgps)]
 
+    def particle_covariance(self, n_paths, seed, stride=1, ess_fraction=0.5, x=None, x0=None):
+        """One particles.SmoothingCovariance per member (VarGP.particle_covariance): the smoothing mean and full second-moment matrices on
+        the grid under the genealogy of the member's own filter, with its own data, observation times and count, prior, theta and Sigma."""
+        xx = None if x is None else self._stack(x)
+        d = self.vgps[0].dim_d
+        prior = (np.stack([v._prior()[0][0] for v in self.vgps]), np.stack([v._prior()[1][0] for v in self.vgps]).reshape(self.B, d, d))
+        res = self._context().particle_covariance(n_paths, seed, stride=stride, ess_fraction=ess_fraction, x=xx, x0=x0, prior=prior)
+        return [v._covariance_record(res, k, stride) for k, v in enumerate(self.vgps)]
+
     def particle_paths(self, n_paths, seed, n_draw, stride=1, ess_fraction=0.5, x=None, x0=None, slots=None):
         """One particles.SmoothingPaths per member (VarGP.particle_paths): n_draw whole smoothing trajectories from the genealogy of the
         member's own filter, with its own data, observation times and count, prior, theta and Sigma."""

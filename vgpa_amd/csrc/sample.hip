@@ -9,7 +9,7 @@
 //                          workgroup, the weighted sums of the wave's D x 64 tile of states taken in LDS
 // The normals are counter-based (Philox4x32-10 + Box-Muller, vgpa_hip.h): every lane generates exactly the draws it consumes, so no result
 // depends on the launch geometry.
-// K is the walk (vgpa_internal.h), stated by the host at every launch_sample_walk; every walk but the last runs on k_sample_small and
+// K is the walk (vgpa_internal.h), stated by the host at every launch_sample_walk; every walk but Forecast runs on k_sample_small and
 // k_sample_mfma:
 //   walk         | what it computes; [the kernels and k_pf_* steps that serve it besides those two]                                 | DESIGN.md
 //   Plain        | the paths, every stride-th point stored  [k_sample_l96]                                                          | s.4.8
@@ -31,6 +31,9 @@
 //                | launch walks K slots alone, each from its slot's state with its slot's counter word, stored as Plain stores      |
 //                | [k_sample_small and k_forecast_l96; k_pf_normalise: W from the log-weights, k_pf_pick: drawn slots,              |
 //                | k_pf_moments_sum]                                                                                                |
+//   ReplayCov    | the replay with the whole matrix: at every kept grid index the workgroup's sums of W x and of the lower triangle | s.4.16
+//                | of W x x^T, above D = 4 as X diag(W) X^T of each wave's 16 states on the matrix pipe  [the replay's steps;        |
+//                | k_pf_cov_unpack: the packed sums to mean [D] and second [D][D], both triangles from one entry]                   |
 #include "vgpa_internal.h"
 
 #include <type_traits>
@@ -143,10 +146,10 @@ __device__ __forceinline__ double wave_max(double v) {
 
 // What the two kernels branch on, per walk: W the walk of the weighted kind (posterior drift, diagonal R), SEG it runs (k_begin, k_end] from
 // and to pf_x, ST it carries the rows of pf_stats, MO it takes the moments of the replay, LN the counter words come from pf_slots;
-// FC it is the forecast (the model's drift from the cloud in pf_x, k_sample_small only); WS: the weight sums are formed.  The seven rows are
-// all there is: no other combination can be instantiated.
+// FC it is the forecast (the model's drift from the cloud in pf_x, k_sample_small only); CV the replay's second moments are the whole matrix
+// (with MO); WS: the weight sums are formed.  The eight rows are all there is: no other combination can be instantiated.
 struct WalkTraits {
-  bool W, SEG, ST, MO, LN, FC;
+  bool W, SEG, ST, MO, LN, FC, CV;
   constexpr bool WS() const { return W && !MO; }
 };
 constexpr WalkTraits kWalkTraits[] = {      // in the order of Walk
@@ -156,7 +159,8 @@ constexpr WalkTraits kWalkTraits[] = {      // in the order of Walk
     {true,  true,  true,  false, false, false},    // SegmentStats
     {true,  true,  false, true,  false, false},    // Replay
     {false, false, false, false, true,  false},    // Lineage
-    {false, false, false, false, false, true}};    // Forecast
+    {false, false, false, false, false, true},     // Forecast
+    {true,  true,  false, true,  false, false, true}};    // ReplayCov
 
 // Weighted: posterior kind, diagonal R: both drifts at x_{k-1}, d = g - f, and per step -sum_i d_i (eta_i + dt d_i / 2) / Sigma_ii with
 // 1 / Sigma_ii = dt / R_ii^2; the observation term at the lane's own problem's times.
@@ -167,6 +171,8 @@ constexpr WalkTraits kWalkTraits[] = {      // in the order of Walk
 // untouched); at a kept k the lanes' W x_i and (W x_i) x_i are added over the wave by a butterfly and over the four waves through four
 // LDS words per value (two sets, alternating: one barrier per kept k), in that fixed order.  A lane behind the last slot walks from 0
 // with the last slot's counters and weight 0 and stores nothing.
+// ReplayCov: the replay with D + D (D + 1) / 2 values per kept k in place of 2 D: W x_i, then (W x_a) x_b for b <= a by rows -- the same
+// butterfly, LDS words and order; the diagonal entries are the replay's own (W x_i) x_i.
 // Lineage: the unweighted posterior walk of lane m = `path`, whose counter word is not m but the entry of its column of pf_slots for the
 // stretch it is in: row 0 for the start, the next row each time the walk has completed an observation index of the lane's own problem (an
 // observation at index 0: before step 1).  No model drift, no sums.
@@ -178,7 +184,8 @@ constexpr WalkTraits kWalkTraits[] = {      // in the order of Walk
 template <int D, Walk K>
 __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
   constexpr WalkTraits T = kWalkTraits[(int)K];
-  constexpr bool W = T.W, SEG = T.SEG, ST = T.ST, MO = T.MO, LN = T.LN, FC = T.FC, WS = T.WS();
+  constexpr bool W = T.W, SEG = T.SEG, ST = T.ST, MO = T.MO, LN = T.LN, FC = T.FC, CV = T.CV, WS = T.WS();
+  constexpr int NV = CV ? D + D * (D + 1) / 2 : 2 * D;      // values a kept k reduces
   size_t gid;
   uint32_t p, path;
   bool live = true;
@@ -265,7 +272,7 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
   int par = 0;
   long long keep_k = 0, keep_slot = 0;
   if constexpr (MO) {
-    __shared__ double red_lds[2 * 2 * D * 4];
+    __shared__ double red_lds[2 * NV * 4];
     red = red_lds;
     oc = ObsCursor(a, p);
     if (!a.seg_first) oc.skip_through(a.k_begin);
@@ -280,19 +287,28 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
     keep_slot = 1; keep_k = a.stride;
   }
   auto reduce = [&](long long slot) {
-    double v[2 * D];
+    double v[NV];
+    if constexpr (CV) {
 #pragma unroll
-    for (int i = 0; i < D; i++) { v[i] = wt * x[i]; v[D + i] = v[i] * x[i]; }
-    double* r = red + par * 8 * D;
+      for (int i = 0; i < D; i++) v[i] = wt * x[i];
 #pragma unroll
-    for (int e = 0; e < 2 * D; e++) {
+      for (int i = 0; i < D; i++)
+#pragma unroll
+        for (int j = 0; j <= i; j++) v[D + i * (i + 1) / 2 + j] = v[i] * x[j];
+    } else {
+#pragma unroll
+      for (int i = 0; i < D; i++) { v[i] = wt * x[i]; v[D + i] = v[i] * x[i]; }
+    }
+    double* r = red + par * 4 * NV;
+#pragma unroll
+    for (int e = 0; e < NV; e++) {
       v[e] = wave_sum(v[e]);
       if ((threadIdx.x & 63) == 0) r[e * 4 + (threadIdx.x >> 6)] = v[e];
     }
     __syncthreads();
-    if (threadIdx.x < 2 * D) {
+    if (threadIdx.x < NV) {
       const double* q4 = r + threadIdx.x * 4;
-      a.pf_part[(((size_t)p * gridDim.y + blockIdx.y) * a.n_keep + (size_t)slot) * 2 * D + threadIdx.x] = ((q4[0] + q4[1]) + q4[2]) + q4[3];
+      a.pf_part[(((size_t)p * gridDim.y + blockIdx.y) * a.n_keep + (size_t)slot) * NV + threadIdx.x] = ((q4[0] + q4[1]) + q4[2]) + q4[3];
     }
     par ^= 1;
   };
@@ -433,12 +449,21 @@ __device__ __forceinline__ void normals_c(uint32_t k0, uint32_t k1, uint32_t k, 
 // cross-lane steps add the 16 paths of the wave, the lanes of path column 0 put their rows into red [4 waves][2][NT] -- the Zs region,
 // which a segment does not use --, and behind the next barrier the walk has anyway (the first of the next step, or one behind the loop)
 // thread t < 2 D adds the four waves in order and stores moment t / D of component t mod D.
+// ReplayCov: the replay, but at a kept k the wave's C_w = sum_{c < 16} W_c x_c x_c^T goes over the matrix pipe.  The wave
+// copies its 16 states into its own quarter of the Zs region with the columns of row i rotated by 2 (i >> 1), so that the transposed read of
+// the operands -- lane (j16, q) takes row mt 16 + j16, path 4 kk + q -- finds the 32 lanes of a half wave on 32 different bank pairs (from Xs,
+// at its row stride of 16 doubles, they sit on 4: an 8-way conflict), and holds them as xa [MT][4].  Tile (ti, tj <= ti) is four products
+// A = xa[ti][kk], B = W xa[tj][kk], the weight of path 4 kk + q fetched from its lane; MT tiles at a time go to the wave's quarter, now its
+// MT tile slots, and behind a barrier thread t adds entry t of each slot over the four waves in wave order and stores the entries of the
+// lower triangle below D.  The mean keeps the replay's cross-lane sum, its [4 waves][NT] words behind the Zs region.  Barriers per kept k:
+// 2 ceil(T / MT) - 1 with T = MT (MT + 1) / 2 tiles, that is 1, 3, 3, 5 at NT = 16, 32, 48, 64; none in a step that keeps nothing.  The last
+// round's slots are read before the next step's barriers, the next kept k writes them behind those.
 // Lineage: as in k_sample_small (diagonal R): every lane of a workgroup belongs to one problem, so all of them change their counter words
 // behind the same steps.  A lane behind the last lineage walks the last one again and stores nothing.
 template <int NT, Walk K>
 __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
   constexpr WalkTraits T = kWalkTraits[(int)K];
-  constexpr bool W = T.W, SEG = T.SEG, ST = T.ST, MO = T.MO, LN = T.LN, WS = T.WS();
+  constexpr bool W = T.W, SEG = T.SEG, ST = T.ST, MO = T.MO, LN = T.LN, CV = T.CV, WS = T.WS();
   using Sh = MfmaShape<NT>;
   constexpr int LDA = Sh::LDA, MT = Sh::MT, KT = Sh::KT, NPF = Sh::NPF;
   extern __shared__ double lds[];
@@ -622,7 +647,71 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
       pending = -1;
     }
   };
-  if constexpr (MO) { if (a.seg_first) reduce(0); }
+  auto reduce_cov = [&](long long slot) {
+    constexpr int T2 = MT * (MT + 1) / 2, ROUNDS = (T2 + MT - 1) / MT;
+    double* zw = red + w * NT * 16;       // the wave's quarter of the Zs region: the rotated copy, then its MT tile slots
+    double* mred = red + 4 * NT * 16;     // [4 waves][NT]
+#pragma unroll
+    for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const int row = mt * 16 + q + 4 * r;
+        double v1 = wt * x[mt][r];
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) v1 += __shfl_xor(v1, o);
+        if (j16 == 0) mred[w * NT + row] = v1;
+        zw[row * 16 + ((j16 + 2 * (row >> 1)) & 15)] = x[mt][r];
+      }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // (the copy is the wave's own: no barrier)
+    __builtin_amdgcn_wave_barrier();
+    double xa[MT][4], wq[4];
+#pragma unroll
+    for (int kk = 0; kk < 4; kk++) wq[kk] = __shfl(wt, kk * 4 + q);
+#pragma unroll
+    for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+      for (int kk = 0; kk < 4; kk++) {
+        const int row = mt * 16 + j16;
+        xa[mt][kk] = zw[row * 16 + ((kk * 4 + q + 2 * (row >> 1)) & 15)];
+      }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // (the operands are read before the slots overwrite the copy)
+    __builtin_amdgcn_wave_barrier();
+    const size_t NVc = (size_t)D + (size_t)D * (D + 1) / 2;
+    double* dst = a.pf_part + (((size_t)p * gridDim.y + blockIdx.y) * a.n_keep + (size_t)slot) * NVc;
+#pragma unroll
+    for (int rd = 0; rd < ROUNDS; rd++) {
+      if (rd > 0) __syncthreads();      // (the slots of the round before have been read)
+#pragma unroll
+      for (int ti = 0; ti < MT; ti++)
+#pragma unroll
+        for (int tj = 0; tj <= ti; tj++) {
+          const int t = ti * (ti + 1) / 2 + tj;
+          if (t / MT == rd) {
+            d4 acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int kk = 0; kk < 4; kk++) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(xa[ti][kk], wq[kk] * xa[tj][kk], acc, 0, 0, 0);
+#pragma unroll
+            for (int r = 0; r < 4; r++) zw[(t % MT) * 256 + r * 64 + lane] = acc[r];
+          }
+        }
+      __syncthreads();
+      if (rd == 0 && tid < D) dst[tid] = ((mred[tid] + mred[NT + tid]) + mred[2 * NT + tid]) + mred[3 * NT + tid];
+#pragma unroll
+      for (int ti = 0; ti < MT; ti++)
+#pragma unroll
+        for (int tj = 0; tj <= ti; tj++) {
+          const int t = ti * (ti + 1) / 2 + tj;
+          if (t / MT == rd) {
+            const double* s0 = red + (t % MT) * 256 + tid;      // entry tid of the tile: row (lane >> 4) + 4 (tid >> 6), column lane & 15
+            const double val = ((s0[0] + s0[NT * 16]) + s0[2 * NT * 16]) + s0[3 * NT * 16];
+            const int ra = ti * 16 + q + 4 * w, cb = tj * 16 + j16;
+            if (ra < D && cb <= ra) dst[D + (size_t)ra * (ra + 1) / 2 + cb] = val;
+          }
+        }
+    }
+  };
+  if constexpr (MO && !CV) { if (a.seg_first) reduce(0); }
+  if constexpr (CV) { if (a.seg_first) reduce_cov(0); }
 
   int until = a.stride;
   for (int k = k_first; k < k_stop; k++) {
@@ -688,7 +777,7 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
       for (int r = 0; r < 4; r++) x[mt][r] = (x[mt][r] + a.dt * (bs[mt * 16 + q + 4 * r] - acc[r])) + nz[r];
     }
     __syncthreads();
-    if constexpr (MO) flush();
+    if constexpr (MO && !CV) flush();
     if (more) {
 #pragma unroll
       for (int n = 0; n < NPF; n++) { const int e = tid + 256 * n; if (e < DD) As[(e / D) * LDA + e % D] = pa[n]; }
@@ -703,8 +792,11 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
     if constexpr (WS) {
       if (k == oc.next) observe();
     }
-    if constexpr (MO) {
+    if constexpr (MO && !CV) {
       if (k == keep_k) { reduce(keep_slot++); keep_k += a.stride; }
+    }
+    if constexpr (CV) {
+      if (k == keep_k) { reduce_cov(keep_slot++); keep_k += a.stride; }
     }
     if constexpr (LN) {
       if (k == oc.next) { oc.advance(); word = (uint32_t)lin[(size_t)oc.cur * a.n_paths]; }
@@ -712,7 +804,7 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
   }
   if constexpr (MO) {
     __syncthreads();
-    flush();
+    if constexpr (!CV) flush();
     put(a.pf_x + ((size_t)p * a.n_paths + path0) * D, (size_t)D);      // (Xs holds x_{k_end} behind the loop's last barrier)
   } else if constexpr (W) {
     pw += __shfl_xor(pw, 16); pw += __shfl_xor(pw, 32);
@@ -1189,6 +1281,18 @@ __global__ __launch_bounds__(256) void k_pf_moments_sum(int n_blocks, size_t len
   out[g] = s;
 }
 
+// packed [rows][V], V = D + D (D + 1) / 2 (the mean, then the lower triangle by rows) -> mean [rows][D], second [rows][D][D]: one thread per
+// entry of second, (a, b) and (b, a) from the one packed entry; the threads of column 0 also carry the mean over
+__global__ __launch_bounds__(256) void k_pf_cov_unpack(int D, size_t total, const double* packed, double* mean, double* second) {
+  const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= total) return;
+  const size_t DD = (size_t)D * D, row = g / DD, e = g - row * DD, ea = e / D, eb = e - ea * D;
+  const size_t hi = ea > eb ? ea : eb, lo = ea > eb ? eb : ea;
+  const double* src = packed + row * ((size_t)D + (size_t)D * (D + 1) / 2);
+  second[g] = src[D + hi * (hi + 1) / 2 + lo];
+  if (eb == 0) mean[row * D + ea] = src[ea];
+}
+
 // ---- the smoothing trajectories: the final slots, their genealogy (the lineage walk is an instantiation of the samplers above) ----------
 // The final slots of K equally weighted trajectories, one workgroup per problem with c observations of its own:
 // systematic resampling from the final weights as k_pf_resample does it -- w_i = exp(lw_i - max lw), cum and S = cum_{n-1} by the same
@@ -1260,7 +1364,8 @@ hipError_t launch_walk(const SampleArgs& a, hipStream_t st) {
   } else {
     auto mfma = [&](auto nt) {
       constexpr int NT = decltype(nt)::value;
-      const size_t lds = MfmaShape<NT>::lds_doubles(!a.R_diag) * sizeof(double);
+      // (ReplayCov: the [4 waves][NT] words of the mean behind the Zs region)
+      const size_t lds = (MfmaShape<NT>::lds_doubles(!a.R_diag) + (kWalkTraits[(int)K].CV ? 4 * NT : 0)) * sizeof(double);
       if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k_sample_mfma<NT, K>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       if ((a.n_paths + 63) / 64 > 65535) return hipErrorInvalidValue;      // (grid.y)
       hipLaunchKernelGGL((k_sample_mfma<NT, K>), dim3(a.batch, (a.n_paths + 63) / 64), dim3(256), lds, st, a);
@@ -1309,6 +1414,13 @@ hipError_t launch_pf_moments_sum(int batch, int n_blocks, size_t len, const doub
   const size_t total = (size_t)batch * len;
   if (batch < 1 || n_blocks < 1 || len < 1 || (total + 255) / 256 > 0x7fffffffu || !part || !out) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_pf_moments_sum, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, n_blocks, len, total, part, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_pf_cov_unpack(int D, size_t rows, const double* packed, double* mean, double* second, hipStream_t st) {
+  const size_t total = rows * (size_t)D * D;
+  if (D < 1 || D > kMaxSmallD || rows < 1 || (total + 255) / 256 > 0x7fffffffu || !packed || !mean || !second) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_pf_cov_unpack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, D, total, packed, mean, second);
   return hipGetLastError();
 }
 
@@ -1372,6 +1484,10 @@ hipError_t launch_sample_walk(Walk w, const SampleArgs& a, hipStream_t st) {
       if (!segment || !a.pf_wtab || a.pf_stats || !a.pf_part || a.stride < 1 || a.pf_rows < 1) return hipErrorInvalidValue;
       if (sample_segment_blocks(a.D, a.n_paths) > 65535) return hipErrorInvalidValue;      // (grid.y)
       return launch_walk<Walk::Replay>(a, st);
+    case Walk::ReplayCov:      // (the replay's fields; pf_part holds sample_cov_len(D) doubles per kept index)
+      if (!segment || !a.pf_wtab || a.pf_stats || !a.pf_part || a.stride < 1 || a.pf_rows < 1) return hipErrorInvalidValue;
+      if (sample_segment_blocks(a.D, a.n_paths) > 65535) return hipErrorInvalidValue;      // (grid.y)
+      return launch_walk<Walk::ReplayCov>(a, st);
     case Walk::Lineage:
       if (a.stride < 1 || a.kind != VGPA_PATHS_POSTERIOR || !a.R_diag || !a.out || !a.pf_slots || a.pf_slot_rows < 1 || a.logw) return hipErrorInvalidValue;
       if (!sample_lineages_fit(a.D, a.batch, a.n_paths)) return hipErrorInvalidValue;

@@ -169,9 +169,10 @@ struct vgpa_ctx {
   // ancestors as int32, clouds), the prior's mean and factor; vgpa_particle_statistics: the two buffers of rows and their mean;
   // vgpa_particle_moments: the descendant weights, the lineage ESS, the workgroups' partial sums, the moments; vgpa_particle_paths: the
   // slot table (int32; the trajectories themselves go through d_sp_out); vgpa_particle_forecast: of these the particles, log-weights, prefix
-  // sums, normalised weights (PF_WTAB), partial sums, moments and slot table
+  // sums, normalised weights (PF_WTAB), partial sums, moments and slot table; vgpa_particle_covariance: the buffers of the moments (the
+  // partial sums and their sum packed, sample_cov_len(D) per kept index) and PF_COV: the mean and behind it the whole matrices
   enum { PF_XA, PF_XB, PF_LW, PF_CUM, PF_ANC, PF_ESS, PF_FLAG, PF_HANC, PF_CLOUDS, PF_MU, PF_LT, PF_STA, PF_STB, PF_MEAN, PF_WTAB, PF_LESS, PF_PART,
-         PF_MOM, PF_SLOTS, PF_COUNT };
+         PF_MOM, PF_SLOTS, PF_COV, PF_COUNT };
   double* d_pf[PF_COUNT] = {};
   size_t pf_n[PF_COUNT] = {};
   // profiling
@@ -1570,7 +1571,7 @@ int vgpa_sample_paths_weighted(vgpa_ctx* c, const double* x, const double* x0, i
 
 // The guided particle filter (see vgpa_hip.h): the weighted walk of vgpa_sample_paths_weighted cut at the observation
 // indices of the batch, the particles resident between the cuts, a resampling step behind every cut that is an observation of some problem.
-// ParticleRequest: what one of the four entry points wants from it and where the results go (nullptr: not wanted).
+// ParticleRequest: what one of the entry points wants from it and where the results go (nullptr: not wanted).
 struct ParticleRequest {
   const double* x; const double* x0; int32_t n_paths; uint64_t seed; double ess_fraction; const double* prior_mu; const double* prior_tau;
   double* logw; double* state; double* ess; int32_t* resampled;      // (up to here: what every entry point has, filled in this order)
@@ -1583,6 +1584,7 @@ struct ParticleRequest {
   // moments is then fc_moments
   bool forecast; int32_t horizon; const double* cloud; const double* cloud_logw; int32_t index0;
   double* fc_moments; double* members; double* state_end;
+  bool covariance; double* cov_mean; double* cov_second;            // vgpa_particle_covariance (lineage_ess as for the moments)
 };
 
 // One run: the filter, then what the request puts behind it.  The passes share the kernels' arguments, the cuts and where the particles are.
@@ -1619,17 +1621,18 @@ struct ParticleRun {
     int rc;
     if ((rc = sample_args(c, VGPA_PATHS_POSTERIOR, q.x, q.x0, q.n_paths, 1, q.seed, true, &a))) return rc;
     const size_t n = (size_t)q.n_paths, BnD = (size_t)B * n * D, Bn = (size_t)B * n, BM = (size_t)B * M1;
-    const bool history = q.ancestors || q.moments || q.paths;
+    const bool history = q.ancestors || q.moments || q.covariance || q.paths;
     auto buf = [&](int which, size_t count) { return grow(c, &c->d_pf[which], &c->pf_n[which], count); };
     auto ints = [](size_t count) { return (count + 1) / 2; };      // int32 entries in a buffer of doubles
     if ((rc = buf(vgpa_ctx::PF_XA, BnD)) || (rc = buf(vgpa_ctx::PF_XB, BnD)) || (rc = buf(vgpa_ctx::PF_LW, Bn)) || (rc = buf(vgpa_ctx::PF_CUM, Bn)) ||
         (rc = buf(vgpa_ctx::PF_ANC, ints(Bn))) || (rc = buf(vgpa_ctx::PF_ESS, BM)) || (rc = buf(vgpa_ctx::PF_FLAG, ints(BM)))) return rc;
     if (history && (rc = buf(vgpa_ctx::PF_HANC, ints(BM * n)))) return rc;
     n_keep = (c->Np - 1) / q.stride + 1; slot_rows = M + 1; rows = M1 + 1; n_blocks = sample_segment_blocks(D, q.n_paths);
-    n_table = (size_t)B * slot_rows * (size_t)q.n_draw; n_traj = (size_t)B * (size_t)q.n_draw * ((size_t)n_keep * D); mom_len = (size_t)n_keep * 2 * D;
+    n_table = (size_t)B * slot_rows * (size_t)q.n_draw; n_traj = (size_t)B * (size_t)q.n_draw * ((size_t)n_keep * D); mom_len = (size_t)n_keep * (q.covariance ? sample_cov_len(D) : (size_t)2 * D);
     if (q.paths && ((rc = buf(vgpa_ctx::PF_SLOTS, ints(n_table))) || (rc = grow(c, &c->d_sp_out, &c->sp_out_n, n_traj)))) return rc;
-    if (q.moments && ((rc = buf(vgpa_ctx::PF_WTAB, (size_t)B * rows * n)) || (rc = buf(vgpa_ctx::PF_LESS, (size_t)B * rows)) ||
+    if ((q.moments || q.covariance) && ((rc = buf(vgpa_ctx::PF_WTAB, (size_t)B * rows * n)) || (rc = buf(vgpa_ctx::PF_LESS, (size_t)B * rows)) ||
                       (rc = buf(vgpa_ctx::PF_PART, (size_t)B * n_blocks * mom_len)) || (rc = buf(vgpa_ctx::PF_MOM, (size_t)B * mom_len)))) return rc;
+    if (q.covariance && (rc = buf(vgpa_ctx::PF_COV, (size_t)B * n_keep * D * ((size_t)D + 1)))) return rc;
     if (q.clouds && (rc = buf(vgpa_ctx::PF_CLOUDS, BM * n * D))) return rc;
     if (q.with_stats && ((rc = buf(vgpa_ctx::PF_STA, 3 * BnD)) || (rc = buf(vgpa_ctx::PF_STB, 3 * BnD)) || (rc = buf(vgpa_ctx::PF_MEAN, (size_t)B * 3 * D)))) return rc;
     f = PfArgs{};
@@ -1684,6 +1687,8 @@ struct ParticleRun {
   // The smoothing moments, behind the filter, whose ancestor history stays on the device: the descendant weights, then
   // the walk once more from the same counters (the stored ancestors in place of the resampling decisions) with the weighted sums taken at
   // every stride-th grid index, their sum over the workgroups, the downloads; `state` is then what the replay arrived at.
+  // The covariance request is the same pass with Walk::ReplayCov: the sums are the mean and the packed lower triangle,
+  // which one more launch spreads to mean [D] and second [D][D] before they leave.
   int moments() {
     const int B = c->B, M = c->M;
     int rc;
@@ -1699,12 +1704,17 @@ struct ParticleRun {
     SampleArgs w = a;
     w.stride = q.stride; w.n_keep = n_keep; w.seg_first = 1; w.pf_stats = nullptr;
     w.pf_wtab = wtab; w.pf_part = c->d_pf[vgpa_ctx::PF_PART]; w.pf_rows = rows;
-    if ((rc = cuts(Walk::Replay, "replay segment launch", w, "replay gather launch", [&](int k) {
+    if ((rc = cuts(q.covariance ? Walk::ReplayCov : Walk::Replay, "replay segment launch", w, "replay gather launch", [&](int k) {
           g.k = k; g.x_in = cur; g.x_out = other;
           return launch_pf_gather(g, c->stream);
         }))) return rc;
     LAUNCH_TRY(c, "moments sum launch", launch_pf_moments_sum(B, n_blocks, mom_len, w.pf_part, c->d_pf[vgpa_ctx::PF_MOM], c->stream));
-    if ((rc = download(c, q.moments, c->d_pf[vgpa_ctx::PF_MOM], (size_t)B * mom_len))) return rc;
+    if (q.covariance) {
+      const size_t kept = (size_t)B * n_keep, n_mean = kept * c->D;
+      double* d_mean = c->d_pf[vgpa_ctx::PF_COV];
+      LAUNCH_TRY(c, "covariance unpack launch", launch_pf_cov_unpack(c->D, kept, c->d_pf[vgpa_ctx::PF_MOM], d_mean, d_mean + n_mean, c->stream));
+      if ((rc = download(c, q.cov_mean, d_mean, n_mean)) || (rc = download(c, q.cov_second, d_mean + n_mean, n_mean * c->D))) return rc;
+    } else if ((rc = download(c, q.moments, c->d_pf[vgpa_ctx::PF_MOM], (size_t)B * mom_len))) return rc;
     if (q.lineage_ess)      // (the device's rows are M1 + 1 = M + 1, but for a context of capacity 0)
       for (int p = 0; p < (rows == M + 1 ? 1 : B); p++)
         if ((rc = download(c, q.lineage_ess + (size_t)p * (M + 1), less + (size_t)p * rows, rows == M + 1 ? (size_t)B * rows : (size_t)M + 1))) return rc;
@@ -1852,9 +1862,18 @@ static int particle_run(vgpa_ctx* c, const ParticleRequest& q) {
       return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing trajectories are built for at most 2^35 entries (batch %d, %d trajectories, %d kept grid indices, D = %d): use a larger stride",
                   B, n_draw, (Np - 1) / stride + 1, D);
   }
+  if (q.covariance && D <= kMaxSmallD) {   // ... of the covariance replay, of the sum of its packed partial sums and of the unpacking launch (grid.x each)
+    const size_t kept = (size_t)B * (size_t)((Np - 1) / stride + 1);
+    if (sample_segment_blocks(D, n_paths) > 65535)
+      return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing covariances are built for at most %d particles per problem at D = %d (n_paths = %d)",
+                  65535 * (D <= kMaxLaneD ? 256 : 64), D, n_paths);
+    if ((kept * D * D + 255) / 256 > 0x7fffffffu || (kept * sample_cov_len(D) + 255) / 256 > 0x7fffffffu)
+      return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing covariances are built for at most 2^39 - 256 entries (batch %d, %d kept grid indices, D = %d): use a larger stride",
+                  B, (Np - 1) / stride + 1, D);
+  }
   ParticleRun r{c, q};
   int rc;
-  if ((rc = r.setup()) || (rc = r.filter()) || (q.moments && (rc = r.moments())) || (q.paths && (rc = r.trajectories()))) return rc;
+  if ((rc = r.setup()) || (rc = r.filter()) || ((q.moments || q.covariance) && (rc = r.moments())) || (q.paths && (rc = r.trajectories()))) return rc;
   const size_t n = (size_t)n_paths, BnD = (size_t)B * n * D;
   if (q.forecast) {      // (the filter's final cloud leaves before the forecast carries it on in place)
     if ((rc = download(c, q.state, r.cur, BnD))) return rc;
@@ -1902,6 +1921,17 @@ int vgpa_particle_moments(vgpa_ctx* c, const double* x, const double* x0, int32_
   if (!moments) return fail(c, VGPA_ERR_ARG, "null argument");
   ParticleRequest q{x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled};
   q.stride = stride; q.moments = moments; q.lineage_ess = lineage_ess;
+  return particle_run(c, q);
+}
+
+// The smoothing mean and the full second-moment matrices on the grid under the particles' genealogy (see vgpa_hip.h)
+int vgpa_particle_covariance(vgpa_ctx* c, const double* x, const double* x0, int32_t n_paths, int32_t stride, uint64_t seed, double ess_fraction,
+                             const double* prior_mu, const double* prior_tau, double* logw, double* state, double* mean, double* second,
+                             double* lineage_ess, double* ess, int32_t* resampled) {
+  if (!c) return VGPA_ERR_ARG;
+  if (!mean || !second) return fail(c, VGPA_ERR_ARG, "null argument");
+  ParticleRequest q{x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled};
+  q.stride = stride; q.covariance = true; q.cov_mean = mean; q.cov_second = second; q.lineage_ess = lineage_ess;
   return particle_run(c, q);
 }
 

@@ -222,9 +222,9 @@ struct ReduceArgs {
   const double* div_v;      // [B] per-problem div (1-D models: sigma_p), or nullptr
 };
 
-// Euler-Maruyama sample paths (sample.hip): x_k = x_{k-1} + dt drift_{k-1}(x_{k-1}) + R xi_k on the context's grid.  The seven things a launch
+// Euler-Maruyama sample paths (sample.hip): x_k = x_{k-1} + dt drift_{k-1}(x_{k-1}) + R xi_k on the context's grid.  The eight things a launch
 // can do with them (the table at the top of sample.hip); the host names one at every launch_sample_walk, and SampleArgs says what each reads
-enum class Walk { Plain, Weighted, Segment, SegmentStats, Replay, Lineage, Forecast };
+enum class Walk { Plain, Weighted, Segment, SegmentStats, Replay, Lineage, Forecast, ReplayCov };
 struct SampleArgs {
   int kind, model, D, Np, batch, n_paths, stride, n_keep;
   double dt;
@@ -284,12 +284,17 @@ struct SampleArgs {
   // to pf_x.  The members: n_paths = K lanes per problem, out and pf_slots [B][1][K] set: lane m starts from slot s = pf_slots[p][0][m] of
   // the cloud, draws with word s and stores as Walk::Plain stores; pf_x is read only
   int pf_n;
+  // Walk::ReplayCov (vgpa_particle_covariance): Walk::Replay with the whole second-moment matrix.  Every field as for the
+  // replay, but pf_part is [B][sample_segment_blocks()][n_keep][V], V = sample_cov_len(D) = D + D (D + 1) / 2: sum_i W_i x_i(k), then the lower
+  // triangle of sum_i W_i x_i(k) x_i(k)^T packed by rows, entry (a, b <= a) at D + a (a + 1) / 2 + b.  No field of its own.
 };
 // hipErrorInvalidValue where a field the walk reads is missing or out of range, where a field that belongs to another walk is set, and for
 // D = 2 in every walk but Plain (no stochastic model has D = 2)
 hipError_t launch_sample_walk(Walk w, const SampleArgs& a, hipStream_t st);
 // workgroups per problem of a segment launch: the blocks of the replay's partial sums
 int sample_segment_blocks(int D, int n_paths);
+// doubles per kept grid index of Walk::ReplayCov's partial sums: the mean and the packed lower triangle
+inline size_t sample_cov_len(int D) { return (size_t)D + (size_t)D * (D + 1) / 2; }
 
 // the start and the resampling step of the particle filter (sample.hip: k_pf_start, k_pf_resample)
 struct PfArgs {
@@ -339,6 +344,10 @@ bool sample_lineages_fit(int D, int batch, int K);
 hipError_t launch_pf_normalise(int batch, int n_paths, const double* lw, double* w, hipStream_t st);
 // out [B][len] = sum over blk, in block order, of part [B][n_blocks][len]
 hipError_t launch_pf_moments_sum(int batch, int n_blocks, size_t len, const double* part, double* out, hipStream_t st);
+// vgpa_particle_covariance (sample.hip: k_pf_cov_unpack): packed [rows][sample_cov_len(D)], rows = B n_keep, as Walk::ReplayCov and the sum
+// leave it, to mean [rows][D] and second [rows][D][D], both triangles from the one packed entry.  One thread per entry of second, a
+// one-dimensional grid: at most (2^31 - 1) 256 = 2^39 - 256 entries
+hipError_t launch_pf_cov_unpack(int D, size_t rows, const double* packed, double* mean, double* second, hipStream_t st);
 
 // launchers (each returns hipGetLastError()) -----------------------------------------------------
 hipError_t launch_ode_generic(int method, bool fwd, const OdeArgs& a, hipStream_t st);

@@ -25,6 +25,10 @@ the stretch between observations j-1 and j is the total final weight of the slot
 with x_i(k) the state of slot i as the walk arrives at k.  These are the marginals of the forward genealogical smoother: exact in the limit
 of many particles for the Euler-discretised model, but early stretches rest on few distinct lineages -- lineage_ess says how few.
 
+SmoothingCovariance: one problem's record of vgpa_particle_covariance -- the same estimate with every cross moment:
+    E[x_k x_k^T | y] ~ sum_i W^{j(k)}_i x_i(k) x_i(k)^T,
+the full matrix the variational S_t is held against, under the same genealogy and with the same caveat.
+
 SmoothingPaths: one problem's record of vgpa_particle_paths -- K whole trajectories on the time grid from the same
 genealogy, for what is no mean or variance: exceedance and first-passage probabilities, plots of posterior draws, predictive checks.  A
 trajectory is the lineage of one final slot; the final slots are drawn from the final weights by systematic resampling (equally weighted
@@ -38,7 +42,7 @@ index0=grid[-1] when the last step is kept).  The weights do not change: there i
 """
 import numpy as np
 
-__all__ = ["ParticleFilterResult", "PathStatistics", "SmoothingMoments", "SmoothingPaths", "Forecast", "descendant_weights"]
+__all__ = ["ParticleFilterResult", "PathStatistics", "SmoothingMoments", "SmoothingCovariance", "SmoothingPaths", "Forecast", "descendant_weights"]
 
 
 def descendant_weights(log_w, ancestors, resampled):
@@ -245,6 +249,97 @@ class SmoothingMoments(object):
     @property
     def std(self):
         return np.sqrt(np.maximum(self.var, 0.0))
+
+    def lineage_ess_on_grid(self):
+        """lineage_ess of the stretch each kept grid index lies in: index k belongs to stretch #{observations before k}"""
+        return self.lineage_ess[np.searchsorted(self.obs_t, self.grid, side="left")]
+
+    def log_evidence(self):
+        """logsumexp(log_w) - log n, as ParticleFilterResult.log_evidence()"""
+        top = np.max(self.log_w)
+        return float(top + np.log(np.sum(np.exp(self.log_w - top))) - np.log(self.log_w.size))
+
+
+class SmoothingCovariance(object):
+    """log_w (n,): the final unnormalised log-weights; mean (n_keep, D): sum_i W_i x_i(k) and second (n_keep, D, D): sum_i W_i x_i(k) x_i(k)^T
+    at the grid indices k = 0, stride, 2 stride, ... < n_pts; obs_t: the problem's own observation indices; lineage_ess (M_p + 1,): 1 / sum W^2
+    of every stretch; ess, resampled over the problem's observations.  single_dim: a 1-D model, the component axes of mean / second / cov /
+    var / corr are dropped."""
+
+    def __init__(self, log_w, mean, second, stride, n_pts, obs_t, lineage_ess, ess=(), resampled=(), single_dim=False) -> None:
+        self.log_w = np.asarray(log_w, dtype=float).ravel()
+        if self.log_w.size < 1:
+            raise ValueError(" SmoothingCovariance: at least one particle.")
+        self.stride, self.n_pts = int(stride), int(n_pts)
+        if self.stride < 1 or self.n_pts < 1:
+            raise ValueError(" SmoothingCovariance: stride and n_pts must be at least 1.")
+        self._mean, self._second = np.asarray(mean, dtype=float), np.asarray(second, dtype=float)
+        n_keep = (self.n_pts - 1) // self.stride + 1
+        if self._mean.ndim != 2 or self._mean.shape[0] != n_keep or self._second.shape != (n_keep, self._mean.shape[1], self._mean.shape[1]):
+            raise ValueError(" SmoothingCovariance: mean must be (n_keep, D) and second (n_keep, D, D).")
+        self.obs_t = np.asarray(obs_t, dtype=np.int64).ravel()
+        self.lineage_ess = np.asarray(lineage_ess, dtype=float).ravel()
+        self.ess = np.asarray(ess, dtype=float).ravel()
+        self.resampled = np.asarray(resampled).astype(bool).ravel()
+        if self.lineage_ess.size != self.obs_t.size + 1 or self.ess.size != self.resampled.size:
+            raise ValueError(" SmoothingCovariance: obs_t, lineage_ess, ess and resampled do not belong together.")
+        self.single_dim = bool(single_dim)
+
+    def __len__(self):
+        return self.log_w.size
+
+    def _vec(self, a):
+        return a[..., 0] if self.single_dim else a
+
+    def _mat(self, a):
+        return a[..., 0, 0] if self.single_dim else a
+
+    @property
+    def grid(self):
+        """the kept grid indices 0, stride, 2 stride, ..."""
+        return np.arange(0, self.n_pts, self.stride)
+
+    @property
+    def mean(self):
+        """E[x_k | y] on the grid"""
+        return self._vec(self._mean.copy())
+
+    @property
+    def second(self):
+        """E[x_k x_k^T | y], the raw second-moment matrices"""
+        return self._mat(self._second.copy())
+
+    def _cov(self):
+        return self._second - self._mean[:, :, None] * self._mean[:, None, :]
+
+    @property
+    def cov(self):
+        """second - mean mean^T, as it comes and not clipped: where a stretch rests on one lineage the difference is rounding noise, and
+        the matrix need not be positive semi-definite"""
+        return self._mat(self._cov())
+
+    @property
+    def var(self):
+        """the diagonal of cov"""
+        return self._vec(np.diagonal(self._cov(), axis1=1, axis2=2).copy())
+
+    @property
+    def corr(self):
+        """cov_ab / sqrt(cov_aa cov_bb); nan where a variance is not positive"""
+        c = self._cov()
+        v = np.diagonal(c, axis1=1, axis2=2)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            s = np.sqrt(np.where(v > 0.0, v, np.nan))
+            return self._mat(c / (s[:, :, None] * s[:, None, :]))
+
+    def gaussian(self, k):
+        """(mean, cov) at the grid index k, which must be a kept one (ValueError otherwise).  At k = n_pts - 1 no observation lies behind k:
+        that is the filtering Gaussian a following window takes as its m0, S0."""
+        k = int(k)
+        if k < 0 or k >= self.n_pts or k % self.stride:
+            raise ValueError(f" SmoothingCovariance: grid index {k} is not kept (stride {self.stride}, n_pts {self.n_pts}).")
+        i = k // self.stride
+        return self._vec(self._mean[i].copy()), self._mat(self._cov()[i])
 
     def lineage_ess_on_grid(self):
         """lineage_ess of the stretch each kept grid index lies in: index k belongs to stretch #{observations before k}"""

@@ -240,6 +240,23 @@ class VarGP(object):
         out = [self._moments_record(res, k, stride) for k in range(res["log_w"].shape[0])]
         return out[0] if self.batch == 1 else out
 
+    def _covariance_record(self, res, k, stride, obs_t=None):
+        """One problem's SmoothingCovariance from row k of Context.particle_covariance's dict, cut to its own observations obs_t"""
+        from .particles import SmoothingCovariance
+        t = np.asarray(self._inputs()["obs_t"] if obs_t is None else obs_t).ravel()
+        return SmoothingCovariance(res["log_w"][k], res["mean"][k], res["second"][k], stride, self.dim_n, t, res["lineage_ess"][k, :t.size + 1],
+                                   res["ess"][k, :t.size], res["resampled"][k, :t.size], self.model.single_dim)
+
+    def particle_covariance(self, n_paths, seed, stride=1, ess_fraction=0.5, x=None, x0=None):
+        """The smoothing mean and full covariance matrices on the time grid from particle_filter with the same arguments: a
+        particles.SmoothingCovariance (with batch > 1 a list, one per problem) -- mean, second, cov, var, corr at the grid indices 0, stride,
+        ... under the filter's genealogy, reduced on the device, and lineage_ess as particle_moments has it.  What to hold the whole of
+        S_t against, its off-diagonal entries included; gaussian(dim_n - 1) is the filtering Gaussian a following window starts from."""
+        xx = None if x is None else np.asarray(x, dtype=float)
+        res = self._context().particle_covariance(n_paths, seed, stride=stride, ess_fraction=ess_fraction, x=xx, x0=x0, prior=self._prior())
+        out = [self._covariance_record(res, k, stride) for k in range(res["log_w"].shape[0])]
+        return out[0] if self.batch == 1 else out
+
     def _paths_record(self, res, k, stride, drawn, obs_t=None):
         """One problem's SmoothingPaths from row k of Context.particle_paths' dict, cut to its own observations obs_t"""
         from .particles import SmoothingPaths
