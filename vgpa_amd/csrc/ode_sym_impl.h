@@ -26,7 +26,9 @@
 //     8-byte slots).  60 KB at D = 40: two workgroups per CU, 256 registers each.
 //   * The vector recursion (m / lambda) is independent of the matrix one.  Its inner product is split over all 256
 //     threads (partial sums before the barrier); behind the barrier EVERY wave sums them and advances its own copy of the
-//     vector, so no second barrier orders "vector published" before "next partial sums".
+//     vector, so no second barrier orders "vector published" before "next partial sums".  (So backward, and forward in the run
+//     layout.  The forward fragment-cover kernels compute A v on the matrix cores, in the product waves: the rectangle wave's
+//     unused unit and a fifth accumulator on two triangle waves -- kCoverVecBlocks; each row arrives as ONE sum from one lane.)
 //   * A(t) is staged HBM -> registers -> LDS one step ahead; S_k / Psi_t go back to HBM from the stage buffer (coalesced
 //     row-pair items).  Everything of a stage that is not the product is ONE LDS round trip behind it (`tail`).
 // Measurements, what was tried and what bounds the kernel: DESIGN.md s.4.1, s.7, EXPERIMENTS.md s.2, s.9, s.11; micro-benchmark tools/ubench/sym_product.hip.
@@ -186,6 +188,25 @@ __host__ __device__ constexpr bool cover_diagonals_in_loop_units() {
   return !cover_slot_used(0, kCoverLoopSlot);
 }
 static_assert(cover_diagonals_in_loop_units(), "single-chain loop units: every diagonal block in slot 2 of a triangle wave, slot 2 of the rectangle wave unused");
+
+// The forward vector recursion on the matrix cores.  m' = -A m + b needs A_t v = Aop^T v each stage: one more chain of products whose
+// row side is a fragment the wave already holds -- map a1 of the A operand -- and whose column side is the stage vector in every column
+// (lane (k, block, column) reads v[k]: one broadcast ds_read_b128 per k-pair from the wave's copy of the vector).  Row r4 of block q
+// of that accumulator is (A v)[4 a1[q] + r4], the same in all four columns; the lanes of column 0 of the blocks below write it to the
+// partial-sum buffer, where every wave picks it up behind the barrier as it did the partial sums.  Bit q of [wave]: block q of map a1
+// delivers its row block -- a1 of waves 0, 2 and the first two blocks of wave 1 hold each of the ten row blocks once.
+constexpr int kCoverVecMap = 1;
+constexpr int kCoverVecBlocks[4] = {0xF, 0x3, 0xF, 0x0};
+__host__ __device__ constexpr bool cover_vec_rows_once() {
+  int cnt[10] = {};
+  for (int w = 0; w < 4; w++)
+    for (int q = 0; q < 4; q++)
+      if ((kCoverVecBlocks[w] >> q) & 1) cnt[kCoverMaps[w][kCoverVecMap][q]]++;
+  for (int i = 0; i < 10; i++)
+    if (cnt[i] != 1) return false;
+  return true;
+}
+static_assert(cover_vec_rows_once(), "the vector chain's publishing blocks must hold every row block of A v exactly once");
 
 template <int NB_>
 struct SGeo {
@@ -704,6 +725,7 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3
   constexpr bool COVER = (GR == 0);      // fragment cover (NSB = 5) instead of runs: see kCoverMaps
   // the cover's loop units (diagonal blocks) run one chain + an in-block transpose: see kCoverLoopSlot
   static_assert(!COVER || (g::NSB == 5 && g::MAXS == 4), "the fragment cover is built for 33 <= D <= 40");
+  constexpr bool VMC = COVER && FWD;     // the vector recursion's A v on the matrix cores, in the product waves: see kCoverVecBlocks
   static_assert(!HLP || COVER, "helper waves: fragment-cover kernels");
   static_assert(!GF || (HLP && QOUT && !FWD && !DENSEJ && METHOD == VGPA_ODE_RK4), "fused gradient assembly: backward RK4 helper-wave kernels with Q'' on");
   static_assert(!H2 || (HLP && !GF), "two helper roles: helper-wave kernels without the gradient waves");
@@ -756,6 +778,8 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3
   const int cov_used = COVER ? kCoverUsed[wq] : 0;
   const bool loop_diag = r4 == c4;                     // diagonal element of a diagonal block (loop unit)
   const int loop_src = 16 * c4 + 4 * bq + r4;          // the lane that holds element (c4, r4) of the same block
+  const int vrow = COVER ? 4 * kCoverMaps[wq][kCoverVecMap][bq] + r4 : 0;      // VMC: the row of A v in this lane's vector accumulator
+  const bool vpub = VMC && c4 == 0 && ((kCoverVecBlocks[wq] >> bq) & 1);      // ... and whether this lane publishes it
   if constexpr (COVER) {
 #pragma unroll
     for (int m = 0; m < 4; m++) colm[m] = 2 * ((4 * kCoverMaps[wq][m][bq] + c4) ^ r4);
@@ -950,7 +974,7 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3
   // phase (arithmetic, LDS writes, HBM stores) that the time loop places one pipeline step apart -- the requests are in flight
   // under a step of products, the finish finds its operands there.  State that lives between the two phases:
   constexpr int NAV = FWD ? g::RPP : 4 * g::CBP;
-  constexpr int NPS = FWD ? g::NPF : g::NPARTB;
+  constexpr int NPS = VMC ? 1 : (FWD ? g::NPF : g::NPARTB);      // (VMC: A v arrives whole from the product waves)
   d2_t tb_av[NAV], tb_xqf[FWD ? g::RPP : 1];
   double tb_xqb[FWD ? 1 : 4 * g::CBP];
   d2_t tc_mid[NITS], tc_items[g::NIT];
@@ -1078,7 +1102,7 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3
 #pragma unroll
     for (int q = 0; q < NPS; q++) ta_ps[q] = pl[q * g::PP];
   };
-  auto vecA_finish = [&](int j) {
+  auto vecA_finish = [&](int j, bool publish = true) {
     double vs = ta_ps[0];
 #pragma unroll
     for (int q = 1; q < NPS; q++) vs += ta_ps[q];
@@ -1097,7 +1121,7 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3
       else if (j == 2) { const double f = cmid - vs; v1 = v1 + 2.0 * f; vn = vk + dt * f; }
       else { vk = vk + (dt * (v1 + (c1 - vs))) * sixth + jm; vn = vk; }
     }
-    *xv_mine = vn;
+    if (publish) *xv_mine = vn;
   };
 
   // the stepper on one owned element: slope f = -z of stage j; returns the next stage state
@@ -1138,6 +1162,19 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3
   d2_t fAa, fXa, fAb[2][COVER ? 2 : 1], fXb[2][COVER ? 2 : 1];
   d2_t fAa1[2], fXa1[2];                 // HALF: map a1 in two buffers (read half a step earlier than it is free)
   d2_t fA[2][(COVER && !HALF) ? 4 : 1], fX[2][(COVER && !HALF) ? 4 : 1];
+  // VMC: the stage vector as a column-side fragment, all five k-pairs (read behind the vector update of pipeline step 0, used from
+  // step 1 on: k-pairs 1 .. 4 beside their row-side fragment, k-pair 0 -- whose row-side fragment is read a second time -- in steps 2, 3)
+  // (RK2's first stage multiplies the matrix by S_k where A_k belongs (quirk Q2) and the vector by A_k: `sep`, the chain's row-side
+  //  fragments are then read from the vector's own operand, all five with the vector's)
+  d2_t fV[VMC ? NKP : 1], fA0, fAs[VMC ? NKP : 1];
+  double wv = 0.0;
+  auto vec_frags = [&](bool sep, const double* Aopv) {
+#pragma unroll
+    for (int kp = 0; kp < (VMC ? NKP : 0); kp++) {
+      fV[kp] = *reinterpret_cast<const d2_t*>(xvw + 8 * kp + 2 * r4);
+      if (sep) fAs[kp] = *reinterpret_cast<const d2_t*>(Aopv + (4 * kp + r4) * LD + colm[kCoverVecMap]);
+    }
+  };
   auto frag_all = [&](int buf, int kp, const double* pa, const double* px) {
 #pragma unroll
     for (int m = 0; m < 4; m++) {
@@ -1192,7 +1229,12 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3
   };
 
   // products (their step-0 fragments are in flight) + stepper + publish of stage j
-  auto product_stage = [&](int j, int step, const double* Aop, const double* Xc, double* Xn, auto&& chore) {
+  // vc_ (VMC): what the wave does for the vector -- 0: the rectangle wave, whose unused unit (slot 2) becomes the vector chain, 1: a
+  // triangle wave with the chain as a fifth accumulator (+10 products), 2: a triangle wave without it; sep: see vec_frags
+  auto product_stage = [&](int j, int step, const double* Aop, const double* Xc, double* Xn, double* pv, bool sep, auto vc_, auto&& chore) {
+    constexpr int VC = decltype(vc_)::value;
+    constexpr bool VCH = VMC && VC != 2;              // this wave runs a vector chain
+    constexpr bool NO2 = VMC && VC == 0;              // ... in place of slot 2's products
     const double* pa = Aop + r4 * LD;
     const double* px = Xc + r4 * LD;
     const bool last = (j == NS - 1);
@@ -1251,15 +1293,31 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3
           // meanwhile
           __builtin_amdgcn_sched_barrier(0);
           if (t + 1 < NSTEP) frag_all(cur ^ 1, (t + 1) % NKP, pa, px);
+          if (VCH && t == 0) wv = 0.0;
+          if (VCH && !sep && t == 1) fA0 = *reinterpret_cast<const d2_t*>(pa + colm[kCoverVecMap]);
+          if (VCH && (t == 2 || t == 3)) wv = __builtin_amdgcn_mfma_f64_4x4x4f64(sep ? fAs[0][t - 2] : fA0[t - 2], fV[0][t - 2], wv, 0, 0, 0);
 #pragma unroll
           for (int hh = 0; hh < 2; hh++) {
 #pragma unroll
-            for (int u = 0; u < 4; u++) w[u] = __builtin_amdgcn_mfma_f64_4x4x4f64(fA[cur][u >> 1][hh], fX[cur][2 + (u & 1)][hh], w[u], 0, 0, 0);
+            for (int u = 0; u < 4; u++)
+              if (!(NO2 && u == kCoverLoopSlot)) w[u] = __builtin_amdgcn_mfma_f64_4x4x4f64(fA[cur][u >> 1][hh], fX[cur][2 + (u & 1)][hh], w[u], 0, 0, 0);
 #pragma unroll
             for (int u = 0; u < 4; u++)
               if (u != kCoverLoopSlot) w[u] = __builtin_amdgcn_mfma_f64_4x4x4f64(fX[cur][u >> 1][hh], fA[cur][2 + (u & 1)][hh], w[u], 0, 0, 0);
+            if (VCH && t >= 1) wv = __builtin_amdgcn_mfma_f64_4x4x4f64(sep ? fAs[VMC ? kp : 0][hh] : fA[cur][kCoverVecMap][hh], fV[VMC ? kp : 0][hh], wv, 0, 0, 0);
           }
-          if (t + 1 < NSTEP) {
+          if (VMC && t + 1 < NSTEP) {
+            // the same placement with this wave's counts: two products in front of a read while there are more products than reads
+            const int nm = 14 - (NO2 ? 2 : 0) + (VCH ? (t >= 1 ? 2 : 0) + ((t == 2 || t == 3) ? 1 : 0) : 0), nr = 8 + ((VCH && !sep && t == 1) ? 1 : 0);
+            const int two = nm - nr < nr ? nm - nr : nr;
+#pragma unroll
+            for (int i = 0; i < 9; i++)
+              if (i < nr) {
+                if (i < two) __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+                else __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+              }
+          } else if (t + 1 < NSTEP) {
 #pragma unroll
             for (int i = 0; i < 6; i++) {
               __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);     // two matrix-core products
@@ -1318,13 +1376,14 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3
       }
       chore(t);                          // everything of the stage that is not the product rides between the products
       if (kp == NKP - 1) {
-        if constexpr (COVER) {           // Z = M + M^T - F on the diagonal blocks: element (r4, c4) of a block adds element (c4, r4)
+        if constexpr (COVER && !NO2) {   // Z = M + M^T - F on the diagonal blocks: element (r4, c4) of a block adds element (c4, r4)
           w[kCoverLoopSlot] += __shfl(w[kCoverLoopSlot], loop_src, 64);
         }
+        if constexpr (VCH) *(vpub ? pv + vrow : trash) = wv;      // A v of this stage's vector, one lane per row
 #pragma unroll
         for (int u = 0; u < NSL; u++) {
           const int s = 2 * g0 + u;
-          if (s < MAXS) {
+          if (s < MAXS && !(NO2 && s == kCoverLoopSlot)) {
             double js = 0.0;
             if (!FWD && last) js = own[s] ? jsd[s] : 0.0;
             const double xn = element(s, j, w[u], js);
@@ -1368,7 +1427,8 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3
   constexpr int SC_F = SPLIT ? cmin(2, LAST) : TCU, SC_R = SPC ? cmin(1, LAST) : SC_F;
   // (helper waves: the loop exists twice, once per role, so that each role's loop carries only its own state -- one loop with a role
   //  branch inside keeps the union of both alive across the back-edge, and the backward instantiations spill)
-  auto time_loop = [&](auto helper_role) {
+  auto time_loop = [&](auto helper_role, auto vc_) {
+  constexpr bool VCH = VMC && decltype(vc_)::value != 2;        // (product waves) this wave runs a vector chain: see product_stage
   constexpr int HK = HLP ? decltype(helper_role)::value : 0;    // 0: product waves (or no helpers); 1: the helper role; 2 / 3 (H2): vector / staging helper
   constexpr bool HR = HK != 0;                                  // this copy is a helper role's
   for (int k = 0; k < n_steps; k++) {
@@ -1393,43 +1453,53 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3
       double* pv = pvb + (Xc == Xb0 ? 0 : g::PV);
       double* pv_prev = pvb + (Xc == Xb0 ? g::PV : 0);         // where the previous stage left its partial sums
       const double* Aopv = aop(k, j, false);
+      const bool sep = VMC && stage_op<METHOD, FWD>(j, true, k) != stage_op<METHOD, FWD>(j, false, k);      // (see vec_frags)
       if constexpr (HR) {
         // every chore of the stage, requests first: the partial sums of the previous stage and (stage 0) the start-point operand and
         // the stage state; then the vector update, its partial products (they read the vector just written, same wave, in order),
         // the staging, the HBM stores and loads
         if (HK != 3 && (j > 0 || k > 0)) vecA_read(pv_prev);
         if (HK != 2) tailC_read(j, Xc);
-        if (HK != 3) {
-          if (j > 0) vecA_finish(j - 1);
+        if (HK != 3) {                   // (VMC: the product waves keep the copy of the vector their fragments read; this one leaves through HBM)
+          if (j > 0) vecA_finish(j - 1, !VMC);
           else if (k > 0) {
-            vecA_finish(NS - 1);
+            vecA_finish(NS - 1, !VMC);
             c0 = c1; c1 = c2;
             if (!FWD) jm = jm_next;
           }
-          tailB_read(Aopv);
-          tailB_finish(pv);
+          if (!VMC) {
+            tailB_read(Aopv);
+            tailB_finish(pv);
+          }
         }
         if (HK == 1) tailC_finish(j, k, K1{});
         if (HK == 2) vec_chores(j, k);
         if (HK == 3) tailC_finish(j, k, K3{});
       } else
-      product_stage(j, k, aop(k, j, true), Xc, Xn, [&](int t) {
-        if (HLP) {                       // (product waves beside helpers: only their own HBM loads -- G_t of the step after the next)
+      product_stage(j, k, aop(k, j, true), Xc, Xn, pv, sep, vc_, [&](int t) {
+        if (HLP && !VMC) {               // (product waves beside helpers: only their own HBM loads -- G_t of the step after the next)
           if (t == SC_F && j == JSEC) prefetch(k, std::false_type{});
           return;
         }
         if (SPLIT) __builtin_amdgcn_sched_barrier(0);
-        if (t == SA_R && (j > 0 || k > 0)) vecA_read(pv_prev);
-        if (t == SA_F) {
+        // (VMC: a wave without a vector chain has no use for a copy of the vector -- wave 0 is the one that stores it)
+        if ((!VMC || VCH) && t == SA_R && (j > 0 || k > 0)) vecA_read(pv_prev);
+        if ((!VMC || VCH) && t == SA_F) {
           if (j > 0) vecA_finish(j - 1);
           else if (k > 0) {
             vecA_finish(NS - 1);
             c0 = c1; c1 = c2;                                   // the vector's forcing terms move on behind its last stage
             if (!FWD) jm = jm_next;
           }
+          if (VMC) vec_frags(sep, Aopv);                         // (the vector just written: same wave, in order)
         }
-        if (t == SB_R) tailB_read(Aopv);
-        if (t == SB_F) tailB_finish(pv);
+        if (HLP) {                       // (VMC beside helpers: the vector update above and its forcing term; every other chore is the helpers')
+          if (VCH && t == SC_F && j == JSEC) c2 = ldgo(cin + vec(tclamp(k + 2)), lane8);
+          if (SPLIT) __builtin_amdgcn_sched_barrier(0);
+          return;
+        }
+        if (!VMC && t == SB_R) tailB_read(Aopv);
+        if (!VMC && t == SB_F) tailB_finish(pv);
         if (t == SC_R) tailC_read(j, Xc);
         if (t == SC_F) tailC_finish(j, k, K1{});
         if (SPLIT) __builtin_amdgcn_sched_barrier(0);
@@ -1443,10 +1513,15 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256 * ((GF || H2) ? 3
     }
   }
   };
-  if (H2 && role == 1) time_loop(K2{});
-  else if (H2 && role == 2) time_loop(K3{});
-  else if (HLP && helper) time_loop(K1{});
-  else time_loop(std::integral_constant<int, 0>{});
+  using K0 = std::integral_constant<int, 0>;
+  static_assert(!kCoverAlias[0] && kCoverVecBlocks[0] && kCoverVecBlocks[1] && kCoverVecBlocks[2] && !kCoverVecBlocks[3], "the product waves' vector roles below");
+  if (H2 && role == 1) time_loop(K2{}, K0{});
+  else if (H2 && role == 2) time_loop(K3{}, K0{});
+  else if (HLP && helper) time_loop(K1{}, K0{});
+  else if (!VMC) time_loop(K0{}, K0{});
+  else if (wq == 0) time_loop(K0{}, K0{});        // (VMC: the loop once per vector role of a product wave -- no branch inside the pipeline)
+  else if (wq == 3) time_loop(K0{}, K2{});
+  else time_loop(K0{}, K1{});
   if constexpr (GF) {
     // the last grid point's gradient: three more barrier intervals.  The helpers finish the vector and leave lam; the gradient
     // waves build (Psi in the stage buffer, the end point's operand in R), then band / u, product, out; the product waves only count.
