@@ -604,6 +604,36 @@ int vgpa_ld_stage(void* stream, const vgpa_ld_stage_args* args);
 int vgpa_ld_gemm_chunk(void* stream, int transa, int M, int N, int K, const double* A0, int lda, const double* B, int ldb,
                        double* C, int cw, int seg_tiles, int seg_stride, int accumulate);
 
+/* What the D > 64 drivers launched, counted on the host where each launch is issued (tests, diagnostics): one table per process,
+ * never reset -- read it before and after a call and take the difference.  vgpa_ld_launch_counts copies the first min(n,
+ * VGPA_LD_COUNT_N) counters to `out` and returns VGPA_LD_COUNT_N (VGPA_ERR_ARG for a null `out` or n < 0).  The hand-written stage
+ * product has one counter per tile height and kernel form: VGPA_LD_COUNT_GEMM + 6 * (0: 32 rows, 1: 64, 2: 128) + VGPA_LD_GEMM_*. */
+enum {
+  VGPA_LD_COUNT_STAGE_PROD_FWD = 0,      /* k_stage_prod, forward, the stage's own A */
+  VGPA_LD_COUNT_STAGE_PROD_FWD_MID = 1,  /* ... averaging the mid-point pair while staging */
+  VGPA_LD_COUNT_STAGE_PROD_BWD = 2,
+  VGPA_LD_COUNT_STAGE_PROD_BWD_MID = 3,
+  VGPA_LD_COUNT_STAGE_WIDE_FWD = 4,      /* k_stage_wide */
+  VGPA_LD_COUNT_STAGE_WIDE_BWD = 5,
+  VGPA_LD_COUNT_STAGE_SYM = 6,           /* k_stage_sym: element-wise stage on tile pairs */
+  VGPA_LD_COUNT_STAGE_ROWS = 7,          /* k_stage: element-wise stage on a row block */
+  VGPA_LD_COUNT_MID = 8,                 /* k_mid: the mid-point operand of a step, single-rank drivers */
+  VGPA_LD_COUNT_TRANSPOSE = 9,           /* k_transpose: literal non-symmetric path */
+  VGPA_LD_COUNT_LIBRARY_GEMM = 10,       /* stage product through the vendor library */
+  VGPA_LD_COUNT_MID_COLS = 11,           /* k_mid_cols: the mid-point operand of a rank's slab, row-sharded driver */
+  VGPA_LD_COUNT_GEMM = 12,
+  VGPA_LD_COUNT_N = 30
+};
+enum {
+  VGPA_LD_GEMM_CHECKED = 0,              /* k_gemm with bounds checks */
+  VGPA_LD_GEMM_FULL = 1,                 /* k_gemm, whole tiles */
+  VGPA_LD_GEMM_VEC = 2,                  /* k_gemm_v: 16-byte loads, two register sets */
+  VGPA_LD_GEMM_VEC4 = 3,                 /* k_gemm_v, four register sets */
+  VGPA_LD_GEMM_SEG = 4,                  /* k_gemm_v, K-chunk launch */
+  VGPA_LD_GEMM_SEG4 = 5                  /* k_gemm_v, K-chunk launch, four register sets */
+};
+int vgpa_ld_launch_counts(int64_t* out, int n);
+
 /* row-sharded recursion for large D on the GPUs of one node (BASELINE configs[4]) ------------------
  * One vgpa_shard per process / GPU.  Rank p of `world` owns rows [p D/world, (p+1) D/world) of S_t / Psi_t inside every
  * Runge-Kutta stage and the contiguous slice [t_lo, t_hi) of the TIME grid of the results (vgpa_shard_time_slice): the

@@ -341,6 +341,7 @@ def test_stage_kernel_versions_above_64(d, n, method, batch, version, monkeypatc
     above, GEMM + k_stage_sym beyond that or on request) at the SAME small sizes -- ragged edge tiles, an odd number of diagonal
     tiles, a batch -- against the oracle.  VGPA_STAGE_FUSED / VGPA_STAGE_WIDE are read per call."""
     from test_gpu_edge_cases import make_problem, gpu_context
+    from vgpa_amd.large_d import launch_counts, launched
     monkeypatch.setenv("VGPA_STAGE_FUSED", "0")
     if version == "two-kernel":
         monkeypatch.setenv("VGPA_STAGE_WIDE", "0")
@@ -348,7 +349,17 @@ def test_stage_kernel_versions_above_64(d, n, method, batch, version, monkeypatc
     ctx = gpu_context(p, batch=batch)
     rng = np.random.default_rng(5)
     xs = np.stack([x + 0.01 * rng.standard_normal(x.size) for _ in range(batch)])
+    before = launch_counts()
     f, g = ctx.sweep(xs if batch > 1 else xs[0])
+    ran = launched(before)
+    # the version the test names ran every stage of both recursions, and neither of the other two ran at all
+    stages = 2 * (n - 1) * {"euler": 1, "heun": 2, "rk2": 2, "rk4": 4}[method]
+    if version == "wide":
+        assert ran.pop("stage_wide_fwd") + ran.pop("stage_wide_bwd") == stages, ran
+    else:
+        product = [k for k in ran if k.startswith("gemm")]
+        assert len(product) == 1 and ran.pop(product[0]) == stages and ran.pop("stage_sym") == stages, ran
+    assert ran.pop("mid", 0) == (2 * (n - 1) if method in ("rk2", "rk4") else 0) and not ran, ran      # (the mid-point operand: once per step)
     f, g = np.atleast_1d(f), np.asarray(g).reshape(batch, -1)
     for q in range(batch):
         f_ref, g_ref, st = vo.sweep(p, xs[q], faithful=False)
@@ -369,8 +380,14 @@ def test_stage_kernel_versions_above_64(d, n, method, batch, version, monkeypatc
 def test_throughput_stage_kernel_above_512(d, n, method):
     """k_stage_wide at its own sizes: 17 tiles (an odd number of diagonal tiles), ragged edge tiles (530 = 16 x 32 + 18)."""
     from test_gpu_edge_cases import make_problem, check
+    from vgpa_amd.large_d import launch_counts, launched
     p, x = make_problem("L96", d, n, method=method)
+    before = launch_counts()
     check(p, x)
+    ran = launched(before)
+    stages = 2 * (n - 1) * {"heun": 2, "rk2": 2, "rk4": 4}[method]
+    assert ran.pop("stage_wide_fwd") + ran.pop("stage_wide_bwd") == stages, ran
+    assert ran.pop("mid", 0) == (2 * (n - 1) if method in ("rk2", "rk4") else 0) and not ran, ran
 
 
 @pytest.mark.gpu
@@ -725,18 +742,19 @@ def ctypes_hip():
     return ctypes.CDLL(paths[0])
 
 
-def _run_native_virtual_ranks(method, d, n, world, chunks=None):
+def _run_native_virtual_ranks(method, d, n, world, chunks=None, inputs=None):
     """chunks: None = the library's default schedule (pipelined gather wherever the row block allows it), 0 = the serial
-    schedule, k = k sub-blocks."""
+    schedule, k = k sub-blocks.  inputs: (a, b, m0, s0, sigma, gm, gs, jm, js) in place of make_inputs(d, n); then every rank's
+    time slice and host arrays are returned beside the schedule: (used, [dict(slice=(lo, hi), mt=, st=, lamt=, psit=), ...])."""
     import threading
     import torch
     from vgpa_amd.large_d import NativeShardedRecursion
     from vgpa_amd._lib import SHARD_OPT_GATHER_CHUNKS
-    a, b, m0, s0, sigma, gm, gs, jm, js = make_inputs(d, n)
+    a, b, m0, s0, sigma, gm, gs, jm, js = make_inputs(d, n) if inputs is None else inputs
     mt_o, st_o = vo.solve_fwd(method, 0.01, False, a, b, m0, s0, sigma)
     lam_o, psi_o = vo.solve_bwd(method, 0.01, False, a, gm, gs, jm, js)
     comm = _CallbackComm(world)
-    errs, fails, slices, used = [None] * world, [], [None] * world, [None] * world
+    errs, fails, slices, used, kept = [None] * world, [], [None] * world, [None] * world, [None] * world
 
     def run(rank):
         try:
@@ -754,6 +772,8 @@ def _run_native_virtual_ranks(method, d, n, world, chunks=None):
                 e = max(rel_err(mt.cpu().numpy(), mt_o[lo:hi]), rel_err(st.cpu().numpy(), st_o[lo:hi]),
                         rel_err(lam.cpu().numpy(), lam_o[lo:hi]), rel_err(psi.cpu().numpy(), psi_o[lo:hi]))
             errs[rank] = e
+            if inputs is not None:
+                kept[rank] = dict(slice=(lo, hi), mt=mt.cpu().numpy(), st=st.cpu().numpy(), lamt=lam.cpu().numpy(), psit=psi.cpu().numpy())
             rec.close()
         except BaseException as exc:      # noqa: BLE001 - a dead thread would leave the others at the barrier
             fails.append(exc)
@@ -772,7 +792,7 @@ def _run_native_virtual_ranks(method, d, n, world, chunks=None):
     assert len(set(used)) == 1
     if world > 1:
         assert (comm.p2p_groups[0] > 0) == (used[0] > 0)
-    return used[0]
+    return used[0] if inputs is None else (used[0], kept)
 
 
 @pytest.mark.gpu

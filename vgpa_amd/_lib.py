@@ -45,7 +45,12 @@ SYMBOLS = ["vgpa_create", "vgpa_destroy", "vgpa_last_error", "vgpa_abi_version",
            "vgpa_shard_solve_fwd", "vgpa_shard_solve_bwd", "vgpa_shard_sweep", "vgpa_shard_sweep_sharded", "vgpa_shard_set_option",
            "vgpa_shard_get_option", "vgpa_shard_time_collectives", "vgpa_ld_gemm_chunk", "vgpa_rccl_unique_id", "vgpa_rccl_comm_create",
            "vgpa_rccl_comm_destroy", "vgpa_rccl_comm_count", "vgpa_rccl_comm_streams", "vgpa_shard_time_stage", "vgpa_shard_phase_ms", "vgpa_time_slice",
-           "vgpa_device_alloc", "vgpa_device_free", "vgpa_device_memcpy"]
+           "vgpa_device_alloc", "vgpa_device_free", "vgpa_device_memcpy", "vgpa_ld_launch_counts"]
+# vgpa_ld_launch_counts: the counters in the order of the header's VGPA_LD_COUNT_* (the stage product: tile height x VGPA_LD_GEMM_*)
+LD_GEMM_FORMS = ("checked", "full", "vec", "vec4", "seg", "seg4")
+LD_COUNT_NAMES = (("stage_prod_fwd", "stage_prod_fwd_mid", "stage_prod_bwd", "stage_prod_bwd_mid", "stage_wide_fwd", "stage_wide_bwd",
+                   "stage_sym", "stage_rows", "mid", "transpose", "library_gemm", "mid_cols") +
+                  tuple(f"gemm{h}_{form}" for h in (32, 64, 128) for form in LD_GEMM_FORMS))
 
 P_DOUBLE = POINTER(c_double)
 
@@ -179,6 +184,7 @@ def load():
     lib.vgpa_shard_time_collectives.argtypes = [c_void_p, c_int, P_DOUBLE, P_DOUBLE]
     lib.vgpa_ld_gemm_chunk.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                                        c_int, c_int, c_int]
+    lib.vgpa_ld_launch_counts.argtypes = [POINTER(c_int64), c_int]
     lib.vgpa_rccl_unique_id.argtypes = [c_void_p]
     lib.vgpa_rccl_comm_create.argtypes = [POINTER(VgpaComm), c_void_p, c_int, c_int, c_int]
     lib.vgpa_rccl_comm_destroy.argtypes = [POINTER(VgpaComm)]

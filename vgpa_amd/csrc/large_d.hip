@@ -31,6 +31,10 @@
 namespace vgpa {
 namespace ld {
 
+std::atomic<long long> g_launches[VGPA_LD_COUNT_N];
+
+constexpr int gemm_counter(int bm, int form) { return VGPA_LD_COUNT_GEMM + 6 * (bm == 32 ? 0 : bm == 64 ? 1 : 2) + form; }
+
 struct GemmArgs {
   int M, N, K;              // C[M x N] = op(A)[M x K] . B[K x N]
   const double* A0;         // TRANSA ? [K x M] : [M x K], leading dimension lda
@@ -433,6 +437,7 @@ template <int BM, bool FULL>
 static void launch_gemm_bm_f(bool transa, const GemmArgs& g, hipStream_t st) {
   dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, g.nb);
   const bool mid = g.A1 != nullptr;
+  count_launch(gemm_counter(BM, FULL ? VGPA_LD_GEMM_FULL : VGPA_LD_GEMM_CHECKED));
   if (transa) {
     if (mid) hipLaunchKernelGGL((k_gemm<true, true, BM, FULL>), grid, dim3(NT), 0, st, g);
     else hipLaunchKernelGGL((k_gemm<true, false, BM, FULL>), grid, dim3(NT), 0, st, g);
@@ -449,10 +454,12 @@ static void launch_gemm_bm_v(bool transa, const GemmArgs& g, hipStream_t st) {
   // four register sets of loads in flight and no load under a branch (k_gemm_v, PFU) when the k-tile count allows it: D = 1024
   // 44.6 -> 39.6 us per product (47 -> 54 TFLOP/s; 2 sets 44.1, 8 sets 40.1), D = 2048 forward recursion 44.0 -> 47.7 TFLOP/s
   if (!mid && (g.K / BK) % 4 == 0) {
+    count_launch(gemm_counter(BM, VGPA_LD_GEMM_VEC4));
     if (transa) hipLaunchKernelGGL((k_gemm_v<true, false, BM, false, 4>), grid, dim3(NT), 0, st, g);
     else hipLaunchKernelGGL((k_gemm_v<false, false, BM, false, 4>), grid, dim3(NT), 0, st, g);
     return;
   }
+  count_launch(gemm_counter(BM, VGPA_LD_GEMM_VEC));
   if (transa) {
     if (mid) hipLaunchKernelGGL((k_gemm_v<true, true, BM>), grid, dim3(NT), 0, st, g);
     else hipLaunchKernelGGL((k_gemm_v<true, false, BM>), grid, dim3(NT), 0, st, g);
@@ -473,10 +480,12 @@ static void launch_gemm_bm(bool transa, const GemmArgs& g, hipStream_t st) {
     if (!h.seg_tiles) { h.seg_tiles = h.K / BK; h.seg_stride = h.K; }
     dim3 grid(g.N / BN, g.M / BM, g.nb);
     if ((h.K / BK) % 4 == 0) {        // four register sets of loads in flight (launch_gemm_bm_v)
+      count_launch(gemm_counter(BM, VGPA_LD_GEMM_SEG4));
       if (transa) hipLaunchKernelGGL((k_gemm_v<true, false, BM, true, 4>), grid, dim3(NT), 0, st, h);
       else hipLaunchKernelGGL((k_gemm_v<false, false, BM, true, 4>), grid, dim3(NT), 0, st, h);
       return;
     }
+    count_launch(gemm_counter(BM, VGPA_LD_GEMM_SEG));
     if (transa) hipLaunchKernelGGL((k_gemm_v<true, false, BM, true>), grid, dim3(NT), 0, st, h);
     else hipLaunchKernelGGL((k_gemm_v<false, false, BM, true>), grid, dim3(NT), 0, st, h);
     return;
@@ -589,10 +598,12 @@ hipError_t launch_stage(const StageArgs& a, hipStream_t st) {
   const int nvec = (a.Mp + (NT / 64) - 1) / (NT / 64);
   if (a.sym_ok && a.Mp == a.D && a.row0 == 0 && a.cw == a.D && a.W == a.Wcol) {
     const int nt = (a.D + TS - 1) / TS;
+    count_launch(VGPA_LD_COUNT_STAGE_SYM);
     hipLaunchKernelGGL(k_stage_sym, dim3(nt * (nt + 1) / 2 + nvec, 1, a.nb), dim3(NT), 0, st, a);
     return hipGetLastError();
   }
   const int ntx = (a.D + TS - 1) / TS, nty = (a.Mp + TS - 1) / TS;
+  count_launch(VGPA_LD_COUNT_STAGE_ROWS);
   hipLaunchKernelGGL(k_stage, dim3(ntx * nty + nvec, 1, a.nb), dim3(NT), 0, st, a);
   return hipGetLastError();
 }
@@ -711,6 +722,7 @@ hipError_t run_stage(const LdCall& c, const Work& w, const StageSpec& s, MidCach
     if (mc->a0.rows != ga0.rows || mc->a1.rows != ga1.rows) {
       const size_t n = (size_t)D * D;
       const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+      count_launch(VGPA_LD_COUNT_MID);
       hipLaunchKernelGGL(k_mid, dim3(blocks, c.nb), dim3(256), 0, st, ga0.rows, ga1.rows, w.AM.rows, n, ga0.stride, w.AM.stride);
       mc->a0 = ga0; mc->a1 = ga1;
     }
@@ -728,6 +740,7 @@ hipError_t run_stage(const LdCall& c, const Work& w, const StageSpec& s, MidCach
     // and W'^T symmetrically (R = -G + W' + W'^T), only the order of its two additions changes.
     // (measured: the library's transposed-A product runs at 31 / 66 / 74 TFLOP/s for D = 1024 / 2048 / 4096, its plain
     // product at 50 / 60 / 67 -- the detour pays below D = 2048 only)
+    count_launch(VGPA_LD_COUNT_LIBRARY_GEMM);
     e = s.fwd ? library_gemm(false, D, D, D, ga0.rows, D, s.X.rows, D, w.W.rows, D, st)
               : (D < 2048 ? library_gemm(false, D, D, D, s.X.rows, D, ga0.rows, D, w.W.rows, D, st)
                           : library_gemm(true, D, D, D, ga0.rows, D, s.X.rows, D, w.W.rows, D, st));
@@ -739,6 +752,7 @@ hipError_t run_stage(const LdCall& c, const Work& w, const StageSpec& s, MidCach
   if (e != hipSuccess) return e;
   if (c.literal) {
     const int nt = (D + 31) / 32;
+    count_launch(VGPA_LD_COUNT_TRANSPOSE);
     hipLaunchKernelGGL(k_transpose, dim3(nt, nt, c.nb), dim3(256), 0, st, s.X.rows, w.XT.rows, D, s.X.stride, w.XT.stride);
     GemmArgs g2{D, D, D, ga0.rows, ga1.rows, D, w.XT.rows, D, w.W2.rows, D};
     g2.nb = c.nb; g2.zA = ga0.stride; g2.zB = w.XT.stride; g2.zC = w.W2.stride;
@@ -1020,6 +1034,7 @@ static hipError_t shard_stage(ShardCtx& c, const ShardStage& s) {
     if (c.mid_a0 != s.Ag0 || c.mid_a1 != s.Ag1 || c.mid_fwd != s.fwd) {
       const size_t n = (size_t)Mp * D;
       const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+      count_launch(VGPA_LD_COUNT_MID_COLS);
       if (s.fwd) hipLaunchKernelGGL(k_mid_cols, dim3(blocks), dim3(256), 0, c.st, s.Ag0, s.Ag1, w.mid, Mp, D, s.ldag);
       else hipLaunchKernelGGL(k_mid_cols, dim3(blocks), dim3(256), 0, c.st, s.Ag0, s.Ag1, w.mid, D, Mp, s.ldag);
       c.mid_a0 = s.Ag0; c.mid_a1 = s.Ag1; c.mid_fwd = s.fwd;
@@ -1496,6 +1511,12 @@ int vgpa_ld_gemm_chunk(void* stream, int transa, int M, int N, int K, const doub
   ld::GemmArgs g{M, N, K, A0, nullptr, lda, B, ldb, C, cw};
   g.seg_tiles = seg_tiles; g.seg_stride = seg_stride; g.accumulate = accumulate != 0;
   return ld::launch_gemm(transa != 0, g, (hipStream_t)stream) == hipSuccess ? VGPA_OK : VGPA_ERR_DEVICE;
+}
+
+int vgpa_ld_launch_counts(int64_t* out, int n) {
+  if (!out || n < 0) return VGPA_ERR_ARG;
+  for (int i = 0; i < n && i < VGPA_LD_COUNT_N; i++) out[i] = (int64_t)ld::g_launches[i].load(std::memory_order_relaxed);
+  return VGPA_LD_COUNT_N;
 }
 
 int vgpa_ld_stage(void* stream, const vgpa_ld_stage_args* p) {

@@ -2,10 +2,17 @@
 // its element-wise helpers.  (The one-kernel stages live in their own translation unit because they are compiled with
 // -mllvm -amdgpu-mfma-vgpr-form -- vgpa_amd/build.py -- and the products are not: see the head of large_d_stage.hip.)
 #pragma once
+#include <atomic>
+
 #include "vgpa_internal.h"
 
 namespace vgpa {
 namespace ld {
+
+// What was launched (vgpa_ld_launch_counts, include/vgpa_hip.h): one counter per VGPA_LD_COUNT_*, advanced on the host beside the launch
+// it names.  Nothing on the device knows of it.
+extern std::atomic<long long> g_launches[VGPA_LD_COUNT_N];
+inline void count_launch(int what) { g_launches[what].fetch_add(1, std::memory_order_relaxed); }
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 

@@ -27,6 +27,27 @@ from ._lib import load, _raise, DeviceArray
 METHODS = ("euler", "heun", "rk2", "rk4")
 
 
+def launch_counts():
+    """What the D > 64 drivers of this process have launched so far (vgpa_ld_launch_counts; tests, diagnostics; read-only): a dict over
+    `_lib.LD_COUNT_NAMES` -- the one-kernel stages `stage_prod_{fwd,bwd}[_mid]` and `stage_wide_{fwd,bwd}`, the element-wise stages
+    `stage_sym` and `stage_rows`, `mid`, `mid_cols`, `transpose`, `library_gemm`, and the hand-written stage product by tile height
+    and kernel form, `gemm{32,64,128}_{checked,full,vec,vec4,seg,seg4}`.  The counters are advanced on the host where a launch is
+    issued and never reset: take the difference around a call (`launched`)."""
+    from ._lib import LD_COUNT_NAMES
+    lib = load()
+    out = (ctypes.c_int64 * len(LD_COUNT_NAMES))()
+    n = lib.vgpa_ld_launch_counts(out, len(LD_COUNT_NAMES))
+    if n != len(LD_COUNT_NAMES):
+        raise RuntimeError(f"vgpa_ld_launch_counts: the library has {n} counters, this package names {len(LD_COUNT_NAMES)}")
+    return dict(zip(LD_COUNT_NAMES, (int(v) for v in out)))
+
+
+def launched(before, after=None):
+    """The counters that moved between two `launch_counts()` (the second: now), with how far."""
+    after = launch_counts() if after is None else after
+    return {k: after[k] - before[k] for k in after if after[k] != before[k]}
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 def _hip_runtime():
     """ctypes handle of the HIP runtime this process already uses (torch bundles its own copy: a second one would not know
