@@ -376,6 +376,50 @@ int vgpa_particle_paths(vgpa_ctx* ctx, const double* x_or_null, const double* x0
                         const double* prior_mu_or_null, const double* prior_tau_or_null, double* logw, double* state, double* paths,
                         int32_t* slots_or_null, double* ess_or_null, int32_t* resampled_or_null);
 
+/* Whole smoothing trajectories by backward simulation (forward filtering, backward simulation): the K trajectories of
+ * vgpa_particle_paths, but at every observation where the cloud was resampled a trajectory does not follow its ancestor: it draws the slot
+ * it came from among all n = n_paths particles of the filter's stored cloud, with probability proportional to (filter weight) x (model
+ * transition density to the trajectory's next state).  The early stretches then do not rest on the few lineages that survive the
+ * resamplings.  Lineages coalesce at the resampling steps only -- inside a stretch every slot carries its own path -- so the block state
+ * z_j = x_{t_{j-1}+1 .. t_j} is backward-simulated: p(z_{j+1} | z_j) depends on z_j through x_{t_j} alone and on z_{j+1} through its first
+ * point alone, one transition density per candidate and cut.
+ * Stretches, t_j, c, x_i(k), clouds_j, anc_j, the resampling flags and the final slots s_c[m] (given, or drawn with the same counter) are
+ * those of vgpa_particle_paths; the filter of vgpa_particle_filter runs unchanged.  Two more quantities:
+ *   hlw_j[i]    the log-weight of slot i at the problem's observation j, that observation's term included, before the resampling decision
+ *   R_dd        the diagonal factor of Sigma_p dt in force
+ * For j = c-1 .. 0, per problem p and trajectory m:
+ *   not resampled at observation j:  s_j[m] = s_{j+1}[m]
+ *   resampled (so k = t_j < Np-1):
+ *     1. x~ = (z + dt (-A_k z + b_k)) + R xi with z = clouds_j[anc_j[s]], s = s_{j+1}[m], xi the sampler's normals of counter (k+1, s, p, .):
+ *        the state of slot s at grid index k+1, recomputed in plain fp64 -- equal to the walk's to rounding, not necessarily to the bit
+ *        (above D = 4 the walk forms A z on the matrix cores)
+ *     2. b_i = hlw_j[i] - 1/2 sum_d ((x~_d - mu_i,d) / R_dd)^2 for every slot i < n, mu_i = clouds_j[i] + dt f(clouds_j[i]; theta_p), f the
+ *        model drift of vgpa_sample_paths(VGPA_PATHS_MODEL) with the theta in force (Lorenz-96 circular on the candidate's own state);
+ *        the device multiplies by 1 / R_dd
+ *     3. g_i = -log(-log u_i), u_i from Philox counter (k, m, p, 0x80000000 | (i >> 1)) under the seed's key: unit_open(r0, r1) for even
+ *        i, unit_open(r2, r3) for odd i (the normals use fourth words below 32, the resamplings 0xffffffff: no collision while n < 2^32)
+ *     4. s_j[m] = the smallest i that attains max_i (b_i + g_i): Gumbel-max, an exact draw from softmax(b), without a prefix sum -- the
+ *        result depends on no summation order and not on the launch geometry
+ *   the walk    as in vgpa_particle_paths: the start with counter word s_0[m], the step to k in stretch j with counter (k, s_j[m], p, .);
+ *               and having completed an observation index t_j of its problem, after that point is stored, the state is replaced by
+ *               clouds_j[anc_j[s_{j+1}[m]]] before the next step (where the cloud was carried on anc_j is the identity: no bit changes)
+ *   paths            host, [batch][K][n_keep][D] as in vgpa_particle_paths.  At stride 1, paths[p][m][t_j] is bit for bit
+ *                    clouds[p][j][s_j[m]] and paths[p][m][Np-1] is bit for bit state[p][s_c[m]].  Drawn trajectories are equally weighted.
+ *                    With ess_fraction = 0, or n_paths = 1, nothing is resampled and paths and slots are vgpa_particle_paths' bit for bit.
+ *                    Two calls with the same arguments give the same bits
+ *   slots_or_null    host int32, [batch][M+1][K]: s_j[m]; rows beyond a problem's own count + 1: -1
+ *   logw, state, ess_or_null, resampled_or_null and every other argument: as in vgpa_particle_filter, and bit-identical to its results with
+ *   the same arguments.  With x NULL the cached state is read and not written
+ * Within a stretch a trajectory is still its slot's own path: the distinct paths of a stretch are bounded by the distinct slots drawn.
+ * Device memory: the two histories the draw reads stay on the device for the call, batch * M * n * (D + 1) doubles (the clouds and hlw),
+ * beside the ancestors (batch * M * n int32) that vgpa_particle_paths keeps.  Work: n * K scores of D terms per resampled observation.
+ * Errors and limits: those of vgpa_particle_paths (D > 64 and a dense Sigma are VGPA_ERR_UNSUPPORTED), and VGPA_ERR_UNSUPPORTED, before
+ * any work, for more than 65535 * 8 trajectories per problem. */
+int vgpa_particle_backward_paths(vgpa_ctx* ctx, const double* x_or_null, const double* x0_or_null, int32_t n_paths, int32_t n_draw,
+                                 const int32_t* final_slots_or_null, int32_t stride, uint64_t seed, double ess_fraction,
+                                 const double* prior_mu_or_null, const double* prior_tau_or_null, double* logw, double* state, double* paths,
+                                 int32_t* slots_or_null, double* ess_or_null, int32_t* resampled_or_null);
+
 /* The particle forecast: a weighted cloud carried past the window under the model SDE, with its mean and spread on the
  * forecast grid and a handful of member trajectories; the cloud never leaves the device between the filter and the forecast.
  * Per problem p: n = n_paths particles x_i with log-weights lw_i at the absolute grid index k0.

@@ -1,13 +1,15 @@
 """
 Time of Context.sample_paths (vgpa_sample_paths), Context.sample_paths_weighted (vgpa_sample_paths_weighted), Context.particle_filter
 (vgpa_particle_filter), Context.particle_statistics (vgpa_particle_statistics), Context.particle_moments (vgpa_particle_moments),
-Context.particle_covariance (vgpa_particle_covariance), Context.particle_paths (vgpa_particle_paths) and Context.particle_forecast (vgpa_particle_forecast) on their jobs, one JSON line.
+Context.particle_covariance (vgpa_particle_covariance), Context.particle_paths (vgpa_particle_paths), Context.particle_backward_paths
+(vgpa_particle_backward_paths) and Context.particle_forecast (vgpa_particle_forecast) on their jobs, one JSON line.
 
     python tools/bench_sample_paths.py [--rounds 3] [--calls 5] [--jobs a,b,c,aw,aw0,bw,bw0,af64_0,af64_5,af1024_0,af1024_5,bf64_0,...]
     python tools/bench_sample_paths.py --statistics [--filter-problems 4096]      # the as* and bs* jobs
     python tools/bench_sample_paths.py --moments [--filter-problems 4096]         # the am* and bm* jobs
     python tools/bench_sample_paths.py --covariance [--filter-problems 4096]      # the ac* and bc* jobs
     python tools/bench_sample_paths.py --paths [--filter-problems 4096] [--paths-strides 1,10]      # the ap* and bp* jobs, once per stride
+    python tools/bench_sample_paths.py --backward [--filter-problems 4096] [--paths-strides 10] [--parent-json FILE]      # the ab* and bb* jobs
     python tools/bench_sample_paths.py --forecast [--forecast-problems 512] [--forecast-particles 4096] [--forecast-horizon 1000]
 
   a   posterior kind, Lorenz-96, D = 40, Np = 1001, B = 512:   64 paths per problem, stride 100
@@ -38,6 +40,13 @@ Context.particle_covariance (vgpa_particle_covariance), Context.particle_paths (
              n = 64 or 1024 particles per problem, ess_fraction 0.5, K = 16 or 64 trajectories per problem drawn from the final weights,
              and particle_filter with the same arguments, the two calls alternating inside every round: both times, their ratio, the
              trajectories copied and how many different paths the K trajectories have in the first and in the last stretch
+
+  ab<n>_<K>, bb<n>_<K>   (--backward selects all eight, each once per stride of --paths-strides) particle_backward_paths with the arguments
+             of ap<n>_<K> / bp<n>_<K>, and particle_paths and particle_filter with the same arguments, the three calls alternating inside
+             every round: the three times, the ratios, and how many different paths the K trajectories have in every stretch (the median
+             over the problems) under backward simulation and under the genealogy.  --parent-json: the output of the parent commit's
+             `--paths` run of the same jobs and strides on the same box (its own checkout and library, its processes alternating with
+             this tool's): its particle_paths time is reported beside, as parent_paths_ms_per_call
 
   --forecast   particle_forecast from a given cloud on a bare Lorenz-96 context (a model, theta, Sigma and dt: nothing evaluated), D = 40,
              B = 512, n = 4096 equally weighted particles, H = 1000 steps, no members, once with stride H (the sums at h = 0 and H alone)
@@ -79,6 +88,7 @@ STATS = {f"{t}s{n}_{f}": (t, n, 0.1 * f) for t in "ab" for n in (64, 1024) for f
 MOMENTS = {f"{t}m{n}_{s}": (t, n, s) for t in "ab" for n in (64, 1024) for s in (1, 10, N_PTS + 3)}          # job -> (context of, particles, stride)
 COV = {f"{t}c{n}_{s}": (t, n, s) for t in "ab" for n in (64, 1024) for s in (1, 10, N_PTS + 3) if t == "b" or s > 1}          # job -> as MOMENTS
 PATHS = {f"{t}p{n}_{k}": (t, n, k) for t in "ab" for n in (64, 1024) for k in (16, 64)}           # job -> (context of, particles, trajectories)
+BACKWARD = {f"{t}b{n}_{k}": (t, n, k) for t in "ab" for n in (64, 1024) for k in (16, 64)}        # job -> as PATHS
 
 
 def tree():
@@ -151,14 +161,14 @@ def run_forecast(B, n, horizon, rounds, calls):
     return out
 
 
-def run(job, rounds, calls, numpy_problems, cache, filter_problems=0, paths_stride=1):
+def run(job, rounds, calls, numpy_problems, cache, filter_problems=0, paths_stride=1, parent=None):
     from bench_problem_batch import StreamTimer, make_contexts
     twin, stored = WEIGHTED.get(job, (job, True))
     weighted = job in WEIGHTED
-    if job in FILTER or job in STATS or job in MOMENTS or job in COV or job in PATHS:
-        twin = (FILTER.get(job) or STATS.get(job) or MOMENTS.get(job) or COV.get(job) or PATHS[job])[0]
+    if job in FILTER or job in STATS or job in MOMENTS or job in COV or job in PATHS or job in BACKWARD:
+        twin = (FILTER.get(job) or STATS.get(job) or MOMENTS.get(job) or COV.get(job) or PATHS.get(job) or BACKWARD[job])[0]
     name, d, B, kind, n_paths, stride = JOBS[twin]
-    if (job in FILTER or job in STATS or job in MOMENTS or job in COV or job in PATHS) and twin == "b" and filter_problems:
+    if (job in FILTER or job in STATS or job in MOMENTS or job in COV or job in PATHS or job in BACKWARD) and twin == "b" and filter_problems:
         B = min(B, filter_problems)
     if (name, B) not in cache:                        # (b and c share a context)
         from helpers import SEED, build_problem
@@ -299,6 +309,46 @@ def run(job, rounds, calls, numpy_problems, cache, filter_problems=0, paths_stri
                 "observations": int(c.n_obs), "resampled_share": round(float(res0["filter"]["resampled"].mean()), 3),
                 "distinct_first_stretch_median": distinct[0], "distinct_last_stretch_median": distinct[1],
                 "d2h_mb": round(8.0 * B * (n_paths * (1 + d) + n_draw * n_keep * d) / 1e6, 1)}
+    if job in BACKWARD:
+        _, n_paths, n_draw = BACKWARD[job]
+        stride = paths_stride
+        calls_of = {"filter": lambda: c.particle_filter(n_paths, 1, ess_fraction=0.5),
+                    "paths": lambda: c.particle_paths(n_paths, 1, n_draw, stride=stride, ess_fraction=0.5),
+                    "backward": lambda: c.particle_backward_paths(n_paths, 1, n_draw, stride=stride, ess_fraction=0.5)}
+        res0 = {k: f() for k, f in calls_of.items()}      # warm-up (first-use allocations)
+        n_keep = (N_PTS - 1) // stride + 1
+        for key in ("log_w", "state", "ess", "resampled"):
+            assert np.array_equal(res0["filter"][key], res0["backward"][key]) and np.array_equal(res0["filter"][key], res0["paths"][key]), key
+        assert res0["backward"]["paths"].shape == (B, n_draw, n_keep, d) and np.all(np.isfinite(res0["backward"]["paths"]))
+        tables = {k: res0[k]["slots"] for k in ("paths", "backward")}
+        assert np.array_equal(tables["paths"][:, -1], tables["backward"][:, -1])      # (the same final slots)
+        distinct = {k: [float(np.median([np.unique(row).size for row in t[:, j]])) for j in range(t.shape[1])] for k, t in tables.items()}
+        del res0["paths"]["paths"], res0["backward"]["paths"]
+        per_round = {k: [] for k in calls_of}
+        for _ in range(rounds):
+            ms = {k: [] for k in calls_of}
+            for _ in range(calls):
+                for k, f in calls_of.items():
+                    ms[k].append(tm.ms(f))
+            for k in calls_of:
+                per_round[k].append(float(np.median(ms[k])))
+        med = {k: float(np.median(v)) for k, v in per_round.items()}
+        out = {"job": job, "model": name, "D": d, "Np": N_PTS, "B": B, "kind": "backward", "n_paths": n_paths, "n_draw": n_draw, "ess_fraction": 0.5,
+               "stride": stride, "backward_ms_per_call": round(med["backward"], 4), "paths_ms_per_call": round(med["paths"], 4),
+               "filter_ms_per_call": round(med["filter"], 4), "ratio_to_paths": round(med["backward"] / med["paths"], 4),
+               "ratio_to_filter": round(med["backward"] / med["filter"], 4),
+               "backward_rounds_ms": [round(v, 4) for v in per_round["backward"]], "paths_rounds_ms": [round(v, 4) for v in per_round["paths"]],
+               "filter_rounds_ms": [round(v, 4) for v in per_round["filter"]],
+               "observations": int(c.n_obs), "resampled_share": round(float(res0["filter"]["resampled"].mean()), 3),
+               "distinct_per_stretch_median_backward": distinct["backward"], "distinct_per_stretch_median_genealogy": distinct["paths"],
+               "histories_on_device_mb": round(8.0 * B * int(c.n_obs) * n_paths * (d + 1) / 1e6, 1),
+               "d2h_mb": round(8.0 * B * (n_paths * (1 + d) + n_draw * n_keep * d) / 1e6, 1)}
+        twin_job = job.replace("b", "p", 1) if job[0] == "a" else "bp" + job[2:]
+        row = (parent or {}).get((twin_job, stride))
+        if row:
+            out.update(parent_tree=row["tree"], parent_paths_ms_per_call=row["paths_ms_per_call"], parent_paths_rounds_ms=row["paths_rounds_ms"],
+                       parent_filter_ms_per_call=row["filter_ms_per_call"], ratio_to_parent_paths=round(med["backward"] / row["paths_ms_per_call"], 4))
+        return out
     if job in FILTER:
         _, n_paths, frac = FILTER[job]
         call = lambda: c.particle_filter(n_paths, 1, ess_fraction=frac)      # noqa: E731
@@ -348,6 +398,8 @@ def main():
     ap.add_argument("--covariance", action="store_true", help="run the ac* and bc* jobs (particle_covariance beside particle_moments and particle_filter)")
     ap.add_argument("--paths", action="store_true", help="run the ap* and bp* jobs (particle_paths beside particle_filter)")
     ap.add_argument("--paths-strides", default="1,10", help="strides of the ap* and bp* jobs: each job runs once per stride")
+    ap.add_argument("--backward", action="store_true", help="run the ab* and bb* jobs (particle_backward_paths beside particle_paths and particle_filter)")
+    ap.add_argument("--parent-json", default="", help="output of the parent commit's --paths run of the same jobs: its times are reported beside")
     ap.add_argument("--forecast", action="store_true", help="run the forecast job (particle_forecast from a given cloud beside the model-kind sampler)")
     ap.add_argument("--forecast-problems", type=int, default=512)
     ap.add_argument("--forecast-particles", type=int, default=4096)
@@ -366,12 +418,22 @@ def main():
         args.jobs = ",".join(sorted(COV))
     if args.paths:
         args.jobs = ",".join(sorted(PATHS))
+    if args.backward and args.jobs == "a,b,c":
+        args.jobs = ",".join(sorted(BACKWARD))
+    parent = {}
+    if args.parent_json:      # (one JSON line per run of the parent's tool; a later run of a job replaces an earlier one)
+        with open(args.parent_json) as fh:
+            for line in fh:
+                if line.strip().startswith("{"):
+                    doc = json.loads(line)
+                    for row in doc.get("jobs", []):
+                        parent[(row["job"], row.get("stride", 1))] = dict(row, tree=doc.get("tree", "unknown"))
     strides = [int(v) for v in args.paths_strides.split(",") if v]
     cache = {}
     out = {"tool": "bench_sample_paths", "tree": tree(), "unit": "ms per call (device events around the call)", "jobs": []}
     for job in [j for j in args.jobs.split(",") if j]:
-        for stride in (strides if job in PATHS else [1]):
-            out["jobs"].append(run(job, args.rounds, args.calls, args.numpy_problems, cache, args.filter_problems, stride))
+        for stride in (strides if job in PATHS or job in BACKWARD else [1]):
+            out["jobs"].append(run(job, args.rounds, args.calls, args.numpy_problems, cache, args.filter_problems, stride, parent))
     for c, _, _, _, tm in cache.values():
         tm.close()
         c.close()

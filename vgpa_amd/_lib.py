@@ -36,7 +36,7 @@ BWD_IDS = {"none": 0, "psi": 1, "q": 2}
 SYMBOLS = ["vgpa_create", "vgpa_destroy", "vgpa_last_error", "vgpa_abi_version", "vgpa_device_count",
            "vgpa_synchronize", "vgpa_stream", "vgpa_solve_fwd", "vgpa_solve_bwd", "vgpa_energy",
            "vgpa_obs_energy", "vgpa_free_energy", "vgpa_gradient", "vgpa_sweep", "vgpa_energy_parts",
-           "vgpa_fetch", "vgpa_theta_gradient", "vgpa_sample_paths", "vgpa_sample_paths_weighted", "vgpa_particle_filter", "vgpa_particle_statistics", "vgpa_particle_moments", "vgpa_particle_covariance", "vgpa_particle_paths", "vgpa_particle_forecast", "vgpa_sweep_dev", "vgpa_free_energy_dev", "vgpa_sweep_enqueue", "vgpa_fetch_f",
+           "vgpa_fetch", "vgpa_theta_gradient", "vgpa_sample_paths", "vgpa_sample_paths_weighted", "vgpa_particle_filter", "vgpa_particle_statistics", "vgpa_particle_moments", "vgpa_particle_covariance", "vgpa_particle_paths", "vgpa_particle_backward_paths", "vgpa_particle_forecast", "vgpa_sweep_dev", "vgpa_free_energy_dev", "vgpa_sweep_enqueue", "vgpa_fetch_f",
            "vgpa_dev_alloc", "vgpa_dev_free", "vgpa_memcpy_h2d", "vgpa_memcpy_d2h",
            "vgpa_profile_begin", "vgpa_profile_end", "vgpa_ld_gemm", "vgpa_ld_stage", "vgpa_gradient_dev", "vgpa_energy_full", "vgpa_set_option", "vgpa_is_streaming", "vgpa_path_info", "vgpa_set_prior_energy",
            "vgpa_set_problem_data", "vgpa_set_problem_params", "vgpa_set_problem_obs_model",
@@ -150,6 +150,7 @@ def load():
                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vgpa_particle_paths.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_uint64, c_double, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.vgpa_particle_backward_paths.argtypes = lib.vgpa_particle_paths.argtypes
     lib.vgpa_particle_forecast.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_uint64, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                                            c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_void_p]
@@ -704,6 +705,18 @@ class Context:
         weighted), their slot in every stretch traced back through the ancestors, and one walk of the trajectories alone.  Returns a dict:
         log_w, state, ess, resampled as particle_filter (bit for bit), paths (B, n_draw, n_keep, D) at the grid indices 0, stride, ..., and
         slots (B, M + 1, n_draw) int32: the slot of every trajectory in every stretch (-1 beyond a problem's own count + 1)."""
+        return self._smoothing_paths(self._lib.vgpa_particle_paths, n_paths, seed, n_draw, stride, ess_fraction, x, x0, prior, slots)
+
+    def particle_backward_paths(self, n_paths, seed, n_draw, stride=1, ess_fraction=0.5, x=None, x0=None, prior=None, slots=None):
+        """n_draw whole smoothing trajectories per problem by backward simulation through particle_filter's clouds
+        (vgpa_particle_backward_paths): the arguments and the dict of particle_paths, the filter and the final slots the same; but at every
+        observation where the cloud was resampled a trajectory does not follow its ancestor: it draws the slot it came from among all n
+        particles, with probability proportional to filter weight times model transition density (Gumbel-max on the device, one launch).
+        Where nothing was resampled (ess_fraction=0, n_paths=1) the result is particle_paths' bit for bit."""
+        return self._smoothing_paths(self._lib.vgpa_particle_backward_paths, n_paths, seed, n_draw, stride, ess_fraction, x, x0, prior, slots)
+
+    def _smoothing_paths(self, entry, n_paths, seed, n_draw, stride, ess_fraction, x, x0, prior, slots):
+        """the arguments of particle_paths / particle_backward_paths checked and laid out, the call, the dict"""
         n_paths, n_draw, stride, m = int(n_paths), int(n_draw), int(stride), self.n_obs
         if not all(-2 ** 31 <= v < 2 ** 31 for v in (n_paths, n_draw, stride)):      # (the C ABI takes int32: nothing may wrap on its way there)
             raise ValueError(f"n_paths, n_draw and stride must fit into 32 bits (n_paths = {n_paths}, n_draw = {n_draw}, stride = {stride})")
@@ -726,9 +739,8 @@ class Context:
         ess, flags = np.zeros((self.B, m)), np.zeros((self.B, m), dtype=np.int32)
         paths = np.empty((self.B, k, (self.Np - 1) // max(stride, 1) + 1, self.D))
         table = np.full((self.B, m + 1, k), -1, dtype=np.int32)
-        self._check(self._lib.vgpa_particle_paths(self._h, _ptr(xx), _ptr(s0), n_paths, n_draw, _ptr(given), stride, int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                                  float(ess_fraction), _ptr(mu), _ptr(tau), _ptr(log_w), _ptr(state), _ptr(paths), _ptr(table),
-                                                  _ptr(ess), _ptr(flags)))
+        self._check(entry(self._h, _ptr(xx), _ptr(s0), n_paths, n_draw, _ptr(given), stride, int(seed) & 0xFFFFFFFFFFFFFFFF, float(ess_fraction),
+                          _ptr(mu), _ptr(tau), _ptr(log_w), _ptr(state), _ptr(paths), _ptr(table), _ptr(ess), _ptr(flags)))
         return {"log_w": log_w, "state": state, "ess": ess, "resampled": flags, "paths": paths, "slots": table}
 
     def particle_forecast(self, horizon, n_paths=None, seed=0, stride=1, n_draw=0, ess_fraction=0.5, x=None, x0=None, cloud=None, log_w=None,

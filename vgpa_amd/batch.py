@@ -252,6 +252,16 @@ class ProblemBatch(object):
         res = self._context().particle_paths(n_paths, seed, n_draw, stride=stride, ess_fraction=ess_fraction, x=xx, x0=x0, prior=prior, slots=slots)
         return [v._paths_record(res, k, stride, slots is None) for k, v in enumerate(self.vgps)]
 
+    def backward_paths(self, n_paths, seed, n_draw, stride=1, ess_fraction=0.5, x=None, x0=None, slots=None):
+        """One particles.SmoothingPaths per member (VarGP.backward_paths): n_draw whole smoothing trajectories drawn backwards through the
+        clouds of the member's own filter, with its own data, observation times and count, prior, theta and Sigma."""
+        xx = None if x is None else self._stack(x)
+        d = self.vgps[0].dim_d
+        prior = (np.stack([v._prior()[0][0] for v in self.vgps]), np.stack([v._prior()[1][0] for v in self.vgps]).reshape(self.B, d, d))
+        res = self._context().particle_backward_paths(n_paths, seed, n_draw, stride=stride, ess_fraction=ess_fraction, x=xx, x0=x0, prior=prior,
+                                                      slots=slots)
+        return [v._paths_record(res, k, stride, slots is None, method="backward") for k, v in enumerate(self.vgps)]
+
     def forecast(self, horizon, n_paths=None, seed=0, stride=1, n_draw=0, ess_fraction=0.5, x=None, x0=None, source="filter", cloud=None,
                  log_w=None, index0=None, slots=None):
         """One particles.Forecast per member (VarGP.forecast): every member's cloud -- its own filter's final one, the end points of its

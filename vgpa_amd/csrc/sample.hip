@@ -34,6 +34,9 @@
 //   ReplayCov    | the replay with the whole matrix: at every kept grid index the workgroup's sums of W x and of the lower triangle | s.4.16
 //                | of W x x^T, above D = 4 as X diag(W) X^T of each wave's 16 states on the matrix pipe  [the replay's steps;        |
 //                | k_pf_cov_unpack: the packed sums to mean [D] and second [D][D], both triangles from one entry]                   |
+//   Backward     | the lineage walk of a table that backward simulation has drawn: behind every observation of its problem the lane | s.4.17
+//                | goes on from the filter's stored particle its next slot was copied from  [k_pf_backward draws the table in the   |
+//                | trace's place: at every resampled observation a Gumbel-max draw among all n particles of the stored cloud]       |
 #include "vgpa_internal.h"
 
 #include <type_traits>
@@ -147,9 +150,10 @@ __device__ __forceinline__ double wave_max(double v) {
 // What the two kernels branch on, per walk: W the walk of the weighted kind (posterior drift, diagonal R), SEG it runs (k_begin, k_end] from
 // and to pf_x, ST it carries the rows of pf_stats, MO it takes the moments of the replay, LN the counter words come from pf_slots;
 // FC it is the forecast (the model's drift from the cloud in pf_x, k_sample_small only); CV the replay's second moments are the whole matrix
-// (with MO); WS: the weight sums are formed.  The eight rows are all there is: no other combination can be instantiated.
+// (with MO); BW: the state is reloaded from the filter's histories behind every observation (with LN); WS: the weight sums are formed.  The
+// nine rows are all there is: no other combination can be instantiated.
 struct WalkTraits {
-  bool W, SEG, ST, MO, LN, FC, CV;
+  bool W, SEG, ST, MO, LN, FC, CV, BW;
   constexpr bool WS() const { return W && !MO; }
 };
 constexpr WalkTraits kWalkTraits[] = {      // in the order of Walk
@@ -160,7 +164,8 @@ constexpr WalkTraits kWalkTraits[] = {      // in the order of Walk
     {true,  true,  false, true,  false, false},    // Replay
     {false, false, false, false, true,  false},    // Lineage
     {false, false, false, false, false, true},     // Forecast
-    {true,  true,  false, true,  false, false, true}};    // ReplayCov
+    {true,  true,  false, true,  false, false, true},     // ReplayCov
+    {false, false, false, false, true,  false, false, true}};    // Backward
 
 // Weighted: posterior kind, diagonal R: both drifts at x_{k-1}, d = g - f, and per step -sum_i d_i (eta_i + dt d_i / 2) / Sigma_ii with
 // 1 / Sigma_ii = dt / R_ii^2; the observation term at the lane's own problem's times.
@@ -176,15 +181,28 @@ constexpr WalkTraits kWalkTraits[] = {      // in the order of Walk
 // Lineage: the unweighted posterior walk of lane m = `path`, whose counter word is not m but the entry of its column of pf_slots for the
 // stretch it is in: row 0 for the start, the next row each time the walk has completed an observation index of the lane's own problem (an
 // observation at index 0: before step 1).  No model drift, no sums.
+// Backward: the lineage walk, and where it changes its counter word -- behind the completed observation j of its problem, whose point has
+// been stored -- the state becomes pf_clouds[p][j][pf_hanc[p][j][s]], s the new word: the particle slot s was copied from (pf_hanc is the
+// identity where the cloud was carried on: the reload then changes no bit).
 // Forecast: launched as the replay is (the problem in blockIdx.x, 256 lanes per workgroup).  The model's drift alone, step h = 1 .. k_end -
 // k_begin drawn at the absolute grid index k_begin + h, from the slot's state in pf_x.  The cloud launch (pf_part set): lane = slot, the
 // replay's sums with W = pf_wtab at h = 0, stride, ..., the end state back to pf_x.  The member launch (out, pf_slots set): lane m starts from
 // slot pf_slots[p][m], draws with that slot's word and stores as Plain stores.  A lane behind the last one walks the last one again with
 // weight 0 and stores nothing.
+// Walk::Backward: x = the particle slot `word` was copied from at observation j of problem p (pf_clouds, pf_hanc and pf_M are the walk's own
+// names of the storage of pf_wtab, pf_part and pf_rows: vgpa_internal.h)
+template <int D>
+__device__ __forceinline__ void backward_reload(const SampleArgs& a, uint32_t p, int j, uint32_t word, double* x) {
+  const size_t hj = (size_t)p * a.pf_M + j;
+  const double* src = a.pf_clouds + (hj * a.pf_n + (size_t)a.pf_hanc[hj * a.pf_n + word]) * D;
+#pragma unroll
+  for (int i = 0; i < D; i++) x[i] = src[i];
+}
+
 template <int D, Walk K>
 __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
   constexpr WalkTraits T = kWalkTraits[(int)K];
-  constexpr bool W = T.W, SEG = T.SEG, ST = T.ST, MO = T.MO, LN = T.LN, FC = T.FC, CV = T.CV, WS = T.WS();
+  constexpr bool W = T.W, SEG = T.SEG, ST = T.ST, MO = T.MO, LN = T.LN, FC = T.FC, CV = T.CV, BW = T.BW, WS = T.WS();
   constexpr int NV = CV ? D + D * (D + 1) / 2 : 2 * D;      // values a kept k reduces
   size_t gid;
   uint32_t p, path;
@@ -264,7 +282,10 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
   }
   if constexpr (LN) {
     oc = ObsCursor(a, p);
-    if (oc.next == 0) { oc.advance(); word = (uint32_t)lin[(size_t)oc.cur * a.n_paths]; }
+    if (oc.next == 0) {
+      oc.advance(); word = (uint32_t)lin[(size_t)oc.cur * a.n_paths];
+      if constexpr (BW) backward_reload<D>(a, p, 0, word, x);
+    }
   }
   // Replay: the segment lies in one stretch of its problem -- the observations behind it are oc.cur, the row of the weights
   double wt = 0.0;
@@ -380,6 +401,9 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
         o += NBUF * D;
       }
     }
+    if constexpr (BW) {      // (the step completed observation oc.cur - 1 of the lane's problem; its point is stored: now the state is replaced)
+      if (oc.cur > 0 && (int)oc.t[oc.cur - 1] == k) backward_reload<D>(a, p, oc.cur - 1, word, x);
+    }
   }
   for (int e = 0; e < slot * D; e++) o[e] = sg[e * 256];
   if constexpr (FC) {
@@ -460,10 +484,12 @@ __device__ __forceinline__ void normals_c(uint32_t k0, uint32_t k1, uint32_t k, 
 // round's slots are read before the next step's barriers, the next kept k writes them behind those.
 // Lineage: as in k_sample_small (diagonal R): every lane of a workgroup belongs to one problem, so all of them change their counter words
 // behind the same steps.  A lane behind the last lineage walks the last one again and stores nothing.
+// Backward: as in k_sample_small; the reload is a gather of the lane's own rows of its path's new particle into the accumulator layout, which
+// then goes to Xs as every step's result does, behind the store of the completed observation's point and in front of one more barrier.
 template <int NT, Walk K>
 __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
   constexpr WalkTraits T = kWalkTraits[(int)K];
-  constexpr bool W = T.W, SEG = T.SEG, ST = T.ST, MO = T.MO, LN = T.LN, CV = T.CV, WS = T.WS();
+  constexpr bool W = T.W, SEG = T.SEG, ST = T.ST, MO = T.MO, LN = T.LN, CV = T.CV, BW = T.BW, WS = T.WS();
   using Sh = MfmaShape<NT>;
   constexpr int LDA = Sh::LDA, MT = Sh::MT, KT = Sh::KT, NPF = Sh::NPF;
   extern __shared__ double lds[];
@@ -612,8 +638,26 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
     if constexpr (!SEG) put(a.start + ((size_t)p * a.n_paths + path0) * D, (size_t)D);
     if (oc.next == 0) observe();
   }
+  // Backward: the particle slot `word` was copied from at the problem's observation j, to x and to the path's column of Xs (the points kept so
+  // far have left Xs: the stores of `put` precede these writes in every lane of the wave that owns the region)
+  auto reload = [&](int j) {      // (pf_clouds, pf_hanc, pf_M: the storage of pf_wtab, pf_part, pf_rows, which this walk does not read)
+    const size_t hj = (size_t)p * a.pf_M + j;
+    const double* src = a.pf_clouds + (hj * a.pf_n + (size_t)a.pf_hanc[hj * a.pf_n + word]) * D;
+#pragma unroll
+    for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const int row = mt * 16 + q + 4 * r;
+        x[mt][r] = row < D ? src[row] : 0.0;
+        Xs[row * 16 + j16] = x[mt][r];
+      }
+    __syncthreads();      // (uniform: the lanes of a workgroup belong to one problem)
+  };
   if constexpr (LN) {
-    if (oc.next == 0) { oc.advance(); word = (uint32_t)lin[(size_t)oc.cur * a.n_paths]; }
+    if (oc.next == 0) {
+      oc.advance(); word = (uint32_t)lin[(size_t)oc.cur * a.n_paths];
+      if constexpr (BW) reload(oc.cur - 1);
+    }
   }
   // Replay: the segment lies in one stretch of its problem -- the observations behind it are oc.cur, the row of the weights
   double wt = 0.0;
@@ -799,7 +843,10 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
       if (k == keep_k) { reduce_cov(keep_slot++); keep_k += a.stride; }
     }
     if constexpr (LN) {
-      if (k == oc.next) { oc.advance(); word = (uint32_t)lin[(size_t)oc.cur * a.n_paths]; }
+      if (k == oc.next) {
+        oc.advance(); word = (uint32_t)lin[(size_t)oc.cur * a.n_paths];
+        if constexpr (BW) reload(oc.cur - 1);
+      }
     }
   }
   if constexpr (MO) {
@@ -1068,7 +1115,7 @@ __device__ __forceinline__ double pf_prefix_sums(const double* lw, int n, double
 // slot order (256 slots per pass: a shuffle scan per wave, the waves' totals and the carry through LDS); resampled iff ESS < ess_fraction n and
 // a.k is not the last grid index: anc_i = min(#{m: cum_m <= (U + i) / n S}, n - 1) by bisection, U from Philox counter (k, 0, p, 0xffffffff),
 // x_out_i = x_in_{anc_i}, lw_i = max lw + log S - log n; else anc_i = i and lw stays.  The histories of observation j (t_j = a.k) are
-// written where asked for; the cloud is x_in.
+// written where asked for; the cloud is x_in, and h_lw gets the log-weights a resampling replaces (no other row of it is written or read).
 // ST: the [3][D] rows of path statistics go from st_in to st_out by the same ancestors (two buffers, as for x: no slot is read after it is
 // written).
 template <bool ST>
@@ -1123,6 +1170,7 @@ __global__ __launch_bounds__(256) void k_pf_resample(PfArgs a) {
         if (cum[mid] <= ui) lo = mid + 1; else hi = mid;
       }
       from = lo < n - 1 ? lo : n - 1;
+      if (a.h_lw) a.h_lw[hj * n + i] = lw[i];
       lw[i] = lw_new;
     }
     anc[i] = from;
@@ -1339,9 +1387,162 @@ __global__ __launch_bounds__(256) void k_pf_trace(PfArgs a, int K, int rows, int
   }
 }
 
+// ---- backward simulation: the slot table of vgpa_particle_backward_paths, in the trace's place -------------------------
+// Workgroup (p, blk) owns the kBackwardBlock trajectories m = blk kBackwardBlock + mm of problem p and walks that problem's cuts
+// j = c-1 .. 0 itself: one launch, nothing between workgroups.  Where the cloud was carried on, row j of the table is row j + 1.  Where it
+// was resampled (k = t_j < Np-1):
+//   x~   thread e < kBackwardBlock D forms component e mod D of trajectory e / D's next state in plain fp64, (z + dt (b_k - A_k z)) + R_dd xi
+//        with z = clouds_j[anc_j[s]], s the trajectory's slot in stretch j + 1, xi the sampler's normal of counter (k + 1, s, p, .); to LDS;
+//   mu   the n candidates go through LDS 256 at a time: a tile of clouds_j is 256 D consecutive doubles, loaded in that order and written
+//        component-major with a row stride of 257 doubles (consecutive components of a candidate fall into consecutive bank pairs; a
+//        thread's own column is read without conflict).  Thread t owns candidate base + t and forms its transition mean x + dt f(x) once
+//        per tile -- D = 1, 3: model_drift<DC> in registers; DC = 0: Lorenz-96 of any D, circular on the candidate's own column, in place
+//        behind three rolling registers as in k_sample_l96 -- for all of the block's trajectories;
+//   b    sum_d ((x~_d - mu_d) (1 / R_dd))^2 for the block's trajectories side by side, mu_d read once per d; b = hlw_j[i] - sum / 2;
+//   g    -log(-log u): the lanes of candidates 2 q and 2 q + 1 share the Philox call of counter (k, m, p, 0x80000000 | q) -- the even lane
+//        makes it for trajectory mm, the odd one for mm + 1, and each hands the half it does not use to its partner;
+//   max  each thread keeps (score, slot) of its best candidate per trajectory; a butterfly over the wave and four LDS words over the
+//        workgroup keep the larger score and, of equal scores, the smaller slot: the smallest i that attains the maximum, whatever the
+//        tiling.
+// A trajectory behind the last one is the last one again and stores nothing.
+template <int DC>
+__global__ __launch_bounds__(256) void k_pf_backward(PfArgs f, SampleArgs a, int K, int rows, int32_t* table) {
+  constexpr int TB = kBackwardBlock, LD = 257;
+  extern __shared__ double lds[];
+  const int D = DC > 0 ? DC : a.D;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, n = f.n_paths, odd = lane & 1;
+  const uint32_t p = blockIdx.x;
+  double* tile = lds;                           // [D][LD]
+  double* xt = tile + (size_t)D * LD;           // [TB][D]
+  double* ir = xt + TB * D;                     // [D] 1 / R_dd
+  double* rbest = ir + D;                       // [4 waves][TB]
+  int* rslot = reinterpret_cast<int*>(rbest + 4 * TB);      // [4 waves][TB]
+  int* scur = rslot + 4 * TB;                   // [TB] the block's slots in the stretch behind the cut
+  const int cnt = f.n_obs_v ? f.n_obs_v[p] : f.n_obs;
+  const int64_t* t = f.obs_t + (size_t)p * f.obs_t_stride;
+  const uint32_t k0 = (uint32_t)(f.seed & 0xffffffffu), k1 = (uint32_t)(f.seed >> 32);
+  const double* Rp = a.R + (size_t)p * a.R_stride;
+  double th[kMaxTheta];
+#pragma unroll
+  for (int i = 0; i < kMaxTheta; i++) th[i] = a.theta_v ? a.theta_v[(size_t)p * kMaxTheta + i] : a.theta[i];
+  const int m0 = blockIdx.y * TB;
+  if (tid < TB) scur[tid] = table[((size_t)p * rows + cnt) * K + (m0 + tid < K ? m0 + tid : K - 1)];
+  if (tid < D) ir[tid] = 1.0 / Rp[tid * D + tid];
+  __syncthreads();
+  for (int j = cnt - 1; j >= 0; j--) {
+    const size_t hj = (size_t)p * f.M + j;
+    int32_t* row = table + ((size_t)p * rows + j) * K;
+    if (!f.h_flag[hj]) {      // (uniform over the workgroup)
+      if (tid < TB && m0 + tid < K) row[m0 + tid] = scur[tid];
+      continue;
+    }
+    const int k = (int)t[j];
+    const double* cloud = f.h_clouds + hj * n * D;
+    const int32_t* anc = f.h_anc + hj * n;
+    const double* hlw = f.h_lw + hj * n;
+    const double* Ak = a.A + (size_t)p * a.stride_x + (size_t)k * D * D;
+    const double* bk = a.b + (size_t)p * a.stride_x + (size_t)k * D;
+    for (int e = tid; e < TB * D; e += 256) {
+      const int mm = e / D, d = e - mm * D;
+      const uint32_t s = (uint32_t)scur[mm];
+      const double* z = cloud + (size_t)anc[s] * D;
+      double sum = 0.0, z0, z1;
+      for (int c = 0; c < D; c++) sum += Ak[d * D + c] * z[c];
+      normal_pair(k0, k1, (uint32_t)k + 1u, s, p, (uint32_t)(d >> 1), &z0, &z1);
+      xt[e] = (z[d] + a.dt * (bk[d] - sum)) + Rp[d * D + d] * ((d & 1) ? z1 : z0);
+    }
+    double best[TB];
+    int bslot[TB];
+#pragma unroll
+    for (int mm = 0; mm < TB; mm++) { best[mm] = -INFINITY; bslot[mm] = 0x7fffffff; }
+    for (int base = 0; base < n; base += 256) {
+      __syncthreads();      // (x~ is written; the columns of the tile before have been read)
+      const int nt = n - base < 256 ? n - base : 256;
+      const double* src = cloud + (size_t)base * D;
+      for (int e = tid; e < nt * D; e += 256) { const int cnd = e / D; tile[(e - cnd * D) * LD + cnd] = src[e]; }
+      __syncthreads();
+      const int i = base + tid;
+      const bool mine = i < n;
+      double* col = tile + tid;
+      double mu[DC > 0 ? DC : 1];
+      if constexpr (DC > 0) {
+        double xc[DC], fc[DC];
+#pragma unroll
+        for (int d = 0; d < DC; d++) xc[d] = mine ? col[d * LD] : 0.0;      // (a lane behind the last candidate: no stale LDS into the drift)
+        model_drift<DC>(a.model, th, xc, fc);
+#pragma unroll
+        for (int d = 0; d < DC; d++) mu[d] = xc[d] + a.dt * fc[d];
+      } else if (mine) {
+        const double x_first = col[0];
+        double om2 = col[(D - 2) * LD], om1 = col[(D - 1) * LD], cur = x_first;
+        for (int d = 0; d < D; d++) {
+          const double nxt = d + 1 < D ? col[(d + 1) * LD] : x_first;
+          const double fd = (nxt - om2) * om1 - cur + th[0];
+          col[d * LD] = cur + a.dt * fd;
+          om2 = om1; om1 = cur; cur = nxt;
+        }
+      }
+      double acc[TB];
+#pragma unroll
+      for (int mm = 0; mm < TB; mm++) acc[mm] = 0.0;
+      if (mine) {
+        for (int d = 0; d < D; d++) {
+          double md;
+          if constexpr (DC > 0) md = mu[d]; else md = col[d * LD];
+          const double ird = ir[d];
+#pragma unroll
+          for (int mm = 0; mm < TB; mm++) { const double v = (xt[mm * D + d] - md) * ird; acc[mm] += v * v; }
+        }
+      }
+      const double lwi = mine ? hlw[i] : 0.0;
+#pragma unroll
+      for (int mm = 0; mm < TB; mm += 2) {
+        const int m = m0 + mm + odd;
+        uint32_t r[4];
+        philox4x32_10((uint32_t)k, (uint32_t)(m < K ? m : K - 1), p, 0x80000000u | ((uint32_t)i >> 1), k0, k1, r);
+        const double ua = unit_open(r[0], r[1]), ub = unit_open(r[2], r[3]);
+        const double got = __shfl_xor(odd ? ua : ub, 1);
+        const double u[2] = {odd ? got : ua, odd ? ub : got};      // this candidate's uniforms of trajectories mm and mm + 1
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+          const double sc = (lwi - 0.5 * acc[mm + h]) + -log(-log(u[h]));
+          if (mine && (sc > best[mm + h] || (sc == best[mm + h] && i < bslot[mm + h]))) { best[mm + h] = sc; bslot[mm + h] = i; }
+        }
+      }
+    }
+#pragma unroll
+    for (int mm = 0; mm < TB; mm++) {
+      double v = best[mm];
+      int sl = bslot[mm];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const double ov = __shfl_xor(v, o);
+        const int os = __shfl_xor(sl, o);
+        if (ov > v || (ov == v && os < sl)) { v = ov; sl = os; }
+      }
+      if (lane == 0) { rbest[w * TB + mm] = v; rslot[w * TB + mm] = sl; }
+    }
+    __syncthreads();
+    if (tid < TB) {
+      double v = rbest[tid];
+      int sl = rslot[tid];
+      for (int q = 1; q < 4; q++) {
+        const double ov = rbest[q * TB + tid];
+        const int os = rslot[q * TB + tid];
+        if (ov > v || (ov == v && os < sl)) { v = ov; sl = os; }
+      }
+      sl = sl < n ? sl : n - 1;      // (no finite score at all: any slot of the cloud)
+      scur[tid] = sl;
+      if (m0 + tid < K) row[m0 + tid] = sl;
+    }
+    __syncthreads();
+  }
+}
+
 // One walk at the D of the arguments: k_sample_small<D, K> up to D = 4 (one lane per path; the replay: the problem in grid.x, 256 slots per
 // workgroup in grid.y), above it k_sample_mfma<NT, K> with NT the next multiple of 16 (grid: problems x 64 paths).  D = 2 exists for the
-// plain walk only: every other walk needs a stochastic model, and none has D = 2.
+// plain walk only: every other walk needs a stochastic model, and none has D = 2.  (Nine walks: 3 instantiations of k_sample_small each
+// and one more for Plain, 4 of k_sample_mfma each but Forecast.)
 template <Walk K>
 hipError_t launch_walk(const SampleArgs& a, hipStream_t st) {
   if (a.D <= kMaxLaneD) {
@@ -1438,6 +1639,25 @@ hipError_t launch_pf_trace(const PfArgs& a, int K, int rows, int32_t* table, hip
   return hipGetLastError();
 }
 
+hipError_t launch_pf_backward(const PfArgs& f, const SampleArgs& a, int K, int rows, int32_t* table, hipStream_t st) {
+  if (f.batch < 1 || f.n_paths < 1 || f.M < 1 || K < 1 || rows < 1 || !pf_backward_fits(K) || !f.h_flag || !f.h_anc || !f.h_clouds || !f.h_lw || !table)
+    return hipErrorInvalidValue;
+  if (a.D < 1 || a.D > kMaxSmallD || a.D != f.D || !a.A || !a.b || !a.R || !a.R_diag) return hipErrorInvalidValue;
+  const dim3 grid(f.batch, (K + kBackwardBlock - 1) / kBackwardBlock), block(256);
+  const size_t lds = ((size_t)a.D * 257 + (size_t)kBackwardBlock * a.D + a.D + 4 * kBackwardBlock) * sizeof(double) + 5 * kBackwardBlock * sizeof(int);
+  if (a.model == VGPA_MODEL_L96 && a.D >= 3) {      // (the circular drift on a column of any length)
+    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k_pf_backward<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(k_pf_backward<0>, grid, block, lds, st, f, a, K, rows, table);
+  } else if (a.D == 1 && (a.model == VGPA_MODEL_OU || a.model == VGPA_MODEL_DW)) {
+    hipLaunchKernelGGL(k_pf_backward<1>, grid, block, lds, st, f, a, K, rows, table);
+  } else if (a.D == 3 && a.model == VGPA_MODEL_L63) {
+    hipLaunchKernelGGL(k_pf_backward<3>, grid, block, lds, st, f, a, K, rows, table);
+  } else {
+    return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
 hipError_t launch_pf_normalise(int batch, int n_paths, const double* lw, double* w, hipStream_t st) {
   if (batch < 1 || n_paths < 1 || !lw || !w) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_pf_normalise, dim3(batch), dim3(256), 0, st, n_paths, lw, w);
@@ -1492,7 +1712,11 @@ hipError_t launch_sample_walk(Walk w, const SampleArgs& a, hipStream_t st) {
       if (a.stride < 1 || a.kind != VGPA_PATHS_POSTERIOR || !a.R_diag || !a.out || !a.pf_slots || a.pf_slot_rows < 1 || a.logw) return hipErrorInvalidValue;
       if (!sample_lineages_fit(a.D, a.batch, a.n_paths)) return hipErrorInvalidValue;
       return launch_walk<Walk::Lineage>(a, st);
-    case Walk::Forecast: {
+    case Walk::Backward:      // (the lineage walk's fields and the histories)
+      if (a.stride < 1 || a.kind != VGPA_PATHS_POSTERIOR || !a.R_diag || !a.out || !a.pf_slots || a.pf_slot_rows < 1 || a.logw) return hipErrorInvalidValue;
+      if (!a.pf_clouds || !a.pf_hanc || a.pf_M < 1 || a.pf_n < 1 || !sample_lineages_fit(a.D, a.batch, a.n_paths)) return hipErrorInvalidValue;
+      return launch_walk<Walk::Backward>(a, st);
+    case Walk::Forecast: {      // (pf_part and pf_wtab are also the storage of Walk::Backward's pf_hanc and pf_clouds: only that walk's caller sets those)
       const bool cloud = a.pf_part && a.pf_wtab && !a.out && !a.pf_slots && a.n_paths == a.pf_n;
       const bool members = a.out && a.pf_slots && a.pf_slot_rows == 1 && !a.pf_part && !a.pf_wtab;
       if (a.stride < 1 || a.kind != VGPA_PATHS_MODEL || !a.R_diag || !known_model || (a.D > kMaxLaneD && a.model != VGPA_MODEL_L96)) return hipErrorInvalidValue;

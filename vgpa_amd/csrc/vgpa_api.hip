@@ -170,9 +170,10 @@ struct vgpa_ctx {
   // vgpa_particle_moments: the descendant weights, the lineage ESS, the workgroups' partial sums, the moments; vgpa_particle_paths: the
   // slot table (int32; the trajectories themselves go through d_sp_out); vgpa_particle_forecast: of these the particles, log-weights, prefix
   // sums, normalised weights (PF_WTAB), partial sums, moments and slot table; vgpa_particle_covariance: the buffers of the moments (the
-  // partial sums and their sum packed, sample_cov_len(D) per kept index) and PF_COV: the mean and behind it the whole matrices
+  // partial sums and their sum packed, sample_cov_len(D) per kept index) and PF_COV: the mean and behind it the whole matrices;
+  // vgpa_particle_backward_paths: the buffers of vgpa_particle_paths, the clouds and PF_HLW: the log-weights the resamplings replaced
   enum { PF_XA, PF_XB, PF_LW, PF_CUM, PF_ANC, PF_ESS, PF_FLAG, PF_HANC, PF_CLOUDS, PF_MU, PF_LT, PF_STA, PF_STB, PF_MEAN, PF_WTAB, PF_LESS, PF_PART,
-         PF_MOM, PF_SLOTS, PF_COV, PF_COUNT };
+         PF_MOM, PF_SLOTS, PF_COV, PF_HLW, PF_COUNT };
   double* d_pf[PF_COUNT] = {};
   size_t pf_n[PF_COUNT] = {};
   // profiling
@@ -1580,6 +1581,7 @@ struct ParticleRequest {
   int32_t stride = 1;                                                // of the grid indices the two smoothers keep
   double* moments; double* lineage_ess;                              // vgpa_particle_moments
   int32_t n_draw; const int32_t* final_slots; double* paths; int32_t* slots_out;      // vgpa_particle_paths; slots_out: where the table goes
+  bool backward;                                                     // vgpa_particle_backward_paths: the table is drawn, not traced
   // vgpa_particle_forecast: horizon steps behind the filter, or from `cloud` at index0; stride, n_draw, final_slots, slots_out as above;
   // moments is then fc_moments
   bool forecast; int32_t horizon; const double* cloud; const double* cloud_logw; int32_t index0;
@@ -1633,7 +1635,8 @@ struct ParticleRun {
     if ((q.moments || q.covariance) && ((rc = buf(vgpa_ctx::PF_WTAB, (size_t)B * rows * n)) || (rc = buf(vgpa_ctx::PF_LESS, (size_t)B * rows)) ||
                       (rc = buf(vgpa_ctx::PF_PART, (size_t)B * n_blocks * mom_len)) || (rc = buf(vgpa_ctx::PF_MOM, (size_t)B * mom_len)))) return rc;
     if (q.covariance && (rc = buf(vgpa_ctx::PF_COV, (size_t)B * n_keep * D * ((size_t)D + 1)))) return rc;
-    if (q.clouds && (rc = buf(vgpa_ctx::PF_CLOUDS, BM * n * D))) return rc;
+    if ((q.clouds || q.backward) && (rc = buf(vgpa_ctx::PF_CLOUDS, BM * n * D))) return rc;      // (backward simulation reads them on the device)
+    if (q.backward && (rc = buf(vgpa_ctx::PF_HLW, BM * n))) return rc;
     if (q.with_stats && ((rc = buf(vgpa_ctx::PF_STA, 3 * BnD)) || (rc = buf(vgpa_ctx::PF_STB, 3 * BnD)) || (rc = buf(vgpa_ctx::PF_MEAN, (size_t)B * 3 * D)))) return rc;
     f = PfArgs{};
     f.D = D; f.batch = B; f.n_paths = q.n_paths; f.M = M1; f.seed = q.seed; f.ess_fraction = q.ess_fraction;
@@ -1653,7 +1656,8 @@ struct ParticleRun {
     f.anc = reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_ANC]);
     f.h_ess = c->d_pf[vgpa_ctx::PF_ESS]; f.h_flag = reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_FLAG]);
     f.h_anc = history ? reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_HANC]) : nullptr;
-    f.h_clouds = q.clouds ? c->d_pf[vgpa_ctx::PF_CLOUDS] : nullptr;
+    f.h_clouds = q.clouds || q.backward ? c->d_pf[vgpa_ctx::PF_CLOUDS] : nullptr;
+    f.h_lw = q.backward ? c->d_pf[vgpa_ctx::PF_HLW] : nullptr;
     // the cuts: the observation indices the kernels will see (each problem's own row and count in force), and the last grid index
     is_obs.assign((size_t)c->Np, 0);
     count.assign((size_t)B, M);
@@ -1725,9 +1729,28 @@ struct ParticleRun {
   // trajectories (final_slots, or drawn from the final weights), their slots in every stretch traced back through the ancestors, one
   // launch of the lineage walk over the n_draw trajectories alone, the downloads.
   int trajectories() {
-    const int B = c->B, n_draw = q.n_draw;
     int rc;
     int32_t* table = reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_SLOTS]);
+    if ((rc = final_slots(table))) return rc;
+    LAUNCH_TRY(c, "genealogy launch", launch_pf_trace(f, q.n_draw, slot_rows, table, c->stream));
+    return walk_table(Walk::Lineage, "lineage walk launch", table);
+  }
+
+  // The smoothing trajectories by backward simulation, behind the filter, whose ancestors, clouds and replaced log-weights
+  // stay on the device: the final slots as trajectories() has them, the table drawn backwards through the clouds in one launch, one launch
+  // of the backward walk over the n_draw trajectories alone, the downloads.
+  int backward_trajectories() {
+    int rc;
+    int32_t* table = reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_SLOTS]);
+    if ((rc = final_slots(table))) return rc;
+    LAUNCH_TRY(c, "backward simulation launch", launch_pf_backward(f, a, q.n_draw, slot_rows, table, c->stream));
+    return walk_table(Walk::Backward, "backward walk launch", table);
+  }
+
+  // row c of the slot table: the caller's final slots, or drawn from the final weights; every other row -1
+  int final_slots(int32_t* table) {
+    const int B = c->B, n_draw = q.n_draw;
+    int rc;
     if (q.final_slots) {             // rows beyond a problem's own count: -1; row c: the caller's slots
       std::vector<int32_t> h_table(n_table, -1);      // (the table as it is uploaded, alive until the stream has been synchronised)
       for (int p = 0; p < B; p++)
@@ -1738,11 +1761,18 @@ struct ParticleRun {
       HIP_TRY(c, hipMemsetAsync(table, 0xff, n_table * sizeof(int32_t), c->stream));
       LAUNCH_TRY(c, "final slots launch", launch_pf_pick(f, c->Np, n_draw, slot_rows, table, c->stream));
     }
-    LAUNCH_TRY(c, "genealogy launch", launch_pf_trace(f, n_draw, slot_rows, table, c->stream));
+    return VGPA_OK;
+  }
+
+  // the walk of the table's n_draw trajectories alone and the downloads
+  int walk_table(Walk walk, const char* what, int32_t* table) {
+    int rc;
     SampleArgs w = a;                // the unweighted walk of n_draw lanes per problem from the same start, factors and counters
-    w.n_paths = n_draw; w.stride = q.stride; w.n_keep = n_keep; w.out = c->d_sp_out;
+    w.n_paths = q.n_draw; w.stride = q.stride; w.n_keep = n_keep; w.out = c->d_sp_out;
     w.pf_x = nullptr; w.pf_lw = nullptr; w.pf_stats = nullptr; w.pf_slots = table; w.pf_slot_rows = slot_rows;
-    LAUNCH_TRY(c, "lineage walk launch", launch_sample_walk(Walk::Lineage, w, c->stream));
+    if (walk == Walk::Backward) { w.pf_clouds = f.h_clouds; w.pf_hanc = f.h_anc; w.pf_M = f.M; w.pf_n = q.n_paths; }
+    hipError_t e = launch_sample_walk(walk, w, c->stream);
+    if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "%s failed: %s", what, hipGetErrorString(e));
     if ((rc = download(c, q.paths, c->d_sp_out, n_traj))) return rc;
     if (q.slots_out) HIP_TRY(c, hipMemcpyAsync(q.slots_out, table, n_table * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     return VGPA_OK;
@@ -1858,6 +1888,8 @@ static int particle_run(vgpa_ctx* c, const ParticleRequest& q) {
   if (q.paths && D <= kMaxSmallD) {        // the launch limits of the lineage walk and the size of its result, before any work
     if (!sample_lineages_fit(D, B, n_draw))
       return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing trajectories are built for at most %d per problem at D = %d (n_draw = %d)", 65535 * 64, D, n_draw);
+    if (q.backward && !pf_backward_fits(n_draw))      // ... and of the backward simulation: grid.y of its one launch
+      return fail(c, VGPA_ERR_UNSUPPORTED, "backward simulation is built for at most %d trajectories per problem (n_draw = %d)", 65535 * kBackwardBlock, n_draw);
     if ((double)B * (double)n_draw * (double)((Np - 1) / stride + 1) * (double)D > 34359738368.0)
       return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing trajectories are built for at most 2^35 entries (batch %d, %d trajectories, %d kept grid indices, D = %d): use a larger stride",
                   B, n_draw, (Np - 1) / stride + 1, D);
@@ -1873,7 +1905,8 @@ static int particle_run(vgpa_ctx* c, const ParticleRequest& q) {
   }
   ParticleRun r{c, q};
   int rc;
-  if ((rc = r.setup()) || (rc = r.filter()) || ((q.moments || q.covariance) && (rc = r.moments())) || (q.paths && (rc = r.trajectories()))) return rc;
+  if ((rc = r.setup()) || (rc = r.filter()) || ((q.moments || q.covariance) && (rc = r.moments())) ||
+      (q.paths && (rc = q.backward ? r.backward_trajectories() : r.trajectories()))) return rc;
   const size_t n = (size_t)n_paths, BnD = (size_t)B * n * D;
   if (q.forecast) {      // (the filter's final cloud leaves before the forecast carries it on in place)
     if ((rc = download(c, q.state, r.cur, BnD))) return rc;
@@ -1944,6 +1977,18 @@ int vgpa_particle_paths(vgpa_ctx* c, const double* x, const double* x0, int32_t 
   if (n_draw < 1) return fail(c, VGPA_ERR_ARG, "n_draw must be at least 1 (n_draw = %d)", n_draw);
   ParticleRequest q{x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled};
   q.stride = stride; q.n_draw = n_draw; q.final_slots = final_slots; q.paths = paths; q.slots_out = slots;
+  return particle_run(c, q);
+}
+
+// Whole smoothing trajectories on the grid by backward simulation through the filter's clouds (see vgpa_hip.h)
+int vgpa_particle_backward_paths(vgpa_ctx* c, const double* x, const double* x0, int32_t n_paths, int32_t n_draw, const int32_t* final_slots,
+                                 int32_t stride, uint64_t seed, double ess_fraction, const double* prior_mu, const double* prior_tau, double* logw,
+                                 double* state, double* paths, int32_t* slots, double* ess, int32_t* resampled) {
+  if (!c) return VGPA_ERR_ARG;
+  if (!paths) return fail(c, VGPA_ERR_ARG, "null argument");
+  if (n_draw < 1) return fail(c, VGPA_ERR_ARG, "n_draw must be at least 1 (n_draw = %d)", n_draw);
+  ParticleRequest q{x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled};
+  q.stride = stride; q.n_draw = n_draw; q.final_slots = final_slots; q.paths = paths; q.slots_out = slots; q.backward = true;
   return particle_run(c, q);
 }
 

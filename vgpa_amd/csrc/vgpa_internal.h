@@ -222,9 +222,9 @@ struct ReduceArgs {
   const double* div_v;      // [B] per-problem div (1-D models: sigma_p), or nullptr
 };
 
-// Euler-Maruyama sample paths (sample.hip): x_k = x_{k-1} + dt drift_{k-1}(x_{k-1}) + R xi_k on the context's grid.  The eight things a launch
+// Euler-Maruyama sample paths (sample.hip): x_k = x_{k-1} + dt drift_{k-1}(x_{k-1}) + R xi_k on the context's grid.  The nine things a launch
 // can do with them (the table at the top of sample.hip); the host names one at every launch_sample_walk, and SampleArgs says what each reads
-enum class Walk { Plain, Weighted, Segment, SegmentStats, Replay, Lineage, Forecast, ReplayCov };
+enum class Walk { Plain, Weighted, Segment, SegmentStats, Replay, Lineage, Forecast, ReplayCov, Backward };
 struct SampleArgs {
   int kind, model, D, Np, batch, n_paths, stride, n_keep;
   double dt;
@@ -269,9 +269,9 @@ struct SampleArgs {
   // the replay of vgpa_particle_moments: Walk::Replay is the walk of the segment without its weight sums (pf_lw is
   // not touched); at every kept grid index k = 0 mod stride of the segment (k = 0: the first segment) workgroup (p, blk) stores
   // sum_i W_i x_i(k) and sum_i W_i x_i(k)^2 over its own slots, W = the row of pf_wtab of the problem's stretch
-  const double* pf_wtab;    // [B][pf_rows][n_paths] descendant weights; nullptr for every other walk
-  double* pf_part;          // [B][sample_segment_blocks()][n_keep][2][D]
-  int pf_rows;
+  union { const double* pf_wtab; const double* pf_clouds; };    // [B][pf_rows][n_paths] descendant weights; nullptr for every other walk (pf_clouds: Walk::Backward, below)
+  union { double* pf_part; const int32_t* pf_hanc; };           // [B][sample_segment_blocks()][n_keep][2][D]
+  union { int pf_rows; int pf_M; };
   // Walk::Lineage (vgpa_particle_paths): the unweighted posterior walk of n_paths = K lanes
   // per problem, stored as vgpa_sample_paths stores it, in which lane m draws with the counter word pf_slots[p][j][m] while it is in
   // stretch j of its problem's own observation row (obs_t / n_obs as above): row 0 for the start, the next row behind every observation
@@ -287,7 +287,14 @@ struct SampleArgs {
   // Walk::ReplayCov (vgpa_particle_covariance): Walk::Replay with the whole second-moment matrix.  Every field as for the
   // replay, but pf_part is [B][sample_segment_blocks()][n_keep][V], V = sample_cov_len(D) = D + D (D + 1) / 2: sum_i W_i x_i(k), then the lower
   // triangle of sum_i W_i x_i(k) x_i(k)^T packed by rows, entry (a, b <= a) at D + a (a + 1) / 2 + b.  No field of its own.
+  // Walk::Backward (vgpa_particle_backward_paths): Walk::Lineage, every field as there, in which lane m, having completed
+  // and stored its problem's observation index t_j, goes on from pf_clouds[p][j][pf_hanc[p][j][pf_slots[p][j + 1][m]]]: the filter's
+  // histories (rows of pf_M observations per problem; pf_n particles per cloud)
+  // They share the storage of three fields the lineage walks do not read (the unions above), so that the arguments keep their size and the
+  // other walks their code: pf_clouds [B][pf_M][pf_n][D] with pf_wtab, pf_hanc [B][pf_M][pf_n] with pf_part, pf_M with pf_rows.
 };
+// (Walk::Backward's three fields are unions with fields of the replay: the arguments must keep the size every other walk was compiled for)
+static_assert(sizeof(SampleArgs) == 368, "SampleArgs has grown: see the unions of Walk::Backward");
 // hipErrorInvalidValue where a field the walk reads is missing or out of range, where a field that belongs to another walk is set, and for
 // D = 2 in every walk but Plain (no stochastic model has D = 2)
 hipError_t launch_sample_walk(Walk w, const SampleArgs& a, hipStream_t st);
@@ -320,6 +327,7 @@ struct PfArgs {
   double* h_ess; int32_t* h_flag;      // [B][M] each
   int32_t* h_anc;           // [B][M][n_paths], or nullptr
   double* h_clouds;         // [B][M][n_paths][D], or nullptr
+  double* h_lw;             // [B][M][n_paths] the log-weights a resampling step finds (the observation's term included), or nullptr
   // the rows of vgpa_particle_statistics, gathered by ancestor together with x; both or neither
   const double* st_in; double* st_out;   // [B][n_paths][3][D] each
 };
@@ -340,6 +348,12 @@ hipError_t launch_pf_gather(const PfArgs& a, hipStream_t st);
 hipError_t launch_pf_pick(const PfArgs& a, int Np, int K, int rows, int32_t* table, hipStream_t st);
 hipError_t launch_pf_trace(const PfArgs& a, int K, int rows, int32_t* table, hipStream_t st);
 bool sample_lineages_fit(int D, int batch, int K);
+// vgpa_particle_backward_paths (sample.hip: k_pf_backward) in place of the trace: rows c-1 .. 0 of table by backward simulation.  f: the
+// histories h_flag, h_anc, h_clouds, h_lw with M, n_paths, seed and the observation rows; a: of the filter's arguments the model, theta,
+// A, b, the diagonal R and dt.  One launch: workgroup (p, blk) owns kBackwardBlock trajectories of problem p through all of its cuts
+constexpr int kBackwardBlock = 8;
+hipError_t launch_pf_backward(const PfArgs& f, const SampleArgs& a, int K, int rows, int32_t* table, hipStream_t st);
+inline bool pf_backward_fits(int K) { return (K + kBackwardBlock - 1) / kBackwardBlock <= 65535; }      // (grid.y)
 // vgpa_particle_forecast (sample.hip: k_pf_normalise): w [B][n_paths] = exp(lw - max lw) / the sum of these, per problem
 hipError_t launch_pf_normalise(int batch, int n_paths, const double* lw, double* w, hipStream_t st);
 // out [B][len] = sum over blk, in block order, of part [B][n_blocks][len]

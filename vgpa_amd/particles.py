@@ -359,9 +359,17 @@ class SmoothingPaths(object):
     dropped.
 
     The trajectories are lineages of one genealogy: where the clouds collapsed, all K of them share their early stretches, and a sample
-    mean over them has there the variance of a single draw.  distinct() says how many different paths each stretch holds."""
+    mean over them has there the variance of a single draw.  distinct() says how many different paths each stretch holds.
 
-    def __init__(self, log_w, paths, slots, stride, n_pts, obs_t, ess=(), resampled=(), drawn=True, single_dim=False) -> None:
+    method: how the table `slots` was made.  "genealogy" (vgpa_particle_paths): row j is the ancestor of row j + 1.  "backward"
+    (vgpa_particle_backward_paths): at every observation where the cloud was resampled, row j is drawn anew among all
+    n slots, in proportion to filter weight times model transition density to the trajectory's next state, so the early stretches do
+    not collapse onto the surviving lineages and hold more distinct paths.  What backward simulation does not change: the filter, the
+    final slots, the weights of the trajectories, and the stretches themselves -- between two observations a trajectory is still its
+    slot's own path, and at a resampled observation it jumps from the cloud's particle to the one its successor was copied from, so
+    distinct() is bounded by the distinct slots chosen, never by more than n."""
+
+    def __init__(self, log_w, paths, slots, stride, n_pts, obs_t, ess=(), resampled=(), drawn=True, single_dim=False, method="genealogy") -> None:
         self.log_w = np.asarray(log_w, dtype=float).ravel()
         if self.log_w.size < 1:
             raise ValueError(" SmoothingPaths: at least one particle.")
@@ -384,6 +392,9 @@ class SmoothingPaths(object):
         if self.ess.size != self.resampled.size:
             raise ValueError(" SmoothingPaths: ess and resampled do not belong together.")
         self.drawn = bool(drawn)
+        if method not in ("genealogy", "backward"):
+            raise ValueError(" SmoothingPaths: method is 'genealogy' or 'backward'.")
+        self.method = method
 
     def __len__(self):
         return self.paths.shape[0]

@@ -257,12 +257,12 @@ class VarGP(object):
         out = [self._covariance_record(res, k, stride) for k in range(res["log_w"].shape[0])]
         return out[0] if self.batch == 1 else out
 
-    def _paths_record(self, res, k, stride, drawn, obs_t=None):
-        """One problem's SmoothingPaths from row k of Context.particle_paths' dict, cut to its own observations obs_t"""
+    def _paths_record(self, res, k, stride, drawn, obs_t=None, method="genealogy"):
+        """One problem's SmoothingPaths from row k of Context.particle_paths' (or particle_backward_paths') dict, cut to its own observations obs_t"""
         from .particles import SmoothingPaths
         t = np.asarray(self._inputs()["obs_t"] if obs_t is None else obs_t).ravel()
         return SmoothingPaths(res["log_w"][k], res["paths"][k], res["slots"][k, :t.size + 1], stride, self.dim_n, t, res["ess"][k, :t.size],
-                              res["resampled"][k, :t.size], drawn, self.model.single_dim)
+                              res["resampled"][k, :t.size], drawn, self.model.single_dim, method=method)
 
     def particle_paths(self, n_paths, seed, n_draw, stride=1, ess_fraction=0.5, x=None, x0=None, slots=None):
         """n_draw whole smoothing trajectories on the time grid from particle_filter with the same arguments: a particles.SmoothingPaths
@@ -274,6 +274,19 @@ class VarGP(object):
         res = self._context().particle_paths(n_paths, seed, n_draw, stride=stride, ess_fraction=ess_fraction, x=xx, x0=x0, prior=self._prior(),
                                              slots=slots)
         out = [self._paths_record(res, k, stride, slots is None) for k in range(res["log_w"].shape[0])]
+        return out[0] if self.batch == 1 else out
+
+    def backward_paths(self, n_paths, seed, n_draw, stride=1, ess_fraction=0.5, x=None, x0=None, slots=None):
+        """n_draw whole smoothing trajectories by backward simulation (forward filtering, backward simulation) through the clouds of
+        particle_filter with the same arguments: a particles.SmoothingPaths with method "backward" (with batch > 1 a list), laid out as
+        particle_paths'.  At every observation where the cloud was resampled a trajectory draws the slot it came from among all n_paths
+        particles, in proportion to filter weight times model transition density, instead of following its ancestor: the early stretches
+        keep more distinct paths than the genealogy leaves.  Between two observations a trajectory is still its slot's own path, so
+        distinct() is bounded by the distinct slots chosen."""
+        xx = None if x is None else np.asarray(x, dtype=float)
+        res = self._context().particle_backward_paths(n_paths, seed, n_draw, stride=stride, ess_fraction=ess_fraction, x=xx, x0=x0,
+                                                      prior=self._prior(), slots=slots)
+        out = [self._paths_record(res, k, stride, slots is None, method="backward") for k in range(res["log_w"].shape[0])]
         return out[0] if self.batch == 1 else out
 
     def _forecast_record(self, res, k, horizon, stride, drawn):
