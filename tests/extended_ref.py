@@ -9,7 +9,9 @@ kernel's.  An evaluation with 11 more bits tells the two apart: every test state
 What is restated (same formulas, same quirks, names as in the oracle): _l96_point_lean -> l96_point (Cholesky of (D + kappa) S_t,
 sigma points, the drift with its FLATTENED np.roll -- Q1 --, e_t, dEsde_dm, dEsde_dS), l96_mean_drift, l96_mean_jacobian, my_trapz,
 energy_l96 (lean), solve_fwd; solve_bwd (zero-padded mid-points, Q3, jumps after the step: Q9), obs_terms (Q4), gradient, energy_ou,
-energy_dw (Q7), energy_l63 and sweep (lean).  The scalar models run the n-D recursions on 1 x 1 matrices.  np.linalg has no extended precision: the Cholesky factor and its inverse are written out here, one
+energy_dw (Q7), energy_l63 (with l63_drift_theta: dEsde_dth) and sweep (lean); theta_gradient (dF/dtheta of a problem from the restated
+sweep state) and, for the scalar results that sum terms of either sign, their summands (obs_terms(parts=True), the dth_t of the
+energies, trapezoid_summands) and kappa = sum |summand| / |sum summand|.  The scalar models run the n-D recursions on 1 x 1 matrices.  np.linalg has no extended precision: the Cholesky factor and its inverse are written out here, one
 row-vectorised step per column / row.  Like the oracle, a non-positive pivot raises LinAlgError.
 
 Every input is taken as the fp64 number it is (the conversion to longdouble is exact); nothing is rounded back before the caller
@@ -290,19 +292,24 @@ def solve_bwd(method, dt, lin_a, de_dm, de_ds, jump_m, jump_s):
 LOG2PI = LD(np.float64(np.log(2.0 * np.pi)))        # the oracle's fp64 constant: an input, like kappa
 
 
-def obs_terms(p, mt, st):
+def obs_terms(p, mt, st, parts=False, q4=True):
     """(E_obs, jump_m, jump_s) of oracle.eobs / eobs_gradients: dense R and a non-identity H through cholesky / tri_inverse; the
-    covariance diagonal is indexed by the observation COUNTER, as the oracle does (Q4)."""
+    covariance diagonal is indexed by the observation COUNTER, as the oracle does (Q4; q4=False: by the observation's grid index, which
+    neither the oracle nor a kernel does -- for the tests that show the difference).  parts=True: a fourth member, the dict
+    (terms (M,), const) with E_obs = sum(terms) + const -- the per-observation summands and the normalisation constant, for kappa."""
     mt, st = _ld(mt), _ld(st)
     obs_t = np.asarray(p.obs_t, dtype=np.int64)
     obs_y, r = _ld(p.obs_y), _ld(p.obs_noise)
     if p.single_dim:
         ex2 = mt[obs_t] ** 2 + st[obs_t]
-        e_obs = np.sum(obs_y ** 2 - 2 * obs_y * mt[obs_t] + ex2) / 2 / r + obs_t.size * (LOG2PI + np.log(r)) / 2
+        const = obs_t.size * (LOG2PI + np.log(r)) / 2
+        e_obs = np.sum(obs_y ** 2 - 2 * obs_y * mt[obs_t] + ex2) / 2 / r + const
         h = LD(1) if p.obs_h is None else _ld(p.obs_h)
         jm, js = np.zeros(mt.shape[0], dtype=LD), np.zeros(mt.shape[0], dtype=LD)
         jm[obs_t] = -(obs_y - h * mt[obs_t]) / r
         js[obs_t] = 1 / (2 * r)
+        if parts:
+            return e_obs, jm, js, dict(terms=(obs_y ** 2 - 2 * obs_y * mt[obs_t] + ex2) / 2 / r, const=const)
         return e_obs, jm, js
     n, d = mt.shape
     dim_m, dim_o = obs_y.shape
@@ -312,16 +319,37 @@ def obs_terms(p, mt, st):
     inv_c = tri_inverse(low)
     inv_r = inv_c.T.dot(inv_c)
     z = w.dot(inv_c.T)
-    acc = LD(0)
+    acc, terms = LD(0), np.zeros(dim_m, dtype=LD)
     for k in range(dim_m):
-        acc = acc + z[k].dot(z[k]) + np.diag(inv_r).dot(np.diag(st[k]))                    # Q4: st[k], not st[obs_t[k]]
+        fit, var = z[k].dot(z[k]), np.diag(inv_r).dot(np.diag(st[k if q4 else obs_t[k]]))   # Q4: st[k], not st[obs_t[k]]
+        acc = acc + fit + var                                                              # (the oracle's order of additions)
+        terms[k] = fit + var
     log_det_r = 2 * np.sum(np.log(np.diag(low)))
     e_obs = (acc + dim_m * (dim_o * LOG2PI + log_det_r)) / 2
     jm, js = np.zeros((n, d), dtype=LD), np.zeros((n, d, d), dtype=LD)
     for k, tn in enumerate(obs_t):
         jm[tn] = -h.T.dot(inv_r).dot(w[k])
         js[tn] = h.T.dot(inv_r).dot(h) / 2
+    if parts:
+        return e_obs, jm, js, dict(terms=terms / 2, const=dim_m * (dim_o * LOG2PI + log_det_r) / 2)
     return e_obs, jm, js
+
+
+def kappa(summands, axis=None):
+    """sum |summand| / |sum summand| of a sum of terms of either sign: by how much its relative rounding error may exceed the unit
+    roundoff whatever the order of the additions (1 for terms of one sign; inf for a sum that is exactly zero)."""
+    summands = _ld(summands)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        k = np.sum(np.abs(summands), axis=axis) / np.abs(np.sum(summands, axis=axis))
+    return float(k) if np.ndim(k) == 0 else np.asarray(k, dtype=float)
+
+
+def trapezoid_summands(fx, dx):
+    """The values of fx (time along axis 0) times their trapezoid weights: dx inside, dx / 2 at both ends -- sum(axis=0) is my_trapz, whose
+    pieces between observations add up to the one global rule."""
+    w = np.full(np.shape(fx)[0], LD(dx), dtype=LD)
+    w[0], w[-1] = w[0] / 2, w[-1] / 2
+    return _ld(fx) * w.reshape((-1,) + (1,) * (np.ndim(fx) - 1))
 
 
 # --------------------------------------------------------------------------- #
@@ -351,7 +379,8 @@ def energy_ou(theta, sigma, dt, a, b, m, s, obs_t=None):
     esde = my_trapz(var_q, dt, obs_t) / 2 / sigma
     return dict(Esde=esde, Ef=-theta * m, Edf=-theta * np.ones(m.shape, dtype=LD),
                 dEsde_dm=(m * (theta - a) ** 2 + theta * b - a * b) / sigma, dEsde_dS=q1 / 2 / sigma,
-                dEsde_dth=my_trapz(ex2 * (theta - a) + m * b, dt, obs_t) / sigma, dEsde_dsig=-esde / sigma)
+                dEsde_dth=my_trapz(ex2 * (theta - a) + m * b, dt, obs_t) / sigma, dEsde_dsig=-esde / sigma,
+                dth_t=(ex2 * (theta - a) + m * b) / sigma)
 
 
 def energy_dw(theta, sigma, dt, a, b, m, s, obs_t=None):
@@ -365,7 +394,8 @@ def energy_dw(theta, sigma, dt, a, b, m, s, obs_t=None):
     de_dm = (16 * gm_dm(m, s, 6) - 8 * c * gm_dm(m, s, 4) + 8 * b * gm_dm(m, s, 3) + c2 * gm_dm(m, s, 2) - 2 * b * c) / 2 / sigma
     de_ds = (16 * gm_ds(m, s, 6) - 8 * c * gm_ds(m, s, 4) + 8 * b * gm_ds(m, s, 3) + c2 * gm_ds(m, s, 2)) / 2 / sigma
     return dict(Esde=esde, Ef=4 * (theta * m - ex3), Edf=4 * (theta - 3 * ex2), dEsde_dm=de_dm, dEsde_dS=de_ds,
-                dEsde_dth=4 * my_trapz(c * ex2 - 4 * ex4 - b * m, dt, obs_t) / sigma, dEsde_dsig=-esde / sigma)
+                dEsde_dth=4 * my_trapz(c * ex2 - 4 * ex4 - b * m, dt, obs_t) / sigma, dEsde_dsig=-esde / sigma,
+                dth_t=4 * (c * ex2 - 4 * ex4 - b * m) / sigma)
 
 
 def l63_point(theta, at, bt, mt, st, isg):
@@ -378,8 +408,18 @@ def l63_point(theta, at, bt, mt, st, isg):
     return efg, de_dm, de_ds
 
 
+def l63_drift_theta(theta, at, bt, mt, st):
+    """oracle.l63_drift_theta on longdouble operands, by the route of l63_point: its text has only Python operators and integer constants,
+    so it evaluates in the precision of its arguments (asserted)."""
+    from oracle import vgpa_oracle as vo
+    v = vo.l63_drift_theta(_ld(theta), _ld(at), _ld(bt), _ld(mt), _ld(st))
+    assert v.dtype == LD
+    return v
+
+
 def energy_l63(theta, sigma, dt, lin_a, off_b, m, s, obs_t=None):
-    """oracle.energy_l63 on Sigma itself (inverted here): a dict under the names of energy_l96."""
+    """oracle.energy_l63 on Sigma itself (inverted here): a dict under the names of energy_l96; dth_t is the integrand of dEsde_dth
+    (Sigma^-1's diagonal folded in), as in energy_ou / energy_dw."""
     theta, lin_a, off_b, m, s = _ld(theta), _ld(lin_a), _ld(off_b), _ld(m), _ld(s)
     n = m.shape[0]
     inv_sigma = spd_inverse(sigma)
@@ -387,14 +427,17 @@ def energy_l63(theta, sigma, dt, lin_a, off_b, m, s, obs_t=None):
     e_t = np.zeros(n, dtype=LD)
     ef, edf = np.zeros((n, 3), dtype=LD), np.zeros((n, 3, 3), dtype=LD)
     de_dm, de_ds, dsg = np.zeros((n, 3), dtype=LD), np.zeros((n, 3, 3), dtype=LD), np.zeros((n, 3), dtype=LD)
+    dth = np.zeros((n, 3), dtype=LD)
     v_s, v_r, v_b = theta
     for t in range(n):
         mt, st = m[t], s[t]
         dsg[t], de_dm[t], de_ds[t] = l63_point(theta, lin_a[t], off_b[t], mt, st, isg)
         e_t[t] = isg.dot(dsg[t]) / 2
+        dth[t] = l63_drift_theta(theta, lin_a[t], off_b[t], mt, st)
         ef[t] = (v_s * (mt[1] - mt[0]), v_r * mt[0] - mt[1] - st[2, 0] - mt[0] * mt[2], st[1, 0] + mt[0] * mt[1] - v_b * mt[2])
         edf[t] = ((-v_s, v_s, 0), (v_r - mt[2], -1, -mt[0]), (mt[1], mt[0], -v_b))
     return dict(Esde=my_trapz(e_t, dt, obs_t), e_t=e_t, Ef=ef, Edf=edf, dEsde_dm=de_dm, dEsde_dS=de_ds,
+                dEsde_dth=isg * my_trapz(dth, dt, obs_t), dth_t=isg * dth,
                 dEsde_dsig=-inv_sigma.dot(np.diag(my_trapz(dsg, dt, obs_t))).dot(inv_sigma) / 2)
 
 
@@ -403,6 +446,22 @@ def model_energy(p, lin_a, off_b, m, s):
     obs_t = list(p.obs_t)
     fn = {"OU": energy_ou, "DW": energy_dw, "L63": energy_l63, "L96": energy_l96}[p.model]
     return fn(p.theta, p.sigma, p.dt, lin_a, off_b, m, s, obs_t)
+
+
+def theta_gradient(p, x, state):
+    """dF/dtheta at fixed (A_t, b_t) from the restated sweep state (mt, st): (value (n_theta,), kappa (n_theta,)).  OU / double well /
+    Lorenz-63: the restated dEsde_dth (the reference's member IS dF/dtheta for these models), kappa over its trapezoid-weighted integrand
+    values.  Lorenz-96: theta_gradient_fd -- the derivative of the unscented E_sde, which the reference's member is not --, kappa over
+    the trapezoid-weighted unscented mean residual, whose integral the same number is."""
+    lin_a, off_b = p.split(np.asarray(x))
+    if p.model == "L96":
+        lin_a, off_b, m, s = _ld(lin_a), _ld(off_b), _ld(state["mt"]), _ld(state["st"])
+        isg = np.diag(spd_inverse(p.sigma)).copy()
+        tg = np.array([isg.dot(l96_point(p.theta, isg, lin_a[t], off_b[t], m[t], s[t])[4]) for t in range(p.n_pts)], dtype=LD)
+        val = theta_gradient_fd(p.theta, p.sigma, p.dt, lin_a, off_b, m, s)
+        return np.atleast_1d(val), np.atleast_1d(kappa(trapezoid_summands(tg, p.dt), axis=0))
+    en = model_energy(p, lin_a, off_b, state["mt"], state["st"])
+    return np.atleast_1d(en["dEsde_dth"]), np.atleast_1d(kappa(trapezoid_summands(en["dth_t"], p.dt), axis=0))
 
 
 # --------------------------------------------------------------------------- #

@@ -47,7 +47,7 @@ from test_stepper_rounding_cpu import (COVER_CASES, DT, FUSED_QUANTITIES, LANE_P
 
 pytestmark = pytest.mark.gpu
 WORST = {}                 # (family, quantity) -> the worst ratio err_k / max(err_o, 2^-53) of this process's run
-MATRIX_KEYS = ("st", "psit", "dEsde_ds")
+MATRIX_KEYS = ("st", "psit", "dEsde_ds", "Edf")
 
 
 def _n_cu():

@@ -415,8 +415,7 @@ def test_restatement_equals_the_oracle_with_dense_noise_and_observation_operator
     en = xr.model_energy(p, *p.split(x), state["mt"], state["st"])
     _, _, (_, _, dth, dsg) = vo.model_energy(p, *p.split(x), st_o["mt"], st_o["st"], faithful=False)
     assert ld_rel_err(dsg, en["dEsde_dsig"]) <= RESTATEMENT_TOL
-    if "dEsde_dth" in en:
-        assert ld_rel_err(dth, en["dEsde_dth"]) <= RESTATEMENT_TOL
+    assert ld_rel_err(dth, en["dEsde_dth"]) <= RESTATEMENT_TOL
 
 
 def test_scalar_recursions_take_the_oracles_one_dimensional_arrays():
