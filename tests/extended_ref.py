@@ -1,7 +1,9 @@
 """
 tests/extended_ref.py -- TEST INFRASTRUCTURE: the sweep of oracle/vgpa_oracle.py (forward and backward steppers, observation terms,
-the four models' energies, the gradient assembly) in np.longdouble (x87 80-bit, 64-bit mantissa), and the seeded covariance generators
-of the conditioning / not-positive-definite tests.
+the four models' energies, the gradient assembly) in np.longdouble (x87 80-bit, 64-bit mantissa), the particle half one step or one
+reduction at a time (Box-Muller normals from the Philox words, the model drifts and phi, one Euler-Maruyama step, the path / observation
+terms and the statistics rows of stored paths, self-normalised weighted sums, the back-propagated stretch weights: each in longdouble or,
+as the fp64 yardstick, in float64), and the seeded covariance generators of the conditioning / not-positive-definite tests.
 
 Why: the fp64 oracle factors S_t with LAPACK, so against an ill-conditioned S_t its own rounding (cond * 1e-16) is as large as a
 kernel's.  An evaluation with 11 more bits tells the two apart: every test states the kernel's error AND the oracle's against it.
@@ -500,6 +502,218 @@ def sweep(p, x, e0):
                  dEsde_dm=en["dEsde_dm"], dEsde_ds=en["dEsde_dS"], dEobs_dm=jm, dEobs_ds=js)
     gla, glb = gradient(p, x, state)
     return LD(e0) + en["Esde"] + e_obs, gla, glb, state
+
+
+# --------------------------------------------------------------------------- #
+#  The particle half (vgpa_amd/csrc/sample.hip): normals, drifts, one Euler-Maruyama step, the sums over stored paths, weighted sums
+# --------------------------------------------------------------------------- #
+# Every function takes the number type T it computes in: np.longdouble (the reference) or np.float64 (the "oracle": the same text,
+# rounded as a careful fp64 evaluation rounds).  Inputs are the fp64 numbers they are; no result is rounded back.
+def levels(n):
+    """ceil(log2 n): the additions every term of a sum of n terms passes when the sum is added as a balanced tree (0 for n <= 1)"""
+    return int(np.ceil(np.log2(n))) if n > 1 else 0
+
+
+def _sum(a, axis):
+    """The sum along `axis` added as a balanced tree (the upper half onto the lower, zero-padded to a power of two): every term passes
+    levels(n) additions, each rounded at no more than the sum of the terms' sizes -- the accumulation term of the floors below.  (np.sum
+    along an axis that is not the last adds one term at a time: no careful evaluation of a sum of hundreds of terms.)"""
+    a = np.moveaxis(a, axis, 0)
+    n = a.shape[0]
+    if n == 0:
+        return np.zeros(a.shape[1:], dtype=a.dtype)
+    full = 1 << levels(n)
+    if full > n:
+        a = np.concatenate((a, np.zeros((full - n,) + a.shape[1:], dtype=a.dtype)))
+    while a.shape[0] > 1:
+        h = a.shape[0] // 2
+        a = a[:h] + a[h:]
+    return a[0]
+
+
+def two_pi(T=LD):
+    return T(2.0 * np.pi) if T is np.float64 else 8 * np.arctan(LD(1))
+
+
+def uniforms(seed, k, word, problem, d):
+    """(u1, u2), each (..., ceil(d / 2)): the fp64 uniforms of the Philox counter (k, word, problem, pair) under key `seed`.  Integer
+    arithmetic and exact conversions only (test_sample_paths_cpu.philox4x32_10 / unit_open): inputs of the normals, not roundings."""
+    from test_sample_paths_cpu import philox4x32_10, unit_open
+    k, word = np.broadcast_arrays(np.asarray(k, dtype=np.uint64), np.asarray(word, dtype=np.uint64))
+    j = np.arange((d + 1) // 2, dtype=np.uint64)
+    r = philox4x32_10((k[..., None], word[..., None], np.uint64(problem), j), (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF))
+    return unit_open(r[0], r[1]), unit_open(r[2], r[3])
+
+
+def box_muller(u1, u2, T=LD, angle=None):
+    """(rho cos(2 pi u2), rho sin(2 pi u2), rho) with rho = sqrt(-2 ln u1); angle: the constant in 2 pi's place (a mutant's)"""
+    u1, u2 = np.asarray(u1, dtype=T), np.asarray(u2, dtype=T)
+    rho = np.sqrt(-2 * np.log(u1))
+    ang = (two_pi(T) if angle is None else T(angle)) * u2
+    return rho * np.cos(ang), rho * np.sin(ang), rho
+
+
+def normals(seed, k, word, problem, d, T=LD, angle=None):
+    """(xi, rho), each (..., d): the d normals of grid index k drawn with counter word `word` (k, word broadcast), and the radius of each one's pair"""
+    u1, u2 = uniforms(seed, k, word, problem, d)
+    c, s, rho = box_muller(u1, u2, T, angle)
+    z = np.stack((c, s), axis=-1)
+    rr = np.stack((rho, rho), axis=-1)
+    return z.reshape(z.shape[:-2] + (-1,))[..., :d], rr.reshape(rr.shape[:-2] + (-1,))[..., :d]
+
+
+def model_drift(model, theta, x, T=LD):
+    """(f, sum |monomial|) of the model SDE's drift at x (..., D), in the kernels' grouping of the terms"""
+    x, th = np.asarray(x, dtype=T), np.asarray(theta, dtype=T)
+    if model == "OU":
+        return -th * x, np.abs(th * x)
+    if model == "DW":
+        return 4 * x * (th - x * x), 4 * np.abs(x * th) + 4 * np.abs(x * x * x)
+    if model == "L63":
+        x0, x1, x2 = x[..., 0], x[..., 1], x[..., 2]
+        f = np.stack((th[0] * (x1 - x0), (th[1] - x2) * x0 - x1, x0 * x1 - th[2] * x2), axis=-1)
+        a = np.stack((np.abs(th[0] * x1) + np.abs(th[0] * x0), np.abs(th[1] * x0) + np.abs(x2 * x0) + np.abs(x1),
+                      np.abs(x0 * x1) + np.abs(th[2] * x2)), axis=-1)
+        return f, a
+    assert model == "L96", model
+    up, d1, d2 = np.roll(x, -1, axis=-1), np.roll(x, 1, axis=-1), np.roll(x, 2, axis=-1)
+    return (up - d2) * d1 - x + th, np.abs(up * d1) + np.abs(d2 * d1) + np.abs(x) + np.abs(th)
+
+
+def model_phi(model, x, T=LD):
+    """phi_j = d f_j / d theta_a(j) at x (..., D): the one parameter component j's drift depends on"""
+    x = np.asarray(x, dtype=T)
+    if model == "OU":
+        return -x
+    if model == "DW":
+        return 4 * x
+    if model == "L63":
+        return np.stack((x[..., 1] - x[..., 0], x[..., 0], -x[..., 2]), axis=-1)
+    return np.ones(x.shape, dtype=T)
+
+
+def posterior_drift(lin_a, off_b, x, T=LD):
+    """(b - A x, sum_j |A_ij x_j| + |b_i|); lin_a (K, D, D), off_b (K, D) against x (n, K, D), or (D, D), (D,) against (..., D)"""
+    a, b, x = np.asarray(lin_a, dtype=T), np.asarray(off_b, dtype=T), np.asarray(x, dtype=T)
+    if a.ndim == 3:
+        return b - np.einsum("kij,nkj->nki", a, x), np.einsum("kij,nkj->nki", np.abs(a), np.abs(x)) + np.abs(b)
+    return b - np.einsum("ij,...j->...i", a, x), np.einsum("ij,...j->...i", np.abs(a), np.abs(x)) + np.abs(b)
+
+
+def em_step(prev, drift, drift_abs, dt, fac, xi, T=LD, xi_size=None):
+    """One Euler-Maruyama step x = (x_prev + dt drift) + R xi with the lower factor R = `fac` (D, D): (x, size), size the number its rounding
+    is measured against.  s_i = |x_prev,i| + dt drift_abs_i + sum_j |R_ij xi_j| is the size of the result's terms.  A careful fp64
+    evaluation rounds: the first sum at no more than |x_prev,i| + dt drift_abs_i and the second at no more than s_i (together
+    2 |x_prev,i| + 2 dt drift_abs_i + n_i); the product dt drift (dt drift_abs_i); the drift's own terms, each once, and their sum, a tree
+    of L = levels(D + 1) additions ((1 + L) dt drift_abs_i); the products R_ij xi_j and their sum ((1 + L) n_i, n_i = sum_j |R_ij xi_j|).
+    So size_i = 2 |x_prev,i| + (4 + L) dt drift_abs_i + (2 + L) n_i and, xi_size given (the size of each normal's own rounding, in the same
+    units), + sum_j |R_ij| xi_size_j: the step takes the xi the device computed, the restatement the xi of the same uniforms in T."""
+    prev, fac, xi, dt = np.asarray(prev, dtype=T), np.asarray(fac, dtype=T), np.asarray(xi, dtype=T), T(dt)
+    noise = np.einsum("ij,...j->...i", fac, xi)
+    new = (prev + dt * np.asarray(drift, dtype=T)) + noise
+    lv = levels(prev.shape[-1] + 1)
+    size = 2 * np.abs(prev) + (4 + lv) * dt * np.asarray(drift_abs, dtype=T) + (2 + lv) * np.einsum("ij,...j->...i", np.abs(fac), np.abs(xi))
+    if xi_size is not None:
+        size = size + np.einsum("ij,...j->...i", np.abs(fac), np.asarray(xi_size, dtype=T))
+    return new, size
+
+
+def path_term(model, theta, sigma_diag, dt, lin_a, off_b, stored, T=LD):
+    """The path term of stored stride-1 paths (n, Np, D) under a diagonal Sigma: (sum_k inc_k, sum_k |inc_k|, the recovery size), each (n,).
+    inc_k = -sum_i d_i (eta_i + dt d_i / 2) / Sigma_ii with d = g - f at x_{k-1} and eta = x_k - (x_{k-1} + dt g), known from the stored
+    states up to the two roundings of the state update: recovery = sum_k sum_i |d_i| / Sigma_ii (|x_k,i| + |x_{k-1},i| + dt |g_i|)."""
+    x, dt = np.asarray(stored, dtype=T), T(dt)
+    isg = 1 / np.asarray(sigma_diag, dtype=T)
+    prev, new = x[:, :-1], x[:, 1:]
+    g, _ = posterior_drift(np.asarray(lin_a)[:-1], np.asarray(off_b)[:-1], prev, T)
+    f, _ = model_drift(model, theta, prev, T)
+    d = g - f
+    eta = new - (prev + dt * g)
+    inc = -np.sum(d * isg * (eta + dt * d / 2), axis=-1)
+    rec = np.sum(np.abs(d) * isg * (np.abs(new) + np.abs(prev) + dt * np.abs(g)), axis=(-1, -2))
+    return np.sum(inc, axis=-1), np.sum(np.abs(inc), axis=-1), rec
+
+
+def obs_quadratic(obs_noise, obs_h, d, T=LD):
+    """(Q = H R^-1 H^T, log det R) of one problem's observation model"""
+    r = np.asarray(obs_noise, dtype=T).reshape(d, d)
+    h = np.eye(d, dtype=T) if obs_h is None or d == 1 else np.asarray(obs_h, dtype=T).reshape(d, d)
+    if T is np.float64:
+        return h @ np.linalg.inv(r) @ h.T, np.linalg.slogdet(r)[1]
+    low = cholesky(r)
+    linv = tri_inverse(low)
+    return h.dot(linv.T.dot(linv)).dot(h.T), 2 * np.sum(np.log(np.diag(low)))
+
+
+def obs_term(obs_t, obs_y, obs_noise, obs_h, stored, T=LD):
+    """The observation term of stored stride-1 paths (n, Np, D): (-sum_n r^T Q r / 2 - const, size), each (n,); const = M (D log 2 pi +
+    log det R) / 2 with the fp64 log 2 pi of the library (an input, as in obs_terms).  With q_n = sum_ij |r_i Q_ij r_j| / 2 (the products of
+    the form, so that no cancellation inside it hides) size = (5 + 2 levels(D) + levels(M) + cond_2(R)) sum_n |q_n| + 4 |const|: the
+    residual y - x is rounded and enters twice (2), the two products of r Q r (2), the D^2 products added as a tree (2 levels(D)), the M
+    terms likewise (levels(M)), Q = H R^-1 H^T, whose inverse carries a relative error of cond_2(R) 2^-53 whoever forms it in fp64; the
+    constant's logarithm, its sum and its product with M / 2 (3); and the last subtraction, rounded at no more than sum |q_n| + |const|."""
+    x = np.asarray(stored, dtype=T)
+    d = x.shape[-1]
+    obs_t = np.asarray(obs_t, dtype=np.int64).ravel()
+    y = np.asarray(obs_y, dtype=T).reshape(obs_t.size, d)
+    q, logdet = obs_quadratic(obs_noise, obs_h, d, T)
+    const = obs_t.size * (d * T(np.float64(np.log(2.0 * np.pi))) + logdet) / 2
+    r = y[None, :, :] - x[:, obs_t, :]
+    terms = -np.einsum("nmi,ij,nmj->nm", r, q, r) / 2
+    forms = np.einsum("nmi,ij,nmj->nm", np.abs(r), np.abs(q), np.abs(r)) / 2
+    cond = T(np.linalg.cond(np.asarray(obs_noise, dtype=np.float64).reshape(d, d)))
+    return np.sum(terms, axis=-1) - const, (5 + 2 * levels(d) + levels(obs_t.size) + cond) * np.sum(forms, axis=-1) + 4 * np.abs(const)
+
+
+def statistics_rows(model, theta, dt, stored, T=LD):
+    """The rows (Q, G, H) of stored stride-1 paths or lineages (n, Np, D): (rows (n, 3, D), sizes (n, 3, D)).  Q_j = sum_k r_j^2 / dt,
+    G_j = sum_k phi_j r_j, H_j = sum_k dt phi_j^2 with r = x_k - x_{k-1} - dt f(x_{k-1}) (= dt d + eta), phi at x_{k-1}.  sizes: the
+    recovery of r from the stored states, sum_k 2 |r_j| (|x_k,j| + |x_{k-1},j| + dt |f_j|) / dt for Q and the same with |phi_j| in
+    2 |r_j| / dt's place for G, plus (1 + levels(Np - 1)) sum_k |summand| -- every summand once and the additions of the sum as a tree;
+    H has that term alone."""
+    x, dt = np.asarray(stored, dtype=T), T(dt)
+    prev, new = x[:, :-1], x[:, 1:]
+    f, _ = model_drift(model, theta, prev, T)
+    phi = model_phi(model, prev, T)
+    r = (new - prev) - dt * f
+    reach = np.abs(new) + np.abs(prev) + dt * np.abs(f)
+    sq, sg, sh = r * r / dt, phi * r, dt * (phi * phi)
+    rows = np.stack((_sum(sq, 1), _sum(sg, 1), _sum(sh, 1)), axis=1)
+    lv = levels(r.shape[1])      # (the Np - 1 summands of a row added as a tree; the recovery terms of Q and G dwarf it, H has nothing else)
+    sizes = np.stack((_sum(2 * np.abs(r) * reach / dt + (1 + lv) * np.abs(sq), 1), _sum(np.abs(phi) * reach + (1 + lv) * np.abs(sg), 1),
+                      (1 + lv) * _sum(np.abs(sh), 1)), axis=1)
+    return rows, sizes
+
+
+def normalised_weights(log_w, T=LD, total_scale=None):
+    """W_i = w_i / sum w, w_i = exp(lw_i - max lw), and the size of each one's rounding in units of itself, 1 + |lw_i - max lw| (the
+    argument of exp carries one rounding of a number of that size).  total_scale: the sum times it (a mutant's)."""
+    lw = np.asarray(log_w, dtype=T)
+    off = lw - np.max(lw, axis=-1, keepdims=True)
+    w = np.exp(off)
+    s = np.expand_dims(_sum(w, -1), -1)
+    return w / (s if total_scale is None else s * T(total_scale)), 1 + np.abs(off)
+
+
+def weighted_sum(log_w, values, T=LD, total_scale=None):
+    """(sum_i W_i v_i, size) over the first axis of values (n, ...): size = sum_i W_i (1 + |lw_i - max lw|) |v_i| + 2 levels(n) sum_i W_i |v_i|
+    -- the weights' own rounding, and the additions of two sums of n terms added as trees: the normalising sum, whose relative error every
+    term inherits, and the sum itself"""
+    w, size = normalised_weights(log_w, T, total_scale)
+    v = np.asarray(values, dtype=T)
+    w, size = w.reshape((-1,) + (1,) * (v.ndim - 1)), size.reshape((-1,) + (1,) * (v.ndim - 1))
+    return _sum(w * v, 0), _sum(w * (size + 2 * levels(v.shape[0])) * np.abs(v), 0)
+
+
+def stretch_weights(log_w, slots, T=LD):
+    """The back-propagated weights of every stretch from the slot table of particle_paths(slots=arange(n)) -- slots (M + 1, n), row j the
+    slot of final slot m's lineage in stretch j: W^j_a = sum_{m: slots[j][m] = a} W_m, (M + 1, n)"""
+    w, _ = normalised_weights(log_w, T)
+    slots = np.asarray(slots, dtype=np.int64)
+    out = np.zeros(slots.shape, dtype=T)
+    for j in range(slots.shape[0]):
+        np.add.at(out[j], slots[j], w)
+    return out
 
 
 # --------------------------------------------------------------------------- #
