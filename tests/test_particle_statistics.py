@@ -225,6 +225,10 @@ def test_errors():
     ref = usable()
     with pytest.raises(ValueError):
         ctx.particle_statistics(0, 1, x=xs)
+    for bad in (2 ** 31, 2 ** 32 + 1, -2 ** 31 - 1):      # (would wrap on its way into the int32 of the C ABI)
+        with pytest.raises(ValueError, match="32 bits"):
+            ctx.particle_statistics(bad, 1, x=xs)
+    assert same(usable(), ref)
     for bad in (-0.1, 1.5, float("nan")):
         with pytest.raises(ValueError, match="ess_fraction"):
             ctx.particle_statistics(5, 1, ess_fraction=bad, x=xs)

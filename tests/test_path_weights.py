@@ -284,6 +284,12 @@ def test_errors():
         ctx.sample_paths_weighted(0, 1, x=xs)
     with pytest.raises(ValueError):
         ctx.sample_paths_weighted(2, 1, stride=0, x=xs)
+    for bad in (2 ** 31, 2 ** 32 + 1, -2 ** 31 - 1):      # (would wrap on its way into the int32 of the C ABI)
+        with pytest.raises(ValueError, match="32 bits"):
+            ctx.sample_paths_weighted(bad, 1, x=xs)
+        with pytest.raises(ValueError, match="32 bits"):
+            ctx.sample_paths_weighted(2, 1, stride=bad, x=xs)
+    assert np.array_equal(usable(), ref)
     xx = np.ascontiguousarray(xs)                                               # a null logw, through the C ABI itself
     rc = ctx._lib.vgpa_sample_paths_weighted(ctx._h, xx.ctypes.data, None, 2, 1, 1, None, None, None)
     assert rc == -1

@@ -284,6 +284,11 @@ def test_errors():
         ctx.sample_paths("posterior", 2, 1, stride=0, x=xs)
     with pytest.raises(ValueError):
         ctx.sample_paths("neither", 2, 1, x=xs)
+    for bad in (2 ** 31, 2 ** 32 + 1, -2 ** 31 - 1):      # (would wrap on its way into the int32 of the C ABI)
+        with pytest.raises(ValueError, match="32 bits"):
+            ctx.sample_paths("posterior", bad, 1, x=xs)
+        with pytest.raises(ValueError, match="32 bits"):
+            ctx.sample_paths("posterior", 2, 1, stride=bad, x=xs)
     assert np.array_equal(usable(), ref)
     # a per-problem Sigma / S0 that is not positive definite
     bad = np.stack([np.reshape(q.sigma, (12, 12)) for q in probs])

@@ -564,6 +564,40 @@ class Context:
         self._check(self._lib.vgpa_theta_gradient(self._h, _ptr(out)))
         return out[0] if self.B == 1 else out
 
+    def _walk_inputs(self, x, x0, prior=None):
+        """x, x0 and prior of a sampler call laid out for the C ABI: xx (B len_x), s0 (B, D), mu (B, D), tau (B, D, D), None where the argument is"""
+        xx = None if x is None else _c64(x)
+        if xx is not None and xx.size != self.B * self.len_x:
+            raise ValueError(f"x has {xx.size} entries, expected {self.B * self.len_x}")
+        s0 = None if x0 is None else _c64(np.broadcast_to(np.asarray(x0, dtype=np.float64).reshape(-1, self.D), (self.B, self.D)))
+        mu = tau = None
+        if prior is not None:
+            mu = _c64(np.broadcast_to(np.asarray(prior[0], dtype=np.float64).reshape(-1, self.D), (self.B, self.D)))
+            tau = _c64(np.broadcast_to(np.asarray(prior[1], dtype=np.float64).reshape(-1, self.D, self.D), (self.B, self.D, self.D)))
+        return xx, s0, mu, tau
+
+    def _filter_outputs(self, n):
+        """the filter's results for n particles, to be filled by the library: log_w (B, n), state (B, n, D), ess (B, M), resampled (B, M) int32"""
+        m = self.n_obs
+        return np.empty((self.B, n)), np.empty((self.B, n, self.D)), np.zeros((self.B, m)), np.zeros((self.B, m), dtype=np.int32)
+
+    @staticmethod
+    def _fit32(**named):
+        """the C ABI takes int32: nothing may wrap on its way there (ctypes wraps silently)"""
+        if not all(-2 ** 31 <= v < 2 ** 31 for v in named.values()):
+            names = list(named)
+            raise ValueError(f"{' and '.join(filter(None, (', '.join(names[:-1]), names[-1])))} must fit into 32 bits ("
+                             + ", ".join(f"{k} = {v}" for k, v in named.items()) + ")")
+
+    def _slot_array(self, slots, k):
+        """slots (B, k) or (k,) as the (B, k) int32 array of the C ABI; None stays None"""
+        if slots is None:
+            return None
+        wide = np.asarray(slots)
+        if wide.dtype.kind not in "iu" or wide.size == 0 or wide.min() < -2 ** 31 or wide.max() >= 2 ** 31:
+            raise ValueError("slots must be integers that fit into 32 bits")
+        return np.ascontiguousarray(np.broadcast_to(wide.reshape(-1, k), (self.B, k)), dtype=np.int32)
+
     def sample_paths(self, kind, n_paths, seed, stride=1, x=None, x0=None):
         """Euler-Maruyama paths on the context's grid: kind "posterior" (dx = (-A_t x + b_t) dt + Sigma^1/2 dW, from x or, x=None, the x of
         the cached evaluation, which stays as it is) or "model" (the model SDE at the theta in force; takes no x).  x0 (B, D): the start of every
@@ -572,10 +606,8 @@ class Context:
         if kind not in PATH_KINDS:
             raise ValueError(f" Unknown kind of paths -> {kind}")
         n_paths, stride = int(n_paths), int(stride)
-        xx = None if x is None else _c64(x)
-        if xx is not None and xx.size != self.B * self.len_x:
-            raise ValueError(f"x has {xx.size} entries, expected {self.B * self.len_x}")
-        s0 = None if x0 is None else _c64(np.broadcast_to(np.asarray(x0, dtype=np.float64).reshape(-1, self.D), (self.B, self.D)))
+        self._fit32(n_paths=n_paths, stride=stride)
+        xx, s0, _, _ = self._walk_inputs(x, x0)
         n_keep = (self.Np - 1) // stride + 1 if stride >= 1 else 0
         out = np.empty((self.B, max(n_paths, 0), n_keep, self.D))
         self._check(self._lib.vgpa_sample_paths(self._h, PATH_KINDS[kind], _ptr(xx), _ptr(s0), n_paths, stride,
@@ -587,10 +619,8 @@ class Context:
         model SDE and the data (vgpa_sample_paths_weighted): (paths (B, n_paths, n_keep, D) or None, logw (B, n_paths, 2): the path term and
         the observation term, start (B, n_paths, D): every x_0).  paths=False: no path is stored or copied."""
         n_paths, stride = int(n_paths), int(stride)
-        xx = None if x is None else _c64(x)
-        if xx is not None and xx.size != self.B * self.len_x:
-            raise ValueError(f"x has {xx.size} entries, expected {self.B * self.len_x}")
-        s0 = None if x0 is None else _c64(np.broadcast_to(np.asarray(x0, dtype=np.float64).reshape(-1, self.D), (self.B, self.D)))
+        self._fit32(n_paths=n_paths, stride=stride)
+        xx, s0, _, _ = self._walk_inputs(x, x0)
         n_keep = (self.Np - 1) // stride + 1 if stride >= 1 else 0
         out = np.empty((self.B, max(n_paths, 0), n_keep, self.D)) if paths else None
         logw, start = np.empty((self.B, max(n_paths, 0), 2)), np.empty((self.B, max(n_paths, 0), self.D))
@@ -605,17 +635,10 @@ class Context:
         and, history=True, ancestors (B, M, n_paths) int32 and clouds (B, M, n_paths, D) (else None), M = the context's n_obs.  Rows at or
         beyond a problem's own observation count: ess 0, resampled 0, ancestors -1, clouds NaN."""
         n_paths, m = int(n_paths), self.n_obs
-        xx = None if x is None else _c64(x)
-        if xx is not None and xx.size != self.B * self.len_x:
-            raise ValueError(f"x has {xx.size} entries, expected {self.B * self.len_x}")
-        s0 = None if x0 is None else _c64(np.broadcast_to(np.asarray(x0, dtype=np.float64).reshape(-1, self.D), (self.B, self.D)))
-        mu = tau = None
-        if prior is not None:
-            mu = _c64(np.broadcast_to(np.asarray(prior[0], dtype=np.float64).reshape(-1, self.D), (self.B, self.D)))
-            tau = _c64(np.broadcast_to(np.asarray(prior[1], dtype=np.float64).reshape(-1, self.D, self.D), (self.B, self.D, self.D)))
+        self._fit32(n_paths=n_paths)
+        xx, s0, mu, tau = self._walk_inputs(x, x0, prior)
         n = max(n_paths, 0)
-        log_w, state = np.empty((self.B, n)), np.empty((self.B, n, self.D))
-        ess, flags = np.zeros((self.B, m)), np.zeros((self.B, m), dtype=np.int32)
+        log_w, state, ess, flags = self._filter_outputs(n)
         anc = np.full((self.B, m, n), -1, dtype=np.int32) if history else None
         clouds = np.full((self.B, m, n, self.D), np.nan) if history else None
         self._check(self._lib.vgpa_particle_filter(self._h, _ptr(xx), _ptr(s0), n_paths, int(seed) & 0xFFFFFFFFFFFFFFFF, float(ess_fraction),
@@ -629,17 +652,10 @@ class Context:
         particle_filter (bit for bit), mean (B, 3, D): the self-normalised weighted mean of the rows, reduced on the device, and stats
         (B, n_paths, 3, D): the rows themselves (per_particle=True, else None)."""
         n_paths, m = int(n_paths), self.n_obs
-        xx = None if x is None else _c64(x)
-        if xx is not None and xx.size != self.B * self.len_x:
-            raise ValueError(f"x has {xx.size} entries, expected {self.B * self.len_x}")
-        s0 = None if x0 is None else _c64(np.broadcast_to(np.asarray(x0, dtype=np.float64).reshape(-1, self.D), (self.B, self.D)))
-        mu = tau = None
-        if prior is not None:
-            mu = _c64(np.broadcast_to(np.asarray(prior[0], dtype=np.float64).reshape(-1, self.D), (self.B, self.D)))
-            tau = _c64(np.broadcast_to(np.asarray(prior[1], dtype=np.float64).reshape(-1, self.D, self.D), (self.B, self.D, self.D)))
+        self._fit32(n_paths=n_paths)
+        xx, s0, mu, tau = self._walk_inputs(x, x0, prior)
         n = max(n_paths, 0)
-        log_w, state = np.empty((self.B, n)), np.empty((self.B, n, self.D))
-        ess, flags = np.zeros((self.B, m)), np.zeros((self.B, m), dtype=np.int32)
+        log_w, state, ess, flags = self._filter_outputs(n)
         mean = np.empty((self.B, 3, self.D))
         stats = np.empty((self.B, n, 3, self.D)) if per_particle else None
         self._check(self._lib.vgpa_particle_statistics(self._h, _ptr(xx), _ptr(s0), n_paths, int(seed) & 0xFFFFFFFFFFFFFFFF, float(ess_fraction),
@@ -653,19 +669,10 @@ class Context:
         resampled as particle_filter (bit for bit), moments (B, n_keep, 2, D): sum W x and sum W x^2 at the grid indices 0, stride, ...,
         and lineage_ess (B, M + 1): 1 / sum W^2 of every stretch between two observations (0 beyond a problem's own count + 1)."""
         n_paths, stride, m = int(n_paths), int(stride), self.n_obs
-        if not -2 ** 31 <= stride < 2 ** 31 or not -2 ** 31 <= n_paths < 2 ** 31:      # (the C ABI takes int32: nothing may wrap on its way there)
-            raise ValueError(f"n_paths and stride must fit into 32 bits (n_paths = {n_paths}, stride = {stride})")
-        xx = None if x is None else _c64(x)
-        if xx is not None and xx.size != self.B * self.len_x:
-            raise ValueError(f"x has {xx.size} entries, expected {self.B * self.len_x}")
-        s0 = None if x0 is None else _c64(np.broadcast_to(np.asarray(x0, dtype=np.float64).reshape(-1, self.D), (self.B, self.D)))
-        mu = tau = None
-        if prior is not None:
-            mu = _c64(np.broadcast_to(np.asarray(prior[0], dtype=np.float64).reshape(-1, self.D), (self.B, self.D)))
-            tau = _c64(np.broadcast_to(np.asarray(prior[1], dtype=np.float64).reshape(-1, self.D, self.D), (self.B, self.D, self.D)))
+        self._fit32(n_paths=n_paths, stride=stride)
+        xx, s0, mu, tau = self._walk_inputs(x, x0, prior)
         n = max(n_paths, 0)
-        log_w, state = np.empty((self.B, n)), np.empty((self.B, n, self.D))
-        ess, flags = np.zeros((self.B, m)), np.zeros((self.B, m), dtype=np.int32)
+        log_w, state, ess, flags = self._filter_outputs(n)
         moments = np.empty((self.B, (self.Np - 1) // max(stride, 1) + 1, 2, self.D))
         lineage_ess = np.zeros((self.B, m + 1))
         self._check(self._lib.vgpa_particle_moments(self._h, _ptr(xx), _ptr(s0), n_paths, stride, int(seed) & 0xFFFFFFFFFFFFFFFF, float(ess_fraction),
@@ -679,19 +686,10 @@ class Context:
         as particle_moments (bit for bit), mean (B, n_keep, D): sum W x, and second (B, n_keep, D, D): sum W x x^T, symmetric to the bit,
         at the grid indices 0, stride, ...  The covariance is second - mean mean^T (SmoothingCovariance.cov)."""
         n_paths, stride, m = int(n_paths), int(stride), self.n_obs
-        if not -2 ** 31 <= stride < 2 ** 31 or not -2 ** 31 <= n_paths < 2 ** 31:      # (the C ABI takes int32: nothing may wrap on its way there)
-            raise ValueError(f"n_paths and stride must fit into 32 bits (n_paths = {n_paths}, stride = {stride})")
-        xx = None if x is None else _c64(x)
-        if xx is not None and xx.size != self.B * self.len_x:
-            raise ValueError(f"x has {xx.size} entries, expected {self.B * self.len_x}")
-        s0 = None if x0 is None else _c64(np.broadcast_to(np.asarray(x0, dtype=np.float64).reshape(-1, self.D), (self.B, self.D)))
-        mu = tau = None
-        if prior is not None:
-            mu = _c64(np.broadcast_to(np.asarray(prior[0], dtype=np.float64).reshape(-1, self.D), (self.B, self.D)))
-            tau = _c64(np.broadcast_to(np.asarray(prior[1], dtype=np.float64).reshape(-1, self.D, self.D), (self.B, self.D, self.D)))
+        self._fit32(n_paths=n_paths, stride=stride)
+        xx, s0, mu, tau = self._walk_inputs(x, x0, prior)
         n, n_keep = max(n_paths, 0), (self.Np - 1) // max(stride, 1) + 1
-        log_w, state = np.empty((self.B, n)), np.empty((self.B, n, self.D))
-        ess, flags = np.zeros((self.B, m)), np.zeros((self.B, m), dtype=np.int32)
+        log_w, state, ess, flags = self._filter_outputs(n)
         mean, second = np.empty((self.B, n_keep, self.D)), np.empty((self.B, n_keep, self.D, self.D))
         lineage_ess = np.zeros((self.B, m + 1))
         self._check(self._lib.vgpa_particle_covariance(self._h, _ptr(xx), _ptr(s0), n_paths, stride, int(seed) & 0xFFFFFFFFFFFFFFFF, float(ess_fraction),
@@ -718,25 +716,11 @@ class Context:
     def _smoothing_paths(self, entry, n_paths, seed, n_draw, stride, ess_fraction, x, x0, prior, slots):
         """the arguments of particle_paths / particle_backward_paths checked and laid out, the call, the dict"""
         n_paths, n_draw, stride, m = int(n_paths), int(n_draw), int(stride), self.n_obs
-        if not all(-2 ** 31 <= v < 2 ** 31 for v in (n_paths, n_draw, stride)):      # (the C ABI takes int32: nothing may wrap on its way there)
-            raise ValueError(f"n_paths, n_draw and stride must fit into 32 bits (n_paths = {n_paths}, n_draw = {n_draw}, stride = {stride})")
-        xx = None if x is None else _c64(x)
-        if xx is not None and xx.size != self.B * self.len_x:
-            raise ValueError(f"x has {xx.size} entries, expected {self.B * self.len_x}")
-        s0 = None if x0 is None else _c64(np.broadcast_to(np.asarray(x0, dtype=np.float64).reshape(-1, self.D), (self.B, self.D)))
-        mu = tau = None
-        if prior is not None:
-            mu = _c64(np.broadcast_to(np.asarray(prior[0], dtype=np.float64).reshape(-1, self.D), (self.B, self.D)))
-            tau = _c64(np.broadcast_to(np.asarray(prior[1], dtype=np.float64).reshape(-1, self.D, self.D), (self.B, self.D, self.D)))
+        self._fit32(n_paths=n_paths, n_draw=n_draw, stride=stride)
+        xx, s0, mu, tau = self._walk_inputs(x, x0, prior)
         n, k = max(n_paths, 0), max(n_draw, 0)
-        given = None
-        if slots is not None:
-            wide = np.asarray(slots)
-            if wide.dtype.kind not in "iu" or wide.size == 0 or wide.min() < -2 ** 31 or wide.max() >= 2 ** 31:
-                raise ValueError("slots must be integers that fit into 32 bits")
-            given = np.ascontiguousarray(np.broadcast_to(wide.reshape(-1, k), (self.B, k)), dtype=np.int32)
-        log_w, state = np.empty((self.B, n)), np.empty((self.B, n, self.D))
-        ess, flags = np.zeros((self.B, m)), np.zeros((self.B, m), dtype=np.int32)
+        given = self._slot_array(slots, k)
+        log_w, state, ess, flags = self._filter_outputs(n)
         paths = np.empty((self.B, k, (self.Np - 1) // max(stride, 1) + 1, self.D))
         table = np.full((self.B, m + 1, k), -1, dtype=np.int32)
         self._check(entry(self._h, _ptr(xx), _ptr(s0), n_paths, n_draw, _ptr(given), stride, int(seed) & 0xFFFFFFFFFFFFFFFF, float(ess_fraction),
@@ -775,26 +759,12 @@ class Context:
                 raise ValueError("log_w and index0 belong to a given cloud")
             cl, lw, k0 = None, None, self.Np - 1
         n_paths = int(n_paths)
-        if not all(-2 ** 31 <= v < 2 ** 31 for v in (n_paths, n_draw, stride, horizon, k0)):      # (the C ABI takes int32: nothing may wrap on its way there)
-            raise ValueError("n_paths, n_draw, stride, horizon and index0 must fit into 32 bits")
-        xx = None if x is None else _c64(x)
-        if xx is not None and xx.size != self.B * self.len_x:
-            raise ValueError(f"x has {xx.size} entries, expected {self.B * self.len_x}")
-        s0 = None if x0 is None else _c64(np.broadcast_to(np.asarray(x0, dtype=np.float64).reshape(-1, self.D), (self.B, self.D)))
-        mu = tau = None
-        if prior is not None:
-            mu = _c64(np.broadcast_to(np.asarray(prior[0], dtype=np.float64).reshape(-1, self.D), (self.B, self.D)))
-            tau = _c64(np.broadcast_to(np.asarray(prior[1], dtype=np.float64).reshape(-1, self.D, self.D), (self.B, self.D, self.D)))
+        self._fit32(n_paths=n_paths, n_draw=n_draw, stride=stride, horizon=horizon, index0=k0)
+        xx, s0, mu, tau = self._walk_inputs(x, x0, prior)
         n, k, m = max(n_paths, 0), max(n_draw, 0), self.n_obs
-        given = None
-        if slots is not None:
-            wide = np.asarray(slots)
-            if wide.dtype.kind not in "iu" or wide.size == 0 or wide.min() < -2 ** 31 or wide.max() >= 2 ** 31:
-                raise ValueError("slots must be integers that fit into 32 bits")
-            given = np.ascontiguousarray(np.broadcast_to(wide.reshape(-1, k), (self.B, k)), dtype=np.int32)
+        given = self._slot_array(slots, k)
         h_keep = max(horizon, 0) // max(stride, 1) + 1
-        out_lw, state = np.empty((self.B, n)), np.empty((self.B, n, self.D))
-        ess, flags = np.zeros((self.B, m)), np.zeros((self.B, m), dtype=np.int32)
+        out_lw, state, ess, flags = self._filter_outputs(n)
         moments, members = np.empty((self.B, h_keep, 2, self.D)), np.empty((self.B, k, h_keep, self.D))
         table, state_end = np.full((self.B, k), -1, dtype=np.int32), np.empty((self.B, n, self.D))
         self._check(self._lib.vgpa_particle_forecast(self._h, _ptr(xx), _ptr(s0), n_paths, int(seed) & 0xFFFFFFFFFFFFFFFF, float(ess_fraction),

@@ -189,8 +189,7 @@ constexpr WalkTraits kWalkTraits[] = {      // in the order of Walk
 // replay's sums with W = pf_wtab at h = 0, stride, ..., the end state back to pf_x.  The member launch (out, pf_slots set): lane m starts from
 // slot pf_slots[p][m], draws with that slot's word and stores as Plain stores.  A lane behind the last one walks the last one again with
 // weight 0 and stores nothing.
-// Walk::Backward: x = the particle slot `word` was copied from at observation j of problem p (pf_clouds, pf_hanc and pf_M are the walk's own
-// names of the storage of pf_wtab, pf_part and pf_rows: vgpa_internal.h)
+// Walk::Backward: x = the particle slot `word` was copied from at observation j of problem p
 template <int D>
 __device__ __forceinline__ void backward_reload(const SampleArgs& a, uint32_t p, int j, uint32_t word, double* x) {
   const size_t hj = (size_t)p * a.pf_M + j;
@@ -640,7 +639,7 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
   }
   // Backward: the particle slot `word` was copied from at the problem's observation j, to x and to the path's column of Xs (the points kept so
   // far have left Xs: the stores of `put` precede these writes in every lane of the wave that owns the region)
-  auto reload = [&](int j) {      // (pf_clouds, pf_hanc, pf_M: the storage of pf_wtab, pf_part, pf_rows, which this walk does not read)
+  auto reload = [&](int j) {
     const size_t hj = (size_t)p * a.pf_M + j;
     const double* src = a.pf_clouds + (hj * a.pf_n + (size_t)a.pf_hanc[hj * a.pf_n + word]) * D;
 #pragma unroll
@@ -882,6 +881,47 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
 // ---- 5 <= D <= 64, model kind: Lorenz-96 ------------------------------------------------------------------------------------------
 // One lane per (problem, path); xs [D][64] in LDS, component-major so that a wave's 64 lanes touch 64 consecutive doubles.  The drift is
 // evaluated in place behind three rolling registers of old values.  zs [D][64]: the normals, when a dense factor needs all of them at once.
+// x_0 = m0 + L0 xi_0 of path `path` of problem p: the normals of grid index 0 to z, then the rows of L0 in order; S doubles between two
+// components of z and of x
+template <int S>
+__device__ __forceinline__ void start_draw(uint32_t k0, uint32_t k1, uint32_t path, uint32_t p, int D, const double* m0, const double* L0,
+                                           double* z, double* x) {
+  for (int j = 0; 2 * j < D; j++) {
+    double c, s;
+    normal_pair(k0, k1, 0u, path, p, (uint32_t)j, &c, &s);
+    z[2 * j * S] = c;
+    if (2 * j + 1 < D) z[(2 * j + 1) * S] = s;
+  }
+  for (int i = 0; i < D; i++) {
+    double s = 0.0;
+    for (int j = 0; j <= i; j++) s += L0[i * D + j] * z[j * S];
+    x[i * S] = m0[i] + s;
+  }
+}
+
+// One Lorenz-96 step of the lane's column xs at grid index k with counter word `word`: a diagonal factor draws each pair of normals where it
+// is used, a dense one (dense) finds all of them in the lane's column zs, drawn by the caller (drawn in here, k_sample_l96 takes 98 VGPRs
+// for 96 and 4 waves per SIMD for 5)
+__device__ __forceinline__ void l96_step(uint32_t k0, uint32_t k1, uint32_t k, uint32_t word, uint32_t p, int D, double th, double dt,
+                                         const double* Rp, bool dense, double* xs, const double* zs) {
+  const double x_first = xs[0];
+  double om2 = xs[(D - 2) * 64], om1 = xs[(D - 1) * 64], cur = x_first, zc = 0.0, zn = 0.0;
+  for (int i = 0; i < D; i++) {
+    const double nxt = i + 1 < D ? xs[(i + 1) * 64] : x_first;
+    const double f = (nxt - om2) * om1 - cur + th;
+    double nz;
+    if (dense) {
+      nz = 0.0;
+      for (int j = 0; j <= i; j++) nz += Rp[i * D + j] * zs[j * 64];
+    } else {
+      if (!(i & 1)) normal_pair(k0, k1, k, word, p, (uint32_t)(i >> 1), &zc, &zn);
+      nz = Rp[i * D + i] * ((i & 1) ? zn : zc);
+    }
+    xs[i * 64] = (cur + dt * f) + nz;
+    om2 = om1; om1 = cur; cur = nxt;
+  }
+}
+
 __global__ __launch_bounds__(64) void k_sample_l96(SampleArgs a) {
   extern __shared__ double lds[];
   const int D = a.D, lane = threadIdx.x;
@@ -899,17 +939,7 @@ __global__ __launch_bounds__(64) void k_sample_l96(SampleArgs a) {
   } else {
     const double* m0 = a.m0 + (size_t)p * a.m0_stride;
     const double* L0 = a.L0 + (size_t)p * a.L0_stride;
-    for (int j = 0; 2 * j < D; j++) {      // (the start draw is written out here and in k_pf_start: as a shared function it changes k_pf_start's code)
-      double c, s;
-      normal_pair(k0, k1, 0u, path, p, (uint32_t)j, &c, &s);
-      zs[2 * j * 64] = c;
-      if (2 * j + 1 < D) zs[(2 * j + 1) * 64] = s;
-    }
-    for (int i = 0; i < D; i++) {
-      double s = 0.0;
-      for (int j = 0; j <= i; j++) s += L0[i * D + j] * zs[j * 64];
-      xs[i * 64] = m0[i] + s;
-    }
+    start_draw<64>(k0, k1, path, p, D, m0, L0, zs, xs);
   }
   double* o = a.out + gid * (size_t)a.n_keep * D;
   for (int i = 0; i < D; i++) o[i] = xs[i * 64];
@@ -923,22 +953,7 @@ __global__ __launch_bounds__(64) void k_sample_l96(SampleArgs a) {
         zs[2 * j * 64] = c;
         if (2 * j + 1 < D) zs[(2 * j + 1) * 64] = s;
       }
-    const double x_first = xs[0];
-    double om2 = xs[(D - 2) * 64], om1 = xs[(D - 1) * 64], cur = x_first, zc = 0.0, zn = 0.0;
-    for (int i = 0; i < D; i++) {
-      const double nxt = i + 1 < D ? xs[(i + 1) * 64] : x_first;
-      const double f = (nxt - om2) * om1 - cur + th;
-      double nz;
-      if (dense) {
-        nz = 0.0;
-        for (int j = 0; j <= i; j++) nz += Rp[i * D + j] * zs[j * 64];
-      } else {
-        if (!(i & 1)) normal_pair(k0, k1, (uint32_t)k, path, p, (uint32_t)(i >> 1), &zc, &zn);
-        nz = Rp[i * D + i] * ((i & 1) ? zn : zc);
-      }
-      xs[i * 64] = (cur + a.dt * f) + nz;
-      om2 = om1; om1 = cur; cur = nxt;
-    }
+    l96_step(k0, k1, (uint32_t)k, path, p, D, th, a.dt, Rp, dense, xs, zs);
     if (--until == 0) {
       until = a.stride;
       for (int i = 0; i < D; i++) o[i] = xs[i * 64];
@@ -1000,16 +1015,7 @@ __global__ __launch_bounds__(64) void k_forecast_l96(SampleArgs a) {
   const int H = a.k_end - a.k_begin;
   for (int h = 0; h < H; h++) {      // (step h + 1; k_begin + h + 1 may be the last index an int holds)
     const uint32_t k = (uint32_t)a.k_begin + (uint32_t)h + 1u;
-    const double x_first = xs[0];
-    double om2 = xs[(D - 2) * 64], om1 = xs[(D - 1) * 64], cur = x_first, zc = 0.0, zn = 0.0;
-    for (int i = 0; i < D; i++) {
-      const double nxt = i + 1 < D ? xs[(i + 1) * 64] : x_first;
-      const double f = (nxt - om2) * om1 - cur + th;
-      if (!(i & 1)) normal_pair(k0, k1, k, word, p, (uint32_t)(i >> 1), &zc, &zn);
-      const double nz = Rp[i * D + i] * ((i & 1) ? zn : zc);
-      xs[i * 64] = (cur + a.dt * f) + nz;
-      om2 = om1; om1 = cur; cur = nxt;
-    }
+    l96_step(k0, k1, k, word, p, D, th, a.dt, Rp, false, xs, nullptr);
     if (--until == 0) {
       until = a.stride;
       if (sums) reduce();
@@ -1043,17 +1049,7 @@ __global__ __launch_bounds__(256) void k_pf_start(PfArgs a) {
   } else {
     const double* m0 = a.m0 + (size_t)p * a.m0_stride;
     const double* L0 = a.L0 + (size_t)p * a.L0_stride;
-    for (int j = 0; 2 * j < D; j++) {
-      double c, s;
-      normal_pair(k0, k1, 0u, path, p, (uint32_t)j, &c, &s);
-      u[2 * j] = c;
-      if (2 * j + 1 < D) u[2 * j + 1] = s;
-    }
-    for (int i = 0; i < D; i++) {
-      double s = 0.0;
-      for (int j = 0; j <= i; j++) s += L0[i * D + j] * u[j];
-      x[i] = m0[i] + s;
-    }
+    start_draw<1>(k0, k1, path, p, D, m0, L0, u, x);
     if (a.mu0) {
       const double* mu = a.mu0 + (size_t)p * D;
       const double* Lt = a.Lt + (size_t)p * D * D;
@@ -1080,7 +1076,7 @@ __global__ __launch_bounds__(256) void k_pf_start(PfArgs a) {
 // pf_max: max lw (red: 4 doubles of LDS).
 // pf_prefix_sums: cum_i = the inclusive prefix sums of w_i = exp(lw_i - mx) in slot order, 256 slots per pass: a shuffle scan per wave, the
 // waves' totals and the carry through LDS (tot: 4 doubles); returns the thread's share of sum w^2.  No barrier behind the last store of cum.
-// (The bisection that follows is written out in either kernel: as a shared function it costs k_pf_resample two SGPRs.)
+// pf_bisect: min(#{m: cum_m <= u}, n - 1), the slot a threshold u falls into.  pf_obs_at: the problem's observation at grid index a.k, or -1.
 __device__ __forceinline__ double pf_max(const double* lw, int n, double* red) {
   double mx = -INFINITY;
   for (int i = threadIdx.x; i < n; i += 256) mx = fmax(mx, lw[i]);
@@ -1088,6 +1084,21 @@ __device__ __forceinline__ double pf_max(const double* lw, int n, double* red) {
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
   __syncthreads();
   return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+}
+__device__ __forceinline__ int pf_bisect(const double* cum, int n, double u) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (cum[mid] <= u) lo = mid + 1; else hi = mid;
+  }
+  return lo < n - 1 ? lo : n - 1;
+}
+__device__ __forceinline__ int pf_obs_at(const PfArgs& a, int p) {
+  const int64_t* t = a.obs_t + (size_t)p * a.obs_t_stride;
+  const int cnt = a.n_obs_v ? a.n_obs_v[p] : a.n_obs;
+  int j = -1;
+  for (int m = 0; m < cnt; m++) if (t[m] == (int64_t)a.k) j = m;
+  return j;
 }
 __device__ __forceinline__ double pf_prefix_sums(const double* lw, int n, double mx, double* cum, double* tot) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -1122,10 +1133,7 @@ template <bool ST>
 __global__ __launch_bounds__(256) void k_pf_resample(PfArgs a) {
   __shared__ double tot[4], red[4];
   const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6, n = a.n_paths, D = a.D;
-  const int64_t* t = a.obs_t + (size_t)p * a.obs_t_stride;
-  const int cnt = a.n_obs_v ? a.n_obs_v[p] : a.n_obs;
-  int j = -1;      // the problem's observation at a.k (written out here and in the other step between segments: a shared function changes the code of both)
-  for (int m = 0; m < cnt; m++) if (t[m] == (int64_t)a.k) j = m;
+  const int j = pf_obs_at(a, p);
   const size_t nD = (size_t)n * D;
   const double* xin = a.x_in + (size_t)p * nD;
   double* xout = a.x_out + (size_t)p * nD;
@@ -1164,12 +1172,7 @@ __global__ __launch_bounds__(256) void k_pf_resample(PfArgs a) {
     int from = i;
     if (go) {
       const double ui = (U + (double)i) / (double)n * S;
-      int lo = 0, hi = n;
-      while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (cum[mid] <= ui) lo = mid + 1; else hi = mid;
-      }
-      from = lo < n - 1 ? lo : n - 1;
+      from = pf_bisect(cum, n, ui);
       if (a.h_lw) a.h_lw[hj * n + i] = lw[i];
       lw[i] = lw_new;
     }
@@ -1304,10 +1307,7 @@ __global__ __launch_bounds__(256) void k_pf_normalise(int n, const double* lw_al
 // unchanged where the problem has no observation there.
 __global__ __launch_bounds__(256) void k_pf_gather(PfArgs a) {
   const int p = blockIdx.x, n = a.n_paths, D = a.D;
-  const int64_t* t = a.obs_t + (size_t)p * a.obs_t_stride;
-  const int cnt = a.n_obs_v ? a.n_obs_v[p] : a.n_obs;
-  int j = -1;      // the problem's observation at a.k (written out here and in the other step between segments: a shared function changes the code of both)
-  for (int m = 0; m < cnt; m++) if (t[m] == (int64_t)a.k) j = m;
+  const int j = pf_obs_at(a, p);
   const size_t nD = (size_t)n * D;
   const double* xin = a.x_in + (size_t)p * nD;
   double* xout = a.x_out + (size_t)p * nD;
@@ -1362,12 +1362,7 @@ __global__ __launch_bounds__(256) void k_pf_pick(PfArgs a, int Np, int K, int ro
   int32_t* row = table + ((size_t)p * rows + cnt) * K;
   for (int m = threadIdx.x; m < K; m += 256) {
     const double um = (U + (double)m) / (double)K * S;
-    int lo = 0, hi = n;
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (cum[mid] <= um) lo = mid + 1; else hi = mid;
-    }
-    row[m] = lo < n - 1 ? lo : n - 1;
+    row[m] = pf_bisect(cum, n, um);
   }
 }
 
@@ -1568,8 +1563,8 @@ hipError_t launch_walk(const SampleArgs& a, hipStream_t st) {
       // (ReplayCov: the [4 waves][NT] words of the mean behind the Zs region)
       const size_t lds = (MfmaShape<NT>::lds_doubles(!a.R_diag) + (kWalkTraits[(int)K].CV ? 4 * NT : 0)) * sizeof(double);
       if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k_sample_mfma<NT, K>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if ((a.n_paths + 63) / 64 > 65535) return hipErrorInvalidValue;      // (grid.y)
-      hipLaunchKernelGGL((k_sample_mfma<NT, K>), dim3(a.batch, (a.n_paths + 63) / 64), dim3(256), lds, st, a);
+      if (a.n_paths > sample_max_paths(a.D)) return hipErrorInvalidValue;
+      hipLaunchKernelGGL((k_sample_mfma<NT, K>), dim3(a.batch, sample_segment_blocks(a.D, a.n_paths)), dim3(256), lds, st, a);
       return hipGetLastError();
     };
     if (a.D <= 16) return mfma(std::integral_constant<int, 16>{});
@@ -1595,7 +1590,11 @@ hipError_t launch_pf_resample(const PfArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
-int sample_segment_blocks(int D, int n_paths) { return D <= kMaxLaneD ? (n_paths + 255) / 256 : (n_paths + 63) / 64; }
+// the slots of a problem in grid.y, 256 per workgroup up to D = 4 and 64 above it; one-dimensional grids in grid.x
+static int segment_slots(int D) { return D <= kMaxLaneD ? 256 : 64; }
+int sample_segment_blocks(int D, int n_paths) { return (n_paths + segment_slots(D) - 1) / segment_slots(D); }
+int sample_max_paths(int D) { return kMaxGridY * segment_slots(D); }
+bool pf_flat_grid_fits(size_t entries) { return (entries + 255) / 256 <= 0x7fffffffu; }
 
 hipError_t launch_pf_descend(const PfArgs& a, int rows, double* wtab, double* less, hipStream_t st) {
   if (a.batch < 1 || a.n_paths < 1 || a.M < 1 || rows < a.M + 1 || !a.lw || !a.h_flag || !a.h_anc || !wtab || !less) return hipErrorInvalidValue;
@@ -1613,14 +1612,14 @@ hipError_t launch_pf_gather(const PfArgs& a, hipStream_t st) {
 
 hipError_t launch_pf_moments_sum(int batch, int n_blocks, size_t len, const double* part, double* out, hipStream_t st) {
   const size_t total = (size_t)batch * len;
-  if (batch < 1 || n_blocks < 1 || len < 1 || (total + 255) / 256 > 0x7fffffffu || !part || !out) return hipErrorInvalidValue;
+  if (batch < 1 || n_blocks < 1 || len < 1 || !pf_flat_grid_fits(total) || !part || !out) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_pf_moments_sum, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, n_blocks, len, total, part, out);
   return hipGetLastError();
 }
 
 hipError_t launch_pf_cov_unpack(int D, size_t rows, const double* packed, double* mean, double* second, hipStream_t st) {
   const size_t total = rows * (size_t)D * D;
-  if (D < 1 || D > kMaxSmallD || rows < 1 || (total + 255) / 256 > 0x7fffffffu || !packed || !mean || !second) return hipErrorInvalidValue;
+  if (D < 1 || D > kMaxSmallD || rows < 1 || !pf_flat_grid_fits(total) || !packed || !mean || !second) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_pf_cov_unpack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, D, total, packed, mean, second);
   return hipGetLastError();
 }
@@ -1633,7 +1632,7 @@ hipError_t launch_pf_pick(const PfArgs& a, int Np, int K, int rows, int32_t* tab
 
 hipError_t launch_pf_trace(const PfArgs& a, int K, int rows, int32_t* table, hipStream_t st) {
   const size_t lanes = (size_t)a.batch * (K > 0 ? K : 0);
-  if (a.batch < 1 || a.n_paths < 1 || a.M < 1 || K < 1 || rows < 1 || (lanes + 255) / 256 > 0x7fffffffu || !a.h_flag || !a.h_anc || !table)
+  if (a.batch < 1 || a.n_paths < 1 || a.M < 1 || K < 1 || rows < 1 || !pf_flat_grid_fits(lanes) || !a.h_flag || !a.h_anc || !table)
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_pf_trace, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, a, K, rows, table);
   return hipGetLastError();
@@ -1665,8 +1664,7 @@ hipError_t launch_pf_normalise(int batch, int n_paths, const double* lw, double*
 }
 
 bool sample_lineages_fit(int D, int batch, int K) {
-  if (D <= kMaxLaneD) return ((size_t)batch * K + 255) / 256 <= 0x7fffffffu;      // (grid.x)
-  return (K + 63) / 64 <= 65535;                                                    // (grid.y)
+  return D <= kMaxLaneD ? pf_flat_grid_fits((size_t)batch * K) : K <= sample_max_paths(D);
 }
 
 hipError_t launch_pf_stats_mean(int D, int batch, int n_paths, const double* lw, const double* stats, double* mean, hipStream_t st) {
@@ -1682,6 +1680,7 @@ hipError_t launch_sample_walk(Walk w, const SampleArgs& a, hipStream_t st) {
   // the weighted kind: the posterior process with diagonal factors against the model's drift; above D = 4 the model is Lorenz-96
   const bool weighable = a.kind == VGPA_PATHS_POSTERIOR && a.R_diag && known_model && (a.D <= kMaxLaneD || a.model == VGPA_MODEL_L96);
   const bool segment = weighable && a.pf_x && a.pf_lw && a.k_begin >= 0 && a.k_end >= a.k_begin && a.k_end < a.Np;
+  if (w == Walk::Backward ? a.pf_wtab || a.pf_part : a.pf_clouds || a.pf_hanc) return hipErrorInvalidValue;      // (the histories are Backward's alone, the sums never its)
   switch (w) {
     case Walk::Plain: {
       if (a.stride < 1 || a.logw) return hipErrorInvalidValue;
@@ -1702,11 +1701,11 @@ hipError_t launch_sample_walk(Walk w, const SampleArgs& a, hipStream_t st) {
       return launch_walk<Walk::SegmentStats>(a, st);
     case Walk::Replay:
       if (!segment || !a.pf_wtab || a.pf_stats || !a.pf_part || a.stride < 1 || a.pf_rows < 1) return hipErrorInvalidValue;
-      if (sample_segment_blocks(a.D, a.n_paths) > 65535) return hipErrorInvalidValue;      // (grid.y)
+      if (a.n_paths > sample_max_paths(a.D)) return hipErrorInvalidValue;
       return launch_walk<Walk::Replay>(a, st);
     case Walk::ReplayCov:      // (the replay's fields; pf_part holds sample_cov_len(D) doubles per kept index)
       if (!segment || !a.pf_wtab || a.pf_stats || !a.pf_part || a.stride < 1 || a.pf_rows < 1) return hipErrorInvalidValue;
-      if (sample_segment_blocks(a.D, a.n_paths) > 65535) return hipErrorInvalidValue;      // (grid.y)
+      if (a.n_paths > sample_max_paths(a.D)) return hipErrorInvalidValue;
       return launch_walk<Walk::ReplayCov>(a, st);
     case Walk::Lineage:
       if (a.stride < 1 || a.kind != VGPA_PATHS_POSTERIOR || !a.R_diag || !a.out || !a.pf_slots || a.pf_slot_rows < 1 || a.logw) return hipErrorInvalidValue;
@@ -1716,12 +1715,12 @@ hipError_t launch_sample_walk(Walk w, const SampleArgs& a, hipStream_t st) {
       if (a.stride < 1 || a.kind != VGPA_PATHS_POSTERIOR || !a.R_diag || !a.out || !a.pf_slots || a.pf_slot_rows < 1 || a.logw) return hipErrorInvalidValue;
       if (!a.pf_clouds || !a.pf_hanc || a.pf_M < 1 || a.pf_n < 1 || !sample_lineages_fit(a.D, a.batch, a.n_paths)) return hipErrorInvalidValue;
       return launch_walk<Walk::Backward>(a, st);
-    case Walk::Forecast: {      // (pf_part and pf_wtab are also the storage of Walk::Backward's pf_hanc and pf_clouds: only that walk's caller sets those)
+    case Walk::Forecast: {
       const bool cloud = a.pf_part && a.pf_wtab && !a.out && !a.pf_slots && a.n_paths == a.pf_n;
       const bool members = a.out && a.pf_slots && a.pf_slot_rows == 1 && !a.pf_part && !a.pf_wtab;
       if (a.stride < 1 || a.kind != VGPA_PATHS_MODEL || !a.R_diag || !known_model || (a.D > kMaxLaneD && a.model != VGPA_MODEL_L96)) return hipErrorInvalidValue;
       if (!a.pf_x || a.pf_n < 1 || a.k_begin < 0 || a.k_end < a.k_begin || cloud == members || a.logw || a.pf_lw || a.pf_stats) return hipErrorInvalidValue;
-      if (a.n_keep != (a.k_end - a.k_begin) / a.stride + 1 || sample_segment_blocks(a.D, a.n_paths) > 65535) return hipErrorInvalidValue;      // (grid.y)
+      if (a.n_keep != (a.k_end - a.k_begin) / a.stride + 1 || a.n_paths > sample_max_paths(a.D)) return hipErrorInvalidValue;
       return launch_walk<Walk::Forecast>(a, st);
     }
   }

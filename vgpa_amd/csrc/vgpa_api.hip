@@ -1471,6 +1471,26 @@ static int factor_rows(vgpa_ctx* c, const double* src, int n, double scale, cons
   return VGPA_OK;
 }
 
+// The lower factors of Sigma dt of the rows in force into a.R / R_stride / R_diag; a dense Sigma is the caller's to refuse
+static int factor_noise(vgpa_ctx* c, SampleArgs* a) {
+  const bool own_Sigma = !c->in.h_Sigma.empty();     // (the host copy of the rows in force)
+  Rows<double> R;
+  bool diag = true;
+  int rc;
+  if ((rc = factor_rows(c, own_Sigma ? c->in.h_Sigma.data() : c->h_sigma.data(), own_Sigma ? c->B : 1, c->cfg.dt, "noise matrix times dt",
+                        &c->d_sp_R, &c->sp_R_n, &R, &diag))) return rc;
+  a->R = R.rows; a->R_stride = R.stride; a->R_diag = diag ? 1 : 0;
+  return VGPA_OK;
+}
+
+// every one of the B x k slots lies in [0, n_paths); the caller's nouns: a "final slot" of a "trajectory", a "slot" of a "member"
+static int check_slots(vgpa_ctx* c, const int32_t* slots, int32_t k, int32_t n_paths, const char* slot, const char* of) {
+  for (size_t e = 0; e < (size_t)c->B * k; e++)
+    if (slots[e] < 0 || slots[e] >= n_paths)
+      return fail(c, VGPA_ERR_ARG, "problem %zu: %s %d of %s %zu does not lie in [0, %d)", e / k, slot, slots[e], of, e % k, n_paths);
+  return VGPA_OK;
+}
+
 // Euler-Maruyama paths of the posterior process or of the model SDE (see vgpa_hip.h), and -- logw set: vgpa_sample_paths_weighted,
 // DESIGN.md s.4.9 -- the weights of the posterior paths against the model SDE and the data, with `out` optional and every x_0 to `start`.  Reads x
 // and the inputs in force; of the cached state nothing is written.  The arguments have been checked by the entry points.
@@ -1489,13 +1509,11 @@ static int sample_args(vgpa_ctx* c, int kind, const double* x, const double* x0,
   a = SampleArgs{};
   a.kind = kind; a.model = c->cfg.model; a.D = D; a.Np = c->Np; a.batch = B; a.n_paths = n_paths; a.stride = stride;
   a.n_keep = (c->Np - 1) / stride + 1; a.dt = c->cfg.dt; a.seed = seed;
-  Rows<double> R, L0;
-  bool diag = true, l0_diag = true;
-  const bool own_Sigma = !c->in.h_Sigma.empty(), own_S0 = !c->in.h_S0.empty();     // (the host copies of the rows in force)
-  if ((rc = factor_rows(c, own_Sigma ? c->in.h_Sigma.data() : c->h_sigma.data(), own_Sigma ? B : 1, c->cfg.dt, "noise matrix times dt",
-                        &c->d_sp_R, &c->sp_R_n, &R, &diag))) return rc;
-  a.R = R.rows; a.R_stride = R.stride; a.R_diag = diag ? 1 : 0;
-  if (weighted && !diag) return fail(c, VGPA_ERR_UNSUPPORTED, "the weights of sampled paths are built for a diagonal Sigma (a dense Sigma is in force)");
+  Rows<double> L0;
+  bool l0_diag = true;
+  const bool own_S0 = !c->in.h_S0.empty();     // (the host copy of the rows in force)
+  if ((rc = factor_noise(c, &a))) return rc;
+  if (weighted && !a.R_diag) return fail(c, VGPA_ERR_UNSUPPORTED, "the weights of sampled paths are built for a diagonal Sigma (a dense Sigma is in force)");
   if (x0) {
     if ((rc = grow(c, &c->d_sp_x0, &c->sp_x0_n, (size_t)B * D))) return rc;
     if ((rc = upload(c, c->d_sp_x0, x0, (size_t)B * D))) return rc;
@@ -1600,6 +1618,8 @@ struct ParticleRun {
   int n_keep, rows, slot_rows, n_blocks; size_t mom_len, n_table, n_traj;
   int k0 = 0;                          // the forecast: the absolute grid index of the cloud
 
+  int buf(int which, size_t count) { return grow(c, &c->d_pf[which], &c->pf_n[which], count); }      // d_pf[which]: at least `count` doubles
+
   // For each cut -- an observation index of some problem, and the last grid index --: the segment launch up to it, then, at an
   // observation, the step between two segments (from cur to other), and the particle buffers swap.
   int cuts(Walk walk, const char* what, SampleArgs& s, const char* step_what, const std::function<hipError_t(int)>& step) {
@@ -1624,7 +1644,6 @@ struct ParticleRun {
     if ((rc = sample_args(c, VGPA_PATHS_POSTERIOR, q.x, q.x0, q.n_paths, 1, q.seed, true, &a))) return rc;
     const size_t n = (size_t)q.n_paths, BnD = (size_t)B * n * D, Bn = (size_t)B * n, BM = (size_t)B * M1;
     const bool history = q.ancestors || q.moments || q.covariance || q.paths;
-    auto buf = [&](int which, size_t count) { return grow(c, &c->d_pf[which], &c->pf_n[which], count); };
     auto ints = [](size_t count) { return (count + 1) / 2; };      // int32 entries in a buffer of doubles
     if ((rc = buf(vgpa_ctx::PF_XA, BnD)) || (rc = buf(vgpa_ctx::PF_XB, BnD)) || (rc = buf(vgpa_ctx::PF_LW, Bn)) || (rc = buf(vgpa_ctx::PF_CUM, Bn)) ||
         (rc = buf(vgpa_ctx::PF_ANC, ints(Bn))) || (rc = buf(vgpa_ctx::PF_ESS, BM)) || (rc = buf(vgpa_ctx::PF_FLAG, ints(BM)))) return rc;
@@ -1787,17 +1806,11 @@ struct ParticleRun {
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     a = SampleArgs{};
     a.model = c->cfg.model; a.D = D; a.Np = c->Np; a.batch = B; a.n_paths = q.n_paths; a.dt = c->cfg.dt; a.seed = q.seed;
-    Rows<double> R;
-    bool diag = true;
-    const bool own_Sigma = !c->in.h_Sigma.empty();
-    if ((rc = factor_rows(c, own_Sigma ? c->in.h_Sigma.data() : c->h_sigma.data(), own_Sigma ? B : 1, c->cfg.dt, "noise matrix times dt",
-                          &c->d_sp_R, &c->sp_R_n, &R, &diag))) return rc;
-    if (!diag) return fail(c, VGPA_ERR_UNSUPPORTED, "the particle forecast is built for a diagonal Sigma (a dense Sigma is in force)");
-    a.R = R.rows; a.R_stride = R.stride; a.R_diag = 1;
+    if ((rc = factor_noise(c, &a))) return rc;
+    if (!a.R_diag) return fail(c, VGPA_ERR_UNSUPPORTED, "the particle forecast is built for a diagonal Sigma (a dense Sigma is in force)");
     copy_theta(c, a.theta);
     a.theta_v = c->in.theta.rows;
     const size_t Bn = (size_t)B * q.n_paths;
-    auto buf = [&](int which, size_t count) { return grow(c, &c->d_pf[which], &c->pf_n[which], count); };
     if ((rc = buf(vgpa_ctx::PF_XA, Bn * D)) || (rc = buf(vgpa_ctx::PF_LW, Bn)) || (rc = buf(vgpa_ctx::PF_CUM, Bn))) return rc;
     f = PfArgs{};
     f.D = D; f.batch = B; f.n_paths = q.n_paths; f.M = 1; f.seed = q.seed;
@@ -1819,7 +1832,6 @@ struct ParticleRun {
     const size_t n = (size_t)q.n_paths, n_slots = (size_t)B * n_draw, n_mem = n_slots * h_keep * D, len = (size_t)h_keep * 2 * D;
     const int blocks = sample_segment_blocks(D, q.n_paths);
     int rc;
-    auto buf = [&](int which, size_t count) { return grow(c, &c->d_pf[which], &c->pf_n[which], count); };
     if ((rc = buf(vgpa_ctx::PF_WTAB, (size_t)B * n)) || (rc = buf(vgpa_ctx::PF_PART, (size_t)B * blocks * len)) || (rc = buf(vgpa_ctx::PF_MOM, (size_t)B * len))) return rc;
     SampleArgs w = SampleArgs{};      // the model's walk: of the filter's arguments the factors and theta
     w.kind = VGPA_PATHS_MODEL; w.model = a.model; w.D = D; w.Np = a.Np; w.batch = B; w.dt = a.dt; w.seed = q.seed;
@@ -1852,13 +1864,17 @@ struct ParticleRun {
   }
 };
 
-// vgpa_particle_forecast from a given cloud: no filter runs
-static int forecast_run(vgpa_ctx* c, const ParticleRequest& q) {
-  ParticleRun r{c, q};
-  int rc;
-  if ((rc = r.given_cloud()) || (rc = r.forecast())) return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return VGPA_OK;
+// Two limits the smoothers and the forecast share, in the caller's nouns.  check_sums: k_pf_moments_sum takes [B][kept][2][D] in one launch;
+// check_stored: k lanes per problem stored as vgpa_sample_paths stores them, [B][k][kept][D], are at most 2^35 entries
+static int check_sums(vgpa_ctx* c, int kept, const char* what, const char* points) {
+  if (pf_flat_grid_fits((size_t)c->B * ((size_t)kept * 2 * c->D))) return VGPA_OK;
+  return fail(c, VGPA_ERR_UNSUPPORTED, "the %s moments are built for at most 2^39 entries (batch %d, %d kept %s, D = %d): use a larger stride",
+              what, c->B, kept, points, c->D);
+}
+static int check_stored(vgpa_ctx* c, int k, int kept, const char* what, const char* lanes, const char* points) {
+  if ((double)c->B * (double)k * (double)kept * (double)c->D <= 34359738368.0) return VGPA_OK;
+  return fail(c, VGPA_ERR_UNSUPPORTED, "the %s are built for at most 2^35 entries (batch %d, %d %s, %d kept %s, D = %d): use a larger stride",
+              what, c->B, k, lanes, kept, points, c->D);
 }
 
 static int particle_run(vgpa_ctx* c, const ParticleRequest& q) {
@@ -1868,43 +1884,30 @@ static int particle_run(vgpa_ctx* c, const ParticleRequest& q) {
   if (q.with_stats && !q.stats && !q.mean) return fail(c, VGPA_ERR_ARG, "at least one of stats and mean must be given");
   const int32_t n_paths = q.n_paths, n_draw = q.n_draw, stride = q.stride;
   if (n_paths < 1) return fail(c, VGPA_ERR_ARG, "n_paths must be at least 1 (n_paths = %d)", n_paths);
-  if (q.paths && q.final_slots)
-    for (size_t e = 0; e < (size_t)c->B * n_draw; e++)
-      if (q.final_slots[e] < 0 || q.final_slots[e] >= n_paths)
-        return fail(c, VGPA_ERR_ARG, "problem %zu: final slot %d of trajectory %zu does not lie in [0, %d)", e / n_draw, q.final_slots[e], e % n_draw, n_paths);
+  int rc;
+  if (q.paths && q.final_slots && (rc = check_slots(c, q.final_slots, n_draw, n_paths, "final slot", "trajectory"))) return rc;
   if (!(q.ess_fraction >= 0.0 && q.ess_fraction <= 1.0)) return fail(c, VGPA_ERR_ARG, "ess_fraction must lie in [0, 1] (ess_fraction = %g)", q.ess_fraction);
   if ((q.prior_mu == nullptr) != (q.prior_tau == nullptr)) return fail(c, VGPA_ERR_ARG, "the prior is a mean and a covariance: both or neither");
   if (c->cfg.model == VGPA_MODEL_NONE) return fail(c, VGPA_ERR_ARG, "context has no stochastic model: no model SDE to weigh the particles against");
   if (!c->full) return fail(c, VGPA_ERR_STATE, "context was created without m0/s0/observations (ODE-only)");
   const int D = c->D, B = c->B, M = c->M, Np = c->Np;
-  if (q.moments && D <= kMaxSmallD) {      // the launch limits of the replay and of the final sum, before any work: grid.y of the segments, grid.x of the sum
-    if (sample_segment_blocks(D, n_paths) > 65535)
-      return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing moments are built for at most %d particles per problem at D = %d (n_paths = %d)",
-                  65535 * (D <= kMaxLaneD ? 256 : 64), D, n_paths);
-    if (((size_t)B * ((size_t)((Np - 1) / stride + 1) * 2 * D) + 255) / 256 > 0x7fffffffu)
-      return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing moments are built for at most 2^39 entries (batch %d, %d kept grid indices, D = %d): use a larger stride",
-                  B, (Np - 1) / stride + 1, D);
-  }
-  if (q.paths && D <= kMaxSmallD) {        // the launch limits of the lineage walk and the size of its result, before any work
-    if (!sample_lineages_fit(D, B, n_draw))
-      return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing trajectories are built for at most %d per problem at D = %d (n_draw = %d)", 65535 * 64, D, n_draw);
-    if (q.backward && !pf_backward_fits(n_draw))      // ... and of the backward simulation: grid.y of its one launch
-      return fail(c, VGPA_ERR_UNSUPPORTED, "backward simulation is built for at most %d trajectories per problem (n_draw = %d)", 65535 * kBackwardBlock, n_draw);
-    if ((double)B * (double)n_draw * (double)((Np - 1) / stride + 1) * (double)D > 34359738368.0)
-      return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing trajectories are built for at most 2^35 entries (batch %d, %d trajectories, %d kept grid indices, D = %d): use a larger stride",
-                  B, n_draw, (Np - 1) / stride + 1, D);
-  }
-  if (q.covariance && D <= kMaxSmallD) {   // ... of the covariance replay, of the sum of its packed partial sums and of the unpacking launch (grid.x each)
-    const size_t kept = (size_t)B * (size_t)((Np - 1) / stride + 1);
-    if (sample_segment_blocks(D, n_paths) > 65535)
-      return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing covariances are built for at most %d particles per problem at D = %d (n_paths = %d)",
-                  65535 * (D <= kMaxLaneD ? 256 : 64), D, n_paths);
-    if ((kept * D * D + 255) / 256 > 0x7fffffffu || (kept * sample_cov_len(D) + 255) / 256 > 0x7fffffffu)
+  const int kept = (Np - 1) / stride + 1;
+  if (D <= kMaxSmallD) {      // the launch limits and the sizes of the results, before any work
+    if ((q.moments || q.covariance) && n_paths > sample_max_paths(D))      // (the replay)
+      return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing %s are built for at most %d particles per problem at D = %d (n_paths = %d)",
+                  q.moments ? "moments" : "covariances", sample_max_paths(D), D, n_paths);
+    if (q.moments && (rc = check_sums(c, kept, "smoothing", "grid indices"))) return rc;
+    // (the sum of the covariance replay's packed partial sums and the unpacking launch)
+    if (q.covariance && !(pf_flat_grid_fits((size_t)B * kept * D * D) && pf_flat_grid_fits((size_t)B * kept * sample_cov_len(D))))
       return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing covariances are built for at most 2^39 - 256 entries (batch %d, %d kept grid indices, D = %d): use a larger stride",
-                  B, (Np - 1) / stride + 1, D);
+                  B, kept, D);
+    if (q.paths && !sample_lineages_fit(D, B, n_draw))      // (the lineage walk; the number is the matrix-core walk's, above D = 4)
+      return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing trajectories are built for at most %d per problem at D = %d (n_draw = %d)", sample_max_paths(kMaxSmallD), D, n_draw);
+    if (q.paths && q.backward && !pf_backward_fits(n_draw))      // (the one launch of the backward simulation)
+      return fail(c, VGPA_ERR_UNSUPPORTED, "backward simulation is built for at most %d trajectories per problem (n_draw = %d)", kMaxGridY * kBackwardBlock, n_draw);
+    if (q.paths && (rc = check_stored(c, n_draw, kept, "smoothing trajectories", "trajectories", "grid indices"))) return rc;
   }
   ParticleRun r{c, q};
-  int rc;
   if ((rc = r.setup()) || (rc = r.filter()) || ((q.moments || q.covariance) && (rc = r.moments())) ||
       (q.paths && (rc = q.backward ? r.backward_trajectories() : r.trajectories()))) return rc;
   const size_t n = (size_t)n_paths, BnD = (size_t)B * n * D;
@@ -2004,31 +2007,28 @@ int vgpa_particle_forecast(vgpa_ctx* c, const double* x, const double* x0, int32
   if (n_draw < 0) return fail(c, VGPA_ERR_ARG, "n_draw must be at least 0 (n_draw = %d)", n_draw);
   if (n_paths < 1) return fail(c, VGPA_ERR_ARG, "n_paths must be at least 1 (n_paths = %d)", n_paths);
   if (cloud && index0 < 0) return fail(c, VGPA_ERR_ARG, "index0 must be at least 0 (index0 = %d)", index0);
-  const int D = c->D, B = c->B;
+  const int D = c->D;
   const int64_t k0 = cloud ? (int64_t)index0 : (int64_t)c->Np - 1;
   // (the uniform of drawn slots comes from grid index k0 + 1, which must be one as well)
   if (k0 + (int64_t)horizon > 0x7fffffffLL || (n_draw > 0 && !final_slots && k0 + 1 > 0x7fffffffLL))
     return fail(c, VGPA_ERR_ARG, "the forecast ends beyond grid index 2^31 - 1 (it starts at %lld, horizon = %d)", (long long)k0, horizon);
-  if (n_draw > 0 && final_slots)
-    for (size_t e = 0; e < (size_t)B * n_draw; e++)
-      if (final_slots[e] < 0 || final_slots[e] >= n_paths)
-        return fail(c, VGPA_ERR_ARG, "problem %zu: slot %d of member %zu does not lie in [0, %d)", e / n_draw, final_slots[e], e % n_draw, n_paths);
+  int rc;
+  if (n_draw > 0 && final_slots && (rc = check_slots(c, final_slots, n_draw, n_paths, "slot", "member"))) return rc;
   if (D > kMaxSmallD) return fail(c, VGPA_ERR_UNSUPPORTED, "the particle forecast is built for D <= %d (D = %d)", kMaxSmallD, D);
   const int h_keep = horizon / stride + 1;      // the launch limits of the two walks and of the final sum, the size of the members: before any work
-  if (sample_segment_blocks(D, n_paths) > 65535 || sample_segment_blocks(D, n_draw) > 65535)
+  if (n_paths > sample_max_paths(D) || n_draw > sample_max_paths(D))
     return fail(c, VGPA_ERR_UNSUPPORTED, "the particle forecast is built for at most %d particles and members per problem at D = %d (n_paths = %d, n_draw = %d)",
-                65535 * (D <= kMaxLaneD ? 256 : 64), D, n_paths, n_draw);
-  if (((size_t)B * ((size_t)h_keep * 2 * D) + 255) / 256 > 0x7fffffffu)
-    return fail(c, VGPA_ERR_UNSUPPORTED, "the forecast moments are built for at most 2^39 entries (batch %d, %d kept steps, D = %d): use a larger stride", B, h_keep, D);
-  if ((double)B * (double)n_draw * (double)h_keep * (double)D > 34359738368.0)
-    return fail(c, VGPA_ERR_UNSUPPORTED, "the forecast members are built for at most 2^35 entries (batch %d, %d members, %d kept steps, D = %d): use a larger stride",
-                B, n_draw, h_keep, D);
+                sample_max_paths(D), D, n_paths, n_draw);
+  if ((rc = check_sums(c, h_keep, "forecast", "steps")) || (rc = check_stored(c, n_draw, h_keep, "forecast members", "members", "steps"))) return rc;
   ParticleRequest q{x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled};
   q.stride = stride; q.n_draw = n_draw; q.final_slots = final_slots; q.slots_out = slots;
   q.forecast = true; q.horizon = horizon; q.cloud = cloud; q.cloud_logw = cloud_logw; q.index0 = index0;
   q.fc_moments = moments; q.members = members; q.state_end = state_end;
-  if (cloud) return forecast_run(c, q);
-  return particle_run(c, q);
+  if (!cloud) return particle_run(c, q);
+  ParticleRun r{c, q};      // a given cloud: no filter runs
+  if ((rc = r.given_cloud()) || (rc = r.forecast())) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return VGPA_OK;
 }
 
 int vgpa_fetch(vgpa_ctx* c, int which, double* out) {

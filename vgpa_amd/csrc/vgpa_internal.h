@@ -242,9 +242,8 @@ struct SampleArgs {
   const double* L0;         // [D][D] lower factor of S0, or [B][D][D] with L0_stride = D*D
   size_t m0_stride, L0_stride;
   double* out;              // [B][n_paths][n_keep][D]
-  // importance weights of the posterior paths against the model SDE (vgpa_sample_paths_weighted), last so that the offsets
-  // above stay where they were.  Walk::Weighted reads them (posterior kind, diagonal R, theta / theta_v set): `out` may be nullptr (no
-  // path is stored), and every path's x_0 goes to `start`
+  // importance weights of the posterior paths against the model SDE (vgpa_sample_paths_weighted).  Walk::Weighted reads
+  // them (posterior kind, diagonal R, theta / theta_v set): `out` may be nullptr (no path is stored), and every path's x_0 goes to `start`
   double* logw;             // [B][n_paths][2]: the path term, the observation term; nullptr for every other walk
   double* start;            // [B][n_paths][D]
   const int64_t* obs_t;     // [M] grid indices, strictly increasing ([B][M] with obs_t_stride = M), as ObsArgs has them
@@ -269,9 +268,9 @@ struct SampleArgs {
   // the replay of vgpa_particle_moments: Walk::Replay is the walk of the segment without its weight sums (pf_lw is
   // not touched); at every kept grid index k = 0 mod stride of the segment (k = 0: the first segment) workgroup (p, blk) stores
   // sum_i W_i x_i(k) and sum_i W_i x_i(k)^2 over its own slots, W = the row of pf_wtab of the problem's stretch
-  union { const double* pf_wtab; const double* pf_clouds; };    // [B][pf_rows][n_paths] descendant weights; nullptr for every other walk (pf_clouds: Walk::Backward, below)
-  union { double* pf_part; const int32_t* pf_hanc; };           // [B][sample_segment_blocks()][n_keep][2][D]
-  union { int pf_rows; int pf_M; };
+  const double* pf_wtab;    // [B][pf_rows][n_paths] descendant weights; nullptr for every other walk
+  double* pf_part;          // [B][sample_segment_blocks()][n_keep][2][D]
+  int pf_rows, pf_M;        // rows per problem of pf_wtab; of Walk::Backward's histories (below)
   // Walk::Lineage (vgpa_particle_paths): the unweighted posterior walk of n_paths = K lanes
   // per problem, stored as vgpa_sample_paths stores it, in which lane m draws with the counter word pf_slots[p][j][m] while it is in
   // stretch j of its problem's own observation row (obs_t / n_obs as above): row 0 for the start, the next row behind every observation
@@ -290,16 +289,15 @@ struct SampleArgs {
   // Walk::Backward (vgpa_particle_backward_paths): Walk::Lineage, every field as there, in which lane m, having completed
   // and stored its problem's observation index t_j, goes on from pf_clouds[p][j][pf_hanc[p][j][pf_slots[p][j + 1][m]]]: the filter's
   // histories (rows of pf_M observations per problem; pf_n particles per cloud)
-  // They share the storage of three fields the lineage walks do not read (the unions above), so that the arguments keep their size and the
-  // other walks their code: pf_clouds [B][pf_M][pf_n][D] with pf_wtab, pf_hanc [B][pf_M][pf_n] with pf_part, pf_M with pf_rows.
+  const double* pf_clouds;  // [B][pf_M][pf_n][D]; nullptr for every other walk
+  const int32_t* pf_hanc;   // [B][pf_M][pf_n]; nullptr for every other walk
 };
-// (Walk::Backward's three fields are unions with fields of the replay: the arguments must keep the size every other walk was compiled for)
-static_assert(sizeof(SampleArgs) == 368, "SampleArgs has grown: see the unions of Walk::Backward");
 // hipErrorInvalidValue where a field the walk reads is missing or out of range, where a field that belongs to another walk is set, and for
 // D = 2 in every walk but Plain (no stochastic model has D = 2)
 hipError_t launch_sample_walk(Walk w, const SampleArgs& a, hipStream_t st);
 // workgroups per problem of a segment launch: the blocks of the replay's partial sums
 int sample_segment_blocks(int D, int n_paths);
+int sample_max_paths(int D);      // the largest n_paths per problem a segment, replay or forecast launch takes at this D (grid.y)
 // doubles per kept grid index of Walk::ReplayCov's partial sums: the mean and the packed lower triangle
 inline size_t sample_cov_len(int D) { return (size_t)D + (size_t)D * (D + 1) / 2; }
 
@@ -348,12 +346,13 @@ hipError_t launch_pf_gather(const PfArgs& a, hipStream_t st);
 hipError_t launch_pf_pick(const PfArgs& a, int Np, int K, int rows, int32_t* table, hipStream_t st);
 hipError_t launch_pf_trace(const PfArgs& a, int K, int rows, int32_t* table, hipStream_t st);
 bool sample_lineages_fit(int D, int batch, int K);
+bool pf_flat_grid_fits(size_t entries);      // grid.x takes one thread per entry, 256 per workgroup (k_pf_moments_sum, k_pf_cov_unpack, k_pf_trace)
 // vgpa_particle_backward_paths (sample.hip: k_pf_backward) in place of the trace: rows c-1 .. 0 of table by backward simulation.  f: the
 // histories h_flag, h_anc, h_clouds, h_lw with M, n_paths, seed and the observation rows; a: of the filter's arguments the model, theta,
 // A, b, the diagonal R and dt.  One launch: workgroup (p, blk) owns kBackwardBlock trajectories of problem p through all of its cuts
-constexpr int kBackwardBlock = 8;
+constexpr int kBackwardBlock = 8, kMaxGridY = 65535;
 hipError_t launch_pf_backward(const PfArgs& f, const SampleArgs& a, int K, int rows, int32_t* table, hipStream_t st);
-inline bool pf_backward_fits(int K) { return (K + kBackwardBlock - 1) / kBackwardBlock <= 65535; }      // (grid.y)
+inline bool pf_backward_fits(int K) { return (K + kBackwardBlock - 1) / kBackwardBlock <= kMaxGridY; }
 // vgpa_particle_forecast (sample.hip: k_pf_normalise): w [B][n_paths] = exp(lw - max lw) / the sum of these, per problem
 hipError_t launch_pf_normalise(int batch, int n_paths, const double* lw, double* w, hipStream_t st);
 // out [B][len] = sum over blk, in block order, of part [B][n_blocks][len]
