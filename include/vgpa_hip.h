@@ -420,6 +420,49 @@ int vgpa_particle_backward_paths(vgpa_ctx* ctx, const double* x_or_null, const d
                                  const double* prior_mu_or_null, const double* prior_tau_or_null, double* logw, double* state, double* paths,
                                  int32_t* slots_or_null, double* ess_or_null, int32_t* resampled_or_null);
 
+/* The conditional particle filter with ancestor sampling: one sweep of particle Gibbs (Andrieu, Doucet & Holenstein 2010;
+ * Lindsten, Jordan & Schoen 2014).  Given a reference trajectory per problem it returns a new trajectory whose law leaves the smoothing
+ * distribution of the Euler-discretised model invariant for any n_paths >= 2 and any proposal (A_t, b_t).  It is vgpa_particle_filter with
+ * the same seed and counters -- the stretches, t_j, c, the walk, the observation terms, ESS, the decision and lw_new are those -- but for:
+ *   start     slot 0 of every problem is x_0 = ref[p][0] (also with x0 given); its lw is the start's formula at that state (init evaluated at
+ *             ref[p][0] for a drawn start under a prior, else 0; minus c_p).  Slots 1 .. n-1 are the filter's
+ *   steps     slots >= 1: the filter's, the same counters and bits.  Slot 0 draws nothing.  At step k it holds x_{k-1} = ref[p][k-1]; with
+ *             g = -A_{k-1} x_{k-1} + b_{k-1} and f = f_theta(x_{k-1}) as every slot forms them, d = g - f, it takes the implied increment
+ *               eta* = (ref[p][k] - ref[p][k-1]) - dt g
+ *             in the place of R xi: lw_0 += -sum_i d_i (eta*_i + dt d_i / 2) / Sigma_ii, then the observation term at x = ref[p][k]; its
+ *             state becomes ref[p][k] as given, not as recomputed: slot 0 follows the reference bit for bit
+ *   at an observation j (k = t_j) where the cloud is resampled (ESS over all n slots, slot 0 included; k < Np-1):
+ *             slots i >= 1  multinomial: anc_i = min(#{m: cum_m <= u_i S}, n - 1), u_i the first uniform of Philox counter (k, i, p, 0xfffffffe),
+ *                           cum and S the filter's prefix sums.  (One forced slot of a systematic resampling is no valid conditional
+ *                           resampling -- Chopin & Singh 2015 --; independent draws are.)
+ *             slot 0        ancestor sampling against x~ = ref[p][k+1]: for every candidate i = 0 .. n-1, slot 0 itself included,
+ *                           b_i = lw_i - 1/2 sum_d ((x~_d - mu_i,d) / R_dd)^2, lw_i before the reset, mu_i = x_i + dt f(x_i; theta_p), R_dd the
+ *                           diagonal factor of Sigma_p dt (the device multiplies by 1 / R_dd); g_i = -log(-log u_i), u_i from Philox
+ *                           counter (k, 0, p, 0x40000000 | (i >> 1)): unit_open(r0, r1) for even i, unit_open(r2, r3) for odd i;
+ *                           anc_0 = the smallest i that attains max_i (b_i + g_i)
+ *             x_i <- x_{anc_i} for i >= 1; x_0 stays (the reference's state): anc_0 goes into the ancestors' history alone;
+ *             every lw_i <- max lw + log S - log n.  Where the cloud is carried on, anc is the identity
+ *   the trajectory  s_c = the final slot by the rule of vgpa_particle_paths with n_draw = 1 (U from counter (Np, 0, p, 0xffffffff)),
+ *             s_j = anc_j[s_{j+1}] where resampled, else s_{j+1}.  In stretch j with s_j != 0 the trajectory is the walk of
+ *             vgpa_particle_backward_paths on this run's clouds and ancestors (the start with counter word s_0; behind the completed
+ *             observation j-1 it goes on from clouds_{j-1}[anc_{j-1}[s_j]], the reference's state where that ancestor is slot 0); in a
+ *             stretch with s_j = 0 it is ref[p][k], copied
+ *   ref         host, [batch][Np][D]: the reference trajectory of every problem on the whole grid (stride 1)
+ *   trajectory  host, [batch][Np][D].  Bit for bit: trajectory[p][k] = ref[p][k] wherever the slot of k's stretch is 0;
+ *               trajectory[p][t_j] = clouds[p][j][s_j]; trajectory[p][Np-1] = state[p][s_c]; clouds[p][j][0] = ref[p][t_j]; with n_paths = 1
+ *               the trajectory is ref.  With ess_fraction = 0 state and logw of the slots >= 1 are vgpa_particle_filter's bit for bit.
+ *               Two calls with the same arguments give the same bits
+ *   slots_or_null  host int32, [batch][M+1]: s_j for j = 0 .. c; rows beyond a problem's own count + 1: -1
+ *   logw, state, ess_or_null, resampled_or_null, ancestors_or_null, clouds_or_null: as in vgpa_particle_filter, of this run
+ *   x_or_null, x0_or_null, n_paths, seed, ess_fraction, the prior: as in vgpa_particle_filter; with x NULL the cached state is read and not
+ *   written
+ * Errors and limits: those of vgpa_particle_paths with n_draw = 1 (D > 64 and a dense Sigma are VGPA_ERR_UNSUPPORTED, an ODE-only context
+ * VGPA_ERR_STATE, VGPA_MODEL_NONE VGPA_ERR_ARG), and VGPA_ERR_ARG for a NULL ref or trajectory.  The context stays usable. */
+int vgpa_particle_conditional(vgpa_ctx* ctx, const double* x_or_null, const double* x0_or_null, const double* ref, int32_t n_paths,
+                              uint64_t seed, double ess_fraction, const double* prior_mu_or_null, const double* prior_tau_or_null,
+                              double* logw, double* state, double* trajectory, int32_t* slots_or_null, double* ess_or_null,
+                              int32_t* resampled_or_null, int32_t* ancestors_or_null, double* clouds_or_null);
+
 /* The particle forecast: a weighted cloud carried past the window under the model SDE, with its mean and spread on the
  * forecast grid and a handful of member trajectories; the cloud never leaves the device between the filter and the forecast.
  * Per problem p: n = n_paths particles x_i with log-weights lw_i at the absolute grid index k0.

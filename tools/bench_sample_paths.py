@@ -10,6 +10,7 @@ Context.particle_covariance (vgpa_particle_covariance), Context.particle_paths (
     python tools/bench_sample_paths.py --covariance [--filter-problems 4096]      # the ac* and bc* jobs
     python tools/bench_sample_paths.py --paths [--filter-problems 4096] [--paths-strides 1,10]      # the ap* and bp* jobs, once per stride
     python tools/bench_sample_paths.py --backward [--filter-problems 4096] [--paths-strides 10] [--parent-json FILE]      # the ab* and bb* jobs
+    python tools/bench_sample_paths.py --gibbs [--filter-problems 4096]           # the ag* and bg* jobs
     python tools/bench_sample_paths.py --forecast [--forecast-problems 512] [--forecast-particles 4096] [--forecast-horizon 1000]
 
   a   posterior kind, Lorenz-96, D = 40, Np = 1001, B = 512:   64 paths per problem, stride 100
@@ -47,6 +48,15 @@ Context.particle_covariance (vgpa_particle_covariance), Context.particle_paths (
              over the problems) under backward simulation and under the genealogy.  --parent-json: the output of the parent commit's
              `--paths` run of the same jobs and strides on the same box (its own checkout and library, its processes alternating with
              this tool's): its particle_paths time is reported beside, as parent_paths_ms_per_call
+
+  ag<n>, bg<n>   (--gibbs selects all six) particle_conditional on the contexts of a and b: n = 16, 64 or 1024 particles per problem,
+             ess_fraction 0.5, the reference the trajectory of particle_paths(n, seed 2, n_draw 1), and particle_paths (one trajectory,
+             stride 1) and particle_filter with the same arguments, the three calls alternating inside every round: the three times,
+             the ratios, the share of the grid on which the sweep left the reference and how often the pinned slot's sampled ancestor
+             was another slot (from one more call with the histories, where they take at most 1 GiB on the host).  --parent-json: the
+             output of this tool, copied into the parent commit's checkout and run there with `--gibbs` on the same box (that checkout
+             has no particle_conditional: the job then times particle_filter and particle_paths alone), its processes alternating
+             with this tree's: the parent's two times are reported beside, as parent_filter_ms_per_call / parent_paths_ms_per_call
 
   --forecast   particle_forecast from a given cloud on a bare Lorenz-96 context (a model, theta, Sigma and dt: nothing evaluated), D = 40,
              B = 512, n = 4096 equally weighted particles, H = 1000 steps, no members, once with stride H (the sums at h = 0 and H alone)
@@ -89,6 +99,7 @@ MOMENTS = {f"{t}m{n}_{s}": (t, n, s) for t in "ab" for n in (64, 1024) for s in 
 COV = {f"{t}c{n}_{s}": (t, n, s) for t in "ab" for n in (64, 1024) for s in (1, 10, N_PTS + 3) if t == "b" or s > 1}          # job -> as MOMENTS
 PATHS = {f"{t}p{n}_{k}": (t, n, k) for t in "ab" for n in (64, 1024) for k in (16, 64)}           # job -> (context of, particles, trajectories)
 BACKWARD = {f"{t}b{n}_{k}": (t, n, k) for t in "ab" for n in (64, 1024) for k in (16, 64)}        # job -> as PATHS
+GIBBS = {f"{t}g{n}": (t, n) for t in "ab" for n in (16, 64, 1024)}                                # job -> (context of, particles)
 
 
 def tree():
@@ -165,10 +176,10 @@ def run(job, rounds, calls, numpy_problems, cache, filter_problems=0, paths_stri
     from bench_problem_batch import StreamTimer, make_contexts
     twin, stored = WEIGHTED.get(job, (job, True))
     weighted = job in WEIGHTED
-    if job in FILTER or job in STATS or job in MOMENTS or job in COV or job in PATHS or job in BACKWARD:
-        twin = (FILTER.get(job) or STATS.get(job) or MOMENTS.get(job) or COV.get(job) or PATHS.get(job) or BACKWARD[job])[0]
+    if job in FILTER or job in STATS or job in MOMENTS or job in COV or job in PATHS or job in BACKWARD or job in GIBBS:
+        twin = (FILTER.get(job) or STATS.get(job) or MOMENTS.get(job) or COV.get(job) or PATHS.get(job) or BACKWARD.get(job) or GIBBS[job])[0]
     name, d, B, kind, n_paths, stride = JOBS[twin]
-    if (job in FILTER or job in STATS or job in MOMENTS or job in COV or job in PATHS or job in BACKWARD) and twin == "b" and filter_problems:
+    if (job in FILTER or job in STATS or job in MOMENTS or job in COV or job in PATHS or job in BACKWARD or job in GIBBS) and twin == "b" and filter_problems:
         B = min(B, filter_problems)
     if (name, B) not in cache:                        # (b and c share a context)
         from helpers import SEED, build_problem
@@ -349,6 +360,60 @@ def run(job, rounds, calls, numpy_problems, cache, filter_problems=0, paths_stri
             out.update(parent_tree=row["tree"], parent_paths_ms_per_call=row["paths_ms_per_call"], parent_paths_rounds_ms=row["paths_rounds_ms"],
                        parent_filter_ms_per_call=row["filter_ms_per_call"], ratio_to_parent_paths=round(med["backward"] / row["paths_ms_per_call"], 4))
         return out
+    if job in GIBBS:
+        _, n_paths = GIBBS[job]
+        ref = np.ascontiguousarray(c.particle_paths(n_paths, 2, 1, ess_fraction=0.5)["paths"][:, 0])
+        calls_of = {"filter": lambda: c.particle_filter(n_paths, 1, ess_fraction=0.5),
+                    "paths": lambda: c.particle_paths(n_paths, 1, 1, ess_fraction=0.5),
+                    "conditional": lambda: c.particle_conditional(ref, n_paths, 1, ess_fraction=0.5)}
+        if not hasattr(c, "particle_conditional"):      # (this tool copied into a checkout without the entry point: the two calls it has)
+            del calls_of["conditional"]
+        res0 = {k: f() for k, f in calls_of.items()}      # warm-up (first-use allocations)
+        moved = other = None
+        flags = res0["filter"]["resampled"].astype(bool)
+        if "conditional" in calls_of:
+            got = res0["conditional"]
+            traj, table = got["trajectory"], got["slots"]
+            assert traj.shape == (B, N_PTS, d) and np.all(np.isfinite(traj))
+            assert np.array_equal(traj[:, -1], np.take_along_axis(got["state"], table[:, -1, None, None].astype(np.int64), axis=1)[:, 0])
+            moved = float(np.mean(np.any(traj != ref, axis=2)))
+            flags = got["resampled"].astype(bool)
+            # the ancestors of the pinned slot: one more call with the histories, where they are small (at 1024 particles the clouds alone
+            # are 8 to 13 GB of host memory: too much for one statistic)
+            if 8.0 * B * int(c.n_obs) * n_paths * (d + 1) <= 2.0 ** 30:
+                anc = c.particle_conditional(ref, n_paths, 1, ess_fraction=0.5, history=True)["ancestors"]
+                other = float(np.mean(anc[:, :, 0][flags] != 0)) if flags.any() else 0.0
+                del anc
+            del got, traj
+        del res0["paths"]["paths"]
+        per_round = {k: [] for k in calls_of}
+        for _ in range(rounds):
+            ms = {k: [] for k in calls_of}
+            for _ in range(calls):
+                for k, f in calls_of.items():
+                    ms[k].append(tm.ms(f))
+            for k in calls_of:
+                per_round[k].append(float(np.median(ms[k])))
+        med = {k: float(np.median(v)) for k, v in per_round.items()}
+        out = {"job": job, "model": name, "D": d, "Np": N_PTS, "B": B, "kind": "gibbs", "n_paths": n_paths, "ess_fraction": 0.5, "stride": 1,
+               "paths_ms_per_call": round(med["paths"], 4), "filter_ms_per_call": round(med["filter"], 4),
+               "paths_rounds_ms": [round(v, 4) for v in per_round["paths"]], "filter_rounds_ms": [round(v, 4) for v in per_round["filter"]],
+               "observations": int(c.n_obs), "resampled_share": round(float(flags.mean()), 3),
+               "filter_resampled_share": round(float(res0["filter"]["resampled"].mean()), 3),
+               "filter_d2h_mb": round(8.0 * B * n_paths * (1 + d) / 1e6, 1), "paths_d2h_mb": round(8.0 * B * (n_paths * (1 + d) + N_PTS * d) / 1e6, 1)}
+        if "conditional" in calls_of:
+            out.update(conditional_ms_per_call=round(med["conditional"], 4), conditional_rounds_ms=[round(v, 4) for v in per_round["conditional"]],
+                       ratio_to_paths=round(med["conditional"] / med["paths"], 4), ratio_to_filter=round(med["conditional"] / med["filter"], 4),
+                       share_of_grid_renewed=round(moved, 4), pinned_ancestor_other_slot_share=None if other is None else round(other, 4),
+                       up_mb=round(8.0 * B * N_PTS * d / 1e6, 1), d2h_mb=round(8.0 * B * (n_paths * (1 + d) + N_PTS * d) / 1e6, 1))
+        row = (parent or {}).get((job, 1))
+        if row:
+            out.update(parent_tree=row["tree"], parent_filter_ms_per_call=row["filter_ms_per_call"], parent_paths_ms_per_call=row["paths_ms_per_call"],
+                       parent_filter_rounds_ms=row["filter_rounds_ms"], parent_paths_rounds_ms=row["paths_rounds_ms"])
+            if "conditional" in calls_of:
+                out.update(ratio_to_parent_filter=round(med["conditional"] / row["filter_ms_per_call"], 4),
+                           ratio_to_parent_paths=round(med["conditional"] / row["paths_ms_per_call"], 4))
+        return out
     if job in FILTER:
         _, n_paths, frac = FILTER[job]
         call = lambda: c.particle_filter(n_paths, 1, ess_fraction=frac)      # noqa: E731
@@ -399,6 +464,7 @@ def main():
     ap.add_argument("--paths", action="store_true", help="run the ap* and bp* jobs (particle_paths beside particle_filter)")
     ap.add_argument("--paths-strides", default="1,10", help="strides of the ap* and bp* jobs: each job runs once per stride")
     ap.add_argument("--backward", action="store_true", help="run the ab* and bb* jobs (particle_backward_paths beside particle_paths and particle_filter)")
+    ap.add_argument("--gibbs", action="store_true", help="run the ag* and bg* jobs (particle_conditional beside particle_paths and particle_filter)")
     ap.add_argument("--parent-json", default="", help="output of the parent commit's --paths run of the same jobs: its times are reported beside")
     ap.add_argument("--forecast", action="store_true", help="run the forecast job (particle_forecast from a given cloud beside the model-kind sampler)")
     ap.add_argument("--forecast-problems", type=int, default=512)
@@ -420,6 +486,8 @@ def main():
         args.jobs = ",".join(sorted(PATHS))
     if args.backward and args.jobs == "a,b,c":
         args.jobs = ",".join(sorted(BACKWARD))
+    if args.gibbs and args.jobs == "a,b,c":
+        args.jobs = ",".join(sorted(GIBBS))
     parent = {}
     if args.parent_json:      # (one JSON line per run of the parent's tool; a later run of a job replaces an earlier one)
         with open(args.parent_json) as fh:

@@ -36,7 +36,7 @@ BWD_IDS = {"none": 0, "psi": 1, "q": 2}
 SYMBOLS = ["vgpa_create", "vgpa_destroy", "vgpa_last_error", "vgpa_abi_version", "vgpa_device_count",
            "vgpa_synchronize", "vgpa_stream", "vgpa_solve_fwd", "vgpa_solve_bwd", "vgpa_energy",
            "vgpa_obs_energy", "vgpa_free_energy", "vgpa_gradient", "vgpa_sweep", "vgpa_energy_parts",
-           "vgpa_fetch", "vgpa_theta_gradient", "vgpa_sample_paths", "vgpa_sample_paths_weighted", "vgpa_particle_filter", "vgpa_particle_statistics", "vgpa_particle_moments", "vgpa_particle_covariance", "vgpa_particle_paths", "vgpa_particle_backward_paths", "vgpa_particle_forecast", "vgpa_sweep_dev", "vgpa_free_energy_dev", "vgpa_sweep_enqueue", "vgpa_fetch_f",
+           "vgpa_fetch", "vgpa_theta_gradient", "vgpa_sample_paths", "vgpa_sample_paths_weighted", "vgpa_particle_filter", "vgpa_particle_statistics", "vgpa_particle_moments", "vgpa_particle_covariance", "vgpa_particle_paths", "vgpa_particle_backward_paths", "vgpa_particle_conditional", "vgpa_particle_forecast", "vgpa_sweep_dev", "vgpa_free_energy_dev", "vgpa_sweep_enqueue", "vgpa_fetch_f",
            "vgpa_dev_alloc", "vgpa_dev_free", "vgpa_memcpy_h2d", "vgpa_memcpy_d2h",
            "vgpa_profile_begin", "vgpa_profile_end", "vgpa_ld_gemm", "vgpa_ld_stage", "vgpa_gradient_dev", "vgpa_energy_full", "vgpa_set_option", "vgpa_is_streaming", "vgpa_path_info", "vgpa_set_prior_energy",
            "vgpa_set_problem_data", "vgpa_set_problem_params", "vgpa_set_problem_obs_model",
@@ -151,6 +151,8 @@ def load():
     lib.vgpa_particle_paths.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_uint64, c_double, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vgpa_particle_backward_paths.argtypes = lib.vgpa_particle_paths.argtypes
+    lib.vgpa_particle_conditional.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_uint64, c_double, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vgpa_particle_forecast.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_uint64, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                                            c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_void_p]
@@ -726,6 +728,34 @@ class Context:
         self._check(entry(self._h, _ptr(xx), _ptr(s0), n_paths, n_draw, _ptr(given), stride, int(seed) & 0xFFFFFFFFFFFFFFFF, float(ess_fraction),
                           _ptr(mu), _ptr(tau), _ptr(log_w), _ptr(state), _ptr(paths), _ptr(table), _ptr(ess), _ptr(flags)))
         return {"log_w": log_w, "state": state, "ess": ess, "resampled": flags, "paths": paths, "slots": table}
+
+    def particle_conditional(self, ref, n_paths, seed, ess_fraction=0.5, x=None, x0=None, prior=None, history=False):
+        """One sweep of particle Gibbs with ancestor sampling (vgpa_particle_conditional): particle_filter with slot 0 of every problem pinned
+        to the reference trajectory ref (B, Np, D) (or (Np, D), shared) and weighted like any other slot, multinomial resampling, and the
+        ancestor of the pinned slot drawn anew at every resampling.  Returns a dict: log_w, state, ess, resampled (and, history=True,
+        ancestors and clouds) as particle_filter, of this run; trajectory (B, Np, D): the drawn trajectory, the next reference; slots
+        (B, M + 1) int32: the slot it sat in during every stretch (0: that stretch is the reference's; -1 beyond a problem's count + 1)."""
+        n_paths, m = int(n_paths), self.n_obs
+        self._fit32(n_paths=n_paths)
+        xx, s0, mu, tau = self._walk_inputs(x, x0, prior)
+        if ref is None:
+            rr = None
+        else:
+            rr = np.asarray(ref, dtype=np.float64)
+            if rr.size not in (self.Np * self.D, self.B * self.Np * self.D):
+                raise ValueError(f"ref has {rr.size} entries, expected {self.B} x {self.Np} x {self.D}")
+            rr = _c64(np.broadcast_to(rr.reshape(-1, self.Np, self.D), (self.B, self.Np, self.D)))
+        n = max(n_paths, 0)
+        log_w, state, ess, flags = self._filter_outputs(n)
+        traj = np.empty((self.B, self.Np, self.D))
+        table = np.full((self.B, m + 1), -1, dtype=np.int32)
+        anc = np.full((self.B, m, n), -1, dtype=np.int32) if history else None
+        clouds = np.full((self.B, m, n, self.D), np.nan) if history else None
+        self._check(self._lib.vgpa_particle_conditional(self._h, _ptr(xx), _ptr(s0), _ptr(rr), n_paths, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                        float(ess_fraction), _ptr(mu), _ptr(tau), _ptr(log_w), _ptr(state), _ptr(traj),
+                                                        _ptr(table), _ptr(ess), _ptr(flags), _ptr(anc), _ptr(clouds)))
+        return {"log_w": log_w, "state": state, "ess": ess, "resampled": flags, "ancestors": anc, "clouds": clouds, "trajectory": traj,
+                "slots": table}
 
     def particle_forecast(self, horizon, n_paths=None, seed=0, stride=1, n_draw=0, ess_fraction=0.5, x=None, x0=None, cloud=None, log_w=None,
                           index0=None, slots=None, prior=None):

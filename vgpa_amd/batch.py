@@ -328,6 +328,54 @@ class ProblemBatch(object):
             trace[key] = np.asarray(trace[key])
         return self._theta_rows(), trace
 
+    def particle_gibbs(self, n_paths, seed, iters, burn=0, thin=1, ess_fraction=0.5, sample_theta=True, theta_prior=None, x=None):
+        """
+        Particle Gibbs with ancestor sampling: the posterior of theta jointly with the path, one particles.GibbsChain per member -- B
+        chains in one context, each member's chain independent of the rest (its draws depend on the seed and its own index alone).
+        Iteration 0 takes its reference from particle_paths(n_paths, seed, n_draw=1).  Iteration i: (1) Context.particle_conditional at the
+        current theta from the current trajectory, with seed + 1 + i; (2) sample_theta=True: theta' ~ N(theta + s / I, 1 / I) given the new
+        trajectory (particles.theta_conditional; theta_prior: None, flat, or (mean, precision) per component), its normals from
+        numpy.random.Generator(PCG64([seed, i, member])) (particles.theta_draw), written to the member's model.theta as
+        particle_fit_theta writes it (the models' own checks apply and nothing is clipped: where a short window says little, a prior keeps
+        the draws admissible).  The trajectories of the iterations burn, burn + thin, ... are kept.
+        (A_t, b_t) stay fixed at x (B, len_x) -- by default the point the last optimise() returned, else initialization() --: they are
+        the proposal, not the model.  The chain is exact for the Euler-discretised model whatever the proposal and for any n_paths >= 2;
+        a better proposal and more particles make it mix faster.
+        """
+        from .particles import GibbsChain, theta_conditional, theta_draw
+        if self.B > 1 and sample_theta and not self.own_parameters:
+            raise ValueError(" ProblemBatch.particle_gibbs: the members of a batch that shares one theta cannot each draw their own "
+                             "(own_parameters=True, or sample_theta=False).")
+        iters, burn, thin, seed = int(iters), int(burn), int(thin), int(seed)
+        if iters < 1 or burn < 0 or thin < 1:
+            raise ValueError(" ProblemBatch.particle_gibbs: iters and thin must be at least 1, burn at least 0.")
+        xx = (self.initialization() if self._x is None else self._x.copy()) if x is None else self._stack(x).copy()
+        d, v0 = self.dim_d, self.vgps[0]
+        prior = (np.stack([v._prior()[0][0] for v in self.vgps]), np.stack([v._prior()[1][0] for v in self.vgps]).reshape(self.B, d, d))
+        dt, model = float(v0.fwd_ode.dt), v0.model._model_id
+        first = self._context().particle_paths(n_paths, seed, 1, ess_fraction=ess_fraction, x=xx, prior=prior)["paths"][:, 0]
+        ref = np.ascontiguousarray(first)
+        theta, moved, kept, paths = [self._theta_rows()], [], [], []
+        for it in range(iters):
+            res = self._context().particle_conditional(ref, n_paths, seed + 1 + it, ess_fraction=ess_fraction, x=xx, prior=prior)
+            new = res["trajectory"]
+            moved.append(np.mean(np.any(new != ref, axis=2), axis=1))
+            ref = new
+            if it >= burn and (it - burn) % thin == 0:
+                kept.append(it)
+                paths.append(new.copy())
+            rows = self._theta_rows()
+            if sample_theta:
+                for k, vgp in enumerate(self.vgps):
+                    sig = np.asarray(vgp._inputs()["sigma"], dtype=float).reshape(d, d).diagonal()
+                    mean, prec = theta_conditional(model, rows[k], new[k], dt, sig, theta_prior)
+                    row = theta_draw(mean, prec, seed, it, k)
+                    vgp.model.theta = float(row[0]) if row.size == 1 else row.copy()
+            theta.append(self._theta_rows())
+        theta, moved = np.asarray(theta), np.asarray(moved)
+        stack = np.asarray(paths).reshape(len(kept), self.B, self.dim_n, d)
+        return [GibbsChain(theta[:, k], stack[:, k], kept, moved[:, k], first[k], v.model.single_dim) for k, v in enumerate(self.vgps)]
+
     def _theta_rows(self):
         return np.stack([np.atleast_1d(np.asarray(v.model.theta, dtype=float)) for v in self.vgps])
 

@@ -37,6 +37,9 @@
 //   Backward     | the lineage walk of a table that backward simulation has drawn: behind every observation of its problem the lane | s.4.17
 //                | goes on from the filter's stored particle its next slot was copied from  [k_pf_backward draws the table in the   |
 //                | trace's place: at every resampled observation a Gumbel-max draw among all n particles of the stored cloud]       |
+//   Conditional  | a segment in which slot 0 of every problem is pinned to a reference trajectory: it draws nothing, is weighted by | s.4.18
+//                | the increment the reference implies and follows the reference bit for bit  [k_pf_pin: slot 0 of the start;       |
+//                | k_pf_cresample: the step between two segments, multinomial, with ancestor sampling for slot 0; k_pf_ref_fill]    |
 #include "vgpa_internal.h"
 
 #include <type_traits>
@@ -147,13 +150,22 @@ __device__ __forceinline__ double wave_max(double v) {
   return v;
 }
 
+// What a walk's kernels take: SampleArgs, and for Conditional alone the reference trajectories behind it -- no other walk's arguments,
+// registers or code know of the pointer.
+struct ConditionalArgs : SampleArgs {
+  const double* pf_ref;      // [B][Np][D]
+};
+template <Walk K> struct WalkArgsOf { using type = SampleArgs; };
+template <> struct WalkArgsOf<Walk::Conditional> { using type = ConditionalArgs; };
+template <Walk K> using WalkArgs = typename WalkArgsOf<K>::type;
+
 // What the two kernels branch on, per walk: W the walk of the weighted kind (posterior drift, diagonal R), SEG it runs (k_begin, k_end] from
 // and to pf_x, ST it carries the rows of pf_stats, MO it takes the moments of the replay, LN the counter words come from pf_slots;
 // FC it is the forecast (the model's drift from the cloud in pf_x, k_sample_small only); CV the replay's second moments are the whole matrix
-// (with MO); BW: the state is reloaded from the filter's histories behind every observation (with LN); WS: the weight sums are formed.  The
-// nine rows are all there is: no other combination can be instantiated.
+// (with MO); BW: the state is reloaded from the filter's histories behind every observation (with LN); CD: slot 0 is pinned to pf_ref of
+// ConditionalArgs (with SEG); WS: the weight sums are formed.  The ten rows are all there is: no other combination can be instantiated.
 struct WalkTraits {
-  bool W, SEG, ST, MO, LN, FC, CV, BW;
+  bool W, SEG, ST, MO, LN, FC, CV, BW, CD;
   constexpr bool WS() const { return W && !MO; }
 };
 constexpr WalkTraits kWalkTraits[] = {      // in the order of Walk
@@ -165,7 +177,8 @@ constexpr WalkTraits kWalkTraits[] = {      // in the order of Walk
     {false, false, false, false, true,  false},    // Lineage
     {false, false, false, false, false, true},     // Forecast
     {true,  true,  false, true,  false, false, true},     // ReplayCov
-    {false, false, false, false, true,  false, false, true}};    // Backward
+    {false, false, false, false, true,  false, false, true},     // Backward
+    {true,  true,  false, false, false, false, false, false, true}};    // Conditional
 
 // Weighted: posterior kind, diagonal R: both drifts at x_{k-1}, d = g - f, and per step -sum_i d_i (eta_i + dt d_i / 2) / Sigma_ii with
 // 1 / Sigma_ii = dt / R_ii^2; the observation term at the lane's own problem's times.
@@ -189,6 +202,9 @@ constexpr WalkTraits kWalkTraits[] = {      // in the order of Walk
 // replay's sums with W = pf_wtab at h = 0, stride, ..., the end state back to pf_x.  The member launch (out, pf_slots set): lane m starts from
 // slot pf_slots[p][m], draws with that slot's word and stores as Plain stores.  A lane behind the last one walks the last one again with
 // weight 0 and stores nothing.
+// Conditional: a segment in which the lane of slot 0 holds x_{k-1} = pf_ref[p][k-1] bit for bit, draws nothing and puts
+// eta* = (ref_k - x_{k-1}) - dt g(x_{k-1}) where the other lanes put R xi: the step term, the observation term and the sums are the segment's; its
+// state becomes ref_k as loaded (D loads per step for that one lane).  Every other lane is the segment's, bit for bit.
 // Walk::Backward: x = the particle slot `word` was copied from at observation j of problem p
 template <int D>
 __device__ __forceinline__ void backward_reload(const SampleArgs& a, uint32_t p, int j, uint32_t word, double* x) {
@@ -199,9 +215,9 @@ __device__ __forceinline__ void backward_reload(const SampleArgs& a, uint32_t p,
 }
 
 template <int D, Walk K>
-__global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
+__global__ __launch_bounds__(256) void k_sample_small(WalkArgs<K> a) {
   constexpr WalkTraits T = kWalkTraits[(int)K];
-  constexpr bool W = T.W, SEG = T.SEG, ST = T.ST, MO = T.MO, LN = T.LN, FC = T.FC, CV = T.CV, BW = T.BW, WS = T.WS();
+  constexpr bool W = T.W, SEG = T.SEG, ST = T.ST, MO = T.MO, LN = T.LN, FC = T.FC, CV = T.CV, BW = T.BW, CD = T.CD, WS = T.WS();
   constexpr int NV = CV ? D + D * (D + 1) / 2 : 2 * D;      // values a kept k reduces
   size_t gid;
   uint32_t p, path;
@@ -346,6 +362,9 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
   int until = a.stride, slot = 0;
   // (the forecast counts its steps from 0: k_begin + h may be the last index an int holds)
   const int k_first = FC ? 0 : SEG ? a.k_begin + 1 : 1, k_stop = FC ? a.k_end - a.k_begin : SEG ? a.k_end + 1 : a.Np;
+  bool pin = false;      // Conditional: the lane of slot 0
+  const double* ref = nullptr;
+  if constexpr (CD) { pin = path == 0; ref = a.pf_ref + (size_t)p * a.Np * D; }
   for (int k = k_first; k < k_stop; k++) {
     double f[D], fm[D];
     if constexpr (WS) model_drift<D>(a.model, th, x, fm);
@@ -362,20 +381,29 @@ __global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
     } else {
       model_drift<D>(a.model, th, x, f);
     }
+    double xr[CD ? D : 1];      // Conditional: ref_k of the pinned lane
+    if constexpr (CD) {
 #pragma unroll
-    for (int j = 0; j < NP; j++) normal_pair(k0, k1, FC ? (uint32_t)a.k_begin + (uint32_t)k + 1u : (uint32_t)k, word, p, (uint32_t)j, &z[2 * j], &z[2 * j + 1]);
+      for (int i = 0; i < D; i++) { xr[i] = pin ? ref[(size_t)k * D + i] : 0.0; z[i] = 0.0; }
+    }
+    if (!CD || !pin) {
+#pragma unroll
+      for (int j = 0; j < NP; j++) normal_pair(k0, k1, FC ? (uint32_t)a.k_begin + (uint32_t)k + 1u : (uint32_t)k, word, p, (uint32_t)j, &z[2 * j], &z[2 * j + 1]);
+    }
     if constexpr (ST) model_phi<D>(a.model, x, phi);
 #pragma unroll
     for (int i = 0; i < D; i++) {
       double s = 0.0;
 #pragma unroll
       for (int j = 0; j <= i; j++) s += R[i * D + j] * z[j];
+      if constexpr (CD) { if (pin) s = (xr[i] - x[i]) - a.dt * f[i]; }      // the increment the reference implies, in R xi's place
       if constexpr (WS) { const double d = f[i] - fm[i]; pw -= isg[i] * d * (s + 0.5 * a.dt * d); }
       if constexpr (ST) {
         const double r = a.dt * (f[i] - fm[i]) + s;
         sq[i] += r * r / a.dt; sg1[i] += phi[i] * r; sh[i] += a.dt * (phi[i] * phi[i]);
       }
       x[i] = (x[i] + a.dt * f[i]) + s;
+      if constexpr (CD) { if (pin) x[i] = xr[i]; }      // (as loaded, not as recomputed)
     }
     if constexpr (WS) {
       if (k == oc.next) { ow += obs_form<D>(a, p, oc.cur, x); oc.advance(); }
@@ -485,10 +513,13 @@ __device__ __forceinline__ void normals_c(uint32_t k0, uint32_t k1, uint32_t k, 
 // behind the same steps.  A lane behind the last lineage walks the last one again and stores nothing.
 // Backward: as in k_sample_small; the reload is a gather of the lane's own rows of its path's new particle into the accumulator layout, which
 // then goes to Xs as every step's result does, behind the store of the completed observation's point and in front of one more barrier.
+// Conditional: as in k_sample_small.  Slot 0 is path column 0 of wave 0 of workgroup (p, 0): its four lanes request their rows of ref_k
+// with the step's A_k, put eta* into nz before the weight term is formed and ref_k into x before the step's own write of x to Xs -- no
+// barrier is added, and the model drift of the next step reads the reference from the column of Xs as it reads every other path.
 template <int NT, Walk K>
-__global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
+__global__ __launch_bounds__(256) void k_sample_mfma(WalkArgs<K> a) {
   constexpr WalkTraits T = kWalkTraits[(int)K];
-  constexpr bool W = T.W, SEG = T.SEG, ST = T.ST, MO = T.MO, LN = T.LN, CV = T.CV, BW = T.BW, WS = T.WS();
+  constexpr bool W = T.W, SEG = T.SEG, ST = T.ST, MO = T.MO, LN = T.LN, CV = T.CV, BW = T.BW, CD = T.CD, WS = T.WS();
   using Sh = MfmaShape<NT>;
   constexpr int LDA = Sh::LDA, MT = Sh::MT, KT = Sh::KT, NPF = Sh::NPF;
   extern __shared__ double lds[];
@@ -757,10 +788,24 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
   if constexpr (CV) { if (a.seg_first) reduce_cov(0); }
 
   int until = a.stride;
+  // Conditional: the four lanes that hold the rows of slot 0 (workgroup (p, 0), wave 0, path column 0)
+  bool pin = false;
+  const double* ref = nullptr;
+  if constexpr (CD) { pin = path == 0; ref = a.pf_ref + (size_t)p * a.Np * D; }
   for (int k = k_first; k < k_stop; k++) {
     // A_k, b_k for the next step: requested now, written to LDS behind this step's products
     double pa[NPF], pb = 0.0;
     const bool more = k + 1 < k_stop;
+    double xref[CD ? MT : 1][4];      // Conditional: the pinned lanes' rows of ref_k, requested now as well
+    if constexpr (CD) {
+#pragma unroll
+      for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+          const int row = mt * 16 + q + 4 * r;
+          xref[mt][r] = pin && row < D ? ref[(size_t)k * D + row] : 0.0;
+        }
+    }
     if (more) {
       const double* Ak = A + (size_t)k * DD;
 #pragma unroll
@@ -795,6 +840,12 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
 #pragma unroll
         for (int kk = 0; kk < KT; kk++) nz = __builtin_amdgcn_mfma_f64_16x16x4f64(rr[kk * 4], Zs[(kk * 4 + q) * 16 + j16], nz, 0, 0, 0);
       }
+      if constexpr (CD) {      // the increment the reference implies, in R xi's place (rows beyond D: 0 - 0)
+        if (pin) {
+#pragma unroll
+          for (int r = 0; r < 4; r++) nz[r] = (xref[mt][r] - x[mt][r]) - a.dt * (bs[mt * 16 + q + 4 * r] - acc[r]);
+        }
+      }
       if constexpr (WS) {
 #pragma unroll
         for (int r = 0; r < 4; r++) {
@@ -818,6 +869,12 @@ __global__ __launch_bounds__(256) void k_sample_mfma(SampleArgs a) {
       }
 #pragma unroll
       for (int r = 0; r < 4; r++) x[mt][r] = (x[mt][r] + a.dt * (bs[mt * 16 + q + 4 * r] - acc[r])) + nz[r];
+      if constexpr (CD) {      // (ref_k as loaded, not as recomputed; it goes to Xs with every lane's rows below)
+        if (pin) {
+#pragma unroll
+          for (int r = 0; r < 4; r++) x[mt][r] = xref[mt][r];
+        }
+      }
     }
     __syncthreads();
     if constexpr (MO && !CV) flush();
@@ -1068,6 +1125,41 @@ __global__ __launch_bounds__(256) void k_pf_start(PfArgs a) {
       }
       init = (-0.5 * q1 - ld1) - (-0.5 * q0 - ld0);
     }
+  }
+  a.lw[gid] = init - a.obs_const_scale * (a.obs_const_v ? a.obs_const_v[p] : a.obs_const);
+}
+
+// vgpa_particle_conditional, behind k_pf_start: one thread per problem pins slot 0 to ref[p][0] and gives it k_pf_start's own log-weight
+// at that state -- the same two triangular solves, x_0 - m0 in place of the drawn normals.
+__global__ __launch_bounds__(256) void k_pf_pin(PfArgs a) {
+  const uint32_t p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= (uint32_t)a.batch) return;
+  const int D = a.D;
+  const size_t gid = (size_t)p * a.n_paths;
+  const double* xr = a.ref + (size_t)p * a.Np * D;
+  double* x = a.x + gid * D;
+  double* u = a.ws + gid * D;
+  for (int i = 0; i < D; i++) x[i] = xr[i];
+  double init = 0.0;
+  if (!a.x0 && a.mu0) {
+    const double* m0 = a.m0 + (size_t)p * a.m0_stride;
+    const double* L0 = a.L0 + (size_t)p * a.L0_stride;
+    const double* mu = a.mu0 + (size_t)p * D;
+    const double* Lt = a.Lt + (size_t)p * D * D;
+    double q0 = 0.0, ld0 = 0.0, q1 = 0.0, ld1 = 0.0;
+    for (int i = 0; i < D; i++) {
+      double s = x[i] - m0[i];
+      for (int j = 0; j < i; j++) s -= L0[i * D + j] * u[j];
+      u[i] = s / L0[i * D + i];
+      q0 += u[i] * u[i]; ld0 += log(L0[i * D + i]);
+    }
+    for (int i = 0; i < D; i++) {
+      double s = x[i] - mu[i];
+      for (int j = 0; j < i; j++) s -= Lt[i * D + j] * u[j];
+      u[i] = s / Lt[i * D + i];
+      q1 += u[i] * u[i]; ld1 += log(Lt[i * D + i]);
+    }
+    init = (-0.5 * q1 - ld1) - (-0.5 * q0 - ld0);
   }
   a.lw[gid] = init - a.obs_const_scale * (a.obs_const_v ? a.obs_const_v[p] : a.obs_const);
 }
@@ -1382,6 +1474,11 @@ __global__ __launch_bounds__(256) void k_pf_trace(PfArgs a, int K, int rows, int
   }
 }
 
+// What the two Gumbel-max draws share (k_pf_backward, k_pf_cresample): the score of a candidate with log-weight lw, quadratic form `quad` of its
+// transition density and uniform u; and whether (score, slot) beats the best so far -- the larger score, of equal scores the smaller slot.
+__device__ __forceinline__ double pf_gumbel_score(double lw, double quad, double u) { return (lw - 0.5 * quad) + -log(-log(u)); }
+__device__ __forceinline__ bool pf_beats(double sc, int slot, double best, int bslot) { return sc > best || (sc == best && slot < bslot); }
+
 // ---- backward simulation: the slot table of vgpa_particle_backward_paths, in the trace's place -------------------------
 // Workgroup (p, blk) owns the kBackwardBlock trajectories m = blk kBackwardBlock + mm of problem p and walks that problem's cuts
 // j = c-1 .. 0 itself: one launch, nothing between workgroups.  Where the cloud was carried on, row j of the table is row j + 1.  Where it
@@ -1500,8 +1597,8 @@ __global__ __launch_bounds__(256) void k_pf_backward(PfArgs f, SampleArgs a, int
         const double u[2] = {odd ? got : ua, odd ? ub : got};      // this candidate's uniforms of trajectories mm and mm + 1
 #pragma unroll
         for (int h = 0; h < 2; h++) {
-          const double sc = (lwi - 0.5 * acc[mm + h]) + -log(-log(u[h]));
-          if (mine && (sc > best[mm + h] || (sc == best[mm + h] && i < bslot[mm + h]))) { best[mm + h] = sc; bslot[mm + h] = i; }
+          const double sc = pf_gumbel_score(lwi, acc[mm + h], u[h]);
+          if (mine && pf_beats(sc, i, best[mm + h], bslot[mm + h])) { best[mm + h] = sc; bslot[mm + h] = i; }
         }
       }
     }
@@ -1513,7 +1610,7 @@ __global__ __launch_bounds__(256) void k_pf_backward(PfArgs f, SampleArgs a, int
       for (int o = 32; o > 0; o >>= 1) {
         const double ov = __shfl_xor(v, o);
         const int os = __shfl_xor(sl, o);
-        if (ov > v || (ov == v && os < sl)) { v = ov; sl = os; }
+        if (pf_beats(ov, os, v, sl)) { v = ov; sl = os; }
       }
       if (lane == 0) { rbest[w * TB + mm] = v; rslot[w * TB + mm] = sl; }
     }
@@ -1524,7 +1621,7 @@ __global__ __launch_bounds__(256) void k_pf_backward(PfArgs f, SampleArgs a, int
       for (int q = 1; q < 4; q++) {
         const double ov = rbest[q * TB + tid];
         const int os = rslot[q * TB + tid];
-        if (ov > v || (ov == v && os < sl)) { v = ov; sl = os; }
+        if (pf_beats(ov, os, v, sl)) { v = ov; sl = os; }
       }
       sl = sl < n ? sl : n - 1;      // (no finite score at all: any slot of the cloud)
       scur[tid] = sl;
@@ -1534,12 +1631,145 @@ __global__ __launch_bounds__(256) void k_pf_backward(PfArgs f, SampleArgs a, int
   }
 }
 
+// ---- particle Gibbs: the step between two segments of the conditional filter, the reference's stretches of the result ---
+// component d of x + dt f(x; theta): the transition mean of the model SDE from one particle's D states (Lorenz-96 circular on them)
+__device__ __forceinline__ double pf_transition_mean(int model, const double* th, const double* x, int D, int d, double dt) {
+  double f;
+  if (model == VGPA_MODEL_OU) f = -th[0] * x[0];
+  else if (model == VGPA_MODEL_DW) f = 4.0 * x[0] * (th[0] - x[0] * x[0]);
+  else if (model == VGPA_MODEL_L63) f = d == 0 ? th[0] * (x[1] - x[0]) : d == 1 ? (th[1] - x[2]) * x[0] - x[1] : x[0] * x[1] - th[2] * x[2];
+  else {
+    const int up = d + 1 < D ? d + 1 : 0, d1 = d >= 1 ? d - 1 : D - 1, d2 = d >= 2 ? d - 2 : D - 2 + d;
+    f = (x[up] - x[d2]) * x[d1] - x[d] + th[0];
+  }
+  return x[d] + dt * f;
+}
+
+// k_pf_resample<false> with slot 0 pinned, one workgroup per problem at grid index f.k.  The decision, ESS, cum, S and lw_new are that
+// kernel's, over all n slots.  Where the cloud is resampled:
+//   slots i >= 1  multinomial: anc_i = pf_bisect(cum, n, u_i S), u_i = unit_open(r0, r1) of Philox counter (k, i, p, 0xfffffffe).  Systematic
+//                 resampling with one slot forced is no valid conditional resampling (Chopin & Singh 2015): its n thresholds are one
+//                 draw, and conditioning on where one of them fell changes the law of all others.  Independent draws are exchangeable,
+//                 so pinning one of them leaves the rest as they are.
+//   slot 0        ancestor sampling (Lindsten, Jordan & Schoen 2014): x~ = ref[p][k + 1]; for every candidate i < n, slot 0 included,
+//                 b_i = lw_i - 1/2 sum_d ((x~_d - mu_i,d) (1 / R_dd))^2 with lw_i before the reset and mu_i = x_i + dt f(x_i; theta_p);
+//                 g_i = -log(-log u_i), u_i from Philox counter (k, 0, p, 0x40000000 | (i >> 1)): unit_open(r0, r1) for even i,
+//                 unit_open(r2, r3) for odd i; anc_0 = the smallest i that attains max (b_i + g_i) -- k_pf_backward's score and comparison
+//                 for one trajectory and one cut.  Thread t scores the candidates t, t + 256, ... from x_in in global memory
+//   x_out_0 = x_in_0: the pinned slot keeps the reference's state; anc_0 goes into the history alone.  lw_i = lw_new for every slot.
+__global__ __launch_bounds__(256) void k_pf_cresample(PfArgs a, SampleArgs s) {
+  __shared__ double tot[4], red[4], rbest[4], ir[kMaxSmallD];
+  __shared__ int rslot[4];
+  const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6, n = a.n_paths, D = a.D;
+  const int j = pf_obs_at(a, p);
+  const size_t nD = (size_t)n * D;
+  const double* xin = a.x_in + (size_t)p * nD;
+  double* xout = a.x_out + (size_t)p * nD;
+  if (j < 0) {      // (uniform over the workgroup)
+    for (size_t e = tid; e < nD; e += 256) xout[e] = xin[e];
+    return;
+  }
+  double* lw = a.lw + (size_t)p * n;
+  double* cum = a.cum + (size_t)p * n;
+  int32_t* anc = a.anc + (size_t)p * n;
+  const double mx = pf_max(lw, n, red);
+  double s2 = pf_prefix_sums(lw, n, mx, cum, tot);
+  __syncthreads();      // (cum is written; red has been read)
+  const double S = cum[n - 1];
+  s2 = wave_sum(s2);
+  if (lane == 0) red[w] = s2;
+  __syncthreads();
+  s2 = (red[0] + red[1]) + (red[2] + red[3]);
+  const double ess = S * S / s2;
+  const bool go = ess < a.ess_fraction * (double)n && !a.last;
+  const size_t hj = (size_t)p * a.M + j;
+  if (tid == 0) { a.h_ess[hj] = ess; a.h_flag[hj] = go ? 1 : 0; }
+  if (a.h_clouds)
+    for (size_t e = tid; e < nD; e += 256) a.h_clouds[hj * nD + e] = xin[e];
+  const uint32_t k0 = (uint32_t)(a.seed & 0xffffffffu), k1 = (uint32_t)(a.seed >> 32);
+  int anc0 = 0;
+  if (go) {      // (uniform over the workgroup; k < Np - 1: ref[p][k + 1] exists)
+    const double* xt = a.ref + ((size_t)p * a.Np + (size_t)a.k + 1) * D;
+    const double* Rp = s.R + (size_t)p * s.R_stride;
+    double th[kMaxTheta];
+#pragma unroll
+    for (int i = 0; i < kMaxTheta; i++) th[i] = s.theta_v ? s.theta_v[(size_t)p * kMaxTheta + i] : s.theta[i];
+    if (tid < D) ir[tid] = 1.0 / Rp[tid * D + tid];
+    __syncthreads();
+    double best = -INFINITY;
+    int bslot = 0x7fffffff;
+    for (int i = tid; i < n; i += 256) {
+      const double* xi = xin + (size_t)i * D;
+      double quad = 0.0;
+      for (int d = 0; d < D; d++) {
+        const double v = (xt[d] - pf_transition_mean(s.model, th, xi, D, d, s.dt)) * ir[d];
+        quad += v * v;
+      }
+      uint32_t r[4];
+      philox4x32_10((uint32_t)a.k, 0u, (uint32_t)p, 0x40000000u | ((uint32_t)i >> 1), k0, k1, r);
+      const double u = (i & 1) ? unit_open(r[2], r[3]) : unit_open(r[0], r[1]);
+      const double sc = pf_gumbel_score(lw[i], quad, u);
+      if (pf_beats(sc, i, best, bslot)) { best = sc; bslot = i; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const double ov = __shfl_xor(best, o);
+      const int os = __shfl_xor(bslot, o);
+      if (pf_beats(ov, os, best, bslot)) { best = ov; bslot = os; }
+    }
+    if (lane == 0) { rbest[w] = best; rslot[w] = bslot; }
+    __syncthreads();      // (every lw_i has been read: the loop below replaces them)
+    best = rbest[0]; bslot = rslot[0];
+    for (int q = 1; q < 4; q++)
+      if (pf_beats(rbest[q], rslot[q], best, bslot)) { best = rbest[q]; bslot = rslot[q]; }
+    anc0 = bslot < n ? bslot : n - 1;      // (no finite score at all: any slot of the cloud)
+  }
+  const double lw_new = mx + log(S) - log((double)n);
+  for (int i = tid; i < n; i += 256) {
+    int from = i, hist = i;
+    if (go) {
+      if (i == 0) hist = anc0;
+      else {
+        uint32_t r[4];
+        philox4x32_10((uint32_t)a.k, (uint32_t)i, (uint32_t)p, 0xfffffffeu, k0, k1, r);
+        from = hist = pf_bisect(cum, n, unit_open(r[0], r[1]) * S);
+      }
+      if (a.h_lw) a.h_lw[hj * n + i] = lw[i];
+      lw[i] = lw_new;
+    }
+    anc[i] = from;
+    if (a.h_anc) a.h_anc[hj * n + i] = hist;
+  }
+  __syncthreads();
+  for (size_t e = tid; e < nD; e += 256) {
+    const size_t i = e / D;
+    xout[e] = xin[(size_t)anc[i] * D + (e - i * D)];
+  }
+}
+
+// out [B][Np][D] (one trajectory per problem, stride 1) = ref wherever the trajectory sat in slot 0: grid index k lies in stretch
+// j(k) = #{observations of the problem before k}, row j(k) of table [B][rows][1].  One thread per entry.
+__global__ __launch_bounds__(256) void k_pf_ref_fill(PfArgs a, int rows, const int32_t* table, double* out) {
+  const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x, per = (size_t)a.Np * a.D;
+  if (g >= (size_t)a.batch * per) return;
+  const size_t p = g / per;
+  const int64_t k = (int64_t)((g - p * per) / a.D);
+  const int64_t* t = a.obs_t + p * a.obs_t_stride;
+  const int cnt = a.n_obs_v ? a.n_obs_v[p] : a.n_obs;
+  int j = 0;
+  for (int m = 0; m < cnt; m++) j += t[m] < k ? 1 : 0;
+  if (table[p * rows + j] == 0) out[g] = a.ref[g];
+}
+
 // One walk at the D of the arguments: k_sample_small<D, K> up to D = 4 (one lane per path; the replay: the problem in grid.x, 256 slots per
 // workgroup in grid.y), above it k_sample_mfma<NT, K> with NT the next multiple of 16 (grid: problems x 64 paths).  D = 2 exists for the
-// plain walk only: every other walk needs a stochastic model, and none has D = 2.  (Nine walks: 3 instantiations of k_sample_small each
+// plain walk only: every other walk needs a stochastic model, and none has D = 2.  (Ten walks: 3 instantiations of k_sample_small each
 // and one more for Plain, 4 of k_sample_mfma each but Forecast.)
 template <Walk K>
-hipError_t launch_walk(const SampleArgs& a, hipStream_t st) {
+hipError_t launch_walk(const SampleArgs& base, hipStream_t st, const double* pf_ref = nullptr) {
+  WalkArgs<K> a;
+  static_cast<SampleArgs&>(a) = base;
+  if constexpr (K == Walk::Conditional) a.pf_ref = pf_ref;
   if (a.D <= kMaxLaneD) {
     const dim3 grid = kWalkTraits[(int)K].MO || kWalkTraits[(int)K].FC ? dim3(a.batch, sample_segment_blocks(a.D, a.n_paths))
                                         : dim3((unsigned)(((size_t)a.batch * a.n_paths + 255) / 256));
@@ -1587,6 +1817,31 @@ hipError_t launch_pf_resample(const PfArgs& a, hipStream_t st) {
   if ((a.st_in == nullptr) != (a.st_out == nullptr) || (a.st_in && a.st_in == a.st_out)) return hipErrorInvalidValue;
   if (a.st_in) hipLaunchKernelGGL(k_pf_resample<true>, dim3(a.batch), dim3(256), 0, st, a);
   else hipLaunchKernelGGL(k_pf_resample<false>, dim3(a.batch), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_pf_pin(const PfArgs& a, hipStream_t st) {
+  if (a.D < 1 || a.D > kMaxSmallD || a.batch < 1 || a.n_paths < 1 || a.Np < 1 || !a.ref || !a.x || !a.ws || !a.lw || (!a.x0 && !(a.m0 && a.L0)) || (a.mu0 && !a.Lt))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_pf_pin, dim3((unsigned)((a.batch + 255) / 256)), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_pf_cresample(const PfArgs& f, const SampleArgs& a, hipStream_t st) {
+  if (f.D < 1 || f.D > kMaxSmallD || f.n_paths < 1 || !f.x_in || !f.x_out || f.x_in == f.x_out || !f.lw || !f.cum || !f.anc || !f.h_ess || !f.h_flag) return hipErrorInvalidValue;
+  if (f.st_in || f.st_out || !f.ref || f.Np < 1 || f.k < 0 || f.k >= f.Np || (!f.last && f.k + 1 >= f.Np)) return hipErrorInvalidValue;
+  if (a.D != f.D || !a.R || !a.R_diag) return hipErrorInvalidValue;
+  const bool model_fits = (a.D == 1 && (a.model == VGPA_MODEL_OU || a.model == VGPA_MODEL_DW)) || (a.D == 3 && a.model == VGPA_MODEL_L63) ||
+                          (a.D >= 3 && a.model == VGPA_MODEL_L96);
+  if (!model_fits) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_pf_cresample, dim3(f.batch), dim3(256), 0, st, f, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_pf_ref_fill(const PfArgs& f, int rows, const int32_t* table, double* out, hipStream_t st) {
+  const size_t total = (size_t)f.batch * (size_t)(f.Np > 0 ? f.Np : 0) * (size_t)f.D;
+  if (f.batch < 1 || f.D < 1 || f.Np < 1 || rows < 1 || !pf_flat_grid_fits(total) || !f.ref || !f.obs_t || !table || !out) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_pf_ref_fill, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, f, rows, table, out);
   return hipGetLastError();
 }
 
@@ -1674,13 +1929,14 @@ hipError_t launch_pf_stats_mean(int D, int batch, int n_paths, const double* lw,
 }
 
 // The walk is what the caller says it is; the fields that walk reads must be set, and the fields that would have meant another walk must not.
-hipError_t launch_sample_walk(Walk w, const SampleArgs& a, hipStream_t st) {
+hipError_t launch_sample_walk(Walk w, const SampleArgs& a, hipStream_t st, const double* pf_ref) {
   if (a.D < 1 || a.D > kMaxSmallD || a.n_paths < 1) return hipErrorInvalidValue;
   const bool known_model = a.model == VGPA_MODEL_OU || a.model == VGPA_MODEL_DW || a.model == VGPA_MODEL_L63 || a.model == VGPA_MODEL_L96;
   // the weighted kind: the posterior process with diagonal factors against the model's drift; above D = 4 the model is Lorenz-96
   const bool weighable = a.kind == VGPA_PATHS_POSTERIOR && a.R_diag && known_model && (a.D <= kMaxLaneD || a.model == VGPA_MODEL_L96);
   const bool segment = weighable && a.pf_x && a.pf_lw && a.k_begin >= 0 && a.k_end >= a.k_begin && a.k_end < a.Np;
   if (w == Walk::Backward ? a.pf_wtab || a.pf_part : a.pf_clouds || a.pf_hanc) return hipErrorInvalidValue;      // (the histories are Backward's alone, the sums never its)
+  if (w != Walk::Conditional && pf_ref) return hipErrorInvalidValue;      // (the reference is Conditional's alone)
   switch (w) {
     case Walk::Plain: {
       if (a.stride < 1 || a.logw) return hipErrorInvalidValue;
@@ -1699,6 +1955,9 @@ hipError_t launch_sample_walk(Walk w, const SampleArgs& a, hipStream_t st) {
     case Walk::SegmentStats:
       if (!segment || !a.pf_stats || a.pf_wtab) return hipErrorInvalidValue;
       return launch_walk<Walk::SegmentStats>(a, st);
+    case Walk::Conditional:      // (the segment's fields and the reference)
+      if (!segment || a.pf_stats || a.pf_wtab || !pf_ref) return hipErrorInvalidValue;
+      return launch_walk<Walk::Conditional>(a, st, pf_ref);
     case Walk::Replay:
       if (!segment || !a.pf_wtab || a.pf_stats || !a.pf_part || a.stride < 1 || a.pf_rows < 1) return hipErrorInvalidValue;
       if (a.n_paths > sample_max_paths(a.D)) return hipErrorInvalidValue;

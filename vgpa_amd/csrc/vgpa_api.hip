@@ -171,9 +171,10 @@ struct vgpa_ctx {
   // slot table (int32; the trajectories themselves go through d_sp_out); vgpa_particle_forecast: of these the particles, log-weights, prefix
   // sums, normalised weights (PF_WTAB), partial sums, moments and slot table; vgpa_particle_covariance: the buffers of the moments (the
   // partial sums and their sum packed, sample_cov_len(D) per kept index) and PF_COV: the mean and behind it the whole matrices;
-  // vgpa_particle_backward_paths: the buffers of vgpa_particle_paths, the clouds and PF_HLW: the log-weights the resamplings replaced
+  // vgpa_particle_backward_paths: the buffers of vgpa_particle_paths, the clouds and PF_HLW: the log-weights the resamplings replaced;
+  // vgpa_particle_conditional: the buffers of vgpa_particle_paths, the clouds and PF_REF: the reference trajectories
   enum { PF_XA, PF_XB, PF_LW, PF_CUM, PF_ANC, PF_ESS, PF_FLAG, PF_HANC, PF_CLOUDS, PF_MU, PF_LT, PF_STA, PF_STB, PF_MEAN, PF_WTAB, PF_LESS, PF_PART,
-         PF_MOM, PF_SLOTS, PF_COV, PF_HLW, PF_COUNT };
+         PF_MOM, PF_SLOTS, PF_COV, PF_HLW, PF_REF, PF_COUNT };
   double* d_pf[PF_COUNT] = {};
   size_t pf_n[PF_COUNT] = {};
   // profiling
@@ -1605,6 +1606,8 @@ struct ParticleRequest {
   bool forecast; int32_t horizon; const double* cloud; const double* cloud_logw; int32_t index0;
   double* fc_moments; double* members; double* state_end;
   bool covariance; double* cov_mean; double* cov_second;            // vgpa_particle_covariance (lineage_ess as for the moments)
+  // vgpa_particle_conditional: slot 0 pinned to ref [B][Np][D]; n_draw = 1, paths: the drawn trajectory, slots_out: its slot table
+  bool conditional; const double* ref;
 };
 
 // One run: the filter, then what the request puts behind it.  The passes share the kernels' arguments, the cuts and where the particles are.
@@ -1627,7 +1630,7 @@ struct ParticleRun {
     for (int k = 0; k < c->Np; k++) {
       if (!is_obs[k] && k != c->Np - 1) continue;
       s.k_begin = prev; s.k_end = k; s.pf_x = cur;
-      hipError_t e = launch_sample_walk(walk, s, c->stream);
+      hipError_t e = launch_sample_walk(walk, s, c->stream, walk == Walk::Conditional ? f.ref : nullptr);
       if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "%s failed: %s", what, hipGetErrorString(e));
       s.seg_first = 0; prev = k;
       if (!is_obs[k]) continue;
@@ -1654,7 +1657,7 @@ struct ParticleRun {
     if ((q.moments || q.covariance) && ((rc = buf(vgpa_ctx::PF_WTAB, (size_t)B * rows * n)) || (rc = buf(vgpa_ctx::PF_LESS, (size_t)B * rows)) ||
                       (rc = buf(vgpa_ctx::PF_PART, (size_t)B * n_blocks * mom_len)) || (rc = buf(vgpa_ctx::PF_MOM, (size_t)B * mom_len)))) return rc;
     if (q.covariance && (rc = buf(vgpa_ctx::PF_COV, (size_t)B * n_keep * D * ((size_t)D + 1)))) return rc;
-    if ((q.clouds || q.backward) && (rc = buf(vgpa_ctx::PF_CLOUDS, BM * n * D))) return rc;      // (backward simulation reads them on the device)
+    if ((q.clouds || q.backward || q.conditional) && (rc = buf(vgpa_ctx::PF_CLOUDS, BM * n * D))) return rc;      // (backward simulation and the conditional filter's walk read them on the device)
     if (q.backward && (rc = buf(vgpa_ctx::PF_HLW, BM * n))) return rc;
     if (q.with_stats && ((rc = buf(vgpa_ctx::PF_STA, 3 * BnD)) || (rc = buf(vgpa_ctx::PF_STB, 3 * BnD)) || (rc = buf(vgpa_ctx::PF_MEAN, (size_t)B * 3 * D)))) return rc;
     f = PfArgs{};
@@ -1675,8 +1678,13 @@ struct ParticleRun {
     f.anc = reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_ANC]);
     f.h_ess = c->d_pf[vgpa_ctx::PF_ESS]; f.h_flag = reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_FLAG]);
     f.h_anc = history ? reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_HANC]) : nullptr;
-    f.h_clouds = q.clouds || q.backward ? c->d_pf[vgpa_ctx::PF_CLOUDS] : nullptr;
+    f.h_clouds = q.clouds || q.backward || q.conditional ? c->d_pf[vgpa_ctx::PF_CLOUDS] : nullptr;
     f.h_lw = q.backward ? c->d_pf[vgpa_ctx::PF_HLW] : nullptr;
+    if (q.conditional) {      // the reference trajectories: uploaded once per call, read from global memory by the walk and the steps
+      const size_t n_ref = (size_t)B * c->Np * D;
+      if ((rc = buf(vgpa_ctx::PF_REF, n_ref)) || (rc = upload(c, c->d_pf[vgpa_ctx::PF_REF], q.ref, n_ref))) return rc;
+      f.ref = c->d_pf[vgpa_ctx::PF_REF]; f.Np = c->Np;
+    }
     // the cuts: the observation indices the kernels will see (each problem's own row and count in force), and the last grid index
     is_obs.assign((size_t)c->Np, 0);
     count.assign((size_t)B, M);
@@ -1697,7 +1705,13 @@ struct ParticleRun {
     HIP_TRY(c, hipMemsetAsync(f.h_flag, 0, BM * sizeof(int32_t), c->stream));
     if (f.h_anc) HIP_TRY(c, hipMemsetAsync(f.h_anc, 0xff, BM * n * sizeof(int32_t), c->stream));      // (-1 beyond a problem's own count)
     LAUNCH_TRY(c, "particle start launch", launch_pf_start(f, c->stream));
+    if (q.conditional) LAUNCH_TRY(c, "pinned start launch", launch_pf_pin(f, c->stream));
     a.pf_lw = f.lw; a.seg_first = 1; a.pf_stats = st_cur;
+    if (q.conditional)      // (the segment with slot 0 pinned, the step with ancestor sampling)
+      return cuts(Walk::Conditional, "conditional segment launch", a, "conditional resampling launch", [&](int k) {
+        f.k = k; f.last = k == c->Np - 1 ? 1 : 0; f.x_in = cur; f.x_out = other;
+        return launch_pf_cresample(f, a, c->stream);
+      });
     if (q.with_stats) HIP_TRY(c, hipMemsetAsync(st_cur, 0, 3 * (size_t)c->B * n * c->D * sizeof(double), c->stream));
     return cuts(q.with_stats ? Walk::SegmentStats : Walk::Segment, "particle segment launch", a, "particle resampling launch", [&](int k) {
       f.k = k; f.last = k == c->Np - 1 ? 1 : 0; f.x_in = cur; f.x_out = other; f.st_in = st_cur; f.st_out = st_other;
@@ -1766,6 +1780,18 @@ struct ParticleRun {
     return walk_table(Walk::Backward, "backward walk launch", table);
   }
 
+  // The trajectory of the conditional filter: the final slot drawn from the final weights, traced through the kept
+  // ancestors (slot 0's are the ancestor-sampled ones), walked by the backward walk on this run's histories -- it goes on from the true
+  // particle, the reference's where the ancestor is slot 0, behind every observation --, and the stretches it spent in slot 0, where that
+  // walk drew with slot 0's counters, overwritten with the reference before the download.
+  int conditional_trajectory() {
+    int rc;
+    int32_t* table = reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_SLOTS]);
+    if ((rc = final_slots(table))) return rc;
+    LAUNCH_TRY(c, "genealogy launch", launch_pf_trace(f, q.n_draw, slot_rows, table, c->stream));
+    return walk_table(Walk::Backward, "backward walk launch", table);
+  }
+
   // row c of the slot table: the caller's final slots, or drawn from the final weights; every other row -1
   int final_slots(int32_t* table) {
     const int B = c->B, n_draw = q.n_draw;
@@ -1792,6 +1818,7 @@ struct ParticleRun {
     if (walk == Walk::Backward) { w.pf_clouds = f.h_clouds; w.pf_hanc = f.h_anc; w.pf_M = f.M; w.pf_n = q.n_paths; }
     hipError_t e = launch_sample_walk(walk, w, c->stream);
     if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "%s failed: %s", what, hipGetErrorString(e));
+    if (q.conditional) LAUNCH_TRY(c, "reference stretches launch", launch_pf_ref_fill(f, slot_rows, table, c->d_sp_out, c->stream));
     if ((rc = download(c, q.paths, c->d_sp_out, n_traj))) return rc;
     if (q.slots_out) HIP_TRY(c, hipMemcpyAsync(q.slots_out, table, n_table * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     return VGPA_OK;
@@ -1909,7 +1936,7 @@ static int particle_run(vgpa_ctx* c, const ParticleRequest& q) {
   }
   ParticleRun r{c, q};
   if ((rc = r.setup()) || (rc = r.filter()) || ((q.moments || q.covariance) && (rc = r.moments())) ||
-      (q.paths && (rc = q.backward ? r.backward_trajectories() : r.trajectories()))) return rc;
+      (q.paths && (rc = q.conditional ? r.conditional_trajectory() : q.backward ? r.backward_trajectories() : r.trajectories()))) return rc;
   const size_t n = (size_t)n_paths, BnD = (size_t)B * n * D;
   if (q.forecast) {      // (the filter's final cloud leaves before the forecast carries it on in place)
     if ((rc = download(c, q.state, r.cur, BnD))) return rc;
@@ -1992,6 +2019,18 @@ int vgpa_particle_backward_paths(vgpa_ctx* c, const double* x, const double* x0,
   if (n_draw < 1) return fail(c, VGPA_ERR_ARG, "n_draw must be at least 1 (n_draw = %d)", n_draw);
   ParticleRequest q{x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled};
   q.stride = stride; q.n_draw = n_draw; q.final_slots = final_slots; q.paths = paths; q.slots_out = slots; q.backward = true;
+  return particle_run(c, q);
+}
+
+// The conditional particle filter with ancestor sampling: one sweep of particle Gibbs (see vgpa_hip.h)
+int vgpa_particle_conditional(vgpa_ctx* c, const double* x, const double* x0, const double* ref, int32_t n_paths, uint64_t seed,
+                              double ess_fraction, const double* prior_mu, const double* prior_tau, double* logw, double* state,
+                              double* trajectory, int32_t* slots, double* ess, int32_t* resampled, int32_t* ancestors, double* clouds) {
+  if (!c) return VGPA_ERR_ARG;
+  if (!ref || !trajectory) return fail(c, VGPA_ERR_ARG, "null argument");
+  ParticleRequest q{x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled};
+  q.ancestors = ancestors; q.clouds = clouds;
+  q.n_draw = 1; q.paths = trajectory; q.slots_out = slots; q.conditional = true; q.ref = ref;
   return particle_run(c, q);
 }
 

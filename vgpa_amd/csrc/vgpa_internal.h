@@ -222,9 +222,9 @@ struct ReduceArgs {
   const double* div_v;      // [B] per-problem div (1-D models: sigma_p), or nullptr
 };
 
-// Euler-Maruyama sample paths (sample.hip): x_k = x_{k-1} + dt drift_{k-1}(x_{k-1}) + R xi_k on the context's grid.  The nine things a launch
+// Euler-Maruyama sample paths (sample.hip): x_k = x_{k-1} + dt drift_{k-1}(x_{k-1}) + R xi_k on the context's grid.  The ten things a launch
 // can do with them (the table at the top of sample.hip); the host names one at every launch_sample_walk, and SampleArgs says what each reads
-enum class Walk { Plain, Weighted, Segment, SegmentStats, Replay, Lineage, Forecast, ReplayCov, Backward };
+enum class Walk { Plain, Weighted, Segment, SegmentStats, Replay, Lineage, Forecast, ReplayCov, Backward, Conditional };
 struct SampleArgs {
   int kind, model, D, Np, batch, n_paths, stride, n_keep;
   double dt;
@@ -291,10 +291,14 @@ struct SampleArgs {
   // histories (rows of pf_M observations per problem; pf_n particles per cloud)
   const double* pf_clouds;  // [B][pf_M][pf_n][D]; nullptr for every other walk
   const int32_t* pf_hanc;   // [B][pf_M][pf_n]; nullptr for every other walk
+  // Walk::Conditional (vgpa_particle_conditional): Walk::Segment, every field as there, in which slot 0 of every problem
+  // is pinned to the reference trajectory pf_ref[p] -- [B][Np][D], the last argument of launch_sample_walk and no field here: the other
+  // walks' kernels take this struct alone --: it draws nothing, takes the increment the reference implies, eta* = (ref_k - ref_{k-1})
+  // - dt g(ref_{k-1}), into the step's weight term in place of R xi, and its state becomes ref_k as loaded
 };
-// hipErrorInvalidValue where a field the walk reads is missing or out of range, where a field that belongs to another walk is set, and for
-// D = 2 in every walk but Plain (no stochastic model has D = 2)
-hipError_t launch_sample_walk(Walk w, const SampleArgs& a, hipStream_t st);
+// hipErrorInvalidValue where a field the walk reads is missing or out of range, where a field that belongs to another walk is set (pf_ref
+// in every walk but Conditional, which needs it), and for D = 2 in every walk but Plain (no stochastic model has D = 2)
+hipError_t launch_sample_walk(Walk w, const SampleArgs& a, hipStream_t st, const double* pf_ref = nullptr);
 // workgroups per problem of a segment launch: the blocks of the replay's partial sums
 int sample_segment_blocks(int D, int n_paths);
 int sample_max_paths(int D);      // the largest n_paths per problem a segment, replay or forecast launch takes at this D (grid.y)
@@ -328,9 +332,21 @@ struct PfArgs {
   double* h_lw;             // [B][M][n_paths] the log-weights a resampling step finds (the observation's term included), or nullptr
   // the rows of vgpa_particle_statistics, gathered by ancestor together with x; both or neither
   const double* st_in; double* st_out;   // [B][n_paths][3][D] each
+  // vgpa_particle_conditional: the reference trajectories slot 0 is pinned to (k_pf_pin, k_pf_cresample, k_pf_ref_fill), or nullptr
+  const double* ref;        // [B][Np][D]
+  int Np;
 };
 hipError_t launch_pf_start(const PfArgs& a, hipStream_t st);
 hipError_t launch_pf_resample(const PfArgs& a, hipStream_t st);
+// vgpa_particle_conditional (sample.hip: k_pf_pin, k_pf_cresample, k_pf_ref_fill).  pin, behind launch_pf_start: slot 0 of
+// every problem becomes ref[p][0], its log-weight the start's own formula at that state.  cresample: the step between two segments with
+// slot 0 pinned -- the decision, ESS and new log-weight of launch_pf_resample, multinomial ancestors for the slots >= 1, the ancestor of slot
+// 0 drawn by ancestor sampling against ref[p][k + 1] (a: the model, theta, the diagonal R and dt of the filter's arguments) into the
+// history alone, x_out_0 = x_in_0.  ref_fill: out [B][Np][D], the one trajectory per problem of Walk::Backward at stride 1, gets ref[p][k]
+// wherever row j(k) of table [B][rows][1] is 0
+hipError_t launch_pf_pin(const PfArgs& a, hipStream_t st);
+hipError_t launch_pf_cresample(const PfArgs& f, const SampleArgs& a, hipStream_t st);
+hipError_t launch_pf_ref_fill(const PfArgs& f, int rows, const int32_t* table, double* out, hipStream_t st);
 // mean [B][3][D] = sum_i w_i stats[.][i] / sum_i w_i, w_i = exp(lw_i - max lw) (sample.hip: k_pf_stats_mean)
 hipError_t launch_pf_stats_mean(int D, int batch, int n_paths, const double* lw, const double* stats, double* mean, hipStream_t st);
 // vgpa_particle_moments (sample.hip: k_pf_descend, k_pf_gather, k_pf_moments_sum).  Of PfArgs, descend reads lw, h_flag, h_anc, M and the

@@ -39,10 +39,21 @@ Forecast: one problem's record of vgpa_particle_forecast -- a
 carried past the window under the model SDE: mean and variance on the forecast grid, reduced on the device, a handful of member
 trajectories, and the cloud at the end of the horizon, from which the next forecast can go on (cloud=state, log_w=log_w,
 index0=grid[-1] when the last step is kept).  The weights do not change: there is nothing to weigh the particles against.
+
+GibbsChain: one problem's record of particle Gibbs with ancestor sampling (vgpa_particle_conditional) -- a Markov chain on
+(theta, trajectory) whose invariant law is the joint posterior of the Euler-discretised model.  Each iteration runs the conditional
+particle filter from the current trajectory at the current theta, then draws theta given the new trajectory: the drift is f0 + Phi theta
+with a diagonal Sigma, so that conditional is Gaussian, component by component, with
+    information I_a = sum_k dt sum_{i in a} phi_i^2 / Sigma_ii (+ the prior's precision),
+    score       s_a = sum_k sum_{i in a} phi_i r_i / Sigma_ii at the current theta (+ precision (prior mean - theta)),
+    theta'_a ~ N(theta_a + s_a / I_a, 1 / I_a)
+-- the rows G and H of PathStatistics on the one trajectory (path_rows, theta_conditional).  The chain is exact for the Euler-discretised
+model whatever the proposal (A_t, b_t) and for any number of particles >= 2: they decide how fast it mixes, not what it converges to.
 """
 import numpy as np
 
-__all__ = ["ParticleFilterResult", "PathStatistics", "SmoothingMoments", "SmoothingCovariance", "SmoothingPaths", "Forecast", "descendant_weights"]
+__all__ = ["ParticleFilterResult", "PathStatistics", "SmoothingMoments", "SmoothingCovariance", "SmoothingPaths", "Forecast", "GibbsChain", "descendant_weights",
+           "path_rows", "theta_conditional", "theta_draw"]
 
 
 def descendant_weights(log_w, ancestors, resampled):
@@ -499,3 +510,97 @@ class Forecast(object):
         """second moment - mean^2, clipped at 0"""
         v = np.maximum(self.moments[:, 1] - self.moments[:, 0] ** 2, 0.0)
         return v[..., 0] if self.single_dim else v
+
+
+def path_rows(model, theta, path, dt):
+    """(3, D): the rows (Q, G, H) of PathStatistics on one trajectory path (Np, D): Q_i = sum_k r_i^2 / dt, G_i = sum_k phi_i r_i,
+    H_i = sum_k dt phi_i^2 with r = x_k - x_{k-1} - dt f_theta(x_{k-1}) and phi_i = d f_i / d theta_a(i) at x_{k-1}.  model: "OU", "DW",
+    "L63", "L96"."""
+    path = np.asarray(path, dtype=float)
+    if path.ndim == 1:
+        path = path[:, None]
+    x, th, dt = path[:-1], np.atleast_1d(np.asarray(theta, dtype=float)).ravel(), float(dt)
+    if model == "OU":
+        f, phi = -th[0] * x, -x
+    elif model == "DW":
+        f, phi = 4.0 * x * (th[0] - x * x), 4.0 * x
+    elif model == "L63":
+        f = np.stack((th[0] * (x[:, 1] - x[:, 0]), (th[1] - x[:, 2]) * x[:, 0] - x[:, 1], x[:, 0] * x[:, 1] - th[2] * x[:, 2]), axis=1)
+        phi = np.stack((x[:, 1] - x[:, 0], x[:, 0], -x[:, 2]), axis=1)
+    elif model == "L96":
+        f = (np.roll(x, -1, axis=1) - np.roll(x, 2, axis=1)) * np.roll(x, 1, axis=1) - x + th[0]
+        phi = np.ones_like(x)
+    else:
+        raise ValueError(f" path_rows: unknown model -> {model}")
+    r = path[1:] - x - dt * f
+    return np.stack((np.sum(r * r, axis=0) / dt, np.sum(phi * r, axis=0), dt * np.sum(phi * phi, axis=0)))
+
+
+def theta_conditional(model, theta, path, dt, sigma_diag, prior=None):
+    """(mean, precision), each (n_theta,): the Gaussian law of theta given one trajectory of the Euler-discretised model.  prior: None
+    (flat) or (mean, precision) per component."""
+    th = np.atleast_1d(np.asarray(theta, dtype=float)).ravel()
+    _, g, h = path_rows(model, th, path, dt)
+    sg = np.broadcast_to(np.asarray(sigma_diag, dtype=float).ravel(), g.shape)
+    score, info = (g / sg, h / sg) if model == "L63" else (np.array([np.sum(g / sg)]), np.array([np.sum(h / sg)]))
+    if prior is not None:
+        pm, pl = (np.broadcast_to(np.asarray(v, dtype=float).ravel(), th.shape) for v in prior)
+        score, info = score + pl * (pm - th), info + pl
+    return th + score / info, info
+
+
+def theta_draw(mean, precision, seed, iteration, problem):
+    """theta' = mean + z / sqrt(precision), z the standard normals of numpy.random.Generator(PCG64([seed, iteration, problem])): the
+    draw depends on the chain's seed, the iteration and the problem's index in its batch alone."""
+    rng = np.random.Generator(np.random.PCG64([int(seed) & 0xFFFFFFFFFFFFFFFF, int(iteration), int(problem)]))
+    mean = np.asarray(mean, dtype=float)
+    return mean + rng.standard_normal(mean.shape) / np.sqrt(np.asarray(precision, dtype=float))
+
+
+class GibbsChain(object):
+    """theta (iters + 1, n_theta): theta before the first and after every iteration; paths (n_kept, Np, D): the trajectories of the kept
+    iterations `kept` (n_kept,) (burn <= it, every thin-th); moved (iters,): the share of grid points at which an iteration's trajectory
+    differs from its reference -- 0 means the conditional filter returned the reference, the chain did not move; first (Np, D): the
+    reference iteration 0 started from.  single_dim: a 1-D model, the last axis of paths / mean / var is dropped.
+
+    Successive trajectories are dependent draws: mean() and var() are ergodic averages, and moved says how fast the chain forgets.
+    The `burn` of the methods counts iterations: paths of iterations < burn and the theta rows they produced are left out."""
+
+    def __init__(self, theta, paths, kept, moved, first=None, single_dim=False) -> None:
+        self.theta = np.asarray(theta, dtype=float)
+        if self.theta.ndim != 2 or self.theta.shape[0] < 1:
+            raise ValueError(" GibbsChain: theta must be (iters + 1, n_theta).")
+        full = np.asarray(paths, dtype=float)
+        self.kept = np.asarray(kept, dtype=np.int64).ravel()
+        self.moved = np.asarray(moved, dtype=float).ravel()
+        if full.ndim != 3 or full.shape[0] != self.kept.size or self.moved.size != self.theta.shape[0] - 1:
+            raise ValueError(" GibbsChain: paths (n_kept, Np, D), kept (n_kept,) and moved (iters,) do not belong together.")
+        if self.kept.size and (self.kept.min() < 0 or self.kept.max() >= self.moved.size or np.any(np.diff(self.kept) <= 0)):
+            raise ValueError(" GibbsChain: kept must be increasing iterations in [0, iters).")
+        self.single_dim = bool(single_dim)
+        self.paths = full[..., 0] if self.single_dim else full
+        self.first = None if first is None else np.asarray(first, dtype=float)
+
+    def __len__(self):
+        return self.moved.size
+
+    def _after(self, burn):
+        sel = self.paths[self.kept >= int(burn)]
+        if sel.shape[0] < 1:
+            raise ValueError(" GibbsChain: no kept trajectory behind the burn-in.")
+        return sel
+
+    def mean(self, burn=0):
+        """the ergodic mean of the kept trajectories of the iterations >= burn, (Np, D)"""
+        return self._after(burn).mean(axis=0)
+
+    def var(self, burn=0):
+        """their variance on the grid"""
+        return self._after(burn).var(axis=0)
+
+    def theta_mean(self, burn=0):
+        """(n_theta,): the mean of theta after the iterations >= burn"""
+        return self.theta[1 + int(burn):].mean(axis=0)
+
+    def theta_var(self, burn=0):
+        return self.theta[1 + int(burn):].var(axis=0)

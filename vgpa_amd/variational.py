@@ -339,6 +339,18 @@ class VarGP(object):
         theta = theta[0]
         return (float(theta[0]) if theta.size == 1 else theta), trace
 
+    def particle_gibbs(self, n_paths, seed, iters, burn=0, thin=1, ess_fraction=0.5, sample_theta=True, theta_prior=None, x=None):
+        """Particle Gibbs with ancestor sampling for the joint posterior of theta and the path (ProblemBatch.particle_gibbs on a batch of
+        one): a particles.GibbsChain.  x: the fixed proposal (A_t, b_t), initialization() by default."""
+        from .batch import ProblemBatch
+        pb = ProblemBatch([self], device=self.device, flags=self.flags)
+        try:
+            chain = pb.particle_gibbs(n_paths, seed, iters, burn=burn, thin=thin, ess_fraction=ess_fraction, sample_theta=sample_theta,
+                                      theta_prior=theta_prior, x=None if x is None else np.asarray(x, dtype=float).reshape(1, -1))[0]
+        finally:
+            pb.close()
+        return chain
+
     def fit_theta(self, x0, rounds, options=None):
         """Variational EM for the drift parameters (ProblemBatch.fit_theta on a batch of one): (x, F, theta, trace), theta in the
         shape of model.theta, trace["F"] of shape (rounds, 2, 1)."""
