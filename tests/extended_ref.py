@@ -665,6 +665,41 @@ def obs_term(obs_t, obs_y, obs_noise, obs_h, stored, T=LD):
     return np.sum(terms, axis=-1) - const, (5 + 2 * levels(d) + levels(obs_t.size) + cond) * np.sum(forms, axis=-1) + 4 * np.abs(const)
 
 
+def gauss_term(x, mean, cov, T=LD):
+    """(-u^T u / 2 - sum_i log L_ii, size) of one point x (D,) under N(mean, cov), L = chol_lower(cov), L u = x - mean: the log-density without
+    its constant D log(2 pi) / 2 (which cancels in the start term), as k_pf_start / k_pf_pin form it by forward substitution.  A careful fp64
+    evaluation rounds, for row i with n_i = |x_i| + |mean_i| + sum_{j<i} |L_ij u_j|: the residual x_i - mean_i, the products L_ij u_j and the
+    sum of these i + 1 terms as a tree ((2 + levels(i + 1)) n_i / L_ii in u_i), and the division (|u_i|).  That local error of u_i is carried
+    into every later row by the substitution itself: e_i = local_i + sum_{j<i} |L_ij| e_j / L_ii.  The quadratic form then moves by
+    sum_i |u_i| e_i, its squares and their tree add (1 + levels(D)) q / 2 with q = sum u_i^2, the factor L, whoever forms it in fp64, carries
+    cond_2(cov) 2^-53 relative into q (cond_2(cov) q / 2), the logarithms are rounded once and added as a tree ((1 + levels(D)) sum |log L_ii|),
+    each sees its L_ii off by a relative 2^-53 (D in all), and the last subtraction is rounded at no more than q / 2 + |sum log L_ii|."""
+    x, mean = np.asarray(x, dtype=T).ravel(), np.asarray(mean, dtype=T).ravel()
+    d = x.size
+    cov64 = np.asarray(cov, dtype=np.float64).reshape(d, d)
+    low = np.linalg.cholesky(cov64) if T is np.float64 else cholesky(np.asarray(cov64, dtype=T))
+    low = np.asarray(low, dtype=T)
+    u, err = np.zeros(d, dtype=T), np.zeros(d, dtype=T)
+    for i in range(d):
+        prods = low[i, :i] * u[:i]
+        u[i] = ((x[i] - mean[i]) - _sum(prods, 0)) / low[i, i]
+        n_i = np.abs(x[i]) + np.abs(mean[i]) + np.sum(np.abs(prods))
+        err[i] = ((2 + levels(i + 1)) * n_i + np.sum(np.abs(low[i, :i]) * err[:i])) / low[i, i] + np.abs(u[i])
+    q, logs = _sum(u * u, 0), np.log(np.diag(low))
+    ld = _sum(logs, 0)
+    size = (np.sum(np.abs(u) * err) + (1 + levels(d) + T(np.linalg.cond(cov64))) * q / 2 + (1 + levels(d)) * np.sum(np.abs(logs)) + d
+            + (q / 2 + np.abs(ld)))
+    return -q / 2 - ld, size
+
+
+def start_term(x, mu0, tau0, m0, s0, T=LD):
+    """(log N(x; mu0, tau0) - log N(x; m0, S0), size) of one start x (D,): the initial term of a drawn start under a prior, two gauss_term
+    and their difference, rounded at no more than the sum of the two terms' magnitudes"""
+    prior, size_p = gauss_term(x, mu0, tau0, T)
+    law, size_l = gauss_term(x, m0, s0, T)
+    return prior - law, size_p + size_l + np.abs(prior) + np.abs(law)
+
+
 def statistics_rows(model, theta, dt, stored, T=LD):
     """The rows (Q, G, H) of stored stride-1 paths or lineages (n, Np, D): (rows (n, 3, D), sizes (n, 3, D)).  Q_j = sum_k r_j^2 / dt,
     G_j = sum_k phi_j r_j, H_j = sum_k dt phi_j^2 with r = x_k - x_{k-1} - dt f(x_{k-1}) (= dt d + eta), phi at x_{k-1}.  sizes: the

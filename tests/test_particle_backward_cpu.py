@@ -125,10 +125,11 @@ def argmax_with_gap(score):
     return win, top2[:, 1] - top2[:, 0]
 
 
-def backward_slots_numpy(problem, x, seed, hist, final, index=0, drift=model_drift):
+def backward_slots_numpy(problem, x, seed, hist, final, index=0, drift=model_drift, divisor=None, target=None):
     """(table (M + 1, K), gaps: one array (K,) per resampled observation).  Row M = final; for j = M-1 .. 0: row j + 1 where the cloud was
     carried on, else per trajectory m the smallest i that attains max_i (b_i + g_i).  drift: the model drift of the transition means
-    (another one: how the table reacts to a wrong drift)."""
+    (another one: how the table reacts to a wrong drift); divisor(rdiag) -> the divisors of the quadratic form and target(z, x~) -> the
+    successor the candidates are scored against (z: the trajectory's state at the cut), the hooks of two more mutants."""
     d, dt = int(problem.dim_d), float(problem.dt)
     rdiag = np.linalg.cholesky(_sigma_diag(problem) * dt).diagonal()
     lin_a, off_b = _split(problem, x)
@@ -146,13 +147,16 @@ def backward_slots_numpy(problem, x, seed, hist, final, index=0, drift=model_dri
         k, s, cloud = int(obs_t[j]), table[j + 1], hist["clouds"][j]
         z = cloud[hist["ancestors"][j][s]]
         xt = (z + dt * (-(z @ lin_a[k].T) + off_b[k])) + normals(seed, k + 1, s, index, d) * rdiag[None, :]
+        if target is not None:
+            xt = target(z, xt)
+        div = rdiag if divisor is None else divisor(rdiag)
         mu = cloud + dt * drift(problem.model, theta, cloud)
         win, gap = np.empty(final.size, dtype=np.int64), np.empty(final.size)
         for lo in range(0, final.size, 256):      # (256 trajectories at a time: the scores are (256, n))
             hi = min(lo + 256, final.size)
             quad = np.zeros((hi - lo, n))
             for c in range(d):
-                quad += ((xt[lo:hi, c, None] - mu[None, :, c]) / rdiag[c]) ** 2
+                quad += ((xt[lo:hi, c, None] - mu[None, :, c]) / div[c]) ** 2
             score = (hist["hlw"][j][None, :] - 0.5 * quad) + gumbels(seed, k, np.arange(lo, hi), index, n)
             win[lo:hi], gap[lo:hi] = argmax_with_gap(score)
         table[j] = win

@@ -189,7 +189,7 @@ def test_errors():
     big.close()
 
 
-@pytest.mark.parametrize("tag,d", [("ou_euler", 1), ("l63_rk4_p", 3)])
+@pytest.mark.parametrize("tag,d", [("ou_euler", 1), ("dw_euler_p", 1), ("l63_rk4_p", 3)])
 def test_chain(tag, d):
     """VarGP.particle_gibbs for 5 iterations on the fixtures' own problems and (A_t, b_t): the same seed gives the same chain; the theta
     trace is the host replay of the conditional draws from the returned trajectories; sweep 1 ran on the device at theta_1 (one

@@ -38,9 +38,10 @@ GAP = 1e-8            # log units, between the two largest scores of an ancestor
 BOUNDARY = 1e-9       # of S, between a multinomial threshold and the nearest prefix sum
 REF_SEED = 11         # the seed of the particle_paths draw the reference trajectories are
 REF_PARTICLES = 17
-# the cases of the GPU tests: D = 1, 3, 12, 17, 40 with a drawn start (the pinned start's initial term), D = 64 with a given one
-GCASES = [("ou_euler", "drawn"), ("l63_euler_p", "drawn"), ("l96d12_euler_p", "drawn"), ("l96d17_rk4_p", "drawn"), ("l96d40_rk4_p", "drawn"),
-          ("l96d64", "given")]
+# the cases of the GPU tests: D = 1 (both one-dimensional models), 3, 12, 17, 40 with a drawn start (the pinned start's initial term), D = 64
+# with a given one
+GCASES = [("ou_euler", "drawn"), ("dw_euler_p", "drawn"), ("l63_euler_p", "drawn"), ("l96d12_euler_p", "drawn"), ("l96d17_rk4_p", "drawn"),
+          ("l96d40_rk4_p", "drawn"), ("l96d64", "given")]
 PARTICLES = (1, 17, 65, 300)
 GFRACTIONS = (0.0, 0.5, 1.0)
 TIGHT = (12, 40)
@@ -76,9 +77,32 @@ def ancestor_draw(lw, quad, g, transition=True):
     return int(win[0]), float(gap[0])
 
 
-def conditional_filter_numpy(problem, x, x0, ref, n, seed, ess_fraction, index=0, transition=True):
+def pinned_draw(problem, theta, rdiag, cloud, lw, ref, k, seed, index=0, transition=True, drift=model_drift, divisor=None, target=None,
+                weights=None, swap_halves=False, limit=None):
+    """(winner, gap) of the pinned slot's ancestor draw at grid index k on the cloud (n, D) with the log-weights lw (n,) before the reset:
+    x~ = ref[k + 1], mu_i = x_i + dt f(x_i; theta), quad_i = sum_d ((x~_d - mu_i,d) / R_dd)^2, ancestor_draw on lw, quad and the Gumbels of
+    the cut.  With the defaults this is conditional_filter_numpy's own draw, operation for operation.  The other arguments are the hooks of
+    the mutants of test_particle_ancestor_cpu: drift(model, theta, cloud) in the model drift's place, divisor(rdiag) -> the divisors used,
+    target(ref, k) -> the x~ used, weights(lw) -> the log-weights used, swap_halves: candidates 2q and 2q + 1 take each other's half of
+    their Philox call, limit: candidates >= limit are not scored."""
+    n, dt = lw.size, float(problem.dt)
+    mu = cloud + dt * drift(problem.model, theta, cloud)
+    xt = ref[k + 1] if target is None else target(ref, k)
+    div = rdiag if divisor is None else divisor(rdiag)
+    quad = np.sum(((xt[None, :] - mu) / div[None, :]) ** 2, axis=1)
+    g = gumbels_ancestor(seed, k, n, index)
+    if swap_halves:
+        g = gumbels_ancestor(seed, k, n + (n & 1), index).reshape(-1, 2)[:, ::-1].reshape(-1)[:n]
+    used = lw if weights is None else weights(lw)
+    if limit is not None and limit < n:
+        used = np.where(np.arange(n) < limit, used, -np.inf)
+    return ancestor_draw(used, quad, g, transition)
+
+
+def conditional_filter_numpy(problem, x, x0, ref, n, seed, ess_fraction, index=0, transition=True, eta_dt=None):
     """One problem's conditional filter with counter word `index`.  Returns history_numpy's dict (ancestors[j][0]: the ancestor-sampled one)
-    and gaps (of the ancestor draws), margins (of the multinomial thresholds, relative to S)."""
+    and gaps (of the ancestor draws), margins (of the multinomial thresholds, relative to S).  eta_dt: the factor in dt's place inside the
+    implied increment of the pinned slot (a mutant's; None: dt)."""
     d, n_pts, dt = int(problem.dim_d), int(problem.n_pts), float(problem.dt)
     sigma = _sigma_diag(problem)
     isg, fac = 1.0 / sigma.diagonal(), np.linalg.cholesky(sigma * dt)
@@ -118,9 +142,7 @@ def conditional_filter_numpy(problem, x, x0, ref, n, seed, ess_fraction, index=0
         if ess < ess_fraction * n and k < n_pts - 1:
             anc, near = bisect_numpy(cum, uniforms_multinomial(seed, k, n, index) * total)
             out["margins"].append(float(near[1:].min() / total) if n > 1 else np.inf)
-            mu = state + dt * model_drift(problem.model, theta, state)
-            quad = np.sum(((ref[k + 1][None, :] - mu) / rdiag[None, :]) ** 2, axis=1)
-            win, gap = ancestor_draw(lw, quad, gumbels_ancestor(seed, k, n, index), transition)
+            win, gap = pinned_draw(problem, theta, rdiag, state, lw, ref, k, seed, index, transition)
             out["gaps"].append(gap)
             hist = anc.copy()
             hist[0], anc[0] = win, 0          # (the pinned slot keeps its state; its ancestor goes into the history alone)
@@ -133,7 +155,7 @@ def conditional_filter_numpy(problem, x, x0, ref, n, seed, ess_fraction, index=0
         g = -(state @ lin_a[k - 1].T) + off_b[k - 1]
         dd = g - model_drift(problem.model, theta, state)
         eta = normals(seed, k, slots, index, d) @ fac.T
-        eta[0] = (ref[k] - state[0]) - dt * g[0]
+        eta[0] = (ref[k] - state[0]) - (dt if eta_dt is None else eta_dt) * g[0]
         lw = lw + (-np.sum(dd * isg * eta, axis=1) - 0.5 * dt * np.sum(dd * isg * dd, axis=1))
         state = (state + dt * g) + eta
         state[0] = ref[k]
@@ -142,9 +164,10 @@ def conditional_filter_numpy(problem, x, x0, ref, n, seed, ess_fraction, index=0
     return out
 
 
-def conditional_trajectory_numpy(problem, x, x0, ref, seed, hist, index=0, table=None):
+def conditional_trajectory_numpy(problem, x, x0, ref, seed, hist, index=0, table=None, side="left"):
     """(trajectory (Np, D), table (M + 1,), the pick's margin): the final slot drawn from the final weights, traced through the kept
-    ancestors, walked by the backward walk on the run's histories; where the table says slot 0, the reference"""
+    ancestors, walked by the backward walk on the run's histories; where the table says slot 0, the reference.  side: "left" counts the
+    observations before k (t_m < k: the stretch of grid index k); "right" is the mutant t_m <= k of the fill."""
     n_pts = int(problem.n_pts)
     final, margin = pick_slots(hist["lw"], 1, seed, n_pts, index=index)
     if table is None:
@@ -153,7 +176,7 @@ def conditional_trajectory_numpy(problem, x, x0, ref, seed, hist, index=0, table
     # (as many copies of the one trajectory as the filter has particles: numpy's matrix product rounds by the shape of its operands)
     path = rewalk_backward_numpy(problem, x, x0, seed, np.repeat(table, hist["lw"].size, axis=1), hist, index=index)[0]
     ref = np.asarray(ref, dtype=float).reshape(path.shape)
-    stretch = np.searchsorted(hist["obs_t"], np.arange(n_pts), side="left")
+    stretch = np.searchsorted(hist["obs_t"], np.arange(n_pts), side=side)
     mine = table[stretch, 0] == 0
     path[mine] = ref[mine]
     return path, table[:, 0], margin
@@ -243,7 +266,7 @@ def test_without_resampling_the_other_slots_are_the_filters(tag, start):
     assert np.array_equal(got["state"][0], ref[-1]) and np.array_equal(got["clouds"][:, 0], ref[got["obs_t"]])
 
 
-@pytest.mark.parametrize("tag,start", GCASES[:3])
+@pytest.mark.parametrize("tag,start", GCASES[:4])
 def test_identities_of_the_restatement(tag, start):
     q = case(tag)[0]
     ref = reference_path(tag, start)
