@@ -198,6 +198,35 @@ int vgpa_fetch(vgpa_ctx* ctx, int which, double* out);
  * it (an S_t of the named problem is not positive definite) -- nothing is written to out then. */
 int vgpa_theta_gradient(vgpa_ctx* ctx, double* out);
 
+/* The two-time covariance of the posterior process dx = (-A_t x + b_t) dt + Sigma^1/2 dW on the context's grid: for
+ * t >= s, K(t, s) = Cov[x_t, x_s] = Phi(t, s) S_s with Phi the propagator of dPhi/dt = -A_t Phi, Phi(s, s) = I -- what autocorrelations, the
+ * joint Gaussian over several times, the variance of an increment x_t - x_s or of a time average and the conditional law x_t | x_s are made
+ * of.  For every anchor s and every grid index k >= s
+ *   C_s = S_s (VGPA_LAG_COVARIANCE)  or  C_s = I (VGPA_LAG_PROPAGATOR),    C_{k+1} = step_k(C_k),
+ * step_k the context's scheme for the MEAN equation applied to every column of C with b = 0 (the recursion m_t itself obeys, so that
+ * m_k = Phi(k, s) m_s + the forcing's part holds for the library's m_t and not only in the limit dt -> 0), h = dt / 2, A_mid = (A_k + A_{k+1}) / 2:
+ *   euler  C - dt A_k C;   heun  p = -A_k C, c = -A_{k+1} (C + dt p): C + h (p + c);   rk2  C - dt A_mid (C - h A_k C)  (no quirk: the mean's branch);
+ *   rk4    the four stages with A_k, A_mid, A_mid, A_{k+1}: C + dt (k1 + 2 (k2 + k3) + k4) / 6.      1-D models: C and A_t are scalars.
+ * K(k, s) for k < s is K(s, k)^T, with k as the anchor: only k >= s is computed.
+ *   anchors    host, [n_anchor]: strictly increasing grid indices in [0, Np)
+ *   out        host, [batch][n_anchor][n_keep][D][D] (1-D models: [batch][n_anchor][n_keep]), n_keep = (Np - 1) / stride + 1: the kept grid
+ *              indices k = 0, stride, 2 stride, ...; the kept rows with k < anchor are zero.  The row k = s (when kept) is bit for bit the S_s
+ *              of vgpa_fetch(VGPA_FETCH_ST), or I.  The block of an anchor does not depend on the other anchors of the call, the block of a
+ *              problem not on the batch around it, a kept row not on the stride: bit for bit.
+ *   VGPA_LAG_PROPAGATOR reads A_t only.  x_or_null as in vgpa_sample_paths: a given x (host, [batch][len_x]) is uploaded and the cached sweep
+ *              state is dropped; NULL: the x of the cached evaluation.  Works on ODE-only contexts and on VGPA_MODEL_NONE (with an x).
+ *   VGPA_LAG_COVARIANCE takes x NULL only and reads the S_t the last fused evaluation left resident, in the layout it is in.  Per-problem x
+ *              is honoured; theta, Sigma and the data enter through S_s alone.
+ * Nothing of the cached state is written: vgpa_gradient(NULL), vgpa_fetch, vgpa_energy_parts and vgpa_theta_gradient return afterwards bit
+ * for bit what they return without this call.
+ * VGPA_ERR_ARG: a null out or anchors, n_anchor < 1, stride < 1, an unknown kind, anchors outside [0, Np) or not strictly increasing, an x
+ * with the covariance kind; VGPA_ERR_UNSUPPORTED, before any work: D > 64 (the time-chunked large-D sweep included), a result of more than
+ * 2^35 entries; VGPA_ERR_STATE: no cached state where one is needed (x NULL; the covariance kind on an ODE-only context).  The context
+ * stays usable after every error. */
+enum { VGPA_LAG_COVARIANCE = 0, VGPA_LAG_PROPAGATOR = 1 };
+int vgpa_lag_covariance(vgpa_ctx* ctx, int kind, const double* x_or_null, int32_t n_anchor, const int64_t* anchors, int32_t stride,
+                        double* out);
+
 /* Sample paths on the context's grid by Euler-Maruyama: n_paths independent paths of every problem, of the posterior process
  * dx = (-A_t x + b_t) dt + Sigma^1/2 dW (VGPA_PATHS_POSTERIOR: what the moments m_t, S_t are the moments of) or of the model SDE
  * dx = f_theta(x) dt + Sigma^1/2 dW (VGPA_PATHS_MODEL: what a data set is a noisy record of; the reference's

@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("VGPA_LIB") or os.path.join(os.path.dirname(os.path.ab
 MODEL_IDS = {"NONE": -1, "OU": 0, "DW": 1, "L63": 2, "L96": 3}
 METHOD_IDS = {"euler": 0, "heun": 1, "rk2": 2, "rk4": 3}
 PATH_KINDS = {"posterior": 0, "model": 1}
+LAG_KINDS = {"covariance": 0, "propagator": 1}
 FETCH_IDS = {"mt": 0, "st": 1, "lamt": 2, "psit": 3, "Efx": 4, "Edf": 5, "dEsde_dm": 6, "dEsde_ds": 7, "Esde_t": 8}
 FLAG_FORCE_GENERIC = 1
 FLAG_STREAM_LARGE_D = 4
@@ -36,7 +37,7 @@ BWD_IDS = {"none": 0, "psi": 1, "q": 2}
 SYMBOLS = ["vgpa_create", "vgpa_destroy", "vgpa_last_error", "vgpa_abi_version", "vgpa_device_count",
            "vgpa_synchronize", "vgpa_stream", "vgpa_solve_fwd", "vgpa_solve_bwd", "vgpa_energy",
            "vgpa_obs_energy", "vgpa_free_energy", "vgpa_gradient", "vgpa_sweep", "vgpa_energy_parts",
-           "vgpa_fetch", "vgpa_theta_gradient", "vgpa_sample_paths", "vgpa_sample_paths_weighted", "vgpa_particle_filter", "vgpa_particle_statistics", "vgpa_particle_moments", "vgpa_particle_covariance", "vgpa_particle_paths", "vgpa_particle_backward_paths", "vgpa_particle_conditional", "vgpa_particle_forecast", "vgpa_sweep_dev", "vgpa_free_energy_dev", "vgpa_sweep_enqueue", "vgpa_fetch_f",
+           "vgpa_fetch", "vgpa_theta_gradient", "vgpa_lag_covariance", "vgpa_sample_paths", "vgpa_sample_paths_weighted", "vgpa_particle_filter", "vgpa_particle_statistics", "vgpa_particle_moments", "vgpa_particle_covariance", "vgpa_particle_paths", "vgpa_particle_backward_paths", "vgpa_particle_conditional", "vgpa_particle_forecast", "vgpa_sweep_dev", "vgpa_free_energy_dev", "vgpa_sweep_enqueue", "vgpa_fetch_f",
            "vgpa_dev_alloc", "vgpa_dev_free", "vgpa_memcpy_h2d", "vgpa_memcpy_d2h",
            "vgpa_profile_begin", "vgpa_profile_end", "vgpa_ld_gemm", "vgpa_ld_stage", "vgpa_gradient_dev", "vgpa_energy_full", "vgpa_set_option", "vgpa_is_streaming", "vgpa_path_info", "vgpa_set_prior_energy",
            "vgpa_set_problem_data", "vgpa_set_problem_params", "vgpa_set_problem_obs_model",
@@ -138,6 +139,7 @@ def load():
     lib.vgpa_energy_parts.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vgpa_fetch.argtypes = [c_void_p, c_int, c_void_p]
     lib.vgpa_theta_gradient.argtypes = [c_void_p, c_void_p]
+    lib.vgpa_lag_covariance.argtypes = [c_void_p, c_int, c_void_p, c_int32, POINTER(c_int64), c_int32, c_void_p]
     lib.vgpa_sample_paths.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_int32, c_int32, c_uint64, c_void_p]
     lib.vgpa_sample_paths_weighted.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_uint64, c_void_p, c_void_p, c_void_p]
     lib.vgpa_particle_filter.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_uint64, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -599,6 +601,36 @@ class Context:
         if wide.dtype.kind not in "iu" or wide.size == 0 or wide.min() < -2 ** 31 or wide.max() >= 2 ** 31:
             raise ValueError("slots must be integers that fit into 32 bits")
         return np.ascontiguousarray(np.broadcast_to(wide.reshape(-1, k), (self.B, k)), dtype=np.int32)
+
+    def lag_covariance(self, anchors, kind="covariance", stride=1, x=None):
+        """The two-time covariance K(k, s) = Phi(k, s) S_s of the posterior process (kind "covariance") or the propagator Phi(k, s) of
+        dPhi/dt = -A_t Phi itself (kind "propagator") from every anchor s to the end of the grid (vgpa_lag_covariance): the context's scheme
+        for the mean equation with b = 0, applied to every column.  anchors: strictly increasing grid indices.  x=None: the x of the cached
+        evaluation, which stays as it is; the covariance kind with an x evaluates free_energy(x) first (its S_t is what the call reads), the
+        propagator kind uploads x and drops the cached state.  Returns a LagCovariance: values (B, n_anchor, n_keep, D, D) at the grid
+        indices 0, stride, ..., zero before each anchor."""
+        from .lagcov import LagCovariance
+        if kind not in LAG_KINDS:
+            raise ValueError(f" Unknown kind of lag covariance -> {kind}")
+        stride = int(stride)
+        anc = np.asarray(anchors)
+        if anc.ndim == 0:
+            anc = anc.reshape(1)
+        if anc.ndim != 1 or (anc.size and anc.dtype.kind not in "iu"):
+            raise ValueError("anchors must be a 1-D sequence of integer grid indices")
+        anc = np.ascontiguousarray(anc, dtype=np.int64)
+        self._fit32(n_anchor=int(anc.size), stride=stride)
+        xx = None if x is None else _c64(x)
+        if xx is not None and xx.size != self.B * self.len_x:
+            raise ValueError(f"x has {xx.size} entries, expected {self.B * self.len_x}")
+        if xx is not None and kind == "covariance":
+            self.free_energy(xx)
+            xx = None
+        n_keep = (self.Np - 1) // stride + 1 if stride >= 1 else 0
+        out = np.empty((self.B, anc.size, n_keep, self.D, self.D))
+        self._check(self._lib.vgpa_lag_covariance(self._h, LAG_KINDS[kind], _ptr(xx), int(anc.size),
+                                                  anc.ctypes.data_as(POINTER(c_int64)) if anc.size else None, stride, _ptr(out)))
+        return LagCovariance(out, anc, np.arange(n_keep) * stride, kind)
 
     def sample_paths(self, kind, n_paths, seed, stride=1, x=None, x0=None):
         """Euler-Maruyama paths on the context's grid: kind "posterior" (dx = (-A_t x + b_t) dt + Sigma^1/2 dW, from x or, x=None, the x of

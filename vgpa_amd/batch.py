@@ -190,6 +190,17 @@ class ProblemBatch(object):
             self.free_energy(x)
         return np.asarray(self._context().theta_gradient(), dtype=float).reshape(self.B, -1)
 
+    def posterior_kernel(self, anchors, kind="covariance", stride=1, x=None):
+        """One lagcov.LagCovariance per member (VarGP.posterior_kernel): K(k, s) = Phi(k, s) S_s of the member's own posterior process, or
+        its propagator Phi(k, s), from the anchors (shared by the batch) to the end of the grid.  x=None: the state of the last
+        free_energy, which stays as it is; else F is evaluated at x first (the propagator only uploads x)."""
+        xx = None if x is None else self._stack(x)
+        if xx is not None and kind == "covariance":
+            self.free_energy(xx)
+            xx = None
+        res = self._context().lag_covariance(anchors, kind=kind, stride=stride, x=xx)
+        return [res.problem(p) for p in range(self.B)]
+
     def sample_paths(self, n_paths, seed, stride=1, x=None, x0=None, kind="posterior"):
         """(B, n_paths, n_keep, D) Euler-Maruyama paths of every member's posterior process (kind="model": of its model SDE, which takes no
         x), each with its own data, prior, theta and Sigma.  x=None: the x of the last free_energy, whose cached state stays as it is.

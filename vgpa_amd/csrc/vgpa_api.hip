@@ -165,6 +165,8 @@ struct vgpa_ctx {
   size_t sp_out_n = 0, sp_R_n = 0, sp_L0_n = 0, sp_x0_n = 0;
   double *d_sp_logw = nullptr, *d_sp_start = nullptr;      // vgpa_sample_paths_weighted: the two sums and x_0 of every path
   size_t sp_logw_n = 0, sp_start_n = 0;
+  double* d_lag_start = nullptr;   // vgpa_lag_covariance: the starting matrices [B][n_anchor][D][D] and, behind them, the anchors (int32); the result goes through d_sp_out
+  size_t lag_start_n = 0;
   // vgpa_particle_filter: the two particle buffers, log-weights, prefix sums, ancestors of a step (int32), the histories (ess, flags and
   // ancestors as int32, clouds), the prior's mean and factor; vgpa_particle_statistics: the two buffers of rows and their mean;
   // vgpa_particle_moments: the descendant weights, the lineage ESS, the workgroups' partial sums, the moments; vgpa_particle_paths: the
@@ -949,7 +951,7 @@ void vgpa_destroy(vgpa_ctx* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   for (void* p : c->allocs) (void)hipFree(p);
   for (void* p : c->user_allocs) (void)hipFree(p);
-  for (double* p : {c->d_sp_out, c->d_sp_R, c->d_sp_L0, c->d_sp_x0, c->d_sp_logw, c->d_sp_start}) if (p) (void)hipFree(p);
+  for (double* p : {c->d_sp_out, c->d_sp_R, c->d_sp_L0, c->d_sp_x0, c->d_sp_logw, c->d_sp_start, c->d_lag_start}) if (p) (void)hipFree(p);
   for (double* p : c->d_pf) if (p) (void)hipFree(p);
   if (c->h_coef) (void)hipHostFree(c->h_coef);
   if (c->h_fs) (void)hipHostFree(c->h_fs);
@@ -2067,6 +2069,56 @@ int vgpa_particle_forecast(vgpa_ctx* c, const double* x, const double* x0, int32
   ParticleRun r{c, q};      // a given cloud: no filter runs
   if ((rc = r.given_cloud()) || (rc = r.forecast())) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return VGPA_OK;
+}
+
+// The two-time covariance K(k, s) = Phi(k, s) S_s of the posterior process, or the propagator Phi(k, s) itself, from every anchor s to the
+// end of the grid (see vgpa_hip.h; lag_cov.hip).  Reads x and, for the covariance, the resident S_t in the layout it is
+// in; of the cached state nothing is written.
+int vgpa_lag_covariance(vgpa_ctx* c, int kind, const double* x, int32_t n_anchor, const int64_t* anchors, int32_t stride, double* out) {
+  if (!c) return VGPA_ERR_ARG;
+  if (!out || !anchors) return fail(c, VGPA_ERR_ARG, "null argument");
+  if (kind != VGPA_LAG_COVARIANCE && kind != VGPA_LAG_PROPAGATOR) return fail(c, VGPA_ERR_ARG, "unknown kind of lag covariance -> %d", kind);
+  if (n_anchor < 1 || stride < 1) return fail(c, VGPA_ERR_ARG, "n_anchor and stride must be at least 1 (n_anchor = %d, stride = %d)", n_anchor, stride);
+  for (int32_t i = 0; i < n_anchor; i++)
+    if (anchors[i] < 0 || anchors[i] >= c->Np || (i > 0 && anchors[i] <= anchors[i - 1]))
+      return fail(c, VGPA_ERR_ARG, "anchor %d -> %lld: the anchors are strictly increasing grid indices in [0, %d)", i, (long long)anchors[i], c->Np);
+  if (kind == VGPA_LAG_COVARIANCE && x) return fail(c, VGPA_ERR_ARG, "the covariance kind reads the cached S_t: it takes no x");
+  if (c->D > kMaxSmallD) return fail(c, VGPA_ERR_UNSUPPORTED, "the lag covariance is built for D <= %d (D = %d)", kMaxSmallD, c->D);
+  const int D = c->D, B = c->B, kept = (c->Np - 1) / stride + 1;
+  int rc;
+  if ((double)B * (double)n_anchor * (double)kept * (double)c->DD > 34359738368.0)      // (the limit of check_stored)
+    return fail(c, VGPA_ERR_UNSUPPORTED, "the lag covariances are built for at most 2^35 entries (batch %d, %d anchors, %d kept grid indices, D = %d): "
+                "use a larger stride or fewer anchors", B, n_anchor, kept, D);
+  if (!lag_grid_fits(D, B, n_anchor))
+    return fail(c, VGPA_ERR_UNSUPPORTED, "the lag covariance is built for at most 2^31 - 1 workgroups (batch %d, %d anchors)", B, n_anchor);
+  if (kind == VGPA_LAG_COVARIANCE && !c->full) return fail(c, VGPA_ERR_STATE, "context was created without m0/s0/observations (ODE-only)");
+  if (!x && !c->res.cached)
+    return fail(c, VGPA_ERR_STATE, "no cached state: lag_covariance without x needs the state cached by a previous free_energy / sweep");
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  if (x) {
+    if ((rc = ingest_x(c, x, false))) return rc;
+    c->res.cache_dropped();           // (d_x no longer holds the x of the cached state)
+  }
+  const size_t n_start = (size_t)B * n_anchor * c->DD, n_out = n_start * kept;
+  if ((rc = grow(c, &c->d_lag_start, &c->lag_start_n, n_start + (size_t)(n_anchor + 1) / 2)) || (rc = grow(c, &c->d_sp_out, &c->sp_out_n, n_out))) return rc;
+  int32_t* d_anchors = reinterpret_cast<int32_t*>(c->d_lag_start + n_start);      // (behind the starting matrices, in the same block)
+  std::vector<int32_t> h_anchors(anchors, anchors + n_anchor);
+  HIP_TRY(c, hipMemcpyAsync(d_anchors, h_anchors.data(), sizeof(int32_t) * n_anchor, hipMemcpyHostToDevice, c->stream));
+  LagStartArgs s{};
+  s.D = D; s.Np = c->Np; s.batch = B; s.n_anchor = n_anchor; s.anchors = d_anchors; s.start = c->d_lag_start;
+  s.layout = LagStartArgs::Identity;
+  if (kind == VGPA_LAG_COVARIANCE) {
+    if (c->res.moments == Resident::Moments::TimeMajor) { s.layout = LagStartArgs::TimeMajor; s.S = c->d_msT; s.bpad = c->bpad; }
+    else { s.layout = c->res.S == Resident::SLayout::Packed ? LagStartArgs::Packed : LagStartArgs::Whole; s.S = c->d_S; }
+  }
+  LAUNCH_TRY(c, "lag covariance start launch", launch_lag_start(s, c->stream));
+  LagArgs a{};
+  a.D = D; a.Np = c->Np; a.batch = B; a.n_anchor = n_anchor; a.stride = stride; a.n_keep = kept; a.method = c->cfg.method; a.dt = c->cfg.dt;
+  a.A = ctx_A(c); a.stride_x = c->len_x; a.start = c->d_lag_start; a.anchors = d_anchors; a.out = c->d_sp_out;
+  LAUNCH_TRY(c, "lag covariance launch", launch_lag(a, c->stream));
+  if ((rc = download(c, out, c->d_sp_out, n_out))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));      // (also: the host copy of the anchors lives on this stack frame)
   return VGPA_OK;
 }
 

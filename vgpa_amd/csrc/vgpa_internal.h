@@ -378,6 +378,29 @@ hipError_t launch_pf_moments_sum(int batch, int n_blocks, size_t len, const doub
 // one-dimensional grid: at most (2^31 - 1) 256 = 2^39 - 256 entries
 hipError_t launch_pf_cov_unpack(int D, size_t rows, const double* packed, double* mean, double* second, hipStream_t st);
 
+// Two-time covariance of the posterior process (lag_cov.hip).  LagStartArgs: the starting matrices of every (problem,
+// anchor) from S_t as it is resident, or the identity.  LagArgs: the recursion C_{k+1} = step_k(C_k) of the mean equation with b = 0 from
+// every anchor to the end of the grid, the kept rows stored
+struct LagStartArgs {
+  enum Layout { Identity, Whole, Packed, TimeMajor };
+  int D, Np, batch, n_anchor, layout, bpad;
+  const double* S;          // Whole: [B][Np][D][D]; Packed: [B][Np][D (D + 1) / 2] (OdeArgs::s_packed); TimeMajor: OdeArgs::msT with bpad; Identity: not read
+  const int32_t* anchors;   // [n_anchor], on the device
+  double* start;            // [B][n_anchor][D][D]
+};
+struct LagArgs {
+  int D, Np, batch, n_anchor, stride, n_keep, method;
+  double dt;
+  const double* A;          // [B][Np][D][D] (problem stride stride_x)
+  size_t stride_x;
+  const double* start;      // [B][n_anchor][D][D]
+  const int32_t* anchors;   // [n_anchor] grid indices in [0, Np), on the device
+  double* out;              // [B][n_anchor][n_keep][D][D]: zero at the kept indices before the anchor
+};
+hipError_t launch_lag_start(const LagStartArgs& a, hipStream_t st);
+hipError_t launch_lag(const LagArgs& a, hipStream_t st);     // D <= kMaxSmallD; hipErrorInvalidValue otherwise
+bool lag_grid_fits(int D, int batch, int n_anchor);          // one workgroup (D <= kMaxLaneD: one lane) per (problem, anchor) in grid.x
+
 // launchers (each returns hipGetLastError()) -----------------------------------------------------
 hipError_t launch_ode_generic(int method, bool fwd, const OdeArgs& a, hipStream_t st);
 hipError_t launch_ode_small(int method, bool fwd, const OdeArgs& a, hipStream_t st);     // D <= kMaxLaneD

@@ -146,6 +146,21 @@ class VarGP(object):
             g = g[..., 0]
         return float(g) if g.ndim == 0 else g
 
+    def posterior_kernel(self, anchors, kind="covariance", stride=1, x=None):
+        """The covariance function of the posterior process between two grid times: a lagcov.LagCovariance (with batch > 1 a list, one per
+        problem) holding K(k, s) = Cov[x_k, x_s] = Phi(k, s) S_s (kind "covariance") or the propagator Phi(k, s) (kind "propagator") for
+        every anchor s in `anchors` and the grid indices k = 0, stride, 2 stride, ... >= s; its cov(k, s) / corr / joint / increment_var
+        give the rest.  x=None: from the state of the last free_energy, which stays as it is; else F is evaluated at x first (the
+        propagator reads A_t alone and only uploads x).  Deterministic: what thousands of sample_paths draws estimate."""
+        xx = None if x is None else np.asarray(x, dtype=float)
+        if xx is not None and kind == "covariance":
+            self.free_energy(xx)
+            xx = None
+        res = self._context().lag_covariance(anchors, kind=kind, stride=stride, x=xx)
+        if xx is not None:
+            self._stale = {"mt", "st", "Efx", "Edf", "lamt", "psit"}
+        return res.problem(0) if self.batch == 1 else [res.problem(p) for p in range(self.batch)]
+
     def sample_paths(self, n_paths, seed, stride=1, x=None, x0=None):
         """Draws from the posterior process dx = (-A_t x + b_t) dt + Sigma^1/2 dW by Euler-Maruyama on the grid: (n_paths, n_keep, D), or
         (n_paths, n_keep) for the 1-D models (with batch > 1 a leading batch axis), the grid points 0, stride, 2 stride, ...  x=None: the
