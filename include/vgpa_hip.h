@@ -329,6 +329,36 @@ int vgpa_particle_statistics(vgpa_ctx* ctx, const double* x_or_null, const doubl
                              const double* prior_mu_or_null, const double* prior_tau_or_null, double* logw, double* state,
                              double* stats_or_null, double* mean_or_null, double* ess_or_null, int32_t* resampled_or_null);
 
+/* Path events of the particle filter's lineages: what no mean or variance on the grid expresses -- whether a component
+ * crossed a level anywhere in the window, when it first did, how long it stayed beyond it and how far it went -- from all n_paths lineages,
+ * with only per-problem summaries leaving the device.  The walk, the counters and the resampling decisions are those of vgpa_particle_filter.
+ *   levels  host, [batch][D], finite: c[p][j];  sides  host, [batch][D] int32, each +1 or -1: s[p][j]
+ *   g_j(x)  = s_j (x_j - c_j): one fp64 subtraction, then an exact change of sign.  Component j of a state is in the event iff g_j(x) > 0
+ *   x_i(k)  the state of slot i as the walk arrives at grid index k, before a resampling decision at k (as for vgpa_particle_moments)
+ * Every slot i carries a row [3][D] = (X, T, N) of records of its own lineage:
+ *   k = 0             X_j = g_j(x_i(0));  T_j = 0 and N_j = 1 if in the event, else T_j = Np (the sentinel: never so far) and N_j = 0
+ *   k = 1 .. Np-1     X_j = fmax(X_j, g_j(x_i(k)));  if in the event, T_j = min(T_j, k) and N_j += 1
+ * At a resampling slot i takes the row of its ancestor, as it takes x -- also at an observation at grid index 0: the row of k = 0 is set
+ * before that decision.  T and N are returned as doubles; they are exact integers.
+ *   rows_or_null  host, [batch][n_paths][3][D]: the final rows, in the order (X, T, N)
+ *   mean_or_null  host, [batch][3][D]: sum_i w_i row_i / sum_i w_i with w_i = exp(lw_i - max lw), reduced on the device as for
+ *                 vgpa_particle_statistics: E[X] the mean extreme of g, E[N] dt the expected occupation time, E[T] with the sentinel in it
+ *   cdf_or_null   host, [batch][n_keep][D], n_keep = (Np-1) / stride + 1: the first-passage distribution on the kept grid indices,
+ *                 cdf[k'][j] = sum_i W_i 1[T_ij <= k' stride], W_i = w_i / sum w.  Non-decreasing in k' to the bit; two calls with the same
+ *                 arguments give the same bits, and a problem's row does not depend on the batch around it
+ *   at least one of the three must be given
+ *   logw, state, ess_or_null, resampled_or_null and every other argument: as in vgpa_particle_filter, and bit-identical to its results with
+ *   the same arguments; with x NULL the cached state is read and not written
+ * The estimator is that of vgpa_particle_statistics: the final weights on the surviving lineages.  It is exact for the Euler-discretised
+ * model as n_paths grows, and in early stretches of the window it rests on the few lineages the genealogy has left there, which
+ * lineage_ess of vgpa_particle_moments reports.
+ * Errors: as vgpa_particle_filter (D > 64 and a dense Sigma: VGPA_ERR_UNSUPPORTED), and VGPA_ERR_ARG for a NULL levels or sides, a side that
+ * is not +1 or -1, a level that is not finite, stride < 1, or rows, mean and cdf all NULL. */
+int vgpa_particle_events(vgpa_ctx* ctx, const double* x_or_null, const double* x0_or_null, int32_t n_paths, int32_t stride, uint64_t seed,
+                         double ess_fraction, const double* prior_mu_or_null, const double* prior_tau_or_null, const double* levels,
+                         const int32_t* sides, double* logw, double* state, double* rows_or_null, double* mean_or_null, double* cdf_or_null,
+                         double* ess_or_null, int32_t* resampled_or_null);
+
 /* The smoothing moments on the time grid under the genealogy of the particle filter: E[x_k | y] and E[x_k^2 | y] of the
  * Euler-discretised model as the filter's surviving lineages estimate them, with O(n D) state per problem -- no path is stored or copied.
  * Three steps on the device: the filter of vgpa_particle_filter with its ancestors kept; the final weights pushed backwards through the

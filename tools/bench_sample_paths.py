@@ -1,11 +1,12 @@
 """
 Time of Context.sample_paths (vgpa_sample_paths), Context.sample_paths_weighted (vgpa_sample_paths_weighted), Context.particle_filter
-(vgpa_particle_filter), Context.particle_statistics (vgpa_particle_statistics), Context.particle_moments (vgpa_particle_moments),
+(vgpa_particle_filter), Context.particle_statistics (vgpa_particle_statistics), Context.particle_events (vgpa_particle_events), Context.particle_moments (vgpa_particle_moments),
 Context.particle_covariance (vgpa_particle_covariance), Context.particle_paths (vgpa_particle_paths), Context.particle_backward_paths
 (vgpa_particle_backward_paths) and Context.particle_forecast (vgpa_particle_forecast) on their jobs, one JSON line.
 
     python tools/bench_sample_paths.py [--rounds 3] [--calls 5] [--jobs a,b,c,aw,aw0,bw,bw0,af64_0,af64_5,af1024_0,af1024_5,bf64_0,...]
     python tools/bench_sample_paths.py --statistics [--filter-problems 4096]      # the as* and bs* jobs
+    python tools/bench_sample_paths.py --events [--filter-problems 4096]          # the ae* and be* jobs
     python tools/bench_sample_paths.py --moments [--filter-problems 4096]         # the am* and bm* jobs
     python tools/bench_sample_paths.py --covariance [--filter-problems 4096]      # the ac* and bc* jobs
     python tools/bench_sample_paths.py --paths [--filter-problems 4096] [--paths-strides 1,10]      # the ap* and bp* jobs, once per stride
@@ -25,6 +26,12 @@ Context.particle_covariance (vgpa_particle_covariance), Context.particle_paths (
   as<n>_<f>, bs<n>_<f>   (--statistics selects all eight) particle_statistics with the arguments of af<n>_<f> / bf<n>_<f>, the mean reduced on
              the device and no rows copied, and particle_filter itself, the two calls alternating inside every round: both times and their
              ratio
+
+  ae<n>, be<n>   (--events selects all four) particle_events on the contexts of a and b: n = 64 or 1024 particles per problem, ess_fraction 0.5,
+             stride 1, the level of every component the mean of the filter's final particles, the sides alternating, the mean and the
+             first-passage distribution reduced on the device and no rows copied; beside it particle_statistics (the same walk, the same
+             number of carried values, the same gather) and particle_filter with the same arguments, the three calls alternating inside
+             every round: the three times and the ratios
 
   am<n>_<s>, bm<n>_<s>   (--moments selects all twelve) particle_moments on the contexts of a and b: n = 64 or 1024 particles per problem,
              ess_fraction 0.5, every s-th grid index kept (s = 1, 10 or 1004: beyond the grid, index 0 alone is reduced -- the replay
@@ -95,6 +102,7 @@ JOBS = {"a": ("L96", 40, 512, "posterior", 64, 100), "b": ("L63", 3, 65536, "pos
 WEIGHTED = {"aw": ("a", True), "aw0": ("a", False), "bw": ("b", True), "bw0": ("b", False)}      # job -> (its unweighted twin, paths stored)
 FILTER = {f"{t}f{n}_{f}": (t, n, 0.1 * f) for t in "ab" for n in (64, 1024) for f in (0, 5)}      # job -> (context of, particles, ess_fraction)
 STATS = {f"{t}s{n}_{f}": (t, n, 0.1 * f) for t in "ab" for n in (64, 1024) for f in (0, 5)}       # job -> as FILTER
+EVENTS = {f"{t}e{n}": (t, n, 0.5) for t in "ab" for n in (64, 1024)}       # job -> as FILTER
 MOMENTS = {f"{t}m{n}_{s}": (t, n, s) for t in "ab" for n in (64, 1024) for s in (1, 10, N_PTS + 3)}          # job -> (context of, particles, stride)
 COV = {f"{t}c{n}_{s}": (t, n, s) for t in "ab" for n in (64, 1024) for s in (1, 10, N_PTS + 3) if t == "b" or s > 1}          # job -> as MOMENTS
 PATHS = {f"{t}p{n}_{k}": (t, n, k) for t in "ab" for n in (64, 1024) for k in (16, 64)}           # job -> (context of, particles, trajectories)
@@ -176,10 +184,10 @@ def run(job, rounds, calls, numpy_problems, cache, filter_problems=0, paths_stri
     from bench_problem_batch import StreamTimer, make_contexts
     twin, stored = WEIGHTED.get(job, (job, True))
     weighted = job in WEIGHTED
-    if job in FILTER or job in STATS or job in MOMENTS or job in COV or job in PATHS or job in BACKWARD or job in GIBBS:
-        twin = (FILTER.get(job) or STATS.get(job) or MOMENTS.get(job) or COV.get(job) or PATHS.get(job) or BACKWARD.get(job) or GIBBS[job])[0]
+    if job in FILTER or job in STATS or job in EVENTS or job in MOMENTS or job in COV or job in PATHS or job in BACKWARD or job in GIBBS:
+        twin = (FILTER.get(job) or STATS.get(job) or EVENTS.get(job) or MOMENTS.get(job) or COV.get(job) or PATHS.get(job) or BACKWARD.get(job) or GIBBS[job])[0]
     name, d, B, kind, n_paths, stride = JOBS[twin]
-    if (job in FILTER or job in STATS or job in MOMENTS or job in COV or job in PATHS or job in BACKWARD or job in GIBBS) and twin == "b" and filter_problems:
+    if (job in FILTER or job in STATS or job in EVENTS or job in MOMENTS or job in COV or job in PATHS or job in BACKWARD or job in GIBBS) and twin == "b" and filter_problems:
         B = min(B, filter_problems)
     if (name, B) not in cache:                        # (b and c share a context)
         from helpers import SEED, build_problem
@@ -218,6 +226,37 @@ def run(job, rounds, calls, numpy_problems, cache, filter_problems=0, paths_stri
                 "filter_rounds_ms": [round(v, 4) for v in per_round["filter"]],
                 "observations": int(c.n_obs), "resampled_share": round(float(res0["filter"]["resampled"].mean()), 3),
                 "d2h_mb": round(8.0 * B * (n_paths * (1 + d) + 3 * d) / 1e6, 1)}
+    if job in EVENTS:
+        _, n_paths, frac = EVENTS[job]
+        flt0 = c.particle_filter(n_paths, 1, ess_fraction=frac)
+        levels, side = flt0["state"].mean(axis=1), np.where(np.arange(d) % 2 == 0, 1, -1)
+        calls_of = {"filter": lambda: c.particle_filter(n_paths, 1, ess_fraction=frac),
+                    "statistics": lambda: c.particle_statistics(n_paths, 1, ess_fraction=frac),
+                    "events": lambda: c.particle_events(n_paths, 1, levels, side=side, ess_fraction=frac)}
+        res0 = {k: f() for k, f in calls_of.items()}      # warm-up (first-use allocations)
+        assert all(np.array_equal(res0["filter"][k], res0["events"][k]) for k in ("log_w", "state", "ess", "resampled"))
+        ev = res0["events"]
+        assert ev["mean"].shape == (B, 3, d) and ev["cdf"].shape == (B, N_PTS, d) and np.all(np.isfinite(ev["mean"])) and np.all(np.diff(ev["cdf"], axis=1) >= 0.0)
+        per_round = {k: [] for k in calls_of}
+        for _ in range(rounds):
+            ms = {k: [] for k in calls_of}
+            for _ in range(calls):
+                for k, f in calls_of.items():
+                    ms[k].append(tm.ms(f))
+            for k in calls_of:
+                per_round[k].append(float(np.median(ms[k])))
+        med = {k: float(np.median(v)) for k, v in per_round.items()}
+        return {"job": job, "model": name, "D": d, "Np": N_PTS, "B": B, "kind": "events", "n_paths": n_paths, "ess_fraction": frac, "stride": 1,
+                "events_ms_per_call": round(med["events"], 4), "statistics_ms_per_call": round(med["statistics"], 4),
+                "filter_ms_per_call": round(med["filter"], 4), "events_over_statistics": round(med["events"] / med["statistics"], 4),
+                "events_over_filter": round(med["events"] / med["filter"], 4),
+                "events_rounds_ms": [round(v, 4) for v in per_round["events"]],
+                "statistics_rounds_ms": [round(v, 4) for v in per_round["statistics"]],
+                "filter_rounds_ms": [round(v, 4) for v in per_round["filter"]],
+                "observations": int(c.n_obs), "resampled_share": round(float(res0["filter"]["resampled"].mean()), 3),
+                "prob_crossed_median": round(float(np.median(ev["cdf"][:, -1])), 4),
+                "events_d2h_mb": round(8.0 * B * (n_paths * (1 + d) + 3 * d + N_PTS * d) / 1e6, 1),
+                "statistics_d2h_mb": round(8.0 * B * (n_paths * (1 + d) + 3 * d) / 1e6, 1)}
     if job in MOMENTS:
         _, n_paths, stride = MOMENTS[job]
         calls_of = {"filter": lambda: c.particle_filter(n_paths, 1, ess_fraction=0.5),
@@ -459,6 +498,7 @@ def main():
     ap.add_argument("--numpy-problems", type=int, default=2)
     ap.add_argument("--filter-problems", type=int, default=0, help="cap on B of the b context's filter jobs (0: none)")
     ap.add_argument("--statistics", action="store_true", help="run the as* and bs* jobs (particle_statistics beside particle_filter)")
+    ap.add_argument("--events", action="store_true", help="run the ae* and be* jobs (particle_events beside particle_statistics and particle_filter)")
     ap.add_argument("--moments", action="store_true", help="run the am* and bm* jobs (particle_moments beside particle_filter)")
     ap.add_argument("--covariance", action="store_true", help="run the ac* and bc* jobs (particle_covariance beside particle_moments and particle_filter)")
     ap.add_argument("--paths", action="store_true", help="run the ap* and bp* jobs (particle_paths beside particle_filter)")
@@ -478,6 +518,8 @@ def main():
         return
     if args.statistics:
         args.jobs = ",".join(sorted(STATS))
+    if args.events:
+        args.jobs = ",".join(sorted(EVENTS))
     if args.moments:
         args.jobs = ",".join(sorted(MOMENTS))
     if args.covariance:

@@ -37,7 +37,7 @@ BWD_IDS = {"none": 0, "psi": 1, "q": 2}
 SYMBOLS = ["vgpa_create", "vgpa_destroy", "vgpa_last_error", "vgpa_abi_version", "vgpa_device_count",
            "vgpa_synchronize", "vgpa_stream", "vgpa_solve_fwd", "vgpa_solve_bwd", "vgpa_energy",
            "vgpa_obs_energy", "vgpa_free_energy", "vgpa_gradient", "vgpa_sweep", "vgpa_energy_parts",
-           "vgpa_fetch", "vgpa_theta_gradient", "vgpa_lag_covariance", "vgpa_sample_paths", "vgpa_sample_paths_weighted", "vgpa_particle_filter", "vgpa_particle_statistics", "vgpa_particle_moments", "vgpa_particle_covariance", "vgpa_particle_paths", "vgpa_particle_backward_paths", "vgpa_particle_conditional", "vgpa_particle_forecast", "vgpa_sweep_dev", "vgpa_free_energy_dev", "vgpa_sweep_enqueue", "vgpa_fetch_f",
+           "vgpa_fetch", "vgpa_theta_gradient", "vgpa_lag_covariance", "vgpa_sample_paths", "vgpa_sample_paths_weighted", "vgpa_particle_filter", "vgpa_particle_statistics", "vgpa_particle_events", "vgpa_particle_moments", "vgpa_particle_covariance", "vgpa_particle_paths", "vgpa_particle_backward_paths", "vgpa_particle_conditional", "vgpa_particle_forecast", "vgpa_sweep_dev", "vgpa_free_energy_dev", "vgpa_sweep_enqueue", "vgpa_fetch_f",
            "vgpa_dev_alloc", "vgpa_dev_free", "vgpa_memcpy_h2d", "vgpa_memcpy_d2h",
            "vgpa_profile_begin", "vgpa_profile_end", "vgpa_ld_gemm", "vgpa_ld_stage", "vgpa_gradient_dev", "vgpa_energy_full", "vgpa_set_option", "vgpa_is_streaming", "vgpa_path_info", "vgpa_set_prior_energy",
            "vgpa_set_problem_data", "vgpa_set_problem_params", "vgpa_set_problem_obs_model",
@@ -146,6 +146,8 @@ def load():
                                          c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vgpa_particle_statistics.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_uint64, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.vgpa_particle_events.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_uint64, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vgpa_particle_moments.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_uint64, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vgpa_particle_covariance.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_uint64, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -696,6 +698,42 @@ class Context:
                                                        _ptr(mu), _ptr(tau), _ptr(log_w), _ptr(state), _ptr(stats), _ptr(mean), _ptr(ess),
                                                        _ptr(flags)))
         return {"log_w": log_w, "state": state, "ess": ess, "resampled": flags, "mean": mean, "stats": stats}
+
+    def _event_inputs(self, levels, side):
+        """levels and side of particle_events laid out for the C ABI: (B, D) float64 and (B, D) int32.  A scalar or (D,) is every problem's."""
+        lev = np.asarray(levels, dtype=np.float64)
+        if lev.size not in (1, self.D, self.B * self.D):
+            raise ValueError(f"levels has {lev.size} entries, expected 1, {self.D} or {self.B * self.D}")
+        lev = _c64(np.broadcast_to(lev.reshape(-1, self.D) if lev.size > 1 else lev.reshape(1, 1), (self.B, self.D)))
+        if not np.all(np.isfinite(lev)):
+            raise ValueError("levels must be finite")
+        sd = np.asarray(side)
+        if sd.size not in (1, self.D, self.B * self.D):
+            raise ValueError(f"side has {sd.size} entries, expected 1, {self.D} or {self.B * self.D}")
+        if not np.all((sd == 1) | (sd == -1)):
+            raise ValueError("side must be +1 or -1")
+        sd = np.ascontiguousarray(np.broadcast_to(sd.reshape(-1, self.D) if sd.size > 1 else sd.reshape(1, 1), (self.B, self.D)), dtype=np.int32)
+        return lev, sd
+
+    def particle_events(self, n_paths, seed, levels, side=1, stride=1, ess_fraction=0.5, x=None, x0=None, prior=None, per_particle=False):
+        """Path events of particle_filter's lineages (vgpa_particle_events): the same walk and resampling decisions, every slot carrying the
+        row (X, T, N) of g_j(x) = side_j (x_j - levels_j) along its lineage: the largest g, the first grid index with g > 0 (Np: never) and
+        the number of grid indices with g > 0.  levels, side: (B, D), or (D,) or a scalar for every problem; side is +1 (above the level) or
+        -1 (below it).  Returns a dict: log_w, state, ess, resampled as particle_filter (bit for bit), mean (B, 3, D): the self-normalised
+        weighted mean of the rows, cdf (B, n_keep, D): the weighted share of lineages with T <= k at the grid indices k = 0, stride, ...,
+        both reduced on the device, and rows (B, n_paths, 3, D): the rows themselves (per_particle=True, else None)."""
+        n_paths, stride = int(n_paths), int(stride)
+        self._fit32(n_paths=n_paths, stride=stride)
+        lev, sd = self._event_inputs(levels, side)
+        xx, s0, mu, tau = self._walk_inputs(x, x0, prior)
+        n = max(n_paths, 0)
+        log_w, state, ess, flags = self._filter_outputs(n)
+        mean, cdf = np.empty((self.B, 3, self.D)), np.empty((self.B, (self.Np - 1) // max(stride, 1) + 1, self.D))
+        rows = np.empty((self.B, n, 3, self.D)) if per_particle else None
+        self._check(self._lib.vgpa_particle_events(self._h, _ptr(xx), _ptr(s0), n_paths, stride, int(seed) & 0xFFFFFFFFFFFFFFFF, float(ess_fraction),
+                                                   _ptr(mu), _ptr(tau), _ptr(lev), _ptr(sd), _ptr(log_w), _ptr(state), _ptr(rows), _ptr(mean),
+                                                   _ptr(cdf), _ptr(ess), _ptr(flags)))
+        return {"log_w": log_w, "state": state, "ess": ess, "resampled": flags, "mean": mean, "cdf": cdf, "rows": rows}
 
     def particle_moments(self, n_paths, seed, stride=1, ess_fraction=0.5, x=None, x0=None, prior=None):
         """The smoothing moments on the grid under particle_filter's genealogy (vgpa_particle_moments): the filter, its final weights pushed

@@ -236,6 +236,18 @@ class ProblemBatch(object):
         res = self._context().particle_statistics(n_paths, seed, ess_fraction=ess_fraction, x=xx, x0=x0, prior=prior, per_particle=per_particle)
         return [v._statistics_record(res, k, np.asarray(v._inputs()["obs_t"]).size) for k, v in enumerate(self.vgps)]
 
+    def particle_events(self, n_paths, seed, levels, side=1, stride=1, ess_fraction=0.5, x=None, x0=None, per_particle=False):
+        """One particles.PathEvents per member (VarGP.particle_events): the filter of particle_filter with the same arguments, each particle
+        carrying the event records of its lineage.  levels and side: (B, D) for per-member levels and sides, or (D,) or a scalar for all."""
+        xx = None if x is None else self._stack(x)
+        d = self.vgps[0].dim_d
+        prior = (np.stack([v._prior()[0][0] for v in self.vgps]), np.stack([v._prior()[1][0] for v in self.vgps]).reshape(self.B, d, d))
+        res = self._context().particle_events(n_paths, seed, levels, side=side, stride=stride, ess_fraction=ess_fraction, x=xx, x0=x0, prior=prior,
+                                              per_particle=per_particle)
+        lev = np.broadcast_to(np.asarray(levels, dtype=float).reshape(-1, d) if np.size(levels) > 1 else np.reshape(levels, (1, 1)), (self.B, d))
+        sd = np.broadcast_to(np.asarray(side).reshape(-1, d) if np.size(side) > 1 else np.reshape(side, (1, 1)), (self.B, d))
+        return [v._events_record(res, k, lev[k], sd[k], stride, np.asarray(v._inputs()["obs_t"]).size) for k, v in enumerate(self.vgps)]
+
     def particle_moments(self, n_paths, seed, stride=1, ess_fraction=0.5, x=None, x0=None):
         """One particles.SmoothingMoments per member (VarGP.particle_moments): the smoothing mean and second moment on the grid under the
         genealogy of the member's own filter, with its own data, observation times and count, prior, theta and Sigma."""

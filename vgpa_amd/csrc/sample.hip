@@ -40,6 +40,9 @@
 //   Conditional  | a segment in which slot 0 of every problem is pinned to a reference trajectory: it draws nothing, is weighted by | s.4.18
 //                | the increment the reference implies and follows the reference bit for bit  [k_pf_pin: slot 0 of the start;       |
 //                | k_pf_cresample: the step between two segments, multinomial, with ancestor sampling for slot 0; k_pf_ref_fill]    |
+//   SegmentEvents| a segment that also carries each slot's [3][D] row of event records (X, T, N) of g_j(x) = s_j (x_j - c_j): the      | s.4.20
+//                | largest g, the first grid index with g > 0, the number of such indices  [k_pf_events_start: the rows of grid      |
+//                | index 0; k_pf_resample<true>, k_pf_stats_mean as for SegmentStats; k_pf_events_cdf: the first-passage distribution] |
 #include "vgpa_internal.h"
 
 #include <type_traits>
@@ -155,17 +158,24 @@ __device__ __forceinline__ double wave_max(double v) {
 struct ConditionalArgs : SampleArgs {
   const double* pf_ref;      // [B][Np][D]
 };
+// ... and for SegmentEvents alone the levels and sides of its events
+struct EventArgs : SampleArgs {
+  const double* ev_level;    // [B][D]
+  const int32_t* ev_side;    // [B][D] +1 / -1
+};
 template <Walk K> struct WalkArgsOf { using type = SampleArgs; };
 template <> struct WalkArgsOf<Walk::Conditional> { using type = ConditionalArgs; };
+template <> struct WalkArgsOf<Walk::SegmentEvents> { using type = EventArgs; };
 template <Walk K> using WalkArgs = typename WalkArgsOf<K>::type;
 
 // What the two kernels branch on, per walk: W the walk of the weighted kind (posterior drift, diagonal R), SEG it runs (k_begin, k_end] from
 // and to pf_x, ST it carries the rows of pf_stats, MO it takes the moments of the replay, LN the counter words come from pf_slots;
 // FC it is the forecast (the model's drift from the cloud in pf_x, k_sample_small only); CV the replay's second moments are the whole matrix
 // (with MO); BW: the state is reloaded from the filter's histories behind every observation (with LN); CD: slot 0 is pinned to pf_ref of
-// ConditionalArgs (with SEG); WS: the weight sums are formed.  The ten rows are all there is: no other combination can be instantiated.
+// ConditionalArgs (with SEG); EV: it carries the event records of EventArgs' levels and sides in the rows of pf_stats (with SEG); WS: the
+// weight sums are formed.  The eleven rows are all there is: no other combination can be instantiated.
 struct WalkTraits {
-  bool W, SEG, ST, MO, LN, FC, CV, BW, CD;
+  bool W, SEG, ST, MO, LN, FC, CV, BW, CD, EV;
   constexpr bool WS() const { return W && !MO; }
 };
 constexpr WalkTraits kWalkTraits[] = {      // in the order of Walk
@@ -178,7 +188,8 @@ constexpr WalkTraits kWalkTraits[] = {      // in the order of Walk
     {false, false, false, false, false, true},     // Forecast
     {true,  true,  false, true,  false, false, true},     // ReplayCov
     {false, false, false, false, true,  false, false, true},     // Backward
-    {true,  true,  false, false, false, false, false, false, true}};    // Conditional
+    {true,  true,  false, false, false, false, false, false, true},     // Conditional
+    {true,  true,  false, false, false, false, false, false, false, true}};    // SegmentEvents
 
 // Weighted: posterior kind, diagonal R: both drifts at x_{k-1}, d = g - f, and per step -sum_i d_i (eta_i + dt d_i / 2) / Sigma_ii with
 // 1 / Sigma_ii = dt / R_ii^2; the observation term at the lane's own problem's times.
@@ -205,6 +216,9 @@ constexpr WalkTraits kWalkTraits[] = {      // in the order of Walk
 // Conditional: a segment in which the lane of slot 0 holds x_{k-1} = pf_ref[p][k-1] bit for bit, draws nothing and puts
 // eta* = (ref_k - x_{k-1}) - dt g(x_{k-1}) where the other lanes put R xi: the step term, the observation term and the sums are the segment's; its
 // state becomes ref_k as loaded (D loads per step for that one lane).  Every other lane is the segment's, bit for bit.
+// SegmentEvents: a segment, bit for bit, that behind every step k holds d = x_j(k) - c_j (one subtraction), g = d or -d by the side, and
+// X_j = fmax(X_j, g); where g > 0, T_j = min(T_j, k) and N_j += 1.  The slot's row of pf_stats is read at the segment's entry and written at
+// its exit, T and N as the doubles the integers are; in between they are 32-bit integers.  (The row of grid index 0 is k_pf_events_start's.)
 // Walk::Backward: x = the particle slot `word` was copied from at observation j of problem p
 template <int D>
 __device__ __forceinline__ void backward_reload(const SampleArgs& a, uint32_t p, int j, uint32_t word, double* x) {
@@ -217,7 +231,7 @@ __device__ __forceinline__ void backward_reload(const SampleArgs& a, uint32_t p,
 template <int D, Walk K>
 __global__ __launch_bounds__(256) void k_sample_small(WalkArgs<K> a) {
   constexpr WalkTraits T = kWalkTraits[(int)K];
-  constexpr bool W = T.W, SEG = T.SEG, ST = T.ST, MO = T.MO, LN = T.LN, FC = T.FC, CV = T.CV, BW = T.BW, CD = T.CD, WS = T.WS();
+  constexpr bool W = T.W, SEG = T.SEG, ST = T.ST, MO = T.MO, LN = T.LN, FC = T.FC, CV = T.CV, BW = T.BW, CD = T.CD, EV = T.EV, WS = T.WS();
   constexpr int NV = CV ? D + D * (D + 1) / 2 : 2 * D;      // values a kept k reduces
   size_t gid;
   uint32_t p, path;
@@ -357,6 +371,16 @@ __global__ __launch_bounds__(256) void k_sample_small(WalkArgs<K> a) {
       sq[i] = a.pf_stats[gid * 3 * D + i]; sg1[i] = a.pf_stats[gid * 3 * D + D + i]; sh[i] = a.pf_stats[gid * 3 * D + 2 * D + i];
     }
   }
+  double ec[EV ? D : 1], ex[EV ? D : 1];      // SegmentEvents: the levels, the slot's row; the sides as a bit per component
+  int et[EV ? D : 1], en[EV ? D : 1], eneg = 0;
+  if constexpr (EV) {
+#pragma unroll
+    for (int i = 0; i < D; i++) {
+      ec[i] = a.ev_level[(size_t)p * D + i];
+      eneg |= a.ev_side[(size_t)p * D + i] < 0 ? 1 << i : 0;
+      ex[i] = a.pf_stats[gid * 3 * D + i]; et[i] = (int)a.pf_stats[gid * 3 * D + D + i]; en[i] = (int)a.pf_stats[gid * 3 * D + 2 * D + i];
+    }
+  }
   const double* A = a.A + (size_t)p * a.stride_x;
   const double* bv = a.b + (size_t)p * a.stride_x;
   int until = a.stride, slot = 0;
@@ -404,6 +428,11 @@ __global__ __launch_bounds__(256) void k_sample_small(WalkArgs<K> a) {
       }
       x[i] = (x[i] + a.dt * f[i]) + s;
       if constexpr (CD) { if (pin) x[i] = xr[i]; }      // (as loaded, not as recomputed)
+      if constexpr (EV) {
+        const double d = x[i] - ec[i], g = (eneg >> i) & 1 ? -d : d;
+        ex[i] = fmax(ex[i], g);
+        if (g > 0.0) { et[i] = min(et[i], k); en[i] += 1; }
+      }
     }
     if constexpr (WS) {
       if (k == oc.next) { ow += obs_form<D>(a, p, oc.cur, x); oc.advance(); }
@@ -451,6 +480,12 @@ __global__ __launch_bounds__(256) void k_sample_small(WalkArgs<K> a) {
 #pragma unroll
       for (int i = 0; i < D; i++) {
         a.pf_stats[gid * 3 * D + i] = sq[i]; a.pf_stats[gid * 3 * D + D + i] = sg1[i]; a.pf_stats[gid * 3 * D + 2 * D + i] = sh[i];
+      }
+    }
+    if constexpr (EV) {
+#pragma unroll
+      for (int i = 0; i < D; i++) {
+        a.pf_stats[gid * 3 * D + i] = ex[i]; a.pf_stats[gid * 3 * D + D + i] = (double)et[i]; a.pf_stats[gid * 3 * D + 2 * D + i] = (double)en[i];
       }
     }
   } else if constexpr (W) { a.logw[2 * gid] = pw; a.logw[2 * gid + 1] = -0.5 * ow - obs_constant(a, p); }
@@ -516,10 +551,14 @@ __device__ __forceinline__ void normals_c(uint32_t k0, uint32_t k1, uint32_t k, 
 // Conditional: as in k_sample_small.  Slot 0 is path column 0 of wave 0 of workgroup (p, 0): its four lanes request their rows of ref_k
 // with the step's A_k, put eta* into nz before the weight term is formed and ref_k into x before the step's own write of x to Xs -- no
 // barrier is added, and the model drift of the next step reads the reference from the column of Xs as it reads every other path.
+// SegmentEvents: as in k_sample_small, lane-local: the lane holds X, T, N of its own rows mt * 16 + q + 4 r of its path's row of pf_stats, read
+// at the segment's entry, updated behind the step's own update of x and written at its exit; the levels lie in LDS as bs does ([NT], in the
+// Zs region) and are read where they are used.  A row beyond D and a lane behind the last path compute on zeros and store nothing.  No
+// barrier or cross-lane step is added.
 template <int NT, Walk K>
 __global__ __launch_bounds__(256) void k_sample_mfma(WalkArgs<K> a) {
   constexpr WalkTraits T = kWalkTraits[(int)K];
-  constexpr bool W = T.W, SEG = T.SEG, ST = T.ST, MO = T.MO, LN = T.LN, CV = T.CV, BW = T.BW, CD = T.CD, WS = T.WS();
+  constexpr bool W = T.W, SEG = T.SEG, ST = T.ST, MO = T.MO, LN = T.LN, CV = T.CV, BW = T.BW, CD = T.CD, EV = T.EV, WS = T.WS();
   using Sh = MfmaShape<NT>;
   constexpr int LDA = Sh::LDA, MT = Sh::MT, KT = Sh::KT, NPF = Sh::NPF;
   extern __shared__ double lds[];
@@ -627,6 +666,24 @@ __global__ __launch_bounds__(256) void k_sample_mfma(WalkArgs<K> a) {
         const int row = mt * 16 + q + 4 * r;
         const bool mine = path < (uint32_t)a.n_paths && row < D;
         sq[mt][r] = mine ? row0[row] : 0.0; sg1[mt][r] = mine ? row0[D + row] : 0.0;
+      }
+  }
+  // SegmentEvents: the records of the lane's rows; the sides as a bit per row; the levels [NT] at the head of the Zs region, which a segment
+  // does not use (written in front of the barrier below)
+  double ex[EV ? MT : 1][4];
+  int et[EV ? MT : 1][4], en[EV ? MT : 1][4], eneg = 0;
+  const double* evc = lds + NT * LDA + NT + 4 * NT * 16;
+  if constexpr (EV) {
+    const double* row0 = a.pf_stats + ((size_t)p * a.n_paths + path) * 3 * D;
+    if (tid < NT) lds[NT * LDA + NT + 4 * NT * 16 + tid] = tid < D ? a.ev_level[(size_t)p * D + tid] : 0.0;
+#pragma unroll
+    for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const int row = mt * 16 + q + 4 * r;
+        const bool mine = path < (uint32_t)a.n_paths && row < D;
+        eneg |= row < D && a.ev_side[(size_t)p * D + row] < 0 ? 1 << (mt * 4 + r) : 0;
+        ex[mt][r] = mine ? row0[row] : 0.0; et[mt][r] = mine ? (int)row0[D + row] : 0; en[mt][r] = mine ? (int)row0[2 * D + row] : 0;
       }
   }
   ObsCursor oc;
@@ -875,6 +932,14 @@ __global__ __launch_bounds__(256) void k_sample_mfma(WalkArgs<K> a) {
           for (int r = 0; r < 4; r++) x[mt][r] = xref[mt][r];
         }
       }
+      if constexpr (EV) {
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+          const double d = x[mt][r] - evc[mt * 16 + q + 4 * r], g = (eneg >> (mt * 4 + r)) & 1 ? -d : d;
+          ex[mt][r] = fmax(ex[mt][r], g);
+          if (g > 0.0) { et[mt][r] = min(et[mt][r], k); en[mt][r] += 1; }
+        }
+      }
     }
     __syncthreads();
     if constexpr (MO && !CV) flush();
@@ -925,6 +990,18 @@ __global__ __launch_bounds__(256) void k_sample_mfma(WalkArgs<K> a) {
             for (int r = 0; r < 4; r++) {
               const int row = mt * 16 + q + 4 * r;
               if (row < D) { row0[row] = sq[mt][r]; row0[D + row] = sg1[mt][r]; row0[2 * D + row] = h; }
+            }
+        }
+      }
+      if constexpr (EV) {
+        if (path < (uint32_t)a.n_paths) {
+          double* row0 = a.pf_stats + ((size_t)p * a.n_paths + path) * 3 * D;
+#pragma unroll
+          for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+              const int row = mt * 16 + q + 4 * r;
+              if (row < D) { row0[row] = ex[mt][r]; row0[D + row] = (double)et[mt][r]; row0[2 * D + row] = (double)en[mt][r]; }
             }
         }
       }
@@ -1394,6 +1471,81 @@ __global__ __launch_bounds__(256) void k_pf_normalise(int n, const double* lw_al
   for (int i = tid; i < n; i += 256) w[i] = exp(lw[i] - mx) / s;
 }
 
+// ---- path events: the rows of grid index 0, the first-passage distribution ---------------------------------------------
+// Behind k_pf_start, one thread per (problem, particle, component): the record of grid index 0 from the particle's state, in front of the
+// first segment and of a resampling decision at grid index 0.  Np is the sentinel "never so far".
+__global__ __launch_bounds__(256) void k_pf_events_start(int D, int n, int Np, size_t total, const double* x, const double* level, const int32_t* side,
+                                                         double* rows) {
+  const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= total) return;
+  const size_t slot = g / D, j = g - slot * D, p = slot / n;
+  const double d = x[g] - level[p * D + j], ev = side[p * D + j] < 0 ? -d : d;
+  double* row = rows + slot * 3 * D + j;
+  row[0] = ev; row[D] = ev > 0.0 ? 0.0 : (double)Np; row[2 * (size_t)D] = ev > 0.0 ? 1.0 : 0.0;
+}
+
+// The first-passage distribution on the kept grid, workgroup (p, j) for component j of problem p: cdf[p][k'][j] = sum_i W_i 1[T_ij <= k' stride],
+// W_i = w_i / S, w_i = exp(lw_i - max lw).  The bin of T is ceil(T / stride), no bin beyond the last kept index (the sentinel Np always is).
+// S is block_sum's fixed order.  The kept indices go in tiles of kCdfTile bins of LDS; per tile the particles' (bin, w) stream through LDS 256
+// at a time in increasing i, and thread t, which owns the kCdfTile / 256 consecutive bins from t kCdfTile / 256 on, adds to its own bins the
+// w_i that fall into them, in increasing i.  Then the inclusive prefix sums in increasing bin order -- each thread over its own bins, the
+// threads' totals in thread order by one thread, the tiles behind one another through `carry` -- and the division by S: every value is the
+// value before it plus a sum of weights >= 0, so the row is non-decreasing to the bit, and no addition depends on the launch or the batch.
+constexpr int kCdfTile = 2048;
+__global__ __launch_bounds__(256) void k_pf_events_cdf(int D, int n, int Np, int stride, const double* lw_all, const double* rows_all, double* cdf_all) {
+  constexpr int PER = kCdfTile / 256;
+  __shared__ double bins[kCdfTile], ws[256], base[257], red[4];
+  __shared__ int bs[256];
+  const int p = blockIdx.x, j = blockIdx.y, tid = threadIdx.x;
+  const int n_keep = (Np - 1) / stride + 1;
+  const double* lw = lw_all + (size_t)p * n;
+  const double* tcol = rows_all + (size_t)p * n * 3 * D + D + j;      // T_ij at tcol[i 3 D]
+  double* cdf = cdf_all + (size_t)p * n_keep * D + j;                 // cdf[k'] at cdf[k' D]
+  const double mx = pf_max(lw, n, red);
+  double S = 0.0;
+  for (int i = tid; i < n; i += 256) S += exp(lw[i] - mx);
+  S = block_sum(S, red);
+  double carry = 0.0;
+  for (int tile = 0; tile < n_keep; tile += kCdfTile) {
+#pragma unroll
+    for (int e = 0; e < PER; e++) bins[tid * PER + e] = 0.0;
+    for (int i0 = 0; i0 < n; i0 += 256) {
+      __syncthreads();      // (the particles before have been read; the first pass: `base` of the tile before)
+      const int i = i0 + tid;
+      int b = -1;
+      double wi = 0.0;
+      if (i < n) {
+        const long long bin = ((long long)tcol[(size_t)i * 3 * D] + stride - 1) / stride - tile;
+        if (bin >= 0 && bin < kCdfTile && bin + tile < n_keep) b = (int)bin;
+        wi = exp(lw[i] - mx);
+      }
+      bs[tid] = b; ws[tid] = wi;
+      __syncthreads();
+      const int cnt = n - i0 < 256 ? n - i0 : 256;
+      for (int m = 0; m < cnt; m++) {
+        const int bm = bs[m];
+        if (bm >= 0 && bm / PER == tid) bins[bm] += ws[m];
+      }
+    }
+    double run = 0.0;      // the thread's own bins: their inclusive prefix sums in place, their total
+#pragma unroll
+    for (int e = 0; e < PER; e++) { run += bins[tid * PER + e]; bins[tid * PER + e] = run; }
+    base[tid + 1] = run;
+    __syncthreads();
+    if (tid == 0) {
+      base[0] = carry;
+      for (int t = 0; t < 256; t++) base[t + 1] = base[t] + base[t + 1];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < PER; e++) {
+      const int kp = tile + tid * PER + e;
+      if (kp < n_keep) cdf[(size_t)kp * D] = (base[tid] + bins[tid * PER + e]) / S;
+    }
+    carry = base[256];
+  }
+}
+
 // The step between two segments of the replay at grid index a.k: workgroup (p, y) moves its share of problem p's particles from x_in to
 // x_out by the ancestors the filter stored for the problem's observation at a.k (the identity where the cloud was carried on), or
 // unchanged where the problem has no observation there.
@@ -1763,13 +1915,15 @@ __global__ __launch_bounds__(256) void k_pf_ref_fill(PfArgs a, int rows, const i
 
 // One walk at the D of the arguments: k_sample_small<D, K> up to D = 4 (one lane per path; the replay: the problem in grid.x, 256 slots per
 // workgroup in grid.y), above it k_sample_mfma<NT, K> with NT the next multiple of 16 (grid: problems x 64 paths).  D = 2 exists for the
-// plain walk only: every other walk needs a stochastic model, and none has D = 2.  (Ten walks: 3 instantiations of k_sample_small each
+// plain walk only: every other walk needs a stochastic model, and none has D = 2.  (Eleven walks: 3 instantiations of k_sample_small each
 // and one more for Plain, 4 of k_sample_mfma each but Forecast.)
 template <Walk K>
-hipError_t launch_walk(const SampleArgs& base, hipStream_t st, const double* pf_ref = nullptr) {
+hipError_t launch_walk(const SampleArgs& base, hipStream_t st, const double* pf_ref = nullptr, const double* ev_level = nullptr,
+                       const int32_t* ev_side = nullptr) {
   WalkArgs<K> a;
   static_cast<SampleArgs&>(a) = base;
   if constexpr (K == Walk::Conditional) a.pf_ref = pf_ref;
+  if constexpr (K == Walk::SegmentEvents) { a.ev_level = ev_level; a.ev_side = ev_side; }
   if (a.D <= kMaxLaneD) {
     const dim3 grid = kWalkTraits[(int)K].MO || kWalkTraits[(int)K].FC ? dim3(a.batch, sample_segment_blocks(a.D, a.n_paths))
                                         : dim3((unsigned)(((size_t)a.batch * a.n_paths + 255) / 256));
@@ -1928,8 +2082,22 @@ hipError_t launch_pf_stats_mean(int D, int batch, int n_paths, const double* lw,
   return hipGetLastError();
 }
 
+hipError_t launch_pf_events_start(int D, int batch, int n_paths, int Np, const double* x, const double* level, const int32_t* side, double* rows,
+                                  hipStream_t st) {
+  const size_t total = (size_t)(batch > 0 ? batch : 0) * (size_t)(n_paths > 0 ? n_paths : 0) * (size_t)(D > 0 ? D : 0);
+  if (D < 1 || D > kMaxSmallD || batch < 1 || n_paths < 1 || Np < 1 || !pf_flat_grid_fits(total) || !x || !level || !side || !rows) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_pf_events_start, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, D, n_paths, Np, total, x, level, side, rows);
+  return hipGetLastError();
+}
+
+hipError_t launch_pf_events_cdf(int D, int batch, int n_paths, int Np, int stride, const double* lw, const double* rows, double* cdf, hipStream_t st) {
+  if (D < 1 || D > kMaxSmallD || batch < 1 || n_paths < 1 || Np < 1 || stride < 1 || !lw || !rows || !cdf) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_pf_events_cdf, dim3(batch, D), dim3(256), 0, st, D, n_paths, Np, stride, lw, rows, cdf);
+  return hipGetLastError();
+}
+
 // The walk is what the caller says it is; the fields that walk reads must be set, and the fields that would have meant another walk must not.
-hipError_t launch_sample_walk(Walk w, const SampleArgs& a, hipStream_t st, const double* pf_ref) {
+hipError_t launch_sample_walk(Walk w, const SampleArgs& a, hipStream_t st, const double* pf_ref, const double* ev_level, const int32_t* ev_side) {
   if (a.D < 1 || a.D > kMaxSmallD || a.n_paths < 1) return hipErrorInvalidValue;
   const bool known_model = a.model == VGPA_MODEL_OU || a.model == VGPA_MODEL_DW || a.model == VGPA_MODEL_L63 || a.model == VGPA_MODEL_L96;
   // the weighted kind: the posterior process with diagonal factors against the model's drift; above D = 4 the model is Lorenz-96
@@ -1937,6 +2105,7 @@ hipError_t launch_sample_walk(Walk w, const SampleArgs& a, hipStream_t st, const
   const bool segment = weighable && a.pf_x && a.pf_lw && a.k_begin >= 0 && a.k_end >= a.k_begin && a.k_end < a.Np;
   if (w == Walk::Backward ? a.pf_wtab || a.pf_part : a.pf_clouds || a.pf_hanc) return hipErrorInvalidValue;      // (the histories are Backward's alone, the sums never its)
   if (w != Walk::Conditional && pf_ref) return hipErrorInvalidValue;      // (the reference is Conditional's alone)
+  if (w != Walk::SegmentEvents && (ev_level || ev_side)) return hipErrorInvalidValue;      // (the levels and sides are SegmentEvents' alone)
   switch (w) {
     case Walk::Plain: {
       if (a.stride < 1 || a.logw) return hipErrorInvalidValue;
@@ -1958,6 +2127,9 @@ hipError_t launch_sample_walk(Walk w, const SampleArgs& a, hipStream_t st, const
     case Walk::Conditional:      // (the segment's fields and the reference)
       if (!segment || a.pf_stats || a.pf_wtab || !pf_ref) return hipErrorInvalidValue;
       return launch_walk<Walk::Conditional>(a, st, pf_ref);
+    case Walk::SegmentEvents:      // (the fields of SegmentStats -- the rows are where pf_stats points -- and the levels and sides)
+      if (!segment || !a.pf_stats || a.pf_wtab || !ev_level || !ev_side) return hipErrorInvalidValue;
+      return launch_walk<Walk::SegmentEvents>(a, st, nullptr, ev_level, ev_side);
     case Walk::Replay:
       if (!segment || !a.pf_wtab || a.pf_stats || !a.pf_part || a.stride < 1 || a.pf_rows < 1) return hipErrorInvalidValue;
       if (a.n_paths > sample_max_paths(a.D)) return hipErrorInvalidValue;

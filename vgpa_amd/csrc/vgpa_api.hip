@@ -174,9 +174,11 @@ struct vgpa_ctx {
   // sums, normalised weights (PF_WTAB), partial sums, moments and slot table; vgpa_particle_covariance: the buffers of the moments (the
   // partial sums and their sum packed, sample_cov_len(D) per kept index) and PF_COV: the mean and behind it the whole matrices;
   // vgpa_particle_backward_paths: the buffers of vgpa_particle_paths, the clouds and PF_HLW: the log-weights the resamplings replaced;
-  // vgpa_particle_conditional: the buffers of vgpa_particle_paths, the clouds and PF_REF: the reference trajectories
+  // vgpa_particle_conditional: the buffers of vgpa_particle_paths, the clouds and PF_REF: the reference trajectories;
+  // vgpa_particle_events: the buffers of vgpa_particle_statistics (the rows are the event records), PF_EVC: the levels, PF_EVS: the sides
+  // (int32), PF_CDF: the first-passage distribution
   enum { PF_XA, PF_XB, PF_LW, PF_CUM, PF_ANC, PF_ESS, PF_FLAG, PF_HANC, PF_CLOUDS, PF_MU, PF_LT, PF_STA, PF_STB, PF_MEAN, PF_WTAB, PF_LESS, PF_PART,
-         PF_MOM, PF_SLOTS, PF_COV, PF_HLW, PF_REF, PF_COUNT };
+         PF_MOM, PF_SLOTS, PF_COV, PF_HLW, PF_REF, PF_EVC, PF_EVS, PF_CDF, PF_COUNT };
   double* d_pf[PF_COUNT] = {};
   size_t pf_n[PF_COUNT] = {};
   // profiling
@@ -1610,6 +1612,9 @@ struct ParticleRequest {
   bool covariance; double* cov_mean; double* cov_second;            // vgpa_particle_covariance (lineage_ess as for the moments)
   // vgpa_particle_conditional: slot 0 pinned to ref [B][Np][D]; n_draw = 1, paths: the drawn trajectory, slots_out: its slot table
   bool conditional; const double* ref;
+  // vgpa_particle_events: the rows of with_stats are the event records (X, T, N) of the levels and sides [B][D]; stats: the final rows, mean:
+  // their weighted mean, cdf: the first-passage distribution at every stride-th grid index
+  bool events; const double* levels; const int32_t* sides; double* cdf;
 };
 
 // One run: the filter, then what the request puts behind it.  The passes share the kernels' arguments, the cuts and where the particles are.
@@ -1622,6 +1627,7 @@ struct ParticleRun {
   double* st_cur; double* st_other;    // ... and their rows of path statistics (with_stats)
   int n_keep, rows, slot_rows, n_blocks; size_t mom_len, n_table, n_traj;
   int k0 = 0;                          // the forecast: the absolute grid index of the cloud
+  const double* ev_level = nullptr; const int32_t* ev_side = nullptr;      // events: the levels and sides [B][D] on the device
 
   int buf(int which, size_t count) { return grow(c, &c->d_pf[which], &c->pf_n[which], count); }      // d_pf[which]: at least `count` doubles
 
@@ -1632,7 +1638,8 @@ struct ParticleRun {
     for (int k = 0; k < c->Np; k++) {
       if (!is_obs[k] && k != c->Np - 1) continue;
       s.k_begin = prev; s.k_end = k; s.pf_x = cur;
-      hipError_t e = launch_sample_walk(walk, s, c->stream, walk == Walk::Conditional ? f.ref : nullptr);
+      const bool ev = walk == Walk::SegmentEvents;
+      hipError_t e = launch_sample_walk(walk, s, c->stream, walk == Walk::Conditional ? f.ref : nullptr, ev ? ev_level : nullptr, ev ? ev_side : nullptr);
       if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "%s failed: %s", what, hipGetErrorString(e));
       s.seg_first = 0; prev = k;
       if (!is_obs[k]) continue;
@@ -1682,6 +1689,13 @@ struct ParticleRun {
     f.h_anc = history ? reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_HANC]) : nullptr;
     f.h_clouds = q.clouds || q.backward || q.conditional ? c->d_pf[vgpa_ctx::PF_CLOUDS] : nullptr;
     f.h_lw = q.backward ? c->d_pf[vgpa_ctx::PF_HLW] : nullptr;
+    if (q.events) {      // the levels and sides: uploaded once per call, read from global memory at every segment's entry
+      const size_t BD = (size_t)B * D;
+      if ((rc = buf(vgpa_ctx::PF_EVC, BD)) || (rc = buf(vgpa_ctx::PF_EVS, ints(BD))) || (q.cdf && (rc = buf(vgpa_ctx::PF_CDF, (size_t)B * n_keep * D)))) return rc;
+      int32_t* d_side = reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_EVS]);
+      if ((rc = upload(c, c->d_pf[vgpa_ctx::PF_EVC], q.levels, BD)) || (rc = upload(c, d_side, q.sides, BD))) return rc;
+      ev_level = c->d_pf[vgpa_ctx::PF_EVC]; ev_side = d_side;
+    }
     if (q.conditional) {      // the reference trajectories: uploaded once per call, read from global memory by the walk and the steps
       const size_t n_ref = (size_t)B * c->Np * D;
       if ((rc = buf(vgpa_ctx::PF_REF, n_ref)) || (rc = upload(c, c->d_pf[vgpa_ctx::PF_REF], q.ref, n_ref))) return rc;
@@ -1700,7 +1714,8 @@ struct ParticleRun {
   }
 
   // The filter: the start, then the segments with the resampling step between them.  with_stats: the same walk, counters
-  // and resampling decisions, every slot's [3][D] row of path statistics carried along its lineage.
+  // and resampling decisions, every slot's [3][D] row of path statistics carried along its lineage.  events: with_stats
+  // with the rows of event records, which start from the particles' states at grid index 0 and not from zero.
   int filter() {
     const size_t n = (size_t)q.n_paths, BM = (size_t)c->B * f.M;
     HIP_TRY(c, hipMemsetAsync(f.h_ess, 0, BM * sizeof(double), c->stream));
@@ -1714,8 +1729,9 @@ struct ParticleRun {
         f.k = k; f.last = k == c->Np - 1 ? 1 : 0; f.x_in = cur; f.x_out = other;
         return launch_pf_cresample(f, a, c->stream);
       });
-    if (q.with_stats) HIP_TRY(c, hipMemsetAsync(st_cur, 0, 3 * (size_t)c->B * n * c->D * sizeof(double), c->stream));
-    return cuts(q.with_stats ? Walk::SegmentStats : Walk::Segment, "particle segment launch", a, "particle resampling launch", [&](int k) {
+    if (q.events) LAUNCH_TRY(c, "event start rows launch", launch_pf_events_start(c->D, c->B, q.n_paths, c->Np, cur, ev_level, ev_side, st_cur, c->stream));
+    else if (q.with_stats) HIP_TRY(c, hipMemsetAsync(st_cur, 0, 3 * (size_t)c->B * n * c->D * sizeof(double), c->stream));
+    return cuts(q.events ? Walk::SegmentEvents : q.with_stats ? Walk::SegmentStats : Walk::Segment, "particle segment launch", a, "particle resampling launch", [&](int k) {
       f.k = k; f.last = k == c->Np - 1 ? 1 : 0; f.x_in = cur; f.x_out = other; f.st_in = st_cur; f.st_out = st_other;
       std::swap(st_cur, st_other);      // (the next segment carries the rows the step is about to write)
       a.pf_stats = st_cur;
@@ -1910,7 +1926,7 @@ static int particle_run(vgpa_ctx* c, const ParticleRequest& q) {
   if (!c) return VGPA_ERR_ARG;
   if (!q.logw || !q.state) return fail(c, VGPA_ERR_ARG, "null argument");
   if (q.stride < 1) return fail(c, VGPA_ERR_ARG, "stride must be at least 1 (stride = %d)", q.stride);
-  if (q.with_stats && !q.stats && !q.mean) return fail(c, VGPA_ERR_ARG, "at least one of stats and mean must be given");
+  if (q.with_stats && !q.events && !q.stats && !q.mean) return fail(c, VGPA_ERR_ARG, "at least one of stats and mean must be given");
   const int32_t n_paths = q.n_paths, n_draw = q.n_draw, stride = q.stride;
   if (n_paths < 1) return fail(c, VGPA_ERR_ARG, "n_paths must be at least 1 (n_paths = %d)", n_paths);
   int rc;
@@ -1950,6 +1966,10 @@ static int particle_run(vgpa_ctx* c, const ParticleRequest& q) {
     if ((rc = download(c, q.mean, c->d_pf[vgpa_ctx::PF_MEAN], (size_t)B * 3 * D))) return rc;
   }
   if (q.with_stats && q.stats && (rc = download(c, q.stats, r.st_cur, 3 * BnD))) return rc;
+  if (q.events && q.cdf) {
+    LAUNCH_TRY(c, "first-passage distribution launch", launch_pf_events_cdf(D, B, n_paths, Np, stride, r.f.lw, r.st_cur, c->d_pf[vgpa_ctx::PF_CDF], c->stream));
+    if ((rc = download(c, q.cdf, c->d_pf[vgpa_ctx::PF_CDF], (size_t)B * kept * D))) return rc;
+  }
   if ((rc = download(c, q.logw, r.f.lw, (size_t)B * n)) || (!q.forecast && (rc = download(c, q.state, r.cur, BnD)))) return rc;
   if (q.ess && (rc = download(c, q.ess, r.f.h_ess, (size_t)B * M))) return rc;
   if (q.resampled && M > 0) HIP_TRY(c, hipMemcpyAsync(q.resampled, r.f.h_flag, (size_t)B * M * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
@@ -1975,6 +1995,24 @@ int vgpa_particle_statistics(vgpa_ctx* c, const double* x, const double* x0, int
                              double* ess, int32_t* resampled) {
   ParticleRequest q{x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled};
   q.with_stats = true; q.stats = stats; q.mean = mean;
+  return particle_run(c, q);
+}
+
+// Path events of the particle filter's lineages: extremes, first passage, occupation (see vgpa_hip.h)
+int vgpa_particle_events(vgpa_ctx* c, const double* x, const double* x0, int32_t n_paths, int32_t stride, uint64_t seed, double ess_fraction,
+                         const double* prior_mu, const double* prior_tau, const double* levels, const int32_t* sides, double* logw, double* state,
+                         double* rows, double* mean, double* cdf, double* ess, int32_t* resampled) {
+  if (!c) return VGPA_ERR_ARG;
+  if (!levels || !sides) return fail(c, VGPA_ERR_ARG, "null argument");
+  if (!rows && !mean && !cdf) return fail(c, VGPA_ERR_ARG, "at least one of rows, mean and cdf must be given");
+  if (stride < 1) return fail(c, VGPA_ERR_ARG, "stride must be at least 1 (stride = %d)", stride);
+  for (size_t e = 0; e < (size_t)c->B * c->D; e++) {
+    if (!std::isfinite(levels[e])) return fail(c, VGPA_ERR_ARG, "levels must be finite (problem %zu, component %zu)", e / c->D, e % c->D);
+    if (sides[e] != 1 && sides[e] != -1) return fail(c, VGPA_ERR_ARG, "sides must be +1 or -1 (problem %zu, component %zu: %d)", e / c->D, e % c->D, sides[e]);
+  }
+  ParticleRequest q{x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled};
+  q.stride = stride; q.with_stats = true; q.stats = rows; q.mean = mean;
+  q.events = true; q.levels = levels; q.sides = sides; q.cdf = cdf;
   return particle_run(c, q);
 }
 

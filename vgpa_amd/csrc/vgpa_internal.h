@@ -222,9 +222,9 @@ struct ReduceArgs {
   const double* div_v;      // [B] per-problem div (1-D models: sigma_p), or nullptr
 };
 
-// Euler-Maruyama sample paths (sample.hip): x_k = x_{k-1} + dt drift_{k-1}(x_{k-1}) + R xi_k on the context's grid.  The ten things a launch
+// Euler-Maruyama sample paths (sample.hip): x_k = x_{k-1} + dt drift_{k-1}(x_{k-1}) + R xi_k on the context's grid.  The eleven things a launch
 // can do with them (the table at the top of sample.hip); the host names one at every launch_sample_walk, and SampleArgs says what each reads
-enum class Walk { Plain, Weighted, Segment, SegmentStats, Replay, Lineage, Forecast, ReplayCov, Backward, Conditional };
+enum class Walk { Plain, Weighted, Segment, SegmentStats, Replay, Lineage, Forecast, ReplayCov, Backward, Conditional, SegmentEvents };
 struct SampleArgs {
   int kind, model, D, Np, batch, n_paths, stride, n_keep;
   double dt;
@@ -295,10 +295,17 @@ struct SampleArgs {
   // is pinned to the reference trajectory pf_ref[p] -- [B][Np][D], the last argument of launch_sample_walk and no field here: the other
   // walks' kernels take this struct alone --: it draws nothing, takes the increment the reference implies, eta* = (ref_k - ref_{k-1})
   // - dt g(ref_{k-1}), into the step's weight term in place of R xi, and its state becomes ref_k as loaded
+  // Walk::SegmentEvents (vgpa_particle_events): Walk::Segment, every field as there, in which every slot carries the row
+  // (X, T, N) of event records of its lineage where pf_stats points, [B][n_paths][3][D] as for SegmentStats: with g_j(x) = s_j (x_j - c_j),
+  // at every step k of the segment X_j = fmax(X_j, g_j(x_k)) and, where g_j(x_k) > 0, T_j = min(T_j, k), N_j += 1 (T, N: exact integers
+  // held as doubles).  The levels c and the sides s are ev_level [B][D] and ev_side [B][D] (+1 / -1), the last arguments of
+  // launch_sample_walk and no fields here
 };
 // hipErrorInvalidValue where a field the walk reads is missing or out of range, where a field that belongs to another walk is set (pf_ref
-// in every walk but Conditional, which needs it), and for D = 2 in every walk but Plain (no stochastic model has D = 2)
-hipError_t launch_sample_walk(Walk w, const SampleArgs& a, hipStream_t st, const double* pf_ref = nullptr);
+// in every walk but Conditional, which needs it; ev_level and ev_side in every walk but SegmentEvents, which needs both), and for D = 2 in
+// every walk but Plain (no stochastic model has D = 2)
+hipError_t launch_sample_walk(Walk w, const SampleArgs& a, hipStream_t st, const double* pf_ref = nullptr, const double* ev_level = nullptr,
+                              const int32_t* ev_side = nullptr);
 // workgroups per problem of a segment launch: the blocks of the replay's partial sums
 int sample_segment_blocks(int D, int n_paths);
 int sample_max_paths(int D);      // the largest n_paths per problem a segment, replay or forecast launch takes at this D (grid.y)
@@ -349,6 +356,14 @@ hipError_t launch_pf_cresample(const PfArgs& f, const SampleArgs& a, hipStream_t
 hipError_t launch_pf_ref_fill(const PfArgs& f, int rows, const int32_t* table, double* out, hipStream_t st);
 // mean [B][3][D] = sum_i w_i stats[.][i] / sum_i w_i, w_i = exp(lw_i - max lw) (sample.hip: k_pf_stats_mean)
 hipError_t launch_pf_stats_mean(int D, int batch, int n_paths, const double* lw, const double* stats, double* mean, hipStream_t st);
+// vgpa_particle_events (sample.hip: k_pf_events_start, k_pf_events_cdf).  start, behind launch_pf_start: rows
+// [B][n_paths][3][D] get the record of grid index 0 from the particles x [B][n_paths][D]: X_j = g_j(x), T_j = 0 and N_j = 1 where g_j(x) > 0,
+// else T_j = Np (never so far) and N_j = 0.  cdf [B][n_keep][D], n_keep = (Np - 1) / stride + 1: cdf[p][k'][j] = sum_i W_i 1[T_ij <= k' stride]
+// with W_i = w_i / sum w, w_i = exp(lw_i - max lw): one workgroup per (problem, component), every addition in an order the launch does not
+// change
+hipError_t launch_pf_events_start(int D, int batch, int n_paths, int Np, const double* x, const double* level, const int32_t* side, double* rows,
+                                  hipStream_t st);
+hipError_t launch_pf_events_cdf(int D, int batch, int n_paths, int Np, int stride, const double* lw, const double* rows, double* cdf, hipStream_t st);
 // vgpa_particle_moments (sample.hip: k_pf_descend, k_pf_gather, k_pf_moments_sum).  Of PfArgs, descend reads lw, h_flag, h_anc, M and the
 // observation counts: wtab [B][rows][n_paths] gets row c = the normalised final weights and rows c-1 .. 0 by the backward recursion
 // through the stored ancestors, less [B][rows] the lineage ESS of the rows written (the others stay as they are); gather is the step

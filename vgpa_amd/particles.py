@@ -18,6 +18,13 @@ There is no Sigma step: the paths are imputed at the Sigma in force, their quadr
 say, so Sigma <- E[Q] / n_steps barely moves (0.77 .. 0.79 from Sigma = 0.8 on the fixtures at dt = 0.01).  Q serves the Q-function and as a
 diagnostic.
 
+PathEvents: one problem's record of vgpa_particle_events -- the same filter, every particle carrying along its lineage
+the records of the event side_j (x_j - level_j) > 0: the largest excursion X, the first grid index T of the event and the number N of grid
+indices in it.  Their weighted means and the distribution of T on the grid are reduced on the device: the probability that a component
+crossed its level anywhere in the window, the first-passage distribution, the expected occupation time and the expected extreme, from all
+n lineages.  The estimator is that of PathStatistics (the final weights on the surviving lineages): exact for the Euler-discretised model
+as n grows; in early stretches it rests on the few lineages the genealogy has left there (lineage_ess of SmoothingMoments says how few).
+
 SmoothingMoments: one problem's record of vgpa_particle_moments -- the smoothing mean and second moment on the time grid
 under the filter's genealogy.  The final weights are pushed backwards through the ancestors (descendant_weights): the weight of slot a in
 the stretch between observations j-1 and j is the total final weight of the slots that descend from it, and
@@ -52,7 +59,7 @@ model whatever the proposal (A_t, b_t) and for any number of particles >= 2: the
 """
 import numpy as np
 
-__all__ = ["ParticleFilterResult", "PathStatistics", "SmoothingMoments", "SmoothingCovariance", "SmoothingPaths", "Forecast", "GibbsChain", "descendant_weights",
+__all__ = ["ParticleFilterResult", "PathStatistics", "PathEvents", "SmoothingMoments", "SmoothingCovariance", "SmoothingPaths", "Forecast", "GibbsChain", "descendant_weights",
            "path_rows", "theta_conditional", "theta_draw"]
 
 
@@ -206,6 +213,103 @@ class PathStatistics(object):
         sg = np.broadcast_to(np.asarray(sigma_diag_new, dtype=float).ravel(), (self.dim_d,))
         q, g, h = self.mean
         return float(-0.5 * np.sum((q - 2.0 * delta * g + delta * delta * h) / sg + self.n_steps * np.log(2.0 * np.pi * sg * self.dt)))
+
+
+class PathEvents(object):
+    """log_w (n,): the final unnormalised log-weights; mean (3, D): the self-normalised weighted mean of the rows (X, T, N); cdf (n_keep, D):
+    the weighted share of lineages whose component j has been beyond its level at or before the grid indices 0, stride, ...; levels (D,),
+    side (D,) of +1 / -1: the event of component j is side_j (x_j - levels_j) > 0; n_pts = Np and dt: the grid; rows (n, 3, D): the rows
+    themselves, or None; ess, resampled over the problem's observations.  T = n_pts in a row says: never in the window."""
+
+    def __init__(self, log_w, mean, cdf, levels, side, stride, n_pts, dt, ess=(), resampled=(), rows=None) -> None:
+        self.log_w = np.asarray(log_w, dtype=float).ravel()
+        if self.log_w.size < 1:
+            raise ValueError(" PathEvents: at least one particle.")
+        self.mean = np.asarray(mean, dtype=float)
+        if self.mean.ndim != 2 or self.mean.shape[0] != 3:
+            raise ValueError(" PathEvents: mean must be (3, D).")
+        d = self.mean.shape[1]
+        self.stride, self.n_pts, self.dt = int(stride), int(n_pts), float(dt)
+        if self.stride < 1 or self.n_pts < 1:
+            raise ValueError(" PathEvents: stride and n_pts must be at least 1.")
+        self.grid = np.arange((self.n_pts - 1) // self.stride + 1) * self.stride
+        self.cdf = np.asarray(cdf, dtype=float)
+        if self.cdf.shape != (self.grid.size, d):
+            raise ValueError(" PathEvents: cdf must be (n_keep, D).")
+        self.levels = np.broadcast_to(np.asarray(levels, dtype=float).ravel(), (d,)).copy()
+        self.side = np.broadcast_to(np.asarray(side).ravel(), (d,)).astype(int)
+        if not np.all(np.abs(self.side) == 1):
+            raise ValueError(" PathEvents: side must be +1 or -1.")
+        self.ess = np.asarray(ess, dtype=float).ravel()
+        self.resampled = np.asarray(resampled).astype(bool).ravel()
+        self.rows = None if rows is None else np.asarray(rows, dtype=float)
+        if self.rows is not None and self.rows.shape != (self.log_w.size,) + self.mean.shape:
+            raise ValueError(" PathEvents: rows must be (particles, 3, D).")
+        if self.ess.size != self.resampled.size:
+            raise ValueError(" PathEvents: ess and resampled do not belong together.")
+
+    def __len__(self):
+        return self.log_w.size
+
+    @property
+    def dim_d(self):
+        return self.mean.shape[1]
+
+    def weights(self):
+        """(n,): w / sum w with w = exp(log_w - max log_w)"""
+        w = np.exp(self.log_w - np.max(self.log_w))
+        return w / np.sum(w)
+
+    def log_evidence(self):
+        """logsumexp(log_w) - log n, as ParticleFilterResult.log_evidence()"""
+        top = np.max(self.log_w)
+        return float(top + np.log(np.sum(np.exp(self.log_w - top))) - np.log(self.log_w.size))
+
+    @property
+    def prob_crossed(self):
+        """(D,): the probability that component j was beyond its level at some grid index of the window: the last row of cdf when the kept
+        grid ends at the last grid index, else the weighted share of the rows with T < n_pts (per_particle=True)"""
+        if (self.n_pts - 1) % self.stride == 0:
+            return self.cdf[-1].copy()
+        if self.rows is None:
+            raise ValueError(" PathEvents: the kept grid ends before the last grid index; prob_crossed then needs the rows (per_particle=True).")
+        return np.tensordot(self.weights(), (self.rows[:, 1] < self.n_pts).astype(float), axes=(0, 0))
+
+    def first_passage_cdf(self):
+        """(grid (n_keep,), cdf (n_keep, D)): P(T_j <= k | y) at the kept grid indices k; multiply grid by dt for times"""
+        return self.grid.copy(), self.cdf.copy()
+
+    def first_passage_quantile(self, q):
+        """(D,): the smallest kept grid index k with P(T_j <= k | y) >= q, NaN where the distribution does not reach q in the window"""
+        if not 0.0 < float(q) <= 1.0:
+            raise ValueError(" PathEvents: q must lie in (0, 1].")
+        hit = self.cdf >= float(q)
+        first = np.argmax(hit, axis=0)
+        return np.where(hit.any(axis=0), self.grid[first].astype(float), np.nan)
+
+    @property
+    def occupation_time(self):
+        """(D,): dt E[N_j], the expected time component j spent beyond its level (in grid steps of length dt, the start included)"""
+        return self.dt * self.mean[2]
+
+    @property
+    def mean_extreme(self):
+        """(D,): levels + side E[X], in the caller's units: the expected maximum of x_j over the window for side +1, its minimum for -1"""
+        return self.levels + self.side * self.mean[0]
+
+    def extreme_quantile(self, q):
+        """(D,): levels + side X_q with X_q the weighted q-quantile of the rows' X (the smallest X whose cumulated weight reaches q): for
+        side +1 the q-quantile of the window's maximum of x_j, for side -1 the (1 - q)-quantile of its minimum.  Needs the rows."""
+        if self.rows is None:
+            raise ValueError(" PathEvents: extreme_quantile needs the rows (per_particle=True).")
+        if not 0.0 <= float(q) <= 1.0:
+            raise ValueError(" PathEvents: q must lie in [0, 1].")
+        w, out = self.weights(), np.empty(self.dim_d)
+        for j in range(self.dim_d):
+            order = np.argsort(self.rows[:, 0, j], kind="stable")
+            cum = np.cumsum(w[order])
+            out[j] = self.rows[order[min(int(np.searchsorted(cum, float(q) * cum[-1], side="left")), order.size - 1)], 0, j]
+        return self.levels + self.side * out
 
 
 class SmoothingMoments(object):

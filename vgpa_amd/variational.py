@@ -238,6 +238,28 @@ class VarGP(object):
         out = [self._statistics_record(res, k) for k in range(res["log_w"].shape[0])]
         return out[0] if self.batch == 1 else out
 
+    def _events_record(self, res, k, levels, side, stride, n_obs=None):
+        """One problem's PathEvents from row k of Context.particle_events' dict, cut to its own n_obs observations"""
+        from .particles import PathEvents
+        m = res["ess"].shape[1] if n_obs is None else int(n_obs)
+        rows = None if res["rows"] is None else res["rows"][k]
+        return PathEvents(res["log_w"][k], res["mean"][k], res["cdf"][k], levels, side, stride, self.dim_n, float(self.fwd_ode.dt), res["ess"][k, :m],
+                          res["resampled"][k, :m], rows)
+
+    def particle_events(self, n_paths, seed, levels, side=1, stride=1, ess_fraction=0.5, x=None, x0=None, per_particle=False):
+        """particle_filter with the same arguments, every particle carrying the event records of its lineage: a particles.PathEvents (with
+        batch > 1 a list, one per problem).  levels (D,) or a scalar, side +1 (above) or -1 (below) per component: the event of component j
+        is side_j (x_j - levels_j) > 0.  prob_crossed, first_passage_cdf(), occupation_time and mean_extreme come from sums reduced on the
+        device over all n_paths lineages (no path is stored or copied); per_particle=True also keeps the rows."""
+        xx = None if x is None else np.asarray(x, dtype=float)
+        res = self._context().particle_events(n_paths, seed, levels, side=side, stride=stride, ess_fraction=ess_fraction, x=xx, x0=x0,
+                                              prior=self._prior(), per_particle=per_particle)
+        d = self.dim_d
+        lev = np.broadcast_to(np.asarray(levels, dtype=float).reshape(-1, d) if np.size(levels) > 1 else np.reshape(levels, (1, 1)), (self.batch, d))
+        sd = np.broadcast_to(np.asarray(side).reshape(-1, d) if np.size(side) > 1 else np.reshape(side, (1, 1)), (self.batch, d))
+        out = [self._events_record(res, k, lev[k], sd[k], stride) for k in range(res["log_w"].shape[0])]
+        return out[0] if self.batch == 1 else out
+
     def _moments_record(self, res, k, stride, obs_t=None):
         """One problem's SmoothingMoments from row k of Context.particle_moments' dict, cut to its own observations obs_t"""
         from .particles import SmoothingMoments
