@@ -262,6 +262,12 @@ def _shaped(a, shape, name, dtype=np.float64):
     return np.ascontiguousarray(a, dtype=dtype)
 
 
+def per_problem(a, batch, d):
+    """Levels or sides of the path events, one row per problem: (batch, d), or (d,) or a scalar for every problem, as a (batch, d) view"""
+    a = np.asarray(a)
+    return np.broadcast_to(a.reshape(-1, d) if a.size > 1 else a.reshape(1, 1), (batch, d))
+
+
 class DeviceBuffer:
     """A caller-owned device allocation (fp64) on the context's device."""
 
@@ -604,6 +610,47 @@ class Context:
             raise ValueError("slots must be integers that fit into 32 bits")
         return np.ascontiguousarray(np.broadcast_to(wide.reshape(-1, k), (self.B, k)), dtype=np.int32)
 
+    def _n_keep(self, stride):
+        """the number of kept grid indices 0, stride, 2 stride, ... (the library refuses a stride below 1)"""
+        return (self.Np - 1) // max(stride, 1) + 1
+
+    @staticmethod
+    def _seed(seed):
+        return int(seed) & 0xFFFFFFFFFFFFFFFF
+
+    def _new(self, *shape, fill=None, dtype=np.float64):
+        """a result (B, *shape) for the library to write: as it comes, or holding `fill` where the library leaves entries as they are"""
+        return np.empty((self.B,) + shape, dtype=dtype) if fill is None else np.full((self.B,) + shape, fill, dtype=dtype)
+
+    def _history(self, n, wanted):
+        """the filter's histories: ancestors (B, M, n) int32 of -1 and clouds (B, M, n, D) of NaN, or None and None"""
+        return {"ancestors": self._new(self.n_obs, n, fill=-1, dtype=np.int32) if wanted else None,
+                "clouds": self._new(self.n_obs, n, self.D, fill=np.nan) if wanted else None}
+
+    def _filter_call(self, entry, ints, seed, ess_fraction, x, x0, prior, outputs=None, inputs=None, head=None, slots=None, history=None):
+        """One call of the filter family.  All its entry points but the forecast have the shape
+            (h, x, x0, [ref], n_paths, [n_draw, final_slots], [stride], seed, ess_fraction, mu, tau, [own inputs], logw, state, [own outputs],
+             ess, resampled, [ancestors, clouds])
+        and a method says what is its own: ints, the entry's integers by name (n_paths and, where it has them, n_draw and stride; with n_draw
+        go the final `slots`); inputs() -> its own input arrays, checked before x; head() -> what stands before n_paths, checked behind x;
+        outputs(n, k, n_keep) -> {key: array or None} in the entry's order; history: None where the entry has no histories, else whether they
+        are wanted.  Returns the dict: log_w, state, ess, resampled, the histories, the entry's own."""
+        ints = {name: int(v) for name, v in ints.items()}
+        self._fit32(**ints)
+        own_in = inputs() if inputs else ()
+        xx, s0, mu, tau = self._walk_inputs(x, x0, prior)
+        first = head() if head else ()
+        n, k = max(ints["n_paths"], 0), max(ints.get("n_draw", 0), 0)
+        draw = (ints["n_draw"], _ptr(self._slot_array(slots, k))) if "n_draw" in ints else ()
+        log_w, state, ess, flags = self._filter_outputs(n)
+        own = outputs(n, k, self._n_keep(ints.get("stride", 1))) if outputs else {}
+        hist = {} if history is None else self._history(n, history)
+        self._check(getattr(self._lib, entry)(self._h, _ptr(xx), _ptr(s0), *map(_ptr, first), ints["n_paths"], *draw,
+                                              *((ints["stride"],) if "stride" in ints else ()), self._seed(seed), float(ess_fraction), _ptr(mu),
+                                              _ptr(tau), *map(_ptr, own_in), _ptr(log_w), _ptr(state), *map(_ptr, own.values()), _ptr(ess),
+                                              _ptr(flags), *map(_ptr, hist.values())))
+        return {"log_w": log_w, "state": state, "ess": ess, "resampled": flags, **hist, **own}
+
     def lag_covariance(self, anchors, kind="covariance", stride=1, x=None):
         """The two-time covariance K(k, s) = Phi(k, s) S_s of the posterior process (kind "covariance") or the propagator Phi(k, s) of
         dPhi/dt = -A_t Phi itself (kind "propagator") from every anchor s to the end of the grid (vgpa_lag_covariance): the context's scheme
@@ -622,14 +669,12 @@ class Context:
             raise ValueError("anchors must be a 1-D sequence of integer grid indices")
         anc = np.ascontiguousarray(anc, dtype=np.int64)
         self._fit32(n_anchor=int(anc.size), stride=stride)
-        xx = None if x is None else _c64(x)
-        if xx is not None and xx.size != self.B * self.len_x:
-            raise ValueError(f"x has {xx.size} entries, expected {self.B * self.len_x}")
+        xx = self._walk_inputs(x, None)[0]
         if xx is not None and kind == "covariance":
             self.free_energy(xx)
             xx = None
-        n_keep = (self.Np - 1) // stride + 1 if stride >= 1 else 0
-        out = np.empty((self.B, anc.size, n_keep, self.D, self.D))
+        n_keep = self._n_keep(stride)
+        out = self._new(anc.size, n_keep, self.D, self.D)
         self._check(self._lib.vgpa_lag_covariance(self._h, LAG_KINDS[kind], _ptr(xx), int(anc.size),
                                                   anc.ctypes.data_as(POINTER(c_int64)) if anc.size else None, stride, _ptr(out)))
         return LagCovariance(out, anc, np.arange(n_keep) * stride, kind)
@@ -644,10 +689,8 @@ class Context:
         n_paths, stride = int(n_paths), int(stride)
         self._fit32(n_paths=n_paths, stride=stride)
         xx, s0, _, _ = self._walk_inputs(x, x0)
-        n_keep = (self.Np - 1) // stride + 1 if stride >= 1 else 0
-        out = np.empty((self.B, max(n_paths, 0), n_keep, self.D))
-        self._check(self._lib.vgpa_sample_paths(self._h, PATH_KINDS[kind], _ptr(xx), _ptr(s0), n_paths, stride,
-                                                int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(out)))
+        out = self._new(max(n_paths, 0), self._n_keep(stride), self.D)
+        self._check(self._lib.vgpa_sample_paths(self._h, PATH_KINDS[kind], _ptr(xx), _ptr(s0), n_paths, stride, self._seed(seed), _ptr(out)))
         return out
 
     def sample_paths_weighted(self, n_paths, seed, stride=1, x=None, x0=None, paths=True):
@@ -657,11 +700,11 @@ class Context:
         n_paths, stride = int(n_paths), int(stride)
         self._fit32(n_paths=n_paths, stride=stride)
         xx, s0, _, _ = self._walk_inputs(x, x0)
-        n_keep = (self.Np - 1) // stride + 1 if stride >= 1 else 0
-        out = np.empty((self.B, max(n_paths, 0), n_keep, self.D)) if paths else None
-        logw, start = np.empty((self.B, max(n_paths, 0), 2)), np.empty((self.B, max(n_paths, 0), self.D))
-        self._check(self._lib.vgpa_sample_paths_weighted(self._h, _ptr(xx), _ptr(s0), n_paths, stride, int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                                         _ptr(out), _ptr(start), _ptr(logw)))
+        n = max(n_paths, 0)
+        out = self._new(n, self._n_keep(stride), self.D) if paths else None
+        logw, start = self._new(n, 2), self._new(n, self.D)
+        self._check(self._lib.vgpa_sample_paths_weighted(self._h, _ptr(xx), _ptr(s0), n_paths, stride, self._seed(seed), _ptr(out), _ptr(start),
+                                                         _ptr(logw)))
         return out, logw, start
 
     def particle_filter(self, n_paths, seed, ess_fraction=0.5, x=None, x0=None, prior=None, history=False):
@@ -670,41 +713,22 @@ class Context:
         initial term of a drawn start, or None.  Returns a dict: log_w (B, n_paths), state (B, n_paths, D), ess (B, M), resampled (B, M) int32
         and, history=True, ancestors (B, M, n_paths) int32 and clouds (B, M, n_paths, D) (else None), M = the context's n_obs.  Rows at or
         beyond a problem's own observation count: ess 0, resampled 0, ancestors -1, clouds NaN."""
-        n_paths, m = int(n_paths), self.n_obs
-        self._fit32(n_paths=n_paths)
-        xx, s0, mu, tau = self._walk_inputs(x, x0, prior)
-        n = max(n_paths, 0)
-        log_w, state, ess, flags = self._filter_outputs(n)
-        anc = np.full((self.B, m, n), -1, dtype=np.int32) if history else None
-        clouds = np.full((self.B, m, n, self.D), np.nan) if history else None
-        self._check(self._lib.vgpa_particle_filter(self._h, _ptr(xx), _ptr(s0), n_paths, int(seed) & 0xFFFFFFFFFFFFFFFF, float(ess_fraction),
-                                                   _ptr(mu), _ptr(tau), _ptr(log_w), _ptr(state), _ptr(ess), _ptr(flags), _ptr(anc),
-                                                   _ptr(clouds)))
-        return {"log_w": log_w, "state": state, "ess": ess, "resampled": flags, "ancestors": anc, "clouds": clouds}
+        return self._filter_call("vgpa_particle_filter", {"n_paths": n_paths}, seed, ess_fraction, x, x0, prior, history=bool(history))
 
     def particle_statistics(self, n_paths, seed, ess_fraction=0.5, x=None, x0=None, prior=None, per_particle=False):
         """The path statistics of particle_filter's lineages (vgpa_particle_statistics): the same walk and resampling decisions, every slot
         carrying its row (Q, G, H) of sum_k r^2 / dt, sum_k phi r, sum_k dt phi^2.  Returns a dict: log_w, state, ess, resampled as
         particle_filter (bit for bit), mean (B, 3, D): the self-normalised weighted mean of the rows, reduced on the device, and stats
         (B, n_paths, 3, D): the rows themselves (per_particle=True, else None)."""
-        n_paths, m = int(n_paths), self.n_obs
-        self._fit32(n_paths=n_paths)
-        xx, s0, mu, tau = self._walk_inputs(x, x0, prior)
-        n = max(n_paths, 0)
-        log_w, state, ess, flags = self._filter_outputs(n)
-        mean = np.empty((self.B, 3, self.D))
-        stats = np.empty((self.B, n, 3, self.D)) if per_particle else None
-        self._check(self._lib.vgpa_particle_statistics(self._h, _ptr(xx), _ptr(s0), n_paths, int(seed) & 0xFFFFFFFFFFFFFFFF, float(ess_fraction),
-                                                       _ptr(mu), _ptr(tau), _ptr(log_w), _ptr(state), _ptr(stats), _ptr(mean), _ptr(ess),
-                                                       _ptr(flags)))
-        return {"log_w": log_w, "state": state, "ess": ess, "resampled": flags, "mean": mean, "stats": stats}
+        return self._filter_call("vgpa_particle_statistics", {"n_paths": n_paths}, seed, ess_fraction, x, x0, prior, lambda n, k, n_keep: {
+            "stats": self._new(n, 3, self.D) if per_particle else None, "mean": self._new(3, self.D)})
 
     def _event_inputs(self, levels, side):
         """levels and side of particle_events laid out for the C ABI: (B, D) float64 and (B, D) int32.  A scalar or (D,) is every problem's."""
         lev = np.asarray(levels, dtype=np.float64)
         if lev.size not in (1, self.D, self.B * self.D):
             raise ValueError(f"levels has {lev.size} entries, expected 1, {self.D} or {self.B * self.D}")
-        lev = _c64(np.broadcast_to(lev.reshape(-1, self.D) if lev.size > 1 else lev.reshape(1, 1), (self.B, self.D)))
+        lev = _c64(per_problem(lev, self.B, self.D))
         if not np.all(np.isfinite(lev)):
             raise ValueError("levels must be finite")
         sd = np.asarray(side)
@@ -712,8 +736,7 @@ class Context:
             raise ValueError(f"side has {sd.size} entries, expected 1, {self.D} or {self.B * self.D}")
         if not np.all((sd == 1) | (sd == -1)):
             raise ValueError("side must be +1 or -1")
-        sd = np.ascontiguousarray(np.broadcast_to(sd.reshape(-1, self.D) if sd.size > 1 else sd.reshape(1, 1), (self.B, self.D)), dtype=np.int32)
-        return lev, sd
+        return lev, np.ascontiguousarray(per_problem(sd, self.B, self.D), dtype=np.int32)
 
     def particle_events(self, n_paths, seed, levels, side=1, stride=1, ess_fraction=0.5, x=None, x0=None, prior=None, per_particle=False):
         """Path events of particle_filter's lineages (vgpa_particle_events): the same walk and resampling decisions, every slot carrying the
@@ -722,52 +745,25 @@ class Context:
         -1 (below it).  Returns a dict: log_w, state, ess, resampled as particle_filter (bit for bit), mean (B, 3, D): the self-normalised
         weighted mean of the rows, cdf (B, n_keep, D): the weighted share of lineages with T <= k at the grid indices k = 0, stride, ...,
         both reduced on the device, and rows (B, n_paths, 3, D): the rows themselves (per_particle=True, else None)."""
-        n_paths, stride = int(n_paths), int(stride)
-        self._fit32(n_paths=n_paths, stride=stride)
-        lev, sd = self._event_inputs(levels, side)
-        xx, s0, mu, tau = self._walk_inputs(x, x0, prior)
-        n = max(n_paths, 0)
-        log_w, state, ess, flags = self._filter_outputs(n)
-        mean, cdf = np.empty((self.B, 3, self.D)), np.empty((self.B, (self.Np - 1) // max(stride, 1) + 1, self.D))
-        rows = np.empty((self.B, n, 3, self.D)) if per_particle else None
-        self._check(self._lib.vgpa_particle_events(self._h, _ptr(xx), _ptr(s0), n_paths, stride, int(seed) & 0xFFFFFFFFFFFFFFFF, float(ess_fraction),
-                                                   _ptr(mu), _ptr(tau), _ptr(lev), _ptr(sd), _ptr(log_w), _ptr(state), _ptr(rows), _ptr(mean),
-                                                   _ptr(cdf), _ptr(ess), _ptr(flags)))
-        return {"log_w": log_w, "state": state, "ess": ess, "resampled": flags, "mean": mean, "cdf": cdf, "rows": rows}
+        return self._filter_call("vgpa_particle_events", {"n_paths": n_paths, "stride": stride}, seed, ess_fraction, x, x0, prior, lambda n, k, n_keep: {
+            "rows": self._new(n, 3, self.D) if per_particle else None, "mean": self._new(3, self.D), "cdf": self._new(n_keep, self.D)},
+            inputs=lambda: self._event_inputs(levels, side))
 
     def particle_moments(self, n_paths, seed, stride=1, ess_fraction=0.5, x=None, x0=None, prior=None):
         """The smoothing moments on the grid under particle_filter's genealogy (vgpa_particle_moments): the filter, its final weights pushed
         back through the ancestors, and the walk once more with the weighted sums taken on the device.  Returns a dict: log_w, state, ess,
         resampled as particle_filter (bit for bit), moments (B, n_keep, 2, D): sum W x and sum W x^2 at the grid indices 0, stride, ...,
         and lineage_ess (B, M + 1): 1 / sum W^2 of every stretch between two observations (0 beyond a problem's own count + 1)."""
-        n_paths, stride, m = int(n_paths), int(stride), self.n_obs
-        self._fit32(n_paths=n_paths, stride=stride)
-        xx, s0, mu, tau = self._walk_inputs(x, x0, prior)
-        n = max(n_paths, 0)
-        log_w, state, ess, flags = self._filter_outputs(n)
-        moments = np.empty((self.B, (self.Np - 1) // max(stride, 1) + 1, 2, self.D))
-        lineage_ess = np.zeros((self.B, m + 1))
-        self._check(self._lib.vgpa_particle_moments(self._h, _ptr(xx), _ptr(s0), n_paths, stride, int(seed) & 0xFFFFFFFFFFFFFFFF, float(ess_fraction),
-                                                    _ptr(mu), _ptr(tau), _ptr(log_w), _ptr(state), _ptr(moments), _ptr(lineage_ess), _ptr(ess),
-                                                    _ptr(flags)))
-        return {"log_w": log_w, "state": state, "ess": ess, "resampled": flags, "moments": moments, "lineage_ess": lineage_ess}
+        return self._filter_call("vgpa_particle_moments", {"n_paths": n_paths, "stride": stride}, seed, ess_fraction, x, x0, prior, lambda n, k, n_keep: {
+            "moments": self._new(n_keep, 2, self.D), "lineage_ess": self._new(self.n_obs + 1, fill=0.0)})
 
     def particle_covariance(self, n_paths, seed, stride=1, ess_fraction=0.5, x=None, x0=None, prior=None):
         """The smoothing mean and the full second-moment matrices on the grid under particle_filter's genealogy (vgpa_particle_covariance):
         particle_moments with every cross moment.  Returns a dict: log_w, state, ess, resampled as particle_filter (bit for bit), lineage_ess
         as particle_moments (bit for bit), mean (B, n_keep, D): sum W x, and second (B, n_keep, D, D): sum W x x^T, symmetric to the bit,
         at the grid indices 0, stride, ...  The covariance is second - mean mean^T (SmoothingCovariance.cov)."""
-        n_paths, stride, m = int(n_paths), int(stride), self.n_obs
-        self._fit32(n_paths=n_paths, stride=stride)
-        xx, s0, mu, tau = self._walk_inputs(x, x0, prior)
-        n, n_keep = max(n_paths, 0), (self.Np - 1) // max(stride, 1) + 1
-        log_w, state, ess, flags = self._filter_outputs(n)
-        mean, second = np.empty((self.B, n_keep, self.D)), np.empty((self.B, n_keep, self.D, self.D))
-        lineage_ess = np.zeros((self.B, m + 1))
-        self._check(self._lib.vgpa_particle_covariance(self._h, _ptr(xx), _ptr(s0), n_paths, stride, int(seed) & 0xFFFFFFFFFFFFFFFF, float(ess_fraction),
-                                                       _ptr(mu), _ptr(tau), _ptr(log_w), _ptr(state), _ptr(mean), _ptr(second), _ptr(lineage_ess),
-                                                       _ptr(ess), _ptr(flags)))
-        return {"log_w": log_w, "state": state, "ess": ess, "resampled": flags, "mean": mean, "second": second, "lineage_ess": lineage_ess}
+        return self._filter_call("vgpa_particle_covariance", {"n_paths": n_paths, "stride": stride}, seed, ess_fraction, x, x0, prior, lambda n, k, n_keep: {
+            "mean": self._new(n_keep, self.D), "second": self._new(n_keep, self.D, self.D), "lineage_ess": self._new(self.n_obs + 1, fill=0.0)})
 
     def particle_paths(self, n_paths, seed, n_draw, stride=1, ess_fraction=0.5, x=None, x0=None, prior=None, slots=None):
         """n_draw whole smoothing trajectories per problem from particle_filter's genealogy (vgpa_particle_paths): the filter, the final
@@ -775,7 +771,7 @@ class Context:
         weighted), their slot in every stretch traced back through the ancestors, and one walk of the trajectories alone.  Returns a dict:
         log_w, state, ess, resampled as particle_filter (bit for bit), paths (B, n_draw, n_keep, D) at the grid indices 0, stride, ..., and
         slots (B, M + 1, n_draw) int32: the slot of every trajectory in every stretch (-1 beyond a problem's own count + 1)."""
-        return self._smoothing_paths(self._lib.vgpa_particle_paths, n_paths, seed, n_draw, stride, ess_fraction, x, x0, prior, slots)
+        return self._smoothing_paths("vgpa_particle_paths", n_paths, seed, n_draw, stride, ess_fraction, x, x0, prior, slots)
 
     def particle_backward_paths(self, n_paths, seed, n_draw, stride=1, ess_fraction=0.5, x=None, x0=None, prior=None, slots=None):
         """n_draw whole smoothing trajectories per problem by backward simulation through particle_filter's clouds
@@ -783,21 +779,12 @@ class Context:
         observation where the cloud was resampled a trajectory does not follow its ancestor: it draws the slot it came from among all n
         particles, with probability proportional to filter weight times model transition density (Gumbel-max on the device, one launch).
         Where nothing was resampled (ess_fraction=0, n_paths=1) the result is particle_paths' bit for bit."""
-        return self._smoothing_paths(self._lib.vgpa_particle_backward_paths, n_paths, seed, n_draw, stride, ess_fraction, x, x0, prior, slots)
+        return self._smoothing_paths("vgpa_particle_backward_paths", n_paths, seed, n_draw, stride, ess_fraction, x, x0, prior, slots)
 
     def _smoothing_paths(self, entry, n_paths, seed, n_draw, stride, ess_fraction, x, x0, prior, slots):
-        """the arguments of particle_paths / particle_backward_paths checked and laid out, the call, the dict"""
-        n_paths, n_draw, stride, m = int(n_paths), int(n_draw), int(stride), self.n_obs
-        self._fit32(n_paths=n_paths, n_draw=n_draw, stride=stride)
-        xx, s0, mu, tau = self._walk_inputs(x, x0, prior)
-        n, k = max(n_paths, 0), max(n_draw, 0)
-        given = self._slot_array(slots, k)
-        log_w, state, ess, flags = self._filter_outputs(n)
-        paths = np.empty((self.B, k, (self.Np - 1) // max(stride, 1) + 1, self.D))
-        table = np.full((self.B, m + 1, k), -1, dtype=np.int32)
-        self._check(entry(self._h, _ptr(xx), _ptr(s0), n_paths, n_draw, _ptr(given), stride, int(seed) & 0xFFFFFFFFFFFFFFFF, float(ess_fraction),
-                          _ptr(mu), _ptr(tau), _ptr(log_w), _ptr(state), _ptr(paths), _ptr(table), _ptr(ess), _ptr(flags)))
-        return {"log_w": log_w, "state": state, "ess": ess, "resampled": flags, "paths": paths, "slots": table}
+        """what particle_paths and particle_backward_paths have of their own, one like the other"""
+        return self._filter_call(entry, {"n_paths": n_paths, "n_draw": n_draw, "stride": stride}, seed, ess_fraction, x, x0, prior, lambda n, k, n_keep: {
+            "paths": self._new(k, n_keep, self.D), "slots": self._new(self.n_obs + 1, k, fill=-1, dtype=np.int32)}, slots=slots)
 
     def particle_conditional(self, ref, n_paths, seed, ess_fraction=0.5, x=None, x0=None, prior=None, history=False):
         """One sweep of particle Gibbs with ancestor sampling (vgpa_particle_conditional): particle_filter with slot 0 of every problem pinned
@@ -805,27 +792,15 @@ class Context:
         ancestor of the pinned slot drawn anew at every resampling.  Returns a dict: log_w, state, ess, resampled (and, history=True,
         ancestors and clouds) as particle_filter, of this run; trajectory (B, Np, D): the drawn trajectory, the next reference; slots
         (B, M + 1) int32: the slot it sat in during every stretch (0: that stretch is the reference's; -1 beyond a problem's count + 1)."""
-        n_paths, m = int(n_paths), self.n_obs
-        self._fit32(n_paths=n_paths)
-        xx, s0, mu, tau = self._walk_inputs(x, x0, prior)
-        if ref is None:
-            rr = None
-        else:
+        def reference():
+            if ref is None:
+                return (None,)
             rr = np.asarray(ref, dtype=np.float64)
             if rr.size not in (self.Np * self.D, self.B * self.Np * self.D):
                 raise ValueError(f"ref has {rr.size} entries, expected {self.B} x {self.Np} x {self.D}")
-            rr = _c64(np.broadcast_to(rr.reshape(-1, self.Np, self.D), (self.B, self.Np, self.D)))
-        n = max(n_paths, 0)
-        log_w, state, ess, flags = self._filter_outputs(n)
-        traj = np.empty((self.B, self.Np, self.D))
-        table = np.full((self.B, m + 1), -1, dtype=np.int32)
-        anc = np.full((self.B, m, n), -1, dtype=np.int32) if history else None
-        clouds = np.full((self.B, m, n, self.D), np.nan) if history else None
-        self._check(self._lib.vgpa_particle_conditional(self._h, _ptr(xx), _ptr(s0), _ptr(rr), n_paths, int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                                        float(ess_fraction), _ptr(mu), _ptr(tau), _ptr(log_w), _ptr(state), _ptr(traj),
-                                                        _ptr(table), _ptr(ess), _ptr(flags), _ptr(anc), _ptr(clouds)))
-        return {"log_w": log_w, "state": state, "ess": ess, "resampled": flags, "ancestors": anc, "clouds": clouds, "trajectory": traj,
-                "slots": table}
+            return (_c64(np.broadcast_to(rr.reshape(-1, self.Np, self.D), (self.B, self.Np, self.D))),)
+        return self._filter_call("vgpa_particle_conditional", {"n_paths": n_paths}, seed, ess_fraction, x, x0, prior, lambda n, k, n_keep: {
+            "trajectory": self._new(self.Np, self.D), "slots": self._new(self.n_obs + 1, fill=-1, dtype=np.int32)}, head=reference, history=bool(history))
 
     def particle_forecast(self, horizon, n_paths=None, seed=0, stride=1, n_draw=0, ess_fraction=0.5, x=None, x0=None, cloud=None, log_w=None,
                           index0=None, slots=None, prior=None):
@@ -861,18 +836,17 @@ class Context:
         n_paths = int(n_paths)
         self._fit32(n_paths=n_paths, n_draw=n_draw, stride=stride, horizon=horizon, index0=k0)
         xx, s0, mu, tau = self._walk_inputs(x, x0, prior)
-        n, k, m = max(n_paths, 0), max(n_draw, 0), self.n_obs
+        n, k = max(n_paths, 0), max(n_draw, 0)
         given = self._slot_array(slots, k)
         h_keep = max(horizon, 0) // max(stride, 1) + 1
         out_lw, state, ess, flags = self._filter_outputs(n)
-        moments, members = np.empty((self.B, h_keep, 2, self.D)), np.empty((self.B, k, h_keep, self.D))
-        table, state_end = np.full((self.B, k), -1, dtype=np.int32), np.empty((self.B, n, self.D))
-        self._check(self._lib.vgpa_particle_forecast(self._h, _ptr(xx), _ptr(s0), n_paths, int(seed) & 0xFFFFFFFFFFFFFFFF, float(ess_fraction),
-                                                     _ptr(mu), _ptr(tau), _ptr(cl), _ptr(lw), k0 if given_cloud else 0, horizon, stride, n_draw,
-                                                     _ptr(given), _ptr(out_lw), _ptr(state), _ptr(ess), _ptr(flags), _ptr(moments),
-                                                     _ptr(members), _ptr(table), _ptr(state_end)))
+        moments, members = self._new(h_keep, 2, self.D), self._new(k, h_keep, self.D)
+        table, state_end = self._new(k, fill=-1, dtype=np.int32), self._new(n, self.D)
+        self._check(self._lib.vgpa_particle_forecast(self._h, _ptr(xx), _ptr(s0), n_paths, self._seed(seed), float(ess_fraction), _ptr(mu), _ptr(tau),
+                                                     _ptr(cl), _ptr(lw), k0 if given_cloud else 0, horizon, stride, n_draw, _ptr(given), _ptr(out_lw),
+                                                     _ptr(state), _ptr(ess), _ptr(flags), _ptr(moments), _ptr(members), _ptr(table), _ptr(state_end)))
         if given_cloud:
-            out_lw, state, ess, flags = (np.zeros((self.B, n)) if lw is None else lw), cl, None, None
+            out_lw, state, ess, flags = (self._new(n, fill=0.0) if lw is None else lw), cl, None, None
         return {"log_w": out_lw, "state": state, "ess": ess, "resampled": flags, "moments": moments, "members": members, "slots": table,
                 "state_end": state_end, "index0": k0}
 

@@ -18,7 +18,7 @@ different length, instruments of different noise, sensors that see different com
 """
 import numpy as np
 
-from ._lib import Context
+from ._lib import Context, per_problem
 
 __all__ = ["ProblemBatch", "theta_mstep", "stack_observations"]
 
@@ -217,73 +217,65 @@ class ProblemBatch(object):
                                                                    paths=stride is not None)
         return [v._path_weights(logw[k], start[k], None if paths is None else paths[k], x0 is None) for k, v in enumerate(self.vgps)]
 
+    def _prior(self):
+        """(mu0 (B, D), tau0 (B, D, D)): every member's own prior, stacked"""
+        mu, tau = zip(*(v._prior() for v in self.vgps))
+        return np.stack([m[0] for m in mu]), np.stack([t[0] for t in tau]).reshape(self.B, self.vgps[0].dim_d, self.vgps[0].dim_d)
+
+    def _particle_call(self, name, record, *args, x=None, late=None, **kwargs):
+        """What the particle methods share: x stacked, the members' priors, Context.<name>(*args, x=, prior=, **kwargs), and
+        record(member, res, k, *late()) for every member k.  late: what the records need beside the dict and can be made only behind the
+        call, which has checked the arguments"""
+        xx = None if x is None else self._stack(x)
+        prior = self._prior()
+        res = getattr(self._context(), name)(*args, x=xx, prior=prior, **kwargs)
+        extra = late() if late else ()
+        return [record(v, res, k, *extra) for k, v in enumerate(self.vgps)]
+
     def particle_filter(self, n_paths, seed, ess_fraction=0.5, x=None, x0=None, history=False):
         """One particles.ParticleFilterResult per member (VarGP.particle_filter): each with its own data, observation times and count,
         prior, theta and Sigma; the histories are cut to the member's own observation count.  A member's result does not depend on the
         rest of the batch."""
-        xx = None if x is None else self._stack(x)
-        d = self.vgps[0].dim_d
-        prior = (np.stack([v._prior()[0][0] for v in self.vgps]), np.stack([v._prior()[1][0] for v in self.vgps]).reshape(self.B, d, d))
-        res = self._context().particle_filter(n_paths, seed, ess_fraction=ess_fraction, x=xx, x0=x0, prior=prior, history=history)
-        return [v._particle_record(res, k, np.asarray(v._inputs()["obs_t"]).size) for k, v in enumerate(self.vgps)]
+        return self._particle_call("particle_filter", lambda v, res, k: v._particle_record(res, k, np.asarray(v._inputs()["obs_t"]).size),
+                                   n_paths, seed, ess_fraction=ess_fraction, x=x, x0=x0, history=history)
 
     def particle_statistics(self, n_paths, seed, ess_fraction=0.5, x=None, x0=None, per_particle=False):
         """One particles.PathStatistics per member (VarGP.particle_statistics): the filter of particle_filter with the same arguments, each
         particle carrying the path statistics of its lineage under the member's own theta, Sigma, data and observation model."""
-        xx = None if x is None else self._stack(x)
-        d = self.vgps[0].dim_d
-        prior = (np.stack([v._prior()[0][0] for v in self.vgps]), np.stack([v._prior()[1][0] for v in self.vgps]).reshape(self.B, d, d))
-        res = self._context().particle_statistics(n_paths, seed, ess_fraction=ess_fraction, x=xx, x0=x0, prior=prior, per_particle=per_particle)
-        return [v._statistics_record(res, k, np.asarray(v._inputs()["obs_t"]).size) for k, v in enumerate(self.vgps)]
+        return self._particle_call("particle_statistics", lambda v, res, k: v._statistics_record(res, k, np.asarray(v._inputs()["obs_t"]).size),
+                                   n_paths, seed, ess_fraction=ess_fraction, x=x, x0=x0, per_particle=per_particle)
 
     def particle_events(self, n_paths, seed, levels, side=1, stride=1, ess_fraction=0.5, x=None, x0=None, per_particle=False):
         """One particles.PathEvents per member (VarGP.particle_events): the filter of particle_filter with the same arguments, each particle
         carrying the event records of its lineage.  levels and side: (B, D) for per-member levels and sides, or (D,) or a scalar for all."""
-        xx = None if x is None else self._stack(x)
-        d = self.vgps[0].dim_d
-        prior = (np.stack([v._prior()[0][0] for v in self.vgps]), np.stack([v._prior()[1][0] for v in self.vgps]).reshape(self.B, d, d))
-        res = self._context().particle_events(n_paths, seed, levels, side=side, stride=stride, ess_fraction=ess_fraction, x=xx, x0=x0, prior=prior,
-                                              per_particle=per_particle)
-        lev = np.broadcast_to(np.asarray(levels, dtype=float).reshape(-1, d) if np.size(levels) > 1 else np.reshape(levels, (1, 1)), (self.B, d))
-        sd = np.broadcast_to(np.asarray(side).reshape(-1, d) if np.size(side) > 1 else np.reshape(side, (1, 1)), (self.B, d))
-        return [v._events_record(res, k, lev[k], sd[k], stride, np.asarray(v._inputs()["obs_t"]).size) for k, v in enumerate(self.vgps)]
+        return self._particle_call("particle_events",
+                                   lambda v, res, k, lev, sd: v._events_record(res, k, lev[k], sd[k], stride, np.asarray(v._inputs()["obs_t"]).size),
+                                   n_paths, seed, levels, side=side, stride=stride, ess_fraction=ess_fraction, x=x, x0=x0, per_particle=per_particle,
+                                   late=lambda: (per_problem(levels, self.B, self.dim_d), per_problem(side, self.B, self.dim_d)))
 
     def particle_moments(self, n_paths, seed, stride=1, ess_fraction=0.5, x=None, x0=None):
         """One particles.SmoothingMoments per member (VarGP.particle_moments): the smoothing mean and second moment on the grid under the
         genealogy of the member's own filter, with its own data, observation times and count, prior, theta and Sigma."""
-        xx = None if x is None else self._stack(x)
-        d = self.vgps[0].dim_d
-        prior = (np.stack([v._prior()[0][0] for v in self.vgps]), np.stack([v._prior()[1][0] for v in self.vgps]).reshape(self.B, d, d))
-        res = self._context().particle_moments(n_paths, seed, stride=stride, ess_fraction=ess_fraction, x=xx, x0=x0, prior=prior)
-        return [v._moments_record(res, k, stride) for k, v in enumerate(self.vgps)]
+        return self._particle_call("particle_moments", lambda v, res, k: v._moments_record(res, k, stride), n_paths, seed, stride=stride,
+                                   ess_fraction=ess_fraction, x=x, x0=x0)
 
     def particle_covariance(self, n_paths, seed, stride=1, ess_fraction=0.5, x=None, x0=None):
         """One particles.SmoothingCovariance per member (VarGP.particle_covariance): the smoothing mean and full second-moment matrices on
         the grid under the genealogy of the member's own filter, with its own data, observation times and count, prior, theta and Sigma."""
-        xx = None if x is None else self._stack(x)
-        d = self.vgps[0].dim_d
-        prior = (np.stack([v._prior()[0][0] for v in self.vgps]), np.stack([v._prior()[1][0] for v in self.vgps]).reshape(self.B, d, d))
-        res = self._context().particle_covariance(n_paths, seed, stride=stride, ess_fraction=ess_fraction, x=xx, x0=x0, prior=prior)
-        return [v._covariance_record(res, k, stride) for k, v in enumerate(self.vgps)]
+        return self._particle_call("particle_covariance", lambda v, res, k: v._covariance_record(res, k, stride), n_paths, seed, stride=stride,
+                                   ess_fraction=ess_fraction, x=x, x0=x0)
 
     def particle_paths(self, n_paths, seed, n_draw, stride=1, ess_fraction=0.5, x=None, x0=None, slots=None):
         """One particles.SmoothingPaths per member (VarGP.particle_paths): n_draw whole smoothing trajectories from the genealogy of the
         member's own filter, with its own data, observation times and count, prior, theta and Sigma."""
-        xx = None if x is None else self._stack(x)
-        d = self.vgps[0].dim_d
-        prior = (np.stack([v._prior()[0][0] for v in self.vgps]), np.stack([v._prior()[1][0] for v in self.vgps]).reshape(self.B, d, d))
-        res = self._context().particle_paths(n_paths, seed, n_draw, stride=stride, ess_fraction=ess_fraction, x=xx, x0=x0, prior=prior, slots=slots)
-        return [v._paths_record(res, k, stride, slots is None) for k, v in enumerate(self.vgps)]
+        return self._particle_call("particle_paths", lambda v, res, k: v._paths_record(res, k, stride, slots is None), n_paths, seed, n_draw,
+                                   stride=stride, ess_fraction=ess_fraction, x=x, x0=x0, slots=slots)
 
     def backward_paths(self, n_paths, seed, n_draw, stride=1, ess_fraction=0.5, x=None, x0=None, slots=None):
         """One particles.SmoothingPaths per member (VarGP.backward_paths): n_draw whole smoothing trajectories drawn backwards through the
         clouds of the member's own filter, with its own data, observation times and count, prior, theta and Sigma."""
-        xx = None if x is None else self._stack(x)
-        d = self.vgps[0].dim_d
-        prior = (np.stack([v._prior()[0][0] for v in self.vgps]), np.stack([v._prior()[1][0] for v in self.vgps]).reshape(self.B, d, d))
-        res = self._context().particle_backward_paths(n_paths, seed, n_draw, stride=stride, ess_fraction=ess_fraction, x=xx, x0=x0, prior=prior,
-                                                      slots=slots)
-        return [v._paths_record(res, k, stride, slots is None, method="backward") for k, v in enumerate(self.vgps)]
+        return self._particle_call("particle_backward_paths", lambda v, res, k: v._paths_record(res, k, stride, slots is None, method="backward"),
+                                   n_paths, seed, n_draw, stride=stride, ess_fraction=ess_fraction, x=x, x0=x0, slots=slots)
 
     def forecast(self, horizon, n_paths=None, seed=0, stride=1, n_draw=0, ess_fraction=0.5, x=None, x0=None, source="filter", cloud=None,
                  log_w=None, index0=None, slots=None):
@@ -291,24 +283,8 @@ class ProblemBatch(object):
         posterior process's paths (source="posterior") or the given cloud (B, n, D) with log_w (B, n) at index0 -- carried `horizon` steps
         forward under its own theta and Sigma."""
         xx = None if x is None else self._stack(x)
-        v0 = self.vgps[0]
-        if source == "posterior":
-            if cloud is not None or n_paths is None:
-                raise ValueError(" forecast: source='posterior' draws its own cloud of n_paths particles.")
-            ends = self._context().sample_paths("posterior", n_paths, seed, stride=v0.dim_n - 1 if v0.dim_n > 1 else 1, x=xx, x0=x0)
-            cloud, log_w, index0 = ends[:, :, -1, :], None, v0.dim_n - 1
-        elif source != "filter":
-            raise ValueError(f" Unknown source of the forecast -> {source}")
-        if cloud is not None:
-            cloud = np.asarray(cloud, dtype=float)
-            cloud = cloud.reshape(cloud.shape + (1,)) if v0.model.single_dim and cloud.shape[-1:] != (1,) else cloud
-            res = self._context().particle_forecast(horizon, seed=seed, stride=stride, n_draw=n_draw, cloud=cloud, log_w=log_w, index0=index0,
-                                                    slots=slots)
-        else:
-            d = v0.dim_d
-            prior = (np.stack([v._prior()[0][0] for v in self.vgps]), np.stack([v._prior()[1][0] for v in self.vgps]).reshape(self.B, d, d))
-            res = self._context().particle_forecast(horizon, n_paths, seed, stride=stride, n_draw=n_draw, ess_fraction=ess_fraction, x=xx, x0=x0,
-                                                    slots=slots, prior=prior)
+        res = self.vgps[0]._forecast(self._context, self._prior, horizon, n_paths, seed, stride, n_draw, ess_fraction, xx, x0, source, cloud, log_w,
+                                     index0, slots)
         return [v._forecast_record(res, k, horizon, stride, slots is None) for k, v in enumerate(self.vgps)]
 
     def particle_fit_theta(self, n_paths, seed, iters, ess_fraction=0.5, refit=True, pooled=False, x0=None, options=None):
@@ -373,8 +349,7 @@ class ProblemBatch(object):
         if iters < 1 or burn < 0 or thin < 1:
             raise ValueError(" ProblemBatch.particle_gibbs: iters and thin must be at least 1, burn at least 0.")
         xx = (self.initialization() if self._x is None else self._x.copy()) if x is None else self._stack(x).copy()
-        d, v0 = self.dim_d, self.vgps[0]
-        prior = (np.stack([v._prior()[0][0] for v in self.vgps]), np.stack([v._prior()[1][0] for v in self.vgps]).reshape(self.B, d, d))
+        d, v0, prior = self.dim_d, self.vgps[0], self._prior()
         dt, model = float(v0.fwd_ode.dt), v0.model._model_id
         first = self._context().particle_paths(n_paths, seed, 1, ess_fraction=ess_fraction, x=xx, prior=prior)["paths"][:, 0]
         ref = np.ascontiguousarray(first)

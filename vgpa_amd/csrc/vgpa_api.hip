@@ -1596,25 +1596,29 @@ int vgpa_sample_paths_weighted(vgpa_ctx* c, const double* x, const double* x0, i
 // The guided particle filter (see vgpa_hip.h): the weighted walk of vgpa_sample_paths_weighted cut at the observation
 // indices of the batch, the particles resident between the cuts, a resampling step behind every cut that is an observation of some problem.
 // ParticleRequest: what one of the entry points wants from it and where the results go (nullptr: not wanted).
+// Its two choices: the rows the filter's slots carry along their lineages, and the pass that runs behind the filter.  A forecast behind
+// the filter is "fc_moments is set"; it goes with Carry::None and Behind::None alone.
+enum class Carry { None, Stats, Events };      // nothing; the path statistics (Q, G, H); the event records (X, T, N)
+// (the order matters: table() below takes every enumerator from Trajectories on as a pass with a slot table; a new pass of sums goes before it)
+enum class Behind { None, Moments, Covariance, Trajectories, Backward, Conditional };
 struct ParticleRequest {
   const double* x; const double* x0; int32_t n_paths; uint64_t seed; double ess_fraction; const double* prior_mu; const double* prior_tau;
   double* logw; double* state; double* ess; int32_t* resampled;      // (up to here: what every entry point has, filled in this order)
-  int32_t* ancestors; double* clouds;                                // vgpa_particle_filter: the histories
-  bool with_stats; double* stats; double* mean;                      // vgpa_particle_statistics: the final rows, their weighted mean
-  int32_t stride = 1;                                                // of the grid indices the two smoothers keep
-  double* moments; double* lineage_ess;                              // vgpa_particle_moments
-  int32_t n_draw; const int32_t* final_slots; double* paths; int32_t* slots_out;      // vgpa_particle_paths; slots_out: where the table goes
-  bool backward;                                                     // vgpa_particle_backward_paths: the table is drawn, not traced
-  // vgpa_particle_forecast: horizon steps behind the filter, or from `cloud` at index0; stride, n_draw, final_slots, slots_out as above;
-  // moments is then fc_moments
-  bool forecast; int32_t horizon; const double* cloud; const double* cloud_logw; int32_t index0;
+  int32_t* ancestors; double* clouds;                                // vgpa_particle_filter, vgpa_particle_conditional: the histories
+  Carry rows; double* stats; double* mean;                            // the final rows, their weighted mean
+  const double* levels; const int32_t* sides; double* cdf;           // Carry::Events: levels and sides [B][D]; the first-passage distribution
+  int32_t stride = 1;                                                // of the grid indices the smoothers, the events and the forecast keep
+  Behind behind;
+  double* moments; double* lineage_ess;                              // Behind::Moments (lineage_ess: Covariance too)
+  double* cov_mean; double* cov_second;                              // Behind::Covariance
+  // Behind::Trajectories / Backward (the table is drawn, not traced) / Conditional (slot 0 pinned to ref [B][Np][D]; n_draw = 1, paths: the
+  // drawn trajectory); slots_out: where the table goes
+  int32_t n_draw; const int32_t* final_slots; double* paths; int32_t* slots_out; const double* ref;
+  // vgpa_particle_forecast: horizon steps behind the filter, or from `cloud` at index0; stride, n_draw, final_slots, slots_out as above
+  int32_t horizon; const double* cloud; const double* cloud_logw; int32_t index0;
   double* fc_moments; double* members; double* state_end;
-  bool covariance; double* cov_mean; double* cov_second;            // vgpa_particle_covariance (lineage_ess as for the moments)
-  // vgpa_particle_conditional: slot 0 pinned to ref [B][Np][D]; n_draw = 1, paths: the drawn trajectory, slots_out: its slot table
-  bool conditional; const double* ref;
-  // vgpa_particle_events: the rows of with_stats are the event records (X, T, N) of the levels and sides [B][D]; stats: the final rows, mean:
-  // their weighted mean, cdf: the first-passage distribution at every stride-th grid index
-  bool events; const double* levels; const int32_t* sides; double* cdf;
+  bool sums() const { return behind == Behind::Moments || behind == Behind::Covariance; }      // the replay with its weighted sums
+  bool table() const { return behind >= Behind::Trajectories; }                                // a slot table and the walk of its trajectories
 };
 
 // One run: the filter, then what the request puts behind it.  The passes share the kernels' arguments, the cuts and where the particles are.
@@ -1624,22 +1628,26 @@ struct ParticleRun {
   std::vector<char> is_obs;            // [Np] the grid index is an observation of some problem
   std::vector<int> count;              // [B] each problem's own observation count
   double* cur; double* other;          // the particles: where they are, where the next step puts them
-  double* st_cur; double* st_other;    // ... and their rows of path statistics (with_stats)
+  double* st_cur; double* st_other;    // ... and their rows (Carry::Stats, Carry::Events)
   int n_keep, rows, slot_rows, n_blocks; size_t mom_len, n_table, n_traj;
   int k0 = 0;                          // the forecast: the absolute grid index of the cloud
   const double* ev_level = nullptr; const int32_t* ev_side = nullptr;      // events: the levels and sides [B][D] on the device
+  // what follows from the request, derived once in setup(): the histories the device keeps (ancestors, clouds, replaced log-weights),
+  // the walk of the filter's segments and whether the step between them is the conditional filter's
+  bool keep_anc = false, keep_clouds = false, keep_lw = false, pinned = false;
+  Walk segment = Walk::Segment;
 
   int buf(int which, size_t count) { return grow(c, &c->d_pf[which], &c->pf_n[which], count); }      // d_pf[which]: at least `count` doubles
 
   // For each cut -- an observation index of some problem, and the last grid index --: the segment launch up to it, then, at an
-  // observation, the step between two segments (from cur to other), and the particle buffers swap.
-  int cuts(Walk walk, const char* what, SampleArgs& s, const char* step_what, const std::function<hipError_t(int)>& step) {
+  // observation, the step between two segments (from cur to other), and the particle buffers swap.  pf_ref, lev, side: the walk's own.
+  int cuts(Walk walk, const char* what, SampleArgs& s, const char* step_what, const std::function<hipError_t(int)>& step,
+           const double* pf_ref = nullptr, const double* lev = nullptr, const int32_t* side = nullptr) {
     int prev = 0;
     for (int k = 0; k < c->Np; k++) {
       if (!is_obs[k] && k != c->Np - 1) continue;
       s.k_begin = prev; s.k_end = k; s.pf_x = cur;
-      const bool ev = walk == Walk::SegmentEvents;
-      hipError_t e = launch_sample_walk(walk, s, c->stream, walk == Walk::Conditional ? f.ref : nullptr, ev ? ev_level : nullptr, ev ? ev_side : nullptr);
+      hipError_t e = launch_sample_walk(walk, s, c->stream, pf_ref, lev, side);
       if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "%s failed: %s", what, hipGetErrorString(e));
       s.seg_first = 0; prev = k;
       if (!is_obs[k]) continue;
@@ -1655,20 +1663,24 @@ struct ParticleRun {
     int rc;
     if ((rc = sample_args(c, VGPA_PATHS_POSTERIOR, q.x, q.x0, q.n_paths, 1, q.seed, true, &a))) return rc;
     const size_t n = (size_t)q.n_paths, BnD = (size_t)B * n * D, Bn = (size_t)B * n, BM = (size_t)B * M1;
-    const bool history = q.ancestors || q.moments || q.covariance || q.paths;
+    keep_anc = q.ancestors || q.behind != Behind::None;      // (every pass behind the filter reads the ancestors)
+    keep_clouds = q.clouds || q.behind == Behind::Backward || q.behind == Behind::Conditional;      // (their walk reads the clouds on the device)
+    keep_lw = q.behind == Behind::Backward; pinned = q.behind == Behind::Conditional;
+    segment = pinned ? Walk::Conditional : q.rows == Carry::Events ? Walk::SegmentEvents : q.rows == Carry::Stats ? Walk::SegmentStats : Walk::Segment;
+    const bool covariance = q.behind == Behind::Covariance, carried = q.rows != Carry::None;
     auto ints = [](size_t count) { return (count + 1) / 2; };      // int32 entries in a buffer of doubles
     if ((rc = buf(vgpa_ctx::PF_XA, BnD)) || (rc = buf(vgpa_ctx::PF_XB, BnD)) || (rc = buf(vgpa_ctx::PF_LW, Bn)) || (rc = buf(vgpa_ctx::PF_CUM, Bn)) ||
         (rc = buf(vgpa_ctx::PF_ANC, ints(Bn))) || (rc = buf(vgpa_ctx::PF_ESS, BM)) || (rc = buf(vgpa_ctx::PF_FLAG, ints(BM)))) return rc;
-    if (history && (rc = buf(vgpa_ctx::PF_HANC, ints(BM * n)))) return rc;
+    if (keep_anc && (rc = buf(vgpa_ctx::PF_HANC, ints(BM * n)))) return rc;
     n_keep = (c->Np - 1) / q.stride + 1; slot_rows = M + 1; rows = M1 + 1; n_blocks = sample_segment_blocks(D, q.n_paths);
-    n_table = (size_t)B * slot_rows * (size_t)q.n_draw; n_traj = (size_t)B * (size_t)q.n_draw * ((size_t)n_keep * D); mom_len = (size_t)n_keep * (q.covariance ? sample_cov_len(D) : (size_t)2 * D);
-    if (q.paths && ((rc = buf(vgpa_ctx::PF_SLOTS, ints(n_table))) || (rc = grow(c, &c->d_sp_out, &c->sp_out_n, n_traj)))) return rc;
-    if ((q.moments || q.covariance) && ((rc = buf(vgpa_ctx::PF_WTAB, (size_t)B * rows * n)) || (rc = buf(vgpa_ctx::PF_LESS, (size_t)B * rows)) ||
+    n_table = (size_t)B * slot_rows * (size_t)q.n_draw; n_traj = (size_t)B * (size_t)q.n_draw * ((size_t)n_keep * D); mom_len = (size_t)n_keep * (covariance ? sample_cov_len(D) : (size_t)2 * D);
+    if (q.table() && ((rc = buf(vgpa_ctx::PF_SLOTS, ints(n_table))) || (rc = grow(c, &c->d_sp_out, &c->sp_out_n, n_traj)))) return rc;
+    if (q.sums() && ((rc = buf(vgpa_ctx::PF_WTAB, (size_t)B * rows * n)) || (rc = buf(vgpa_ctx::PF_LESS, (size_t)B * rows)) ||
                       (rc = buf(vgpa_ctx::PF_PART, (size_t)B * n_blocks * mom_len)) || (rc = buf(vgpa_ctx::PF_MOM, (size_t)B * mom_len)))) return rc;
-    if (q.covariance && (rc = buf(vgpa_ctx::PF_COV, (size_t)B * n_keep * D * ((size_t)D + 1)))) return rc;
-    if ((q.clouds || q.backward || q.conditional) && (rc = buf(vgpa_ctx::PF_CLOUDS, BM * n * D))) return rc;      // (backward simulation and the conditional filter's walk read them on the device)
-    if (q.backward && (rc = buf(vgpa_ctx::PF_HLW, BM * n))) return rc;
-    if (q.with_stats && ((rc = buf(vgpa_ctx::PF_STA, 3 * BnD)) || (rc = buf(vgpa_ctx::PF_STB, 3 * BnD)) || (rc = buf(vgpa_ctx::PF_MEAN, (size_t)B * 3 * D)))) return rc;
+    if (covariance && (rc = buf(vgpa_ctx::PF_COV, (size_t)B * n_keep * D * ((size_t)D + 1)))) return rc;
+    if (keep_clouds && (rc = buf(vgpa_ctx::PF_CLOUDS, BM * n * D))) return rc;
+    if (keep_lw && (rc = buf(vgpa_ctx::PF_HLW, BM * n))) return rc;
+    if (carried && ((rc = buf(vgpa_ctx::PF_STA, 3 * BnD)) || (rc = buf(vgpa_ctx::PF_STB, 3 * BnD)) || (rc = buf(vgpa_ctx::PF_MEAN, (size_t)B * 3 * D)))) return rc;
     f = PfArgs{};
     f.D = D; f.batch = B; f.n_paths = q.n_paths; f.M = M1; f.seed = q.seed; f.ess_fraction = q.ess_fraction;
     f.x0 = a.x0; f.m0 = a.m0; f.L0 = a.L0; f.m0_stride = a.m0_stride; f.L0_stride = a.L0_stride;
@@ -1682,21 +1694,21 @@ struct ParticleRun {
       f.mu0 = c->d_pf[vgpa_ctx::PF_MU]; f.Lt = c->d_pf[vgpa_ctx::PF_LT];
     }
     cur = c->d_pf[vgpa_ctx::PF_XA]; other = c->d_pf[vgpa_ctx::PF_XB];
-    st_cur = q.with_stats ? c->d_pf[vgpa_ctx::PF_STA] : nullptr; st_other = q.with_stats ? c->d_pf[vgpa_ctx::PF_STB] : nullptr;
+    st_cur = carried ? c->d_pf[vgpa_ctx::PF_STA] : nullptr; st_other = carried ? c->d_pf[vgpa_ctx::PF_STB] : nullptr;
     f.x = cur; f.ws = other; f.lw = c->d_pf[vgpa_ctx::PF_LW]; f.cum = c->d_pf[vgpa_ctx::PF_CUM];
     f.anc = reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_ANC]);
     f.h_ess = c->d_pf[vgpa_ctx::PF_ESS]; f.h_flag = reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_FLAG]);
-    f.h_anc = history ? reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_HANC]) : nullptr;
-    f.h_clouds = q.clouds || q.backward || q.conditional ? c->d_pf[vgpa_ctx::PF_CLOUDS] : nullptr;
-    f.h_lw = q.backward ? c->d_pf[vgpa_ctx::PF_HLW] : nullptr;
-    if (q.events) {      // the levels and sides: uploaded once per call, read from global memory at every segment's entry
+    f.h_anc = keep_anc ? reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_HANC]) : nullptr;
+    f.h_clouds = keep_clouds ? c->d_pf[vgpa_ctx::PF_CLOUDS] : nullptr;
+    f.h_lw = keep_lw ? c->d_pf[vgpa_ctx::PF_HLW] : nullptr;
+    if (q.rows == Carry::Events) {      // the levels and sides: uploaded once per call, read from global memory at every segment's entry
       const size_t BD = (size_t)B * D;
       if ((rc = buf(vgpa_ctx::PF_EVC, BD)) || (rc = buf(vgpa_ctx::PF_EVS, ints(BD))) || (q.cdf && (rc = buf(vgpa_ctx::PF_CDF, (size_t)B * n_keep * D)))) return rc;
       int32_t* d_side = reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_EVS]);
       if ((rc = upload(c, c->d_pf[vgpa_ctx::PF_EVC], q.levels, BD)) || (rc = upload(c, d_side, q.sides, BD))) return rc;
       ev_level = c->d_pf[vgpa_ctx::PF_EVC]; ev_side = d_side;
     }
-    if (q.conditional) {      // the reference trajectories: uploaded once per call, read from global memory by the walk and the steps
+    if (pinned) {      // the reference trajectories: uploaded once per call, read from global memory by the walk and the steps
       const size_t n_ref = (size_t)B * c->Np * D;
       if ((rc = buf(vgpa_ctx::PF_REF, n_ref)) || (rc = upload(c, c->d_pf[vgpa_ctx::PF_REF], q.ref, n_ref))) return rc;
       f.ref = c->d_pf[vgpa_ctx::PF_REF]; f.Np = c->Np;
@@ -1722,21 +1734,21 @@ struct ParticleRun {
     HIP_TRY(c, hipMemsetAsync(f.h_flag, 0, BM * sizeof(int32_t), c->stream));
     if (f.h_anc) HIP_TRY(c, hipMemsetAsync(f.h_anc, 0xff, BM * n * sizeof(int32_t), c->stream));      // (-1 beyond a problem's own count)
     LAUNCH_TRY(c, "particle start launch", launch_pf_start(f, c->stream));
-    if (q.conditional) LAUNCH_TRY(c, "pinned start launch", launch_pf_pin(f, c->stream));
+    if (pinned) LAUNCH_TRY(c, "pinned start launch", launch_pf_pin(f, c->stream));
     a.pf_lw = f.lw; a.seg_first = 1; a.pf_stats = st_cur;
-    if (q.conditional)      // (the segment with slot 0 pinned, the step with ancestor sampling)
-      return cuts(Walk::Conditional, "conditional segment launch", a, "conditional resampling launch", [&](int k) {
+    if (pinned)      // (the segment with slot 0 pinned, the step with ancestor sampling)
+      return cuts(segment, "conditional segment launch", a, "conditional resampling launch", [&](int k) {
         f.k = k; f.last = k == c->Np - 1 ? 1 : 0; f.x_in = cur; f.x_out = other;
         return launch_pf_cresample(f, a, c->stream);
-      });
-    if (q.events) LAUNCH_TRY(c, "event start rows launch", launch_pf_events_start(c->D, c->B, q.n_paths, c->Np, cur, ev_level, ev_side, st_cur, c->stream));
-    else if (q.with_stats) HIP_TRY(c, hipMemsetAsync(st_cur, 0, 3 * (size_t)c->B * n * c->D * sizeof(double), c->stream));
-    return cuts(q.events ? Walk::SegmentEvents : q.with_stats ? Walk::SegmentStats : Walk::Segment, "particle segment launch", a, "particle resampling launch", [&](int k) {
+      }, f.ref);
+    if (q.rows == Carry::Events) LAUNCH_TRY(c, "event start rows launch", launch_pf_events_start(c->D, c->B, q.n_paths, c->Np, cur, ev_level, ev_side, st_cur, c->stream));
+    else if (q.rows == Carry::Stats) HIP_TRY(c, hipMemsetAsync(st_cur, 0, 3 * (size_t)c->B * n * c->D * sizeof(double), c->stream));
+    return cuts(segment, "particle segment launch", a, "particle resampling launch", [&](int k) {
       f.k = k; f.last = k == c->Np - 1 ? 1 : 0; f.x_in = cur; f.x_out = other; f.st_in = st_cur; f.st_out = st_other;
       std::swap(st_cur, st_other);      // (the next segment carries the rows the step is about to write)
       a.pf_stats = st_cur;
       return launch_pf_resample(f, c->stream);
-    });
+    }, nullptr, ev_level, ev_side);
   }
 
   // The smoothing moments, behind the filter, whose ancestor history stays on the device: the descendant weights, then
@@ -1759,12 +1771,13 @@ struct ParticleRun {
     SampleArgs w = a;
     w.stride = q.stride; w.n_keep = n_keep; w.seg_first = 1; w.pf_stats = nullptr;
     w.pf_wtab = wtab; w.pf_part = c->d_pf[vgpa_ctx::PF_PART]; w.pf_rows = rows;
-    if ((rc = cuts(q.covariance ? Walk::ReplayCov : Walk::Replay, "replay segment launch", w, "replay gather launch", [&](int k) {
+    const bool covariance = q.behind == Behind::Covariance;
+    if ((rc = cuts(covariance ? Walk::ReplayCov : Walk::Replay, "replay segment launch", w, "replay gather launch", [&](int k) {
           g.k = k; g.x_in = cur; g.x_out = other;
           return launch_pf_gather(g, c->stream);
         }))) return rc;
     LAUNCH_TRY(c, "moments sum launch", launch_pf_moments_sum(B, n_blocks, mom_len, w.pf_part, c->d_pf[vgpa_ctx::PF_MOM], c->stream));
-    if (q.covariance) {
+    if (covariance) {
       const size_t kept = (size_t)B * n_keep, n_mean = kept * c->D;
       double* d_mean = c->d_pf[vgpa_ctx::PF_COV];
       LAUNCH_TRY(c, "covariance unpack launch", launch_pf_cov_unpack(c->D, kept, c->d_pf[vgpa_ctx::PF_MOM], d_mean, d_mean + n_mean, c->stream));
@@ -1776,37 +1789,21 @@ struct ParticleRun {
     return VGPA_OK;
   }
 
-  // The smoothing trajectories, behind the filter, whose ancestor history stays on the device: the final slots of n_draw
-  // trajectories (final_slots, or drawn from the final weights), their slots in every stretch traced back through the ancestors, one
-  // launch of the lineage walk over the n_draw trajectories alone, the downloads.
+  // The trajectories behind the filter, whose histories stay on the device: the final slots of n_draw trajectories (final_slots, or drawn
+  // from the final weights), the table of their slots in every stretch made in one launch, one launch of the walk over the n_draw
+  // trajectories alone, the downloads.
+  //   Behind::Trajectories: the table traced back through the ancestors, the lineage walk.
+  //   Behind::Backward (s.4.17): the table drawn backwards through the clouds and the replaced log-weights, the backward walk.
+  //   Behind::Conditional (s.4.18): the table traced (slot 0's ancestors are the ancestor-sampled ones), the backward walk on this run's
+  //   histories -- it goes on from the true particle, the reference's where the ancestor is slot 0, behind every observation --, and the
+  //   stretches spent in slot 0, where that walk drew with slot 0's counters, overwritten with the reference before the download.
   int trajectories() {
     int rc;
     int32_t* table = reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_SLOTS]);
     if ((rc = final_slots(table))) return rc;
-    LAUNCH_TRY(c, "genealogy launch", launch_pf_trace(f, q.n_draw, slot_rows, table, c->stream));
-    return walk_table(Walk::Lineage, "lineage walk launch", table);
-  }
-
-  // The smoothing trajectories by backward simulation, behind the filter, whose ancestors, clouds and replaced log-weights
-  // stay on the device: the final slots as trajectories() has them, the table drawn backwards through the clouds in one launch, one launch
-  // of the backward walk over the n_draw trajectories alone, the downloads.
-  int backward_trajectories() {
-    int rc;
-    int32_t* table = reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_SLOTS]);
-    if ((rc = final_slots(table))) return rc;
-    LAUNCH_TRY(c, "backward simulation launch", launch_pf_backward(f, a, q.n_draw, slot_rows, table, c->stream));
-    return walk_table(Walk::Backward, "backward walk launch", table);
-  }
-
-  // The trajectory of the conditional filter: the final slot drawn from the final weights, traced through the kept
-  // ancestors (slot 0's are the ancestor-sampled ones), walked by the backward walk on this run's histories -- it goes on from the true
-  // particle, the reference's where the ancestor is slot 0, behind every observation --, and the stretches it spent in slot 0, where that
-  // walk drew with slot 0's counters, overwritten with the reference before the download.
-  int conditional_trajectory() {
-    int rc;
-    int32_t* table = reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_SLOTS]);
-    if ((rc = final_slots(table))) return rc;
-    LAUNCH_TRY(c, "genealogy launch", launch_pf_trace(f, q.n_draw, slot_rows, table, c->stream));
+    if (q.behind == Behind::Backward) LAUNCH_TRY(c, "backward simulation launch", launch_pf_backward(f, a, q.n_draw, slot_rows, table, c->stream));
+    else LAUNCH_TRY(c, "genealogy launch", launch_pf_trace(f, q.n_draw, slot_rows, table, c->stream));
+    if (q.behind == Behind::Trajectories) return walk_table(Walk::Lineage, "lineage walk launch", table);
     return walk_table(Walk::Backward, "backward walk launch", table);
   }
 
@@ -1836,7 +1833,7 @@ struct ParticleRun {
     if (walk == Walk::Backward) { w.pf_clouds = f.h_clouds; w.pf_hanc = f.h_anc; w.pf_M = f.M; w.pf_n = q.n_paths; }
     hipError_t e = launch_sample_walk(walk, w, c->stream);
     if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "%s failed: %s", what, hipGetErrorString(e));
-    if (q.conditional) LAUNCH_TRY(c, "reference stretches launch", launch_pf_ref_fill(f, slot_rows, table, c->d_sp_out, c->stream));
+    if (pinned) LAUNCH_TRY(c, "reference stretches launch", launch_pf_ref_fill(f, slot_rows, table, c->d_sp_out, c->stream));
     if ((rc = download(c, q.paths, c->d_sp_out, n_traj))) return rc;
     if (q.slots_out) HIP_TRY(c, hipMemcpyAsync(q.slots_out, table, n_table * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     return VGPA_OK;
@@ -1926,51 +1923,51 @@ static int particle_run(vgpa_ctx* c, const ParticleRequest& q) {
   if (!c) return VGPA_ERR_ARG;
   if (!q.logw || !q.state) return fail(c, VGPA_ERR_ARG, "null argument");
   if (q.stride < 1) return fail(c, VGPA_ERR_ARG, "stride must be at least 1 (stride = %d)", q.stride);
-  if (q.with_stats && !q.events && !q.stats && !q.mean) return fail(c, VGPA_ERR_ARG, "at least one of stats and mean must be given");
+  if (q.rows == Carry::Stats && !q.stats && !q.mean) return fail(c, VGPA_ERR_ARG, "at least one of stats and mean must be given");
   const int32_t n_paths = q.n_paths, n_draw = q.n_draw, stride = q.stride;
   if (n_paths < 1) return fail(c, VGPA_ERR_ARG, "n_paths must be at least 1 (n_paths = %d)", n_paths);
   int rc;
-  if (q.paths && q.final_slots && (rc = check_slots(c, q.final_slots, n_draw, n_paths, "final slot", "trajectory"))) return rc;
+  if (q.table() && q.final_slots && (rc = check_slots(c, q.final_slots, n_draw, n_paths, "final slot", "trajectory"))) return rc;
   if (!(q.ess_fraction >= 0.0 && q.ess_fraction <= 1.0)) return fail(c, VGPA_ERR_ARG, "ess_fraction must lie in [0, 1] (ess_fraction = %g)", q.ess_fraction);
   if ((q.prior_mu == nullptr) != (q.prior_tau == nullptr)) return fail(c, VGPA_ERR_ARG, "the prior is a mean and a covariance: both or neither");
   if (c->cfg.model == VGPA_MODEL_NONE) return fail(c, VGPA_ERR_ARG, "context has no stochastic model: no model SDE to weigh the particles against");
   if (!c->full) return fail(c, VGPA_ERR_STATE, "context was created without m0/s0/observations (ODE-only)");
   const int D = c->D, B = c->B, M = c->M, Np = c->Np;
   const int kept = (Np - 1) / stride + 1;
+  const bool moments = q.behind == Behind::Moments, covariance = q.behind == Behind::Covariance, carried = q.rows != Carry::None;
   if (D <= kMaxSmallD) {      // the launch limits and the sizes of the results, before any work
-    if ((q.moments || q.covariance) && n_paths > sample_max_paths(D))      // (the replay)
+    if (q.sums() && n_paths > sample_max_paths(D))      // (the replay)
       return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing %s are built for at most %d particles per problem at D = %d (n_paths = %d)",
-                  q.moments ? "moments" : "covariances", sample_max_paths(D), D, n_paths);
-    if (q.moments && (rc = check_sums(c, kept, "smoothing", "grid indices"))) return rc;
+                  moments ? "moments" : "covariances", sample_max_paths(D), D, n_paths);
+    if (moments && (rc = check_sums(c, kept, "smoothing", "grid indices"))) return rc;
     // (the sum of the covariance replay's packed partial sums and the unpacking launch)
-    if (q.covariance && !(pf_flat_grid_fits((size_t)B * kept * D * D) && pf_flat_grid_fits((size_t)B * kept * sample_cov_len(D))))
+    if (covariance && !(pf_flat_grid_fits((size_t)B * kept * D * D) && pf_flat_grid_fits((size_t)B * kept * sample_cov_len(D))))
       return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing covariances are built for at most 2^39 - 256 entries (batch %d, %d kept grid indices, D = %d): use a larger stride",
                   B, kept, D);
-    if (q.paths && !sample_lineages_fit(D, B, n_draw))      // (the lineage walk; the number is the matrix-core walk's, above D = 4)
+    if (q.table() && !sample_lineages_fit(D, B, n_draw))      // (the lineage walk; the number is the matrix-core walk's, above D = 4)
       return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing trajectories are built for at most %d per problem at D = %d (n_draw = %d)", sample_max_paths(kMaxSmallD), D, n_draw);
-    if (q.paths && q.backward && !pf_backward_fits(n_draw))      // (the one launch of the backward simulation)
+    if (q.behind == Behind::Backward && !pf_backward_fits(n_draw))      // (the one launch of the backward simulation)
       return fail(c, VGPA_ERR_UNSUPPORTED, "backward simulation is built for at most %d trajectories per problem (n_draw = %d)", kMaxGridY * kBackwardBlock, n_draw);
-    if (q.paths && (rc = check_stored(c, n_draw, kept, "smoothing trajectories", "trajectories", "grid indices"))) return rc;
+    if (q.table() && (rc = check_stored(c, n_draw, kept, "smoothing trajectories", "trajectories", "grid indices"))) return rc;
   }
   ParticleRun r{c, q};
-  if ((rc = r.setup()) || (rc = r.filter()) || ((q.moments || q.covariance) && (rc = r.moments())) ||
-      (q.paths && (rc = q.conditional ? r.conditional_trajectory() : q.backward ? r.backward_trajectories() : r.trajectories()))) return rc;
+  if ((rc = r.setup()) || (rc = r.filter()) || (q.sums() && (rc = r.moments())) || (q.table() && (rc = r.trajectories()))) return rc;
   const size_t n = (size_t)n_paths, BnD = (size_t)B * n * D;
-  if (q.forecast) {      // (the filter's final cloud leaves before the forecast carries it on in place)
+  if (q.fc_moments) {      // (the filter's final cloud leaves before the forecast carries it on in place)
     if ((rc = download(c, q.state, r.cur, BnD))) return rc;
     r.k0 = Np - 1;
     if ((rc = r.forecast())) return rc;
   }
-  if (q.with_stats && q.mean) {
+  if (carried && q.mean) {
     LAUNCH_TRY(c, "path statistics mean launch", launch_pf_stats_mean(D, B, n_paths, r.f.lw, r.st_cur, c->d_pf[vgpa_ctx::PF_MEAN], c->stream));
     if ((rc = download(c, q.mean, c->d_pf[vgpa_ctx::PF_MEAN], (size_t)B * 3 * D))) return rc;
   }
-  if (q.with_stats && q.stats && (rc = download(c, q.stats, r.st_cur, 3 * BnD))) return rc;
-  if (q.events && q.cdf) {
+  if (carried && q.stats && (rc = download(c, q.stats, r.st_cur, 3 * BnD))) return rc;
+  if (q.rows == Carry::Events && q.cdf) {
     LAUNCH_TRY(c, "first-passage distribution launch", launch_pf_events_cdf(D, B, n_paths, Np, stride, r.f.lw, r.st_cur, c->d_pf[vgpa_ctx::PF_CDF], c->stream));
     if ((rc = download(c, q.cdf, c->d_pf[vgpa_ctx::PF_CDF], (size_t)B * kept * D))) return rc;
   }
-  if ((rc = download(c, q.logw, r.f.lw, (size_t)B * n)) || (!q.forecast && (rc = download(c, q.state, r.cur, BnD)))) return rc;
+  if ((rc = download(c, q.logw, r.f.lw, (size_t)B * n)) || (!q.fc_moments && (rc = download(c, q.state, r.cur, BnD)))) return rc;
   if (q.ess && (rc = download(c, q.ess, r.f.h_ess, (size_t)B * M))) return rc;
   if (q.resampled && M > 0) HIP_TRY(c, hipMemcpyAsync(q.resampled, r.f.h_flag, (size_t)B * M * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   if (q.ancestors && M > 0) HIP_TRY(c, hipMemcpyAsync(q.ancestors, r.f.h_anc, (size_t)B * M * n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
@@ -1994,7 +1991,7 @@ int vgpa_particle_statistics(vgpa_ctx* c, const double* x, const double* x0, int
                              const double* prior_mu, const double* prior_tau, double* logw, double* state, double* stats, double* mean,
                              double* ess, int32_t* resampled) {
   ParticleRequest q{x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled};
-  q.with_stats = true; q.stats = stats; q.mean = mean;
+  q.rows = Carry::Stats; q.stats = stats; q.mean = mean;
   return particle_run(c, q);
 }
 
@@ -2011,8 +2008,8 @@ int vgpa_particle_events(vgpa_ctx* c, const double* x, const double* x0, int32_t
     if (sides[e] != 1 && sides[e] != -1) return fail(c, VGPA_ERR_ARG, "sides must be +1 or -1 (problem %zu, component %zu: %d)", e / c->D, e % c->D, sides[e]);
   }
   ParticleRequest q{x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled};
-  q.stride = stride; q.with_stats = true; q.stats = rows; q.mean = mean;
-  q.events = true; q.levels = levels; q.sides = sides; q.cdf = cdf;
+  q.stride = stride; q.rows = Carry::Events; q.stats = rows; q.mean = mean;
+  q.levels = levels; q.sides = sides; q.cdf = cdf;
   return particle_run(c, q);
 }
 
@@ -2023,7 +2020,7 @@ int vgpa_particle_moments(vgpa_ctx* c, const double* x, const double* x0, int32_
   if (!c) return VGPA_ERR_ARG;
   if (!moments) return fail(c, VGPA_ERR_ARG, "null argument");
   ParticleRequest q{x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled};
-  q.stride = stride; q.moments = moments; q.lineage_ess = lineage_ess;
+  q.stride = stride; q.behind = Behind::Moments; q.moments = moments; q.lineage_ess = lineage_ess;
   return particle_run(c, q);
 }
 
@@ -2034,7 +2031,7 @@ int vgpa_particle_covariance(vgpa_ctx* c, const double* x, const double* x0, int
   if (!c) return VGPA_ERR_ARG;
   if (!mean || !second) return fail(c, VGPA_ERR_ARG, "null argument");
   ParticleRequest q{x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled};
-  q.stride = stride; q.covariance = true; q.cov_mean = mean; q.cov_second = second; q.lineage_ess = lineage_ess;
+  q.stride = stride; q.behind = Behind::Covariance; q.cov_mean = mean; q.cov_second = second; q.lineage_ess = lineage_ess;
   return particle_run(c, q);
 }
 
@@ -2046,7 +2043,7 @@ int vgpa_particle_paths(vgpa_ctx* c, const double* x, const double* x0, int32_t 
   if (!paths) return fail(c, VGPA_ERR_ARG, "null argument");
   if (n_draw < 1) return fail(c, VGPA_ERR_ARG, "n_draw must be at least 1 (n_draw = %d)", n_draw);
   ParticleRequest q{x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled};
-  q.stride = stride; q.n_draw = n_draw; q.final_slots = final_slots; q.paths = paths; q.slots_out = slots;
+  q.stride = stride; q.n_draw = n_draw; q.final_slots = final_slots; q.paths = paths; q.slots_out = slots; q.behind = Behind::Trajectories;
   return particle_run(c, q);
 }
 
@@ -2058,7 +2055,7 @@ int vgpa_particle_backward_paths(vgpa_ctx* c, const double* x, const double* x0,
   if (!paths) return fail(c, VGPA_ERR_ARG, "null argument");
   if (n_draw < 1) return fail(c, VGPA_ERR_ARG, "n_draw must be at least 1 (n_draw = %d)", n_draw);
   ParticleRequest q{x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled};
-  q.stride = stride; q.n_draw = n_draw; q.final_slots = final_slots; q.paths = paths; q.slots_out = slots; q.backward = true;
+  q.stride = stride; q.n_draw = n_draw; q.final_slots = final_slots; q.paths = paths; q.slots_out = slots; q.behind = Behind::Backward;
   return particle_run(c, q);
 }
 
@@ -2070,7 +2067,7 @@ int vgpa_particle_conditional(vgpa_ctx* c, const double* x, const double* x0, co
   if (!ref || !trajectory) return fail(c, VGPA_ERR_ARG, "null argument");
   ParticleRequest q{x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled};
   q.ancestors = ancestors; q.clouds = clouds;
-  q.n_draw = 1; q.paths = trajectory; q.slots_out = slots; q.conditional = true; q.ref = ref;
+  q.n_draw = 1; q.paths = trajectory; q.slots_out = slots; q.behind = Behind::Conditional; q.ref = ref;
   return particle_run(c, q);
 }
 
@@ -2101,7 +2098,7 @@ int vgpa_particle_forecast(vgpa_ctx* c, const double* x, const double* x0, int32
   if ((rc = check_sums(c, h_keep, "forecast", "steps")) || (rc = check_stored(c, n_draw, h_keep, "forecast members", "members", "steps"))) return rc;
   ParticleRequest q{x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled};
   q.stride = stride; q.n_draw = n_draw; q.final_slots = final_slots; q.slots_out = slots;
-  q.forecast = true; q.horizon = horizon; q.cloud = cloud; q.cloud_logw = cloud_logw; q.index0 = index0;
+  q.horizon = horizon; q.cloud = cloud; q.cloud_logw = cloud_logw; q.index0 = index0;
   q.fc_moments = moments; q.members = members; q.state_end = state_end;
   if (!cloud) return particle_run(c, q);
   ParticleRun r{c, q};      // a given cloud: no filter runs

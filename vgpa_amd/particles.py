@@ -73,45 +73,86 @@ def descendant_weights(log_w, ancestors, resampled):
     flags = np.asarray(resampled).astype(bool).ravel()
     if flags.size != anc.shape[0]:
         raise ValueError(" descendant_weights: ancestors and resampled do not belong together.")
-    w = np.exp(log_w - np.max(log_w))
     out = np.empty((flags.size + 1, log_w.size))
-    out[-1] = w / np.sum(w)
+    out[-1] = _weights_of(log_w)
     for j in range(flags.size - 1, -1, -1):
         out[j] = np.bincount(anc[j], weights=out[j + 1], minlength=log_w.size) if flags[j] else out[j + 1]
     return out
 
 
-class ParticleFilterResult(object):
+def _weights_of(log_w):
+    """w / sum w with w = exp(log_w - max log_w)"""
+    w = np.exp(log_w - np.max(log_w))
+    return w / np.sum(w)
+
+
+class _WalkRecord(object):
+    """What every record of the filter's walk carries: the final log-weights log_w (n,), and ess and resampled over the problem's
+    observations.  A record takes them in its own order (_take_weights first, _take_decisions where its checks have it); the texts carry
+    the record's own name."""
+
+    def _take_weights(self, log_w):
+        self.log_w = np.asarray(log_w, dtype=float).ravel()
+        if self.log_w.size < 1:
+            raise ValueError(f" {type(self).__name__}: at least one particle.")
+
+    def _take_decisions(self, ess, resampled, what="ess and resampled", also=False):
+        """ess and resampled; ValueError where they differ in length, or where `also` says that something else named in `what` does not fit"""
+        self.ess = np.asarray(ess, dtype=float).ravel()
+        self.resampled = np.asarray(resampled).astype(bool).ravel()
+        if also or self.ess.size != self.resampled.size:
+            raise ValueError(f" {type(self).__name__}: {what} do not belong together.")
+
+    def __len__(self):
+        return self.log_w.size
+
+    def _normalised(self):
+        return _weights_of(self.log_w)
+
+    def log_evidence(self):
+        """logsumexp(log_w) - log n: the estimate of log p(y | theta, Sigma), unbiased in the evidence with or without resampling"""
+        top = np.max(self.log_w)
+        return float(top + np.log(np.sum(np.exp(self.log_w - top))) - np.log(self.log_w.size))
+
+
+class _Strided(object):
+    """A record that keeps every stride-th of n_pts grid indices: the two numbers and their check"""
+
+    def _take_grid(self, stride, n_pts):
+        self.stride, self.n_pts = int(stride), int(n_pts)
+        if self.stride < 1 or self.n_pts < 1:
+            raise ValueError(f" {type(self).__name__}: stride and n_pts must be at least 1.")
+        return (self.n_pts - 1) // self.stride + 1
+
+
+class _KeptGrid(_Strided):
+    """... with the kept grid indices 0, stride, 2 stride, ... < n_pts computed on demand and, with obs_t, the stretch between observations
+    each of them lies in"""
+
+    @property
+    def grid(self):
+        """the kept grid indices 0, stride, 2 stride, ..."""
+        return np.arange(0, self.n_pts, self.stride)
+
+    def _stretch_on_grid(self):
+        """index k belongs to stretch #{observations before k}"""
+        return np.searchsorted(self.obs_t, self.grid, side="left")
+
+
+class ParticleFilterResult(_WalkRecord):
     """log_w (n,): the final unnormalised log-weights; state (n, D): the final particles; over the problem's M_p observations: ess (M_p,),
     resampled (M_p,) bool, and -- history=True, else None -- ancestors (M_p, n): slot i behind observation j came from slot ancestors[j, i]
     of clouds[j] (the identity where the cloud was carried on), clouds (M_p, n, D): the particles at observation j before the resampling
     decision.  The 1-D models drop the last axis of state and clouds."""
 
     def __init__(self, log_w, state, ess, resampled, ancestors=None, clouds=None) -> None:
-        self.log_w = np.asarray(log_w, dtype=float).ravel()
-        if self.log_w.size < 1:
-            raise ValueError(" ParticleFilterResult: at least one particle.")
+        self._take_weights(log_w)
         self.state = np.asarray(state, dtype=float)
-        self.ess = np.asarray(ess, dtype=float).ravel()
-        self.resampled = np.asarray(resampled).astype(bool).ravel()
         self.ancestors = None if ancestors is None else np.asarray(ancestors, dtype=np.int64)
         self.clouds = None if clouds is None else np.asarray(clouds, dtype=float)
-        if self.state.shape[0] != self.log_w.size or self.ess.size != self.resampled.size:
-            raise ValueError(" ParticleFilterResult: log_w, state, ess and resampled do not belong together.")
+        self._take_decisions(ess, resampled, "log_w, state, ess and resampled", self.state.shape[0] != self.log_w.size)
         if self.ancestors is not None and self.ancestors.shape != (self.ess.size, self.log_w.size):
             raise ValueError(" ParticleFilterResult: ancestors must be (observations, particles).")
-
-    def __len__(self):
-        return self.log_w.size
-
-    def _normalised(self):
-        w = np.exp(self.log_w - np.max(self.log_w))
-        return w / np.sum(w)
-
-    def log_evidence(self):
-        """logsumexp(log_w) - log n: the estimate of log p(y | theta, Sigma), unbiased in the evidence with or without resampling"""
-        top = np.max(self.log_w)
-        return float(top + np.log(np.sum(np.exp(self.log_w - top))) - np.log(self.log_w.size))
 
     def final_ess(self):
         """(sum w)^2 / sum w^2 of the final weights, between 1 and n"""
@@ -144,15 +185,13 @@ class ParticleFilterResult(object):
         return descendant_weights(self.log_w, self.ancestors, self.resampled)
 
 
-class PathStatistics(object):
+class PathStatistics(_WalkRecord):
     """log_w (n,): the final unnormalised log-weights; mean (3, D): the self-normalised weighted mean of the rows (Q, G, H); rows
     (n, 3, D): the rows themselves, or None; ess, resampled over the problem's observations; dt, n_steps = Np - 1 and model ("OU", "DW",
     "L63", "L96") say how the rows were made.  sigma_diag below: the diagonal of Sigma, (D,) or a scalar."""
 
     def __init__(self, log_w, mean, dt, n_steps, model, ess=(), resampled=(), rows=None) -> None:
-        self.log_w = np.asarray(log_w, dtype=float).ravel()
-        if self.log_w.size < 1:
-            raise ValueError(" PathStatistics: at least one particle.")
+        self._take_weights(log_w)
         self.mean = np.asarray(mean, dtype=float)
         if self.mean.ndim != 2 or self.mean.shape[0] != 3:
             raise ValueError(" PathStatistics: mean must be (3, D).")
@@ -161,16 +200,10 @@ class PathStatistics(object):
         if model == "L63" and self.mean.shape[1] != 3:
             raise ValueError(" PathStatistics: Lorenz-63 has three components.")
         self.dt, self.n_steps, self.model = float(dt), int(n_steps), model
-        self.ess = np.asarray(ess, dtype=float).ravel()
-        self.resampled = np.asarray(resampled).astype(bool).ravel()
         self.rows = None if rows is None else np.asarray(rows, dtype=float)
         if self.rows is not None and self.rows.shape != (self.log_w.size,) + self.mean.shape:
             raise ValueError(" PathStatistics: rows must be (particles, 3, D).")
-        if self.ess.size != self.resampled.size:
-            raise ValueError(" PathStatistics: ess and resampled do not belong together.")
-
-    def __len__(self):
-        return self.log_w.size
+        self._take_decisions(ess, resampled)
 
     @property
     def dim_d(self):
@@ -179,11 +212,6 @@ class PathStatistics(object):
     @property
     def n_theta(self):
         return 3 if self.model == "L63" else 1
-
-    def log_evidence(self):
-        """logsumexp(log_w) - log n, as ParticleFilterResult.log_evidence()"""
-        top = np.max(self.log_w)
-        return float(top + np.log(np.sum(np.exp(self.log_w - top))) - np.log(self.log_w.size))
 
     def expected(self):
         """(E[Q], E[G], E[H]), each (D,)"""
@@ -215,24 +243,20 @@ class PathStatistics(object):
         return float(-0.5 * np.sum((q - 2.0 * delta * g + delta * delta * h) / sg + self.n_steps * np.log(2.0 * np.pi * sg * self.dt)))
 
 
-class PathEvents(object):
+class PathEvents(_WalkRecord, _Strided):
     """log_w (n,): the final unnormalised log-weights; mean (3, D): the self-normalised weighted mean of the rows (X, T, N); cdf (n_keep, D):
     the weighted share of lineages whose component j has been beyond its level at or before the grid indices 0, stride, ...; levels (D,),
     side (D,) of +1 / -1: the event of component j is side_j (x_j - levels_j) > 0; n_pts = Np and dt: the grid; rows (n, 3, D): the rows
     themselves, or None; ess, resampled over the problem's observations.  T = n_pts in a row says: never in the window."""
 
     def __init__(self, log_w, mean, cdf, levels, side, stride, n_pts, dt, ess=(), resampled=(), rows=None) -> None:
-        self.log_w = np.asarray(log_w, dtype=float).ravel()
-        if self.log_w.size < 1:
-            raise ValueError(" PathEvents: at least one particle.")
+        self._take_weights(log_w)
         self.mean = np.asarray(mean, dtype=float)
         if self.mean.ndim != 2 or self.mean.shape[0] != 3:
             raise ValueError(" PathEvents: mean must be (3, D).")
         d = self.mean.shape[1]
-        self.stride, self.n_pts, self.dt = int(stride), int(n_pts), float(dt)
-        if self.stride < 1 or self.n_pts < 1:
-            raise ValueError(" PathEvents: stride and n_pts must be at least 1.")
-        self.grid = np.arange((self.n_pts - 1) // self.stride + 1) * self.stride
+        self.dt = float(dt)
+        self.grid = np.arange(self._take_grid(stride, n_pts)) * self.stride
         self.cdf = np.asarray(cdf, dtype=float)
         if self.cdf.shape != (self.grid.size, d):
             raise ValueError(" PathEvents: cdf must be (n_keep, D).")
@@ -240,16 +264,10 @@ class PathEvents(object):
         self.side = np.broadcast_to(np.asarray(side).ravel(), (d,)).astype(int)
         if not np.all(np.abs(self.side) == 1):
             raise ValueError(" PathEvents: side must be +1 or -1.")
-        self.ess = np.asarray(ess, dtype=float).ravel()
-        self.resampled = np.asarray(resampled).astype(bool).ravel()
         self.rows = None if rows is None else np.asarray(rows, dtype=float)
         if self.rows is not None and self.rows.shape != (self.log_w.size,) + self.mean.shape:
             raise ValueError(" PathEvents: rows must be (particles, 3, D).")
-        if self.ess.size != self.resampled.size:
-            raise ValueError(" PathEvents: ess and resampled do not belong together.")
-
-    def __len__(self):
-        return self.log_w.size
+        self._take_decisions(ess, resampled)
 
     @property
     def dim_d(self):
@@ -257,13 +275,7 @@ class PathEvents(object):
 
     def weights(self):
         """(n,): w / sum w with w = exp(log_w - max log_w)"""
-        w = np.exp(self.log_w - np.max(self.log_w))
-        return w / np.sum(w)
-
-    def log_evidence(self):
-        """logsumexp(log_w) - log n, as ParticleFilterResult.log_evidence()"""
-        top = np.max(self.log_w)
-        return float(top + np.log(np.sum(np.exp(self.log_w - top))) - np.log(self.log_w.size))
+        return self._normalised()
 
     @property
     def prob_crossed(self):
@@ -312,39 +324,35 @@ class PathEvents(object):
         return self.levels + self.side * out
 
 
-class SmoothingMoments(object):
+class _GenealogySums(_WalkRecord, _KeptGrid):
+    """The sums on the kept grid under the filter's genealogy: with them obs_t and lineage_ess (M_p + 1,), one entry per stretch"""
+
+    def _take_stretches(self, obs_t, lineage_ess, ess, resampled):
+        self.obs_t = np.asarray(obs_t, dtype=np.int64).ravel()
+        self.lineage_ess = np.asarray(lineage_ess, dtype=float).ravel()
+        self._take_decisions(ess, resampled, "obs_t, lineage_ess, ess and resampled", self.lineage_ess.size != self.obs_t.size + 1)
+
+    def lineage_ess_on_grid(self):
+        """lineage_ess of the stretch each kept grid index lies in: index k belongs to stretch #{observations before k}"""
+        return self.lineage_ess[self._stretch_on_grid()]
+
+
+class SmoothingMoments(_GenealogySums):
     """log_w (n,): the final unnormalised log-weights; moments (n_keep, 2, D): sum_i W_i x_i(k) and sum_i W_i x_i(k)^2 at the grid indices
     k = 0, stride, 2 stride, ... < n_pts; obs_t: the problem's own observation indices; lineage_ess (M_p + 1,): 1 / sum W^2 of every stretch;
     ess, resampled over the problem's observations.  single_dim: a 1-D model, the last axis of mean / second / var / std is dropped."""
 
     def __init__(self, log_w, moments, stride, n_pts, obs_t, lineage_ess, ess=(), resampled=(), single_dim=False) -> None:
-        self.log_w = np.asarray(log_w, dtype=float).ravel()
-        if self.log_w.size < 1:
-            raise ValueError(" SmoothingMoments: at least one particle.")
-        self.stride, self.n_pts = int(stride), int(n_pts)
-        if self.stride < 1 or self.n_pts < 1:
-            raise ValueError(" SmoothingMoments: stride and n_pts must be at least 1.")
+        self._take_weights(log_w)
+        n_keep = self._take_grid(stride, n_pts)
         self.moments = np.asarray(moments, dtype=float)
-        if self.moments.ndim != 3 or self.moments.shape[:2] != ((self.n_pts - 1) // self.stride + 1, 2):
+        if self.moments.ndim != 3 or self.moments.shape[:2] != (n_keep, 2):
             raise ValueError(" SmoothingMoments: moments must be (n_keep, 2, D).")
-        self.obs_t = np.asarray(obs_t, dtype=np.int64).ravel()
-        self.lineage_ess = np.asarray(lineage_ess, dtype=float).ravel()
-        self.ess = np.asarray(ess, dtype=float).ravel()
-        self.resampled = np.asarray(resampled).astype(bool).ravel()
-        if self.lineage_ess.size != self.obs_t.size + 1 or self.ess.size != self.resampled.size:
-            raise ValueError(" SmoothingMoments: obs_t, lineage_ess, ess and resampled do not belong together.")
+        self._take_stretches(obs_t, lineage_ess, ess, resampled)
         self.single_dim = bool(single_dim)
-
-    def __len__(self):
-        return self.log_w.size
 
     def _shape(self, a):
         return a[..., 0] if self.single_dim else a
-
-    @property
-    def grid(self):
-        """the kept grid indices 0, stride, 2 stride, ..."""
-        return np.arange(0, self.n_pts, self.stride)
 
     @property
     def mean(self):
@@ -365,54 +373,27 @@ class SmoothingMoments(object):
     def std(self):
         return np.sqrt(np.maximum(self.var, 0.0))
 
-    def lineage_ess_on_grid(self):
-        """lineage_ess of the stretch each kept grid index lies in: index k belongs to stretch #{observations before k}"""
-        return self.lineage_ess[np.searchsorted(self.obs_t, self.grid, side="left")]
 
-    def log_evidence(self):
-        """logsumexp(log_w) - log n, as ParticleFilterResult.log_evidence()"""
-        top = np.max(self.log_w)
-        return float(top + np.log(np.sum(np.exp(self.log_w - top))) - np.log(self.log_w.size))
-
-
-class SmoothingCovariance(object):
+class SmoothingCovariance(_GenealogySums):
     """log_w (n,): the final unnormalised log-weights; mean (n_keep, D): sum_i W_i x_i(k) and second (n_keep, D, D): sum_i W_i x_i(k) x_i(k)^T
     at the grid indices k = 0, stride, 2 stride, ... < n_pts; obs_t: the problem's own observation indices; lineage_ess (M_p + 1,): 1 / sum W^2
     of every stretch; ess, resampled over the problem's observations.  single_dim: a 1-D model, the component axes of mean / second / cov /
     var / corr are dropped."""
 
     def __init__(self, log_w, mean, second, stride, n_pts, obs_t, lineage_ess, ess=(), resampled=(), single_dim=False) -> None:
-        self.log_w = np.asarray(log_w, dtype=float).ravel()
-        if self.log_w.size < 1:
-            raise ValueError(" SmoothingCovariance: at least one particle.")
-        self.stride, self.n_pts = int(stride), int(n_pts)
-        if self.stride < 1 or self.n_pts < 1:
-            raise ValueError(" SmoothingCovariance: stride and n_pts must be at least 1.")
+        self._take_weights(log_w)
+        n_keep = self._take_grid(stride, n_pts)
         self._mean, self._second = np.asarray(mean, dtype=float), np.asarray(second, dtype=float)
-        n_keep = (self.n_pts - 1) // self.stride + 1
         if self._mean.ndim != 2 or self._mean.shape[0] != n_keep or self._second.shape != (n_keep, self._mean.shape[1], self._mean.shape[1]):
             raise ValueError(" SmoothingCovariance: mean must be (n_keep, D) and second (n_keep, D, D).")
-        self.obs_t = np.asarray(obs_t, dtype=np.int64).ravel()
-        self.lineage_ess = np.asarray(lineage_ess, dtype=float).ravel()
-        self.ess = np.asarray(ess, dtype=float).ravel()
-        self.resampled = np.asarray(resampled).astype(bool).ravel()
-        if self.lineage_ess.size != self.obs_t.size + 1 or self.ess.size != self.resampled.size:
-            raise ValueError(" SmoothingCovariance: obs_t, lineage_ess, ess and resampled do not belong together.")
+        self._take_stretches(obs_t, lineage_ess, ess, resampled)
         self.single_dim = bool(single_dim)
-
-    def __len__(self):
-        return self.log_w.size
 
     def _vec(self, a):
         return a[..., 0] if self.single_dim else a
 
     def _mat(self, a):
         return a[..., 0, 0] if self.single_dim else a
-
-    @property
-    def grid(self):
-        """the kept grid indices 0, stride, 2 stride, ..."""
-        return np.arange(0, self.n_pts, self.stride)
 
     @property
     def mean(self):
@@ -456,17 +437,8 @@ class SmoothingCovariance(object):
         i = k // self.stride
         return self._vec(self._mean[i].copy()), self._mat(self._cov()[i])
 
-    def lineage_ess_on_grid(self):
-        """lineage_ess of the stretch each kept grid index lies in: index k belongs to stretch #{observations before k}"""
-        return self.lineage_ess[np.searchsorted(self.obs_t, self.grid, side="left")]
 
-    def log_evidence(self):
-        """logsumexp(log_w) - log n, as ParticleFilterResult.log_evidence()"""
-        top = np.max(self.log_w)
-        return float(top + np.log(np.sum(np.exp(self.log_w - top))) - np.log(self.log_w.size))
-
-
-class SmoothingPaths(object):
+class SmoothingPaths(_WalkRecord, _KeptGrid):
     """log_w (n,): the filter's final unnormalised log-weights; paths (K, n_keep, D): the trajectories at the grid indices k = 0, stride,
     2 stride, ... < n_pts; slots (M_p + 1, K): the slot trajectory m sat in during stretch j (row M_p: its final slot); obs_t: the problem's
     own observation indices; ess, resampled over them.  drawn: the final slots were drawn from the final weights, the trajectories are
@@ -485,14 +457,10 @@ class SmoothingPaths(object):
     distinct() is bounded by the distinct slots chosen, never by more than n."""
 
     def __init__(self, log_w, paths, slots, stride, n_pts, obs_t, ess=(), resampled=(), drawn=True, single_dim=False, method="genealogy") -> None:
-        self.log_w = np.asarray(log_w, dtype=float).ravel()
-        if self.log_w.size < 1:
-            raise ValueError(" SmoothingPaths: at least one particle.")
-        self.stride, self.n_pts = int(stride), int(n_pts)
-        if self.stride < 1 or self.n_pts < 1:
-            raise ValueError(" SmoothingPaths: stride and n_pts must be at least 1.")
+        self._take_weights(log_w)
+        n_keep = self._take_grid(stride, n_pts)
         full = np.asarray(paths, dtype=float)
-        if full.ndim != 3 or full.shape[0] < 1 or full.shape[1] != (self.n_pts - 1) // self.stride + 1:
+        if full.ndim != 3 or full.shape[0] < 1 or full.shape[1] != n_keep:
             raise ValueError(" SmoothingPaths: paths must be (K, n_keep, D).")
         self.single_dim = bool(single_dim)
         self.paths = full[..., 0] if self.single_dim else full
@@ -502,22 +470,14 @@ class SmoothingPaths(object):
             raise ValueError(" SmoothingPaths: slots must be (M + 1, K).")
         if self.slots.min() < 0 or self.slots.max() >= self.log_w.size:
             raise ValueError(" SmoothingPaths: a slot outside [0, n).")
-        self.ess = np.asarray(ess, dtype=float).ravel()
-        self.resampled = np.asarray(resampled).astype(bool).ravel()
-        if self.ess.size != self.resampled.size:
-            raise ValueError(" SmoothingPaths: ess and resampled do not belong together.")
+        self._take_decisions(ess, resampled)
         self.drawn = bool(drawn)
         if method not in ("genealogy", "backward"):
             raise ValueError(" SmoothingPaths: method is 'genealogy' or 'backward'.")
         self.method = method
 
-    def __len__(self):
+    def __len__(self):      # (K, not n)
         return self.paths.shape[0]
-
-    @property
-    def grid(self):
-        """the kept grid indices 0, stride, 2 stride, ..."""
-        return np.arange(0, self.n_pts, self.stride)
 
     def _weights(self, weights):
         if weights is None:
@@ -552,12 +512,7 @@ class SmoothingPaths(object):
 
     def distinct_on_grid(self):
         """distinct() of the stretch each kept grid index lies in: index k belongs to stretch #{observations before k}"""
-        return self.distinct()[np.searchsorted(self.obs_t, self.grid, side="left")]
-
-    def log_evidence(self):
-        """logsumexp(log_w) - log n, as ParticleFilterResult.log_evidence()"""
-        top = np.max(self.log_w)
-        return float(top + np.log(np.sum(np.exp(self.log_w - top))) - np.log(self.log_w.size))
+        return self.distinct()[self._stretch_on_grid()]
 
 
 class Forecast(object):

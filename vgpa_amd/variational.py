@@ -12,7 +12,7 @@ Like the reference the object is stateful: `gradient(x)` without `eval_fun` uses
 import numpy as np
 from scipy.interpolate import CubicSpline
 
-from ._lib import Context
+from ._lib import Context, per_problem
 
 
 class VarGP(object):
@@ -207,6 +207,16 @@ class VarGP(object):
         d = self.dim_d
         return np.reshape(np.asarray(self.kl0.mu0, dtype=float), (1, d)), np.reshape(np.asarray(self.kl0.tau0, dtype=float), (1, d, d))
 
+    def _particle_call(self, name, record, *args, x=None, late=None, **kwargs):
+        """What the particle methods share: x as a float array, the prior of kl0, Context.<name>(*args, x=, prior=, **kwargs), and
+        record(res, k, *late()) for every problem k of its dict -- one record with batch = 1, else their list.  late: what the records
+        need beside the dict and can be made only behind the call, which has checked the arguments"""
+        xx = None if x is None else np.asarray(x, dtype=float)
+        res = getattr(self._context(), name)(*args, x=xx, prior=self._prior(), **kwargs)
+        extra = late() if late else ()
+        out = [record(res, k, *extra) for k in range(res["log_w"].shape[0])]
+        return out[0] if self.batch == 1 else out
+
     def particle_filter(self, n_paths, seed, ess_fraction=0.5, x=None, x0=None, history=False):
         """A guided particle filter with the posterior process as its proposal: n_paths particles walk the recursion of sample_paths,
         take in their weight against the model SDE and the data observation by observation, and are resampled (systematic) whenever
@@ -214,10 +224,7 @@ class VarGP(object):
         prior of kl0 (0 when x0 is given).  ess_fraction=0 never resamples: the weights of importance_weights().  history=True keeps the
         ancestors and the clouds at the observations (lineages()).  x=None: the (A_t, b_t) of the last free_energy.  From the first
         resampling on a particle depends on n_paths."""
-        xx = None if x is None else np.asarray(x, dtype=float)
-        res = self._context().particle_filter(n_paths, seed, ess_fraction=ess_fraction, x=xx, x0=x0, prior=self._prior(), history=history)
-        out = [self._particle_record(res, k) for k in range(res["log_w"].shape[0])]
-        return out[0] if self.batch == 1 else out
+        return self._particle_call("particle_filter", self._particle_record, n_paths, seed, ess_fraction=ess_fraction, x=x, x0=x0, history=history)
 
     def _statistics_record(self, res, k, n_obs=None):
         """One problem's PathStatistics from row k of Context.particle_statistics' dict, cut to its own n_obs observations"""
@@ -232,11 +239,8 @@ class VarGP(object):
         particles.PathStatistics (with batch > 1 a list, one per problem) with the weighted mean of the rows, reduced on the device, and
         -- per_particle=True -- the rows.  Its score(), theta_step() and expected_loglik() are the score of log p(y | theta, Sigma), the
         exact EM step in theta and the EM Q-function under the particles' smoothing distribution."""
-        xx = None if x is None else np.asarray(x, dtype=float)
-        res = self._context().particle_statistics(n_paths, seed, ess_fraction=ess_fraction, x=xx, x0=x0, prior=self._prior(),
-                                                  per_particle=per_particle)
-        out = [self._statistics_record(res, k) for k in range(res["log_w"].shape[0])]
-        return out[0] if self.batch == 1 else out
+        return self._particle_call("particle_statistics", self._statistics_record, n_paths, seed, ess_fraction=ess_fraction, x=x, x0=x0,
+                                   per_particle=per_particle)
 
     def _events_record(self, res, k, levels, side, stride, n_obs=None):
         """One problem's PathEvents from row k of Context.particle_events' dict, cut to its own n_obs observations"""
@@ -251,14 +255,9 @@ class VarGP(object):
         batch > 1 a list, one per problem).  levels (D,) or a scalar, side +1 (above) or -1 (below) per component: the event of component j
         is side_j (x_j - levels_j) > 0.  prob_crossed, first_passage_cdf(), occupation_time and mean_extreme come from sums reduced on the
         device over all n_paths lineages (no path is stored or copied); per_particle=True also keeps the rows."""
-        xx = None if x is None else np.asarray(x, dtype=float)
-        res = self._context().particle_events(n_paths, seed, levels, side=side, stride=stride, ess_fraction=ess_fraction, x=xx, x0=x0,
-                                              prior=self._prior(), per_particle=per_particle)
-        d = self.dim_d
-        lev = np.broadcast_to(np.asarray(levels, dtype=float).reshape(-1, d) if np.size(levels) > 1 else np.reshape(levels, (1, 1)), (self.batch, d))
-        sd = np.broadcast_to(np.asarray(side).reshape(-1, d) if np.size(side) > 1 else np.reshape(side, (1, 1)), (self.batch, d))
-        out = [self._events_record(res, k, lev[k], sd[k], stride) for k in range(res["log_w"].shape[0])]
-        return out[0] if self.batch == 1 else out
+        return self._particle_call("particle_events", lambda res, k, lev, sd: self._events_record(res, k, lev[k], sd[k], stride), n_paths, seed, levels,
+                                   side=side, stride=stride, ess_fraction=ess_fraction, x=x, x0=x0, per_particle=per_particle,
+                                   late=lambda: (per_problem(levels, self.batch, self.dim_d), per_problem(side, self.batch, self.dim_d)))
 
     def _moments_record(self, res, k, stride, obs_t=None):
         """One problem's SmoothingMoments from row k of Context.particle_moments' dict, cut to its own observations obs_t"""
@@ -272,10 +271,8 @@ class VarGP(object):
         (with batch > 1 a list, one per problem) -- mean, second, var, std at the grid indices 0, stride, ... under the filter's
         genealogy, reduced on the device (no path is stored or copied), and lineage_ess, the number of distinct lineages each stretch
         between two observations rests on in effect.  What to hold m_t and S_t against."""
-        xx = None if x is None else np.asarray(x, dtype=float)
-        res = self._context().particle_moments(n_paths, seed, stride=stride, ess_fraction=ess_fraction, x=xx, x0=x0, prior=self._prior())
-        out = [self._moments_record(res, k, stride) for k in range(res["log_w"].shape[0])]
-        return out[0] if self.batch == 1 else out
+        return self._particle_call("particle_moments", lambda res, k: self._moments_record(res, k, stride), n_paths, seed, stride=stride,
+                                   ess_fraction=ess_fraction, x=x, x0=x0)
 
     def _covariance_record(self, res, k, stride, obs_t=None):
         """One problem's SmoothingCovariance from row k of Context.particle_covariance's dict, cut to its own observations obs_t"""
@@ -289,10 +286,8 @@ class VarGP(object):
         particles.SmoothingCovariance (with batch > 1 a list, one per problem) -- mean, second, cov, var, corr at the grid indices 0, stride,
         ... under the filter's genealogy, reduced on the device, and lineage_ess as particle_moments has it.  What to hold the whole of
         S_t against, its off-diagonal entries included; gaussian(dim_n - 1) is the filtering Gaussian a following window starts from."""
-        xx = None if x is None else np.asarray(x, dtype=float)
-        res = self._context().particle_covariance(n_paths, seed, stride=stride, ess_fraction=ess_fraction, x=xx, x0=x0, prior=self._prior())
-        out = [self._covariance_record(res, k, stride) for k in range(res["log_w"].shape[0])]
-        return out[0] if self.batch == 1 else out
+        return self._particle_call("particle_covariance", lambda res, k: self._covariance_record(res, k, stride), n_paths, seed, stride=stride,
+                                   ess_fraction=ess_fraction, x=x, x0=x0)
 
     def _paths_record(self, res, k, stride, drawn, obs_t=None, method="genealogy"):
         """One problem's SmoothingPaths from row k of Context.particle_paths' (or particle_backward_paths') dict, cut to its own observations obs_t"""
@@ -307,11 +302,8 @@ class VarGP(object):
         from the filter's genealogy (slots=None) or the lineages of the given final slots, and the slot of every trajectory in every
         stretch.  Only the n_draw trajectories are walked again and copied.  On collapsing clouds the early stretches of all
         trajectories coincide: distinct() says how many are left."""
-        xx = None if x is None else np.asarray(x, dtype=float)
-        res = self._context().particle_paths(n_paths, seed, n_draw, stride=stride, ess_fraction=ess_fraction, x=xx, x0=x0, prior=self._prior(),
-                                             slots=slots)
-        out = [self._paths_record(res, k, stride, slots is None) for k in range(res["log_w"].shape[0])]
-        return out[0] if self.batch == 1 else out
+        return self._particle_call("particle_paths", lambda res, k: self._paths_record(res, k, stride, slots is None), n_paths, seed, n_draw,
+                                   stride=stride, ess_fraction=ess_fraction, x=x, x0=x0, slots=slots)
 
     def backward_paths(self, n_paths, seed, n_draw, stride=1, ess_fraction=0.5, x=None, x0=None, slots=None):
         """n_draw whole smoothing trajectories by backward simulation (forward filtering, backward simulation) through the clouds of
@@ -320,11 +312,8 @@ class VarGP(object):
         particles, in proportion to filter weight times model transition density, instead of following its ancestor: the early stretches
         keep more distinct paths than the genealogy leaves.  Between two observations a trajectory is still its slot's own path, so
         distinct() is bounded by the distinct slots chosen."""
-        xx = None if x is None else np.asarray(x, dtype=float)
-        res = self._context().particle_backward_paths(n_paths, seed, n_draw, stride=stride, ess_fraction=ess_fraction, x=xx, x0=x0,
-                                                      prior=self._prior(), slots=slots)
-        out = [self._paths_record(res, k, stride, slots is None, method="backward") for k in range(res["log_w"].shape[0])]
-        return out[0] if self.batch == 1 else out
+        return self._particle_call("particle_backward_paths", lambda res, k: self._paths_record(res, k, stride, slots is None, method="backward"),
+                                   n_paths, seed, n_draw, stride=stride, ess_fraction=ess_fraction, x=x, x0=x0, slots=slots)
 
     def _forecast_record(self, res, k, horizon, stride, drawn):
         """One problem's Forecast from row k of Context.particle_forecast's dict"""
@@ -332,16 +321,22 @@ class VarGP(object):
         return Forecast(res["log_w"][k], res["moments"][k], res["members"][k], res["slots"][k], res["state_end"][k], res["index0"], horizon, stride,
                         float(self.fwd_ode.dt), float(np.ravel(self.model.time_window)[0]), drawn, self.model.single_dim)
 
-    def _forecast_source(self, source, n_paths, seed, xx, x0, cloud, log_w, index0):
-        """The cloud of forecast(): (cloud, log_w, index0) as Context.particle_forecast takes them; cloud None: the filter's"""
+    def _forecast(self, context, prior, horizon, n_paths, seed, stride, n_draw, ess_fraction, xx, x0, source, cloud, log_w, index0, slots):
+        """Context.particle_forecast's dict for forecast(), here and in a batch of members like this one (context, prior: how to get them):
+        the source of the cloud chosen, a given cloud of a 1-D model given its component axis"""
         if source not in ("filter", "posterior"):
             raise ValueError(f" Unknown source of the forecast -> {source}")
         if source == "posterior":      # the end points of the posterior process's paths, equally weighted, at the last grid index
             if cloud is not None or n_paths is None:
                 raise ValueError(" forecast: source='posterior' draws its own cloud of n_paths particles.")
-            ends = self._context().sample_paths("posterior", n_paths, seed, stride=self.dim_n - 1 if self.dim_n > 1 else 1, x=xx, x0=x0)
-            return ends[:, :, -1, :], None, self.dim_n - 1
-        return cloud, log_w, index0
+            ends = context().sample_paths("posterior", n_paths, seed, stride=self.dim_n - 1 if self.dim_n > 1 else 1, x=xx, x0=x0)
+            cloud, log_w, index0 = ends[:, :, -1, :], None, self.dim_n - 1
+        if cloud is None:
+            return context().particle_forecast(horizon, n_paths, seed, stride=stride, n_draw=n_draw, ess_fraction=ess_fraction, x=xx, x0=x0,
+                                               slots=slots, prior=prior())
+        cloud = np.asarray(cloud, dtype=float)
+        cloud = cloud.reshape(cloud.shape + (1,)) if self.model.single_dim and cloud.shape[-1:] != (1,) else cloud
+        return context().particle_forecast(horizon, seed=seed, stride=stride, n_draw=n_draw, cloud=cloud, log_w=log_w, index0=index0, slots=slots)
 
     def forecast(self, horizon, n_paths=None, seed=0, stride=1, n_draw=0, ess_fraction=0.5, x=None, x0=None, source="filter", cloud=None,
                  log_w=None, index0=None, slots=None):
@@ -352,15 +347,8 @@ class VarGP(object):
         sample_paths(n_paths, seed, x=x, x0=x0), equally weighted.  cloud (n, D), log_w (n,), index0: a given cloud at that absolute grid
         index (None: the last one of the window) -- the state and log_w of an earlier forecast continue it."""
         xx = None if x is None else np.asarray(x, dtype=float)
-        cloud, log_w, index0 = self._forecast_source(source, n_paths, seed, xx, x0, cloud, log_w, index0)
-        if cloud is not None:
-            cloud = np.asarray(cloud, dtype=float)
-            cloud = cloud.reshape(cloud.shape + (1,)) if self.model.single_dim and cloud.shape[-1:] != (1,) else cloud
-            res = self._context().particle_forecast(horizon, seed=seed, stride=stride, n_draw=n_draw, cloud=cloud, log_w=log_w, index0=index0,
-                                                    slots=slots)
-        else:
-            res = self._context().particle_forecast(horizon, n_paths, seed, stride=stride, n_draw=n_draw, ess_fraction=ess_fraction, x=xx, x0=x0,
-                                                    slots=slots, prior=self._prior())
+        res = self._forecast(self._context, self._prior, horizon, n_paths, seed, stride, n_draw, ess_fraction, xx, x0, source, cloud, log_w, index0,
+                             slots)
         out = [self._forecast_record(res, k, horizon, stride, slots is None) for k in range(res["moments"].shape[0])]
         return out[0] if self.batch == 1 else out
 
