@@ -404,6 +404,39 @@ int vgpa_particle_covariance(vgpa_ctx* ctx, const double* x_or_null, const doubl
                              double ess_fraction, const double* prior_mu_or_null, const double* prior_tau_or_null, double* logw, double* state,
                              double* mean, double* second, double* lineage_ess_or_null, double* ess_or_null, int32_t* resampled_or_null);
 
+/* The smoothing marginals on the time grid under the genealogy of the particle filter: the law of x_k[d] | y itself, as a
+ * histogram over a ladder of levels per component -- whether it is bimodal, where its quantiles lie, P(x_k[d] > c | y) along the window -- with
+ * only the histograms leaving the device.  The steps on the device are those of vgpa_particle_moments; the second walk counts where that one
+ * sums.  Stretches, x_i(k), j(k), W^c_i, the ancestors and the kept grid indices are those of vgpa_particle_moments.
+ *   levels      host, [batch][D][L], L = n_levels in [1, 63]: the ladder c[p][d][0] < ... < c[p][d][L-1] of component d of problem p, finite,
+ *               strictly increasing, the same for every grid index
+ *   bin(x)      = #{ l : c_l < x }, fp64 compares alone: x <= c_0 gives bin 0, c_{b-1} < x <= c_b bin b, x > c_{L-1} bin L; a NaN falls into
+ *               bin 0.  The index lies in [0, L] by construction and is never computed by arithmetic on x
+ *   q_i         = (uint64) trunc(W^c_i 2^62) of the final slots, W^c_i with the very bits vgpa_particle_moments normalises to;  Q^c = q
+ *   Q^j_a       for j = c-1 .. 0: where the cloud was resampled at observation j with ancestors anc, the sum of Q^{j+1}_i over the slots i with
+ *               anc_i = a, in 64-bit integer arithmetic; else Q^{j+1}_a.  sum_i q_i <= 2^62 (1 + n 2^-53) < 2^64: nothing overflows, and the
+ *               truncation loses less than 2^-62 per particle
+ *   mass             host uint64, [batch][n_keep][D][L+1], n_keep = (Np-1) / stride + 1: for the kept grid indices k = k' stride in stretch
+ *                    j(k), mass[k'][d][b] = sum_i Q^{j(k)}_i 1[bin(x_i(k)[d]) = b].  Integer addition is associative: the result does not
+ *                    depend on the launch geometry, the batch or the order of any addition, and equals exactly the histogram of the n final
+ *                    lineages' states at k weighted by q_i.  sum_b mass is the same for every d and every kept k of a stretch; the CDF on
+ *                    the ladder, cdf[l] = sum_{b <= l} mass[b] / sum_b mass[b], is non-decreasing and lies in [0, 1] by construction
+ *   qfinal_or_null   host uint64, [batch][n_paths]: q_i
+ *   lineage_ess_or_null  as in vgpa_particle_moments, and bit-identical to its result with the same arguments
+ *   logw, ess_or_null, resampled_or_null and every other argument: as in vgpa_particle_filter, and bit-identical to its results with the
+ *   same arguments.  state is copied behind the second walk and is bit-identical as well.  With x NULL the cached state is read and not
+ *   written
+ * The estimator is that of vgpa_particle_moments: the final weights on the surviving lineages.  It is exact for the Euler-discretised model
+ * as n_paths grows, and in early stretches it rests on the few lineages the genealogy has left there, which lineage_ess reports.
+ * Errors: as vgpa_particle_moments, and VGPA_ERR_ARG for a NULL levels or mass, n_levels outside [1, 63], a level that is not finite, a ladder
+ * that is not strictly increasing (the message names the problem and the component), or stride < 1; VGPA_ERR_UNSUPPORTED, before any work,
+ * for more than 65535 workgroups per problem or more than 2^39 - 256 entries of mass; D > 64 and a dense Sigma are refused as in
+ * vgpa_particle_filter. */
+int vgpa_particle_marginals(vgpa_ctx* ctx, const double* x_or_null, const double* x0_or_null, int32_t n_paths, int32_t stride, uint64_t seed,
+                            double ess_fraction, const double* prior_mu_or_null, const double* prior_tau_or_null, const double* levels,
+                            int32_t n_levels, double* logw, double* state, uint64_t* mass, uint64_t* qfinal_or_null,
+                            double* lineage_ess_or_null, double* ess_or_null, int32_t* resampled_or_null);
+
 /* Whole smoothing trajectories on the time grid, drawn from the genealogy of the particle filter: K = n_draw complete
  * paths of the Euler-discretised model as the filter's surviving lineages hold them, for path functionals that are no mean or variance.
  * Three steps on the device behind the filter of vgpa_particle_filter, which runs unchanged with its ancestors kept: the final slots; their

@@ -1,7 +1,7 @@
 """
 Time of Context.sample_paths (vgpa_sample_paths), Context.sample_paths_weighted (vgpa_sample_paths_weighted), Context.particle_filter
 (vgpa_particle_filter), Context.particle_statistics (vgpa_particle_statistics), Context.particle_events (vgpa_particle_events), Context.particle_moments (vgpa_particle_moments),
-Context.particle_covariance (vgpa_particle_covariance), Context.particle_paths (vgpa_particle_paths), Context.particle_backward_paths
+Context.particle_covariance (vgpa_particle_covariance), Context.particle_marginals (vgpa_particle_marginals), Context.particle_paths (vgpa_particle_paths), Context.particle_backward_paths
 (vgpa_particle_backward_paths) and Context.particle_forecast (vgpa_particle_forecast) on their jobs, one JSON line.
 
     python tools/bench_sample_paths.py [--rounds 3] [--calls 5] [--jobs a,b,c,aw,aw0,bw,bw0,af64_0,af64_5,af1024_0,af1024_5,bf64_0,...]
@@ -9,6 +9,7 @@ Context.particle_covariance (vgpa_particle_covariance), Context.particle_paths (
     python tools/bench_sample_paths.py --events [--filter-problems 4096]          # the ae* and be* jobs
     python tools/bench_sample_paths.py --moments [--filter-problems 4096]         # the am* and bm* jobs
     python tools/bench_sample_paths.py --covariance [--filter-problems 4096]      # the ac* and bc* jobs
+    python tools/bench_sample_paths.py --marginals [--filter-problems 4096] [--levels 31]      # the ah* and bh* jobs
     python tools/bench_sample_paths.py --paths [--filter-problems 4096] [--paths-strides 1,10]      # the ap* and bp* jobs, once per stride
     python tools/bench_sample_paths.py --backward [--filter-problems 4096] [--paths-strides 10] [--parent-json FILE]      # the ab* and bb* jobs
     python tools/bench_sample_paths.py --gibbs [--filter-problems 4096]           # the ag* and bg* jobs
@@ -43,6 +44,12 @@ Context.particle_covariance (vgpa_particle_covariance), Context.particle_paths (
              sums of stride 1 take 3.5 GB at n = 64 and 56 GB at n = 1024, the matrices 6.6 GB to copy) --, and particle_moments and
              particle_filter with the same arguments, the three calls alternating inside every round: the three times, the ratios to
              particle_moments and to particle_filter, the partial-sum buffer on the device and the result copied
+
+  ah<n>_<s>, bh<n>_<s>   (--marginals selects all eight) particle_marginals on the contexts of a and b: n = 64 or 1024 particles per problem,
+             ess_fraction 0.5, every s-th grid index kept (s = 1 or 10), per problem and component the --levels levels of
+             particles.gaussian_ladder over the cached posterior's m_t -+ 4 sqrt(S_t), and particle_moments with the same arguments -- the
+             same filter, backward pass and replay, another reduction --, the two calls alternating inside every round: both times, their
+             ratio and what each copies to the host
 
   ap<n>_<K>, bp<n>_<K>   (--paths selects all eight, each once per stride of --paths-strides) particle_paths on the contexts of a and b:
              n = 64 or 1024 particles per problem, ess_fraction 0.5, K = 16 or 64 trajectories per problem drawn from the final weights,
@@ -105,6 +112,7 @@ STATS = {f"{t}s{n}_{f}": (t, n, 0.1 * f) for t in "ab" for n in (64, 1024) for f
 EVENTS = {f"{t}e{n}": (t, n, 0.5) for t in "ab" for n in (64, 1024)}       # job -> as FILTER
 MOMENTS = {f"{t}m{n}_{s}": (t, n, s) for t in "ab" for n in (64, 1024) for s in (1, 10, N_PTS + 3)}          # job -> (context of, particles, stride)
 COV = {f"{t}c{n}_{s}": (t, n, s) for t in "ab" for n in (64, 1024) for s in (1, 10, N_PTS + 3) if t == "b" or s > 1}          # job -> as MOMENTS
+MARG = {f"{t}h{n}_{s}": (t, n, s) for t in "ab" for n in (64, 1024) for s in (1, 10)}                       # job -> as MOMENTS
 PATHS = {f"{t}p{n}_{k}": (t, n, k) for t in "ab" for n in (64, 1024) for k in (16, 64)}           # job -> (context of, particles, trajectories)
 BACKWARD = {f"{t}b{n}_{k}": (t, n, k) for t in "ab" for n in (64, 1024) for k in (16, 64)}        # job -> as PATHS
 GIBBS = {f"{t}g{n}": (t, n) for t in "ab" for n in (16, 64, 1024)}                                # job -> (context of, particles)
@@ -180,14 +188,14 @@ def run_forecast(B, n, horizon, rounds, calls):
     return out
 
 
-def run(job, rounds, calls, numpy_problems, cache, filter_problems=0, paths_stride=1, parent=None):
+def run(job, rounds, calls, numpy_problems, cache, filter_problems=0, paths_stride=1, parent=None, n_levels=31):
     from bench_problem_batch import StreamTimer, make_contexts
     twin, stored = WEIGHTED.get(job, (job, True))
     weighted = job in WEIGHTED
-    if job in FILTER or job in STATS or job in EVENTS or job in MOMENTS or job in COV or job in PATHS or job in BACKWARD or job in GIBBS:
-        twin = (FILTER.get(job) or STATS.get(job) or EVENTS.get(job) or MOMENTS.get(job) or COV.get(job) or PATHS.get(job) or BACKWARD.get(job) or GIBBS[job])[0]
+    if job in FILTER or job in STATS or job in EVENTS or job in MOMENTS or job in COV or job in MARG or job in PATHS or job in BACKWARD or job in GIBBS:
+        twin = (FILTER.get(job) or STATS.get(job) or EVENTS.get(job) or MOMENTS.get(job) or COV.get(job) or MARG.get(job) or PATHS.get(job) or BACKWARD.get(job) or GIBBS[job])[0]
     name, d, B, kind, n_paths, stride = JOBS[twin]
-    if (job in FILTER or job in STATS or job in EVENTS or job in MOMENTS or job in COV or job in PATHS or job in BACKWARD or job in GIBBS) and twin == "b" and filter_problems:
+    if (job in FILTER or job in STATS or job in EVENTS or job in MOMENTS or job in COV or job in MARG or job in PATHS or job in BACKWARD or job in GIBBS) and twin == "b" and filter_problems:
         B = min(B, filter_problems)
     if (name, B) not in cache:                        # (b and c share a context)
         from helpers import SEED, build_problem
@@ -327,6 +335,48 @@ def run(job, rounds, calls, numpy_problems, cache, filter_problems=0, paths_stri
                 "partial_buffer_mb": round(8.0 * B * blocks * n_keep * packed / 1e6, 1),
                 "moments_partial_buffer_mb": round(8.0 * B * blocks * n_keep * 2 * d / 1e6, 1),
                 "d2h_mb": round(8.0 * B * (n_paths * (1 + d) + n_keep * d * (d + 1)) / 1e6, 1),
+                "moments_d2h_mb": round(8.0 * B * (n_paths * (1 + d) + n_keep * 2 * d) / 1e6, 1)}
+    if job in MARG:
+        from vgpa_amd.particles import gaussian_ladder
+        _, n_paths, stride = MARG[job]
+        mt, st = np.asarray(c.fetch("mt")).reshape(B, N_PTS, d), np.asarray(c.fetch("st")).reshape(B, N_PTS, d, d)
+        ladders = np.stack([gaussian_ladder(mt[p], st[p], n_levels) for p in range(B)])
+        del mt, st
+        calls_of = {"moments": lambda: c.particle_moments(n_paths, 1, stride=stride, ess_fraction=0.5),
+                    "marginals": lambda: c.particle_marginals(n_paths, 1, ladders, stride=stride, ess_fraction=0.5)}
+        res0 = {k: f() for k, f in calls_of.items()}      # warm-up (first-use allocations)
+        n_keep = (N_PTS - 1) // stride + 1
+        mg, mom = res0["marginals"], res0["moments"]
+        assert all(np.array_equal(mom[k], mg[k]) for k in ("log_w", "state", "ess", "resampled", "lineage_ess"))
+        assert mg["mass"].shape == (B, n_keep, d, n_levels + 1) and mg["mass"].dtype == np.uint64
+        total = mg["q_final"].sum(axis=1, dtype=np.uint64)
+        assert np.all(mg["mass"].sum(axis=3, dtype=np.uint64) == total[:, None, None])
+        # the mean of the histogram (bin centres; the end bins at their level) against the moments' mean, in units of the ladder's step
+        step = ladders[:, :, 1] - ladders[:, :, 0]
+        centres = np.concatenate((ladders[:, :, :1], 0.5 * (ladders[:, :, 1:] + ladders[:, :, :-1]), ladders[:, :, -1:]), axis=2)
+        few = slice(0, min(B, 16))      # (on a few problems: at stride 1 the masses of job a are 5 GB)
+        hist_mean = np.einsum("pkdb,pdb->pkd", mg["mass"][few].astype(float), centres[few]) / total[few].astype(float)[:, None, None]
+        off = float(np.max(np.abs(hist_mean - mom["moments"][few, :, 0]) / step[few, None, :]))
+        outside = float(np.max((mg["mass"][few, ..., 0] + mg["mass"][few, ..., -1]).astype(float) / total[few].astype(float)[:, None, None]))
+        del mg, mom, hist_mean, centres, res0["marginals"]["mass"], res0["moments"]["moments"]
+        per_round = {k: [] for k in calls_of}
+        for _ in range(rounds):
+            ms = {k: [] for k in calls_of}
+            for _ in range(calls):
+                for k, f in calls_of.items():
+                    ms[k].append(tm.ms(f))
+            for k in calls_of:
+                per_round[k].append(float(np.median(ms[k])))
+        med = {k: float(np.median(v)) for k, v in per_round.items()}
+        return {"job": job, "model": name, "D": d, "Np": N_PTS, "B": B, "kind": "marginals", "n_paths": n_paths, "ess_fraction": 0.5,
+                "stride": stride, "levels": n_levels, "marginals_ms_per_call": round(med["marginals"], 4),
+                "moments_ms_per_call": round(med["moments"], 4), "ratio": round(med["marginals"] / med["moments"], 4),
+                "marginals_rounds_ms": [round(v, 4) for v in per_round["marginals"]],
+                "moments_rounds_ms": [round(v, 4) for v in per_round["moments"]],
+                "observations": int(c.n_obs), "resampled_share": round(float(res0["moments"]["resampled"].mean()), 3),
+                "histogram_mean_off_by_steps_max": round(off, 4), "mass_in_the_end_bins_max": round(outside, 6),
+                "up_mb": round(8.0 * B * d * n_levels / 1e6, 2),
+                "d2h_mb": round(8.0 * B * (n_paths * (2 + d) + n_keep * d * (n_levels + 1)) / 1e6, 1),
                 "moments_d2h_mb": round(8.0 * B * (n_paths * (1 + d) + n_keep * 2 * d) / 1e6, 1)}
     if job in PATHS:
         _, n_paths, n_draw = PATHS[job]
@@ -501,6 +551,8 @@ def main():
     ap.add_argument("--events", action="store_true", help="run the ae* and be* jobs (particle_events beside particle_statistics and particle_filter)")
     ap.add_argument("--moments", action="store_true", help="run the am* and bm* jobs (particle_moments beside particle_filter)")
     ap.add_argument("--covariance", action="store_true", help="run the ac* and bc* jobs (particle_covariance beside particle_moments and particle_filter)")
+    ap.add_argument("--marginals", action="store_true", help="run the ah* and bh* jobs (particle_marginals beside particle_moments)")
+    ap.add_argument("--levels", type=int, default=31, help="levels per component of the ah* and bh* jobs")
     ap.add_argument("--paths", action="store_true", help="run the ap* and bp* jobs (particle_paths beside particle_filter)")
     ap.add_argument("--paths-strides", default="1,10", help="strides of the ap* and bp* jobs: each job runs once per stride")
     ap.add_argument("--backward", action="store_true", help="run the ab* and bb* jobs (particle_backward_paths beside particle_paths and particle_filter)")
@@ -524,6 +576,8 @@ def main():
         args.jobs = ",".join(sorted(MOMENTS))
     if args.covariance:
         args.jobs = ",".join(sorted(COV))
+    if args.marginals and args.jobs == "a,b,c":
+        args.jobs = ",".join(sorted(MARG))
     if args.paths:
         args.jobs = ",".join(sorted(PATHS))
     if args.backward and args.jobs == "a,b,c":
@@ -543,7 +597,7 @@ def main():
     out = {"tool": "bench_sample_paths", "tree": tree(), "unit": "ms per call (device events around the call)", "jobs": []}
     for job in [j for j in args.jobs.split(",") if j]:
         for stride in (strides if job in PATHS or job in BACKWARD else [1]):
-            out["jobs"].append(run(job, args.rounds, args.calls, args.numpy_problems, cache, args.filter_problems, stride, parent))
+            out["jobs"].append(run(job, args.rounds, args.calls, args.numpy_problems, cache, args.filter_problems, stride, parent, args.levels))
     for c, _, _, _, tm in cache.values():
         tm.close()
         c.close()

@@ -3,7 +3,7 @@
 // allocation a calloc of its own, so AddressSanitizer sees a copy or memset that leaves it), the launchers of sample.hip record their name
 // and arguments and do nothing, and every operation on the stream -- memset, copy in either direction, launch, synchronisation -- is
 // printed in order, device pointers as "d<allocation>+<offset>".  One request per entry point and variant (histories, rows, given slots,
-// given start, both modes of the forecast) on a batch of two Lorenz-63 problems with different observation counts.  Two commits run the
+// given start, both modes of the forecast; the marginals last) on a batch of two Lorenz-63 problems with different observation counts.  Two commits run the
 // same host logic exactly when the two outputs are equal.
 //
 //   hipcc -x hip --offload-host-only -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -Iinclude -Ivgpa_amd/csrc \
@@ -105,9 +105,11 @@ static void walk(const SampleArgs& a) {
       a.n_paths, a.stride, a.n_keep, a.seg_first, a.k_begin, a.k_end, a.pf_rows, a.pf_M, a.pf_slot_rows, a.pf_n, W(a.x0), W(a.out), W(a.logw), W(a.start), W(a.pf_x),
       W(a.pf_lw), W(a.pf_stats), W(a.pf_wtab), W(a.pf_part), W(a.pf_slots), W(a.pf_clouds), W(a.pf_hanc), W(a.A), W(a.b), W(a.R), W(a.theta_v));
 }
-hipError_t launch_sample_walk(Walk w, const SampleArgs& a, hipStream_t, const double* pf_ref, const double* ev_level, const int32_t* ev_side) {
+hipError_t launch_sample_walk(Walk w, const SampleArgs& a, hipStream_t, const double* pf_ref, const double* ev_level, const int32_t* ev_side,
+                              const MarginalArgs* mg) {
   rec("launch sample_walk walk %d pf_ref %s ev_level %s ev_side %s", (int)w, W(pf_ref), W(ev_level), W(ev_side));
   walk(a);
+  if (mg) rec("       levels %s L %d qtab %s mass %s", W(mg->levels), mg->L, W(mg->qtab), W(mg->mass));      // (Walk::ReplayMarginals alone)
   return hipSuccess;
 }
 int sample_segment_blocks(int, int n_paths) { return (n_paths + 63) / 64; }
@@ -127,6 +129,16 @@ hipError_t launch_pf_gather(const PfArgs& a, hipStream_t) { pf("pf_gather", a); 
 hipError_t launch_pf_descend(const PfArgs& a, int rows, double* wtab, double* less, hipStream_t) {
   pf("pf_descend", a);
   rec("       rows %d wtab %s less %s", rows, W(wtab), W(less));
+  return hipSuccess;
+}
+hipError_t launch_pf_quantise(const PfArgs& a, int rows, const double* wtab, uint64_t* qtab, uint64_t* qfinal, hipStream_t) {
+  pf("pf_quantise", a);
+  rec("       rows %d wtab %s qtab %s qfinal %s", rows, W(wtab), W(qtab), W(qfinal));
+  return hipSuccess;
+}
+hipError_t launch_pf_descend_q(const PfArgs& a, int rows, uint64_t* qtab, hipStream_t) {
+  pf("pf_descend_q", a);
+  rec("       rows %d qtab %s", rows, W(qtab));
   return hipSuccess;
 }
 hipError_t launch_pf_pick(const PfArgs& a, int k, int n_draw, int rows, int32_t* table, hipStream_t) {
@@ -229,6 +241,18 @@ int main() {
   std::printf("   %s\n", vgpa_last_error(c));
   run("refused: a slot outside", vgpa_particle_paths(c, x.data(), nullptr, 4, K, given.data(), 1, 7, 0.5, nullptr, nullptr, lw.data(), st.data(), paths.data(), nullptr, nullptr, nullptr) == VGPA_OK);
   std::printf("   %s\n", vgpa_last_error(c));
+  // the marginals, behind every earlier request: their allocations and operations stay what they were
+  {
+    const int L = 5;
+    std::vector<double> ladder((size_t)B * D * L);
+    for (size_t e = 0; e < ladder.size(); e++) ladder[e] = 0.5 * (double)(e % L) - 1.0;
+    std::vector<uint64_t> mass((size_t)B * Np * D * (L + 1)), qfinal((size_t)B * n);
+    run("marginals", vgpa_particle_marginals(c, x.data(), nullptr, n, 3, 7, 0.5, mu.data(), tau.data(), ladder.data(), L, lw.data(), st.data(), mass.data(), qfinal.data(), less.data(), ess.data(), flag.data()));
+    run("marginals, given start, mass alone", vgpa_particle_marginals(c, x.data(), x0.data(), n, 1, 7, 0.5, nullptr, nullptr, ladder.data(), L, lw.data(), st.data(), mass.data(), nullptr, nullptr, nullptr, nullptr));
+    ladder[(size_t)(1 * D + 2) * L + 3] = ladder[(size_t)(1 * D + 2) * L + 2];
+    run("refused: a ladder that does not increase", vgpa_particle_marginals(c, x.data(), nullptr, n, 1, 7, 0.5, nullptr, nullptr, ladder.data(), L, lw.data(), st.data(), mass.data(), nullptr, nullptr, nullptr, nullptr) == VGPA_OK);
+    std::printf("   %s\n", vgpa_last_error(c));
+  }
   recording = false;
   vgpa_destroy(c);
   return failed ? 1 : 0;

@@ -33,11 +33,13 @@ MOMENTS_IDS = {"row_major": 0, "time_major": 1}
 LAYOUT_IDS = {"whole": 0, "upper": 1, "packed": 2}
 BWD_IDS = {"none": 0, "psi": 1, "q": 2}
 
+MAX_MARGINAL_LEVELS = 63      # kMaxMarginalLevels of the library: a bin is found with at most 6 compares
+
 # exported symbols, checked by the CPU test-suite against include/vgpa_hip.h
 SYMBOLS = ["vgpa_create", "vgpa_destroy", "vgpa_last_error", "vgpa_abi_version", "vgpa_device_count",
            "vgpa_synchronize", "vgpa_stream", "vgpa_solve_fwd", "vgpa_solve_bwd", "vgpa_energy",
            "vgpa_obs_energy", "vgpa_free_energy", "vgpa_gradient", "vgpa_sweep", "vgpa_energy_parts",
-           "vgpa_fetch", "vgpa_theta_gradient", "vgpa_lag_covariance", "vgpa_sample_paths", "vgpa_sample_paths_weighted", "vgpa_particle_filter", "vgpa_particle_statistics", "vgpa_particle_events", "vgpa_particle_moments", "vgpa_particle_covariance", "vgpa_particle_paths", "vgpa_particle_backward_paths", "vgpa_particle_conditional", "vgpa_particle_forecast", "vgpa_sweep_dev", "vgpa_free_energy_dev", "vgpa_sweep_enqueue", "vgpa_fetch_f",
+           "vgpa_fetch", "vgpa_theta_gradient", "vgpa_lag_covariance", "vgpa_sample_paths", "vgpa_sample_paths_weighted", "vgpa_particle_filter", "vgpa_particle_statistics", "vgpa_particle_events", "vgpa_particle_moments", "vgpa_particle_covariance", "vgpa_particle_marginals", "vgpa_particle_paths", "vgpa_particle_backward_paths", "vgpa_particle_conditional", "vgpa_particle_forecast", "vgpa_sweep_dev", "vgpa_free_energy_dev", "vgpa_sweep_enqueue", "vgpa_fetch_f",
            "vgpa_dev_alloc", "vgpa_dev_free", "vgpa_memcpy_h2d", "vgpa_memcpy_d2h",
            "vgpa_profile_begin", "vgpa_profile_end", "vgpa_ld_gemm", "vgpa_ld_stage", "vgpa_gradient_dev", "vgpa_energy_full", "vgpa_set_option", "vgpa_is_streaming", "vgpa_path_info", "vgpa_set_prior_energy",
            "vgpa_set_problem_data", "vgpa_set_problem_params", "vgpa_set_problem_obs_model",
@@ -152,6 +154,8 @@ def load():
                                           c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vgpa_particle_covariance.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_uint64, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.vgpa_particle_marginals.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_uint64, c_double, c_void_p, c_void_p, c_void_p, c_int32,
+                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vgpa_particle_paths.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_uint64, c_double, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vgpa_particle_backward_paths.argtypes = lib.vgpa_particle_paths.argtypes
@@ -248,6 +252,11 @@ def _c64(a):
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(c_void_p)
+
+
+def _arg(a):
+    """an input of an entry point as ctypes takes it: an integer as it is, an array (or None) as its pointer"""
+    return a if type(a) is int else _ptr(a)
 
 
 def _shaped(a, shape, name, dtype=np.float64):
@@ -632,7 +641,7 @@ class Context:
             (h, x, x0, [ref], n_paths, [n_draw, final_slots], [stride], seed, ess_fraction, mu, tau, [own inputs], logw, state, [own outputs],
              ess, resampled, [ancestors, clouds])
         and a method says what is its own: ints, the entry's integers by name (n_paths and, where it has them, n_draw and stride; with n_draw
-        go the final `slots`); inputs() -> its own input arrays, checked before x; head() -> what stands before n_paths, checked behind x;
+        go the final `slots`); inputs() -> its own input arrays (and an integer that goes with them), checked before x; head() -> what stands before n_paths, checked behind x;
         outputs(n, k, n_keep) -> {key: array or None} in the entry's order; history: None where the entry has no histories, else whether they
         are wanted.  Returns the dict: log_w, state, ess, resampled, the histories, the entry's own."""
         ints = {name: int(v) for name, v in ints.items()}
@@ -647,7 +656,7 @@ class Context:
         hist = {} if history is None else self._history(n, history)
         self._check(getattr(self._lib, entry)(self._h, _ptr(xx), _ptr(s0), *map(_ptr, first), ints["n_paths"], *draw,
                                               *((ints["stride"],) if "stride" in ints else ()), self._seed(seed), float(ess_fraction), _ptr(mu),
-                                              _ptr(tau), *map(_ptr, own_in), _ptr(log_w), _ptr(state), *map(_ptr, own.values()), _ptr(ess),
+                                              _ptr(tau), *map(_arg, own_in), _ptr(log_w), _ptr(state), *map(_ptr, own.values()), _ptr(ess),
                                               _ptr(flags), *map(_ptr, hist.values())))
         return {"log_w": log_w, "state": state, "ess": ess, "resampled": flags, **hist, **own}
 
@@ -764,6 +773,43 @@ class Context:
         at the grid indices 0, stride, ...  The covariance is second - mean mean^T (SmoothingCovariance.cov)."""
         return self._filter_call("vgpa_particle_covariance", {"n_paths": n_paths, "stride": stride}, seed, ess_fraction, x, x0, prior, lambda n, k, n_keep: {
             "mean": self._new(n_keep, self.D), "second": self._new(n_keep, self.D, self.D), "lineage_ess": self._new(self.n_obs + 1, fill=0.0)})
+
+    def _ladder_input(self, levels):
+        """levels of particle_marginals laid out for the C ABI: (B, D, L) float64 and L.  (L,) is every component's of every problem, (D, L)
+        every problem's."""
+        lev = np.asarray(levels, dtype=np.float64)
+        if lev.ndim not in (1, 2, 3) or lev.size == 0:
+            raise ValueError(f"levels has shape {lev.shape}, expected (L,), ({self.D}, L) or ({self.B}, {self.D}, L)")
+        n_levels = lev.shape[-1]
+        if lev.shape[:-1] not in ((), (self.D,), (self.B, self.D)):
+            raise ValueError(f"levels has shape {lev.shape}, expected ({n_levels},), ({self.D}, {n_levels}) or ({self.B}, {self.D}, {n_levels})")
+        if not 1 <= n_levels <= MAX_MARGINAL_LEVELS:
+            raise ValueError(f"levels holds {n_levels} levels per component, expected 1 to {MAX_MARGINAL_LEVELS}")
+        if lev.ndim == 1:
+            lev = np.broadcast_to(lev, (self.D, n_levels))
+        lev = _c64(per_problem(lev, self.B, self.D * n_levels)).reshape(self.B, self.D, n_levels)
+        if not np.all(np.isfinite(lev)):
+            raise ValueError("levels must be finite")
+        if not np.all(lev[..., 1:] > lev[..., :-1]):
+            p, d = np.argwhere(~np.all(lev[..., 1:] > lev[..., :-1], axis=-1))[0]
+            raise ValueError(f"levels must be strictly increasing (problem {p}, component {d})")
+        return lev, int(n_levels)
+
+    def particle_marginals(self, n_paths, seed, levels, stride=1, ess_fraction=0.5, x=None, x0=None, prior=None):
+        """The smoothing marginals on the grid under particle_filter's genealogy (vgpa_particle_marginals): particle_moments' filter, descendant
+        weights and second walk, which counts where that one sums.  levels: per problem and component a strictly increasing ladder of L <= 63
+        finite levels, (B, D, L), or (D, L) or (L,) for every problem (and component); bin(x) = #{l: levels_l < x}.  Returns a dict: log_w,
+        state, ess, resampled as particle_filter (bit for bit), mass (B, n_keep, D, L + 1) uint64: the sum of the lineages' integer weights per
+        bin at the grid indices 0, stride, ..., exact and independent of any order of addition, q_final (B, n_paths) uint64:
+        trunc(W 2^62) of the final weights, and lineage_ess as particle_moments (bit for bit)."""
+        ladder = []      # (levels, L): made where _filter_call checks the entry's own inputs, read where it makes the outputs
+
+        def inputs():
+            ladder.extend(self._ladder_input(levels))
+            return tuple(ladder)
+        return self._filter_call("vgpa_particle_marginals", {"n_paths": n_paths, "stride": stride}, seed, ess_fraction, x, x0, prior, lambda n, k, n_keep: {
+            "mass": self._new(n_keep, self.D, ladder[1] + 1, dtype=np.uint64), "q_final": self._new(n, dtype=np.uint64),
+            "lineage_ess": self._new(self.n_obs + 1, fill=0.0)}, inputs=inputs)
 
     def particle_paths(self, n_paths, seed, n_draw, stride=1, ess_fraction=0.5, x=None, x0=None, prior=None, slots=None):
         """n_draw whole smoothing trajectories per problem from particle_filter's genealogy (vgpa_particle_paths): the filter, the final

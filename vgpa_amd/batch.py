@@ -265,6 +265,19 @@ class ProblemBatch(object):
         return self._particle_call("particle_covariance", lambda v, res, k: v._covariance_record(res, k, stride), n_paths, seed, stride=stride,
                                    ess_fraction=ess_fraction, x=x, x0=x0)
 
+    def particle_marginals(self, n_paths, seed, levels=None, stride=1, ess_fraction=0.5, x=None, x0=None, n_levels=31, width=4.0):
+        """One particles.SmoothingMarginals per member (VarGP.particle_marginals): per component a histogram of x_k | y over a ladder of
+        levels on the grid under the genealogy of the member's own filter.  levels: (B, D, L) for per-member ladders, or (D, L) or (L,) for
+        all; None: every member's own particles.gaussian_ladder of its Gaussian posterior at x."""
+        if levels is None:
+            from .particles import posterior_ladders
+            if x is not None:      # (F at x first: the call behind it reads the cached state)
+                self.free_energy(x)
+            levels, x = posterior_ladders(self._context(), n_levels, width), None
+        return self._particle_call("particle_marginals", lambda v, res, k, lev: v._marginals_record(res, k, lev[k], stride), n_paths, seed, levels,
+                                   stride=stride, ess_fraction=ess_fraction, x=x, x0=x0,
+                                   late=lambda: (self._context()._ladder_input(levels)[0],))
+
     def particle_paths(self, n_paths, seed, n_draw, stride=1, ess_fraction=0.5, x=None, x0=None, slots=None):
         """One particles.SmoothingPaths per member (VarGP.particle_paths): n_draw whole smoothing trajectories from the genealogy of the
         member's own filter, with its own data, observation times and count, prior, theta and Sigma."""

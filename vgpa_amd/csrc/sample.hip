@@ -43,6 +43,9 @@
 //   SegmentEvents| a segment that also carries each slot's [3][D] row of event records (X, T, N) of g_j(x) = s_j (x_j - c_j): the      | s.4.20
 //                | largest g, the first grid index with g > 0, the number of such indices  [k_pf_events_start: the rows of grid      |
 //                | index 0; k_pf_resample<true>, k_pf_stats_mean as for SegmentStats; k_pf_events_cdf: the first-passage distribution] |
+//   ReplayMarginals| the replay with counts in place of sums: at every kept grid index each slot finds, per component, the bin of its  | s.4.21
+//                | state on the component's ladder of levels and adds its integer descendant weight to that bin's mass  [the replay's  |
+//                | steps; k_pf_quantise: the final weights as integers, k_pf_descend_q: k_pf_descend in 64-bit integer arithmetic]     |
 #include "vgpa_internal.h"
 
 #include <type_traits>
@@ -163,19 +166,28 @@ struct EventArgs : SampleArgs {
   const double* ev_level;    // [B][D]
   const int32_t* ev_side;    // [B][D] +1 / -1
 };
+// ... and for ReplayMarginals alone the ladders, the integer weights and the masses
+struct MarginalWalkArgs : SampleArgs {
+  const double* mg_level;            // [B][D][L]
+  int mg_L;
+  const uint64_t* mg_qtab;           // [B][pf_rows][n_paths]
+  unsigned long long* mg_mass;       // [B][n_keep][D][L + 1]
+};
 template <Walk K> struct WalkArgsOf { using type = SampleArgs; };
 template <> struct WalkArgsOf<Walk::Conditional> { using type = ConditionalArgs; };
 template <> struct WalkArgsOf<Walk::SegmentEvents> { using type = EventArgs; };
+template <> struct WalkArgsOf<Walk::ReplayMarginals> { using type = MarginalWalkArgs; };
 template <Walk K> using WalkArgs = typename WalkArgsOf<K>::type;
 
 // What the two kernels branch on, per walk: W the walk of the weighted kind (posterior drift, diagonal R), SEG it runs (k_begin, k_end] from
 // and to pf_x, ST it carries the rows of pf_stats, MO it takes the moments of the replay, LN the counter words come from pf_slots;
 // FC it is the forecast (the model's drift from the cloud in pf_x, k_sample_small only); CV the replay's second moments are the whole matrix
 // (with MO); BW: the state is reloaded from the filter's histories behind every observation (with LN); CD: slot 0 is pinned to pf_ref of
-// ConditionalArgs (with SEG); EV: it carries the event records of EventArgs' levels and sides in the rows of pf_stats (with SEG); WS: the
-// weight sums are formed.  The eleven rows are all there is: no other combination can be instantiated.
+// ConditionalArgs (with SEG); EV: it carries the event records of EventArgs' levels and sides in the rows of pf_stats (with SEG); MG: at a
+// kept index the replay adds MarginalWalkArgs' integer weights to the bins of its states and forms no sum (with MO); WS: the weight sums
+// are formed.  The twelve rows are all there is: no other combination can be instantiated.
 struct WalkTraits {
-  bool W, SEG, ST, MO, LN, FC, CV, BW, CD, EV;
+  bool W, SEG, ST, MO, LN, FC, CV, BW, CD, EV, MG;
   constexpr bool WS() const { return W && !MO; }
 };
 constexpr WalkTraits kWalkTraits[] = {      // in the order of Walk
@@ -189,7 +201,19 @@ constexpr WalkTraits kWalkTraits[] = {      // in the order of Walk
     {true,  true,  false, true,  false, false, true},     // ReplayCov
     {false, false, false, false, true,  false, false, true},     // Backward
     {true,  true,  false, false, false, false, false, false, true},     // Conditional
-    {true,  true,  false, false, false, false, false, false, false, true}};    // SegmentEvents
+    {true,  true,  false, false, false, false, false, false, false, true},    // SegmentEvents
+    {true,  true,  false, true,  false, false, false, false, false, false, true}};    // ReplayMarginals
+
+// Walk::ReplayMarginals: the bin of x on a strictly increasing ladder of L levels, #{l: c_l < x}, by bisection on fp64 compares alone (at most 6
+// for L <= 63; a NaN compares false everywhere: bin 0), and the slot's weight added to that bin of row [L + 1]
+__device__ __forceinline__ void marginal_add(const double* lev, int L, unsigned long long* row, double x, unsigned long long qw) {
+  int lo = 0, hi = L;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (lev[mid] < x) lo = mid + 1; else hi = mid;
+  }
+  atomicAdd(row + lo, qw);
+}
 
 // Weighted: posterior kind, diagonal R: both drifts at x_{k-1}, d = g - f, and per step -sum_i d_i (eta_i + dt d_i / 2) / Sigma_ii with
 // 1 / Sigma_ii = dt / R_ii^2; the observation term at the lane's own problem's times.
@@ -219,6 +243,10 @@ constexpr WalkTraits kWalkTraits[] = {      // in the order of Walk
 // SegmentEvents: a segment, bit for bit, that behind every step k holds d = x_j(k) - c_j (one subtraction), g = d or -d by the side, and
 // X_j = fmax(X_j, g); where g > 0, T_j = min(T_j, k) and N_j += 1.  The slot's row of pf_stats is read at the segment's entry and written at
 // its exit, T and N as the doubles the integers are; in between they are 32-bit integers.  (The row of grid index 0 is k_pf_events_start's.)
+// ReplayMarginals: the replay's launch, states and kept indices; no weight is a double and nothing is summed over lanes.  At a kept k a live
+// lane whose integer weight Q (the row of mg_qtab of the problem's stretch) is not 0 adds Q to mass[p][k'][i][bin(x_i)] for each of its
+// components with one 64-bit integer atomic per component, the ladder read from global memory.  Integer addition is associative: the masses
+// do not depend on the order the atomics arrive in.
 // Walk::Backward: x = the particle slot `word` was copied from at observation j of problem p
 template <int D>
 __device__ __forceinline__ void backward_reload(const SampleArgs& a, uint32_t p, int j, uint32_t word, double* x) {
@@ -231,7 +259,7 @@ __device__ __forceinline__ void backward_reload(const SampleArgs& a, uint32_t p,
 template <int D, Walk K>
 __global__ __launch_bounds__(256) void k_sample_small(WalkArgs<K> a) {
   constexpr WalkTraits T = kWalkTraits[(int)K];
-  constexpr bool W = T.W, SEG = T.SEG, ST = T.ST, MO = T.MO, LN = T.LN, FC = T.FC, CV = T.CV, BW = T.BW, CD = T.CD, EV = T.EV, WS = T.WS();
+  constexpr bool W = T.W, SEG = T.SEG, ST = T.ST, MO = T.MO, LN = T.LN, FC = T.FC, CV = T.CV, BW = T.BW, CD = T.CD, EV = T.EV, MG = T.MG, WS = T.WS();
   constexpr int NV = CV ? D + D * (D + 1) / 2 : 2 * D;      // values a kept k reduces
   size_t gid;
   uint32_t p, path;
@@ -321,7 +349,14 @@ __global__ __launch_bounds__(256) void k_sample_small(WalkArgs<K> a) {
   double* red = nullptr;
   int par = 0;
   long long keep_k = 0, keep_slot = 0;
-  if constexpr (MO) {
+  unsigned long long qw = 0;      // ReplayMarginals: the slot's integer weight
+  if constexpr (MG) {
+    oc = ObsCursor(a, p);
+    if (!a.seg_first) oc.skip_through(a.k_begin);
+    qw = live ? a.mg_qtab[((size_t)p * a.pf_rows + oc.cur) * a.n_paths + path] : 0ull;
+    keep_slot = ((long long)a.k_begin + a.stride) / a.stride;
+    keep_k = keep_slot * a.stride;
+  } else if constexpr (MO) {
     __shared__ double red_lds[2 * NV * 4];
     red = red_lds;
     oc = ObsCursor(a, p);
@@ -336,6 +371,16 @@ __global__ __launch_bounds__(256) void k_sample_small(WalkArgs<K> a) {
     wt = live && a.pf_wtab ? a.pf_wtab[gid] : 0.0;
     keep_slot = 1; keep_k = a.stride;
   }
+  auto count = [&](long long slot) {      // ReplayMarginals, in reduce's place
+    if constexpr (MG) {
+      if (qw != 0) {
+#pragma unroll
+        for (int i = 0; i < D; i++)
+          marginal_add(a.mg_level + ((size_t)p * D + i) * a.mg_L, a.mg_L,
+                       a.mg_mass + (((size_t)p * a.n_keep + (size_t)slot) * D + i) * ((size_t)a.mg_L + 1), x[i], qw);
+      }
+    }
+  };
   auto reduce = [&](long long slot) {
     double v[NV];
     if constexpr (CV) {
@@ -362,7 +407,8 @@ __global__ __launch_bounds__(256) void k_sample_small(WalkArgs<K> a) {
     }
     par ^= 1;
   };
-  if constexpr (MO) { if (a.seg_first) reduce(0); }
+  if constexpr (MG) { if (a.seg_first) count(0); }
+  else if constexpr (MO) { if (a.seg_first) reduce(0); }
   if constexpr (FC) { if (a.pf_part) reduce(0); }
   double sq[ST ? D : 1], sg1[ST ? D : 1], sh[ST ? D : 1], phi[ST ? D : 1];
   if constexpr (ST) {
@@ -437,7 +483,9 @@ __global__ __launch_bounds__(256) void k_sample_small(WalkArgs<K> a) {
     if constexpr (WS) {
       if (k == oc.next) { ow += obs_form<D>(a, p, oc.cur, x); oc.advance(); }
     }
-    if constexpr (MO) {
+    if constexpr (MG) {
+      if (k == keep_k) { count(keep_slot++); keep_k += a.stride; }
+    } else if constexpr (MO) {
       if (k == keep_k) { reduce(keep_slot++); keep_k += a.stride; }
     }
     if constexpr (LN) {
@@ -558,7 +606,7 @@ __device__ __forceinline__ void normals_c(uint32_t k0, uint32_t k1, uint32_t k, 
 template <int NT, Walk K>
 __global__ __launch_bounds__(256) void k_sample_mfma(WalkArgs<K> a) {
   constexpr WalkTraits T = kWalkTraits[(int)K];
-  constexpr bool W = T.W, SEG = T.SEG, ST = T.ST, MO = T.MO, LN = T.LN, CV = T.CV, BW = T.BW, CD = T.CD, EV = T.EV, WS = T.WS();
+  constexpr bool W = T.W, SEG = T.SEG, ST = T.ST, MO = T.MO, LN = T.LN, CV = T.CV, BW = T.BW, CD = T.CD, EV = T.EV, MG = T.MG, WS = T.WS();
   using Sh = MfmaShape<NT>;
   constexpr int LDA = Sh::LDA, MT = Sh::MT, KT = Sh::KT, NPF = Sh::NPF;
   extern __shared__ double lds[];
@@ -750,8 +798,10 @@ __global__ __launch_bounds__(256) void k_sample_mfma(WalkArgs<K> a) {
   double wt = 0.0;
   double* red = lds + NT * LDA + NT + 4 * NT * 16;
   long long keep_k = 0, keep_slot = 0, pending = -1;
+  unsigned long long qw = 0;      // ReplayMarginals: the path's integer weight
+  if constexpr (MG) qw = path < (uint32_t)a.n_paths ? a.mg_qtab[((size_t)p * a.pf_rows + oc.cur) * a.n_paths + path] : 0ull;
   if constexpr (MO) {
-    wt = path < (uint32_t)a.n_paths ? a.pf_wtab[((size_t)p * a.pf_rows + oc.cur) * a.n_paths + path] : 0.0;
+    if constexpr (!MG) wt = path < (uint32_t)a.n_paths ? a.pf_wtab[((size_t)p * a.pf_rows + oc.cur) * a.n_paths + path] : 0.0;
     keep_slot = ((long long)a.k_begin + a.stride) / a.stride;      // the first kept index behind k_begin
     keep_k = keep_slot * a.stride;
   }
@@ -776,6 +826,21 @@ __global__ __launch_bounds__(256) void k_sample_mfma(WalkArgs<K> a) {
             ((r0[0] + r0[2 * NT]) + r0[4 * NT]) + r0[6 * NT];
       }
       pending = -1;
+    }
+  };
+  auto count = [&](long long slot) {      // ReplayMarginals, in reduce's place: the lane's own rows of its path, no cross-lane step
+    if constexpr (MG) {
+      if (qw != 0) {
+#pragma unroll
+        for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+          for (int r = 0; r < 4; r++) {
+            const int row = mt * 16 + q + 4 * r;
+            if (row < D)
+              marginal_add(a.mg_level + ((size_t)p * D + row) * a.mg_L, a.mg_L,
+                           a.mg_mass + (((size_t)p * a.n_keep + (size_t)slot) * D + row) * ((size_t)a.mg_L + 1), x[mt][r], qw);
+          }
+      }
     }
   };
   auto reduce_cov = [&](long long slot) {
@@ -841,7 +906,8 @@ __global__ __launch_bounds__(256) void k_sample_mfma(WalkArgs<K> a) {
         }
     }
   };
-  if constexpr (MO && !CV) { if (a.seg_first) reduce(0); }
+  if constexpr (MG) { if (a.seg_first) count(0); }
+  if constexpr (MO && !CV && !MG) { if (a.seg_first) reduce(0); }
   if constexpr (CV) { if (a.seg_first) reduce_cov(0); }
 
   int until = a.stride;
@@ -942,7 +1008,7 @@ __global__ __launch_bounds__(256) void k_sample_mfma(WalkArgs<K> a) {
       }
     }
     __syncthreads();
-    if constexpr (MO && !CV) flush();
+    if constexpr (MO && !CV && !MG) flush();
     if (more) {
 #pragma unroll
       for (int n = 0; n < NPF; n++) { const int e = tid + 256 * n; if (e < DD) As[(e / D) * LDA + e % D] = pa[n]; }
@@ -957,7 +1023,10 @@ __global__ __launch_bounds__(256) void k_sample_mfma(WalkArgs<K> a) {
     if constexpr (WS) {
       if (k == oc.next) observe();
     }
-    if constexpr (MO && !CV) {
+    if constexpr (MG) {
+      if (k == keep_k) { count(keep_slot++); keep_k += a.stride; }
+    }
+    if constexpr (MO && !CV && !MG) {
       if (k == keep_k) { reduce(keep_slot++); keep_k += a.stride; }
     }
     if constexpr (CV) {
@@ -972,7 +1041,7 @@ __global__ __launch_bounds__(256) void k_sample_mfma(WalkArgs<K> a) {
   }
   if constexpr (MO) {
     __syncthreads();
-    if constexpr (!CV) flush();
+    if constexpr (!CV && !MG) flush();
     put(a.pf_x + ((size_t)p * a.n_paths + path0) * D, (size_t)D);      // (Xs holds x_{k_end} behind the loop's last barrier)
   } else if constexpr (W) {
     pw += __shfl_xor(pw, 16); pw += __shfl_xor(pw, 32);
@@ -1458,6 +1527,60 @@ __global__ __launch_bounds__(256) void k_pf_descend(PfArgs a, int rows, double* 
   }
 }
 
+// ---- the smoothing marginals: the descendant weights as integers ------------------------------------------------------
+// Behind k_pf_descend, one thread per (problem, slot): row c of qtab [rows][n] = (uint64) trunc(W 2^62) of row c of wtab, c the problem's own
+// observation count, and the same value to qfinal [B][n], the dense array that leaves in one copy.  W <= 1 and the product by a power of two
+// is exact: the conversion alone rounds, towards zero.
+__global__ __launch_bounds__(256) void k_pf_quantise(PfArgs a, int rows, const double* wtab, uint64_t* qtab, uint64_t* qfinal) {
+  const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= (size_t)a.batch * a.n_paths) return;
+  const size_t p = g / a.n_paths, i = g - p * a.n_paths;
+  const int cnt = a.n_obs_v ? a.n_obs_v[p] : a.n_obs;
+  const size_t e = (p * rows + cnt) * a.n_paths + i;
+  const double v = wtab[e] * 0x1.0p62;
+  const uint64_t qv = v >= 1.0 ? (uint64_t)v : 0ull;      // (a NaN or a negative weight: 0)
+  qtab[e] = qv; qfinal[g] = qv;
+}
+
+// k_pf_descend's recursion on the integers, one workgroup per problem: for j = c-1 .. 0 row j of qtab is row j+1 where the cloud was carried
+// on at observation j, else Q^j_a = the sum of Q^{j+1}_i over the run [first i with anc_i >= a, first i with anc_i >= a + 1) of the
+// non-decreasing ancestors, found by the same two bisections and added by slot a's own thread in 64-bit integer arithmetic.
+__global__ __launch_bounds__(256) void k_pf_descend_q(PfArgs a, int rows, uint64_t* qtab_all) {
+  const int p = blockIdx.x, tid = threadIdx.x, n = a.n_paths;
+  const int cnt = a.n_obs_v ? a.n_obs_v[p] : a.n_obs;
+  uint64_t* qtab = qtab_all + (size_t)p * rows * n;
+  uint64_t* row = qtab + (size_t)cnt * n;
+  for (int j = cnt - 1; j >= 0; j--) {
+    const uint64_t* next = row;
+    row = qtab + (size_t)j * n;
+    const size_t hj = (size_t)p * a.M + j;
+    const int32_t* anc = a.h_anc + hj * n;
+    const bool gathered = a.h_flag[hj] != 0;      // (uniform over the workgroup)
+    for (int i = tid; i < n; i += 256) {
+      uint64_t qi = next[i];
+      if (gathered) {
+        int lo = 0, hi = n;
+        while (lo < hi) { const int mid = (lo + hi) >> 1; if (anc[mid] < i) lo = mid + 1; else hi = mid; }
+        int end = lo;
+        hi = n;
+        while (end < hi) { const int mid = (end + hi) >> 1; if (anc[mid] <= i) end = mid + 1; else hi = mid; }
+        qi = 0;
+        int m = lo;
+        for (; m + 8 <= end; m += 8) {      // (eight loads in flight, as in k_pf_descend)
+          uint64_t t8[8];
+#pragma unroll
+          for (int u = 0; u < 8; u++) t8[u] = next[m + u];
+#pragma unroll
+          for (int u = 0; u < 8; u++) qi += t8[u];
+        }
+        for (; m < end; m++) qi += next[m];
+      }
+      row[i] = qi;
+    }
+    __syncthreads();      // (the row is written before the next one reads it)
+  }
+}
+
 // The forecast's weights, one workgroup per problem: W_i = w_i / sum w with w_i = exp(lw_i - max lw), the sum in the fixed order of block_sum.
 __global__ __launch_bounds__(256) void k_pf_normalise(int n, const double* lw_all, double* w_all) {
   __shared__ double red[4];
@@ -1915,15 +2038,16 @@ __global__ __launch_bounds__(256) void k_pf_ref_fill(PfArgs a, int rows, const i
 
 // One walk at the D of the arguments: k_sample_small<D, K> up to D = 4 (one lane per path; the replay: the problem in grid.x, 256 slots per
 // workgroup in grid.y), above it k_sample_mfma<NT, K> with NT the next multiple of 16 (grid: problems x 64 paths).  D = 2 exists for the
-// plain walk only: every other walk needs a stochastic model, and none has D = 2.  (Eleven walks: 3 instantiations of k_sample_small each
+// plain walk only: every other walk needs a stochastic model, and none has D = 2.  (Twelve walks: 3 instantiations of k_sample_small each
 // and one more for Plain, 4 of k_sample_mfma each but Forecast.)
 template <Walk K>
 hipError_t launch_walk(const SampleArgs& base, hipStream_t st, const double* pf_ref = nullptr, const double* ev_level = nullptr,
-                       const int32_t* ev_side = nullptr) {
+                       const int32_t* ev_side = nullptr, const MarginalArgs* mg = nullptr) {
   WalkArgs<K> a;
   static_cast<SampleArgs&>(a) = base;
   if constexpr (K == Walk::Conditional) a.pf_ref = pf_ref;
   if constexpr (K == Walk::SegmentEvents) { a.ev_level = ev_level; a.ev_side = ev_side; }
+  if constexpr (K == Walk::ReplayMarginals) { a.mg_level = mg->levels; a.mg_L = mg->L; a.mg_qtab = mg->qtab; a.mg_mass = mg->mass; }
   if (a.D <= kMaxLaneD) {
     const dim3 grid = kWalkTraits[(int)K].MO || kWalkTraits[(int)K].FC ? dim3(a.batch, sample_segment_blocks(a.D, a.n_paths))
                                         : dim3((unsigned)(((size_t)a.batch * a.n_paths + 255) / 256));
@@ -2008,6 +2132,19 @@ bool pf_flat_grid_fits(size_t entries) { return (entries + 255) / 256 <= 0x7ffff
 hipError_t launch_pf_descend(const PfArgs& a, int rows, double* wtab, double* less, hipStream_t st) {
   if (a.batch < 1 || a.n_paths < 1 || a.M < 1 || rows < a.M + 1 || !a.lw || !a.h_flag || !a.h_anc || !wtab || !less) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_pf_descend, dim3(a.batch), dim3(256), 0, st, a, rows, wtab, less);
+  return hipGetLastError();
+}
+
+hipError_t launch_pf_quantise(const PfArgs& a, int rows, const double* wtab, uint64_t* qtab, uint64_t* qfinal, hipStream_t st) {
+  const size_t lanes = (size_t)(a.batch > 0 ? a.batch : 0) * (size_t)(a.n_paths > 0 ? a.n_paths : 0);
+  if (a.batch < 1 || a.n_paths < 1 || a.M < 1 || rows < a.M + 1 || !pf_flat_grid_fits(lanes) || !wtab || !qtab || !qfinal) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_pf_quantise, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, a, rows, wtab, qtab, qfinal);
+  return hipGetLastError();
+}
+
+hipError_t launch_pf_descend_q(const PfArgs& a, int rows, uint64_t* qtab, hipStream_t st) {
+  if (a.batch < 1 || a.n_paths < 1 || a.M < 1 || rows < a.M + 1 || !a.h_flag || !a.h_anc || !qtab) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_pf_descend_q, dim3(a.batch), dim3(256), 0, st, a, rows, qtab);
   return hipGetLastError();
 }
 
@@ -2097,7 +2234,8 @@ hipError_t launch_pf_events_cdf(int D, int batch, int n_paths, int Np, int strid
 }
 
 // The walk is what the caller says it is; the fields that walk reads must be set, and the fields that would have meant another walk must not.
-hipError_t launch_sample_walk(Walk w, const SampleArgs& a, hipStream_t st, const double* pf_ref, const double* ev_level, const int32_t* ev_side) {
+hipError_t launch_sample_walk(Walk w, const SampleArgs& a, hipStream_t st, const double* pf_ref, const double* ev_level, const int32_t* ev_side,
+                              const MarginalArgs* mg) {
   if (a.D < 1 || a.D > kMaxSmallD || a.n_paths < 1) return hipErrorInvalidValue;
   const bool known_model = a.model == VGPA_MODEL_OU || a.model == VGPA_MODEL_DW || a.model == VGPA_MODEL_L63 || a.model == VGPA_MODEL_L96;
   // the weighted kind: the posterior process with diagonal factors against the model's drift; above D = 4 the model is Lorenz-96
@@ -2106,6 +2244,7 @@ hipError_t launch_sample_walk(Walk w, const SampleArgs& a, hipStream_t st, const
   if (w == Walk::Backward ? a.pf_wtab || a.pf_part : a.pf_clouds || a.pf_hanc) return hipErrorInvalidValue;      // (the histories are Backward's alone, the sums never its)
   if (w != Walk::Conditional && pf_ref) return hipErrorInvalidValue;      // (the reference is Conditional's alone)
   if (w != Walk::SegmentEvents && (ev_level || ev_side)) return hipErrorInvalidValue;      // (the levels and sides are SegmentEvents' alone)
+  if (w != Walk::ReplayMarginals && mg) return hipErrorInvalidValue;      // (the ladders, integer weights and masses are ReplayMarginals' alone)
   switch (w) {
     case Walk::Plain: {
       if (a.stride < 1 || a.logw) return hipErrorInvalidValue;
@@ -2138,6 +2277,11 @@ hipError_t launch_sample_walk(Walk w, const SampleArgs& a, hipStream_t st, const
       if (!segment || !a.pf_wtab || a.pf_stats || !a.pf_part || a.stride < 1 || a.pf_rows < 1) return hipErrorInvalidValue;
       if (a.n_paths > sample_max_paths(a.D)) return hipErrorInvalidValue;
       return launch_walk<Walk::ReplayCov>(a, st);
+    case Walk::ReplayMarginals:      // (the replay's fields without its weights and sums; the ladders, the integer weights, the masses)
+      if (!segment || a.pf_wtab || a.pf_stats || a.pf_part || a.stride < 1 || a.pf_rows < 1 || a.n_keep < 1) return hipErrorInvalidValue;
+      if (!mg || !mg->levels || !mg->qtab || !mg->mass || mg->L < 1 || mg->L > kMaxMarginalLevels) return hipErrorInvalidValue;
+      if (a.n_paths > sample_max_paths(a.D)) return hipErrorInvalidValue;
+      return launch_walk<Walk::ReplayMarginals>(a, st, nullptr, nullptr, nullptr, mg);
     case Walk::Lineage:
       if (a.stride < 1 || a.kind != VGPA_PATHS_POSTERIOR || !a.R_diag || !a.out || !a.pf_slots || a.pf_slot_rows < 1 || a.logw) return hipErrorInvalidValue;
       if (!sample_lineages_fit(a.D, a.batch, a.n_paths)) return hipErrorInvalidValue;

@@ -176,9 +176,10 @@ struct vgpa_ctx {
   // vgpa_particle_backward_paths: the buffers of vgpa_particle_paths, the clouds and PF_HLW: the log-weights the resamplings replaced;
   // vgpa_particle_conditional: the buffers of vgpa_particle_paths, the clouds and PF_REF: the reference trajectories;
   // vgpa_particle_events: the buffers of vgpa_particle_statistics (the rows are the event records), PF_EVC: the levels, PF_EVS: the sides
-  // (int32), PF_CDF: the first-passage distribution
+  // (int32), PF_CDF: the first-passage distribution; vgpa_particle_marginals: the descendant weights and the lineage ESS of the moments,
+  // PF_QTAB: the integer descendant weights (uint64), PF_QFIN: their final row of every problem [B][n], PF_MGL: the ladders, PF_MASS: the masses (uint64)
   enum { PF_XA, PF_XB, PF_LW, PF_CUM, PF_ANC, PF_ESS, PF_FLAG, PF_HANC, PF_CLOUDS, PF_MU, PF_LT, PF_STA, PF_STB, PF_MEAN, PF_WTAB, PF_LESS, PF_PART,
-         PF_MOM, PF_SLOTS, PF_COV, PF_HLW, PF_REF, PF_EVC, PF_EVS, PF_CDF, PF_COUNT };
+         PF_MOM, PF_SLOTS, PF_COV, PF_HLW, PF_REF, PF_EVC, PF_EVS, PF_CDF, PF_QTAB, PF_QFIN, PF_MGL, PF_MASS, PF_COUNT };
   double* d_pf[PF_COUNT] = {};
   size_t pf_n[PF_COUNT] = {};
   // profiling
@@ -1600,7 +1601,7 @@ int vgpa_sample_paths_weighted(vgpa_ctx* c, const double* x, const double* x0, i
 // the filter is "fc_moments is set"; it goes with Carry::None and Behind::None alone.
 enum class Carry { None, Stats, Events };      // nothing; the path statistics (Q, G, H); the event records (X, T, N)
 // (the order matters: table() below takes every enumerator from Trajectories on as a pass with a slot table; a new pass of sums goes before it)
-enum class Behind { None, Moments, Covariance, Trajectories, Backward, Conditional };
+enum class Behind { None, Moments, Covariance, Marginals, Trajectories, Backward, Conditional };
 struct ParticleRequest {
   const double* x; const double* x0; int32_t n_paths; uint64_t seed; double ess_fraction; const double* prior_mu; const double* prior_tau;
   double* logw; double* state; double* ess; int32_t* resampled;      // (up to here: what every entry point has, filled in this order)
@@ -1611,6 +1612,7 @@ struct ParticleRequest {
   Behind behind;
   double* moments; double* lineage_ess;                              // Behind::Moments (lineage_ess: Covariance too)
   double* cov_mean; double* cov_second;                              // Behind::Covariance
+  const double* mg_levels; int32_t n_levels; uint64_t* mass; uint64_t* qfinal;      // Behind::Marginals (lineage_ess too): ladders [B][D][L]
   // Behind::Trajectories / Backward (the table is drawn, not traced) / Conditional (slot 0 pinned to ref [B][Np][D]; n_draw = 1, paths: the
   // drawn trajectory); slots_out: where the table goes
   int32_t n_draw; const int32_t* final_slots; double* paths; int32_t* slots_out; const double* ref;
@@ -1642,12 +1644,12 @@ struct ParticleRun {
   // For each cut -- an observation index of some problem, and the last grid index --: the segment launch up to it, then, at an
   // observation, the step between two segments (from cur to other), and the particle buffers swap.  pf_ref, lev, side: the walk's own.
   int cuts(Walk walk, const char* what, SampleArgs& s, const char* step_what, const std::function<hipError_t(int)>& step,
-           const double* pf_ref = nullptr, const double* lev = nullptr, const int32_t* side = nullptr) {
+           const double* pf_ref = nullptr, const double* lev = nullptr, const int32_t* side = nullptr, const MarginalArgs* mg = nullptr) {
     int prev = 0;
     for (int k = 0; k < c->Np; k++) {
       if (!is_obs[k] && k != c->Np - 1) continue;
       s.k_begin = prev; s.k_end = k; s.pf_x = cur;
-      hipError_t e = launch_sample_walk(walk, s, c->stream, pf_ref, lev, side);
+      hipError_t e = launch_sample_walk(walk, s, c->stream, pf_ref, lev, side, mg);
       if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "%s failed: %s", what, hipGetErrorString(e));
       s.seg_first = 0; prev = k;
       if (!is_obs[k]) continue;
@@ -1678,6 +1680,9 @@ struct ParticleRun {
     if (q.sums() && ((rc = buf(vgpa_ctx::PF_WTAB, (size_t)B * rows * n)) || (rc = buf(vgpa_ctx::PF_LESS, (size_t)B * rows)) ||
                       (rc = buf(vgpa_ctx::PF_PART, (size_t)B * n_blocks * mom_len)) || (rc = buf(vgpa_ctx::PF_MOM, (size_t)B * mom_len)))) return rc;
     if (covariance && (rc = buf(vgpa_ctx::PF_COV, (size_t)B * n_keep * D * ((size_t)D + 1)))) return rc;
+    if (q.behind == Behind::Marginals &&
+        ((rc = buf(vgpa_ctx::PF_WTAB, (size_t)B * rows * n)) || (rc = buf(vgpa_ctx::PF_LESS, (size_t)B * rows)) || (rc = buf(vgpa_ctx::PF_QTAB, (size_t)B * rows * n)) || (rc = buf(vgpa_ctx::PF_QFIN, Bn)) ||
+         (rc = buf(vgpa_ctx::PF_MGL, (size_t)B * D * q.n_levels)) || (rc = buf(vgpa_ctx::PF_MASS, (size_t)B * n_keep * D * ((size_t)q.n_levels + 1))))) return rc;
     if (keep_clouds && (rc = buf(vgpa_ctx::PF_CLOUDS, BM * n * D))) return rc;
     if (keep_lw && (rc = buf(vgpa_ctx::PF_HLW, BM * n))) return rc;
     if (carried && ((rc = buf(vgpa_ctx::PF_STA, 3 * BnD)) || (rc = buf(vgpa_ctx::PF_STB, 3 * BnD)) || (rc = buf(vgpa_ctx::PF_MEAN, (size_t)B * 3 * D)))) return rc;
@@ -1784,6 +1789,43 @@ struct ParticleRun {
       if ((rc = download(c, q.cov_mean, d_mean, n_mean)) || (rc = download(c, q.cov_second, d_mean + n_mean, n_mean * c->D))) return rc;
     } else if ((rc = download(c, q.moments, c->d_pf[vgpa_ctx::PF_MOM], (size_t)B * mom_len))) return rc;
     if (q.lineage_ess)      // (the device's rows are M1 + 1 = M + 1, but for a context of capacity 0)
+      for (int p = 0; p < (rows == M + 1 ? 1 : B); p++)
+        if ((rc = download(c, q.lineage_ess + (size_t)p * (M + 1), less + (size_t)p * rows, rows == M + 1 ? (size_t)B * rows : (size_t)M + 1))) return rc;
+    return VGPA_OK;
+  }
+
+  // The smoothing marginals, behind the filter: the descendant weights of moments() -- its lineage ESS is this call's --,
+  // their final row as integers, the integer recursion through the same ancestors, the masses zeroed, then the replay with
+  // Walk::ReplayMarginals, which adds every slot's integer weight to the bin of each of its components at every kept grid index.
+  int marginals() {
+    const int B = c->B, M = c->M, L = q.n_levels;
+    int rc;
+    double* wtab = c->d_pf[vgpa_ctx::PF_WTAB];
+    double* less = c->d_pf[vgpa_ctx::PF_LESS];
+    uint64_t* qtab = reinterpret_cast<uint64_t*>(c->d_pf[vgpa_ctx::PF_QTAB]);
+    uint64_t* qfin = reinterpret_cast<uint64_t*>(c->d_pf[vgpa_ctx::PF_QFIN]);
+    unsigned long long* mass = reinterpret_cast<unsigned long long*>(c->d_pf[vgpa_ctx::PF_MASS]);
+    const size_t n_mass = (size_t)B * n_keep * c->D * ((size_t)L + 1);
+    if ((rc = upload(c, c->d_pf[vgpa_ctx::PF_MGL], q.mg_levels, (size_t)B * c->D * L))) return rc;
+    HIP_TRY(c, hipMemsetAsync(less, 0, (size_t)B * rows * sizeof(double), c->stream));
+    LAUNCH_TRY(c, "descendant weights launch", launch_pf_descend(f, rows, wtab, less, c->stream));
+    LAUNCH_TRY(c, "weight quantisation launch", launch_pf_quantise(f, rows, wtab, qtab, qfin, c->stream));
+    LAUNCH_TRY(c, "integer descendant weights launch", launch_pf_descend_q(f, rows, qtab, c->stream));
+    HIP_TRY(c, hipMemsetAsync(mass, 0, n_mass * sizeof(uint64_t), c->stream));
+    cur = c->d_pf[vgpa_ctx::PF_XA]; other = c->d_pf[vgpa_ctx::PF_XB];
+    PfArgs g = f;
+    g.x = cur; g.ws = other; g.lw = c->d_pf[vgpa_ctx::PF_CUM]; g.st_in = nullptr; g.st_out = nullptr;
+    LAUNCH_TRY(c, "particle start launch", launch_pf_start(g, c->stream));
+    SampleArgs w = a;
+    w.stride = q.stride; w.n_keep = n_keep; w.seg_first = 1; w.pf_stats = nullptr; w.pf_rows = rows;
+    const MarginalArgs mg{c->d_pf[vgpa_ctx::PF_MGL], L, qtab, mass};
+    if ((rc = cuts(Walk::ReplayMarginals, "marginals replay launch", w, "replay gather launch", [&](int k) {
+          g.k = k; g.x_in = cur; g.x_out = other;
+          return launch_pf_gather(g, c->stream);
+        }, nullptr, nullptr, nullptr, &mg))) return rc;
+    if ((rc = download(c, q.mass, reinterpret_cast<const uint64_t*>(mass), n_mass))) return rc;
+    if (q.qfinal && (rc = download(c, q.qfinal, reinterpret_cast<const uint64_t*>(qfin), (size_t)B * q.n_paths))) return rc;
+    if (q.lineage_ess)      // (as in moments())
       for (int p = 0; p < (rows == M + 1 ? 1 : B); p++)
         if ((rc = download(c, q.lineage_ess + (size_t)p * (M + 1), less + (size_t)p * rows, rows == M + 1 ? (size_t)B * rows : (size_t)M + 1))) return rc;
     return VGPA_OK;
@@ -1944,6 +1986,13 @@ static int particle_run(vgpa_ctx* c, const ParticleRequest& q) {
     if (covariance && !(pf_flat_grid_fits((size_t)B * kept * D * D) && pf_flat_grid_fits((size_t)B * kept * sample_cov_len(D))))
       return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing covariances are built for at most 2^39 - 256 entries (batch %d, %d kept grid indices, D = %d): use a larger stride",
                   B, kept, D);
+    if (q.behind == Behind::Marginals) {      // (the replay; one launch-sized array of masses)
+      if (n_paths > sample_max_paths(D))
+        return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing marginals are built for at most %d particles per problem at D = %d (n_paths = %d)", sample_max_paths(D), D, n_paths);
+      if (!pf_flat_grid_fits((size_t)B * kept * D * ((size_t)q.n_levels + 1)))
+        return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing marginals are built for at most 2^39 - 256 entries of mass (batch %d, %d kept grid indices, D = %d, %d levels): use a larger stride",
+                    B, kept, D, q.n_levels);
+    }
     if (q.table() && !sample_lineages_fit(D, B, n_draw))      // (the lineage walk; the number is the matrix-core walk's, above D = 4)
       return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing trajectories are built for at most %d per problem at D = %d (n_draw = %d)", sample_max_paths(kMaxSmallD), D, n_draw);
     if (q.behind == Behind::Backward && !pf_backward_fits(n_draw))      // (the one launch of the backward simulation)
@@ -1951,7 +2000,7 @@ static int particle_run(vgpa_ctx* c, const ParticleRequest& q) {
     if (q.table() && (rc = check_stored(c, n_draw, kept, "smoothing trajectories", "trajectories", "grid indices"))) return rc;
   }
   ParticleRun r{c, q};
-  if ((rc = r.setup()) || (rc = r.filter()) || (q.sums() && (rc = r.moments())) || (q.table() && (rc = r.trajectories()))) return rc;
+  if ((rc = r.setup()) || (rc = r.filter()) || (q.sums() && (rc = r.moments())) || (q.behind == Behind::Marginals && (rc = r.marginals())) || (q.table() && (rc = r.trajectories()))) return rc;
   const size_t n = (size_t)n_paths, BnD = (size_t)B * n * D;
   if (q.fc_moments) {      // (the filter's final cloud leaves before the forecast carries it on in place)
     if ((rc = download(c, q.state, r.cur, BnD))) return rc;
@@ -2032,6 +2081,27 @@ int vgpa_particle_covariance(vgpa_ctx* c, const double* x, const double* x0, int
   if (!mean || !second) return fail(c, VGPA_ERR_ARG, "null argument");
   ParticleRequest q{x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled};
   q.stride = stride; q.behind = Behind::Covariance; q.cov_mean = mean; q.cov_second = second; q.lineage_ess = lineage_ess;
+  return particle_run(c, q);
+}
+
+// The smoothing marginals on the grid as exact integer histograms over a ladder of levels (see vgpa_hip.h)
+int vgpa_particle_marginals(vgpa_ctx* c, const double* x, const double* x0, int32_t n_paths, int32_t stride, uint64_t seed, double ess_fraction,
+                            const double* prior_mu, const double* prior_tau, const double* levels, int32_t n_levels, double* logw, double* state,
+                            uint64_t* mass, uint64_t* qfinal, double* lineage_ess, double* ess, int32_t* resampled) {
+  if (!c) return VGPA_ERR_ARG;
+  if (!levels || !mass) return fail(c, VGPA_ERR_ARG, "null argument");
+  if (n_levels < 1 || n_levels > kMaxMarginalLevels) return fail(c, VGPA_ERR_ARG, "n_levels must lie in [1, %d] (n_levels = %d)", kMaxMarginalLevels, n_levels);
+  if (stride < 1) return fail(c, VGPA_ERR_ARG, "stride must be at least 1 (stride = %d)", stride);
+  for (size_t e = 0; e < (size_t)c->B * c->D; e++) {
+    const double* lad = levels + e * n_levels;
+    for (int l = 0; l < n_levels; l++) {
+      if (!std::isfinite(lad[l])) return fail(c, VGPA_ERR_ARG, "levels must be finite (problem %zu, component %zu, level %d)", e / c->D, e % c->D, l);
+      if (l > 0 && !(lad[l - 1] < lad[l]))
+        return fail(c, VGPA_ERR_ARG, "levels must be strictly increasing (problem %zu, component %zu, level %d)", e / c->D, e % c->D, l);
+    }
+  }
+  ParticleRequest q{x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled};
+  q.stride = stride; q.behind = Behind::Marginals; q.mg_levels = levels; q.n_levels = n_levels; q.mass = mass; q.qfinal = qfinal; q.lineage_ess = lineage_ess;
   return particle_run(c, q);
 }
 

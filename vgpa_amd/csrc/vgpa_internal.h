@@ -222,9 +222,9 @@ struct ReduceArgs {
   const double* div_v;      // [B] per-problem div (1-D models: sigma_p), or nullptr
 };
 
-// Euler-Maruyama sample paths (sample.hip): x_k = x_{k-1} + dt drift_{k-1}(x_{k-1}) + R xi_k on the context's grid.  The eleven things a launch
+// Euler-Maruyama sample paths (sample.hip): x_k = x_{k-1} + dt drift_{k-1}(x_{k-1}) + R xi_k on the context's grid.  The twelve things a launch
 // can do with them (the table at the top of sample.hip); the host names one at every launch_sample_walk, and SampleArgs says what each reads
-enum class Walk { Plain, Weighted, Segment, SegmentStats, Replay, Lineage, Forecast, ReplayCov, Backward, Conditional, SegmentEvents };
+enum class Walk { Plain, Weighted, Segment, SegmentStats, Replay, Lineage, Forecast, ReplayCov, Backward, Conditional, SegmentEvents, ReplayMarginals };
 struct SampleArgs {
   int kind, model, D, Np, batch, n_paths, stride, n_keep;
   double dt;
@@ -300,12 +300,23 @@ struct SampleArgs {
   // at every step k of the segment X_j = fmax(X_j, g_j(x_k)) and, where g_j(x_k) > 0, T_j = min(T_j, k), N_j += 1 (T, N: exact integers
   // held as doubles).  The levels c and the sides s are ev_level [B][D] and ev_side [B][D] (+1 / -1), the last arguments of
   // launch_sample_walk and no fields here
+  // Walk::ReplayMarginals (vgpa_particle_marginals): Walk::Replay's states, every field as there but pf_wtab and pf_part,
+  // which stay nullptr: at a kept grid index k' stride slot i adds its integer descendant weight Q_i (MarginalArgs::qtab, the row of the
+  // problem's stretch) to mass[p][k'][d][bin(x_i[d])] for every component d, bin(x) = #{l: c_l < x} over the component's ladder of L levels
 };
+// The levels, weights and result of Walk::ReplayMarginals: the last argument of launch_sample_walk and no fields of SampleArgs
+struct MarginalArgs {
+  const double* levels;            // [B][D][L], finite and strictly increasing along L
+  int L;                           // 1 .. kMaxMarginalLevels
+  const uint64_t* qtab;            // [B][pf_rows][n_paths] integer descendant weights
+  unsigned long long* mass;        // [B][n_keep][D][L + 1], zero before the first segment
+};
+constexpr int kMaxMarginalLevels = 63;
 // hipErrorInvalidValue where a field the walk reads is missing or out of range, where a field that belongs to another walk is set (pf_ref
-// in every walk but Conditional, which needs it; ev_level and ev_side in every walk but SegmentEvents, which needs both), and for D = 2 in
-// every walk but Plain (no stochastic model has D = 2)
+// in every walk but Conditional, which needs it; ev_level and ev_side in every walk but SegmentEvents, which needs both; mg in every walk but ReplayMarginals, which
+// needs it whole), and for D = 2 in every walk but Plain (no stochastic model has D = 2)
 hipError_t launch_sample_walk(Walk w, const SampleArgs& a, hipStream_t st, const double* pf_ref = nullptr, const double* ev_level = nullptr,
-                              const int32_t* ev_side = nullptr);
+                              const int32_t* ev_side = nullptr, const MarginalArgs* mg = nullptr);
 // workgroups per problem of a segment launch: the blocks of the replay's partial sums
 int sample_segment_blocks(int D, int n_paths);
 int sample_max_paths(int D);      // the largest n_paths per problem a segment, replay or forecast launch takes at this D (grid.y)
@@ -369,6 +380,11 @@ hipError_t launch_pf_events_cdf(int D, int batch, int n_paths, int Np, int strid
 // through the stored ancestors, less [B][rows] the lineage ESS of the rows written (the others stay as they are); gather is the step
 // between two segments of the replay, x_out_i = x_in_{h_anc[p][j][i]} at the problem's observation j with t_j = k, a copy without one
 hipError_t launch_pf_descend(const PfArgs& a, int rows, double* wtab, double* less, hipStream_t st);
+// vgpa_particle_marginals (sample.hip: k_pf_quantise, k_pf_descend_q).  quantise, behind launch_pf_descend: row c of qtab
+// [B][rows][n_paths] = (uint64) trunc(W 2^62) of row c of wtab, and the same values densely to qfinal [B][n_paths].  descend_q: rows c-1 .. 0 of qtab by launch_pf_descend's recursion -- the
+// same bisections on the stored ancestors -- in 64-bit integer arithmetic
+hipError_t launch_pf_quantise(const PfArgs& a, int rows, const double* wtab, uint64_t* qtab, uint64_t* qfinal, hipStream_t st);
+hipError_t launch_pf_descend_q(const PfArgs& a, int rows, uint64_t* qtab, hipStream_t st);
 hipError_t launch_pf_gather(const PfArgs& a, hipStream_t st);
 // vgpa_particle_paths (sample.hip: k_pf_pick, k_pf_trace).  table [B][rows][K] int32, rows > every problem's observation count c.  pick
 // reads lw, seed and the counts and overwrites cum: row c gets the final slots of K trajectories, by systematic resampling from the final

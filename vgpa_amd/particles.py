@@ -36,6 +36,12 @@ SmoothingCovariance: one problem's record of vgpa_particle_covariance (DESIGN.md
     E[x_k x_k^T | y] ~ sum_i W^{j(k)}_i x_i(k) x_i(k)^T,
 the full matrix the variational S_t is held against, under the same genealogy and with the same caveat.
 
+SmoothingMarginals: one problem's record of vgpa_particle_marginals -- the marginal law of x_k[d] | y itself under the
+same genealogy, as a histogram over a ladder of levels per component: bin(x) = #{l: levels_l < x}, and the mass of a bin is the sum of
+the integer weights Q = the descendants' share of q_i = trunc(W_i 2^62) of the lineages whose state falls into it.  Integer sums do not
+depend on any order of addition: the record is exact, the CDF on the ladder non-decreasing by construction.  From it: whether a marginal
+is bimodal (modes), its quantiles and bands against m_t +- 1.64 sqrt(S_t), and P(x_k[d] > c | y) along the window (exceedance).
+
 SmoothingPaths: one problem's record of vgpa_particle_paths -- K whole trajectories on the time grid from the same
 genealogy, for what is no mean or variance: exceedance and first-passage probabilities, plots of posterior draws, predictive checks.  A
 trajectory is the lineage of one final slot; the final slots are drawn from the final weights by systematic resampling (equally weighted
@@ -59,7 +65,7 @@ model whatever the proposal (A_t, b_t) and for any number of particles >= 2: the
 """
 import numpy as np
 
-__all__ = ["ParticleFilterResult", "PathStatistics", "PathEvents", "SmoothingMoments", "SmoothingCovariance", "SmoothingPaths", "Forecast", "GibbsChain", "descendant_weights",
+__all__ = ["ParticleFilterResult", "PathStatistics", "PathEvents", "SmoothingMoments", "SmoothingCovariance", "SmoothingMarginals", "gaussian_ladder", "SmoothingPaths", "Forecast", "GibbsChain", "descendant_weights",
            "path_rows", "theta_conditional", "theta_draw"]
 
 
@@ -436,6 +442,125 @@ class SmoothingCovariance(_GenealogySums):
             raise ValueError(f" SmoothingCovariance: grid index {k} is not kept (stride {self.stride}, n_pts {self.n_pts}).")
         i = k // self.stride
         return self._vec(self._mean[i].copy()), self._mat(self._cov()[i])
+
+
+def gaussian_ladder(mt, st, n_levels=31, width=4.0):
+    """(D, n_levels): per component a uniform ladder from min_k (m - width sqrt(S)) to max_k (m + width sqrt(S)) of a Gaussian posterior on the
+    grid.  mt (Np, D) or (Np,): the means; st (Np, D, D), (Np, D) or (Np,): the covariance matrices or the variances."""
+    m = np.asarray(mt, dtype=float)
+    m = m.reshape(m.shape[0], -1)
+    v = np.asarray(st, dtype=float)
+    v = np.diagonal(v, axis1=1, axis2=2) if v.ndim == 3 else v.reshape(v.shape[0], -1)
+    n_levels, width = int(n_levels), float(width)
+    if v.shape != m.shape or n_levels < 1 or not width > 0.0:
+        raise ValueError(" gaussian_ladder: mt (Np, D) and st (Np, D, D) or (Np, D) must belong together, n_levels >= 1, width > 0.")
+    sd = np.sqrt(np.maximum(v, 0.0))
+    lo, hi = np.min(m - width * sd, axis=0), np.max(m + width * sd, axis=0)
+    if n_levels == 1:
+        return (0.5 * (lo + hi))[:, None]
+    out = lo[:, None] + (hi - lo)[:, None] * (np.arange(n_levels) / (n_levels - 1.0))[None, :]
+    out[:, -1] = hi      # (the ends as computed: the ladder covers m +- width sqrt(S) to the bit)
+    return out
+
+
+def posterior_ladders(ctx, n_levels=31, width=4.0):
+    """(B, D, n_levels): gaussian_ladder of every problem's Gaussian posterior (m_t, S_t) as the context `ctx` holds it from its last
+    evaluation of F (fetched; the cached state stays as it is)"""
+    mt = np.asarray(ctx.fetch("mt"), dtype=float).reshape(ctx.B, ctx.Np, ctx.D)
+    st = np.asarray(ctx.fetch("st"), dtype=float).reshape(ctx.B, ctx.Np, ctx.D, ctx.D)
+    return np.stack([gaussian_ladder(mt[p], st[p], n_levels, width) for p in range(ctx.B)])
+
+
+class SmoothingMarginals(_GenealogySums):
+    """log_w (n,): the final unnormalised log-weights; levels (D, L): per component a strictly increasing ladder; mass (n_keep, D, L + 1)
+    uint64: the integer weight of the lineages whose component d lies in bin b = #{l: levels[d, l] < x} at the grid indices k = 0, stride,
+    ... < n_pts; q_final (n,) uint64: trunc(W 2^62) of the final weights; obs_t, lineage_ess, ess, resampled as in SmoothingMoments.
+    single_dim: a 1-D model, the component axis of cdf / hist / exceedance / quantile / band / modes is dropped."""
+
+    def __init__(self, log_w, levels, mass, q_final, stride, n_pts, obs_t, lineage_ess, ess=(), resampled=(), single_dim=False) -> None:
+        self._take_weights(log_w)
+        n_keep = self._take_grid(stride, n_pts)
+        self.levels = np.asarray(levels, dtype=float)
+        if self.levels.ndim != 2 or self.levels.shape[1] < 1 or not np.all(self.levels[:, 1:] > self.levels[:, :-1]):
+            raise ValueError(" SmoothingMarginals: levels must be (D, L), strictly increasing along L.")
+        self.mass = np.asarray(mass)
+        if self.mass.dtype != np.uint64 or self.mass.shape != (n_keep,) + (self.levels.shape[0], self.levels.shape[1] + 1):
+            raise ValueError(" SmoothingMarginals: mass must be uint64 (n_keep, D, L + 1).")
+        self.q_final = np.asarray(q_final, dtype=np.uint64).ravel()
+        if self.q_final.size != self.log_w.size:
+            raise ValueError(" SmoothingMarginals: q_final must hold one weight per particle.")
+        self._take_stretches(obs_t, lineage_ess, ess, resampled)
+        self.single_dim = bool(single_dim)
+
+    def _shape(self, a, axis=1):
+        return np.take(a, 0, axis=axis) if self.single_dim else a
+
+    def total(self):
+        """(n_keep, D) uint64: the sum over the bins, in integer arithmetic -- the same for every component and every kept index of a stretch"""
+        return self._shape(self.mass.sum(axis=2, dtype=np.uint64))
+
+    def _cdf(self):
+        cum = np.cumsum(self.mass, axis=2, dtype=np.uint64)
+        return cum[:, :, :-1].astype(float) / cum[:, :, -1:].astype(float)
+
+    def cdf(self):
+        """(n_keep, D, L): P(x_k[d] <= levels[d, l] | y), the exact integer prefix sums over the total: non-decreasing in l, within [0, 1]"""
+        return self._shape(self._cdf())
+
+    def hist(self):
+        """(n_keep, D, L + 1): the probability of every bin"""
+        return self._shape(self.mass.astype(float) / self.mass.sum(axis=2, dtype=np.uint64).astype(float)[:, :, None])
+
+    def exceedance(self, level_index):
+        """(n_keep, D): P(x_k[d] > levels[d, level_index] | y) = 1 - cdf"""
+        return self._shape(1.0 - self._cdf()[:, :, range(self.levels.shape[1])[int(level_index)]])
+
+    def _quantile(self, q):
+        q = float(q)
+        if not 0.0 <= q <= 1.0:
+            raise ValueError(" SmoothingMarginals: q must lie in [0, 1].")
+        cdf, lev = self._cdf(), self.levels
+        n_levels = lev.shape[1]
+        out = np.empty(cdf.shape[:2])
+        for d in range(lev.shape[0]):
+            for k in range(cdf.shape[0]):
+                c = cdf[k, d]
+                hi = int(np.searchsorted(c, q, side="left"))      # the first level whose cdf reaches q
+                if hi == 0:
+                    out[k, d] = lev[d, 0] if q == c[0] else -np.inf
+                elif hi == n_levels:
+                    out[k, d] = np.inf
+                elif c[hi] == q:
+                    out[k, d] = lev[d, hi]
+                else:
+                    out[k, d] = lev[d, hi - 1] + (lev[d, hi] - lev[d, hi - 1]) * (q - c[hi - 1]) / (c[hi] - c[hi - 1])
+        return out
+
+    def quantile(self, q):
+        """(n_keep, D): the q-quantile of every marginal, linear inside the pair of levels that brackets it; -inf / +inf where q lies in the
+        open bin below the first / above the last level"""
+        return self._shape(self._quantile(q))
+
+    def band(self, lo=0.05, hi=0.95):
+        """(quantile(lo), quantile(hi)): e.g. the 5 % and 95 % quantiles, to hold against m_t -+ 1.64 sqrt(S_t)"""
+        if not float(lo) <= float(hi):
+            raise ValueError(" SmoothingMarginals: lo must not exceed hi.")
+        return self.quantile(lo), self.quantile(hi)
+
+    def modes(self, k):
+        """(D,) int: the number of interior local maxima of the bin density mass / bin width at the grid index k, which must be a kept one
+        (ValueError otherwise): a maximal run of equal densities counts once, where it is higher than both its neighbours; the two open end
+        bins have no width and count as density 0.  2 or more: the marginal is multimodal on this ladder."""
+        k = int(k)
+        if k < 0 or k >= self.n_pts or k % self.stride:
+            raise ValueError(f" SmoothingMarginals: grid index {k} is not kept (stride {self.stride}, n_pts {self.n_pts}).")
+        dens = self.mass[k // self.stride, :, 1:-1].astype(float) / np.diff(self.levels, axis=1)
+        out = np.zeros(self.levels.shape[0], dtype=int)
+        for d in range(out.size):
+            row = np.concatenate(([0.0], dens[d], [0.0]))
+            row = row[np.concatenate(([True], row[1:] != row[:-1]))]      # runs of equal densities: one entry each
+            out[d] = int(np.sum((row[1:-1] > row[:-2]) & (row[1:-1] > row[2:])))
+        return out[0] if self.single_dim else out
 
 
 class SmoothingPaths(_WalkRecord, _KeptGrid):

@@ -289,6 +289,34 @@ class VarGP(object):
         return self._particle_call("particle_covariance", lambda res, k: self._covariance_record(res, k, stride), n_paths, seed, stride=stride,
                                    ess_fraction=ess_fraction, x=x, x0=x0)
 
+    def _marginals_record(self, res, k, levels, stride, obs_t=None):
+        """One problem's SmoothingMarginals from row k of Context.particle_marginals' dict, cut to its own observations obs_t"""
+        from .particles import SmoothingMarginals
+        t = np.asarray(self._inputs()["obs_t"] if obs_t is None else obs_t).ravel()
+        return SmoothingMarginals(res["log_w"][k], levels, res["mass"][k], res["q_final"][k], stride, self.dim_n, t, res["lineage_ess"][k, :t.size + 1],
+                                  res["ess"][k, :t.size], res["resampled"][k, :t.size], self.model.single_dim)
+
+    def _gaussian_ladders(self, x, n_levels, width):
+        """(ladders (batch, D, n_levels), None): particles.posterior_ladders of the Gaussian posterior at x -- F is evaluated at x first, so
+        that the call behind it reads the cached state -- or, x=None, of the last free_energy.  (ProblemBatch's free_energy stacks x.)"""
+        from .particles import posterior_ladders
+        if x is not None:
+            self.free_energy(x)
+        return posterior_ladders(self._context(), n_levels, width), None
+
+    def particle_marginals(self, n_paths, seed, levels=None, stride=1, ess_fraction=0.5, x=None, x0=None, n_levels=31, width=4.0):
+        """The smoothing marginals on the time grid from particle_filter with the same arguments: a particles.SmoothingMarginals (with
+        batch > 1 a list, one per problem) -- per component a histogram of x_k | y over a ladder of levels at the grid indices 0, stride,
+        ..., counted on the device in integer arithmetic (no path is stored or copied): cdf(), hist(), exceedance(), quantile(), band() and
+        modes().  levels: (L,), (D, L) or (batch, D, L), strictly increasing, L <= 63; None: per component n_levels uniform levels over
+        m_t -+ width sqrt(S_t) of the Gaussian posterior at x (particles.gaussian_ladder).  What m_t and S_t cannot say: whether the
+        marginal is bimodal, and where its quantiles lie against m_t -+ 1.64 sqrt(S_t)."""
+        if levels is None:
+            levels, x = self._gaussian_ladders(x, n_levels, width)
+        return self._particle_call("particle_marginals", lambda res, k, lev: self._marginals_record(res, k, lev[k], stride), n_paths, seed, levels,
+                                   stride=stride, ess_fraction=ess_fraction, x=x, x0=x0,
+                                   late=lambda: (self._context()._ladder_input(levels)[0],))
+
     def _paths_record(self, res, k, stride, drawn, obs_t=None, method="genealogy"):
         """One problem's SmoothingPaths from row k of Context.particle_paths' (or particle_backward_paths') dict, cut to its own observations obs_t"""
         from .particles import SmoothingPaths
