@@ -105,11 +105,10 @@ static void walk(const SampleArgs& a) {
       a.n_paths, a.stride, a.n_keep, a.seg_first, a.k_begin, a.k_end, a.pf_rows, a.pf_M, a.pf_slot_rows, a.pf_n, W(a.x0), W(a.out), W(a.logw), W(a.start), W(a.pf_x),
       W(a.pf_lw), W(a.pf_stats), W(a.pf_wtab), W(a.pf_part), W(a.pf_slots), W(a.pf_clouds), W(a.pf_hanc), W(a.A), W(a.b), W(a.R), W(a.theta_v));
 }
-hipError_t launch_sample_walk(Walk w, const SampleArgs& a, hipStream_t, const double* pf_ref, const double* ev_level, const int32_t* ev_side,
-                              const MarginalArgs* mg) {
-  rec("launch sample_walk walk %d pf_ref %s ev_level %s ev_side %s", (int)w, W(pf_ref), W(ev_level), W(ev_side));
+hipError_t launch_sample_walk(Walk w, const SampleArgs& a, hipStream_t, const WalkOwn& own) {
+  rec("launch sample_walk walk %d pf_ref %s ev_level %s ev_side %s", (int)w, W(own.pf_ref), W(own.ev_level), W(own.ev_side));
   walk(a);
-  if (mg) rec("       levels %s L %d qtab %s mass %s", W(mg->levels), mg->L, W(mg->qtab), W(mg->mass));      // (Walk::ReplayMarginals alone)
+  if (const MarginalArgs* mg = own.mg) rec("       levels %s L %d qtab %s mass %s", W(mg->levels), mg->L, W(mg->qtab), W(mg->mass));      // (Walk::ReplayMarginals alone)
   return hipSuccess;
 }
 int sample_segment_blocks(int, int n_paths) { return (n_paths + 63) / 64; }

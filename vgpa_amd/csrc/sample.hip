@@ -11,6 +11,7 @@
 // depends on the launch geometry.
 // K is the walk (vgpa_internal.h), stated by the host at every launch_sample_walk; every walk but Forecast runs on k_sample_small and
 // k_sample_mfma:
+// (the properties the kernels branch on for each walk: kWalkTraits below)
 //   walk         | what it computes; [the kernels and k_pf_* steps that serve it besides those two]                                 | DESIGN.md
 //   Plain        | the paths, every stride-th point stored  [k_sample_l96]                                                          | s.4.8
 //   Weighted     | the same paths and, summed where the path is made, the log-ratio of the model SDE's path density to the          | s.4.9
@@ -179,30 +180,41 @@ template <> struct WalkArgsOf<Walk::SegmentEvents> { using type = EventArgs; };
 template <> struct WalkArgsOf<Walk::ReplayMarginals> { using type = MarginalWalkArgs; };
 template <Walk K> using WalkArgs = typename WalkArgsOf<K>::type;
 
-// What the two kernels branch on, per walk: W the walk of the weighted kind (posterior drift, diagonal R), SEG it runs (k_begin, k_end] from
-// and to pf_x, ST it carries the rows of pf_stats, MO it takes the moments of the replay, LN the counter words come from pf_slots;
-// FC it is the forecast (the model's drift from the cloud in pf_x, k_sample_small only); CV the replay's second moments are the whole matrix
-// (with MO); BW: the state is reloaded from the filter's histories behind every observation (with LN); CD: slot 0 is pinned to pf_ref of
-// ConditionalArgs (with SEG); EV: it carries the event records of EventArgs' levels and sides in the rows of pf_stats (with SEG); MG: at a
-// kept index the replay adds MarginalWalkArgs' integer weights to the bins of its states and forms no sum (with MO); WS: the weight sums
-// are formed.  The twelve rows are all there is: no other combination can be instantiated.
+// What the two kernels branch on, per walk.  Four properties a walk has or has not, and three choices that exclude one another by type:
+//   weighted   the walk of the weighted kind (posterior drift, diagonal R)
+//   segment    it runs (k_begin, k_end] from and to pf_x
+//   forecast   the model's drift from the cloud in pf_x (k_sample_small only)
+//   pinned     slot 0 is pinned to pf_ref of ConditionalArgs (a segment)
+//   carry      the [3][D] row a slot carries in pf_stats (a segment): Carry::Stats the path statistics, Carry::Events the event records of
+//              EventArgs' levels and sides
+//   kept       what happens at a kept grid index (a segment launched as the replay): Kept::Moments the sums of W x and W x^2, Kept::Covariance
+//              of W x and the whole W x x^T, Kept::Marginals MarginalWalkArgs' integer weights added to the bins of the states, no sum formed
+//   words      where the counter words come from: Words::Own the lane's own index, Words::Table pf_slots, Words::TableReload pf_slots with the
+//              state reloaded from the filter's histories behind every observation
+// and, derived, WS(): the weight sums are formed.  The twelve rows are all there is: no other combination can be instantiated.
+enum class Kept { None, Moments, Covariance, Marginals };      // (the words of the host's Behind for the same passes)
+enum class Words { Own, Table, TableReload };
 struct WalkTraits {
-  bool W, SEG, ST, MO, LN, FC, CV, BW, CD, EV, MG;
-  constexpr bool WS() const { return W && !MO; }
+  bool weighted = false, segment = false, forecast = false, pinned = false;
+  Carry carry = Carry::None;
+  Kept kept = Kept::None;
+  Words words = Words::Own;
+  constexpr bool WS() const { return weighted && kept == Kept::None; }
+  constexpr bool by_problem() const { return kept != Kept::None || forecast; }      // launched with the problem in grid.x, the slots in grid.y
 };
 constexpr WalkTraits kWalkTraits[] = {      // in the order of Walk
-    {false, false, false, false, false, false},    // Plain
-    {true,  false, false, false, false, false},    // Weighted
-    {true,  true,  false, false, false, false},    // Segment
-    {true,  true,  true,  false, false, false},    // SegmentStats
-    {true,  true,  false, true,  false, false},    // Replay
-    {false, false, false, false, true,  false},    // Lineage
-    {false, false, false, false, false, true},     // Forecast
-    {true,  true,  false, true,  false, false, true},     // ReplayCov
-    {false, false, false, false, true,  false, false, true},     // Backward
-    {true,  true,  false, false, false, false, false, false, true},     // Conditional
-    {true,  true,  false, false, false, false, false, false, false, true},    // SegmentEvents
-    {true,  true,  false, true,  false, false, false, false, false, false, true}};    // ReplayMarginals
+    /* Plain           */ {},
+    /* Weighted        */ {.weighted = true},
+    /* Segment         */ {.weighted = true, .segment = true},
+    /* SegmentStats    */ {.weighted = true, .segment = true, .carry = Carry::Stats},
+    /* Replay          */ {.weighted = true, .segment = true, .kept = Kept::Moments},
+    /* Lineage         */ {.words = Words::Table},
+    /* Forecast        */ {.forecast = true},
+    /* ReplayCov       */ {.weighted = true, .segment = true, .kept = Kept::Covariance},
+    /* Backward        */ {.words = Words::TableReload},
+    /* Conditional     */ {.weighted = true, .segment = true, .pinned = true},
+    /* SegmentEvents   */ {.weighted = true, .segment = true, .carry = Carry::Events},
+    /* ReplayMarginals */ {.weighted = true, .segment = true, .kept = Kept::Marginals}};
 
 // Walk::ReplayMarginals: the bin of x on a strictly increasing ladder of L levels, #{l: c_l < x}, by bisection on fp64 compares alone (at most 6
 // for L <= 63; a NaN compares false everywhere: bin 0), and the slot's weight added to that bin of row [L + 1]
@@ -215,43 +227,82 @@ __device__ __forceinline__ void marginal_add(const double* lev, int L, unsigned 
   atomicAdd(row + lo, qw);
 }
 
-// Weighted: posterior kind, diagonal R: both drifts at x_{k-1}, d = g - f, and per step -sum_i d_i (eta_i + dt d_i / 2) / Sigma_ii with
+// ---- the walks' rules, each stated once for both kernels ------------------------------------------------------------------------------
+// Carry::Events: behind step k, with d = x_j(k) - c_j (one subtraction) and g = d or -d by the side: X_j = fmax(X_j, g); where g > 0,
+// T_j = min(T_j, k) and N_j += 1
+__device__ __forceinline__ void event_step(double x, double level, bool below, int k, double& X, int& T, int& N) {
+  const double d = x - level, g = below ? -d : d;
+  X = fmax(X, g);
+  if (g > 0.0) { T = min(T, k); N += 1; }
+}
+// Carry::Stats: a step's r = dt d + eta (d = g - f) of one component: Q += r^2 / dt, G += phi r.  (H += dt phi^2 is k_sample_small's own:
+// with phi = 1 k_sample_mfma writes H as a constant.)
+__device__ __forceinline__ void stats_step(double dt, double d, double eta, double phi, double& Q, double& G) {
+  const double r = dt * d + eta;
+  Q += r * r / dt; G += phi * r;
+}
+// a slot's [3][D] carried row of pf_stats (Carry::Stats: Q, G, H; Carry::Events: X, T, N), slot = p n_paths + path: member m of component i
+__device__ __forceinline__ double& carried(const SampleArgs& a, size_t slot, int D, int m, int i) { return a.pf_stats[slot * 3 * D + m * D + i]; }
+// Words::TableReload: the particle slot `word` was copied from at observation j of problem p: pf_clouds[p][j][pf_hanc[p][j][word]]
+__device__ __forceinline__ const double* backward_source(const SampleArgs& a, uint32_t p, int j, uint32_t word, int D) {
+  const size_t hj = (size_t)p * a.pf_M + j;
+  return a.pf_clouds + (hj * a.pf_n + (size_t)a.pf_hanc[hj * a.pf_n + word]) * D;
+}
+// the replay: a segment lies in one stretch of its problem -- the observations behind it count the row of its weights in a table
+// [B][pf_rows][n_paths] (pf_wtab, mg_qtab): the entry of `path`
+template <class V>
+__device__ __forceinline__ V stretch_weight(const SampleArgs& a, const V* table, uint32_t p, int stretch, uint32_t path) {
+  return table[((size_t)p * a.pf_rows + stretch) * a.n_paths + path];
+}
+// the replay: the next kept grid index (a multiple of the stride) and its slot among the n_keep results
+struct KeptCursor {
+  long long k = 0, slot = 0;
+  __device__ __forceinline__ void first_behind(int k_begin, int stride) { slot = ((long long)k_begin + stride) / stride; k = slot * stride; }
+};
+// Kept::Marginals: component i of a state x_i at kept slot `slot` of problem p: the weight qw to its bin of mass[p][slot][i][L + 1], on the
+// ladder level[p][i][L]
+__device__ __forceinline__ const double* marginal_ladder(const MarginalWalkArgs& a, uint32_t p, int i, int D) { return a.mg_level + ((size_t)p * D + i) * a.mg_L; }
+__device__ __forceinline__ unsigned long long* mass_row(const MarginalWalkArgs& a, uint32_t p, long long slot, int i, int D) {
+  return a.mg_mass + (((size_t)p * a.n_keep + (size_t)slot) * D + i) * ((size_t)a.mg_L + 1);
+}
+
+// What each walk does in k_sample_small, by the property of kWalkTraits that brings it in.
+// Weighted (weighted): posterior kind, diagonal R: both drifts at x_{k-1}, d = g - f, and per step -sum_i d_i (eta_i + dt d_i / 2) / Sigma_ii with
 // 1 / Sigma_ii = dt / R_ii^2; the observation term at the lane's own problem's times.
-// Segment: the weighted walk over (k_begin, k_end] from and to pf_x, the sums added to pf_lw; nothing else is stored.
-// SegmentStats: a segment that adds its steps to the slot's row of pf_stats: Q_i += r^2 / dt, G_i += phi_i r, H_i += dt phi_i^2 with
-// r = dt d + eta.
-// Replay: a segment launched with the problem in blockIdx.x and 256 slots per workgroup.  The states only (no model drift, no sums, pf_lw
+// Segment (segment): the weighted walk over (k_begin, k_end] from and to pf_x, the sums added to pf_lw; nothing else is stored.
+// SegmentStats (Carry::Stats): a segment that adds its steps to the slot's row of pf_stats (carried): Q_i and G_i by stats_step,
+// H_i += dt phi_i^2.
+// Replay (Kept::Moments): a segment launched with the problem in blockIdx.x and 256 slots per workgroup.  The states only (no model drift, no sums, pf_lw
 // untouched); at a kept k the lanes' W x_i and (W x_i) x_i are added over the wave by a butterfly and over the four waves through four
 // LDS words per value (two sets, alternating: one barrier per kept k), in that fixed order.  A lane behind the last slot walks from 0
 // with the last slot's counters and weight 0 and stores nothing.
-// ReplayCov: the replay with D + D (D + 1) / 2 values per kept k in place of 2 D: W x_i, then (W x_a) x_b for b <= a by rows -- the same
+// ReplayCov (Kept::Covariance): the replay with D + D (D + 1) / 2 values per kept k in place of 2 D: W x_i, then (W x_a) x_b for b <= a by rows -- the same
 // butterfly, LDS words and order; the diagonal entries are the replay's own (W x_i) x_i.
-// Lineage: the unweighted posterior walk of lane m = `path`, whose counter word is not m but the entry of its column of pf_slots for the
+// Lineage (Words::Table): the unweighted posterior walk of lane m = `path`, whose counter word is not m but the entry of its column of pf_slots for the
 // stretch it is in: row 0 for the start, the next row each time the walk has completed an observation index of the lane's own problem (an
 // observation at index 0: before step 1).  No model drift, no sums.
-// Backward: the lineage walk, and where it changes its counter word -- behind the completed observation j of its problem, whose point has
-// been stored -- the state becomes pf_clouds[p][j][pf_hanc[p][j][s]], s the new word: the particle slot s was copied from (pf_hanc is the
-// identity where the cloud was carried on: the reload then changes no bit).
-// Forecast: launched as the replay is (the problem in blockIdx.x, 256 lanes per workgroup).  The model's drift alone, step h = 1 .. k_end -
+// Backward (Words::TableReload): the lineage walk, and where it changes its counter word -- behind the completed observation j of its problem,
+// whose point has been stored -- the state becomes backward_source's particle of the new word (pf_hanc is the identity where the cloud was
+// carried on: the reload then changes no bit).
+// Forecast (forecast): launched as the replay is (the problem in blockIdx.x, 256 lanes per workgroup).  The model's drift alone, step h = 1 .. k_end -
 // k_begin drawn at the absolute grid index k_begin + h, from the slot's state in pf_x.  The cloud launch (pf_part set): lane = slot, the
 // replay's sums with W = pf_wtab at h = 0, stride, ..., the end state back to pf_x.  The member launch (out, pf_slots set): lane m starts from
 // slot pf_slots[p][m], draws with that slot's word and stores as Plain stores.  A lane behind the last one walks the last one again with
 // weight 0 and stores nothing.
-// Conditional: a segment in which the lane of slot 0 holds x_{k-1} = pf_ref[p][k-1] bit for bit, draws nothing and puts
+// Conditional (pinned): a segment in which the lane of slot 0 holds x_{k-1} = pf_ref[p][k-1] bit for bit, draws nothing and puts
 // eta* = (ref_k - x_{k-1}) - dt g(x_{k-1}) where the other lanes put R xi: the step term, the observation term and the sums are the segment's; its
 // state becomes ref_k as loaded (D loads per step for that one lane).  Every other lane is the segment's, bit for bit.
-// SegmentEvents: a segment, bit for bit, that behind every step k holds d = x_j(k) - c_j (one subtraction), g = d or -d by the side, and
-// X_j = fmax(X_j, g); where g > 0, T_j = min(T_j, k) and N_j += 1.  The slot's row of pf_stats is read at the segment's entry and written at
+// SegmentEvents (Carry::Events): a segment, bit for bit, that behind every step k takes event_step for each component.  The slot's row of
+// pf_stats (carried) is read at the segment's entry and written at
 // its exit, T and N as the doubles the integers are; in between they are 32-bit integers.  (The row of grid index 0 is k_pf_events_start's.)
-// ReplayMarginals: the replay's launch, states and kept indices; no weight is a double and nothing is summed over lanes.  At a kept k a live
-// lane whose integer weight Q (the row of mg_qtab of the problem's stretch) is not 0 adds Q to mass[p][k'][i][bin(x_i)] for each of its
+// ReplayMarginals (Kept::Marginals): the replay's launch, states and kept indices; no weight is a double and nothing is summed over lanes.  At a
+// kept k a live lane whose integer weight Q (stretch_weight of mg_qtab) is not 0 adds Q to mass_row(p, k', i)[bin(x_i)] for each of its
 // components with one 64-bit integer atomic per component, the ladder read from global memory.  Integer addition is associative: the masses
 // do not depend on the order the atomics arrive in.
 // Walk::Backward: x = the particle slot `word` was copied from at observation j of problem p
 template <int D>
 __device__ __forceinline__ void backward_reload(const SampleArgs& a, uint32_t p, int j, uint32_t word, double* x) {
-  const size_t hj = (size_t)p * a.pf_M + j;
-  const double* src = a.pf_clouds + (hj * a.pf_n + (size_t)a.pf_hanc[hj * a.pf_n + word]) * D;
+  const double* src = backward_source(a, p, j, word, D);
 #pragma unroll
   for (int i = 0; i < D; i++) x[i] = src[i];
 }
@@ -259,12 +310,15 @@ __device__ __forceinline__ void backward_reload(const SampleArgs& a, uint32_t p,
 template <int D, Walk K>
 __global__ __launch_bounds__(256) void k_sample_small(WalkArgs<K> a) {
   constexpr WalkTraits T = kWalkTraits[(int)K];
-  constexpr bool W = T.W, SEG = T.SEG, ST = T.ST, MO = T.MO, LN = T.LN, FC = T.FC, CV = T.CV, BW = T.BW, CD = T.CD, EV = T.EV, MG = T.MG, WS = T.WS();
-  constexpr int NV = CV ? D + D * (D + 1) / 2 : 2 * D;      // values a kept k reduces
+  constexpr bool weighted = T.weighted, segment = T.segment, forecast = T.forecast, pinned = T.pinned, sums = T.WS();
+  constexpr Carry carry = T.carry;
+  constexpr Kept kept = T.kept;
+  constexpr bool table = T.words != Words::Own, replay = kept != Kept::None;
+  constexpr int NV = kept == Kept::Covariance ? D + D * (D + 1) / 2 : 2 * D;      // values a kept k reduces
   size_t gid;
   uint32_t p, path;
   bool live = true;
-  if constexpr (MO || FC) {
+  if constexpr (T.by_problem()) {
     const uint32_t slot = blockIdx.y * 256 + threadIdx.x;
     live = slot < (uint32_t)a.n_paths;
     p = blockIdx.x; path = live ? slot : (uint32_t)a.n_paths - 1;
@@ -276,8 +330,8 @@ __global__ __launch_bounds__(256) void k_sample_small(WalkArgs<K> a) {
   }
   uint32_t word = path;      // the counter word of the lane's draws
   const int32_t* lin = nullptr;
-  if constexpr (LN) { lin = a.pf_slots + (size_t)p * a.pf_slot_rows * a.n_paths + path; word = (uint32_t)lin[0]; }
-  if constexpr (FC) { if (a.pf_slots) word = (uint32_t)a.pf_slots[gid]; }
+  if constexpr (table) { lin = a.pf_slots + (size_t)p * a.pf_slot_rows * a.n_paths + path; word = (uint32_t)lin[0]; }
+  if constexpr (forecast) { if (a.pf_slots) word = (uint32_t)a.pf_slots[gid]; }
   const uint32_t k0 = (uint32_t)(a.seed & 0xffffffffu), k1 = (uint32_t)(a.seed >> 32);
   constexpr int NP = (D + 1) / 2;
   // kept points wait in LDS (slot-major, thread fastest: no conflicts) until NBUF of them -- 16 doubles for D = 1, 2, 4, 15 for D = 3 -- go out as
@@ -293,15 +347,12 @@ __global__ __launch_bounds__(256) void k_sample_small(WalkArgs<K> a) {
 #pragma unroll
     for (int i = 0; i < kMaxTheta; i++) th[i] = a.theta_v ? a.theta_v[(size_t)p * kMaxTheta + i] : a.theta[i];
   }
-  if constexpr (FC) {
+  if constexpr (forecast) {
 #pragma unroll
     for (int i = 0; i < D; i++) x[i] = a.pf_x[((size_t)p * a.pf_n + word) * D + i];
-  } else if constexpr (MO) {
+  } else if constexpr (segment) {
 #pragma unroll
-    for (int i = 0; i < D; i++) x[i] = live ? a.pf_x[gid * D + i] : 0.0;
-  } else if constexpr (SEG) {
-#pragma unroll
-    for (int i = 0; i < D; i++) x[i] = a.pf_x[gid * D + i];
+    for (int i = 0; i < D; i++) x[i] = !replay || live ? a.pf_x[gid * D + i] : 0.0;
   } else if (a.x0) {
 #pragma unroll
     for (int i = 0; i < D; i++) x[i] = a.x0[(size_t)p * D + i];
@@ -318,7 +369,7 @@ __global__ __launch_bounds__(256) void k_sample_small(WalkArgs<K> a) {
       x[i] = m0[i] + s;
     }
   }
-  const bool store = FC ? live && a.out != nullptr : !SEG && (!W || a.out != nullptr);
+  const bool store = forecast ? live && a.out != nullptr : !segment && (!weighted || a.out != nullptr);
   double* o = store ? a.out + gid * (size_t)a.n_keep * D : nullptr;
   if (store) {
 #pragma unroll
@@ -327,118 +378,110 @@ __global__ __launch_bounds__(256) void k_sample_small(WalkArgs<K> a) {
   }
   double isg[D], pw = 0.0, ow = 0.0;
   ObsCursor oc;
-  if constexpr (WS) {
+  if constexpr (sums) {
     oc = ObsCursor(a, p);
 #pragma unroll
     for (int i = 0; i < D; i++) {
       isg[i] = a.dt / (R[i * D + i] * R[i * D + i]);
-      if constexpr (!SEG) a.start[gid * D + i] = x[i];
+      if constexpr (!segment) a.start[gid * D + i] = x[i];
     }
-    if constexpr (SEG) { if (!a.seg_first) oc.skip_through(a.k_begin); }
+    if constexpr (segment) { if (!a.seg_first) oc.skip_through(a.k_begin); }
     if (oc.next == 0) { ow += obs_form<D>(a, p, oc.cur, x); oc.advance(); }
   }
-  if constexpr (LN) {
+  if constexpr (table) {
     oc = ObsCursor(a, p);
     if (oc.next == 0) {
       oc.advance(); word = (uint32_t)lin[(size_t)oc.cur * a.n_paths];
-      if constexpr (BW) backward_reload<D>(a, p, 0, word, x);
+      if constexpr (T.words == Words::TableReload) backward_reload<D>(a, p, 0, word, x);
     }
   }
-  // Replay: the segment lies in one stretch of its problem -- the observations behind it are oc.cur, the row of the weights
+  // the replay: the slot's weight of the segment's stretch (Kept::Marginals: the integer one), the first kept index behind k_begin
   double wt = 0.0;
   double* red = nullptr;
   int par = 0;
-  long long keep_k = 0, keep_slot = 0;
-  unsigned long long qw = 0;      // ReplayMarginals: the slot's integer weight
-  if constexpr (MG) {
+  KeptCursor next_kept;
+  unsigned long long qw = 0;
+  if constexpr (replay) {
     oc = ObsCursor(a, p);
     if (!a.seg_first) oc.skip_through(a.k_begin);
-    qw = live ? a.mg_qtab[((size_t)p * a.pf_rows + oc.cur) * a.n_paths + path] : 0ull;
-    keep_slot = ((long long)a.k_begin + a.stride) / a.stride;
-    keep_k = keep_slot * a.stride;
-  } else if constexpr (MO) {
-    __shared__ double red_lds[2 * NV * 4];
-    red = red_lds;
-    oc = ObsCursor(a, p);
-    if (!a.seg_first) oc.skip_through(a.k_begin);
-    wt = live ? a.pf_wtab[((size_t)p * a.pf_rows + oc.cur) * a.n_paths + path] : 0.0;
-    keep_slot = ((long long)a.k_begin + a.stride) / a.stride;      // the first kept index behind k_begin
-    keep_k = keep_slot * a.stride;
+    if constexpr (kept == Kept::Marginals) qw = live ? stretch_weight(a, a.mg_qtab, p, oc.cur, path) : 0ull;
+    else {
+      __shared__ double red_lds[2 * NV * 4];
+      red = red_lds;
+      wt = live ? stretch_weight(a, a.pf_wtab, p, oc.cur, path) : 0.0;
+    }
+    next_kept.first_behind(a.k_begin, a.stride);
   }
-  if constexpr (FC) {      // (keep_k counts steps: h = k + 1 behind step k of the loop below)
+  if constexpr (forecast) {      // (next_kept.k counts steps: h = k + 1 behind step k of the loop below)
     __shared__ double red_lds[2 * 2 * D * 4];
     red = red_lds;
     wt = live && a.pf_wtab ? a.pf_wtab[gid] : 0.0;
-    keep_slot = 1; keep_k = a.stride;
+    next_kept.slot = 1; next_kept.k = a.stride;
   }
-  auto count = [&](long long slot) {      // ReplayMarginals, in reduce's place
-    if constexpr (MG) {
+  // the action at a kept index, by the walk's `kept` (the forecast's cloud launch: the moments): Kept::Marginals counts, the others reduce
+  auto at_kept = [&](long long slot) {
+    if constexpr (kept == Kept::Marginals) {      // count: the slot's weight to the bin of each of its components
       if (qw != 0) {
 #pragma unroll
-        for (int i = 0; i < D; i++)
-          marginal_add(a.mg_level + ((size_t)p * D + i) * a.mg_L, a.mg_L,
-                       a.mg_mass + (((size_t)p * a.n_keep + (size_t)slot) * D + i) * ((size_t)a.mg_L + 1), x[i], qw);
+        for (int i = 0; i < D; i++) marginal_add(marginal_ladder(a, p, i, D), a.mg_L, mass_row(a, p, slot, i, D), x[i], qw);
       }
+    } else {      // reduce: the workgroup's sums over its slots, NV values
+      double v[NV];
+      if constexpr (kept == Kept::Covariance) {
+#pragma unroll
+        for (int i = 0; i < D; i++) v[i] = wt * x[i];
+#pragma unroll
+        for (int i = 0; i < D; i++)
+#pragma unroll
+          for (int j = 0; j <= i; j++) v[D + i * (i + 1) / 2 + j] = v[i] * x[j];
+      } else {
+#pragma unroll
+        for (int i = 0; i < D; i++) { v[i] = wt * x[i]; v[D + i] = v[i] * x[i]; }
+      }
+      double* r = red + par * 4 * NV;
+#pragma unroll
+      for (int e = 0; e < NV; e++) {
+        v[e] = wave_sum(v[e]);
+        if ((threadIdx.x & 63) == 0) r[e * 4 + (threadIdx.x >> 6)] = v[e];
+      }
+      __syncthreads();
+      if (threadIdx.x < NV) {
+        const double* q4 = r + threadIdx.x * 4;
+        a.pf_part[(((size_t)p * gridDim.y + blockIdx.y) * a.n_keep + (size_t)slot) * NV + threadIdx.x] = ((q4[0] + q4[1]) + q4[2]) + q4[3];
+      }
+      par ^= 1;
     }
   };
-  auto reduce = [&](long long slot) {
-    double v[NV];
-    if constexpr (CV) {
+  if constexpr (replay) { if (a.seg_first) at_kept(0); }
+  if constexpr (forecast) { if (a.pf_part) at_kept(0); }
+  constexpr bool stats = carry == Carry::Stats, events = carry == Carry::Events;
+  double sq[stats ? D : 1], sg1[stats ? D : 1], sh[stats ? D : 1], phi[stats ? D : 1];
+  if constexpr (stats) {
 #pragma unroll
-      for (int i = 0; i < D; i++) v[i] = wt * x[i];
-#pragma unroll
-      for (int i = 0; i < D; i++)
-#pragma unroll
-        for (int j = 0; j <= i; j++) v[D + i * (i + 1) / 2 + j] = v[i] * x[j];
-    } else {
-#pragma unroll
-      for (int i = 0; i < D; i++) { v[i] = wt * x[i]; v[D + i] = v[i] * x[i]; }
-    }
-    double* r = red + par * 4 * NV;
-#pragma unroll
-    for (int e = 0; e < NV; e++) {
-      v[e] = wave_sum(v[e]);
-      if ((threadIdx.x & 63) == 0) r[e * 4 + (threadIdx.x >> 6)] = v[e];
-    }
-    __syncthreads();
-    if (threadIdx.x < NV) {
-      const double* q4 = r + threadIdx.x * 4;
-      a.pf_part[(((size_t)p * gridDim.y + blockIdx.y) * a.n_keep + (size_t)slot) * NV + threadIdx.x] = ((q4[0] + q4[1]) + q4[2]) + q4[3];
-    }
-    par ^= 1;
-  };
-  if constexpr (MG) { if (a.seg_first) count(0); }
-  else if constexpr (MO) { if (a.seg_first) reduce(0); }
-  if constexpr (FC) { if (a.pf_part) reduce(0); }
-  double sq[ST ? D : 1], sg1[ST ? D : 1], sh[ST ? D : 1], phi[ST ? D : 1];
-  if constexpr (ST) {
-#pragma unroll
-    for (int i = 0; i < D; i++) {
-      sq[i] = a.pf_stats[gid * 3 * D + i]; sg1[i] = a.pf_stats[gid * 3 * D + D + i]; sh[i] = a.pf_stats[gid * 3 * D + 2 * D + i];
-    }
+    for (int i = 0; i < D; i++) { sq[i] = carried(a, gid, D, 0, i); sg1[i] = carried(a, gid, D, 1, i); sh[i] = carried(a, gid, D, 2, i); }
   }
-  double ec[EV ? D : 1], ex[EV ? D : 1];      // SegmentEvents: the levels, the slot's row; the sides as a bit per component
-  int et[EV ? D : 1], en[EV ? D : 1], eneg = 0;
-  if constexpr (EV) {
+  double ec[events ? D : 1], ex[events ? D : 1];      // Carry::Events: the levels, the slot's row; the sides as a bit per component
+  int et[events ? D : 1], en[events ? D : 1], eneg = 0;
+  if constexpr (events) {
 #pragma unroll
     for (int i = 0; i < D; i++) {
       ec[i] = a.ev_level[(size_t)p * D + i];
       eneg |= a.ev_side[(size_t)p * D + i] < 0 ? 1 << i : 0;
-      ex[i] = a.pf_stats[gid * 3 * D + i]; et[i] = (int)a.pf_stats[gid * 3 * D + D + i]; en[i] = (int)a.pf_stats[gid * 3 * D + 2 * D + i];
+      ex[i] = carried(a, gid, D, 0, i); et[i] = (int)carried(a, gid, D, 1, i); en[i] = (int)carried(a, gid, D, 2, i);
     }
   }
   const double* A = a.A + (size_t)p * a.stride_x;
   const double* bv = a.b + (size_t)p * a.stride_x;
   int until = a.stride, slot = 0;
   // (the forecast counts its steps from 0: k_begin + h may be the last index an int holds)
-  const int k_first = FC ? 0 : SEG ? a.k_begin + 1 : 1, k_stop = FC ? a.k_end - a.k_begin : SEG ? a.k_end + 1 : a.Np;
-  bool pin = false;      // Conditional: the lane of slot 0
+  const int k_first = forecast ? 0 : segment ? a.k_begin + 1 : 1, k_stop = forecast ? a.k_end - a.k_begin : segment ? a.k_end + 1 : a.Np;
+  bool pin = false;      // pinned: the lane of slot 0
   const double* ref = nullptr;
-  if constexpr (CD) { pin = path == 0; ref = a.pf_ref + (size_t)p * a.Np * D; }
+  if constexpr (pinned) { pin = path == 0; ref = a.pf_ref + (size_t)p * a.Np * D; }
   for (int k = k_first; k < k_stop; k++) {
     double f[D], fm[D];
-    if constexpr (WS) model_drift<D>(a.model, th, x, fm);
-    if (!FC && (W || LN || a.kind == VGPA_PATHS_POSTERIOR)) {
+    if constexpr (sums) model_drift<D>(a.model, th, x, fm);
+    if (!forecast && (weighted || table || a.kind == VGPA_PATHS_POSTERIOR)) {
       const double* Ak = A + (size_t)(k - 1) * D * D;
       const double* bk = bv + (size_t)(k - 1) * D;
 #pragma unroll
@@ -451,48 +494,37 @@ __global__ __launch_bounds__(256) void k_sample_small(WalkArgs<K> a) {
     } else {
       model_drift<D>(a.model, th, x, f);
     }
-    double xr[CD ? D : 1];      // Conditional: ref_k of the pinned lane
-    if constexpr (CD) {
+    double xr[pinned ? D : 1];      // pinned: ref_k of the pinned lane
+    if constexpr (pinned) {
 #pragma unroll
       for (int i = 0; i < D; i++) { xr[i] = pin ? ref[(size_t)k * D + i] : 0.0; z[i] = 0.0; }
     }
-    if (!CD || !pin) {
+    if (!pinned || !pin) {
 #pragma unroll
-      for (int j = 0; j < NP; j++) normal_pair(k0, k1, FC ? (uint32_t)a.k_begin + (uint32_t)k + 1u : (uint32_t)k, word, p, (uint32_t)j, &z[2 * j], &z[2 * j + 1]);
+      for (int j = 0; j < NP; j++) normal_pair(k0, k1, forecast ? (uint32_t)a.k_begin + (uint32_t)k + 1u : (uint32_t)k, word, p, (uint32_t)j, &z[2 * j], &z[2 * j + 1]);
     }
-    if constexpr (ST) model_phi<D>(a.model, x, phi);
+    if constexpr (stats) model_phi<D>(a.model, x, phi);
 #pragma unroll
     for (int i = 0; i < D; i++) {
       double s = 0.0;
 #pragma unroll
       for (int j = 0; j <= i; j++) s += R[i * D + j] * z[j];
-      if constexpr (CD) { if (pin) s = (xr[i] - x[i]) - a.dt * f[i]; }      // the increment the reference implies, in R xi's place
-      if constexpr (WS) { const double d = f[i] - fm[i]; pw -= isg[i] * d * (s + 0.5 * a.dt * d); }
-      if constexpr (ST) {
-        const double r = a.dt * (f[i] - fm[i]) + s;
-        sq[i] += r * r / a.dt; sg1[i] += phi[i] * r; sh[i] += a.dt * (phi[i] * phi[i]);
-      }
+      if constexpr (pinned) { if (pin) s = (xr[i] - x[i]) - a.dt * f[i]; }      // the increment the reference implies, in R xi's place
+      if constexpr (sums) { const double d = f[i] - fm[i]; pw -= isg[i] * d * (s + 0.5 * a.dt * d); }
+      if constexpr (stats) { stats_step(a.dt, f[i] - fm[i], s, phi[i], sq[i], sg1[i]); sh[i] += a.dt * (phi[i] * phi[i]); }
       x[i] = (x[i] + a.dt * f[i]) + s;
-      if constexpr (CD) { if (pin) x[i] = xr[i]; }      // (as loaded, not as recomputed)
-      if constexpr (EV) {
-        const double d = x[i] - ec[i], g = (eneg >> i) & 1 ? -d : d;
-        ex[i] = fmax(ex[i], g);
-        if (g > 0.0) { et[i] = min(et[i], k); en[i] += 1; }
-      }
+      if constexpr (pinned) { if (pin) x[i] = xr[i]; }      // (as loaded, not as recomputed)
+      if constexpr (events) event_step(x[i], ec[i], (eneg >> i) & 1, k, ex[i], et[i], en[i]);
     }
-    if constexpr (WS) {
+    if constexpr (sums) {
       if (k == oc.next) { ow += obs_form<D>(a, p, oc.cur, x); oc.advance(); }
     }
-    if constexpr (MG) {
-      if (k == keep_k) { count(keep_slot++); keep_k += a.stride; }
-    } else if constexpr (MO) {
-      if (k == keep_k) { reduce(keep_slot++); keep_k += a.stride; }
-    }
-    if constexpr (LN) {
+    if constexpr (replay) { if (k == next_kept.k) { at_kept(next_kept.slot++); next_kept.k += a.stride; } }
+    if constexpr (table) {
       if (k == oc.next) { oc.advance(); word = (uint32_t)lin[(size_t)oc.cur * a.n_paths]; }
     }
-    if constexpr (FC) {
-      if (a.pf_part && k + 1 == keep_k) { reduce(keep_slot++); keep_k += a.stride; }
+    if constexpr (forecast) {
+      if (a.pf_part && k + 1 == next_kept.k) { at_kept(next_kept.slot++); next_kept.k += a.stride; }
     }
     if (store && --until == 0) {
       until = a.stride;
@@ -505,38 +537,27 @@ __global__ __launch_bounds__(256) void k_sample_small(WalkArgs<K> a) {
         o += NBUF * D;
       }
     }
-    if constexpr (BW) {      // (the step completed observation oc.cur - 1 of the lane's problem; its point is stored: now the state is replaced)
+    if constexpr (T.words == Words::TableReload) {      // (the step completed observation oc.cur - 1 of the lane's problem; its point is stored: now the state is replaced)
       if (oc.cur > 0 && (int)oc.t[oc.cur - 1] == k) backward_reload<D>(a, p, oc.cur - 1, word, x);
     }
   }
   for (int e = 0; e < slot * D; e++) o[e] = sg[e * 256];
-  if constexpr (FC) {
-    if (live && a.pf_part) {
+  if constexpr (segment && sums) a.pf_lw[gid] += pw - 0.5 * ow;
+  if constexpr (segment || forecast) {      // back to pf_x: every live slot's end state (the forecast: of the cloud launch alone)
+    if (forecast ? live && a.pf_part : live) {
 #pragma unroll
       for (int i = 0; i < D; i++) a.pf_x[gid * D + i] = x[i];
     }
-  } else if constexpr (MO) {
-    if (live) {
+  }
+  if constexpr (stats) {
 #pragma unroll
-      for (int i = 0; i < D; i++) a.pf_x[gid * D + i] = x[i];
-    }
-  } else if constexpr (SEG) {
-    a.pf_lw[gid] += pw - 0.5 * ow;
+    for (int i = 0; i < D; i++) { carried(a, gid, D, 0, i) = sq[i]; carried(a, gid, D, 1, i) = sg1[i]; carried(a, gid, D, 2, i) = sh[i]; }
+  }
+  if constexpr (events) {
 #pragma unroll
-    for (int i = 0; i < D; i++) a.pf_x[gid * D + i] = x[i];
-    if constexpr (ST) {
-#pragma unroll
-      for (int i = 0; i < D; i++) {
-        a.pf_stats[gid * 3 * D + i] = sq[i]; a.pf_stats[gid * 3 * D + D + i] = sg1[i]; a.pf_stats[gid * 3 * D + 2 * D + i] = sh[i];
-      }
-    }
-    if constexpr (EV) {
-#pragma unroll
-      for (int i = 0; i < D; i++) {
-        a.pf_stats[gid * 3 * D + i] = ex[i]; a.pf_stats[gid * 3 * D + D + i] = (double)et[i]; a.pf_stats[gid * 3 * D + 2 * D + i] = (double)en[i];
-      }
-    }
-  } else if constexpr (W) { a.logw[2 * gid] = pw; a.logw[2 * gid + 1] = -0.5 * ow - obs_constant(a, p); }
+    for (int i = 0; i < D; i++) { carried(a, gid, D, 0, i) = ex[i]; carried(a, gid, D, 1, i) = (double)et[i]; carried(a, gid, D, 2, i) = (double)en[i]; }
+  }
+  if constexpr (weighted && !segment) { a.logw[2 * gid] = pw; a.logw[2 * gid + 1] = -0.5 * ow - obs_constant(a, p); }
 }
 
 // ---- 5 <= D <= 64, posterior kind ---------------------------------------------------------------------------------------------------
@@ -571,19 +592,20 @@ __device__ __forceinline__ void normals_c(uint32_t k0, uint32_t k1, uint32_t k, 
   }
 }
 
-// Weighted: Lorenz-96, diagonal R.  At step k the lane holds rows mt * 16 + q + 4 r of x_{k-1}, of g = bs - acc and of eta = nz; the model
+// What each walk does in k_sample_mfma, by the same properties (the rules above are shared; the row nest mt, r is written out in every user).
+// Weighted (weighted): Lorenz-96, diagonal R.  At step k the lane holds rows mt * 16 + q + 4 r of x_{k-1}, of g = bs - acc and of eta = nz; the model
 // drift f_i reads rows (i + 1) mod D, (i - 2) mod D, (i - 1) mod D of the path's column of Xs.  Each lane sums its rows over time; the four
 // q-lanes of a path are added once at the end.  The observation term is evaluated from Xs at the problem's observation times, which a
 // workgroup walks with one cursor.
-// Segment: as in k_sample_small; A_{k_begin} is the first matrix loaded, and the end states leave through `put` as [path][D].
-// SegmentStats: the lane adds r^2 / dt and r = dt d + eta (phi = 1: Lorenz-96) of its own rows to Q and G of the path's row of pf_stats,
+// Segment (segment): as in k_sample_small; A_{k_begin} is the first matrix loaded, and the end states leave through `put` as [path][D].
+// SegmentStats (Carry::Stats): the lane adds stats_step with phi = 1 (Lorenz-96) of its own rows to Q and G of the path's row of pf_stats,
 // read at the segment's entry and written at its exit; H_j = dt k_end, the constant dt times the steps walked so far, is written and not
 // summed.
-// Replay: the states only.  At a kept k every lane multiplies its rows of x_k by its path's weight (0 behind the last path), four
+// Replay (Kept::Moments): the states only.  At a kept k every lane multiplies its rows of x_k by its path's weight (0 behind the last path), four
 // cross-lane steps add the 16 paths of the wave, the lanes of path column 0 put their rows into red [4 waves][2][NT] -- the Zs region,
 // which a segment does not use --, and behind the next barrier the walk has anyway (the first of the next step, or one behind the loop)
 // thread t < 2 D adds the four waves in order and stores moment t / D of component t mod D.
-// ReplayCov: the replay, but at a kept k the wave's C_w = sum_{c < 16} W_c x_c x_c^T goes over the matrix pipe.  The wave
+// ReplayCov (Kept::Covariance): the replay, but at a kept k the wave's C_w = sum_{c < 16} W_c x_c x_c^T goes over the matrix pipe.  The wave
 // copies its 16 states into its own quarter of the Zs region with the columns of row i rotated by 2 (i >> 1), so that the transposed read of
 // the operands -- lane (j16, q) takes row mt 16 + j16, path 4 kk + q -- finds the 32 lanes of a half wave on 32 different bank pairs (from Xs,
 // at its row stride of 16 doubles, they sit on 4: an 8-way conflict), and holds them as xa [MT][4].  Tile (ti, tj <= ti) is four products
@@ -592,26 +614,29 @@ __device__ __forceinline__ void normals_c(uint32_t k0, uint32_t k1, uint32_t k, 
 // lower triangle below D.  The mean keeps the replay's cross-lane sum, its [4 waves][NT] words behind the Zs region.  Barriers per kept k:
 // 2 ceil(T / MT) - 1 with T = MT (MT + 1) / 2 tiles, that is 1, 3, 3, 5 at NT = 16, 32, 48, 64; none in a step that keeps nothing.  The last
 // round's slots are read before the next step's barriers, the next kept k writes them behind those.
-// Lineage: as in k_sample_small (diagonal R): every lane of a workgroup belongs to one problem, so all of them change their counter words
+// Lineage (Words::Table): as in k_sample_small (diagonal R): every lane of a workgroup belongs to one problem, so all of them change their counter words
 // behind the same steps.  A lane behind the last lineage walks the last one again and stores nothing.
-// Backward: as in k_sample_small; the reload is a gather of the lane's own rows of its path's new particle into the accumulator layout, which
+// Backward (Words::TableReload): as in k_sample_small; the reload is a gather of the lane's own rows of its path's new particle into the accumulator layout, which
 // then goes to Xs as every step's result does, behind the store of the completed observation's point and in front of one more barrier.
-// Conditional: as in k_sample_small.  Slot 0 is path column 0 of wave 0 of workgroup (p, 0): its four lanes request their rows of ref_k
+// Conditional (pinned): as in k_sample_small.  Slot 0 is path column 0 of wave 0 of workgroup (p, 0): its four lanes request their rows of ref_k
 // with the step's A_k, put eta* into nz before the weight term is formed and ref_k into x before the step's own write of x to Xs -- no
 // barrier is added, and the model drift of the next step reads the reference from the column of Xs as it reads every other path.
-// SegmentEvents: as in k_sample_small, lane-local: the lane holds X, T, N of its own rows mt * 16 + q + 4 r of its path's row of pf_stats, read
+// SegmentEvents (Carry::Events): as in k_sample_small, lane-local: the lane holds X, T, N of its own rows mt * 16 + q + 4 r of its path's row of pf_stats, read
 // at the segment's entry, updated behind the step's own update of x and written at its exit; the levels lie in LDS as bs does ([NT], in the
 // Zs region) and are read where they are used.  A row beyond D and a lane behind the last path compute on zeros and store nothing.  No
 // barrier or cross-lane step is added.
 template <int NT, Walk K>
 __global__ __launch_bounds__(256) void k_sample_mfma(WalkArgs<K> a) {
   constexpr WalkTraits T = kWalkTraits[(int)K];
-  constexpr bool W = T.W, SEG = T.SEG, ST = T.ST, MO = T.MO, LN = T.LN, CV = T.CV, BW = T.BW, CD = T.CD, EV = T.EV, MG = T.MG, WS = T.WS();
+  constexpr bool weighted = T.weighted, segment = T.segment, pinned = T.pinned, sums = T.WS();
+  constexpr bool stats = T.carry == Carry::Stats, events = T.carry == Carry::Events;
+  constexpr Kept kept = T.kept;
+  constexpr bool table = T.words != Words::Own, replay = kept != Kept::None;
   using Sh = MfmaShape<NT>;
   constexpr int LDA = Sh::LDA, MT = Sh::MT, KT = Sh::KT, NPF = Sh::NPF;
   extern __shared__ double lds[];
   const int D = a.D, DD = D * D, tid = threadIdx.x, w = tid >> 6, lane = tid & 63, j16 = lane & 15, q = lane >> 4;
-  const bool dense = !W && !LN && !a.R_diag;      // (the weighted walks and the lineage walk are launched with diagonal factors only)
+  const bool dense = !weighted && !table && !a.R_diag;      // (the weighted walks and the lineage walk are launched with diagonal factors only)
   double* As = lds;
   double* bs = As + NT * LDA;
   double* Rs = bs + NT;
@@ -620,7 +645,7 @@ __global__ __launch_bounds__(256) void k_sample_mfma(WalkArgs<K> a) {
   const uint32_t p = blockIdx.x, path = blockIdx.y * 64 + w * 16 + j16;
   uint32_t word = path;      // the counter word of the lane's draws
   const int32_t* lin = nullptr;
-  if constexpr (LN) {
+  if constexpr (table) {
     lin = a.pf_slots + (size_t)p * a.pf_slot_rows * a.n_paths + (path < (uint32_t)a.n_paths ? path : (uint32_t)a.n_paths - 1);
     word = (uint32_t)lin[0];
   }
@@ -628,7 +653,7 @@ __global__ __launch_bounds__(256) void k_sample_mfma(WalkArgs<K> a) {
   const double* A = a.A + (size_t)p * a.stride_x;
   const double* bv = a.b + (size_t)p * a.stride_x;
   const double* Rp = a.R + (size_t)p * a.R_stride;
-  const int k_first = SEG ? a.k_begin + 1 : 1, k_stop = SEG ? a.k_end + 1 : a.Np;
+  const int k_first = segment ? a.k_begin + 1 : 1, k_stop = segment ? a.k_end + 1 : a.Np;
 
   for (int e = tid; e < NT * LDA * (dense ? 2 : 1) + NT; e += 256) lds[e] = 0.0;
   __syncthreads();
@@ -646,7 +671,7 @@ __global__ __launch_bounds__(256) void k_sample_mfma(WalkArgs<K> a) {
       const int row = mt * 16 + q + 4 * r;
       rd[mt][r] = (!dense && row < D) ? Rp[row * D + row] : 0.0;
     }
-  if constexpr (SEG) {
+  if constexpr (segment) {
     const bool live = path < (uint32_t)a.n_paths;      // (a lane behind the last path walks zeros and stores nothing)
 #pragma unroll
     for (int mt = 0; mt < MT; mt++)
@@ -686,7 +711,7 @@ __global__ __launch_bounds__(256) void k_sample_mfma(WalkArgs<K> a) {
   // A kept point leaves from Xs, where the wave's 16 states lie as [row][path]: element e = lane + 64 i of the 16 rows of `out` (path e / D,
   // component e % D), so that one store instruction writes runs of D consecutive doubles instead of 4 per path
   const uint32_t path0 = blockIdx.y * 64 + w * 16;
-  const bool store = !SEG && (!W || a.out != nullptr);
+  const bool store = !segment && (!weighted || a.out != nullptr);
   double* o = store ? a.out + ((size_t)p * a.n_paths + path0) * (size_t)a.n_keep * D : nullptr;
   const size_t row_len = (size_t)a.n_keep * D;
   auto put = [&](double* dst, size_t len) {
@@ -703,10 +728,10 @@ __global__ __launch_bounds__(256) void k_sample_mfma(WalkArgs<K> a) {
     if (store) { put(o, row_len); o += D; }
   };
   // weighted: 1 / Sigma_ii of the lane's rows, the two sums, theta, the observation cursor
-  double isg[WS ? MT : 1][4], pw = 0.0, ow = 0.0, th = 0.0;
-  double sq[ST ? MT : 1][4], sg1[ST ? MT : 1][4];
-  if constexpr (ST) {
-    const double* row0 = a.pf_stats + ((size_t)p * a.n_paths + path) * 3 * D;
+  double isg[sums ? MT : 1][4], pw = 0.0, ow = 0.0, th = 0.0;
+  double sq[stats ? MT : 1][4], sg1[stats ? MT : 1][4];
+  if constexpr (stats) {
+    const double* row0 = &carried(a, (size_t)p * a.n_paths + path, D, 0, 0);
 #pragma unroll
     for (int mt = 0; mt < MT; mt++)
 #pragma unroll
@@ -718,11 +743,11 @@ __global__ __launch_bounds__(256) void k_sample_mfma(WalkArgs<K> a) {
   }
   // SegmentEvents: the records of the lane's rows; the sides as a bit per row; the levels [NT] at the head of the Zs region, which a segment
   // does not use (written in front of the barrier below)
-  double ex[EV ? MT : 1][4];
-  int et[EV ? MT : 1][4], en[EV ? MT : 1][4], eneg = 0;
+  double ex[events ? MT : 1][4];
+  int et[events ? MT : 1][4], en[events ? MT : 1][4], eneg = 0;
   const double* evc = lds + NT * LDA + NT + 4 * NT * 16;
-  if constexpr (EV) {
-    const double* row0 = a.pf_stats + ((size_t)p * a.n_paths + path) * 3 * D;
+  if constexpr (events) {
+    const double* row0 = a.pf_stats + ((size_t)p * a.n_paths + path) * 3 * D;      // (carried()'s row, written out: through it the four kernels move)
     if (tid < NT) lds[NT * LDA + NT + 4 * NT * 16 + tid] = tid < D ? a.ev_level[(size_t)p * D + tid] : 0.0;
 #pragma unroll
     for (int mt = 0; mt < MT; mt++)
@@ -735,8 +760,8 @@ __global__ __launch_bounds__(256) void k_sample_mfma(WalkArgs<K> a) {
       }
   }
   ObsCursor oc;
-  if constexpr (W || LN) oc = ObsCursor(a, p);
-  if constexpr (SEG) { if (!a.seg_first) oc.skip_through(a.k_begin); }
+  if constexpr (weighted || table) oc = ObsCursor(a, p);
+  if constexpr (segment) { if (!a.seg_first) oc.skip_through(a.k_begin); }
   auto observe = [&]() {      // x_k is in x and, whole, in the path's column of Xs
     const double* y = a.obs_y + (size_t)p * a.obs_y_stride + (size_t)oc.cur * D;
     const double* Qp = a.Q + (size_t)p * a.Q_stride;
@@ -756,7 +781,7 @@ __global__ __launch_bounds__(256) void k_sample_mfma(WalkArgs<K> a) {
       }
     oc.advance();
   };
-  if constexpr (WS) {
+  if constexpr (sums) {
     th = a.theta_v ? a.theta_v[(size_t)p * kMaxTheta] : a.theta[0];
 #pragma unroll
     for (int mt = 0; mt < MT; mt++)
@@ -769,15 +794,14 @@ __global__ __launch_bounds__(256) void k_sample_mfma(WalkArgs<K> a) {
     for (int r = 0; r < 4; r++) Xs[(mt * 16 + q + 4 * r) * 16 + j16] = x[mt][r];
   __syncthreads();
   keep();
-  if constexpr (WS) {
-    if constexpr (!SEG) put(a.start + ((size_t)p * a.n_paths + path0) * D, (size_t)D);
+  if constexpr (sums) {
+    if constexpr (!segment) put(a.start + ((size_t)p * a.n_paths + path0) * D, (size_t)D);
     if (oc.next == 0) observe();
   }
   // Backward: the particle slot `word` was copied from at the problem's observation j, to x and to the path's column of Xs (the points kept so
   // far have left Xs: the stores of `put` precede these writes in every lane of the wave that owns the region)
   auto reload = [&](int j) {
-    const size_t hj = (size_t)p * a.pf_M + j;
-    const double* src = a.pf_clouds + (hj * a.pf_n + (size_t)a.pf_hanc[hj * a.pf_n + word]) * D;
+    const double* src = backward_source(a, p, j, word, D);
 #pragma unroll
     for (int mt = 0; mt < MT; mt++)
 #pragma unroll
@@ -788,34 +812,109 @@ __global__ __launch_bounds__(256) void k_sample_mfma(WalkArgs<K> a) {
       }
     __syncthreads();      // (uniform: the lanes of a workgroup belong to one problem)
   };
-  if constexpr (LN) {
+  if constexpr (table) {
     if (oc.next == 0) {
       oc.advance(); word = (uint32_t)lin[(size_t)oc.cur * a.n_paths];
-      if constexpr (BW) reload(oc.cur - 1);
+      if constexpr (T.words == Words::TableReload) reload(oc.cur - 1);
     }
   }
-  // Replay: the segment lies in one stretch of its problem -- the observations behind it are oc.cur, the row of the weights
+  // the replay: the path's weight of the segment's stretch (Kept::Marginals: the integer one), the first kept index behind k_begin
   double wt = 0.0;
   double* red = lds + NT * LDA + NT + 4 * NT * 16;
-  long long keep_k = 0, keep_slot = 0, pending = -1;
-  unsigned long long qw = 0;      // ReplayMarginals: the path's integer weight
-  if constexpr (MG) qw = path < (uint32_t)a.n_paths ? a.mg_qtab[((size_t)p * a.pf_rows + oc.cur) * a.n_paths + path] : 0ull;
-  if constexpr (MO) {
-    if constexpr (!MG) wt = path < (uint32_t)a.n_paths ? a.pf_wtab[((size_t)p * a.pf_rows + oc.cur) * a.n_paths + path] : 0.0;
-    keep_slot = ((long long)a.k_begin + a.stride) / a.stride;      // the first kept index behind k_begin
-    keep_k = keep_slot * a.stride;
+  KeptCursor next_kept;
+  long long pending = -1;
+  unsigned long long qw = 0;
+  if constexpr (replay) {
+    if constexpr (kept == Kept::Marginals) qw = path < (uint32_t)a.n_paths ? stretch_weight(a, a.mg_qtab, p, oc.cur, path) : 0ull;
+    else wt = path < (uint32_t)a.n_paths ? stretch_weight(a, a.pf_wtab, p, oc.cur, path) : 0.0;
+    next_kept.first_behind(a.k_begin, a.stride);
   }
-  auto reduce = [&](long long slot) {
+  // the action at a kept index, by the walk's `kept`
+  auto at_kept = [&](long long slot) {
+    if constexpr (kept == Kept::Marginals) {      // count, in reduce's place: the lane's own rows of its path, no cross-lane step
+      if (qw != 0) {
 #pragma unroll
-    for (int mt = 0; mt < MT; mt++)
+        for (int mt = 0; mt < MT; mt++)
 #pragma unroll
-      for (int r = 0; r < 4; r++) {
-        double v1 = wt * x[mt][r], v2 = v1 * x[mt][r];
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) { v1 += __shfl_xor(v1, o); v2 += __shfl_xor(v2, o); }
-        if (j16 == 0) { red[(w * 2 + 0) * NT + mt * 16 + q + 4 * r] = v1; red[(w * 2 + 1) * NT + mt * 16 + q + 4 * r] = v2; }
+          for (int r = 0; r < 4; r++) {
+            const int row = mt * 16 + q + 4 * r;
+            if (row < D) marginal_add(marginal_ladder(a, p, row, D), a.mg_L, mass_row(a, p, slot, row, D), x[mt][r], qw);
+          }
       }
-    pending = slot;
+    } else if constexpr (kept == Kept::Covariance) {      // reduce_cov
+      constexpr int T2 = MT * (MT + 1) / 2, ROUNDS = (T2 + MT - 1) / MT;
+      double* zw = red + w * NT * 16;       // the wave's quarter of the Zs region: the rotated copy, then its MT tile slots
+      double* mred = red + 4 * NT * 16;     // [4 waves][NT]
+#pragma unroll
+      for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+          const int row = mt * 16 + q + 4 * r;
+          double v1 = wt * x[mt][r];
+#pragma unroll
+          for (int o = 1; o < 16; o <<= 1) v1 += __shfl_xor(v1, o);
+          if (j16 == 0) mred[w * NT + row] = v1;
+          zw[row * 16 + ((j16 + 2 * (row >> 1)) & 15)] = x[mt][r];
+        }
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // (the copy is the wave's own: no barrier)
+      __builtin_amdgcn_wave_barrier();
+      double xa[MT][4], wq[4];
+#pragma unroll
+      for (int kk = 0; kk < 4; kk++) wq[kk] = __shfl(wt, kk * 4 + q);
+#pragma unroll
+      for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+        for (int kk = 0; kk < 4; kk++) {
+          const int row = mt * 16 + j16;
+          xa[mt][kk] = zw[row * 16 + ((kk * 4 + q + 2 * (row >> 1)) & 15)];
+        }
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // (the operands are read before the slots overwrite the copy)
+      __builtin_amdgcn_wave_barrier();
+      const size_t NVc = (size_t)D + (size_t)D * (D + 1) / 2;
+      double* dst = a.pf_part + (((size_t)p * gridDim.y + blockIdx.y) * a.n_keep + (size_t)slot) * NVc;
+#pragma unroll
+      for (int rd = 0; rd < ROUNDS; rd++) {
+        if (rd > 0) __syncthreads();      // (the slots of the round before have been read)
+#pragma unroll
+        for (int ti = 0; ti < MT; ti++)
+#pragma unroll
+          for (int tj = 0; tj <= ti; tj++) {
+            const int t = ti * (ti + 1) / 2 + tj;
+            if (t / MT == rd) {
+              d4 acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+              for (int kk = 0; kk < 4; kk++) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(xa[ti][kk], wq[kk] * xa[tj][kk], acc, 0, 0, 0);
+#pragma unroll
+              for (int r = 0; r < 4; r++) zw[(t % MT) * 256 + r * 64 + lane] = acc[r];
+            }
+          }
+        __syncthreads();
+        if (rd == 0 && tid < D) dst[tid] = ((mred[tid] + mred[NT + tid]) + mred[2 * NT + tid]) + mred[3 * NT + tid];
+#pragma unroll
+        for (int ti = 0; ti < MT; ti++)
+#pragma unroll
+          for (int tj = 0; tj <= ti; tj++) {
+            const int t = ti * (ti + 1) / 2 + tj;
+            if (t / MT == rd) {
+              const double* s0 = red + (t % MT) * 256 + tid;      // entry tid of the tile: row (lane >> 4) + 4 (tid >> 6), column lane & 15
+              const double val = ((s0[0] + s0[NT * 16]) + s0[2 * NT * 16]) + s0[3 * NT * 16];
+              const int ra = ti * 16 + q + 4 * w, cb = tj * 16 + j16;
+              if (ra < D && cb <= ra) dst[D + (size_t)ra * (ra + 1) / 2 + cb] = val;
+            }
+          }
+      }
+    } else {      // reduce; flush() stores behind the next barrier
+#pragma unroll
+      for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+          double v1 = wt * x[mt][r], v2 = v1 * x[mt][r];
+#pragma unroll
+          for (int o = 1; o < 16; o <<= 1) { v1 += __shfl_xor(v1, o); v2 += __shfl_xor(v2, o); }
+          if (j16 == 0) { red[(w * 2 + 0) * NT + mt * 16 + q + 4 * r] = v1; red[(w * 2 + 1) * NT + mt * 16 + q + 4 * r] = v2; }
+        }
+      pending = slot;
+    }
   };
   auto flush = [&]() {      // (behind a barrier that follows reduce)
     if (pending >= 0) {
@@ -828,99 +927,19 @@ __global__ __launch_bounds__(256) void k_sample_mfma(WalkArgs<K> a) {
       pending = -1;
     }
   };
-  auto count = [&](long long slot) {      // ReplayMarginals, in reduce's place: the lane's own rows of its path, no cross-lane step
-    if constexpr (MG) {
-      if (qw != 0) {
-#pragma unroll
-        for (int mt = 0; mt < MT; mt++)
-#pragma unroll
-          for (int r = 0; r < 4; r++) {
-            const int row = mt * 16 + q + 4 * r;
-            if (row < D)
-              marginal_add(a.mg_level + ((size_t)p * D + row) * a.mg_L, a.mg_L,
-                           a.mg_mass + (((size_t)p * a.n_keep + (size_t)slot) * D + row) * ((size_t)a.mg_L + 1), x[mt][r], qw);
-          }
-      }
-    }
-  };
-  auto reduce_cov = [&](long long slot) {
-    constexpr int T2 = MT * (MT + 1) / 2, ROUNDS = (T2 + MT - 1) / MT;
-    double* zw = red + w * NT * 16;       // the wave's quarter of the Zs region: the rotated copy, then its MT tile slots
-    double* mred = red + 4 * NT * 16;     // [4 waves][NT]
-#pragma unroll
-    for (int mt = 0; mt < MT; mt++)
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        const int row = mt * 16 + q + 4 * r;
-        double v1 = wt * x[mt][r];
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) v1 += __shfl_xor(v1, o);
-        if (j16 == 0) mred[w * NT + row] = v1;
-        zw[row * 16 + ((j16 + 2 * (row >> 1)) & 15)] = x[mt][r];
-      }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // (the copy is the wave's own: no barrier)
-    __builtin_amdgcn_wave_barrier();
-    double xa[MT][4], wq[4];
-#pragma unroll
-    for (int kk = 0; kk < 4; kk++) wq[kk] = __shfl(wt, kk * 4 + q);
-#pragma unroll
-    for (int mt = 0; mt < MT; mt++)
-#pragma unroll
-      for (int kk = 0; kk < 4; kk++) {
-        const int row = mt * 16 + j16;
-        xa[mt][kk] = zw[row * 16 + ((kk * 4 + q + 2 * (row >> 1)) & 15)];
-      }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // (the operands are read before the slots overwrite the copy)
-    __builtin_amdgcn_wave_barrier();
-    const size_t NVc = (size_t)D + (size_t)D * (D + 1) / 2;
-    double* dst = a.pf_part + (((size_t)p * gridDim.y + blockIdx.y) * a.n_keep + (size_t)slot) * NVc;
-#pragma unroll
-    for (int rd = 0; rd < ROUNDS; rd++) {
-      if (rd > 0) __syncthreads();      // (the slots of the round before have been read)
-#pragma unroll
-      for (int ti = 0; ti < MT; ti++)
-#pragma unroll
-        for (int tj = 0; tj <= ti; tj++) {
-          const int t = ti * (ti + 1) / 2 + tj;
-          if (t / MT == rd) {
-            d4 acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int kk = 0; kk < 4; kk++) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(xa[ti][kk], wq[kk] * xa[tj][kk], acc, 0, 0, 0);
-#pragma unroll
-            for (int r = 0; r < 4; r++) zw[(t % MT) * 256 + r * 64 + lane] = acc[r];
-          }
-        }
-      __syncthreads();
-      if (rd == 0 && tid < D) dst[tid] = ((mred[tid] + mred[NT + tid]) + mred[2 * NT + tid]) + mred[3 * NT + tid];
-#pragma unroll
-      for (int ti = 0; ti < MT; ti++)
-#pragma unroll
-        for (int tj = 0; tj <= ti; tj++) {
-          const int t = ti * (ti + 1) / 2 + tj;
-          if (t / MT == rd) {
-            const double* s0 = red + (t % MT) * 256 + tid;      // entry tid of the tile: row (lane >> 4) + 4 (tid >> 6), column lane & 15
-            const double val = ((s0[0] + s0[NT * 16]) + s0[2 * NT * 16]) + s0[3 * NT * 16];
-            const int ra = ti * 16 + q + 4 * w, cb = tj * 16 + j16;
-            if (ra < D && cb <= ra) dst[D + (size_t)ra * (ra + 1) / 2 + cb] = val;
-          }
-        }
-    }
-  };
-  if constexpr (MG) { if (a.seg_first) count(0); }
-  if constexpr (MO && !CV && !MG) { if (a.seg_first) reduce(0); }
-  if constexpr (CV) { if (a.seg_first) reduce_cov(0); }
+  if constexpr (replay) { if (a.seg_first) at_kept(0); }
 
   int until = a.stride;
-  // Conditional: the four lanes that hold the rows of slot 0 (workgroup (p, 0), wave 0, path column 0)
+  // pinned: the four lanes that hold the rows of slot 0 (workgroup (p, 0), wave 0, path column 0)
   bool pin = false;
   const double* ref = nullptr;
-  if constexpr (CD) { pin = path == 0; ref = a.pf_ref + (size_t)p * a.Np * D; }
+  if constexpr (pinned) { pin = path == 0; ref = a.pf_ref + (size_t)p * a.Np * D; }
   for (int k = k_first; k < k_stop; k++) {
     // A_k, b_k for the next step: requested now, written to LDS behind this step's products
     double pa[NPF], pb = 0.0;
     const bool more = k + 1 < k_stop;
-    double xref[CD ? MT : 1][4];      // Conditional: the pinned lanes' rows of ref_k, requested now as well
-    if constexpr (CD) {
+    double xref[pinned ? MT : 1][4];      // pinned: the pinned lanes' rows of ref_k, requested now as well
+    if constexpr (pinned) {
 #pragma unroll
       for (int mt = 0; mt < MT; mt++)
 #pragma unroll
@@ -949,7 +968,7 @@ __global__ __launch_bounds__(256) void k_sample_mfma(WalkArgs<K> a) {
     // weighted: the rows of x_{k-1} that the circular drift reaches by wrapping around -- 0, D - 1, D - 2 -- once per step
     const double* xq = Xs + q * 16 + j16;
     double w0 = 0.0, wl1 = 0.0, wl2 = 0.0;
-    if constexpr (WS) { w0 = Xs[j16]; wl1 = Xs[(D - 1) * 16 + j16]; wl2 = Xs[(D - 2) * 16 + j16]; }
+    if constexpr (sums) { w0 = Xs[j16]; wl1 = Xs[(D - 1) * 16 + j16]; wl2 = Xs[(D - 2) * 16 + j16]; }
 #pragma unroll
     for (int mt = 0; mt < MT; mt++) {
       d4 acc = {0.0, 0.0, 0.0, 0.0};
@@ -963,13 +982,13 @@ __global__ __launch_bounds__(256) void k_sample_mfma(WalkArgs<K> a) {
 #pragma unroll
         for (int kk = 0; kk < KT; kk++) nz = __builtin_amdgcn_mfma_f64_16x16x4f64(rr[kk * 4], Zs[(kk * 4 + q) * 16 + j16], nz, 0, 0, 0);
       }
-      if constexpr (CD) {      // the increment the reference implies, in R xi's place (rows beyond D: 0 - 0)
+      if constexpr (pinned) {      // the increment the reference implies, in R xi's place (rows beyond D: 0 - 0)
         if (pin) {
 #pragma unroll
           for (int r = 0; r < 4; r++) nz[r] = (xref[mt][r] - x[mt][r]) - a.dt * (bs[mt * 16 + q + 4 * r] - acc[r]);
         }
       }
-      if constexpr (WS) {
+      if constexpr (sums) {
 #pragma unroll
         for (int r = 0; r < 4; r++) {
           const int row = mt * 16 + q + 4 * r;
@@ -986,29 +1005,25 @@ __global__ __launch_bounds__(256) void k_sample_mfma(WalkArgs<K> a) {
             const double f = (xu - xd2) * xd1 - x[mt][r] + th;
             const double d = (bs[row] - acc[r]) - f;
             pw -= isg[mt][r] * d * (nz[r] + 0.5 * a.dt * d);
-            if constexpr (ST) { const double res = a.dt * d + nz[r]; sq[mt][r] += res * res / a.dt; sg1[mt][r] += res; }
+            if constexpr (stats) stats_step(a.dt, d, nz[r], 1.0, sq[mt][r], sg1[mt][r]);      // (phi = 1: Lorenz-96)
           }
         }
       }
 #pragma unroll
       for (int r = 0; r < 4; r++) x[mt][r] = (x[mt][r] + a.dt * (bs[mt * 16 + q + 4 * r] - acc[r])) + nz[r];
-      if constexpr (CD) {      // (ref_k as loaded, not as recomputed; it goes to Xs with every lane's rows below)
+      if constexpr (pinned) {      // (ref_k as loaded, not as recomputed; it goes to Xs with every lane's rows below)
         if (pin) {
 #pragma unroll
           for (int r = 0; r < 4; r++) x[mt][r] = xref[mt][r];
         }
       }
-      if constexpr (EV) {
+      if constexpr (events) {
 #pragma unroll
-        for (int r = 0; r < 4; r++) {
-          const double d = x[mt][r] - evc[mt * 16 + q + 4 * r], g = (eneg >> (mt * 4 + r)) & 1 ? -d : d;
-          ex[mt][r] = fmax(ex[mt][r], g);
-          if (g > 0.0) { et[mt][r] = min(et[mt][r], k); en[mt][r] += 1; }
-        }
+        for (int r = 0; r < 4; r++) event_step(x[mt][r], evc[mt * 16 + q + 4 * r], (eneg >> (mt * 4 + r)) & 1, k, ex[mt][r], et[mt][r], en[mt][r]);
       }
     }
     __syncthreads();
-    if constexpr (MO && !CV && !MG) flush();
+    if constexpr (kept == Kept::Moments) flush();
     if (more) {
 #pragma unroll
       for (int n = 0; n < NPF; n++) { const int e = tid + 256 * n; if (e < DD) As[(e / D) * LDA + e % D] = pa[n]; }
@@ -1020,38 +1035,30 @@ __global__ __launch_bounds__(256) void k_sample_mfma(WalkArgs<K> a) {
       for (int r = 0; r < 4; r++) Xs[(mt * 16 + q + 4 * r) * 16 + j16] = x[mt][r];
     __syncthreads();
     if (--until == 0) { until = a.stride; keep(); }
-    if constexpr (WS) {
+    if constexpr (sums) {
       if (k == oc.next) observe();
     }
-    if constexpr (MG) {
-      if (k == keep_k) { count(keep_slot++); keep_k += a.stride; }
-    }
-    if constexpr (MO && !CV && !MG) {
-      if (k == keep_k) { reduce(keep_slot++); keep_k += a.stride; }
-    }
-    if constexpr (CV) {
-      if (k == keep_k) { reduce_cov(keep_slot++); keep_k += a.stride; }
-    }
-    if constexpr (LN) {
+    if constexpr (replay) { if (k == next_kept.k) { at_kept(next_kept.slot++); next_kept.k += a.stride; } }
+    if constexpr (table) {
       if (k == oc.next) {
         oc.advance(); word = (uint32_t)lin[(size_t)oc.cur * a.n_paths];
-        if constexpr (BW) reload(oc.cur - 1);
+        if constexpr (T.words == Words::TableReload) reload(oc.cur - 1);
       }
     }
   }
-  if constexpr (MO) {
+  if constexpr (replay) {
     __syncthreads();
-    if constexpr (!CV && !MG) flush();
+    if constexpr (kept == Kept::Moments) flush();
     put(a.pf_x + ((size_t)p * a.n_paths + path0) * D, (size_t)D);      // (Xs holds x_{k_end} behind the loop's last barrier)
-  } else if constexpr (W) {
+  } else if constexpr (weighted) {
     pw += __shfl_xor(pw, 16); pw += __shfl_xor(pw, 32);
     ow += __shfl_xor(ow, 16); ow += __shfl_xor(ow, 32);
-    if constexpr (SEG) {
+    if constexpr (segment) {
       if (q == 0 && path < (uint32_t)a.n_paths) a.pf_lw[(size_t)p * a.n_paths + path] += pw - 0.5 * ow;
       put(a.pf_x + ((size_t)p * a.n_paths + path0) * D, (size_t)D);      // (Xs holds x_{k_end} behind the loop's last barrier)
-      if constexpr (ST) {
+      if constexpr (stats) {
         if (path < (uint32_t)a.n_paths) {
-          double* row0 = a.pf_stats + ((size_t)p * a.n_paths + path) * 3 * D;
+          double* row0 = &carried(a, (size_t)p * a.n_paths + path, D, 0, 0);
           const double h = a.dt * (double)a.k_end;
 #pragma unroll
           for (int mt = 0; mt < MT; mt++)
@@ -1062,9 +1069,9 @@ __global__ __launch_bounds__(256) void k_sample_mfma(WalkArgs<K> a) {
             }
         }
       }
-      if constexpr (EV) {
+      if constexpr (events) {
         if (path < (uint32_t)a.n_paths) {
-          double* row0 = a.pf_stats + ((size_t)p * a.n_paths + path) * 3 * D;
+          double* row0 = a.pf_stats + ((size_t)p * a.n_paths + path) * 3 * D;      // (written out, as at the entry)
 #pragma unroll
           for (int mt = 0; mt < MT; mt++)
 #pragma unroll
@@ -2041,15 +2048,14 @@ __global__ __launch_bounds__(256) void k_pf_ref_fill(PfArgs a, int rows, const i
 // plain walk only: every other walk needs a stochastic model, and none has D = 2.  (Twelve walks: 3 instantiations of k_sample_small each
 // and one more for Plain, 4 of k_sample_mfma each but Forecast.)
 template <Walk K>
-hipError_t launch_walk(const SampleArgs& base, hipStream_t st, const double* pf_ref = nullptr, const double* ev_level = nullptr,
-                       const int32_t* ev_side = nullptr, const MarginalArgs* mg = nullptr) {
+hipError_t launch_walk(const SampleArgs& base, hipStream_t st, const WalkOwn& own) {
   WalkArgs<K> a;
   static_cast<SampleArgs&>(a) = base;
-  if constexpr (K == Walk::Conditional) a.pf_ref = pf_ref;
-  if constexpr (K == Walk::SegmentEvents) { a.ev_level = ev_level; a.ev_side = ev_side; }
-  if constexpr (K == Walk::ReplayMarginals) { a.mg_level = mg->levels; a.mg_L = mg->L; a.mg_qtab = mg->qtab; a.mg_mass = mg->mass; }
+  if constexpr (K == Walk::Conditional) a.pf_ref = own.pf_ref;
+  if constexpr (K == Walk::SegmentEvents) { a.ev_level = own.ev_level; a.ev_side = own.ev_side; }
+  if constexpr (K == Walk::ReplayMarginals) { a.mg_level = own.mg->levels; a.mg_L = own.mg->L; a.mg_qtab = own.mg->qtab; a.mg_mass = own.mg->mass; }
   if (a.D <= kMaxLaneD) {
-    const dim3 grid = kWalkTraits[(int)K].MO || kWalkTraits[(int)K].FC ? dim3(a.batch, sample_segment_blocks(a.D, a.n_paths))
+    const dim3 grid = kWalkTraits[(int)K].by_problem() ? dim3(a.batch, sample_segment_blocks(a.D, a.n_paths))
                                         : dim3((unsigned)(((size_t)a.batch * a.n_paths + 255) / 256));
     const dim3 block(256);
     switch (a.D) {
@@ -2069,7 +2075,7 @@ hipError_t launch_walk(const SampleArgs& base, hipStream_t st, const double* pf_
     auto mfma = [&](auto nt) {
       constexpr int NT = decltype(nt)::value;
       // (ReplayCov: the [4 waves][NT] words of the mean behind the Zs region)
-      const size_t lds = (MfmaShape<NT>::lds_doubles(!a.R_diag) + (kWalkTraits[(int)K].CV ? 4 * NT : 0)) * sizeof(double);
+      const size_t lds = (MfmaShape<NT>::lds_doubles(!a.R_diag) + (kWalkTraits[(int)K].kept == Kept::Covariance ? 4 * NT : 0)) * sizeof(double);
       if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k_sample_mfma<NT, K>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       if (a.n_paths > sample_max_paths(a.D)) return hipErrorInvalidValue;
       hipLaunchKernelGGL((k_sample_mfma<NT, K>), dim3(a.batch, sample_segment_blocks(a.D, a.n_paths)), dim3(256), lds, st, a);
@@ -2234,21 +2240,22 @@ hipError_t launch_pf_events_cdf(int D, int batch, int n_paths, int Np, int strid
 }
 
 // The walk is what the caller says it is; the fields that walk reads must be set, and the fields that would have meant another walk must not.
-hipError_t launch_sample_walk(Walk w, const SampleArgs& a, hipStream_t st, const double* pf_ref, const double* ev_level, const int32_t* ev_side,
-                              const MarginalArgs* mg) {
+hipError_t launch_sample_walk(Walk w, const SampleArgs& a, hipStream_t st, const WalkOwn& own) {
   if (a.D < 1 || a.D > kMaxSmallD || a.n_paths < 1) return hipErrorInvalidValue;
   const bool known_model = a.model == VGPA_MODEL_OU || a.model == VGPA_MODEL_DW || a.model == VGPA_MODEL_L63 || a.model == VGPA_MODEL_L96;
   // the weighted kind: the posterior process with diagonal factors against the model's drift; above D = 4 the model is Lorenz-96
   const bool weighable = a.kind == VGPA_PATHS_POSTERIOR && a.R_diag && known_model && (a.D <= kMaxLaneD || a.model == VGPA_MODEL_L96);
   const bool segment = weighable && a.pf_x && a.pf_lw && a.k_begin >= 0 && a.k_end >= a.k_begin && a.k_end < a.Np;
-  if (w == Walk::Backward ? a.pf_wtab || a.pf_part : a.pf_clouds || a.pf_hanc) return hipErrorInvalidValue;      // (the histories are Backward's alone, the sums never its)
-  if (w != Walk::Conditional && pf_ref) return hipErrorInvalidValue;      // (the reference is Conditional's alone)
-  if (w != Walk::SegmentEvents && (ev_level || ev_side)) return hipErrorInvalidValue;      // (the levels and sides are SegmentEvents' alone)
-  if (w != Walk::ReplayMarginals && mg) return hipErrorInvalidValue;      // (the ladders, integer weights and masses are ReplayMarginals' alone)
+  // what is one walk's alone: the histories Backward's (and the sums never its), the reference Conditional's, the levels and sides
+  // SegmentEvents', the ladders, integer weights and masses ReplayMarginals'
+  const bool foreign = (w == Walk::Backward ? a.pf_wtab || a.pf_part : a.pf_clouds || a.pf_hanc) || (w != Walk::Conditional && own.pf_ref) ||
+                       (w != Walk::SegmentEvents && (own.ev_level || own.ev_side)) || (w != Walk::ReplayMarginals && own.mg);
+  if (foreign) return hipErrorInvalidValue;
+  const MarginalArgs* mg = own.mg;
   switch (w) {
     case Walk::Plain: {
       if (a.stride < 1 || a.logw) return hipErrorInvalidValue;
-      if (a.D <= kMaxLaneD || a.kind == VGPA_PATHS_POSTERIOR) return launch_walk<Walk::Plain>(a, st);
+      if (a.D <= kMaxLaneD || a.kind == VGPA_PATHS_POSTERIOR) return launch_walk<Walk::Plain>(a, st, own);
       if (a.model != VGPA_MODEL_L96) return hipErrorInvalidValue;
       const size_t lanes = (size_t)a.batch * a.n_paths, lds = (size_t)a.D * 64 * sizeof(double) * ((!a.R_diag || !a.x0) ? 2 : 1);
       hipLaunchKernelGGL(k_sample_l96, dim3((unsigned)((lanes + 63) / 64)), dim3(64), lds, st, a);
@@ -2256,47 +2263,47 @@ hipError_t launch_sample_walk(Walk w, const SampleArgs& a, hipStream_t st, const
     }
     case Walk::Weighted:
       if (a.stride < 1 || !a.logw || !a.start || !weighable) return hipErrorInvalidValue;
-      return launch_walk<Walk::Weighted>(a, st);
+      return launch_walk<Walk::Weighted>(a, st, own);
     case Walk::Segment:
       if (!segment || a.pf_stats || a.pf_wtab) return hipErrorInvalidValue;
-      return launch_walk<Walk::Segment>(a, st);
+      return launch_walk<Walk::Segment>(a, st, own);
     case Walk::SegmentStats:
       if (!segment || !a.pf_stats || a.pf_wtab) return hipErrorInvalidValue;
-      return launch_walk<Walk::SegmentStats>(a, st);
+      return launch_walk<Walk::SegmentStats>(a, st, own);
     case Walk::Conditional:      // (the segment's fields and the reference)
-      if (!segment || a.pf_stats || a.pf_wtab || !pf_ref) return hipErrorInvalidValue;
-      return launch_walk<Walk::Conditional>(a, st, pf_ref);
+      if (!segment || a.pf_stats || a.pf_wtab || !own.pf_ref) return hipErrorInvalidValue;
+      return launch_walk<Walk::Conditional>(a, st, own);
     case Walk::SegmentEvents:      // (the fields of SegmentStats -- the rows are where pf_stats points -- and the levels and sides)
-      if (!segment || !a.pf_stats || a.pf_wtab || !ev_level || !ev_side) return hipErrorInvalidValue;
-      return launch_walk<Walk::SegmentEvents>(a, st, nullptr, ev_level, ev_side);
+      if (!segment || !a.pf_stats || a.pf_wtab || !own.ev_level || !own.ev_side) return hipErrorInvalidValue;
+      return launch_walk<Walk::SegmentEvents>(a, st, own);
     case Walk::Replay:
       if (!segment || !a.pf_wtab || a.pf_stats || !a.pf_part || a.stride < 1 || a.pf_rows < 1) return hipErrorInvalidValue;
       if (a.n_paths > sample_max_paths(a.D)) return hipErrorInvalidValue;
-      return launch_walk<Walk::Replay>(a, st);
+      return launch_walk<Walk::Replay>(a, st, own);
     case Walk::ReplayCov:      // (the replay's fields; pf_part holds sample_cov_len(D) doubles per kept index)
       if (!segment || !a.pf_wtab || a.pf_stats || !a.pf_part || a.stride < 1 || a.pf_rows < 1) return hipErrorInvalidValue;
       if (a.n_paths > sample_max_paths(a.D)) return hipErrorInvalidValue;
-      return launch_walk<Walk::ReplayCov>(a, st);
+      return launch_walk<Walk::ReplayCov>(a, st, own);
     case Walk::ReplayMarginals:      // (the replay's fields without its weights and sums; the ladders, the integer weights, the masses)
       if (!segment || a.pf_wtab || a.pf_stats || a.pf_part || a.stride < 1 || a.pf_rows < 1 || a.n_keep < 1) return hipErrorInvalidValue;
       if (!mg || !mg->levels || !mg->qtab || !mg->mass || mg->L < 1 || mg->L > kMaxMarginalLevels) return hipErrorInvalidValue;
       if (a.n_paths > sample_max_paths(a.D)) return hipErrorInvalidValue;
-      return launch_walk<Walk::ReplayMarginals>(a, st, nullptr, nullptr, nullptr, mg);
+      return launch_walk<Walk::ReplayMarginals>(a, st, own);
     case Walk::Lineage:
       if (a.stride < 1 || a.kind != VGPA_PATHS_POSTERIOR || !a.R_diag || !a.out || !a.pf_slots || a.pf_slot_rows < 1 || a.logw) return hipErrorInvalidValue;
       if (!sample_lineages_fit(a.D, a.batch, a.n_paths)) return hipErrorInvalidValue;
-      return launch_walk<Walk::Lineage>(a, st);
+      return launch_walk<Walk::Lineage>(a, st, own);
     case Walk::Backward:      // (the lineage walk's fields and the histories)
       if (a.stride < 1 || a.kind != VGPA_PATHS_POSTERIOR || !a.R_diag || !a.out || !a.pf_slots || a.pf_slot_rows < 1 || a.logw) return hipErrorInvalidValue;
       if (!a.pf_clouds || !a.pf_hanc || a.pf_M < 1 || a.pf_n < 1 || !sample_lineages_fit(a.D, a.batch, a.n_paths)) return hipErrorInvalidValue;
-      return launch_walk<Walk::Backward>(a, st);
+      return launch_walk<Walk::Backward>(a, st, own);
     case Walk::Forecast: {
       const bool cloud = a.pf_part && a.pf_wtab && !a.out && !a.pf_slots && a.n_paths == a.pf_n;
       const bool members = a.out && a.pf_slots && a.pf_slot_rows == 1 && !a.pf_part && !a.pf_wtab;
       if (a.stride < 1 || a.kind != VGPA_PATHS_MODEL || !a.R_diag || !known_model || (a.D > kMaxLaneD && a.model != VGPA_MODEL_L96)) return hipErrorInvalidValue;
       if (!a.pf_x || a.pf_n < 1 || a.k_begin < 0 || a.k_end < a.k_begin || cloud == members || a.logw || a.pf_lw || a.pf_stats) return hipErrorInvalidValue;
       if (a.n_keep != (a.k_end - a.k_begin) / a.stride + 1 || a.n_paths > sample_max_paths(a.D)) return hipErrorInvalidValue;
-      return launch_walk<Walk::Forecast>(a, st);
+      return launch_walk<Walk::Forecast>(a, st, own);
     }
   }
   return hipErrorInvalidValue;

@@ -1599,7 +1599,7 @@ int vgpa_sample_paths_weighted(vgpa_ctx* c, const double* x, const double* x0, i
 // ParticleRequest: what one of the entry points wants from it and where the results go (nullptr: not wanted).
 // Its two choices: the rows the filter's slots carry along their lineages, and the pass that runs behind the filter.  A forecast behind
 // the filter is "fc_moments is set"; it goes with Carry::None and Behind::None alone.
-enum class Carry { None, Stats, Events };      // nothing; the path statistics (Q, G, H); the event records (X, T, N)
+// (Carry -- nothing; the path statistics (Q, G, H); the event records (X, T, N) -- is vgpa_internal.h's: the walks carry by the same word)
 // (the order matters: table() below takes every enumerator from Trajectories on as a pass with a slot table; a new pass of sums goes before it)
 enum class Behind { None, Moments, Covariance, Marginals, Trajectories, Backward, Conditional };
 struct ParticleRequest {
@@ -1633,7 +1633,7 @@ struct ParticleRun {
   double* st_cur; double* st_other;    // ... and their rows (Carry::Stats, Carry::Events)
   int n_keep, rows, slot_rows, n_blocks; size_t mom_len, n_table, n_traj;
   int k0 = 0;                          // the forecast: the absolute grid index of the cloud
-  const double* ev_level = nullptr; const int32_t* ev_side = nullptr;      // events: the levels and sides [B][D] on the device
+  WalkOwn own;                         // what the filter's segments read alone: the events' levels and sides, the reference, on the device
   // what follows from the request, derived once in setup(): the histories the device keeps (ancestors, clouds, replaced log-weights),
   // the walk of the filter's segments and whether the step between them is the conditional filter's
   bool keep_anc = false, keep_clouds = false, keep_lw = false, pinned = false;
@@ -1642,14 +1642,13 @@ struct ParticleRun {
   int buf(int which, size_t count) { return grow(c, &c->d_pf[which], &c->pf_n[which], count); }      // d_pf[which]: at least `count` doubles
 
   // For each cut -- an observation index of some problem, and the last grid index --: the segment launch up to it, then, at an
-  // observation, the step between two segments (from cur to other), and the particle buffers swap.  pf_ref, lev, side: the walk's own.
-  int cuts(Walk walk, const char* what, SampleArgs& s, const char* step_what, const std::function<hipError_t(int)>& step,
-           const double* pf_ref = nullptr, const double* lev = nullptr, const int32_t* side = nullptr, const MarginalArgs* mg = nullptr) {
+  // observation, the step between two segments (from cur to other), and the particle buffers swap.
+  int cuts(Walk walk, const char* what, SampleArgs& s, const char* step_what, const std::function<hipError_t(int)>& step, const WalkOwn& walk_own = {}) {
     int prev = 0;
     for (int k = 0; k < c->Np; k++) {
       if (!is_obs[k] && k != c->Np - 1) continue;
       s.k_begin = prev; s.k_end = k; s.pf_x = cur;
-      hipError_t e = launch_sample_walk(walk, s, c->stream, pf_ref, lev, side, mg);
+      hipError_t e = launch_sample_walk(walk, s, c->stream, walk_own);
       if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "%s failed: %s", what, hipGetErrorString(e));
       s.seg_first = 0; prev = k;
       if (!is_obs[k]) continue;
@@ -1711,12 +1710,12 @@ struct ParticleRun {
       if ((rc = buf(vgpa_ctx::PF_EVC, BD)) || (rc = buf(vgpa_ctx::PF_EVS, ints(BD))) || (q.cdf && (rc = buf(vgpa_ctx::PF_CDF, (size_t)B * n_keep * D)))) return rc;
       int32_t* d_side = reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_EVS]);
       if ((rc = upload(c, c->d_pf[vgpa_ctx::PF_EVC], q.levels, BD)) || (rc = upload(c, d_side, q.sides, BD))) return rc;
-      ev_level = c->d_pf[vgpa_ctx::PF_EVC]; ev_side = d_side;
+      own.ev_level = c->d_pf[vgpa_ctx::PF_EVC]; own.ev_side = d_side;
     }
     if (pinned) {      // the reference trajectories: uploaded once per call, read from global memory by the walk and the steps
       const size_t n_ref = (size_t)B * c->Np * D;
       if ((rc = buf(vgpa_ctx::PF_REF, n_ref)) || (rc = upload(c, c->d_pf[vgpa_ctx::PF_REF], q.ref, n_ref))) return rc;
-      f.ref = c->d_pf[vgpa_ctx::PF_REF]; f.Np = c->Np;
+      f.ref = own.pf_ref = c->d_pf[vgpa_ctx::PF_REF]; f.Np = c->Np;
     }
     // the cuts: the observation indices the kernels will see (each problem's own row and count in force), and the last grid index
     is_obs.assign((size_t)c->Np, 0);
@@ -1745,15 +1744,15 @@ struct ParticleRun {
       return cuts(segment, "conditional segment launch", a, "conditional resampling launch", [&](int k) {
         f.k = k; f.last = k == c->Np - 1 ? 1 : 0; f.x_in = cur; f.x_out = other;
         return launch_pf_cresample(f, a, c->stream);
-      }, f.ref);
-    if (q.rows == Carry::Events) LAUNCH_TRY(c, "event start rows launch", launch_pf_events_start(c->D, c->B, q.n_paths, c->Np, cur, ev_level, ev_side, st_cur, c->stream));
+      }, own);
+    if (q.rows == Carry::Events) LAUNCH_TRY(c, "event start rows launch", launch_pf_events_start(c->D, c->B, q.n_paths, c->Np, cur, own.ev_level, own.ev_side, st_cur, c->stream));
     else if (q.rows == Carry::Stats) HIP_TRY(c, hipMemsetAsync(st_cur, 0, 3 * (size_t)c->B * n * c->D * sizeof(double), c->stream));
     return cuts(segment, "particle segment launch", a, "particle resampling launch", [&](int k) {
       f.k = k; f.last = k == c->Np - 1 ? 1 : 0; f.x_in = cur; f.x_out = other; f.st_in = st_cur; f.st_out = st_other;
       std::swap(st_cur, st_other);      // (the next segment carries the rows the step is about to write)
       a.pf_stats = st_cur;
       return launch_pf_resample(f, c->stream);
-    }, nullptr, ev_level, ev_side);
+    }, own);
   }
 
   // The smoothing moments, behind the filter, whose ancestor history stays on the device: the descendant weights, then
@@ -1819,10 +1818,12 @@ struct ParticleRun {
     SampleArgs w = a;
     w.stride = q.stride; w.n_keep = n_keep; w.seg_first = 1; w.pf_stats = nullptr; w.pf_rows = rows;
     const MarginalArgs mg{c->d_pf[vgpa_ctx::PF_MGL], L, qtab, mass};
+    WalkOwn replay_own;
+    replay_own.mg = &mg;
     if ((rc = cuts(Walk::ReplayMarginals, "marginals replay launch", w, "replay gather launch", [&](int k) {
           g.k = k; g.x_in = cur; g.x_out = other;
           return launch_pf_gather(g, c->stream);
-        }, nullptr, nullptr, nullptr, &mg))) return rc;
+        }, replay_own))) return rc;
     if ((rc = download(c, q.mass, reinterpret_cast<const uint64_t*>(mass), n_mass))) return rc;
     if (q.qfinal && (rc = download(c, q.qfinal, reinterpret_cast<const uint64_t*>(qfin), (size_t)B * q.n_paths))) return rc;
     if (q.lineage_ess)      // (as in moments())

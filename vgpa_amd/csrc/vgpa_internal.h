@@ -222,6 +222,8 @@ struct ReduceArgs {
   const double* div_v;      // [B] per-problem div (1-D models: sigma_p), or nullptr
 };
 
+// What a slot of the particle filter carries along its lineage (the host's request and the walks' property use the one word)
+enum class Carry { None, Stats, Events };      // nothing; the path statistics (Q, G, H); the event records (X, T, N)
 // Euler-Maruyama sample paths (sample.hip): x_k = x_{k-1} + dt drift_{k-1}(x_{k-1}) + R xi_k on the context's grid.  The twelve things a launch
 // can do with them (the table at the top of sample.hip); the host names one at every launch_sample_walk, and SampleArgs says what each reads
 enum class Walk { Plain, Weighted, Segment, SegmentStats, Replay, Lineage, Forecast, ReplayCov, Backward, Conditional, SegmentEvents, ReplayMarginals };
@@ -292,19 +294,19 @@ struct SampleArgs {
   const double* pf_clouds;  // [B][pf_M][pf_n][D]; nullptr for every other walk
   const int32_t* pf_hanc;   // [B][pf_M][pf_n]; nullptr for every other walk
   // Walk::Conditional (vgpa_particle_conditional): Walk::Segment, every field as there, in which slot 0 of every problem
-  // is pinned to the reference trajectory pf_ref[p] -- [B][Np][D], the last argument of launch_sample_walk and no field here: the other
+  // is pinned to the reference trajectory pf_ref[p] -- [B][Np][D], WalkOwn::pf_ref and no field here: the other
   // walks' kernels take this struct alone --: it draws nothing, takes the increment the reference implies, eta* = (ref_k - ref_{k-1})
   // - dt g(ref_{k-1}), into the step's weight term in place of R xi, and its state becomes ref_k as loaded
   // Walk::SegmentEvents (vgpa_particle_events): Walk::Segment, every field as there, in which every slot carries the row
   // (X, T, N) of event records of its lineage where pf_stats points, [B][n_paths][3][D] as for SegmentStats: with g_j(x) = s_j (x_j - c_j),
   // at every step k of the segment X_j = fmax(X_j, g_j(x_k)) and, where g_j(x_k) > 0, T_j = min(T_j, k), N_j += 1 (T, N: exact integers
-  // held as doubles).  The levels c and the sides s are ev_level [B][D] and ev_side [B][D] (+1 / -1), the last arguments of
-  // launch_sample_walk and no fields here
+  // held as doubles).  The levels c and the sides s are ev_level [B][D] and ev_side [B][D] (+1 / -1), of WalkOwn
+  // and no fields here
   // Walk::ReplayMarginals (vgpa_particle_marginals): Walk::Replay's states, every field as there but pf_wtab and pf_part,
   // which stay nullptr: at a kept grid index k' stride slot i adds its integer descendant weight Q_i (MarginalArgs::qtab, the row of the
   // problem's stretch) to mass[p][k'][d][bin(x_i[d])] for every component d, bin(x) = #{l: c_l < x} over the component's ladder of L levels
 };
-// The levels, weights and result of Walk::ReplayMarginals: the last argument of launch_sample_walk and no fields of SampleArgs
+// The levels, weights and result of Walk::ReplayMarginals: WalkOwn::mg and no fields of SampleArgs
 struct MarginalArgs {
   const double* levels;            // [B][D][L], finite and strictly increasing along L
   int L;                           // 1 .. kMaxMarginalLevels
@@ -312,11 +314,17 @@ struct MarginalArgs {
   unsigned long long* mass;        // [B][n_keep][D][L + 1], zero before the first segment
 };
 constexpr int kMaxMarginalLevels = 63;
-// hipErrorInvalidValue where a field the walk reads is missing or out of range, where a field that belongs to another walk is set (pf_ref
-// in every walk but Conditional, which needs it; ev_level and ev_side in every walk but SegmentEvents, which needs both; mg in every walk but ReplayMarginals, which
-// needs it whole), and for D = 2 in every walk but Plain (no stochastic model has D = 2)
-hipError_t launch_sample_walk(Walk w, const SampleArgs& a, hipStream_t st, const double* pf_ref = nullptr, const double* ev_level = nullptr,
-                              const int32_t* ev_side = nullptr, const MarginalArgs* mg = nullptr);
+// What one walk alone reads besides SampleArgs, as the host hands it to launch_sample_walk: no other walk's kernel takes any of it
+struct WalkOwn {
+  const double* pf_ref = nullptr;        // Walk::Conditional: the reference trajectories [B][Np][D]
+  const double* ev_level = nullptr;      // Walk::SegmentEvents: the levels [B][D] ...
+  const int32_t* ev_side = nullptr;      // ... and the sides [B][D] (+1 / -1)
+  const MarginalArgs* mg = nullptr;      // Walk::ReplayMarginals
+};
+// hipErrorInvalidValue where a field the walk reads is missing or out of range, where a field that belongs to another walk is set (of
+// `own`: pf_ref in every walk but Conditional, which needs it; ev_level and ev_side in every walk but SegmentEvents, which needs both; mg
+// in every walk but ReplayMarginals, which needs it whole), and for D = 2 in every walk but Plain (no stochastic model has D = 2)
+hipError_t launch_sample_walk(Walk w, const SampleArgs& a, hipStream_t st, const WalkOwn& own = {});
 // workgroups per problem of a segment launch: the blocks of the replay's partial sums
 int sample_segment_blocks(int D, int n_paths);
 int sample_max_paths(int D);      // the largest n_paths per problem a segment, replay or forecast launch takes at this D (grid.y)
