@@ -5,6 +5,7 @@
 //                                 _grad_at :308)
 //   E_sde = trapezoid(e_t)      : src/numerics/utilities.py:144-201 (piecewise sums == one global sum)
 #include "vgpa_internal.h"
+#include "dispatch.h"
 #include "energy_small.h"
 
 namespace vgpa {
@@ -763,50 +764,24 @@ hipError_t launch_psi_from_q(int batch, int Np, int D, size_t strideA, const dou
 }
 
 hipError_t launch_grad(const GradArgs& a, hipStream_t st) {
-  if (a.D <= 4) {
-    dim3 grid((a.Np + 63) / 64, a.batch);
-    switch (a.D) {
-      case 1: hipLaunchKernelGGL(k_grad_small<1>, grid, dim3(64), 0, st, a); break;
-      case 2: hipLaunchKernelGGL(k_grad_small<2>, grid, dim3(64), 0, st, a); break;
-      case 3: hipLaunchKernelGGL(k_grad_small<3>, grid, dim3(64), 0, st, a); break;
-      default: hipLaunchKernelGGL(k_grad_small<4>, grid, dim3(64), 0, st, a); break;
-    }
-    return hipGetLastError();
-  }
+  if (a.D <= 4)      // (D < 1 is never asked; it has always gone to the D = 4 kernel)
+    return with_int<1, 4>(a.D < 1 ? 4 : a.D, [&](auto d) {
+      hipLaunchKernelGGL(k_grad_small<decltype(d)::value>, dim3((a.Np + 63) / 64, a.batch), dim3(64), 0, st, a);
+      return hipGetLastError();
+    });
   if (a.D > kMaxSmallD) return hipErrorInvalidValue;
   if (a.sigma_diag && !a.scalar_product) {
     const int nb = (a.D + 3) / 4, P = 4 * nb;
     const size_t lds = sizeof(double) * (size_t)(2 * P * (P + 1) + 3 * P);
-#define VGPA_GRAD_CASE(NBV)                                                                                          \
-  case NBV:                                                                                                          \
-    if (lds > 48 * 1024)                                                                                             \
-      (void)hipFuncSetAttribute((const void*)k_grad_mfma<NBV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL(k_grad_mfma<NBV>, dim3(a.Np, a.batch), dim3(NT), lds, st, a);                                  \
-    return hipGetLastError();
-    if (a.psi_is_q && !a.Edf && (nb == 9 || nb == 10)) {          // (what sym::stores_q allows)
-      if (lds > 48 * 1024) {
-        (void)hipFuncSetAttribute((const void*)k_grad_mfma_q<9>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)k_grad_mfma_q<10>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      }
-      const dim3 grid((a.Np + kGradTPW - 1) / kGradTPW, a.batch);
-      if (nb == 9) hipLaunchKernelGGL(k_grad_mfma_q<9>, grid, dim3(NT), lds, st, a);
-      else hipLaunchKernelGGL(k_grad_mfma_q<10>, grid, dim3(NT), lds, st, a);
-      return hipGetLastError();
-    }
-    switch (nb) {
-      VGPA_GRAD_CASE(2) VGPA_GRAD_CASE(3) VGPA_GRAD_CASE(4) VGPA_GRAD_CASE(5) VGPA_GRAD_CASE(6) VGPA_GRAD_CASE(7)
-      VGPA_GRAD_CASE(8) VGPA_GRAD_CASE(9) VGPA_GRAD_CASE(10) VGPA_GRAD_CASE(11) VGPA_GRAD_CASE(12)
-      VGPA_GRAD_CASE(13) VGPA_GRAD_CASE(14) VGPA_GRAD_CASE(15) VGPA_GRAD_CASE(16)
-      default: break;
-    }
-#undef VGPA_GRAD_CASE
+    if (a.psi_is_q && !a.Edf && (nb == 9 || nb == 10))          // (what sym::stores_q allows)
+      return with_int<9, 10>(nb, [&](auto n) {
+        return launch_lds(k_grad_mfma_q<decltype(n)::value>, dim3((a.Np + kGradTPW - 1) / kGradTPW, a.batch), dim3(NT), lds, st, a);
+      });
+    return with_int<2, kMaxSmallD / 4>(nb, [&](auto n) { return launch_lds(k_grad_mfma<decltype(n)::value>, dim3(a.Np, a.batch), dim3(NT), lds, st, a); });
   }
   const int LD = a.D + 1;
   const size_t lds = sizeof(double) * (size_t)((a.sigma_diag ? 2 : 3) * a.D * LD + 3 * a.D);
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute((const void*)k_grad, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(k_grad, dim3(a.Np, a.batch), dim3(NT), lds, st, a);
-  return hipGetLastError();
+  return launch_lds(k_grad, dim3(a.Np, a.batch), dim3(NT), lds, st, a);
 }
 
 hipError_t launch_reduce(const ReduceArgs& a, hipStream_t st) {

@@ -10,6 +10,7 @@
 //         SURVEY.md s.8a ("Algebra the kernels may exploit"); the flat np.roll of the sigma-point
 //         matrix (quirk Q1) is reproduced exactly.
 #include "vgpa_internal.h"
+#include "dispatch.h"
 #include "energy_small.h"
 #include "chol_wave.h"
 
@@ -1171,29 +1172,14 @@ hipError_t launch_energy(const EnergyArgs& a, hipStream_t st) {
     if (a.D < 4 || a.D > kMaxSmallD) return hipErrorInvalidValue;
     const bool one_matrix = (a.hyp == nullptr);      // the hyper-parameter integrands need the second LDS matrix
     if (a.tg && !one_matrix) return hipErrorInvalidValue;
-    size_t lds = (one_matrix ? l96r_lds_doubles(a.D) : l96_lds_doubles(a.D)) * sizeof(double);
+    const size_t lds = (one_matrix ? l96r_lds_doubles(a.D) : l96_lds_doubles(a.D)) * sizeof(double);
     const long long nwaves = (long long)a.Np * a.batch;
     if (nwaves > 0x7fffffffLL) return hipErrorInvalidValue;
-#define VGPA_L96_CASE(NBV)                                                                                          \
-  case NBV:                                                                                                         \
-    if (lds > 48 * 1024)                                                                                            \
-      (void)hipFuncSetAttribute(one_matrix ? (const void*)k_energy_l96_r<NBV> : (const void*)k_energy_l96<NBV>,       \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                \
-    if (a.tg) {                                                                                                     \
-      if (lds > 48 * 1024)                                                                                          \
-        (void)hipFuncSetAttribute((const void*)k_energy_l96_r<NBV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-      hipLaunchKernelGGL((k_energy_l96_r<NBV, true>), dim3((unsigned)nwaves), dim3(64), lds, st, a);                  \
-    } else                                                                                                          \
-    if (one_matrix) hipLaunchKernelGGL(k_energy_l96_r<NBV>, dim3((unsigned)nwaves), dim3(64), lds, st, a);          \
-    else hipLaunchKernelGGL(k_energy_l96<NBV>, dim3((unsigned)nwaves), dim3(64), lds, st, a);                        \
-    break;
-    switch ((a.D + 3) / 4) {
-      VGPA_L96_CASE(1) VGPA_L96_CASE(2) VGPA_L96_CASE(3) VGPA_L96_CASE(4) VGPA_L96_CASE(5) VGPA_L96_CASE(6)
-      VGPA_L96_CASE(7) VGPA_L96_CASE(8) VGPA_L96_CASE(9) VGPA_L96_CASE(10) VGPA_L96_CASE(11) VGPA_L96_CASE(12)
-      VGPA_L96_CASE(13) VGPA_L96_CASE(14) VGPA_L96_CASE(15) VGPA_L96_CASE(16)
-      default: return hipErrorInvalidValue;
-    }
-#undef VGPA_L96_CASE
+    return with_int<1, kMaxSmallD / 4>((a.D + 3) / 4, [&](auto nb) {
+      constexpr int NB = decltype(nb)::value;
+      auto kern = !one_matrix ? k_energy_l96<NB> : a.tg ? k_energy_l96_r<NB, true> : k_energy_l96_r<NB>;
+      return launch_lds(kern, dim3((unsigned)nwaves), dim3(64), lds, st, a);
+    });
   } else {
     return hipErrorInvalidValue;
   }

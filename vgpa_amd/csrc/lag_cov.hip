@@ -25,6 +25,7 @@
 // 16 rows x 2 columns a half wave reads fall into 32 different bank pairs), three images: A_k and A_{k+1} alternate, A_mid is formed as
 // A_{k+1} is written.  A thread carries its NPF elements of A_{k+2} in registers across the step's products (the HBM latency is behind them).
 #include "vgpa_internal.h"
+#include "dispatch.h"
 
 namespace vgpa {
 namespace {
@@ -269,39 +270,6 @@ __global__ void __launch_bounds__(kLagThreads) k_lag_mfma(LagArgs a) {
   }
 }
 
-template <int D>
-hipError_t launch_lane(const LagArgs& a, hipStream_t st) {
-  const size_t n = (size_t)a.batch * a.n_anchor;
-  const dim3 grid((unsigned)((n + kLagThreads - 1) / kLagThreads)), block(kLagThreads);
-  switch (a.method) {
-    case VGPA_ODE_EULER: hipLaunchKernelGGL((k_lag_lane<D, VGPA_ODE_EULER>), grid, block, 0, st, a); break;
-    case VGPA_ODE_HEUN: hipLaunchKernelGGL((k_lag_lane<D, VGPA_ODE_HEUN>), grid, block, 0, st, a); break;
-    case VGPA_ODE_RK2: hipLaunchKernelGGL((k_lag_lane<D, VGPA_ODE_RK2>), grid, block, 0, st, a); break;
-    case VGPA_ODE_RK4: hipLaunchKernelGGL((k_lag_lane<D, VGPA_ODE_RK4>), grid, block, 0, st, a); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-
-template <int NT, int METHOD>
-hipError_t launch_mfma_m(const LagArgs& a, hipStream_t st) {
-  constexpr size_t lds = LagShape<NT>::lds_bytes;
-  if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k_lag_mfma<NT, METHOD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((k_lag_mfma<NT, METHOD>), dim3((unsigned)((size_t)a.batch * a.n_anchor)), dim3(kLagThreads), lds, st, a);
-  return hipGetLastError();
-}
-
-template <int NT>
-hipError_t launch_mfma(const LagArgs& a, hipStream_t st) {
-  switch (a.method) {
-    case VGPA_ODE_EULER: return launch_mfma_m<NT, VGPA_ODE_EULER>(a, st);
-    case VGPA_ODE_HEUN: return launch_mfma_m<NT, VGPA_ODE_HEUN>(a, st);
-    case VGPA_ODE_RK2: return launch_mfma_m<NT, VGPA_ODE_RK2>(a, st);
-    case VGPA_ODE_RK4: return launch_mfma_m<NT, VGPA_ODE_RK4>(a, st);
-    default: return hipErrorInvalidValue;
-  }
-}
-
 }  // namespace
 
 bool lag_grid_fits(int D, int batch, int n_anchor) {
@@ -321,17 +289,19 @@ hipError_t launch_lag(const LagArgs& a, hipStream_t st) {
   if (!a.A || !a.start || !a.anchors || !a.out || a.D < 1 || a.D > kMaxSmallD || a.Np < 1 || a.batch < 1 || a.n_anchor < 1 || a.stride < 1 ||
       a.n_keep != (a.Np - 1) / a.stride + 1 || !lag_grid_fits(a.D, a.batch, a.n_anchor))
     return hipErrorInvalidValue;
-  switch (a.D) {
-    case 1: return launch_lane<1>(a, st);
-    case 2: return launch_lane<2>(a, st);
-    case 3: return launch_lane<3>(a, st);
-    case 4: return launch_lane<4>(a, st);
-    default: break;
-  }
-  if (a.D <= 16) return launch_mfma<16>(a, st);
-  if (a.D <= 32) return launch_mfma<32>(a, st);
-  if (a.D <= 48) return launch_mfma<48>(a, st);
-  return launch_mfma<64>(a, st);
+  const size_t n = (size_t)a.batch * a.n_anchor;
+  return with_method(a.method, [&](auto m) {
+    constexpr int METHOD = decltype(m)::value;
+    if (a.D <= kMaxLaneD)      // one lane per anchor
+      return with_int<1, kMaxLaneD>(a.D, [&](auto d) {
+        hipLaunchKernelGGL((k_lag_lane<decltype(d)::value, METHOD>), dim3((unsigned)((n + kLagThreads - 1) / kLagThreads)), dim3(kLagThreads), 0, st, a);
+        return hipGetLastError();
+      });
+    return with_int<1, 4>((a.D + 15) / 16, [&](auto tiles) {      // one workgroup per anchor, D padded to 16, 32, 48 or 64
+      constexpr int NT = 16 * decltype(tiles)::value;
+      return launch_lds(k_lag_mfma<NT, METHOD>, dim3((unsigned)n), dim3(kLagThreads), LagShape<NT>::lds_bytes, st, a);
+    });
+  });
 }
 
 }  // namespace vgpa

@@ -25,6 +25,7 @@
 #include <thread>
 
 #include "vgpa_internal.h"
+#include "dispatch.h"
 
 #include "large_d_stage.h"
 
@@ -434,65 +435,48 @@ __global__ void __launch_bounds__(NT) k_stage(StageArgs a) {
 }
 
 template <int BM, bool FULL>
-static void launch_gemm_bm_f(bool transa, const GemmArgs& g, hipStream_t st) {
+static hipError_t launch_gemm_bm_f(bool transa, const GemmArgs& g, hipStream_t st) {
   dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, g.nb);
-  const bool mid = g.A1 != nullptr;
   count_launch(gemm_counter(BM, FULL ? VGPA_LD_GEMM_FULL : VGPA_LD_GEMM_CHECKED));
-  if (transa) {
-    if (mid) hipLaunchKernelGGL((k_gemm<true, true, BM, FULL>), grid, dim3(NT), 0, st, g);
-    else hipLaunchKernelGGL((k_gemm<true, false, BM, FULL>), grid, dim3(NT), 0, st, g);
-  } else {
-    if (mid) hipLaunchKernelGGL((k_gemm<false, true, BM, FULL>), grid, dim3(NT), 0, st, g);
-    else hipLaunchKernelGGL((k_gemm<false, false, BM, FULL>), grid, dim3(NT), 0, st, g);
-  }
+  return with_flag(transa, [&](auto ta) { return with_flag(g.A1 != nullptr, [&](auto mid) {
+    hipLaunchKernelGGL((k_gemm<decltype(ta)::value, decltype(mid)::value, BM, FULL>), grid, dim3(NT), 0, st, g);
+    return hipGetLastError();
+  }); });
 }
 
-template <int BM>
-static void launch_gemm_bm_v(bool transa, const GemmArgs& g, hipStream_t st) {
+// The 16-byte-load kernels on full, aligned shapes.  SEG: a K-chunk launch (no mid-point operand: the sharded driver forms it once per
+// step).  Four register sets of loads in flight and no load under a branch (k_gemm_v, PFU) when the k-tile count allows it and there is
+// no mid-point operand: D = 1024 44.6 -> 39.6 us per product (47 -> 54 TFLOP/s; 2 sets 44.1, 8 sets 40.1), D = 2048 forward recursion
+// 44.0 -> 47.7 TFLOP/s
+template <int BM, bool SEG>
+static hipError_t launch_gemm_bm_v(bool transa, const GemmArgs& g, hipStream_t st) {
   dim3 grid(g.N / BN, g.M / BM, g.nb);
-  const bool mid = g.A1 != nullptr;
-  // four register sets of loads in flight and no load under a branch (k_gemm_v, PFU) when the k-tile count allows it: D = 1024
-  // 44.6 -> 39.6 us per product (47 -> 54 TFLOP/s; 2 sets 44.1, 8 sets 40.1), D = 2048 forward recursion 44.0 -> 47.7 TFLOP/s
-  if (!mid && (g.K / BK) % 4 == 0) {
-    count_launch(gemm_counter(BM, VGPA_LD_GEMM_VEC4));
-    if (transa) hipLaunchKernelGGL((k_gemm_v<true, false, BM, false, 4>), grid, dim3(NT), 0, st, g);
-    else hipLaunchKernelGGL((k_gemm_v<false, false, BM, false, 4>), grid, dim3(NT), 0, st, g);
-    return;
-  }
-  count_launch(gemm_counter(BM, VGPA_LD_GEMM_VEC));
-  if (transa) {
-    if (mid) hipLaunchKernelGGL((k_gemm_v<true, true, BM>), grid, dim3(NT), 0, st, g);
-    else hipLaunchKernelGGL((k_gemm_v<true, false, BM>), grid, dim3(NT), 0, st, g);
-  } else {
-    if (mid) hipLaunchKernelGGL((k_gemm_v<false, true, BM>), grid, dim3(NT), 0, st, g);
-    else hipLaunchKernelGGL((k_gemm_v<false, false, BM>), grid, dim3(NT), 0, st, g);
-  }
+  const bool mid = g.A1 != nullptr, four = !mid && (g.K / BK) % 4 == 0;
+  count_launch(gemm_counter(BM, SEG ? (four ? VGPA_LD_GEMM_SEG4 : VGPA_LD_GEMM_SEG) : (four ? VGPA_LD_GEMM_VEC4 : VGPA_LD_GEMM_VEC)));
+  return with_flag(transa, [&](auto ta) { return with_flag(mid, [&](auto md) { return with_flag(four, [&](auto f4) {
+    constexpr bool MID = decltype(md)::value, FOUR = decltype(f4)::value;
+    if constexpr ((MID && FOUR) || (MID && SEG)) {
+      return hipErrorInvalidValue;      // (never asked: see `four`, and launch_gemm_bm for SEG)
+    } else {
+      hipLaunchKernelGGL((k_gemm_v<decltype(ta)::value, MID, BM, SEG, FOUR ? 4 : 0>), grid, dim3(NT), 0, st, g);
+      return hipGetLastError();
+    }
+  }); }); });
 }
 
 template <int BM>
-static void launch_gemm_bm(bool transa, const GemmArgs& g, hipStream_t st) {
+static hipError_t launch_gemm_bm(bool transa, const GemmArgs& g, hipStream_t st) {
   const bool full = g.M % BM == 0 && g.N % BN == 0 && g.K % BK == 0;
   auto al16 = [](const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
   const bool vec = full && g.lda % 2 == 0 && g.ldb % 2 == 0 && al16(g.A0) && al16(g.A1) && al16(g.B);
   const bool seg = g.seg_tiles > 0 || g.accumulate;
-  if (vec && seg && !g.A1) {        // K-chunk launch (no mid-point operand: the sharded driver forms it once per step)
+  if (vec && seg && !g.A1) {
     GemmArgs h = g;
     if (!h.seg_tiles) { h.seg_tiles = h.K / BK; h.seg_stride = h.K; }
-    dim3 grid(g.N / BN, g.M / BM, g.nb);
-    if ((h.K / BK) % 4 == 0) {        // four register sets of loads in flight (launch_gemm_bm_v)
-      count_launch(gemm_counter(BM, VGPA_LD_GEMM_SEG4));
-      if (transa) hipLaunchKernelGGL((k_gemm_v<true, false, BM, true, 4>), grid, dim3(NT), 0, st, h);
-      else hipLaunchKernelGGL((k_gemm_v<false, false, BM, true, 4>), grid, dim3(NT), 0, st, h);
-      return;
-    }
-    count_launch(gemm_counter(BM, VGPA_LD_GEMM_SEG));
-    if (transa) hipLaunchKernelGGL((k_gemm_v<true, false, BM, true>), grid, dim3(NT), 0, st, h);
-    else hipLaunchKernelGGL((k_gemm_v<false, false, BM, true>), grid, dim3(NT), 0, st, h);
-    return;
+    return launch_gemm_bm_v<BM, true>(transa, h, st);
   }
-  if (vec && !seg) launch_gemm_bm_v<BM>(transa, g, st);
-  else if (full) launch_gemm_bm_f<BM, true>(transa, g, st);
-  else launch_gemm_bm_f<BM, false>(transa, g, st);
+  if (vec && !seg) return launch_gemm_bm_v<BM, false>(transa, g, st);
+  return with_flag(full, [&](auto f) { return launch_gemm_bm_f<BM, decltype(f)::value>(transa, g, st); });
 }
 
 hipError_t launch_gemm(bool transa, const GemmArgs& g, hipStream_t st) {
@@ -514,10 +498,9 @@ hipError_t launch_gemm(bool transa, const GemmArgs& g, hipStream_t st) {
     const double score = (double)w / (double)((w + 255) / 256 * 256) * worth[h] * (w < 512 ? std::pow((double)w / 512.0, 0.22) : 1.0);
     if (score >= best_score) { best_score = score; best = heights[h]; }      // (ties: the taller tile)
   }
-  if (best == 128) launch_gemm_bm<128>(transa, g, st);
-  else if (best == 64) launch_gemm_bm<64>(transa, g, st);
-  else launch_gemm_bm<32>(transa, g, st);
-  return hipGetLastError();
+  if (best == 128) return launch_gemm_bm<128>(transa, g, st);
+  if (best == 64) return launch_gemm_bm<64>(transa, g, st);
+  return launch_gemm_bm<32>(transa, g, st);
 }
 
 // One rank owns every row (Mp = D, W = Wcol): R = -(W + W^T) + E is symmetric, so a workgroup takes the PAIR of tiles (by, bx)

@@ -10,6 +10,7 @@
 //                              trailing  : C[R,R] -= L[R,J] L[R,J]^T              (GEMM, lower tiles only)
 //   inverse  (by halves)    :  X_21 = -X_22 (L_21 X_11), log2(T) levels          (2 GEMMs per level)
 #include "vgpa_internal.h"
+#include "dispatch.h"
 #include "chol_wave.h"
 
 namespace vgpa {
@@ -343,16 +344,11 @@ hipError_t gemm_b(bool ta, bool tb, GemmB g, int nb, hipStream_t st, int nsub = 
   const bool vec = !tb && g.M % 64 == 0 && g.N % BN == 0 && g.K % BK == 0 && g.lda % 2 == 0 &&
                    g.ldb % 2 == 0 && g.sA % 2 == 0 && g.sB % 2 == 0 && al16(g.A) && al16(g.B) &&
                    (nsub == 1 || (g.sA2 % 2 == 0 && g.sB2 % 2 == 0));
-  if (vec) {
-    if (ta) hipLaunchKernelGGL((k_gemm_bv<true>), grid, dim3(NT), 0, st, g);
-    else hipLaunchKernelGGL((k_gemm_bv<false>), grid, dim3(NT), 0, st, g);
+  return with_flag(ta, [&](auto a) { return with_flag(tb, [&](auto b) {
+    auto kern = vec ? k_gemm_bv<decltype(a)::value> : k_gemm_b<decltype(a)::value, decltype(b)::value, 64>;      // (vec: never with tb)
+    hipLaunchKernelGGL(kern, grid, dim3(NT), 0, st, g);
     return hipGetLastError();
-  }
-  if (ta && tb) hipLaunchKernelGGL((k_gemm_b<true, true, 64>), grid, dim3(NT), 0, st, g);
-  else if (ta) hipLaunchKernelGGL((k_gemm_b<true, false, 64>), grid, dim3(NT), 0, st, g);
-  else if (tb) hipLaunchKernelGGL((k_gemm_b<false, true, 64>), grid, dim3(NT), 0, st, g);
-  else hipLaunchKernelGGL((k_gemm_b<false, false, 64>), grid, dim3(NT), 0, st, g);
-  return hipGetLastError();
+  }); });
 }
 
 // ---- 64 x 64 diagonal block: L_JJ = chol(C_JJ) (in place, strict upper zeroed) and X_JJ = L_JJ^-1 ------------------
@@ -832,11 +828,6 @@ static hipError_t lde_energy_impl(int D, int Np, double theta, const double* isg
   const int T = (D + NBLK - 1) / NBLK, M = 2 * D + 1;
   const double kappa = 1.05 * D, c = D + kappa;
   constexpr size_t lds_diagm = sizeof(double) * (2 * NBLK * (NBLK + 1) + 16 * (NBLK / 4) + NBLK);
-  static const bool diag_lds = [] {
-    (void)hipFuncSetAttribute((const void*)k_diag64m, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_diagm);
-    return true;
-  }();
-  (void)diag_lds;
   constexpr int wpan = 4;                             // diagonal blocks per outer panel of the Cholesky (see the trailing update)
   const bool two_halves = side != nullptr && side != st;
   EventPair evs;                                      // (destroyed on every return path)
@@ -880,7 +871,7 @@ static hipError_t lde_energy_impl(int D, int Np, double theta, const double* isg
         const int n = hb_[hh + 1] - hb_[hh];
         double* Ch = C + (size_t)hb_[hh] * DD;
         double* Xh = X + (size_t)hb_[hh] * DD;
-        hipLaunchKernelGGL(k_diag64m, dim3(n), dim3(64), lds_diagm, sh, D, J, Ch, Xh, DD, DD, status, 30);
+        LDE_TRY_FORKED(launch_lds(k_diag64m, dim3(n), dim3(64), lds_diagm, sh, D, J, Ch, Xh, DD, DD, status, 30));
         if (r1 >= D) continue;
         GemmB p{};   // L[R,J] = C[R,J] X_JJ^T   (in place)
         p.M = Mr; p.N = kw; p.K = kw; p.A = Ch + (size_t)r1 * D + J * NBLK; p.lda = D; p.sA = DD;

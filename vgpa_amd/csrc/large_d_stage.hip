@@ -7,6 +7,7 @@
 #include <cstdlib>
 
 #include "large_d_stage.h"
+#include "dispatch.h"
 
 namespace vgpa {
 namespace ld {
@@ -422,21 +423,18 @@ hipError_t launch_stage_fused(int kind, const StageArgs& a, hipStream_t st) {
   if (kind == 0) {
     const dim3 grid(nt * (nt + 1) / 2 + nvec, 1, a.nb);
     count_launch((a.fwd ? VGPA_LD_COUNT_STAGE_PROD_FWD : VGPA_LD_COUNT_STAGE_PROD_BWD) + (a.M1 ? 1 : 0));
-    if (a.fwd) {
-      if (a.M1) hipLaunchKernelGGL((k_stage_prod<false, true>), grid, dim3(NT), 0, st, a);
-      else hipLaunchKernelGGL((k_stage_prod<false, false>), grid, dim3(NT), 0, st, a);
-    } else {
-      if (a.M1) hipLaunchKernelGGL((k_stage_prod<true, true>), grid, dim3(NT), 0, st, a);
-      else hipLaunchKernelGGL((k_stage_prod<true, false>), grid, dim3(NT), 0, st, a);
-    }
-  } else {
-    const int nmat = nt * (nt - 1) / 2 + (nt + 1) / 2;
-    const dim3 grid(8 * ((nmat + 7) / 8) + nvec, 1, a.nb);      // (matrix workgroups padded to whole XCD rounds: see k_stage_wide)
-    count_launch(a.fwd ? VGPA_LD_COUNT_STAGE_WIDE_FWD : VGPA_LD_COUNT_STAGE_WIDE_BWD);
-    if (a.fwd) hipLaunchKernelGGL((k_stage_wide<false>), grid, dim3(NT), 0, st, a);
-    else hipLaunchKernelGGL((k_stage_wide<true>), grid, dim3(NT), 0, st, a);
+    return with_flag(!a.fwd, [&](auto ta) { return with_flag(a.M1 != nullptr, [&](auto mid) {
+      hipLaunchKernelGGL((k_stage_prod<decltype(ta)::value, decltype(mid)::value>), grid, dim3(NT), 0, st, a);
+      return hipGetLastError();
+    }); });
   }
-  return hipGetLastError();
+  const int nmat = nt * (nt - 1) / 2 + (nt + 1) / 2;
+  const dim3 grid(8 * ((nmat + 7) / 8) + nvec, 1, a.nb);      // (matrix workgroups padded to whole XCD rounds: see k_stage_wide)
+  count_launch(a.fwd ? VGPA_LD_COUNT_STAGE_WIDE_FWD : VGPA_LD_COUNT_STAGE_WIDE_BWD);
+  return with_flag(!a.fwd, [&](auto ta) {
+    hipLaunchKernelGGL((k_stage_wide<decltype(ta)::value>), grid, dim3(NT), 0, st, a);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace ld

@@ -12,6 +12,7 @@
 //   backward: euler.py:94-154, heun.py:113-190, runge_kutta2.py:104-194, runge_kutta4.py:115-211
 //             (jumps added after the step, Q9; f_lam uses A.lam, Q3)
 #include "vgpa_internal.h"
+#include "dispatch.h"
 
 namespace vgpa {
 namespace {
@@ -412,33 +413,25 @@ hipError_t launch_m(const OdeArgs& a, hipStream_t st) {
   const int D = a.D, DD = D * D;
   const size_t lds = (size_t)(3 * DD + 2 * D) * sizeof(double);
   const int ept = (DD + NT - 1) / NT;
-  dim3 grid(a.batch), block(NT);
-#define VGPA_LAUNCH(E)                                                                       \
-  do {                                                                                       \
-    auto kern = FWD ? k_fwd_generic<METHOD, E> : a.js_const_stride ? k_bwd_generic<METHOD, E, true> : k_bwd_generic<METHOD, E>; \
-    if (lds > 48 * 1024)                                                                      \
-      (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL(kern, grid, block, lds, st, a);                                        \
-  } while (0)
-  if (ept <= 1) VGPA_LAUNCH(1);
-  else if (ept <= 4) VGPA_LAUNCH(4);
-  else if (ept <= 8) VGPA_LAUNCH(8);
-  else VGPA_LAUNCH(16);
-#undef VGPA_LAUNCH
-  return hipGetLastError();
+  const int ept_fit = ept <= 1 ? 1 : ept <= 4 ? 4 : ept <= 8 ? 8 : 16;      // elements per thread: the kernels exist for 1, 4, 8, 16
+  return with_int<1, 16>(ept_fit, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    if constexpr (E == 1 || E == 4 || E == 8 || E == 16) {
+      auto kern = FWD ? k_fwd_generic<METHOD, E> : a.js_const_stride ? k_bwd_generic<METHOD, E, true> : k_bwd_generic<METHOD, E>;
+      return launch_lds(kern, dim3(a.batch), dim3(NT), lds, st, a);
+    } else {
+      return hipErrorInvalidValue;
+    }
+  });
 }
 
 }  // namespace
 
 hipError_t launch_ode_generic(int method, bool fwd, const OdeArgs& a, hipStream_t st) {
   if (a.D < 1 || a.D > kMaxSmallD) return hipErrorInvalidValue;
-  switch (method) {
-    case VGPA_ODE_EULER: return fwd ? launch_m<VGPA_ODE_EULER, true>(a, st) : launch_m<VGPA_ODE_EULER, false>(a, st);
-    case VGPA_ODE_HEUN: return fwd ? launch_m<VGPA_ODE_HEUN, true>(a, st) : launch_m<VGPA_ODE_HEUN, false>(a, st);
-    case VGPA_ODE_RK2: return fwd ? launch_m<VGPA_ODE_RK2, true>(a, st) : launch_m<VGPA_ODE_RK2, false>(a, st);
-    case VGPA_ODE_RK4: return fwd ? launch_m<VGPA_ODE_RK4, true>(a, st) : launch_m<VGPA_ODE_RK4, false>(a, st);
-  }
-  return hipErrorInvalidValue;
+  return with_method(method, [&](auto m) {
+    return with_flag(fwd, [&](auto f) { return launch_m<decltype(m)::value, decltype(f)::value>(a, st); });
+  });
 }
 
 }  // namespace vgpa

@@ -30,9 +30,12 @@
 // + vectors + the constant matrix jump 13 KB: 82 KB.
 #pragma once
 #include "vgpa_internal.h"
+#include "dispatch.h"
 
 namespace vgpa {
 namespace sym {
+constexpr int kMaxNB = kMaxSmallD / 4;      // NB = (D + 3) / 4 of the symmetric-unit kernels (ode_sym_impl.h): D <= 64
+
 // the backward kernels that can store Q''_t = Sigma^-1 A_t - 2 Psi_t instead of Psi_t (OdeArgs::q_on): the fragment-cover
 // kernels (ode_sym_impl.h, 33 <= D <= 40) of the mid-point methods with sparse jumps
 constexpr bool stores_q(int method, int D) {
@@ -828,11 +831,7 @@ hipError_t launch_pe(const OdeArgs& a, hipStream_t st) {
   static_assert(!(DENSEJ && PJ), "the per-problem constant jump belongs to the kernels with sparse jumps");
   constexpr size_t lds = Geo<NB>::LDS_DOUBLES * sizeof(double);
   static_assert(lds <= 160 * 1024, "LDS budget");
-  auto kern = k_ode_pe<METHOD, FWD, NB, DENSEJ, PJ>;
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(kern, dim3(a.batch), dim3(64 * kNPW + kNE), lds, st, a);
-  return hipGetLastError();
+  return launch_lds(k_ode_pe<METHOD, FWD, NB, DENSEJ, PJ>, dim3(a.batch), dim3(64 * kNPW + kNE), lds, st, a);
 }
 
 template <int METHOD, bool FWD, int NB>

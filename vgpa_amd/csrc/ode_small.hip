@@ -25,6 +25,7 @@
 #include <cstdlib>
 
 #include "vgpa_internal.h"
+#include "dispatch.h"
 #include "energy_small.h"
 
 namespace vgpa {
@@ -874,40 +875,25 @@ __global__ void __launch_bounds__(NTS) __attribute__((amdgpu_waves_per_eu(1, 1))
 template <int METHOD, bool FWD, int D>
 hipError_t launch_d(const OdeArgs& a, hipStream_t st) {
   dim3 grid((a.batch + NTS - 1) / NTS), block(NTS);
-  constexpr int T = (D == 1) ? 16 : (D == 2 ? 8 : 4);      // grid points per chunk: the LDS of four waves per CU decides
-  if (FWD && a.msT) {
-    if constexpr (D == 1 || D == 3) {      // (the models of the fused lane pass)
-      constexpr int TT = D == 3 ? 6 : 16;
-      if (a.Sigma_stride) hipLaunchKernelGGL((k_fwd_lane<METHOD, D, TT, true, true>), grid, block, 0, st, a);
-      else hipLaunchKernelGGL((k_fwd_lane<METHOD, D, TT, true>), grid, block, 0, st, a);
+  if constexpr (FWD) {
+    return with_flag(a.msT != nullptr, [&](auto out_t) { return with_flag(a.Sigma_stride != 0, [&](auto ps) {
+      constexpr bool OUT_T = decltype(out_t)::value;
+      // grid points per chunk: the LDS of four waves per CU decides
+      constexpr int T = OUT_T ? (D == 3 ? 6 : 16) : (D == 1) ? 16 : (D == 2 ? 8 : 4);
+      if constexpr (!OUT_T || D == 1 || D == 3) {      // (the models of the fused lane pass)
+        hipLaunchKernelGGL((k_fwd_lane<METHOD, D, T, OUT_T, decltype(ps)::value>), grid, block, 0, st, a);
+        return hipGetLastError();
+      } else {
+        return hipErrorInvalidValue;
+      }
+    }); });
+  } else {
+    if (a.js_const_stride && (!a.obs_idx_stride || a.js_dense)) return hipErrorInvalidValue;      // (the lane's own jump row comes with the lane's own observation index)
+    return with_flag(a.js_const_stride != 0, [&](auto pj) {
+      hipLaunchKernelGGL((k_bwd_small<METHOD, D, decltype(pj)::value>), grid, block, 0, st, a);
       return hipGetLastError();
-    }
-    return hipErrorInvalidValue;
+    });
   }
-  if (FWD && a.Sigma_stride) hipLaunchKernelGGL((k_fwd_lane<METHOD, D, T, false, true>), grid, block, 0, st, a);
-  else if (FWD) hipLaunchKernelGGL((k_fwd_lane<METHOD, D, T>), grid, block, 0, st, a);
-  else if (a.js_const_stride) {
-    if (!a.obs_idx_stride || a.js_dense) return hipErrorInvalidValue;      // (the lane's own jump row comes with the lane's own observation index)
-    hipLaunchKernelGGL((k_bwd_small<METHOD, D, true>), grid, block, 0, st, a);
-  } else hipLaunchKernelGGL((k_bwd_small<METHOD, D>), grid, block, 0, st, a);
-  return hipGetLastError();
-}
-
-template <int METHOD, bool FWD>
-hipError_t launch_m(const OdeArgs& a, hipStream_t st) {
-  switch (a.D) {
-    case 1: return launch_d<METHOD, FWD, 1>(a, st);
-    case 2: return launch_d<METHOD, FWD, 2>(a, st);
-    case 3: return launch_d<METHOD, FWD, 3>(a, st);
-    case 4: return launch_d<METHOD, FWD, 4>(a, st);
-  }
-  return hipErrorInvalidValue;
-}
-
-template <int METHOD, int MODEL, int T, bool PT, bool PP, bool PJ = false>
-void launch_sweep_lane_k(const LaneSweepArgs& q, dim3 grid, dim3 block, hipStream_t st) {
-  if (q.want_grad) hipLaunchKernelGGL((k_sweep_lane<METHOD, MODEL, true, T, PT, PP, PJ>), grid, block, 0, st, q);
-  else hipLaunchKernelGGL((k_sweep_lane<METHOD, MODEL, false, T, PT, PP>), grid, block, 0, st, q);      // (F alone takes no jump)
 }
 
 template <int METHOD, int MODEL>
@@ -919,44 +905,29 @@ hipError_t launch_sweep_mm(const LaneSweepArgs& q, hipStream_t st) {
   // 4.67 | 5.16-5.49 ms per 65536 problems.
   constexpr int T = (MODEL == VGPA_MODEL_L63) ? 4 : 16;
   if (q.o.obs_idx_stride && !q.o.jmT) return hipErrorInvalidValue;      // (per-problem times read the jumps from jmT)
-  if (q.o.js_const_stride) {      // per-problem observation model: on the per-problem-times kernels
-    if (!q.o.obs_idx_stride || !q.o.js_const) return hipErrorInvalidValue;
-    if (q.theta_v) {
-      if (!q.sigma1_v || !q.isig_v) return hipErrorInvalidValue;
-      launch_sweep_lane_k<METHOD, MODEL, T, true, true, true>(q, grid, block, st);
-    } else launch_sweep_lane_k<METHOD, MODEL, T, true, false, true>(q, grid, block, st);
-    return hipGetLastError();
-  }
-  if (q.theta_v) {
-    if (!q.sigma1_v || !q.isig_v) return hipErrorInvalidValue;
-    if (q.o.obs_idx_stride) launch_sweep_lane_k<METHOD, MODEL, T, true, true>(q, grid, block, st);
-    else launch_sweep_lane_k<METHOD, MODEL, T, false, true>(q, grid, block, st);
-  } else if (q.o.obs_idx_stride) launch_sweep_lane_k<METHOD, MODEL, T, true, false>(q, grid, block, st);
-  else launch_sweep_lane_k<METHOD, MODEL, T, false, false>(q, grid, block, st);
-  return hipGetLastError();
-}
-
-template <int METHOD>
-hipError_t launch_sweep_m(const LaneSweepArgs& q, hipStream_t st) {
-  switch (q.model) {
-    case VGPA_MODEL_OU: return launch_sweep_mm<METHOD, VGPA_MODEL_OU>(q, st);
-    case VGPA_MODEL_DW: return launch_sweep_mm<METHOD, VGPA_MODEL_DW>(q, st);
-    case VGPA_MODEL_L63: return launch_sweep_mm<METHOD, VGPA_MODEL_L63>(q, st);
-  }
-  return hipErrorInvalidValue;
+  // per-problem observation model: on the per-problem-times kernels
+  if (q.o.js_const_stride && (!q.o.obs_idx_stride || !q.o.js_const)) return hipErrorInvalidValue;
+  if (q.theta_v && (!q.sigma1_v || !q.isig_v)) return hipErrorInvalidValue;
+  return with_flag(q.want_grad != 0, [&](auto grad) { return with_flag(q.o.obs_idx_stride != 0, [&](auto pt) {
+    return with_flag(q.theta_v != nullptr, [&](auto pp) { return with_flag(q.o.js_const_stride != 0, [&](auto pj) {
+      constexpr bool GRAD = decltype(grad)::value, PT = decltype(pt)::value, PJ = decltype(pj)::value;
+      if constexpr (PJ && !PT) {
+        return hipErrorInvalidValue;      // (refused above)
+      } else {
+        hipLaunchKernelGGL((k_sweep_lane<METHOD, MODEL, GRAD, T, PT, decltype(pp)::value, GRAD && PJ>), grid, block, 0, st, q);      // (F alone takes no jump)
+        return hipGetLastError();
+      }
+    }); });
+  }); });
 }
 
 }  // namespace
 
 hipError_t launch_ode_small(int method, bool fwd, const OdeArgs& a, hipStream_t st) {
   if (a.D < 1 || a.D > kMaxLaneD) return hipErrorInvalidValue;
-  switch (method) {
-    case VGPA_ODE_EULER: return fwd ? launch_m<VGPA_ODE_EULER, true>(a, st) : launch_m<VGPA_ODE_EULER, false>(a, st);
-    case VGPA_ODE_HEUN: return fwd ? launch_m<VGPA_ODE_HEUN, true>(a, st) : launch_m<VGPA_ODE_HEUN, false>(a, st);
-    case VGPA_ODE_RK2: return fwd ? launch_m<VGPA_ODE_RK2, true>(a, st) : launch_m<VGPA_ODE_RK2, false>(a, st);
-    case VGPA_ODE_RK4: return fwd ? launch_m<VGPA_ODE_RK4, true>(a, st) : launch_m<VGPA_ODE_RK4, false>(a, st);
-  }
-  return hipErrorInvalidValue;
+  return with_method(method, [&](auto m) { return with_flag(fwd, [&](auto f) { return with_int<1, 4>(a.D, [&](auto d) {
+    return launch_d<decltype(m)::value, decltype(f)::value, decltype(d)::value>(a, st);
+  }); }); });
 }
 
 namespace {
@@ -1094,49 +1065,37 @@ hipError_t launch_ms_untranspose(int D, int Np, int batch, int bpad, const doubl
 hipError_t launch_obs_lane(const ObsArgs& a, const double* msT, int bpad, double* jmT, hipStream_t st) {
   const dim3 grid((a.batch + NTS - 1) / NTS), block(NTS);
   if (a.n_obs_v && (!a.obs_const_v || !a.Q_stride || !a.K_stride || !a.rinv_stride)) return hipErrorInvalidValue;
-  if (a.D == 1 && a.n_obs_v) hipLaunchKernelGGL((k_obs_lane<1, true>), grid, block, 0, st, a, msT, bpad, jmT);
-  else if (a.D == 3 && a.n_obs_v) hipLaunchKernelGGL((k_obs_lane<3, true>), grid, block, 0, st, a, msT, bpad, jmT);
-  else if (a.D == 1) hipLaunchKernelGGL(k_obs_lane<1>, grid, block, 0, st, a, msT, bpad, jmT);
-  else if (a.D == 3) hipLaunchKernelGGL(k_obs_lane<3>, grid, block, 0, st, a, msT, bpad, jmT);
-  else return hipErrorInvalidValue;
-  return hipGetLastError();
+  return with_int<1, 3>(a.D, [&](auto d) { return with_flag(a.n_obs_v != nullptr, [&](auto pm) {
+    constexpr int D = decltype(d)::value;
+    if constexpr (D == 1 || D == 3) {
+      hipLaunchKernelGGL((k_obs_lane<D, decltype(pm)::value>), grid, block, 0, st, a, msT, bpad, jmT);
+      return hipGetLastError();
+    } else {
+      return hipErrorInvalidValue;
+    }
+  }); });
 }
 
 bool sweep_lane_supported(int model, int D) {
   return (model == VGPA_MODEL_L63 && D == 3) || ((model == VGPA_MODEL_OU || model == VGPA_MODEL_DW) && D == 1);
 }
 
-namespace {
-template <int MODEL>
-hipError_t launch_theta_lane_m(const ThetaLaneArgs& q, hipStream_t st) {
-  const dim3 grid((q.batch + NTS - 1) / NTS), block(NTS);
-  constexpr int T = (MODEL == VGPA_MODEL_L63) ? 4 : 16;      // (the chunk sizes of k_sweep_lane)
-  if (q.theta_v) hipLaunchKernelGGL((k_theta_lane<MODEL, T, true>), grid, block, 0, st, q);
-  else hipLaunchKernelGGL((k_theta_lane<MODEL, T, false>), grid, block, 0, st, q);
-  return hipGetLastError();
-}
-}  // namespace
-
 hipError_t launch_theta_lane(const ThetaLaneArgs& q, hipStream_t st) {
   // (32-bit byte offsets inside a wave's 64 problems, like every lane kernel: the stepper's choice of this path guarantees it)
   if (!sweep_lane_supported(q.model, q.D) || q.Np < 2 || !q.msT || !q.out || q.stride_x >= ((size_t)1 << 22)) return hipErrorInvalidValue;
-  switch (q.model) {
-    case VGPA_MODEL_OU: return launch_theta_lane_m<VGPA_MODEL_OU>(q, st);
-    case VGPA_MODEL_DW: return launch_theta_lane_m<VGPA_MODEL_DW>(q, st);
-    case VGPA_MODEL_L63: return launch_theta_lane_m<VGPA_MODEL_L63>(q, st);
-  }
-  return hipErrorInvalidValue;
+  const dim3 grid((q.batch + NTS - 1) / NTS), block(NTS);
+  return with_model(q.model, [&](auto model) { return with_flag(q.theta_v != nullptr, [&](auto pp) {
+    constexpr int MODEL = decltype(model)::value, T = (MODEL == VGPA_MODEL_L63) ? 4 : 16;      // (the chunk sizes of k_sweep_lane)
+    hipLaunchKernelGGL((k_theta_lane<MODEL, T, decltype(pp)::value>), grid, block, 0, st, q);
+    return hipGetLastError();
+  }); });
 }
 
 hipError_t launch_sweep_lane(int method, const LaneSweepArgs& q, hipStream_t st) {
   if (!sweep_lane_supported(q.model, q.o.D) || q.o.js_dense || q.o.Np < 2 || !q.o.msT) return hipErrorInvalidValue;
-  switch (method) {
-    case VGPA_ODE_EULER: return launch_sweep_m<VGPA_ODE_EULER>(q, st);
-    case VGPA_ODE_HEUN: return launch_sweep_m<VGPA_ODE_HEUN>(q, st);
-    case VGPA_ODE_RK2: return launch_sweep_m<VGPA_ODE_RK2>(q, st);
-    case VGPA_ODE_RK4: return launch_sweep_m<VGPA_ODE_RK4>(q, st);
-  }
-  return hipErrorInvalidValue;
+  return with_method(method, [&](auto m) { return with_model(q.model, [&](auto model) {
+    return launch_sweep_mm<decltype(m)::value, decltype(model)::value>(q, st);
+  }); });
 }
 
 }  // namespace vgpa

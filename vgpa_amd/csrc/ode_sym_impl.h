@@ -54,8 +54,6 @@ using mfma::OP_M;
 using mfma::OP_R;
 using mfma::OP_X;
 
-constexpr int kMaxNB = 16;          // D <= 64
-
 // ---- runs: a cover of the unordered pairs {c, j} of super-block indices (loops included) by stars of <= 2 edges ---------
 // Run = super-row c with up to two partners.  Greedy: every loop (c, c) with the edge to c + 1; then, vertex by vertex, two
 // uncovered edges at a time; what is left are single edges.  Returns the `want`-th run (c = -1 beyond the last one) and,
@@ -1616,19 +1614,11 @@ hipError_t launch_variant(const OdeArgs& a, hipStream_t st) {
   if constexpr (sym_variant_exists<METHOD, FWD, NB>(V)) {
     constexpr SymLaunchShape L = sym_launch_shape<NB>(V);
     static_assert(L.lds <= 160 * 1024, "LDS budget");
-    auto kern = k_ode_sym<METHOD, FWD, NB, DENSE, L.gr, L.wpe, QOUT, (ROLES > 0), GRAD, (ROLES == 2), PJ>;
-    if (L.lds > 48 * 1024)
-      (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds);
-    hipLaunchKernelGGL(kern, dim3(a.batch), dim3(L.threads), L.lds, st, a);
-    return hipGetLastError();
+    return launch_lds(k_ode_sym<METHOD, FWD, NB, DENSE, L.gr, L.wpe, QOUT, (ROLES > 0), GRAD, (ROLES == 2), PJ>, dim3(a.batch), dim3(L.threads), L.lds, st, a);
   } else {
     return hipErrorInvalidValue;
   }
 }
-
-// a run-time flag as a compile-time one: f(std::true_type) or f(std::false_type)
-template <class F>
-hipError_t with_flag(bool on, F f) { return on ? f(std::true_type{}) : f(std::false_type{}); }
 
 // helper_roles: Plan::helper_roles (vgpa_api.hip).  The gradient-wave kernel has its one helper role whatever the count says.
 template <int METHOD, bool FWD, int NB>
@@ -1638,14 +1628,10 @@ hipError_t launch_sym(const OdeArgs& a, int helper_roles, hipStream_t st) {
   if (!sym_variant_exists<METHOD, FWD, NB>(v)) return hipErrorInvalidValue;      // (q_on / grad_on asked of a kernel without them included)
   if (v.grad && (!a.s_packed || !a.g || !a.S || !a.m || !a.Ef || !a.Am || !a.b)) return hipErrorInvalidValue;
   return with_flag(v.dense, [&](auto dj) { return with_flag(v.q_out, [&](auto qo) { return with_flag(v.own_jump, [&](auto pj) {
-    return with_flag(v.grad, [&](auto gf) {
-      constexpr bool DJ = decltype(dj)::value, QO = decltype(qo)::value, PJ = decltype(pj)::value, GF = decltype(gf)::value;
-      switch (v.helper_roles) {
-        case 1: return launch_variant<METHOD, FWD, NB, DJ, QO, PJ, GF, 1>(a, st);
-        case 2: return launch_variant<METHOD, FWD, NB, DJ, QO, PJ, GF, 2>(a, st);
-        default: return launch_variant<METHOD, FWD, NB, DJ, QO, PJ, GF, 0>(a, st);
-      }
-    }); }); }); });
+    return with_flag(v.grad, [&](auto gf) { return with_int<0, 2>(v.helper_roles, [&](auto hr) {
+      return launch_variant<METHOD, FWD, NB, decltype(dj)::value, decltype(qo)::value, decltype(pj)::value, decltype(gf)::value, decltype(hr)::value>(a, st);
+    }); });
+  }); }); });
 }
 
 // D <= 44 has both kernel families: the role-specialised 8-wave kernels of ode_mfma_impl.h (faster for one problem per CU and for a
@@ -1663,14 +1649,9 @@ hipError_t launch_any(const OdeArgs& a, int helper_roles, hipStream_t st) {
 // One instantiation set per stepper: ode_mfma_m<METHOD>.hip instantiates these two, so that the steppers compile in parallel.
 template <int METHOD> bool mfma_method_supported(int nb) { return nb >= 1 && nb <= sym::kMaxNB; }
 template <int METHOD> hipError_t mfma_method_launch(bool fwd, const OdeArgs& a, int helper_roles, hipStream_t st) {
-  switch ((a.D + 3) / 4) {
-#define VGPA_NB_CASE(NB) \
-  case NB: return fwd ? sym::launch_any<METHOD, true, NB>(a, helper_roles, st) : sym::launch_any<METHOD, false, NB>(a, helper_roles, st);
-    VGPA_NB_CASE(1) VGPA_NB_CASE(2) VGPA_NB_CASE(3) VGPA_NB_CASE(4) VGPA_NB_CASE(5) VGPA_NB_CASE(6) VGPA_NB_CASE(7) VGPA_NB_CASE(8)
-    VGPA_NB_CASE(9) VGPA_NB_CASE(10) VGPA_NB_CASE(11) VGPA_NB_CASE(12) VGPA_NB_CASE(13) VGPA_NB_CASE(14) VGPA_NB_CASE(15) VGPA_NB_CASE(16)
-#undef VGPA_NB_CASE
-    default: return hipErrorNotSupported;
-  }
+  return with_int<1, sym::kMaxNB>((a.D + 3) / 4, [&](auto nb) {
+    return with_flag(fwd, [&](auto f) { return sym::launch_any<METHOD, decltype(f)::value, decltype(nb)::value>(a, helper_roles, st); });
+  }, hipErrorNotSupported);
 }
 
 }  // namespace vgpa

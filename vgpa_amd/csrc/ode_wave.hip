@@ -7,6 +7,7 @@
 // RK4 step) to the latency of the shuffles.  From 512 problems per launch ode_small.hip (one lane per problem) takes over.
 // Everything a step reads from HBM is requested one step earlier.
 #include "vgpa_internal.h"
+#include "dispatch.h"
 
 namespace vgpa {
 namespace {
@@ -272,34 +273,29 @@ __global__ void __launch_bounds__(NTW) k_bwd_wave(OdeArgs a) {
 template <int METHOD, bool FWD, int D>
 hipError_t launch_d(const OdeArgs& a, hipStream_t st) {
   dim3 grid((a.batch + 3) / 4), block(NTW);
-  if (FWD) hipLaunchKernelGGL((k_fwd_wave<METHOD, D>), grid, block, 0, st, a);
-  else if (a.js_dense) hipLaunchKernelGGL((k_bwd_wave<METHOD, D, true>), grid, block, 0, st, a);
-  else if (a.js_const_stride) hipLaunchKernelGGL((k_bwd_wave<METHOD, D, false, true>), grid, block, 0, st, a);
-  else hipLaunchKernelGGL((k_bwd_wave<METHOD, D, false>), grid, block, 0, st, a);
-  return hipGetLastError();
-}
-
-template <int METHOD, bool FWD>
-hipError_t launch_m(const OdeArgs& a, hipStream_t st) {
-  switch (a.D) {
-    case 2: return launch_d<METHOD, FWD, 2>(a, st);
-    case 3: return launch_d<METHOD, FWD, 3>(a, st);
-    case 4: return launch_d<METHOD, FWD, 4>(a, st);
+  if constexpr (FWD) {
+    hipLaunchKernelGGL((k_fwd_wave<METHOD, D>), grid, block, 0, st, a);
+    return hipGetLastError();
+  } else {      // (the per-problem constant jump belongs to the kernels with sparse jumps)
+    return with_flag(a.js_dense != nullptr, [&](auto dj) { return with_flag(!a.js_dense && a.js_const_stride, [&](auto pj) {
+      constexpr bool DJ = decltype(dj)::value, PJ = decltype(pj)::value;
+      if constexpr (DJ && PJ) {
+        return hipErrorInvalidValue;      // (never asked: see the flags)
+      } else {
+        hipLaunchKernelGGL((k_bwd_wave<METHOD, D, DJ, PJ>), grid, block, 0, st, a);
+        return hipGetLastError();
+      }
+    }); });
   }
-  return hipErrorInvalidValue;
 }
 
 }  // namespace
 
 hipError_t launch_ode_wave(int method, bool fwd, const OdeArgs& a, hipStream_t st) {
   if (a.D < 2 || a.D > kMaxLaneD) return hipErrorInvalidValue;
-  switch (method) {
-    case VGPA_ODE_EULER: return fwd ? launch_m<VGPA_ODE_EULER, true>(a, st) : launch_m<VGPA_ODE_EULER, false>(a, st);
-    case VGPA_ODE_HEUN: return fwd ? launch_m<VGPA_ODE_HEUN, true>(a, st) : launch_m<VGPA_ODE_HEUN, false>(a, st);
-    case VGPA_ODE_RK2: return fwd ? launch_m<VGPA_ODE_RK2, true>(a, st) : launch_m<VGPA_ODE_RK2, false>(a, st);
-    case VGPA_ODE_RK4: return fwd ? launch_m<VGPA_ODE_RK4, true>(a, st) : launch_m<VGPA_ODE_RK4, false>(a, st);
-  }
-  return hipErrorInvalidValue;
+  return with_method(method, [&](auto m) { return with_flag(fwd, [&](auto f) { return with_int<2, 4>(a.D, [&](auto d) {
+    return launch_d<decltype(m)::value, decltype(f)::value, decltype(d)::value>(a, st);
+  }); }); });
 }
 
 }  // namespace vgpa

@@ -48,6 +48,7 @@
 //                | state on the component's ladder of levels and adds its integer descendant weight to that bin's mass  [the replay's  |
 //                | steps; k_pf_quantise: the final weights as integers, k_pf_descend_q: k_pf_descend in 64-bit integer arithmetic]     |
 #include "vgpa_internal.h"
+#include "dispatch.h"
 
 #include <type_traits>
 
@@ -2057,34 +2058,27 @@ hipError_t launch_walk(const SampleArgs& base, hipStream_t st, const WalkOwn& ow
   if (a.D <= kMaxLaneD) {
     const dim3 grid = kWalkTraits[(int)K].by_problem() ? dim3(a.batch, sample_segment_blocks(a.D, a.n_paths))
                                         : dim3((unsigned)(((size_t)a.batch * a.n_paths + 255) / 256));
-    const dim3 block(256);
-    switch (a.D) {
-      case 1: hipLaunchKernelGGL((k_sample_small<1, K>), grid, block, 0, st, a); break;
-      case 2:
-        if constexpr (K == Walk::Plain) { hipLaunchKernelGGL((k_sample_small<2, K>), grid, block, 0, st, a); break; }
-        else return hipErrorInvalidValue;
-      case 3: hipLaunchKernelGGL((k_sample_small<3, K>), grid, block, 0, st, a); break;
-      default: hipLaunchKernelGGL((k_sample_small<4, K>), grid, block, 0, st, a); break;
-    }
-    return hipGetLastError();
+    return with_int<1, kMaxLaneD>(a.D, [&](auto d) {      // (launch_sample_walk has refused D < 1)
+      constexpr int D = decltype(d)::value;
+      if constexpr (D != 2 || K == Walk::Plain) {
+        hipLaunchKernelGGL((k_sample_small<D, K>), grid, dim3(256), 0, st, a);
+        return hipGetLastError();
+      } else {
+        return hipErrorInvalidValue;
+      }
+    });
   }
   if constexpr (K == Walk::Forecast) {      // (the matrix-core kernel is posterior kind only: above D = 4 the forecast is Lorenz-96's own kernel)
     hipLaunchKernelGGL(k_forecast_l96, dim3(a.batch, sample_segment_blocks(a.D, a.n_paths)), dim3(64), ((size_t)a.D + 1) * 64 * sizeof(double), st, a);
     return hipGetLastError();
   } else {
-    auto mfma = [&](auto nt) {
-      constexpr int NT = decltype(nt)::value;
+    if (a.n_paths > sample_max_paths(a.D)) return hipErrorInvalidValue;
+    return with_int<1, kMaxSmallD / 16>((a.D + 15) / 16, [&](auto tiles) {      // (launch_sample_walk has refused D > 64)
+      constexpr int NT = 16 * decltype(tiles)::value;
       // (ReplayCov: the [4 waves][NT] words of the mean behind the Zs region)
       const size_t lds = (MfmaShape<NT>::lds_doubles(!a.R_diag) + (kWalkTraits[(int)K].kept == Kept::Covariance ? 4 * NT : 0)) * sizeof(double);
-      if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k_sample_mfma<NT, K>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (a.n_paths > sample_max_paths(a.D)) return hipErrorInvalidValue;
-      hipLaunchKernelGGL((k_sample_mfma<NT, K>), dim3(a.batch, sample_segment_blocks(a.D, a.n_paths)), dim3(256), lds, st, a);
-      return hipGetLastError();
-    };
-    if (a.D <= 16) return mfma(std::integral_constant<int, 16>{});
-    if (a.D <= 32) return mfma(std::integral_constant<int, 32>{});
-    if (a.D <= 48) return mfma(std::integral_constant<int, 48>{});
-    return mfma(std::integral_constant<int, 64>{});
+      return launch_lds(k_sample_mfma<NT, K>, dim3(a.batch, sample_segment_blocks(a.D, a.n_paths)), dim3(256), lds, st, a);
+    });
   }
 }
 
@@ -2196,17 +2190,12 @@ hipError_t launch_pf_backward(const PfArgs& f, const SampleArgs& a, int K, int r
   if (a.D < 1 || a.D > kMaxSmallD || a.D != f.D || !a.A || !a.b || !a.R || !a.R_diag) return hipErrorInvalidValue;
   const dim3 grid(f.batch, (K + kBackwardBlock - 1) / kBackwardBlock), block(256);
   const size_t lds = ((size_t)a.D * 257 + (size_t)kBackwardBlock * a.D + a.D + 4 * kBackwardBlock) * sizeof(double) + 5 * kBackwardBlock * sizeof(int);
-  if (a.model == VGPA_MODEL_L96 && a.D >= 3) {      // (the circular drift on a column of any length)
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k_pf_backward<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(k_pf_backward<0>, grid, block, lds, st, f, a, K, rows, table);
-  } else if (a.D == 1 && (a.model == VGPA_MODEL_OU || a.model == VGPA_MODEL_DW)) {
-    hipLaunchKernelGGL(k_pf_backward<1>, grid, block, lds, st, f, a, K, rows, table);
-  } else if (a.D == 3 && a.model == VGPA_MODEL_L63) {
-    hipLaunchKernelGGL(k_pf_backward<3>, grid, block, lds, st, f, a, K, rows, table);
-  } else {
-    return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  auto kern = a.model == VGPA_MODEL_L96 && a.D >= 3                            ? k_pf_backward<0>      // (the circular drift on a column of any length)
+              : a.D == 1 && (a.model == VGPA_MODEL_OU || a.model == VGPA_MODEL_DW) ? k_pf_backward<1>
+              : a.D == 3 && a.model == VGPA_MODEL_L63                              ? k_pf_backward<3>
+                                                                                   : nullptr;
+  if (!kern) return hipErrorInvalidValue;
+  return launch_lds(kern, grid, block, lds, st, f, a, K, rows, table);
 }
 
 hipError_t launch_pf_normalise(int batch, int n_paths, const double* lw, double* w, hipStream_t st) {
