@@ -437,6 +437,49 @@ int vgpa_particle_marginals(vgpa_ctx* ctx, const double* x_or_null, const double
                             int32_t n_levels, double* logw, double* state, uint64_t* mass, uint64_t* qfinal_or_null,
                             double* lineage_ess_or_null, double* ess_or_null, int32_t* resampled_or_null);
 
+/* The two-time moments of the smoothing law under the genealogy of the particle filter: the particle estimate of
+ * Cov[x_k, x_s | y] for k != s -- what vgpa_lag_covariance's K(k, s) is held against --, with only the moments leaving the device.
+ * The filter, its weights, the stretches and the kept grid indices k = k' stride, n_keep = (Np-1) / stride + 1, are those of
+ * vgpa_particle_filter / vgpa_particle_paths.
+ *   X_i(k)      the trajectory of final slot i, i = 0 .. n_paths-1: bit for bit the one vgpa_particle_paths returns for n_draw = n_paths and
+ *               final_slots = 0 .. n_paths-1 (traced back through the ancestors, walked with the counter word of the slot its lineage sat
+ *               in; at an observation index the state before the resampling decision)
+ *   W_i         = w_i / sum w, w_i = exp(lw_i - max lw) of the final log-weights
+ *   anchors     host int64, [n_anchor]: strictly increasing grid indices in [0, Np), each a multiple of stride; shared by the problems
+ *   mean        host, [batch][n_keep][D]:                     mean[k'][a]        = sum_i W_i X_i(k' stride)[a]
+ *   cross       host, [batch][n_anchor][n_keep][D][D]:        cross[q][k'][a][b] = sum_i W_i X_i(k' stride)[a] X_i(anchors[q])[b]
+ *               (1-D models: [batch][n_anchor][n_keep]); every kept k' is filled, on both sides of the anchor
+ *   lineage_ess_or_null  as in vgpa_particle_moments, and bit-identical to its result with the same arguments
+ *   logw, state, ess_or_null, resampled_or_null and every other argument: as in vgpa_particle_filter, and bit-identical to its results with
+ *   the same arguments.  With x NULL the cached state is read and not written
+ * Raw moments: the covariance cross - mean[k'] mean[anchor]^T is the caller's subtraction, where its cancellation is visible.  The paths of
+ * a problem are added in increasing i whatever the launch: a problem's block does not depend on the batch around it, an anchor's block not
+ * on the other anchors, a kept row not on the stride.  The estimator is that of vgpa_particle_statistics: the final weights on the
+ * surviving lineages; early stretches rest on the few lineages the genealogy has left there, which lineage_ess reports.
+ * Memory: the trajectories stay on the device, batch n_paths n_keep D doubles; the stride is the lever.
+ * Errors: as vgpa_particle_paths, and VGPA_ERR_ARG for a NULL mean, cross or anchors, n_anchor < 1, an anchor out of range, anchors not
+ * strictly increasing or an anchor that is no multiple of stride; VGPA_ERR_UNSUPPORTED, before any work, beyond the limits of
+ * vgpa_particle_paths with n_draw = n_paths, for more than 65535 anchors or problems, or more than 2^39 - 256 entries of cross; D > 64 and
+ * a dense Sigma are refused as in vgpa_particle_filter. */
+int vgpa_particle_lag_covariance(vgpa_ctx* ctx, const double* x_or_null, const double* x0_or_null, int32_t n_paths, int32_t stride, uint64_t seed,
+                                 double ess_fraction, const double* prior_mu_or_null, const double* prior_tau_or_null, int32_t n_anchor,
+                                 const int64_t* anchors, double* logw, double* state, double* mean, double* cross, double* lineage_ess_or_null,
+                                 double* ess_or_null, int32_t* resampled_or_null);
+
+/* The contraction of vgpa_particle_lag_covariance alone, on trajectories and weights of the caller: for paths drawn
+ * otherwise -- vgpa_particle_backward_paths' equally weighted draws, vgpa_sample_paths_weighted's paths with their weights.
+ *   paths            host, [batch][n_paths][n_keep][D]
+ *   weights_or_null  host, [batch][n_paths], used as given (their normalisation is the caller's); NULL: 1 / n_paths each
+ *   anchor_rows      host int32, [n_anchor]: rows of the kept axis, each in [0, n_keep); any order, repeats allowed
+ *   mean             host, [batch][n_keep][D]:               mean[k][a]        = sum_i W_i X_i(k)[a]
+ *   cross            host, [batch][n_anchor][n_keep][D][D]:  cross[q][k][a][b] = sum_i W_i X_i(k)[a] X_i(anchor_rows[q])[b]
+ * Every term is fma(X_i(k)[a], W_i X_i(r)[b], .), the paths in increasing i.  Works on any context with D <= 64 (batch and D are the
+ * context's), ODE-only and VGPA_MODEL_NONE included; reads nothing of the cached state and writes nothing to it.
+ * Errors: VGPA_ERR_ARG for a NULL paths, anchor_rows, mean or cross, a count below 1 or a row out of range; VGPA_ERR_UNSUPPORTED for
+ * D > 64, more than 2^35 entries of paths, more than 65535 anchors or problems, or more than 2^39 - 256 entries of cross. */
+int vgpa_path_cross_moments(vgpa_ctx* ctx, const double* paths, const double* weights_or_null, int32_t n_paths, int32_t n_keep, int32_t n_anchor,
+                            const int32_t* anchor_rows, double* mean, double* cross);
+
 /* Whole smoothing trajectories on the time grid, drawn from the genealogy of the particle filter: K = n_draw complete
  * paths of the Euler-discretised model as the filter's surviving lineages hold them, for path functionals that are no mean or variance.
  * Three steps on the device behind the filter of vgpa_particle_filter, which runs unchanged with its ancestors kept: the final slots; their

@@ -13,6 +13,7 @@ Context.particle_covariance (vgpa_particle_covariance), Context.particle_margina
     python tools/bench_sample_paths.py --paths [--filter-problems 4096] [--paths-strides 1,10]      # the ap* and bp* jobs, once per stride
     python tools/bench_sample_paths.py --backward [--filter-problems 4096] [--paths-strides 10] [--parent-json FILE]      # the ab* and bb* jobs
     python tools/bench_sample_paths.py --gibbs [--filter-problems 4096]           # the ag* and bg* jobs
+    python tools/bench_sample_paths.py --lag-covariance [--lag-problems 512] [--filter-problems 4096]      # the al* and bl* jobs
     python tools/bench_sample_paths.py --forecast [--forecast-problems 512] [--forecast-particles 4096] [--forecast-horizon 1000]
 
   a   posterior kind, Lorenz-96, D = 40, Np = 1001, B = 512:   64 paths per problem, stride 100
@@ -72,6 +73,12 @@ Context.particle_covariance (vgpa_particle_covariance), Context.particle_margina
              has no particle_conditional: the job then times particle_filter and particle_paths alone), its processes alternating
              with this tree's: the parent's two times are reported beside, as parent_filter_ms_per_call / parent_paths_ms_per_call
 
+  al1024, bl64   (--lag-covariance selects both) particle_lag_covariance on the contexts of a (1024 particles; --lag-problems caps its B) and
+             b (64 particles; --filter-problems caps its B): ess_fraction 0.5, stride 10, 8 anchors at 0, 120, ... 840, and beside it the
+             only way to the same numbers without it: particle_paths(n_draw = n_paths, slots = 0 .. n-1) with the same arguments and the
+             contraction on the host (one BLAS product per problem and anchor), timed as one call with the host clock; the two alternate
+             inside every round.  Both times, their ratio, what each copies, and the contraction's FLOP count 2 B n_anchor n_keep n D^2
+
   --forecast   particle_forecast from a given cloud on a bare Lorenz-96 context (a model, theta, Sigma and dt: nothing evaluated), D = 40,
              B = 512, n = 4096 equally weighted particles, H = 1000 steps, no members, once with stride H (the sums at h = 0 and H alone)
              and once with stride 1 (the sums at every step), and beside them the model-kind sampler on the same lanes -- sample_paths(
@@ -116,6 +123,8 @@ MARG = {f"{t}h{n}_{s}": (t, n, s) for t in "ab" for n in (64, 1024) for s in (1,
 PATHS = {f"{t}p{n}_{k}": (t, n, k) for t in "ab" for n in (64, 1024) for k in (16, 64)}           # job -> (context of, particles, trajectories)
 BACKWARD = {f"{t}b{n}_{k}": (t, n, k) for t in "ab" for n in (64, 1024) for k in (16, 64)}        # job -> as PATHS
 GIBBS = {f"{t}g{n}": (t, n) for t in "ab" for n in (16, 64, 1024)}                                # job -> (context of, particles)
+LAG = {"al1024": ("a", 1024, 10), "bl64": ("b", 64, 10)}                                          # job -> as MOMENTS
+LAG_ANCHORS = 8
 
 
 def tree():
@@ -188,15 +197,19 @@ def run_forecast(B, n, horizon, rounds, calls):
     return out
 
 
-def run(job, rounds, calls, numpy_problems, cache, filter_problems=0, paths_stride=1, parent=None, n_levels=31):
+def run(job, rounds, calls, numpy_problems, cache, filter_problems=0, paths_stride=1, parent=None, n_levels=31, lag_problems=0):
     from bench_problem_batch import StreamTimer, make_contexts
     twin, stored = WEIGHTED.get(job, (job, True))
     weighted = job in WEIGHTED
-    if job in FILTER or job in STATS or job in EVENTS or job in MOMENTS or job in COV or job in MARG or job in PATHS or job in BACKWARD or job in GIBBS:
+    if job in LAG:
+        twin = LAG[job][0]
+    elif job in FILTER or job in STATS or job in EVENTS or job in MOMENTS or job in COV or job in MARG or job in PATHS or job in BACKWARD or job in GIBBS:
         twin = (FILTER.get(job) or STATS.get(job) or EVENTS.get(job) or MOMENTS.get(job) or COV.get(job) or MARG.get(job) or PATHS.get(job) or BACKWARD.get(job) or GIBBS[job])[0]
     name, d, B, kind, n_paths, stride = JOBS[twin]
     if (job in FILTER or job in STATS or job in EVENTS or job in MOMENTS or job in COV or job in MARG or job in PATHS or job in BACKWARD or job in GIBBS) and twin == "b" and filter_problems:
         B = min(B, filter_problems)
+    if job in LAG:
+        B = min(B, filter_problems if twin == "b" and filter_problems else B, lag_problems if twin == "a" and lag_problems else B)
     if (name, B) not in cache:                        # (b and c share a context)
         from helpers import SEED, build_problem
         ctxs, x0 = make_contexts(name, d, N_PTS, DT, B, modes=("shared",))
@@ -378,6 +391,54 @@ def run(job, rounds, calls, numpy_problems, cache, filter_problems=0, paths_stri
                 "up_mb": round(8.0 * B * d * n_levels / 1e6, 2),
                 "d2h_mb": round(8.0 * B * (n_paths * (2 + d) + n_keep * d * (n_levels + 1)) / 1e6, 1),
                 "moments_d2h_mb": round(8.0 * B * (n_paths * (1 + d) + n_keep * 2 * d) / 1e6, 1)}
+    if job in LAG:
+        _, n_paths, stride = LAG[job]
+        n_keep = (N_PTS - 1) // stride + 1
+        anchors = np.arange(LAG_ANCHORS) * (12 * stride)
+        rows, every = anchors // stride, np.arange(n_paths)
+
+        def on_the_host():
+            res = c.particle_paths(n_paths, 1, n_paths, stride=stride, ess_fraction=0.5, slots=every)
+            lw, paths = res["log_w"], res["paths"]
+            w = np.exp(lw - lw.max(axis=1, keepdims=True))
+            w /= w.sum(axis=1, keepdims=True)
+            mean, cross = np.einsum("pi,pikd->pkd", w, paths), np.empty((B, LAG_ANCHORS, n_keep, d, d))
+            for p in range(B):
+                flat = paths[p].reshape(n_paths, n_keep * d)
+                for q, r in enumerate(rows):      # (W x(s))^T X: (D, n) @ (n, n_keep D)
+                    cross[p, q] = np.transpose(((w[p][:, None] * paths[p, :, r]).T @ flat).reshape(d, n_keep, d), (1, 2, 0))
+            return {"mean": mean, "cross": cross}
+
+        def host_ms(f):
+            t0 = time.perf_counter()
+            f()
+            return 1e3 * (time.perf_counter() - t0)
+        dev0, host0 = c.particle_lag_covariance(n_paths, 1, anchors, stride=stride, ess_fraction=0.5), on_the_host()
+        scale = np.abs(host0["cross"]).max()
+        off = float(np.abs(dev0["cross"] - host0["cross"]).max() / scale)
+        assert dev0["cross"].shape == (B, LAG_ANCHORS, n_keep, d, d) and off < 1e-12, off
+        del dev0, host0
+        per_round = {"lag": [], "lag_host_clock": [], "paths_and_host": []}
+        for _ in range(rounds):
+            ms = {k: [] for k in per_round}
+            for _ in range(calls):
+                ms["lag"].append(tm.ms(lambda: c.particle_lag_covariance(n_paths, 1, anchors, stride=stride, ess_fraction=0.5)))
+                ms["lag_host_clock"].append(host_ms(lambda: c.particle_lag_covariance(n_paths, 1, anchors, stride=stride, ess_fraction=0.5)))
+                ms["paths_and_host"].append(host_ms(on_the_host))
+            for k in per_round:
+                per_round[k].append(float(np.median(ms[k])))
+        med = {k: float(np.median(v)) for k, v in per_round.items()}
+        return {"job": job, "model": name, "D": d, "Np": N_PTS, "B": B, "kind": "lag_covariance", "n_paths": n_paths, "ess_fraction": 0.5,
+                "stride": stride, "anchors": anchors.tolist(), "lag_ms_per_call": round(med["lag"], 4),
+                "lag_host_clock_ms_per_call": round(med["lag_host_clock"], 4), "paths_and_host_ms_per_call": round(med["paths_and_host"], 4),
+                "ratio_host_way_to_lag": round(med["paths_and_host"] / med["lag_host_clock"], 3),
+                "lag_rounds_ms": [round(v, 4) for v in per_round["lag"]],
+                "paths_and_host_rounds_ms": [round(v, 4) for v in per_round["paths_and_host"]],
+                "largest_difference_over_largest_entry": off,
+                "contraction_gflop": round(2.0 * B * LAG_ANCHORS * n_keep * n_paths * d * d / 1e9, 3),
+                "trajectories_on_device_mb": round(8.0 * B * n_paths * n_keep * d / 1e6, 1),
+                "d2h_mb": round(8.0 * B * (n_paths * (1 + d) + n_keep * d * (1 + LAG_ANCHORS * d)) / 1e6, 1),
+                "host_way_d2h_mb": round(8.0 * B * (n_paths * (1 + d) + n_paths * n_keep * d) / 1e6, 1)}
     if job in PATHS:
         _, n_paths, n_draw = PATHS[job]
         stride = paths_stride
@@ -553,6 +614,8 @@ def main():
     ap.add_argument("--covariance", action="store_true", help="run the ac* and bc* jobs (particle_covariance beside particle_moments and particle_filter)")
     ap.add_argument("--marginals", action="store_true", help="run the ah* and bh* jobs (particle_marginals beside particle_moments)")
     ap.add_argument("--levels", type=int, default=31, help="levels per component of the ah* and bh* jobs")
+    ap.add_argument("--lag-covariance", action="store_true", help="run the al* and bl* jobs (particle_lag_covariance beside particle_paths and the host's contraction)")
+    ap.add_argument("--lag-problems", type=int, default=0, help="cap on B of the a context's lag-covariance job (0: none)")
     ap.add_argument("--paths", action="store_true", help="run the ap* and bp* jobs (particle_paths beside particle_filter)")
     ap.add_argument("--paths-strides", default="1,10", help="strides of the ap* and bp* jobs: each job runs once per stride")
     ap.add_argument("--backward", action="store_true", help="run the ab* and bb* jobs (particle_backward_paths beside particle_paths and particle_filter)")
@@ -578,6 +641,8 @@ def main():
         args.jobs = ",".join(sorted(COV))
     if args.marginals and args.jobs == "a,b,c":
         args.jobs = ",".join(sorted(MARG))
+    if args.lag_covariance and args.jobs == "a,b,c":
+        args.jobs = ",".join(sorted(LAG))
     if args.paths:
         args.jobs = ",".join(sorted(PATHS))
     if args.backward and args.jobs == "a,b,c":
@@ -597,7 +662,7 @@ def main():
     out = {"tool": "bench_sample_paths", "tree": tree(), "unit": "ms per call (device events around the call)", "jobs": []}
     for job in [j for j in args.jobs.split(",") if j]:
         for stride in (strides if job in PATHS or job in BACKWARD else [1]):
-            out["jobs"].append(run(job, args.rounds, args.calls, args.numpy_problems, cache, args.filter_problems, stride, parent, args.levels))
+            out["jobs"].append(run(job, args.rounds, args.calls, args.numpy_problems, cache, args.filter_problems, stride, parent, args.levels, args.lag_problems))
     for c, _, _, _, tm in cache.values():
         tm.close()
         c.close()

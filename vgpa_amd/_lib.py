@@ -39,7 +39,7 @@ MAX_MARGINAL_LEVELS = 63      # kMaxMarginalLevels of the library: a bin is foun
 SYMBOLS = ["vgpa_create", "vgpa_destroy", "vgpa_last_error", "vgpa_abi_version", "vgpa_device_count",
            "vgpa_synchronize", "vgpa_stream", "vgpa_solve_fwd", "vgpa_solve_bwd", "vgpa_energy",
            "vgpa_obs_energy", "vgpa_free_energy", "vgpa_gradient", "vgpa_sweep", "vgpa_energy_parts",
-           "vgpa_fetch", "vgpa_theta_gradient", "vgpa_lag_covariance", "vgpa_sample_paths", "vgpa_sample_paths_weighted", "vgpa_particle_filter", "vgpa_particle_statistics", "vgpa_particle_events", "vgpa_particle_moments", "vgpa_particle_covariance", "vgpa_particle_marginals", "vgpa_particle_paths", "vgpa_particle_backward_paths", "vgpa_particle_conditional", "vgpa_particle_forecast", "vgpa_sweep_dev", "vgpa_free_energy_dev", "vgpa_sweep_enqueue", "vgpa_fetch_f",
+           "vgpa_fetch", "vgpa_theta_gradient", "vgpa_lag_covariance", "vgpa_sample_paths", "vgpa_sample_paths_weighted", "vgpa_particle_filter", "vgpa_particle_statistics", "vgpa_particle_events", "vgpa_particle_moments", "vgpa_particle_covariance", "vgpa_particle_marginals", "vgpa_particle_lag_covariance", "vgpa_path_cross_moments", "vgpa_particle_paths", "vgpa_particle_backward_paths", "vgpa_particle_conditional", "vgpa_particle_forecast", "vgpa_sweep_dev", "vgpa_free_energy_dev", "vgpa_sweep_enqueue", "vgpa_fetch_f",
            "vgpa_dev_alloc", "vgpa_dev_free", "vgpa_memcpy_h2d", "vgpa_memcpy_d2h",
            "vgpa_profile_begin", "vgpa_profile_end", "vgpa_ld_gemm", "vgpa_ld_stage", "vgpa_gradient_dev", "vgpa_energy_full", "vgpa_set_option", "vgpa_is_streaming", "vgpa_path_info", "vgpa_set_prior_energy",
            "vgpa_set_problem_data", "vgpa_set_problem_params", "vgpa_set_problem_obs_model",
@@ -156,6 +156,9 @@ def load():
                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vgpa_particle_marginals.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_uint64, c_double, c_void_p, c_void_p, c_void_p, c_int32,
                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.vgpa_particle_lag_covariance.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_uint64, c_double, c_void_p, c_void_p, c_int32, c_void_p,
+                                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.vgpa_path_cross_moments.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]
     lib.vgpa_particle_paths.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_uint64, c_double, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vgpa_particle_backward_paths.argtypes = lib.vgpa_particle_paths.argtypes
@@ -810,6 +813,61 @@ class Context:
         return self._filter_call("vgpa_particle_marginals", {"n_paths": n_paths, "stride": stride}, seed, ess_fraction, x, x0, prior, lambda n, k, n_keep: {
             "mass": self._new(n_keep, self.D, ladder[1] + 1, dtype=np.uint64), "q_final": self._new(n, dtype=np.uint64),
             "lineage_ess": self._new(self.n_obs + 1, fill=0.0)}, inputs=inputs)
+
+    @staticmethod
+    def _index_array(values, name, dtype):
+        """a 1-D sequence of integers (a scalar is one of them) as a contiguous array of `dtype`"""
+        v = np.asarray(values)
+        if v.ndim == 0:
+            v = v.reshape(1)
+        if v.ndim != 1 or (v.size and v.dtype.kind not in "iu"):
+            raise ValueError(f"{name} must be a 1-D sequence of integers")
+        if v.size and (int(v.min()) < np.iinfo(dtype).min or int(v.max()) > np.iinfo(dtype).max):
+            raise ValueError(f"{name} must fit into {np.iinfo(dtype).bits} bits")
+        return np.ascontiguousarray(v, dtype=dtype)
+
+    def particle_lag_covariance(self, n_paths, seed, anchors, stride=1, ess_fraction=0.5, x=None, x0=None, prior=None):
+        """The two-time moments of the smoothing law under particle_filter's genealogy (vgpa_particle_lag_covariance): the filter, the
+        trajectory of every final slot as particle_paths(n_draw=n_paths, slots=arange(n_paths)) walks it -- kept on the device, B n_paths
+        n_keep D doubles: the stride is the lever --, and their contraction with the normalised final weights W.  anchors: strictly
+        increasing grid indices, each a multiple of stride, shared by the problems.  Returns a dict: log_w, state, ess, resampled as
+        particle_filter (bit for bit), lineage_ess as particle_moments (bit for bit), mean (B, n_keep, D): sum W x(k), and cross
+        (B, n_anchor, n_keep, D, D): sum W x(k) x(anchor)^T at the grid indices k = 0, stride, ..., on both sides of the anchor.  The
+        covariance is cross - mean(k) mean(anchor)^T (SmoothingLagCovariance.cov)."""
+        own = []      # (the anchors: made where _filter_call checks the entry's own inputs, read where it makes the outputs)
+
+        def inputs():
+            own.append(self._index_array(anchors, "anchors", np.int64))
+            self._fit32(n_anchor=int(own[0].size))
+            return int(own[0].size), (own[0] if own[0].size else None)
+        return self._filter_call("vgpa_particle_lag_covariance", {"n_paths": n_paths, "stride": stride}, seed, ess_fraction, x, x0, prior, lambda n, k, n_keep: {
+            "mean": self._new(n_keep, self.D), "cross": self._new(own[0].size, n_keep, self.D, self.D),
+            "lineage_ess": self._new(self.n_obs + 1, fill=0.0)}, inputs=inputs)
+
+    def path_cross_moments(self, paths, anchor_rows, weights=None):
+        """The contraction of particle_lag_covariance alone on given trajectories (vgpa_path_cross_moments): paths (B, n, n_keep, D) -- or
+        (n, n_keep, D) with B = 1 --, weights (B, n) or (n,) used as given (None: 1 / n each), anchor_rows: rows of the kept axis.  Returns
+        (mean (B, n_keep, D), cross (B, n_anchor, n_keep, D, D)): sum_i W_i x_i(k) and sum_i W_i x_i(k) x_i(row)^T, every term
+        fma(x_i(k)[a], W_i x_i(row)[b], .), the paths in increasing order.  Reads and writes nothing of the cached state."""
+        pp = np.asarray(paths, dtype=np.float64)
+        if pp.ndim == 3 and self.B == 1:
+            pp = pp[None]
+        if pp.ndim != 4 or pp.shape[0] != self.B or pp.shape[3] != self.D or pp.size == 0:
+            raise ValueError(f"paths has shape {np.shape(paths)}, expected ({self.B}, n, n_keep, {self.D})")
+        pp = _c64(pp)
+        n, n_keep = pp.shape[1], pp.shape[2]
+        ww = None
+        if weights is not None:
+            ww = np.asarray(weights, dtype=np.float64)
+            if ww.size != self.B * n:
+                raise ValueError(f"weights has {ww.size} entries, expected {self.B} x {n}")
+            ww = _c64(ww.reshape(self.B, n))
+        rows = self._index_array(anchor_rows, "anchor_rows", np.int32)
+        self._fit32(n_paths=n, n_keep=n_keep, n_anchor=int(rows.size))
+        mean, cross = self._new(n_keep, self.D), self._new(rows.size, n_keep, self.D, self.D)
+        self._check(self._lib.vgpa_path_cross_moments(self._h, _ptr(pp), _ptr(ww), n, n_keep, int(rows.size), _ptr(rows) if rows.size else None,
+                                                      _ptr(mean), _ptr(cross)))
+        return mean, cross
 
     def particle_paths(self, n_paths, seed, n_draw, stride=1, ess_fraction=0.5, x=None, x0=None, prior=None, slots=None):
         """n_draw whole smoothing trajectories per problem from particle_filter's genealogy (vgpa_particle_paths): the filter, the final

@@ -265,6 +265,12 @@ class ProblemBatch(object):
         return self._particle_call("particle_covariance", lambda v, res, k: v._covariance_record(res, k, stride), n_paths, seed, stride=stride,
                                    ess_fraction=ess_fraction, x=x, x0=x0)
 
+    def particle_kernel(self, n_paths, seed, anchors, stride=1, ess_fraction=0.5, x=None, x0=None):
+        """One particles.SmoothingLagCovariance per member (VarGP.particle_kernel): Cov[x_k, x_s | y] between every kept grid index and the
+        anchors -- shared by the members -- under the genealogy of the member's own filter."""
+        return self._particle_call("particle_lag_covariance", lambda v, res, k: v._kernel_record(res, k, anchors, stride), n_paths, seed, anchors,
+                                   stride=stride, ess_fraction=ess_fraction, x=x, x0=x0)
+
     def particle_marginals(self, n_paths, seed, levels=None, stride=1, ess_fraction=0.5, x=None, x0=None, n_levels=31, width=4.0):
         """One particles.SmoothingMarginals per member (VarGP.particle_marginals): per component a histogram of x_k | y over a ladder of
         levels on the grid under the genealogy of the member's own filter.  levels: (B, D, L) for per-member ladders, or (D, L) or (L,) for

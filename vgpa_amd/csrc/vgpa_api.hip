@@ -177,9 +177,13 @@ struct vgpa_ctx {
   // vgpa_particle_conditional: the buffers of vgpa_particle_paths, the clouds and PF_REF: the reference trajectories;
   // vgpa_particle_events: the buffers of vgpa_particle_statistics (the rows are the event records), PF_EVC: the levels, PF_EVS: the sides
   // (int32), PF_CDF: the first-passage distribution; vgpa_particle_marginals: the descendant weights and the lineage ESS of the moments,
-  // PF_QTAB: the integer descendant weights (uint64), PF_QFIN: their final row of every problem [B][n], PF_MGL: the ladders, PF_MASS: the masses (uint64)
+  // PF_QTAB: the integer descendant weights (uint64), PF_QFIN: their final row of every problem [B][n], PF_MGL: the ladders, PF_MASS: the masses (uint64);
+  // vgpa_particle_lag_covariance: the slot table and d_sp_out of vgpa_particle_paths with all n_paths trajectories, [B][n][n_keep][D], which
+  // stay on the device (the stride is the lever on their size), the descendant weights and behind them the normalised final weights
+  // (PF_WTAB), the lineage ESS, PF_LAGR: the anchors' rows of the kept axis (int32), PF_LAG: the mean and behind it the cross moments;
+  // vgpa_path_cross_moments: d_sp_out (the given paths), PF_WTAB (the given weights), PF_LAGR and PF_LAG
   enum { PF_XA, PF_XB, PF_LW, PF_CUM, PF_ANC, PF_ESS, PF_FLAG, PF_HANC, PF_CLOUDS, PF_MU, PF_LT, PF_STA, PF_STB, PF_MEAN, PF_WTAB, PF_LESS, PF_PART,
-         PF_MOM, PF_SLOTS, PF_COV, PF_HLW, PF_REF, PF_EVC, PF_EVS, PF_CDF, PF_QTAB, PF_QFIN, PF_MGL, PF_MASS, PF_COUNT };
+         PF_MOM, PF_SLOTS, PF_COV, PF_HLW, PF_REF, PF_EVC, PF_EVS, PF_CDF, PF_QTAB, PF_QFIN, PF_MGL, PF_MASS, PF_LAGR, PF_LAG, PF_COUNT };
   double* d_pf[PF_COUNT] = {};
   size_t pf_n[PF_COUNT] = {};
   // profiling
@@ -1594,6 +1598,30 @@ int vgpa_sample_paths_weighted(vgpa_ctx* c, const double* x, const double* x0, i
   return sample_paths(c, VGPA_PATHS_POSTERIOR, x, x0, n_paths, stride, seed, out, start, logw);
 }
 
+// The weighted cross moments of trajectories on the device (particle_lag.hip): what vgpa_particle_lag_covariance and
+// vgpa_path_cross_moments share.  d_paths [B][n][n_keep][D] and d_w [B][n] (or nullptr) are on the device, h_rows [n_anchor] on the host
+// and alive until the stream has been synchronised, which is the caller's; mean and cross are the caller's host arrays.
+static bool cross_moments_fit(int B, int n_keep, int D, int n_anchor) {      // (one array of cross: at most 2^39 - 256 entries)
+  return (double)B * (double)n_anchor * (double)n_keep * (double)D * (double)D <= 549755813632.0;
+}
+static int cross_moments(vgpa_ctx* c, const double* d_paths, const double* d_w, int n, int n_keep, int n_anchor, const int32_t* h_rows, double* mean,
+                         double* cross) {
+  const int D = c->D, B = c->B;
+  const size_t n_mean = (size_t)B * n_keep * D, n_cross = n_mean * D * (size_t)n_anchor;
+  int rc;
+  if ((rc = grow(c, &c->d_pf[vgpa_ctx::PF_LAGR], &c->pf_n[vgpa_ctx::PF_LAGR], ((size_t)n_anchor + 1) / 2)) ||
+      (rc = grow(c, &c->d_pf[vgpa_ctx::PF_LAG], &c->pf_n[vgpa_ctx::PF_LAG], n_mean + n_cross))) return rc;
+  int32_t* d_rows = reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_LAGR]);
+  double* d_mean = c->d_pf[vgpa_ctx::PF_LAG];
+  if ((rc = upload(c, d_rows, h_rows, (size_t)n_anchor))) return rc;
+  PathMomentArgs g{};
+  g.D = D; g.batch = B; g.n_paths = n; g.n_keep = n_keep; g.n_anchor = n_anchor;
+  g.paths = d_paths; g.weights = d_w; g.anchor_rows = d_rows; g.mean = d_mean; g.cross = d_mean + n_mean;
+  LAUNCH_TRY(c, "path cross moments launch", launch_path_cross_moments(g, c->stream));
+  if ((rc = download(c, mean, d_mean, n_mean)) || (rc = download(c, cross, d_mean + n_mean, n_cross))) return rc;
+  return VGPA_OK;
+}
+
 // The guided particle filter (see vgpa_hip.h): the weighted walk of vgpa_sample_paths_weighted cut at the observation
 // indices of the batch, the particles resident between the cuts, a resampling step behind every cut that is an observation of some problem.
 // ParticleRequest: what one of the entry points wants from it and where the results go (nullptr: not wanted).
@@ -1601,7 +1629,7 @@ int vgpa_sample_paths_weighted(vgpa_ctx* c, const double* x, const double* x0, i
 // the filter is "fc_moments is set"; it goes with Carry::None and Behind::None alone.
 // (Carry -- nothing; the path statistics (Q, G, H); the event records (X, T, N) -- is vgpa_internal.h's: the walks carry by the same word)
 // (the order matters: table() below takes every enumerator from Trajectories on as a pass with a slot table; a new pass of sums goes before it)
-enum class Behind { None, Moments, Covariance, Marginals, Trajectories, Backward, Conditional };
+enum class Behind { None, Moments, Covariance, Marginals, LagCovariance, Trajectories, Backward, Conditional };
 struct ParticleRequest {
   const double* x; const double* x0; int32_t n_paths; uint64_t seed; double ess_fraction; const double* prior_mu; const double* prior_tau;
   double* logw; double* state; double* ess; int32_t* resampled;      // (up to here: what every entry point has, filled in this order)
@@ -1613,6 +1641,9 @@ struct ParticleRequest {
   double* moments; double* lineage_ess;                              // Behind::Moments (lineage_ess: Covariance too)
   double* cov_mean; double* cov_second;                              // Behind::Covariance
   const double* mg_levels; int32_t n_levels; uint64_t* mass; uint64_t* qfinal;      // Behind::Marginals (lineage_ess too): ladders [B][D][L]
+  // Behind::LagCovariance (lineage_ess too): anchor_rows [n_anchor] = anchors / stride; n_draw = n_paths: every final slot's trajectory,
+  // walked as Behind::Trajectories walks it and kept on the device
+  int32_t n_anchor; const int32_t* anchor_rows; double* lag_mean; double* lag_cross;
   // Behind::Trajectories / Backward (the table is drawn, not traced) / Conditional (slot 0 pinned to ref [B][Np][D]; n_draw = 1, paths: the
   // drawn trajectory); slots_out: where the table goes
   int32_t n_draw; const int32_t* final_slots; double* paths; int32_t* slots_out; const double* ref;
@@ -1620,6 +1651,7 @@ struct ParticleRequest {
   int32_t horizon; const double* cloud; const double* cloud_logw; int32_t index0;
   double* fc_moments; double* members; double* state_end;
   bool sums() const { return behind == Behind::Moments || behind == Behind::Covariance; }      // the replay with its weighted sums
+  bool lag() const { return behind == Behind::LagCovariance; }                                 // every final slot's trajectory and their contraction
   bool table() const { return behind >= Behind::Trajectories; }                                // a slot table and the walk of its trajectories
 };
 
@@ -1682,6 +1714,9 @@ struct ParticleRun {
     if (q.behind == Behind::Marginals &&
         ((rc = buf(vgpa_ctx::PF_WTAB, (size_t)B * rows * n)) || (rc = buf(vgpa_ctx::PF_LESS, (size_t)B * rows)) || (rc = buf(vgpa_ctx::PF_QTAB, (size_t)B * rows * n)) || (rc = buf(vgpa_ctx::PF_QFIN, Bn)) ||
          (rc = buf(vgpa_ctx::PF_MGL, (size_t)B * D * q.n_levels)) || (rc = buf(vgpa_ctx::PF_MASS, (size_t)B * n_keep * D * ((size_t)q.n_levels + 1))))) return rc;
+    // (the trajectories of all n final slots stay in d_sp_out, batch n n_keep D doubles; the normalised final weights behind the descendant ones)
+    if (q.lag() && ((rc = buf(vgpa_ctx::PF_SLOTS, ints(n_table))) || (rc = grow(c, &c->d_sp_out, &c->sp_out_n, n_traj)) ||
+                    (rc = buf(vgpa_ctx::PF_WTAB, (size_t)B * rows * n + Bn)) || (rc = buf(vgpa_ctx::PF_LESS, (size_t)B * rows)))) return rc;
     if (keep_clouds && (rc = buf(vgpa_ctx::PF_CLOUDS, BM * n * D))) return rc;
     if (keep_lw && (rc = buf(vgpa_ctx::PF_HLW, BM * n))) return rc;
     if (carried && ((rc = buf(vgpa_ctx::PF_STA, 3 * BnD)) || (rc = buf(vgpa_ctx::PF_STB, 3 * BnD)) || (rc = buf(vgpa_ctx::PF_MEAN, (size_t)B * 3 * D)))) return rc;
@@ -1832,6 +1867,31 @@ struct ParticleRun {
     return VGPA_OK;
   }
 
+  // The two-time moments of the lineages, behind the filter: the identity slot table, its
+  // trace through the ancestors, the lineage walk of all n_paths trajectories into d_sp_out -- Behind::Trajectories' steps, the paths staying
+  // on the device --, the normalised final weights, the descendant weights for the lineage ESS as in moments(), then the contraction.
+  int lag_covariance() {
+    const int B = c->B, M = c->M;
+    int rc;
+    int32_t* table = reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_SLOTS]);
+    std::vector<int32_t> every((size_t)B * q.n_paths);      // (final_slots() is done with it when it returns)
+    for (size_t e = 0; e < every.size(); e++) every[e] = (int32_t)(e % (size_t)q.n_paths);
+    if ((rc = final_slots(table, every.data()))) return rc;
+    LAUNCH_TRY(c, "genealogy launch", launch_pf_trace(f, q.n_draw, slot_rows, table, c->stream));
+    if ((rc = walk_lanes(Walk::Lineage, "lineage walk launch", table))) return rc;
+    double* wtab = c->d_pf[vgpa_ctx::PF_WTAB];
+    double* wfin = wtab + (size_t)B * rows * q.n_paths;
+    double* less = c->d_pf[vgpa_ctx::PF_LESS];
+    LAUNCH_TRY(c, "final weights launch", launch_pf_normalise(B, q.n_paths, f.lw, wfin, c->stream));
+    HIP_TRY(c, hipMemsetAsync(less, 0, (size_t)B * rows * sizeof(double), c->stream));
+    LAUNCH_TRY(c, "descendant weights launch", launch_pf_descend(f, rows, wtab, less, c->stream));
+    if ((rc = cross_moments(c, c->d_sp_out, wfin, q.n_paths, n_keep, q.n_anchor, q.anchor_rows, q.lag_mean, q.lag_cross))) return rc;
+    if (q.lineage_ess)      // (as in moments())
+      for (int p = 0; p < (rows == M + 1 ? 1 : B); p++)
+        if ((rc = download(c, q.lineage_ess + (size_t)p * (M + 1), less + (size_t)p * rows, rows == M + 1 ? (size_t)B * rows : (size_t)M + 1))) return rc;
+    return VGPA_OK;
+  }
+
   // The trajectories behind the filter, whose histories stay on the device: the final slots of n_draw trajectories (final_slots, or drawn
   // from the final weights), the table of their slots in every stretch made in one launch, one launch of the walk over the n_draw
   // trajectories alone, the downloads.
@@ -1843,21 +1903,21 @@ struct ParticleRun {
   int trajectories() {
     int rc;
     int32_t* table = reinterpret_cast<int32_t*>(c->d_pf[vgpa_ctx::PF_SLOTS]);
-    if ((rc = final_slots(table))) return rc;
+    if ((rc = final_slots(table, q.final_slots))) return rc;
     if (q.behind == Behind::Backward) LAUNCH_TRY(c, "backward simulation launch", launch_pf_backward(f, a, q.n_draw, slot_rows, table, c->stream));
     else LAUNCH_TRY(c, "genealogy launch", launch_pf_trace(f, q.n_draw, slot_rows, table, c->stream));
     if (q.behind == Behind::Trajectories) return walk_table(Walk::Lineage, "lineage walk launch", table);
     return walk_table(Walk::Backward, "backward walk launch", table);
   }
 
-  // row c of the slot table: the caller's final slots, or drawn from the final weights; every other row -1
-  int final_slots(int32_t* table) {
+  // row c of the slot table: the given final slots [B][n_draw], or (nullptr) drawn from the final weights; every other row -1
+  int final_slots(int32_t* table, const int32_t* given) {
     const int B = c->B, n_draw = q.n_draw;
     int rc;
-    if (q.final_slots) {             // rows beyond a problem's own count: -1; row c: the caller's slots
+    if (given) {                     // rows beyond a problem's own count: -1; row c: the caller's slots
       std::vector<int32_t> h_table(n_table, -1);      // (the table as it is uploaded, alive until the stream has been synchronised)
       for (int p = 0; p < B; p++)
-        for (int m = 0; m < n_draw; m++) h_table[((size_t)p * slot_rows + count[p]) * n_draw + m] = q.final_slots[(size_t)p * n_draw + m];
+        for (int m = 0; m < n_draw; m++) h_table[((size_t)p * slot_rows + count[p]) * n_draw + m] = given[(size_t)p * n_draw + m];
       if ((rc = upload(c, table, h_table.data(), n_table))) return rc;
       HIP_TRY(c, hipStreamSynchronize(c->stream));
     } else {
@@ -1867,15 +1927,21 @@ struct ParticleRun {
     return VGPA_OK;
   }
 
-  // the walk of the table's n_draw trajectories alone and the downloads
-  int walk_table(Walk walk, const char* what, int32_t* table) {
-    int rc;
+  // the walk of the table's n_draw trajectories alone, into d_sp_out
+  int walk_lanes(Walk walk, const char* what, int32_t* table) {
     SampleArgs w = a;                // the unweighted walk of n_draw lanes per problem from the same start, factors and counters
     w.n_paths = q.n_draw; w.stride = q.stride; w.n_keep = n_keep; w.out = c->d_sp_out;
     w.pf_x = nullptr; w.pf_lw = nullptr; w.pf_stats = nullptr; w.pf_slots = table; w.pf_slot_rows = slot_rows;
     if (walk == Walk::Backward) { w.pf_clouds = f.h_clouds; w.pf_hanc = f.h_anc; w.pf_M = f.M; w.pf_n = q.n_paths; }
     hipError_t e = launch_sample_walk(walk, w, c->stream);
     if (e != hipSuccess) return fail(c, VGPA_ERR_DEVICE, "%s failed: %s", what, hipGetErrorString(e));
+    return VGPA_OK;
+  }
+
+  // ... and the downloads
+  int walk_table(Walk walk, const char* what, int32_t* table) {
+    int rc;
+    if ((rc = walk_lanes(walk, what, table))) return rc;
     if (pinned) LAUNCH_TRY(c, "reference stretches launch", launch_pf_ref_fill(f, slot_rows, table, c->d_sp_out, c->stream));
     if ((rc = download(c, q.paths, c->d_sp_out, n_traj))) return rc;
     if (q.slots_out) HIP_TRY(c, hipMemcpyAsync(q.slots_out, table, n_table * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
@@ -1994,6 +2060,17 @@ static int particle_run(vgpa_ctx* c, const ParticleRequest& q) {
         return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing marginals are built for at most 2^39 - 256 entries of mass (batch %d, %d kept grid indices, D = %d, %d levels): use a larger stride",
                     B, kept, D, q.n_levels);
     }
+    if (q.lag()) {      // (the trajectories' own limits with n_paths of them, then the contraction's)
+      if (!sample_lineages_fit(D, B, n_paths))
+        return fail(c, VGPA_ERR_UNSUPPORTED, "the lag covariance walks every particle's trajectory, at most %d per problem at D = %d (n_paths = %d)", sample_max_paths(kMaxSmallD), D, n_paths);
+      if ((rc = check_stored(c, n_paths, kept, "lag covariance's trajectories", "particles", "grid indices"))) return rc;
+      if (!path_moments_grid_fits(D, B, kept, q.n_anchor))
+        return fail(c, VGPA_ERR_UNSUPPORTED, "the lag covariance is built for at most %d anchors and a batch of at most %d (batch %d, %d anchors, %d kept grid indices)",
+                    kMaxGridY, kMaxGridY, B, q.n_anchor, kept);
+      if (!cross_moments_fit(B, kept, D, q.n_anchor))
+        return fail(c, VGPA_ERR_UNSUPPORTED, "the lag covariance is built for at most 2^39 - 256 entries of cross (batch %d, %d anchors, %d kept grid indices, D = %d): "
+                    "use a larger stride or fewer anchors", B, q.n_anchor, kept, D);
+    }
     if (q.table() && !sample_lineages_fit(D, B, n_draw))      // (the lineage walk; the number is the matrix-core walk's, above D = 4)
       return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing trajectories are built for at most %d per problem at D = %d (n_draw = %d)", sample_max_paths(kMaxSmallD), D, n_draw);
     if (q.behind == Behind::Backward && !pf_backward_fits(n_draw))      // (the one launch of the backward simulation)
@@ -2001,7 +2078,8 @@ static int particle_run(vgpa_ctx* c, const ParticleRequest& q) {
     if (q.table() && (rc = check_stored(c, n_draw, kept, "smoothing trajectories", "trajectories", "grid indices"))) return rc;
   }
   ParticleRun r{c, q};
-  if ((rc = r.setup()) || (rc = r.filter()) || (q.sums() && (rc = r.moments())) || (q.behind == Behind::Marginals && (rc = r.marginals())) || (q.table() && (rc = r.trajectories()))) return rc;
+  if ((rc = r.setup()) || (rc = r.filter()) || (q.sums() && (rc = r.moments())) || (q.behind == Behind::Marginals && (rc = r.marginals())) ||
+      (q.lag() && (rc = r.lag_covariance())) || (q.table() && (rc = r.trajectories()))) return rc;
   const size_t n = (size_t)n_paths, BnD = (size_t)B * n * D;
   if (q.fc_moments) {      // (the filter's final cloud leaves before the forecast carries it on in place)
     if ((rc = download(c, q.state, r.cur, BnD))) return rc;
@@ -2104,6 +2182,59 @@ int vgpa_particle_marginals(vgpa_ctx* c, const double* x, const double* x0, int3
   ParticleRequest q{x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled};
   q.stride = stride; q.behind = Behind::Marginals; q.mg_levels = levels; q.n_levels = n_levels; q.mass = mass; q.qfinal = qfinal; q.lineage_ess = lineage_ess;
   return particle_run(c, q);
+}
+
+// The two-time moments of the particle filter's lineages against a set of anchors (see vgpa_hip.h)
+int vgpa_particle_lag_covariance(vgpa_ctx* c, const double* x, const double* x0, int32_t n_paths, int32_t stride, uint64_t seed, double ess_fraction,
+                                 const double* prior_mu, const double* prior_tau, int32_t n_anchor, const int64_t* anchors, double* logw, double* state,
+                                 double* mean, double* cross, double* lineage_ess, double* ess, int32_t* resampled) {
+  if (!c) return VGPA_ERR_ARG;
+  if (!mean || !cross || !anchors) return fail(c, VGPA_ERR_ARG, "null argument");
+  if (n_anchor < 1 || stride < 1) return fail(c, VGPA_ERR_ARG, "n_anchor and stride must be at least 1 (n_anchor = %d, stride = %d)", n_anchor, stride);
+  if (n_paths < 1) return fail(c, VGPA_ERR_ARG, "n_paths must be at least 1 (n_paths = %d)", n_paths);
+  std::vector<int32_t> rows((size_t)n_anchor);      // (alive until particle_run has synchronised the stream)
+  for (int32_t i = 0; i < n_anchor; i++) {
+    if (anchors[i] < 0 || anchors[i] >= c->Np || (i > 0 && anchors[i] <= anchors[i - 1]))
+      return fail(c, VGPA_ERR_ARG, "anchor %d -> %lld: the anchors are strictly increasing grid indices in [0, %d)", i, (long long)anchors[i], c->Np);
+    if (anchors[i] % stride != 0)
+      return fail(c, VGPA_ERR_ARG, "anchor %d -> %lld is no multiple of the stride %d: the anchors lie on the kept grid", i, (long long)anchors[i], stride);
+    rows[(size_t)i] = (int32_t)(anchors[i] / stride);
+  }
+  ParticleRequest q{x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled};
+  q.stride = stride; q.behind = Behind::LagCovariance; q.lineage_ess = lineage_ess;
+  q.n_anchor = n_anchor; q.anchor_rows = rows.data(); q.lag_mean = mean; q.lag_cross = cross;
+  q.n_draw = n_paths;      // (every final slot's trajectory: the pass makes the identity table itself)
+  return particle_run(c, q);
+}
+
+// The contraction of vgpa_particle_lag_covariance alone on given trajectories and weights (see vgpa_hip.h).  Reads the
+// context's D and batch and nothing of the cached state; writes nothing to it.
+int vgpa_path_cross_moments(vgpa_ctx* c, const double* paths, const double* weights, int32_t n_paths, int32_t n_keep, int32_t n_anchor,
+                            const int32_t* anchor_rows, double* mean, double* cross) {
+  if (!c) return VGPA_ERR_ARG;
+  if (!paths || !anchor_rows || !mean || !cross) return fail(c, VGPA_ERR_ARG, "null argument");
+  if (n_paths < 1 || n_keep < 1 || n_anchor < 1)
+    return fail(c, VGPA_ERR_ARG, "n_paths, n_keep and n_anchor must be at least 1 (n_paths = %d, n_keep = %d, n_anchor = %d)", n_paths, n_keep, n_anchor);
+  for (int32_t i = 0; i < n_anchor; i++)
+    if (anchor_rows[i] < 0 || anchor_rows[i] >= n_keep)
+      return fail(c, VGPA_ERR_ARG, "anchor row %d -> %d does not lie in [0, %d)", i, anchor_rows[i], n_keep);
+  const int D = c->D, B = c->B;
+  if (D > kMaxSmallD) return fail(c, VGPA_ERR_UNSUPPORTED, "the path cross moments are built for D <= %d (D = %d)", kMaxSmallD, D);
+  int rc;
+  if ((rc = check_stored(c, n_paths, n_keep, "paths", "paths", "rows"))) return rc;
+  if (!path_moments_grid_fits(D, B, n_keep, n_anchor))
+    return fail(c, VGPA_ERR_UNSUPPORTED, "the path cross moments are built for at most %d anchors and a batch of at most %d (batch %d, %d anchors, %d kept rows)",
+                kMaxGridY, kMaxGridY, B, n_anchor, n_keep);
+  if (!cross_moments_fit(B, n_keep, D, n_anchor))
+    return fail(c, VGPA_ERR_UNSUPPORTED, "the path cross moments are built for at most 2^39 - 256 entries of cross (batch %d, %d anchors, %d kept rows, D = %d): "
+                "use fewer rows or fewer anchors", B, n_anchor, n_keep, D);
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  const size_t Bn = (size_t)B * n_paths, n_traj = Bn * n_keep * D;
+  if ((rc = grow(c, &c->d_sp_out, &c->sp_out_n, n_traj)) || (weights && (rc = grow(c, &c->d_pf[vgpa_ctx::PF_WTAB], &c->pf_n[vgpa_ctx::PF_WTAB], Bn)))) return rc;
+  if ((rc = upload(c, c->d_sp_out, paths, n_traj)) || (weights && (rc = upload(c, c->d_pf[vgpa_ctx::PF_WTAB], weights, Bn)))) return rc;
+  if ((rc = cross_moments(c, c->d_sp_out, weights ? c->d_pf[vgpa_ctx::PF_WTAB] : nullptr, n_paths, n_keep, n_anchor, anchor_rows, mean, cross))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return VGPA_OK;
 }
 
 // Whole smoothing trajectories on the grid from the particles' genealogy (see vgpa_hip.h)

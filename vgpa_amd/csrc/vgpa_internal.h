@@ -440,6 +440,20 @@ hipError_t launch_lag_start(const LagStartArgs& a, hipStream_t st);
 hipError_t launch_lag(const LagArgs& a, hipStream_t st);     // D <= kMaxSmallD; hipErrorInvalidValue otherwise
 bool lag_grid_fits(int D, int batch, int n_anchor);          // one workgroup (D <= kMaxLaneD: one lane) per (problem, anchor) in grid.x
 
+// Weighted cross moments of stored trajectories (particle_lag.hip): mean [B][n_keep][D] = sum_i W_i X_i(k) and
+// cross [B][n_anchor][n_keep][D][D] = sum_i W_i X_i(k) X_i(anchor_rows[q])^T, the paths added in increasing order whatever the launch
+struct PathMomentArgs {
+  int D, batch, n_paths, n_keep, n_anchor;
+  const double* paths;            // [B][n_paths][n_keep][D], as vgpa_sample_paths stores them
+  const double* weights;          // [B][n_paths], used as they are; nullptr: 1 / n_paths each
+  const int32_t* anchor_rows;     // [n_anchor] rows of the kept axis in [0, n_keep), on the device
+  double* mean;
+  double* cross;
+};
+hipError_t launch_path_cross_moments(const PathMomentArgs& g, hipStream_t st);      // D <= kMaxSmallD; hipErrorInvalidValue otherwise
+// grid.x: the kept rows (D <= kMaxLaneD: the entries of one anchor's block, 256 per workgroup), grid.y: the anchors, grid.z: the problems
+bool path_moments_grid_fits(int D, int batch, int n_keep, int n_anchor);
+
 // launchers (each returns hipGetLastError()) -----------------------------------------------------
 hipError_t launch_ode_generic(int method, bool fwd, const OdeArgs& a, hipStream_t st);
 hipError_t launch_ode_small(int method, bool fwd, const OdeArgs& a, hipStream_t st);     // D <= kMaxLaneD

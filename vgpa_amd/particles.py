@@ -36,6 +36,11 @@ SmoothingCovariance: one problem's record of vgpa_particle_covariance (DESIGN.md
     E[x_k x_k^T | y] ~ sum_i W^{j(k)}_i x_i(k) x_i(k)^T,
 the full matrix the variational S_t is held against, under the same genealogy and with the same caveat.
 
+SmoothingLagCovariance: one problem's record of vgpa_particle_lag_covariance -- the same estimator at two times,
+    E[x_k x_s^T | y] ~ sum_i W_i X_i(k) X_i(s)^T
+over the final slots' whole trajectories X_i with the final weights W: the particle counterpart of lagcov.LagCovariance, what the
+covariance function K(k, s) of the variational process is held against, under the same genealogy and with the same caveat.
+
 SmoothingMarginals: one problem's record of vgpa_particle_marginals -- the marginal law of x_k[d] | y itself under the
 same genealogy, as a histogram over a ladder of levels per component: bin(x) = #{l: levels_l < x}, and the mass of a bin is the sum of
 the integer weights Q = the descendants' share of q_i = trunc(W_i 2^62) of the lineages whose state falls into it.  Integer sums do not
@@ -65,7 +70,7 @@ model whatever the proposal (A_t, b_t) and for any number of particles >= 2: the
 """
 import numpy as np
 
-__all__ = ["ParticleFilterResult", "PathStatistics", "PathEvents", "SmoothingMoments", "SmoothingCovariance", "SmoothingMarginals", "gaussian_ladder", "SmoothingPaths", "Forecast", "GibbsChain", "descendant_weights",
+__all__ = ["ParticleFilterResult", "PathStatistics", "PathEvents", "SmoothingMoments", "SmoothingCovariance", "SmoothingLagCovariance", "SmoothingMarginals", "gaussian_ladder", "SmoothingPaths", "Forecast", "GibbsChain", "descendant_weights",
            "path_rows", "theta_conditional", "theta_draw"]
 
 
@@ -444,6 +449,131 @@ class SmoothingCovariance(_GenealogySums):
         return self._vec(self._mean[i].copy()), self._mat(self._cov()[i])
 
 
+class SmoothingLagCovariance(_GenealogySums):
+    """The two-time moments of the smoothing law (vgpa_particle_lag_covariance), the particle counterpart of
+    lagcov.LagCovariance -- cov, corr, increment_var and joint take the same arguments and mean the same --: log_w (n,): the final
+    unnormalised log-weights; mean (n_keep, D): sum_i W_i x_i(k); cross (n_anchor, n_keep, D, D): block [q, j] is
+    sum_i W_i x_i(grid[j]) x_i(anchors[q])^T, filled on both sides of the anchor; anchors (n_anchor,): strictly increasing kept grid
+    indices; obs_t, lineage_ess, ess, resampled as SmoothingCovariance.  single_dim: a 1-D model, the component axes of every result are
+    dropped.  Nothing is clipped: where a stretch rests on one lineage a variance is rounding noise of either sign and stays so."""
+
+    def __init__(self, log_w, mean, cross, anchors, stride, n_pts, obs_t, lineage_ess, ess=(), resampled=(), single_dim=False) -> None:
+        self._take_weights(log_w)
+        n_keep = self._take_grid(stride, n_pts)
+        self._mean, self._cross = np.asarray(mean, dtype=float), np.asarray(cross, dtype=float)
+        self.anchors = np.asarray(anchors, dtype=np.int64).ravel()
+        if self._mean.ndim != 2 or self._mean.shape[0] != n_keep or self._cross.shape != (self.anchors.size, n_keep) + 2 * (self._mean.shape[1],):
+            raise ValueError(" SmoothingLagCovariance: mean must be (n_keep, D) and cross (n_anchor, n_keep, D, D).")
+        if self.anchors.size < 1 or np.any(np.diff(self.anchors) <= 0) or self.anchors[0] < 0 or self.anchors[-1] >= self.n_pts or np.any(self.anchors % self.stride):
+            raise ValueError(" SmoothingLagCovariance: anchors must be strictly increasing kept grid indices.")
+        self._take_stretches(obs_t, lineage_ess, ess, resampled)
+        self.single_dim = bool(single_dim)
+        self._anchor_at = {int(s): q for q, s in enumerate(self.anchors)}
+
+    def _vec(self, a):
+        return a[..., 0] if self.single_dim else a
+
+    def _mat(self, a):
+        return a[..., 0, 0] if self.single_dim else a
+
+    @property
+    def mean(self):
+        """E[x_k | y] on the kept grid"""
+        return self._vec(self._mean.copy())
+
+    @property
+    def cross(self):
+        """E[x_k x_s^T | y], the raw cross moments of every anchor s"""
+        return self._mat(self._cross.copy())
+
+    def _row(self, k):
+        k = int(k)
+        if k < 0 or k >= self.n_pts or k % self.stride:
+            raise KeyError(f"grid index {k} is not on the kept grid (stride {self.stride}, n_pts {self.n_pts})")
+        return k // self.stride
+
+    def _block(self, k, s):
+        """cross - mean mean^T at kept index k and anchor s, (D, D)"""
+        j, i = self._row(k), self._row(s)
+        return self._cross[self._anchor_at[int(s)], j] - self._mean[j][:, None] * self._mean[i][None, :]
+
+    def _cov(self, k, s):
+        k, s = int(k), int(s)
+        if s in self._anchor_at:
+            return self._block(k, s)
+        if k in self._anchor_at:
+            return self._block(s, k).T
+        raise KeyError(f"neither {k} nor {s} is an anchor (anchors: {self.anchors.tolist()})")
+
+    def cov(self, k, s):
+        """Cov[x_k, x_s | y] = cross - mean_k mean_s^T, (D, D), as it comes: the block of anchor s at the kept index k, or the transpose of
+        the block of anchor k at the kept index s.  KeyError where neither index is an anchor or the other one is not kept."""
+        return self._mat(self._cov(k, s))
+
+    def _marginal(self, k, st=None):
+        if st is None:
+            return self._cov(k, k)
+        st = np.asarray(st, dtype=float)
+        if st.ndim == 1:
+            st = st[:, None, None]
+        return st[self._row(k)]
+
+    def marginal(self, k, st=None):
+        """Cov[x_k | y], (D, D): from st (n_keep, D, D), the marginal covariances on the kept grid (SmoothingCovariance.cov), or -- st=None
+        -- from the row k of anchor k"""
+        return self._mat(self._marginal(k, st))
+
+    def _corr(self, k, s, st=None):
+        vk, vs = np.diagonal(self._marginal(k, st)), np.diagonal(self._marginal(s, st))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            dk, ds = np.sqrt(np.where(vk > 0.0, vk, np.nan)), np.sqrt(np.where(vs > 0.0, vs, np.nan))
+            return self._cov(k, s) / (dk[:, None] * ds[None, :])
+
+    def corr(self, k, s, st=None):
+        """Corr[x_k,a, x_s,b] = cov_ab / sqrt(Var x_k,a Var x_s,b), (D, D); the marginals as in marginal(); nan where a variance is not
+        positive"""
+        return self._mat(self._corr(k, s, st))
+
+    def increment_var(self, k, s, st=None):
+        """Cov[x_k - x_s | y] = S_k + S_s - C - C^T with C = cov(k, s), (D, D), not clipped"""
+        c = self._cov(k, s)
+        return self._mat(self._marginal(k, st) + self._marginal(s, st) - c - c.T)
+
+    def autocorrelation(self, s, var=None):
+        """Corr[x_k,a, x_s,a] of anchor s at every kept grid index k, (n_keep, D).  var (n_keep, D): the marginal variances on the kept
+        grid (SmoothingMoments.var, SmoothingCovariance.var); None: they are known at the anchors alone, and the other rows are nan."""
+        q = self._anchor_at.get(int(s))
+        if q is None:
+            raise KeyError(f"{int(s)} is not an anchor (anchors: {self.anchors.tolist()})")
+        i = self._row(s)
+        c = np.diagonal(self._cross[q], axis1=1, axis2=2) - self._mean * self._mean[i][None, :]
+        if var is None:
+            v = np.full(self._mean.shape, np.nan)
+            for a in self.anchors:
+                v[self._row(a)] = np.diagonal(self._cov(a, a))
+        else:
+            v = np.asarray(var, dtype=float).reshape(self._mean.shape)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            d = np.sqrt(np.where(v > 0.0, v, np.nan))
+            return self._vec(c / (d * d[i][None, :]))
+
+    def joint(self):
+        """(mean (n_anchor D,), covariance (n_anchor D, n_anchor D)) of the stacked anchor states (x_{s_1}, ..., x_{s_n}) | y: block (i, j)
+        of the covariance is cov(s_i, s_j), taken from the anchor rows of cross for j <= i and transposed above the diagonal; the diagonal
+        blocks are symmetrised (their two triangles are two roundings of the same sum)."""
+        n, d = self.anchors.size, self._mean.shape[1]
+        m = np.concatenate([self._mean[self._row(s)] for s in self.anchors])
+        out = np.empty((n * d, n * d))
+        for i, si in enumerate(self.anchors):
+            for j, sj in enumerate(self.anchors[:i + 1]):
+                c = self._cov(si, sj)
+                if j == i:
+                    c = 0.5 * (c + c.T)
+                out[i * d:(i + 1) * d, j * d:(j + 1) * d] = c
+                out[j * d:(j + 1) * d, i * d:(i + 1) * d] = c.T
+        return m, out
+
+
 def gaussian_ladder(mt, st, n_levels=31, width=4.0):
     """(D, n_levels): per component a uniform ladder from min_k (m - width sqrt(S)) to max_k (m + width sqrt(S)) of a Gaussian posterior on the
     grid.  mt (Np, D) or (Np,): the means; st (Np, D, D), (Np, D) or (Np,): the covariance matrices or the variances."""
@@ -629,6 +759,19 @@ class SmoothingPaths(_WalkRecord, _KeptGrid):
         w = self._weights(weights)
         dev = self.paths - np.tensordot(w, self.paths, axes=(0, 0))[None]
         return np.tensordot(w, dev * dev, axes=(0, 0))
+
+    def lag_covariance(self, anchors, context, weights=None):
+        """The two-time moments of these trajectories as a SmoothingLagCovariance (Context.path_cross_moments on `context`, a Context of
+        batch 1 and this model's D): equal weights for drawn final slots -- backward simulation's draws, which do not suffer the
+        genealogy's collapse --, `weights` (K,) for given ones.  lineage_ess of the record is nan: the trajectories are no genealogy's
+        sums."""
+        anc = np.asarray(anchors, dtype=np.int64).ravel()
+        if anc.size < 1 or np.any(anc % self.stride) or anc.min() < 0 or anc.max() >= self.n_pts:
+            raise ValueError(" SmoothingPaths: anchors must be kept grid indices.")
+        full = self.paths[..., None] if self.single_dim else self.paths
+        mean, cross = context.path_cross_moments(full[None], anc // self.stride, weights=self._weights(weights)[None])
+        return SmoothingLagCovariance(self.log_w, mean[0], cross[0], anc, self.stride, self.n_pts, self.obs_t, np.full(self.obs_t.size + 1, np.nan),
+                                      self.ess, self.resampled, self.single_dim)
 
     def distinct(self):
         """(M_p + 1,): the number of different slots among the K trajectories in every stretch -- the number of different paths there.

@@ -289,6 +289,22 @@ class VarGP(object):
         return self._particle_call("particle_covariance", lambda res, k: self._covariance_record(res, k, stride), n_paths, seed, stride=stride,
                                    ess_fraction=ess_fraction, x=x, x0=x0)
 
+    def _kernel_record(self, res, k, anchors, stride, obs_t=None):
+        """One problem's SmoothingLagCovariance from row k of Context.particle_lag_covariance's dict, cut to its own observations obs_t"""
+        from .particles import SmoothingLagCovariance
+        t = np.asarray(self._inputs()["obs_t"] if obs_t is None else obs_t).ravel()
+        return SmoothingLagCovariance(res["log_w"][k], res["mean"][k], res["cross"][k], anchors, stride, self.dim_n, t,
+                                      res["lineage_ess"][k, :t.size + 1], res["ess"][k, :t.size], res["resampled"][k, :t.size], self.model.single_dim)
+
+    def particle_kernel(self, n_paths, seed, anchors, stride=1, ess_fraction=0.5, x=None, x0=None):
+        """The particle estimate of the posterior's covariance function, Cov[x_k, x_s | y] for every kept grid index k and every anchor s,
+        from particle_filter with the same arguments: a particles.SmoothingLagCovariance (with batch > 1 a list, one per problem) -- cov,
+        corr, increment_var, autocorrelation and joint(), named and called as lagcov.LagCovariance's -- from the two-time moments of all
+        n_paths lineages, contracted on the device; only the moments are copied.  anchors: strictly increasing grid indices, multiples
+        of stride.  What to hold posterior_kernel()'s K(k, s) against; lineage_ess says how few lineages the early stretches rest on."""
+        return self._particle_call("particle_lag_covariance", lambda res, k: self._kernel_record(res, k, anchors, stride), n_paths, seed, anchors,
+                                   stride=stride, ess_fraction=ess_fraction, x=x, x0=x0)
+
     def _marginals_record(self, res, k, levels, stride, obs_t=None):
         """One problem's SmoothingMarginals from row k of Context.particle_marginals' dict, cut to its own observations obs_t"""
         from .particles import SmoothingMarginals
