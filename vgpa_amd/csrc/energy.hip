@@ -210,6 +210,48 @@ __device__ __forceinline__ void wave_gemm_elem(int u, int& row, int& col, bool& 
   row = 4 * Ib + r4; col = 4 * Jb + c4;
 }
 
+// ---- X^T diag(q) X, lower triangle, in 16 x 16 tiles (v_mfma_f64_16x16x4_f64) for the packed dE/dS of 33 <= D <= 40 (NB = 9, 10) --------
+// Lane l gives A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15] and holds C[(l >> 4) + 4 r][l & 15] in r = 0..3 (sample.hip).  Both
+// operands of tile (I, J <= I) are fragments of X = L^-1: A[i][k] = X[4K + k][16I + i], B[k][j] = q[4K + k] X[4K + k][16J + j].  X is lower
+// triangular, so tile (I, J) sums the k-steps K >= 4 I only, known at compile time.  What decides this phase's time is the matrix pipe's
+// cycles (measured: EXPERIMENTS.md s.17), and a 16 x 16 x 4 product takes 64 of them where a 4 x 4 x 4 unit (a row block of four rows x 16
+// columns) takes 16.  So a tile product is issued only where all four row blocks of its block-row take part: from k-step 4 I + 3 on in the
+// block-rows 0 and 1 (13 products at NB = 10).  The first three k-steps of a block-row reach 1, 2, 3 of its row blocks (row i of the result
+// takes k >= i), and the last block-row has NB - 8 row blocks at all: those are 4 x 4 x 4 units (27 at NB = 10) whose B operand is the same
+// scaled fragment and whose A operand X[4K + k][4 I2 + i] is one more read per (K, row block).  33 reads of X and 40 products, where the
+// 4 x 4 x 4 units of wave_gemm<NB, 1, 2> take 78 products from 75 reads (and dE/dm another 40 + 40 reads).
+template <int NB>
+struct TileSyrk {
+  static constexpr bool on = (NB == 9 || NB == 10);
+  static constexpr int MT = (NB + 3) / 4, NTILE = (MT - 1) * MT / 2;       // tile columns; tiles of the block-rows 0 .. MT - 2
+  static constexpr int LAST0 = 4 * (MT - 1), NLAST = on ? NB - LAST0 : 1;   // the row blocks of the last block-row
+  static constexpr int tile(int I, int J) { return I * (I + 1) / 2 + J; }
+  static constexpr int first_k(int I) { return 4 * I; }              // first k-step of the tiles of block-row I ...
+  static constexpr int first_row(int I) { return 4 * first_k(I); }   // ... = the first row of X that tile column I is read at
+  static constexpr int whole_k(int I) { return first_k(I) + 3; }      // from this k-step on all four row blocks of block-row I take part
+  static constexpr int products() {                                  // 16 x 16 x 4
+    int p = 0;
+    for (int I = 0; I < MT - 1; I++) p += (I + 1) * (NB - whole_k(I));
+    return p;
+  }
+  static constexpr int unit_products() {                             // 4 x 4 x 4: the first three k-steps of a block-row, the last block-row
+    int p = 0;
+    for (int I = 0; I < MT - 1; I++) p += (I + 1) * (1 + 2 + 3);
+    for (int v = 0; v < NLAST; v++) p += MT * (NB - (LAST0 + v));
+    return p;
+  }
+  // the order of the k-steps: the steps every tile takes first (independent chains), then a step of block-rows 0 and 1 and a step that
+  // only tile (0, 0) takes in turn -- the four products that tile alone needs would else be one dependent chain
+  struct Order { int k[NB]; };
+  static constexpr Order order() {
+    Order o{};
+    int n = 0;
+    for (int K = NB - 1; K >= 8; K--) o.k[n++] = K;
+    for (int s = 0; s < 4; s++) { o.k[n++] = 7 - s; o.k[n++] = 3 - s; }
+    return o;
+  }
+};
+
 struct L96Lds {
   double *Lm, *Gm, *mv, *bv, *am, *sg, *vv, *dl, *qq, *rd;
 };
@@ -1059,7 +1101,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NB <= 1
   }
 
   // ---- 5. dE/dm = (c/2) X^T delta ; dE/dS = (c/2) X^T diag(q) X
-  {
+  constexpr bool TILE = TileSyrk<NB>::on;        // the packed triangle of 33 <= D <= 40 comes from 16 x 16 tiles, and dE/dm with it (below)
+  if (!(TILE && a.ds_packed)) {
     double s = 0.0;
     if constexpr (CMP) {               // (rows 0 .. 7 of the columns >= 16 hold the diagonal blocks' inverses, not the zeros of X: masked)
       const bool z0 = li < 4, z1 = li < 8;
@@ -1073,7 +1116,102 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NB <= 1
   double* ds = a.dEs + o * D * D;
   {
     double acc[WaveGemmGeo<NB>::NU];
-    if (a.ds_packed) {                // the lower triangle, packed (a row's 16-column segment of a unit is contiguous): the units above the
+    if (TILE && a.ds_packed) {
+      // the lower triangle, packed, from 16 x 16 tiles on v_mfma_f64_16x16x4_f64 (TileSyrk): ONE fragment of X per (k-step K, tile column I),
+      // lane (g = l >> 4, n = l & 15) reads X[4K + g][16I + n].  It is the A operand of every tile of block-row I, times q[4K + g] the B
+      // operand of every tile of block-column I, and times delta[4K + g] this lane's share of dE/dm[16I + n].
+      //   * The LAST block-row (rows 32 .. Dp - 1: four or eight rows of a tile's sixteen) and the first three k-steps of the other two are
+      //     4 x 4 x 4 units, one per (row block I2, 16-column group u): the scaled fragment of group u IS the unit's B operand -- block slot
+      //     b = (l >> 2) & 3 holds the columns 16u + 4b .. + 3 -- and the A operand X[4K + g][4 I2 + c4] is one more read per (K, I2 <= K).
+      //   * Tile column MT - 1 reaches past the matrix (columns Dp .. 16 MT - 1): those lanes read column Dp - 1 of the same row instead --
+      //     a valid, finite entry of X; all they produce lies in columns >= Dp >= D of the result (or in dE/dm beyond D) and is never stored.
+      //   * X is lower triangular: tile column I is read from row 16 I on.  In the compact layout (NB = 10) the rows 0 .. 7 of the columns
+      //     >= 16 hold the diagonal blocks' inverses, not the zeros of X: no tile column but the first is read above row 16, so nothing is masked.
+      if constexpr (TILE) {
+        using ts = TileSyrk<NB>;
+        static_assert(ts::MT == 3 && ts::first_row(1) >= 8 && ts::first_row(2) >= 8, "rows 0 .. 7 of the columns >= 16 are not X (compact layout)");
+        static_assert(ts::first_row(ts::MT - 1) < Dp && 4 * (NB - 1) + 3 < Dp, "every fragment row lies inside the matrix");
+        static_assert(ts::products() == (NB == 10 ? 13 : 10) && ts::unit_products() == (NB == 10 ? 27 : 21), "k-steps per tile: NB - 4 I - 3; units: 6 per tile, NB - I2 per row block of the last block-row");
+        typedef double d4_t __attribute__((ext_vector_type(4)));
+        constexpr auto ord = ts::order();
+        const int g = l >> 4, n = l & 15;
+        double* dsp = a.dEs + o * PK;
+        const double* xf[ts::MT];
+#pragma unroll
+        for (int I = 0; I < ts::MT; I++) xf[I] = S.Lm + g * LD + (16 * I + n < Dp ? 16 * I + n : Dp - 1);
+        const double* xa = S.Lm + g * LD + c4;            // A operand of the 4 x 4 x 4 units: [i = c4][k = g]
+        d4_t ct[ts::NTILE];
+        double cl[ts::NLAST][ts::MT], dmp[ts::MT];
+#pragma unroll
+        for (int u = 0; u < ts::NTILE; u++) ct[u] = d4_t{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int I = 0; I < ts::MT; I++) {
+          dmp[I] = 0.0;
+#pragma unroll
+          for (int v = 0; v < ts::NLAST; v++) cl[v][I] = 0.0;
+        }
+#pragma unroll
+        for (int s = 0; s < NB; s++) {
+          const int K = ord.k[s];
+          const double qk = S.qq[4 * K + g], dk = S.dl[4 * K + g];
+          double fa[ts::MT], fb[ts::MT];
+#pragma unroll
+          for (int I = 0; I < ts::MT; I++)
+            if (ts::first_k(I) <= K) {
+              fa[I] = xf[I][4 * K * LD];
+              fb[I] = qk * fa[I];
+              dmp[I] = __builtin_fma(fa[I], dk, dmp[I]);
+            }
+#pragma unroll
+          for (int I = 0; I < ts::MT - 1; I++) {
+            if (ts::whole_k(I) <= K) {
+#pragma unroll
+              for (int J = 0; J <= I; J++) ct[ts::tile(I, J)] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[I], fb[J], ct[ts::tile(I, J)], 0, 0, 0);
+            } else if (ts::first_k(I) <= K) {
+              // the first three k-steps of a block-row reach its row blocks 4I .. K only (row i of the result takes k >= i): register r of
+              // a tile's accumulator IS the 4 x 4 x 4 unit of row block 4I + r over the tile's sixteen columns
+#pragma unroll
+              for (int r = 0; r <= K - ts::first_k(I); r++) {
+                const double ar = xa[4 * K * LD + 4 * (ts::first_k(I) + r)];
+#pragma unroll
+                for (int J = 0; J <= I; J++) ct[ts::tile(I, J)][r] = __builtin_amdgcn_mfma_f64_4x4x4f64(ar, fb[J], ct[ts::tile(I, J)][r], 0, 0, 0);
+              }
+            }
+          }
+#pragma unroll
+          for (int v = 0; v < ts::NLAST; v++)
+            if (ts::LAST0 + v <= K) {
+              const double ar = xa[4 * K * LD + 4 * (ts::LAST0 + v)];
+#pragma unroll
+              for (int u = 0; u < ts::MT; u++) cl[v][u] = __builtin_amdgcn_mfma_f64_4x4x4f64(ar, fb[u], cl[v][u], 0, 0, 0);
+            }
+        }
+        // dE/dm: the four lane groups g of a column are summed by one ones-product (block slot = (l >> 2) & 3, k = g); lanes 0 .. 15 store
+#pragma unroll
+        for (int I = 0; I < ts::MT; I++) {
+          const double s = __builtin_amdgcn_mfma_f64_4x4x4f64(1.0, dmp[I], 0.0, 0, 0, 0);
+          const int i = 16 * I + n;
+          if (g == 0 && i < D) a.dEm[o * D + i] = 0.5 * c * s;
+        }
+        // a tile's lane holds C[16I + g + 4r][16J + n], a unit's lane C[4 I2 + g][16u + n]: sixteen lanes write 128 contiguous bytes of a packed row
+#pragma unroll
+        for (int I = 0; I < ts::MT - 1; I++)
+#pragma unroll
+          for (int J = 0; J <= I; J++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+              const int row = 16 * I + g + 4 * r, col = 16 * J + n;
+              if (row < D && col <= row) dsp[tri_off(row) + col] = 0.5 * c * ct[ts::tile(I, J)][r];
+            }
+#pragma unroll
+        for (int v = 0; v < ts::NLAST; v++)
+#pragma unroll
+          for (int u = 0; u < ts::MT; u++) {
+            const int row = 4 * (ts::LAST0 + v) + g, col = 16 * u + n;
+            if (row < D && col <= row) dsp[tri_off(row) + col] = 0.5 * c * cl[v][u];
+          }
+      }
+    } else if (!TILE && a.ds_packed) { // the lower triangle, packed (a row's 16-column segment of a unit is contiguous): the units above the
       using gg = WaveGemmGeo<NB>;     // diagonal are not computed
       double* dsp = a.dEs + o * PK;
       wave_gemm<NB, 1, 2>(S.Lm, S.Lm, LD, acc, S.qq);
