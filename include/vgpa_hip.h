@@ -555,6 +555,55 @@ int vgpa_particle_backward_paths(vgpa_ctx* ctx, const double* x_or_null, const d
                                  const double* prior_mu_or_null, const double* prior_tau_or_null, double* logw, double* state, double* paths,
                                  int32_t* slots_or_null, double* ess_or_null, int32_t* resampled_or_null);
 
+/* The smoothing moments on the time grid under the marginal backward smoother (Doucet, Godsill & Andrieu 2000): what
+ * vgpa_particle_moments estimates, with the weights of every stretch taken from all n = n_paths particles of the filter's stored clouds and
+ * not from the lineages that survive the resamplings -- the expectation of the draw vgpa_particle_backward_paths makes, with its block-state
+ * argument: one n x n table of transition densities per resampled observation.  Stretches, t_j, c, x_i(k), clouds_j, anc_j, hlw_j, R_dd and
+ * the resampling flags are those of vgpa_particle_backward_paths; the filter of vgpa_particle_filter runs unchanged.  Per problem p:
+ *   W^c_i       = w_i / sum w,  w_i = exp(lw_i - max lw) of the final log-weights: vgpa_particle_moments' first row, bit for bit
+ *   W^j         for j = c-1 .. 0, not resampled at observation j: W^{j+1}
+ *               resampled (so k = t_j < Np-1), for every successor slot s < n and candidate i < n:
+ *     1. x~_s = (z + dt (-A_k z + b_k)) + R xi with z = clouds_j[anc_j[s]], xi the sampler's normals of counter (k+1, s, p, .): step 1 of
+ *        vgpa_particle_backward_paths with s in place of s_{j+1}[m], in plain fp64
+ *     2. b_{s,i} = hlw_j[i] - 1/2 sum_d ((x~_{s,d} - mu_{i,d}) / R_dd)^2, mu_i = clouds_j[i] + dt f(clouds_j[i]; theta_p): step 2 there; the
+ *        device multiplies by 1 / R_dd, and for Lorenz-96 with D >= 5 it evaluates the sum as (|a_s|^2 + |m_i|^2) - 2 <a_s, m_i> with
+ *        a = (x~ - c) / R, m = (mu - c) / R and c the mean of clouds_j, the cross term on the fp64 matrix cores (equal
+ *        within the rounding bound of the scores)
+ *     3. P_{s,i} = exp(b_{s,i} - max_i b_{s,i}) / sum_i exp(b_{s,i} - max_i b_{s,i})
+ *     4. W^j_i = sum_s W^{j+1}_s P_{s,i}, the terms added in an order n alone fixes: no atomics, nothing that depends on the launch
+ *   With the indicator i = anc_j[s] in place of P this is vgpa_particle_moments' recursion; nothing else differs from that call.
+ *   moments          host, [batch][n_keep][2][D] as in vgpa_particle_moments: M1[k][d] = sum_i W^{j(k)}_i x_i(k)[d] and M2 likewise, by the
+ *                    same second walk.  With ess_fraction = 0, or n_paths = 1, nothing is resampled and moments are vgpa_particle_moments'
+ *                    bit for bit.  Two calls with the same arguments give the same bits, and a problem's results do not depend on the
+ *                    batch around it
+ *   smoothing_ess_or_null  host, [batch][M+1]: 1 / sum_i (W^j_i)^2 for j = 0 .. c (at a carried cut: the entry of j + 1); rows beyond a
+ *                    problem's own count + 1: 0, as lineage_ess of vgpa_particle_moments
+ *   weights_or_null  host, [batch][M+1][n]: W^j_i, downloaded only when asked for; rows beyond a problem's own count + 1: 0
+ *   logw, state, ess_or_null, resampled_or_null and every other argument: as in vgpa_particle_filter, and bit-identical to its results with
+ *   the same arguments.  With x NULL the cached state is read and not written
+ * Where the particles of a cloud lie many transition widths apart (the Lorenz-96 fixtures) P is one-hot on the ancestor and the result is
+ * vgpa_particle_moments': the gain is on clouds that overlap, the 1-D and 3-D models with many observations.  It is no cure
+ * for a filter that has lost the posterior: the clouds are the filter's.
+ * Device memory: the histories of vgpa_particle_backward_paths, batch * M * n * (D + 1) doubles, the table batch * (M+1) * n, and batch *
+ * (n * (D + 2) + 64 + (M+1) * ceil(n / 64)) of work space (the successors, their (max, sum), the centre, the partial sums of W^2); the n x n table of a cut is never stored.  Work: 2 n^2 scores of D terms per resampled observation.
+ * Errors and limits: those of vgpa_particle_moments and of vgpa_particle_backward_paths (D > 64 and a dense Sigma are VGPA_ERR_UNSUPPORTED),
+ * and VGPA_ERR_UNSUPPORTED, before any work, for more than 65535 * 16 particles per problem or more than 65535 * 256 / D. */
+int vgpa_particle_backward_moments(vgpa_ctx* ctx, const double* x_or_null, const double* x0_or_null, int32_t n_paths, int32_t stride, uint64_t seed,
+                                   double ess_fraction, const double* prior_mu_or_null, const double* prior_tau_or_null, double* logw, double* state,
+                                   double* moments, double* smoothing_ess_or_null, double* weights_or_null, double* ess_or_null,
+                                   int32_t* resampled_or_null);
+
+/* hlw_j of the last vgpa_particle_backward_paths or vgpa_particle_backward_moments call on this context, as its kernels read them: the
+ * log-weights its resamplings replaced.  What a caller needs, beside vgpa_particle_filter's ancestors and clouds, to recompute a backward
+ * table on the host from the device's own histories.
+ *   n_paths     that call's n_paths
+ *   hlw         host, [batch][M][n_paths]: hlw_j[i] where the cloud of the problem's observation j was resampled; NaN in every other row
+ * Errors: VGPA_ERR_ARG for a NULL hlw; VGPA_ERR_STATE unless the last call on this context that ran the particle filter (every
+ * vgpa_particle_* entry point but a vgpa_particle_forecast from a given cloud) was one of the two, succeeded and had this n_paths.  Calls
+ * that run no filter -- vgpa_path_cross_moments, the forecast from a given cloud, the sweeps -- leave these histories as they are, and
+ * the accessor goes on returning them.  Reads nothing of the cached state and writes nothing to it. */
+int vgpa_particle_replaced_logw(vgpa_ctx* ctx, int32_t n_paths, double* hlw);
+
 /* The conditional particle filter with ancestor sampling: one sweep of particle Gibbs (Andrieu, Doucet & Holenstein 2010;
  * Lindsten, Jordan & Schoen 2014).  Given a reference trajectory per problem it returns a new trajectory whose law leaves the smoothing
  * distribution of the Euler-discretised model invariant for any n_paths >= 2 and any proposal (A_t, b_t).  It is vgpa_particle_filter with

@@ -2,7 +2,7 @@
 Time of Context.sample_paths (vgpa_sample_paths), Context.sample_paths_weighted (vgpa_sample_paths_weighted), Context.particle_filter
 (vgpa_particle_filter), Context.particle_statistics (vgpa_particle_statistics), Context.particle_events (vgpa_particle_events), Context.particle_moments (vgpa_particle_moments),
 Context.particle_covariance (vgpa_particle_covariance), Context.particle_marginals (vgpa_particle_marginals), Context.particle_paths (vgpa_particle_paths), Context.particle_backward_paths
-(vgpa_particle_backward_paths) and Context.particle_forecast (vgpa_particle_forecast) on their jobs, one JSON line.
+(vgpa_particle_backward_paths), Context.particle_backward_moments (vgpa_particle_backward_moments) and Context.particle_forecast (vgpa_particle_forecast) on their jobs, one JSON line.
 
     python tools/bench_sample_paths.py [--rounds 3] [--calls 5] [--jobs a,b,c,aw,aw0,bw,bw0,af64_0,af64_5,af1024_0,af1024_5,bf64_0,...]
     python tools/bench_sample_paths.py --statistics [--filter-problems 4096]      # the as* and bs* jobs
@@ -11,6 +11,7 @@ Context.particle_covariance (vgpa_particle_covariance), Context.particle_margina
     python tools/bench_sample_paths.py --covariance [--filter-problems 4096]      # the ac* and bc* jobs
     python tools/bench_sample_paths.py --marginals [--filter-problems 4096] [--levels 31]      # the ah* and bh* jobs
     python tools/bench_sample_paths.py --paths [--filter-problems 4096] [--paths-strides 1,10]      # the ap* and bp* jobs, once per stride
+    python tools/bench_sample_paths.py --backward-moments [--smooth-problems 8]      # the aw*, bw* and ow* jobs
     python tools/bench_sample_paths.py --backward [--filter-problems 4096] [--paths-strides 10] [--parent-json FILE]      # the ab* and bb* jobs
     python tools/bench_sample_paths.py --gibbs [--filter-problems 4096]           # the ag* and bg* jobs
     python tools/bench_sample_paths.py --lag-covariance [--lag-problems 512] [--filter-problems 4096]      # the al* and bl* jobs
@@ -112,7 +113,8 @@ for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")):
 
 HBM_BYTES_PER_S = 8.0e12
 N_PTS, DT = 1001, 0.01
-JOBS = {"a": ("L96", 40, 512, "posterior", 64, 100), "b": ("L63", 3, 65536, "posterior", 1, 100), "c": ("L63", 3, 65536, "model", 1, 1)}
+JOBS = {"a": ("L96", 40, 512, "posterior", 64, 100), "b": ("L63", 3, 65536, "posterior", 1, 100), "c": ("L63", 3, 65536, "model", 1, 1),
+        "o": ("OU", 1, 65536, "posterior", 1, 100)}      # (o: the context of the ow* jobs alone)
 WEIGHTED = {"aw": ("a", True), "aw0": ("a", False), "bw": ("b", True), "bw0": ("b", False)}      # job -> (its unweighted twin, paths stored)
 FILTER = {f"{t}f{n}_{f}": (t, n, 0.1 * f) for t in "ab" for n in (64, 1024) for f in (0, 5)}      # job -> (context of, particles, ess_fraction)
 STATS = {f"{t}s{n}_{f}": (t, n, 0.1 * f) for t in "ab" for n in (64, 1024) for f in (0, 5)}       # job -> as FILTER
@@ -122,6 +124,10 @@ COV = {f"{t}c{n}_{s}": (t, n, s) for t in "ab" for n in (64, 1024) for s in (1, 
 MARG = {f"{t}h{n}_{s}": (t, n, s) for t in "ab" for n in (64, 1024) for s in (1, 10)}                       # job -> as MOMENTS
 PATHS = {f"{t}p{n}_{k}": (t, n, k) for t in "ab" for n in (64, 1024) for k in (16, 64)}           # job -> (context of, particles, trajectories)
 BACKWARD = {f"{t}b{n}_{k}": (t, n, k) for t in "ab" for n in (64, 1024) for k in (16, 64)}        # job -> as PATHS
+# (--backward-moments selects all six) particle_backward_moments beside particle_moments (the genealogical call), particle_backward_paths with
+# K = n (the existing kernel forming the same n^2 scores once, with its Gumbels) and particle_filter, the four calls alternating inside every
+# round, on --smooth-problems problems of the contexts of a, b and o: the histories take B M n (D + 1) doubles
+SMOOTH = {f"{t}w{n}": (t, n) for t in "abo" for n in (1024, 4096)}                                # job -> (context of, particles)
 GIBBS = {f"{t}g{n}": (t, n) for t in "ab" for n in (16, 64, 1024)}                                # job -> (context of, particles)
 LAG = {"al1024": ("a", 1024, 10), "bl64": ("b", 64, 10)}                                          # job -> as MOMENTS
 LAG_ANCHORS = 8
@@ -197,7 +203,7 @@ def run_forecast(B, n, horizon, rounds, calls):
     return out
 
 
-def run(job, rounds, calls, numpy_problems, cache, filter_problems=0, paths_stride=1, parent=None, n_levels=31, lag_problems=0):
+def run(job, rounds, calls, numpy_problems, cache, filter_problems=0, paths_stride=1, parent=None, n_levels=31, lag_problems=0, smooth_problems=8):
     from bench_problem_batch import StreamTimer, make_contexts
     twin, stored = WEIGHTED.get(job, (job, True))
     weighted = job in WEIGHTED
@@ -205,7 +211,11 @@ def run(job, rounds, calls, numpy_problems, cache, filter_problems=0, paths_stri
         twin = LAG[job][0]
     elif job in FILTER or job in STATS or job in EVENTS or job in MOMENTS or job in COV or job in MARG or job in PATHS or job in BACKWARD or job in GIBBS:
         twin = (FILTER.get(job) or STATS.get(job) or EVENTS.get(job) or MOMENTS.get(job) or COV.get(job) or MARG.get(job) or PATHS.get(job) or BACKWARD.get(job) or GIBBS[job])[0]
+    if job in SMOOTH:
+        twin = SMOOTH[job][0]
     name, d, B, kind, n_paths, stride = JOBS[twin]
+    if job in SMOOTH:
+        B = min(B, smooth_problems)
     if (job in FILTER or job in STATS or job in EVENTS or job in MOMENTS or job in COV or job in MARG or job in PATHS or job in BACKWARD or job in GIBBS) and twin == "b" and filter_problems:
         B = min(B, filter_problems)
     if job in LAG:
@@ -510,6 +520,42 @@ def run(job, rounds, calls, numpy_problems, cache, filter_problems=0, paths_stri
             out.update(parent_tree=row["tree"], parent_paths_ms_per_call=row["paths_ms_per_call"], parent_paths_rounds_ms=row["paths_rounds_ms"],
                        parent_filter_ms_per_call=row["filter_ms_per_call"], ratio_to_parent_paths=round(med["backward"] / row["paths_ms_per_call"], 4))
         return out
+    if job in SMOOTH:
+        _, n_paths = SMOOTH[job]
+        stride = N_PTS + 3      # (one kept grid index: the K = n trajectories of the draw's call leave as B n D doubles, not B n n_keep D)
+        calls_of = {"filter": lambda: c.particle_filter(n_paths, 1, ess_fraction=0.5),
+                    "moments": lambda: c.particle_moments(n_paths, 1, stride=stride, ess_fraction=0.5),
+                    "backward_moments": lambda: c.particle_backward_moments(n_paths, 1, stride=stride, ess_fraction=0.5, weights=False),
+                    "backward_paths": lambda: c.particle_backward_paths(n_paths, 1, n_paths, stride=stride, ess_fraction=0.5)}
+        res0 = {k: f() for k, f in calls_of.items()}      # warm-up (first-use allocations)
+        for key in ("log_w", "state", "ess", "resampled"):
+            assert all(np.array_equal(res0["filter"][key], res0[k][key]) for k in calls_of), key
+        got, old = res0["backward_moments"], res0["moments"]
+        assert got["moments"].shape == old["moments"].shape and np.all(np.isfinite(got["moments"]))
+        ess = {"backward": np.median(got["smoothing_ess"], axis=0), "genealogy": np.median(old["lineage_ess"], axis=0)}
+        del res0["backward_paths"]["paths"]
+        per_round = {k: [] for k in calls_of}
+        for _ in range(rounds):
+            ms = {k: [] for k in calls_of}
+            for _ in range(calls):
+                for k, f in calls_of.items():
+                    ms[k].append(tm.ms(f))
+            for k in calls_of:
+                per_round[k].append(float(np.median(ms[k])))
+        med = {k: float(np.median(v)) for k, v in per_round.items()}
+        out = {"job": job, "model": name, "D": d, "Np": N_PTS, "B": B, "kind": "backward_moments", "n_paths": n_paths, "ess_fraction": 0.5, "stride": stride,
+               "observations": int(c.n_obs), "resampled_share": round(float(res0["filter"]["resampled"].mean()), 3)}
+        for k in calls_of:
+            out[k + "_ms_per_call"] = round(med[k], 4)
+            out[k + "_rounds_ms"] = [round(v, 4) for v in per_round[k]]
+        out.update(ratio_to_moments=round(med["backward_moments"] / med["moments"], 4),
+                   ratio_to_backward_paths=round(med["backward_moments"] / med["backward_paths"], 4),
+                   pass_ms_over_moments=round(med["backward_moments"] - med["moments"], 4),
+                   draw_ms_over_filter=round(med["backward_paths"] - med["filter"], 4),
+                   smoothing_ess_first_middle=[round(float(ess["backward"][0]), 2), round(float(ess["backward"][ess["backward"].size // 2]), 2)],
+                   lineage_ess_first_middle=[round(float(ess["genealogy"][0]), 2), round(float(ess["genealogy"][ess["genealogy"].size // 2]), 2)],
+                   histories_on_device_mb=round(8.0 * B * int(c.n_obs) * n_paths * (d + 1) / 1e6, 1))
+        return out
     if job in GIBBS:
         _, n_paths = GIBBS[job]
         ref = np.ascontiguousarray(c.particle_paths(n_paths, 2, 1, ess_fraction=0.5)["paths"][:, 0])
@@ -619,6 +665,8 @@ def main():
     ap.add_argument("--paths", action="store_true", help="run the ap* and bp* jobs (particle_paths beside particle_filter)")
     ap.add_argument("--paths-strides", default="1,10", help="strides of the ap* and bp* jobs: each job runs once per stride")
     ap.add_argument("--backward", action="store_true", help="run the ab* and bb* jobs (particle_backward_paths beside particle_paths and particle_filter)")
+    ap.add_argument("--backward-moments", action="store_true", help="run the aw*, bw* and ow* jobs (particle_backward_moments beside particle_moments, particle_backward_paths with K = n and particle_filter)")
+    ap.add_argument("--smooth-problems", type=int, default=8, help="B of the aw*, bw* and ow* jobs")
     ap.add_argument("--gibbs", action="store_true", help="run the ag* and bg* jobs (particle_conditional beside particle_paths and particle_filter)")
     ap.add_argument("--parent-json", default="", help="output of the parent commit's --paths run of the same jobs: its times are reported beside")
     ap.add_argument("--forecast", action="store_true", help="run the forecast job (particle_forecast from a given cloud beside the model-kind sampler)")
@@ -647,6 +695,8 @@ def main():
         args.jobs = ",".join(sorted(PATHS))
     if args.backward and args.jobs == "a,b,c":
         args.jobs = ",".join(sorted(BACKWARD))
+    if args.backward_moments and args.jobs == "a,b,c":
+        args.jobs = ",".join(sorted(SMOOTH))
     if args.gibbs and args.jobs == "a,b,c":
         args.jobs = ",".join(sorted(GIBBS))
     parent = {}
@@ -662,7 +712,7 @@ def main():
     out = {"tool": "bench_sample_paths", "tree": tree(), "unit": "ms per call (device events around the call)", "jobs": []}
     for job in [j for j in args.jobs.split(",") if j]:
         for stride in (strides if job in PATHS or job in BACKWARD else [1]):
-            out["jobs"].append(run(job, args.rounds, args.calls, args.numpy_problems, cache, args.filter_problems, stride, parent, args.levels, args.lag_problems))
+            out["jobs"].append(run(job, args.rounds, args.calls, args.numpy_problems, cache, args.filter_problems, stride, parent, args.levels, args.lag_problems, args.smooth_problems))
     for c, _, _, _, tm in cache.values():
         tm.close()
         c.close()

@@ -13,10 +13,10 @@ from .variational import VarGP                                             # noq
 from .scg import SCG, DeviceSCG                                            # noqa: F401
 from .batch import ProblemBatch                                            # noqa: F401
 from .weights import PathWeights                                           # noqa: F401
-from .particles import ParticleFilterResult, PathStatistics, PathEvents, SmoothingMoments, SmoothingCovariance, SmoothingLagCovariance, SmoothingMarginals, SmoothingPaths, Forecast, GibbsChain   # noqa: F401
+from .particles import ParticleFilterResult, PathStatistics, PathEvents, SmoothingMoments, BackwardSmoothingMoments, SmoothingCovariance, SmoothingLagCovariance, SmoothingMarginals, SmoothingPaths, Forecast, GibbsChain   # noqa: F401
 from .h5io import save_h5, load_h5, result_dict, save_results, load_results   # noqa: F401
 
 __all__ = ["Context", "device_count", "load", "OdeSolver", "Euler", "Heun", "RungeKutta2", "RungeKutta4",
            "num_integration", "FwdOde", "BwdOde", "StochasticProcess", "OrnsteinUhlenbeck", "DoubleWell",
            "Lorenz63", "Lorenz96", "dynamical_systems", "Likelihood", "GaussianLikelihood", "PriorKL0",
-           "VarGP", "ProblemBatch", "PathWeights", "ParticleFilterResult", "PathStatistics", "PathEvents", "SmoothingMoments", "SmoothingCovariance", "SmoothingLagCovariance", "SmoothingMarginals", "SmoothingPaths", "Forecast", "GibbsChain", "SCG", "DeviceSCG", "result_dict", "save_results", "load_results", "save_h5", "load_h5"]
+           "VarGP", "ProblemBatch", "PathWeights", "ParticleFilterResult", "PathStatistics", "PathEvents", "SmoothingMoments", "BackwardSmoothingMoments", "SmoothingCovariance", "SmoothingLagCovariance", "SmoothingMarginals", "SmoothingPaths", "Forecast", "GibbsChain", "SCG", "DeviceSCG", "result_dict", "save_results", "load_results", "save_h5", "load_h5"]

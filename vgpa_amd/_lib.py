@@ -39,7 +39,7 @@ MAX_MARGINAL_LEVELS = 63      # kMaxMarginalLevels of the library: a bin is foun
 SYMBOLS = ["vgpa_create", "vgpa_destroy", "vgpa_last_error", "vgpa_abi_version", "vgpa_device_count",
            "vgpa_synchronize", "vgpa_stream", "vgpa_solve_fwd", "vgpa_solve_bwd", "vgpa_energy",
            "vgpa_obs_energy", "vgpa_free_energy", "vgpa_gradient", "vgpa_sweep", "vgpa_energy_parts",
-           "vgpa_fetch", "vgpa_theta_gradient", "vgpa_lag_covariance", "vgpa_sample_paths", "vgpa_sample_paths_weighted", "vgpa_particle_filter", "vgpa_particle_statistics", "vgpa_particle_events", "vgpa_particle_moments", "vgpa_particle_covariance", "vgpa_particle_marginals", "vgpa_particle_lag_covariance", "vgpa_path_cross_moments", "vgpa_particle_paths", "vgpa_particle_backward_paths", "vgpa_particle_conditional", "vgpa_particle_forecast", "vgpa_sweep_dev", "vgpa_free_energy_dev", "vgpa_sweep_enqueue", "vgpa_fetch_f",
+           "vgpa_fetch", "vgpa_theta_gradient", "vgpa_lag_covariance", "vgpa_sample_paths", "vgpa_sample_paths_weighted", "vgpa_particle_filter", "vgpa_particle_statistics", "vgpa_particle_events", "vgpa_particle_moments", "vgpa_particle_covariance", "vgpa_particle_marginals", "vgpa_particle_lag_covariance", "vgpa_path_cross_moments", "vgpa_particle_paths", "vgpa_particle_backward_paths", "vgpa_particle_backward_moments", "vgpa_particle_replaced_logw", "vgpa_particle_conditional", "vgpa_particle_forecast", "vgpa_sweep_dev", "vgpa_free_energy_dev", "vgpa_sweep_enqueue", "vgpa_fetch_f",
            "vgpa_dev_alloc", "vgpa_dev_free", "vgpa_memcpy_h2d", "vgpa_memcpy_d2h",
            "vgpa_profile_begin", "vgpa_profile_end", "vgpa_ld_gemm", "vgpa_ld_stage", "vgpa_gradient_dev", "vgpa_energy_full", "vgpa_set_option", "vgpa_is_streaming", "vgpa_path_info", "vgpa_set_prior_energy",
            "vgpa_set_problem_data", "vgpa_set_problem_params", "vgpa_set_problem_obs_model",
@@ -162,6 +162,9 @@ def load():
     lib.vgpa_particle_paths.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_uint64, c_double, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vgpa_particle_backward_paths.argtypes = lib.vgpa_particle_paths.argtypes
+    lib.vgpa_particle_backward_moments.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_uint64, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.vgpa_particle_replaced_logw.argtypes = [c_void_p, c_int32, c_void_p]
     lib.vgpa_particle_conditional.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_uint64, c_double, c_void_p, c_void_p, c_void_p,
                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vgpa_particle_forecast.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_uint64, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
@@ -768,6 +771,29 @@ class Context:
         and lineage_ess (B, M + 1): 1 / sum W^2 of every stretch between two observations (0 beyond a problem's own count + 1)."""
         return self._filter_call("vgpa_particle_moments", {"n_paths": n_paths, "stride": stride}, seed, ess_fraction, x, x0, prior, lambda n, k, n_keep: {
             "moments": self._new(n_keep, 2, self.D), "lineage_ess": self._new(self.n_obs + 1, fill=0.0)})
+
+    def particle_backward_moments(self, n_paths, seed, stride=1, ess_fraction=0.5, x=None, x0=None, prior=None, weights=True):
+        """The smoothing moments on the grid under the marginal backward smoother (vgpa_particle_backward_moments): particle_moments with the
+        weights of every stretch taken from all n particles of particle_filter's stored clouds -- at every observation where the cloud was
+        resampled W^j = W^{j+1} P, P the row-normalised table of filter weight times model transition density, the expectation of
+        particle_backward_paths' draw -- and not from the lineages the resamplings have left.  Returns a dict: log_w, state, ess, resampled as
+        particle_filter (bit for bit), moments (B, n_keep, 2, D) as particle_moments, smoothing_ess (B, M + 1): 1 / sum W^2 of every stretch
+        (0 beyond a problem's own count + 1), and weights (B, M + 1, n_paths): the table itself (weights=True, else None).  Where nothing
+        was resampled (ess_fraction=0, n_paths=1) moments are particle_moments' bit for bit; where the particles of a cloud lie many
+        transition widths apart P is one-hot and the result is the genealogy's."""
+        return self._filter_call("vgpa_particle_backward_moments", {"n_paths": n_paths, "stride": stride}, seed, ess_fraction, x, x0, prior, lambda n, k, n_keep: {
+            "moments": self._new(n_keep, 2, self.D), "smoothing_ess": self._new(self.n_obs + 1, fill=0.0),
+            "weights": self._new(self.n_obs + 1, n, fill=0.0) if weights else None})
+
+    def particle_replaced_logw(self, n_paths):
+        """(B, M, n_paths): the log-weights the resamplings of the last particle_backward_paths / particle_backward_moments call with this
+        n_paths replaced (vgpa_particle_replaced_logw), the observation's term included; NaN where the cloud was carried on.  With
+        particle_filter(history=True)'s ancestors and clouds: the histories the backward kernels read."""
+        n_paths = int(n_paths)
+        self._fit32(n_paths=n_paths)
+        out = self._new(self.n_obs, max(n_paths, 0), fill=np.nan)
+        self._check(self._lib.vgpa_particle_replaced_logw(self._h, n_paths, _ptr(out)))
+        return out
 
     def particle_covariance(self, n_paths, seed, stride=1, ess_fraction=0.5, x=None, x0=None, prior=None):
         """The smoothing mean and the full second-moment matrices on the grid under particle_filter's genealogy (vgpa_particle_covariance):

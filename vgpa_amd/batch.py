@@ -259,6 +259,13 @@ class ProblemBatch(object):
         return self._particle_call("particle_moments", lambda v, res, k: v._moments_record(res, k, stride), n_paths, seed, stride=stride,
                                    ess_fraction=ess_fraction, x=x, x0=x0)
 
+    def backward_moments(self, n_paths, seed, stride=1, ess_fraction=0.5, x=None, x0=None):
+        """One particles.BackwardSmoothingMoments per member (VarGP.backward_moments): particle_moments under the weights of the marginal
+        backward smoother, each member with its own data, observation times and count, prior, theta and Sigma; a member's result does not
+        depend on the rest of the batch."""
+        return self._particle_call("particle_backward_moments", lambda v, res, k: v._backward_moments_record(res, k, stride), n_paths, seed,
+                                   stride=stride, ess_fraction=ess_fraction, x=x, x0=x0)
+
     def particle_covariance(self, n_paths, seed, stride=1, ess_fraction=0.5, x=None, x0=None):
         """One particles.SmoothingCovariance per member (VarGP.particle_covariance): the smoothing mean and full second-moment matrices on
         the grid under the genealogy of the member's own filter, with its own data, observation times and count, prior, theta and Sigma."""

@@ -49,6 +49,7 @@
 //                | steps; k_pf_quantise: the final weights as integers, k_pf_descend_q: k_pf_descend in 64-bit integer arithmetic]     |
 #include "vgpa_internal.h"
 #include "dispatch.h"
+#include "pf_device.h"
 
 #include <type_traits>
 
@@ -57,50 +58,7 @@ namespace {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t* r) {
-#pragma unroll
-  for (int i = 0; i < 10; i++) {
-    const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-    const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-    c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
-}
-
-__device__ __forceinline__ double unit_open(uint32_t hi, uint32_t lo) {
-  const double u = (((double)(hi >> 5) * 67108864.0 + (double)(lo >> 6)) + 0.5) * 0x1.0p-53;
-  return fmin(u, 0x1.fffffffffffffp-1);     // (2^53 - 1 + 0.5 rounds to 2^53 in fp64: the one value that would reach 1)
-}
-
-// the pair (xi_2j, xi_2j+1) of grid index k, path `path`, problem p
-__device__ __forceinline__ void normal_pair(uint32_t k0, uint32_t k1, uint32_t k, uint32_t path, uint32_t p, uint32_t j, double* z0, double* z1) {
-  uint32_t r[4];
-  philox4x32_10(k, path, p, j, k0, k1, r);
-  const double u1 = unit_open(r[0], r[1]), u2 = unit_open(r[2], r[3]);
-  const double rho = sqrt(-2.0 * log(u1));
-  double s, c;
-  sincos(6.283185307179586 * u2, &s, &c);
-  *z0 = rho * c; *z1 = rho * s;
-}
-
-// ---- D <= 4: one lane per (problem, path) -----------------------------------------------------------------------------------------
-template <int D>
-__device__ __forceinline__ void model_drift(int model, const double* th, const double* x, double* f) {
-  if (model == VGPA_MODEL_OU) { f[0] = -th[0] * x[0]; }
-  else if (model == VGPA_MODEL_DW) { f[0] = 4.0 * x[0] * (th[0] - x[0] * x[0]); }
-  else if (model == VGPA_MODEL_L63) {
-    if constexpr (D == 3) {
-      f[0] = th[0] * (x[1] - x[0]);
-      f[1] = (th[1] - x[2]) * x[0] - x[1];
-      f[2] = x[0] * x[1] - th[2] * x[2];
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < D; i++) f[i] = (x[(i + 1) % D] - x[(i + D - 2) % D]) * x[(i + D - 1) % D] - x[i] + th[0];
-  }
-}
-
+// ---- D <= 4: one lane per (problem, path) (model_drift: pf_device.h) ---------------------------------------------------------------
 // phi_j = d f_j / d theta_a(j) at x, a(j) the one parameter component j's drift depends on
 template <int D>
 __device__ __forceinline__ void model_phi(int model, const double* x, double* phi) {
@@ -145,17 +103,6 @@ __device__ __forceinline__ double obs_form(const SampleArgs& a, uint32_t p, int 
 
 __device__ __forceinline__ double obs_constant(const SampleArgs& a, uint32_t p) {
   return a.obs_const_scale * (a.obs_const_v ? a.obs_const_v[p] : a.obs_const);
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-  return v;
 }
 
 // What a walk's kernels take: SampleArgs, and for Conditional alone the reference trajectories behind it -- no other walk's arguments,
@@ -1339,13 +1286,6 @@ __device__ __forceinline__ int pf_bisect(const double* cum, int n, double u) {
   }
   return lo < n - 1 ? lo : n - 1;
 }
-__device__ __forceinline__ int pf_obs_at(const PfArgs& a, int p) {
-  const int64_t* t = a.obs_t + (size_t)p * a.obs_t_stride;
-  const int cnt = a.n_obs_v ? a.n_obs_v[p] : a.n_obs;
-  int j = -1;
-  for (int m = 0; m < cnt; m++) if (t[m] == (int64_t)a.k) j = m;
-  return j;
-}
 __device__ __forceinline__ double pf_prefix_sums(const double* lw, int n, double mx, double* cum, double* tot) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   double carry = 0.0, s2 = 0.0;
@@ -1848,14 +1788,7 @@ __global__ __launch_bounds__(256) void k_pf_backward(PfArgs f, SampleArgs a, int
 #pragma unroll
         for (int d = 0; d < DC; d++) mu[d] = xc[d] + a.dt * fc[d];
       } else if (mine) {
-        const double x_first = col[0];
-        double om2 = col[(D - 2) * LD], om1 = col[(D - 1) * LD], cur = x_first;
-        for (int d = 0; d < D; d++) {
-          const double nxt = d + 1 < D ? col[(d + 1) * LD] : x_first;
-          const double fd = (nxt - om2) * om1 - cur + th[0];
-          col[d * LD] = cur + a.dt * fd;
-          om2 = om1; om1 = cur; cur = nxt;
-        }
+        l96_mean_in_place(col, LD, D, a.dt, th[0]);
       }
       double acc[TB];
 #pragma unroll

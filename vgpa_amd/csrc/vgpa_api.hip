@@ -6,6 +6,7 @@
 #include <cstring>
 #include <functional>
 #include <string>
+#include <limits>
 #include <vector>
 
 #include "vgpa_internal.h"
@@ -181,11 +182,14 @@ struct vgpa_ctx {
   // vgpa_particle_lag_covariance: the slot table and d_sp_out of vgpa_particle_paths with all n_paths trajectories, [B][n][n_keep][D], which
   // stay on the device (the stride is the lever on their size), the descendant weights and behind them the normalised final weights
   // (PF_WTAB), the lineage ESS, PF_LAGR: the anchors' rows of the kept axis (int32), PF_LAG: the mean and behind it the cross moments;
-  // vgpa_path_cross_moments: d_sp_out (the given paths), PF_WTAB (the given weights), PF_LAGR and PF_LAG
+  // vgpa_path_cross_moments: d_sp_out (the given paths), PF_WTAB (the given weights), PF_LAGR and PF_LAG;
+  // vgpa_particle_backward_moments: the buffers of vgpa_particle_moments (PF_WTAB: the smoothing weights), the clouds and PF_HLW, PF_SMX: the
+  // successors of one cut [B][n][D], PF_SMR: every successor's (max, sum) [2][B][n], PF_SMP: the column workgroups' sums of W^2
   enum { PF_XA, PF_XB, PF_LW, PF_CUM, PF_ANC, PF_ESS, PF_FLAG, PF_HANC, PF_CLOUDS, PF_MU, PF_LT, PF_STA, PF_STB, PF_MEAN, PF_WTAB, PF_LESS, PF_PART,
-         PF_MOM, PF_SLOTS, PF_COV, PF_HLW, PF_REF, PF_EVC, PF_EVS, PF_CDF, PF_QTAB, PF_QFIN, PF_MGL, PF_MASS, PF_LAGR, PF_LAG, PF_COUNT };
+         PF_MOM, PF_SLOTS, PF_COV, PF_HLW, PF_REF, PF_EVC, PF_EVS, PF_CDF, PF_QTAB, PF_QFIN, PF_MGL, PF_MASS, PF_LAGR, PF_LAG, PF_SMX, PF_SMR, PF_SMP, PF_COUNT };
   double* d_pf[PF_COUNT] = {};
   size_t pf_n[PF_COUNT] = {};
+  int32_t pf_hlw_paths = 0;        // n_paths of the last particle call if it kept PF_HLW (vgpa_particle_replaced_logw reads it with PF_FLAG), else 0
   // profiling
   bool prof = false;
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -1629,7 +1633,7 @@ static int cross_moments(vgpa_ctx* c, const double* d_paths, const double* d_w, 
 // the filter is "fc_moments is set"; it goes with Carry::None and Behind::None alone.
 // (Carry -- nothing; the path statistics (Q, G, H); the event records (X, T, N) -- is vgpa_internal.h's: the walks carry by the same word)
 // (the order matters: table() below takes every enumerator from Trajectories on as a pass with a slot table; a new pass of sums goes before it)
-enum class Behind { None, Moments, Covariance, Marginals, LagCovariance, Trajectories, Backward, Conditional };
+enum class Behind { None, Moments, Covariance, BackwardMoments, Marginals, LagCovariance, Trajectories, Backward, Conditional };
 struct ParticleRequest {
   const double* x; const double* x0; int32_t n_paths; uint64_t seed; double ess_fraction; const double* prior_mu; const double* prior_tau;
   double* logw; double* state; double* ess; int32_t* resampled;      // (up to here: what every entry point has, filled in this order)
@@ -1639,6 +1643,7 @@ struct ParticleRequest {
   int32_t stride = 1;                                                // of the grid indices the smoothers, the events and the forecast keep
   Behind behind;
   double* moments; double* lineage_ess;                              // Behind::Moments (lineage_ess: Covariance too)
+  double* smooth_weights;                                            // Behind::BackwardMoments: moments; lineage_ess: the smoothing ESS; the table [B][M + 1][n]
   double* cov_mean; double* cov_second;                              // Behind::Covariance
   const double* mg_levels; int32_t n_levels; uint64_t* mass; uint64_t* qfinal;      // Behind::Marginals (lineage_ess too): ladders [B][D][L]
   // Behind::LagCovariance (lineage_ess too): anchor_rows [n_anchor] = anchors / stride; n_draw = n_paths: every final slot's trajectory,
@@ -1650,7 +1655,8 @@ struct ParticleRequest {
   // vgpa_particle_forecast: horizon steps behind the filter, or from `cloud` at index0; stride, n_draw, final_slots, slots_out as above
   int32_t horizon; const double* cloud; const double* cloud_logw; int32_t index0;
   double* fc_moments; double* members; double* state_end;
-  bool sums() const { return behind == Behind::Moments || behind == Behind::Covariance; }      // the replay with its weighted sums
+  bool sums() const { return behind == Behind::Moments || behind == Behind::Covariance || behind == Behind::BackwardMoments; }      // the replay with its weighted sums
+  bool smoothed() const { return behind == Behind::BackwardMoments; }                          // ... under the backward smoother's weights
   bool lag() const { return behind == Behind::LagCovariance; }                                 // every final slot's trajectory and their contraction
   bool table() const { return behind >= Behind::Trajectories; }                                // a slot table and the walk of its trajectories
 };
@@ -1697,8 +1703,8 @@ struct ParticleRun {
     if ((rc = sample_args(c, VGPA_PATHS_POSTERIOR, q.x, q.x0, q.n_paths, 1, q.seed, true, &a))) return rc;
     const size_t n = (size_t)q.n_paths, BnD = (size_t)B * n * D, Bn = (size_t)B * n, BM = (size_t)B * M1;
     keep_anc = q.ancestors || q.behind != Behind::None;      // (every pass behind the filter reads the ancestors)
-    keep_clouds = q.clouds || q.behind == Behind::Backward || q.behind == Behind::Conditional;      // (their walk reads the clouds on the device)
-    keep_lw = q.behind == Behind::Backward; pinned = q.behind == Behind::Conditional;
+    keep_clouds = q.clouds || q.behind == Behind::Backward || q.smoothed() || q.behind == Behind::Conditional;      // (their pass reads the clouds on the device)
+    keep_lw = q.behind == Behind::Backward || q.smoothed(); pinned = q.behind == Behind::Conditional;
     segment = pinned ? Walk::Conditional : q.rows == Carry::Events ? Walk::SegmentEvents : q.rows == Carry::Stats ? Walk::SegmentStats : Walk::Segment;
     const bool covariance = q.behind == Behind::Covariance, carried = q.rows != Carry::None;
     auto ints = [](size_t count) { return (count + 1) / 2; };      // int32 entries in a buffer of doubles
@@ -1710,6 +1716,8 @@ struct ParticleRun {
     if (q.table() && ((rc = buf(vgpa_ctx::PF_SLOTS, ints(n_table))) || (rc = grow(c, &c->d_sp_out, &c->sp_out_n, n_traj)))) return rc;
     if (q.sums() && ((rc = buf(vgpa_ctx::PF_WTAB, (size_t)B * rows * n)) || (rc = buf(vgpa_ctx::PF_LESS, (size_t)B * rows)) ||
                       (rc = buf(vgpa_ctx::PF_PART, (size_t)B * n_blocks * mom_len)) || (rc = buf(vgpa_ctx::PF_MOM, (size_t)B * mom_len)))) return rc;
+    if (q.smoothed() && ((rc = buf(vgpa_ctx::PF_SMX, BnD)) || (rc = buf(vgpa_ctx::PF_SMR, 2 * Bn + (size_t)B * kMaxSmallD)) ||
+                         (rc = buf(vgpa_ctx::PF_SMP, (size_t)B * rows * smooth_column_blocks(q.n_paths))))) return rc;
     if (covariance && (rc = buf(vgpa_ctx::PF_COV, (size_t)B * n_keep * D * ((size_t)D + 1)))) return rc;
     if (q.behind == Behind::Marginals &&
         ((rc = buf(vgpa_ctx::PF_WTAB, (size_t)B * rows * n)) || (rc = buf(vgpa_ctx::PF_LESS, (size_t)B * rows)) || (rc = buf(vgpa_ctx::PF_QTAB, (size_t)B * rows * n)) || (rc = buf(vgpa_ctx::PF_QFIN, Bn)) ||
@@ -1800,8 +1808,10 @@ struct ParticleRun {
     int rc;
     double* wtab = c->d_pf[vgpa_ctx::PF_WTAB];
     double* less = c->d_pf[vgpa_ctx::PF_LESS];
+    if (q.smoothed()) HIP_TRY(c, hipMemsetAsync(wtab, 0, (size_t)B * rows * q.n_paths * sizeof(double), c->stream));      // (the rows beyond a problem's own count + 1)
     HIP_TRY(c, hipMemsetAsync(less, 0, (size_t)B * rows * sizeof(double), c->stream));
     LAUNCH_TRY(c, "descendant weights launch", launch_pf_descend(f, rows, wtab, less, c->stream));
+    if (q.smoothed() && (rc = backward_weights(wtab, less))) return rc;
     // the replay: the start and the segments once more; the start's log-weights go to the prefix sums' buffer, which nothing reads any more
     cur = c->d_pf[vgpa_ctx::PF_XA]; other = c->d_pf[vgpa_ctx::PF_XB];
     PfArgs g = f;
@@ -1825,6 +1835,31 @@ struct ParticleRun {
     if (q.lineage_ess)      // (the device's rows are M1 + 1 = M + 1, but for a context of capacity 0)
       for (int p = 0; p < (rows == M + 1 ? 1 : B); p++)
         if ((rc = download(c, q.lineage_ess + (size_t)p * (M + 1), less + (size_t)p * rows, rows == M + 1 ? (size_t)B * rows : (size_t)M + 1))) return rc;
+    return VGPA_OK;
+  }
+
+  // The smoothing weights of the marginal backward smoother in the descendant weights' place: row c and its ESS are
+  // launch_pf_descend's, which moments() has just run; the union of the batch's cuts is walked backwards, one launch_smooth_cut per cut --
+  // every problem looks up its own observation there and copies or recurses by its own flag --, then the ESS of the rows below c.  The
+  // table leaves here where it is asked for; the replay behind it is moments()' own.
+  int backward_weights(double* wtab, double* less) {
+    const int B = c->B, M = c->M;
+    const size_t Bn = (size_t)B * q.n_paths;
+    int rc;
+    SmoothArgs sm{};
+    sm.rows = rows; sm.xt = c->d_pf[vgpa_ctx::PF_SMX]; sm.rmax = c->d_pf[vgpa_ctx::PF_SMR]; sm.rsum = sm.rmax + Bn; sm.centre = sm.rsum + Bn;
+    sm.wtab = wtab; sm.part = c->d_pf[vgpa_ctx::PF_SMP]; sm.less = less;
+    PfArgs g = f;
+    for (int k = c->Np - 1; k >= 0; k--) {
+      if (!is_obs[k]) continue;
+      g.k = k;
+      LAUNCH_TRY(c, "backward smoothing launch", launch_smooth_cut(g, a, sm, c->stream));
+    }
+    LAUNCH_TRY(c, "smoothing ESS launch", launch_smooth_ess(g, sm, c->stream));
+    if (q.smooth_weights)      // (the device's rows are M1 + 1 = M + 1, but for a context of capacity 0)
+      for (int p = 0; p < (rows == M + 1 ? 1 : B); p++)
+        if ((rc = download(c, q.smooth_weights + (size_t)p * (M + 1) * q.n_paths, wtab + (size_t)p * rows * q.n_paths,
+                           (rows == M + 1 ? (size_t)B * rows : (size_t)M + 1) * q.n_paths))) return rc;
     return VGPA_OK;
   }
 
@@ -2043,12 +2078,15 @@ static int particle_run(vgpa_ctx* c, const ParticleRequest& q) {
   if (!c->full) return fail(c, VGPA_ERR_STATE, "context was created without m0/s0/observations (ODE-only)");
   const int D = c->D, B = c->B, M = c->M, Np = c->Np;
   const int kept = (Np - 1) / stride + 1;
-  const bool moments = q.behind == Behind::Moments, covariance = q.behind == Behind::Covariance, carried = q.rows != Carry::None;
+  const bool moments = q.behind == Behind::Moments || q.smoothed(), covariance = q.behind == Behind::Covariance, carried = q.rows != Carry::None;
   if (D <= kMaxSmallD) {      // the launch limits and the sizes of the results, before any work
     if (q.sums() && n_paths > sample_max_paths(D))      // (the replay)
       return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing %s are built for at most %d particles per problem at D = %d (n_paths = %d)",
                   moments ? "moments" : "covariances", sample_max_paths(D), D, n_paths);
     if (moments && (rc = check_sums(c, kept, "smoothing", "grid indices"))) return rc;
+    if (q.smoothed() && !smooth_grid_fits(D, n_paths))      // (the launches of one cut: the successors, the row pass)
+      return fail(c, VGPA_ERR_UNSUPPORTED, "backward smoothing is built for at most %d particles per problem at D = %d (n_paths = %d)",
+                  std::min(kMaxGridY * kSmoothRowBlock, kMaxGridY * 256 / D), D, n_paths);
     // (the sum of the covariance replay's packed partial sums and the unpacking launch)
     if (covariance && !(pf_flat_grid_fits((size_t)B * kept * D * D) && pf_flat_grid_fits((size_t)B * kept * sample_cov_len(D))))
       return fail(c, VGPA_ERR_UNSUPPORTED, "the smoothing covariances are built for at most 2^39 - 256 entries (batch %d, %d kept grid indices, D = %d): use a larger stride",
@@ -2077,6 +2115,7 @@ static int particle_run(vgpa_ctx* c, const ParticleRequest& q) {
       return fail(c, VGPA_ERR_UNSUPPORTED, "backward simulation is built for at most %d trajectories per problem (n_draw = %d)", kMaxGridY * kBackwardBlock, n_draw);
     if (q.table() && (rc = check_stored(c, n_draw, kept, "smoothing trajectories", "trajectories", "grid indices"))) return rc;
   }
+  c->pf_hlw_paths = 0;      // (the histories of the call before are about to be overwritten)
   ParticleRun r{c, q};
   if ((rc = r.setup()) || (rc = r.filter()) || (q.sums() && (rc = r.moments())) || (q.behind == Behind::Marginals && (rc = r.marginals())) ||
       (q.lag() && (rc = r.lag_covariance())) || (q.table() && (rc = r.trajectories()))) return rc;
@@ -2103,6 +2142,27 @@ static int particle_run(vgpa_ctx* c, const ParticleRequest& q) {
     for (int p = 0; p < B; p++)
       if (r.count[p] > 0 && (rc = download(c, q.clouds + (size_t)p * M * n * D, r.f.h_clouds + (size_t)p * M * n * D, (size_t)r.count[p] * n * D))) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (r.keep_lw) c->pf_hlw_paths = n_paths;
+  return VGPA_OK;
+}
+
+// The log-weights the resamplings of the last backward call replaced, as its kernels read them (see vgpa_hip.h)
+int vgpa_particle_replaced_logw(vgpa_ctx* c, int32_t n_paths, double* hlw) {
+  if (!c) return VGPA_ERR_ARG;
+  if (!hlw) return fail(c, VGPA_ERR_ARG, "null argument");
+  if (c->pf_hlw_paths == 0 || c->pf_hlw_paths != n_paths)
+    return fail(c, VGPA_ERR_STATE, "the last particle call kept no replaced log-weights of %d particles: call vgpa_particle_backward_paths or "
+                "vgpa_particle_backward_moments first", n_paths);
+  const size_t B = (size_t)c->B, M = (size_t)c->M, n = (size_t)n_paths;
+  if (M == 0) return VGPA_OK;
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  std::vector<int32_t> flags(B * M);
+  int rc;
+  if ((rc = download(c, hlw, c->d_pf[vgpa_ctx::PF_HLW], B * M * n))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(flags.data(), c->d_pf[vgpa_ctx::PF_FLAG], B * M * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (size_t e = 0; e < B * M; e++)      // (the device writes the rows of the resampled observations alone)
+    if (!flags[e]) std::fill(hlw + e * n, hlw + (e + 1) * n, std::numeric_limits<double>::quiet_NaN());
   return VGPA_OK;
 }
 
@@ -2149,6 +2209,17 @@ int vgpa_particle_moments(vgpa_ctx* c, const double* x, const double* x0, int32_
   if (!moments) return fail(c, VGPA_ERR_ARG, "null argument");
   ParticleRequest q{x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled};
   q.stride = stride; q.behind = Behind::Moments; q.moments = moments; q.lineage_ess = lineage_ess;
+  return particle_run(c, q);
+}
+
+// The smoothing moments on the grid under the marginal backward smoother's weights (see vgpa_hip.h)
+int vgpa_particle_backward_moments(vgpa_ctx* c, const double* x, const double* x0, int32_t n_paths, int32_t stride, uint64_t seed, double ess_fraction,
+                                   const double* prior_mu, const double* prior_tau, double* logw, double* state, double* moments,
+                                   double* smoothing_ess, double* weights, double* ess, int32_t* resampled) {
+  if (!c) return VGPA_ERR_ARG;
+  if (!moments) return fail(c, VGPA_ERR_ARG, "null argument");
+  ParticleRequest q{x, x0, n_paths, seed, ess_fraction, prior_mu, prior_tau, logw, state, ess, resampled};
+  q.stride = stride; q.behind = Behind::BackwardMoments; q.moments = moments; q.lineage_ess = smoothing_ess; q.smooth_weights = weights;
   return particle_run(c, q);
 }
 

@@ -454,6 +454,28 @@ hipError_t launch_path_cross_moments(const PathMomentArgs& g, hipStream_t st);  
 // grid.x: the kept rows (D <= kMaxLaneD: the entries of one anchor's block, 256 per workgroup), grid.y: the anchors, grid.z: the problems
 bool path_moments_grid_fits(int D, int batch, int n_keep, int n_anchor);
 
+// The marginal backward smoother (particle_smooth.hip): the smoothing weights of vgpa_particle_backward_moments in place of
+// launch_pf_descend's rows c-1 .. 0.  f: the histories h_flag, h_anc, h_clouds, h_lw with M, n_paths, seed, the observation rows and k, the
+// grid index of the cut; a: of the filter's arguments the model, theta, A, b, the diagonal R and dt, as launch_pf_backward reads them
+struct SmoothArgs {
+  int rows;                 // rows per problem of wtab, part and less (> every problem's observation count)
+  double* xt;               // [B][n_paths][D] work space: the successors of the cut
+  double* rmax;             // [B][n_paths] work space: max_i b_{s,i} ...
+  double* rsum;             // ... and sum_i exp(b_{s,i} - max) of every successor s
+  double* centre;           // [B][kMaxSmallD] work space: the mean of the cut's cloud (D >= 5: the point the matrix-core scores are centred on)
+  double* wtab;             // [B][rows][n_paths]: row c (and less[c]) is launch_pf_descend's
+  double* part;             // [B][rows][smooth_column_blocks(n_paths)] the column workgroups' sums of W^2
+  double* less;             // [B][rows] 1 / sum_i (W^j_i)^2
+};
+constexpr int kSmoothRowBlock = 16, kSmoothColBlock = 64;      // successors per workgroup of the row pass, candidates per workgroup of the column pass
+// One cut at grid index f.k, behind the cuts above it: every problem with an observation j there gets row j of wtab from row j + 1 -- a
+// copy where its cloud was carried on, else x~ (k_ps_successors), the rows' (max, sum) (k_ps_rows) and W^j = W^{j+1} P (k_ps_columns).
+// launch_smooth_ess, behind the last cut: less[j] for j < c from the partial sums, in block order (less[j + 1] at a carried cut)
+hipError_t launch_smooth_cut(const PfArgs& f, const SampleArgs& a, const SmoothArgs& sm, hipStream_t st);
+hipError_t launch_smooth_ess(const PfArgs& f, const SmoothArgs& sm, hipStream_t st);
+int smooth_column_blocks(int n_paths);
+bool smooth_grid_fits(int D, int n_paths);      // grid.y: the successors 256 / D and 16 per workgroup, the candidates 64 per workgroup
+
 // launchers (each returns hipGetLastError()) -----------------------------------------------------
 hipError_t launch_ode_generic(int method, bool fwd, const OdeArgs& a, hipStream_t st);
 hipError_t launch_ode_small(int method, bool fwd, const OdeArgs& a, hipStream_t st);     // D <= kMaxLaneD

@@ -70,7 +70,7 @@ model whatever the proposal (A_t, b_t) and for any number of particles >= 2: the
 """
 import numpy as np
 
-__all__ = ["ParticleFilterResult", "PathStatistics", "PathEvents", "SmoothingMoments", "SmoothingCovariance", "SmoothingLagCovariance", "SmoothingMarginals", "gaussian_ladder", "SmoothingPaths", "Forecast", "GibbsChain", "descendant_weights",
+__all__ = ["ParticleFilterResult", "PathStatistics", "PathEvents", "SmoothingMoments", "BackwardSmoothingMoments", "SmoothingCovariance", "SmoothingLagCovariance", "SmoothingMarginals", "gaussian_ladder", "SmoothingPaths", "Forecast", "GibbsChain", "descendant_weights",
            "path_rows", "theta_conditional", "theta_draw"]
 
 
@@ -383,6 +383,36 @@ class SmoothingMoments(_GenealogySums):
     @property
     def std(self):
         return np.sqrt(np.maximum(self.var, 0.0))
+
+
+class BackwardSmoothingMoments(_WalkRecord, _KeptGrid):
+    """One problem's record of vgpa_particle_backward_moments: SmoothingMoments' sums under the weights of the marginal
+    backward smoother.  log_w (n,): the final unnormalised log-weights; moments (n_keep, 2, D): sum_i W_i x_i(k) and sum_i W_i x_i(k)^2 at the
+    grid indices k = 0, stride, 2 stride, ... < n_pts; obs_t: the problem's own observation indices; smoothing_ess (M_p + 1,): 1 / sum W^2 of
+    every stretch; weights (M_p + 1, n): W^j_i, every row summing to 1, or None; ess, resampled over the problem's observations.  A stretch's
+    weights come from all n particles of the cloud behind it, so early stretches do not rest on the one lineage the genealogy leaves there
+    -- where the clouds overlap.  Where the particles of a cloud lie many transition widths apart (high D, few observations) the table is
+    the genealogy's and so is every number here.  single_dim: a 1-D model, the last axis of mean / second / var / std is dropped."""
+
+    def __init__(self, log_w, moments, stride, n_pts, obs_t, smoothing_ess, weights=None, ess=(), resampled=(), single_dim=False) -> None:
+        self._take_weights(log_w)
+        n_keep = self._take_grid(stride, n_pts)
+        self.moments = np.asarray(moments, dtype=float)
+        if self.moments.ndim != 3 or self.moments.shape[:2] != (n_keep, 2):
+            raise ValueError(" BackwardSmoothingMoments: moments must be (n_keep, 2, D).")
+        self.obs_t = np.asarray(obs_t, dtype=np.int64).ravel()
+        self.smoothing_ess = np.asarray(smoothing_ess, dtype=float).ravel()
+        self.weights = None if weights is None else np.asarray(weights, dtype=float)
+        fits = self.weights is None or self.weights.shape == (self.obs_t.size + 1, self.log_w.size)
+        self._take_decisions(ess, resampled, "obs_t, smoothing_ess, weights, ess and resampled", self.smoothing_ess.size != self.obs_t.size + 1 or not fits)
+        self.single_dim = bool(single_dim)
+
+    _shape = SmoothingMoments._shape
+    mean, second, var, std = SmoothingMoments.mean, SmoothingMoments.second, SmoothingMoments.var, SmoothingMoments.std
+
+    def smoothing_ess_on_grid(self):
+        """smoothing_ess of the stretch each kept grid index lies in: index k belongs to stretch #{observations before k}"""
+        return self.smoothing_ess[self._stretch_on_grid()]
 
 
 class SmoothingCovariance(_GenealogySums):

@@ -274,6 +274,23 @@ class VarGP(object):
         return self._particle_call("particle_moments", lambda res, k: self._moments_record(res, k, stride), n_paths, seed, stride=stride,
                                    ess_fraction=ess_fraction, x=x, x0=x0)
 
+    def _backward_moments_record(self, res, k, stride, obs_t=None):
+        """One problem's BackwardSmoothingMoments from row k of Context.particle_backward_moments' dict, cut to its own observations obs_t"""
+        from .particles import BackwardSmoothingMoments
+        t = np.asarray(self._inputs()["obs_t"] if obs_t is None else obs_t).ravel()
+        return BackwardSmoothingMoments(res["log_w"][k], res["moments"][k], stride, self.dim_n, t, res["smoothing_ess"][k, :t.size + 1],
+                                        res["weights"][k, :t.size + 1], res["ess"][k, :t.size], res["resampled"][k, :t.size], self.model.single_dim)
+
+    def backward_moments(self, n_paths, seed, stride=1, ess_fraction=0.5, x=None, x0=None):
+        """particle_moments with the weights of the marginal backward smoother: a particles.BackwardSmoothingMoments (with batch > 1 a list,
+        one per problem) -- mean, second, var, std on the grid, smoothing_ess per stretch and the weights themselves.  At every observation
+        where the cloud was resampled the weights of the stretch before it come from all n_paths particles of the stored cloud (filter
+        weight times model transition density, normalised per successor), the expectation of backward_paths' draw: early stretches keep a
+        variance where the genealogy's has collapsed to zero -- on clouds that overlap (the 1-D and 3-D models with many observations).
+        Where the particles lie many transition widths apart the result is particle_moments'."""
+        return self._particle_call("particle_backward_moments", lambda res, k: self._backward_moments_record(res, k, stride), n_paths, seed,
+                                   stride=stride, ess_fraction=ess_fraction, x=x, x0=x0)
+
     def _covariance_record(self, res, k, stride, obs_t=None):
         """One problem's SmoothingCovariance from row k of Context.particle_covariance's dict, cut to its own observations obs_t"""
         from .particles import SmoothingCovariance
