@@ -3,9 +3,8 @@ Backward-simulation smoothing trajectories (vgpa_particle_backward_paths; forwar
 observations): the numpy restatement, its bit equalities, the gap condition of the GPU tests, an exact anchor on a linear chain, and the
 host-side surface.
 
-history_numpy          the filter of test_particle_paths_cpu.particle_paths_numpy, operation for operation, without the carried paths and
-                       with hlw (M, n): every slot's log-weight at the problem's observation j, that observation's term included, before the
-                       resampling decision.
+history_numpy          the walk of particle_ref.FilterWalk with hlw (M, n): every slot's log-weight at the problem's observation j, that
+                       observation's term included, before the resampling decision.
 backward_slots_numpy   the table as vgpa_hip.h states it: row c the final slots; row j = row j + 1 where the cloud was carried on, else the
                        Gumbel-max draw among all n slots.  Returns, per draw, the gap between the two largest scores b + g.
 rewalk_backward_numpy  the trajectories: rewalk_numpy with the reload of the state at every completed observation.
@@ -26,14 +25,14 @@ import pytest
 import vgpa_amd as va
 from vgpa_amd import _lib
 from vgpa_amd.particles import SmoothingPaths
-from vgpa_amd.weights import init_term
 from conftest import ROOT
+from particle_ref import FilterWalk
 from test_gpu_edge_cases import make_problem
 from test_particle_filter_cpu import FRACTIONS, MARGIN, PLACEMENTS, SEED, SEED_BATCH, batch_case, case, placement_case
 from test_particle_moments_cpu import rts_marginals
 from test_particle_paths_cpu import DRAWN, particle_paths_numpy, pick_slots, rewalk_numpy, trace_slots
-from test_path_weights_cpu import FIXTURES, _sigma_diag, _split, obs_model
-from test_sample_paths_cpu import model_drift, normals, philox4x32_10, unit_open
+from test_path_weights_cpu import FIXTURES, _sigma_diag, _split
+from test_sample_paths_cpu import em_noise, em_step, model_drift, normals, philox4x32_10, start_cloud, unit_open
 
 GAP = 1e-8
 # the cases of the GPU tests: D = 1, 1, 3, 12, 17, 40 with a drawn start; D = 64 (NT = 64 without a padding row), a quiet case (resampled and
@@ -47,63 +46,13 @@ BIG = ("ou_euler", 4096, 4096, 0.5, 436)      # the one large run: the seed of t
 
 
 def history_numpy(problem, x, x0, n, seed, ess_fraction, index=0):
-    """One problem's filter with counter word `index`.  Returns a dict: lw (n,), state (n, D), ess (M,), resampled (M,) int,
-    ancestors (M, n) (the identity where the cloud was carried on), clouds (M, n, D), hlw (M, n), obs_t, margins (of the resamplings, as
-    particle_paths_numpy has them)."""
-    d, n_pts, dt = int(problem.dim_d), int(problem.n_pts), float(problem.dt)
-    sigma = _sigma_diag(problem)
-    isg, fac = 1.0 / sigma.diagonal(), np.linalg.cholesky(sigma * dt)
-    lin_a, off_b = _split(problem, x)
-    theta = np.asarray(problem.theta, dtype=float)
-    obs_t, obs_y, q, const = obs_model(problem)
-    at = {int(t): j for j, t in enumerate(obs_t)}
-    slots = np.arange(n)
-    if x0 is None:
-        l0 = np.linalg.cholesky(np.reshape(np.asarray(problem.s0, dtype=float), (d, d)))
-        state = np.reshape(np.asarray(problem.m0, dtype=float), (1, d)) + normals(seed, 0, slots, index, d) @ l0.T
-        init = init_term(state, problem.mu0, problem.tau0, problem.m0, problem.s0)
-    else:
-        state = np.tile(np.reshape(np.asarray(x0, dtype=float), (1, d)), (n, 1))
-        init = np.zeros(n)
-    m = obs_t.size
-    out = dict(ess=np.zeros(m), resampled=np.zeros(m, dtype=np.int64), ancestors=np.full((m, n), -1, dtype=np.int64),
-               clouds=np.full((m, n, d), np.nan), hlw=np.full((m, n), np.nan), margins=[])
-    lw = init - const
-    key = (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
-
-    def observe(k, state, lw):
-        if k not in at:
-            return state, lw
-        j = at[k]
-        r = obs_y[j][None, :] - state
-        lw = lw + (-0.5 * np.einsum("pi,ij,pj->p", r, q, r))
-        top = lw.max()
-        w = np.exp(lw - top)
-        cum = np.cumsum(w)
-        total = cum[-1]
-        ess = total * total / np.sum(w * w)
-        out["ess"][j], out["clouds"][j], out["ancestors"][j], out["hlw"][j] = ess, state, slots, lw
-        if ess < ess_fraction * n and k < n_pts - 1:
-            rr = philox4x32_10((k, 0, index, 0xFFFFFFFF), key)
-            u = (float(unit_open(rr[0], rr[1])) + slots) / n * total
-            pos = np.searchsorted(cum, u, side="right")
-            near = np.minimum(np.abs(u - cum[np.minimum(pos, n - 1)]), np.where(pos > 0, np.abs(u - cum[np.maximum(pos - 1, 0)]), np.inf))
-            out["margins"].append(float(near.min() / total))
-            anc = np.minimum(pos, n - 1)
-            out["resampled"][j], out["ancestors"][j] = 1, anc
-            state, lw = state[anc], np.full(n, top + np.log(total) - np.log(n))
-        return state, lw
-
-    state, lw = observe(0, state, lw)
-    for k in range(1, n_pts):
-        g = -(state @ lin_a[k - 1].T) + off_b[k - 1]
-        dd = g - model_drift(problem.model, theta, state)
-        eta = normals(seed, k, slots, index, d) @ fac.T
-        lw = lw + (-np.sum(dd * isg * eta, axis=1) - 0.5 * dt * np.sum(dd * isg * dd, axis=1))
-        state = (state + dt * g) + eta
-        state, lw = observe(k, state, lw)
-    out.update(lw=lw, state=state, obs_t=np.asarray(obs_t, dtype=np.int64))
-    return out
+    """One problem's filter with counter word `index`.  Returns FilterWalk.record's dict with hlw (M, n)."""
+    walk = FilterWalk(problem, x, x0, n, seed, ess_fraction, index)
+    hlw = np.full((walk.obs_t.size, n), np.nan)
+    for event, j in walk:
+        if event == "cut":
+            hlw[j] = walk.lw
+    return walk.record(hlw=hlw)
 
 
 def gumbels(seed, k, m, index, n):
@@ -167,29 +116,22 @@ def backward_slots_numpy(problem, x, seed, hist, final, index=0, drift=model_dri
 def rewalk_backward_numpy(problem, x, x0, seed, table, hist, index=0):
     """(K, Np, D): rewalk_numpy's walk -- the start with the counter word table[0], the step to k with table[j(k)] -- in which the state is
     replaced, behind every completed observation j and after that point is stored, by clouds[j][ancestors[j][table[j + 1]]]"""
-    d, n_pts, dt = int(problem.dim_d), int(problem.n_pts), float(problem.dt)
+    n_pts, dt = int(problem.n_pts), float(problem.dt)
     fac = np.linalg.cholesky(_sigma_diag(problem) * dt)
     lin_a, off_b = _split(problem, x)
     obs_t = hist["obs_t"]
     at = {int(t): j for j, t in enumerate(obs_t)}
     table = np.asarray(table, dtype=np.int64)
     assert table.shape[0] == obs_t.size + 1
-    if x0 is None:
-        l0 = np.linalg.cholesky(np.reshape(np.asarray(problem.s0, dtype=float), (d, d)))
-        state = np.reshape(np.asarray(problem.m0, dtype=float), (1, d)) + normals(seed, 0, table[0], index, d) @ l0.T
-    else:
-        state = np.tile(np.reshape(np.asarray(x0, dtype=float), (1, d)), (table.shape[1], 1))
-    out = np.empty((table.shape[1], n_pts, d))
-    out[:, 0] = state
-    if 0 in at:
-        state = hist["clouds"][0][hist["ancestors"][0][table[1]]]
-    for k in range(1, n_pts):
-        j = int(np.searchsorted(obs_t, k, side="left"))
-        g = -(state @ lin_a[k - 1].T) + off_b[k - 1]
-        state = (state + dt * g) + normals(seed, k, table[j], index, d) @ fac.T
+    state = start_cloud(problem, x0, seed, table[0], index)
+    out = np.empty((table.shape[1], n_pts, int(problem.dim_d)))
+    for k in range(n_pts):
+        if k > 0:
+            j = int(np.searchsorted(obs_t, k, side="left"))
+            state = em_step(state, dt, -(state @ lin_a[k - 1].T) + off_b[k - 1], em_noise(seed, k, table[j], index, fac))
         out[:, k] = state
         if k in at:
-            state = hist["clouds"][j][hist["ancestors"][j][table[j + 1]]]
+            state = hist["clouds"][at[k]][hist["ancestors"][at[k]][table[at[k] + 1]]]
     return out
 
 

@@ -8,7 +8,7 @@ backward_step              one cut: W^j from W^{j+1} and the histories of test_p
                            the hooks of backward_slots_numpy (drift, divisor, target) and one more for the hlw term
 backward_weights_numpy     the table (M + 1, n): row M the normalised final weights, row j < M a copy or backward_step; its ESS
 backward_weights_longdouble  the twin
-replay_numpy               x_i(k) of every slot and grid index: history_numpy's walk with the stored ancestors in place of the decisions
+replay_numpy               x_i(k) of every slot and grid index: particle_ref.visited_states through the stored ancestors
 smoothing_moments          M1, M2 and sum W |x| on the grid from a table and the replay
 
 The bound, per cut (one recursion step, as in test_particle_rounding_cpu): with W^{j+1} given, the row under test against the longdouble
@@ -39,6 +39,7 @@ import vgpa_amd as va
 from vgpa_amd import _lib
 from vgpa_amd.particles import BackwardSmoothingMoments, _weights_of, descendant_weights
 from conftest import ROOT
+from particle_ref import visited_states
 from test_gpu_edge_cases import make_problem
 from test_particle_backward_cpu import BCASES, TIGHT, TIGHT_RUNS, history, history_numpy, tight_case
 from test_particle_filter_cpu import FRACTIONS, PLACEMENTS, SEED, SEED_BATCH, batch_case, case, placement_case
@@ -46,7 +47,7 @@ from test_particle_moments_cpu import particle_moments_numpy, rts_marginals
 from test_particle_paths_cpu import DRAWN
 from test_particle_rounding_cpu import FACTOR, UNIT, errors, ratio, within
 from test_path_weights_cpu import FIXTURES, _sigma_diag, _split
-from test_sample_paths_cpu import model_drift, normals
+from test_sample_paths_cpu import model_drift
 
 LD = np.longdouble
 F64 = np.float64
@@ -149,28 +150,10 @@ def step_errors(problem, x, seed, hist, j, w_next, got, index=0):
 
 
 def replay_numpy(problem, x, x0, seed, hist, index=0):
-    """(Np, n, D): the state of slot i as the walk arrives at k, before a resampling decision at k -- history_numpy's walk, operation for
-    operation, with the stored ancestors (the identity where the cloud was carried on) in place of the decisions"""
-    d, n_pts, dt = int(problem.dim_d), int(problem.n_pts), float(problem.dt)
-    fac = np.linalg.cholesky(_sigma_diag(problem) * dt)
-    lin_a, off_b = _split(problem, x)
-    at = {int(t): j for j, t in enumerate(hist["obs_t"])}
-    n = int(np.asarray(hist["lw"]).size)
-    slots = np.arange(n)
-    if x0 is None:
-        l0 = np.linalg.cholesky(np.reshape(np.asarray(problem.s0, dtype=float), (d, d)))
-        state = np.reshape(np.asarray(problem.m0, dtype=float), (1, d)) + normals(seed, 0, slots, index, d) @ l0.T
-    else:
-        state = np.tile(np.reshape(np.asarray(x0, dtype=float), (1, d)), (n, 1))
-    out = np.empty((n_pts, n, d))
-    for k in range(n_pts):
-        if k:
-            g = -(state @ lin_a[k - 1].T) + off_b[k - 1]
-            state = (state + dt * g) + normals(seed, k, slots, index, d) @ fac.T
-        out[k] = state
-        if k in at:
-            state = state[np.asarray(hist["ancestors"][at[k]], dtype=np.int64)]
-    return out
+    """(Np, n, D): the state of slot i as the walk arrives at k, before a resampling decision at k -- history_numpy's walk with the stored
+    ancestors (the identity where the cloud was carried on) in place of the decisions"""
+    gathers = {int(t): np.asarray(hist["ancestors"][j], dtype=np.int64) for j, t in enumerate(hist["obs_t"])}
+    return visited_states(problem, x, x0, seed, int(np.asarray(hist["lw"]).size), gathers, index)[0]
 
 
 def smoothing_moments(table, states, obs_t, stride=1):

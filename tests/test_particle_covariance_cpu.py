@@ -3,9 +3,8 @@ The smoothing mean and full second-moment matrices on the grid under the particl
 restatement, its checks against the restatement of the moments it extends, against the backward recursion of
 vgpa_amd.particles.descendant_weights and against stored paths, the record SmoothingCovariance and the host-side surface.
 
-The restatement is the reference of tests/test_particle_covariance.py.  It is test_particle_moments_cpu.particle_moments_numpy, operation
-for operation (every slot carries its whole path; a resampling copies the paths through the same `anc` as the states), which returns in
-addition, with W = w / sum w of the final weights,
+The restatement is the reference of tests/test_particle_covariance.py.  It is test_particle_moments_cpu.particle_moments_numpy (the same
+walk, test_particle_moments_cpu.lineage_paths: every slot carries its whole path through the resamplings), which returns in addition, with W = w / sum w of the final weights,
     second[k][a][b] = sum_i W_i path_i(k)[a] path_i(k)[b],   a2[k][a][b] = sum_i W_i |path_i(k)[a]| |path_i(k)[b]|   (the scale of its rounding).
 The lower triangle is summed, (W x_a) x_b in slot order, and mirrored.
 """
@@ -20,12 +19,11 @@ import pytest
 import vgpa_amd as va
 from vgpa_amd import _lib
 from vgpa_amd.particles import SmoothingCovariance, descendant_weights
-from vgpa_amd.weights import init_term
 from conftest import ROOT
 from test_particle_filter_cpu import SEED, case
-from test_particle_moments_cpu import particle_moments_numpy
-from test_path_weights_cpu import FIXTURES, _sigma_diag, _split, obs_model, path_weights_numpy
-from test_sample_paths_cpu import model_drift, normals, philox4x32_10, sample_paths_numpy, unit_open
+from test_particle_moments_cpu import final_weights, lineage_moments, lineage_paths, particle_moments_numpy
+from test_path_weights_cpu import FIXTURES, path_weights_numpy
+from test_sample_paths_cpu import sample_paths_numpy
 
 WALK_TAGS = ["ou_euler", "l63_euler_p", "l96d12_euler_p", "l96d17_rk4_p", "quiet_l96d12"]      # (those of test_particle_moments_cpu)
 
@@ -39,70 +37,9 @@ def weighted_second(w, pts):
 def particle_covariance_numpy(problem, x, x0, n, seed, ess_fraction, index=0):
     """One problem's filter with counter word `index`, every slot carrying its path.  Returns particle_moments_numpy's dict and second / a2
     (Np, D, D)."""
-    d, n_pts, dt = int(problem.dim_d), int(problem.n_pts), float(problem.dt)
-    sigma = _sigma_diag(problem)
-    isg, fac = 1.0 / sigma.diagonal(), np.linalg.cholesky(sigma * dt)
-    lin_a, off_b = _split(problem, x)
-    theta = np.asarray(problem.theta, dtype=float)
-    obs_t, obs_y, q, const = obs_model(problem)
-    at = {int(t): j for j, t in enumerate(obs_t)}
-    slots = np.arange(n)
-    if x0 is None:
-        l0 = np.linalg.cholesky(np.reshape(np.asarray(problem.s0, dtype=float), (d, d)))
-        state = np.reshape(np.asarray(problem.m0, dtype=float), (1, d)) + normals(seed, 0, slots, index, d) @ l0.T
-        init = init_term(state, problem.mu0, problem.tau0, problem.m0, problem.s0)
-    else:
-        state = np.tile(np.reshape(np.asarray(x0, dtype=float), (1, d)), (n, 1))
-        init = np.zeros(n)
-    m = obs_t.size
-    out = dict(ess=np.zeros(m), resampled=np.zeros(m, dtype=np.int64), ancestors=np.full((m, n), -1, dtype=np.int64),
-               clouds=np.full((m, n, d), np.nan), margins=[])
-    lw = init - const
-    paths = np.zeros((n, n_pts, d))
-    key = (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
-
-    def observe(k, state, lw, paths):
-        if k not in at:
-            return state, lw, paths
-        j = at[k]
-        r = obs_y[j][None, :] - state
-        lw = lw + (-0.5 * np.einsum("pi,ij,pj->p", r, q, r))
-        top = lw.max()
-        w = np.exp(lw - top)
-        cum = np.cumsum(w)
-        total = cum[-1]
-        ess = total * total / np.sum(w * w)
-        out["ess"][j], out["clouds"][j], out["ancestors"][j] = ess, state, slots
-        if ess < ess_fraction * n and k < n_pts - 1:
-            rr = philox4x32_10((k, 0, index, 0xFFFFFFFF), key)
-            u = (float(unit_open(rr[0], rr[1])) + slots) / n * total
-            pos = np.searchsorted(cum, u, side="right")
-            near = np.minimum(np.abs(u - cum[np.minimum(pos, n - 1)]), np.where(pos > 0, np.abs(u - cum[np.maximum(pos - 1, 0)]), np.inf))
-            out["margins"].append(float(near.min() / total))
-            anc = np.minimum(pos, n - 1)
-            out["resampled"][j], out["ancestors"][j] = 1, anc
-            state, lw, paths = state[anc], np.full(n, top + np.log(total) - np.log(n)), paths[anc]
-        return state, lw, paths
-
-    paths[:, 0] = state
-    state, lw, paths = observe(0, state, lw, paths)
-    for k in range(1, n_pts):
-        g = -(state @ lin_a[k - 1].T) + off_b[k - 1]
-        dd = g - model_drift(problem.model, theta, state)
-        eta = normals(seed, k, slots, index, d) @ fac.T
-        inc = -np.sum(dd * isg * eta, axis=1) - 0.5 * dt * np.sum(dd * isg * dd, axis=1)
-        lw = lw + inc
-        state = (state + dt * g) + eta
-        paths[:, k] = state
-        state, lw, paths = observe(k, state, lw, paths)
-    w = np.exp(lw - lw.max())
-    w = w / w.sum()
-    out.update(lw=lw, state=state, m1=np.einsum("i,ikd->kd", w, paths), m2=np.einsum("i,ikd->kd", w, paths * paths),
-               a1=np.einsum("i,ikd->kd", w, np.abs(paths)), obs_t=np.asarray(obs_t, dtype=np.int64),
-               second=weighted_second(w, paths), a2=weighted_second(w, np.abs(paths)))
-    table = descendant_weights(lw, out["ancestors"], out["resampled"]) if m else w[None, :]
-    out["lineage_ess"] = 1.0 / np.sum(table * table, axis=1)
-    return out
+    walk, paths = lineage_paths(problem, x, x0, n, seed, ess_fraction, index)
+    w = final_weights(walk.lw)
+    return walk.record(second=weighted_second(w, paths), a2=weighted_second(w, np.abs(paths)), **lineage_moments(walk, paths))
 
 
 @functools.lru_cache(maxsize=None)

@@ -4,7 +4,7 @@ against the lineage paths, the level recipe and the conditions on the cases of t
 restatement, the longdouble restatement of the two reductions, the record PathEvents and the host-side surface.
 
 The restatement rides on test_particle_filter_cpu.particle_filter_numpy: walk_numpy takes that filter's ancestors and decisions, walks the
-states once more with the same operations -- (x + dt g) + eta, gathered through the stored ancestors where the filter resampled -- and keeps
+states once more with the same operations (particle_ref.visited_states: gathered through the stored ancestors where the filter resampled) and keeps
 every visited state x_i(k), the state of slot i as the walk arrives at k, before a resampling decision at k.  The walk is asserted bit-equal
 to the filter's (its clouds at every observation, its final state).  event_rows then carries the row (X, T, N) of
     g_j(x) = s_j (x_j - c_j)   (one subtraction, an exact change of sign; in the event iff g > 0)
@@ -32,10 +32,10 @@ import vgpa_amd as va
 from vgpa_amd import _lib
 from vgpa_amd.particles import PathEvents
 from conftest import ROOT
+from particle_ref import visited_states
 from test_particle_filter_cpu import (FRACTIONS, PLACEMENTS, QUIET, SEED, SEED_BATCH, _given, batch_case, case, particle_filter_numpy, placement_case)
 from test_particle_paths_cpu import rewalk_numpy, trace_slots
-from test_path_weights_cpu import TAGS, _sigma_diag, _split, obs_model
-from test_sample_paths_cpu import normals
+from test_path_weights_cpu import TAGS
 
 EVENT_MARGIN = 1e-7
 SIZES = (1, 17, 65, 300)
@@ -47,30 +47,14 @@ def walk_numpy(problem, x, x0, n, seed, ess_fraction, index=0):
     """The filter of particle_filter_numpy and, from its ancestors, every visited state.  Returns the filter's dict plus visited (Np, n, D),
     gathers: {k: ancestors} for the grid indices k at which the cloud was resampled, n_pts."""
     flt = dict(particle_filter_numpy(problem, x, x0, n, seed, ess_fraction, index=index))
-    d, n_pts, dt = int(problem.dim_d), int(problem.n_pts), float(problem.dt)
-    fac = np.linalg.cholesky(_sigma_diag(problem) * dt)
-    lin_a, off_b = _split(problem, x)
-    obs_t = np.asarray(obs_model(problem)[0], dtype=np.int64)
+    obs_t = flt["obs_t"]
     gathers = {int(t): flt["ancestors"][j] for j, t in enumerate(obs_t) if flt["resampled"][j]}
-    slots = np.arange(n)
-    if x0 is None:
-        l0 = np.linalg.cholesky(np.reshape(np.asarray(problem.s0, dtype=float), (d, d)))
-        state = np.reshape(np.asarray(problem.m0, dtype=float), (1, d)) + normals(seed, 0, slots, index, d) @ l0.T
-    else:
-        state = np.tile(np.reshape(np.asarray(x0, dtype=float), (1, d)), (n, 1))
-    visited = np.empty((n_pts, n, d))
-    for k in range(n_pts):
-        if k > 0:
-            g = -(state @ lin_a[k - 1].T) + off_b[k - 1]
-            state = (state + dt * g) + normals(seed, k, slots, index, d) @ fac.T
-        visited[k] = state
-        if k in gathers:
-            state = state[gathers[k]]
+    visited, state = visited_states(problem, x, x0, seed, n, gathers, index)
     # the walk is the filter's, bit for bit: its clouds are the visited states at the observations, its final particles the last ones
     for j, t in enumerate(obs_t):
         assert np.array_equal(visited[int(t)], flt["clouds"][j]), ("cloud", j)
     assert np.array_equal(state, flt["state"])
-    flt.update(visited=visited, gathers=gathers, n_pts=n_pts, obs_t=obs_t)
+    flt.update(visited=visited, gathers=gathers, n_pts=int(problem.n_pts))
     return flt
 
 

@@ -2,20 +2,11 @@
 The guided particle filter (vgpa_particle_filter): the numpy restatement, its checks against the importance weights it generalises and against
 the exact evidence of a linear chain, the record ParticleFilterResult, the host-side surface, and the margin condition of the GPU tests.
 
-The restatement is the reference of tests/test_particle_filter.py.  It walks the recursion of test_path_weights_cpu.path_weights_numpy (the
-same normals, model drift, observation model and initial term) with n particles per problem, takes the observation terms into the
-log-weights lw where they occur, and behind every observation forms
-    w_i = exp(lw_i - max lw),  cum = cumsum(w) in slot order,  S = cum[n - 1],  ESS = S^2 / sum w_i^2
-and resamples iff ESS < ess_fraction n and k < Np - 1:
-    U = unit_open(r0, r1) of Philox counter (k, 0, problem, 0xffffffff),  u_i = (U + i) / n S,  anc_i = min(#{m: cum_m <= u_i}, n - 1),
-    x_i <- x_{anc_i},  lw_i <- max lw + log S - log n.
-(S is taken as the last prefix sum, which is sum_i w_i in slot order, so that every threshold lies below cum[n - 1] as it does in exact
-arithmetic.)  For each resampling it also returns the margin min_{i,m} |u_i - cum_m| / S: device and host weights agree to about 1e-13, so
-above a margin of 1e-7 the device's ancestors must be identical to the restatement's -- the condition test_margin_condition asserts for
-every (case, n, seed) the GPU tests use.
+The restatement is the reference of tests/test_particle_filter.py.  It is the walk of particle_ref.FilterWalk (the recursion, the resampling
+rule and the margin are described there) and carries, per slot,
 
-scale: per slot, sum_k |increment_k| of the path term as in path_weights_numpy; a resampling sets every slot's scale to the largest (the
-common log-weight is made of all of them).
+scale: sum_k |increment_k| of the path term as in path_weights_numpy; a resampling sets every slot's scale to the largest (the common
+log-weight is made of all of them).
 """
 import dataclasses
 import functools
@@ -29,12 +20,11 @@ import pytest
 import vgpa_amd as va
 from vgpa_amd import _lib
 from vgpa_amd.particles import ParticleFilterResult
-from vgpa_amd.weights import init_term
 from conftest import ROOT, load_golden
 from oracle import vgpa_oracle as vo
+from particle_ref import FilterWalk
 from test_gpu_edge_cases import make_problem
-from test_path_weights_cpu import FIXTURES, TAGS, _sigma_diag, _split, obs_model, path_weights_numpy
-from test_sample_paths_cpu import model_drift, normals, philox4x32_10, unit_open
+from test_path_weights_cpu import FIXTURES, TAGS, path_weights_numpy
 
 SEED = 7                         # (seed 5 leaves l96d5 and two quiet cases a margin of 2.5e-8 .. 6.6e-8 at n = 300: another seed, the same bound)
 SEED_BATCH = 9                   # ... and the batch cases' (seed 7: 3.1e-8)
@@ -49,63 +39,15 @@ BATCH_TIMES = [np.array([0, 6, 13, 27, 40]), np.array([3, 4, 30, 39]), np.array(
 
 
 def particle_filter_numpy(problem, x, x0, n, seed, ess_fraction, index=0):
-    """One problem's filter with counter word `index`.  Returns a dict: lw (n,), state (n, D), ess (M,), resampled (M,) int, ancestors
-    (M, n), clouds (M, n, D), margins (one per resampling), scale (n,), init (n,)."""
-    d, n_pts, dt = int(problem.dim_d), int(problem.n_pts), float(problem.dt)
-    sigma = _sigma_diag(problem)
-    isg, fac = 1.0 / sigma.diagonal(), np.linalg.cholesky(sigma * dt)
-    lin_a, off_b = _split(problem, x)
-    theta = np.asarray(problem.theta, dtype=float)
-    obs_t, obs_y, q, const = obs_model(problem)
-    at = {int(t): j for j, t in enumerate(obs_t)}
-    slots = np.arange(n)
-    if x0 is None:
-        l0 = np.linalg.cholesky(np.reshape(np.asarray(problem.s0, dtype=float), (d, d)))
-        state = np.reshape(np.asarray(problem.m0, dtype=float), (1, d)) + normals(seed, 0, slots, index, d) @ l0.T
-        init = init_term(state, problem.mu0, problem.tau0, problem.m0, problem.s0)
-    else:
-        state = np.tile(np.reshape(np.asarray(x0, dtype=float), (1, d)), (n, 1))
-        init = np.zeros(n)
-    m = obs_t.size
-    out = dict(ess=np.zeros(m), resampled=np.zeros(m, dtype=np.int64), ancestors=np.full((m, n), -1, dtype=np.int64),
-               clouds=np.full((m, n, d), np.nan), margins=[], init=init)
-    lw, scale = init - const, np.zeros(n)
-    key = (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
-
-    def observe(k, state, lw, scale):
-        if k not in at:
-            return state, lw, scale
-        j = at[k]
-        r = obs_y[j][None, :] - state
-        lw = lw + (-0.5 * np.einsum("pi,ij,pj->p", r, q, r))
-        top = lw.max()
-        w = np.exp(lw - top)
-        cum = np.cumsum(w)
-        total = cum[-1]
-        ess = total * total / np.sum(w * w)
-        out["ess"][j], out["clouds"][j], out["ancestors"][j] = ess, state, slots
-        if ess < ess_fraction * n and k < n_pts - 1:
-            rr = philox4x32_10((k, 0, index, 0xFFFFFFFF), key)
-            u = (float(unit_open(rr[0], rr[1])) + slots) / n * total
-            pos = np.searchsorted(cum, u, side="right")
-            near = np.minimum(np.abs(u - cum[np.minimum(pos, n - 1)]), np.where(pos > 0, np.abs(u - cum[np.maximum(pos - 1, 0)]), np.inf))
-            out["margins"].append(float(near.min() / total))
-            anc = np.minimum(pos, n - 1)
-            out["resampled"][j], out["ancestors"][j] = 1, anc
-            state, lw, scale = state[anc], np.full(n, top + np.log(total) - np.log(n)), np.full(n, scale.max())
-        return state, lw, scale
-
-    state, lw, scale = observe(0, state, lw, scale)
-    for k in range(1, n_pts):
-        g = -(state @ lin_a[k - 1].T) + off_b[k - 1]
-        dd = g - model_drift(problem.model, theta, state)
-        eta = normals(seed, k, slots, index, d) @ fac.T
-        inc = -np.sum(dd * isg * eta, axis=1) - 0.5 * dt * np.sum(dd * isg * dd, axis=1)
-        lw, scale = lw + inc, scale + np.abs(inc)
-        state = (state + dt * g) + eta
-        state, lw, scale = observe(k, state, lw, scale)
-    out.update(lw=lw, state=state, scale=scale)
-    return out
+    """One problem's filter with counter word `index`.  Returns FilterWalk.record's dict with scale (n,) and init (n,)."""
+    walk = FilterWalk(problem, x, x0, n, seed, ess_fraction, index)
+    scale = np.zeros(n)
+    for event, _ in walk:
+        if event == "step":
+            scale = scale + np.abs(walk.inc)
+        elif event == "gather":
+            scale = np.full(n, scale.max())
+    return walk.record(scale=scale, init=walk.init)
 
 
 def log_mean_exp(lw):

@@ -3,7 +3,7 @@ Particle Gibbs with ancestor sampling (vgpa_particle_conditional, VarGP.particle
 conditional particle filter, its bit equalities, the margin conditions of the GPU tests, the theta draw against least squares, the
 host-side surface and a statistical anchor on a linear chain.
 
-conditional_filter_numpy   test_particle_backward_cpu.history_numpy, operation for operation, with slot 0 pinned to `ref`: it starts at
+conditional_filter_numpy   test_particle_backward_cpu.history_numpy, from the same pieces (particle_ref), with slot 0 pinned to `ref`: it starts at
                            ref[0], takes the implied increment (ref[k] - ref[k-1]) - dt g in the place of R xi, and is set to ref[k]; the
                            resampling is multinomial for the slots >= 1 and ancestor sampling (Gumbel-max) for slot 0, whose state stays.
 conditional_trajectory_numpy   the final slot (pick_slots, one trajectory), trace_slots through the kept ancestors, rewalk_backward_numpy on
@@ -25,14 +25,14 @@ import pytest
 import vgpa_amd as va
 from vgpa_amd import _lib
 from vgpa_amd.particles import GibbsChain, path_rows, theta_conditional, theta_draw
-from vgpa_amd.weights import init_term
 from conftest import ROOT
+from particle_ref import reset_weights, weight_sums
 from test_particle_filter_cpu import MARGIN, SEED, SEED_BATCH, batch_case, case
 from test_particle_moments_cpu import rts_marginals
 from test_particle_paths_cpu import pick_slots, rewalk_numpy, trace_slots
 from test_particle_backward_cpu import argmax_with_gap, history_numpy, rewalk_backward_numpy, tight_case
-from test_path_weights_cpu import _sigma_diag, _split, obs_model
-from test_sample_paths_cpu import model_drift, normals, philox4x32_10, unit_open
+from test_path_weights_cpu import _sigma_diag, _split, observation_term, obs_model, path_increment, start_term
+from test_sample_paths_cpu import em_noise, em_step, model_drift, philox4x32_10, start_cloud, unit_open
 
 GAP = 1e-8            # log units, between the two largest scores of an ancestor draw
 BOUNDARY = 1e-9       # of S, between a multinomial threshold and the nearest prefix sum
@@ -113,31 +113,26 @@ def conditional_filter_numpy(problem, x, x0, ref, n, seed, ess_fraction, index=0
     at = {int(t): j for j, t in enumerate(obs_t)}
     slots = np.arange(n)
     ref = np.asarray(ref, dtype=float).reshape(n_pts, d)
-    if x0 is None:
-        l0 = np.linalg.cholesky(np.reshape(np.asarray(problem.s0, dtype=float), (d, d)))
-        state = np.reshape(np.asarray(problem.m0, dtype=float), (1, d)) + normals(seed, 0, slots, index, d) @ l0.T
-        state[0] = ref[0]
-        init = init_term(state, problem.mu0, problem.tau0, problem.m0, problem.s0)
-    else:
-        state = np.tile(np.reshape(np.asarray(x0, dtype=float), (1, d)), (n, 1))
-        state[0] = ref[0]
-        init = np.zeros(n)
+    state = start_cloud(problem, x0, seed, slots, index)
+    state[0] = ref[0]
     m = obs_t.size
     out = dict(ess=np.zeros(m), resampled=np.zeros(m, dtype=np.int64), ancestors=np.full((m, n), -1, dtype=np.int64),
                clouds=np.full((m, n, d), np.nan), hlw=np.full((m, n), np.nan), margins=[], gaps=[])
-    lw = init - const
-
-    def observe(k, state, lw):
+    lw = start_term(problem, state, x0) - const
+    for k in range(n_pts):
+        if k > 0:
+            g = -(state @ lin_a[k - 1].T) + off_b[k - 1]
+            dd = g - model_drift(problem.model, theta, state)
+            eta = em_noise(seed, k, slots, index, fac)
+            eta[0] = (ref[k] - state[0]) - (dt if eta_dt is None else eta_dt) * g[0]
+            lw = lw + path_increment(dd, eta, isg, dt)
+            state = em_step(state, dt, g, eta)
+            state[0] = ref[k]
         if k not in at:
-            return state, lw
+            continue
         j = at[k]
-        r = obs_y[j][None, :] - state
-        lw = lw + (-0.5 * np.einsum("pi,ij,pj->p", r, q, r))
-        top = lw.max()
-        w = np.exp(lw - top)
-        cum = np.cumsum(w)
-        total = cum[-1]
-        ess = total * total / np.sum(w * w)
+        lw = lw + observation_term(obs_y[j], state, q)
+        top, _, cum, total, ess = weight_sums(lw)
         out["ess"][j], out["clouds"][j], out["ancestors"][j], out["hlw"][j] = ess, state, slots, lw
         if ess < ess_fraction * n and k < n_pts - 1:
             anc, near = bisect_numpy(cum, uniforms_multinomial(seed, k, n, index) * total)
@@ -147,19 +142,7 @@ def conditional_filter_numpy(problem, x, x0, ref, n, seed, ess_fraction, index=0
             hist = anc.copy()
             hist[0], anc[0] = win, 0          # (the pinned slot keeps its state; its ancestor goes into the history alone)
             out["resampled"][j], out["ancestors"][j] = 1, hist
-            state, lw = state[anc], np.full(n, top + np.log(total) - np.log(n))
-        return state, lw
-
-    state, lw = observe(0, state, lw)
-    for k in range(1, n_pts):
-        g = -(state @ lin_a[k - 1].T) + off_b[k - 1]
-        dd = g - model_drift(problem.model, theta, state)
-        eta = normals(seed, k, slots, index, d) @ fac.T
-        eta[0] = (ref[k] - state[0]) - (dt if eta_dt is None else eta_dt) * g[0]
-        lw = lw + (-np.sum(dd * isg * eta, axis=1) - 0.5 * dt * np.sum(dd * isg * dd, axis=1))
-        state = (state + dt * g) + eta
-        state[0] = ref[k]
-        state, lw = observe(k, state, lw)
+            state, lw = state[anc], reset_weights(top, total, n)
     out.update(lw=lw, state=state, obs_t=np.asarray(obs_t, dtype=np.int64))
     return out
 

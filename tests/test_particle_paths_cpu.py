@@ -4,9 +4,9 @@ filter and the moments they ride on, the pick of the final slots, the margin con
 the record SmoothingPaths and the host-side surface.
 
 Two restatements, which the device must both agree with:
-  particle_paths_numpy   the forward algorithm -- the walk of test_particle_moments_cpu.particle_moments_numpy, operation for operation, in
-                         which every slot carries its whole path and, beside it, the slot its lineage sat in during every stretch; a
-                         resampling copies both through the same `anc` as the states.  What the trajectories ARE.
+  particle_paths_numpy   the forward algorithm -- the walk of particle_ref.FilterWalk, in which every slot carries its whole path and,
+                         beside it, the slot its lineage sat in during every stretch; a resampling copies both through the same `anc`
+                         as the states.  What the trajectories ARE.
   trace_slots + rewalk_numpy   what the device does: the final slots traced backwards through the stored ancestors, then every trajectory
                          walked alone from the counters of its slots, nothing carried and nothing gathered.
 test_trace_and_rewalk_is_the_forward_algorithm asserts that the two give the same bits, so the GPU tests may use the second (which costs K
@@ -27,13 +27,13 @@ import pytest
 import vgpa_amd as va
 from vgpa_amd import _lib
 from vgpa_amd.particles import SmoothingPaths
-from vgpa_amd.weights import init_term
 from conftest import ROOT
+from particle_ref import FilterWalk
 from test_particle_filter_cpu import FRACTIONS, MARGIN, QUIET, SEED, case, particle_filter_numpy
 from test_particle_filter_cpu import reference as filter_reference
 from test_particle_moments_cpu import particle_moments_numpy, rts_marginals
 from test_path_weights_cpu import TAGS, _sigma_diag, _split, obs_model
-from test_sample_paths_cpu import model_drift, normals, philox4x32_10, unit_open
+from test_sample_paths_cpu import em_noise, em_step, philox4x32_10, start_cloud, unit_open
 
 CASES = [(t, s) for t in TAGS for s in ("given", "drawn")] + [(t, "given") for t in QUIET]
 # (particles, trajectories) of the GPU tests in drawn mode: one particle; more trajectories than particles and a second workgroup above
@@ -42,70 +42,21 @@ DRAWN = [(1, 17), (17, 65), (65, 17), (300, 1), (300, 65)]
 
 
 def particle_paths_numpy(problem, x, x0, n, seed, ess_fraction, index=0):
-    """One problem's filter with counter word `index`, every slot carrying its path and its lineage's slots.  Returns a dict: lw (n,),
-    state (n, D), ess (M,), resampled (M,) int, ancestors (M, n), clouds (M, n, D), margins, obs_t, paths (n, Np, D): the path of the
-    lineage that ends in each final slot, table (M + 1, n): the slot that lineage sat in during every stretch (row M: the final slot)."""
-    d, n_pts, dt = int(problem.dim_d), int(problem.n_pts), float(problem.dt)
-    sigma = _sigma_diag(problem)
-    isg, fac = 1.0 / sigma.diagonal(), np.linalg.cholesky(sigma * dt)
-    lin_a, off_b = _split(problem, x)
-    theta = np.asarray(problem.theta, dtype=float)
-    obs_t, obs_y, q, const = obs_model(problem)
-    at = {int(t): j for j, t in enumerate(obs_t)}
-    slots = np.arange(n)
-    if x0 is None:
-        l0 = np.linalg.cholesky(np.reshape(np.asarray(problem.s0, dtype=float), (d, d)))
-        state = np.reshape(np.asarray(problem.m0, dtype=float), (1, d)) + normals(seed, 0, slots, index, d) @ l0.T
-        init = init_term(state, problem.mu0, problem.tau0, problem.m0, problem.s0)
-    else:
-        state = np.tile(np.reshape(np.asarray(x0, dtype=float), (1, d)), (n, 1))
-        init = np.zeros(n)
-    m = obs_t.size
-    out = dict(ess=np.zeros(m), resampled=np.zeros(m, dtype=np.int64), ancestors=np.full((m, n), -1, dtype=np.int64),
-               clouds=np.full((m, n, d), np.nan), margins=[])
-    lw = init - const
-    paths = np.zeros((n, n_pts, d))
-    table = np.full((m + 1, n), -1, dtype=np.int64)
-    key = (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
-
-    def observe(k, state, lw, paths, table):
-        if k not in at:
-            return state, lw, paths, table
-        j = at[k]
-        table[j] = slots                    # stretch j ends here: the slot the lineage is in
-        r = obs_y[j][None, :] - state
-        lw = lw + (-0.5 * np.einsum("pi,ij,pj->p", r, q, r))
-        top = lw.max()
-        w = np.exp(lw - top)
-        cum = np.cumsum(w)
-        total = cum[-1]
-        ess = total * total / np.sum(w * w)
-        out["ess"][j], out["clouds"][j], out["ancestors"][j] = ess, state, slots
-        if ess < ess_fraction * n and k < n_pts - 1:
-            rr = philox4x32_10((k, 0, index, 0xFFFFFFFF), key)
-            u = (float(unit_open(rr[0], rr[1])) + slots) / n * total
-            pos = np.searchsorted(cum, u, side="right")
-            near = np.minimum(np.abs(u - cum[np.minimum(pos, n - 1)]), np.where(pos > 0, np.abs(u - cum[np.maximum(pos - 1, 0)]), np.inf))
-            out["margins"].append(float(near.min() / total))
-            anc = np.minimum(pos, n - 1)
-            out["resampled"][j], out["ancestors"][j] = 1, anc
-            state, lw, paths, table = state[anc], np.full(n, top + np.log(total) - np.log(n)), paths[anc], table[:, anc]
-        return state, lw, paths, table
-
-    paths[:, 0] = state
-    state, lw, paths, table = observe(0, state, lw, paths, table)
-    for k in range(1, n_pts):
-        g = -(state @ lin_a[k - 1].T) + off_b[k - 1]
-        dd = g - model_drift(problem.model, theta, state)
-        eta = normals(seed, k, slots, index, d) @ fac.T
-        inc = -np.sum(dd * isg * eta, axis=1) - 0.5 * dt * np.sum(dd * isg * dd, axis=1)
-        lw = lw + inc
-        state = (state + dt * g) + eta
-        paths[:, k] = state
-        state, lw, paths, table = observe(k, state, lw, paths, table)
-    table[m] = slots
-    out.update(lw=lw, state=state, paths=paths, table=table, obs_t=np.asarray(obs_t, dtype=np.int64))
-    return out
+    """One problem's filter with counter word `index`, every slot carrying its path and its lineage's slots.  Returns FilterWalk.record's
+    dict with paths (n, Np, D): the path of the lineage that ends in each final slot, and table (M + 1, n): the slot that lineage sat in
+    during every stretch (row M: the final slot)."""
+    walk = FilterWalk(problem, x, x0, n, seed, ess_fraction, index)
+    paths = np.zeros((n, walk.n_pts, walk.d))
+    table = np.full((walk.obs_t.size + 1, n), -1, dtype=np.int64)
+    for event, i in walk:
+        if event in ("start", "step"):
+            paths[:, i] = walk.state
+        elif event == "cut":
+            table[i] = np.arange(n)         # stretch i ends here: the slot the lineage is in
+        elif event == "gather":
+            paths, table = paths[walk.anc], table[:, walk.anc]
+    table[-1] = np.arange(n)
+    return walk.record(paths=paths, table=table)
 
 
 def trace_slots(final, ancestors, resampled):
@@ -123,23 +74,18 @@ def trace_slots(final, ancestors, resampled):
 def rewalk_numpy(problem, x, x0, seed, table, index=0):
     """(K, Np, D): every trajectory walked alone (step 3 of vgpa_hip.h): the start with the counter word table[0], the step to k with
     table[j(k)], j(k) = #{observations before k}.  The unweighted recursion of sample_paths_numpy, its operations in the filter's order."""
-    d, n_pts, dt = int(problem.dim_d), int(problem.n_pts), float(problem.dt)
+    n_pts, dt = int(problem.n_pts), float(problem.dt)
     fac = np.linalg.cholesky(_sigma_diag(problem) * dt)
     lin_a, off_b = _split(problem, x)
     obs_t = np.asarray(obs_model(problem)[0], dtype=np.int64)
     table = np.asarray(table, dtype=np.int64)
     assert table.shape[0] == obs_t.size + 1
-    if x0 is None:
-        l0 = np.linalg.cholesky(np.reshape(np.asarray(problem.s0, dtype=float), (d, d)))
-        state = np.reshape(np.asarray(problem.m0, dtype=float), (1, d)) + normals(seed, 0, table[0], index, d) @ l0.T
-    else:
-        state = np.tile(np.reshape(np.asarray(x0, dtype=float), (1, d)), (table.shape[1], 1))
-    out = np.empty((table.shape[1], n_pts, d))
+    state = start_cloud(problem, x0, seed, table[0], index)
+    out = np.empty((table.shape[1], n_pts, int(problem.dim_d)))
     out[:, 0] = state
     for k in range(1, n_pts):
         j = int(np.searchsorted(obs_t, k, side="left"))
-        g = -(state @ lin_a[k - 1].T) + off_b[k - 1]
-        state = (state + dt * g) + normals(seed, k, table[j], index, d) @ fac.T
+        state = em_step(state, dt, -(state @ lin_a[k - 1].T) + off_b[k - 1], em_noise(seed, k, table[j], index, fac))
         out[:, k] = state
     return out
 

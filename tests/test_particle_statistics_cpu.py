@@ -2,8 +2,8 @@
 The path statistics of the particle filter's lineages (vgpa_particle_statistics): the numpy restatement, its checks against the filter it
 rides on, against stored paths and against the exact smoother of a linear chain, the record PathStatistics and the host-side surface.
 
-The restatement is the reference of tests/test_particle_statistics.py.  It is the walk of test_particle_filter_cpu.particle_filter_numpy,
-operation for operation, with a row (Q, G, H) per slot,
+The restatement is the reference of tests/test_particle_statistics.py.  It is the walk of particle_ref.FilterWalk with a row (Q, G, H) per
+slot,
     Q_j += r_j^2 / dt,  G_j += phi_j r_j,  H_j += dt phi_j^2,  r = dt (g - f_theta(x_{k-1})) + eta_k,  phi_j = df_j / dtheta_a(j) at x_{k-1},
 and, per entry, the scale sum_k |increment_k|.  A resampling copies rows and scales through the same `anc` as the states.
 """
@@ -18,11 +18,11 @@ import pytest
 import vgpa_amd as va
 from vgpa_amd import _lib
 from vgpa_amd.particles import PathStatistics
-from vgpa_amd.weights import init_term
 from conftest import ROOT
+from particle_ref import FilterWalk
 from test_particle_filter_cpu import SEED, case, particle_filter_numpy
-from test_path_weights_cpu import _sigma_diag, _split, obs_model
-from test_sample_paths_cpu import model_drift, normals, philox4x32_10, sample_paths_numpy, unit_open
+from test_path_weights_cpu import _sigma_diag
+from test_sample_paths_cpu import model_drift, sample_paths_numpy
 
 THETA_CASES = ["ou_euler", "dw_euler_p", "l63_euler_p", "l96d12_euler_p"]
 
@@ -39,66 +39,19 @@ def model_phi(model, x):
 
 
 def particle_statistics_numpy(problem, x, x0, n, seed, ess_fraction, index=0):
-    """One problem's filter with counter word `index`, the rows carried along.  Returns a dict: lw (n,), state (n, D), ess (M,), resampled
-    (M,) int, margins, rows (n, 3, D), scale (n, 3, D)."""
-    d, n_pts, dt = int(problem.dim_d), int(problem.n_pts), float(problem.dt)
-    sigma = _sigma_diag(problem)
-    isg, fac = 1.0 / sigma.diagonal(), np.linalg.cholesky(sigma * dt)
-    lin_a, off_b = _split(problem, x)
-    theta = np.asarray(problem.theta, dtype=float)
-    obs_t, obs_y, q, const = obs_model(problem)
-    at = {int(t): j for j, t in enumerate(obs_t)}
-    slots = np.arange(n)
-    if x0 is None:
-        l0 = np.linalg.cholesky(np.reshape(np.asarray(problem.s0, dtype=float), (d, d)))
-        state = np.reshape(np.asarray(problem.m0, dtype=float), (1, d)) + normals(seed, 0, slots, index, d) @ l0.T
-        init = init_term(state, problem.mu0, problem.tau0, problem.m0, problem.s0)
-    else:
-        state = np.tile(np.reshape(np.asarray(x0, dtype=float), (1, d)), (n, 1))
-        init = np.zeros(n)
-    m = obs_t.size
-    out = dict(ess=np.zeros(m), resampled=np.zeros(m, dtype=np.int64), margins=[])
-    lw = init - const
-    rows, scale = np.zeros((n, 3, d)), np.zeros((n, 3, d))
-    key = (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
-
-    def observe(k, state, lw, rows, scale):
-        if k not in at:
-            return state, lw, rows, scale
-        j = at[k]
-        r = obs_y[j][None, :] - state
-        lw = lw + (-0.5 * np.einsum("pi,ij,pj->p", r, q, r))
-        top = lw.max()
-        w = np.exp(lw - top)
-        cum = np.cumsum(w)
-        total = cum[-1]
-        ess = total * total / np.sum(w * w)
-        out["ess"][j] = ess
-        if ess < ess_fraction * n and k < n_pts - 1:
-            rr = philox4x32_10((k, 0, index, 0xFFFFFFFF), key)
-            u = (float(unit_open(rr[0], rr[1])) + slots) / n * total
-            pos = np.searchsorted(cum, u, side="right")
-            near = np.minimum(np.abs(u - cum[np.minimum(pos, n - 1)]), np.where(pos > 0, np.abs(u - cum[np.maximum(pos - 1, 0)]), np.inf))
-            out["margins"].append(float(near.min() / total))
-            anc = np.minimum(pos, n - 1)
-            out["resampled"][j] = 1
-            state, lw, rows, scale = state[anc], np.full(n, top + np.log(total) - np.log(n)), rows[anc], scale[anc]
-        return state, lw, rows, scale
-
-    state, lw, rows, scale = observe(0, state, lw, rows, scale)
-    for k in range(1, n_pts):
-        g = -(state @ lin_a[k - 1].T) + off_b[k - 1]
-        dd = g - model_drift(problem.model, theta, state)
-        eta = normals(seed, k, slots, index, d) @ fac.T
-        inc = -np.sum(dd * isg * eta, axis=1) - 0.5 * dt * np.sum(dd * isg * dd, axis=1)
-        res, phi = dt * dd + eta, model_phi(problem.model, state)
-        step = np.stack((res * res / dt, phi * res, dt * (phi * phi)), axis=1)
-        rows, scale = rows + step, scale + np.abs(step)
-        lw = lw + inc
-        state = (state + dt * g) + eta
-        state, lw, rows, scale = observe(k, state, lw, rows, scale)
-    out.update(lw=lw, state=state, rows=rows, scale=scale)
-    return out
+    """One problem's filter with counter word `index`, the rows carried along.  Returns FilterWalk.record's dict with rows (n, 3, D) and
+    scale (n, 3, D)."""
+    walk = FilterWalk(problem, x, x0, n, seed, ess_fraction, index)
+    dt = walk.dt
+    rows, scale = np.zeros((n, 3, walk.d)), np.zeros((n, 3, walk.d))
+    for event, _ in walk:
+        if event == "step":
+            res, phi = dt * walk.dd + walk.eta, model_phi(problem.model, walk.prev)
+            step = np.stack((res * res / dt, phi * res, dt * (phi * phi)), axis=1)
+            rows, scale = rows + step, scale + np.abs(step)
+        elif event == "gather":
+            rows, scale = rows[walk.anc], scale[walk.anc]
+    return walk.record(rows=rows, scale=scale)
 
 
 @functools.lru_cache(maxsize=None)

@@ -21,7 +21,7 @@ from vgpa_amd import _lib
 from vgpa_amd.weights import PathWeights, gauss_logpdf, init_term
 from conftest import ROOT, load_golden
 from oracle import vgpa_oracle as vo
-from test_sample_paths_cpu import model_drift, normals, sample_paths_numpy
+from test_sample_paths_cpu import em_noise, em_step, model_drift, sample_paths_numpy, start_cloud
 
 FIXTURES = ["ou_euler", "dw_euler_p", "l63_euler_p", "l96d12_euler_p", "l96d17_rk4_p", "l96d40_rk4_p"]
 # the tags of the sampler tests: the fixtures, "l96d<D>" = make_problem("L96", D, 41, method="euler") on a bare context (D = 4: the widest
@@ -54,6 +54,24 @@ def obs_model(problem):
     return obs_t, obs_y, q, 0.5 * obs_t.size * (d * np.log(2.0 * np.pi) + np.linalg.slogdet(r)[1])
 
 
+def start_term(problem, state, x0):
+    """(n,): init of the module's docstring for the start `state` of start_cloud -- 0 for a given start"""
+    if x0 is not None:
+        return np.zeros(state.shape[0])
+    return init_term(state, problem.mu0, problem.tau0, problem.m0, problem.s0)
+
+
+def path_increment(dd, eta, isg, dt):
+    """(n,): one step's term of `path` for d = dd (n, D), eta (n, D) and the diagonal isg of Sigma^-1"""
+    return -np.sum(dd * isg * eta, axis=1) - 0.5 * dt * np.sum(dd * isg * dd, axis=1)
+
+
+def observation_term(y, state, q):
+    """(n,): one observation's term of `obs` (without the constant) for the states (n, D)"""
+    r = y[None, :] - state
+    return -0.5 * np.einsum("pi,ij,pj->p", r, q, r)
+
+
 def path_weights_numpy(problem, x, x0, n_paths, seed, index=0):
     """(init, path, obs, scale), each (n_paths,), of the paths sample_paths_numpy(problem, "posterior", x, x0, n_paths, 1, seed, index) draws"""
     d, n, dt = int(problem.dim_d), int(problem.n_pts), float(problem.dt)
@@ -64,29 +82,23 @@ def path_weights_numpy(problem, x, x0, n_paths, seed, index=0):
     obs_t, obs_y, q, const = obs_model(problem)
     at = {int(t): k for k, t in enumerate(obs_t)}
     paths = np.arange(n_paths)
-    if x0 is None:
-        l0 = np.linalg.cholesky(np.reshape(np.asarray(problem.s0, dtype=float), (d, d)))
-        state = np.reshape(np.asarray(problem.m0, dtype=float), (1, d)) + normals(seed, 0, paths, index, d) @ l0.T
-        init = init_term(state, problem.mu0, problem.tau0, problem.m0, problem.s0)
-    else:
-        state = np.tile(np.reshape(np.asarray(x0, dtype=float), (1, d)), (n_paths, 1))
-        init = np.zeros(n_paths)
+    state = start_cloud(problem, x0, seed, paths, index)
+    init = start_term(problem, state, x0)
     path, scale, obs = np.zeros(n_paths), np.zeros(n_paths), np.full(n_paths, -const)
 
     def observe(k):
         if k in at:
-            r = obs_y[at[k]][None, :] - state
-            obs[:] += -0.5 * np.einsum("pi,ij,pj->p", r, q, r)
+            obs[:] += observation_term(obs_y[at[k]], state, q)
 
     observe(0)
     for k in range(1, n):
         g = -(state @ lin_a[k - 1].T) + off_b[k - 1]
         dd = g - model_drift(problem.model, theta, state)
-        eta = normals(seed, k, paths, index, d) @ fac.T
-        inc = -np.sum(dd * isg * eta, axis=1) - 0.5 * dt * np.sum(dd * isg * dd, axis=1)
+        eta = em_noise(seed, k, paths, index, fac)
+        inc = path_increment(dd, eta, isg, dt)
         path += inc
         scale += np.abs(inc)
-        state = (state + dt * g) + eta
+        state = em_step(state, dt, g, eta)
         observe(k)
     return init, path, obs, scale
 

@@ -51,6 +51,26 @@ def normals(seed, k, path, problem, d):
     return z.reshape(z.shape[:-2] + (-1,))[..., :d]
 
 
+def start_cloud(problem, x0, seed, words, index=0):
+    """(len(words), D): the start of every walk -- m0 + chol(S0) xi_0 with the normals of grid index 0 and the counter words `words`, or
+    the given x0 once per word"""
+    d = int(problem.dim_d)
+    if x0 is not None:
+        return np.tile(np.reshape(np.asarray(x0, dtype=float), (1, d)), (len(words), 1))
+    l0 = np.linalg.cholesky(np.reshape(np.asarray(problem.s0, dtype=float), (d, d)))
+    return np.reshape(np.asarray(problem.m0, dtype=float), (1, d)) + normals(seed, 0, words, index, d) @ l0.T
+
+
+def em_noise(seed, k, words, index, fac):
+    """(len(words), D): eta_k = R xi_k of the step to grid index k, R = fac = chol(Sigma dt)"""
+    return normals(seed, k, words, index, fac.shape[0]) @ fac.T
+
+
+def em_step(state, dt, g, eta):
+    """the Euler-Maruyama step, in the order every walk of the tests (and the device) adds it up"""
+    return (state + dt * g) + eta
+
+
 def n_keep(n_pts, stride):
     return (n_pts - 1) // stride + 1
 
@@ -74,11 +94,7 @@ def sample_paths_numpy(problem, kind, x, x0, n_paths, stride, seed, index=0):
     sigma = np.reshape(np.asarray(problem.sigma, dtype=float), (d, d))
     fac = np.linalg.cholesky(sigma * dt)
     paths = np.arange(n_paths)
-    if x0 is None:
-        l0 = np.linalg.cholesky(np.reshape(np.asarray(problem.s0, dtype=float), (d, d)))
-        state = np.reshape(np.asarray(problem.m0, dtype=float), (1, d)) + normals(seed, 0, paths, index, d) @ l0.T
-    else:
-        state = np.tile(np.reshape(np.asarray(x0, dtype=float), (1, d)), (n_paths, 1))
+    state = start_cloud(problem, x0, seed, paths, index)
     if kind == "posterior":
         x = np.asarray(x, dtype=float)
         lin_a, off_b = x[:n * d * d].reshape(n, d, d), x[n * d * d:].reshape(n, d)
@@ -90,7 +106,7 @@ def sample_paths_numpy(problem, kind, x, x0, n_paths, stride, seed, index=0):
             drift = -(state @ lin_a[k - 1].T) + off_b[k - 1]
         else:
             drift = model_drift(problem.model, theta, state)
-        state = (state + dt * drift) + normals(seed, k, paths, index, d) @ fac.T
+        state = em_step(state, dt, drift, em_noise(seed, k, paths, index, fac))
         if k % stride == 0:
             out[:, k // stride] = state
     return out
